@@ -4,13 +4,18 @@ synthetic byte corpus of SURVEY.md 8(d) config 3, with the bound of each phase o
 the streaming phase (fused k_apply, whole iterations) and the dependent-trip floor of the sparse phase (k_scan_skip: one
 launch applies a BATCH of merges) -- and the reference's algorithm in pure Python on the host as the CPU baseline.
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 A "step" is ONE whole training job: words already resident in HBM (flat u8 bytes + u64 offsets) ->
 tile build + initial pair count -> `merges` merge iterations.  value = merges completed / wall time of the
 K timed steps (max over ranks).  N > 1: the same 1 GiB corpus is word-sharded over the ranks (strong scaling).
 Prints ONE JSON line on rank 0.
+
+A plain run sets up, warms up, times the K steps and prints the headline line (with `roofline`, which the timed steps
+measure themselves).  --full adds what takes runs of its own: `latency` (the device's latency probe), `dedup_layout`,
+`pretokenize`, `long_words` (--long-words N) and the CPU baselines.  --dump-outputs DIR writes the merges of the last
+timed step (left, right, merged token ids and their pair counts, as float64) to DIR/<name>.npy.
 """
 from __future__ import annotations
 
@@ -79,6 +84,18 @@ def cpu_baseline_c_port(ctx, pb, po, n_words, merges, budget_bytes, specials, ma
             "sample": f"first {int(off[-1])} bytes ({k} words, {info['unique_words']} unique): {len(mg)} merges in {dt:.1f} s (loop stopped after {max_seconds:.0f} s)"}
 
 
+def dump_outputs(out_dir: str, res: dict) -> None:
+    """What a caller of the timed path receives (Context.train: the merges' token ids and pair counts), one .npy per array."""
+    import numpy as np
+
+    d = Path(out_dir)
+    d.mkdir(parents=True, exist_ok=True)
+    for name in ("left", "right", "merged", "count"):
+        if name in res:  # (the word-sharded runner returns no counts)
+            np.save(d / f"{name}.npy", np.asarray(res[name]).astype(np.float64))
+    log(f"outputs of the last timed step: {', '.join(n for n in ('left', 'right', 'merged', 'count') if n in res)} -> {d}")
+
+
 def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -89,11 +106,17 @@ def main() -> None:
     ap.add_argument("--event-sample", type=int, default=0, help="time every Nth sparse-phase launch with HIP events too (0 = off: the phase is timed as a whole)")
     ap.add_argument("--event-sample-dense", type=int, default=2, help="... every Nth launch of the streaming phase (fused k_apply)")
     ap.add_argument("--cpu-sample-mib", type=int, default=64)
-    ap.add_argument("--long-words", type=int, default=0, help="auxiliary line: the job on 256 MiB of the corpus with N words of 64..300 bytes added (the long-word path), next to the same job without them")
+    ap.add_argument("--long-words", type=int, default=0, help="(with --full) auxiliary line: the job on 256 MiB of the corpus with N words of 64..300 bytes added (the long-word path), next to the same job without them")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-dedup-line", action="store_true")
     ap.add_argument("--no-pretok-line", action="store_true")
+    ap.add_argument("--full", action="store_true", help="also the lines that take runs of their own: latency probe, pooled layout, "
+                    "pre-tokeniser, long words, CPU baselines (off: set up, warm up, time the steps, print the headline line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the last timed step's merges (left, right, merged, count) "
+                    "as DIR/<name>.npy, float64")
     args = ap.parse_args()
+    if args.long_words and not args.full:
+        ap.error("--long-words adds a line of --full")
 
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -146,7 +169,7 @@ def main() -> None:
             ctx.set_vocab(base)
             ctx.load_words_ptr(pb, po, n_words, dedup=dedup)
             left, right, merged, count = ctx.train(args.merges, 1)
-            return {"n_merges": len(left), "stats": ctx.stats(), "left": left, "right": right, "merged": merged}
+            return {"n_merges": len(left), "stats": ctx.stats(), "left": left, "right": right, "merged": merged, "count": count}
 
     def barrier():
         torch.cuda.synchronize()
@@ -176,6 +199,8 @@ def main() -> None:
         t = torch.tensor([elapsed], device="cpu" if rehearsal else "cuda", dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, res)
 
     st = res["stats"]
     n_merges = res["n_merges"]
@@ -251,7 +276,7 @@ def main() -> None:
                         "tile from its first changed slot on -- in the first merges nearly every tile changes, so the algorithmic figure "
                         "(reads of live tokens only) cannot be met by any in-place rewrite; against the bytes the kernel has to move the launch "
                         "runs at the traffic_frac_of_peak given here"}
-    if st["sparse_merges"] and rank == 0:
+    if st["sparse_merges"] and rank == 0 and args.full:
         lat = gen.latency_probe()
         n_load, n_coh, n_atomic = 4, 4, 3
         floor = lat["launch_gap_us"] + n_load * lat["load_trip_us"] + n_coh * lat["coherent_trip_us"] + n_atomic * lat["atomic_trip_us"]
@@ -283,7 +308,7 @@ def main() -> None:
             tiles_read = st["scan_skip_tiles_read"] / max(1, st["scan_skip_launches"])
             out["latency"]["event_timed"] = {"launches": n_l, "avg_launch_us": round(1e3 * st["scan_ms_sampled"] / max(1, n_l), 2),
                                              "avg_fraction_of_tiles_read": round(tiles_read / max(1, st["n_tiles"]), 4)}
-    if rank == 0 and not args.no_dedup_line and world == 1:
+    if rank == 0 and args.full and not args.no_dedup_line and world == 1:
         t1 = time.perf_counter()
         rd = one_job(True, 0)
         torch.cuda.synchronize()
@@ -292,7 +317,7 @@ def main() -> None:
         out["dedup_layout"] = {"merges_per_sec": round(rd["n_merges"] / dt, 2), "seconds": round(dt, 3),
                                "unique_words": rd["stats"]["n_words"], "same_merges_as_flat": same,
                                "device_ms": {"dedup_load_count": round(rd["stats"]["load_ms"], 2), "merge_loop": round(rd["stats"]["train_ms"], 2)}}
-    if rank == 0 and not args.no_pretok_line and world == 1:
+    if rank == 0 and args.full and not args.no_pretok_line and world == 1:
         # the step before the path: GPT-2 pre-tokenisation of text resident in HBM.  Text = the config-2
         # style generator at this run's size (space + lower-case word, Zipf over 50k types), pre-tokens must equal its words.
         with _native.Context(local_rank) as pt:
@@ -325,7 +350,7 @@ def main() -> None:
                                   "offsets_equal_generator_words": same_offsets, "cpu_baseline": cpu_pt,
                                   "note": "yabpe_pretokenize (UTF-8 validation + GPT-2 split + special tokens -> word offsets in HBM), "
                                           "wall time incl. scratch allocation, best of 3; not part of `value`"}
-    if rank == 0 and args.long_words > 0 and world == 1:
+    if rank == 0 and args.full and args.long_words > 0 and world == 1:
         # the long-word path (words of more than 63 tokens live outside the tile stream): what it costs per merge, measured
         import numpy as np
 
@@ -345,7 +370,7 @@ def main() -> None:
                 res_lw[name] = {"merges": len(l_), "merge_loop_ms": round(s_["train_ms"], 2), "us_per_merge": round(1000.0 * s_["train_ms"] / max(1, len(l_)), 2),
                                 "long_words": s_["n_long_words"]}
         out["long_words"] = {"corpus": f"first {int(off[-1])} bytes of the corpus, + {args.long_words} words of 64..300 random letters", **res_lw}
-    if rank == 0 and not args.no_cpu_baseline and world == 1:  # (the CPU baseline is an N=1 item)
+    if rank == 0 and args.full and not args.no_cpu_baseline and world == 1:  # (the CPU baseline is an N=1 item)
         out["cpu_baseline"] = cpu_baseline(gen, pb, po, n_words, args.merges, args.cpu_sample_mib << 20, specials)
         out["cpu_baseline_c_port"] = cpu_baseline_c_port(gen, pb, po, n_words, args.merges, 32 << 20, specials)
     if runner is not None:
