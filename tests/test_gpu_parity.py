@@ -161,7 +161,7 @@ def test_many_tiles_retile_and_table_growth():
     for opts in ({"split": 1}, {"split": 0}, {"sig_rebuild_every": 3, "check_interval": 2}, {"rank_rides": 0}, {"cand_argmax": 0}, {"cand_min_count": 1, "check_interval": 3},
                  {"batch_max": 1}, {"batch_max": 2}, {"batch_max": 3, "check_interval": 5}, {"batch_max": 8, "check_interval": 1}, {"batch_max": 8, "split": 1, "check_interval": 3},
                  {"batch_max": 8, "cand_min_count": 1, "split": 1}, {"batch_max": 8, "cand_target": 64, "check_interval": 4}, {"batch_max": 8, "full_wpb": 16}, {"batch_max": 8, "full_wpb": 4, "agg_small": 0},
-                 {"fuse_select": 0}, {"cand_rebuild_every": 1}, {"cand_rebuild_every": 100000, "check_interval": 8}, {"full_skip_blocks": 2}, {"full_skip_blocks": 1}, {"sig_rebuild_pct": 0, "check_interval": 5},
+                 {"cand_rebuild_every": 1}, {"cand_rebuild_every": 100000, "check_interval": 8}, {"full_skip_blocks": 2}, {"full_skip_blocks": 1}, {"sig_rebuild_pct": 0, "check_interval": 5},
                  {"retile_pct": 95, "retile_min_tiles": 16}, {"split": 1, "retile_pct": 95, "retile_min_tiles": 16},
                  {"fused": 0}, {"fused": 0, "split": 1}, {"fused": 1, "check_interval": 3}, {"cand_target": 64, "check_interval": 4}, {"table_load_pct": 70, "table_grow_x": 2},
                  {"full_wpb": 4}, {"full_wpb": 8}, {"full_wpb": 16}, {"full_wpb": 16, "full_skip_blocks": 3}, {"full_wpb": 8, "check_interval": 5},

@@ -1,7 +1,7 @@
 // batch_sim.cpp -- design study (CPU, not part of the product): how many consecutive merges of sequential BPE can be
 // decided from ONE look at the pair table?  Runs exact sequential BPE on pooled words (its own small implementation) and,
 // at every batch start, walks the candidates in selection order (count, bytes(left), bytes(right)) under the batching rule
-// the device selection uses (see select_body in csrc/yabpe_kernels.h):
+// the device selection uses (see select_eval in csrc/yabpe_kernels.h):
 //
 //   accept candidate j after the accepted merges i < j iff
 //     (1) right(j) != a_i and left(j) != b_i             (its own count cannot move: only (x,a_i), (b_i,y), (a_i,b_i) fall)

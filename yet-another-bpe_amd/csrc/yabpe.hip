@@ -1301,17 +1301,14 @@ static int launch_select(yabpe_ctx *c, uint32_t rec_base) {
     const uint32_t n_part = c->use_cand ? std::min<uint32_t>(c->n_partials_cap, 64) : c->n_partials;
     const SelectParams S = select_params(c, rec_base, n_part, c->blk_used);
     c->blk_used = 0;  // the selection folds and clears them; what follows counts the next merge's grids
-    bool selected = false;
-    if (c->use_cand) {
-        const bool fuse = optv(c, "fuse_select", 1) != 0;
-        CandParams CP{c->table, c->tt.rec, c->partials, c->st, c->cand_state, fuse ? c->sel_ticket : nullptr, S};
+    if (c->use_cand) {  // (its last workgroup selects)
+        CandParams CP{c->table, c->tt.rec, c->partials, c->st, c->cand_state, c->sel_ticket, S};
         hipLaunchKernelGGL(k_argmax_cand, dim3(n_part), dim3(BLOCK), 0, c->stream, CP);
-        selected = fuse;
     } else {
         ArgmaxParams A{c->table, c->tt.rec, c->partials, c->st};
         hipLaunchKernelGGL(k_argmax_partial, dim3(c->n_partials), dim3(BLOCK), 0, c->stream, A);
+        hipLaunchKernelGGL(k_select, dim3(1), dim3(BLOCK), 0, c->stream, S);
     }
-    if (!selected) hipLaunchKernelGGL(k_select, dim3(1), dim3(BLOCK), 0, c->stream, S);
     HIPCHK(c, hipGetLastError());
     return 0;
 }

@@ -11,9 +11,10 @@
 //                 packed dwords, tiles with sites rewritten + compacted in place, pair-count deltas (tile_logic.h).
 //   k_scan_skip   sparse phase: a tile-level skip index (blocked Bloom signatures) finds the ~1 % of the tiles that may hold
 //                 the pair; only those are read and rewritten.
-//   select_body   the next merge: exact argmax over a candidate list by (count, lexrank[left], lexrank[right])
+//   select_eval   the next merges: exact argmax over a candidate list by (count, lexrank[left], lexrank[right])
 //                 (trainer.py:246), stop rules, merged-token creation / byte-string identity (trainer.py:241-251, 296-300);
-//                 run by the LAST workgroup of the launch that applied the previous merge (fused_select_tail).
+//                 run by the LAST workgroup of the launch that applied the previous batch (fused_select_tail).
+//                 select_body: one merge, as a launch of its own; both end in sel_stop, a single merge in commit_merge.
 //   rank blocks   extra workgroups of every launch keep lexrank[] = rank of every token's bytes in Python bytes order
 #pragma once
 #include <hip/hip_runtime.h>
@@ -1333,7 +1334,7 @@ __device__ __forceinline__ int tok_cmp_concat2(const TokTable &tt, uint32_t a1, 
 // lexrank maintenance after the last selection created new tokens c_k = a_k + b_k (the batch in DevState; a_k, b_k are older
 // tokens, their bytes are in the pool): a token moves up by one for every new token below it, and a new token's rank is the
 // number of tokens below it.  The first block also writes the new tokens' bytes into the pool (the selection only reserved
-// the place: it works from hashes, see select_body).
+// the place: it works from hashes, see commit_merge).
 struct RankParams {
     TokTable tt;
     DevState *st;
@@ -1856,32 +1857,15 @@ __device__ unsigned long long g_sel_acc[3 * 24]; // three ranges of merges x (co
 #define YB_SEL_STAMP(i) do { } while (0)
 #define YB_STOP(it, why, n, nw) do { } while (0)
 #endif
-// What a thread knows about its best candidate: the argmax record plus the two tokens' (len, hash), so that the winner's
-// merged token needs no further trip to the token table.
-struct BestEx {
-    Best b;
-    unsigned long long hx, hy;
-    uint32_t lx, ly;
-    uint32_t have; // hx .. ly are valid
-};
-__device__ __forceinline__ BestEx best_ex_none() { return BestEx{Best{0ull, 0u, EMPTY, 0u, 0u}, 0ull, 0ull, 0u, 0u, 0u}; }
-
-// Best entry among list[first, first + step, ...), four entries per thread in flight: count, ranks, lengths and hashes of
-// an entry are one round trip (the key rides in the list, a token's record is 16 B).  Every load goes past the caches: in
-// the fused form the list, the counts and the ranks were written by other workgroups of the same launch.
-__device__ __forceinline__ void ld_rec_coherent(const TokRec *r, uint32_t &rank, uint32_t &len, unsigned long long &hash) {
-    const unsigned long long *q = reinterpret_cast<const unsigned long long *>(r);
-    const unsigned long long a = ld_coherent(q);
-    hash = ld_coherent(q + 1);
-    rank = (uint32_t)a;
-    len = (uint32_t)(a >> 32);
-}
+// Best entry among list[first, first + step, ...), four entries per thread in flight: count and ranks of an entry are one
+// round trip (the key rides in the list).  Every load goes past the caches: the list, the counts and the ranks may have
+// been written by other workgroups of the same launch.
 template <int NF = 4> // entries in flight per thread
-__device__ __forceinline__ BestEx cand_list_best(const PairTable &t, const TokRec *rec, uint32_t n, uint32_t first, uint32_t step) {
-    BestEx best = best_ex_none();
+__device__ __forceinline__ Best cand_list_best(const PairTable &t, const TokRec *rec, uint32_t n, uint32_t first, uint32_t step) {
+    Best best{0ull, 0u, EMPTY, 0u, 0u};
     for (uint32_t i0 = first; i0 < n; i0 += (uint32_t)NF * step) {
-        unsigned long long e[NF], cn[NF], hx[NF], hy[NF];
-        uint32_t rl[NF], rr[NF], lx[NF], ly[NF];
+        unsigned long long e[NF], cn[NF];
+        uint32_t rl[NF], rr[NF];
 #pragma unroll
         for (int k = 0; k < NF; ++k) {
             const uint32_t i = i0 + (uint32_t)k * step;
@@ -1893,15 +1877,15 @@ __device__ __forceinline__ BestEx cand_list_best(const PairTable &t, const TokRe
             if (i0 + (uint32_t)k * step < n) {
                 const uint32_t key = (uint32_t)(e[k] >> 32);
                 cn[k] = ld_coherent(pt_count_ptr(t, e[k]));
-                ld_rec_coherent(&rec[key >> 16], rl[k], lx[k], hx[k]);
-                ld_rec_coherent(&rec[key & 0xffffu], rr[k], ly[k], hy[k]);
+                rl[k] = ld_coherent(&rec[key >> 16].rank);
+                rr[k] = ld_coherent(&rec[key & 0xffffu].rank);
             }
         }
 #pragma unroll
         for (int k = 0; k < NF; ++k) {
             if ((long long)cn[k] <= 0) continue;
             const Best b{cn[k], (rl[k] << 16) | rr[k], (uint32_t)(e[k] >> 32), (uint32_t)e[k], 0u};
-            if (best_gt(b, best.b)) best = BestEx{b, hx[k], hy[k], lx[k], ly[k], 1u};
+            if (best_gt(b, best)) best = b;
         }
     }
     return best;
@@ -1945,48 +1929,193 @@ __device__ __forceinline__ int cmp_pre8(unsigned long long px, uint32_t lx, unsi
     return 2;
 }
 
-// The selection as a launch of its own (k_select, or the last workgroup of k_argmax_cand): one workgroup commits a pending
-// halt, folds the apply pass's counters, reduces the argmax partials, applies the stop rules and creates the merged token.
-// ONE merge (DevState::batch[0]).  Used when no merge is pending (start of a job, after a halt) and when no candidate list
-// can prove the maximum; the per-batch launches end with select_eval below instead.
-//   - thread 0 keeps the DevState fields it needs in registers and writes back what it changes;
-//   - the merged token is created from the two tokens' records: its hash follows from theirs (yb_hash_concat), one probe of
-//     the byte-string set says whether those bytes are already a token (trainer.py:298), and its bytes are written by the
-//     NEXT launch (rank_update_block) -- the winner's bytes are never read here unless hash and length match an entry.
+// ---------------------------------------------------------------- what both selections share
+// select_body (one merge, a launch of its own) and select_eval (a batch, the tail of every per-batch launch) read the same
+// DevState snapshot, apply the same stop rules and commit a single merge the same way.  All of it runs in one thread or one
+// wave of the selecting workgroup.
+
+// The DevState fields a selection reads, loaded by ONE thread (thread 0; the others keep zeros).  list: a candidate list is
+// attached -- without one, T = 0 and no overflow, so the stop rules never ask for a rescan.
+struct SelState {
+    uint32_t iter, done, halt, halt_req, n_tokens, pool_used, num_merges, cand_over, cand_n;
+    unsigned long long min_freq, table_entries, live_slots, sites, tokens_now, prev_others, candT;
+};
+__device__ __forceinline__ SelState sel_state_load(const SelectParams &P, bool list) {
+    const DevState *st = P.st;
+    SelState S{};
+    S.iter = st->iter;
+    S.done = st->done;
+    S.halt = st->halt;
+    S.n_tokens = st->n_tokens;
+    S.pool_used = st->pool_used;
+    S.num_merges = st->num_merges;
+    S.min_freq = st->min_freq;
+    S.live_slots = st->live_slots;
+    S.tokens_now = st->tokens_now;
+    S.prev_others = st->batch_others;
+    // fields other workgroups of this launch may have moved (atomics): read them past the caches
+    S.halt_req = ld_coherent(&st->halt_req);
+    S.table_entries = ld_coherent(&st->table_entries);
+    S.sites = ld_coherent(&st->sites);
+    if (list) {
+        S.candT = P.cs->T;
+        S.cand_over = ld_coherent(&P.cs->overflow);
+        S.cand_n = ld_coherent(&P.cs->n);
+    }
+    return S;
+}
+
+// The stop rules, by the thread that holds S: commits a pending halt, folds in the last apply pass's counters (sites merged,
+// slots freed), closes the site log of the batch it applied and writes back what every path writes.  best_cnt: the largest
+// count there is.  Returns 1 when nothing is to be selected (done or halt).
+__device__ __forceinline__ uint32_t sel_stop(const SelectParams &P, SelState &S, unsigned long long fold_sites, unsigned long long fold_freed,
+                                             unsigned long long best_cnt) {
+    DevState *st = P.st;
+    uint32_t stop = 0;
+    if (S.halt == 0 && S.halt_req != 0) S.halt = S.halt_req;
+    if (P.delta_hdr) { // this rank's send header for the next exchange
+        P.delta_hdr->count = 0ull;
+        P.delta_hdr->halt = S.halt;
+    }
+    // Deterministic across ranks (all replicas hold the same keys): stop before the table gets crowded, so that no replica
+    // can run out of probes on its own.
+    if (S.halt == 0 && S.table_entries * 5ull > (unsigned long long)P.table.cap * 4ull) S.halt = HALT_TABLE_FULL; // > 80 % full
+    S.sites += fold_sites;
+    S.live_slots -= fold_freed;
+    if (S.done | S.halt) {
+        stop = 1;
+    } else {
+        // close the log entries of the batch that has just been applied: merges [it - pb, it).  Flat layout, a != b: a
+        // merge's sites are exactly its count, and only the last merge of a batch can have a == b -- it gets what is
+        // left.  (Pooled words / several ranks: counts are not resident sites; the whole batch is logged on its last merge.)
+        const uint32_t it = S.iter;
+        if (it > P.rec_base && S.sites) { // (0: already closed, this is a re-run)
+            // (the batch's other merges were logged with their counts when they were selected: what is left is the last one's)
+            const unsigned long long others = P.flat_single ? S.prev_others : 0ull;
+            P.rec_sites[it - 1 - P.rec_base] = others <= S.sites ? S.sites - others : S.sites;
+        }
+        S.tokens_now -= S.sites;
+        S.sites = 0;
+        if (it < S.num_merges && (best_cnt < S.candT || S.cand_over)) {
+            S.halt = HALT_RESCAN; // the candidate list no longer proves the maximum: the host redoes this merge with a full scan
+            stop = 1;
+        } else if (it >= S.num_merges || best_cnt == 0 || best_cnt < S.min_freq) {
+            S.done = 1; // stop rules: iteration limit (trainer.py:241), no pairs (:242-243), min_frequency (:247-248)
+            stop = 1;
+        }
+    }
+    st->halt = S.halt;
+    st->done = S.done;
+    st->sites = S.sites;
+    st->live_slots = S.live_slots;
+    st->tokens_now = S.tokens_now;
+    st->cand_n = S.cand_n;
+    if (stop) st->n_batch = 0u;
+    return stop;
+}
+
+// Commits ONE merge: the pair m.key with count m.cnt in table slot m.slot, from its two tokens' hashes, lengths and 8-byte
+// prefixes.  Called by a whole wave with the same m; S is lane 0's.  The merged token's hash follows from its parts'
+// (yb_hash_concat), and the byte-string set says whether those bytes are a token already (trainer.py:298-300: then the
+// merge takes that id).  Its entries carry 32 bits of the hash, so a slot that holds another string is passed over
+// without looking at that string; a match is settled by a full byte compare (rare: the token exists already, or a 2^-32
+// coincidence).  A new token gets its id and pool space here, its bytes are written by the NEXT launch (rank_update_block).
+__device__ __forceinline__ void commit_merge(const SelectParams &P, const SelState &S, const WinEnt &m) {
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t x = m.key >> 16, y = m.key & 0xffffu, L = m.lx + m.ly;
+    const unsigned long long H = yb_hash_concat(m.hx, m.hy, m.ly);
+    uint32_t slot = yb_vset_home(H, L) & P.tt.vset_mask, found = EMPTY;
+    YB_SEL_STAMP(5);
+    while (true) { // (every lane walks the same slots)
+        const unsigned long long en = ld_coherent(&P.tt.vset[slot]);
+        if (en == VSET_EMPTY) break;
+        if ((en >> 32) == (H >> 32)) {
+            const uint32_t cand = (uint32_t)en;
+            const TokRec rc = P.tt.rec[cand];
+            if (rc.len == L && rc.hash == H) {
+                const uint32_t oc = P.tt.off[cand], ox = P.tt.off[x], oy = P.tt.off[y];
+                bool ne = false;
+                for (uint32_t i = lane; i < L; i += 64u)
+                    ne |= pool_byte_coherent(P.tt.pool, oc + i) != pool_byte_coherent(P.tt.pool, i < m.lx ? ox + i : oy + (i - m.lx));
+                if (!__any(ne)) {
+                    found = cand;
+                    break;
+                }
+            }
+        }
+        slot = (slot + 1) & P.tt.vset_mask;
+    }
+    YB_SEL_STAMP(6);
+    const uint32_t it = __builtin_amdgcn_readfirstlane(S.iter), ntok = __builtin_amdgcn_readfirstlane(S.n_tokens);
+    const uint32_t pool = __builtin_amdgcn_readfirstlane(S.pool_used);
+    if (lane == 0) {
+        DevState *st = P.st;
+        uint32_t cid = 0, is_new = 0;
+        bool ok = true;
+        if (found != EMPTY) {
+            cid = found; // bytes already a token: no id is consumed
+        } else if (ntok >= YB_MAX_TOKENS) {
+            st->halt = HALT_VOCAB_FULL;
+            ok = false;
+        } else if ((unsigned long long)pool + L + 4ull > P.tt.pool_cap) {
+            st->halt = HALT_POOL_FULL;
+            ok = false;
+        } else { // merged = p0 + p1 (trainer.py:251): place reserved, bytes written by the next launch
+            cid = ntok;
+            P.tt.off[cid] = pool;
+            P.tt.len[cid] = L;
+            P.tt.rec[cid] = TokRec{0u, L, H, pre8_concat(m.px, m.lx, m.py), 0ull};
+            P.tt.vset[slot] = yb_vset_entry(cid, H);
+            is_new = 1;
+        }
+        if (!ok) {
+            st->n_batch = 0u;
+        } else {
+            const uint32_t ri = it - P.rec_base;
+            P.rec_left[ri] = x; // merges.append(best_pair) (trainer.py:296)
+            P.rec_right[ri] = y;
+            P.rec_merged[ri] = cid;
+            P.rec_count[ri] = m.cnt;
+            P.rec_live_slots[ri] = S.live_slots;
+            // after this merge no (x, y) adjacency is left anywhere (trainer.py:276-285), so its count is exactly 0: set it
+            // here once instead of letting every workgroup subtract its share from one hot address
+            P.table.cnt[m.slot] = 0ull;
+            st->a = x;
+            st->b = y;
+            st->c = cid;
+            st->c_is_new = is_new;
+            st->best_count = m.cnt;
+            st->batch[0] = BatchMerge{x, y, cid, is_new};
+            st->n_batch = 1u;
+            st->n_select = st->n_select + 1u;
+            st->batch_others = 0ull;
+            st->iter = it + 1u;
+            st->pool_used = is_new ? ((pool + L + 3u) & ~3u) : pool;
+            st->n_tokens = ntok + is_new;
+#ifdef YB_PROFILE_LAUNCH
+            g_launch_prof[(it & 0xFFFFu) * 4 + 3] = wall_clock64(); // (same index as the launch that ran this selection: its st->iter at start)
+#endif
+        }
+    }
+}
+
+// The selection as a launch of its own (k_select, or the last workgroup of k_argmax_cand): ONE merge (DevState::batch[0]).
+// Used when no merge is pending (start of a job, after a halt) and when no candidate list can prove the maximum; the
+// per-batch launches end with select_eval below instead.  What is its own: the per-workgroup counters of the last apply
+// pass are folded and the argmax partials reduced by the whole workgroup; then thread 0 applies the stop rules, two
+// threads read the winner's token records and wave 0 commits it.
 __device__ __forceinline__ void select_body(const SelectParams &P) {
     __shared__ Best s_b[WPB];
-    __shared__ uint32_t s_flag, s_slot, s_eq, s_lx, s_ly;
-    __shared__ unsigned long long s_fold[2], s_hx, s_hy, s_px, s_py, s_ent;
-    DevState *st = P.st;
+    __shared__ uint32_t s_flag;
+    __shared__ unsigned long long s_fold[2];
+    __shared__ WinEnt s_m; // the winner
     const int tid = threadIdx.x;
     YB_SEL_STAMP(1);
-    uint32_t d_iter = 0, d_done = 0, d_halt = 0, d_halt_req = 0, d_n_tokens = 0, d_pool_used = 0, d_num_merges = 0;
-    unsigned long long d_min_freq = 0, d_table_entries = 0, d_live_slots = 0, d_sites = 0, d_tokens_now = 0, d_prev_others = 0;
-    unsigned long long candT = 0;
-    uint32_t cand_over = 0, cand_n = 0;
+    SelState S{};
     if (tid == 0) {
-        d_iter = st->iter;
-        d_done = st->done;
-        d_halt = st->halt;
-        d_n_tokens = st->n_tokens;
-        d_pool_used = st->pool_used;
-        d_num_merges = st->num_merges;
-        d_min_freq = st->min_freq;
-        d_live_slots = st->live_slots;
-        d_tokens_now = st->tokens_now;
-        d_prev_others = st->batch_others;
-        // fields other workgroups of this launch may have moved (atomics): read them past the caches
-        d_halt_req = ld_coherent(&st->halt_req);
-        d_table_entries = ld_coherent(&st->table_entries);
-        d_sites = ld_coherent(&st->sites);
-        if (P.cs) {
-            candT = P.cs->T;
-            cand_over = ld_coherent(&P.cs->overflow);
-            cand_n = ld_coherent(&P.cs->n);
-        }
+        S = sel_state_load(P, P.cs != nullptr);
         s_fold[0] = 0;
         s_fold[1] = 0;
-        s_flag = 0;
     }
     // the counters of the last apply pass (one slot per workgroup): summed and cleared
     unsigned long long fa = 0, ff = 0;
@@ -2021,161 +2150,23 @@ __device__ __forceinline__ void select_body(const SelectParams &P) {
     __syncthreads();
     YB_SEL_STAMP(2);
     if (tid == 0) {
-        if (d_halt == 0 && d_halt_req != 0) d_halt = d_halt_req;
-        if (P.delta_hdr) { // this rank's send header for the next exchange
-            P.delta_hdr->count = 0ull;
-            P.delta_hdr->halt = d_halt;
-        }
-        // Deterministic across ranks (all replicas hold the same keys): stop before the table gets crowded, so that
-        // no replica can run out of probes on its own.
-        if (d_halt == 0 && d_table_entries * 5ull > (unsigned long long)P.table.cap * 4ull) d_halt = HALT_TABLE_FULL; // > 80 % full
-        d_sites += s_fold[0];
-        d_live_slots -= s_fold[1];
-        if (d_done | d_halt) {
-            s_flag = 1;
-        } else {
-            for (int w = 1; w < WPB; ++w)
-                if (best_gt(s_b[w], best)) best = s_b[w];
-            s_b[0] = best;
-            // close the log entries of the batch that has just been applied: merges [it - pb, it).  Flat layout, a != b: a
-            // merge's sites are exactly its count, and only the last merge of a batch can have a == b -- it gets what is
-            // left.  (Pooled words / several ranks: counts are not resident sites; the whole batch is logged on its last merge.)
-            const uint32_t it = d_iter;
-            if (it > P.rec_base && d_sites) { // (0: already closed, this is a re-run)
-                // (the batch's other merges were logged with their counts when they were selected: what is left is the last one's)
-                const unsigned long long others = P.flat_single ? d_prev_others : 0ull;
-                P.rec_sites[it - 1 - P.rec_base] = others <= d_sites ? d_sites - others : d_sites;
-            }
-            d_tokens_now -= d_sites;
-            d_sites = 0;
-            if (P.cs && it < d_num_merges && (best.cnt < candT || cand_over)) {
-                // the candidate set no longer proves that this is the maximum: the host redoes this merge with a full scan
-                d_halt = HALT_RESCAN;
-                s_flag = 1;
-            } else if (it >= d_num_merges || best.cnt == 0 || best.cnt < d_min_freq) {
-                // stop rules: iteration limit (trainer.py:241), no pairs (:242-243), min_frequency (:247-248)
-                d_done = 1;
-                s_flag = 1;
-            }
-        }
-        // what every path writes back (the rest follows when a merge has been selected)
-        st->halt = d_halt;
-        st->done = d_done;
-        st->sites = d_sites;
-        st->live_slots = d_live_slots;
-        st->tokens_now = d_tokens_now;
-        st->cand_n = cand_n;
-        if (s_flag) st->n_batch = 0u;
+        for (int w = 1; w < WPB; ++w)
+            if (best_gt(s_b[w], best)) best = s_b[w];
+        s_flag = sel_stop(P, S, s_fold[0], s_fold[1], best.cnt);
+        s_m.cnt = best.cnt;
+        s_m.key = best.key;
+        s_m.slot = best.slot;
     }
     __syncthreads();
     if (s_flag) return;
     YB_SEL_STAMP(3);
-    const Best win = s_b[0];
-    const uint32_t x = win.key >> 16, y = win.key & 0xffffu;
     if (tid < 2) { // the two tokens' records
-        const TokRec r = P.tt.rec[tid ? y : x];
-        if (tid) { s_hy = r.hash; s_ly = r.len; s_py = r.pre8; } else { s_hx = r.hash; s_lx = r.len; s_px = r.pre8; }
+        const TokRec r = P.tt.rec[tid ? s_m.key & 0xffffu : s_m.key >> 16];
+        if (tid) { s_m.hy = r.hash; s_m.ly = r.len; s_m.py = r.pre8; } else { s_m.hx = r.hash; s_m.lx = r.len; s_m.px = r.pre8; }
     }
     __syncthreads();
     YB_SEL_STAMP(4);
-    const uint32_t lx = s_lx, L = s_lx + s_ly, pu = d_pool_used; // (thread 0 only)
-    const unsigned long long H = yb_hash_concat(s_hx, s_hy, s_ly);
-    // "merged not in vocab" (trainer.py:298): probe the byte-string set; entries carry 32 bits of the hash, so a slot that
-    // holds another string is passed over without looking at that string
-    if (tid == 0) {
-        uint32_t slot = yb_vset_home(H, L) & P.tt.vset_mask;
-        unsigned long long ve = P.tt.vset[slot];
-        while (ve != VSET_EMPTY && (ve >> 32) != (H >> 32)) {
-            slot = (slot + 1) & P.tt.vset_mask;
-            ve = P.tt.vset[slot];
-        }
-        s_slot = slot;
-        s_ent = ve;
-    }
-    __syncthreads();
-    YB_SEL_STAMP(5);
-    uint32_t found = EMPTY;
-    while (s_ent != VSET_EMPTY) { // same 32 hash bits: compare for real (rare: the token exists already, or a 2^-32 coincidence)
-        const uint32_t cand = (uint32_t)s_ent;
-        if (tid == 0) s_eq = 1;
-        __syncthreads();
-        const TokRec rc = P.tt.rec[cand];
-        if (rc.len == L && rc.hash == H) {
-            const uint32_t oc = P.tt.off[cand], ox = P.tt.off[x], oy = P.tt.off[y];
-            int ne = 0;
-            for (uint32_t i = tid; i < L; i += BLOCK)
-                ne |= pool_byte_coherent(P.tt.pool, oc + i) != pool_byte_coherent(P.tt.pool, i < lx ? ox + i : oy + (i - lx));
-            if (ne) s_eq = 0; // benign race: every writer stores 0
-        } else if (tid == 0) {
-            s_eq = 0;
-        }
-        __syncthreads();
-        if (s_eq) {
-            found = cand;
-            break;
-        }
-        if (tid == 0) { // next slot with the same 32 hash bits, or the empty slot that ends the run
-            uint32_t slot = (s_slot + 1) & P.tt.vset_mask;
-            unsigned long long ve = P.tt.vset[slot];
-            while (ve != VSET_EMPTY && (ve >> 32) != (H >> 32)) {
-                slot = (slot + 1) & P.tt.vset_mask;
-                ve = P.tt.vset[slot];
-            }
-            s_slot = slot;
-            s_ent = ve;
-        }
-        __syncthreads();
-    }
-    YB_SEL_STAMP(6);
-    if (tid == 0) {
-        uint32_t cid = 0;
-        uint32_t is_new = 0;
-        bool ok = true;
-        if (found != EMPTY) {
-            cid = found; // bytes already a token: no id is consumed (trainer.py:298-300)
-        } else if (d_n_tokens >= YB_MAX_TOKENS) {
-            st->halt = HALT_VOCAB_FULL;
-            st->n_batch = 0u;
-            ok = false;
-        } else if ((unsigned long long)pu + L + 4ull > P.tt.pool_cap) {
-            st->halt = HALT_POOL_FULL;
-            st->n_batch = 0u;
-            ok = false;
-        } else {
-            cid = d_n_tokens; // merged = p0 + p1 (trainer.py:251): place reserved, bytes written by the next launch
-            P.tt.off[cid] = pu;
-            P.tt.len[cid] = L;
-            P.tt.rec[cid] = TokRec{0u, L, H, pre8_concat(s_px, s_lx, s_py), 0ull};
-            P.tt.vset[s_slot] = yb_vset_entry(cid, H);
-            is_new = 1;
-        }
-        if (ok) {
-            const uint32_t ri = d_iter - P.rec_base;
-            P.rec_left[ri] = x; // merges.append(best_pair) (trainer.py:296)
-            P.rec_right[ri] = y;
-            P.rec_merged[ri] = cid;
-            P.rec_count[ri] = win.cnt;
-            P.rec_live_slots[ri] = d_live_slots;
-            // after this merge no (x,y) adjacency is left anywhere (trainer.py:276-285), so its count is exactly 0:
-            // set it here once instead of letting every workgroup subtract its share from one hot address
-            P.table.cnt[win.slot] = 0ull;
-            st->a = x;
-            st->b = y;
-            st->c = cid;
-            st->best_count = win.cnt;
-            st->c_is_new = is_new;
-            st->batch[0] = BatchMerge{x, y, cid, is_new};
-            st->n_batch = 1u;
-            st->n_select = st->n_select + 1u;
-            st->batch_others = 0ull;
-            st->iter = d_iter + 1;
-            st->pool_used = is_new ? ((pu + L + 3u) & ~3u) : pu;
-            st->n_tokens = d_n_tokens + is_new;
-#ifdef YB_PROFILE_LAUNCH
-            g_launch_prof[(d_iter & 0xFFFFu) * 4 + 3] = wall_clock64(); // (same index as the launch that ran this selection: its st->iter at start)
-#endif
-        }
-    }
+    if (tid < 64) commit_merge(P, S, s_m);
     YB_SEL_STAMP(7);
 }
 
@@ -2209,33 +2200,16 @@ __device__ __forceinline__ void select_eval(const SelectParams &P, WinEnt *s_win
     for (int k = 0; k < 4; ++k) e[k] = ld_coherent(&P.table.cand_list[tid + k * BLOCK]);
     const uint32_t n_list = min(ld_coherent(&P.cs->n), CAND_CAP);
     const uint32_t kmax = min(st->kmax, (uint32_t)KMAX);
-    uint32_t d_iter = 0, d_done = 0, d_halt = 0, d_halt_req = 0, d_n_tokens = 0, d_pool_used = 0, d_num_merges = 0;
-    unsigned long long d_min_freq = 0, d_table_entries = 0, d_live_slots = 0, d_sites = 0, d_tokens_now = 0, candT = 0, d_prev_others = 0;
-    uint32_t cand_over = 0, cand_n = 0;
+    SelState S{};
     if (tid == 0) {
-        d_iter = st->iter;
-        d_done = st->done;
-        d_halt = st->halt;
-        d_n_tokens = st->n_tokens;
-        d_pool_used = st->pool_used;
-        d_num_merges = st->num_merges;
-        d_min_freq = st->min_freq;
-        d_live_slots = st->live_slots;
-        d_tokens_now = st->tokens_now;
-        d_prev_others = st->batch_others;
-        d_halt_req = ld_coherent(&st->halt_req);
-        d_table_entries = ld_coherent(&st->table_entries);
-        d_sites = ld_coherent(&st->sites);
-        candT = P.cs->T;
-        cand_over = ld_coherent(&P.cs->overflow);
-        cand_n = ld_coherent(&P.cs->n);
+        S = sel_state_load(P, true);
         s_fold[0] = 0;
         s_fold[1] = 0;
         s_nwin = 0;
         s_flags[0] = 0u; // positions of the selection order that fail the batch rule
         s_flags[1] = 0u; // positions that hold a run merge (p == q)
-        s_lim[0] = candT;
-        s_lim[1] = d_min_freq;
+        s_lim[0] = S.candT;
+        s_lim[1] = S.min_freq;
     }
     unsigned long long vx[4], vy[4];
 #pragma unroll
@@ -2410,7 +2384,7 @@ __device__ __forceinline__ void select_eval(const SelectParams &P, WinEnt *s_win
     }
     __syncthreads();
     YB_SEL_STAMP(11);
-    // ---- the batch rule (above select_body), for every window entry side by side instead of a walk.  The entries in
+    // ---- the batch rule ("batches of merges" above), for every window entry side by side instead of a walk.  The entries in
     // selection order are the window sorted by (count, lexranks) descending -- distinct pairs: no ties -- and the merges
     // accepted before position j are exactly positions 0 .. j-1, so everything rule (1) and rule (2) ask about position j is
     // known without walking: an entry's two bit sets over the first KMAX positions (ra: bit i = "my right token is a_i",
@@ -2488,43 +2462,8 @@ __device__ __forceinline__ void select_eval(const SelectParams &P, WinEnt *s_win
     if (tid >= 64) return; // ---- from here on: wave 0 alone, wave-level synchronisation only
     // ---- stop rules and the first merge (lane 0 holds the state)
     uint32_t flag = 0; // 1: nothing selected (done / halt)
-    const unsigned long long best_cnt = cmax;
     if (lane == 0) {
-        if (d_halt == 0 && d_halt_req != 0) d_halt = d_halt_req;
-        if (P.delta_hdr) { // this rank's send header for the next exchange
-            P.delta_hdr->count = 0ull;
-            P.delta_hdr->halt = d_halt;
-        }
-        if (d_halt == 0 && d_table_entries * 5ull > (unsigned long long)P.table.cap * 4ull) d_halt = HALT_TABLE_FULL; // > 80 % full (the same on every rank)
-        d_sites += s_fold[0];
-        d_live_slots -= s_fold[1];
-        if (d_done | d_halt) {
-            flag = 1;
-        } else {
-            // close the log entries of the batch that has just been applied (see select_body)
-            const uint32_t it = d_iter;
-            if (it > P.rec_base && d_sites) {
-                // (the batch's other merges were logged with their counts when they were selected: what is left is the last one's)
-                const unsigned long long others = P.flat_single ? d_prev_others : 0ull;
-                P.rec_sites[it - 1 - P.rec_base] = others <= d_sites ? d_sites - others : d_sites;
-            }
-            d_tokens_now -= d_sites;
-            d_sites = 0;
-            if (it < d_num_merges && (best_cnt < candT || cand_over)) {
-                d_halt = HALT_RESCAN; // the candidate set no longer proves the maximum: the host redoes this merge with a full scan
-                flag = 1;
-            } else if (it >= d_num_merges || best_cnt == 0 || best_cnt < d_min_freq) {
-                d_done = 1; // stop rules: iteration limit (trainer.py:241), no pairs (:242-243), min_frequency (:247-248)
-                flag = 1;
-            }
-        }
-        st->halt = d_halt;
-        st->done = d_done;
-        st->sites = d_sites;
-        st->live_slots = d_live_slots;
-        st->tokens_now = d_tokens_now;
-        st->cand_n = cand_n;
-        if (flag) st->n_batch = 0u;
+        flag = sel_stop(P, S, s_fold[0], s_fold[1], cmax);
         // next time: a narrower window after an overflow, a wider one when this one held few pairs
         if (kmax > 1u) st->win_shift = narrowed ? min(wshift + narrowed, 20u) : (n_win < 4u * kmax && wshift > 1u) ? wshift - 1u : wshift;
     }
@@ -2532,7 +2471,7 @@ __device__ __forceinline__ void select_eval(const SelectParams &P, WinEnt *s_win
     if (flag) return;
     YB_SEL_STAMP(3);
     // ---- the batch: positions [0, nacc) -- up to the first position that fails, the first run merge included, the limits
-    const uint32_t it0 = __builtin_amdgcn_readfirstlane(d_iter), num_merges = __builtin_amdgcn_readfirstlane(d_num_merges);
+    const uint32_t it0 = __builtin_amdgcn_readfirstlane(S.iter), num_merges = __builtin_amdgcn_readfirstlane(S.num_merges);
     uint32_t nacc = min(min(kmax, num_merges - it0), n_top), why = 4u;
     (void)why;
     {
@@ -2574,7 +2513,7 @@ __device__ __forceinline__ void select_eval(const SelectParams &P, WinEnt *s_win
         if ((uint32_t)lane < nacc && (uint32_t)lane > k2 && (s2 == vslot || (h2 == Hk && l2 == Lk))) bad = 1u;
     }
     // pool offsets: exclusive prefix of the 4-byte-rounded lengths (a handful of lanes)
-    const uint32_t ntok0 = __builtin_amdgcn_readfirstlane(d_n_tokens), pool0 = __builtin_amdgcn_readfirstlane(d_pool_used);
+    const uint32_t ntok0 = __builtin_amdgcn_readfirstlane(S.n_tokens), pool0 = __builtin_amdgcn_readfirstlane(S.pool_used);
     uint32_t pool_at = pool0;
     for (uint32_t k2 = 0; k2 + 1 < nacc; ++k2) {
         const uint32_t l2 = __builtin_amdgcn_readlane(Lk, k2);
@@ -2602,7 +2541,7 @@ __device__ __forceinline__ void select_eval(const SelectParams &P, WinEnt *s_win
         P.rec_merged[ri] = cid;
         P.rec_count[ri] = s_win[wk].cnt;
         if (P.flat_single && k + 1u < keep) P.rec_sites[ri] = s_win[wk].cnt; // flat layout, a != b: a merge's sites are exactly its count (the last merge of the batch gets what is left, next time)
-        P.rec_live_slots[ri] = ((unsigned long long)__builtin_amdgcn_readfirstlane((uint32_t)(d_live_slots >> 32)) << 32) | __builtin_amdgcn_readfirstlane((uint32_t)d_live_slots);
+        P.rec_live_slots[ri] = ((unsigned long long)__builtin_amdgcn_readfirstlane((uint32_t)(S.live_slots >> 32)) << 32) | __builtin_amdgcn_readfirstlane((uint32_t)S.live_slots);
         // after the merge no (x, y) adjacency is left anywhere (trainer.py:276-285), so its count is exactly 0: set it here once
         // instead of letting every workgroup subtract its share from one hot address
         P.table.cnt[s_win[wk].slot] = 0ull;
@@ -2641,77 +2580,7 @@ __device__ __forceinline__ void select_eval(const SelectParams &P, WinEnt *s_win
     if (keep != 0u) return;
     // ---- the first merge could not be created blindly: its bytes may be a token already (trainer.py:298-300: then it keeps
     // that id), or there is no id / no pool space left.  Settled here by the whole wave, one merge, the batch ends with it.
-    {
-        const uint32_t w = s_acc[0].win;
-        const uint32_t key = s_win[w].key, x = key >> 16, y = key & 0xffffu, lx = s_win[w].lx, Lm = lx + s_win[w].ly;
-        const unsigned long long Hm = yb_hash_concat(s_win[w].hx, s_win[w].hy, s_win[w].ly);
-        uint32_t slot = yb_vset_home(Hm, Lm) & P.tt.vset_mask, found = EMPTY;
-        while (true) { // (every lane walks the same slots)
-            const unsigned long long en = ld_coherent(&P.tt.vset[slot]);
-            if (en == VSET_EMPTY) break;
-            if ((en >> 32) == (Hm >> 32)) {
-                const uint32_t cand = (uint32_t)en;
-                const TokRec rc = P.tt.rec[cand];
-                if (rc.len == Lm && rc.hash == Hm) {
-                    const uint32_t oc = P.tt.off[cand], ox = P.tt.off[x], oy = P.tt.off[y];
-                    bool ne = false;
-                    for (uint32_t i = (uint32_t)lane; i < Lm; i += 64u)
-                        ne |= pool_byte_coherent(P.tt.pool, oc + i) != pool_byte_coherent(P.tt.pool, i < lx ? ox + i : oy + (i - lx));
-                    if (!__any(ne)) {
-                        found = cand;
-                        break;
-                    }
-                }
-            }
-            slot = (slot + 1) & P.tt.vset_mask;
-        }
-        if (lane == 0) {
-            uint32_t cid = 0, is_new = 0;
-            bool ok = true;
-            if (found != EMPTY) {
-                cid = found; // bytes already a token: no id is consumed
-            } else if (ntok0 >= YB_MAX_TOKENS) {
-                st->halt = HALT_VOCAB_FULL;
-                ok = false;
-            } else if ((unsigned long long)pool0 + Lm + 4ull > P.tt.pool_cap) {
-                st->halt = HALT_POOL_FULL;
-                ok = false;
-            } else {
-                cid = ntok0;
-                P.tt.off[cid] = pool0;
-                P.tt.len[cid] = Lm;
-                P.tt.rec[cid] = TokRec{0u, Lm, Hm, s_acc[0].pc, 0ull};
-                P.tt.vset[slot] = yb_vset_entry(cid, Hm);
-                is_new = 1;
-            }
-            if (!ok) {
-                st->n_batch = 0u;
-            } else {
-                const uint32_t ri = it0 - P.rec_base;
-                P.rec_left[ri] = x;
-                P.rec_right[ri] = y;
-                P.rec_merged[ri] = cid;
-                P.rec_count[ri] = s_win[w].cnt;
-                P.rec_live_slots[ri] = d_live_slots;
-                P.table.cnt[s_win[w].slot] = 0ull;
-                st->a = x;
-                st->b = y;
-                st->c = cid;
-                st->c_is_new = is_new;
-                st->best_count = s_win[w].cnt;
-                st->batch[0] = BatchMerge{x, y, cid, is_new};
-                st->n_batch = 1u;
-                st->n_select = st->n_select + 1u;
-                st->batch_others = 0ull;
-                st->iter = it0 + 1u;
-                st->pool_used = is_new ? ((pool0 + Lm + 3u) & ~3u) : pool0;
-                st->n_tokens = ntok0 + is_new;
-#ifdef YB_PROFILE_LAUNCH
-                g_launch_prof[(it0 & 0xFFFFu) * 4 + 3] = wall_clock64();
-#endif
-            }
-        }
-    }
+    commit_merge(P, S, s_win[s_acc[0].win]);
 }
 
 __global__ __launch_bounds__(BLOCK) void k_select(SelectParams P) { select_body(P); }
@@ -2830,7 +2699,7 @@ struct CandParams {
     Best *partials;
     DevState *st;
     CandState *cs;
-    uint32_t *ticket;  // != NULL: the last workgroup to finish runs the selection itself (no k_select launch)
+    uint32_t *ticket;  // k_argmax_cand: the last workgroup to finish runs the selection itself
     SelectParams sel;
 };
 
@@ -2886,7 +2755,7 @@ __global__ __launch_bounds__(BLOCK) void k_argmax_cand(CandParams P) {
 #endif
     const uint32_t stop = P.st->done | P.st->halt; // (these loads do not depend on each other: one round trip)
     if (!stop) { // (the list is complete: nothing updates the table while this kernel runs)
-        Best best = cand_list_best(P.table, P.rec, min(P.cs->n, CAND_CAP), blockIdx.x * BLOCK + threadIdx.x, gridDim.x * BLOCK).b;
+        Best best = cand_list_best(P.table, P.rec, min(P.cs->n, CAND_CAP), blockIdx.x * BLOCK + threadIdx.x, gridDim.x * BLOCK);
         best = best_wave_reduce(best);
         const int lane = threadIdx.x & 63, wib = threadIdx.x >> 6;
         if (lane == 0) s_b[wib] = best;
@@ -2900,7 +2769,6 @@ __global__ __launch_bounds__(BLOCK) void k_argmax_cand(CandParams P) {
         if (blockIdx.x == 0) YB_SEL_STAMP(9);
 #endif
     }
-    if (!P.ticket) return;
     // The workgroup that finishes last does the selection.  No __threadfence (an L2 write-back on this part): what
     // the selection reads from THIS kernel -- the partials -- goes through device-scope accesses; each workgroup waits
     // for its own to be acknowledged before it takes its ticket.
