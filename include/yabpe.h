@@ -205,6 +205,45 @@ int yabpe_pretokenize(yabpe_ctx *ctx, const uint8_t *text, uint64_t n_bytes, con
                       const uint8_t **out_dev_text, uint64_t **out_dev_word_off, uint64_t *out_n_words, int64_t *out_bad_pos);
 int yabpe_pretokenize_free(yabpe_ctx *ctx);
 
+/* Encoder (BBPETokenizer.encode on the device, yet_another_bpe/tokenizer.py) ----------------------------------------
+ * A trained model: the vocab (n_vocab byte strings, vocab_off: n_vocab + 1 offsets, vocab_ids: their ids), the merges in
+ * order (merge_off: 2 n_merges + 1 offsets, left and right operand of merge i = entries 2i and 2i + 1) and the specials in
+ * the tokenizer's order (longest first, stable).  unk_id = vocab.get(b"[UNK]", 0).  The library interns every byte string
+ * that can be a token (single bytes, both operands and the concatenation of every merge) and keeps the pair table, the
+ * id map and the specials on the device.  Rejects an empty special (YABPE_E_INVALID) and more than 254 specials
+ * (YABPE_E_CAPACITY).  Ids are u32. */
+int yabpe_encode_set_model(yabpe_ctx *ctx, const uint8_t *vocab_bytes, const uint64_t *vocab_off, const uint32_t *vocab_ids,
+                           uint32_t n_vocab, const uint8_t *merge_bytes, const uint64_t *merge_off, uint32_t n_merges,
+                           const uint8_t *special_bytes, const uint32_t *special_off, uint32_t n_special, uint32_t unk_id);
+/* Encodes n_docs documents: document d = text[doc_off[d], doc_off[d + 1]) (the last one ends at n_bytes; doc_off[0] = 0,
+ * ascending; text host or device memory), each exactly as a separate BBPETokenizer.encode call would.  Results (device
+ * memory owned by the library, released by yabpe_encode_free, the next yabpe_encode or yabpe_destroy): *out_dev_ids =
+ * *out_n_ids u32 ids, *out_dev_doc_off = n_docs + 1 offsets into them.  Malformed UTF-8: YABPE_E_UTF8 and *out_bad_pos =
+ * UnicodeDecodeError.start of the whole text.  More than 2^32 - 1 pre-tokens in one call: YABPE_E_CAPACITY. */
+int yabpe_encode(yabpe_ctx *ctx, const uint8_t *text, uint64_t n_bytes, const uint64_t *doc_off, uint32_t n_docs,
+                 uint32_t **out_dev_ids, uint64_t **out_dev_doc_off, uint64_t *out_n_ids, int64_t *out_bad_pos);
+int yabpe_encode_free(yabpe_ctx *ctx);
+/* What the last yabpe_encode saw, and the device time of its phases (HIP events around each phase's launches). */
+typedef struct yabpe_encode_stats_t {
+    uint64_t n_bytes, n_docs;
+    uint64_t n_pretokens;      /* pre-tokens, specials included */
+    uint64_t n_unique;         /* unique pre-tokens (pooled words) */
+    uint64_t n_unique_long;    /* ... of them longer than 64 bytes (the sequential path) */
+    uint64_t n_specials;       /* special-token occurrences taken */
+    uint64_t n_ids;
+    double split_ms;           /* special split + UTF-8 check + pre-token starts */
+    double pretok_ms;          /* starts -> pre-token offsets */
+    double pool_ms;            /* pre-tokens -> unique words */
+    double words_ms;           /* merges of every unique word */
+    double emit_ms;            /* ids and document offsets */
+    double total_ms;           /* first to last event, host gaps in between included */
+} yabpe_encode_stats_t;
+int yabpe_encode_stats(yabpe_ctx *ctx, yabpe_encode_stats_t *out);
+/* Debug: yabpe_stream_checksum's fold (FNV over each word's token bytes with the 0x1ff boundary, mixed, summed) over the
+ * last yabpe_encode's pre-tokens, specials excluded, that end as at least 2 tokens (the words a flat training stream still
+ * holds), plus the number of those pre-tokens and of their tokens. */
+int yabpe_encode_checksum(yabpe_ctx *ctx, uint64_t *out_sum, uint64_t *out_words, uint64_t *out_tokens);
+
 /* Multi-GPU (one process per GPU; words are sharded by the caller) -----------------
  * Every rank holds its shard of the words and a replica of the pair table.  After each apply pass the ranks
  * exchange their aggregated (pair, delta) records with ONE all-gather on the compute stream and every rank adds all

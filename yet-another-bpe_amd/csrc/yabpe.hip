@@ -25,6 +25,7 @@
 #include "yabpe_kernels.h"
 #include "yabpe_aux_kernels.h"
 #include "yabpe_pretok_kernels.h"
+#include "yabpe_encode_kernels.h"
 #include "unicode_classes.inc"
 
 using namespace yb;
@@ -141,6 +142,21 @@ struct yabpe_ctx {
     std::vector<void *> synth_bufs;
     std::vector<void *> pretok_bufs;          // staged text / word offsets handed out by yabpe_pretokenize
     uint8_t *pt_cls = nullptr;                // class per code point (unicode_classes.inc expanded), built on first use
+    // encoder (yabpe_encode_set_model / yabpe_encode)
+    bool have_enc_model = false;
+    unsigned long long *enc_keys = nullptr;   // pair table: (a << 32 | b) -> enc_vals (rank, result)
+    uint32_t *enc_vals = nullptr;
+    unsigned long long enc_mask = 0;
+    uint32_t *enc_out_id = nullptr;           // internal id -> output id
+    uint8_t *enc_sp_bytes = nullptr, *enc_sp_has = nullptr;
+    uint32_t *enc_sp_off = nullptr, *enc_sp_id = nullptr;
+    uint32_t enc_n_special = 0, enc_sp_max_len = 0;
+    uint32_t *enc_ids = nullptr;              // results of the last yabpe_encode
+    unsigned long long *enc_doc = nullptr;
+    yabpe_encode_stats_t enc_stats{};
+    unsigned long long enc_sums[4] = {0, 0, 0, 0};  // checksum, words, tokens, specials taken
+    bool enc_done = false;
+    hipEvent_t enc_ev[8] = {};
     // misc device scratch
     unsigned long long *scratch64 = nullptr;  // 16 x u64: [0] live sum [1] freq overflow [2,3] long words [4,5,6] verify/checksum
                                               // [7] comm_max [8] exchange record count [9] local count-table entries [10..12] comm_max3
@@ -898,8 +914,38 @@ int retile_flat(yabpe_ctx *c) {
 
 }  // namespace
 
+namespace {
+// The device buffers of one yabpe_encode call (released on every way out).
+struct EncScratch {
+    std::vector<void *> bufs;
+    template <class T>
+    int get(yabpe_ctx *c, T **p, uint64_t n) {
+        TRY(dmalloc(c, p, n));
+        bufs.push_back(*p);
+        return 0;
+    }
+    ~EncScratch() {
+        for (void *p : bufs) dfree(p);
+    }
+};
+}  // namespace
+
 // =================================================================================================== C ABI
 extern "C" {
+
+// the class per code point of the pre-tokeniser (unicode_classes.inc expanded), built on first use
+static int class_table(yabpe_ctx *c) {
+    if (c->pt_cls) return 0;
+    std::vector<uint8_t> cls(0x110000, PT_O);
+    for (unsigned r = 0; r < YB_UNICODE_CLASS_NRUNS; ++r) {
+        const unsigned lo = YB_UNICODE_CLASS_RUNS[r][0];
+        const unsigned hi = r + 1 < YB_UNICODE_CLASS_NRUNS ? YB_UNICODE_CLASS_RUNS[r + 1][0] : 0x110000;
+        memset(cls.data() + lo, (int)YB_UNICODE_CLASS_RUNS[r][1], hi - lo);
+    }
+    TRY(dmalloc(c, &c->pt_cls, cls.size()));
+    HIPCHK(c, hipMemcpy(c->pt_cls, cls.data(), cls.size(), hipMemcpyHostToDevice));
+    return 0;
+}
 
 int yabpe_abi_version(void) { return YABPE_ABI_VERSION; }
 
@@ -967,6 +1013,11 @@ void yabpe_destroy(yabpe_ctx *c) {
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     yabpe_synth_free(c);
     yabpe_pretokenize_free(c);
+    yabpe_encode_free(c);
+    dfree(c->enc_keys); dfree(c->enc_vals); dfree(c->enc_out_id);
+    dfree(c->enc_sp_bytes); dfree(c->enc_sp_has); dfree(c->enc_sp_off); dfree(c->enc_sp_id);
+    for (auto &e : c->enc_ev)
+        if (e) (void)hipEventDestroy(e);
     dfree(c->pt_cls);
     free_corpus(c);
     free_records(c);
@@ -2260,16 +2311,7 @@ int yabpe_pretokenize(yabpe_ctx *c, const uint8_t *text, uint64_t n_bytes, const
     } else {
         chunks.push_back(0);
     }
-    if (!c->pt_cls) {  // expand the generated runs into one byte per code point
-        std::vector<uint8_t> cls(0x110000, PT_O);
-        for (unsigned r = 0; r < YB_UNICODE_CLASS_NRUNS; ++r) {
-            const unsigned lo = YB_UNICODE_CLASS_RUNS[r][0];
-            const unsigned hi = r + 1 < YB_UNICODE_CLASS_NRUNS ? YB_UNICODE_CLASS_RUNS[r + 1][0] : 0x110000;
-            memset(cls.data() + lo, (int)YB_UNICODE_CLASS_RUNS[r][1], hi - lo);
-        }
-        TRY(dmalloc(c, &c->pt_cls, cls.size()));
-        HIPCHK(c, hipMemcpy(c->pt_cls, cls.data(), cls.size(), hipMemcpyHostToDevice));
-    }
+    TRY(class_table(c));
     // inputs on the device
     const uint8_t *d_text = text;
     void *own_text = nullptr;
@@ -2314,6 +2356,272 @@ int yabpe_pretokenize_free(yabpe_ctx *c) {
     if (!c) return YABPE_E_INVALID;
     for (void *p : c->pretok_bufs) dfree(p);
     c->pretok_bufs.clear();
+    return YABPE_OK;
+}
+
+// ---------------------------------------------------------------------------------------------- encoder
+int yabpe_encode_set_model(yabpe_ctx *c, const uint8_t *vocab_bytes, const uint64_t *vocab_off, const uint32_t *vocab_ids, uint32_t n_vocab,
+                           const uint8_t *merge_bytes, const uint64_t *merge_off, uint32_t n_merges, const uint8_t *special_bytes,
+                           const uint32_t *special_off, uint32_t n_special, uint32_t unk_id) {
+    if (!c) return YABPE_E_INVALID;
+    if ((n_vocab && (!vocab_bytes || !vocab_off || !vocab_ids)) || (n_merges && (!merge_bytes || !merge_off)) ||
+        (n_special && (!special_bytes || !special_off)))
+        return fail(c, YABPE_E_INVALID, "model arrays are NULL");
+    HIPCHK(c, hipSetDevice(c->device));
+    EncModelHost m;
+    const int r = enc_build_model(vocab_bytes, vocab_off, vocab_ids, n_vocab, merge_bytes, merge_off, n_merges, special_bytes, special_off,
+                                  n_special, unk_id, &m);
+    if (r == -1) return fail(c, YABPE_E_INVALID, "a special token is empty (it would match at every position)");
+    if (r != 0) return fail(c, YABPE_E_CAPACITY, "at most %u special tokens and 2^32 - 2 interned byte strings", ENC_MAX_SPECIALS);
+    c->have_enc_model = false;
+    dfree(c->enc_keys); dfree(c->enc_vals); dfree(c->enc_out_id);
+    dfree(c->enc_sp_bytes); dfree(c->enc_sp_has); dfree(c->enc_sp_off); dfree(c->enc_sp_id);
+    c->enc_keys = nullptr; c->enc_vals = nullptr; c->enc_out_id = nullptr;
+    c->enc_sp_bytes = nullptr; c->enc_sp_has = nullptr; c->enc_sp_off = nullptr; c->enc_sp_id = nullptr;
+    TRY(dmalloc(c, &c->enc_keys, m.keys.size()));
+    TRY(dmalloc(c, &c->enc_vals, m.vals.size()));
+    TRY(dmalloc(c, &c->enc_out_id, m.out_id.size()));
+    HIPCHK(c, hipMemcpy(c->enc_keys, m.keys.data(), m.keys.size() * 8, hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(c->enc_vals, m.vals.data(), m.vals.size() * 4, hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(c->enc_out_id, m.out_id.data(), m.out_id.size() * 4, hipMemcpyHostToDevice));
+    c->enc_mask = m.keys.size() - 1;
+    c->enc_n_special = n_special;
+    c->enc_sp_max_len = 0;
+    if (n_special) {
+        for (uint32_t s = 0; s < n_special; ++s) c->enc_sp_max_len = std::max(c->enc_sp_max_len, special_off[s + 1] - special_off[s]);
+        TRY(dmalloc(c, &c->enc_sp_bytes, special_off[n_special]));
+        TRY(dmalloc(c, &c->enc_sp_off, n_special + 1));
+        TRY(dmalloc(c, &c->enc_sp_id, n_special));
+        TRY(dmalloc(c, &c->enc_sp_has, n_special));
+        HIPCHK(c, hipMemcpy(c->enc_sp_bytes, special_bytes, special_off[n_special], hipMemcpyHostToDevice));
+        HIPCHK(c, hipMemcpy(c->enc_sp_off, special_off, (n_special + 1) * 4, hipMemcpyHostToDevice));
+        HIPCHK(c, hipMemcpy(c->enc_sp_id, m.sp_id.data(), n_special * 4, hipMemcpyHostToDevice));
+        HIPCHK(c, hipMemcpy(c->enc_sp_has, m.sp_has.data(), n_special, hipMemcpyHostToDevice));
+    }
+    c->have_enc_model = true;
+    return YABPE_OK;
+}
+
+int yabpe_encode_free(yabpe_ctx *c) {
+    if (!c) return YABPE_E_INVALID;
+    dfree(c->enc_ids);
+    dfree(c->enc_doc);
+    c->enc_ids = nullptr;
+    c->enc_doc = nullptr;
+    return YABPE_OK;
+}
+
+int yabpe_encode(yabpe_ctx *c, const uint8_t *text, uint64_t n_bytes, const uint64_t *doc_off, uint32_t n_docs, uint32_t **out_dev_ids,
+                 uint64_t **out_dev_doc_off, uint64_t *out_n_ids, int64_t *out_bad_pos) {
+    if (!c || !out_dev_ids || !out_dev_doc_off || !out_n_ids || !out_bad_pos) return YABPE_E_INVALID;
+    HIPCHK(c, hipSetDevice(c->device));
+    *out_dev_ids = nullptr; *out_dev_doc_off = nullptr; *out_n_ids = 0; *out_bad_pos = -1;
+    if (!c->have_enc_model) return fail(c, YABPE_E_INVALID, "no model: call yabpe_encode_set_model first");
+    if (n_bytes && !text) return fail(c, YABPE_E_INVALID, "text is NULL");
+    if (!doc_off || !n_docs || doc_off[0] != 0) return fail(c, YABPE_E_INVALID, "doc_off must hold n_docs >= 1 starts, the first one 0");
+    for (uint32_t d = 1; d < n_docs; ++d)
+        if (doc_off[d] < doc_off[d - 1] || doc_off[d] > n_bytes) return fail(c, YABPE_E_INVALID, "document starts must ascend inside the text");
+    yabpe_encode_free(c);
+    c->enc_done = false;
+    c->enc_stats = yabpe_encode_stats_t{};
+    c->enc_stats.n_bytes = n_bytes;
+    c->enc_stats.n_docs = n_docs;
+    TRY(class_table(c));
+    for (auto &e : c->enc_ev)
+        if (!e) HIPCHK(c, hipEventCreate(&e));
+    hipStream_t s = c->stream;
+    const unsigned long long n = n_bytes;
+    EncScratch S;
+    // inputs on the device
+    const uint8_t *d_text = text;
+    if (n && !is_device_ptr(text)) {
+        uint8_t *own = nullptr;
+        TRY(S.get(c, &own, n));
+        HIPCHK(c, hipMemcpy(own, text, n, hipMemcpyHostToDevice));
+        d_text = own;
+    }
+    unsigned long long *d_docs = nullptr;
+    TRY(S.get(c, &d_docs, n_docs));
+    HIPCHK(c, hipMemcpy(d_docs, doc_off, (size_t)n_docs * 8, hipMemcpyHostToDevice));
+    TRY(dmalloc(c, &c->enc_doc, (uint64_t)n_docs + 1));
+    unsigned long long *doc_ids = (unsigned long long *)c->enc_doc;
+    if (n == 0) { // every document is empty
+        HIPCHK(c, hipMemsetAsync(doc_ids, 0, ((size_t)n_docs + 1) * 8, s));
+        TRY(dmalloc(c, &c->enc_ids, 1));
+        HIPCHK(c, hipStreamSynchronize(s));
+        c->enc_sums[0] = c->enc_sums[1] = c->enc_sums[2] = c->enc_sums[3] = 0;
+        c->enc_done = true;
+        *out_dev_ids = c->enc_ids;
+        *out_dev_doc_off = (uint64_t *)c->enc_doc;
+        return YABPE_OK;
+    }
+    const uint32_t grid = (uint32_t)std::min<unsigned long long>((n + BLOCK - 1) / BLOCK, 1u << 20);
+    // ---- split: document marks, the special split, classes / UTF-8 / pre-token starts
+    uint8_t *meta = nullptr, *flags = nullptr, *sflag = nullptr;
+    unsigned long long *err = nullptr;
+    TRY(S.get(c, &meta, n));
+    TRY(S.get(c, &flags, n + 8));
+    TRY(S.get(c, &err, 1));
+    if (c->enc_n_special) TRY(S.get(c, &sflag, n));
+    HIPCHK(c, hipEventRecord(c->enc_ev[0], s));
+    HIPCHK(c, hipMemsetAsync(meta, 0, n, s));
+    HIPCHK(c, hipMemsetAsync(err, 0xff, 8, s));
+    hipLaunchKernelGGL(k_pt_mark_chunks, dim3((n_docs + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, s, meta, d_docs, n_docs, n);
+    const PtSpecials sp{c->enc_sp_bytes, c->enc_sp_off, c->enc_n_special, c->enc_sp_max_len};
+    if (sflag) {
+        HIPCHK(c, hipMemsetAsync(sflag, 0, n, s));
+        hipLaunchKernelGGL(k_enc_special, dim3(grid), dim3(BLOCK), 0, s, d_text, meta, n, sp, sflag);
+        hipLaunchKernelGGL(k_enc_segments, dim3(grid), dim3(BLOCK), 0, s, sflag, n, meta);
+    }
+    PretokParams P{d_text, meta, flags, n, c->pt_cls, err, PtSpecials{nullptr, nullptr, 0, 0}};
+    const uint32_t wgrid = (uint32_t)std::min<unsigned long long>((n + PT_WIN - 1) / PT_WIN, 1u << 20);
+    hipLaunchKernelGGL(k_pt_fused, dim3(wgrid), dim3(BLOCK), 0, s, P);
+    if (sflag) hipLaunchKernelGGL(k_enc_clear, dim3(grid), dim3(BLOCK), 0, s, sflag, n, flags);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipEventRecord(c->enc_ev[1], s));
+    unsigned long long h_err = 0;
+    HIPCHK(c, hipMemcpyAsync(&h_err, err, 8, hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipStreamSynchronize(s));
+    if (h_err != ~0ull) {
+        *out_bad_pos = (int64_t)h_err;
+        return fail(c, YABPE_E_UTF8, "invalid UTF-8 at byte %llu", h_err);
+    }
+    // ---- pre-token offsets
+    const unsigned long long nb = (n + PT_PER_BLOCK - 1) / PT_PER_BLOCK;
+    unsigned long long *sums = nullptr, *bases = nullptr, *off = nullptr;
+    TRY(S.get(c, &sums, nb));
+    TRY(S.get(c, &bases, nb + 1));
+    hipLaunchKernelGGL(k_pt_count, dim3((uint32_t)nb), dim3(BLOCK), 0, s, flags, n, sums);
+    HIPCHK(c, hipGetLastError());
+    if (exclusive_scan<unsigned long long>(s, sums, nb, bases, nb + 1) != 0) return fail(c, YABPE_E_HIP, "scan of the start counts failed");
+    unsigned long long n_pre = 0;
+    HIPCHK(c, hipMemcpyAsync(&n_pre, bases + nb, 8, hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipStreamSynchronize(s));
+    if (n_pre > 0xFFFFFFFEull) return fail(c, YABPE_E_CAPACITY, "%llu pre-tokens in one call: at most 2^32 - 2", n_pre);
+    TRY(S.get(c, &off, n_pre + 1));
+    hipLaunchKernelGGL(k_pt_scatter, dim3((uint32_t)nb), dim3(BLOCK), 0, s, flags, n, bases, off);
+    HIPCHK(c, hipMemcpyAsync(off + n_pre, &n, 8, hipMemcpyHostToDevice, s));
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipEventRecord(c->enc_ev[2], s));
+    // ---- pooling: each pre-token's representative, the list of unique words
+    unsigned long long cap = 1024;
+    while (cap < n_pre * 2) cap <<= 1;
+    unsigned long long *hash = nullptr, *count = nullptr, *uidx = nullptr, *uoff = nullptr;
+    uint32_t *slots = nullptr, *rep = nullptr, *flag = nullptr, *ulen = nullptr;
+    TRY(S.get(c, &hash, n_pre));
+    TRY(S.get(c, &count, n_pre));
+    TRY(S.get(c, &slots, cap));
+    TRY(S.get(c, &rep, n_pre));
+    TRY(S.get(c, &flag, n_pre));
+    TRY(S.get(c, &ulen, n_pre));
+    TRY(S.get(c, &uidx, n_pre + 1));
+    TRY(S.get(c, &uoff, n_pre + 1));
+    const uint32_t pgrid = (uint32_t)((n_pre + 255) / 256);
+    HIPCHK(c, hipMemsetAsync(slots, 0xFF, cap * 4, s));
+    HIPCHK(c, hipMemsetAsync(count, 0, n_pre * 8, s));
+    hipLaunchKernelGGL(k_word_hash, dim3(pgrid), dim3(256), 0, s, d_text, off, n_pre, hash);
+    hipLaunchKernelGGL(k_word_dedup, dim3(pgrid), dim3(256), 0, s, d_text, off, (const unsigned long long *)nullptr, n_pre, hash, slots, cap - 1,
+                       rep, count);
+    hipLaunchKernelGGL(k_dedup_flags, dim3(pgrid), dim3(256), 0, s, rep, off, n_pre, flag, ulen);
+    HIPCHK(c, hipGetLastError());
+    if (exclusive_scan<uint32_t>(s, flag, n_pre, uidx, n_pre + 1) != 0 || exclusive_scan<uint32_t>(s, ulen, n_pre, uoff, n_pre + 1) != 0)
+        return fail(c, YABPE_E_HIP, "scan of the unique words failed");
+    unsigned long long nu_tb[2] = {0, 0};
+    HIPCHK(c, hipMemcpyAsync(&nu_tb[0], uidx + n_pre, 8, hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipMemcpyAsync(&nu_tb[1], uoff + n_pre, 8, hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipStreamSynchronize(s));
+    const unsigned long long nu = nu_tb[0], ubytes = nu_tb[1];
+    uint32_t *ulist = nullptr, *llen = nullptr, *uids = nullptr;
+    unsigned long long *lbase = nullptr;
+    TRY(S.get(c, &ulist, nu));
+    TRY(S.get(c, &llen, nu));
+    TRY(S.get(c, &lbase, nu + 1));
+    TRY(S.get(c, &uids, ubytes));
+    hipLaunchKernelGGL(k_enc_compact, dim3(pgrid), dim3(256), 0, s, flag, uidx, off, n_pre, ulist, llen);
+    HIPCHK(c, hipGetLastError());
+    if (exclusive_scan<uint32_t>(s, llen, nu, lbase, nu + 1) != 0) return fail(c, YABPE_E_HIP, "scan of the long words failed");
+    unsigned long long lbytes = 0;
+    HIPCHK(c, hipMemcpyAsync(&lbytes, lbase + nu, 8, hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipEventRecord(c->enc_ev[3], s));
+    HIPCHK(c, hipStreamSynchronize(s));
+    // ---- the merges of every unique word (flag is free again: it becomes the per-word id count)
+    uint32_t *ltok = nullptr, *lnxt = nullptr, *lprv = nullptr;
+    unsigned long long *lheap = nullptr, *wsums = nullptr;
+    TRY(S.get(c, &ltok, lbytes));
+    TRY(S.get(c, &lnxt, lbytes));
+    TRY(S.get(c, &lprv, lbytes));
+    TRY(S.get(c, &lheap, 3 * lbytes));
+    TRY(S.get(c, &wsums, 4));
+    HIPCHK(c, hipMemsetAsync(wsums, 0, 32, s));
+    HIPCHK(c, hipEventRecord(c->enc_ev[4], s));  // (the words phase starts here: the scratch allocation above is host work)
+    EncWordsParams W{d_text, off, ulist, nu, uoff, lbase, count, sflag, EncTable{c->enc_keys, c->enc_vals, c->enc_mask}, c->enc_out_id,
+                     c->enc_sp_id, c->enc_sp_has, flag, uids, ltok, lnxt, lprv, lheap, wsums};
+    const uint32_t wg = (uint32_t)std::max<unsigned long long>(1, std::min<unsigned long long>((nu + WPB - 1) / WPB, (unsigned long long)c->n_cu * 8));
+    hipLaunchKernelGGL(k_enc_words, dim3(wg), dim3(BLOCK), 0, s, W);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipEventRecord(c->enc_ev[5], s));
+    // ---- emission: per pre-token count -> id offsets -> ids; per-document offsets
+    unsigned long long *id_off = nullptr;
+    TRY(S.get(c, &id_off, n_pre + 1));
+    HIPCHK(c, hipEventRecord(c->enc_ev[6], s));
+    hipLaunchKernelGGL(k_enc_count, dim3(pgrid), dim3(256), 0, s, rep, flag, n_pre, ulen);
+    HIPCHK(c, hipGetLastError());
+    if (exclusive_scan<uint32_t>(s, ulen, n_pre, id_off, n_pre + 1) != 0) return fail(c, YABPE_E_HIP, "scan of the id counts failed");
+    unsigned long long n_ids = 0;
+    HIPCHK(c, hipMemcpyAsync(&n_ids, id_off + n_pre, 8, hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipMemcpyAsync(c->enc_sums, wsums, 32, hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipStreamSynchronize(s));
+    TRY(dmalloc(c, &c->enc_ids, n_ids));
+    hipLaunchKernelGGL(k_enc_emit, dim3(pgrid), dim3(256), 0, s, rep, uoff, uids, id_off, n_pre, c->enc_ids);
+    hipLaunchKernelGGL(k_enc_docs, dim3((n_docs + 1 + 255) / 256), dim3(256), 0, s, d_docs, n_docs, n, off, n_pre, id_off, doc_ids);
+    (void)hipEventRecord(c->enc_ev[7], s);
+    const hipError_t le = hipGetLastError();
+    const hipError_t se = hipStreamSynchronize(s);
+    float ms[6] = {0, 0, 0, 0, 0, 0};
+    if (le == hipSuccess && se == hipSuccess) {
+        (void)hipEventElapsedTime(&ms[0], c->enc_ev[0], c->enc_ev[1]);
+        (void)hipEventElapsedTime(&ms[1], c->enc_ev[1], c->enc_ev[2]);
+        (void)hipEventElapsedTime(&ms[2], c->enc_ev[2], c->enc_ev[3]);
+        (void)hipEventElapsedTime(&ms[3], c->enc_ev[4], c->enc_ev[5]);
+        (void)hipEventElapsedTime(&ms[4], c->enc_ev[6], c->enc_ev[7]);
+        (void)hipEventElapsedTime(&ms[5], c->enc_ev[0], c->enc_ev[7]);
+    }
+    if (le != hipSuccess || se != hipSuccess) return fail(c, YABPE_E_HIP, "encoder kernels failed: %s", hipGetErrorString(le != hipSuccess ? le : se));
+    auto &st = c->enc_stats;
+    st.n_pretokens = n_pre;
+    st.n_unique = nu;
+    st.n_ids = n_ids;
+    st.split_ms = ms[0];
+    st.pretok_ms = ms[1];
+    st.pool_ms = ms[2];
+    st.words_ms = ms[3];
+    st.emit_ms = ms[4];
+    st.total_ms = ms[5];
+    {   // counts for the statistics: long unique words and the specials taken (small host reads)
+        std::vector<uint32_t> h_llen(nu);
+        if (nu) HIPCHK(c, hipMemcpy(h_llen.data(), llen, nu * 4, hipMemcpyDeviceToHost));
+        for (uint32_t x : h_llen) st.n_unique_long += x ? 1 : 0;
+        st.n_specials = c->enc_sums[3];
+    }
+    c->enc_done = true;
+    *out_dev_ids = c->enc_ids;
+    *out_dev_doc_off = (uint64_t *)c->enc_doc;
+    *out_n_ids = n_ids;
+    return YABPE_OK;
+}
+
+int yabpe_encode_stats(yabpe_ctx *c, yabpe_encode_stats_t *out) {
+    if (!c || !out) return YABPE_E_INVALID;
+    *out = c->enc_stats;
+    return YABPE_OK;
+}
+
+int yabpe_encode_checksum(yabpe_ctx *c, uint64_t *out_sum, uint64_t *out_words, uint64_t *out_tokens) {
+    if (!c) return YABPE_E_INVALID;
+    if (!c->enc_done) return fail(c, YABPE_E_INVALID, "no encode has completed on this context");
+    if (out_sum) *out_sum = c->enc_sums[0];
+    if (out_words) *out_words = c->enc_sums[1];
+    if (out_tokens) *out_tokens = c->enc_sums[2];
     return YABPE_OK;
 }
 

@@ -46,6 +46,11 @@ class Stats(ctypes.Structure):
         ("dense_launches", c_uint64), ("dense_merges", c_uint64)]
 
 
+class EncodeStats(ctypes.Structure):
+    _fields_ = [(n, c_uint64) for n in ("n_bytes", "n_docs", "n_pretokens", "n_unique", "n_unique_long", "n_specials", "n_ids")] + [
+        (n, c_double) for n in ("split_ms", "pretok_ms", "pool_ms", "words_ms", "emit_ms", "total_ms")]
+
+
 class Latency(ctypes.Structure):
     _fields_ = [(n, c_double) for n in ("launch_gap_us", "load_trip_us", "coherent_trip_us", "atomic_trip_us")]
 
@@ -61,6 +66,7 @@ SYMBOLS = [
     "yabpe_iter_log", "yabpe_event_log", "yabpe_latency_probe", "yabpe_verify_table", "yabpe_stream_checksum", "yabpe_synth_generate", "yabpe_synth_generate_lex", "yabpe_synth_free",
     "yabpe_memcpy_d2h", "yabpe_memcpy_h2d", "yabpe_pretokenize", "yabpe_pretokenize_free",
     "yabpe_comm_unique_id", "yabpe_comm_init", "yabpe_comm_init_custom", "yabpe_comm_enable_p2p",
+    "yabpe_encode_set_model", "yabpe_encode", "yabpe_encode_free", "yabpe_encode_stats", "yabpe_encode_checksum",
 ]
 
 
@@ -104,6 +110,13 @@ def lib() -> ctypes.CDLL:
         L.yabpe_comm_init.argtypes = [c_void_p, c_int, c_int, c_void_p]
         L.yabpe_comm_init_custom.argtypes = [c_void_p, c_int, c_int, ALLGATHER_FN, c_void_p]
         L.yabpe_comm_enable_p2p.argtypes = [c_void_p]
+        L.yabpe_encode_set_model.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_uint32, c_void_p, c_void_p, c_uint32,
+                                             c_void_p, c_void_p, c_uint32, c_uint32]
+        L.yabpe_encode.argtypes = [c_void_p, c_void_p, c_uint64, c_void_p, c_uint32, POINTER(c_void_p), POINTER(c_void_p),
+                                   POINTER(c_uint64), POINTER(ctypes.c_int64)]
+        L.yabpe_encode_free.argtypes = [c_void_p]
+        L.yabpe_encode_stats.argtypes = [c_void_p, POINTER(EncodeStats)]
+        L.yabpe_encode_checksum.argtypes = [c_void_p, POINTER(c_uint64), POINTER(c_uint64), POINTER(c_uint64)]
         if L.yabpe_abi_version() != 2:
             raise ImportError("libyabpe.so ABI version mismatch")
         _lib = L
@@ -289,6 +302,53 @@ class Context:
     def pretokenize_free(self) -> None:
         self._chk(lib().yabpe_pretokenize_free(self._h))
 
+    # -- encoding with a trained model (BBPETokenizer.encode on the device)
+    def encode_set_model(self, vocab: dict, merges, specials_ordered, unk_id: int) -> None:
+        """vocab {bytes: id}, merges [(bytes, bytes)] in order, specials in the tokenizer's order (longest first)."""
+        a = encode_model_arrays(vocab, merges, specials_ordered)
+        self._enc_model = a  # (the library copies; kept only for the duration of the call)
+        self._chk(lib().yabpe_encode_set_model(self._h, a["vb"].ctypes.data, a["vo"].ctypes.data, a["vi"].ctypes.data, len(a["vi"]),
+                                               a["mb"].ctypes.data, a["mo"].ctypes.data, len(a["mo"]) // 2, a["sb"].ctypes.data,
+                                               a["so"].ctypes.data, len(a["so"]) - 1, int(unk_id)))
+
+    def encode(self, text, n_bytes: int | None = None, doc_starts=None):
+        """text: bytes / u8 array (staged) or a device address (n_bytes required); doc_starts: ascending document starts, the
+        first one 0.  -> (dev_ids_ptr u32, dev_doc_off_ptr u64[n_docs + 1], n_ids); the buffers live until the next encode,
+        encode_free() or close().  Raises Utf8Error(position) on malformed UTF-8."""
+        keep = None
+        if isinstance(text, int):
+            ptr, n = c_void_p(text), int(n_bytes)
+        else:
+            keep = np.frombuffer(text, dtype=np.uint8) if not isinstance(text, np.ndarray) else np.ascontiguousarray(text, dtype=np.uint8)
+            ptr, n = c_void_p(keep.ctypes.data if keep.size else 0), int(keep.size)
+        docs = np.ascontiguousarray(doc_starts if doc_starts is not None and len(doc_starts) else [0], dtype=np.uint64)
+        di, dd, ni, bad = c_void_p(), c_void_p(), c_uint64(0), ctypes.c_int64(-1)
+        rc = lib().yabpe_encode(self._h, ptr, n, docs.ctypes.data, len(docs), byref(di), byref(dd), byref(ni), byref(bad))
+        if rc == E_UTF8:
+            raise Utf8Error(bad.value)
+        self._chk(rc)
+        return di.value or 0, dd.value, ni.value
+
+    def encode_to_host(self, text, n_bytes: int | None = None, doc_starts=None):
+        """-> (ids u32[n_ids], doc_off u64[n_docs + 1]) copied to the host."""
+        n_docs = len(doc_starts) if doc_starts is not None and len(doc_starts) else 1
+        di, dd, ni = self.encode(text, n_bytes, doc_starts)
+        ids = self.d2h(di, 4 * ni, np.uint32) if ni else np.zeros(0, np.uint32)
+        return ids, self.d2h(dd, 8 * (n_docs + 1), np.uint64)
+
+    def encode_free(self) -> None:
+        self._chk(lib().yabpe_encode_free(self._h))
+
+    def encode_stats(self) -> dict:
+        s = EncodeStats()
+        self._chk(lib().yabpe_encode_stats(self._h, byref(s)))
+        return {f: getattr(s, f) for f, _ in EncodeStats._fields_}
+
+    def encode_checksum(self) -> tuple[int, int, int]:
+        a, b, c = c_uint64(0), c_uint64(0), c_uint64(0)
+        self._chk(lib().yabpe_encode_checksum(self._h, byref(a), byref(b), byref(c)))
+        return a.value, b.value, c.value
+
     def h2d(self, dev_ptr: int, arr: np.ndarray) -> None:
         arr = np.ascontiguousarray(arr)
         self._chk(lib().yabpe_memcpy_h2d(self._h, c_void_p(dev_ptr), arr.ctypes.data, arr.nbytes))
@@ -328,6 +388,24 @@ class Context:
         out = np.empty(nbytes // np.dtype(dtype).itemsize, dtype=dtype)
         self._chk(lib().yabpe_memcpy_d2h(self._h, out.ctypes.data, c_void_p(dev_ptr), nbytes))
         return out
+
+
+def encode_model_arrays(vocab: dict, merges, specials_ordered) -> dict:
+    """The flat arrays of yabpe_encode_set_model: vocab bytes / u64 offsets / u32 ids, merges as 2 n + 1 u64 offsets
+    (left, right, left, right ...), specials' bytes / u32 offsets."""
+    def flat(items, dtype):
+        blob = np.frombuffer(b"".join(items) or b"\0", dtype=np.uint8).copy()
+        off = np.zeros(len(items) + 1, dtype=dtype)
+        if items:
+            off[1:] = np.cumsum([len(x) for x in items])
+        return blob, off
+
+    toks = list(vocab)
+    vb, vo = flat(toks, np.uint64)
+    vi = np.asarray([vocab[t] for t in toks] or [0], dtype=np.uint32)[:len(toks)]
+    mb, mo = flat([x for pair in merges for x in pair], np.uint64)
+    sb, so = flat([t.encode("utf-8") if isinstance(t, str) else bytes(t) for t in specials_ordered], np.uint32)
+    return {"vb": vb, "vo": vo, "vi": np.ascontiguousarray(vi), "mb": mb, "mo": mo, "sb": sb, "so": so}
 
 
 def train_words(words_flat, words_off, freq, base_tokens: list[bytes], num_merges: int, min_frequency: int,

@@ -2,8 +2,8 @@
 
 Plain Python, same public API as the reference `src/yet_another_bpe/tokenizer.py:35-398`
 (encode, decode, encode_batch, decode_batch, from_file, vocab_size, special_tokens, get_vocab,
-clear_cache, cache_info, _encode_word).  Inference is outside the accelerated hot path (SURVEY.md §8f-3);
-this module exists so that models trained on the GPU can be used and round-tripped.
+clear_cache, cache_info, _encode_word).  encode / encode_batch stay plain Python;
+encode_array / encode_batch_device compute the same ids on the GPU (yabpe_encode, include/yabpe.h).
 """
 from __future__ import annotations
 
@@ -12,6 +12,7 @@ from collections.abc import Sequence
 from functools import lru_cache
 from pathlib import Path
 
+import numpy as np
 import regex
 
 _GPT2_SPLIT = r"""'(?:[sdmt]|ll|ve|re)| ?\p{L}+| ?\p{N}+| ?[^\s\p{L}\p{N}]+|\s+(?!\S)|\s+"""
@@ -36,6 +37,7 @@ class BBPETokenizer:
             ordered = sorted(self._special_tokens, key=len, reverse=True)
             self._special_pattern = regex.compile("(" + "|".join(regex.escape(t) for t in ordered) + ")")
         self._word_ids = lru_cache(maxsize=_WORD_CACHE)(self._word_ids_uncached)
+        self._device_ctx = None  # created on the first device call (encode_array / encode_batch_device)
 
     # ------------------------------------------------------------------ persistence (tokenizer.py:106-150)
     @classmethod
@@ -123,6 +125,38 @@ class BBPETokenizer:
 
     def encode_batch(self, texts: Sequence[str]) -> list[list[int]]:
         return [self.encode(t) for t in texts]
+
+    # ------------------------------------------------------------------ encode on the GPU (yabpe_encode; same ids as encode)
+    def _device(self):
+        if self._device_ctx is None:
+            from . import _native
+
+            ctx = _native.Context()
+            ordered = sorted(self._special_tokens, key=len, reverse=True)  # the split pattern's order
+            ctx.encode_set_model(self._vocab, self._merges, ordered, self._vocab.get(b"[UNK]", 0))
+            self._device_ctx = ctx
+        return self._device_ctx
+
+    def encode_array(self, texts) -> tuple[np.ndarray, np.ndarray]:
+        """Encodes on the GPU: `texts` is a sequence of str (one document each) or one bytes buffer (one document).
+        -> (ids np.uint32[n], doc_off np.uint64[n_docs + 1]): document d's ids are ids[doc_off[d]:doc_off[d + 1]], equal to
+        encode(texts[d]).  Malformed UTF-8 in a bytes buffer raises _native.Utf8Error (.position = UnicodeDecodeError.start)."""
+        if isinstance(texts, (bytes, bytearray, memoryview)):
+            data, starts = bytes(texts), [0]
+        else:
+            blobs = [t.encode("utf-8") for t in texts]
+            if not blobs:
+                return np.zeros(0, np.uint32), np.zeros(1, np.uint64)
+            data = b"".join(blobs)
+            starts = np.zeros(len(blobs), dtype=np.uint64)
+            starts[1:] = np.cumsum([len(b) for b in blobs], dtype=np.uint64)[:-1]
+        return self._device().encode_to_host(np.frombuffer(data, dtype=np.uint8), doc_starts=starts)
+
+    def encode_batch_device(self, texts: Sequence[str]) -> list[list[int]]:
+        """encode_batch(texts), computed on the GPU in one call."""
+        ids, off = self.encode_array(texts)
+        ids, off = ids.tolist(), off.tolist()
+        return [ids[off[d]:off[d + 1]] for d in range(len(off) - 1)]
 
     # ------------------------------------------------------------------ decode (tokenizer.py:324-349)
     def decode(self, ids: Sequence[int]) -> str:
