@@ -244,6 +244,39 @@ int yabpe_encode_stats(yabpe_ctx *ctx, yabpe_encode_stats_t *out);
  * holds), plus the number of those pre-tokens and of their tokens. */
 int yabpe_encode_checksum(yabpe_ctx *ctx, uint64_t *out_sum, uint64_t *out_words, uint64_t *out_tokens);
 
+/* Decoder (BBPETokenizer.decode on the device, yet_another_bpe/tokenizer.py) ----------------------------------------
+ * The vocab as yabpe_encode_set_model takes it (n_vocab byte strings, vocab_off: n_vocab + 1 offsets, vocab_ids: their ids).
+ * The library keeps a dense table id -> bytes on the device; when two strings share an id the last one wins (decode's
+ * {i: t for t, i in vocab.items()}).  An id above 2^24 - 1 or a vocab of 2^32 - 1 bytes or more: YABPE_E_CAPACITY.
+ * Independent of yabpe_encode_set_model. */
+int yabpe_decode_set_model(yabpe_ctx *ctx, const uint8_t *vocab_bytes, const uint64_t *vocab_off, const uint32_t *vocab_ids,
+                           uint32_t n_vocab);
+/* Decodes n_docs documents: document d = ids[doc_off[d], doc_off[d + 1]) (the last one ends at n_ids; doc_off[0] = 0,
+ * ascending; doc_off == NULL with n_docs <= 1: one document), each exactly as a separate BBPETokenizer.decode call would,
+ * as UTF-8: ids the vocab does not name are skipped, and every maximal subpart of an ill-formed sequence becomes U+FFFD
+ * (errors="replace"; a sequence cut off at a document's end is replaced there).  ids and doc_off may be host or device
+ * memory (yabpe_encode's results can be passed as they are).  Results (device memory owned by the library, released by
+ * yabpe_decode_free, the next yabpe_decode or yabpe_destroy): *out_dev_text = *out_n_bytes bytes, *out_dev_text_off =
+ * n_docs + 1 offsets into them.  No model: YABPE_E_INVALID. */
+int yabpe_decode(yabpe_ctx *ctx, const uint32_t *ids, uint64_t n_ids, const uint64_t *doc_off, uint32_t n_docs,
+                 uint8_t **out_dev_text, uint64_t **out_dev_text_off, uint64_t *out_n_bytes);
+int yabpe_decode_free(yabpe_ctx *ctx);
+/* What the last yabpe_decode saw, and the device time of its phases (HIP events around each phase's launches). */
+typedef struct yabpe_decode_stats_t {
+    uint64_t n_ids, n_docs;
+    uint64_t n_unknown;        /* ids skipped: not in the table */
+    uint64_t n_gathered;       /* bytes of the known ids' tokens */
+    uint64_t n_bytes;          /* bytes out */
+    uint64_t n_replacements;   /* U+FFFD written */
+    uint64_t n_docs_repaired;  /* documents with at least one U+FFFD */
+    double lengths_ms;         /* per-block byte counts + their scan */
+    double gather_ms;          /* token bytes -> text, document offsets */
+    double check_ms;           /* UTF-8 roles and the U+FFFD count */
+    double repair_ms;          /* 0 when the text was valid: scan + rewrite with U+FFFD */
+    double total_ms;           /* first to last event, host gaps in between included */
+} yabpe_decode_stats_t;
+int yabpe_decode_stats(yabpe_ctx *ctx, yabpe_decode_stats_t *out);
+
 /* Multi-GPU (one process per GPU; words are sharded by the caller) -----------------
  * Every rank holds its shard of the words and a replica of the pair table.  After each apply pass the ranks
  * exchange their aggregated (pair, delta) records with ONE all-gather on the compute stream and every rank adds all

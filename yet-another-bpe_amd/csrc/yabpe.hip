@@ -26,6 +26,7 @@
 #include "yabpe_aux_kernels.h"
 #include "yabpe_pretok_kernels.h"
 #include "yabpe_encode_kernels.h"
+#include "yabpe_decode_kernels.h"
 #include "unicode_classes.inc"
 
 using namespace yb;
@@ -157,6 +158,15 @@ struct yabpe_ctx {
     unsigned long long enc_sums[4] = {0, 0, 0, 0};  // checksum, words, tokens, specials taken
     bool enc_done = false;
     hipEvent_t enc_ev[8] = {};
+    // decoder (yabpe_decode_set_model / yabpe_decode)
+    bool have_dec_model = false;
+    uint2 *dec_ent = nullptr;                 // id -> (offset into dec_pool, length)
+    uint8_t *dec_pool = nullptr;
+    uint32_t dec_n = 0;                       // ids in the table
+    uint8_t *dec_text = nullptr;              // results of the last yabpe_decode
+    unsigned long long *dec_doc = nullptr;
+    yabpe_decode_stats_t dec_stats{};
+    hipEvent_t dec_ev[7] = {};
     // misc device scratch
     unsigned long long *scratch64 = nullptr;  // 16 x u64: [0] live sum [1] freq overflow [2,3] long words [4,5,6] verify/checksum
                                               // [7] comm_max [8] exchange record count [9] local count-table entries [10..12] comm_max3
@@ -1017,6 +1027,10 @@ void yabpe_destroy(yabpe_ctx *c) {
     dfree(c->enc_keys); dfree(c->enc_vals); dfree(c->enc_out_id);
     dfree(c->enc_sp_bytes); dfree(c->enc_sp_has); dfree(c->enc_sp_off); dfree(c->enc_sp_id);
     for (auto &e : c->enc_ev)
+        if (e) (void)hipEventDestroy(e);
+    yabpe_decode_free(c);
+    dfree(c->dec_ent); dfree(c->dec_pool);
+    for (auto &e : c->dec_ev)
         if (e) (void)hipEventDestroy(e);
     dfree(c->pt_cls);
     free_corpus(c);
@@ -2622,6 +2636,195 @@ int yabpe_encode_checksum(yabpe_ctx *c, uint64_t *out_sum, uint64_t *out_words, 
     if (out_sum) *out_sum = c->enc_sums[0];
     if (out_words) *out_words = c->enc_sums[1];
     if (out_tokens) *out_tokens = c->enc_sums[2];
+    return YABPE_OK;
+}
+
+// ---------------------------------------------------------------------------------------------- decoder
+int yabpe_decode_set_model(yabpe_ctx *c, const uint8_t *vocab_bytes, const uint64_t *vocab_off, const uint32_t *vocab_ids, uint32_t n_vocab) {
+    if (!c) return YABPE_E_INVALID;
+    if (n_vocab && (!vocab_bytes || !vocab_off || !vocab_ids)) return fail(c, YABPE_E_INVALID, "vocab arrays are NULL");
+    HIPCHK(c, hipSetDevice(c->device));
+    DecTableHost t;
+    const int r = dec_build_table(vocab_off, vocab_ids, n_vocab, &t);
+    if (r == -1) return fail(c, YABPE_E_CAPACITY, "a token id is above %u: the decode table holds ids below 2^24", DEC_MAX_ID);
+    if (r != 0) return fail(c, YABPE_E_CAPACITY, "the vocab holds %llu bytes: the decode table addresses fewer than 2^32 - 1",
+                            (unsigned long long)vocab_off[n_vocab]);
+    c->have_dec_model = false;
+    dfree(c->dec_ent); dfree(c->dec_pool);
+    c->dec_ent = nullptr; c->dec_pool = nullptr;
+    const uint64_t pool_bytes = n_vocab ? vocab_off[n_vocab] : 0;
+    c->dec_n = (uint32_t)(t.ent.size() / 2);
+    TRY(dmalloc(c, &c->dec_ent, c->dec_n));
+    TRY(dmalloc(c, &c->dec_pool, pool_bytes));
+    if (c->dec_n) HIPCHK(c, hipMemcpy(c->dec_ent, t.ent.data(), t.ent.size() * 4, hipMemcpyHostToDevice));
+    if (pool_bytes) HIPCHK(c, hipMemcpy(c->dec_pool, vocab_bytes, pool_bytes, hipMemcpyHostToDevice));
+    c->have_dec_model = true;
+    return YABPE_OK;
+}
+
+int yabpe_decode_free(yabpe_ctx *c) {
+    if (!c) return YABPE_E_INVALID;
+    dfree(c->dec_text);
+    dfree(c->dec_doc);
+    c->dec_text = nullptr;
+    c->dec_doc = nullptr;
+    return YABPE_OK;
+}
+
+int yabpe_decode(yabpe_ctx *c, const uint32_t *ids, uint64_t n_ids, const uint64_t *doc_off, uint32_t n_docs, uint8_t **out_dev_text,
+                 uint64_t **out_dev_text_off, uint64_t *out_n_bytes) {
+    if (!c || !out_dev_text || !out_dev_text_off || !out_n_bytes) return YABPE_E_INVALID;
+    HIPCHK(c, hipSetDevice(c->device));
+    *out_dev_text = nullptr; *out_dev_text_off = nullptr; *out_n_bytes = 0;
+    if (!c->have_dec_model) return fail(c, YABPE_E_INVALID, "no model: call yabpe_decode_set_model first");
+    if (n_ids && !ids) return fail(c, YABPE_E_INVALID, "ids is NULL");
+    if (!doc_off && n_docs > 1) return fail(c, YABPE_E_INVALID, "doc_off is NULL with %u documents", n_docs);
+    const unsigned long long nb = (n_ids + DEC_IPB - 1) / DEC_IPB;
+    if (nb > (1ull << 23)) return fail(c, YABPE_E_CAPACITY, "%llu ids in one call: at most 2^34", (unsigned long long)n_ids);
+    // the document starts on the host (validated: the kernels index the ids with them) and on the device
+    const bool docs_dev = doc_off && is_device_ptr(doc_off);
+    if (!doc_off) n_docs = 1;
+    std::vector<uint64_t> h_docs(n_docs, 0);
+    if (doc_off && n_docs) {
+        if (docs_dev) HIPCHK(c, hipMemcpy(h_docs.data(), doc_off, (size_t)n_docs * 8, hipMemcpyDeviceToHost));
+        else memcpy(h_docs.data(), doc_off, (size_t)n_docs * 8);
+    }
+    if (!n_docs || h_docs[0] != 0) return fail(c, YABPE_E_INVALID, "doc_off must hold n_docs >= 1 starts, the first one 0");
+    for (uint32_t d = 1; d < n_docs; ++d)
+        if (h_docs[d] < h_docs[d - 1] || h_docs[d] > n_ids) return fail(c, YABPE_E_INVALID, "document starts must ascend inside the ids");
+    yabpe_decode_free(c);
+    c->dec_stats = yabpe_decode_stats_t{};
+    c->dec_stats.n_ids = n_ids;
+    c->dec_stats.n_docs = n_docs;
+    for (auto &e : c->dec_ev)
+        if (!e) HIPCHK(c, hipEventCreate(&e));
+    hipStream_t s = c->stream;
+    EncScratch S;
+    // inputs on the device (16-B aligned ids: the kernels load them 4 at a time)
+    const uint32_t *d_ids = ids;
+    if (n_ids && (!is_device_ptr(ids) || ((uintptr_t)ids & 15u))) {
+        uint32_t *own = nullptr;
+        TRY(S.get(c, &own, n_ids));
+        HIPCHK(c, hipMemcpy(own, ids, n_ids * 4, hipMemcpyDefault));
+        d_ids = own;
+    }
+    const unsigned long long *d_docs = (const unsigned long long *)doc_off;
+    if (!docs_dev) {
+        unsigned long long *own = nullptr;
+        TRY(S.get(c, &own, n_docs));
+        HIPCHK(c, hipMemcpy(own, h_docs.data(), (size_t)n_docs * 8, hipMemcpyHostToDevice));
+        d_docs = own;
+    }
+    TRY(dmalloc(c, &c->dec_doc, (uint64_t)n_docs + 1));
+    if (n_ids == 0) { // every document is empty
+        HIPCHK(c, hipMemsetAsync(c->dec_doc, 0, ((size_t)n_docs + 1) * 8, s));
+        TRY(dmalloc(c, &c->dec_text, 1));
+        HIPCHK(c, hipStreamSynchronize(s));
+        *out_dev_text = c->dec_text;
+        *out_dev_text_off = (uint64_t *)c->dec_doc;
+        return YABPE_OK;
+    }
+    const DecTable tab{c->dec_ent, c->dec_n, c->dec_pool};
+    // ---- lengths: per-block byte counts -> block output bases
+    unsigned long long *bsum = nullptr, *bbase = nullptr, *counters = nullptr;
+    TRY(S.get(c, &bsum, nb));
+    TRY(S.get(c, &bbase, nb + 1));
+    TRY(S.get(c, &counters, 2));
+    HIPCHK(c, hipEventRecord(c->dec_ev[0], s));
+    HIPCHK(c, hipMemsetAsync(counters, 0, 16, s));
+    hipLaunchKernelGGL(k_dec_lengths, dim3((uint32_t)nb), dim3(BLOCK), 0, s, d_ids, (unsigned long long)n_ids, tab, bsum, counters);
+    HIPCHK(c, hipGetLastError());
+    if (exclusive_scan<unsigned long long>(s, bsum, nb, bbase, nb + 1) != 0) return fail(c, YABPE_E_HIP, "scan of the block lengths failed");
+    HIPCHK(c, hipEventRecord(c->dec_ev[1], s));
+    unsigned long long G = 0;
+    HIPCHK(c, hipMemcpyAsync(&G, bbase + nb, 8, hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipStreamSynchronize(s));
+    const unsigned long long nt = (G + DEC_TILE - 1) / DEC_TILE;
+    if (nt > (1ull << 24)) return fail(c, YABPE_E_CAPACITY, "%llu bytes of text in one call: at most 2^36", G);
+    // ---- gather: token bytes -> text, document offsets
+    uint8_t *gtext = nullptr;
+    TRY(dmalloc(c, &gtext, G));
+    HIPCHK(c, hipEventRecord(c->dec_ev[2], s)); // (the allocation above is host work)
+    hipLaunchKernelGGL(k_dec_gather, dim3((uint32_t)nb), dim3(BLOCK), 0, s,
+                       DecGatherParams{d_ids, n_ids, tab, bbase, d_docs, n_docs, gtext, c->dec_doc});
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipEventRecord(c->dec_ev[3], s));
+    // ---- check: output bytes per tile, U+FFFD count
+    uint32_t *osum = nullptr;
+    TRY(S.get(c, &osum, nt));
+    if (nt) hipLaunchKernelGGL(k_dec_check, dim3((uint32_t)nt), dim3(BLOCK), 0, s, DecCheckParams{gtext, G, c->dec_doc, n_docs, osum, counters});
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipEventRecord(c->dec_ev[4], s));
+    unsigned long long h_cnt[2] = {0, 0};
+    HIPCHK(c, hipMemcpyAsync(h_cnt, counters, 16, hipMemcpyDeviceToHost, s));
+    const hipError_t ce = hipStreamSynchronize(s);
+    if (ce != hipSuccess) {
+        dfree(gtext);
+        return fail(c, YABPE_E_HIP, "decoder kernels failed: %s", hipGetErrorString(ce));
+    }
+    auto &st = c->dec_stats;
+    st.n_unknown = h_cnt[0];
+    st.n_gathered = G;
+    st.n_replacements = h_cnt[1];
+    float ms[5] = {0, 0, 0, 0, 0};
+    (void)hipEventElapsedTime(&ms[0], c->dec_ev[0], c->dec_ev[1]);
+    (void)hipEventElapsedTime(&ms[1], c->dec_ev[2], c->dec_ev[3]);
+    (void)hipEventElapsedTime(&ms[2], c->dec_ev[3], c->dec_ev[4]);
+    hipEvent_t last = c->dec_ev[4];
+    unsigned long long n_out = G;
+    if (h_cnt[1] == 0) { // valid UTF-8: the gathered text is the result
+        c->dec_text = gtext;
+    } else {
+        // ---- repair: tile output bases, the rewrite with U+FFFD, the repaired documents
+        S.bufs.push_back(gtext); // (the gathered text and its offsets are scratch from here on)
+        S.bufs.push_back(c->dec_doc);
+        const unsigned long long *gdoc = c->dec_doc;
+        c->dec_doc = nullptr;
+        unsigned long long *rbase = nullptr, *nbad = nullptr;
+        uint32_t *docbad = nullptr;
+        TRY(S.get(c, &rbase, nt + 1));
+        TRY(S.get(c, &docbad, n_docs));
+        TRY(S.get(c, &nbad, (uint64_t)n_docs + 1));
+        TRY(dmalloc(c, &c->dec_doc, (uint64_t)n_docs + 1));
+        HIPCHK(c, hipEventRecord(c->dec_ev[5], s));
+        HIPCHK(c, hipMemsetAsync(docbad, 0, (size_t)n_docs * 4, s));
+        int r = exclusive_scan<uint32_t>(s, osum, nt, rbase, nt + 1);
+        if (r == 0) r = hipMemcpyAsync(&n_out, rbase + nt, 8, hipMemcpyDeviceToHost, s) == hipSuccess && hipStreamSynchronize(s) == hipSuccess ? 0 : -1;
+        if (r == 0) r = dmalloc(c, &c->dec_text, n_out);
+        if (r == 0) {
+            hipLaunchKernelGGL(k_dec_repair, dim3((uint32_t)nt), dim3(BLOCK), 0, s,
+                               DecRepairParams{gtext, G, gdoc, n_docs, rbase, c->dec_text, c->dec_doc, docbad});
+            r = hipGetLastError() == hipSuccess ? 0 : -1;
+        }
+        if (r == 0) r = exclusive_scan<uint32_t>(s, docbad, n_docs, nbad, (uint64_t)n_docs + 1);
+        HIPCHK(c, hipEventRecord(c->dec_ev[6], s));
+        unsigned long long h_bad = 0;
+        if (r == 0) r = hipMemcpyAsync(&h_bad, nbad + n_docs, 8, hipMemcpyDeviceToHost, s) == hipSuccess ? 0 : -1;
+        const hipError_t se = hipStreamSynchronize(s);
+        if (r != 0 || se != hipSuccess) {
+            yabpe_decode_free(c);
+            return fail(c, YABPE_E_HIP, "decoder repair failed%s%s", se != hipSuccess ? ": " : "", se != hipSuccess ? hipGetErrorString(se) : "");
+        }
+        st.n_docs_repaired = h_bad;
+        (void)hipEventElapsedTime(&ms[3], c->dec_ev[5], c->dec_ev[6]);
+        last = c->dec_ev[6];
+    }
+    (void)hipEventElapsedTime(&ms[4], c->dec_ev[0], last);
+    st.n_bytes = n_out;
+    st.lengths_ms = ms[0];
+    st.gather_ms = ms[1];
+    st.check_ms = ms[2];
+    st.repair_ms = ms[3];
+    st.total_ms = ms[4];
+    *out_dev_text = c->dec_text;
+    *out_dev_text_off = (uint64_t *)c->dec_doc;
+    *out_n_bytes = n_out;
+    return YABPE_OK;
+}
+
+int yabpe_decode_stats(yabpe_ctx *c, yabpe_decode_stats_t *out) {
+    if (!c || !out) return YABPE_E_INVALID;
+    *out = c->dec_stats;
     return YABPE_OK;
 }
 

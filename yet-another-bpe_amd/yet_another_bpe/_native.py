@@ -29,6 +29,7 @@ class Utf8Error(ValueError):
         self.position = position
 
 
+E_CAPACITY = -4
 E_UTF8 = -7
 
 
@@ -51,6 +52,11 @@ class EncodeStats(ctypes.Structure):
         (n, c_double) for n in ("split_ms", "pretok_ms", "pool_ms", "words_ms", "emit_ms", "total_ms")]
 
 
+class DecodeStats(ctypes.Structure):
+    _fields_ = [(n, c_uint64) for n in ("n_ids", "n_docs", "n_unknown", "n_gathered", "n_bytes", "n_replacements", "n_docs_repaired")] + [
+        (n, c_double) for n in ("lengths_ms", "gather_ms", "check_ms", "repair_ms", "total_ms")]
+
+
 class Latency(ctypes.Structure):
     _fields_ = [(n, c_double) for n in ("launch_gap_us", "load_trip_us", "coherent_trip_us", "atomic_trip_us")]
 
@@ -67,6 +73,7 @@ SYMBOLS = [
     "yabpe_memcpy_d2h", "yabpe_memcpy_h2d", "yabpe_pretokenize", "yabpe_pretokenize_free",
     "yabpe_comm_unique_id", "yabpe_comm_init", "yabpe_comm_init_custom", "yabpe_comm_enable_p2p",
     "yabpe_encode_set_model", "yabpe_encode", "yabpe_encode_free", "yabpe_encode_stats", "yabpe_encode_checksum",
+    "yabpe_decode_set_model", "yabpe_decode", "yabpe_decode_free", "yabpe_decode_stats",
 ]
 
 
@@ -117,6 +124,10 @@ def lib() -> ctypes.CDLL:
         L.yabpe_encode_free.argtypes = [c_void_p]
         L.yabpe_encode_stats.argtypes = [c_void_p, POINTER(EncodeStats)]
         L.yabpe_encode_checksum.argtypes = [c_void_p, POINTER(c_uint64), POINTER(c_uint64), POINTER(c_uint64)]
+        L.yabpe_decode_set_model.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_uint32]
+        L.yabpe_decode.argtypes = [c_void_p, c_void_p, c_uint64, c_void_p, c_uint32, POINTER(c_void_p), POINTER(c_void_p), POINTER(c_uint64)]
+        L.yabpe_decode_free.argtypes = [c_void_p]
+        L.yabpe_decode_stats.argtypes = [c_void_p, POINTER(DecodeStats)]
         if L.yabpe_abi_version() != 2:
             raise ImportError("libyabpe.so ABI version mismatch")
         _lib = L
@@ -349,6 +360,48 @@ class Context:
         self._chk(lib().yabpe_encode_checksum(self._h, byref(a), byref(b), byref(c)))
         return a.value, b.value, c.value
 
+    # -- decoding with a trained model (BBPETokenizer.decode on the device)
+    def decode_set_model(self, vocab: dict) -> None:
+        """vocab {bytes: id}: the table id -> bytes (when two strings share an id, the last one in dict order wins)."""
+        a = decode_model_arrays(vocab)
+        self._chk(lib().yabpe_decode_set_model(self._h, a["vb"].ctypes.data, a["vo"].ctypes.data, a["vi"].ctypes.data, len(a["vi"])))
+
+    def decode(self, ids, n_ids: int | None = None, doc_starts=None, n_docs: int | None = None):
+        """ids: u32 array (staged) or a device address (n_ids required); doc_starts: ascending document starts into the ids,
+        the first one 0, as an array or a device address (n_docs required); None: one document.
+        -> (dev_text_ptr u8, dev_text_off_ptr u64[n_docs + 1], n_bytes); the buffers live until the next decode, decode_free()
+        or close()."""
+        keep = None
+        if isinstance(ids, int):
+            ptr, n = c_void_p(ids), int(n_ids)
+        else:
+            keep = np.ascontiguousarray(ids, dtype=np.uint32)
+            ptr, n = c_void_p(keep.ctypes.data if keep.size else 0), int(keep.size)
+        if isinstance(doc_starts, int):
+            dptr, nd = c_void_p(doc_starts), int(n_docs)
+        else:
+            docs = np.ascontiguousarray(doc_starts if doc_starts is not None and len(doc_starts) else [0], dtype=np.uint64)
+            dptr, nd = c_void_p(docs.ctypes.data), len(docs)
+        dt, do, nb = c_void_p(), c_void_p(), c_uint64(0)
+        self._chk(lib().yabpe_decode(self._h, ptr, n, dptr, nd, byref(dt), byref(do), byref(nb)))
+        return dt.value or 0, do.value, nb.value
+
+    def decode_to_host(self, ids, n_ids: int | None = None, doc_starts=None, n_docs: int | None = None):
+        """-> (text u8[n_bytes], text_off u64[n_docs + 1]) copied to the host."""
+        if n_docs is None:
+            n_docs = len(doc_starts) if doc_starts is not None and not isinstance(doc_starts, int) and len(doc_starts) else 1
+        dt, do, nb = self.decode(ids, n_ids, doc_starts, n_docs)
+        text = self.d2h(dt, nb) if nb else np.zeros(0, np.uint8)
+        return text, self.d2h(do, 8 * (n_docs + 1), np.uint64)
+
+    def decode_free(self) -> None:
+        self._chk(lib().yabpe_decode_free(self._h))
+
+    def decode_stats(self) -> dict:
+        s = DecodeStats()
+        self._chk(lib().yabpe_decode_stats(self._h, byref(s)))
+        return {f: getattr(s, f) for f, _ in DecodeStats._fields_}
+
     def h2d(self, dev_ptr: int, arr: np.ndarray) -> None:
         arr = np.ascontiguousarray(arr)
         self._chk(lib().yabpe_memcpy_h2d(self._h, c_void_p(dev_ptr), arr.ctypes.data, arr.nbytes))
@@ -406,6 +459,21 @@ def encode_model_arrays(vocab: dict, merges, specials_ordered) -> dict:
     mb, mo = flat([x for pair in merges for x in pair], np.uint64)
     sb, so = flat([t.encode("utf-8") if isinstance(t, str) else bytes(t) for t in specials_ordered], np.uint32)
     return {"vb": vb, "vo": vo, "vi": np.ascontiguousarray(vi), "mb": mb, "mo": mo, "sb": sb, "so": so}
+
+
+def decode_model_arrays(vocab: dict) -> dict:
+    """The flat arrays of yabpe_decode_set_model, in dict order: vocab bytes / u64 offsets / u32 ids.  An id outside
+    [0, 2^32) raises YabpeError(E_CAPACITY) (the device table holds ids below 2^24)."""
+    toks = list(vocab)
+    for t in toks:
+        if not 0 <= vocab[t] < 1 << 32:
+            raise YabpeError(E_CAPACITY, f"token id {vocab[t]} of {t!r}: the decode table holds ids below 2^24")
+    blob = np.frombuffer(b"".join(toks) or b"\0", dtype=np.uint8).copy()
+    off = np.zeros(len(toks) + 1, dtype=np.uint64)
+    if toks:
+        off[1:] = np.cumsum([len(t) for t in toks])
+    vi = np.asarray([vocab[t] for t in toks] or [0], dtype=np.uint32)[:len(toks)]
+    return {"vb": blob, "vo": off, "vi": np.ascontiguousarray(vi)}
 
 
 def train_words(words_flat, words_off, freq, base_tokens: list[bytes], num_merges: int, min_frequency: int,

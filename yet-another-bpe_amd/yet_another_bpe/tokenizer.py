@@ -2,8 +2,9 @@
 
 Plain Python, same public API as the reference `src/yet_another_bpe/tokenizer.py:35-398`
 (encode, decode, encode_batch, decode_batch, from_file, vocab_size, special_tokens, get_vocab,
-clear_cache, cache_info, _encode_word).  encode / encode_batch stay plain Python;
-encode_array / encode_batch_device compute the same ids on the GPU (yabpe_encode, include/yabpe.h).
+clear_cache, cache_info, _encode_word).  encode / encode_batch / decode / decode_batch stay plain Python;
+encode_array / encode_batch_device compute the same ids on the GPU (yabpe_encode, include/yabpe.h), and
+decode_array / decode_batch_device the same text (yabpe_decode).
 """
 from __future__ import annotations
 
@@ -37,7 +38,8 @@ class BBPETokenizer:
             ordered = sorted(self._special_tokens, key=len, reverse=True)
             self._special_pattern = regex.compile("(" + "|".join(regex.escape(t) for t in ordered) + ")")
         self._word_ids = lru_cache(maxsize=_WORD_CACHE)(self._word_ids_uncached)
-        self._device_ctx = None  # created on the first device call (encode_array / encode_batch_device)
+        self._device_ctx = None  # created on the first device call (encode_array / decode_array and their batch forms)
+        self._device_models: set[str] = set()  # models uploaded to it: "encode", "decode" (each on its first use)
 
     # ------------------------------------------------------------------ persistence (tokenizer.py:106-150)
     @classmethod
@@ -127,14 +129,18 @@ class BBPETokenizer:
         return [self.encode(t) for t in texts]
 
     # ------------------------------------------------------------------ encode on the GPU (yabpe_encode; same ids as encode)
-    def _device(self):
+    def _device(self, model: str = "encode"):
         if self._device_ctx is None:
             from . import _native
 
-            ctx = _native.Context()
-            ordered = sorted(self._special_tokens, key=len, reverse=True)  # the split pattern's order
-            ctx.encode_set_model(self._vocab, self._merges, ordered, self._vocab.get(b"[UNK]", 0))
-            self._device_ctx = ctx
+            self._device_ctx = _native.Context()
+        if model not in self._device_models:
+            if model == "encode":
+                ordered = sorted(self._special_tokens, key=len, reverse=True)  # the split pattern's order
+                self._device_ctx.encode_set_model(self._vocab, self._merges, ordered, self._vocab.get(b"[UNK]", 0))
+            else:
+                self._device_ctx.decode_set_model(self._vocab)
+            self._device_models.add(model)
         return self._device_ctx
 
     def encode_array(self, texts) -> tuple[np.ndarray, np.ndarray]:
@@ -172,6 +178,34 @@ class BBPETokenizer:
     def decode_batch(self, ids_batch: Sequence[Sequence[int]]) -> list[str]:
         return [self.decode(ids) for ids in ids_batch]
 
+    # ------------------------------------------------------------------ decode on the GPU (yabpe_decode; same text as decode)
+    def decode_array(self, ids, doc_off=None) -> tuple[np.ndarray, np.ndarray]:
+        """Decodes on the GPU: document d = ids[doc_off[d]:doc_off[d + 1]] (encode_array's layout: n_docs + 1 offsets, the
+        last one len(ids)); doc_off None: all of ids is one document.  -> (text np.uint8[n], text_off np.uint64[n_docs + 1]):
+        text[text_off[d]:text_off[d + 1]] is decode(ids[doc_off[d]:doc_off[d + 1]]) as UTF-8."""
+        if doc_off is None:
+            doc_off = [0, len(ids)]
+        off = np.asarray(doc_off, dtype=np.int64)
+        if off.ndim != 1 or len(off) < 2 or off[0] != 0 or off[-1] != len(ids) or np.any(np.diff(off) < 0):
+            raise ValueError("doc_off must be n_docs + 1 ascending offsets from 0 to len(ids)")
+        arr = ids if isinstance(ids, np.ndarray) and ids.dtype == np.uint32 else _u32_ids(ids)
+        if len(arr) != len(ids):  # ids no vocab can hold were dropped: move the document offsets with them
+            keep = _u32_mask(ids)
+            kept = np.concatenate(([0], np.cumsum(keep, dtype=np.int64)))
+            off = kept[off]
+        return self._device("decode").decode_to_host(arr, doc_starts=off[:-1].astype(np.uint64))
+
+    def decode_batch_device(self, ids_batch: Sequence[Sequence[int]]) -> list[str]:
+        """decode_batch(ids_batch), computed on the GPU in one call."""
+        if not len(ids_batch):
+            return []
+        flat = [i for ids in ids_batch for i in ids]
+        off = np.zeros(len(ids_batch) + 1, dtype=np.int64)
+        off[1:] = np.cumsum([len(ids) for ids in ids_batch])
+        text, toff = self.decode_array(flat, off)
+        data, toff = text.tobytes(), toff.tolist()
+        return [data[toff[d]:toff[d + 1]].decode("utf-8") for d in range(len(ids_batch))]
+
     # ------------------------------------------------------------------ introspection
     @property
     def vocab_size(self) -> int:
@@ -190,3 +224,24 @@ class BBPETokenizer:
     def cache_info(self) -> str:
         info = self._word_ids.cache_info()
         return f"hits={info.hits}, misses={info.misses}, size={info.currsize}/{info.maxsize}"
+
+
+def _u32_mask(ids) -> np.ndarray:
+    """Which ids lie in [0, 2^32) (Python ints of any size, or an integer array)."""
+    try:
+        a = np.asarray(ids, dtype=np.int64) if not isinstance(ids, np.ndarray) else ids
+    except OverflowError:
+        return np.fromiter((0 <= i < 1 << 32 for i in ids), dtype=bool, count=len(ids))
+    if a.dtype.kind == "u":
+        return a < (1 << 32)
+    return (a >= 0) & (a < (1 << 32))
+
+
+def _u32_ids(ids) -> np.ndarray:
+    """ids as u32, without those outside [0, 2^32): no vocab the device can hold names them, and decode skips what its
+    vocab does not name."""
+    try:
+        a = np.asarray(ids, dtype=np.int64) if not isinstance(ids, np.ndarray) else ids
+    except OverflowError:
+        return np.asarray([i for i in ids if 0 <= i < 1 << 32], dtype=np.uint32)
+    return a[_u32_mask(a)].astype(np.uint32)
