@@ -69,6 +69,27 @@ int yabpe_set_vocab(yabpe_ctx *ctx, const uint8_t *tok_bytes, const uint32_t *to
 int yabpe_load_words(yabpe_ctx *ctx, const uint8_t *bytes, const uint64_t *word_off, const uint64_t *word_freq,
                      uint64_t n_words, uint32_t flags);
 
+/* Continuing from a trained model: the same corpus arguments as yabpe_load_words, plus the model's merges as id triples in
+ * order (left, right, merged: what replaying model.merges over the base vocabulary as _decode_merges does gives).  Call after
+ * yabpe_set_vocab with ALL of the model's tokens in id order.  Every word is brought to the state the training loop would
+ * have left it in -- rewritten by merge 0, then merge 1, ... each over its id pair, greedily from the left -- and tiled by
+ * its token count; yabpe_train then continues (new merges get the next ids).  Needs the pooled layout (word_freq or
+ * YABPE_LOAD_DEDUP), else YABPE_E_INVALID; a triple that names an id >= n_tokens or whose merged token is not as long as
+ * its operands together: YABPE_E_INVALID.  n_merges == 0 behaves as yabpe_load_words.  Single GPU. */
+int yabpe_load_words_resumed(yabpe_ctx *ctx, const uint8_t *bytes, const uint64_t *word_off, const uint64_t *word_freq,
+                             uint64_t n_words, uint32_t flags, const uint32_t *merge_left, const uint32_t *merge_right,
+                             const uint32_t *merge_merged, uint32_t n_merges);
+/* What the last resumed load saw (HIP events; segment_ms includes the pooling of equal words, build_ms the tiles and the
+ * initial pair count). */
+typedef struct yabpe_resume_stats_t {
+    uint64_t n_unique;   /* pooled words */
+    uint64_t n_long;     /* ... of them long by their TOKEN count after the replay */
+    uint64_t tokens;     /* tokens after the replay */
+    double segment_ms;
+    double build_ms;
+} yabpe_resume_stats_t;
+int yabpe_resume_stats(yabpe_ctx *ctx, yabpe_resume_stats_t *out);
+
 /* Merge loop -----------------------------------------------------------------------------------------
  * Runs trainer.py:238-300: at most `num_merges` iterations (the host computes max(0, vocab_size - len(vocab)),
  * :238), stops early when no pair is left (:242-243) or the best count < min_frequency (:247-248).
@@ -168,7 +189,7 @@ int yabpe_latency_probe(yabpe_ctx *ctx, yabpe_latency_t *out);
    incrementally maintained table.  *out_mismatches = number of differing keys. */
 int yabpe_verify_table(yabpe_ctx *ctx, uint64_t *out_mismatches);
 /* Debug: decode the resident token stream back to bytes and return an order-independent checksum over
-   (word bytes, segmentation) plus the number of words/tokens it saw. */
+   (word bytes, segmentation) plus the number of words/tokens it saw (the long-word buffer included). */
 int yabpe_stream_checksum(yabpe_ctx *ctx, uint64_t *out_sum, uint64_t *out_words, uint64_t *out_tokens);
 
 /* Synthetic corpus of SURVEY.md 8(d), generated on the device (bit-identical to yet_another_bpe/synth.py).

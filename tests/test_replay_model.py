@@ -1,0 +1,147 @@
+"""CPU: the rules of the resumed load (yet-another-bpe_amd/csrc/replay_logic.h, the functions the HIP kernels call) against
+the literal replay -- every word rewritten by merge 0, then merge 1, ... -- which is the specification; and the naive
+continuation that the GPU tests compare with, pinned against the oracle."""
+from __future__ import annotations
+
+import ctypes
+import random
+
+import numpy as np
+import pytest
+
+from oracle import py_trainer
+from tests import helpers, resume_helpers as rh
+from yet_another_bpe import _native
+
+SP = ["<|endoftext|>"]
+
+
+@pytest.fixture(scope="module")
+def lib():
+    return rh.replay_lib()
+
+
+def random_model(rng: random.Random, alphabet: bytes, specials, n_merges: int, dup: float = 0.15, same: float = 0.2):
+    """A merges list built by repeatedly merging random token pairs over `alphabet` (any two tokens can stand next to each
+    other), with deliberate duplicate pairs and left == right pairs."""
+    toks = [bytes([b]) for b in alphabet] + [s.encode() for s in specials if all(ch in alphabet for ch in s.encode())]
+    toks = list(dict.fromkeys(toks))
+    merges = []
+    for _ in range(n_merges):
+        if merges and rng.random() < dup:
+            merges.append(rng.choice(merges))
+            continue
+        l = rng.choice(toks)
+        r = l if rng.random() < same else rng.choice(toks)
+        merges.append((l, r))
+        if l + r not in toks:
+            toks.append(l + r)
+    return merges
+
+
+def check(lib, words, base, merges):
+    toks, triples = _native.merge_triples(base, merges)
+    ids = {t: i for i, t in enumerate(toks)}
+    want = [[ids[t] for t in rh.literal_replay(w, merges)] for w in words]
+    for form in (0, 1):
+        assert rh.model_replay(lib, words, triples, form) == want, form
+
+
+def test_random_models_against_the_literal_replay(lib):
+    rng = random.Random(20)
+    reused = 0
+    for trial in range(120):
+        alphabet = rng.choice([b"ab", b"abc", b"abcd", bytes([0, 255]), b"a b"])
+        specials = rng.choice([[], ["ab"], ["ab", "ba"], ["<|x|>"], ["aa"]])
+        base = helpers.base_tokens(specials)
+        merges = random_model(rng, alphabet, specials, rng.randint(1, 40))
+        toks, (_, _, merged) = _native.merge_triples(base, merges)
+        reused += len(merges) - (len(toks) - len(base))
+        lengths = [1, 2, 3, 63, 64, 65, 66, 127, 300] + [rng.randint(1, 300) for _ in range(12)]
+        words = [bytes(rng.choice(alphabet) for _ in range(n)) for n in lengths]
+        words += [bytes([alphabet[0]]) * n for n in (2, 3, 4, 5, 64, 65, 129)]  # left == right runs
+        check(lib, words, base, merges)
+    assert reused > 50  # duplicates and re-created ids were really there
+
+
+def test_id_reuse_through_a_special_token(lib):
+    base = helpers.base_tokens(["ab"])  # "ab" has id 256 before any merge
+    merges = [(b"b", b"c"), (b"a", b"b"), (b"ab", b"ab"), (b"ab", b"c"), (b"a", b"bc")]
+    toks, (l, r, m) = _native.merge_triples(base, merges)
+    assert m[1] == 256 and len(toks) == len(base) + 3  # (a, b) re-creates the special's bytes; (a, bc) re-creates abc
+    check(lib, [b"ab", b"abab", b"ababab", b"abc", b"aabcab", b"abcabcabc" * 20], base, merges)
+
+
+def test_left_equals_right_runs(lib):
+    base = helpers.base_tokens([])
+    merges = [(b"a", b"a"), (b"aa", b"aa"), (b"aa", b"a"), (b"aaaa", b"aaaa")]
+    words = [b"a" * n for n in range(1, 40)] + [b"a" * n for n in (63, 64, 65, 100, 255, 256, 257, 300)] + [b"aabaaabaaaab" * 9]
+    check(lib, words, base, merges)
+    # the parity rule by hand: the sites of a run are its even positions
+    toks, triples = _native.merge_triples(base, [(b"a", b"a")])
+    aa, a = toks.index(b"aa"), toks.index(b"a")
+    for form in (0, 1):
+        assert rh.model_replay(lib, [b"aaa", b"aaaaa", b"aaaa"], triples, form) == [[aa, a], [aa, aa, a], [aa, aa]]
+
+
+def test_a_re_created_id_is_not_merged_at_a_rank_behind_the_loop(lib):
+    """(b, c), (a, b), (ab, c) -> abc, (abc, d), then (a, bc) re-creates abc under the same id: the abc d that arises at
+    rank 4 stays, because rank 3 is behind the loop.  The tokenizer's rule merges it -- the two rules differ."""
+    base = helpers.base_tokens([])
+    merges = [(b"b", b"c"), (b"a", b"b"), (b"ab", b"c"), (b"abc", b"d"), (b"a", b"bc")]
+    assert rh.literal_replay(b"abcd", merges) == (b"abc", b"d")
+    assert rh.tokenizer_rule(b"abcd", merges) == (b"abcd",)
+    assert rh.literal_replay(b"abcd", merges) != rh.tokenizer_rule(b"abcd", merges)
+    check(lib, [b"abcd", b"abcdabcd", b"xabcd" * 30], base, merges)
+    # ... unless (abc, d) is selected again as a later, duplicate entry of the list
+    again = merges + [(b"abc", b"d")]
+    assert rh.literal_replay(b"abcd", again) == (b"abcd",)
+    check(lib, [b"abcd", b"abcdabcd", b"xabcd" * 30], base, again)
+
+
+def test_lookup_smallest_rank_not_below_t(lib):
+    left = np.array([1, 2, 1, 3, 1], dtype=np.uint32)
+    right = np.array([2, 2, 2, 1, 2], dtype=np.uint32)
+    merged = np.array([9, 8, 9, 7, 9], dtype=np.uint32)
+    vp = lambda x: ctypes.c_void_p(x.ctypes.data)  # noqa: E731
+    for tmin, want in [(0, 0), (1, 2), (2, 2), (3, 4), (4, 4), (5, None)]:
+        rank, res = ctypes.c_uint32(0), ctypes.c_uint32(0)
+        got = lib.replay_model_lookup(vp(left), vp(right), vp(merged), ctypes.c_uint32(5), ctypes.c_uint32(1), ctypes.c_uint32(2),
+                                      ctypes.c_uint32(tmin), ctypes.byref(rank), ctypes.byref(res))
+        assert (got == 1, rank.value if got else None) == (want is not None, want)
+        assert not got or res.value == 9
+    rank, res = ctypes.c_uint32(0), ctypes.c_uint32(0)
+    assert lib.replay_model_lookup(vp(left), vp(right), vp(merged), ctypes.c_uint32(5), ctypes.c_uint32(2), ctypes.c_uint32(1),
+                                   ctypes.c_uint32(0), ctypes.byref(rank), ctypes.byref(res)) == 0
+
+
+# ---------------------------------------------------------------- the naive continuation, pinned
+def test_naive_continuation_from_scratch_equals_the_oracle():
+    words = helpers.corpus_en_words()
+    base = helpers.base_tokens(SP)
+    vocab, merges = rh.resume_naive(words, base, [], 1200, 1)
+    ref_vocab, ref_merges = py_trainer.merge_loop(words, len(base) + 1200, 1, SP)
+    assert merges == ref_merges and vocab == ref_vocab
+
+
+@pytest.mark.parametrize("v1", [1, 100, 743, 1500])
+def test_literal_replay_plus_continuation_equals_from_scratch_corpus_en(v1, golden_dir):
+    g1 = helpers.read_hex_merges(golden_dir / "g1_corpus_en_exhaustive.hex")
+    words = helpers.corpus_en_words()
+    base = helpers.base_tokens(SP)
+    total = 2000
+    vocab, merges = rh.resume_naive(words, base, g1[:v1], total - v1, 1)
+    assert merges == g1[:total]
+    assert vocab == {t: i for i, t in enumerate(_native.merge_triples(base, g1[:total])[0])}
+
+
+def test_literal_replay_plus_continuation_on_the_small_golden_cases():
+    for c in helpers.golden_cases():
+        base = helpers.base_tokens(c["special_tokens"])
+        full = c["merges_b"]
+        budget = max(0, c["vocab_size"] - len(base))
+        for v1 in sorted({0, 1, len(full) // 2, max(0, len(full) - 1), len(full)}):
+            vocab, merges = rh.resume_naive(c["words_b"], base, full[:v1], budget - v1, c["min_frequency"])
+            assert merges == full, (c["name"], v1)
+            assert len(vocab) == c["vocab_len"], (c["name"], v1)
+            assert {k: v for k, v in vocab.items() if v >= 256} == c["vocab_b"], (c["name"], v1)

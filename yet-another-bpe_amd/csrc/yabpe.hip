@@ -27,6 +27,7 @@
 #include "yabpe_pretok_kernels.h"
 #include "yabpe_encode_kernels.h"
 #include "yabpe_decode_kernels.h"
+#include "yabpe_replay_kernels.h"
 #include "unicode_classes.inc"
 
 using namespace yb;
@@ -167,6 +168,8 @@ struct yabpe_ctx {
     unsigned long long *dec_doc = nullptr;
     yabpe_decode_stats_t dec_stats{};
     hipEvent_t dec_ev[7] = {};
+    // resumed load (yabpe_load_words_resumed)
+    yabpe_resume_stats_t resume_stats{};
     // misc device scratch
     unsigned long long *scratch64 = nullptr;  // 16 x u64: [0] live sum [1] freq overflow [2,3] long words [4,5,6] verify/checksum
                                               // [7] comm_max [8] exchange record count [9] local count-table entries [10..12] comm_max3
@@ -1137,15 +1140,35 @@ int yabpe_set_vocab(yabpe_ctx *c, const uint8_t *tok_bytes, const uint32_t *tok_
 }
 
 // ---------------------------------------------------------------------------------------------- corpus
-int yabpe_load_words(yabpe_ctx *c, const uint8_t *bytes, const uint64_t *word_off, const uint64_t *word_freq,
-                     uint64_t n_words, uint32_t flags) {
-    if (!c) return YABPE_E_INVALID;
+// rp != NULL: the words are brought to the state the model's merges leave them in before they are tiled (the table's
+// arrays are device memory; pooled layout only)
+static int load_words_impl(yabpe_ctx *c, const uint8_t *bytes, const uint64_t *word_off, const uint64_t *word_freq,
+                           uint64_t n_words, uint32_t flags, const RpTable *rp) {
     HIPCHK(c, hipSetDevice(c->device));
     if (!c->have_vocab) return fail(c, YABPE_E_INVALID, "call yabpe_set_vocab first");
     if (!word_off) return fail(c, YABPE_E_INVALID, "word_off is NULL");
     if (n_words >= 0xFFFFFFFFull) return fail(c, YABPE_E_CAPACITY, "more than 2^32-2 words per context");
     free_corpus(c);
-    hipEvent_t ev0, ev1;
+    // (temporaries of the resumed load and the events: released on every way out of this function)
+    struct Temps {
+        hipEvent_t ev0 = nullptr, ev1 = nullptr, ev_seg = nullptr;
+        uint32_t *wcnt = nullptr, *llen = nullptr, *ltok = nullptr, *lnxt = nullptr, *lprv = nullptr;
+        uint16_t *wtok = nullptr;
+        unsigned long long *tokoff = nullptr, *lbase = nullptr, *lheap = nullptr;
+        void free_walk() {
+            dfree(llen); dfree(lbase); dfree(ltok); dfree(lnxt); dfree(lprv); dfree(lheap);
+            llen = ltok = lnxt = lprv = nullptr;
+            lbase = lheap = nullptr;
+        }
+        ~Temps() {
+            free_walk();
+            dfree(wcnt); dfree(wtok); dfree(tokoff);
+            if (ev0) (void)hipEventDestroy(ev0);
+            if (ev1) (void)hipEventDestroy(ev1);
+            if (ev_seg) (void)hipEventDestroy(ev_seg);
+        }
+    } tmp;
+    hipEvent_t &ev0 = tmp.ev0, &ev1 = tmp.ev1, &ev_seg = tmp.ev_seg;
     HIPCHK(c, hipEventCreate(&ev0));
     HIPCHK(c, hipEventCreate(&ev1));
 
@@ -1184,7 +1207,13 @@ int yabpe_load_words(yabpe_ctx *c, const uint8_t *bytes, const uint64_t *word_of
             d_freq = (const unsigned long long *)own_freq;
         }
     }
-    auto cleanup_inputs = [&]() { dfree(own_off); dfree(own_bytes); dfree(own_freq); own_off = own_bytes = own_freq = nullptr; };
+    uint32_t *&d_wcnt = tmp.wcnt;             // resumed load: tokens per word after the replay ...
+    uint16_t *&d_wtok = tmp.wtok;             // ... the tokens, word w's where its bytes start ...
+    unsigned long long *&d_tokoff = tmp.tokoff; // ... and the exclusive scan of the counts
+    auto cleanup_inputs = [&]() {
+        dfree(own_off); dfree(own_bytes); dfree(own_freq); own_off = own_bytes = own_freq = nullptr;
+        dfree(d_wcnt); dfree(d_wtok); dfree(d_tokoff); d_wcnt = nullptr; d_wtok = nullptr; d_tokoff = nullptr;
+    };
     HIPCHK(c, hipEventRecord(ev0, c->stream));
 
     c->n_words_input = n_words;
@@ -1205,8 +1234,59 @@ int yabpe_load_words(yabpe_ctx *c, const uint8_t *bytes, const uint64_t *word_of
     c->n_words = n_words;
     c->tokens_initial = total_bytes;
 
+    // ---- resumed load: every word rewritten by the model's merges (replay_logic.h), then placed by its token count
+    uint64_t total_tokens = total_bytes;
+    if (rp) {
+        HIPCHK(c, hipEventCreate(&ev_seg));
+        c->resume_stats = yabpe_resume_stats_t{};
+        c->resume_stats.n_unique = n_words;
+        if (n_words) {
+            uint32_t *&d_llen = tmp.llen, *&d_ltok = tmp.ltok, *&d_lnxt = tmp.lnxt, *&d_lprv = tmp.lprv;
+            unsigned long long *&d_lbase = tmp.lbase, *&d_lheap = tmp.lheap;
+            TRY(dmalloc(c, &d_wcnt, n_words));
+            TRY(dmalloc(c, &d_wtok, std::max<uint64_t>(total_bytes, 1)));
+            TRY(dmalloc(c, &d_tokoff, n_words + 1));
+            TRY(dmalloc(c, &d_llen, n_words));
+            TRY(dmalloc(c, &d_lbase, n_words + 1));
+            HIPCHK(c, hipMemsetAsync(&c->scratch64[2], 0, 8, c->stream));
+            hipLaunchKernelGGL(k_replay_llen, dim3(cdiv64(n_words, 256)), dim3(256), 0, c->stream, d_off, (unsigned long long)n_words, d_llen, (uint32_t *)&c->scratch64[2]);
+            HIPCHK(c, hipGetLastError());
+            if (exclusive_scan<uint32_t>(c->stream, d_llen, n_words, d_lbase, (unsigned long long)n_words + 1) != 0) {
+                cleanup_inputs();
+                return fail(c, YABPE_E_HIP, "scan of the long words failed: %s", hipGetErrorString(hipGetLastError()));
+            }
+            unsigned long long long_bytes = 0, too_long = 0;
+            HIPCHK(c, hipMemcpyAsync(&long_bytes, d_lbase + n_words, 8, hipMemcpyDeviceToHost, c->stream));
+            HIPCHK(c, hipMemcpyAsync(&too_long, &c->scratch64[2], 8, hipMemcpyDeviceToHost, c->stream));
+            HIPCHK(c, hipStreamSynchronize(c->stream));
+            if (too_long & 0xFFFFFFFFull) { cleanup_inputs(); return fail(c, YABPE_E_CAPACITY, "a single word longer than 2^32-1 bytes"); }
+            if (long_bytes) {
+                TRY(dmalloc(c, &d_ltok, long_bytes));
+                TRY(dmalloc(c, &d_lnxt, long_bytes));
+                TRY(dmalloc(c, &d_lprv, long_bytes));
+                TRY(dmalloc(c, &d_lheap, 3 * long_bytes));
+            }
+            ReplayWordsParams RW{d_bytes, d_off, (unsigned long long)off_base, (unsigned long long)n_words, d_lbase, *rp, d_wcnt, d_wtok, d_ltok, d_lnxt, d_lprv, d_lheap};
+            const uint32_t grid = (uint32_t)std::min<uint64_t>(cdiv64(n_words, WPB), (uint64_t)std::max(1, c->n_cu) * 8);
+            hipLaunchKernelGGL(k_replay_words, dim3(grid), dim3(BLOCK), 0, c->stream, RW);
+            HIPCHK(c, hipGetLastError());
+            if (exclusive_scan<uint32_t>(c->stream, d_wcnt, n_words, d_tokoff, (unsigned long long)n_words + 1) != 0) {
+                cleanup_inputs();
+                return fail(c, YABPE_E_HIP, "scan of the token counts failed: %s", hipGetErrorString(hipGetLastError()));
+            }
+            unsigned long long tt = 0;
+            HIPCHK(c, hipMemcpyAsync(&tt, d_tokoff + n_words, 8, hipMemcpyDeviceToHost, c->stream));
+            HIPCHK(c, hipStreamSynchronize(c->stream));
+            total_tokens = tt;
+            tmp.free_walk();
+        }
+        HIPCHK(c, hipEventRecord(ev_seg, c->stream));
+        c->tokens_initial = total_tokens;
+        c->resume_stats.tokens = total_tokens;
+    }
+
     // ---- tiles
-    const uint64_t packed = total_bytes + n_words;
+    const uint64_t packed = total_tokens + n_words;
     const uint64_t n_tiles64 = (packed + SPAN - 1) / SPAN;
     if (n_tiles64 >= 0xFFFFFFF0ull) { cleanup_inputs(); return fail(c, YABPE_E_CAPACITY, "corpus too large for one context"); }
     c->n_tiles = (uint32_t)n_tiles64;
@@ -1236,7 +1316,13 @@ int yabpe_load_words(yabpe_ctx *c, const uint8_t *bytes, const uint64_t *word_of
         if (n_words) {
             LoadParams P{d_bytes, d_off, (unsigned long long)off_base, (unsigned long long)n_words, c->tiles, c->tile_len, c->tile_wbase,
                          (uint32_t *)&c->scratch64[2], &c->scratch64[3], d_long_word, long_cap};
-            hipLaunchKernelGGL(k_load_words, dim3(cdiv64(n_words, BLOCK)), dim3(BLOCK), 0, c->stream, P);
+            if (rp) {
+                LoadTokParams Q{d_wtok, d_wcnt, d_tokoff, d_off, (unsigned long long)off_base, (unsigned long long)n_words, c->tiles, c->tile_len,
+                                c->tile_wbase, P.long_count, P.long_total, d_long_word, long_cap};
+                hipLaunchKernelGGL(k_load_words_tok, dim3(cdiv64(n_words, BLOCK)), dim3(BLOCK), 0, c->stream, Q);
+            } else {
+                hipLaunchKernelGGL(k_load_words, dim3(cdiv64(n_words, BLOCK)), dim3(BLOCK), 0, c->stream, P);
+            }
             HIPCHK(c, hipGetLastError());
         }
         unsigned long long host2[2];
@@ -1264,7 +1350,10 @@ int yabpe_load_words(yabpe_ctx *c, const uint8_t *bytes, const uint64_t *word_of
         TRY(dmalloc(c, &d_ll, c->n_long));
         TRY(dmalloc(c, &c->long_off, c->n_long + 1));
         HIPCHK(c, hipMemsetAsync(&c->scratch64[2], 0, 8, c->stream));
-        hipLaunchKernelGGL(k_long_lengths, dim3(cdiv64(c->n_long, 256)), dim3(256), 0, c->stream, d_off, d_long_word, c->n_long, d_ll, (uint32_t *)&c->scratch64[2]);
+        if (rp)
+            hipLaunchKernelGGL(k_long_lengths_tok, dim3(cdiv64(c->n_long, 256)), dim3(256), 0, c->stream, d_wcnt, d_long_word, c->n_long, d_ll);
+        else
+            hipLaunchKernelGGL(k_long_lengths, dim3(cdiv64(c->n_long, 256)), dim3(256), 0, c->stream, d_off, d_long_word, c->n_long, d_ll, (uint32_t *)&c->scratch64[2]);
         HIPCHK(c, hipGetLastError());
         if (exclusive_scan<uint32_t>(c->stream, d_ll, c->n_long, c->long_off, (unsigned long long)c->n_long + 1) != 0) {
             cleanup_inputs();
@@ -1280,8 +1369,13 @@ int yabpe_load_words(yabpe_ctx *c, const uint8_t *bytes, const uint64_t *word_of
         TRY(dmalloc(c, &c->long_tok, long_total));
         TRY(dmalloc(c, &c->long_len, c->n_long));
         if (c->weighted) TRY(dmalloc(c, &c->long_freq, c->n_long));
-        LoadLongParams L{d_bytes, d_off, d_freq, d_long_word, c->long_off, c->long_tok, c->long_len, c->long_freq, c->n_long};
-        hipLaunchKernelGGL(k_load_long, dim3(c->n_long), dim3(BLOCK), 0, c->stream, L);
+        if (rp) {
+            LoadLongTokParams L{d_wtok, d_wcnt, d_off, (unsigned long long)off_base, d_freq, d_long_word, c->long_off, c->long_tok, c->long_len, c->long_freq, c->n_long};
+            hipLaunchKernelGGL(k_load_long_tok, dim3(c->n_long), dim3(BLOCK), 0, c->stream, L);
+        } else {
+            LoadLongParams L{d_bytes, d_off, d_freq, d_long_word, c->long_off, c->long_tok, c->long_len, c->long_freq, c->n_long};
+            hipLaunchKernelGGL(k_load_long, dim3(c->n_long), dim3(BLOCK), 0, c->stream, L);
+        }
         HIPCHK(c, hipGetLastError());
         if (optv(c, "long_sig", 1)) {  // signatures: a merge whose pair is in no long word then costs 8 bytes per long word
             c->long_sig_stride = (c->n_long + 31u) & ~31u;
@@ -1299,19 +1393,26 @@ int yabpe_load_words(yabpe_ctx *c, const uint8_t *bytes, const uint64_t *word_of
     TRY(state_pull(c));
     DevState *h = c->st_host;
     h->iter = 0; h->done = 0; h->halt = 0; h->halt_req = 0; h->sites = 0;
-    h->tokens_now = total_bytes;
+    h->tokens_now = total_tokens;
     h->table_entries = 0;
     TRY(state_push(c));
     TRY(refresh_live_slots(c));
     c->sig_valid = false;
-    TRY(table_rebuild(c, 1ull << 18, /*all_bytes=*/true));  // 65,536 possible byte pairs: start at load <= 1/4
+    // 65,536 possible byte pairs: start at load <= 1/4.  A resumed job's tokens are not bytes: the generic count, and a table
+    // that grows until its load is <= 1/2 (table_rebuild)
+    TRY(table_rebuild(c, 1ull << 18, /*all_bytes=*/rp == nullptr));
     c->stats.table_rebuilds = 0;
     HIPCHK(c, hipEventRecord(ev1, c->stream));
     HIPCHK(c, hipEventSynchronize(ev1));
     float ms = 0;
     HIPCHK(c, hipEventElapsedTime(&ms, ev0, ev1));
-    (void)hipEventDestroy(ev0);
-    (void)hipEventDestroy(ev1);
+    if (rp) {
+        float sms = 0;
+        HIPCHK(c, hipEventElapsedTime(&sms, ev0, ev_seg));
+        c->resume_stats.segment_ms = sms;  // (pooling of equal words included)
+        c->resume_stats.build_ms = ms - sms;
+        c->resume_stats.n_long = c->n_long;
+    }
     c->stats.load_ms = ms;
     c->stats.retiles = 0;
     c->stats.train_ms = 0;
@@ -1349,6 +1450,61 @@ int yabpe_load_words(yabpe_ctx *c, const uint8_t *bytes, const uint64_t *word_of
     if (c->blk_read) HIPCHK(c, hipMemsetAsync(c->blk_read, 0, MAX_LISTS * 8, c->stream));
     c->stats.algo_bytes_total = 0;
     c->have_words = true;
+    return YABPE_OK;
+}
+
+int yabpe_load_words(yabpe_ctx *c, const uint8_t *bytes, const uint64_t *word_off, const uint64_t *word_freq,
+                     uint64_t n_words, uint32_t flags) {
+    if (!c) return YABPE_E_INVALID;
+    return load_words_impl(c, bytes, word_off, word_freq, n_words, flags, nullptr);
+}
+
+int yabpe_load_words_resumed(yabpe_ctx *c, const uint8_t *bytes, const uint64_t *word_off, const uint64_t *word_freq, uint64_t n_words,
+                             uint32_t flags, const uint32_t *merge_left, const uint32_t *merge_right, const uint32_t *merge_merged,
+                             uint32_t n_merges) {
+    if (!c) return YABPE_E_INVALID;
+    HIPCHK(c, hipSetDevice(c->device));
+    if (!c->have_vocab) return fail(c, YABPE_E_INVALID, "call yabpe_set_vocab first (with all of the model's tokens)");
+    if (n_merges == 0) return load_words_impl(c, bytes, word_off, word_freq, n_words, flags, nullptr);
+    if (!word_freq && !(flags & YABPE_LOAD_DEDUP))
+        return fail(c, YABPE_E_INVALID, "a resumed load needs the pooled layout: pass word_freq or YABPE_LOAD_DEDUP");
+    if (c->multi) return fail(c, YABPE_E_INVALID, "a resumed load on several GPUs is not supported");
+    if (!merge_left || !merge_right || !merge_merged) return fail(c, YABPE_E_INVALID, "merge triples are NULL");
+    TRY(state_pull(c));
+    const uint32_t n_tokens = c->st_host->n_tokens;
+    std::vector<uint32_t> len(n_tokens);
+    HIPCHK(c, hipMemcpy(len.data(), c->tt.len, (size_t)n_tokens * 4, hipMemcpyDeviceToHost));
+    for (uint32_t i = 0; i < n_merges; ++i) {
+        const uint32_t l = merge_left[i], r = merge_right[i], m = merge_merged[i];
+        if (l >= n_tokens || r >= n_tokens || m >= n_tokens)
+            return fail(c, YABPE_E_INVALID, "merge %u names token id %u, the vocabulary has %u", i, std::max(l, std::max(r, m)), n_tokens);
+        if (len[m] != len[l] + len[r])
+            return fail(c, YABPE_E_INVALID, "merge %u: token %u has %u bytes, its operands %u + %u", i, m, len[m], len[l], len[r]);
+    }
+    RpTableHost th;
+    rp_build_table(merge_left, merge_right, merge_merged, n_merges, &th);
+    struct TableBufs {  // (released on every way out)
+        uint32_t *key = nullptr, *first = nullptr;
+        RpEntry *ent = nullptr;
+        ~TableBufs() { dfree(key); dfree(first); dfree(ent); }
+    } tb;
+    uint32_t *&d_key = tb.key, *&d_first = tb.first;
+    RpEntry *&d_ent = tb.ent;
+    TRY(dmalloc(c, &d_key, th.idx_key.size()));
+    TRY(dmalloc(c, &d_first, th.idx_first.size()));
+    TRY(dmalloc(c, &d_ent, th.ent.size()));
+    HIPCHK(c, hipMemcpy(d_key, th.idx_key.data(), th.idx_key.size() * 4, hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(d_first, th.idx_first.data(), th.idx_first.size() * 4, hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(d_ent, th.ent.data(), th.ent.size() * sizeof(RpEntry), hipMemcpyHostToDevice));
+    const RpTable t{d_key, d_first, (uint32_t)th.idx_key.size() - 1u, d_ent};
+    const int rc = load_words_impl(c, bytes, word_off, word_freq, n_words, flags, &t);
+    (void)hipStreamSynchronize(c->stream);
+    return rc;
+}
+
+int yabpe_resume_stats(yabpe_ctx *c, yabpe_resume_stats_t *out) {
+    if (!c || !out) return YABPE_E_INVALID;
+    *out = c->resume_stats;
     return YABPE_OK;
 }
 
@@ -2185,6 +2341,11 @@ int yabpe_stream_checksum(yabpe_ctx *c, uint64_t *out_sum, uint64_t *out_words, 
         ChecksumParams P{c->tiles, c->tile_len, c->tile_wbase, c->wfreq, c->n_tiles, c->tt,
                          &c->scratch64[4], &c->scratch64[5], &c->scratch64[6]};
         hipLaunchKernelGGL(k_stream_checksum, dim3(cdiv64(c->n_tiles, BLOCK)), dim3(BLOCK), 0, c->stream, P);
+        HIPCHK(c, hipGetLastError());
+    }
+    if (c->n_long) {  // the words outside the tile stream
+        LongChecksumParams L{c->long_tok, c->long_off, c->long_len, c->long_freq, c->n_long, c->tt, &c->scratch64[4], &c->scratch64[5], &c->scratch64[6]};
+        hipLaunchKernelGGL(k_long_checksum, dim3(cdiv64(c->n_long, BLOCK)), dim3(BLOCK), 0, c->stream, L);
         HIPCHK(c, hipGetLastError());
     }
     unsigned long long r[3];

@@ -57,6 +57,10 @@ class DecodeStats(ctypes.Structure):
         (n, c_double) for n in ("lengths_ms", "gather_ms", "check_ms", "repair_ms", "total_ms")]
 
 
+class ResumeStats(ctypes.Structure):
+    _fields_ = [(n, c_uint64) for n in ("n_unique", "n_long", "tokens")] + [(n, c_double) for n in ("segment_ms", "build_ms")]
+
+
 class Latency(ctypes.Structure):
     _fields_ = [(n, c_double) for n in ("launch_gap_us", "load_trip_us", "coherent_trip_us", "atomic_trip_us")]
 
@@ -74,6 +78,7 @@ SYMBOLS = [
     "yabpe_comm_unique_id", "yabpe_comm_init", "yabpe_comm_init_custom", "yabpe_comm_enable_p2p",
     "yabpe_encode_set_model", "yabpe_encode", "yabpe_encode_free", "yabpe_encode_stats", "yabpe_encode_checksum",
     "yabpe_decode_set_model", "yabpe_decode", "yabpe_decode_free", "yabpe_decode_stats",
+    "yabpe_load_words_resumed", "yabpe_resume_stats",
 ]
 
 
@@ -95,6 +100,8 @@ def lib() -> ctypes.CDLL:
         L.yabpe_set_option.argtypes = [c_void_p, c_char_p, c_int64]
         L.yabpe_set_vocab.argtypes = [c_void_p, c_void_p, c_void_p, c_uint32]
         L.yabpe_load_words.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_uint64, c_uint32]
+        L.yabpe_load_words_resumed.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_uint64, c_uint32, c_void_p, c_void_p, c_void_p, c_uint32]
+        L.yabpe_resume_stats.argtypes = [c_void_p, POINTER(ResumeStats)]
         L.yabpe_train.argtypes = [c_void_p, c_uint32, c_uint64, c_void_p, c_void_p, c_void_p, c_void_p, POINTER(c_uint32)]
         L.yabpe_n_tokens.argtypes = [c_void_p, POINTER(c_uint32)]
         L.yabpe_token_bytes.argtypes = [c_void_p, c_uint32, c_void_p, c_uint32, POINTER(c_uint32)]
@@ -204,6 +211,36 @@ class Context:
         """Device (or host) addresses, e.g. from synth_generate() or torch tensors' data_ptr()."""
         self._chk(lib().yabpe_load_words(self._h, c_void_p(bytes_ptr), c_void_p(off_ptr),
                                          c_void_p(freq_ptr) if freq_ptr else None, n_words, LOAD_DEDUP if dedup else 0))
+
+    # -- continuing from a trained model: `triples` = (left, right, merged) u32 arrays (merge_triples), after set_vocab with
+    # all of the model's tokens
+    def load_words_resumed(self, flat, off, freq, triples, dedup: bool = False) -> None:
+        flat = np.ascontiguousarray(flat, dtype=np.uint8)
+        off = np.ascontiguousarray(off, dtype=np.uint64)
+        n = len(off) - 1
+        fq = None
+        if freq is not None:
+            fq = np.ascontiguousarray(freq, dtype=np.uint64)
+            assert len(fq) == n
+        l, r, m = (np.ascontiguousarray(x, dtype=np.uint32) for x in triples)
+        self._keep = (flat, off, fq, l, r, m)
+        self._chk(lib().yabpe_load_words_resumed(self._h, flat.ctypes.data if flat.size else None, off.ctypes.data,
+                                                 fq.ctypes.data if fq is not None else None, n, LOAD_DEDUP if dedup else 0,
+                                                 l.ctypes.data if len(l) else None, r.ctypes.data if len(l) else None,
+                                                 m.ctypes.data if len(l) else None, len(l)))
+
+    def load_words_resumed_ptr(self, bytes_ptr: int, off_ptr: int, n_words: int, triples, freq_ptr: int = 0, dedup: bool = True) -> None:
+        """Device (or host) addresses for the words, e.g. the results of pretokenize()."""
+        l, r, m = (np.ascontiguousarray(x, dtype=np.uint32) for x in triples)
+        self._keep = (l, r, m)
+        self._chk(lib().yabpe_load_words_resumed(self._h, c_void_p(bytes_ptr), c_void_p(off_ptr), c_void_p(freq_ptr) if freq_ptr else None,
+                                                 n_words, LOAD_DEDUP if dedup else 0, l.ctypes.data if len(l) else None,
+                                                 r.ctypes.data if len(l) else None, m.ctypes.data if len(l) else None, len(l)))
+
+    def resume_stats(self) -> dict:
+        s = ResumeStats()
+        self._chk(lib().yabpe_resume_stats(self._h, byref(s)))
+        return {f: getattr(s, f) for f, _ in ResumeStats._fields_}
 
     def train(self, num_merges: int, min_frequency: int):
         left = np.zeros(max(num_merges, 1), dtype=np.uint32)
@@ -474,6 +511,28 @@ def decode_model_arrays(vocab: dict) -> dict:
         off[1:] = np.cumsum([len(t) for t in toks])
     vi = np.asarray([vocab[t] for t in toks] or [0], dtype=np.uint32)[:len(toks)]
     return {"vb": blob, "vo": off, "vi": np.ascontiguousarray(vi)}
+
+
+def merge_triples(base_tokens, merges):
+    """Replays `merges` [(bytes, bytes)] over the base token list as BBPETrainer._decode_merges does: -> (tokens in id order,
+    (left, right, merged) u32 arrays).  l + r gets the next id unless those bytes are a token already (trainer.py:298-300).
+    Raises ValueError when an operand is not a token at that point."""
+    toks = list(base_tokens)
+    ids = {t: i for i, t in enumerate(toks)}
+    left = np.zeros(len(merges), dtype=np.uint32)
+    right = np.zeros(len(merges), dtype=np.uint32)
+    merged = np.zeros(len(merges), dtype=np.uint32)
+    for k, (l, r) in enumerate(merges):
+        l, r = bytes(l), bytes(r)
+        for side in (l, r):
+            if side not in ids:
+                raise ValueError(f"merge {k} names {side!r}, which is not a token when that merge is replayed")
+        m = ids.get(l + r)
+        if m is None:
+            m = ids[l + r] = len(toks)
+            toks.append(l + r)
+        left[k], right[k], merged[k] = ids[l], ids[r], m
+    return toks, (left, right, merged)
 
 
 def train_words(words_flat, words_off, freq, base_tokens: list[bytes], num_merges: int, min_frequency: int,

@@ -59,6 +59,25 @@ class BBPEModel:
         self.merges: list[tuple[bytes, bytes]] = list(merges)
         self.special_tokens: list[str] = list(special_tokens)
 
+    @classmethod
+    def from_file_lossless(cls, model_dir: str | Path) -> "BBPEModel":
+        """Loads what BBPETrainer.save_lossless wrote (vocab.hex.json, merges.hex, special_tokens.json): every token and
+        merge exactly as trained -- the form BBPETrainer.train_from can continue from."""
+        d = Path(model_dir)
+        with open(d / "vocab.hex.json", encoding="ascii") as f:
+            vocab = {bytes.fromhex(k): v for k, v in json.load(f).items()}
+        merges: list[tuple[bytes, bytes]] = []
+        with open(d / "merges.hex", encoding="ascii") as f:
+            for line in f:
+                left, _, right = line.strip().partition(" ")
+                if left or right:
+                    merges.append((bytes.fromhex(left), bytes.fromhex(right)))
+        specials: list[str] = []
+        if (d / "special_tokens.json").exists():
+            with open(d / "special_tokens.json", encoding="utf-8") as f:
+                specials = list(json.load(f))
+        return cls(vocab=vocab, merges=merges, special_tokens=specials)
+
 
 def _utf8_cut(window: bytes, pos: int) -> int:
     """Largest cut <= pos inside `window` that is not in the middle of a UTF-8 sequence
@@ -135,8 +154,32 @@ class BBPETrainer:
         from . import _native  # fails loudly when libyabpe.so / a GPU is missing
 
         specials = list(self.config.special_tokens)
+        text, chunks, total = self._gather_text(paths)
+        base = self._base_tokens()
+        num_merges = max(0, self.config.vocab_size - len(base))
+        empty = BBPEModel(vocab={t: i for i, t in enumerate(base)}, merges=[], special_tokens=specials)
+        if total == 0:
+            self._vocab, self._merges = dict(empty.vocab), []
+            return empty
+        with _native.Context() as ctx:
+            dev_text, dev_off, n_words = self._pretokenize_device(ctx, text, chunks)
+            if n_words == 0 or num_merges == 0:
+                self._vocab, self._merges = dict(empty.vocab), []
+                return empty
+            ctx.set_vocab(base)
+            ctx.load_words_ptr(dev_text, dev_off, n_words, dedup=os.environ.get("YABPE_LAYOUT", "dedup") != "flat")
+            left, right, merged, _count = ctx.train(num_merges, max(0, int(self.config.min_frequency)))  # (<= 0: merge to exhaustion, as the reference does)
+            self.last_stats = ctx.stats()
+        vocab, merges = self._decode_merges(base, left, right, merged)
+        self._vocab = vocab
+        self._merges = merges
+        return BBPEModel(vocab=vocab, merges=merges, special_tokens=specials)
+
+    def _gather_text(self, paths: Sequence[Path]):
+        """The files' chunks joined into one u8 buffer (None when empty), each chunk as (start in the buffer, file, start in
+        the file), and the number of bytes."""
         pieces: list[np.ndarray] = []
-        chunks: list[tuple[int, Path, int]] = []  # (start in the joined buffer, file, start in the file)
+        chunks: list[tuple[int, Path, int]] = []
         total = 0
         for path in paths:
             if not path.exists():
@@ -149,31 +192,100 @@ class BBPETrainer:
                 chunks.append((total, path, start))
                 pieces.append(data[start:stop])
                 total += stop - start
-        base = self._base_tokens()
-        num_merges = max(0, self.config.vocab_size - len(base))
-        empty = BBPEModel(vocab={t: i for i, t in enumerate(base)}, merges=[], special_tokens=specials)
-        if total == 0:
-            self._vocab, self._merges = dict(empty.vocab), []
-            return empty
-        text = pieces[0] if len(pieces) == 1 else np.concatenate(pieces)
-        with _native.Context() as ctx:
-            try:
-                dev_text, dev_off, n_words = ctx.pretokenize(text, chunk_starts=[c[0] for c in chunks], special_tokens=specials)
-            except _native.Utf8Error as e:
-                k = max(i for i, c in enumerate(chunks) if c[0] <= e.position)
-                g0, path, f0 = chunks[k]
-                raise ValueError(f"File {path} contains invalid UTF-8 at position {f0 + e.position - g0}.") from e
-            if n_words == 0 or num_merges == 0:
-                self._vocab, self._merges = dict(empty.vocab), []
-                return empty
-            ctx.set_vocab(base)
-            ctx.load_words_ptr(dev_text, dev_off, n_words, dedup=os.environ.get("YABPE_LAYOUT", "dedup") != "flat")
-            left, right, merged, _count = ctx.train(num_merges, max(0, int(self.config.min_frequency)))  # (<= 0: merge to exhaustion, as the reference does)
-            self.last_stats = ctx.stats()
-        vocab, merges = self._decode_merges(base, left, right, merged)
-        self._vocab = vocab
-        self._merges = merges
-        return BBPEModel(vocab=vocab, merges=merges, special_tokens=specials)
+        text = None if not pieces else pieces[0] if len(pieces) == 1 else np.concatenate(pieces)
+        return text, chunks, total
+
+    def _pretokenize_device(self, ctx, text, chunks):
+        from . import _native
+
+        try:
+            return ctx.pretokenize(text, chunk_starts=[c[0] for c in chunks], special_tokens=list(self.config.special_tokens))
+        except _native.Utf8Error as e:
+            k = max(i for i, c in enumerate(chunks) if c[0] <= e.position)
+            g0, path, f0 = chunks[k]
+            raise ValueError(f"File {path} contains invalid UTF-8 at position {f0 + e.position - g0}.") from e
+
+    # ------------------------------------------------------------------ continuing from a trained model
+    def _resumable(self, model) -> tuple[list[bytes], tuple]:
+        """Checks that `model` is what this trainer's configuration would have produced -- replaying its merges over
+        _base_tokens() as _decode_merges does gives model.vocab exactly, and the special tokens are the configured ones --
+        and returns (tokens in id order, the merges as (left, right, merged) id arrays).  ValueError otherwise."""
+        from ._native import merge_triples
+
+        vocab, merges = dict(model.vocab), list(model.merges)
+        if list(model.special_tokens) != list(self.config.special_tokens):
+            raise ValueError(f"cannot continue from this model: its special tokens {list(model.special_tokens)!r} are not the "
+                             f"trainer's {list(self.config.special_tokens)!r}")
+        if sorted(vocab.values()) != list(range(len(vocab))):
+            raise ValueError("cannot continue from this model: its token ids are not dense (0 .. len(vocab) - 1, each once)")
+        hint = ("; a model reloaded in the reference's text format (from_file) has lost merges and tokens -- save it with "
+                "save_lossless and reload it with from_file_lossless")
+        try:
+            toks, triples = merge_triples(self._base_tokens(), merges)
+        except ValueError as e:
+            raise ValueError(f"cannot continue from this model: {e}{hint}") from None
+        if {t: i for i, t in enumerate(toks)} != vocab:
+            raise ValueError("cannot continue from this model: replaying its merges over the trainer's base vocabulary does not "
+                             f"reproduce its vocab ({len(toks)} tokens replayed, {len(vocab)} in the model){hint}")
+        return toks, triples
+
+    def train_from(self, model, files: Sequence[str | Path]) -> BBPEModel:
+        """Continues training from `model` (a BBPEModel, or anything with .vocab, .merges and .special_tokens) on `files`:
+        more merges on the same corpus, or new merges learned from a new one.  Every existing id is kept; the result is
+        model.merges + the new merges and the extended vocab, exactly what train() gives when the corpus is the one the
+        model was trained on.  The iteration budget is max(0, vocab_size - len(base) - len(model.merges)) (a merge that
+        reused an id cost an iteration too, trainer.py:238).  An empty corpus or a zero budget returns the model unchanged.
+        Pre-tokenisation is train()'s (special tokens are ordinary words), on the device under the same size / environment
+        rule; the words are pooled (the flat layout does not apply)."""
+        if not files:
+            raise ValueError("At least one file must be provided")
+        paths = [Path(f) if isinstance(f, str) else f for f in files]
+        toks, triples = self._resumable(model)
+        specials = list(self.config.special_tokens)
+        old_merges = [(bytes(l), bytes(r)) for l, r in model.merges]
+        num_merges = max(0, self.config.vocab_size - len(self._base_tokens()) - len(old_merges))
+
+        def unchanged() -> BBPEModel:
+            self._vocab, self._merges = dict(model.vocab), list(old_merges)
+            return BBPEModel(vocab=self._vocab, merges=self._merges, special_tokens=specials)
+
+        for path in paths:
+            if not path.exists():
+                raise FileNotFoundError(f"File not found: {path}")
+        if num_merges == 0:
+            return unchanged()
+        from . import _native  # fails loudly when libyabpe.so / a GPU is missing
+
+        min_freq = max(0, int(self.config.min_frequency))
+        mode = os.environ.get("YABPE_PRETOKENIZE", "auto")
+        if mode == "gpu" or (mode == "auto" and sum(p.stat().st_size for p in paths) >= (1 << 20)):
+            text, chunks, total = self._gather_text(paths)
+            if total == 0:
+                return unchanged()
+            with _native.Context() as ctx:
+                dev_text, dev_off, n_words = self._pretokenize_device(ctx, text, chunks)
+                if n_words == 0:
+                    return unchanged()
+                ctx.set_vocab(toks)
+                ctx.load_words_resumed_ptr(dev_text, dev_off, n_words, triples, dedup=True)
+                left, right, merged, _count = ctx.train(num_merges, min_freq)
+                self.last_stats = ctx.stats()
+        else:
+            pooled = Counter(self._pretokenize(paths))
+            if not pooled:
+                return unchanged()
+            words = [t.encode("utf-8") for t in pooled]
+            off = np.zeros(len(words) + 1, dtype=np.uint64)
+            np.cumsum([len(w) for w in words], out=off[1:])
+            with _native.Context() as ctx:
+                ctx.set_vocab(toks)
+                ctx.load_words_resumed(np.frombuffer(b"".join(words), dtype=np.uint8), off,
+                                       np.fromiter(pooled.values(), dtype=np.uint64, count=len(pooled)), triples)
+                left, right, merged, _count = ctx.train(num_merges, min_freq)
+                self.last_stats = ctx.stats()
+        vocab, new_merges = self._decode_merges(toks, left, right, merged)
+        self._vocab, self._merges = vocab, old_merges + new_merges
+        return BBPEModel(vocab=self._vocab, merges=self._merges, special_tokens=specials)
 
     @staticmethod
     def _decode_merges(base: Sequence[bytes], left, right, merged):
