@@ -243,8 +243,20 @@ int yabpe_encode_set_model(yabpe_ctx *ctx, const uint8_t *vocab_bytes, const uin
  * UnicodeDecodeError.start of the whole text.  More than 2^32 - 1 pre-tokens in one call: YABPE_E_CAPACITY. */
 int yabpe_encode(yabpe_ctx *ctx, const uint8_t *text, uint64_t n_bytes, const uint64_t *doc_off, uint32_t n_docs,
                  uint32_t **out_dev_ids, uint64_t **out_dev_doc_off, uint64_t *out_n_ids, int64_t *out_bad_pos);
+/* yabpe_encode that also says which piece of its document every id was made from.  Arguments, errors and ownership are
+ * yabpe_encode's; flags: 0 or YABPE_SPANS_CHARS (anything else: YABPE_E_INVALID).  *out_dev_spans = 2 * *out_n_ids u64,
+ * interleaved (start, end) per id, relative to the start of the id's document (device memory owned by the library, released
+ * by yabpe_encode_free, the next yabpe_encode or yabpe_encode_spans, or yabpe_destroy).  Bytes: the bytes the token was
+ * merged from -- also for a token the vocab lacks (the unk id keeps its span); a special with an id spans its occurrence,
+ * one without an id emits nothing and leaves a gap; all other spans of a document tile it in ascending order.
+ * YABPE_SPANS_CHARS: code-point indices instead, the smallest run of whole characters that covers the token's bytes (with
+ * lead(p) = the non-continuation bytes below p: start = lead(start_byte + 1) - 1, end = lead(end_byte)). */
+#define YABPE_SPANS_CHARS 0x1u   /* code points instead of bytes */
+int yabpe_encode_spans(yabpe_ctx *ctx, const uint8_t *text, uint64_t n_bytes, const uint64_t *doc_off, uint32_t n_docs,
+                       uint32_t flags, uint32_t **out_dev_ids, uint64_t **out_dev_doc_off, uint64_t **out_dev_spans,
+                       uint64_t *out_n_ids, int64_t *out_bad_pos);
 int yabpe_encode_free(yabpe_ctx *ctx);
-/* What the last yabpe_encode saw, and the device time of its phases (HIP events around each phase's launches). */
+/* What the last yabpe_encode / yabpe_encode_spans saw (the span work counts into words_ms and emit_ms), and the device time of its phases (HIP events around each phase's launches). */
 typedef struct yabpe_encode_stats_t {
     uint64_t n_bytes, n_docs;
     uint64_t n_pretokens;      /* pre-tokens, specials included */

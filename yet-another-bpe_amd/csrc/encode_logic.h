@@ -1,5 +1,5 @@
 // encode_logic.h -- the rules of BBPETokenizer.encode (yet_another_bpe/tokenizer.py) on ids, shared by the HIP kernels
-// (yabpe_encode_kernels.h) and by the CPU unit-test model (tests/hostmodel/encode_model.cpp).
+// (yabpe_encode_kernels.h) and by the CPU unit-test models (tests/hostmodel/encode_model.cpp, spans_model.cpp).
 //
 //   specials   regex.split("(s1|s2|...)") with the specials in the tokenizer's order (longest first, stable): leftmost
 //              occurrence, first alternative at that position, no overlaps.  Occurrences that overlap form a CHAIN, resolved
@@ -192,6 +192,58 @@ YB_HD unsigned long long enc_word_hash(const uint8_t *w, uint32_t L, const uint3
         h = enc_fnv_mark(h);
     }
     return enc_fnv_final(h);
+}
+
+// ---------------------------------------------------------------- spans: which bytes / characters each token covers
+// Byte unit: token k of a word covers [start_k, start_{k+1}) of it, the last one up to the word's end.  The starts are the
+// alive lanes of the lane form and, on the long path, what enc_merge_heap leaves in nxt[0..count).
+YB_HD uint32_t enc_heap_start(const uint32_t *nxt, uint32_t k) { return nxt[k]; }
+YB_HD uint32_t enc_token_end(const uint32_t *starts, uint32_t count, uint32_t L, uint32_t k) { return k + 1 < count ? starts[k + 1] : L; }
+
+// Char unit: with lead(p) = the number of non-continuation bytes below p, the smallest run of whole characters that covers
+// the bytes [s, e) is [lead(s + 1) - 1, lead(e)).  (A token may begin or end inside a character.)
+YB_HD bool enc_is_lead(uint8_t b) { return (b & 0xC0) != 0x80; }
+template <class LeadF>
+YB_HD unsigned long long enc_char_start(LeadF lead, unsigned long long s) { return lead(s + 1) - 1ull; }
+template <class LeadF>
+YB_HD unsigned long long enc_char_end(LeadF lead, unsigned long long e) { return lead(e); }
+
+// lead() from a prefix every ENC_GRANULE bytes: table[g] = lead(g * ENC_GRANULE), then at most four 16-byte chunks of the
+// text.  `text` must be 16-byte aligned; a chunk that would reach past n is read byte by byte.
+constexpr uint32_t ENC_GRANULE = 64;
+struct alignas(16) EncChunk {
+    unsigned long long lo, hi;
+};
+
+// the continuation bytes (10xxxxxx) among the low `bytes` bytes of x (bytes in 1..8)
+YB_HD uint32_t enc_cont_count(unsigned long long x, uint32_t bytes) {
+    unsigned long long c = x & ~(x << 1) & 0x8080808080808080ull;
+    if (bytes < 8) c &= (1ull << (8 * bytes)) - 1ull;
+#if defined(__HIP_DEVICE_COMPILE__)
+    return (uint32_t)__popcll(c);
+#else
+    return (uint32_t)__builtin_popcountll(c);
+#endif
+}
+
+// non-continuation bytes in [c, c + m), c a multiple of 16, 1 <= m <= 16
+YB_HD uint32_t enc_lead_chunk(const uint8_t *text, unsigned long long n, unsigned long long c, uint32_t m) {
+    uint32_t cont = 0;
+    if (c + 16 <= n) {
+        const EncChunk v = *(const EncChunk *)(text + c);
+        cont = enc_cont_count(v.lo, m < 8 ? m : 8);
+        if (m > 8) cont += enc_cont_count(v.hi, m - 8);
+    } else {
+        for (uint32_t k = 0; k < m; ++k) cont += enc_is_lead(text[c + k]) ? 0u : 1u;
+    }
+    return m - cont;
+}
+
+YB_HD unsigned long long enc_lead(const uint8_t *text, unsigned long long n, const unsigned long long *table, unsigned long long p) {
+    const unsigned long long g = p / ENC_GRANULE;
+    unsigned long long r = table[g];
+    for (unsigned long long c = g * ENC_GRANULE; c < p; c += 16) r += enc_lead_chunk(text, n, c, p - c < 16 ? (uint32_t)(p - c) : 16u);
+    return r;
 }
 
 // ---------------------------------------------------------------- the model, built on the host

@@ -153,8 +153,9 @@ struct yabpe_ctx {
     uint8_t *enc_sp_bytes = nullptr, *enc_sp_has = nullptr;
     uint32_t *enc_sp_off = nullptr, *enc_sp_id = nullptr;
     uint32_t enc_n_special = 0, enc_sp_max_len = 0;
-    uint32_t *enc_ids = nullptr;              // results of the last yabpe_encode
+    uint32_t *enc_ids = nullptr;              // results of the last yabpe_encode / yabpe_encode_spans
     unsigned long long *enc_doc = nullptr;
+    unsigned long long *enc_spans = nullptr;  // (yabpe_encode_spans only)
     yabpe_encode_stats_t enc_stats{};
     unsigned long long enc_sums[4] = {0, 0, 0, 0};  // checksum, words, tokens, specials taken
     bool enc_done = false;
@@ -2581,16 +2582,21 @@ int yabpe_encode_free(yabpe_ctx *c) {
     if (!c) return YABPE_E_INVALID;
     dfree(c->enc_ids);
     dfree(c->enc_doc);
+    dfree(c->enc_spans);
     c->enc_ids = nullptr;
     c->enc_doc = nullptr;
+    c->enc_spans = nullptr;
     return YABPE_OK;
 }
 
-int yabpe_encode(yabpe_ctx *c, const uint8_t *text, uint64_t n_bytes, const uint64_t *doc_off, uint32_t n_docs, uint32_t **out_dev_ids,
-                 uint64_t **out_dev_doc_off, uint64_t *out_n_ids, int64_t *out_bad_pos) {
-    if (!c || !out_dev_ids || !out_dev_doc_off || !out_n_ids || !out_bad_pos) return YABPE_E_INVALID;
+// yabpe_encode (out_dev_spans == nullptr) and yabpe_encode_spans: one body.
+static int encode_run(yabpe_ctx *c, const uint8_t *text, uint64_t n_bytes, const uint64_t *doc_off, uint32_t n_docs, uint32_t span_flags,
+                      uint32_t **out_dev_ids, uint64_t **out_dev_doc_off, uint64_t **out_dev_spans, uint64_t *out_n_ids, int64_t *out_bad_pos) {
+    const bool spans = out_dev_spans != nullptr, chars = spans && (span_flags & YABPE_SPANS_CHARS);
     HIPCHK(c, hipSetDevice(c->device));
     *out_dev_ids = nullptr; *out_dev_doc_off = nullptr; *out_n_ids = 0; *out_bad_pos = -1;
+    if (spans) *out_dev_spans = nullptr;
+    if (span_flags & ~YABPE_SPANS_CHARS) return fail(c, YABPE_E_INVALID, "unknown flags 0x%x", span_flags);
     if (!c->have_enc_model) return fail(c, YABPE_E_INVALID, "no model: call yabpe_encode_set_model first");
     if (n_bytes && !text) return fail(c, YABPE_E_INVALID, "text is NULL");
     if (!doc_off || !n_docs || doc_off[0] != 0) return fail(c, YABPE_E_INVALID, "doc_off must hold n_docs >= 1 starts, the first one 0");
@@ -2614,6 +2620,11 @@ int yabpe_encode(yabpe_ctx *c, const uint8_t *text, uint64_t n_bytes, const uint
         TRY(S.get(c, &own, n));
         HIPCHK(c, hipMemcpy(own, text, n, hipMemcpyHostToDevice));
         d_text = own;
+    } else if (n && chars && ((uintptr_t)text & 15)) { // enc_lead reads the text in aligned 16-byte chunks
+        uint8_t *own = nullptr;
+        TRY(S.get(c, &own, n));
+        HIPCHK(c, hipMemcpy(own, text, n, hipMemcpyDeviceToDevice));
+        d_text = own;
     }
     unsigned long long *d_docs = nullptr;
     TRY(S.get(c, &d_docs, n_docs));
@@ -2623,6 +2634,10 @@ int yabpe_encode(yabpe_ctx *c, const uint8_t *text, uint64_t n_bytes, const uint
     if (n == 0) { // every document is empty
         HIPCHK(c, hipMemsetAsync(doc_ids, 0, ((size_t)n_docs + 1) * 8, s));
         TRY(dmalloc(c, &c->enc_ids, 1));
+        if (spans) {
+            TRY(dmalloc(c, &c->enc_spans, 2));
+            *out_dev_spans = (uint64_t *)c->enc_spans;
+        }
         HIPCHK(c, hipStreamSynchronize(s));
         c->enc_sums[0] = c->enc_sums[1] = c->enc_sums[2] = c->enc_sums[3] = 0;
         c->enc_done = true;
@@ -2712,6 +2727,8 @@ int yabpe_encode(yabpe_ctx *c, const uint8_t *text, uint64_t n_bytes, const uint
     TRY(S.get(c, &llen, nu));
     TRY(S.get(c, &lbase, nu + 1));
     TRY(S.get(c, &uids, ubytes));
+    uint32_t *upos = nullptr;
+    if (spans) TRY(S.get(c, &upos, ubytes));
     hipLaunchKernelGGL(k_enc_compact, dim3(pgrid), dim3(256), 0, s, flag, uidx, off, n_pre, ulist, llen);
     HIPCHK(c, hipGetLastError());
     if (exclusive_scan<uint32_t>(s, llen, nu, lbase, nu + 1) != 0) return fail(c, YABPE_E_HIP, "scan of the long words failed");
@@ -2730,14 +2747,24 @@ int yabpe_encode(yabpe_ctx *c, const uint8_t *text, uint64_t n_bytes, const uint
     HIPCHK(c, hipMemsetAsync(wsums, 0, 32, s));
     HIPCHK(c, hipEventRecord(c->enc_ev[4], s));  // (the words phase starts here: the scratch allocation above is host work)
     EncWordsParams W{d_text, off, ulist, nu, uoff, lbase, count, sflag, EncTable{c->enc_keys, c->enc_vals, c->enc_mask}, c->enc_out_id,
-                     c->enc_sp_id, c->enc_sp_has, flag, uids, ltok, lnxt, lprv, lheap, wsums};
+                     c->enc_sp_id, c->enc_sp_has, flag, uids, upos, ltok, lnxt, lprv, lheap, wsums};
     const uint32_t wg = (uint32_t)std::max<unsigned long long>(1, std::min<unsigned long long>((nu + WPB - 1) / WPB, (unsigned long long)c->n_cu * 8));
-    hipLaunchKernelGGL(k_enc_words, dim3(wg), dim3(BLOCK), 0, s, W);
+    if (spans)
+        hipLaunchKernelGGL(k_enc_words<true>, dim3(wg), dim3(BLOCK), 0, s, W);
+    else
+        hipLaunchKernelGGL(k_enc_words<false>, dim3(wg), dim3(BLOCK), 0, s, W);
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipEventRecord(c->enc_ev[5], s));
     // ---- emission: per pre-token count -> id offsets -> ids; per-document offsets
     unsigned long long *id_off = nullptr;
     TRY(S.get(c, &id_off, n_pre + 1));
+    const unsigned long long n_gran = (n + ENC_GRANULE - 1) / ENC_GRANULE;
+    uint8_t *lead_cnt = nullptr;
+    unsigned long long *lead_table = nullptr;
+    if (chars) {
+        TRY(S.get(c, &lead_cnt, n_gran));
+        TRY(S.get(c, &lead_table, n_gran + 1));
+    }
     HIPCHK(c, hipEventRecord(c->enc_ev[6], s));
     hipLaunchKernelGGL(k_enc_count, dim3(pgrid), dim3(256), 0, s, rep, flag, n_pre, ulen);
     HIPCHK(c, hipGetLastError());
@@ -2748,6 +2775,19 @@ int yabpe_encode(yabpe_ctx *c, const uint8_t *text, uint64_t n_bytes, const uint
     HIPCHK(c, hipStreamSynchronize(s));
     TRY(dmalloc(c, &c->enc_ids, n_ids));
     hipLaunchKernelGGL(k_enc_emit, dim3(pgrid), dim3(256), 0, s, rep, uoff, uids, id_off, n_pre, c->enc_ids);
+    if (spans) {
+        TRY(dmalloc(c, &c->enc_spans, 2 * n_ids));
+        if (chars) { // the lead-byte prefix of the text, one entry per granule
+            hipLaunchKernelGGL(k_enc_lead_count, dim3((uint32_t)((n_gran * 4 + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, s, d_text, n, lead_cnt);
+            HIPCHK(c, hipGetLastError());
+            if (exclusive_scan<uint8_t>(s, lead_cnt, n_gran, lead_table, n_gran + 1) != 0) return fail(c, YABPE_E_HIP, "scan of the lead-byte counts failed");
+            hipLaunchKernelGGL(k_enc_emit_spans<true>, dim3(pgrid), dim3(256), 0, s, rep, uoff, upos, id_off, off, n_pre, d_docs, n_docs, d_text, n,
+                               lead_table, (ulonglong2 *)c->enc_spans);
+        } else {
+            hipLaunchKernelGGL(k_enc_emit_spans<false>, dim3(pgrid), dim3(256), 0, s, rep, uoff, upos, id_off, off, n_pre, d_docs, n_docs, d_text, n,
+                               lead_table, (ulonglong2 *)c->enc_spans);
+        }
+    }
     hipLaunchKernelGGL(k_enc_docs, dim3((n_docs + 1 + 255) / 256), dim3(256), 0, s, d_docs, n_docs, n, off, n_pre, id_off, doc_ids);
     (void)hipEventRecord(c->enc_ev[7], s);
     const hipError_t le = hipGetLastError();
@@ -2781,8 +2821,21 @@ int yabpe_encode(yabpe_ctx *c, const uint8_t *text, uint64_t n_bytes, const uint
     c->enc_done = true;
     *out_dev_ids = c->enc_ids;
     *out_dev_doc_off = (uint64_t *)c->enc_doc;
+    if (spans) *out_dev_spans = (uint64_t *)c->enc_spans;
     *out_n_ids = n_ids;
     return YABPE_OK;
+}
+
+int yabpe_encode(yabpe_ctx *c, const uint8_t *text, uint64_t n_bytes, const uint64_t *doc_off, uint32_t n_docs, uint32_t **out_dev_ids,
+                 uint64_t **out_dev_doc_off, uint64_t *out_n_ids, int64_t *out_bad_pos) {
+    if (!c || !out_dev_ids || !out_dev_doc_off || !out_n_ids || !out_bad_pos) return YABPE_E_INVALID;
+    return encode_run(c, text, n_bytes, doc_off, n_docs, 0, out_dev_ids, out_dev_doc_off, nullptr, out_n_ids, out_bad_pos);
+}
+
+int yabpe_encode_spans(yabpe_ctx *c, const uint8_t *text, uint64_t n_bytes, const uint64_t *doc_off, uint32_t n_docs, uint32_t flags,
+                       uint32_t **out_dev_ids, uint64_t **out_dev_doc_off, uint64_t **out_dev_spans, uint64_t *out_n_ids, int64_t *out_bad_pos) {
+    if (!c || !out_dev_ids || !out_dev_doc_off || !out_dev_spans || !out_n_ids || !out_bad_pos) return YABPE_E_INVALID;
+    return encode_run(c, text, n_bytes, doc_off, n_docs, flags, out_dev_ids, out_dev_doc_off, out_dev_spans, out_n_ids, out_bad_pos);
 }
 
 int yabpe_encode_stats(yabpe_ctx *c, yabpe_encode_stats_t *out) {

@@ -10,6 +10,9 @@
 //   words     k_enc_words: one wave per unique word -- the ids of its tokens, their number and the checksum fold
 //   emit      k_enc_count / exclusive_scan / k_enc_emit: per pre-token count -> id offsets -> u32 ids; k_enc_docs: the
 //             per-document offsets into the ids
+// With spans (yabpe_encode_spans): k_enc_words<true> also writes every token's byte offset inside its word, and
+// k_enc_emit_spans writes (start, end) per id, relative to its document; in characters after k_enc_lead_count /
+// exclusive_scan built the lead-byte prefix of the text.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -76,6 +79,7 @@ struct EncWordsParams {
     const uint8_t *sp_has;
     uint32_t *wcnt;                   // out, per representative: number of ids
     uint32_t *uids;                   // out: the ids of every unique word
+    uint32_t *upos;                   // out (SPANS): per slot of uids, the token's byte offset inside its word
     uint32_t *ltok, *lnxt, *lprv;     // long-path scratch
     unsigned long long *lheap;
     unsigned long long *sums;         // [0] checksum [1] words [2] tokens: over the words of >= 2 tokens (encode_logic.h); [3] specials
@@ -93,6 +97,8 @@ __device__ __forceinline__ unsigned long long wave_min_u64(unsigned long long x)
 // One wave per unique word.  Words of at most 64 bytes: lane p holds the token that starts at byte p (while one does) and
 // the rank of the pair it begins; each step takes the smallest (rank, position) by a wave reduction, and only the two lanes
 // whose pair changed look the table up again.  Longer words: lane 0 runs the heap walk of encode_logic.h in global scratch.
+// SPANS: beside each id, the byte offset of its token inside the word (the lane; on the long path the walk's list).
+template <bool SPANS>
 __global__ __launch_bounds__(BLOCK) void k_enc_words(EncWordsParams P) {
     const int lane = threadIdx.x & 63;
     const unsigned long long wave0 = (unsigned long long)blockIdx.x * WPB + (threadIdx.x >> 6), waves = (unsigned long long)gridDim.x * WPB;
@@ -107,6 +113,7 @@ __global__ __launch_bounds__(BLOCK) void k_enc_words(EncWordsParams P) {
                 const uint32_t k = sf - 1u;
                 P.wcnt[w] = P.sp_has[k] ? 1u : 0u;
                 if (P.sp_has[k]) P.uids[base] = P.sp_id[k];
+                if (SPANS && P.sp_has[k]) P.upos[base] = 0u;
                 atomicAdd(&P.sums[3], P.count[w]);
             }
             continue;
@@ -118,6 +125,8 @@ __global__ __launch_bounds__(BLOCK) void k_enc_words(EncWordsParams P) {
                 uint32_t *tok = P.ltok + lb, *nxt = P.lnxt + lb;
                 const uint32_t cnt = enc_merge_heap(P.text + s, L, P.tab, tok, nxt, P.lprv + lb, P.lheap + 3 * lb);
                 for (uint32_t k = 0; k < cnt; ++k) P.uids[base + k] = P.out_id[tok[k]];
+                if (SPANS)
+                    for (uint32_t k = 0; k < cnt; ++k) P.upos[base + k] = enc_heap_start(nxt, k);
                 P.wcnt[w] = cnt;
                 if (cnt >= 2) {
                     sum += f * enc_word_hash(P.text + s, L, nxt, cnt);
@@ -157,6 +166,7 @@ __global__ __launch_bounds__(BLOCK) void k_enc_words(EncWordsParams P) {
         }
         const uint32_t cnt = (uint32_t)__popcll(am);
         if (alive) P.uids[base + __popcll(am & ((1ull << lane) - 1ull))] = P.out_id[tok];
+        if (SPANS && alive) P.upos[base + __popcll(am & ((1ull << lane) - 1ull))] = (uint32_t)lane;
         // the checksum fold: every lane walks the word's bytes with the token boundaries of the alive mask (same value in all)
         unsigned long long h = enc_fnv_init();
         for (uint32_t p = 0; p < L; ++p) {
@@ -192,6 +202,62 @@ __global__ void k_enc_emit(const uint32_t *rep, const unsigned long long *uoff, 
     const unsigned long long a = id_off[w], e = id_off[w + 1];
     const uint32_t *src = uids + uoff[rep[w]];
     for (unsigned long long k = a; k < e; ++k) ids[k] = src[k - a];
+}
+
+// cnt[g] = the non-continuation bytes of granule g (ENC_GRANULE bytes of text, 16-byte aligned): one 16-byte chunk per
+// thread, four neighbouring lanes make a granule.  Its exclusive scan is enc_lead's table.
+__global__ __launch_bounds__(BLOCK) void k_enc_lead_count(const uint8_t *text, unsigned long long n, uint8_t *cnt) {
+    const unsigned long long t = (unsigned long long)blockIdx.x * BLOCK + threadIdx.x, c = t * 16; // (whole waves run: the shuffles below)
+    uint32_t v = c < n ? enc_lead_chunk(text, n, c, n - c < 16 ? (uint32_t)(n - c) : 16u) : 0u;
+    v += __shfl_xor(v, 1);
+    v += __shfl_xor(v, 2);
+    if ((threadIdx.x & 3) == 0 && c < n) cnt[t >> 2] = (uint8_t)v;
+}
+
+// The spans of every id: (start, end) relative to the id's document, one 16-byte store each.  Bytes: start = pre-token
+// offset + in-word offset - document start, end = the next token's start or the pre-token's end.  CHARS: both ends by the
+// lead rule of encode_logic.h.  A pre-token never crosses a document start; its document is searched between the documents
+// of the block's first and last pre-token (nearly always the same one: no search).
+template <bool CHARS>
+__global__ __launch_bounds__(256) void k_enc_emit_spans(const uint32_t *rep, const unsigned long long *uoff, const uint32_t *upos,
+                                                        const unsigned long long *id_off, const unsigned long long *off, unsigned long long n,
+                                                        const unsigned long long *doc_start, uint32_t n_docs, const uint8_t *text,
+                                                        unsigned long long n_bytes, const unsigned long long *lead_table, ulonglong2 *spans) {
+    __shared__ uint32_t s_doc[2];
+    auto doc_of = [&](unsigned long long pos, uint32_t lo, uint32_t hi) -> uint32_t { // last d in [lo, hi] with doc_start[d] <= pos
+        while (lo < hi) {
+            const uint32_t mid = lo + (hi - lo + 1) / 2;
+            if (doc_start[mid] <= pos) lo = mid; else hi = mid - 1;
+        }
+        return lo;
+    };
+    const unsigned long long w0 = (unsigned long long)blockIdx.x * blockDim.x, w = w0 + threadIdx.x;
+    if (threadIdx.x < 2) {
+        const unsigned long long wl = w0 + blockDim.x - 1 < n ? w0 + blockDim.x - 1 : n - 1;
+        s_doc[threadIdx.x] = doc_of(off[threadIdx.x ? wl : w0], 0, n_docs - 1);
+    }
+    __syncthreads();
+    if (w >= n) return;
+    const unsigned long long a = id_off[w], e = id_off[w + 1];
+    if (a == e) return;
+    const unsigned long long ws = off[w], we = off[w + 1];
+    const unsigned long long ds = doc_start[doc_of(ws, s_doc[0], s_doc[1])];
+    const uint32_t *src = upos + uoff[rep[w]];
+    auto lead = [&](unsigned long long p) { return enc_lead(text, n_bytes, lead_table, p); };
+    const unsigned long long dl = CHARS ? lead(ds) : 0ull;
+    unsigned long long st = ws + src[0], ls = CHARS ? lead(st) : 0ull; // ls = lead(st): the previous token's lead(end)
+    for (unsigned long long k = a; k < e; ++k) {
+        const unsigned long long en = k + 1 < e ? ws + src[k + 1 - a] : we;
+        if (CHARS) {
+            auto lead_next = [&](unsigned long long p) { return ls + (enc_is_lead(text[p - 1]) ? 1ull : 0ull); }; // lead(st + 1)
+            const unsigned long long le = enc_char_end(lead, en);
+            spans[k] = make_ulonglong2(enc_char_start(lead_next, st) - dl, le - dl);
+            ls = le;
+        } else {
+            spans[k] = make_ulonglong2(st - ds, en - ds);
+        }
+        st = en;
+    }
 }
 
 // doc_ids[d] = id offset of the first pre-token at or after document d's start (d == n_docs: the total)

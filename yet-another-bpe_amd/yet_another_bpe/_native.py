@@ -76,7 +76,7 @@ SYMBOLS = [
     "yabpe_iter_log", "yabpe_event_log", "yabpe_latency_probe", "yabpe_verify_table", "yabpe_stream_checksum", "yabpe_synth_generate", "yabpe_synth_generate_lex", "yabpe_synth_free",
     "yabpe_memcpy_d2h", "yabpe_memcpy_h2d", "yabpe_pretokenize", "yabpe_pretokenize_free",
     "yabpe_comm_unique_id", "yabpe_comm_init", "yabpe_comm_init_custom", "yabpe_comm_enable_p2p",
-    "yabpe_encode_set_model", "yabpe_encode", "yabpe_encode_free", "yabpe_encode_stats", "yabpe_encode_checksum",
+    "yabpe_encode_set_model", "yabpe_encode", "yabpe_encode_spans", "yabpe_encode_free", "yabpe_encode_stats", "yabpe_encode_checksum",
     "yabpe_decode_set_model", "yabpe_decode", "yabpe_decode_free", "yabpe_decode_stats",
     "yabpe_load_words_resumed", "yabpe_resume_stats",
 ]
@@ -128,6 +128,8 @@ def lib() -> ctypes.CDLL:
                                              c_void_p, c_void_p, c_uint32, c_uint32]
         L.yabpe_encode.argtypes = [c_void_p, c_void_p, c_uint64, c_void_p, c_uint32, POINTER(c_void_p), POINTER(c_void_p),
                                    POINTER(c_uint64), POINTER(ctypes.c_int64)]
+        L.yabpe_encode_spans.argtypes = [c_void_p, c_void_p, c_uint64, c_void_p, c_uint32, c_uint32, POINTER(c_void_p), POINTER(c_void_p),
+                                         POINTER(c_void_p), POINTER(c_uint64), POINTER(ctypes.c_int64)]
         L.yabpe_encode_free.argtypes = [c_void_p]
         L.yabpe_encode_stats.argtypes = [c_void_p, POINTER(EncodeStats)]
         L.yabpe_encode_checksum.argtypes = [c_void_p, POINTER(c_uint64), POINTER(c_uint64), POINTER(c_uint64)]
@@ -142,6 +144,7 @@ def lib() -> ctypes.CDLL:
 
 
 LOAD_DEDUP = 0x1
+SPANS_CHARS = 0x1  # yabpe_encode_spans: code points instead of bytes
 
 
 class Context:
@@ -359,10 +362,8 @@ class Context:
                                                a["mb"].ctypes.data, a["mo"].ctypes.data, len(a["mo"]) // 2, a["sb"].ctypes.data,
                                                a["so"].ctypes.data, len(a["so"]) - 1, int(unk_id)))
 
-    def encode(self, text, n_bytes: int | None = None, doc_starts=None):
-        """text: bytes / u8 array (staged) or a device address (n_bytes required); doc_starts: ascending document starts, the
-        first one 0.  -> (dev_ids_ptr u32, dev_doc_off_ptr u64[n_docs + 1], n_ids); the buffers live until the next encode,
-        encode_free() or close().  Raises Utf8Error(position) on malformed UTF-8."""
+    def _encode_call(self, text, n_bytes, doc_starts, flags):
+        """yabpe_encode (flags None) or yabpe_encode_spans -> (dev ids, dev doc_off, dev spans or None, n_ids)"""
         keep = None
         if isinstance(text, int):
             ptr, n = c_void_p(text), int(n_bytes)
@@ -370,12 +371,23 @@ class Context:
             keep = np.frombuffer(text, dtype=np.uint8) if not isinstance(text, np.ndarray) else np.ascontiguousarray(text, dtype=np.uint8)
             ptr, n = c_void_p(keep.ctypes.data if keep.size else 0), int(keep.size)
         docs = np.ascontiguousarray(doc_starts if doc_starts is not None and len(doc_starts) else [0], dtype=np.uint64)
-        di, dd, ni, bad = c_void_p(), c_void_p(), c_uint64(0), ctypes.c_int64(-1)
-        rc = lib().yabpe_encode(self._h, ptr, n, docs.ctypes.data, len(docs), byref(di), byref(dd), byref(ni), byref(bad))
+        di, dd, ds, ni, bad = c_void_p(), c_void_p(), c_void_p(), c_uint64(0), ctypes.c_int64(-1)
+        if flags is None:
+            rc = lib().yabpe_encode(self._h, ptr, n, docs.ctypes.data, len(docs), byref(di), byref(dd), byref(ni), byref(bad))
+        else:
+            rc = lib().yabpe_encode_spans(self._h, ptr, n, docs.ctypes.data, len(docs), int(flags), byref(di), byref(dd), byref(ds), byref(ni),
+                                          byref(bad))
         if rc == E_UTF8:
             raise Utf8Error(bad.value)
         self._chk(rc)
-        return di.value or 0, dd.value, ni.value
+        return di.value or 0, dd.value, ds.value, ni.value
+
+    def encode(self, text, n_bytes: int | None = None, doc_starts=None):
+        """text: bytes / u8 array (staged) or a device address (n_bytes required); doc_starts: ascending document starts, the
+        first one 0.  -> (dev_ids_ptr u32, dev_doc_off_ptr u64[n_docs + 1], n_ids); the buffers live until the next encode,
+        encode_free() or close().  Raises Utf8Error(position) on malformed UTF-8."""
+        di, dd, _ds, ni = self._encode_call(text, n_bytes, doc_starts, None)
+        return di, dd, ni
 
     def encode_to_host(self, text, n_bytes: int | None = None, doc_starts=None):
         """-> (ids u32[n_ids], doc_off u64[n_docs + 1]) copied to the host."""
@@ -383,6 +395,19 @@ class Context:
         di, dd, ni = self.encode(text, n_bytes, doc_starts)
         ids = self.d2h(di, 4 * ni, np.uint32) if ni else np.zeros(0, np.uint32)
         return ids, self.d2h(dd, 8 * (n_docs + 1), np.uint64)
+
+    def encode_spans(self, text, n_bytes: int | None = None, doc_starts=None, chars: bool = False):
+        """encode() plus every id's span in its document (yabpe_encode_spans; chars: code points instead of bytes).
+        -> (dev_ids_ptr u32, dev_doc_off_ptr u64[n_docs + 1], dev_spans_ptr u64[2 n_ids] as (start, end) pairs, n_ids)."""
+        return self._encode_call(text, n_bytes, doc_starts, SPANS_CHARS if chars else 0)
+
+    def encode_spans_to_host(self, text, n_bytes: int | None = None, doc_starts=None, chars: bool = False):
+        """-> (ids u32[n_ids], doc_off u64[n_docs + 1], spans u64[n_ids, 2]) copied to the host."""
+        n_docs = len(doc_starts) if doc_starts is not None and len(doc_starts) else 1
+        di, dd, ds, ni = self.encode_spans(text, n_bytes, doc_starts, chars)
+        ids = self.d2h(di, 4 * ni, np.uint32) if ni else np.zeros(0, np.uint32)
+        spans = self.d2h(ds, 16 * ni, np.uint64).reshape(-1, 2) if ni else np.zeros((0, 2), np.uint64)
+        return ids, self.d2h(dd, 8 * (n_docs + 1), np.uint64), spans
 
     def encode_free(self) -> None:
         self._chk(lib().yabpe_encode_free(self._h))

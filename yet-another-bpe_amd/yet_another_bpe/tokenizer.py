@@ -4,7 +4,9 @@ Plain Python, same public API as the reference `src/yet_another_bpe/tokenizer.py
 (encode, decode, encode_batch, decode_batch, from_file, vocab_size, special_tokens, get_vocab,
 clear_cache, cache_info, _encode_word).  encode / encode_batch / decode / decode_batch stay plain Python;
 encode_array / encode_batch_device compute the same ids on the GPU (yabpe_encode, include/yabpe.h), and
-decode_array / decode_batch_device the same text (yabpe_decode).
+decode_array / decode_batch_device the same text (yabpe_decode).  encode_with_offsets / encode_batch_with_offsets also say
+which bytes or characters of the text every id covers; encode_array_with_offsets / encode_batch_device_with_offsets compute
+the same on the GPU (yabpe_encode_spans).
 """
 from __future__ import annotations
 
@@ -38,6 +40,7 @@ class BBPETokenizer:
             ordered = sorted(self._special_tokens, key=len, reverse=True)
             self._special_pattern = regex.compile("(" + "|".join(regex.escape(t) for t in ordered) + ")")
         self._word_ids = lru_cache(maxsize=_WORD_CACHE)(self._word_ids_uncached)
+        self._word_lens = lru_cache(maxsize=_WORD_CACHE)(self._word_lens_uncached)  # (a cache of its own: cache_info is _word_ids')
         self._device_ctx = None  # created on the first device call (encode_array / decode_array and their batch forms)
         self._device_models: set[str] = set()  # models uploaded to it: "encode", "decode" (each on its first use)
 
@@ -82,11 +85,7 @@ class BBPETokenizer:
         return cls(vocab=vocab, merges=merges, special_tokens=specials)
 
     # ------------------------------------------------------------------ encode
-    def _word_ids_uncached(self, word: str) -> tuple[int, ...]:
-        data = word.encode("utf-8")
-        if not data:
-            return ()
-        unk = self._vocab.get(b"[UNK]", 0)
+    def _word_parts(self, data: bytes) -> list[bytes]:
         parts = [bytes([b]) for b in data]
         rank = self._rank
         while len(parts) > 1:
@@ -98,7 +97,18 @@ class BBPETokenizer:
             if best_rank is None:
                 break
             parts[best_i:best_i + 2] = [parts[best_i] + parts[best_i + 1]]
-        return tuple(self._vocab.get(p, unk) for p in parts)
+        return parts
+
+    def _word_ids_uncached(self, word: str) -> tuple[int, ...]:
+        data = word.encode("utf-8")
+        if not data:
+            return ()
+        unk = self._vocab.get(b"[UNK]", 0)
+        return tuple(self._vocab.get(p, unk) for p in self._word_parts(data))
+
+    def _word_lens_uncached(self, word: str) -> tuple[int, ...]:
+        """The byte length of every part of the word: one per id of _word_ids(word), in the vocab or not."""
+        return tuple(len(p) for p in self._word_parts(word.encode("utf-8")))
 
     def _encode_word(self, word: str) -> list[int]:
         return list(self._word_ids(word))
@@ -128,6 +138,62 @@ class BBPETokenizer:
     def encode_batch(self, texts: Sequence[str]) -> list[list[int]]:
         return [self.encode(t) for t in texts]
 
+    # ------------------------------------------------------------------ encode with offsets
+    def _byte_spans(self, text: str) -> tuple[list[int], list[tuple[int, int]]]:
+        ids: list[int] = []
+        spans: list[tuple[int, int]] = []
+        pos = 0  # byte offset into text.encode("utf-8"); the parts of the special split and the pre-tokens tile the text
+
+        def plain(part: str) -> None:
+            nonlocal pos
+            for pre in self._pattern.findall(part):
+                ids.extend(self._word_ids(pre))
+                for n in self._word_lens(pre):
+                    spans.append((pos, pos + n))
+                    pos += n
+
+        if self._special_pattern is None:
+            plain(text)
+            return ids, spans
+        for part in self._special_pattern.split(text):
+            if not part:
+                continue
+            if part in self._special_set:
+                data = part.encode("utf-8")
+                tid = self._vocab.get(data)
+                if tid is not None:
+                    ids.append(tid)
+                    spans.append((pos, pos + len(data)))
+                pos += len(data)  # (without an id: no span, a gap)
+            else:
+                plain(part)
+        return ids, spans
+
+    def encode_with_offsets(self, text: str, unit: str = "char") -> tuple[list[int], list[tuple[int, int]]]:
+        """-> (encode(text), one (start, end) per id).  unit "byte": offsets into text.encode("utf-8"), the bytes the token was
+        merged from (also when the vocab lacks it and the id is [UNK]'s); a special with an id spans its occurrence, one without
+        an id leaves a gap; everything else tiles the text in ascending order.  unit "char": code-point offsets into text, the
+        smallest run of whole characters that covers the token's bytes -- with lead(p) = the non-continuation bytes below p,
+        (lead(start + 1) - 1, lead(end))."""
+        if unit not in ("char", "byte"):
+            raise ValueError(f"unit must be 'char' or 'byte', not {unit!r}")
+        if not text:
+            return [], []
+        ids, spans = self._byte_spans(text)
+        if unit == "char" and spans:
+            data = np.frombuffer(text.encode("utf-8"), dtype=np.uint8)
+            if len(data) != len(text):  # (all ASCII: a byte is a character)
+                lead = np.zeros(len(data) + 1, dtype=np.int64)
+                np.cumsum((data & 0xC0) != 0x80, out=lead[1:])
+                lead = lead.tolist()
+                spans = [(lead[s + 1] - 1, lead[e]) for s, e in spans]
+        return ids, spans
+
+    def encode_batch_with_offsets(self, texts: Sequence[str], unit: str = "char"):
+        if unit not in ("char", "byte"):
+            raise ValueError(f"unit must be 'char' or 'byte', not {unit!r}")
+        return [self.encode_with_offsets(t, unit) for t in texts]
+
     # ------------------------------------------------------------------ encode on the GPU (yabpe_encode; same ids as encode)
     def _device(self, model: str = "encode"):
         if self._device_ctx is None:
@@ -143,26 +209,49 @@ class BBPETokenizer:
             self._device_models.add(model)
         return self._device_ctx
 
+    @staticmethod
+    def _device_input(texts):
+        """-> (the documents' bytes back to back, their starts), or None for an empty sequence"""
+        if isinstance(texts, (bytes, bytearray, memoryview)):
+            return bytes(texts), [0]
+        blobs = [t.encode("utf-8") for t in texts]
+        if not blobs:
+            return None
+        starts = np.zeros(len(blobs), dtype=np.uint64)
+        starts[1:] = np.cumsum([len(b) for b in blobs], dtype=np.uint64)[:-1]
+        return b"".join(blobs), starts
+
     def encode_array(self, texts) -> tuple[np.ndarray, np.ndarray]:
         """Encodes on the GPU: `texts` is a sequence of str (one document each) or one bytes buffer (one document).
         -> (ids np.uint32[n], doc_off np.uint64[n_docs + 1]): document d's ids are ids[doc_off[d]:doc_off[d + 1]], equal to
         encode(texts[d]).  Malformed UTF-8 in a bytes buffer raises _native.Utf8Error (.position = UnicodeDecodeError.start)."""
-        if isinstance(texts, (bytes, bytearray, memoryview)):
-            data, starts = bytes(texts), [0]
-        else:
-            blobs = [t.encode("utf-8") for t in texts]
-            if not blobs:
-                return np.zeros(0, np.uint32), np.zeros(1, np.uint64)
-            data = b"".join(blobs)
-            starts = np.zeros(len(blobs), dtype=np.uint64)
-            starts[1:] = np.cumsum([len(b) for b in blobs], dtype=np.uint64)[:-1]
-        return self._device().encode_to_host(np.frombuffer(data, dtype=np.uint8), doc_starts=starts)
+        inp = self._device_input(texts)
+        if inp is None:
+            return np.zeros(0, np.uint32), np.zeros(1, np.uint64)
+        return self._device().encode_to_host(np.frombuffer(inp[0], dtype=np.uint8), doc_starts=inp[1])
 
     def encode_batch_device(self, texts: Sequence[str]) -> list[list[int]]:
         """encode_batch(texts), computed on the GPU in one call."""
         ids, off = self.encode_array(texts)
         ids, off = ids.tolist(), off.tolist()
         return [ids[off[d]:off[d + 1]] for d in range(len(off) - 1)]
+
+    def encode_array_with_offsets(self, texts, unit: str = "char") -> tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """encode_array(texts) plus every id's span, computed on the GPU in the same call.
+        -> (ids np.uint32[n], doc_off np.uint64[n_docs + 1], offsets np.uint64[n, 2]): offsets[k] = (start, end) of id k in its
+        own document, as encode_with_offsets(texts[d], unit) gives them."""
+        if unit not in ("char", "byte"):
+            raise ValueError(f"unit must be 'char' or 'byte', not {unit!r}")
+        inp = self._device_input(texts)
+        if inp is None:
+            return np.zeros(0, np.uint32), np.zeros(1, np.uint64), np.zeros((0, 2), np.uint64)
+        return self._device().encode_spans_to_host(np.frombuffer(inp[0], dtype=np.uint8), doc_starts=inp[1], chars=unit == "char")
+
+    def encode_batch_device_with_offsets(self, texts: Sequence[str], unit: str = "char"):
+        """encode_batch_with_offsets(texts, unit), computed on the GPU in one call."""
+        ids, off, spans = self.encode_array_with_offsets(texts, unit)
+        ids, off, spans = ids.tolist(), off.tolist(), [tuple(p) for p in spans.tolist()]
+        return [(ids[off[d]:off[d + 1]], spans[off[d]:off[d + 1]]) for d in range(len(off) - 1)]
 
     # ------------------------------------------------------------------ decode (tokenizer.py:324-349)
     def decode(self, ids: Sequence[int]) -> str:
