@@ -24,6 +24,7 @@
 #include "../../include/yabpe.h"
 #include "yabpe_kernels.h"
 #include "yabpe_aux_kernels.h"
+#include "yabpe_devmem.h"
 #include "yabpe_pretok_kernels.h"
 #include "yabpe_encode_kernels.h"
 #include "yabpe_decode_kernels.h"
@@ -260,90 +261,10 @@ int fail(yabpe_ctx *c, int code, const char *fmt, ...) {
                         rccl() && rccl()->GetErrorString ? rccl()->GetErrorString(r__) : "?", __FILE__, __LINE__); \
     } while (0)
 
-static bool trace_alloc_on() {
-    static const bool on = [] { const char *e = getenv("YABPE_TRACE_ALLOC"); return e && *e == '1'; }();
-    return on;
-}
-
-// Device allocations go through a small per-process cache: a training job allocates a few large buffers (tiles,
-// signatures, worklists, retile targets) and frees them at the end, and the next job asks for the same sizes again.
-// hipMalloc / hipFree of multi-GB buffers are host-side stalls of anywhere from 1 ms to 100+ ms depending on the state of
-// the driver's page tables (measured: 14 ms vs 340 ms for the same yabpe_load_words on two boxes) -- time the GPU idles.
-// Freed blocks are kept (up to YABPE_POOL_MAX_GIB, default 24) and handed out again to requests of the same rounded size.
-struct DevPool {
-    std::mutex m;
-    std::multimap<std::pair<int, size_t>, void *> free_blocks;  // (device, bytes) -> block
-    std::map<void *, std::pair<int, size_t>> live;              // block -> (device, bytes)
-    size_t held = 0;
-    size_t cap = [] { const char *e = getenv("YABPE_POOL_MAX_GIB"); return (size_t)(e ? atoll(e) : 24) << 30; }();
-};
-static DevPool &pool() {
-    static DevPool *p = new DevPool();  // (never destroyed: device memory is released by the runtime at process exit)
-    return *p;
-}
-static size_t pool_round(size_t bytes) { return bytes >= (1u << 20) ? (bytes + ((2u << 20) - 1)) & ~(size_t)((2u << 20) - 1) : (bytes + 255) & ~(size_t)255; }
-static void pool_trim(int dev, size_t need_free) {  // give cached blocks back to the runtime (largest first)
-    DevPool &P = pool();
-    size_t freed = 0;
-    while (freed < need_free && !P.free_blocks.empty()) {
-        auto it = std::prev(P.free_blocks.end());
-        (void)dev;
-        freed += it->first.second;
-        P.held -= it->first.second;
-        (void)hipFree(it->second);
-        P.free_blocks.erase(it);
-    }
-}
-static hipError_t pool_alloc(int dev, void **out, size_t bytes) {
-    DevPool &P = pool();
-    const size_t rb = pool_round(bytes);
-    std::lock_guard<std::mutex> g(P.m);
-    auto it = P.free_blocks.find({dev, rb});
-    if (it != P.free_blocks.end()) {
-        *out = it->second;
-        P.held -= rb;
-        P.free_blocks.erase(it);
-        P.live[*out] = {dev, rb};
-        return hipSuccess;
-    }
-    hipError_t e = hipMalloc(out, rb);
-    if (e != hipSuccess) {  // out of memory with blocks in the cache: release them and try once more
-        (void)hipGetLastError();
-        pool_trim(dev, ~(size_t)0);
-        e = hipMalloc(out, rb);
-    }
-    if (e == hipSuccess) P.live[*out] = {dev, rb};
-    return e;
-}
-static void pool_free(void *p) {
-    DevPool &P = pool();
-    std::lock_guard<std::mutex> g(P.m);
-    auto it = P.live.find(p);
-    if (it == P.live.end()) {  // not ours (allocated with hipMalloc directly)
-        (void)hipFree(p);
-        return;
-    }
-    const auto key = it->second;
-    P.live.erase(it);
-    if (key.second > P.cap) {
-        (void)hipFree(p);
-        return;
-    }
-    if (P.held + key.second > P.cap) pool_trim(key.first, P.held + key.second - P.cap);
-    P.free_blocks.insert({key, p});
-    P.held += key.second;
-}
-
-// YABPE_TRACE_ALLOC=1: every device allocation of the library goes to stderr (address range, element size) -- the map
-// that tells which buffer a "Memory access fault ... on address X" belongs to or lies next to.
+// Device memory comes from the block cache of yabpe_devmem.h; these two add the context's error text.
 template <class T>
 int dmalloc(yabpe_ctx *c, T **p, uint64_t n) {
-    *p = nullptr;
-    if (n == 0) n = 1;
-    HIPCHK(c, pool_alloc(c ? c->device : 0, (void **)p, n * sizeof(T)));
-    if (trace_alloc_on())
-        fprintf(stderr, "[yabpe alloc r%d] %p .. %p  %llu x %zu B\n", c ? c->rank : -1, (void *)*p, (void *)((char *)*p + n * sizeof(T)),
-                (unsigned long long)n, sizeof(T));
+    HIPCHK(c, dev_alloc(c ? c->device : 0, c ? c->rank : -1, (void **)p, n * sizeof(T)));
     return 0;
 }
 #define TRY(x)               \
@@ -352,10 +273,7 @@ int dmalloc(yabpe_ctx *c, T **p, uint64_t n) {
         if (r__ != 0) return r__; \
     } while (0)
 
-void dfree(void *p) {
-    if (p && trace_alloc_on()) fprintf(stderr, "[yabpe free] %p\n", p);
-    if (p) pool_free(p);
-}
+void dfree(void *p) { dev_free(p); }
 
 int64_t optv(yabpe_ctx *c, const char *k, int64_t dflt) {
     auto it = c->opt.find(k);
@@ -929,19 +847,26 @@ int retile_flat(yabpe_ctx *c) {
 }  // namespace
 
 namespace {
-// The device buffers of one yabpe_encode call (released on every way out).
-struct EncScratch {
-    std::vector<void *> bufs;
-    template <class T>
-    int get(yabpe_ctx *c, T **p, uint64_t n) {
-        TRY(dmalloc(c, p, n));
-        bufs.push_back(*p);
-        return 0;
-    }
-    ~EncScratch() {
-        for (void *p : bufs) dfree(p);
-    }
-};
+// *dst = src if it already is device memory with the asked alignment, else a copy of it that S owns (bytes == 0: src).
+template <class T>
+int to_device(yabpe_ctx *c, Scratch &S, const T *src, uint64_t bytes, uintptr_t align, const T **dst) {
+    *dst = src;
+    const bool on_dev = is_device_ptr(src);
+    if (bytes == 0 || (on_dev && ((uintptr_t)src & (align - 1)) == 0)) return 0;
+    uint8_t *own = nullptr;
+    HIPCHK(c, S.get(&own, bytes));
+    HIPCHK(c, hipMemcpy(own, src, bytes, on_dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice));
+    *dst = (const T *)own;
+    return 0;
+}
+
+// the document starts of encode (what = "text") and decode ("ids"): host array, validated before a kernel indexes with it
+int check_starts(yabpe_ctx *c, const uint64_t *starts, uint32_t n, uint64_t limit, const char *what) {
+    if (!starts || !n || starts[0] != 0) return fail(c, YABPE_E_INVALID, "doc_off must hold n_docs >= 1 starts, the first one 0");
+    for (uint32_t d = 1; d < n; ++d)
+        if (starts[d] < starts[d - 1] || starts[d] > limit) return fail(c, YABPE_E_INVALID, "document starts must ascend inside the %s", what);
+    return 0;
+}
 }  // namespace
 
 // =================================================================================================== C ABI
@@ -1150,81 +1075,52 @@ static int load_words_impl(yabpe_ctx *c, const uint8_t *bytes, const uint64_t *w
     if (!word_off) return fail(c, YABPE_E_INVALID, "word_off is NULL");
     if (n_words >= 0xFFFFFFFFull) return fail(c, YABPE_E_CAPACITY, "more than 2^32-2 words per context");
     free_corpus(c);
-    // (temporaries of the resumed load and the events: released on every way out of this function)
-    struct Temps {
+    struct Events {  // (destroyed on every way out)
         hipEvent_t ev0 = nullptr, ev1 = nullptr, ev_seg = nullptr;
-        uint32_t *wcnt = nullptr, *llen = nullptr, *ltok = nullptr, *lnxt = nullptr, *lprv = nullptr;
-        uint16_t *wtok = nullptr;
-        unsigned long long *tokoff = nullptr, *lbase = nullptr, *lheap = nullptr;
-        void free_walk() {
-            dfree(llen); dfree(lbase); dfree(ltok); dfree(lnxt); dfree(lprv); dfree(lheap);
-            llen = ltok = lnxt = lprv = nullptr;
-            lbase = lheap = nullptr;
-        }
-        ~Temps() {
-            free_walk();
-            dfree(wcnt); dfree(wtok); dfree(tokoff);
+        ~Events() {
             if (ev0) (void)hipEventDestroy(ev0);
             if (ev1) (void)hipEventDestroy(ev1);
             if (ev_seg) (void)hipEventDestroy(ev_seg);
         }
-    } tmp;
-    hipEvent_t &ev0 = tmp.ev0, &ev1 = tmp.ev1, &ev_seg = tmp.ev_seg;
+    } evs;
+    hipEvent_t &ev0 = evs.ev0, &ev1 = evs.ev1, &ev_seg = evs.ev_seg;
     HIPCHK(c, hipEventCreate(&ev0));
     HIPCHK(c, hipEventCreate(&ev1));
+    Scratch S(c->device, c->rank);  // every temporary of the load: staged inputs, pooled words, walk buffers, long-word lists
 
     // ---- make inputs device-resident
     const unsigned long long *d_off = nullptr;
-    const uint8_t *d_bytes = nullptr;
+    const uint8_t *d_bytes = bytes;
     const unsigned long long *d_freq = nullptr;
-    void *own_off = nullptr, *own_bytes = nullptr, *own_freq = nullptr;
     uint64_t total_bytes = 0, off_base = 0;
     if (is_device_ptr(word_off)) {
-        d_off = (const unsigned long long *)word_off;
         HIPCHK(c, hipMemcpy(&total_bytes, word_off + n_words, 8, hipMemcpyDeviceToHost));
         HIPCHK(c, hipMemcpy(&off_base, word_off, 8, hipMemcpyDeviceToHost));
         total_bytes -= off_base;
     } else {
         off_base = word_off[0];
         total_bytes = word_off[n_words] - off_base;
-        HIPCHK(c, hipMalloc(&own_off, (n_words + 1) * 8));
-        HIPCHK(c, hipMemcpy(own_off, word_off, (n_words + 1) * 8, hipMemcpyHostToDevice));
-        d_off = (const unsigned long long *)own_off;
     }
+    TRY(to_device(c, S, (const unsigned long long *)word_off, (n_words + 1) * 8, 1, &d_off));
     if (total_bytes && !bytes) return fail(c, YABPE_E_INVALID, "bytes is NULL");
-    if (is_device_ptr(bytes) || total_bytes == 0) {
-        d_bytes = bytes;
-    } else {
-        HIPCHK(c, hipMalloc(&own_bytes, total_bytes));
-        HIPCHK(c, hipMemcpy(own_bytes, bytes + off_base, total_bytes, hipMemcpyHostToDevice));
-        d_bytes = (const uint8_t *)own_bytes - off_base;  // offsets stay absolute
+    if (total_bytes) {
+        TRY(to_device(c, S, bytes + off_base, total_bytes, 1, &d_bytes));
+        d_bytes -= off_base;  // offsets stay absolute
     }
-    if (word_freq) {
-        if (is_device_ptr(word_freq)) {
-            d_freq = (const unsigned long long *)word_freq;
-        } else {
-            HIPCHK(c, hipMalloc(&own_freq, std::max<uint64_t>(n_words, 1) * 8));
-            HIPCHK(c, hipMemcpy(own_freq, word_freq, n_words * 8, hipMemcpyHostToDevice));
-            d_freq = (const unsigned long long *)own_freq;
-        }
-    }
-    uint32_t *&d_wcnt = tmp.wcnt;             // resumed load: tokens per word after the replay ...
-    uint16_t *&d_wtok = tmp.wtok;             // ... the tokens, word w's where its bytes start ...
-    unsigned long long *&d_tokoff = tmp.tokoff; // ... and the exclusive scan of the counts
-    auto cleanup_inputs = [&]() {
-        dfree(own_off); dfree(own_bytes); dfree(own_freq); own_off = own_bytes = own_freq = nullptr;
-        dfree(d_wcnt); dfree(d_wtok); dfree(d_tokoff); d_wcnt = nullptr; d_wtok = nullptr; d_tokoff = nullptr;
-    };
+    if (word_freq) TRY(to_device(c, S, (const unsigned long long *)word_freq, n_words * 8, 1, &d_freq));
+    uint32_t *d_wcnt = nullptr;             // resumed load: tokens per word after the replay ...
+    uint16_t *d_wtok = nullptr;             // ... the tokens, word w's where its bytes start ...
+    unsigned long long *d_tokoff = nullptr; // ... and the exclusive scan of the counts
     HIPCHK(c, hipEventRecord(ev0, c->stream));
 
     c->n_words_input = n_words;
     // ---- optional device-side pooling of equal words (trainer.py:221-225)
     DedupOut dd{};
     if ((flags & YABPE_LOAD_DEDUP) && n_words > 0) {
-        int r = dedup_words(c->stream, d_bytes, d_off, d_freq, n_words, total_bytes, &dd);
-        if (r != 0) { cleanup_inputs(); return fail(c, YABPE_E_HIP, "device dedup failed (%d): %s", r, hipGetErrorString(hipGetLastError())); }
-        cleanup_inputs();
-        own_bytes = dd.bytes; own_off = dd.off; own_freq = dd.freq;
+        int r = dedup_words(c->stream, d_bytes, d_off, d_freq, n_words, &dd);
+        if (r != 0) return fail(c, YABPE_E_HIP, "device dedup failed (%d): %s", r, hipGetErrorString(hipGetLastError()));
+        S.release();  // (the staged inputs: the pooled words replace them)
+        S.adopt(dd.bytes); S.adopt(dd.off); S.adopt(dd.freq);
         d_bytes = dd.bytes; d_off = dd.off; d_freq = dd.freq;
         n_words = dd.n_unique;
         total_bytes = dd.total_bytes;
@@ -1242,44 +1138,41 @@ static int load_words_impl(yabpe_ctx *c, const uint8_t *bytes, const uint64_t *w
         c->resume_stats = yabpe_resume_stats_t{};
         c->resume_stats.n_unique = n_words;
         if (n_words) {
-            uint32_t *&d_llen = tmp.llen, *&d_ltok = tmp.ltok, *&d_lnxt = tmp.lnxt, *&d_lprv = tmp.lprv;
-            unsigned long long *&d_lbase = tmp.lbase, *&d_lheap = tmp.lheap;
-            TRY(dmalloc(c, &d_wcnt, n_words));
-            TRY(dmalloc(c, &d_wtok, std::max<uint64_t>(total_bytes, 1)));
-            TRY(dmalloc(c, &d_tokoff, n_words + 1));
-            TRY(dmalloc(c, &d_llen, n_words));
-            TRY(dmalloc(c, &d_lbase, n_words + 1));
+            uint32_t *d_llen = nullptr, *d_ltok = nullptr, *d_lnxt = nullptr, *d_lprv = nullptr;
+            unsigned long long *d_lbase = nullptr, *d_lheap = nullptr;
+            HIPCHK(c, S.get(&d_wcnt, n_words));
+            HIPCHK(c, S.get(&d_wtok, total_bytes));
+            HIPCHK(c, S.get(&d_tokoff, n_words + 1));
+            HIPCHK(c, S.get(&d_llen, n_words));
+            HIPCHK(c, S.get(&d_lbase, n_words + 1));
             HIPCHK(c, hipMemsetAsync(&c->scratch64[2], 0, 8, c->stream));
             hipLaunchKernelGGL(k_replay_llen, dim3(cdiv64(n_words, 256)), dim3(256), 0, c->stream, d_off, (unsigned long long)n_words, d_llen, (uint32_t *)&c->scratch64[2]);
             HIPCHK(c, hipGetLastError());
-            if (exclusive_scan<uint32_t>(c->stream, d_llen, n_words, d_lbase, (unsigned long long)n_words + 1) != 0) {
-                cleanup_inputs();
+            if (exclusive_scan<uint32_t>(c->stream, d_llen, n_words, d_lbase, (unsigned long long)n_words + 1) != 0)
                 return fail(c, YABPE_E_HIP, "scan of the long words failed: %s", hipGetErrorString(hipGetLastError()));
-            }
             unsigned long long long_bytes = 0, too_long = 0;
             HIPCHK(c, hipMemcpyAsync(&long_bytes, d_lbase + n_words, 8, hipMemcpyDeviceToHost, c->stream));
             HIPCHK(c, hipMemcpyAsync(&too_long, &c->scratch64[2], 8, hipMemcpyDeviceToHost, c->stream));
             HIPCHK(c, hipStreamSynchronize(c->stream));
-            if (too_long & 0xFFFFFFFFull) { cleanup_inputs(); return fail(c, YABPE_E_CAPACITY, "a single word longer than 2^32-1 bytes"); }
+            if (too_long & 0xFFFFFFFFull) return fail(c, YABPE_E_CAPACITY, "a single word longer than 2^32-1 bytes");
             if (long_bytes) {
-                TRY(dmalloc(c, &d_ltok, long_bytes));
-                TRY(dmalloc(c, &d_lnxt, long_bytes));
-                TRY(dmalloc(c, &d_lprv, long_bytes));
-                TRY(dmalloc(c, &d_lheap, 3 * long_bytes));
+                HIPCHK(c, S.get(&d_ltok, long_bytes));
+                HIPCHK(c, S.get(&d_lnxt, long_bytes));
+                HIPCHK(c, S.get(&d_lprv, long_bytes));
+                HIPCHK(c, S.get(&d_lheap, 3 * long_bytes));
             }
             ReplayWordsParams RW{d_bytes, d_off, (unsigned long long)off_base, (unsigned long long)n_words, d_lbase, *rp, d_wcnt, d_wtok, d_ltok, d_lnxt, d_lprv, d_lheap};
             const uint32_t grid = (uint32_t)std::min<uint64_t>(cdiv64(n_words, WPB), (uint64_t)std::max(1, c->n_cu) * 8);
             hipLaunchKernelGGL(k_replay_words, dim3(grid), dim3(BLOCK), 0, c->stream, RW);
             HIPCHK(c, hipGetLastError());
-            if (exclusive_scan<uint32_t>(c->stream, d_wcnt, n_words, d_tokoff, (unsigned long long)n_words + 1) != 0) {
-                cleanup_inputs();
+            if (exclusive_scan<uint32_t>(c->stream, d_wcnt, n_words, d_tokoff, (unsigned long long)n_words + 1) != 0)
                 return fail(c, YABPE_E_HIP, "scan of the token counts failed: %s", hipGetErrorString(hipGetLastError()));
-            }
             unsigned long long tt = 0;
             HIPCHK(c, hipMemcpyAsync(&tt, d_tokoff + n_words, 8, hipMemcpyDeviceToHost, c->stream));
             HIPCHK(c, hipStreamSynchronize(c->stream));
             total_tokens = tt;
-            tmp.free_walk();
+            for (void *p : {(void *)d_llen, (void *)d_lbase, (void *)d_ltok, (void *)d_lnxt, (void *)d_lprv, (void *)d_lheap})
+                S.release(p);  // (the walk buffers: gone before the tiles are allocated)
         }
         HIPCHK(c, hipEventRecord(ev_seg, c->stream));
         c->tokens_initial = total_tokens;
@@ -1289,7 +1182,7 @@ static int load_words_impl(yabpe_ctx *c, const uint8_t *bytes, const uint64_t *w
     // ---- tiles
     const uint64_t packed = total_tokens + n_words;
     const uint64_t n_tiles64 = (packed + SPAN - 1) / SPAN;
-    if (n_tiles64 >= 0xFFFFFFF0ull) { cleanup_inputs(); return fail(c, YABPE_E_CAPACITY, "corpus too large for one context"); }
+    if (n_tiles64 >= 0xFFFFFFF0ull) return fail(c, YABPE_E_CAPACITY, "corpus too large for one context");
     c->n_tiles = (uint32_t)n_tiles64;
     c->tiles_cap = c->n_tiles;
     c->tiles_alt_cap = 0;
@@ -1312,8 +1205,8 @@ static int load_words_impl(yabpe_ctx *c, const uint8_t *bytes, const uint64_t *w
         HIPCHK(c, hipMemsetAsync(c->tile_len, 0, (size_t)c->n_tiles * 4, c->stream));
         if (c->weighted) TRY(fill_u32(c, c->tile_wbase, c->n_tiles, 0xFFFFFFFFu));
         HIPCHK(c, hipMemsetAsync(&c->scratch64[2], 0, 16, c->stream));  // [2] = long count (u32), [3] = long tokens
-        dfree(d_long_word);
-        TRY(dmalloc(c, &d_long_word, long_cap));
+        S.release(d_long_word);
+        HIPCHK(c, S.get(&d_long_word, long_cap));
         if (n_words) {
             LoadParams P{d_bytes, d_off, (unsigned long long)off_base, (unsigned long long)n_words, c->tiles, c->tile_len, c->tile_wbase,
                          (uint32_t *)&c->scratch64[2], &c->scratch64[3], d_long_word, long_cap};
@@ -1333,12 +1226,12 @@ static int load_words_impl(yabpe_ctx *c, const uint8_t *bytes, const uint64_t *w
         c->long_tokens = host2[1];
         if (c->n_long <= long_cap) break;
         long_cap = c->n_long;
-        if (attempt == 1) { cleanup_inputs(); return fail(c, YABPE_E_INTERNAL, "long-word list overflow"); }
+        if (attempt == 1) return fail(c, YABPE_E_INTERNAL, "long-word list overflow");
     }
     if (c->weighted) {
         unsigned long long ov = 0;
         HIPCHK(c, hipMemcpy(&ov, &c->scratch64[1], 8, hipMemcpyDeviceToHost));
-        if (ov & 0xFFFFFFFFu) { cleanup_inputs(); return fail(c, YABPE_E_CAPACITY, "a word frequency exceeds 2^32-1"); }
+        if (ov & 0xFFFFFFFFu) return fail(c, YABPE_E_CAPACITY, "a word frequency exceeds 2^32-1");
     }
     // ---- long words: own buffer, one workgroup per word
     if (c->n_long) {
@@ -1348,7 +1241,7 @@ static int load_words_impl(yabpe_ctx *c, const uint8_t *bytes, const uint64_t *w
         HIPCHK(c, hipMemcpy(d_long_word, lw.data(), (size_t)c->n_long * 4, hipMemcpyHostToDevice));
         // where each long word goes: prefix sum of their lengths, on the device
         uint32_t *d_ll = nullptr;
-        TRY(dmalloc(c, &d_ll, c->n_long));
+        HIPCHK(c, S.get(&d_ll, c->n_long));
         TRY(dmalloc(c, &c->long_off, c->n_long + 1));
         HIPCHK(c, hipMemsetAsync(&c->scratch64[2], 0, 8, c->stream));
         if (rp)
@@ -1356,17 +1249,15 @@ static int load_words_impl(yabpe_ctx *c, const uint8_t *bytes, const uint64_t *w
         else
             hipLaunchKernelGGL(k_long_lengths, dim3(cdiv64(c->n_long, 256)), dim3(256), 0, c->stream, d_off, d_long_word, c->n_long, d_ll, (uint32_t *)&c->scratch64[2]);
         HIPCHK(c, hipGetLastError());
-        if (exclusive_scan<uint32_t>(c->stream, d_ll, c->n_long, c->long_off, (unsigned long long)c->n_long + 1) != 0) {
-            cleanup_inputs();
+        if (exclusive_scan<uint32_t>(c->stream, d_ll, c->n_long, c->long_off, (unsigned long long)c->n_long + 1) != 0)
             return fail(c, YABPE_E_HIP, "long-word scan failed: %s", hipGetErrorString(hipGetLastError()));
-        }
         unsigned long long long_total = 0, too_long = 0;
         // (on the context's stream: it does not synchronise with the null stream, and a one-block scan returns without waiting)
         HIPCHK(c, hipMemcpyAsync(&long_total, c->long_off + c->n_long, 8, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipMemcpyAsync(&too_long, &c->scratch64[2], 8, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
-        dfree(d_ll);
-        if (too_long & 0xFFFFFFFFull) { cleanup_inputs(); return fail(c, YABPE_E_CAPACITY, "a single word longer than 2^32-1 bytes"); }
+        S.release(d_ll);
+        if (too_long & 0xFFFFFFFFull) return fail(c, YABPE_E_CAPACITY, "a single word longer than 2^32-1 bytes");
         TRY(dmalloc(c, &c->long_tok, long_total));
         TRY(dmalloc(c, &c->long_len, c->n_long));
         if (c->weighted) TRY(dmalloc(c, &c->long_freq, c->n_long));
@@ -1387,8 +1278,7 @@ static int load_words_impl(yabpe_ctx *c, const uint8_t *bytes, const uint64_t *w
         }
     }
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    dfree(d_long_word);
-    cleanup_inputs();
+    S.release();  // (before the pair table is built)
 
     // ---- state + initial pair count (trainer.py:227-235)
     TRY(state_pull(c));
@@ -1484,16 +1374,12 @@ int yabpe_load_words_resumed(yabpe_ctx *c, const uint8_t *bytes, const uint64_t 
     }
     RpTableHost th;
     rp_build_table(merge_left, merge_right, merge_merged, n_merges, &th);
-    struct TableBufs {  // (released on every way out)
-        uint32_t *key = nullptr, *first = nullptr;
-        RpEntry *ent = nullptr;
-        ~TableBufs() { dfree(key); dfree(first); dfree(ent); }
-    } tb;
-    uint32_t *&d_key = tb.key, *&d_first = tb.first;
-    RpEntry *&d_ent = tb.ent;
-    TRY(dmalloc(c, &d_key, th.idx_key.size()));
-    TRY(dmalloc(c, &d_first, th.idx_first.size()));
-    TRY(dmalloc(c, &d_ent, th.ent.size()));
+    Scratch S(c->device, c->rank);
+    uint32_t *d_key = nullptr, *d_first = nullptr;
+    RpEntry *d_ent = nullptr;
+    HIPCHK(c, S.get(&d_key, th.idx_key.size()));
+    HIPCHK(c, S.get(&d_first, th.idx_first.size()));
+    HIPCHK(c, S.get(&d_ent, th.ent.size()));
     HIPCHK(c, hipMemcpy(d_key, th.idx_key.data(), th.idx_key.size() * 4, hipMemcpyHostToDevice));
     HIPCHK(c, hipMemcpy(d_first, th.idx_first.data(), th.idx_first.size() * 4, hipMemcpyHostToDevice));
     HIPCHK(c, hipMemcpy(d_ent, th.ent.data(), th.ent.size() * sizeof(RpEntry), hipMemcpyHostToDevice));
@@ -2489,38 +2375,31 @@ int yabpe_pretokenize(yabpe_ctx *c, const uint8_t *text, uint64_t n_bytes, const
     }
     TRY(class_table(c));
     // inputs on the device
-    const uint8_t *d_text = text;
-    void *own_text = nullptr;
-    if (n_bytes && !is_device_ptr(text)) {
-        HIPCHK(c, hipMalloc(&own_text, n_bytes));
-        if (hipMemcpy(own_text, text, n_bytes, hipMemcpyHostToDevice) != hipSuccess) { dfree(own_text); return fail(c, YABPE_E_HIP, "staging the text failed"); }
-        d_text = (const uint8_t *)own_text;
-    }
+    Scratch S(c->device, c->rank);
+    const uint8_t *d_text = nullptr;
+    TRY(to_device(c, S, text, n_bytes, 1, &d_text));
     unsigned long long *d_chunks = nullptr;
-    uint8_t *d_spb = nullptr;
-    uint32_t *d_spo = nullptr;
-    auto drop = [&]() { dfree(d_chunks); dfree(d_spb); dfree(d_spo); };
-    if (hipMalloc((void **)&d_chunks, chunks.size() * 8) != hipSuccess ||
-        hipMemcpy(d_chunks, chunks.data(), chunks.size() * 8, hipMemcpyHostToDevice) != hipSuccess) { drop(); dfree(own_text); return fail(c, YABPE_E_HIP, "chunk table"); }
+    if (S.get(&d_chunks, chunks.size()) != hipSuccess ||
+        hipMemcpy(d_chunks, chunks.data(), chunks.size() * 8, hipMemcpyHostToDevice) != hipSuccess) return fail(c, YABPE_E_HIP, "chunk table");
     PtSpecials sp{nullptr, nullptr, n_special, max_len};
     if (n_special) {
         const uint32_t tot = special_off[n_special];
-        if (hipMalloc((void **)&d_spb, tot) != hipSuccess || hipMalloc((void **)&d_spo, (n_special + 1) * 4) != hipSuccess ||
+        uint8_t *d_spb = nullptr;
+        uint32_t *d_spo = nullptr;
+        if (S.get(&d_spb, tot) != hipSuccess || S.get(&d_spo, n_special + 1) != hipSuccess ||
             hipMemcpy(d_spb, special_bytes, tot, hipMemcpyHostToDevice) != hipSuccess ||
-            hipMemcpy(d_spo, special_off, (n_special + 1) * 4, hipMemcpyHostToDevice) != hipSuccess) { drop(); dfree(own_text); return fail(c, YABPE_E_HIP, "special token table"); }
+            hipMemcpy(d_spo, special_off, (n_special + 1) * 4, hipMemcpyHostToDevice) != hipSuccess) return fail(c, YABPE_E_HIP, "special token table");
         sp.bytes = d_spb;
         sp.off = d_spo;
     }
     PretokOut po{};
-    const int r = pretokenize(c->stream, d_text, n_bytes, d_chunks, (uint32_t)chunks.size(), c->pt_cls, sp, &po);
-    drop();
-    if (r != 0) { dfree(own_text); return fail(c, YABPE_E_HIP, "pre-tokeniser failed: %s", hipGetErrorString(hipGetLastError())); }
+    if (pretokenize(c->stream, d_text, n_bytes, d_chunks, (uint32_t)chunks.size(), c->pt_cls, sp, &po) != 0)
+        return fail(c, YABPE_E_HIP, "pre-tokeniser failed: %s", hipGetErrorString(hipGetLastError()));
     if (po.bad_pos >= 0) {
-        dfree(own_text);
         *out_bad_pos = po.bad_pos;
         return fail(c, YABPE_E_UTF8, "invalid UTF-8 at byte %lld", po.bad_pos);
     }
-    if (own_text) c->pretok_bufs.push_back(own_text);
+    if (d_text != text) c->pretok_bufs.push_back(S.take(const_cast<uint8_t *>(d_text)));  // (the staged text is handed out)
     c->pretok_bufs.push_back(po.off);
     *out_dev_text = d_text;
     *out_dev_word_off = (uint64_t *)po.off;
@@ -2599,9 +2478,7 @@ static int encode_run(yabpe_ctx *c, const uint8_t *text, uint64_t n_bytes, const
     if (span_flags & ~YABPE_SPANS_CHARS) return fail(c, YABPE_E_INVALID, "unknown flags 0x%x", span_flags);
     if (!c->have_enc_model) return fail(c, YABPE_E_INVALID, "no model: call yabpe_encode_set_model first");
     if (n_bytes && !text) return fail(c, YABPE_E_INVALID, "text is NULL");
-    if (!doc_off || !n_docs || doc_off[0] != 0) return fail(c, YABPE_E_INVALID, "doc_off must hold n_docs >= 1 starts, the first one 0");
-    for (uint32_t d = 1; d < n_docs; ++d)
-        if (doc_off[d] < doc_off[d - 1] || doc_off[d] > n_bytes) return fail(c, YABPE_E_INVALID, "document starts must ascend inside the text");
+    TRY(check_starts(c, doc_off, n_docs, n_bytes, "text"));
     yabpe_encode_free(c);
     c->enc_done = false;
     c->enc_stats = yabpe_encode_stats_t{};
@@ -2612,22 +2489,12 @@ static int encode_run(yabpe_ctx *c, const uint8_t *text, uint64_t n_bytes, const
         if (!e) HIPCHK(c, hipEventCreate(&e));
     hipStream_t s = c->stream;
     const unsigned long long n = n_bytes;
-    EncScratch S;
-    // inputs on the device
-    const uint8_t *d_text = text;
-    if (n && !is_device_ptr(text)) {
-        uint8_t *own = nullptr;
-        TRY(S.get(c, &own, n));
-        HIPCHK(c, hipMemcpy(own, text, n, hipMemcpyHostToDevice));
-        d_text = own;
-    } else if (n && chars && ((uintptr_t)text & 15)) { // enc_lead reads the text in aligned 16-byte chunks
-        uint8_t *own = nullptr;
-        TRY(S.get(c, &own, n));
-        HIPCHK(c, hipMemcpy(own, text, n, hipMemcpyDeviceToDevice));
-        d_text = own;
-    }
+    Scratch S(c->device, c->rank);
+    // inputs on the device (enc_lead reads the text in aligned 16-byte chunks)
+    const uint8_t *d_text = nullptr;
+    TRY(to_device(c, S, text, n, chars ? 16 : 1, &d_text));
     unsigned long long *d_docs = nullptr;
-    TRY(S.get(c, &d_docs, n_docs));
+    HIPCHK(c, S.get(&d_docs, n_docs));
     HIPCHK(c, hipMemcpy(d_docs, doc_off, (size_t)n_docs * 8, hipMemcpyHostToDevice));
     TRY(dmalloc(c, &c->enc_doc, (uint64_t)n_docs + 1));
     unsigned long long *doc_ids = (unsigned long long *)c->enc_doc;
@@ -2649,10 +2516,10 @@ static int encode_run(yabpe_ctx *c, const uint8_t *text, uint64_t n_bytes, const
     // ---- split: document marks, the special split, classes / UTF-8 / pre-token starts
     uint8_t *meta = nullptr, *flags = nullptr, *sflag = nullptr;
     unsigned long long *err = nullptr;
-    TRY(S.get(c, &meta, n));
-    TRY(S.get(c, &flags, n + 8));
-    TRY(S.get(c, &err, 1));
-    if (c->enc_n_special) TRY(S.get(c, &sflag, n));
+    HIPCHK(c, S.get(&meta, n));
+    HIPCHK(c, S.get(&flags, n + 8));
+    HIPCHK(c, S.get(&err, 1));
+    if (c->enc_n_special) HIPCHK(c, S.get(&sflag, n));
     HIPCHK(c, hipEventRecord(c->enc_ev[0], s));
     HIPCHK(c, hipMemsetAsync(meta, 0, n, s));
     HIPCHK(c, hipMemsetAsync(err, 0xff, 8, s));
@@ -2677,58 +2544,27 @@ static int encode_run(yabpe_ctx *c, const uint8_t *text, uint64_t n_bytes, const
         return fail(c, YABPE_E_UTF8, "invalid UTF-8 at byte %llu", h_err);
     }
     // ---- pre-token offsets
-    const unsigned long long nb = (n + PT_PER_BLOCK - 1) / PT_PER_BLOCK;
-    unsigned long long *sums = nullptr, *bases = nullptr, *off = nullptr;
-    TRY(S.get(c, &sums, nb));
-    TRY(S.get(c, &bases, nb + 1));
-    hipLaunchKernelGGL(k_pt_count, dim3((uint32_t)nb), dim3(BLOCK), 0, s, flags, n, sums);
-    HIPCHK(c, hipGetLastError());
-    if (exclusive_scan<unsigned long long>(s, sums, nb, bases, nb + 1) != 0) return fail(c, YABPE_E_HIP, "scan of the start counts failed");
-    unsigned long long n_pre = 0;
-    HIPCHK(c, hipMemcpyAsync(&n_pre, bases + nb, 8, hipMemcpyDeviceToHost, s));
-    HIPCHK(c, hipStreamSynchronize(s));
-    if (n_pre > 0xFFFFFFFEull) return fail(c, YABPE_E_CAPACITY, "%llu pre-tokens in one call: at most 2^32 - 2", n_pre);
-    TRY(S.get(c, &off, n_pre + 1));
-    hipLaunchKernelGGL(k_pt_scatter, dim3((uint32_t)nb), dim3(BLOCK), 0, s, flags, n, bases, off);
-    HIPCHK(c, hipMemcpyAsync(off + n_pre, &n, 8, hipMemcpyHostToDevice, s));
-    HIPCHK(c, hipGetLastError());
+    unsigned long long *off = nullptr, n_pre = 0;
+    const int pr = pt_offsets(s, S, flags, n, 0xFFFFFFFEull, &off, &n_pre);
+    if (pr == -2) return fail(c, YABPE_E_CAPACITY, "%llu pre-tokens in one call: at most 2^32 - 2", n_pre);
+    if (pr != 0) return fail(c, YABPE_E_HIP, "pre-token offsets failed: %s", hipGetErrorString(hipGetLastError()));
     HIPCHK(c, hipEventRecord(c->enc_ev[2], s));
     // ---- pooling: each pre-token's representative, the list of unique words
-    unsigned long long cap = 1024;
-    while (cap < n_pre * 2) cap <<= 1;
-    unsigned long long *hash = nullptr, *count = nullptr, *uidx = nullptr, *uoff = nullptr;
-    uint32_t *slots = nullptr, *rep = nullptr, *flag = nullptr, *ulen = nullptr;
-    TRY(S.get(c, &hash, n_pre));
-    TRY(S.get(c, &count, n_pre));
-    TRY(S.get(c, &slots, cap));
-    TRY(S.get(c, &rep, n_pre));
-    TRY(S.get(c, &flag, n_pre));
-    TRY(S.get(c, &ulen, n_pre));
-    TRY(S.get(c, &uidx, n_pre + 1));
-    TRY(S.get(c, &uoff, n_pre + 1));
+    PoolOut pw{};
+    if (pool_words(s, S, d_text, off, nullptr, n_pre, &pw) != 0)
+        return fail(c, YABPE_E_HIP, "pooling of the pre-tokens failed: %s", hipGetErrorString(hipGetLastError()));
+    uint32_t *const rep = pw.rep, *const flag = pw.flag, *const ulen = pw.ulen;
+    unsigned long long *const count = pw.count, *const uidx = pw.uidx, *const uoff = pw.uoff;
+    const unsigned long long nu = pw.n_unique, ubytes = pw.unique_bytes;
     const uint32_t pgrid = (uint32_t)((n_pre + 255) / 256);
-    HIPCHK(c, hipMemsetAsync(slots, 0xFF, cap * 4, s));
-    HIPCHK(c, hipMemsetAsync(count, 0, n_pre * 8, s));
-    hipLaunchKernelGGL(k_word_hash, dim3(pgrid), dim3(256), 0, s, d_text, off, n_pre, hash);
-    hipLaunchKernelGGL(k_word_dedup, dim3(pgrid), dim3(256), 0, s, d_text, off, (const unsigned long long *)nullptr, n_pre, hash, slots, cap - 1,
-                       rep, count);
-    hipLaunchKernelGGL(k_dedup_flags, dim3(pgrid), dim3(256), 0, s, rep, off, n_pre, flag, ulen);
-    HIPCHK(c, hipGetLastError());
-    if (exclusive_scan<uint32_t>(s, flag, n_pre, uidx, n_pre + 1) != 0 || exclusive_scan<uint32_t>(s, ulen, n_pre, uoff, n_pre + 1) != 0)
-        return fail(c, YABPE_E_HIP, "scan of the unique words failed");
-    unsigned long long nu_tb[2] = {0, 0};
-    HIPCHK(c, hipMemcpyAsync(&nu_tb[0], uidx + n_pre, 8, hipMemcpyDeviceToHost, s));
-    HIPCHK(c, hipMemcpyAsync(&nu_tb[1], uoff + n_pre, 8, hipMemcpyDeviceToHost, s));
-    HIPCHK(c, hipStreamSynchronize(s));
-    const unsigned long long nu = nu_tb[0], ubytes = nu_tb[1];
     uint32_t *ulist = nullptr, *llen = nullptr, *uids = nullptr;
     unsigned long long *lbase = nullptr;
-    TRY(S.get(c, &ulist, nu));
-    TRY(S.get(c, &llen, nu));
-    TRY(S.get(c, &lbase, nu + 1));
-    TRY(S.get(c, &uids, ubytes));
+    HIPCHK(c, S.get(&ulist, nu));
+    HIPCHK(c, S.get(&llen, nu));
+    HIPCHK(c, S.get(&lbase, nu + 1));
+    HIPCHK(c, S.get(&uids, ubytes));
     uint32_t *upos = nullptr;
-    if (spans) TRY(S.get(c, &upos, ubytes));
+    if (spans) HIPCHK(c, S.get(&upos, ubytes));
     hipLaunchKernelGGL(k_enc_compact, dim3(pgrid), dim3(256), 0, s, flag, uidx, off, n_pre, ulist, llen);
     HIPCHK(c, hipGetLastError());
     if (exclusive_scan<uint32_t>(s, llen, nu, lbase, nu + 1) != 0) return fail(c, YABPE_E_HIP, "scan of the long words failed");
@@ -2739,11 +2575,11 @@ static int encode_run(yabpe_ctx *c, const uint8_t *text, uint64_t n_bytes, const
     // ---- the merges of every unique word (flag is free again: it becomes the per-word id count)
     uint32_t *ltok = nullptr, *lnxt = nullptr, *lprv = nullptr;
     unsigned long long *lheap = nullptr, *wsums = nullptr;
-    TRY(S.get(c, &ltok, lbytes));
-    TRY(S.get(c, &lnxt, lbytes));
-    TRY(S.get(c, &lprv, lbytes));
-    TRY(S.get(c, &lheap, 3 * lbytes));
-    TRY(S.get(c, &wsums, 4));
+    HIPCHK(c, S.get(&ltok, lbytes));
+    HIPCHK(c, S.get(&lnxt, lbytes));
+    HIPCHK(c, S.get(&lprv, lbytes));
+    HIPCHK(c, S.get(&lheap, 3 * lbytes));
+    HIPCHK(c, S.get(&wsums, 4));
     HIPCHK(c, hipMemsetAsync(wsums, 0, 32, s));
     HIPCHK(c, hipEventRecord(c->enc_ev[4], s));  // (the words phase starts here: the scratch allocation above is host work)
     EncWordsParams W{d_text, off, ulist, nu, uoff, lbase, count, sflag, EncTable{c->enc_keys, c->enc_vals, c->enc_mask}, c->enc_out_id,
@@ -2757,13 +2593,13 @@ static int encode_run(yabpe_ctx *c, const uint8_t *text, uint64_t n_bytes, const
     HIPCHK(c, hipEventRecord(c->enc_ev[5], s));
     // ---- emission: per pre-token count -> id offsets -> ids; per-document offsets
     unsigned long long *id_off = nullptr;
-    TRY(S.get(c, &id_off, n_pre + 1));
+    HIPCHK(c, S.get(&id_off, n_pre + 1));
     const unsigned long long n_gran = (n + ENC_GRANULE - 1) / ENC_GRANULE;
     uint8_t *lead_cnt = nullptr;
     unsigned long long *lead_table = nullptr;
     if (chars) {
-        TRY(S.get(c, &lead_cnt, n_gran));
-        TRY(S.get(c, &lead_table, n_gran + 1));
+        HIPCHK(c, S.get(&lead_cnt, n_gran));
+        HIPCHK(c, S.get(&lead_table, n_gran + 1));
     }
     HIPCHK(c, hipEventRecord(c->enc_ev[6], s));
     hipLaunchKernelGGL(k_enc_count, dim3(pgrid), dim3(256), 0, s, rep, flag, n_pre, ulen);
@@ -2903,9 +2739,7 @@ int yabpe_decode(yabpe_ctx *c, const uint32_t *ids, uint64_t n_ids, const uint64
         if (docs_dev) HIPCHK(c, hipMemcpy(h_docs.data(), doc_off, (size_t)n_docs * 8, hipMemcpyDeviceToHost));
         else memcpy(h_docs.data(), doc_off, (size_t)n_docs * 8);
     }
-    if (!n_docs || h_docs[0] != 0) return fail(c, YABPE_E_INVALID, "doc_off must hold n_docs >= 1 starts, the first one 0");
-    for (uint32_t d = 1; d < n_docs; ++d)
-        if (h_docs[d] < h_docs[d - 1] || h_docs[d] > n_ids) return fail(c, YABPE_E_INVALID, "document starts must ascend inside the ids");
+    TRY(check_starts(c, h_docs.data(), n_docs, n_ids, "ids"));
     yabpe_decode_free(c);
     c->dec_stats = yabpe_decode_stats_t{};
     c->dec_stats.n_ids = n_ids;
@@ -2913,22 +2747,12 @@ int yabpe_decode(yabpe_ctx *c, const uint32_t *ids, uint64_t n_ids, const uint64
     for (auto &e : c->dec_ev)
         if (!e) HIPCHK(c, hipEventCreate(&e));
     hipStream_t s = c->stream;
-    EncScratch S;
+    Scratch S(c->device, c->rank);
     // inputs on the device (16-B aligned ids: the kernels load them 4 at a time)
-    const uint32_t *d_ids = ids;
-    if (n_ids && (!is_device_ptr(ids) || ((uintptr_t)ids & 15u))) {
-        uint32_t *own = nullptr;
-        TRY(S.get(c, &own, n_ids));
-        HIPCHK(c, hipMemcpy(own, ids, n_ids * 4, hipMemcpyDefault));
-        d_ids = own;
-    }
-    const unsigned long long *d_docs = (const unsigned long long *)doc_off;
-    if (!docs_dev) {
-        unsigned long long *own = nullptr;
-        TRY(S.get(c, &own, n_docs));
-        HIPCHK(c, hipMemcpy(own, h_docs.data(), (size_t)n_docs * 8, hipMemcpyHostToDevice));
-        d_docs = own;
-    }
+    const uint32_t *d_ids = nullptr;
+    TRY(to_device(c, S, ids, n_ids * 4, 16, &d_ids));
+    const unsigned long long *d_docs = nullptr;
+    TRY(to_device(c, S, docs_dev ? (const unsigned long long *)doc_off : (const unsigned long long *)h_docs.data(), (uint64_t)n_docs * 8, 1, &d_docs));
     TRY(dmalloc(c, &c->dec_doc, (uint64_t)n_docs + 1));
     if (n_ids == 0) { // every document is empty
         HIPCHK(c, hipMemsetAsync(c->dec_doc, 0, ((size_t)n_docs + 1) * 8, s));
@@ -2941,9 +2765,9 @@ int yabpe_decode(yabpe_ctx *c, const uint32_t *ids, uint64_t n_ids, const uint64
     const DecTable tab{c->dec_ent, c->dec_n, c->dec_pool};
     // ---- lengths: per-block byte counts -> block output bases
     unsigned long long *bsum = nullptr, *bbase = nullptr, *counters = nullptr;
-    TRY(S.get(c, &bsum, nb));
-    TRY(S.get(c, &bbase, nb + 1));
-    TRY(S.get(c, &counters, 2));
+    HIPCHK(c, S.get(&bsum, nb));
+    HIPCHK(c, S.get(&bbase, nb + 1));
+    HIPCHK(c, S.get(&counters, 2));
     HIPCHK(c, hipEventRecord(c->dec_ev[0], s));
     HIPCHK(c, hipMemsetAsync(counters, 0, 16, s));
     hipLaunchKernelGGL(k_dec_lengths, dim3((uint32_t)nb), dim3(BLOCK), 0, s, d_ids, (unsigned long long)n_ids, tab, bsum, counters);
@@ -2956,8 +2780,8 @@ int yabpe_decode(yabpe_ctx *c, const uint32_t *ids, uint64_t n_ids, const uint64
     const unsigned long long nt = (G + DEC_TILE - 1) / DEC_TILE;
     if (nt > (1ull << 24)) return fail(c, YABPE_E_CAPACITY, "%llu bytes of text in one call: at most 2^36", G);
     // ---- gather: token bytes -> text, document offsets
-    uint8_t *gtext = nullptr;
-    TRY(dmalloc(c, &gtext, G));
+    uint8_t *gtext = nullptr;  // (scratch until it turns out to be the result)
+    HIPCHK(c, S.get(&gtext, G));
     HIPCHK(c, hipEventRecord(c->dec_ev[2], s)); // (the allocation above is host work)
     hipLaunchKernelGGL(k_dec_gather, dim3((uint32_t)nb), dim3(BLOCK), 0, s,
                        DecGatherParams{d_ids, n_ids, tab, bbase, d_docs, n_docs, gtext, c->dec_doc});
@@ -2965,17 +2789,14 @@ int yabpe_decode(yabpe_ctx *c, const uint32_t *ids, uint64_t n_ids, const uint64
     HIPCHK(c, hipEventRecord(c->dec_ev[3], s));
     // ---- check: output bytes per tile, U+FFFD count
     uint32_t *osum = nullptr;
-    TRY(S.get(c, &osum, nt));
+    HIPCHK(c, S.get(&osum, nt));
     if (nt) hipLaunchKernelGGL(k_dec_check, dim3((uint32_t)nt), dim3(BLOCK), 0, s, DecCheckParams{gtext, G, c->dec_doc, n_docs, osum, counters});
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipEventRecord(c->dec_ev[4], s));
     unsigned long long h_cnt[2] = {0, 0};
     HIPCHK(c, hipMemcpyAsync(h_cnt, counters, 16, hipMemcpyDeviceToHost, s));
     const hipError_t ce = hipStreamSynchronize(s);
-    if (ce != hipSuccess) {
-        dfree(gtext);
-        return fail(c, YABPE_E_HIP, "decoder kernels failed: %s", hipGetErrorString(ce));
-    }
+    if (ce != hipSuccess) return fail(c, YABPE_E_HIP, "decoder kernels failed: %s", hipGetErrorString(ce));
     auto &st = c->dec_stats;
     st.n_unknown = h_cnt[0];
     st.n_gathered = G;
@@ -2987,18 +2808,17 @@ int yabpe_decode(yabpe_ctx *c, const uint32_t *ids, uint64_t n_ids, const uint64
     hipEvent_t last = c->dec_ev[4];
     unsigned long long n_out = G;
     if (h_cnt[1] == 0) { // valid UTF-8: the gathered text is the result
-        c->dec_text = gtext;
+        c->dec_text = S.take(gtext);
     } else {
         // ---- repair: tile output bases, the rewrite with U+FFFD, the repaired documents
-        S.bufs.push_back(gtext); // (the gathered text and its offsets are scratch from here on)
-        S.bufs.push_back(c->dec_doc);
+        S.adopt(c->dec_doc); // (the gathered text and its offsets are scratch from here on)
         const unsigned long long *gdoc = c->dec_doc;
         c->dec_doc = nullptr;
         unsigned long long *rbase = nullptr, *nbad = nullptr;
         uint32_t *docbad = nullptr;
-        TRY(S.get(c, &rbase, nt + 1));
-        TRY(S.get(c, &docbad, n_docs));
-        TRY(S.get(c, &nbad, (uint64_t)n_docs + 1));
+        HIPCHK(c, S.get(&rbase, nt + 1));
+        HIPCHK(c, S.get(&docbad, n_docs));
+        HIPCHK(c, S.get(&nbad, (uint64_t)n_docs + 1));
         TRY(dmalloc(c, &c->dec_doc, (uint64_t)n_docs + 1));
         HIPCHK(c, hipEventRecord(c->dec_ev[5], s));
         HIPCHK(c, hipMemsetAsync(docbad, 0, (size_t)n_docs * 4, s));

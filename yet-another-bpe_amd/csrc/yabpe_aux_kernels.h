@@ -8,6 +8,7 @@
 #include <algorithm>
 #include <vector>
 
+#include "yabpe_devmem.h"
 #include "yabpe_kernels.h"
 
 namespace yb {
@@ -75,20 +76,17 @@ int exclusive_scan(hipStream_t s, const TIn *in, unsigned long long n_in, unsign
         YB_RET(hipGetLastError());
         return 0;
     }
+    Scratch S;
     unsigned long long *sums = nullptr, *sums_scan = nullptr;
-    YB_RET(hipMalloc((void **)&sums, nb * 8));
-    YB_RET(hipMalloc((void **)&sums_scan, nb * 8));
+    YB_RET(S.get(&sums, nb));
+    YB_RET(S.get(&sums_scan, nb));
     hipLaunchKernelGGL(k_scan_block<TIn>, dim3((uint32_t)nb), dim3(BLOCK), 0, s, in, n_in, out, n_out, sums);
     YB_RET(hipGetLastError());
-    int r = exclusive_scan<unsigned long long>(s, sums, nb, sums_scan, nb);
-    if (r == 0) {
-        hipLaunchKernelGGL(k_scan_add, dim3((uint32_t)nb), dim3(BLOCK), 0, s, out, n_out, sums_scan);
-        if (hipGetLastError() != hipSuccess) r = -1;
-    }
-    if (hipStreamSynchronize(s) != hipSuccess) r = -1;
-    (void)hipFree(sums);
-    (void)hipFree(sums_scan);
-    return r;
+    if (exclusive_scan<unsigned long long>(s, sums, nb, sums_scan, nb) != 0) return -1;
+    hipLaunchKernelGGL(k_scan_add, dim3((uint32_t)nb), dim3(BLOCK), 0, s, out, n_out, sums_scan);
+    YB_RET(hipGetLastError());
+    YB_RET(hipStreamSynchronize(s));  // (the block sums go back to the cache, which other streams draw from)
+    return 0;
 }
 
 // ================================================================ synthetic corpus (mirrors yet_another_bpe/synth.py)
@@ -160,6 +158,7 @@ inline int synth_generate(hipStream_t s, unsigned long long target, uint32_t n_t
                           const uint8_t *alphabet, uint32_t alen, int space_prefix, SynthOut *out) {
     const uint32_t prefix = space_prefix ? 1 : 0;
     const unsigned long long n_cand = target / 4 + 4096;
+    Scratch S;
     uint8_t *d_alpha = nullptr, *d_tb = nullptr, *d_tl = nullptr, *d_wl = nullptr, *d_bytes = nullptr;
     unsigned long long *d_cum = nullptr, *d_off = nullptr, *d_cut = nullptr;
     uint32_t *d_wt = nullptr;
@@ -169,45 +168,32 @@ inline int synth_generate(hipStream_t s, unsigned long long target, uint32_t n_t
         acc += (1ull << 40) / (j + 1ull);
         cum[j] = acc;
     }
-    int rc = -1;
-    do {
-        if (hipMalloc((void **)&d_alpha, alen) != hipSuccess) break;
-        if (hipMalloc((void **)&d_tb, (size_t)n_types * 12) != hipSuccess) break;
-        if (hipMalloc((void **)&d_tl, n_types) != hipSuccess) break;
-        if (hipMalloc((void **)&d_cum, (size_t)n_types * 8) != hipSuccess) break;
-        if (hipMalloc((void **)&d_wt, n_cand * 4) != hipSuccess) break;
-        if (hipMalloc((void **)&d_wl, n_cand) != hipSuccess) break;
-        if (hipMalloc((void **)&d_off, (n_cand + 1) * 8) != hipSuccess) break;
-        if (hipMalloc((void **)&d_cut, 16) != hipSuccess) break;
-        if (hipMemcpy(d_alpha, alphabet, alen, hipMemcpyHostToDevice) != hipSuccess) break;
-        if (hipMemcpy(d_cum, cum.data(), (size_t)n_types * 8, hipMemcpyHostToDevice) != hipSuccess) break;
-        hipLaunchKernelGGL(k_synth_lexicon, dim3((n_types + 255) / 256), dim3(256), 0, s, seed, n_types, d_alpha, alen, d_tb, d_tl);
-        hipLaunchKernelGGL(k_synth_draw, dim3((uint32_t)((n_cand + 255) / 256)), dim3(256), 0, s, seed, n_cand, d_cum, n_types,
-                           d_tl, prefix, d_wt, d_wl);
-        if (hipGetLastError() != hipSuccess) break;
-        if (exclusive_scan<uint8_t>(s, d_wl, n_cand, d_off, n_cand + 1) != 0) break;
-        hipLaunchKernelGGL(k_synth_cut, dim3(1), dim3(1), 0, s, d_off, n_cand, target, d_cut);
-        unsigned long long cut[2];
-        if (hipMemcpyAsync(cut, d_cut, 16, hipMemcpyDeviceToHost, s) != hipSuccess) break;
-        if (hipStreamSynchronize(s) != hipSuccess) break;
-        if (cut[0] == 0) { rc = -2; break; }
-        if (hipMalloc((void **)&d_bytes, cut[1]) != hipSuccess) break;
-        hipLaunchKernelGGL(k_synth_fill, dim3((uint32_t)((cut[0] + 255) / 256)), dim3(256), 0, s, d_wt, d_off, cut[0], d_tb, d_tl, prefix, d_bytes);
-        if (hipGetLastError() != hipSuccess) break;
-        if (hipStreamSynchronize(s) != hipSuccess) break;
-        out->bytes = d_bytes;
-        out->off = d_off;
-        out->n_words = cut[0];
-        out->n_bytes = cut[1];
-        d_bytes = nullptr;
-        d_off = nullptr;
-        rc = 0;
-    } while (0);
-    (void)hipFree(d_alpha); (void)hipFree(d_tb); (void)hipFree(d_tl); (void)hipFree(d_cum);
-    (void)hipFree(d_wt); (void)hipFree(d_wl); (void)hipFree(d_cut);
-    if (d_bytes) (void)hipFree(d_bytes);
-    if (d_off) (void)hipFree(d_off);
-    return rc;
+    YB_RET(S.get(&d_alpha, alen));
+    YB_RET(S.get(&d_tb, (size_t)n_types * 12));
+    YB_RET(S.get(&d_tl, n_types));
+    YB_RET(S.get(&d_cum, n_types));
+    YB_RET(S.get(&d_wt, n_cand));
+    YB_RET(S.get(&d_wl, n_cand));
+    YB_RET(S.get(&d_off, n_cand + 1));
+    YB_RET(S.get(&d_cut, 2));
+    YB_RET(hipMemcpy(d_alpha, alphabet, alen, hipMemcpyHostToDevice));
+    YB_RET(hipMemcpy(d_cum, cum.data(), (size_t)n_types * 8, hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(k_synth_lexicon, dim3((n_types + 255) / 256), dim3(256), 0, s, seed, n_types, d_alpha, alen, d_tb, d_tl);
+    hipLaunchKernelGGL(k_synth_draw, dim3((uint32_t)((n_cand + 255) / 256)), dim3(256), 0, s, seed, n_cand, d_cum, n_types,
+                       d_tl, prefix, d_wt, d_wl);
+    YB_RET(hipGetLastError());
+    if (exclusive_scan<uint8_t>(s, d_wl, n_cand, d_off, n_cand + 1) != 0) return -1;
+    hipLaunchKernelGGL(k_synth_cut, dim3(1), dim3(1), 0, s, d_off, n_cand, target, d_cut);
+    unsigned long long cut[2];
+    YB_RET(hipMemcpyAsync(cut, d_cut, 16, hipMemcpyDeviceToHost, s));
+    YB_RET(hipStreamSynchronize(s));
+    if (cut[0] == 0) return -2;
+    YB_RET(S.get(&d_bytes, cut[1]));
+    hipLaunchKernelGGL(k_synth_fill, dim3((uint32_t)((cut[0] + 255) / 256)), dim3(256), 0, s, d_wt, d_off, cut[0], d_tb, d_tl, prefix, d_bytes);
+    YB_RET(hipGetLastError());
+    YB_RET(hipStreamSynchronize(s));
+    *out = SynthOut{S.take(d_bytes), S.take(d_off), cut[0], cut[1]};
+    return 0;
 }
 
 // ---------------------------------------------------------------- the same Zipf draw over a lexicon the caller supplies
@@ -240,6 +226,7 @@ __global__ void k_synth_fill_lex(const uint32_t *word_type, const unsigned long 
 // lex_bytes / lex_off: HOST arrays (n_types + 1 offsets).  n_cand: how many draws to make (>= the words the target needs).
 inline int synth_generate_lex(hipStream_t s, unsigned long long target, uint32_t n_types, unsigned long long seed,
                               const uint8_t *lex_bytes, const unsigned long long *lex_off, unsigned long long n_cand, SynthOut *out) {
+    Scratch S;
     uint8_t *d_lb = nullptr, *d_bytes = nullptr;
     unsigned long long *d_lo = nullptr, *d_cum = nullptr, *d_off = nullptr, *d_cut = nullptr;
     uint32_t *d_wt = nullptr, *d_wl = nullptr;
@@ -250,43 +237,30 @@ inline int synth_generate_lex(hipStream_t s, unsigned long long target, uint32_t
         cum[j] = acc;
     }
     const unsigned long long lex_total = lex_off[n_types];
-    int rc = -1;
-    do {
-        if (hipMalloc((void **)&d_lb, lex_total ? lex_total : 1) != hipSuccess) break;
-        if (hipMalloc((void **)&d_lo, ((size_t)n_types + 1) * 8) != hipSuccess) break;
-        if (hipMalloc((void **)&d_cum, (size_t)n_types * 8) != hipSuccess) break;
-        if (hipMalloc((void **)&d_wt, n_cand * 4) != hipSuccess) break;
-        if (hipMalloc((void **)&d_wl, n_cand * 4) != hipSuccess) break;
-        if (hipMalloc((void **)&d_off, (n_cand + 1) * 8) != hipSuccess) break;
-        if (hipMalloc((void **)&d_cut, 16) != hipSuccess) break;
-        if (hipMemcpy(d_lb, lex_bytes, lex_total, hipMemcpyHostToDevice) != hipSuccess) break;
-        if (hipMemcpy(d_lo, lex_off, ((size_t)n_types + 1) * 8, hipMemcpyHostToDevice) != hipSuccess) break;
-        if (hipMemcpy(d_cum, cum.data(), (size_t)n_types * 8, hipMemcpyHostToDevice) != hipSuccess) break;
-        hipLaunchKernelGGL(k_synth_draw_lex, dim3((uint32_t)((n_cand + 255) / 256)), dim3(256), 0, s, seed, n_cand, d_cum, n_types, d_lo, d_wt, d_wl);
-        if (hipGetLastError() != hipSuccess) break;
-        if (exclusive_scan<uint32_t>(s, d_wl, n_cand, d_off, n_cand + 1) != 0) break;
-        hipLaunchKernelGGL(k_synth_cut, dim3(1), dim3(1), 0, s, d_off, n_cand, target, d_cut);
-        unsigned long long cut[2];
-        if (hipMemcpyAsync(cut, d_cut, 16, hipMemcpyDeviceToHost, s) != hipSuccess) break;
-        if (hipStreamSynchronize(s) != hipSuccess) break;
-        if (cut[0] == 0) { rc = -2; break; }  // (not enough draws for the target)
-        if (hipMalloc((void **)&d_bytes, cut[1]) != hipSuccess) break;
-        hipLaunchKernelGGL(k_synth_fill_lex, dim3((uint32_t)((cut[0] + 255) / 256)), dim3(256), 0, s, d_wt, d_off, cut[0], d_lb, d_lo, d_bytes);
-        if (hipGetLastError() != hipSuccess) break;
-        if (hipStreamSynchronize(s) != hipSuccess) break;
-        out->bytes = d_bytes;
-        out->off = d_off;
-        out->n_words = cut[0];
-        out->n_bytes = cut[1];
-        d_bytes = nullptr;
-        d_off = nullptr;
-        rc = 0;
-    } while (0);
-    (void)hipFree(d_lb); (void)hipFree(d_lo); (void)hipFree(d_cum);
-    (void)hipFree(d_wt); (void)hipFree(d_wl); (void)hipFree(d_cut);
-    if (d_bytes) (void)hipFree(d_bytes);
-    if (d_off) (void)hipFree(d_off);
-    return rc;
+    YB_RET(S.get(&d_lb, lex_total));
+    YB_RET(S.get(&d_lo, (size_t)n_types + 1));
+    YB_RET(S.get(&d_cum, n_types));
+    YB_RET(S.get(&d_wt, n_cand));
+    YB_RET(S.get(&d_wl, n_cand));
+    YB_RET(S.get(&d_off, n_cand + 1));
+    YB_RET(S.get(&d_cut, 2));
+    YB_RET(hipMemcpy(d_lb, lex_bytes, lex_total, hipMemcpyHostToDevice));
+    YB_RET(hipMemcpy(d_lo, lex_off, ((size_t)n_types + 1) * 8, hipMemcpyHostToDevice));
+    YB_RET(hipMemcpy(d_cum, cum.data(), (size_t)n_types * 8, hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(k_synth_draw_lex, dim3((uint32_t)((n_cand + 255) / 256)), dim3(256), 0, s, seed, n_cand, d_cum, n_types, d_lo, d_wt, d_wl);
+    YB_RET(hipGetLastError());
+    if (exclusive_scan<uint32_t>(s, d_wl, n_cand, d_off, n_cand + 1) != 0) return -1;
+    hipLaunchKernelGGL(k_synth_cut, dim3(1), dim3(1), 0, s, d_off, n_cand, target, d_cut);
+    unsigned long long cut[2];
+    YB_RET(hipMemcpyAsync(cut, d_cut, 16, hipMemcpyDeviceToHost, s));
+    YB_RET(hipStreamSynchronize(s));
+    if (cut[0] == 0) return -2;  // (not enough draws for the target)
+    YB_RET(S.get(&d_bytes, cut[1]));
+    hipLaunchKernelGGL(k_synth_fill_lex, dim3((uint32_t)((cut[0] + 255) / 256)), dim3(256), 0, s, d_wt, d_off, cut[0], d_lb, d_lo, d_bytes);
+    YB_RET(hipGetLastError());
+    YB_RET(hipStreamSynchronize(s));
+    *out = SynthOut{S.take(d_bytes), S.take(d_off), cut[0], cut[1]};
+    return 0;
 }
 
 // ================================================================ device-side pooling of equal words (trainer.py:221-225)
@@ -387,55 +361,60 @@ struct DedupOut {
     unsigned long long n_unique, total_bytes;
 };
 
-inline int dedup_words(hipStream_t s, const uint8_t *bytes, const unsigned long long *off, const unsigned long long *freq,
-                       unsigned long long n, unsigned long long total_bytes, DedupOut *out) {
-    (void)total_bytes;
+// The pooling pass both of its users start with: hash -> representative and count of every word -> unique flags and
+// lengths -> their two scans -> the totals.  Every array belongs to S; ends in a synchronise (the totals are host values).
+struct PoolOut {
+    uint32_t *rep, *flag, *ulen;             // per word: its representative, 1 / its length if it is one (else 0)
+    unsigned long long *count, *uidx, *uoff; // count[rep]; exclusive scans of flag and ulen (n + 1 entries)
+    unsigned long long n_unique, unique_bytes;
+};
+
+inline int pool_words(hipStream_t s, Scratch &S, const uint8_t *bytes, const unsigned long long *off, const unsigned long long *freq,
+                      unsigned long long n, PoolOut *out) {
     unsigned long long cap = 1024;
     while (cap < n * 2) cap <<= 1;
-    unsigned long long *d_hash = nullptr, *d_count = nullptr, *d_uidx = nullptr, *d_uoff = nullptr;
-    uint32_t *d_slots = nullptr, *d_rep = nullptr, *d_flag = nullptr, *d_ulen = nullptr;
+    unsigned long long *d_hash = nullptr;
+    uint32_t *d_slots = nullptr;
+    YB_RET(S.get(&d_hash, n));
+    YB_RET(S.get(&out->count, n));
+    YB_RET(S.get(&d_slots, cap));
+    YB_RET(S.get(&out->rep, n));
+    YB_RET(S.get(&out->flag, n));
+    YB_RET(S.get(&out->ulen, n));
+    YB_RET(S.get(&out->uidx, n + 1));
+    YB_RET(S.get(&out->uoff, n + 1));
+    const uint32_t grid = (uint32_t)((n + 255) / 256);
+    YB_RET(hipMemsetAsync(d_slots, 0xFF, cap * 4, s));
+    YB_RET(hipMemsetAsync(out->count, 0, n * 8, s));
+    hipLaunchKernelGGL(k_word_hash, dim3(grid), dim3(256), 0, s, bytes, off, n, d_hash);
+    hipLaunchKernelGGL(k_word_dedup, dim3(grid), dim3(256), 0, s, bytes, off, freq, n, d_hash, d_slots, cap - 1, out->rep, out->count);
+    hipLaunchKernelGGL(k_dedup_flags, dim3(grid), dim3(256), 0, s, out->rep, off, n, out->flag, out->ulen);
+    YB_RET(hipGetLastError());
+    if (exclusive_scan<uint32_t>(s, out->flag, n, out->uidx, n + 1) != 0) return -1;
+    if (exclusive_scan<uint32_t>(s, out->ulen, n, out->uoff, n + 1) != 0) return -1;
+    YB_RET(hipMemcpyAsync(&out->n_unique, out->uidx + n, 8, hipMemcpyDeviceToHost, s));
+    YB_RET(hipMemcpyAsync(&out->unique_bytes, out->uoff + n, 8, hipMemcpyDeviceToHost, s));
+    YB_RET(hipStreamSynchronize(s));
+    return 0;
+}
+
+inline int dedup_words(hipStream_t s, const uint8_t *bytes, const unsigned long long *off, const unsigned long long *freq,
+                       unsigned long long n, DedupOut *out) {
+    Scratch S;
+    PoolOut po{};
+    if (pool_words(s, S, bytes, off, freq, n, &po) != 0) return -1;
+    const unsigned long long nu = po.n_unique, tb = po.unique_bytes;
     uint8_t *o_bytes = nullptr;
     unsigned long long *o_off = nullptr, *o_freq = nullptr;
-    const uint32_t grid = (uint32_t)((n + 255) / 256);
-    int rc = -1;
-    do {
-        if (hipMalloc((void **)&d_hash, n * 8) != hipSuccess) break;
-        if (hipMalloc((void **)&d_count, n * 8) != hipSuccess) break;
-        if (hipMalloc((void **)&d_slots, cap * 4) != hipSuccess) break;
-        if (hipMalloc((void **)&d_rep, n * 4) != hipSuccess) break;
-        if (hipMalloc((void **)&d_flag, n * 4) != hipSuccess) break;
-        if (hipMalloc((void **)&d_ulen, n * 4) != hipSuccess) break;
-        if (hipMalloc((void **)&d_uidx, (n + 1) * 8) != hipSuccess) break;
-        if (hipMalloc((void **)&d_uoff, (n + 1) * 8) != hipSuccess) break;
-        if (hipMemsetAsync(d_slots, 0xFF, cap * 4, s) != hipSuccess) break;
-        if (hipMemsetAsync(d_count, 0, n * 8, s) != hipSuccess) break;
-        hipLaunchKernelGGL(k_word_hash, dim3(grid), dim3(256), 0, s, bytes, off, n, d_hash);
-        hipLaunchKernelGGL(k_word_dedup, dim3(grid), dim3(256), 0, s, bytes, off, freq, n, d_hash, d_slots, cap - 1, d_rep, d_count);
-        hipLaunchKernelGGL(k_dedup_flags, dim3(grid), dim3(256), 0, s, d_rep, off, n, d_flag, d_ulen);
-        if (hipGetLastError() != hipSuccess) break;
-        if (exclusive_scan<uint32_t>(s, d_flag, n, d_uidx, n + 1) != 0) break;
-        if (exclusive_scan<uint32_t>(s, d_ulen, n, d_uoff, n + 1) != 0) break;
-        unsigned long long nu = 0, tb = 0;
-        if (hipMemcpyAsync(&nu, d_uidx + n, 8, hipMemcpyDeviceToHost, s) != hipSuccess) break;
-        if (hipMemcpyAsync(&tb, d_uoff + n, 8, hipMemcpyDeviceToHost, s) != hipSuccess) break;
-        if (hipStreamSynchronize(s) != hipSuccess) break;
-        if (hipMalloc((void **)&o_bytes, tb ? tb : 1) != hipSuccess) break;
-        if (hipMalloc((void **)&o_off, (nu + 1) * 8) != hipSuccess) break;
-        if (hipMalloc((void **)&o_freq, (nu ? nu : 1) * 8) != hipSuccess) break;
-        hipLaunchKernelGGL(k_dedup_gather, dim3(grid), dim3(256), 0, s, bytes, off, d_rep, n, d_uidx, d_uoff, d_count, o_bytes, o_off, o_freq);
-        if (hipGetLastError() != hipSuccess) break;
-        if (hipStreamSynchronize(s) != hipSuccess) break;
-        out->bytes = o_bytes; out->off = o_off; out->freq = o_freq;
-        out->n_unique = nu; out->total_bytes = tb;
-        o_bytes = nullptr; o_off = nullptr; o_freq = nullptr;
-        rc = 0;
-    } while (0);
-    (void)hipFree(d_hash); (void)hipFree(d_count); (void)hipFree(d_slots); (void)hipFree(d_rep);
-    (void)hipFree(d_flag); (void)hipFree(d_ulen); (void)hipFree(d_uidx); (void)hipFree(d_uoff);
-    if (o_bytes) (void)hipFree(o_bytes);
-    if (o_off) (void)hipFree(o_off);
-    if (o_freq) (void)hipFree(o_freq);
-    return rc;
+    YB_RET(S.get(&o_bytes, tb));
+    YB_RET(S.get(&o_off, nu + 1));
+    YB_RET(S.get(&o_freq, nu));
+    hipLaunchKernelGGL(k_dedup_gather, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, s, bytes, off, po.rep, n, po.uidx, po.uoff, po.count,
+                       o_bytes, o_off, o_freq);
+    YB_RET(hipGetLastError());
+    YB_RET(hipStreamSynchronize(s));
+    *out = DedupOut{S.take(o_bytes), S.take(o_off), S.take(o_freq), nu, tb};
+    return 0;
 }
 
 // ================================================================ retile (flat layout): repack live words into fresh tiles

@@ -212,63 +212,68 @@ struct PretokOut {
     long long bad_pos;       // first malformed UTF-8 byte, -1 if the text is valid
 };
 
+// flags -> offsets: count per workgroup, scan, the total (a synchronise), scatter, the sentinel off[n_words] = n.
+// *off (n_words + 1 entries) belongs to S.  More than max_words starts: -2, with *n_words set and *off not allocated.
+// The scatter and the sentinel are left in flight; n is read by the sentinel copy, so it must outlive the next synchronise.
+inline int pt_offsets(hipStream_t s, Scratch &S, const uint8_t *flags, const unsigned long long &n, unsigned long long max_words,
+                      unsigned long long **off, unsigned long long *n_words) {
+    const unsigned long long nb = (n + PT_PER_BLOCK - 1) / PT_PER_BLOCK;
+    unsigned long long *sums = nullptr, *bases = nullptr;
+    YB_RET(S.get(&sums, nb));
+    YB_RET(S.get(&bases, nb + 1));
+    hipLaunchKernelGGL(k_pt_count, dim3((uint32_t)nb), dim3(BLOCK), 0, s, flags, n, sums);
+    YB_RET(hipGetLastError());
+    if (exclusive_scan<unsigned long long>(s, sums, nb, bases, nb + 1) != 0) return -1;
+    YB_RET(hipMemcpyAsync(n_words, bases + nb, 8, hipMemcpyDeviceToHost, s));
+    YB_RET(hipStreamSynchronize(s));
+    if (*n_words > max_words) return -2;
+    YB_RET(S.get(off, *n_words + 1));
+    hipLaunchKernelGGL(k_pt_scatter, dim3((uint32_t)nb), dim3(BLOCK), 0, s, flags, n, bases, *off);
+    YB_RET(hipMemcpyAsync(*off + *n_words, &n, 8, hipMemcpyHostToDevice, s));
+    YB_RET(hipGetLastError());
+    return 0;
+}
+
 // Runs all passes on `text` (device).  chunk_off: device array of n_chunks chunk starts.  cls: device class table.
-// Scratch (meta, flags) is allocated and released here; out->off is the caller's to free.
+// Scratch (meta, flags) is allocated and released here; out->off is the caller's to free (dev_free).
 inline int pretokenize(hipStream_t s, const uint8_t *text, unsigned long long n, const unsigned long long *chunk_off, uint32_t n_chunks,
                        const uint8_t *cls, const PtSpecials &sp_dev, PretokOut *out) {
-    out->off = nullptr;
-    out->n_words = 0;
-    out->bad_pos = -1;
+    *out = PretokOut{nullptr, 0, -1};
+    Scratch S;
+    unsigned long long *off = nullptr;
     if (n == 0) {
-        YB_RET(hipMalloc((void **)&out->off, 8));
-        YB_RET(hipMemsetAsync(out->off, 0, 8, s));
+        YB_RET(S.get(&off, 1));
+        YB_RET(hipMemsetAsync(off, 0, 8, s));
         YB_RET(hipStreamSynchronize(s));
+        out->off = S.take(off);
         return 0;
     }
     uint8_t *meta = nullptr, *flags = nullptr;
-    unsigned long long *err = nullptr, *sums = nullptr, *bases = nullptr;
-    const unsigned long long nb = (n + PT_PER_BLOCK - 1) / PT_PER_BLOCK;
-    int rc = -1;
-    do {
-        if (hipMalloc((void **)&meta, n) != hipSuccess || hipMalloc((void **)&flags, n + 8) != hipSuccess) break;
-        if (hipMalloc((void **)&err, 8) != hipSuccess || hipMalloc((void **)&sums, nb * 8) != hipSuccess) break;
-        if (hipMalloc((void **)&bases, (nb + 1) * 8) != hipSuccess) break;
-        if (hipMemsetAsync(meta, 0, n, s) != hipSuccess || hipMemsetAsync(err, 0xff, 8, s) != hipSuccess) break;
-        const uint32_t grid = (uint32_t)std::min<unsigned long long>((n + BLOCK - 1) / BLOCK, 1u << 20);
-        PretokParams P{text, meta, flags, n, cls, err, sp_dev};
-        hipLaunchKernelGGL(k_pt_mark_chunks, dim3((n_chunks + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, s, meta, chunk_off, n_chunks, n);
-        const uint32_t wgrid = (uint32_t)std::min<unsigned long long>((n + PT_WIN - 1) / PT_WIN, 1u << 20);
-        hipLaunchKernelGGL(k_pt_fused, dim3(wgrid), dim3(BLOCK), 0, s, P);
-        unsigned long long h_err = 0;
-        if (hipMemcpyAsync(&h_err, err, 8, hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess) break;
-        if (h_err != ~0ull) { // malformed UTF-8: nothing else is computed (the neighbour walks assume valid text)
-            out->bad_pos = (long long)h_err;
-            rc = 0;
-            break;
-        }
-        if (sp_dev.n) hipLaunchKernelGGL(k_pt_special, dim3(grid), dim3(BLOCK), 0, s, P);
-        hipLaunchKernelGGL(k_pt_count, dim3((uint32_t)nb), dim3(BLOCK), 0, s, flags, n, sums);
-        if (hipGetLastError() != hipSuccess) break;
-        if (exclusive_scan<unsigned long long>(s, sums, nb, bases, nb + 1) != 0) break;
-        unsigned long long total = 0;
-        if (hipMemcpyAsync(&total, bases + nb, 8, hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess) break;
-        if (hipMalloc((void **)&out->off, (total + 1) * 8) != hipSuccess) break;
-        hipLaunchKernelGGL(k_pt_scatter, dim3((uint32_t)nb), dim3(BLOCK), 0, s, flags, n, bases, out->off);
-        if (hipMemcpyAsync(out->off + total, &n, 8, hipMemcpyHostToDevice, s) != hipSuccess) break;
-        if (hipStreamSynchronize(s) != hipSuccess) break;
-        out->n_words = total;
-        rc = 0;
-    } while (false);
-    (void)hipFree(meta);
-    (void)hipFree(flags);
-    (void)hipFree(err);
-    (void)hipFree(sums);
-    (void)hipFree(bases);
-    if (rc != 0 && out->off) {
-        (void)hipFree(out->off);
-        out->off = nullptr;
+    unsigned long long *err = nullptr;
+    YB_RET(S.get(&meta, n));
+    YB_RET(S.get(&flags, n + 8));
+    YB_RET(S.get(&err, 1));
+    YB_RET(hipMemsetAsync(meta, 0, n, s));
+    YB_RET(hipMemsetAsync(err, 0xff, 8, s));
+    const uint32_t grid = (uint32_t)std::min<unsigned long long>((n + BLOCK - 1) / BLOCK, 1u << 20);
+    PretokParams P{text, meta, flags, n, cls, err, sp_dev};
+    hipLaunchKernelGGL(k_pt_mark_chunks, dim3((n_chunks + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, s, meta, chunk_off, n_chunks, n);
+    const uint32_t wgrid = (uint32_t)std::min<unsigned long long>((n + PT_WIN - 1) / PT_WIN, 1u << 20);
+    hipLaunchKernelGGL(k_pt_fused, dim3(wgrid), dim3(BLOCK), 0, s, P);
+    unsigned long long h_err = 0;
+    YB_RET(hipMemcpyAsync(&h_err, err, 8, hipMemcpyDeviceToHost, s));
+    YB_RET(hipStreamSynchronize(s));
+    if (h_err != ~0ull) { // malformed UTF-8: nothing else is computed (the neighbour walks assume valid text)
+        out->bad_pos = (long long)h_err;
+        return 0;
     }
-    return rc;
+    if (sp_dev.n) hipLaunchKernelGGL(k_pt_special, dim3(grid), dim3(BLOCK), 0, s, P);
+    unsigned long long total = 0;
+    if (pt_offsets(s, S, flags, n, ~0ull, &off, &total) != 0) return -1;
+    YB_RET(hipStreamSynchronize(s));
+    out->off = S.take(off);
+    out->n_words = total;
+    return 0;
 }
 
 } // namespace yb
