@@ -310,6 +310,56 @@ typedef struct yabpe_decode_stats_t {
 } yabpe_decode_stats_t;
 int yabpe_decode_stats(yabpe_ctx *ctx, yabpe_decode_stats_t *out);
 
+/* Fixed-shape batches (BBPETokenizer.encode_batch_padded / encode_batch_packed on the device) -----------------------
+ * ids and doc_off are taken as yabpe_decode takes them: document d = ids[doc_off[d], doc_off[d + 1]) (the last one ends at
+ * n_ids; doc_off[0] = 0, ascending; doc_off == NULL with n_docs <= 1: one document), host or device memory; yabpe_encode's
+ * results can be passed as they are and are left alone.  No model is needed.  With seq(d) = [bos_id] + the document's ids +
+ * [eos_id] (YABPE_LAYOUT_BOS / _EOS say which of the two are given; n_added = how many):
+ *   yabpe_layout_pad   one row of row_len slots per document.  A seq(d) longer than row_len loses ids from the end of its
+ *       content (YABPE_LAYOUT_TRUNC_LEFT: from the start); BOS and EOS always survive.  *out_dev_len[d] = the length after the
+ *       cut.  The kept sequence sits at the left end of its row (YABPE_LAYOUT_PAD_LEFT: at the right end), pad_id elsewhere.
+ *       row_len == 0: the longest seq(d), found on the device; *out_row_len = the row length used.
+ *       Results: *out_dev_rows = n_docs * *out_row_len u32, *out_dev_len = n_docs u32.
+ *   yabpe_layout_pack  all seq(d) end to end in document order, cut into rows of row_len: *out_n_rows = ceil(stream /
+ *       row_len) rows, or floor with YABPE_LAYOUT_DROP_LAST (the last partial row is dropped).  Per slot: the id, the index
+ *       of the document it came from, and its index inside seq(d) (BOS is 0).  Slots of the last row past the stream:
+ *       pad_id, document 0xFFFFFFFF, position 0.  Results: three arrays of *out_n_rows * row_len u32.
+ * Results are device memory owned by the library, in buffers of their own (a later yabpe_encode leaves them valid), released
+ * by yabpe_layout_free, the next layout call or yabpe_destroy.
+ * YABPE_E_INVALID: flags outside YABPE_LAYOUT_*, or one that does not belong to the call (TRUNC_LEFT / PAD_LEFT: pad only;
+ * DROP_LAST: pack only); 0 < row_len < n_added for pad; row_len == 0 for pack; doc_off that does not ascend from 0 inside the
+ * ids.  YABPE_E_CAPACITY: more than 2^36 output slots in one call; a seq(d) of more than 2^32 - 1 entries (pack: positions
+ * are u32; pad with row_len == 0: so is the row length). */
+#define YABPE_LAYOUT_BOS        0x01u
+#define YABPE_LAYOUT_EOS        0x02u
+#define YABPE_LAYOUT_TRUNC_LEFT 0x04u
+#define YABPE_LAYOUT_PAD_LEFT   0x08u
+#define YABPE_LAYOUT_DROP_LAST  0x10u
+typedef struct yabpe_layout_t {
+    uint32_t row_len;  /* pad: max_length (0: the longest sequence); pack: seq_len */
+    uint32_t pad_id, bos_id, eos_id;  /* bos_id / eos_id are read only with their flag */
+    uint32_t flags;    /* YABPE_LAYOUT_* */
+} yabpe_layout_t;
+int yabpe_layout_pad(yabpe_ctx *ctx, const uint32_t *ids, uint64_t n_ids, const uint64_t *doc_off, uint32_t n_docs,
+                     const yabpe_layout_t *layout, uint32_t **out_dev_rows, uint32_t **out_dev_len, uint32_t *out_row_len);
+int yabpe_layout_pack(yabpe_ctx *ctx, const uint32_t *ids, uint64_t n_ids, const uint64_t *doc_off, uint32_t n_docs,
+                      const yabpe_layout_t *layout, uint32_t **out_dev_ids, uint32_t **out_dev_doc, uint32_t **out_dev_pos,
+                      uint64_t *out_n_rows);
+int yabpe_layout_free(yabpe_ctx *ctx);
+/* What the last yabpe_layout_pad / yabpe_layout_pack saw, and the device time of its phases (HIP events around each phase's
+ * launches). */
+typedef struct yabpe_layout_stats_t {
+    uint64_t n_ids, n_docs;
+    uint64_t n_rows, row_len;
+    uint64_t n_truncated_docs; /* pad: documents whose seq was cut */
+    uint64_t n_ids_dropped;    /* pad: ids cut away; pack: stream entries of the row YABPE_LAYOUT_DROP_LAST dropped */
+    uint64_t n_pad_slots;      /* slots that hold pad_id */
+    double lengths_ms;         /* kept lengths and the call's counters (pad) / stream offsets (pack) */
+    double write_ms;           /* the output pass */
+    double total_ms;           /* first to last event, host gaps in between included */
+} yabpe_layout_stats_t;
+int yabpe_layout_stats(yabpe_ctx *ctx, yabpe_layout_stats_t *out);
+
 /* Multi-GPU (one process per GPU; words are sharded by the caller) -----------------
  * Every rank holds its shard of the words and a replica of the pair table.  After each apply pass the ranks
  * exchange their aggregated (pair, delta) records with ONE all-gather on the compute stream and every rank adds all

@@ -1,0 +1,128 @@
+#!/usr/bin/env python3
+"""Dev tool: the fixed-shape batch layouts (yabpe_layout_pad / yabpe_layout_pack) on the ids of 1 GiB of synth.text_lexicon text
+generated on the device, encoded with a 32,000-merge model trained on the device from that text; documents cut at pre-token
+boundaries to a mean of about 1,000 ids.  Encode once, then both layouts, best of --reps after a warm-up: device time per phase
+from yabpe_layout_stats, bytes read + written over write_ms as GB/s, and that rate against a plain device-to-device
+hipMemcpyAsync of the same number of output bytes (HIP events, same run).  Padded: max_length 1024; packed: seq_len 2048 with an
+EOS.  For comparison, what a user does without the layout calls on a --host-mib sample: encode_array, then a numpy loop per
+document on the host that builds the same padded batch.
+   python tools/layout_bench.py [--mib 1024] [--merges 32000] [--reps 3] [--host-mib 64] [--json out.json]"""
+import argparse, ctypes, json, sys, time
+from pathlib import Path
+REPO = Path(__file__).resolve().parent.parent
+sys.path.insert(0, str(REPO / "yet-another-bpe_amd"))
+sys.path.insert(0, str(REPO))
+import numpy as np
+from yet_another_bpe import _native, synth
+from yet_another_bpe.tokenizer import BBPETokenizer
+
+ap = argparse.ArgumentParser()
+ap.add_argument("--mib", type=int, default=1024)
+ap.add_argument("--merges", type=int, default=32000)
+ap.add_argument("--reps", type=int, default=3)
+ap.add_argument("--host-mib", type=int, default=64)
+ap.add_argument("--doc-ids", type=int, default=1000)
+ap.add_argument("--json", default="")
+a = ap.parse_args()
+PAD_LEN, PACK_LEN, EOS = 1024, 2048, 2
+
+
+def copy_ms(n_bytes: int, reps: int) -> float:
+    """best device time of hipMemcpyAsync(device to device) of n_bytes, HIP events on the null stream"""
+    hip = ctypes.CDLL("libamdhip64.so")
+    src, dst, e0, e1, ms = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_float(0)
+    def ok(rc):
+        if rc != 0:
+            raise RuntimeError(f"HIP error {rc}")
+    ok(hip.hipMalloc(ctypes.byref(src), ctypes.c_size_t(n_bytes))); ok(hip.hipMalloc(ctypes.byref(dst), ctypes.c_size_t(n_bytes)))
+    ok(hip.hipMemset(src, 1, ctypes.c_size_t(n_bytes))); ok(hip.hipEventCreate(ctypes.byref(e0))); ok(hip.hipEventCreate(ctypes.byref(e1)))
+    best = float("inf")
+    for _ in range(reps + 1):  # (the first one is the warm-up)
+        ok(hip.hipEventRecord(e0, None))
+        ok(hip.hipMemcpyAsync(dst, src, ctypes.c_size_t(n_bytes), 3, None))
+        ok(hip.hipEventRecord(e1, None)); ok(hip.hipEventSynchronize(e1)); ok(hip.hipEventElapsedTime(ctypes.byref(ms), e0, e1))
+        best = min(best, ms.value) if _ else best
+    hip.hipFree(src); hip.hipFree(dst); hip.hipEventDestroy(e0); hip.hipEventDestroy(e1)
+    return best
+
+
+lb, lo = synth.text_lexicon(30000, 11)
+with _native.Context() as gen:
+    tb, _to, _np, tn = gen.synth_generate_lex(a.mib << 20, 11, lb, lo)
+    dt, do, nw = gen.pretokenize(tb, n_bytes=tn)
+    pre_off = gen.d2h(do, 8 * (nw + 1), np.uint64)
+    base = [bytes([b]) for b in range(256)]
+    with _native.Context() as tr:
+        tr.set_vocab(base)
+        tr.load_words_ptr(dt, do, nw, dedup=True)
+        left, right, merged, _c = tr.train(a.merges, 1)
+    gen.pretokenize_free()
+    toks, merges = list(base), []
+    for l, r, m in zip(left.tolist(), right.tolist(), merged.tolist()):
+        merges.append((toks[l], toks[r]))
+        if m == len(toks):
+            toks.append(toks[l] + toks[r])
+    vocab = {t: i for i, t in enumerate(toks)}
+    gen.encode_set_model(vocab, merges, [], 0)
+    _di, _dd, n_all = gen.encode(tb, n_bytes=tn)
+    step = max(1, round(a.doc_ids * nw / n_all))  # pre-tokens per document
+    starts = np.ascontiguousarray(pre_off[:-1:step])
+    n_docs = len(starts)
+    gen.encode(tb, n_bytes=tn, doc_starts=starts)  # warm-up
+    di, dd, ni = gen.encode(tb, n_bytes=tn, doc_starts=starts)
+    enc = gen.encode_stats()
+    doc_off = gen.d2h(dd, 8 * (n_docs + 1), np.uint64).astype(np.int64)
+
+    def timed(call):
+        call()  # warm-up
+        runs = []
+        for _ in range(a.reps):
+            call()
+            runs.append(gen.layout_stats())
+        return min(runs, key=lambda r: r["total_ms"]), [round(r["total_ms"], 3) for r in runs]
+
+    def report(st, all_ms, read_b, write_b):
+        cp = copy_ms(write_b, a.reps)
+        rate, cp_rate = (read_b + write_b) / st["write_ms"] / 1e6, 2 * write_b / cp / 1e6
+        return {"rows": st["n_rows"], "row_len": st["row_len"], "truncated_docs": st["n_truncated_docs"], "ids_dropped": st["n_ids_dropped"],
+                "pad_slots": st["n_pad_slots"], "lengths_ms": round(st["lengths_ms"], 3), "write_ms": round(st["write_ms"], 3),
+                "total_ms": round(st["total_ms"], 3), "all_total_ms": all_ms, "bytes_read": read_b, "bytes_written": write_b,
+                "write_GB_per_s": round(rate, 1), "copy_same_output_bytes_ms": round(cp, 3), "copy_GB_per_s": round(cp_rate, 1),
+                "write_rate_vs_copy": round(rate / cp_rate, 3), "write_ms_vs_copy_ms": round(st["write_ms"] / cp, 2),
+                "total_vs_encode_emit_ms": round(st["total_ms"] / enc["emit_ms"], 3)}
+
+    lens = np.diff(doc_off)
+    st, all_ms = timed(lambda: gen.layout_pad(di, ni, dd, n_docs, row_len=PAD_LEN, pad_id=0))
+    padded = report(st, all_ms, 4 * int(np.minimum(lens, PAD_LEN).sum()) + 8 * n_docs, 4 * n_docs * PAD_LEN + 4 * n_docs)
+    st, all_ms = timed(lambda: gen.layout_pack(di, ni, dd, n_docs, row_len=PACK_LEN, pad_id=0, eos_id=EOS))
+    packed = report(st, all_ms, 4 * ni + 8 * (n_docs + 1), 12 * st["n_rows"] * PACK_LEN)
+    gen.layout_free()
+    n_host = int(np.searchsorted(starts, a.host_mib << 20))  # the documents that lie inside the host sample
+    sample = gen.d2h(tb, int(starts[n_host]) if n_host < n_docs else tn).tobytes()
+    cuts = starts[:n_host].tolist() + [len(sample)]
+
+docs = [sample[p:q].decode("utf-8") for p, q in zip(cuts, cuts[1:])]
+tok = BBPETokenizer(vocab=vocab, merges=merges)
+tok.encode_array_padded(docs[:8], PAD_LEN, pad_id=0)  # (model upload, warm-up)
+t0 = time.perf_counter()
+rows_dev, _len = tok.encode_array_padded(docs, PAD_LEN, pad_id=0)
+dev_s = time.perf_counter() - t0
+t0 = time.perf_counter()
+ids, off = tok.encode_array(docs)
+enc_s = time.perf_counter() - t0
+rows = np.zeros((len(docs), PAD_LEN), dtype=np.uint32)
+for d in range(len(docs)):  # what a user writes today: one slice and one assignment per document
+    s = ids[off[d]:off[d + 1]][:PAD_LEN]
+    rows[d, :len(s)] = s
+host_s = time.perf_counter() - t0
+assert np.array_equal(rows, rows_dev)
+out = {"text_bytes": tn, "merges": len(merges), "ids": ni, "docs": n_docs, "mean_ids_per_doc": round(ni / n_docs, 1),
+       "encode_emit_ms": round(enc["emit_ms"], 3), "encode_total_ms": round(enc["total_ms"], 3), "padded_1024": padded,
+       "packed_2048_eos": packed,
+       "host_sample": {"text_bytes": len(sample), "docs": len(docs), "encode_array_then_numpy_loop_s": round(host_s, 3),
+                       "of_which_encode_array_s": round(enc_s, 3), "MB_per_s": round(len(sample) / host_s / 1e6, 1),
+                       "encode_array_padded_s": round(dev_s, 3), "encode_array_padded_MB_per_s": round(len(sample) / dev_s / 1e6, 1)}}
+print(json.dumps(out))
+if a.json:
+    Path(a.json).parent.mkdir(parents=True, exist_ok=True)
+    Path(a.json).write_text(json.dumps(out, indent=1))

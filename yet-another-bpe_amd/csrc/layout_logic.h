@@ -1,0 +1,77 @@
+// layout_logic.h -- the index rules of BBPETokenizer.encode_batch_padded / encode_batch_packed (yet_another_bpe/tokenizer.py) on
+// flat arrays, shared by the HIP kernels (yabpe_layout_kernels.h) and by the CPU unit-test model (tests/hostmodel/layout_model.cpp).
+//
+//   seq(d)    [bos] + the document's ids + [eos]; n_added = how many of the two are given; len(seq(d)) = n(d) + n_added.
+//   padded    row d holds seq(d) cut to row_len: the content keeps its head (or, LAY_TRUNC_LEFT, its tail), BOS and EOS always
+//             survive; the kept sequence sits at the row's left end (or, LAY_PAD_LEFT, at its right end), pad_id elsewhere.
+//             Rule 1 (lay_pad_slot): which source id, if any, slot (row, col) holds.
+//   packed    all seq(d) end to end, cut into rows of row_len.  The stream offset of document d is the exclusive scan of
+//             len(seq(d)); the ids of a call are already laid end to end with their starts in doc_off, so that scan has the
+//             closed form soff[d] = doc_off[d] + n_added * d (soff[n_docs] = n_ids + n_added * n_docs).
+//             Rule 2 (lay_find_doc / lay_pack_slot): which (doc, pos) a stream position belongs to, given soff.  A document
+//             with an empty seq has soff[d] == soff[d + 1] and owns no position: the search takes the LAST d with soff[d] <= g.
+#pragma once
+#include <stdint.h>
+
+#include "tile_logic.h" // YB_HD
+
+// (the values of YABPE_LAYOUT_* in include/yabpe.h)
+constexpr uint32_t LAY_BOS = 0x01u, LAY_EOS = 0x02u, LAY_TRUNC_LEFT = 0x04u, LAY_PAD_LEFT = 0x08u, LAY_DROP_LAST = 0x10u;
+constexpr uint32_t LAY_PAD_FLAGS = LAY_BOS | LAY_EOS | LAY_TRUNC_LEFT | LAY_PAD_LEFT;
+constexpr uint32_t LAY_PACK_FLAGS = LAY_BOS | LAY_EOS | LAY_DROP_LAST;
+constexpr uint32_t LAY_NO_DOC = 0xFFFFFFFFu;                   // `doc` of a packed slot past the end of the stream
+constexpr unsigned long long LAY_MAX_SLOTS = 1ull << 36;       // output slots one call addresses at most
+
+// what a slot holds: a source id (index into ids), or one of the three constants
+constexpr unsigned long long LAY_SLOT_PAD = ~0ull, LAY_SLOT_BOS = ~0ull - 1, LAY_SLOT_EOS = ~0ull - 2;
+
+YB_HD uint32_t lay_n_added(uint32_t flags) { return (flags & LAY_BOS ? 1u : 0u) + (flags & LAY_EOS ? 1u : 0u); }
+
+// length of seq(d) after the cut to row_len (row_len >= n_added), n = the document's ids
+YB_HD unsigned long long lay_kept(unsigned long long n, unsigned long long row_len, uint32_t flags) {
+    const unsigned long long seq = n + lay_n_added(flags);
+    return seq < row_len ? seq : row_len;
+}
+
+// Rule 1.  Slot `col` of the padded row of a document whose n ids start at ids[start]: the index of the id it holds, or
+// LAY_SLOT_PAD / LAY_SLOT_BOS / LAY_SLOT_EOS.
+YB_HD unsigned long long lay_pad_slot(unsigned long long start, unsigned long long n, uint32_t row_len, uint32_t flags, uint32_t col) {
+    const uint32_t added = lay_n_added(flags), bos = flags & LAY_BOS ? 1u : 0u;
+    const uint32_t kept = (uint32_t)lay_kept(n, row_len, flags);
+    const uint32_t lead = flags & LAY_PAD_LEFT ? row_len - kept : 0u; // pad slots in front of the sequence
+    if (col < lead || col - lead >= kept) return LAY_SLOT_PAD;
+    const uint32_t p = col - lead; // index into the kept sequence
+    if (bos && p == 0) return LAY_SLOT_BOS;
+    if ((flags & LAY_EOS) && p == kept - 1) return LAY_SLOT_EOS;
+    const unsigned long long kc = kept - added; // content ids kept: the head, or the tail
+    return start + (flags & LAY_TRUNC_LEFT ? n - kc : 0ull) + (p - bos);
+}
+
+// Rule 2.  The document stream position g lies in: the largest d in [lo, hi] with soff[d - org] <= g (soff[lo - org] <= g is
+// the caller's promise; hi = the last document that may own g).  org: the document soff[0] belongs to (an LDS window).
+YB_HD uint32_t lay_find_doc(const unsigned long long *soff, uint32_t org, uint32_t lo, uint32_t hi, unsigned long long g) {
+    while (lo < hi) {
+        const uint32_t mid = lo + (hi - lo + 1) / 2;
+        if (soff[mid - org] <= g)
+            lo = mid;
+        else
+            hi = mid - 1;
+    }
+    return lo;
+}
+
+// Stream position g in document d (soff_d = soff[d], soff_next = soff[d + 1]): *pos = its index inside seq(d); returns the index
+// of the id it holds, or LAY_SLOT_BOS / LAY_SLOT_EOS.  The document's ids start at soff_d - n_added * d.
+YB_HD unsigned long long lay_pack_slot(unsigned long long g, uint32_t d, unsigned long long soff_d, unsigned long long soff_next, uint32_t flags,
+                                       unsigned long long *pos) {
+    const unsigned long long p = g - soff_d;
+    *pos = p;
+    if ((flags & LAY_BOS) && p == 0) return LAY_SLOT_BOS;
+    if ((flags & LAY_EOS) && g + 1 == soff_next) return LAY_SLOT_EOS;
+    return g - (unsigned long long)lay_n_added(flags) * d - (flags & LAY_BOS ? 1u : 0u);
+}
+
+// rows of a packed batch over a stream of `total` positions
+YB_HD unsigned long long lay_pack_rows(unsigned long long total, uint32_t row_len, uint32_t flags) {
+    return flags & LAY_DROP_LAST ? total / row_len : (total + row_len - 1) / row_len;
+}

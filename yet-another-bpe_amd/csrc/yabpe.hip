@@ -28,6 +28,7 @@
 #include "yabpe_pretok_kernels.h"
 #include "yabpe_encode_kernels.h"
 #include "yabpe_decode_kernels.h"
+#include "yabpe_layout_kernels.h"
 #include "yabpe_replay_kernels.h"
 #include "unicode_classes.inc"
 
@@ -170,6 +171,10 @@ struct yabpe_ctx {
     unsigned long long *dec_doc = nullptr;
     yabpe_decode_stats_t dec_stats{};
     hipEvent_t dec_ev[7] = {};
+    // fixed-shape batches (yabpe_layout_pad / yabpe_layout_pack)
+    uint32_t *lay_buf[3] = {};                // results of the last layout call: rows, lengths / ids, doc, pos
+    yabpe_layout_stats_t lay_stats{};
+    hipEvent_t lay_ev[4] = {};
     // resumed load (yabpe_load_words_resumed)
     yabpe_resume_stats_t resume_stats{};
     // misc device scratch
@@ -960,6 +965,9 @@ void yabpe_destroy(yabpe_ctx *c) {
     yabpe_decode_free(c);
     dfree(c->dec_ent); dfree(c->dec_pool);
     for (auto &e : c->dec_ev)
+        if (e) (void)hipEventDestroy(e);
+    yabpe_layout_free(c);
+    for (auto &e : c->lay_ev)
         if (e) (void)hipEventDestroy(e);
     dfree(c->pt_cls);
     free_corpus(c);
@@ -2859,6 +2867,178 @@ int yabpe_decode(yabpe_ctx *c, const uint32_t *ids, uint64_t n_ids, const uint64
 int yabpe_decode_stats(yabpe_ctx *c, yabpe_decode_stats_t *out) {
     if (!c || !out) return YABPE_E_INVALID;
     *out = c->dec_stats;
+    return YABPE_OK;
+}
+
+// ---------------------------------------------------------------------------------------------- fixed-shape batches
+int yabpe_layout_free(yabpe_ctx *c) {
+    if (!c) return YABPE_E_INVALID;
+    for (auto &p : c->lay_buf) {
+        dfree(p);
+        p = nullptr;
+    }
+    return YABPE_OK;
+}
+
+// What both layout calls begin with: the arguments checked (mode_flags: the flags the call takes), the last layout released,
+// the stats reset, the ids and the validated document starts on the device.
+static int layout_begin(yabpe_ctx *c, Scratch &S, const uint32_t *ids, uint64_t n_ids, const uint64_t *doc_off, uint32_t *n_docs,
+                        const yabpe_layout_t *lay, uint32_t mode_flags, const uint32_t **d_ids, const unsigned long long **d_docs) {
+    if (!lay) return fail(c, YABPE_E_INVALID, "layout is NULL");
+    if (lay->flags & ~(LAY_PAD_FLAGS | LAY_PACK_FLAGS)) return fail(c, YABPE_E_INVALID, "unknown layout flags 0x%x", lay->flags);
+    if (lay->flags & ~mode_flags)
+        return fail(c, YABPE_E_INVALID, "layout flags 0x%x do not belong to this call (it takes 0x%x)", lay->flags & ~mode_flags, mode_flags);
+    if (n_ids && !ids) return fail(c, YABPE_E_INVALID, "ids is NULL");
+    if (!doc_off && *n_docs > 1) return fail(c, YABPE_E_INVALID, "doc_off is NULL with %u documents", *n_docs);
+    // the document starts on the host (validated: the kernels index the ids with them) and on the device
+    const bool docs_dev = doc_off && is_device_ptr(doc_off);
+    if (!doc_off) *n_docs = 1;
+    std::vector<uint64_t> h_docs(*n_docs, 0);
+    if (doc_off && *n_docs) {
+        if (docs_dev) HIPCHK(c, hipMemcpy(h_docs.data(), doc_off, (size_t)*n_docs * 8, hipMemcpyDeviceToHost));
+        else memcpy(h_docs.data(), doc_off, (size_t)*n_docs * 8);
+    }
+    TRY(check_starts(c, h_docs.data(), *n_docs, n_ids, "ids"));
+    yabpe_layout_free(c);
+    c->lay_stats = yabpe_layout_stats_t{};
+    c->lay_stats.n_ids = n_ids;
+    c->lay_stats.n_docs = *n_docs;
+    for (auto &e : c->lay_ev)
+        if (!e) HIPCHK(c, hipEventCreate(&e));
+    TRY(to_device(c, S, ids, n_ids * 4, 4, d_ids));
+    TRY(to_device(c, S, docs_dev ? (const unsigned long long *)doc_off : (const unsigned long long *)h_docs.data(), (uint64_t)*n_docs * 8, 8, d_docs));
+    return 0;
+}
+
+// lay_ev[0..1] around the lengths pass, [2..3] around the write pass
+static void layout_times(yabpe_ctx *c) {
+    float ms[3] = {0, 0, 0};
+    (void)hipEventElapsedTime(&ms[0], c->lay_ev[0], c->lay_ev[1]);
+    (void)hipEventElapsedTime(&ms[1], c->lay_ev[2], c->lay_ev[3]);
+    (void)hipEventElapsedTime(&ms[2], c->lay_ev[0], c->lay_ev[3]);
+    c->lay_stats.lengths_ms = ms[0];
+    c->lay_stats.write_ms = ms[1];
+    c->lay_stats.total_ms = ms[2];
+}
+
+int yabpe_layout_pad(yabpe_ctx *c, const uint32_t *ids, uint64_t n_ids, const uint64_t *doc_off, uint32_t n_docs, const yabpe_layout_t *lay,
+                     uint32_t **out_dev_rows, uint32_t **out_dev_len, uint32_t *out_row_len) {
+    if (!c || !out_dev_rows || !out_dev_len || !out_row_len) return YABPE_E_INVALID;
+    HIPCHK(c, hipSetDevice(c->device));
+    *out_dev_rows = nullptr; *out_dev_len = nullptr; *out_row_len = 0;
+    if (lay && lay->row_len && lay->row_len < lay_n_added(lay->flags & LAY_PAD_FLAGS))
+        return fail(c, YABPE_E_INVALID, "row_len %u cannot hold BOS and EOS", lay->row_len);
+    if (lay && (unsigned long long)lay->row_len * n_docs > LAY_MAX_SLOTS)
+        return fail(c, YABPE_E_CAPACITY, "%u rows of %u slots: at most 2^36 slots in one call", n_docs, lay->row_len);
+    Scratch S(c->device, c->rank);
+    const uint32_t *d_ids = nullptr;
+    const unsigned long long *d_docs = nullptr;
+    TRY(layout_begin(c, S, ids, n_ids, doc_off, &n_docs, lay, LAY_PAD_FLAGS, &d_ids, &d_docs));
+    hipStream_t s = c->stream;
+    // ---- lengths: kept length per document, the longest sequence, what the cut drops
+    unsigned long long *counters = nullptr;
+    HIPCHK(c, S.get(&counters, 4));
+    TRY(dmalloc(c, &c->lay_buf[1], n_docs));
+    HIPCHK(c, hipEventRecord(c->lay_ev[0], s));
+    HIPCHK(c, hipMemsetAsync(counters, 0, 32, s));
+    hipLaunchKernelGGL(k_lay_lengths<false>, dim3(cdiv64(n_docs, BLOCK)), dim3(BLOCK), 0, s,
+                       LayLenParams{d_docs, n_docs, n_ids, lay->row_len, lay->flags, c->lay_buf[1], nullptr, counters});
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipEventRecord(c->lay_ev[1], s));
+    unsigned long long h_cnt[4] = {0, 0, 0, 0};
+    HIPCHK(c, hipMemcpyAsync(h_cnt, counters, 32, hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipStreamSynchronize(s));
+    const unsigned long long L = lay->row_len ? lay->row_len : h_cnt[0];
+    const unsigned long long n_slots = L * n_docs;
+    if (L > 0xFFFFFFFFull || n_slots > LAY_MAX_SLOTS) {
+        yabpe_layout_free(c);
+        return fail(c, YABPE_E_CAPACITY, "%u rows of %llu slots (the longest sequence): at most 2^36 slots of at most 2^32 - 1 a row", n_docs, L);
+    }
+    // ---- write
+    TRY(dmalloc(c, &c->lay_buf[0], n_slots));
+    HIPCHK(c, hipEventRecord(c->lay_ev[2], s));
+    if (n_slots)
+        hipLaunchKernelGGL(k_lay_pad_write, dim3(cdiv64(n_slots, LAY_PIECE)), dim3(BLOCK), 0, s,
+                           LayPadParams{d_ids, d_docs, n_docs, n_ids, (uint32_t)L, lay->flags, LayConst{lay->pad_id, lay->bos_id, lay->eos_id},
+                                        c->lay_buf[0], n_slots});
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipEventRecord(c->lay_ev[3], s));
+    const hipError_t se = hipStreamSynchronize(s);
+    if (se != hipSuccess) {
+        yabpe_layout_free(c);
+        return fail(c, YABPE_E_HIP, "layout kernels failed: %s", hipGetErrorString(se));
+    }
+    auto &st = c->lay_stats;
+    st.n_rows = n_docs;
+    st.row_len = L;
+    st.n_truncated_docs = h_cnt[1];
+    st.n_ids_dropped = h_cnt[2];
+    st.n_pad_slots = n_slots - h_cnt[3];
+    layout_times(c);
+    *out_dev_rows = c->lay_buf[0];
+    *out_dev_len = c->lay_buf[1];
+    *out_row_len = (uint32_t)L;
+    return YABPE_OK;
+}
+
+int yabpe_layout_pack(yabpe_ctx *c, const uint32_t *ids, uint64_t n_ids, const uint64_t *doc_off, uint32_t n_docs, const yabpe_layout_t *lay,
+                      uint32_t **out_dev_ids, uint32_t **out_dev_doc, uint32_t **out_dev_pos, uint64_t *out_n_rows) {
+    if (!c || !out_dev_ids || !out_dev_doc || !out_dev_pos || !out_n_rows) return YABPE_E_INVALID;
+    HIPCHK(c, hipSetDevice(c->device));
+    *out_dev_ids = nullptr; *out_dev_doc = nullptr; *out_dev_pos = nullptr; *out_n_rows = 0;
+    if (lay && lay->row_len == 0) return fail(c, YABPE_E_INVALID, "row_len is 0: a packed row holds at least one slot");
+    Scratch S(c->device, c->rank);
+    const uint32_t *d_ids = nullptr;
+    const unsigned long long *d_docs = nullptr;
+    TRY(layout_begin(c, S, ids, n_ids, doc_off, &n_docs, lay, LAY_PACK_FLAGS, &d_ids, &d_docs));
+    const unsigned long long total = n_ids + (unsigned long long)lay_n_added(lay->flags) * n_docs;
+    if (total > LAY_MAX_SLOTS) return fail(c, YABPE_E_CAPACITY, "a stream of %llu entries: at most 2^36 slots in one call", total);
+    const unsigned long long n_rows = lay_pack_rows(total, lay->row_len, lay->flags), n_slots = n_rows * lay->row_len;
+    hipStream_t s = c->stream;
+    // ---- lengths: the stream offsets (closed form) and the longest sequence
+    unsigned long long *counters = nullptr, *soff = nullptr;
+    HIPCHK(c, S.get(&counters, 4));
+    HIPCHK(c, S.get(&soff, (uint64_t)n_docs + 1));
+    HIPCHK(c, hipEventRecord(c->lay_ev[0], s));
+    HIPCHK(c, hipMemsetAsync(counters, 0, 32, s));
+    hipLaunchKernelGGL(k_lay_lengths<true>, dim3(cdiv64(n_docs, BLOCK)), dim3(BLOCK), 0, s,
+                       LayLenParams{d_docs, n_docs, n_ids, lay->row_len, lay->flags, nullptr, soff, counters});
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipEventRecord(c->lay_ev[1], s));
+    unsigned long long longest = 0;
+    HIPCHK(c, hipMemcpyAsync(&longest, counters, 8, hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipStreamSynchronize(s));
+    if (longest > 0xFFFFFFFFull) return fail(c, YABPE_E_CAPACITY, "a document of %llu stream entries: positions are u32", longest);
+    // ---- write
+    for (auto &p : c->lay_buf) TRY(dmalloc(c, &p, n_slots));
+    HIPCHK(c, hipEventRecord(c->lay_ev[2], s));
+    if (n_slots)
+        hipLaunchKernelGGL(k_lay_pack_write, dim3(cdiv64(n_slots, LAY_PIECE)), dim3(BLOCK), 0, s,
+                           LayPackParams{d_ids, soff, n_docs, total, n_slots, lay->flags, LayConst{lay->pad_id, lay->bos_id, lay->eos_id},
+                                         c->lay_buf[0], c->lay_buf[1], c->lay_buf[2]});
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipEventRecord(c->lay_ev[3], s));
+    const hipError_t se = hipStreamSynchronize(s);
+    if (se != hipSuccess) {
+        yabpe_layout_free(c);
+        return fail(c, YABPE_E_HIP, "layout kernels failed: %s", hipGetErrorString(se));
+    }
+    auto &st = c->lay_stats;
+    st.n_rows = n_rows;
+    st.row_len = lay->row_len;
+    st.n_ids_dropped = total > n_slots ? total - n_slots : 0;
+    st.n_pad_slots = n_slots > total ? n_slots - total : 0;
+    layout_times(c);
+    *out_dev_ids = c->lay_buf[0];
+    *out_dev_doc = c->lay_buf[1];
+    *out_dev_pos = c->lay_buf[2];
+    *out_n_rows = n_rows;
+    return YABPE_OK;
+}
+
+int yabpe_layout_stats(yabpe_ctx *c, yabpe_layout_stats_t *out) {
+    if (!c || !out) return YABPE_E_INVALID;
+    *out = c->lay_stats;
     return YABPE_OK;
 }
 

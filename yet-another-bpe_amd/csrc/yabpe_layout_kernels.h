@@ -1,0 +1,222 @@
+// yabpe_layout_kernels.h -- ragged ids + document starts -> the two fixed shapes a model consumes (rules in layout_logic.h;
+// contract: BBPETokenizer.encode_batch_padded / encode_batch_packed, yet_another_bpe/tokenizer.py).
+//
+// Passes (host orchestration: yabpe_layout_pad / yabpe_layout_pack in yabpe.hip):
+//   lengths   k_lay_lengths: one thread per document.  Padded: the kept length of every row, and per call the longest
+//             sequence, the truncated documents, the ids dropped and the slots kept (one atomic per counter and workgroup).
+//             Packed: the stream offsets soff[n_docs + 1] in their closed form doc_off[d] + n_added * d (layout_logic.h: the ids
+//             already lie end to end, so the exclusive scan of len(seq(d)) needs no scan pass), and the longest sequence.
+//   write     k_lay_pad_write / k_lay_pack_write: the output is indexed flat; a thread owns 4 consecutive slots per step,
+//             resolves each of them and stores 16 bytes (output buffers are 256-B aligned, so a store at a flat index that is a
+//             multiple of 4 is aligned whatever row_len is).  A workgroup owns LAY_PIECE consecutive slots.  The packed form
+//             finds the piece's first and last document by binary search in soff and stages that window in LDS; a window of
+//             more than LAY_STAGE offsets (many tiny documents in one piece) is searched in global memory instead.  The pad
+//             tail of the last packed row is written by the same kernel.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "layout_logic.h"
+#include "yabpe_kernels.h" // BLOCK, WPB
+
+namespace yb {
+
+constexpr int LAY_VPT = 4;                     // 16-byte stores per thread (and output array)
+constexpr int LAY_PIECE = BLOCK * 4 * LAY_VPT; // output slots per workgroup
+constexpr int LAY_STAGE = 2048;                // stream offsets the packed write stages in LDS (16 KiB)
+
+struct LayLenParams {
+    const unsigned long long *doc;  // n_docs document starts (ids), ascending, doc[0] = 0
+    uint32_t n_docs;
+    unsigned long long n_ids;
+    uint32_t row_len, flags;        // padded: row_len 0 = no cut (the longest sequence becomes the row length)
+    uint32_t *len;                  // out, padded: kept length per document
+    unsigned long long *soff;       // out, packed: n_docs + 1 stream offsets
+    unsigned long long *counters;   // [0] longest sequence; padded also [1] truncated documents [2] ids dropped [3] slots kept
+};
+
+template <bool PACK>
+__global__ __launch_bounds__(BLOCK) void k_lay_lengths(LayLenParams P) {
+    __shared__ unsigned long long s_red[WPB][4];
+    const unsigned long long d = (unsigned long long)blockIdx.x * BLOCK + threadIdx.x;
+    const uint32_t added = lay_n_added(P.flags);
+    unsigned long long v[4] = {0, 0, 0, 0}; // max, truncated, dropped, kept
+    if (d < P.n_docs) {
+        const unsigned long long a = P.doc[d], b = d + 1 < P.n_docs ? P.doc[d + 1] : P.n_ids;
+        const unsigned long long seq = b - a + added;
+        v[0] = seq;
+        if (PACK) {
+            P.soff[d] = a + added * d;
+            if (d + 1 == P.n_docs) P.soff[d + 1] = P.n_ids + (unsigned long long)added * P.n_docs;
+        } else {
+            const unsigned long long kept = P.row_len ? lay_kept(b - a, P.row_len, P.flags) : seq;
+            P.len[d] = (uint32_t)kept;
+            v[1] = seq > kept ? 1u : 0u;
+            v[2] = seq - kept;
+            v[3] = kept;
+        }
+    }
+    const int lane = threadIdx.x & 63, wib = threadIdx.x >> 6;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const unsigned long long m = __shfl_xor(v[0], o);
+        v[0] = m > v[0] ? m : v[0];
+#pragma unroll
+        for (int k = 1; k < 4; ++k) v[k] += __shfl_xor(v[k], o);
+    }
+    if (lane == 0)
+        for (int k = 0; k < 4; ++k) s_red[wib][k] = v[k];
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int w = 1; w < WPB; ++w) {
+            v[0] = s_red[w][0] > v[0] ? s_red[w][0] : v[0];
+            for (int k = 1; k < 4; ++k) v[k] += s_red[w][k];
+        }
+        atomicMax(&P.counters[0], v[0]);
+        if (!PACK)
+            for (int k = 1; k < 4; ++k)
+                if (v[k]) atomicAdd(&P.counters[k], v[k]);
+    }
+}
+
+struct LayConst {
+    uint32_t pad_id, bos_id, eos_id;
+};
+
+// the id a resolved slot holds (slot: an index into ids or one of LAY_SLOT_*)
+__device__ __forceinline__ uint32_t lay_value(const uint32_t *ids, unsigned long long slot, const LayConst &K) {
+    if (slot == LAY_SLOT_PAD) return K.pad_id;
+    if (slot == LAY_SLOT_BOS) return K.bos_id;
+    if (slot == LAY_SLOT_EOS) return K.eos_id;
+    return ids[slot];
+}
+
+// 4 slots at flat index f (a multiple of 4) of an array of n_slots: one 16-B store, or the last 1..3 slots one by one
+__device__ __forceinline__ void lay_store4(uint32_t *out, unsigned long long f, unsigned long long n_slots, const uint32_t (&v)[4]) {
+    if (f + 4 <= n_slots) {
+        *reinterpret_cast<uint4 *>(out + f) = make_uint4(v[0], v[1], v[2], v[3]);
+        return;
+    }
+    for (int k = 0; k < 4; ++k)
+        if (f + k < n_slots) out[f + k] = v[k];
+}
+
+struct LayPadParams {
+    const uint32_t *ids;
+    const unsigned long long *doc;  // n_docs document starts
+    uint32_t n_docs;
+    unsigned long long n_ids;
+    uint32_t row_len, flags;        // row_len >= 1
+    LayConst K;
+    uint32_t *rows;                 // out: n_docs * row_len slots
+    unsigned long long n_slots;
+};
+
+__global__ __launch_bounds__(BLOCK) void k_lay_pad_write(LayPadParams P) {
+    const unsigned long long f0 = (unsigned long long)blockIdx.x * LAY_PIECE;
+    const bool narrow = P.n_slots <= 0xFFFFFFFFull; // (uniform: the 32-bit division then)
+#pragma unroll
+    for (int s = 0; s < LAY_VPT; ++s) {
+        const unsigned long long f = f0 + ((unsigned long long)s * BLOCK + threadIdx.x) * 4;
+        if (f >= P.n_slots) break;
+        unsigned long long row;
+        uint32_t col;
+        if (narrow) {
+            row = (uint32_t)f / P.row_len;
+            col = (uint32_t)f % P.row_len;
+        } else {
+            row = f / P.row_len;
+            col = (uint32_t)(f % P.row_len);
+        }
+        unsigned long long a = P.doc[row], b = row + 1 < P.n_docs ? P.doc[row + 1] : P.n_ids;
+        uint32_t v[4] = {0, 0, 0, 0};
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            if (f + k >= P.n_slots) break;
+            v[k] = lay_value(P.ids, lay_pad_slot(a, b - a, P.row_len, P.flags, col), P.K);
+            if (++col == P.row_len && row + 1 < P.n_docs) { // the next slot opens the next row
+                col = 0;
+                ++row;
+                a = b;
+                b = row + 1 < P.n_docs ? P.doc[row + 1] : P.n_ids;
+            }
+        }
+        lay_store4(P.rows, f, P.n_slots, v);
+    }
+}
+
+struct LayPackParams {
+    const uint32_t *ids;
+    const unsigned long long *soff; // n_docs + 1 stream offsets (k_lay_lengths<true>)
+    uint32_t n_docs;
+    unsigned long long total;       // stream positions: soff[n_docs]
+    unsigned long long n_slots;     // n_rows * row_len: slots at or past `total` are the pad tail
+    uint32_t flags;
+    LayConst K;
+    uint32_t *out_ids, *out_doc, *out_pos;
+};
+
+// The slots of one lane: w = the stream offsets of the documents [d0, d1 + 1] seen through the origin org (w[d - org]).
+__device__ __forceinline__ void lay_pack_lane(const LayPackParams &P, const unsigned long long *w, uint32_t org, uint32_t d0, uint32_t d1,
+                                              unsigned long long g0, unsigned long long g1) {
+#pragma unroll
+    for (int s = 0; s < LAY_VPT; ++s) {
+        const unsigned long long g = g0 + ((unsigned long long)s * BLOCK + threadIdx.x) * 4;
+        if (g >= g1) break;
+        uint32_t vi[4] = {0, 0, 0, 0}, vd[4] = {0, 0, 0, 0}, vp[4] = {0, 0, 0, 0};
+        uint32_t d = d0;
+        unsigned long long sd = 0, next = 0; // soff[d], soff[d + 1]; next = 0: not looked up yet
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const unsigned long long gg = g + k;
+            if (gg >= g1) break; // (the last vector of the output: slots that do not exist; [d0, d1] does not cover them)
+            if (gg >= P.total) { // the pad tail
+                vi[k] = P.K.pad_id;
+                vd[k] = LAY_NO_DOC;
+                continue;
+            }
+            if (gg >= next) { // the first slot, or the document ended: the last document that starts at or before gg
+                d = lay_find_doc(w, org, next ? d + 1 : d0, d1, gg);
+                sd = w[d - org];
+                next = w[d + 1 - org];
+            }
+            unsigned long long pos;
+            vi[k] = lay_value(P.ids, lay_pack_slot(gg, d, sd, next, P.flags, &pos), P.K);
+            vd[k] = d;
+            vp[k] = (uint32_t)pos;
+        }
+        lay_store4(P.out_ids, g, P.n_slots, vi);
+        lay_store4(P.out_doc, g, P.n_slots, vd);
+        lay_store4(P.out_pos, g, P.n_slots, vp);
+    }
+}
+
+__global__ __launch_bounds__(BLOCK) void k_lay_pack_write(LayPackParams P) {
+    __shared__ unsigned long long s_off[LAY_STAGE];
+    __shared__ uint32_t s_d[2];
+    const unsigned long long g0 = (unsigned long long)blockIdx.x * LAY_PIECE;
+    const unsigned long long g1 = g0 + LAY_PIECE < P.n_slots ? g0 + LAY_PIECE : P.n_slots;
+    const unsigned long long e = g1 < P.total ? g1 : P.total; // end of the piece's part of the stream
+    uint32_t d0 = 0, d1 = 0;
+    bool staged = false;
+    if (g0 < e) { // (uniform)
+        if (threadIdx.x == 0) {
+            s_d[0] = lay_find_doc(P.soff, 0, 0, P.n_docs - 1, g0);
+            s_d[1] = lay_find_doc(P.soff, 0, s_d[0], P.n_docs - 1, e - 1);
+        }
+        __syncthreads();
+        d0 = s_d[0];
+        d1 = s_d[1];
+        staged = d1 - d0 + 2 <= (uint32_t)LAY_STAGE;
+        if (staged) {
+            for (uint32_t i = threadIdx.x; i < d1 - d0 + 2; i += BLOCK) s_off[i] = P.soff[d0 + i];
+            __syncthreads();
+        }
+    }
+    if (staged)
+        lay_pack_lane(P, s_off, d0, d0, d1, g0, g1);
+    else
+        lay_pack_lane(P, P.soff, 0, d0, d1, g0, g1);
+}
+
+} // namespace yb

@@ -57,6 +57,16 @@ class DecodeStats(ctypes.Structure):
         (n, c_double) for n in ("lengths_ms", "gather_ms", "check_ms", "repair_ms", "total_ms")]
 
 
+class LayoutStats(ctypes.Structure):
+    _fields_ = [(n, c_uint64) for n in ("n_ids", "n_docs", "n_rows", "row_len", "n_truncated_docs", "n_ids_dropped", "n_pad_slots")] + [
+        (n, c_double) for n in ("lengths_ms", "write_ms", "total_ms")]
+
+
+class Layout(ctypes.Structure):
+    """yabpe_layout_t"""
+    _fields_ = [(n, c_uint32) for n in ("row_len", "pad_id", "bos_id", "eos_id", "flags")]
+
+
 class ResumeStats(ctypes.Structure):
     _fields_ = [(n, c_uint64) for n in ("n_unique", "n_long", "tokens")] + [(n, c_double) for n in ("segment_ms", "build_ms")]
 
@@ -79,6 +89,7 @@ SYMBOLS = [
     "yabpe_encode_set_model", "yabpe_encode", "yabpe_encode_spans", "yabpe_encode_free", "yabpe_encode_stats", "yabpe_encode_checksum",
     "yabpe_decode_set_model", "yabpe_decode", "yabpe_decode_free", "yabpe_decode_stats",
     "yabpe_load_words_resumed", "yabpe_resume_stats",
+    "yabpe_layout_pad", "yabpe_layout_pack", "yabpe_layout_free", "yabpe_layout_stats",
 ]
 
 
@@ -137,6 +148,12 @@ def lib() -> ctypes.CDLL:
         L.yabpe_decode.argtypes = [c_void_p, c_void_p, c_uint64, c_void_p, c_uint32, POINTER(c_void_p), POINTER(c_void_p), POINTER(c_uint64)]
         L.yabpe_decode_free.argtypes = [c_void_p]
         L.yabpe_decode_stats.argtypes = [c_void_p, POINTER(DecodeStats)]
+        L.yabpe_layout_pad.argtypes = [c_void_p, c_void_p, c_uint64, c_void_p, c_uint32, POINTER(Layout), POINTER(c_void_p), POINTER(c_void_p),
+                                       POINTER(c_uint32)]
+        L.yabpe_layout_pack.argtypes = [c_void_p, c_void_p, c_uint64, c_void_p, c_uint32, POINTER(Layout), POINTER(c_void_p), POINTER(c_void_p),
+                                        POINTER(c_void_p), POINTER(c_uint64)]
+        L.yabpe_layout_free.argtypes = [c_void_p]
+        L.yabpe_layout_stats.argtypes = [c_void_p, POINTER(LayoutStats)]
         if L.yabpe_abi_version() != 2:
             raise ImportError("libyabpe.so ABI version mismatch")
         _lib = L
@@ -145,6 +162,8 @@ def lib() -> ctypes.CDLL:
 
 LOAD_DEDUP = 0x1
 SPANS_CHARS = 0x1  # yabpe_encode_spans: code points instead of bytes
+LAYOUT_BOS, LAYOUT_EOS, LAYOUT_TRUNC_LEFT, LAYOUT_PAD_LEFT, LAYOUT_DROP_LAST = 0x01, 0x02, 0x04, 0x08, 0x10  # yabpe_layout_t.flags
+LAYOUT_NO_DOC = 0xFFFFFFFF  # `doc` of a packed slot past the end of the stream
 
 
 class Context:
@@ -463,6 +482,71 @@ class Context:
         s = DecodeStats()
         self._chk(lib().yabpe_decode_stats(self._h, byref(s)))
         return {f: getattr(s, f) for f, _ in DecodeStats._fields_}
+
+    # -- fixed-shape batches (BBPETokenizer.encode_batch_padded / encode_batch_packed on the device)
+    @staticmethod
+    def _layout_args(ids, n_ids, doc_starts, n_docs, row_len, pad_id, bos_id, eos_id, flags):
+        """ids / doc_starts as decode() takes them -> (keep-alive arrays, ids pointer, n_ids, starts pointer, n_docs, Layout)"""
+        keep = docs = None
+        if isinstance(ids, int):
+            ptr, n = c_void_p(ids), int(n_ids)
+        else:
+            keep = np.ascontiguousarray(ids, dtype=np.uint32)
+            ptr, n = c_void_p(keep.ctypes.data if keep.size else 0), int(keep.size)
+        if isinstance(doc_starts, int):
+            dptr, nd = c_void_p(doc_starts), int(n_docs)
+        else:
+            docs = np.ascontiguousarray(doc_starts if doc_starts is not None and len(doc_starts) else [0], dtype=np.uint64)
+            dptr, nd = c_void_p(docs.ctypes.data), len(docs)
+        flags = int(flags) | (LAYOUT_BOS if bos_id is not None else 0) | (LAYOUT_EOS if eos_id is not None else 0)
+        return (keep, docs), ptr, n, dptr, nd, Layout(int(row_len), int(pad_id), int(bos_id or 0), int(eos_id or 0), flags)
+
+    def layout_pad(self, ids, n_ids: int | None = None, doc_starts=None, n_docs: int | None = None, row_len: int = 0, pad_id: int = 0,
+                   bos_id: int | None = None, eos_id: int | None = None, trunc_left: bool = False, pad_left: bool = False, flags: int = 0):
+        """One padded row per document (yabpe_layout_pad).  ids: u32 array (staged) or a device address (n_ids required);
+        doc_starts: ascending document starts into the ids, the first one 0, as an array or a device address (n_docs
+        required); None: one document -- encode()'s device results go straight in.  row_len 0: the longest sequence.
+        flags: further YABPE_LAYOUT_* bits as they are.
+        -> (dev_rows_ptr u32[n_docs * row_len], dev_len_ptr u32[n_docs], row_len); the buffers live until the next layout
+        call, layout_free() or close()."""
+        _keep, ptr, n, dptr, nd, lay = self._layout_args(ids, n_ids, doc_starts, n_docs, row_len, pad_id, bos_id, eos_id,
+                                                         flags | (LAYOUT_TRUNC_LEFT if trunc_left else 0) | (LAYOUT_PAD_LEFT if pad_left else 0))
+        dr, dl, rl = c_void_p(), c_void_p(), c_uint32(0)
+        self._chk(lib().yabpe_layout_pad(self._h, ptr, n, dptr, nd, byref(lay), byref(dr), byref(dl), byref(rl)))
+        return dr.value or 0, dl.value or 0, rl.value
+
+    def layout_pad_to_host(self, ids, n_ids: int | None = None, doc_starts=None, n_docs: int | None = None, **kw):
+        """-> (rows u32[n_docs, row_len], lengths u32[n_docs]) copied to the host."""
+        if n_docs is None:
+            n_docs = len(doc_starts) if doc_starts is not None and not isinstance(doc_starts, int) and len(doc_starts) else 1
+        dr, dl, rl = self.layout_pad(ids, n_ids, doc_starts, n_docs, **kw)
+        rows = self.d2h(dr, 4 * n_docs * rl, np.uint32) if n_docs * rl else np.zeros(0, np.uint32)
+        return rows.reshape(n_docs, rl), self.d2h(dl, 4 * n_docs, np.uint32)
+
+    def layout_pack(self, ids, n_ids: int | None = None, doc_starts=None, n_docs: int | None = None, row_len: int = 0, pad_id: int = 0,
+                    bos_id: int | None = None, eos_id: int | None = None, drop_last: bool = False, flags: int = 0):
+        """The documents end to end in rows of row_len (yabpe_layout_pack); arguments as layout_pad takes them.
+        -> (dev_ids_ptr, dev_doc_ptr, dev_pos_ptr: u32[n_rows * row_len] each, n_rows); the buffers live until the next
+        layout call, layout_free() or close()."""
+        _keep, ptr, n, dptr, nd, lay = self._layout_args(ids, n_ids, doc_starts, n_docs, row_len, pad_id, bos_id, eos_id,
+                                                         flags | (LAYOUT_DROP_LAST if drop_last else 0))
+        di, dd, dp, nr = c_void_p(), c_void_p(), c_void_p(), c_uint64(0)
+        self._chk(lib().yabpe_layout_pack(self._h, ptr, n, dptr, nd, byref(lay), byref(di), byref(dd), byref(dp), byref(nr)))
+        return di.value or 0, dd.value or 0, dp.value or 0, nr.value
+
+    def layout_pack_to_host(self, ids, n_ids: int | None = None, doc_starts=None, n_docs: int | None = None, **kw):
+        """-> (ids, doc, pos), each u32[n_rows, row_len], copied to the host."""
+        di, dd, dp, nr = self.layout_pack(ids, n_ids, doc_starts, n_docs, **kw)
+        rl = int(kw.get("row_len", 0))
+        return tuple(self.d2h(p, 4 * nr * rl, np.uint32).reshape(nr, rl) if nr else np.zeros((0, rl), np.uint32) for p in (di, dd, dp))
+
+    def layout_free(self) -> None:
+        self._chk(lib().yabpe_layout_free(self._h))
+
+    def layout_stats(self) -> dict:
+        s = LayoutStats()
+        self._chk(lib().yabpe_layout_stats(self._h, byref(s)))
+        return {f: getattr(s, f) for f, _ in LayoutStats._fields_}
 
     def h2d(self, dev_ptr: int, arr: np.ndarray) -> None:
         arr = np.ascontiguousarray(arr)

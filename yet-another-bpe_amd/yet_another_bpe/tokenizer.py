@@ -6,11 +6,13 @@ clear_cache, cache_info, _encode_word).  encode / encode_batch / decode / decode
 encode_array / encode_batch_device compute the same ids on the GPU (yabpe_encode, include/yabpe.h), and
 decode_array / decode_batch_device the same text (yabpe_decode).  encode_with_offsets / encode_batch_with_offsets also say
 which bytes or characters of the text every id covers; encode_array_with_offsets / encode_batch_device_with_offsets compute
-the same on the GPU (yabpe_encode_spans).
+the same on the GPU (yabpe_encode_spans).  encode_batch_padded / encode_batch_packed lay a batch out in the two fixed shapes a
+model consumes; encode_array_padded / encode_array_packed compute the same on the GPU (yabpe_layout_pad / yabpe_layout_pack).
 """
 from __future__ import annotations
 
 import json
+import operator
 from collections.abc import Sequence
 from functools import lru_cache
 from pathlib import Path
@@ -194,6 +196,83 @@ class BBPETokenizer:
             raise ValueError(f"unit must be 'char' or 'byte', not {unit!r}")
         return [self.encode_with_offsets(t, unit) for t in texts]
 
+    # ------------------------------------------------------------------ fixed-shape batches
+    def _layout_ids(self, pad_id, bos_id, eos_id) -> tuple[int, int | None, int | None, int]:
+        """-> (pad id, bos id or None, eos id or None, n_added); every id given must be an integer in [0, 2^32)"""
+        if pad_id is None:
+            pad_id = self._vocab.get(b"[PAD]", 0)
+        out = []
+        for name, v in (("pad_id", pad_id), ("bos_id", bos_id), ("eos_id", eos_id)):
+            if v is not None:
+                try:
+                    v = operator.index(v)
+                except TypeError:
+                    raise ValueError(f"{name} must be an integer in [0, 2^32), not {v!r}") from None
+                if not 0 <= v < 1 << 32:
+                    raise ValueError(f"{name} must be an integer in [0, 2^32), not {v!r}")
+            out.append(v)
+        return out[0], out[1], out[2], (bos_id is not None) + (eos_id is not None)
+
+    @staticmethod
+    def _row_length(value, name: str, least: int) -> int:
+        try:
+            value = operator.index(value)
+        except TypeError:
+            raise ValueError(f"{name} must be an integer, not {value!r}") from None
+        if value < least:
+            raise ValueError(f"{name} must be at least {least}, not {value}")
+        return value
+
+    def _padded_args(self, max_length, pad_id, bos_id, eos_id, truncation, padding_side):
+        pad, bos, eos, added = self._layout_ids(pad_id, bos_id, eos_id)
+        for name, v in (("truncation", truncation), ("padding_side", padding_side)):
+            if v not in ("left", "right"):
+                raise ValueError(f"{name} must be 'left' or 'right', not {v!r}")
+        if max_length is not None:
+            max_length = self._row_length(max_length, "max_length", added)  # (BOS and EOS always survive the cut)
+        return max_length, pad, bos, eos, added
+
+    def encode_batch_padded(self, texts: Sequence[str], max_length: int | None = None, *, pad_id: int | None = None,
+                            bos_id: int | None = None, eos_id: int | None = None, truncation: str = "right",
+                            padding_side: str = "right") -> tuple[list[list[int]], list[int]]:
+        """One row of L = max_length ids per text (None: the longest sequence, 0 without texts) -> (rows, lengths).
+        seq(d) = [bos_id] + encode(texts[d]) + [eos_id] (each only if given).  A seq longer than L loses content ids from its
+        end (truncation "left": from its start); BOS and EOS always survive.  lengths[d] = the length after the cut; the kept
+        sequence sits at the left end of its row (padding_side "left": at the right end), pad_id (None: the id of b"[PAD]",
+        else 0) everywhere else.  Ids are any integers in [0, 2^32), in the vocab or not."""
+        L, pad, bos, eos, added = self._padded_args(max_length, pad_id, bos_id, eos_id, truncation, padding_side)
+        docs = self.encode_batch(texts)
+        if L is None:
+            L = max((len(ids) + added for ids in docs), default=0)
+        rows, lengths = [], []
+        for ids in docs:
+            keep = min(len(ids), L - added)
+            content = ids[:keep] if truncation == "right" else ids[len(ids) - keep:]
+            seq = ([bos] if bos is not None else []) + content + ([eos] if eos is not None else [])
+            fill = [pad] * (L - len(seq))
+            rows.append(seq + fill if padding_side == "right" else fill + seq)
+            lengths.append(len(seq))
+        return rows, lengths
+
+    def encode_batch_packed(self, texts: Sequence[str], seq_len: int, *, pad_id: int | None = None, bos_id: int | None = None,
+                            eos_id: int | None = None, drop_last: bool = False) -> tuple[list[list[int]], list[list[int]], list[list[int]]]:
+        """All seq(d) = [bos_id] + encode(texts[d]) + [eos_id] end to end in document order, cut into rows of seq_len
+        -> (ids, doc, pos), each ceil(stream / seq_len) rows (drop_last: floor -- the last partial row is dropped).
+        doc[r][c] = the index into texts of the document the slot came from, pos[r][c] = the slot's index inside seq(d) (BOS is
+        0).  The slots of the last row past the end of the stream hold pad_id, document 0xFFFFFFFF and position 0."""
+        pad, bos, eos, _added = self._layout_ids(pad_id, bos_id, eos_id)
+        seq_len = self._row_length(seq_len, "seq_len", 1)
+        stream, doc, pos = [], [], []
+        for d, ids in enumerate(self.encode_batch(texts)):
+            seq = ([bos] if bos is not None else []) + ids + ([eos] if eos is not None else [])
+            stream += seq
+            doc += [d] * len(seq)
+            pos += range(len(seq))
+        n_rows = len(stream) // seq_len if drop_last else -(-len(stream) // seq_len)
+        fill = max(0, n_rows * seq_len - len(stream))
+        cut = lambda flat, filler: [(flat + [filler] * fill)[r * seq_len:(r + 1) * seq_len] for r in range(n_rows)]  # noqa: E731
+        return cut(stream, pad), cut(doc, 0xFFFFFFFF), cut(pos, 0)
+
     # ------------------------------------------------------------------ encode on the GPU (yabpe_encode; same ids as encode)
     def _device(self, model: str = "encode"):
         if self._device_ctx is None:
@@ -252,6 +331,35 @@ class BBPETokenizer:
         ids, off, spans = self.encode_array_with_offsets(texts, unit)
         ids, off, spans = ids.tolist(), off.tolist(), [tuple(p) for p in spans.tolist()]
         return [(ids[off[d]:off[d + 1]], spans[off[d]:off[d + 1]]) for d in range(len(off) - 1)]
+
+    def encode_array_padded(self, texts, max_length: int | None = None, *, pad_id: int | None = None, bos_id: int | None = None,
+                            eos_id: int | None = None, truncation: str = "right",
+                            padding_side: str = "right") -> tuple[np.ndarray, np.ndarray]:
+        """encode_batch_padded(texts, ...), computed on the GPU: yabpe_encode, then yabpe_layout_pad on its device results (the
+        ragged ids never visit the host).  `texts` as encode_array takes them.
+        -> (ids np.uint32[n_docs, L], lengths np.uint32[n_docs])."""
+        L, pad, bos, eos, _added = self._padded_args(max_length, pad_id, bos_id, eos_id, truncation, padding_side)
+        inp = self._device_input(texts)
+        n_docs = 0 if inp is None else len(inp[1])
+        if inp is None or L == 0:  # (no rows, or rows of no slots: with BOS / EOS L is at least 1)
+            return np.zeros((n_docs, L or 0), np.uint32), np.zeros(n_docs, np.uint32)
+        ctx = self._device()
+        di, dd, ni = ctx.encode(np.frombuffer(inp[0], dtype=np.uint8), doc_starts=inp[1])
+        return ctx.layout_pad_to_host(di, ni, dd, n_docs, row_len=L or 0, pad_id=pad, bos_id=bos, eos_id=eos,
+                                      trunc_left=truncation == "left", pad_left=padding_side == "left")
+
+    def encode_array_packed(self, texts, seq_len: int, *, pad_id: int | None = None, bos_id: int | None = None,
+                            eos_id: int | None = None, drop_last: bool = False) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """encode_batch_packed(texts, ...), computed on the GPU: yabpe_encode, then yabpe_layout_pack on its device results.
+        `texts` as encode_array takes them.  -> (ids, doc, pos), each np.uint32[n_rows, seq_len]."""
+        pad, bos, eos, _added = self._layout_ids(pad_id, bos_id, eos_id)
+        seq_len = self._row_length(seq_len, "seq_len", 1)
+        inp = self._device_input(texts)
+        if inp is None:
+            return tuple(np.zeros((0, seq_len), np.uint32) for _ in range(3))
+        ctx = self._device()
+        di, dd, ni = ctx.encode(np.frombuffer(inp[0], dtype=np.uint8), doc_starts=inp[1])
+        return ctx.layout_pack_to_host(di, ni, dd, len(inp[1]), row_len=seq_len, pad_id=pad, bos_id=bos, eos_id=eos, drop_last=drop_last)
 
     # ------------------------------------------------------------------ decode (tokenizer.py:324-349)
     def decode(self, ids: Sequence[int]) -> str:
