@@ -255,8 +255,22 @@ int yabpe_encode(yabpe_ctx *ctx, const uint8_t *text, uint64_t n_bytes, const ui
 int yabpe_encode_spans(yabpe_ctx *ctx, const uint8_t *text, uint64_t n_bytes, const uint64_t *doc_off, uint32_t n_docs,
                        uint32_t flags, uint32_t **out_dev_ids, uint64_t **out_dev_doc_off, uint64_t **out_dev_spans,
                        uint64_t *out_n_ids, int64_t *out_bad_pos);
+/* yabpe_encode with BPE-dropout (BBPETokenizer.encode_dropout; Provilkov et al., 2020): at every merge step of every
+ * pre-token each candidate pair is skipped with probability p = threshold / 2^32, reproducibly from (seed, document index,
+ * position): with rnd(seed, stream, i) of yet_another_bpe/synth.py, Kd = rnd(seed, 0x64, d) for document d, Kw =
+ * rnd(Kd, 0x77, s) for the pre-token at byte s of its document, and the candidate whose left part starts at byte q of the
+ * word is skipped at step t (merges performed so far) iff rnd(Kw, t, q) >> 32 < threshold; the surviving candidate of lowest
+ * rank merges, leftmost on ties; no survivor ends the word.  threshold = min(2^32, int(p * 2^32)): 0 gives yabpe_encode's
+ * ids, 2^32 one id per byte; above 2^32: YABPE_E_INVALID.  Specials draw nothing.  Arguments, errors, ownership and release
+ * are yabpe_encode's, and the results serve wherever its results do (yabpe_decode, yabpe_layout_pad, yabpe_layout_pack).
+ * Every occurrence is merged on its own: yabpe_encode_stats reports n_unique = 0 and pool_ms = 0, n_unique_long counts the
+ * occurrences longer than 64 bytes, and yabpe_encode_checksum has nothing to report after this call.
+ * Option "dropout_pack" (default 1): 0 gives every word of up to 64 bytes a wave of its own (for measurements). */
+int yabpe_encode_dropout(yabpe_ctx *ctx, const uint8_t *text, uint64_t n_bytes, const uint64_t *doc_off, uint32_t n_docs,
+                         uint64_t threshold, uint64_t seed, uint32_t **out_dev_ids, uint64_t **out_dev_doc_off,
+                         uint64_t *out_n_ids, int64_t *out_bad_pos);
 int yabpe_encode_free(yabpe_ctx *ctx);
-/* What the last yabpe_encode / yabpe_encode_spans saw (the span work counts into words_ms and emit_ms), and the device time of its phases (HIP events around each phase's launches). */
+/* What the last yabpe_encode / yabpe_encode_spans / yabpe_encode_dropout saw (the span work counts into words_ms and emit_ms), and the device time of its phases (HIP events around each phase's launches). */
 typedef struct yabpe_encode_stats_t {
     uint64_t n_bytes, n_docs;
     uint64_t n_pretokens;      /* pre-tokens, specials included */

@@ -1,0 +1,51 @@
+"""Build-time guard (no GPU needed: hipcc cross-compiles): the kernels that yabpe_encode_dropout adds use no scratch (private)
+memory and no LDS, and the merge kernel keeps the registers of a full-occupancy wave within reach."""
+from __future__ import annotations
+
+import re
+import shutil
+import subprocess
+from pathlib import Path
+
+import pytest
+
+CSRC = Path(__file__).resolve().parent.parent / "yet-another-bpe_amd" / "csrc"
+HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+# (itanium names: template kernels carry their arguments)
+KERNELS = [r"_ZN2yb\d+k_drop_wordsILb0EE", r"_ZN2yb\d+k_drop_wordsILb1EE", r"_ZN2yb\d+k_drop_long_listE", r"_ZN2yb\d+k_drop_longE",
+           r"_ZN2yb\d+k_drop_long_emitE"]
+
+
+@pytest.fixture(scope="module")
+def resources():
+    if not Path(HIPCC).exists():
+        pytest.skip("no hipcc")
+    flags = re.search(r"^CXXFLAGS \?= (.*)$", (CSRC / "Makefile").read_text(), re.M).group(1).split()
+    out = subprocess.run([HIPCC, "--offload-arch=gfx950", *flags, "-Rpass-analysis=kernel-resource-usage", "-c", "-o", "/dev/null", "yabpe.hip"],
+                         cwd=CSRC, capture_output=True, text=True, timeout=900)
+    assert out.returncode == 0, out.stderr[-2000:]
+    res, cur = {}, None
+    for line in out.stderr.splitlines():
+        m = re.search(r"Function Name: (\S+)", line)
+        if m:
+            cur = res.setdefault(m.group(1), {})
+            continue
+        m = re.search(r"remark:\s+(VGPRs|ScratchSize \[bytes/lane\]|Occupancy \[waves/SIMD\]|LDS Size \[bytes/block\]): (\d+)", line)
+        if m and cur is not None:
+            cur[m.group(1).split(" ")[0]] = int(m.group(2))
+    return res
+
+
+def test_no_dropout_kernel_uses_scratch_memory_or_lds(resources):
+    for k in KERNELS:
+        found = {name: r for name, r in resources.items() if re.match(k, name)}
+        assert len(found) == 1, (k, sorted(found))
+        for name, r in found.items():
+            assert r["ScratchSize"] == 0 and r["LDS"] == 0, (name, r)
+
+
+def test_merge_kernel_keeps_its_occupancy(resources):
+    """k_drop_words hides its table lookups behind other waves: at most 72 VGPRs (7 waves per SIMD of the 512 a lane has)."""
+    for k in KERNELS[:2]:
+        (r,) = [r for name, r in resources.items() if re.match(k, name)]
+        assert r["VGPRs"] <= 72 and r["Occupancy"] >= 7, (k, r)

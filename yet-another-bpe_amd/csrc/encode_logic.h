@@ -183,6 +183,75 @@ YB_HD uint32_t enc_merge_heap(const uint8_t *w, uint32_t L, const EncTable &t, u
     return k;
 }
 
+// ---------------------------------------------------------------- BPE-dropout (BBPETokenizer.encode_dropout)
+// rnd(seed, stream, i) of yet_another_bpe/synth.py (synth_rnd of yabpe_aux_kernels.h: the same mix), u64 with wraparound.
+// Document key Kd = rnd(seed, 0x64, doc); word key Kw = rnd(Kd, 0x77, s), s = the pre-token's byte offset in its document.
+// At merge step t (merges performed so far) the candidate whose left part starts at byte q of the word is dropped iff
+// rnd(Kw, t, q) >> 32 < T, T = min(2^32, int(p * 2^32)); the surviving candidate of lowest rank, leftmost on ties, merges.
+constexpr unsigned long long ENC_RND_G = 0x9E3779B97F4A7C15ull, ENC_RND_S = 0xD1B54A32D192ED03ull;
+constexpr unsigned long long ENC_DROP_DOC = 0x64, ENC_DROP_WORD = 0x77;
+constexpr unsigned long long ENC_DROP_ALL = 1ull << 32; // T of p = 1
+
+YB_HD unsigned long long enc_rnd(unsigned long long seed, unsigned long long stream, unsigned long long i) {
+    return enc_mix(seed + ENC_RND_G * (i + 1) + ENC_RND_S * stream);
+}
+YB_HD unsigned long long enc_drop_doc_key(unsigned long long seed, unsigned long long doc) { return enc_rnd(seed, ENC_DROP_DOC, doc); }
+YB_HD unsigned long long enc_drop_word_key(unsigned long long kd, unsigned long long s) { return enc_rnd(kd, ENC_DROP_WORD, s); }
+// The draw in two halves, so that a lane keeps what does not change from step to step: lane = enc_drop_lane(Kw, q) once,
+// then enc_dropped(lane + ENC_RND_S * t, T) at step t.
+YB_HD unsigned long long enc_drop_lane(unsigned long long kw, uint32_t q) { return kw + ENC_RND_G * ((unsigned long long)q + 1); }
+YB_HD bool enc_dropped(unsigned long long lane_t, unsigned long long T) { return (enc_mix(lane_t) >> 32) < T; }
+YB_HD bool enc_drop_draw(unsigned long long kw, uint32_t t, uint32_t q, unsigned long long T) {
+    return enc_dropped(enc_drop_lane(kw, q) + ENC_RND_S * t, T);
+}
+
+// enc_merge_heap with dropout: the draws are evaluated lazily.  The smallest current entry is popped; dropped at (t, q), it
+// is set aside and the next one popped, so the first entry that survives is the smallest candidate not dropped at step t.
+// After its merge the entries set aside go back to the heap (their draws at t + 1 are new ones); when the heap runs empty
+// without a survivor the word is finished.  Expected pops per step 1 / (1 - p); T = 2^32 drains the heap once.
+// The entries set aside live at the top end of `heap`, growing down: heap and set-aside together only ever hold entries
+// that were pushed and not yet discarded, at most 3 (L - 1).  Scratch and result as enc_merge_heap.
+YB_HD uint32_t enc_merge_heap_dropout(const uint8_t *w, uint32_t L, const EncTable &t, unsigned long long kw, unsigned long long T,
+                                      uint32_t *tok, uint32_t *nxt, uint32_t *prv, unsigned long long *heap) {
+    for (uint32_t p = 0; p < L; ++p) {
+        tok[p] = w[p];
+        nxt[p] = p + 1 < L ? p + 1 : ENC_NONE;
+        prv[p] = p ? p - 1 : ENC_NONE;
+    }
+    uint32_t hn = 0, r = 0, res = 0, step = 0, aside = 3 * L; // set aside: heap[aside .. 3 L)
+    for (uint32_t p = 0; p + 1 < L; ++p)
+        if (enc_lookup(t, tok[p], tok[p + 1], &r, &res)) enc_heap_push(heap, hn, ((unsigned long long)r << 32) | p);
+    while (hn) {
+        const unsigned long long e = enc_heap_pop(heap, hn);
+        const uint32_t p = (uint32_t)e, er = (uint32_t)(e >> 32);
+        if (tok[p] == ENC_NONE) continue;
+        const uint32_t q = nxt[p];
+        if (q == ENC_NONE) continue;
+        if (!enc_lookup(t, tok[p], tok[q], &r, &res) || r != er) continue;
+        if (enc_drop_draw(kw, step, p, T)) {
+            heap[--aside] = e;
+            continue;
+        }
+        tok[p] = res;
+        tok[q] = ENC_NONE;
+        nxt[p] = nxt[q];
+        if (nxt[q] != ENC_NONE) prv[nxt[q]] = p;
+        ++step;
+        while (aside < 3 * L) enc_heap_push(heap, hn, heap[aside++]); // (hn < aside here: the push never overwrites what it reads)
+        if (nxt[p] != ENC_NONE && enc_lookup(t, tok[p], tok[nxt[p]], &r, &res)) enc_heap_push(heap, hn, ((unsigned long long)r << 32) | p);
+        const uint32_t a = prv[p];
+        if (a != ENC_NONE && enc_lookup(t, tok[a], tok[p], &r, &res)) enc_heap_push(heap, hn, ((unsigned long long)r << 32) | a);
+    }
+    uint32_t k = 0, p = L ? 0 : ENC_NONE;
+    while (p != ENC_NONE) {
+        const uint32_t np = nxt[p];
+        nxt[k] = p;
+        tok[k++] = tok[p];
+        p = np;
+    }
+    return k;
+}
+
 // The checksum hash of a word whose tokens start at starts[0..count) (byte offsets into w, ascending).
 YB_HD unsigned long long enc_word_hash(const uint8_t *w, uint32_t L, const uint32_t *starts, uint32_t count) {
     unsigned long long h = enc_fnv_init();

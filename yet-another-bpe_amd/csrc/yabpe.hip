@@ -27,6 +27,7 @@
 #include "yabpe_devmem.h"
 #include "yabpe_pretok_kernels.h"
 #include "yabpe_encode_kernels.h"
+#include "yabpe_dropout_kernels.h"
 #include "yabpe_decode_kernels.h"
 #include "yabpe_layout_kernels.h"
 #include "yabpe_replay_kernels.h"
@@ -2476,6 +2477,57 @@ int yabpe_encode_free(yabpe_ctx *c) {
     return YABPE_OK;
 }
 
+// The phases every encoder shares, on staged inputs (n > 0): the split (document marks, the special split, classes / UTF-8 /
+// pre-token starts; events 0 .. 1) and the pre-token offsets (.. event 2).  Malformed UTF-8: YABPE_E_UTF8, *out_bad_pos.
+struct EncFront {
+    uint8_t *meta = nullptr, *flags = nullptr, *sflag = nullptr;  // (sflag: nullptr without specials)
+    unsigned long long *off = nullptr, n_pre = 0;
+};
+
+static int encode_front(yabpe_ctx *c, Scratch &S, const uint8_t *d_text, unsigned long long n, const unsigned long long *d_docs, uint32_t n_docs,
+                        int64_t *out_bad_pos, EncFront *F) {
+    hipStream_t s = c->stream;
+    const uint32_t grid = (uint32_t)std::min<unsigned long long>((n + BLOCK - 1) / BLOCK, 1u << 20);
+    // ---- split: document marks, the special split, classes / UTF-8 / pre-token starts
+    uint8_t *meta = nullptr, *flags = nullptr, *sflag = nullptr;
+    unsigned long long *err = nullptr;
+    HIPCHK(c, S.get(&meta, n));
+    HIPCHK(c, S.get(&flags, n + 8));
+    HIPCHK(c, S.get(&err, 1));
+    if (c->enc_n_special) HIPCHK(c, S.get(&sflag, n));
+    HIPCHK(c, hipEventRecord(c->enc_ev[0], s));
+    HIPCHK(c, hipMemsetAsync(meta, 0, n, s));
+    HIPCHK(c, hipMemsetAsync(err, 0xff, 8, s));
+    hipLaunchKernelGGL(k_pt_mark_chunks, dim3((n_docs + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, s, meta, d_docs, n_docs, n);
+    const PtSpecials sp{c->enc_sp_bytes, c->enc_sp_off, c->enc_n_special, c->enc_sp_max_len};
+    if (sflag) {
+        HIPCHK(c, hipMemsetAsync(sflag, 0, n, s));
+        hipLaunchKernelGGL(k_enc_special, dim3(grid), dim3(BLOCK), 0, s, d_text, meta, n, sp, sflag);
+        hipLaunchKernelGGL(k_enc_segments, dim3(grid), dim3(BLOCK), 0, s, sflag, n, meta);
+    }
+    PretokParams P{d_text, meta, flags, n, c->pt_cls, err, PtSpecials{nullptr, nullptr, 0, 0}};
+    const uint32_t wgrid = (uint32_t)std::min<unsigned long long>((n + PT_WIN - 1) / PT_WIN, 1u << 20);
+    hipLaunchKernelGGL(k_pt_fused, dim3(wgrid), dim3(BLOCK), 0, s, P);
+    if (sflag) hipLaunchKernelGGL(k_enc_clear, dim3(grid), dim3(BLOCK), 0, s, sflag, n, flags);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipEventRecord(c->enc_ev[1], s));
+    unsigned long long h_err = 0;
+    HIPCHK(c, hipMemcpyAsync(&h_err, err, 8, hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipStreamSynchronize(s));
+    if (h_err != ~0ull) {
+        *out_bad_pos = (int64_t)h_err;
+        return fail(c, YABPE_E_UTF8, "invalid UTF-8 at byte %llu", h_err);
+    }
+    // ---- pre-token offsets
+    unsigned long long *off = nullptr, n_pre = 0;
+    const int pr = pt_offsets(s, S, flags, n, 0xFFFFFFFEull, &off, &n_pre);
+    if (pr == -2) return fail(c, YABPE_E_CAPACITY, "%llu pre-tokens in one call: at most 2^32 - 2", n_pre);
+    if (pr != 0) return fail(c, YABPE_E_HIP, "pre-token offsets failed: %s", hipGetErrorString(hipGetLastError()));
+    HIPCHK(c, hipEventRecord(c->enc_ev[2], s));
+    F->meta = meta; F->flags = flags; F->sflag = sflag; F->off = off; F->n_pre = n_pre;
+    return YABPE_OK;
+}
+
 // yabpe_encode (out_dev_spans == nullptr) and yabpe_encode_spans: one body.
 static int encode_run(yabpe_ctx *c, const uint8_t *text, uint64_t n_bytes, const uint64_t *doc_off, uint32_t n_docs, uint32_t span_flags,
                       uint32_t **out_dev_ids, uint64_t **out_dev_doc_off, uint64_t **out_dev_spans, uint64_t *out_n_ids, int64_t *out_bad_pos) {
@@ -2520,43 +2572,11 @@ static int encode_run(yabpe_ctx *c, const uint8_t *text, uint64_t n_bytes, const
         *out_dev_doc_off = (uint64_t *)c->enc_doc;
         return YABPE_OK;
     }
-    const uint32_t grid = (uint32_t)std::min<unsigned long long>((n + BLOCK - 1) / BLOCK, 1u << 20);
-    // ---- split: document marks, the special split, classes / UTF-8 / pre-token starts
-    uint8_t *meta = nullptr, *flags = nullptr, *sflag = nullptr;
-    unsigned long long *err = nullptr;
-    HIPCHK(c, S.get(&meta, n));
-    HIPCHK(c, S.get(&flags, n + 8));
-    HIPCHK(c, S.get(&err, 1));
-    if (c->enc_n_special) HIPCHK(c, S.get(&sflag, n));
-    HIPCHK(c, hipEventRecord(c->enc_ev[0], s));
-    HIPCHK(c, hipMemsetAsync(meta, 0, n, s));
-    HIPCHK(c, hipMemsetAsync(err, 0xff, 8, s));
-    hipLaunchKernelGGL(k_pt_mark_chunks, dim3((n_docs + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, s, meta, d_docs, n_docs, n);
-    const PtSpecials sp{c->enc_sp_bytes, c->enc_sp_off, c->enc_n_special, c->enc_sp_max_len};
-    if (sflag) {
-        HIPCHK(c, hipMemsetAsync(sflag, 0, n, s));
-        hipLaunchKernelGGL(k_enc_special, dim3(grid), dim3(BLOCK), 0, s, d_text, meta, n, sp, sflag);
-        hipLaunchKernelGGL(k_enc_segments, dim3(grid), dim3(BLOCK), 0, s, sflag, n, meta);
-    }
-    PretokParams P{d_text, meta, flags, n, c->pt_cls, err, PtSpecials{nullptr, nullptr, 0, 0}};
-    const uint32_t wgrid = (uint32_t)std::min<unsigned long long>((n + PT_WIN - 1) / PT_WIN, 1u << 20);
-    hipLaunchKernelGGL(k_pt_fused, dim3(wgrid), dim3(BLOCK), 0, s, P);
-    if (sflag) hipLaunchKernelGGL(k_enc_clear, dim3(grid), dim3(BLOCK), 0, s, sflag, n, flags);
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipEventRecord(c->enc_ev[1], s));
-    unsigned long long h_err = 0;
-    HIPCHK(c, hipMemcpyAsync(&h_err, err, 8, hipMemcpyDeviceToHost, s));
-    HIPCHK(c, hipStreamSynchronize(s));
-    if (h_err != ~0ull) {
-        *out_bad_pos = (int64_t)h_err;
-        return fail(c, YABPE_E_UTF8, "invalid UTF-8 at byte %llu", h_err);
-    }
-    // ---- pre-token offsets
-    unsigned long long *off = nullptr, n_pre = 0;
-    const int pr = pt_offsets(s, S, flags, n, 0xFFFFFFFEull, &off, &n_pre);
-    if (pr == -2) return fail(c, YABPE_E_CAPACITY, "%llu pre-tokens in one call: at most 2^32 - 2", n_pre);
-    if (pr != 0) return fail(c, YABPE_E_HIP, "pre-token offsets failed: %s", hipGetErrorString(hipGetLastError()));
-    HIPCHK(c, hipEventRecord(c->enc_ev[2], s));
+    EncFront F;
+    TRY(encode_front(c, S, d_text, n, d_docs, n_docs, out_bad_pos, &F));
+    uint8_t *const sflag = F.sflag;
+    unsigned long long *const off = F.off;
+    const unsigned long long n_pre = F.n_pre;
     // ---- pooling: each pre-token's representative, the list of unique words
     PoolOut pw{};
     if (pool_words(s, S, d_text, off, nullptr, n_pre, &pw) != 0)
@@ -2680,6 +2700,124 @@ int yabpe_encode_spans(yabpe_ctx *c, const uint8_t *text, uint64_t n_bytes, cons
                        uint32_t **out_dev_ids, uint64_t **out_dev_doc_off, uint64_t **out_dev_spans, uint64_t *out_n_ids, int64_t *out_bad_pos) {
     if (!c || !out_dev_ids || !out_dev_doc_off || !out_dev_spans || !out_n_ids || !out_bad_pos) return YABPE_E_INVALID;
     return encode_run(c, text, n_bytes, doc_off, n_docs, flags, out_dev_ids, out_dev_doc_off, out_dev_spans, out_n_ids, out_bad_pos);
+}
+
+// BBPETokenizer.encode_dropout on the device (yabpe_dropout_kernels.h): the shared front, then per occurrence -- nothing is
+// pooled.  The merge runs twice (count, scan, emit in place): no staging of 4 bytes per text byte.
+int yabpe_encode_dropout(yabpe_ctx *c, const uint8_t *text, uint64_t n_bytes, const uint64_t *doc_off, uint32_t n_docs, uint64_t threshold,
+                         uint64_t seed, uint32_t **out_dev_ids, uint64_t **out_dev_doc_off, uint64_t *out_n_ids, int64_t *out_bad_pos) {
+    if (!c || !out_dev_ids || !out_dev_doc_off || !out_n_ids || !out_bad_pos) return YABPE_E_INVALID;
+    HIPCHK(c, hipSetDevice(c->device));
+    *out_dev_ids = nullptr; *out_dev_doc_off = nullptr; *out_n_ids = 0; *out_bad_pos = -1;
+    if (threshold > ENC_DROP_ALL) return fail(c, YABPE_E_INVALID, "threshold %llu: at most 2^32 (p = 1)", (unsigned long long)threshold);
+    if (!c->have_enc_model) return fail(c, YABPE_E_INVALID, "no model: call yabpe_encode_set_model first");
+    if (n_bytes && !text) return fail(c, YABPE_E_INVALID, "text is NULL");
+    TRY(check_starts(c, doc_off, n_docs, n_bytes, "text"));
+    yabpe_encode_free(c);
+    c->enc_done = false;  // (the checksum fold is the pooled encoder's: none here)
+    c->enc_stats = yabpe_encode_stats_t{};
+    c->enc_stats.n_bytes = n_bytes;
+    c->enc_stats.n_docs = n_docs;
+    TRY(class_table(c));
+    for (auto &e : c->enc_ev)
+        if (!e) HIPCHK(c, hipEventCreate(&e));
+    hipStream_t s = c->stream;
+    const unsigned long long n = n_bytes;
+    Scratch S(c->device, c->rank);
+    const uint8_t *d_text = nullptr;
+    TRY(to_device(c, S, text, n, 1, &d_text));
+    unsigned long long *d_docs = nullptr;
+    HIPCHK(c, S.get(&d_docs, n_docs));
+    HIPCHK(c, hipMemcpy(d_docs, doc_off, (size_t)n_docs * 8, hipMemcpyHostToDevice));
+    TRY(dmalloc(c, &c->enc_doc, (uint64_t)n_docs + 1));
+    unsigned long long *doc_ids = (unsigned long long *)c->enc_doc;
+    if (n == 0) { // every document is empty
+        HIPCHK(c, hipMemsetAsync(doc_ids, 0, ((size_t)n_docs + 1) * 8, s));
+        TRY(dmalloc(c, &c->enc_ids, 1));
+        HIPCHK(c, hipStreamSynchronize(s));
+        *out_dev_ids = c->enc_ids;
+        *out_dev_doc_off = (uint64_t *)c->enc_doc;
+        return YABPE_OK;
+    }
+    EncFront F;
+    TRY(encode_front(c, S, d_text, n, d_docs, n_docs, out_bad_pos, &F));
+    S.release(F.meta);  // (dead from here on: the peak is the front's)
+    S.release(F.flags);
+    unsigned long long *const off = F.off;
+    const unsigned long long n_pre = F.n_pre;
+    const EncTable tab{c->enc_keys, c->enc_vals, c->enc_mask};
+    const uint32_t pgrid = (uint32_t)((n_pre + 255) / 256);
+    // ---- long words: their list, the walk's scratch, the walk (once: its tokens stay in the scratch for the emit)
+    const unsigned long long lcap = n / (ENC_SHORT + 1) + 1;
+    uint32_t *cnt = nullptr, *llist = nullptr;
+    unsigned long long *id_off = nullptr, *lbase = nullptr, *ctr = nullptr;
+    HIPCHK(c, S.get(&cnt, n_pre));
+    HIPCHK(c, S.get(&id_off, n_pre + 1));
+    HIPCHK(c, S.get(&llist, lcap));
+    HIPCHK(c, S.get(&lbase, lcap));
+    HIPCHK(c, S.get(&ctr, 3));  // long words, their bytes; specials met
+    HIPCHK(c, hipMemsetAsync(ctr, 0, 24, s));
+    hipLaunchKernelGGL(k_drop_long_list, dim3(pgrid), dim3(256), 0, s, off, n_pre, F.sflag, lcap, llist, lbase, ctr);
+    HIPCHK(c, hipGetLastError());
+    unsigned long long h_ctr[3] = {0, 0, 0};
+    HIPCHK(c, hipMemcpyAsync(h_ctr, ctr, 16, hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipStreamSynchronize(s));
+    const unsigned long long n_long = std::min(h_ctr[0], lcap), lbytes = h_ctr[1];
+    uint32_t *ltok = nullptr, *lnxt = nullptr, *lprv = nullptr;
+    unsigned long long *lheap = nullptr;
+    HIPCHK(c, S.get(&ltok, lbytes));
+    HIPCHK(c, S.get(&lnxt, lbytes));
+    HIPCHK(c, S.get(&lprv, lbytes));
+    HIPCHK(c, S.get(&lheap, 3 * lbytes));
+    HIPCHK(c, hipEventRecord(c->enc_ev[4], s));  // (the words phase: the long walks and the count pass)
+    const uint32_t lgrid = (uint32_t)((n_long + 63) / 64);
+    if (n_long) {
+        const DropLongParams LP{d_text, off, d_docs, n_docs, llist, lbase, n_long, tab, seed, threshold, cnt, ltok, lnxt, lprv, lheap};
+        hipLaunchKernelGGL(k_drop_long, dim3(lgrid), dim3(64), 0, s, LP);
+    }
+    DropParams W{d_text, off, n_pre, d_docs, n_docs, optv(c, "dropout_pack", 1) ? DROP_PACK : 0u, F.sflag, tab, c->enc_out_id, c->enc_sp_id,
+                 c->enc_sp_has, seed, threshold, cnt, nullptr, nullptr, ctr + 2};
+    const uint32_t wg = (uint32_t)std::max<unsigned long long>(1, std::min<unsigned long long>((n_pre + 64ull * WPB - 1) / (64ull * WPB), (unsigned long long)c->n_cu * 8));
+    hipLaunchKernelGGL(k_drop_words<false>, dim3(wg), dim3(BLOCK), 0, s, W);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipEventRecord(c->enc_ev[5], s));
+    // ---- emission: id offsets, the merges again with the ids written in place, the per-document offsets
+    HIPCHK(c, hipEventRecord(c->enc_ev[6], s));
+    if (exclusive_scan<uint32_t>(s, cnt, n_pre, id_off, n_pre + 1) != 0) return fail(c, YABPE_E_HIP, "scan of the id counts failed");
+    unsigned long long n_ids = 0;
+    HIPCHK(c, hipMemcpyAsync(&n_ids, id_off + n_pre, 8, hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipMemcpyAsync(&h_ctr[2], ctr + 2, 8, hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipStreamSynchronize(s));
+    TRY(dmalloc(c, &c->enc_ids, n_ids));
+    W.id_off = id_off;
+    W.ids = c->enc_ids;
+    hipLaunchKernelGGL(k_drop_words<true>, dim3(wg), dim3(BLOCK), 0, s, W);
+    if (n_long) hipLaunchKernelGGL(k_drop_long_emit, dim3(lgrid), dim3(64), 0, s, llist, lbase, n_long, ltok, id_off, c->enc_out_id, c->enc_ids);
+    hipLaunchKernelGGL(k_enc_docs, dim3((n_docs + 1 + 255) / 256), dim3(256), 0, s, d_docs, n_docs, n, off, n_pre, id_off, doc_ids);
+    (void)hipEventRecord(c->enc_ev[7], s);
+    const hipError_t le = hipGetLastError();
+    const hipError_t se = hipStreamSynchronize(s);
+    if (le != hipSuccess || se != hipSuccess) return fail(c, YABPE_E_HIP, "encoder kernels failed: %s", hipGetErrorString(le != hipSuccess ? le : se));
+    float ms[5] = {0, 0, 0, 0, 0};
+    (void)hipEventElapsedTime(&ms[0], c->enc_ev[0], c->enc_ev[1]);
+    (void)hipEventElapsedTime(&ms[1], c->enc_ev[1], c->enc_ev[2]);
+    (void)hipEventElapsedTime(&ms[2], c->enc_ev[4], c->enc_ev[5]);
+    (void)hipEventElapsedTime(&ms[3], c->enc_ev[6], c->enc_ev[7]);
+    (void)hipEventElapsedTime(&ms[4], c->enc_ev[0], c->enc_ev[7]);
+    auto &st = c->enc_stats;  // (n_unique and pool_ms stay 0: nothing is pooled; n_unique_long counts occurrences here)
+    st.n_pretokens = n_pre;
+    st.n_unique_long = n_long;
+    st.n_specials = h_ctr[2];
+    st.n_ids = n_ids;
+    st.split_ms = ms[0];
+    st.pretok_ms = ms[1];
+    st.words_ms = ms[2];
+    st.emit_ms = ms[3];
+    st.total_ms = ms[4];
+    *out_dev_ids = c->enc_ids;
+    *out_dev_doc_off = (uint64_t *)c->enc_doc;
+    *out_n_ids = n_ids;
+    return YABPE_OK;
 }
 
 int yabpe_encode_stats(yabpe_ctx *c, yabpe_encode_stats_t *out) {

@@ -86,7 +86,7 @@ SYMBOLS = [
     "yabpe_iter_log", "yabpe_event_log", "yabpe_latency_probe", "yabpe_verify_table", "yabpe_stream_checksum", "yabpe_synth_generate", "yabpe_synth_generate_lex", "yabpe_synth_free",
     "yabpe_memcpy_d2h", "yabpe_memcpy_h2d", "yabpe_pretokenize", "yabpe_pretokenize_free",
     "yabpe_comm_unique_id", "yabpe_comm_init", "yabpe_comm_init_custom", "yabpe_comm_enable_p2p",
-    "yabpe_encode_set_model", "yabpe_encode", "yabpe_encode_spans", "yabpe_encode_free", "yabpe_encode_stats", "yabpe_encode_checksum",
+    "yabpe_encode_set_model", "yabpe_encode", "yabpe_encode_spans", "yabpe_encode_dropout", "yabpe_encode_free", "yabpe_encode_stats", "yabpe_encode_checksum",
     "yabpe_decode_set_model", "yabpe_decode", "yabpe_decode_free", "yabpe_decode_stats",
     "yabpe_load_words_resumed", "yabpe_resume_stats",
     "yabpe_layout_pad", "yabpe_layout_pack", "yabpe_layout_free", "yabpe_layout_stats",
@@ -141,6 +141,8 @@ def lib() -> ctypes.CDLL:
                                    POINTER(c_uint64), POINTER(ctypes.c_int64)]
         L.yabpe_encode_spans.argtypes = [c_void_p, c_void_p, c_uint64, c_void_p, c_uint32, c_uint32, POINTER(c_void_p), POINTER(c_void_p),
                                          POINTER(c_void_p), POINTER(c_uint64), POINTER(ctypes.c_int64)]
+        L.yabpe_encode_dropout.argtypes = [c_void_p, c_void_p, c_uint64, c_void_p, c_uint32, c_uint64, c_uint64, POINTER(c_void_p),
+                                           POINTER(c_void_p), POINTER(c_uint64), POINTER(ctypes.c_int64)]
         L.yabpe_encode_free.argtypes = [c_void_p]
         L.yabpe_encode_stats.argtypes = [c_void_p, POINTER(EncodeStats)]
         L.yabpe_encode_checksum.argtypes = [c_void_p, POINTER(c_uint64), POINTER(c_uint64), POINTER(c_uint64)]
@@ -381,8 +383,9 @@ class Context:
                                                a["mb"].ctypes.data, a["mo"].ctypes.data, len(a["mo"]) // 2, a["sb"].ctypes.data,
                                                a["so"].ctypes.data, len(a["so"]) - 1, int(unk_id)))
 
-    def _encode_call(self, text, n_bytes, doc_starts, flags):
-        """yabpe_encode (flags None) or yabpe_encode_spans -> (dev ids, dev doc_off, dev spans or None, n_ids)"""
+    def _encode_call(self, text, n_bytes, doc_starts, flags, dropout=None):
+        """yabpe_encode (flags None), yabpe_encode_spans or yabpe_encode_dropout (dropout = (threshold, seed))
+        -> (dev ids, dev doc_off, dev spans or None, n_ids)"""
         keep = None
         if isinstance(text, int):
             ptr, n = c_void_p(text), int(n_bytes)
@@ -391,7 +394,10 @@ class Context:
             ptr, n = c_void_p(keep.ctypes.data if keep.size else 0), int(keep.size)
         docs = np.ascontiguousarray(doc_starts if doc_starts is not None and len(doc_starts) else [0], dtype=np.uint64)
         di, dd, ds, ni, bad = c_void_p(), c_void_p(), c_void_p(), c_uint64(0), ctypes.c_int64(-1)
-        if flags is None:
+        if dropout is not None:
+            rc = lib().yabpe_encode_dropout(self._h, ptr, n, docs.ctypes.data, len(docs), int(dropout[0]), int(dropout[1]), byref(di), byref(dd),
+                                            byref(ni), byref(bad))
+        elif flags is None:
             rc = lib().yabpe_encode(self._h, ptr, n, docs.ctypes.data, len(docs), byref(di), byref(dd), byref(ni), byref(bad))
         else:
             rc = lib().yabpe_encode_spans(self._h, ptr, n, docs.ctypes.data, len(docs), int(flags), byref(di), byref(dd), byref(ds), byref(ni),
@@ -427,6 +433,19 @@ class Context:
         ids = self.d2h(di, 4 * ni, np.uint32) if ni else np.zeros(0, np.uint32)
         spans = self.d2h(ds, 16 * ni, np.uint64).reshape(-1, 2) if ni else np.zeros((0, 2), np.uint64)
         return ids, self.d2h(dd, 8 * (n_docs + 1), np.uint64), spans
+
+    def encode_dropout(self, text, threshold: int, seed: int = 0, n_bytes: int | None = None, doc_starts=None):
+        """encode() with BPE-dropout (yabpe_encode_dropout): threshold = min(2^32, int(p * 2^32)), seed in [0, 2^64).
+        -> (dev_ids_ptr u32, dev_doc_off_ptr u64[n_docs + 1], n_ids), owned and released as encode()'s."""
+        di, dd, _ds, ni = self._encode_call(text, n_bytes, doc_starts, None, dropout=(threshold, seed))
+        return di, dd, ni
+
+    def encode_dropout_to_host(self, text, threshold: int, seed: int = 0, n_bytes: int | None = None, doc_starts=None):
+        """-> (ids u32[n_ids], doc_off u64[n_docs + 1]) copied to the host."""
+        n_docs = len(doc_starts) if doc_starts is not None and len(doc_starts) else 1
+        di, dd, ni = self.encode_dropout(text, threshold, seed, n_bytes, doc_starts)
+        ids = self.d2h(di, 4 * ni, np.uint32) if ni else np.zeros(0, np.uint32)
+        return ids, self.d2h(dd, 8 * (n_docs + 1), np.uint64)
 
     def encode_free(self) -> None:
         self._chk(lib().yabpe_encode_free(self._h))

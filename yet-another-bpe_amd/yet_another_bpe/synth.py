@@ -38,6 +38,17 @@ def rnd(seed: int, stream: int, i: np.ndarray) -> np.ndarray:
         return mix(np.uint64(seed) + _G * (i + np.uint64(1)) + _S * np.uint64(stream))
 
 
+def rnd_int(seed: int, stream: int, i: int) -> int:
+    """rnd() for one draw on Python integers (u64 with wraparound): the same value, without the array round trip."""
+    m = (1 << 64) - 1
+    x = (seed + int(_G) * (i + 1) + int(_S) * stream) & m
+    x ^= x >> 30
+    x = (x * int(_M1)) & m
+    x ^= x >> 27
+    x = (x * int(_M2)) & m
+    return x ^ (x >> 31)
+
+
 @dataclass(frozen=True)
 class SynthSpec:
     target_bytes: int

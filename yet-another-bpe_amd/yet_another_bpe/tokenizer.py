@@ -8,10 +8,14 @@ decode_array / decode_batch_device the same text (yabpe_decode).  encode_with_of
 which bytes or characters of the text every id covers; encode_array_with_offsets / encode_batch_device_with_offsets compute
 the same on the GPU (yabpe_encode_spans).  encode_batch_padded / encode_batch_packed lay a batch out in the two fixed shapes a
 model consumes; encode_array_padded / encode_array_packed compute the same on the GPU (yabpe_layout_pad / yabpe_layout_pack).
+encode_dropout / encode_batch_dropout segment with BPE-dropout, reproducibly from (seed, document, position);
+encode_array_dropout / encode_batch_device_dropout compute the same ids on the GPU (yabpe_encode_dropout), and the fixed-shape
+forms take dropout= and seed=.
 """
 from __future__ import annotations
 
 import json
+import numbers
 import operator
 from collections.abc import Sequence
 from functools import lru_cache
@@ -19,6 +23,8 @@ from pathlib import Path
 
 import numpy as np
 import regex
+
+from .synth import rnd_int
 
 _GPT2_SPLIT = r"""'(?:[sdmt]|ll|ve|re)| ?\p{L}+| ?\p{N}+| ?[^\s\p{L}\p{N}]+|\s+(?!\S)|\s+"""
 _WORD_CACHE = 8192
@@ -140,6 +146,87 @@ class BBPETokenizer:
     def encode_batch(self, texts: Sequence[str]) -> list[list[int]]:
         return [self.encode(t) for t in texts]
 
+    # ------------------------------------------------------------------ encode with BPE-dropout
+    @staticmethod
+    def _dropout_threshold(p) -> int:
+        """T = min(2^32, int(p * 2^32)): a draw (32 bits) below T drops its candidate.  p: a real number in [0, 1]."""
+        if not isinstance(p, numbers.Real) or not 0.0 <= float(p) <= 1.0:  # (NaN compares false)
+            raise ValueError(f"p must be a real number in [0, 1], not {p!r}")
+        return min(1 << 32, int(float(p) * 4294967296.0))
+
+    @staticmethod
+    def _u64(value, name: str) -> int:
+        try:
+            value = operator.index(value)
+        except TypeError:
+            raise ValueError(f"{name} must be an integer in [0, 2^64), not {value!r}") from None
+        if not 0 <= value < 1 << 64:
+            raise ValueError(f"{name} must be an integer in [0, 2^64), not {value!r}")
+        return value
+
+    def _word_parts_dropout(self, data: bytes, kw: int, T: int) -> list[bytes]:
+        """_word_parts where, at step t (merges performed so far), the candidate whose left part starts at byte q is dropped
+        iff rnd(kw, t, q) >> 32 < T; the surviving candidate of lowest rank merges, leftmost on ties; none: finished."""
+        parts = [bytes([b]) for b in data]
+        starts = list(range(len(data)))
+        rank = self._rank
+        t = 0
+        while len(parts) > 1:
+            best_rank, best_i = None, -1
+            for i in range(len(parts) - 1):
+                r = rank.get((parts[i], parts[i + 1]))
+                if r is None or (rnd_int(kw, t, starts[i]) >> 32) < T:
+                    continue
+                if best_rank is None or r < best_rank:
+                    best_rank, best_i = r, i
+            if best_rank is None:
+                break
+            parts[best_i:best_i + 2] = [parts[best_i] + parts[best_i + 1]]
+            del starts[best_i + 1]
+            t += 1
+        return parts
+
+    def encode_dropout(self, text: str, p: float, seed: int = 0, *, doc: int = 0) -> list[int]:
+        """encode(text) with BPE-dropout (Provilkov et al., 2020): at every merge step of every pre-token each candidate pair
+        is skipped with probability p.  The result depends on (model, text, p, seed, doc) alone: with rnd of synth.py, the
+        document key is Kd = rnd(seed, 0x64, doc), the key of the pre-token at byte s of text.encode("utf-8") is Kw =
+        rnd(Kd, 0x77, s), and _word_parts_dropout draws from Kw.  The special split, the pre-tokens, [UNK] and the specials
+        are encode's; specials draw nothing.  p = 0 gives encode(text), p = 1 one id per byte of every pre-token.
+        Nothing is cached: every occurrence of a word draws on its own."""
+        T = self._dropout_threshold(p)
+        seed, doc = self._u64(seed, "seed"), self._u64(doc, "doc")
+        if not text:
+            return []
+        kd = rnd_int(seed, 0x64, doc)
+        unk = self._vocab.get(b"[UNK]", 0)
+        ids: list[int] = []
+        pos = 0  # byte offset into text.encode("utf-8"), as in _byte_spans
+        parts = [text] if self._special_pattern is None else self._special_pattern.split(text)
+        for part in parts:
+            if not part:
+                continue
+            if part in self._special_set:
+                data = part.encode("utf-8")
+                tid = self._vocab.get(data)
+                if tid is not None:
+                    ids.append(tid)
+                pos += len(data)
+                continue
+            for pre in self._pattern.findall(part):
+                data = pre.encode("utf-8")
+                ids.extend(self._vocab.get(x, unk) for x in self._word_parts_dropout(data, rnd_int(kd, 0x77, pos), T))
+                pos += len(data)
+        return ids
+
+    def encode_batch_dropout(self, texts: Sequence[str], p: float, seed: int = 0) -> list[list[int]]:
+        """Document d draws as encode_dropout(texts[d], p, seed, doc=d): equal documents of one batch differ."""
+        return [self.encode_dropout(t, p, seed, doc=d) for d, t in enumerate(texts)]
+
+    def _encode_batch_for_layout(self, texts: Sequence[str], dropout, seed) -> list[list[int]]:
+        """the content ids of the fixed-shape forms: encode_batch's, or encode_batch_dropout's when a draw can drop"""
+        T, seed = self._dropout_threshold(dropout), self._u64(seed, "seed")
+        return self.encode_batch_dropout(texts, dropout, seed) if T else self.encode_batch(texts)
+
     # ------------------------------------------------------------------ encode with offsets
     def _byte_spans(self, text: str) -> tuple[list[int], list[tuple[int, int]]]:
         ids: list[int] = []
@@ -234,14 +321,15 @@ class BBPETokenizer:
 
     def encode_batch_padded(self, texts: Sequence[str], max_length: int | None = None, *, pad_id: int | None = None,
                             bos_id: int | None = None, eos_id: int | None = None, truncation: str = "right",
-                            padding_side: str = "right") -> tuple[list[list[int]], list[int]]:
+                            padding_side: str = "right", dropout: float = 0.0, seed: int = 0) -> tuple[list[list[int]], list[int]]:
         """One row of L = max_length ids per text (None: the longest sequence, 0 without texts) -> (rows, lengths).
         seq(d) = [bos_id] + encode(texts[d]) + [eos_id] (each only if given).  A seq longer than L loses content ids from its
         end (truncation "left": from its start); BOS and EOS always survive.  lengths[d] = the length after the cut; the kept
         sequence sits at the left end of its row (padding_side "left": at the right end), pad_id (None: the id of b"[PAD]",
-        else 0) everywhere else.  Ids are any integers in [0, 2^32), in the vocab or not."""
+        else 0) everywhere else.  Ids are any integers in [0, 2^32), in the vocab or not.  dropout > 0: the content ids are
+        encode_batch_dropout(texts, dropout, seed)."""
         L, pad, bos, eos, added = self._padded_args(max_length, pad_id, bos_id, eos_id, truncation, padding_side)
-        docs = self.encode_batch(texts)
+        docs = self._encode_batch_for_layout(texts, dropout, seed)
         if L is None:
             L = max((len(ids) + added for ids in docs), default=0)
         rows, lengths = [], []
@@ -255,15 +343,17 @@ class BBPETokenizer:
         return rows, lengths
 
     def encode_batch_packed(self, texts: Sequence[str], seq_len: int, *, pad_id: int | None = None, bos_id: int | None = None,
-                            eos_id: int | None = None, drop_last: bool = False) -> tuple[list[list[int]], list[list[int]], list[list[int]]]:
+                            eos_id: int | None = None, drop_last: bool = False, dropout: float = 0.0,
+                            seed: int = 0) -> tuple[list[list[int]], list[list[int]], list[list[int]]]:
         """All seq(d) = [bos_id] + encode(texts[d]) + [eos_id] end to end in document order, cut into rows of seq_len
         -> (ids, doc, pos), each ceil(stream / seq_len) rows (drop_last: floor -- the last partial row is dropped).
         doc[r][c] = the index into texts of the document the slot came from, pos[r][c] = the slot's index inside seq(d) (BOS is
-        0).  The slots of the last row past the end of the stream hold pad_id, document 0xFFFFFFFF and position 0."""
+        0).  The slots of the last row past the end of the stream hold pad_id, document 0xFFFFFFFF and position 0.
+        dropout > 0: the content ids are encode_batch_dropout(texts, dropout, seed)."""
         pad, bos, eos, _added = self._layout_ids(pad_id, bos_id, eos_id)
         seq_len = self._row_length(seq_len, "seq_len", 1)
         stream, doc, pos = [], [], []
-        for d, ids in enumerate(self.encode_batch(texts)):
+        for d, ids in enumerate(self._encode_batch_for_layout(texts, dropout, seed)):
             seq = ([bos] if bos is not None else []) + ids + ([eos] if eos is not None else [])
             stream += seq
             doc += [d] * len(seq)
@@ -332,11 +422,35 @@ class BBPETokenizer:
         ids, off, spans = ids.tolist(), off.tolist(), [tuple(p) for p in spans.tolist()]
         return [(ids[off[d]:off[d + 1]], spans[off[d]:off[d + 1]]) for d in range(len(off) - 1)]
 
+    def _device_encode_for_layout(self, ctx, inp, dropout, seed):
+        """-> the device results the layout passes read: yabpe_encode's, or yabpe_encode_dropout's when dropout > 0"""
+        T, seed = self._dropout_threshold(dropout), self._u64(seed, "seed")
+        text = np.frombuffer(inp[0], dtype=np.uint8)
+        if T == 0:
+            return ctx.encode(text, doc_starts=inp[1])
+        return ctx.encode_dropout(text, T, seed, doc_starts=inp[1])
+
+    def encode_array_dropout(self, texts, p: float, seed: int = 0) -> tuple[np.ndarray, np.ndarray]:
+        """encode_batch_dropout(texts, p, seed) on the GPU, id for id: `texts` and the results as encode_array's (one bytes
+        buffer is document 0)."""
+        T, seed = self._dropout_threshold(p), self._u64(seed, "seed")
+        inp = self._device_input(texts)
+        if inp is None:
+            return np.zeros(0, np.uint32), np.zeros(1, np.uint64)
+        return self._device().encode_dropout_to_host(np.frombuffer(inp[0], dtype=np.uint8), T, seed, doc_starts=inp[1])
+
+    def encode_batch_device_dropout(self, texts: Sequence[str], p: float, seed: int = 0) -> list[list[int]]:
+        """encode_batch_dropout(texts, p, seed), computed on the GPU in one call."""
+        ids, off = self.encode_array_dropout(texts, p, seed)
+        ids, off = ids.tolist(), off.tolist()
+        return [ids[off[d]:off[d + 1]] for d in range(len(off) - 1)]
+
     def encode_array_padded(self, texts, max_length: int | None = None, *, pad_id: int | None = None, bos_id: int | None = None,
-                            eos_id: int | None = None, truncation: str = "right",
-                            padding_side: str = "right") -> tuple[np.ndarray, np.ndarray]:
-        """encode_batch_padded(texts, ...), computed on the GPU: yabpe_encode, then yabpe_layout_pad on its device results (the
-        ragged ids never visit the host).  `texts` as encode_array takes them.
+                            eos_id: int | None = None, truncation: str = "right", padding_side: str = "right",
+                            dropout: float = 0.0, seed: int = 0) -> tuple[np.ndarray, np.ndarray]:
+        """encode_batch_padded(texts, ...), computed on the GPU: yabpe_encode (dropout > 0: yabpe_encode_dropout with
+        this seed -- the form a training loop calls every epoch), then yabpe_layout_pad on its device results (the ragged ids
+        never visit the host).  `texts` as encode_array takes them.
         -> (ids np.uint32[n_docs, L], lengths np.uint32[n_docs])."""
         L, pad, bos, eos, _added = self._padded_args(max_length, pad_id, bos_id, eos_id, truncation, padding_side)
         inp = self._device_input(texts)
@@ -344,21 +458,23 @@ class BBPETokenizer:
         if inp is None or L == 0:  # (no rows, or rows of no slots: with BOS / EOS L is at least 1)
             return np.zeros((n_docs, L or 0), np.uint32), np.zeros(n_docs, np.uint32)
         ctx = self._device()
-        di, dd, ni = ctx.encode(np.frombuffer(inp[0], dtype=np.uint8), doc_starts=inp[1])
+        di, dd, ni = self._device_encode_for_layout(ctx, inp, dropout, seed)
         return ctx.layout_pad_to_host(di, ni, dd, n_docs, row_len=L or 0, pad_id=pad, bos_id=bos, eos_id=eos,
                                       trunc_left=truncation == "left", pad_left=padding_side == "left")
 
     def encode_array_packed(self, texts, seq_len: int, *, pad_id: int | None = None, bos_id: int | None = None,
-                            eos_id: int | None = None, drop_last: bool = False) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
-        """encode_batch_packed(texts, ...), computed on the GPU: yabpe_encode, then yabpe_layout_pack on its device results.
-        `texts` as encode_array takes them.  -> (ids, doc, pos), each np.uint32[n_rows, seq_len]."""
+                            eos_id: int | None = None, drop_last: bool = False, dropout: float = 0.0,
+                            seed: int = 0) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """encode_batch_packed(texts, ...), computed on the GPU: yabpe_encode (dropout > 0: yabpe_encode_dropout with
+        this seed), then yabpe_layout_pack on its device results.  `texts` as encode_array takes them.
+        -> (ids, doc, pos), each np.uint32[n_rows, seq_len]."""
         pad, bos, eos, _added = self._layout_ids(pad_id, bos_id, eos_id)
         seq_len = self._row_length(seq_len, "seq_len", 1)
         inp = self._device_input(texts)
         if inp is None:
             return tuple(np.zeros((0, seq_len), np.uint32) for _ in range(3))
         ctx = self._device()
-        di, dd, ni = ctx.encode(np.frombuffer(inp[0], dtype=np.uint8), doc_starts=inp[1])
+        di, dd, ni = self._device_encode_for_layout(ctx, inp, dropout, seed)
         return ctx.layout_pack_to_host(di, ni, dd, len(inp[1]), row_len=seq_len, pad_id=pad, bos_id=bos, eos_id=eos, drop_last=drop_last)
 
     # ------------------------------------------------------------------ decode (tokenizer.py:324-349)
