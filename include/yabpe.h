@@ -226,6 +226,51 @@ int yabpe_pretokenize(yabpe_ctx *ctx, const uint8_t *text, uint64_t n_bytes, con
                       const uint8_t **out_dev_text, uint64_t **out_dev_word_off, uint64_t *out_n_words, int64_t *out_bad_pos);
 int yabpe_pretokenize_free(yabpe_ctx *ctx);
 
+/* Word pool (corpora larger than device memory) -----------------------------------------------------
+ * The word-frequency pooling of trainer.py:221-225 (word_freq[word_tuple] += 1 over all sequences) as a structure that
+ * persists across calls: the context keeps the multiset of distinct byte strings seen so far with u64 counts, on the device.
+ * Text goes through in bounded batches (yabpe_pretokenize -> yabpe_pool_add -> yabpe_pretokenize_free), and the merge loop is
+ * loaded from the pool at the end.  The pool needs no vocab and is independent of the loaded corpus: yabpe_load_words leaves
+ * it alone, and the pool calls leave the corpus alone.
+ *   yabpe_pool_add   adds every word's count to the pool.  The arguments are read as yabpe_load_words reads them: pointers
+ *       may be host or device memory (yabpe_pretokenize's results go in as they are), word_off may point into the middle of
+ *       a larger array, word_freq == NULL means every word counts once.  Zero-length words are dropped (trainer.py:170, 211)
+ *       and counted in the stats.  n_words == 0 is a valid no-op.  YABPE_E_INVALID: word_off is NULL, or bytes is NULL while
+ *       the words have bytes.  YABPE_E_CAPACITY: 2^32 - 2 words or more in one call; the pool would pass 2^32 - 2 unique
+ *       words (yabpe_load_words's own limit); a word of 2^32 bytes or more.  A failed call leaves the pool as it was.
+ *   yabpe_pool_get   the pool as the three arrays yabpe_load_words and yabpe_load_words_resumed take: *out_n_unique + 1
+ *       offsets from 0, *out_n_bytes bytes, *out_n_unique u64 counts -- device memory owned by the library, valid until the
+ *       next yabpe_pool_add, yabpe_pool_clear or yabpe_destroy.  The order of the words is unspecified (within a call it
+ *       follows which occurrence won a race); the trained model does not depend on it.  Before any add: *out_n_unique = 0
+ *       (and one offset, 0).  The load COPIES what it needs (the tiles and the long-word buffer are built from the arrays,
+ *       and every temporary of the load is gone when it returns), so the pool may be cleared right after yabpe_load_words /
+ *       yabpe_load_words_resumed returns.  A count above 2^32 - 1 is the load's YABPE_E_CAPACITY, as for any word_freq.
+ *   yabpe_pool_clear frees the pool; the next add starts an empty one (and reads the options again).
+ * Options (read when a pool starts): "pool_init_slots" (65,536) and "pool_init_bytes" (1 MiB): the starting capacities of
+ * the slot array (rounded up to a power of two, at least 2) and of the byte arena; "pool_hash_bits" (64): only the low N
+ * bits of a word's hash are used for placement and for the hash pre-check (0: every word on one probe chain; for tests). */
+int yabpe_pool_add(yabpe_ctx *ctx, const uint8_t *bytes, const uint64_t *word_off, const uint64_t *word_freq, uint64_t n_words);
+int yabpe_pool_get(yabpe_ctx *ctx, const uint8_t **out_dev_bytes, const uint64_t **out_dev_off, const uint64_t **out_dev_freq,
+                   uint64_t *out_n_unique, uint64_t *out_n_bytes);
+int yabpe_pool_clear(yabpe_ctx *ctx);
+/* The pool since it started, and the device time of the last add that had words (HIP events around each phase's launches). */
+typedef struct yabpe_pool_stats_t {
+    uint64_t n_calls;          /* yabpe_pool_add calls that succeeded, empty ones included */
+    uint64_t n_words_added;    /* words those calls passed (entries of word_off, zero-length ones included) */
+    uint64_t n_empty_dropped;  /* occurrences of zero-length words dropped (with word_freq: their frequencies) */
+    uint64_t n_unique;         /* words in the pool */
+    uint64_t n_bytes;          /* their bytes */
+    uint64_t slot_capacity;    /* slots (>= 2 n_unique); the per-word arrays hold slot_capacity / 2 words */
+    uint64_t arena_capacity;   /* bytes the arena holds */
+    uint64_t slot_growths;     /* times the slots (and the per-word arrays with them) were reallocated and refilled */
+    uint64_t arena_growths;    /* times the arena was reallocated */
+    double pool_ms;            /* the call-local pooling of equal words */
+    double probe_ms;           /* list of the call's unique words, their lookup, scans of the new ones */
+    double append_ms;          /* growth (copies, re-insertion) and the append */
+    double total_ms;           /* first to last event, host gaps in between included */
+} yabpe_pool_stats_t;
+int yabpe_pool_stats(yabpe_ctx *ctx, yabpe_pool_stats_t *out);
+
 /* Encoder (BBPETokenizer.encode on the device, yet_another_bpe/tokenizer.py) ----------------------------------------
  * A trained model: the vocab (n_vocab byte strings, vocab_off: n_vocab + 1 offsets, vocab_ids: their ids), the merges in
  * order (merge_off: 2 n_merges + 1 offsets, left and right operand of merge i = entries 2i and 2i + 1) and the specials in

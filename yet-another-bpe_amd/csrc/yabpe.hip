@@ -31,6 +31,7 @@
 #include "yabpe_decode_kernels.h"
 #include "yabpe_layout_kernels.h"
 #include "yabpe_replay_kernels.h"
+#include "yabpe_pool_kernels.h"
 #include "unicode_classes.inc"
 
 using namespace yb;
@@ -178,6 +179,12 @@ struct yabpe_ctx {
     hipEvent_t lay_ev[4] = {};
     // resumed load (yabpe_load_words_resumed)
     yabpe_resume_stats_t resume_stats{};
+    // persistent word pool (yabpe_pool_add / yabpe_pool_get): arena, off / count / hash, slots (pool_logic.h)
+    bool have_pool = false;
+    PoolView wpool{};
+    uint64_t wpool_arena_cap = 0, wpool_n = 0, wpool_bytes = 0;
+    yabpe_pool_stats_t wpool_stats{};
+    hipEvent_t wpool_ev[4] = {};
     // misc device scratch
     unsigned long long *scratch64 = nullptr;  // 16 x u64: [0] live sum [1] freq overflow [2,3] long words [4,5,6] verify/checksum
                                               // [7] comm_max [8] exchange record count [9] local count-table entries [10..12] comm_max3
@@ -969,6 +976,9 @@ void yabpe_destroy(yabpe_ctx *c) {
         if (e) (void)hipEventDestroy(e);
     yabpe_layout_free(c);
     for (auto &e : c->lay_ev)
+        if (e) (void)hipEventDestroy(e);
+    yabpe_pool_clear(c);
+    for (auto &e : c->wpool_ev)
         if (e) (void)hipEventDestroy(e);
     dfree(c->pt_cls);
     free_corpus(c);
@@ -2420,6 +2430,203 @@ int yabpe_pretokenize_free(yabpe_ctx *c) {
     if (!c) return YABPE_E_INVALID;
     for (void *p : c->pretok_bufs) dfree(p);
     c->pretok_bufs.clear();
+    return YABPE_OK;
+}
+
+// ---------------------------------------------------------------------------------------------- word pool
+// the empty pool with the capacities the options ask for (first add or get after yabpe_create / yabpe_pool_clear)
+static int pool_start(yabpe_ctx *c) {
+    if (c->have_pool) return 0;
+    const unsigned long long slot_cap = pl_pow2((unsigned long long)std::max<int64_t>(2, std::min<int64_t>(optv(c, "pool_init_slots", 1 << 16), 1ll << 32)));
+    const unsigned long long arena_cap = (unsigned long long)std::max<int64_t>(1, optv(c, "pool_init_bytes", 1 << 20));
+    Scratch S(c->device, c->rank);
+    PoolView V{};
+    HIPCHK(c, S.get(&V.arena, arena_cap));
+    HIPCHK(c, S.get(&V.off, pl_words_for(slot_cap) + 1));
+    HIPCHK(c, S.get(&V.count, pl_words_for(slot_cap)));
+    HIPCHK(c, S.get(&V.hash, pl_words_for(slot_cap)));
+    HIPCHK(c, S.get(&V.slots, slot_cap));
+    V.slot_cap = slot_cap;
+    V.hash_bits = (uint32_t)std::max<int64_t>(0, std::min<int64_t>(optv(c, "pool_hash_bits", 64), 64));
+    HIPCHK(c, hipMemsetAsync(V.slots, 0xFF, slot_cap * 4, c->stream));
+    HIPCHK(c, hipMemsetAsync(V.off, 0, 8, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    S.take(V.arena); S.take(V.off); S.take(V.count); S.take(V.hash); S.take(V.slots);
+    c->wpool = V;
+    c->wpool_arena_cap = arena_cap;
+    c->wpool_n = c->wpool_bytes = 0;
+    c->wpool_stats = yabpe_pool_stats_t{};
+    c->have_pool = true;
+    return 0;
+}
+
+int yabpe_pool_clear(yabpe_ctx *c) {
+    if (!c) return YABPE_E_INVALID;
+    if (c->have_pool) {
+        (void)hipSetDevice(c->device);
+        if (c->stream) (void)hipStreamSynchronize(c->stream);
+        dfree(c->wpool.arena); dfree(c->wpool.off); dfree(c->wpool.count); dfree(c->wpool.hash); dfree(c->wpool.slots);
+    }
+    c->wpool = PoolView{};
+    c->wpool_arena_cap = c->wpool_n = c->wpool_bytes = 0;
+    c->wpool_stats = yabpe_pool_stats_t{};
+    c->have_pool = false;
+    return YABPE_OK;
+}
+
+int yabpe_pool_add(yabpe_ctx *c, const uint8_t *bytes, const uint64_t *word_off, const uint64_t *word_freq, uint64_t n_words) {
+    if (!c) return YABPE_E_INVALID;
+    HIPCHK(c, hipSetDevice(c->device));
+    if (n_words >= PL_MAX_WORDS) return fail(c, YABPE_E_CAPACITY, "2^32-2 words or more in one yabpe_pool_add call");
+    TRY(pool_start(c));
+    if (n_words == 0) {
+        c->wpool_stats.n_calls++;
+        return YABPE_OK;
+    }
+    if (!word_off) return fail(c, YABPE_E_INVALID, "word_off is NULL");
+    for (auto &e : c->wpool_ev)
+        if (!e) HIPCHK(c, hipEventCreate(&e));
+    hipEvent_t *ev = c->wpool_ev;
+    Scratch S(c->device, c->rank);  // staged inputs, the call-local pooling, the probe's results; a grown pool's old arrays
+
+    // ---- inputs on the device (as load_words_impl reads them)
+    const unsigned long long *d_off = nullptr, *d_freq = nullptr;
+    const uint8_t *d_bytes = bytes;
+    uint64_t total_bytes = 0, off_base = 0;
+    if (is_device_ptr(word_off)) {
+        HIPCHK(c, hipMemcpy(&total_bytes, word_off + n_words, 8, hipMemcpyDeviceToHost));
+        HIPCHK(c, hipMemcpy(&off_base, word_off, 8, hipMemcpyDeviceToHost));
+    } else {
+        off_base = word_off[0];
+        total_bytes = word_off[n_words];
+    }
+    if (total_bytes < off_base) return fail(c, YABPE_E_INVALID, "word offsets must ascend");
+    total_bytes -= off_base;
+    if (total_bytes && !bytes) return fail(c, YABPE_E_INVALID, "bytes is NULL");
+    TRY(to_device(c, S, (const unsigned long long *)word_off, (n_words + 1) * 8, 1, &d_off));
+    if (total_bytes) {
+        TRY(to_device(c, S, bytes + off_base, total_bytes, 1, &d_bytes));
+        d_bytes -= off_base;  // offsets stay absolute
+    }
+    if (word_freq) TRY(to_device(c, S, (const unsigned long long *)word_freq, n_words * 8, 1, &d_freq));
+    HIPCHK(c, hipEventRecord(ev[0], c->stream));
+
+    // ---- 1. the call's words among themselves: every occurrence is touched here and nowhere else
+    PoolOut po{};
+    if (pool_words(c->stream, S, d_bytes, d_off, d_freq, n_words, &po) != 0)
+        return fail(c, YABPE_E_HIP, "pooling of the call's words failed: %s", hipGetErrorString(hipGetLastError()));
+    HIPCHK(c, hipEventRecord(ev[1], c->stream));
+    const unsigned long long n_call = po.n_unique;  // (>= 1)
+
+    // ---- 2. probe: which of the call's unique words the pool has
+    uint32_t *d_ulist = nullptr, *d_hit = nullptr, *d_nflag = nullptr, *d_nlen = nullptr;
+    unsigned long long *d_nidx = nullptr, *d_noff = nullptr, *d_misc = nullptr;  // d_misc: [0] too-long flag [1] zero-length count
+    HIPCHK(c, S.get(&d_ulist, n_call));
+    HIPCHK(c, S.get(&d_hit, n_call));
+    HIPCHK(c, S.get(&d_nflag, n_call));
+    HIPCHK(c, S.get(&d_nlen, n_call));
+    HIPCHK(c, S.get(&d_nidx, n_call + 1));
+    HIPCHK(c, S.get(&d_noff, n_call + 1));
+    HIPCHK(c, S.get(&d_misc, 2));
+    HIPCHK(c, hipMemsetAsync(d_misc, 0, 16, c->stream));
+    hipLaunchKernelGGL(k_pool_compact, dim3(cdiv64(n_words, 256)), dim3(256), 0, c->stream, po.flag, po.uidx, (unsigned long long)n_words, d_ulist);
+    const PoolCall call{d_bytes, d_off, po.hash, po.count, d_ulist, n_call};
+    const uint32_t grid = cdiv64(n_call, BLOCK);
+    hipLaunchKernelGGL(k_pool_probe, dim3(grid), dim3(BLOCK), 0, c->stream, PoolProbeParams{call, c->wpool, d_hit, d_nflag, d_nlen, (uint32_t *)d_misc});
+    HIPCHK(c, hipGetLastError());
+
+    // ---- 3. where the new words go; room for them
+    if (exclusive_scan<uint32_t>(c->stream, d_nflag, n_call, d_nidx, n_call + 1) != 0 ||
+        exclusive_scan<uint32_t>(c->stream, d_nlen, n_call, d_noff, n_call + 1) != 0)
+        return fail(c, YABPE_E_HIP, "scan of the new words failed: %s", hipGetErrorString(hipGetLastError()));
+    HIPCHK(c, hipEventRecord(ev[2], c->stream));
+    unsigned long long n_new = 0, new_bytes = 0, too_long = 0;
+    HIPCHK(c, hipMemcpyAsync(&n_new, d_nidx + n_call, 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(&new_bytes, d_noff + n_call, 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(&too_long, d_misc, 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (too_long) return fail(c, YABPE_E_CAPACITY, "a single word of 2^32 bytes or more");
+    const unsigned long long n_total = c->wpool_n + n_new, bytes_total = c->wpool_bytes + new_bytes;
+    if (n_total > PL_MAX_WORDS) return fail(c, YABPE_E_CAPACITY, "the pool would hold more than 2^32-2 unique words");
+    // (up to here the pool has only been read; every allocation of the growth is made before anything is replaced)
+    PoolView V = c->wpool;
+    const bool grow_slots = pl_slots_full(n_total, V.slot_cap), grow_arena = bytes_total > c->wpool_arena_cap;
+    const unsigned long long arena_cap = pl_grow(c->wpool_arena_cap, bytes_total);
+    Scratch G(c->device, c->rank);
+    if (grow_slots) {
+        V.slot_cap = pl_slots_for(V.slot_cap, n_total);
+        HIPCHK(c, G.get(&V.off, pl_words_for(V.slot_cap) + 1));
+        HIPCHK(c, G.get(&V.count, pl_words_for(V.slot_cap)));
+        HIPCHK(c, G.get(&V.hash, pl_words_for(V.slot_cap)));
+        HIPCHK(c, G.get(&V.slots, V.slot_cap));
+    }
+    if (grow_arena) HIPCHK(c, G.get(&V.arena, arena_cap));
+    if (grow_slots) {
+        const PoolView &O = c->wpool;
+        HIPCHK(c, hipMemcpyAsync(V.off, O.off, (c->wpool_n + 1) * 8, hipMemcpyDeviceToDevice, c->stream));
+        HIPCHK(c, hipMemsetAsync(V.slots, 0xFF, V.slot_cap * 4, c->stream));
+        if (c->wpool_n) {
+            HIPCHK(c, hipMemcpyAsync(V.count, O.count, c->wpool_n * 8, hipMemcpyDeviceToDevice, c->stream));
+            HIPCHK(c, hipMemcpyAsync(V.hash, O.hash, c->wpool_n * 8, hipMemcpyDeviceToDevice, c->stream));
+            hipLaunchKernelGGL(k_pool_rehash, dim3(cdiv64(c->wpool_n, 256)), dim3(256), 0, c->stream, V.hash, (unsigned long long)c->wpool_n, V.slots, V.slot_cap);
+            HIPCHK(c, hipGetLastError());
+        }
+        S.adopt(O.off); S.adopt(O.count); S.adopt(O.hash); S.adopt(O.slots);  // (freed when the call returns, after the synchronise)
+        G.take(V.off); G.take(V.count); G.take(V.hash); G.take(V.slots);
+        c->wpool_stats.slot_growths++;
+    }
+    if (grow_arena) {
+        if (c->wpool_bytes) HIPCHK(c, hipMemcpyAsync(V.arena, c->wpool.arena, c->wpool_bytes, hipMemcpyDeviceToDevice, c->stream));
+        S.adopt(c->wpool.arena);
+        G.take(V.arena);
+        c->wpool_arena_cap = arena_cap;
+        c->wpool_stats.arena_growths++;
+    }
+    c->wpool = V;
+
+    // ---- 4. append: counts of the found words, bytes / off / count / hash / slot of the new ones
+    hipLaunchKernelGGL(k_pool_append, dim3(grid), dim3(BLOCK), 0, c->stream,
+                       PoolAppendParams{call, V, d_hit, d_nidx, d_noff, (unsigned long long)c->wpool_n, (unsigned long long)c->wpool_bytes, d_misc + 1});
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipEventRecord(ev[3], c->stream));
+    unsigned long long dropped = 0;
+    HIPCHK(c, hipMemcpyAsync(&dropped, d_misc + 1, 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    c->wpool_n = n_total;
+    c->wpool_bytes = bytes_total;
+    yabpe_pool_stats_t &st = c->wpool_stats;
+    st.n_calls++;
+    st.n_words_added += n_words;
+    st.n_empty_dropped += dropped;
+    float ms[4] = {0, 0, 0, 0};
+    HIPCHK(c, hipEventElapsedTime(&ms[0], ev[0], ev[1]));
+    HIPCHK(c, hipEventElapsedTime(&ms[1], ev[1], ev[2]));
+    HIPCHK(c, hipEventElapsedTime(&ms[2], ev[2], ev[3]));
+    HIPCHK(c, hipEventElapsedTime(&ms[3], ev[0], ev[3]));
+    st.pool_ms = ms[0]; st.probe_ms = ms[1]; st.append_ms = ms[2]; st.total_ms = ms[3];
+    return YABPE_OK;
+}
+
+int yabpe_pool_get(yabpe_ctx *c, const uint8_t **out_dev_bytes, const uint64_t **out_dev_off, const uint64_t **out_dev_freq,
+                   uint64_t *out_n_unique, uint64_t *out_n_bytes) {
+    if (!c || !out_dev_bytes || !out_dev_off || !out_dev_freq || !out_n_unique || !out_n_bytes) return YABPE_E_INVALID;
+    HIPCHK(c, hipSetDevice(c->device));
+    TRY(pool_start(c));
+    *out_dev_bytes = c->wpool.arena;
+    *out_dev_off = (const uint64_t *)c->wpool.off;
+    *out_dev_freq = (const uint64_t *)c->wpool.count;
+    *out_n_unique = c->wpool_n;
+    *out_n_bytes = c->wpool_bytes;
+    return YABPE_OK;
+}
+
+int yabpe_pool_stats(yabpe_ctx *c, yabpe_pool_stats_t *out) {
+    if (!c || !out) return YABPE_E_INVALID;
+    *out = c->wpool_stats;
+    out->n_unique = c->wpool_n;
+    out->n_bytes = c->wpool_bytes;
+    out->slot_capacity = c->wpool.slot_cap;
+    out->arena_capacity = c->wpool_arena_cap;
     return YABPE_OK;
 }
 

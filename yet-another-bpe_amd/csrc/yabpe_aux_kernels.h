@@ -367,6 +367,7 @@ struct PoolOut {
     uint32_t *rep, *flag, *ulen;             // per word: its representative, 1 / its length if it is one (else 0)
     unsigned long long *count, *uidx, *uoff; // count[rep]; exclusive scans of flag and ulen (n + 1 entries)
     unsigned long long n_unique, unique_bytes;
+    unsigned long long *hash;                // per word: k_word_hash of its bytes
 };
 
 inline int pool_words(hipStream_t s, Scratch &S, const uint8_t *bytes, const unsigned long long *off, const unsigned long long *freq,
@@ -376,6 +377,7 @@ inline int pool_words(hipStream_t s, Scratch &S, const uint8_t *bytes, const uns
     unsigned long long *d_hash = nullptr;
     uint32_t *d_slots = nullptr;
     YB_RET(S.get(&d_hash, n));
+    out->hash = d_hash;
     YB_RET(S.get(&out->count, n));
     YB_RET(S.get(&d_slots, cap));
     YB_RET(S.get(&out->rep, n));

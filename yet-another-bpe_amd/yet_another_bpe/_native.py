@@ -71,6 +71,12 @@ class ResumeStats(ctypes.Structure):
     _fields_ = [(n, c_uint64) for n in ("n_unique", "n_long", "tokens")] + [(n, c_double) for n in ("segment_ms", "build_ms")]
 
 
+class PoolStats(ctypes.Structure):
+    _fields_ = [(n, c_uint64) for n in ("n_calls", "n_words_added", "n_empty_dropped", "n_unique", "n_bytes", "slot_capacity",
+                                        "arena_capacity", "slot_growths", "arena_growths")] + [
+        (n, c_double) for n in ("pool_ms", "probe_ms", "append_ms", "total_ms")]
+
+
 class Latency(ctypes.Structure):
     _fields_ = [(n, c_double) for n in ("launch_gap_us", "load_trip_us", "coherent_trip_us", "atomic_trip_us")]
 
@@ -90,6 +96,7 @@ SYMBOLS = [
     "yabpe_decode_set_model", "yabpe_decode", "yabpe_decode_free", "yabpe_decode_stats",
     "yabpe_load_words_resumed", "yabpe_resume_stats",
     "yabpe_layout_pad", "yabpe_layout_pack", "yabpe_layout_free", "yabpe_layout_stats",
+    "yabpe_pool_add", "yabpe_pool_get", "yabpe_pool_clear", "yabpe_pool_stats",
 ]
 
 
@@ -156,6 +163,10 @@ def lib() -> ctypes.CDLL:
                                         POINTER(c_void_p), POINTER(c_uint64)]
         L.yabpe_layout_free.argtypes = [c_void_p]
         L.yabpe_layout_stats.argtypes = [c_void_p, POINTER(LayoutStats)]
+        L.yabpe_pool_add.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_uint64]
+        L.yabpe_pool_get.argtypes = [c_void_p, POINTER(c_void_p), POINTER(c_void_p), POINTER(c_void_p), POINTER(c_uint64), POINTER(c_uint64)]
+        L.yabpe_pool_clear.argtypes = [c_void_p]
+        L.yabpe_pool_stats.argtypes = [c_void_p, POINTER(PoolStats)]
         if L.yabpe_abi_version() != 2:
             raise ImportError("libyabpe.so ABI version mismatch")
         _lib = L
@@ -566,6 +577,51 @@ class Context:
         s = LayoutStats()
         self._chk(lib().yabpe_layout_stats(self._h, byref(s)))
         return {f: getattr(s, f) for f, _ in LayoutStats._fields_}
+
+    # -- the persistent word pool (corpora larger than device memory: words go in call by call, the merge loop loads the pool)
+    def pool_add(self, flat, off, freq=None) -> None:
+        """Adds the words' counts to the context's pool.  flat: u8 bytes, off: u64 offsets (n + 1), freq: optional u64
+        counts (None: every word counts once) -- host arrays, as load_words takes them."""
+        flat = np.ascontiguousarray(flat, dtype=np.uint8)
+        off = np.ascontiguousarray(off, dtype=np.uint64)
+        n = max(len(off) - 1, 0)
+        fq = None
+        if freq is not None:
+            fq = np.ascontiguousarray(freq, dtype=np.uint64)
+            assert len(fq) == n
+        self._chk(lib().yabpe_pool_add(self._h, flat.ctypes.data if flat.size else None, off.ctypes.data if off.size else None,
+                                       fq.ctypes.data if fq is not None and fq.size else None, n))
+
+    def pool_add_ptr(self, bytes_ptr: int, off_ptr: int, n_words: int, freq_ptr: int = 0) -> None:
+        """Device (or host) addresses, e.g. the results of pretokenize()."""
+        self._chk(lib().yabpe_pool_add(self._h, c_void_p(bytes_ptr) if bytes_ptr else None, c_void_p(off_ptr) if off_ptr else None,
+                                       c_void_p(freq_ptr) if freq_ptr else None, n_words))
+
+    def pool_get(self):
+        """-> (dev_bytes_ptr, dev_off_ptr u64[n_unique + 1], dev_freq_ptr u64[n_unique], n_unique, n_bytes): what
+        load_words_ptr(bytes, off, n_unique, freq) takes; valid until the next pool_add, pool_clear() or close().  The pool
+        may be cleared as soon as the load has returned."""
+        pb, po, pf, nu, nb = c_void_p(), c_void_p(), c_void_p(), c_uint64(0), c_uint64(0)
+        self._chk(lib().yabpe_pool_get(self._h, byref(pb), byref(po), byref(pf), byref(nu), byref(nb)))
+        return pb.value or 0, po.value or 0, pf.value or 0, nu.value, nb.value
+
+    def pool_items(self) -> dict:
+        """The pool copied to the host as {word bytes: count} (tests and small pools)."""
+        pb, po, pf, nu, nb = self.pool_get()
+        if not nu:
+            return {}
+        off = self.d2h(po, 8 * (nu + 1), np.uint64).tolist()
+        cnt = self.d2h(pf, 8 * nu, np.uint64).tolist()
+        blob = self.d2h(pb, nb).tobytes()
+        return {blob[a:b]: k for a, b, k in zip(off[:-1], off[1:], cnt)}
+
+    def pool_clear(self) -> None:
+        self._chk(lib().yabpe_pool_clear(self._h))
+
+    def pool_stats(self) -> dict:
+        s = PoolStats()
+        self._chk(lib().yabpe_pool_stats(self._h, byref(s)))
+        return {f: getattr(s, f) for f, _ in PoolStats._fields_}
 
     def h2d(self, dev_ptr: int, arr: np.ndarray) -> None:
         arr = np.ascontiguousarray(arr)

@@ -10,7 +10,9 @@ Host-only steps (file chunking, save format) stay in Python as in the reference.
 GPT-2 regex, trainer.py:136-214) exists twice with identical results: `_preprocess_corpus` runs the `regex` module on
 the host and returns Python lists, as the reference's method does; `train()` on a corpus of 1 MiB or more (or with
 YABPE_PRETOKENIZE=gpu) hands the raw file bytes to `yabpe_pretokenize` instead and never builds Python objects per
-pre-token (YABPE_PRETOKENIZE=host forces the host path).
+pre-token (YABPE_PRETOKENIZE=host forces the host path).  With `batch_bytes` (or YABPE_BATCH_BYTES) the device path reads
+the files batch by batch and pools each batch's pre-tokens into the context's word pool (`yabpe_pool_add`), so neither the
+host nor the device ever holds more text than one batch; the merge loop is loaded from the pool.
 """
 from __future__ import annotations
 
@@ -112,6 +114,23 @@ def chunk_ranges(size: int, step: int, read) -> list[tuple[int, int]]:
     return ranges
 
 
+def group_chunks(sizes: Sequence[int], batch_bytes: int) -> list[tuple[int, int]]:
+    """Consecutive chunks grouped into batches: [(first, end)] index ranges that cover range(len(sizes)) in order, each with
+    at least one chunk and at most `batch_bytes` bytes -- except that a chunk larger than that is a batch by itself."""
+    if batch_bytes <= 0:
+        raise ValueError("batch_bytes must be positive")
+    batches: list[tuple[int, int]] = []
+    first, held = 0, 0
+    for i, n in enumerate(sizes):
+        if i > first and held + n > batch_bytes:
+            batches.append((first, i))
+            first, held = i, 0
+        held += n
+    if len(sizes) > first:
+        batches.append((first, len(sizes)))
+    return batches
+
+
 class BBPETrainer:
     """Byte-level BPE trainer with the reference's API; the merge loop runs on the GPU."""
 
@@ -122,11 +141,19 @@ class BBPETrainer:
         self.last_stats: dict | None = None  # yabpe_stats of the last merge loop (not in the reference)
 
     # ------------------------------------------------------------------ train / save (trainer.py:63-117)
-    def train(self, files: Sequence[str | Path]) -> BBPEModel:
+    def train(self, files: Sequence[str | Path], batch_bytes: int | None = None) -> BBPEModel:
+        """`batch_bytes` (None: the environment variable YABPE_BATCH_BYTES; unset: everything at once): the files go through
+        the device pre-tokeniser in batches of whole chunks of at most that many bytes and their pre-tokens are pooled on
+        the device batch by batch -- for corpora larger than host or device memory.  The model is the same."""
         if not files:
             raise ValueError("At least one file must be provided")
         paths = [Path(f) if isinstance(f, str) else f for f in files]
         mode = os.environ.get("YABPE_PRETOKENIZE", "auto")
+        batch = self._batch_bytes(batch_bytes)
+        if batch is not None:
+            if os.environ.get("YABPE_LAYOUT", "dedup") == "flat":
+                raise ValueError("batch_bytes needs the pooled layout: YABPE_LAYOUT=flat keeps every occurrence resident")
+            return self._train_device_batched(paths, batch)
         if mode == "gpu" or (mode == "auto" and sum(p.stat().st_size for p in paths if p.exists()) >= (1 << 20)):
             return self._train_device(paths)
         pretokens = self._pretokenize(paths)
@@ -169,6 +196,87 @@ class BBPETrainer:
             ctx.set_vocab(base)
             ctx.load_words_ptr(dev_text, dev_off, n_words, dedup=os.environ.get("YABPE_LAYOUT", "dedup") != "flat")
             left, right, merged, _count = ctx.train(num_merges, max(0, int(self.config.min_frequency)))  # (<= 0: merge to exhaustion, as the reference does)
+            self.last_stats = ctx.stats()
+        vocab, merges = self._decode_merges(base, left, right, merged)
+        self._vocab = vocab
+        self._merges = merges
+        return BBPEModel(vocab=vocab, merges=merges, special_tokens=specials)
+
+    # ------------------------------------------------------------------ batched device path (the context's word pool)
+    @staticmethod
+    def _batch_bytes(batch_bytes: int | None) -> int | None:
+        if batch_bytes is None:
+            env = os.environ.get("YABPE_BATCH_BYTES", "")
+            if not env:
+                return None
+            batch_bytes = int(env)
+        if int(batch_bytes) <= 0:
+            raise ValueError("batch_bytes must be positive")
+        if os.environ.get("YABPE_PRETOKENIZE", "auto") == "host":
+            raise ValueError("batch_bytes needs the device pre-tokeniser (YABPE_PRETOKENIZE=host is set)")
+        return int(batch_bytes)
+
+    def _file_chunks(self, paths: Sequence[Path]) -> list[tuple[Path, int, int]]:
+        """The reference's chunks of every file, in order: (file, start, stop)."""
+        chunks: list[tuple[Path, int, int]] = []
+        for path in paths:
+            if not path.exists():
+                raise FileNotFoundError(f"File not found: {path}")
+            chunks.extend((path, start, stop) for start, stop in self._chunk_ranges(path))
+        return chunks
+
+    def _pool_chunks(self, ctx, chunks: Sequence[tuple[Path, int, int]], batch_bytes: int) -> None:
+        """Reads the chunks batch by batch (one batch on the host at a time), pre-tokenises each batch on the device and adds
+        its pre-tokens to ctx's word pool.  Pre-tokens never cross a chunk cut, so the pooled multiset is the one the
+        unbatched path pools."""
+        from . import _native
+
+        specials = list(self.config.special_tokens)
+        for first, end in group_chunks([stop - start for _p, start, stop in chunks], batch_bytes):
+            batch = chunks[first:end]
+            buf = np.empty(sum(stop - start for _p, start, stop in batch), dtype=np.uint8)
+            starts: list[int] = []
+            pos = 0
+            for path, start, stop in batch:
+                starts.append(pos)
+                with open(path, "rb") as f:
+                    f.seek(start)
+                    if f.readinto(memoryview(buf[pos:pos + stop - start])) != stop - start:
+                        raise OSError(f"File {path} changed while it was read")
+                pos += stop - start
+            try:
+                dev_text, dev_off, n_words = ctx.pretokenize(buf, chunk_starts=starts, special_tokens=specials)
+            except _native.Utf8Error as e:
+                k = max(i for i, s0 in enumerate(starts) if s0 <= e.position)
+                path, start, _stop = batch[k]
+                raise ValueError(f"File {path} contains invalid UTF-8 at position {start + e.position - starts[k]}.") from e
+            ctx.pool_add_ptr(dev_text, dev_off, n_words)
+            ctx.pretokenize_free()
+            del buf
+
+    def _train_device_batched(self, paths: Sequence[Path], batch_bytes: int) -> BBPEModel:
+        """_train_device with the text going through in batches: files -> [batch -> yabpe_pretokenize -> yabpe_pool_add]* ->
+        yabpe_pool_get -> yabpe_load_words (the pool's counts; nothing left to pool) -> merge loop."""
+        from . import _native  # fails loudly when libyabpe.so / a GPU is missing
+
+        specials = list(self.config.special_tokens)
+        chunks = self._file_chunks(paths)
+        base = self._base_tokens()
+        num_merges = max(0, self.config.vocab_size - len(base))
+        empty = BBPEModel(vocab={t: i for i, t in enumerate(base)}, merges=[], special_tokens=specials)
+        if not chunks:
+            self._vocab, self._merges = dict(empty.vocab), []
+            return empty
+        with _native.Context() as ctx:
+            self._pool_chunks(ctx, chunks, batch_bytes)
+            dev_bytes, dev_off, dev_freq, n_unique, _n_bytes = ctx.pool_get()
+            if n_unique == 0 or num_merges == 0:
+                self._vocab, self._merges = dict(empty.vocab), []
+                return empty
+            ctx.set_vocab(base)
+            ctx.load_words_ptr(dev_bytes, dev_off, n_unique, freq_ptr=dev_freq, dedup=False)
+            ctx.pool_clear()  # (the load copied what it needs)
+            left, right, merged, _count = ctx.train(num_merges, max(0, int(self.config.min_frequency)))
             self.last_stats = ctx.stats()
         vocab, merges = self._decode_merges(base, left, right, merged)
         self._vocab = vocab
@@ -229,14 +337,14 @@ class BBPETrainer:
                              f"reproduce its vocab ({len(toks)} tokens replayed, {len(vocab)} in the model){hint}")
         return toks, triples
 
-    def train_from(self, model, files: Sequence[str | Path]) -> BBPEModel:
+    def train_from(self, model, files: Sequence[str | Path], batch_bytes: int | None = None) -> BBPEModel:
         """Continues training from `model` (a BBPEModel, or anything with .vocab, .merges and .special_tokens) on `files`:
         more merges on the same corpus, or new merges learned from a new one.  Every existing id is kept; the result is
         model.merges + the new merges and the extended vocab, exactly what train() gives when the corpus is the one the
         model was trained on.  The iteration budget is max(0, vocab_size - len(base) - len(model.merges)) (a merge that
         reused an id cost an iteration too, trainer.py:238).  An empty corpus or a zero budget returns the model unchanged.
         Pre-tokenisation is train()'s (special tokens are ordinary words), on the device under the same size / environment
-        rule; the words are pooled (the flat layout does not apply)."""
+        rule; the words are pooled (the flat layout does not apply).  `batch_bytes`: as train() takes it."""
         if not files:
             raise ValueError("At least one file must be provided")
         paths = [Path(f) if isinstance(f, str) else f for f in files]
@@ -258,7 +366,22 @@ class BBPETrainer:
 
         min_freq = max(0, int(self.config.min_frequency))
         mode = os.environ.get("YABPE_PRETOKENIZE", "auto")
-        if mode == "gpu" or (mode == "auto" and sum(p.stat().st_size for p in paths) >= (1 << 20)):
+        batch = self._batch_bytes(batch_bytes)
+        if batch is not None:
+            file_chunks = self._file_chunks(paths)
+            if not file_chunks:
+                return unchanged()
+            with _native.Context() as ctx:
+                self._pool_chunks(ctx, file_chunks, batch)
+                dev_bytes, dev_off, dev_freq, n_unique, _n_bytes = ctx.pool_get()
+                if n_unique == 0:
+                    return unchanged()
+                ctx.set_vocab(toks)
+                ctx.load_words_resumed_ptr(dev_bytes, dev_off, n_unique, triples, freq_ptr=dev_freq, dedup=False)
+                ctx.pool_clear()  # (the load copied what it needs)
+                left, right, merged, _count = ctx.train(num_merges, min_freq)
+                self.last_stats = ctx.stats()
+        elif mode == "gpu" or (mode == "auto" and sum(p.stat().st_size for p in paths) >= (1 << 20)):
             text, chunks, total = self._gather_text(paths)
             if total == 0:
                 return unchanged()
