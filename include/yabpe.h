@@ -98,7 +98,17 @@ int yabpe_resume_stats(yabpe_ctx *ctx, yabpe_resume_stats_t *out);
  *   out_merged           id of left+right: a fresh id, or the existing id when those bytes are already a
  *                        token (no id consumed, :298-300)
  *   out_count            the pair's count when it was selected
- * May be called again to continue training with more merges. */
+ * May be called again to continue training with more merges.
+ *
+ * Maximum token length: option "max_token_bytes" (yabpe_set_option; 0, the default: no limit; N >= 2: the limit in bytes).
+ * With a limit the best pair of every step is the maximum over the pairs whose two tokens are together at most N bytes
+ * long, and the stop rules look at that pair: training stops when no such pair is left or its count is below
+ * min_frequency, whatever longer pairs count.  Everything else is unchanged; base-vocabulary tokens (specials) and the
+ * merges a resumed load replays are not subject to it.  The limit is a property of a LOAD, not of a yabpe_train call: it is
+ * read by yabpe_load_words / yabpe_load_words_resumed and holds until the next load -- for every yabpe_train call on that
+ * load and for yabpe_verify_table; setting the option later changes nothing until words are loaded again.  (Pairs over the
+ * limit are never put into the pair table, so one dropped under a tight limit could not be recovered by loosening it, and
+ * one admitted under a loose limit would survive tightening.)  1 or a negative value: YABPE_E_INVALID from the next load. */
 int yabpe_train(yabpe_ctx *ctx, uint32_t num_merges, uint64_t min_frequency, uint32_t *out_left,
                 uint32_t *out_right, uint32_t *out_merged, uint64_t *out_count, uint32_t *out_n_merges);
 

@@ -1093,6 +1093,10 @@ static int load_words_impl(yabpe_ctx *c, const uint8_t *bytes, const uint64_t *w
     if (!c->have_vocab) return fail(c, YABPE_E_INVALID, "call yabpe_set_vocab first");
     if (!word_off) return fail(c, YABPE_E_INVALID, "word_off is NULL");
     if (n_words >= 0xFFFFFFFFull) return fail(c, YABPE_E_CAPACITY, "more than 2^32-2 words per context");
+    // maximum token length: a property of the load -- read here, fixed until the next load
+    const int64_t max_token_bytes = optv(c, "max_token_bytes", 0);
+    if (!yb_limit_valid(max_token_bytes))
+        return fail(c, YABPE_E_INVALID, "max_token_bytes is %lld: 0 (no limit) or a length of at least %u bytes", (long long)max_token_bytes, YB_LIMIT_MIN);
     free_corpus(c);
     struct Events {  // (destroyed on every way out)
         hipEvent_t ev0 = nullptr, ev1 = nullptr, ev_seg = nullptr;
@@ -1305,6 +1309,8 @@ static int load_words_impl(yabpe_ctx *c, const uint8_t *bytes, const uint64_t *w
     h->iter = 0; h->done = 0; h->halt = 0; h->halt_req = 0; h->sites = 0;
     h->tokens_now = total_tokens;
     h->table_entries = 0;
+    h->tok_len = c->tt.len;  // (in place before the first key enters the table: the count below already leaves out what is too long)
+    h->max_token_bytes = (uint32_t)max_token_bytes;
     TRY(state_push(c));
     TRY(refresh_live_slots(c));
     c->sig_valid = false;

@@ -22,6 +22,7 @@
 
 #include <type_traits>
 
+#include "limit_logic.h"
 #include "tile_logic.h"
 
 namespace yb {
@@ -76,6 +77,11 @@ struct DevState {
     uint32_t n_batch;              // merges selected and not applied yet: batch[0 .. n_batch), in selection order; a, b, c above = batch[0]
     uint32_t n_select;             // selections that committed a batch so far (= apply launches that had work to do, plus the pending one)
     BatchMerge batch[KMAX];
+    // maximum token length, written by the host when words are loaded and fixed until the next load; read only
+    // where a pair table takes a NEW key (gt_add_from), hence at the end: nothing the per-merge launches read moves
+    const uint32_t *tok_len;       // TokTable::len
+    uint32_t max_token_bytes;      // 0: no limit
+    uint32_t pad_limit;
 };
 
 // multi-GPU exchange records: what a rank's apply pass sends to the others (see k_delta_apply)
@@ -275,6 +281,17 @@ __device__ __forceinline__ void gt_add_from(const PairTable &t, DevState *st, ui
     for (uint32_t probe = 0; probe < t.max_probe; ++probe) {
         uint32_t k = __hip_atomic_load(&t.keys[s], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         if (k == EMPTY) {
+            // The ONE place where a key enters a table (main table, replica, the scratch table of a recount, a rehash).  With a
+            // maximum token length set, a pair whose two tokens are together longer never gets in: its delta is dropped, and so
+            // is every later one -- they walk to an EMPTY slot of the same chain.  Such a pair can never be merged, so its count
+            // has no reader; selection, candidate list and stop rules see it as absent.  Both lengths are final: a token's
+            // length is written by the selection that creates it, a launch before any pair can name it (plain loads).  The
+            // loads are consumed right here, inside the rare branch: nothing is pending where it rejoins ((c) "vmcnt" (1)).
+            const uint32_t lim = st->max_token_bytes;
+            if (lim != 0u) {
+                const uint32_t *len = st->tok_len;
+                if (!yb_pair_fits(len[key >> 16], len[key & 0xffffu], lim)) return;
+            }
             k = atomicCAS(&t.keys[s], EMPTY, key);
             if (k == EMPTY) {
                 if (inserted) ++*inserted; else atomicAdd(t.entries, 1ull);
@@ -821,6 +838,7 @@ __global__ __launch_bounds__(BLOCK) void k_dense_to_table(DenseToTableParams P) 
     const uint32_t i = blockIdx.x * BLOCK + threadIdx.x; // i = left * 256 + right
     if (i >= 65536u) return;
     const unsigned long long v = P.dense[i];
+    // (both tokens are single bytes: 1 + 1 <= every maximum token length, which is >= YB_LIMIT_MIN = 2 -- and gt_add checks anyway)
     if (v) gt_add(P.table, P.st, yb_pairkey(i >> 8, i & 255u), (long long)v);
 }
 

@@ -156,8 +156,9 @@ def train_text_sharded(ctx_factory, files, config, rank: int, world: int, transp
     from pathlib import Path
 
     from . import _native
-    from .trainer import BBPEModel, BBPETrainer
+    from .trainer import BBPEModel, BBPETrainer, max_token_bytes
 
+    limit = max_token_bytes(config)  # (ValueError before any file is read)
     tr = BBPETrainer(config)
     paths = [Path(f) for f in files]
     for p in paths:
@@ -176,6 +177,8 @@ def train_text_sharded(ctx_factory, files, config, rank: int, world: int, transp
     with ctx_factory() as ctx:
         for k, v in (options or {}).items():
             ctx.set_option(k, v)
+        if limit:  # config.max_token_length: the same on every rank, so every replica leaves out the same pairs
+            ctx.set_option("max_token_bytes", limit)
         ctx.set_vocab(base)
         attach(ctx, rank, world, transport)
         err = None
@@ -210,8 +213,9 @@ def train_device_text_sharded(ctx_factory, make_text, config, rank: int, world: 
     `make_text(ctx) -> (dev_ptr, n_bytes)` runs on every rank; the chunk cuts are the reference's (config.chunk_size_bytes),
     this rank pre-tokenises ITS chunks, pools the pre-tokens and joins the collective merge loop.
     Returns (left, right, merged, count, stats, n_pretokens_here)."""
-    from .trainer import BBPETrainer, chunk_ranges
+    from .trainer import BBPETrainer, chunk_ranges, max_token_bytes
 
+    limit = max_token_bytes(config)
     tr = BBPETrainer(config)
     base = tr._base_tokens()
     specials = list(config.special_tokens)
@@ -219,6 +223,8 @@ def train_device_text_sharded(ctx_factory, make_text, config, rank: int, world: 
     with ctx_factory() as ctx:
         for k, v in (options or {}).items():
             ctx.set_option(k, v)
+        if limit:  # config.max_token_length: the same on every rank, so every replica leaves out the same pairs
+            ctx.set_option("max_token_bytes", limit)
         ctx.set_vocab(base)
         attach(ctx, rank, world, transport)
         ptr, n_bytes = make_text(ctx)

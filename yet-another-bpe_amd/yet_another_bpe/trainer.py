@@ -42,6 +42,12 @@ class BBPETrainerConfig:
         chunk_size_bytes: logical chunk size when splitting large files.
         seed: unused (kept for compatibility, as in the reference).
         special_tokens: strings that get vocabulary ids right after the 256 bytes.
+        max_token_length: longest token a merge may create, in BYTES (not in the reference; `max_token_length` of other BPE
+            trainers, where one character of a byte-level alphabet is one byte).  None: no limit; an integer >= 2: at every
+            step the best pair is taken among the pairs with len(left) + len(right) <= max_token_length, and training stops
+            when none of those is left or the best of them is below min_frequency.  Special tokens are vocabulary entries,
+            not merges, and may be longer; the merges of a model that train_from continues are replayed as they are.  The
+            limit is NOT stored by save / save_lossless: a train_from that should keep it needs it in its own config.
     """
 
     vocab_size: int = 32000
@@ -50,6 +56,18 @@ class BBPETrainerConfig:
     chunk_size_bytes: int = 8 * 1024 * 1024
     seed: int = 42
     special_tokens: Sequence[str] = field(default_factory=lambda: ["[PAD]", "[UNK]", "[BOS]", "[EOS]"])
+    max_token_length: int | None = None
+
+
+def max_token_bytes(config: BBPETrainerConfig) -> int:
+    """config.max_token_length as the library's option `max_token_bytes` (0: no limit).  ValueError for anything but None or
+    an integer >= 2 (two single bytes must be able to merge); bool is not an integer here."""
+    n = getattr(config, "max_token_length", None)
+    if n is None:
+        return 0
+    if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or n < 2:
+        raise ValueError(f"max_token_length must be None or an integer >= 2 (bytes), got {n!r}")
+    return int(n)
 
 
 class BBPEModel:
@@ -140,11 +158,27 @@ class BBPETrainer:
         self._merges: list[tuple[bytes, bytes]] = []
         self.last_stats: dict | None = None  # yabpe_stats of the last merge loop (not in the reference)
 
+    def _context(self):
+        """A device context for a merge loop of this trainer: the maximum token length, when set, goes in as an option before
+        any words are loaded (the library reads it at the load)."""
+        from . import _native  # fails loudly when libyabpe.so / a GPU is missing
+
+        limit = max_token_bytes(self.config)
+        ctx = _native.Context()
+        if limit:
+            try:
+                ctx.set_option("max_token_bytes", limit)
+            except BaseException:
+                ctx.close()
+                raise
+        return ctx
+
     # ------------------------------------------------------------------ train / save (trainer.py:63-117)
     def train(self, files: Sequence[str | Path], batch_bytes: int | None = None) -> BBPEModel:
         """`batch_bytes` (None: the environment variable YABPE_BATCH_BYTES; unset: everything at once): the files go through
         the device pre-tokeniser in batches of whole chunks of at most that many bytes and their pre-tokens are pooled on
         the device batch by batch -- for corpora larger than host or device memory.  The model is the same."""
+        max_token_bytes(self.config)  # (a bad limit fails before any file is read or any device call is made)
         if not files:
             raise ValueError("At least one file must be provided")
         paths = [Path(f) if isinstance(f, str) else f for f in files]
@@ -188,7 +222,7 @@ class BBPETrainer:
         if total == 0:
             self._vocab, self._merges = dict(empty.vocab), []
             return empty
-        with _native.Context() as ctx:
+        with self._context() as ctx:
             dev_text, dev_off, n_words = self._pretokenize_device(ctx, text, chunks)
             if n_words == 0 or num_merges == 0:
                 self._vocab, self._merges = dict(empty.vocab), []
@@ -267,7 +301,7 @@ class BBPETrainer:
         if not chunks:
             self._vocab, self._merges = dict(empty.vocab), []
             return empty
-        with _native.Context() as ctx:
+        with self._context() as ctx:
             self._pool_chunks(ctx, chunks, batch_bytes)
             dev_bytes, dev_off, dev_freq, n_unique, _n_bytes = ctx.pool_get()
             if n_unique == 0 or num_merges == 0:
@@ -344,7 +378,10 @@ class BBPETrainer:
         model was trained on.  The iteration budget is max(0, vocab_size - len(base) - len(model.merges)) (a merge that
         reused an id cost an iteration too, trainer.py:238).  An empty corpus or a zero budget returns the model unchanged.
         Pre-tokenisation is train()'s (special tokens are ordinary words), on the device under the same size / environment
-        rule; the words are pooled (the flat layout does not apply).  `batch_bytes`: as train() takes it."""
+        rule; the words are pooled (the flat layout does not apply).  `batch_bytes`: as train() takes it.
+        config.max_token_length constrains only the merges learned here: the model's own merges are replayed whatever their
+        length (the limit is not part of a saved model)."""
+        max_token_bytes(self.config)  # (a bad limit fails before any file is read or any device call is made)
         if not files:
             raise ValueError("At least one file must be provided")
         paths = [Path(f) if isinstance(f, str) else f for f in files]
@@ -371,7 +408,7 @@ class BBPETrainer:
             file_chunks = self._file_chunks(paths)
             if not file_chunks:
                 return unchanged()
-            with _native.Context() as ctx:
+            with self._context() as ctx:
                 self._pool_chunks(ctx, file_chunks, batch)
                 dev_bytes, dev_off, dev_freq, n_unique, _n_bytes = ctx.pool_get()
                 if n_unique == 0:
@@ -385,7 +422,7 @@ class BBPETrainer:
             text, chunks, total = self._gather_text(paths)
             if total == 0:
                 return unchanged()
-            with _native.Context() as ctx:
+            with self._context() as ctx:
                 dev_text, dev_off, n_words = self._pretokenize_device(ctx, text, chunks)
                 if n_words == 0:
                     return unchanged()
@@ -400,7 +437,7 @@ class BBPETrainer:
             words = [t.encode("utf-8") for t in pooled]
             off = np.zeros(len(words) + 1, dtype=np.uint64)
             np.cumsum([len(w) for w in words], out=off[1:])
-            with _native.Context() as ctx:
+            with self._context() as ctx:
                 ctx.set_vocab(toks)
                 ctx.load_words_resumed(np.frombuffer(b"".join(words), dtype=np.uint8), off,
                                        np.fromiter(pooled.values(), dtype=np.uint64, count=len(pooled)), triples)
@@ -519,6 +556,7 @@ class BBPETrainer:
         return self._merge_loop_words(words, None)
 
     def _merge_loop_words(self, words: Sequence[bytes], freq: np.ndarray | None):
+        max_token_bytes(self.config)
         base = self._base_tokens()
         num_merges = max(0, self.config.vocab_size - len(base))  # trainer.py:238
         if not words or num_merges == 0:
@@ -529,7 +567,7 @@ class BBPETrainer:
         off = np.zeros(len(words) + 1, dtype=np.uint64)
         np.cumsum(lens, out=off[1:])
         flat = np.frombuffer(b"".join(words), dtype=np.uint8)
-        with _native.Context() as ctx:
+        with self._context() as ctx:
             ctx.set_vocab(base)
             ctx.load_words(flat, off, freq)
             left, right, merged, _count = ctx.train(num_merges, max(0, int(self.config.min_frequency)))  # (<= 0: merge to exhaustion, as the reference does)
