@@ -175,6 +175,8 @@ typedef struct yabpe_stats_t {
        merges in one pass over the stream); dense_algo_bytes_sampled / dense_actual_bytes_sampled are the phase's totals
        scaled to the event-timed launches */
     uint64_t dense_launches, dense_merges;
+    /* sparse launches over a stream of more chunks than workgroups: pieces of the second round taken from the shared counter */
+    uint64_t scan_skip_pieces_taken;
 } yabpe_stats_t;
 int yabpe_stats(yabpe_ctx *ctx, yabpe_stats_t *out);
 /* Per-iteration log of the last yabpe_train call: sites merged M_i and live slots read by iteration i. */

@@ -86,6 +86,8 @@ Rccl *rccl() {
 
 constexpr uint32_t MAX_APPLY_BLOCKS = 8192;
 constexpr uint32_t MAX_LISTS = 2048;  // the sparse launch's scan workgroups at most (blk_read slots)
+// blk_read: [0, MAX_LISTS) tiles read, [MAX_LISTS, 2 MAX_LISTS) second-round pieces taken, then the piece counter's own 128-B line
+constexpr uint32_t BLK_READ_WORDS = 2 * MAX_LISTS + 16;
 thread_local std::string g_create_error;
 
 struct EventPair {
@@ -197,8 +199,9 @@ struct yabpe_ctx {
     // skip index
     unsigned long long *sig = nullptr;
     uint32_t sig_stride = 0;
-    unsigned long long *blk_read = nullptr;  // [MAX_LISTS] tiles read by k_scan_skip, accumulated
+    unsigned long long *blk_read = nullptr;  // [BLK_READ_WORDS] tiles read by k_scan_skip, accumulated; pieces taken; the piece counter
     uint64_t scan_skip_launches = 0;
+    uint64_t piece_tag = 0;                  // tag of the last launch that used the piece counter: never reset while blk_read lives
     bool sig_valid = false;
     uint32_t sig_built_at = 0;
     uint64_t sig_tokens_at_build = 0;  // T when the signatures were last built (stale bits grow with the sites merged since)
@@ -1363,7 +1366,7 @@ static int load_words_impl(yabpe_ctx *c, const uint8_t *bytes, const uint64_t *w
     c->xeff_sum = 0;
     c->exchange_growths = 0;
     c->exchange_max_records = 0;
-    if (c->blk_read) HIPCHK(c, hipMemsetAsync(c->blk_read, 0, MAX_LISTS * 8, c->stream));
+    if (c->blk_read) HIPCHK(c, hipMemsetAsync(c->blk_read, 0, 2 * MAX_LISTS * 8, c->stream));  // (the statistics; the counter word keeps its tag)
     c->stats.algo_bytes_total = 0;
     c->have_words = true;
     return YABPE_OK;
@@ -1533,15 +1536,22 @@ static int launch_apply(yabpe_ctx *c, uint32_t rec_base, uint32_t tokens_upper, 
             const uint32_t n_chunks = (c->n_tiles + chunk - 1) / chunk;
             const uint32_t scan_grid = std::max(1u, std::min<uint32_t>(std::min<uint32_t>(n_chunks, target), MAX_LISTS));
             if (!c->blk_read) {
-                TRY(dmalloc(c, &c->blk_read, MAX_LISTS));
-                HIPCHK(c, hipMemsetAsync(c->blk_read, 0, MAX_LISTS * 8, c->stream));
+                TRY(dmalloc(c, &c->blk_read, BLK_READ_WORDS));
+                HIPCHK(c, hipMemsetAsync(c->blk_read, 0, BLK_READ_WORDS * 8, c->stream));
             }
+            // a stream of more chunks than workgroups (the early sparse merges: the chunk is capped by the registers of the
+            // signature sweep): the tiles behind the first round go out in pieces, to whoever finishes first (steal_logic.h)
+            const uint32_t rest = c->n_tiles - std::min<uint64_t>(c->n_tiles, (uint64_t)scan_grid * chunk);
+            const bool pieces = rest && nw == 8 && optv(c, "chunk_steal", 1);  // (the 16-wave form has no counter path: chosen where ONE round covers the stream)
+            const uint32_t piece = !rest ? 0u : pieces ? yb_piece_tiles(rest, scan_grid, chunk) : chunk;
             // (a sparse merge leaves a workgroup a few dozen deltas: a quarter of the aggregator per merge of the batch is
             // plenty -- less to initialise and to flush; the count of the LAST batch's merges bounds this batch's)
             if (optv(c, "agg_small", 1) && !c->weighted && c->st_host->best_count * 4 < 48ull * std::max<uint32_t>(1u, c->n_cu * 3))
                 P.agg_mask = (uint32_t)(c->kmax_now > 2 ? AGG_N : nw >= 16 ? AGG_N / 2 : AGG_N / 4) - 1u;
             const uint32_t rr_blocks = rank_rides ? rank_blocks : 0u;
-            ScanSkipParams SQ{P, c->blk_read, scan_grid, kt, chunk, R, fuse_params(scan_grid), LW, scan_grid + rr_blocks};
+            ScanSkipParams SQ{P, c->blk_read, scan_grid, kt, chunk, R, fuse_params(scan_grid), LW, scan_grid + rr_blocks,
+                              piece, pieces ? yb_piece_count(rest, piece) : 0u, pieces ? c->blk_read + 2 * MAX_LISTS : nullptr,
+                              pieces ? ++c->piece_tag : 0ull, c->blk_read + MAX_LISTS};
             c->blk_used = std::max(c->blk_used, scan_grid);
             const uint32_t grid = scan_grid + rr_blocks + long_blocks;
 #define YB_LAUNCH_SPARSE(NW_)                                                                                        \
@@ -2125,10 +2135,12 @@ int yabpe_stats(yabpe_ctx *c, yabpe_stats_t *out) {
     c->stats.exchange_max_records = c->exchange_max_records;
     c->stats.scan_skip_launches = c->scan_skip_launches;
     c->stats.scan_skip_tiles_read = 0;
+    c->stats.scan_skip_pieces_taken = 0;
     if (c->blk_read) {
-        std::vector<unsigned long long> br(MAX_LISTS);
-        HIPCHK(c, hipMemcpy(br.data(), c->blk_read, MAX_LISTS * 8, hipMemcpyDeviceToHost));
-        for (auto v : br) c->stats.scan_skip_tiles_read += v;
+        std::vector<unsigned long long> br(2 * MAX_LISTS);
+        HIPCHK(c, hipMemcpy(br.data(), c->blk_read, 2 * MAX_LISTS * 8, hipMemcpyDeviceToHost));
+        for (uint32_t i = 0; i < MAX_LISTS; ++i) c->stats.scan_skip_tiles_read += br[i];
+        for (uint32_t i = MAX_LISTS; i < 2 * MAX_LISTS; ++i) c->stats.scan_skip_pieces_taken += br[i];
     }
     *out = c->stats;
     return YABPE_OK;
@@ -2290,10 +2302,21 @@ int yabpe_debug_launch_profile(unsigned long long *out, int reset) { // 65536 x 
     if (reset) {
         std::vector<unsigned long long> z(65536 * 4, 0ull);
         for (size_t i = 0; i < 65536; ++i) z[i * 4] = ~0ull;
+#ifdef YB_PROFILE_LAUNCH
+        {
+            std::vector<unsigned long long> zw(65536 * 8, 0ull);
+            if (hipMemcpyToSymbol(HIP_SYMBOL(yb::g_launch_wg), zw.data(), zw.size() * 8) != hipSuccess) return -1;
+        }
+#endif
         return hipMemcpyToSymbol(HIP_SYMBOL(yb::g_launch_prof), z.data(), z.size() * 8) == hipSuccess ? 0 : -1;
     }
     return hipMemcpyFromSymbol(out, HIP_SYMBOL(yb::g_launch_prof), (size_t)65536 * 32) == hipSuccess ? 0 : -1;
 }
+#ifdef YB_PROFILE_LAUNCH
+int yabpe_debug_launch_wg(unsigned long long *out) { // 65536 x 8 u64
+    return hipMemcpyFromSymbol(out, HIP_SYMBOL(yb::g_launch_wg), (size_t)65536 * 64) == hipSuccess ? 0 : -1;
+}
+#endif
 int yabpe_debug_stop_hist(unsigned long long *out) { // 65536 x u64
     return hipMemcpyFromSymbol(out, HIP_SYMBOL(yb::g_stop_hist), (size_t)65536 * 8) == hipSuccess ? 0 : -1;
 }

@@ -23,6 +23,7 @@
 #include <type_traits>
 
 #include "limit_logic.h"
+#include "steal_logic.h"
 #include "tile_logic.h"
 
 namespace yb {
@@ -2909,6 +2910,23 @@ __global__ __launch_bounds__(BLOCK) void k_apply(ApplyParams P, uint32_t apply_b
 #ifdef YB_PROFILE_LAUNCH // (its own build: these same-address atomics sit in front of the workgroups' loads and distort the phase stamps)
 #define YB_LAUNCH_START(it) do { if (threadIdx.x == 0) atomicMin(&g_launch_prof[((it) & 0xFFFFu) * 4 + 0], wall_clock64()); } while (0)
 #define YB_LAUNCH_END(it) do { if (threadIdx.x == 0) atomicMax(&g_launch_prof[((it) & 0xFFFFu) * 4 + 1], wall_clock64()); } while (0)
+// per launch, over the SCAN workgroups: sum of their end stamps, their number, the last end, sum and maximum of their candidate
+// tiles, the last end of the candidate phase (what a launch loses to its stragglers: last end - mean end; tools/straggler_profile.py)
+__device__ unsigned long long g_launch_wg[65536 * 8];
+#define YB_LAUNCH_WG_END(it, ncand, t_cand)                                             \
+    do {                                                                                \
+        if (threadIdx.x == 0) {                                                         \
+            unsigned long long *w_ = &g_launch_wg[((it) & 0xFFFFu) * 8];                \
+            const unsigned long long e_ = wall_clock64();                               \
+            atomicAdd(&w_[0], e_);                                                      \
+            atomicAdd(&w_[1], 1ull);                                                    \
+            atomicMax(&w_[2], e_);                                                      \
+            atomicAdd(&w_[3], (unsigned long long)(ncand));                             \
+            atomicMax(&w_[4], (unsigned long long)(ncand));                             \
+            atomicAdd(&w_[5], (unsigned long long)(t_cand));                            \
+            atomicMax(&w_[6], (unsigned long long)(t_cand));                            \
+        }                                                                               \
+    } while (0)
 #else
 #define YB_LAUNCH_START(it) do { } while (0)
 #define YB_LAUNCH_END(it) do { } while (0)
@@ -2934,6 +2952,18 @@ struct ScanSkipParams {
     FuseParams F;                 // ticket != NULL: the workgroup that finishes last selects the next batch
     LongParams LW;                // the long words ride along too: workgroups [long_first, gridDim.x) (k_apply_long's work)
     uint32_t long_first;
+    // second round (steal_logic.h): the tiles behind the first scan_blocks chunks, in pieces of `piece` tiles that the
+    // workgroups take from ONE tagged counter as they finish.  piece_ctr == NULL: dealt by workgroup index, a chunk each
+    uint32_t piece;                // (0: the first round covers the stream -- all but the earliest sparse launches)
+    uint32_t n_pieces;
+    unsigned long long *piece_ctr; // the counter word (a 128-B line of its own)
+    unsigned long long piece_tag;  // grows with every launch: nothing is cleared in between
+    unsigned long long *piece_taken; // [scan_blocks] pieces this workgroup took (statistics; plain stores)
+};
+struct PieceCtrOps { // (device-scope atomics on the counter word: yb_steal_claim's two operations)
+    unsigned long long *p;
+    __device__ __forceinline__ unsigned long long add(unsigned long long v) { return atomicAdd(p, v); }
+    __device__ __forceinline__ void max(unsigned long long v) { atomicMax(p, v); }
 };
 
 template <bool WEIGHTED, int NW>
@@ -2941,7 +2971,11 @@ __device__ __forceinline__ bool scan_skip_block(DevState *st, const ScanSkipPara
     using AggV = typename std::conditional<WEIGHTED, unsigned long long, int>::type;
     constexpr int NT = NW * 64;                   // threads of the workgroup (NW waves)
     constexpr int KTM = scan_kt_max(NW);
+    // (the second round's counter: the 8-wave form only.  The 16-wave form is chosen where the stream fits ONE round of its
+    // workgroups; forced on a longer stream it deals the second round by workgroup index -- it has no register to spare)
+    constexpr bool DYN = NW == 8;
     __shared__ uint32_t s_n, s_claim;             // entries on the hit list; the next one no wave has taken yet
+    __shared__ uint32_t s_piece;                  // second round: the piece thread 0 took for the workgroup
     __shared__ uint2 s_list[NT * KTM];            // (tile, live length | merges noted << 16)
     __shared__ uint32_t s_keys[AGG_N];
     __shared__ AggV s_vals[AGG_N];
@@ -3003,14 +3037,15 @@ __device__ __forceinline__ bool scan_skip_block(DevState *st, const ScanSkipPara
     unsigned long long wave_sites = 0, wave_freed = 0;
     const uint32_t kt = Q.kt;
     const uint32_t chunk = Q.chunk;
-    const uint32_t n_chunks = (P.n_tiles + chunk - 1) / chunk;
-    for (uint32_t ch = blockIdx.x; ch < n_chunks; ch += n_blocks) {
+    // first round: chunk blockIdx.x.  Then the tiles from `rest0` on, if there are any: in pieces, first come first served
+    uint32_t t0 = blockIdx.x * chunk; // (the only thing about the workgroup's place in the stream that lives through the candidate loop)
+    while (t0 < P.n_tiles) {
         // all of this thread's lengths are requested first, then the signature words merge by merge
         uint32_t len[KTM], km[KTM];
-        const uint32_t t_end = min(P.n_tiles, ch * chunk + chunk);
+        const uint32_t t_end = min(P.n_tiles, t0 + ((DYN && Q.piece_ctr && t0 >= n_blocks * chunk) ? Q.piece : chunk));
 #pragma unroll
         for (uint32_t j = 0; j < (uint32_t)KTM; ++j) {
-            const uint32_t t = ch * chunk + j * NT + threadIdx.x;
+            const uint32_t t = t0 + j * NT + threadIdx.x;
             len[j] = 0;
             km[j] = 0;
             if (j < kt && t < t_end) len[j] = P.tile_len[t]; // (t_end: the end of this workgroup's run of tiles, or of the stream)
@@ -3026,7 +3061,7 @@ __device__ __forceinline__ bool scan_skip_block(DevState *st, const ScanSkipPara
                 const unsigned long long *rowp = P.sig + (size_t)s_bm.row[(k0 + kk) & (uint32_t)(KMAX - 1)] * P.sig_stride;
 #pragma unroll
                 for (uint32_t j = 0; j < (uint32_t)KTM; ++j) {
-                    const uint32_t t = ch * chunk + j * NT + threadIdx.x;
+                    const uint32_t t = t0 + j * NT + threadIdx.x;
                     w[kk][j] = (on && j < kt && t < t_end) ? rowp[t] : 0ull;
                 }
             }
@@ -3048,7 +3083,7 @@ __device__ __forceinline__ bool scan_skip_block(DevState *st, const ScanSkipPara
             uint32_t base = 0;
             if (lane == 0 && m) base = atomicAdd(&s_n, (uint32_t)__popcll(m));
             base = __builtin_amdgcn_readfirstlane(base);
-            if (mb) s_list[base + bits_below_lane(m)] = make_uint2(ch * chunk + j * NT + threadIdx.x, len[j] | (km[j] << 16));
+            if (mb) s_list[base + bits_below_lane(m)] = make_uint2(t0 + j * NT + threadIdx.x, len[j] | (km[j] << 16));
         }
         __syncthreads();
         const uint32_t n = s_n;
@@ -3163,12 +3198,37 @@ __device__ __forceinline__ bool scan_skip_block(DevState *st, const ScanSkipPara
             s_n = zero;
             s_claim = first;
         }
+        // (the launch's geometry is read from the argument segment HERE, once per chunk: nothing of it lives through the loop)
+        const uint32_t piece = Q.piece;
+        const bool more = piece != 0u;           // uniform over the grid: most launches have ONE round and never get here
+        if (DYN && more && Q.piece_ctr && threadIdx.x == 0) {
+            PieceCtrOps ops{Q.piece_ctr};
+            const uint32_t pc = yb_steal_claim(ops, Q.piece_tag);
+            s_piece = pc;
+            if (pc < Q.n_pieces) Q.piece_taken[blockIdx.x] += 1ull; // (statistics)
+        }
         __syncthreads();
+        if (!more) break;
+        const uint32_t rest0 = n_blocks * chunk; // (no wrap: n_blocks <= chunks of the stream)
+        if (DYN && Q.piece_ctr) {
+            const uint32_t pc = __builtin_amdgcn_readfirstlane(s_piece);
+            if (pc >= Q.n_pieces) break; // (checked before the multiplication: nothing to take is the usual answer)
+            t0 = rest0 + pc * piece;
+        } else {
+            if (t0 + rest0 < t0) break; // (u32 wrap)
+            t0 += rest0;
+        }
     }
     if (threadIdx.x == 0 && Q.blk_read) Q.blk_read[blockIdx.x] += n_read;
     YB_SCAN_STAMP(4);
+#ifdef YB_PROFILE_LAUNCH
+    const unsigned long long prof_tc = wall_clock64(); // (every wave of the workgroup has left the candidate loop)
+#endif
     apply_epilogue<AggV, NT>(P, C.agg, st, s_cnt, wave_sites, wave_freed, lane);
     YB_SCAN_STAMP(7);
+#ifdef YB_PROFILE_LAUNCH
+    YB_LAUNCH_WG_END(prof_it, n_read, prof_tc);
+#endif
     YB_LAUNCH_END(prof_it);
     return true;
 }
