@@ -232,7 +232,17 @@ int yabpe_memcpy_h2d(yabpe_ctx *ctx, void *dst_dev, const void *src_host, uint64
  * straight to yabpe_load_words (no copy; add YABPE_LOAD_DEDUP to pool equal pre-tokens, trainer.py:221-225).
  * Malformed UTF-8: returns YABPE_E_UTF8 and *out_bad_pos = UnicodeDecodeError.start of the first bad chunk (:156-161).
  * The character classes (\p{L}, \p{N}, \s) are those of the third-party `regex` module the reference uses
- * (csrc/unicode_classes.inc, generated by tools/gen_unicode_classes.py). */
+ * (csrc/unicode_classes.inc, generated by tools/gen_unicode_classes.py).
+ * Digit groups: option "digit_group" (yabpe_set_option; 0, the default: the GPT-2 pattern as it is; G in 1 .. 255: \p{N}+ is
+ * replaced by \p{N}{1,G}, the digit rule of the GPT-4 / Llama-3 family (G = 3) and of the single-digit family (G = 1)).  The
+ * option is read by every yabpe_pretokenize, yabpe_encode, yabpe_encode_spans and yabpe_encode_dropout call; any other value
+ * makes that call return YABPE_E_INVALID.  The rule, on the starts the GPT-2 pattern gives (specials included): in every
+ * pre-token that is a run of \p{N} characters (with or without the U+0020 in front) the characters are numbered 0, 1, 2, ..
+ * from the first digit, and a new pre-token starts at every one whose number is a positive multiple of G.  Characters are
+ * counted, not bytes; a chunk start and the end of a special start a new run.  With G >= 1 a special token whose first
+ * character is \p{N} is rejected (YABPE_E_INVALID, the message names it): it could match at a group boundary, where the
+ * GPT-2 pattern has no token start.  The pass costs three more kernels (linear in the text whatever it holds, a file of
+ * digits included); with 0 nothing is launched or allocated for it. */
 int yabpe_pretokenize(yabpe_ctx *ctx, const uint8_t *text, uint64_t n_bytes, const uint64_t *chunk_off, uint32_t n_chunks,
                       const uint8_t *special_bytes, const uint32_t *special_off, uint32_t n_special,
                       const uint8_t **out_dev_text, uint64_t **out_dev_word_off, uint64_t *out_n_words, int64_t *out_bad_pos);
@@ -297,7 +307,10 @@ int yabpe_encode_set_model(yabpe_ctx *ctx, const uint8_t *vocab_bytes, const uin
  * ascending; text host or device memory), each exactly as a separate BBPETokenizer.encode call would.  Results (device
  * memory owned by the library, released by yabpe_encode_free, the next yabpe_encode or yabpe_destroy): *out_dev_ids =
  * *out_n_ids u32 ids, *out_dev_doc_off = n_docs + 1 offsets into them.  Malformed UTF-8: YABPE_E_UTF8 and *out_bad_pos =
- * UnicodeDecodeError.start of the whole text.  More than 2^32 - 1 pre-tokens in one call: YABPE_E_CAPACITY. */
+ * UnicodeDecodeError.start of the whole text.  More than 2^32 - 1 pre-tokens in one call: YABPE_E_CAPACITY.
+ * Option "digit_group" (see yabpe_pretokenize): the pre-tokens of the text between the specials are those of the grouped
+ * pattern, in yabpe_encode, yabpe_encode_spans and yabpe_encode_dropout alike -- BBPETokenizer(digit_group=G).  The specials
+ * are split out first and every piece between them is a text of its own, so here a special may begin with a digit. */
 int yabpe_encode(yabpe_ctx *ctx, const uint8_t *text, uint64_t n_bytes, const uint64_t *doc_off, uint32_t n_docs,
                  uint32_t **out_dev_ids, uint64_t **out_dev_doc_off, uint64_t *out_n_ids, int64_t *out_bad_pos);
 /* yabpe_encode that also says which piece of its document every id was made from.  Arguments, errors and ownership are

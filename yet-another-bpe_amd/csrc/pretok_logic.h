@@ -212,9 +212,12 @@ YB_HD bool pt_special_is_head(const PtView &v, const PtSpecials &sp, OccF occ, u
     return true;
 }
 
-// Resolves the chain headed by the occurrence `o0` at i, left to right, and writes the flags it changes.
+// Resolves the chain headed by the occurrence `o0` at i, left to right, and writes the flags it changes.  `inside`: the
+// value for the bytes of a taken special after its first -- 0 (no start), or a mark that a later pass turns into 0
+// (group_logic.h: GRP_INSIDE).
 template <class OccF>
-YB_HD void pt_special_walk(const PtView &v, const PtSpecials &sp, OccF occ, uint8_t *flags, uint64_t i, uint32_t o0) {
+YB_HD void pt_special_walk(const PtView &v, const PtSpecials &sp, OccF occ, uint8_t *flags, uint64_t i, uint32_t o0,
+                           uint8_t inside = 0) {
     int64_t cover = -1;        // end of the last special that was taken
     uint64_t q = i;
     uint32_t oq = o0;
@@ -227,7 +230,7 @@ YB_HD void pt_special_walk(const PtView &v, const PtSpecials &sp, OccF occ, uint
         else taken = pt_is_start(v, q, cover >= 0 && (int64_t)q <= cover + 3 ? cover : -1);
         if (taken) {
             flags[q] = 1;
-            for (uint32_t k = 1; k < len; ++k) flags[q + k] = 0;
+            for (uint32_t k = 1; k < len; ++k) flags[q + k] = inside;
             cover = (int64_t)(q + len);
             // a token starts right after the match; redo the (at most 3) positions a contraction there can reach
             for (uint64_t j = (uint64_t)cover; j < (uint64_t)cover + 4 && j < v.n; ++j) {

@@ -888,6 +888,25 @@ int check_starts(yabpe_ctx *c, const uint64_t *starts, uint32_t n, uint64_t limi
 // =================================================================================================== C ABI
 extern "C" {
 
+// The option "digit_group" (group_logic.h), read by every call that pre-tokenises: 0 (GPT-2's \p{N}+) or G in [1, 255].
+static int digit_group_opt(yabpe_ctx *c, uint32_t *G) {
+    const int64_t v = optv(c, "digit_group", 0);
+    if (v < 0 || v > (int64_t)GRP_MAX) return fail(c, YABPE_E_INVALID, "option digit_group is %lld: 0 (off) or a group of 1 .. 255 digits", (long long)v);
+    *G = (uint32_t)v;
+    return YABPE_OK;
+}
+
+// the pre-tokeniser's class of one code point, from the runs the class table is built from
+static uint8_t class_of(uint32_t cp) {
+    unsigned lo = 0, hi = YB_UNICODE_CLASS_NRUNS; // the last run that starts at or below cp
+    while (hi - lo > 1) {
+        const unsigned mid = (lo + hi) / 2;
+        if (YB_UNICODE_CLASS_RUNS[mid][0] <= cp) lo = mid;
+        else hi = mid;
+    }
+    return YB_UNICODE_CLASS_RUNS[lo][0] <= cp ? (uint8_t)YB_UNICODE_CLASS_RUNS[lo][1] : (uint8_t)PT_O;
+}
+
 // the class per code point of the pre-tokeniser (unicode_classes.inc expanded), built on first use
 static int class_table(yabpe_ctx *c) {
     if (c->pt_cls) return 0;
@@ -2411,6 +2430,17 @@ int yabpe_pretokenize(yabpe_ctx *c, const uint8_t *text, uint64_t n_bytes, const
             return fail(c, YABPE_E_INVALID, "special token %u is empty (it would match at every position)", s);
         max_len = std::max(max_len, special_off[s + 1] - special_off[s]);
     }
+    uint32_t G = 0;
+    TRY(digit_group_opt(c, &G));
+    for (uint32_t s = 0; G && s < n_special; ++s) { // group_logic.h: such a special could match where no GPT-2 token starts
+        const uint8_t *b = special_bytes + special_off[s];
+        const uint64_t len = special_off[s + 1] - special_off[s];
+        const PtView v{b, nullptr, len, 0};
+        uint32_t cp = 0;
+        if (pt_decode(v, 0, len, &cp) && class_of(cp) == PT_N)
+            return fail(c, YABPE_E_INVALID, "special token %u (\"%.*s\") begins with a \\p{N} character: not allowed with digit_group = %u", s,
+                        (int)std::min<uint64_t>(len, 64), (const char *)b, G);
+    }
     std::vector<unsigned long long> chunks;
     if (chunk_off && n_chunks) {
         for (uint32_t k = 0; k < n_chunks; ++k) {
@@ -2441,7 +2471,7 @@ int yabpe_pretokenize(yabpe_ctx *c, const uint8_t *text, uint64_t n_bytes, const
         sp.off = d_spo;
     }
     PretokOut po{};
-    if (pretokenize(c->stream, d_text, n_bytes, d_chunks, (uint32_t)chunks.size(), c->pt_cls, sp, &po) != 0)
+    if (pretokenize(c->stream, d_text, n_bytes, d_chunks, (uint32_t)chunks.size(), c->pt_cls, sp, G, &po) != 0)
         return fail(c, YABPE_E_HIP, "pre-tokeniser failed: %s", hipGetErrorString(hipGetLastError()));
     if (po.bad_pos >= 0) {
         *out_bad_pos = po.bad_pos;
@@ -2724,7 +2754,9 @@ static int encode_front(yabpe_ctx *c, Scratch &S, const uint8_t *d_text, unsigne
                         int64_t *out_bad_pos, EncFront *F) {
     hipStream_t s = c->stream;
     const uint32_t grid = (uint32_t)std::min<unsigned long long>((n + BLOCK - 1) / BLOCK, 1u << 20);
-    // ---- split: document marks, the special split, classes / UTF-8 / pre-token starts
+    uint32_t G = 0;
+    TRY(digit_group_opt(c, &G));
+    // ---- split: document marks, the special split, classes / UTF-8 / pre-token starts, digit groups
     uint8_t *meta = nullptr, *flags = nullptr, *sflag = nullptr;
     unsigned long long *err = nullptr;
     HIPCHK(c, S.get(&meta, n));
@@ -2741,10 +2773,11 @@ static int encode_front(yabpe_ctx *c, Scratch &S, const uint8_t *d_text, unsigne
         hipLaunchKernelGGL(k_enc_special, dim3(grid), dim3(BLOCK), 0, s, d_text, meta, n, sp, sflag);
         hipLaunchKernelGGL(k_enc_segments, dim3(grid), dim3(BLOCK), 0, s, sflag, n, meta);
     }
-    PretokParams P{d_text, meta, flags, n, c->pt_cls, err, PtSpecials{nullptr, nullptr, 0, 0}};
+    PretokParams P{d_text, meta, flags, n, c->pt_cls, err, PtSpecials{nullptr, nullptr, 0, 0}, 0};
     const uint32_t wgrid = (uint32_t)std::min<unsigned long long>((n + PT_WIN - 1) / PT_WIN, 1u << 20);
     hipLaunchKernelGGL(k_pt_fused, dim3(wgrid), dim3(BLOCK), 0, s, P);
-    if (sflag) hipLaunchKernelGGL(k_enc_clear, dim3(grid), dim3(BLOCK), 0, s, sflag, n, flags);
+    if (sflag) hipLaunchKernelGGL(k_enc_clear, dim3(grid), dim3(BLOCK), 0, s, sflag, n, flags, (uint8_t)(G ? GRP_INSIDE : 0));
+    if (G && pt_group(s, S, meta, flags, n, G) != 0) return fail(c, YABPE_E_HIP, "digit groups failed: %s", hipGetErrorString(hipGetLastError()));
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipEventRecord(c->enc_ev[1], s));
     unsigned long long h_err = 0;
@@ -2773,6 +2806,8 @@ static int encode_run(yabpe_ctx *c, const uint8_t *text, uint64_t n_bytes, const
     if (spans) *out_dev_spans = nullptr;
     if (span_flags & ~YABPE_SPANS_CHARS) return fail(c, YABPE_E_INVALID, "unknown flags 0x%x", span_flags);
     if (!c->have_enc_model) return fail(c, YABPE_E_INVALID, "no model: call yabpe_encode_set_model first");
+    uint32_t G_checked = 0;
+    TRY(digit_group_opt(c, &G_checked)); // (also when there is no text to split)
     if (n_bytes && !text) return fail(c, YABPE_E_INVALID, "text is NULL");
     TRY(check_starts(c, doc_off, n_docs, n_bytes, "text"));
     yabpe_encode_free(c);
@@ -2947,6 +2982,8 @@ int yabpe_encode_dropout(yabpe_ctx *c, const uint8_t *text, uint64_t n_bytes, co
     *out_dev_ids = nullptr; *out_dev_doc_off = nullptr; *out_n_ids = 0; *out_bad_pos = -1;
     if (threshold > ENC_DROP_ALL) return fail(c, YABPE_E_INVALID, "threshold %llu: at most 2^32 (p = 1)", (unsigned long long)threshold);
     if (!c->have_enc_model) return fail(c, YABPE_E_INVALID, "no model: call yabpe_encode_set_model first");
+    uint32_t G_checked = 0;
+    TRY(digit_group_opt(c, &G_checked)); // (also when there is no text to split)
     if (n_bytes && !text) return fail(c, YABPE_E_INVALID, "text is NULL");
     TRY(check_starts(c, doc_off, n_docs, n_bytes, "text"));
     yabpe_encode_free(c);

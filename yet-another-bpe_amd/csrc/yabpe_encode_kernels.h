@@ -3,7 +3,8 @@
 // Passes (host orchestration: yabpe_encode in yabpe.hip):
 //   split     k_pt_mark_chunks (document starts) -> k_enc_special (sflag: the tokenizer's special split) -> k_enc_segments
 //             (every special span and every text between spans becomes a text of its own) -> k_pt_fused (classes, UTF-8,
-//             pre-token starts) -> k_enc_clear (no start inside a special)
+//             pre-token starts) -> k_enc_clear (no start inside a special) -> with the option "digit_group": k_grp_windows /
+//             k_grp_carry / k_grp_apply (digit runs cut into groups, yabpe_pretok_kernels.h)
 //   pretok    k_pt_count / exclusive_scan / k_pt_scatter: starts -> u64 pre-token offsets into the text
 //   pool      k_word_hash / k_word_dedup / k_dedup_flags + scans: each pre-token's representative (unique word), then
 //             k_enc_compact lists the unique words and the scratch each long one needs
@@ -49,9 +50,10 @@ __global__ __launch_bounds__(BLOCK) void k_enc_segments(const uint8_t *sflag, un
         if (enc_segment_start(sflag, i)) meta[i] |= PT_CHUNK0;
 }
 
-__global__ __launch_bounds__(BLOCK) void k_enc_clear(const uint8_t *sflag, unsigned long long n, uint8_t *flags) {
+// (inside: 0, or GRP_INSIDE when the grouping pass follows -- it turns the mark into 0, group_logic.h)
+__global__ __launch_bounds__(BLOCK) void k_enc_clear(const uint8_t *sflag, unsigned long long n, uint8_t *flags, uint8_t inside) {
     for (unsigned long long i = (unsigned long long)blockIdx.x * BLOCK + threadIdx.x; i < n; i += (unsigned long long)gridDim.x * BLOCK)
-        if (sflag[i] == ENC_INSIDE) flags[i] = 0;
+        if (sflag[i] == ENC_INSIDE) flags[i] = inside;
 }
 
 // ulist[u] = the pre-token that represents unique word u; llen[u] = its length when it takes the sequential (long) path

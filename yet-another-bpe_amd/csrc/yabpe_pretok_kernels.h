@@ -10,11 +10,14 @@
 //               k_pt_fused     text -> meta (class, continuation, UTF-8 validation: first malformed byte by atomicMin)
 //                                      and flags, through an LDS window per workgroup
 //               k_pt_special   text, meta -> corrected flags (only when special tokens are configured)
+//               k_grp_windows / k_grp_carry / k_grp_apply   meta, flags -> flags with digit runs cut into groups (only with
+//                                      the option "digit_group" >= 1; group_logic.h)
 //               k_pt_count / k_pt_scatter   flags -> offsets
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "group_logic.h"
 #include "pretok_logic.h"
 #include "yabpe_aux_kernels.h"
 
@@ -30,6 +33,8 @@ struct PretokParams {
     const uint8_t *cls;       // class per code point (0x110000 entries)
     unsigned long long *err;  // smallest malformed byte position (atomicMin), ~0 = none
     PtSpecials sp;
+    uint8_t inside;           // what k_pt_special writes on the bytes of a taken special after its first: 0, or GRP_INSIDE
+                              // when the grouping pass follows (it has to tell them from the digits of a digit run)
 };
 
 __global__ __launch_bounds__(BLOCK) void k_pt_mark_chunks(uint8_t *meta, const unsigned long long *chunk_off, uint32_t n_chunks,
@@ -157,8 +162,152 @@ __global__ __launch_bounds__(BLOCK) void k_pt_special(PretokParams P) {
     };
     for (unsigned long long i = (unsigned long long)blockIdx.x * BLOCK + threadIdx.x; i < P.n; i += (unsigned long long)gridDim.x * BLOCK) {
         const uint32_t o = occ(i);
-        if (o && pt_special_is_head(v, sp, occ, i)) pt_special_walk(v, sp, occ, P.flags, i, o);
+        if (o && pt_special_is_head(v, sp, occ, i)) pt_special_walk(v, sp, occ, P.flags, i, o, P.inside);
     }
+}
+
+// ---------------------------------------------------------------- digit groups (rules and states: group_logic.h)
+// Whether a pre-token starts at a digit depends on how many digits of its run stand in front of it, however many that
+// is: a segmented scan over the text, in three steps of linear work.  A thread owns GRP_PIECE = 16 bytes (one 16-B load
+// of meta and of flags, kept in registers), a workgroup a window of PT_WIN bytes.
+//   k_grp_windows   per window: the combined state of its bytes (does it hold a start; digits counted after the last one)
+//   k_grp_carry     one workgroup: exclusive scan of the window states in place (n / PT_WIN of them) -> the state in front
+//                   of every window
+//   k_grp_apply     per window: exclusive scan of the piece states behind that carry, then every thread walks its piece
+//                   and writes its 16 final flags
+// Every read of the flags as k_pt_fused / k_pt_special / k_enc_clear left them happens in the first two kernels or, in
+// k_grp_apply, by the one thread that afterwards writes those same 16 bytes: a start this pass adds is never taken for
+// one it should count from.
+static_assert(PT_WIN == GRP_WIN && PT_WIN == BLOCK * GRP_PIECE, "one piece per thread, one window per workgroup");
+
+struct GrpPiece {
+    uint32_t m[4], f[4]; // 16 meta bytes, 16 flag bytes
+    __device__ __forceinline__ void get(int k, uint8_t *meta, uint8_t *flag) const {
+        *meta = (uint8_t)(m[k >> 2] >> ((k & 3) * 8));
+        *flag = (uint8_t)(f[k >> 2] >> ((k & 3) * 8));
+    }
+};
+
+// the piece at byte g (a multiple of 16); bytes past the text read as meta PT_O, flag 0
+__device__ __forceinline__ GrpPiece grp_load(const uint8_t *meta, const uint8_t *flags, unsigned long long g, unsigned long long n) {
+    GrpPiece p;
+    if (g + GRP_PIECE <= n) {
+        const uint4 a = *reinterpret_cast<const uint4 *>(meta + g), b = *reinterpret_cast<const uint4 *>(flags + g);
+        p.m[0] = a.x; p.m[1] = a.y; p.m[2] = a.z; p.m[3] = a.w;
+        p.f[0] = b.x; p.f[1] = b.y; p.f[2] = b.z; p.f[3] = b.w;
+    } else {
+#pragma unroll
+        for (int w = 0; w < 4; ++w) {
+            p.m[w] = PT_O * 0x01010101u;
+            p.f[w] = 0u;
+        }
+#pragma unroll
+        for (int k = 0; k < GRP_PIECE; ++k)
+            if (g + k < n) {
+                const int sh = (k & 3) * 8;
+                p.m[k >> 2] = (p.m[k >> 2] & ~(0xFFu << sh)) | ((uint32_t)meta[g + k] << sh);
+                p.f[k >> 2] |= (uint32_t)flags[g + k] << sh;
+            }
+    }
+    return p;
+}
+
+// Exclusive scan of one state per thread over the workgroup, in thread order; *total = all of them combined.  s_w: WPB
+// states in LDS, free again after the next __syncthreads().
+__device__ __forceinline__ GrpState grp_block_scan(GrpState mine, uint32_t G, GrpState *s_w, GrpState *total) {
+    const int lane = threadIdx.x & 63, wib = threadIdx.x >> 6;
+    GrpState inc = mine;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const GrpState u = __shfl_up(inc, o);
+        if (lane >= o) inc = grp_combine(u, inc, G);
+    }
+    const GrpState up = __shfl_up(inc, 1);
+    if (lane == 63) s_w[wib] = inc;
+    __syncthreads();
+    GrpState before = 0, all = 0;
+#pragma unroll
+    for (int w = 0; w < WPB; ++w) {
+        if (w == wib) before = all;
+        all = grp_combine(all, s_w[w], G);
+    }
+    *total = all;
+    return lane ? grp_combine(before, up, G) : before;
+}
+
+__global__ __launch_bounds__(BLOCK) void k_grp_windows(const uint8_t *meta, const uint8_t *flags, unsigned long long n, uint32_t G,
+                                                       GrpState *win) {
+    __shared__ GrpState s_w[WPB];
+    const unsigned long long n_win = (n + PT_WIN - 1) / PT_WIN;
+    for (unsigned long long w = blockIdx.x; w < n_win; w += gridDim.x) {
+        const GrpPiece p = grp_load(meta, flags, w * PT_WIN + (unsigned long long)threadIdx.x * GRP_PIECE, n);
+        const GrpState mine = grp_piece_state([&](int k, uint8_t *m, uint8_t *f) { p.get(k, m, f); }, G);
+        GrpState total;
+        (void)grp_block_scan(mine, G, s_w, &total);
+        if (threadIdx.x == 0) win[w] = total;
+        __syncthreads();
+    }
+}
+
+// win[w] = the states of windows 0 .. w - 1 combined (one workgroup; a tile of BLOCK * GRP_CARRY_ITEMS states per iteration)
+constexpr int GRP_CARRY_ITEMS = 8;
+__global__ __launch_bounds__(BLOCK) void k_grp_carry(GrpState *win, unsigned long long n_win, uint32_t G) {
+    __shared__ GrpState s_w[WPB];
+    GrpState carry = 0;
+    for (unsigned long long t0 = 0; t0 < n_win; t0 += BLOCK * GRP_CARRY_ITEMS) {
+        const unsigned long long base = t0 + (unsigned long long)threadIdx.x * GRP_CARRY_ITEMS;
+        GrpState v[GRP_CARRY_ITEMS], mine = 0;
+#pragma unroll
+        for (int k = 0; k < GRP_CARRY_ITEMS; ++k) {
+            v[k] = base + k < n_win ? win[base + k] : 0u;
+            mine = grp_combine(mine, v[k], G);
+        }
+        GrpState total;
+        GrpState run = grp_combine(carry, grp_block_scan(mine, G, s_w, &total), G);
+#pragma unroll
+        for (int k = 0; k < GRP_CARRY_ITEMS; ++k) {
+            if (base + k < n_win) win[base + k] = run;
+            run = grp_combine(run, v[k], G);
+        }
+        carry = grp_combine(carry, total, G);
+        __syncthreads();
+    }
+}
+
+__global__ __launch_bounds__(BLOCK) void k_grp_apply(const uint8_t *meta, uint8_t *flags, unsigned long long n, uint32_t G,
+                                                     const GrpState *win) {
+    __shared__ GrpState s_w[WPB];
+    const unsigned long long n_win = (n + PT_WIN - 1) / PT_WIN;
+    for (unsigned long long w = blockIdx.x; w < n_win; w += gridDim.x) {
+        const unsigned long long g = w * PT_WIN + (unsigned long long)threadIdx.x * GRP_PIECE;
+        const GrpPiece p = grp_load(meta, flags, g, n);
+        auto get = [&](int k, uint8_t *m, uint8_t *f) { p.get(k, m, f); };
+        GrpState total;
+        const GrpState before = grp_combine(win[w], grp_block_scan(grp_piece_state(get, G), G, s_w, &total), G);
+        uint32_t o[4] = {0u, 0u, 0u, 0u};
+        grp_piece_flags(before, get, [&](int k, uint8_t f) { o[k >> 2] |= (uint32_t)f << ((k & 3) * 8); }, G);
+        if (g + GRP_PIECE <= n) {
+            *reinterpret_cast<uint4 *>(flags + g) = make_uint4(o[0], o[1], o[2], o[3]);
+        } else {
+#pragma unroll
+            for (int k = 0; k < GRP_PIECE; ++k)
+                if (g + k < n) flags[g + k] = (uint8_t)(o[k >> 2] >> ((k & 3) * 8));
+        }
+        __syncthreads();
+    }
+}
+
+// The three steps on meta / flags of n > 0 bytes, left in flight on s.  G in [1, GRP_MAX].  The window states belong to S.
+inline int pt_group(hipStream_t s, Scratch &S, const uint8_t *meta, uint8_t *flags, unsigned long long n, uint32_t G) {
+    const unsigned long long n_win = (n + PT_WIN - 1) / PT_WIN;
+    GrpState *win = nullptr;
+    YB_RET(S.get(&win, n_win));
+    const uint32_t wgrid = (uint32_t)std::min<unsigned long long>(n_win, 1u << 20);
+    hipLaunchKernelGGL(k_grp_windows, dim3(wgrid), dim3(BLOCK), 0, s, meta, (const uint8_t *)flags, n, G, win);
+    hipLaunchKernelGGL(k_grp_carry, dim3(1), dim3(BLOCK), 0, s, win, n_win, G);
+    hipLaunchKernelGGL(k_grp_apply, dim3(wgrid), dim3(BLOCK), 0, s, meta, flags, n, G, (const GrpState *)win);
+    YB_RET(hipGetLastError());
+    return 0;
 }
 
 // flags -> offsets, pass 1: number of starts per workgroup of PT_PER_BLOCK bytes
@@ -235,9 +384,10 @@ inline int pt_offsets(hipStream_t s, Scratch &S, const uint8_t *flags, const uns
 }
 
 // Runs all passes on `text` (device).  chunk_off: device array of n_chunks chunk starts.  cls: device class table.
+// digit_group: 0, or G of group_logic.h (no special may then begin with a \p{N} character: the caller checks).
 // Scratch (meta, flags) is allocated and released here; out->off is the caller's to free (dev_free).
 inline int pretokenize(hipStream_t s, const uint8_t *text, unsigned long long n, const unsigned long long *chunk_off, uint32_t n_chunks,
-                       const uint8_t *cls, const PtSpecials &sp_dev, PretokOut *out) {
+                       const uint8_t *cls, const PtSpecials &sp_dev, uint32_t digit_group, PretokOut *out) {
     *out = PretokOut{nullptr, 0, -1};
     Scratch S;
     unsigned long long *off = nullptr;
@@ -256,7 +406,7 @@ inline int pretokenize(hipStream_t s, const uint8_t *text, unsigned long long n,
     YB_RET(hipMemsetAsync(meta, 0, n, s));
     YB_RET(hipMemsetAsync(err, 0xff, 8, s));
     const uint32_t grid = (uint32_t)std::min<unsigned long long>((n + BLOCK - 1) / BLOCK, 1u << 20);
-    PretokParams P{text, meta, flags, n, cls, err, sp_dev};
+    PretokParams P{text, meta, flags, n, cls, err, sp_dev, (uint8_t)(digit_group ? GRP_INSIDE : 0)};
     hipLaunchKernelGGL(k_pt_mark_chunks, dim3((n_chunks + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, s, meta, chunk_off, n_chunks, n);
     const uint32_t wgrid = (uint32_t)std::min<unsigned long long>((n + PT_WIN - 1) / PT_WIN, 1u << 20);
     hipLaunchKernelGGL(k_pt_fused, dim3(wgrid), dim3(BLOCK), 0, s, P);
@@ -268,6 +418,7 @@ inline int pretokenize(hipStream_t s, const uint8_t *text, unsigned long long n,
         return 0;
     }
     if (sp_dev.n) hipLaunchKernelGGL(k_pt_special, dim3(grid), dim3(BLOCK), 0, s, P);
+    if (digit_group && pt_group(s, S, meta, flags, n, digit_group) != 0) return -1;
     unsigned long long total = 0;
     if (pt_offsets(s, S, flags, n, ~0ull, &off, &total) != 0) return -1;
     YB_RET(hipStreamSynchronize(s));

@@ -29,6 +29,32 @@ import regex
 
 # GPT-2 pre-tokenisation pattern (reference trainer.py:163)
 _GPT2_SPLIT = r"""'(?:[sdmt]|ll|ve|re)| ?\p{L}+| ?\p{N}+| ?[^\s\p{L}\p{N}]+|\s+(?!\S)|\s+"""
+PRETOKENIZER_FILE = "pretokenizer.json"  # {"digit_group": G}, written next to a saved model only when a group is set
+
+
+def split_pattern(group: int | None = None) -> str:
+    """The GPT-2 pattern; with a digit group G, \\p{N}+ replaced by \\p{N}{1,G} (the one place where the byte-level BPEs after
+    GPT-2 differ from it: groups of up to three digits, or single digits)."""
+    return _GPT2_SPLIT if not group else _GPT2_SPLIT.replace(r"\p{N}+", r"\p{N}{1,%d}" % group, 1)
+
+
+def read_digit_group(model_dir: str | Path) -> int | None:
+    """The digit group a saved model was trained with: pretokenizer.json in its directory, None when there is none."""
+    f = Path(model_dir) / PRETOKENIZER_FILE
+    if not f.exists():
+        return None
+    with open(f, encoding="utf-8") as fh:
+        return check_digit_group(json.load(fh).get("digit_group")) or None
+
+
+def check_digit_group(n) -> int:
+    """A digit group as the library's option `digit_group` (0: none).  ValueError for anything but None or an integer from 1
+    to 255; bool is not an integer here."""
+    if n is None:
+        return 0
+    if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or not 1 <= n <= 255:
+        raise ValueError(f"digit_group must be None or an integer from 1 to 255, got {n!r}")
+    return int(n)
 
 
 @dataclass
@@ -48,6 +74,12 @@ class BBPETrainerConfig:
             when none of those is left or the best of them is below min_frequency.  Special tokens are vocabulary entries,
             not merges, and may be longer; the merges of a model that train_from continues are replayed as they are.  The
             limit is NOT stored by save / save_lossless: a train_from that should keep it needs it in its own config.
+        digit_group: None: the GPT-2 pattern as it is (a digit run of any length is one pre-token); an integer G from 1 to
+            255: \\p{N}+ of the pattern becomes \\p{N}{1,G}, so a digit run is cut after every G characters, counted from its
+            first digit (3: the digit rule of the GPT-4 / Llama-3 family, 1: single digits) and no learned token holds more
+            than G digits.  Part of the model: train and train_from set BBPEModel.digit_group, save / save_lossless store it
+            (pretokenizer.json) and BBPETokenizer reads it.  With a group no special token may begin with a \\p{N}
+            character (ValueError): it could match at a group boundary, where the device rule never looks.
     """
 
     vocab_size: int = 32000
@@ -57,6 +89,7 @@ class BBPETrainerConfig:
     seed: int = 42
     special_tokens: Sequence[str] = field(default_factory=lambda: ["[PAD]", "[UNK]", "[BOS]", "[EOS]"])
     max_token_length: int | None = None
+    digit_group: int | None = None
 
 
 def max_token_bytes(config: BBPETrainerConfig) -> int:
@@ -70,14 +103,26 @@ def max_token_bytes(config: BBPETrainerConfig) -> int:
     return int(n)
 
 
+def digit_group(config: BBPETrainerConfig) -> int:
+    """config.digit_group as the library's option `digit_group` (0: none), checked together with the special tokens."""
+    group = check_digit_group(getattr(config, "digit_group", None))
+    if group:
+        for tok in config.special_tokens:
+            if regex.match(r"\p{N}", tok):
+                raise ValueError(f"special token {tok!r} begins with a digit (\\p{{N}}): not allowed with digit_group = {group}")
+    return group
+
+
 class BBPEModel:
-    """Result container (reference trainer.py:41-52): copies of vocab, merges, special tokens."""
+    """Result container (reference trainer.py:41-52): copies of vocab, merges, special tokens; digit_group (not in the
+    reference): the digit group of the pre-tokenisation the model was trained with, None for the GPT-2 pattern."""
 
     def __init__(self, vocab: Mapping[bytes, int], merges: Sequence[tuple[bytes, bytes]],
-                 special_tokens: Sequence[str]) -> None:
+                 special_tokens: Sequence[str], digit_group: int | None = None) -> None:
         self.vocab: dict[bytes, int] = dict(vocab)
         self.merges: list[tuple[bytes, bytes]] = list(merges)
         self.special_tokens: list[str] = list(special_tokens)
+        self.digit_group: int | None = check_digit_group(digit_group) or None
 
     @classmethod
     def from_file_lossless(cls, model_dir: str | Path) -> "BBPEModel":
@@ -96,7 +141,7 @@ class BBPEModel:
         if (d / "special_tokens.json").exists():
             with open(d / "special_tokens.json", encoding="utf-8") as f:
                 specials = list(json.load(f))
-        return cls(vocab=vocab, merges=merges, special_tokens=specials)
+        return cls(vocab=vocab, merges=merges, special_tokens=specials, digit_group=read_digit_group(d))
 
 
 def _utf8_cut(window: bytes, pos: int) -> int:
@@ -160,18 +205,23 @@ class BBPETrainer:
 
     def _context(self):
         """A device context for a merge loop of this trainer: the maximum token length, when set, goes in as an option before
-        any words are loaded (the library reads it at the load)."""
+        any words are loaded (the library reads it at the load), the digit group before any text is pre-tokenised."""
         from . import _native  # fails loudly when libyabpe.so / a GPU is missing
 
-        limit = max_token_bytes(self.config)
+        limit, group = max_token_bytes(self.config), digit_group(self.config)
         ctx = _native.Context()
-        if limit:
-            try:
+        try:
+            if limit:
                 ctx.set_option("max_token_bytes", limit)
-            except BaseException:
-                ctx.close()
-                raise
+            if group:
+                ctx.set_option("digit_group", group)
+        except BaseException:
+            ctx.close()
+            raise
         return ctx
+
+    def _model(self, vocab, merges) -> BBPEModel:
+        return BBPEModel(vocab=vocab, merges=merges, special_tokens=list(self.config.special_tokens), digit_group=self.config.digit_group)
 
     # ------------------------------------------------------------------ train / save (trainer.py:63-117)
     def train(self, files: Sequence[str | Path], batch_bytes: int | None = None) -> BBPEModel:
@@ -179,6 +229,7 @@ class BBPETrainer:
         the device pre-tokeniser in batches of whole chunks of at most that many bytes and their pre-tokens are pooled on
         the device batch by batch -- for corpora larger than host or device memory.  The model is the same."""
         max_token_bytes(self.config)  # (a bad limit fails before any file is read or any device call is made)
+        digit_group(self.config)      # (and so does a bad digit group, or a special it does not allow)
         if not files:
             raise ValueError("At least one file must be provided")
         paths = [Path(f) if isinstance(f, str) else f for f in files]
@@ -191,11 +242,10 @@ class BBPETrainer:
         if mode == "gpu" or (mode == "auto" and sum(p.stat().st_size for p in paths if p.exists()) >= (1 << 20)):
             return self._train_device(paths)
         pretokens = self._pretokenize(paths)
-        specials = list(self.config.special_tokens)
         if not pretokens:  # empty corpus: base vocab only (trainer.py:81-85)
             self._vocab = self._init_base_vocab()
             self._merges = []
-            return BBPEModel(vocab=self._vocab, merges=[], special_tokens=specials)
+            return self._model(self._vocab, [])
         # word-frequency pooling (trainer.py:221-225) on the host: the pre-tokens are Python strings here anyway
         if os.environ.get("YABPE_LAYOUT", "dedup") == "flat":
             words = [t.encode("utf-8") for t in pretokens]
@@ -207,18 +257,17 @@ class BBPETrainer:
         vocab, merges = self._merge_loop_words(words, freq)
         self._vocab = vocab
         self._merges = merges
-        return BBPEModel(vocab=vocab, merges=merges, special_tokens=specials)
+        return self._model(vocab, merges)
 
     def _train_device(self, paths: Sequence[Path]) -> BBPEModel:
         """train() with the pre-tokeniser on the GPU: file bytes -> yabpe_pretokenize -> word offsets in HBM ->
         yabpe_load_words (equal pre-tokens pooled on the device) -> merge loop.  Same results as the host path."""
         from . import _native  # fails loudly when libyabpe.so / a GPU is missing
 
-        specials = list(self.config.special_tokens)
         text, chunks, total = self._gather_text(paths)
         base = self._base_tokens()
         num_merges = max(0, self.config.vocab_size - len(base))
-        empty = BBPEModel(vocab={t: i for i, t in enumerate(base)}, merges=[], special_tokens=specials)
+        empty = self._model({t: i for i, t in enumerate(base)}, [])
         if total == 0:
             self._vocab, self._merges = dict(empty.vocab), []
             return empty
@@ -234,7 +283,7 @@ class BBPETrainer:
         vocab, merges = self._decode_merges(base, left, right, merged)
         self._vocab = vocab
         self._merges = merges
-        return BBPEModel(vocab=vocab, merges=merges, special_tokens=specials)
+        return self._model(vocab, merges)
 
     # ------------------------------------------------------------------ batched device path (the context's word pool)
     @staticmethod
@@ -293,11 +342,10 @@ class BBPETrainer:
         yabpe_pool_get -> yabpe_load_words (the pool's counts; nothing left to pool) -> merge loop."""
         from . import _native  # fails loudly when libyabpe.so / a GPU is missing
 
-        specials = list(self.config.special_tokens)
         chunks = self._file_chunks(paths)
         base = self._base_tokens()
         num_merges = max(0, self.config.vocab_size - len(base))
-        empty = BBPEModel(vocab={t: i for i, t in enumerate(base)}, merges=[], special_tokens=specials)
+        empty = self._model({t: i for i, t in enumerate(base)}, [])
         if not chunks:
             self._vocab, self._merges = dict(empty.vocab), []
             return empty
@@ -315,7 +363,7 @@ class BBPETrainer:
         vocab, merges = self._decode_merges(base, left, right, merged)
         self._vocab = vocab
         self._merges = merges
-        return BBPEModel(vocab=vocab, merges=merges, special_tokens=specials)
+        return self._model(vocab, merges)
 
     def _gather_text(self, paths: Sequence[Path]):
         """The files' chunks joined into one u8 buffer (None when empty), each chunk as (start in the buffer, file, start in
@@ -382,17 +430,20 @@ class BBPETrainer:
         config.max_token_length constrains only the merges learned here: the model's own merges are replayed whatever their
         length (the limit is not part of a saved model)."""
         max_token_bytes(self.config)  # (a bad limit fails before any file is read or any device call is made)
+        digit_group(self.config)      # (and so does a bad digit group, or a special it does not allow)
         if not files:
             raise ValueError("At least one file must be provided")
         paths = [Path(f) if isinstance(f, str) else f for f in files]
+        if getattr(model, "digit_group", None) != (self.config.digit_group or None):
+            raise ValueError(f"cannot continue from this model: it was trained with digit_group = {getattr(model, 'digit_group', None)!r}, "
+                             f"the trainer's is {self.config.digit_group!r} (its merges would be replayed over words it never saw)")
         toks, triples = self._resumable(model)
-        specials = list(self.config.special_tokens)
         old_merges = [(bytes(l), bytes(r)) for l, r in model.merges]
         num_merges = max(0, self.config.vocab_size - len(self._base_tokens()) - len(old_merges))
 
         def unchanged() -> BBPEModel:
             self._vocab, self._merges = dict(model.vocab), list(old_merges)
-            return BBPEModel(vocab=self._vocab, merges=self._merges, special_tokens=specials)
+            return self._model(self._vocab, self._merges)
 
         for path in paths:
             if not path.exists():
@@ -445,7 +496,7 @@ class BBPETrainer:
                 self.last_stats = ctx.stats()
         vocab, new_merges = self._decode_merges(toks, left, right, merged)
         self._vocab, self._merges = vocab, old_merges + new_merges
-        return BBPEModel(vocab=self._vocab, merges=self._merges, special_tokens=specials)
+        return self._model(self._vocab, self._merges)
 
     @staticmethod
     def _decode_merges(base: Sequence[bytes], left, right, merged):
@@ -458,7 +509,8 @@ class BBPETrainer:
         return {t: i for i, t in enumerate(toks)}, merges
 
     def save(self, output_dir: str | Path) -> None:
-        """vocab.json / merges.txt / special_tokens.json in the reference's format (trainer.py:94-117)."""
+        """vocab.json / merges.txt / special_tokens.json in the reference's format (trainer.py:94-117); with a digit group
+        also pretokenizer.json ({"digit_group": G})."""
         if not self._vocab:
             raise ValueError("Model has not been trained yet. Call train() first.")
         out = Path(output_dir)
@@ -470,6 +522,17 @@ class BBPETrainer:
                 f.write(f"{left.decode('latin-1')} {right.decode('latin-1')}\n")
         with open(out / "special_tokens.json", "w", encoding="utf-8") as f:
             json.dump(list(self.config.special_tokens), f, ensure_ascii=False, indent=2)
+        self._save_pretokenizer(out)
+
+    def _save_pretokenizer(self, out: Path) -> None:
+        """pretokenizer.json, only when the model was trained with a digit group (without one the directory holds exactly
+        the files it always held; a file left there by an earlier save is removed)."""
+        group = digit_group(self.config)
+        if group:
+            with open(out / PRETOKENIZER_FILE, "w", encoding="utf-8") as f:
+                json.dump({"digit_group": group}, f)
+        elif (out / PRETOKENIZER_FILE).exists():
+            (out / PRETOKENIZER_FILE).unlink()
 
     def save_lossless(self, output_dir: str | Path) -> None:
         """The same model in a format that survives a reload byte for byte: `vocab.hex.json` ({token hex: id}),
@@ -488,6 +551,7 @@ class BBPETrainer:
                 f.write(f"{left.hex()} {right.hex()}\n")
         with open(out / "special_tokens.json", "w", encoding="utf-8") as f:
             json.dump(list(self.config.special_tokens), f, ensure_ascii=False, indent=2)
+        self._save_pretokenizer(out)
 
     # ------------------------------------------------------------------ base vocab (trainer.py:119-134)
     def _base_tokens(self) -> list[bytes]:
@@ -514,7 +578,7 @@ class BBPETrainer:
             return chunk_ranges(size, self.config.chunk_size_bytes, read)
 
     def _split_pattern(self) -> "regex.Pattern[str]":
-        pat = _GPT2_SPLIT
+        pat = split_pattern(digit_group(self.config))
         if self.config.special_tokens:  # specials first, in config order, kept as words (trainer.py:165-167)
             pat = "|".join(regex.escape(t) for t in self.config.special_tokens) + "|" + pat
         return regex.compile(pat)
