@@ -196,6 +196,12 @@ def gpu_sharded(rank, world, dist, scenario, transport="torch"):
         words = [b" " * 900, b"ab" * 700, b"xyz" * 50, b"abcabc", b"  ", b"aaa"] * 3 + [b"hello world"] * 5
         flat, off = helpers.flatten(words)
         freq, merges = None, 120
+    elif scenario == "tie_stems":  # tie-heavy stems through the batched selection: every rank must walk the same window
+        from tests import tie_helpers
+
+        flat, off = helpers.flatten(tie_helpers.stems())
+        freq, merges = None, 400
+        opts.update({"split": 1, "batch_max": 16, "cand_min_count": 1})
     else:
         raise ValueError(scenario)
     left, right, merged, count, stats = train_sharded(lambda: _native.Context(0), flat, off, freq, base, merges, 1, rank, world,

@@ -72,3 +72,42 @@ def test_golden_corpus_batches_equal_sequential_bpe(batch_sim, tmp_path, golden_
     r = subprocess.run([str(batch_sim), str(wf), "743", "16", "3"], capture_output=True, text=True, timeout=600)
     n_merges, n_batches, mismatches = _result(r)
     assert mismatches == 0 and n_merges == 743 and n_batches < 743, (r.stdout[-1000:], r.stderr[-1000:])
+
+
+# ---------------------------------------------------------------- the stem corpus of tests/tie_helpers.py: does it discriminate the rule?
+def _counters(r) -> tuple[int, int]:
+    """-> (undecided tie comparisons, tie comparisons) from the two lines in front of "mismatches"."""
+    m = re.search(r"^undecided (\d+)\ntiecmp (\d+)\nmismatches ", r.stdout, re.M)
+    assert m, r.stdout[-2000:]
+    return int(m.group(1)), int(m.group(2))
+
+
+@pytest.fixture(scope="module")
+def stems_file(tmp_path_factory):
+    from tests import helpers, tie_helpers
+
+    wf = tmp_path_factory.mktemp("stems") / "stems.bin"
+    _words_file(wf, *helpers.flatten(tie_helpers.stems()))
+    return wf
+
+
+def _stems_run(batch_sim, stems_file, variant: int):
+    r = subprocess.run([str(batch_sim), str(stems_file), "400", "16", str(variant)], capture_output=True, text=True, timeout=600)
+    return _result(r), _counters(r), r
+
+
+def test_stems_device_rule_is_exact_and_meets_undecided_comparisons(batch_sim, stems_file):
+    """Variant 3 (what the device decides): no mismatch, batches form, and the 8-byte prefixes leave tie comparisons undecided."""
+    (n_merges, n_batches, mismatches), (undecided, tiecmp), r = _stems_run(batch_sim, stems_file, 3)
+    assert mismatches == 0, r.stderr[-2000:]
+    assert 300 <= n_merges <= 400 and n_batches < n_merges
+    assert undecided > 0 and tiecmp >= undecided
+
+
+@pytest.mark.parametrize("variant,what", [(4, "undecided counts as 'sorts below'"), (5, "rule (2) skipped")])
+def test_stems_tells_a_wrong_rule_from_the_right_one(batch_sim, stems_file, variant, what):
+    """Negative controls: a subtly wrong rule predicts merges sequential BPE does not take -- on this corpus, at this size."""
+    (_n_merges, _n_batches, mismatches), (undecided, _tiecmp), r = _stems_run(batch_sim, stems_file, variant)
+    assert mismatches > 0, (what, r.stdout[-1000:])
+    if variant == 4:
+        assert undecided > 0  # (the wrong answers come from the comparisons the prefixes cannot decide)

@@ -27,6 +27,10 @@ def _expect(scenario):
     if scenario == "synthetic_tight_exchange":
         flat, off = synth.generate(synth.SynthSpec(6 << 20, 30_000, 17, bytes(range(256)), False))
         return oracle.train_flat(flat, off, 257 + 600, 1, SP)[1]
+    if scenario == "tie_stems":
+        from tests import tie_helpers
+
+        return oracle.merge_loop(tie_helpers.stems(), 257 + 400, 1, SP)[1]
     words = [b" " * 900, b"ab" * 700, b"xyz" * 50, b"abcabc", b"  ", b"aaa"] * 3 + [b"hello world"] * 5
     return oracle.merge_loop(words, 257 + 120, 1, SP)[1]
 
@@ -40,6 +44,19 @@ def test_two_ranks_one_gpu(scenario):
     assert outs[0][1] > 0 and outs[1][1] > 0  # both ranks held words
     if scenario in ("synthetic_small_buffers", "synthetic_tight_exchange"):
         assert outs[0][2] >= 1  # the overflow recovery (global recount) ran
+
+
+def test_two_ranks_walk_the_same_window():
+    """The tie-heavy stem corpus (tests/tie_helpers.py) word-sharded over two ranks and forced through the batched selection
+    with a candidate list at every count: both replicas must build the same window and cut every batch at the same place --
+    a rank that walked another one would select other merges.  Both ranks return the oracle's merges."""
+    exp = _expect("tie_stems")
+    assert 300 <= len(exp) <= 400
+    outs = dist_workers.spawn(dist_workers.gpu_sharded, 2, "tie_stems", timeout=300)
+    assert len(outs) == 2
+    for merges, n_words, rebuilds, retiles in outs:
+        assert [(bytes.fromhex(a), bytes.fromhex(b)) for a, b in merges] == exp
+        assert n_words > 0  # both ranks held words
 
 
 @pytest.mark.parametrize("world,scenario", [(2, "corpus_en_flat"), (2, "corpus_en_weighted"), (2, "synthetic_small_buffers"), (2, "synthetic_tight_exchange"),

@@ -17,6 +17,12 @@ from tests import helpers
 
 pytestmark = pytest.mark.gpu
 SP = ["<|endoftext|>"]
+# The small cases in three forms: as a job of their size runs by default (one tile: the streaming form, one merge per look, and
+# no candidate list below a best count of 16), and forced through the batched selection with a list at every count, fused
+# into the apply launch and as a launch of its own.
+FORMS = {"default": None,
+         "batch16": {"split": 1, "batch_max": 16, "cand_min_count": 1},
+         "batch16_unfused": {"split": 1, "batch_max": 16, "cand_min_count": 1, "fused": 0}}
 
 
 def gpu_train(words, freq, vocab_size, min_frequency, specials, dedup=False, options=None, want_stats=False):
@@ -36,20 +42,21 @@ def test_device_present_and_library_loaded():
     assert _native.lib().yabpe_device_count() >= 1
 
 
-@pytest.mark.parametrize("layout", ["flat", "weighted", "device_dedup"])
-def test_golden_cases(layout):
+@pytest.mark.parametrize("layout,form", [pytest.param(l, f, id=l if f == "default" else f"{l}-{f}")
+                                         for f in FORMS for l in ("flat", "weighted", "device_dedup")])
+def test_golden_cases(layout, form):
     for c in helpers.golden_cases():
         if not c["words_b"]:
             continue
         if layout == "weighted":
             uw, fq = helpers.pooled(c["words_b"])
-            vocab, merges = gpu_train(uw, fq, c["vocab_size"], c["min_frequency"], c["special_tokens"])
+            vocab, merges = gpu_train(uw, fq, c["vocab_size"], c["min_frequency"], c["special_tokens"], options=FORMS[form])
         else:
             vocab, merges = gpu_train(c["words_b"], None, c["vocab_size"], c["min_frequency"], c["special_tokens"],
-                                      dedup=(layout == "device_dedup"))
-        assert merges == c["merges_b"], (layout, c["name"])
-        assert len(vocab) == c["vocab_len"], (layout, c["name"])
-        assert {k: v for k, v in vocab.items() if v >= 256} == c["vocab_b"], (layout, c["name"])
+                                      dedup=(layout == "device_dedup"), options=FORMS[form])
+        assert merges == c["merges_b"], (layout, form, c["name"])
+        assert len(vocab) == c["vocab_len"], (layout, form, c["name"])
+        assert {k: v for k, v in vocab.items() if v >= 256} == c["vocab_b"], (layout, form, c["name"])
 
 
 @pytest.mark.parametrize("layout", ["flat", "weighted", "device_dedup"])
@@ -112,7 +119,8 @@ def test_config2_synthetic_10mib_1k_merges(golden_dir):
             assert all(count[i] >= count[i + 1] for i in range(len(count) - 1))  # best count never increases
 
 
-def test_random_small_vs_oracle():
+@pytest.mark.parametrize("form", list(FORMS))
+def test_random_small_vs_oracle(form):
     rng = random.Random(11)
     for t in range(120):
         al = rng.choice([b"ab", b"abc", b"xyz ", bytes([0, 255, 254, 1]), b"abcdefghijklmnop"])
@@ -123,9 +131,9 @@ def test_random_small_vs_oracle():
         sp = rng.choice([[], ["ab"], ["<|x|>"], ["a", "b"], ["[PAD]", "[UNK]", "[BOS]", "[EOS]"]])
         vs, mf = 256 + rng.randint(0, 120), rng.randint(1, 3)
         exp = oracle.merge_loop(words, vs, mf, sp)
-        assert gpu_train(words, None, vs, mf, sp) == exp, t
+        assert gpu_train(words, None, vs, mf, sp, options=FORMS[form]) == exp, (form, t)
         uw, fq = helpers.pooled(words)
-        assert gpu_train(uw, fq, vs, mf, sp) == exp, t
+        assert gpu_train(uw, fq, vs, mf, sp, options=FORMS[form]) == exp, (form, t)
 
 
 def test_long_words_and_runs():

@@ -13,7 +13,9 @@
 // The prediction is then checked against the sequence sequential BPE really takes (any mismatch is printed: the rule must
 // be exact), and the batch-size histogram is printed by segment of the job.
 //
-//   g++ -O2 -o /tmp/batch_sim tools/batch_sim.cpp && /tmp/batch_sim words.bin 32000 [maxbatch]
+//   g++ -O2 -o /tmp/batch_sim tools/batch_sim.cpp && /tmp/batch_sim words.bin 32000 [maxbatch] [variant]
+//   variant: 0 strict rule (1), 1 rule (1) as stated, 2 + ties by exact bytes, 3 + ties as the device decides them (use this one),
+//            4 / 5 deliberately wrong (see below).  Last lines: "undecided N", "tiecmp N", "mismatches N", "histogram: ...".
 //   words.bin: u64 n_words, u64 n_bytes, u64 off[n_words+1], u8 bytes[n_bytes]
 #include <algorithm>
 #include <cstdint>
@@ -31,6 +33,7 @@ static std::vector<std::string> tok;
 static std::unordered_map<std::string, uint32_t> vocab;
 static std::unordered_map<uint64_t, PairInfo> table;
 static std::vector<Word> words;
+static unsigned long long n_undecided = 0, n_tiecmp = 0; // tie comparisons of rule (2): those the prefixes could not decide, all
 
 static inline uint64_t K(uint32_t a, uint32_t b) { return ((uint64_t)a << 32) | b; }
 static bool lex_gt(uint64_t x, uint64_t y) { // (bytes(l), bytes(r)) of x > of y
@@ -148,17 +151,22 @@ int main(int argc, char **argv) {
                     for (uint64_t ak : acc) {
                         const uint32_t a = ak >> 32, b = (uint32_t)ak;
                         if (!(r == a || l == b)) continue;
+                        if (variant == 5) continue; // (negative control: rule (2) skipped)
                         if (variant >= 2 && cl[k].cnt == nj) {
+                            ++n_tiecmp;
                             // tie: the pairs this one can turn into reach at most nj; they block only if they would be selected before j.
                             // left token of a new pair: l itself, or the new token of an accepted merge whose b is l; right token likewise
                             // variant 2: exact byte comparison; variant 3: what the device can decide from 8-byte prefixes + lengths
+                            // variants 4 and 5 are WRONG on purpose (negative controls of tests/test_batch_rule.py, never the default):
+                            // 4 takes "cannot tell" for "sorts below", 5 skips rule (2) altogether
                             auto cmp3 = [&](const std::string &x, const std::string &y) -> int { // -1 / 0 / +1, 2 = unknown (variant 3)
                                 if (variant == 2) return x < y ? -1 : x > y ? 1 : 0;
                                 std::string xp = x.substr(0, 8), yp = y.substr(0, 8);
                                 xp.resize(8, '\0'); yp.resize(8, '\0');
                                 if (xp != yp) return xp < yp ? -1 : 1;
                                 if (x.size() <= 8 && y.size() <= 8) return x.size() < y.size() ? -1 : x.size() > y.size() ? 1 : 0;
-                                return 2;
+                                ++n_undecided;
+                                return variant == 4 ? -1 : 2;
                             };
                             auto new_gt_j = [&](const std::string &nl, const std::string &nr) { // may (nl, nr) be selected before (p, q)?
                                 const int cl_ = cmp3(nl, tok[p]);
@@ -228,6 +236,7 @@ int main(int argc, char **argv) {
             for (auto it = table.begin(); it != table.end();) { if (it->second.cnt <= 0 && it->second.words.empty()) it = table.erase(it); else ++it; }
         }
     }
+    printf("undecided %llu\ntiecmp %llu\n", n_undecided, n_tiecmp);
     printf("mismatches %llu\nhistogram:", (unsigned long long)mism);
     for (size_t k = 0; k <= maxbatch; ++k) printf(" %zu:%llu", k, (unsigned long long)hist[k]);
     printf("\n");
