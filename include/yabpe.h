@@ -242,7 +242,19 @@ int yabpe_memcpy_h2d(yabpe_ctx *ctx, void *dst_dev, const void *src_host, uint64
  * counted, not bytes; a chunk start and the end of a special start a new run.  With G >= 1 a special token whose first
  * character is \p{N} is rejected (YABPE_E_INVALID, the message names it): it could match at a group boundary, where the
  * GPT-2 pattern has no token start.  The pass costs three more kernels (linear in the text whatever it holds, a file of
- * digits included); with 0 nothing is launched or allocated for it. */
+ * digits included); with 0 nothing is launched or allocated for it.
+ * Split pattern: option "split_pattern" (yabpe_set_option; 0, the default: the GPT-2 pattern; 1: the cl100k pattern of GPT-4,
+ * Llama-3 (digit_group 3) and Qwen2 (digit_group 1),
+ *   (?i:'s|'t|'re|'ve|'m|'ll|'d)|[^\r\n\p{L}\p{N}]?\p{L}+|\p{N}{1,G}| ?[^\s\p{L}\p{N}]+[\r\n]*|\s*[\r\n]+|\s+(?!\S)|\s+
+ * with G = the option "digit_group", which must then be 1 .. 255).  Read by the same four calls; any other value, or 1 with
+ * digit_group 0, makes the call return YABPE_E_INVALID.  Against GPT-2: contractions match in either case; one character that
+ * is no letter, digit, CR or LF joins the letter run behind it; digits take no space in front; a run of punctuation swallows
+ * the CR / LF behind it, and a whitespace run that holds a CR / LF is cut after its last one (csrc/split4_logic.h has the
+ * rule per position).  With 1 a special token of yabpe_pretokenize whose first character is \s or \p{N} is rejected
+ * (YABPE_E_INVALID, the message names it): whether a token starts at a whitespace character can depend on the whole
+ * whitespace run, which is known only after the specials are placed.  The newline rules cost three more kernels in front of
+ * the digit groups (two segmented scans, linear on a file of blank lines or a newline and a gigabyte of spaces); with 0
+ * nothing of this is launched or allocated, and the GPT-2 kernels are the ones that run. */
 int yabpe_pretokenize(yabpe_ctx *ctx, const uint8_t *text, uint64_t n_bytes, const uint64_t *chunk_off, uint32_t n_chunks,
                       const uint8_t *special_bytes, const uint32_t *special_off, uint32_t n_special,
                       const uint8_t **out_dev_text, uint64_t **out_dev_word_off, uint64_t *out_n_words, int64_t *out_bad_pos);
@@ -310,7 +322,9 @@ int yabpe_encode_set_model(yabpe_ctx *ctx, const uint8_t *vocab_bytes, const uin
  * UnicodeDecodeError.start of the whole text.  More than 2^32 - 1 pre-tokens in one call: YABPE_E_CAPACITY.
  * Option "digit_group" (see yabpe_pretokenize): the pre-tokens of the text between the specials are those of the grouped
  * pattern, in yabpe_encode, yabpe_encode_spans and yabpe_encode_dropout alike -- BBPETokenizer(digit_group=G).  The specials
- * are split out first and every piece between them is a text of its own, so here a special may begin with a digit. */
+ * are split out first and every piece between them is a text of its own, so here a special may begin with a digit.
+ * Option "split_pattern" (see yabpe_pretokenize) likewise: 1 gives the pre-tokens of the cl100k pattern in all three calls --
+ * BBPETokenizer(pretokenizer="cl100k") -- and here a special may begin with whitespace too. */
 int yabpe_encode(yabpe_ctx *ctx, const uint8_t *text, uint64_t n_bytes, const uint64_t *doc_off, uint32_t n_docs,
                  uint32_t **out_dev_ids, uint64_t **out_dev_doc_off, uint64_t *out_n_ids, int64_t *out_bad_pos);
 /* yabpe_encode that also says which piece of its document every id was made from.  Arguments, errors and ownership are

@@ -896,6 +896,16 @@ static int digit_group_opt(yabpe_ctx *c, uint32_t *G) {
     return YABPE_OK;
 }
 
+// The option "split_pattern" (split4_logic.h), read by every call that pre-tokenises, after digit_group: 0 the GPT-2 pattern,
+// 1 the cl100k pattern, whose \p{N}{1,G} needs a digit group.
+static int split_pattern_opt(yabpe_ctx *c, uint32_t G, uint32_t *pattern) {
+    const int64_t v = optv(c, "split_pattern", 0);
+    if (v != 0 && v != 1) return fail(c, YABPE_E_INVALID, "option split_pattern is %lld: 0 (GPT-2) or 1 (cl100k)", (long long)v);
+    if (v == 1 && G == 0) return fail(c, YABPE_E_INVALID, "option split_pattern is 1 (cl100k): digit_group must be 1 .. 255, it is 0");
+    *pattern = (uint32_t)v;
+    return YABPE_OK;
+}
+
 // the pre-tokeniser's class of one code point, from the runs the class table is built from
 static uint8_t class_of(uint32_t cp) {
     unsigned lo = 0, hi = YB_UNICODE_CLASS_NRUNS; // the last run that starts at or below cp
@@ -2430,8 +2440,9 @@ int yabpe_pretokenize(yabpe_ctx *c, const uint8_t *text, uint64_t n_bytes, const
             return fail(c, YABPE_E_INVALID, "special token %u is empty (it would match at every position)", s);
         max_len = std::max(max_len, special_off[s + 1] - special_off[s]);
     }
-    uint32_t G = 0;
+    uint32_t G = 0, pattern = 0;
     TRY(digit_group_opt(c, &G));
+    TRY(split_pattern_opt(c, G, &pattern));
     for (uint32_t s = 0; G && s < n_special; ++s) { // group_logic.h: such a special could match where no GPT-2 token starts
         const uint8_t *b = special_bytes + special_off[s];
         const uint64_t len = special_off[s + 1] - special_off[s];
@@ -2440,6 +2451,10 @@ int yabpe_pretokenize(yabpe_ctx *c, const uint8_t *text, uint64_t n_bytes, const
         if (pt_decode(v, 0, len, &cp) && class_of(cp) == PT_N)
             return fail(c, YABPE_E_INVALID, "special token %u (\"%.*s\") begins with a \\p{N} character: not allowed with digit_group = %u", s,
                         (int)std::min<uint64_t>(len, 64), (const char *)b, G);
+        // split4_logic.h: whether a token starts at a whitespace character can be open until the scan pass has run
+        if (pattern && pt_decode(v, 0, len, &cp) && class_of(cp) == PT_S)
+            return fail(c, YABPE_E_INVALID, "special token %u (\"%.*s\") begins with a \\s character: not allowed with split_pattern = 1", s,
+                        (int)std::min<uint64_t>(len, 64), (const char *)b);
     }
     std::vector<unsigned long long> chunks;
     if (chunk_off && n_chunks) {
@@ -2471,7 +2486,7 @@ int yabpe_pretokenize(yabpe_ctx *c, const uint8_t *text, uint64_t n_bytes, const
         sp.off = d_spo;
     }
     PretokOut po{};
-    if (pretokenize(c->stream, d_text, n_bytes, d_chunks, (uint32_t)chunks.size(), c->pt_cls, sp, G, &po) != 0)
+    if (pretokenize(c->stream, d_text, n_bytes, d_chunks, (uint32_t)chunks.size(), c->pt_cls, sp, G, pattern, &po) != 0)
         return fail(c, YABPE_E_HIP, "pre-tokeniser failed: %s", hipGetErrorString(hipGetLastError()));
     if (po.bad_pos >= 0) {
         *out_bad_pos = po.bad_pos;
@@ -2754,8 +2769,9 @@ static int encode_front(yabpe_ctx *c, Scratch &S, const uint8_t *d_text, unsigne
                         int64_t *out_bad_pos, EncFront *F) {
     hipStream_t s = c->stream;
     const uint32_t grid = (uint32_t)std::min<unsigned long long>((n + BLOCK - 1) / BLOCK, 1u << 20);
-    uint32_t G = 0;
+    uint32_t G = 0, pattern = 0;
     TRY(digit_group_opt(c, &G));
+    TRY(split_pattern_opt(c, G, &pattern));
     // ---- split: document marks, the special split, classes / UTF-8 / pre-token starts, digit groups
     uint8_t *meta = nullptr, *flags = nullptr, *sflag = nullptr;
     unsigned long long *err = nullptr;
@@ -2775,8 +2791,10 @@ static int encode_front(yabpe_ctx *c, Scratch &S, const uint8_t *d_text, unsigne
     }
     PretokParams P{d_text, meta, flags, n, c->pt_cls, err, PtSpecials{nullptr, nullptr, 0, 0}, 0};
     const uint32_t wgrid = (uint32_t)std::min<unsigned long long>((n + PT_WIN - 1) / PT_WIN, 1u << 20);
-    hipLaunchKernelGGL(k_pt_fused, dim3(wgrid), dim3(BLOCK), 0, s, P);
+    if (pattern) hipLaunchKernelGGL(k_pt4_fused, dim3(wgrid), dim3(BLOCK), 0, s, P);
+    else hipLaunchKernelGGL(k_pt_fused, dim3(wgrid), dim3(BLOCK), 0, s, P);
     if (sflag) hipLaunchKernelGGL(k_enc_clear, dim3(grid), dim3(BLOCK), 0, s, sflag, n, flags, (uint8_t)(G ? GRP_INSIDE : 0));
+    if (pattern && pt_newlines(s, S, meta, flags, n) != 0) return fail(c, YABPE_E_HIP, "newline rules failed: %s", hipGetErrorString(hipGetLastError()));
     if (G && pt_group(s, S, meta, flags, n, G) != 0) return fail(c, YABPE_E_HIP, "digit groups failed: %s", hipGetErrorString(hipGetLastError()));
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipEventRecord(c->enc_ev[1], s));
@@ -2808,6 +2826,8 @@ static int encode_run(yabpe_ctx *c, const uint8_t *text, uint64_t n_bytes, const
     if (!c->have_enc_model) return fail(c, YABPE_E_INVALID, "no model: call yabpe_encode_set_model first");
     uint32_t G_checked = 0;
     TRY(digit_group_opt(c, &G_checked)); // (also when there is no text to split)
+    uint32_t pattern_checked = 0;
+    TRY(split_pattern_opt(c, G_checked, &pattern_checked));
     if (n_bytes && !text) return fail(c, YABPE_E_INVALID, "text is NULL");
     TRY(check_starts(c, doc_off, n_docs, n_bytes, "text"));
     yabpe_encode_free(c);
@@ -2984,6 +3004,8 @@ int yabpe_encode_dropout(yabpe_ctx *c, const uint8_t *text, uint64_t n_bytes, co
     if (!c->have_enc_model) return fail(c, YABPE_E_INVALID, "no model: call yabpe_encode_set_model first");
     uint32_t G_checked = 0;
     TRY(digit_group_opt(c, &G_checked)); // (also when there is no text to split)
+    uint32_t pattern_checked = 0;
+    TRY(split_pattern_opt(c, G_checked, &pattern_checked));
     if (n_bytes && !text) return fail(c, YABPE_E_INVALID, "text is NULL");
     TRY(check_starts(c, doc_off, n_docs, n_bytes, "text"));
     yabpe_encode_free(c);

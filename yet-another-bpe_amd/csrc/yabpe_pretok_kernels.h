@@ -13,12 +13,15 @@
 //               k_grp_windows / k_grp_carry / k_grp_apply   meta, flags -> flags with digit runs cut into groups (only with
 //                                      the option "digit_group" >= 1; group_logic.h)
 //               k_pt_count / k_pt_scatter   flags -> offsets
+// With the option "split_pattern" = 1 (the cl100k pattern, split4_logic.h) the first two are k_pt4_fused / k_pt4_special,
+// and k_nl_windows / k_nl_carry / k_nl_apply (the newline rules: two segmented scans) run in front of the digit groups.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "group_logic.h"
 #include "pretok_logic.h"
+#include "split4_logic.h"
 #include "yabpe_aux_kernels.h"
 
 namespace yb {
@@ -48,9 +51,12 @@ __global__ __launch_bounds__(BLOCK) void k_pt_mark_chunks(uint8_t *meta, const u
 // then decides the start flag of every byte of the window from LDS.  The text is read from HBM once, meta and flags are
 // written once, 16 B per lane.  The rules are the same functions the CPU model runs, on an LDS view (PtView::org).
 constexpr int PT_WIN = BLOCK * 16; // bytes per workgroup and iteration
-constexpr int PT_HALO = 16;        // >= reach of the rules: 7 bytes back (contraction + previous character), 4 ahead
+constexpr int PT_HALO = 16;        // >= reach of the rules: 7 bytes back (contraction + previous character; cl100k: 11), 4 ahead
 constexpr int PT_LDS = PT_HALO + PT_WIN + PT_HALO;
-__global__ __launch_bounds__(BLOCK) void k_pt_fused(PretokParams P) {
+// PAT 0: the GPT-2 rules; PAT 1: the cl100k rules (split4_logic.h; they look 11 bytes back, meta gets PT4_NL, a flag can
+// be PT4_PENDING).
+template <int PAT>
+__device__ __forceinline__ void pt_fused_body(const PretokParams &P) {
     __shared__ __attribute__((aligned(16))) uint8_t s_text[PT_LDS];
     __shared__ __attribute__((aligned(16))) uint8_t s_meta[PT_LDS];
     __shared__ __attribute__((aligned(16))) uint8_t s_tmp[PT_LDS]; // classes, then flags
@@ -92,8 +98,8 @@ __global__ __launch_bounds__(BLOCK) void k_pt_fused(PretokParams P) {
         const PtView v{first ? s_text + PT_HALO : s_text, first ? s_meta + PT_HALO : s_meta, P.n, vorg};
         uint8_t *tmp = first ? s_tmp + PT_HALO : s_tmp;   // tmp[pos - vorg]
         uint8_t *meta_w = first ? s_meta + PT_HALO : s_meta;
-        // ---- classify the window + 8 bytes on each side (what the start rules can look at)
-        const long long c_lo = (long long)base - 8, c_hi = (long long)base + PT_WIN + 8; // [c_lo, c_hi)
+        // ---- classify the window + 8 bytes on each side (cl100k: 12 in front): what the start rules can look at
+        const long long c_lo = (long long)base - (PAT ? 12 : 8), c_hi = (long long)base + PT_WIN + 8; // [c_lo, c_hi)
         {
             unsigned long long bad_pos = ~0ull;
             for (long long pos = c_lo + threadIdx.x; pos < c_hi; pos += BLOCK) { // (consecutive lanes, consecutive bytes)
@@ -116,12 +122,14 @@ __global__ __launch_bounds__(BLOCK) void k_pt_fused(PretokParams P) {
             if (pos < 0 || (unsigned long long)pos >= P.n) continue;
             const unsigned long long k = (unsigned long long)pos - vorg;
             meta_w[k] = (uint8_t)((meta_w[k] & PT_CHUNK0) | tmp[k]);
+            if (PAT && pt4_is_nl(v.T((unsigned long long)pos))) meta_w[k] |= PT4_NL;
         }
         __syncthreads();
         // ---- start flags of the window (tmp is free again), then meta and flags go out as 16-B pieces
         for (int k = threadIdx.x; k < PT_WIN; k += BLOCK) {
             const unsigned long long j = base + k;
-            tmp[j - vorg] = j < P.n ? (pt_is_start(v, j, -1) ? 1 : 0) : 0;
+            if (PAT) tmp[j - vorg] = j < P.n ? pt4_is_start(v, j, -1) : 0;
+            else tmp[j - vorg] = j < P.n ? (pt_is_start(v, j, -1) ? 1 : 0) : 0;
         }
         __syncthreads();
         {
@@ -141,10 +149,14 @@ __global__ __launch_bounds__(BLOCK) void k_pt_fused(PretokParams P) {
     }
 }
 
+__global__ __launch_bounds__(BLOCK) void k_pt_fused(PretokParams P) { pt_fused_body<0>(P); }
+__global__ __launch_bounds__(BLOCK) void k_pt4_fused(PretokParams P) { pt_fused_body<1>(P); }
+
 // Special tokens: one pass.  A 256-bit set of the specials' first bytes keeps nearly every thread out of the compare;
 // a thread that finds an occurrence checks whether it heads its chain (occurrences before it are looked up on demand,
 // through the same filter) and, if so, resolves the whole chain (pretok_logic.h).
-__global__ __launch_bounds__(BLOCK) void k_pt_special(PretokParams P) {
+template <int PAT>
+__device__ __forceinline__ void pt_special_body(const PretokParams &P) {
     __shared__ uint32_t s_first[8];
     if (threadIdx.x < 8) s_first[threadIdx.x] = 0u;
     __syncthreads();
@@ -162,9 +174,16 @@ __global__ __launch_bounds__(BLOCK) void k_pt_special(PretokParams P) {
     };
     for (unsigned long long i = (unsigned long long)blockIdx.x * BLOCK + threadIdx.x; i < P.n; i += (unsigned long long)gridDim.x * BLOCK) {
         const uint32_t o = occ(i);
-        if (o && pt_special_is_head(v, sp, occ, i)) pt_special_walk(v, sp, occ, P.flags, i, o, P.inside);
+        if (PAT) {
+            if (o && pt4_special_is_head(v, sp, occ, i)) pt4_special_walk(v, sp, occ, P.flags, i, o);
+        } else {
+            if (o && pt_special_is_head(v, sp, occ, i)) pt_special_walk(v, sp, occ, P.flags, i, o, P.inside);
+        }
     }
 }
+
+__global__ __launch_bounds__(BLOCK) void k_pt_special(PretokParams P) { pt_special_body<0>(P); }
+__global__ __launch_bounds__(BLOCK) void k_pt4_special(PretokParams P) { pt_special_body<1>(P); }
 
 // ---------------------------------------------------------------- digit groups (rules and states: group_logic.h)
 // Whether a pre-token starts at a digit depends on how many digits of its run stand in front of it, however many that
@@ -310,6 +329,140 @@ inline int pt_group(hipStream_t s, Scratch &S, const uint8_t *meta, uint8_t *fla
     return 0;
 }
 
+// ---------------------------------------------------------------- newline rules of the cl100k pattern (split4_logic.h)
+// Whether a whitespace character behind a newline starts a pre-token (PT4_PENDING) depends on the whole whitespace run around
+// it, however long: two segmented scans, one in each direction, in the three steps and the geometry of the digit groups.
+//   k_nl_windows   per window: one word with both summaries (what the window does to B behind it, to F in front of it)
+//   k_nl_carry     one workgroup: the forward summaries scanned left to right, the backward ones right to left, in place ->
+//                  per window the value of everything in front of it (bits 0-1) and of everything behind it (bits 2-3)
+//   k_nl_apply     per window: both scans over the pieces between those carries, then every thread resolves its 16 flags
+// As in the digit groups, a piece's flags are read as the passes before left them by the thread that then writes them.
+
+// Exclusive scans of one state per thread over the workgroup: bits 0-1 over the threads in front (thread order), bits 2-3
+// over the threads behind (nearest last).  *total: all of them, in both senses.  s_w: 2 * WPB words.
+__device__ __forceinline__ NlState nl_block_scan(NlState mine, uint32_t *s_w, NlState *total) {
+    const int lane = threadIdx.x & 63, wib = threadIdx.x >> 6;
+    uint32_t f = mine & NL_MASK, b = mine >> NL_BWD;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const uint32_t uf = __shfl_up(f, o), ub = __shfl_down(b, o);
+        if (lane >= o) f = nl_comb(uf, f);
+        if (lane + o < 64) b = nl_comb(ub, b);
+    }
+    const uint32_t pf = __shfl_up(f, 1), pb = __shfl_down(b, 1);
+    if (lane == 63) s_w[wib] = f;
+    if (lane == 0) s_w[WPB + wib] = b;
+    __syncthreads();
+    uint32_t bf = NL_KEEP, af = NL_KEEP, bb = NL_KEEP, ab = NL_KEEP;
+#pragma unroll
+    for (int w = 0; w < WPB; ++w) {
+        if (w == wib) bf = af;
+        af = nl_comb(af, s_w[w]);
+    }
+#pragma unroll
+    for (int w = WPB - 1; w >= 0; --w) {
+        if (w == wib) bb = ab;
+        ab = nl_comb(ab, s_w[WPB + w]);
+    }
+    *total = af | (ab << NL_BWD);
+    const uint32_t ef = lane ? nl_comb(bf, pf) : bf, eb = lane < 63 ? nl_comb(bb, pb) : bb;
+    return ef | (eb << NL_BWD);
+}
+
+__global__ __launch_bounds__(BLOCK) void k_nl_windows(const uint8_t *meta, const uint8_t *flags, unsigned long long n, NlState *win) {
+    __shared__ uint32_t s_w[2 * WPB];
+    const unsigned long long n_win = (n + PT_WIN - 1) / PT_WIN;
+    for (unsigned long long w = blockIdx.x; w < n_win; w += gridDim.x) {
+        const GrpPiece p = grp_load(meta, flags, w * PT_WIN + (unsigned long long)threadIdx.x * GRP_PIECE, n);
+        NlState total;
+        (void)nl_block_scan(nl_piece_state(nl_piece(p.m, p.f)), s_w, &total);
+        if (threadIdx.x == 0) win[w] = total;
+        __syncthreads();
+    }
+}
+
+// In place.  A thread reads and writes the same BLOCK-strided words in both halves: no word passes between threads through memory.
+constexpr int NL_CARRY_ITEMS = 8;
+constexpr unsigned long long NL_CARRY_TILE = (unsigned long long)BLOCK * NL_CARRY_ITEMS;
+__global__ __launch_bounds__(BLOCK) void k_nl_carry(NlState *win, unsigned long long n_win) {
+    __shared__ uint32_t s_w[2 * WPB];
+    const unsigned long long n_tiles = (n_win + NL_CARRY_TILE - 1) / NL_CARRY_TILE;
+    uint32_t carry = NL_KEEP;
+    for (unsigned long long t = 0; t < n_tiles; ++t) { // forward: left to right
+        const unsigned long long base = t * NL_CARRY_TILE + (unsigned long long)threadIdx.x * NL_CARRY_ITEMS;
+        uint32_t v[NL_CARRY_ITEMS], mine = NL_KEEP;
+#pragma unroll
+        for (int k = 0; k < NL_CARRY_ITEMS; ++k) {
+            v[k] = base + k < n_win ? win[base + k] : 0u;
+            mine = nl_comb(mine, v[k] & NL_MASK);
+        }
+        NlState total;
+        uint32_t run = nl_comb(carry, nl_block_scan(mine, s_w, &total) & NL_MASK);
+#pragma unroll
+        for (int k = 0; k < NL_CARRY_ITEMS; ++k) {
+            if (base + k < n_win) win[base + k] = (v[k] & ~NL_MASK) | run;
+            run = nl_comb(run, v[k] & NL_MASK);
+        }
+        carry = nl_comb(carry, total & NL_MASK);
+        __syncthreads();
+    }
+    carry = NL_KEEP;
+    for (unsigned long long t = n_tiles; t-- > 0;) { // backward: right to left, the nearest window last
+        const unsigned long long base = t * NL_CARRY_TILE + (unsigned long long)threadIdx.x * NL_CARRY_ITEMS;
+        uint32_t v[NL_CARRY_ITEMS], mine = NL_KEEP;
+#pragma unroll
+        for (int k = NL_CARRY_ITEMS - 1; k >= 0; --k) {
+            v[k] = base + k < n_win ? win[base + k] : 0u;
+            mine = nl_comb(mine, (v[k] >> NL_BWD) & NL_MASK);
+        }
+        NlState total;
+        uint32_t run = nl_comb(carry, nl_block_scan(mine << NL_BWD, s_w, &total) >> NL_BWD);
+#pragma unroll
+        for (int k = NL_CARRY_ITEMS - 1; k >= 0; --k) {
+            if (base + k < n_win) win[base + k] = (v[k] & NL_MASK) | (run << NL_BWD);
+            run = nl_comb(run, (v[k] >> NL_BWD) & NL_MASK);
+        }
+        carry = nl_comb(carry, total >> NL_BWD);
+        __syncthreads();
+    }
+}
+
+__global__ __launch_bounds__(BLOCK) void k_nl_apply(const uint8_t *meta, uint8_t *flags, unsigned long long n, const NlState *win) {
+    __shared__ uint32_t s_w[2 * WPB];
+    const unsigned long long n_win = (n + PT_WIN - 1) / PT_WIN;
+    for (unsigned long long w = blockIdx.x; w < n_win; w += gridDim.x) {
+        const unsigned long long g = w * PT_WIN + (unsigned long long)threadIdx.x * GRP_PIECE;
+        const GrpPiece p = grp_load(meta, flags, g, n);
+        const NlPiece q = nl_piece(p.m, p.f);
+        NlState total;
+        const NlState in = nl_block_scan(nl_piece_state(q), s_w, &total), edge = win[w];
+        const uint32_t before = nl_comb(edge & NL_MASK, in & NL_MASK), after = nl_comb(edge >> NL_BWD, in >> NL_BWD);
+        uint32_t o[4] = {p.f[0], p.f[1], p.f[2], p.f[3]};
+        nl_piece_flags(before, after, q, o);
+        if (g + GRP_PIECE <= n) {
+            *reinterpret_cast<uint4 *>(flags + g) = make_uint4(o[0], o[1], o[2], o[3]);
+        } else {
+#pragma unroll
+            for (int k = 0; k < GRP_PIECE; ++k)
+                if (g + k < n) flags[g + k] = (uint8_t)(o[k >> 2] >> ((k & 3) * 8));
+        }
+        __syncthreads();
+    }
+}
+
+// The three steps on meta / flags of n > 0 bytes, left in flight on s.  The window states belong to S.
+inline int pt_newlines(hipStream_t s, Scratch &S, const uint8_t *meta, uint8_t *flags, unsigned long long n) {
+    const unsigned long long n_win = (n + PT_WIN - 1) / PT_WIN;
+    NlState *win = nullptr;
+    YB_RET(S.get(&win, n_win));
+    const uint32_t wgrid = (uint32_t)std::min<unsigned long long>(n_win, 1u << 20);
+    hipLaunchKernelGGL(k_nl_windows, dim3(wgrid), dim3(BLOCK), 0, s, meta, (const uint8_t *)flags, n, win);
+    hipLaunchKernelGGL(k_nl_carry, dim3(1), dim3(BLOCK), 0, s, win, n_win);
+    hipLaunchKernelGGL(k_nl_apply, dim3(wgrid), dim3(BLOCK), 0, s, meta, flags, n, (const NlState *)win);
+    YB_RET(hipGetLastError());
+    return 0;
+}
+
 // flags -> offsets, pass 1: number of starts per workgroup of PT_PER_BLOCK bytes
 __global__ __launch_bounds__(BLOCK) void k_pt_count(const uint8_t *flags, unsigned long long n, unsigned long long *block_sums) {
     __shared__ uint32_t s_w[WPB];
@@ -385,9 +538,10 @@ inline int pt_offsets(hipStream_t s, Scratch &S, const uint8_t *flags, const uns
 
 // Runs all passes on `text` (device).  chunk_off: device array of n_chunks chunk starts.  cls: device class table.
 // digit_group: 0, or G of group_logic.h (no special may then begin with a \p{N} character: the caller checks).
+// pattern: 0 GPT-2, 1 cl100k (split4_logic.h; digit_group >= 1, and no special begins with \s either: the caller checks).
 // Scratch (meta, flags) is allocated and released here; out->off is the caller's to free (dev_free).
 inline int pretokenize(hipStream_t s, const uint8_t *text, unsigned long long n, const unsigned long long *chunk_off, uint32_t n_chunks,
-                       const uint8_t *cls, const PtSpecials &sp_dev, uint32_t digit_group, PretokOut *out) {
+                       const uint8_t *cls, const PtSpecials &sp_dev, uint32_t digit_group, uint32_t pattern, PretokOut *out) {
     *out = PretokOut{nullptr, 0, -1};
     Scratch S;
     unsigned long long *off = nullptr;
@@ -409,7 +563,8 @@ inline int pretokenize(hipStream_t s, const uint8_t *text, unsigned long long n,
     PretokParams P{text, meta, flags, n, cls, err, sp_dev, (uint8_t)(digit_group ? GRP_INSIDE : 0)};
     hipLaunchKernelGGL(k_pt_mark_chunks, dim3((n_chunks + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, s, meta, chunk_off, n_chunks, n);
     const uint32_t wgrid = (uint32_t)std::min<unsigned long long>((n + PT_WIN - 1) / PT_WIN, 1u << 20);
-    hipLaunchKernelGGL(k_pt_fused, dim3(wgrid), dim3(BLOCK), 0, s, P);
+    if (pattern) hipLaunchKernelGGL(k_pt4_fused, dim3(wgrid), dim3(BLOCK), 0, s, P);
+    else hipLaunchKernelGGL(k_pt_fused, dim3(wgrid), dim3(BLOCK), 0, s, P);
     unsigned long long h_err = 0;
     YB_RET(hipMemcpyAsync(&h_err, err, 8, hipMemcpyDeviceToHost, s));
     YB_RET(hipStreamSynchronize(s));
@@ -417,7 +572,11 @@ inline int pretokenize(hipStream_t s, const uint8_t *text, unsigned long long n,
         out->bad_pos = (long long)h_err;
         return 0;
     }
-    if (sp_dev.n) hipLaunchKernelGGL(k_pt_special, dim3(grid), dim3(BLOCK), 0, s, P);
+    if (sp_dev.n) {
+        if (pattern) hipLaunchKernelGGL(k_pt4_special, dim3(grid), dim3(BLOCK), 0, s, P);
+        else hipLaunchKernelGGL(k_pt_special, dim3(grid), dim3(BLOCK), 0, s, P);
+    }
+    if (pattern && pt_newlines(s, S, meta, flags, n) != 0) return -1;
     if (digit_group && pt_group(s, S, meta, flags, n, digit_group) != 0) return -1;
     unsigned long long total = 0;
     if (pt_offsets(s, S, flags, n, ~0ull, &off, &total) != 0) return -1;

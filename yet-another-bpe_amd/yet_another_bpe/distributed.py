@@ -156,9 +156,9 @@ def train_text_sharded(ctx_factory, files, config, rank: int, world: int, transp
     from pathlib import Path
 
     from . import _native
-    from .trainer import BBPEModel, BBPETrainer, digit_group, max_token_bytes
+    from .trainer import PRETOKENIZERS, BBPEModel, BBPETrainer, max_token_bytes, pretokenizer
 
-    limit, group = max_token_bytes(config), digit_group(config)  # (ValueError before any file is read)
+    limit, (pattern, group) = max_token_bytes(config), pretokenizer(config)  # (ValueError before any file is read)
     tr = BBPETrainer(config)
     paths = [Path(f) for f in files]
     for p in paths:
@@ -181,6 +181,8 @@ def train_text_sharded(ctx_factory, files, config, rank: int, world: int, transp
             ctx.set_option("max_token_bytes", limit)
         if group:  # config.digit_group: the same on every rank, so every rank cuts its chunks' digit runs alike
             ctx.set_option("digit_group", group)
+        if pattern:  # config.pretokenizer: likewise
+            ctx.set_option("split_pattern", pattern)
         ctx.set_vocab(base)
         attach(ctx, rank, world, transport)
         err = None
@@ -207,7 +209,7 @@ def train_text_sharded(ctx_factory, files, config, rank: int, world: int, transp
             ctx.load_words(np.zeros(0, np.uint8), np.zeros(1, np.uint64), None, dedup=True)  # no words here: same layout as the peers
         left, right, merged, _count = ctx.train(num_merges, int(config.min_frequency))
     vocab, merges = BBPETrainer._decode_merges(base, left, right, merged)
-    return BBPEModel(vocab=vocab, merges=merges, special_tokens=specials, digit_group=group or None)
+    return BBPEModel(vocab=vocab, merges=merges, special_tokens=specials, digit_group=group or None, pretokenizer=PRETOKENIZERS[pattern])
 
 
 def train_device_text_sharded(ctx_factory, make_text, config, rank: int, world: int, transport: str = "rccl", options: dict | None = None):
@@ -215,9 +217,9 @@ def train_device_text_sharded(ctx_factory, make_text, config, rank: int, world: 
     `make_text(ctx) -> (dev_ptr, n_bytes)` runs on every rank; the chunk cuts are the reference's (config.chunk_size_bytes),
     this rank pre-tokenises ITS chunks, pools the pre-tokens and joins the collective merge loop.
     Returns (left, right, merged, count, stats, n_pretokens_here)."""
-    from .trainer import BBPETrainer, chunk_ranges, digit_group, max_token_bytes
+    from .trainer import BBPETrainer, chunk_ranges, max_token_bytes, pretokenizer
 
-    limit, group = max_token_bytes(config), digit_group(config)
+    limit, (pattern, group) = max_token_bytes(config), pretokenizer(config)
     tr = BBPETrainer(config)
     base = tr._base_tokens()
     specials = list(config.special_tokens)
@@ -229,6 +231,8 @@ def train_device_text_sharded(ctx_factory, make_text, config, rank: int, world: 
             ctx.set_option("max_token_bytes", limit)
         if group:  # config.digit_group: the same on every rank, so every rank cuts its chunks' digit runs alike
             ctx.set_option("digit_group", group)
+        if pattern:  # config.pretokenizer: likewise
+            ctx.set_option("split_pattern", pattern)
         ctx.set_vocab(base)
         attach(ctx, rank, world, transport)
         ptr, n_bytes = make_text(ctx)

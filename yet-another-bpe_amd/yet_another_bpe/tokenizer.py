@@ -25,7 +25,7 @@ import numpy as np
 import regex
 
 from .synth import rnd_int
-from .trainer import check_digit_group, read_digit_group, split_pattern
+from .trainer import CL100K_DIGIT_GROUP, PRETOKENIZERS, check_digit_group, check_pretokenizer, read_pretokenizer, split_pattern
 
 _WORD_CACHE = 8192
 
@@ -33,18 +33,20 @@ _WORD_CACHE = 8192
 class BBPETokenizer:
     """Applies learned merges, lowest rank first (leftmost on ties), to GPT-2 pre-tokens; with digit_group = G (1 .. 255; not
     in the reference) to the pre-tokens of the pattern whose \\p{N}+ is \\p{N}{1,G} -- the pre-tokenisation of a model trained
-    with BBPETrainerConfig(digit_group=G).  Every method, plain Python or on the GPU, follows it."""
+    with BBPETrainerConfig(digit_group=G); with pretokenizer = "cl100k" to those of the GPT-4 / Llama-3 pattern (digit_group
+    None: 3).  Every method, plain Python or on the GPU, follows it."""
 
     def __init__(self, vocab: dict[bytes, int] | None = None, merges: list[tuple[bytes, bytes]] | None = None,
-                 special_tokens: list[str] | None = None, digit_group: int | None = None) -> None:
+                 special_tokens: list[str] | None = None, digit_group: int | None = None, pretokenizer: str = "gpt2") -> None:
         self._vocab: dict[bytes, int] = vocab or {}
         self._vocab_inv: dict[int, bytes] = {i: t for t, i in self._vocab.items()}
         self._merges: list[tuple[bytes, bytes]] = merges or []
         self._special_tokens: list[str] = special_tokens or []
         self._special_set = frozenset(self._special_tokens)
         self._rank: dict[tuple[bytes, bytes], int] = {pair: i for i, pair in enumerate(self._merges)}
-        self._digit_group: int | None = check_digit_group(digit_group) or None
-        self._pattern = regex.compile(split_pattern(self._digit_group))
+        self._pretokenizer: str = PRETOKENIZERS[check_pretokenizer(pretokenizer)]
+        self._digit_group: int | None = check_digit_group(digit_group) or (CL100K_DIGIT_GROUP if self._pretokenizer == "cl100k" else None)
+        self._pattern = regex.compile(split_pattern(self._digit_group, self._pretokenizer))
         # specials are split out first, longest first (reference tokenizer.py:100-102)
         self._special_pattern = None
         if self._special_tokens:
@@ -75,7 +77,8 @@ class BBPETokenizer:
         if sp.exists():
             with open(sp, encoding="utf-8") as f:
                 specials = list(json.load(f))
-        return cls(vocab=vocab, merges=merges, special_tokens=specials, digit_group=read_digit_group(d))
+        name, group = read_pretokenizer(d)
+        return cls(vocab=vocab, merges=merges, special_tokens=specials, digit_group=group, pretokenizer=name)
 
     @classmethod
     def from_file_lossless(cls, model_dir: str | Path) -> "BBPETokenizer":
@@ -93,7 +96,8 @@ class BBPETokenizer:
         if (d / "special_tokens.json").exists():
             with open(d / "special_tokens.json", encoding="utf-8") as f:
                 specials = list(json.load(f))
-        return cls(vocab=vocab, merges=merges, special_tokens=specials, digit_group=read_digit_group(d))
+        name, group = read_pretokenizer(d)
+        return cls(vocab=vocab, merges=merges, special_tokens=specials, digit_group=group, pretokenizer=name)
 
     # ------------------------------------------------------------------ encode
     def _word_parts(self, data: bytes) -> list[bytes]:
@@ -374,6 +378,8 @@ class BBPETokenizer:
             self._device_ctx = _native.Context()
             if self._digit_group:  # (read by every encode call of the context)
                 self._device_ctx.set_option("digit_group", self._digit_group)
+            if self._pretokenizer == "cl100k":
+                self._device_ctx.set_option("split_pattern", 1)
         if model not in self._device_models:
             if model == "encode":
                 ordered = sorted(self._special_tokens, key=len, reverse=True)  # the split pattern's order
@@ -532,6 +538,10 @@ class BBPETokenizer:
     @property
     def digit_group(self) -> int | None:
         return self._digit_group
+
+    @property
+    def pretokenizer(self) -> str:
+        return self._pretokenizer
 
     @property
     def special_tokens(self) -> list[str]:

@@ -7,7 +7,7 @@ loaded with ctypes by `_native`).  There is no CPU fallback: without the built l
 `_merge_loop` raises.
 
 Host-only steps (file chunking, save format) stay in Python as in the reference.  Pre-tokenisation (UTF-8 decode +
-GPT-2 regex, trainer.py:136-214) exists twice with identical results: `_preprocess_corpus` runs the `regex` module on
+GPT-2 regex, trainer.py:136-214; with BBPETrainerConfig(pretokenizer="cl100k") the GPT-4 / Llama-3 pattern) exists twice with identical results: `_preprocess_corpus` runs the `regex` module on
 the host and returns Python lists, as the reference's method does; `train()` on a corpus of 1 MiB or more (or with
 YABPE_PRETOKENIZE=gpu) hands the raw file bytes to `yabpe_pretokenize` instead and never builds Python objects per
 pre-token (YABPE_PRETOKENIZE=host forces the host path).  With `batch_bytes` (or YABPE_BATCH_BYTES) the device path reads
@@ -29,22 +29,46 @@ import regex
 
 # GPT-2 pre-tokenisation pattern (reference trainer.py:163)
 _GPT2_SPLIT = r"""'(?:[sdmt]|ll|ve|re)| ?\p{L}+| ?\p{N}+| ?[^\s\p{L}\p{N}]+|\s+(?!\S)|\s+"""
-PRETOKENIZER_FILE = "pretokenizer.json"  # {"digit_group": G}, written next to a saved model only when a group is set
+# the split of cl100k_base (GPT-4), Llama-3 (G = 3) and Qwen2 (G = 1); %d: the digit group
+_CL100K_SPLIT = r"""(?i:'s|'t|'re|'ve|'m|'ll|'d)|[^\r\n\p{L}\p{N}]?\p{L}+|\p{N}{1,%d}| ?[^\s\p{L}\p{N}]+[\r\n]*|\s*[\r\n]+|\s+(?!\S)|\s+"""
+PRETOKENIZERS = ("gpt2", "cl100k")  # the library's option `split_pattern`: the index
+CL100K_DIGIT_GROUP = 3  # digit_group=None with the cl100k pattern
+# {"digit_group": G} (GPT-2 pattern with a group) or {"pattern": "cl100k", "digit_group": G}, written next to a saved model;
+# the plain GPT-2 pattern writes no file
+PRETOKENIZER_FILE = "pretokenizer.json"
 
 
-def split_pattern(group: int | None = None) -> str:
-    """The GPT-2 pattern; with a digit group G, \\p{N}+ replaced by \\p{N}{1,G} (the one place where the byte-level BPEs after
-    GPT-2 differ from it: groups of up to three digits, or single digits)."""
+def split_pattern(group: int | None = None, pretokenizer: str = "gpt2") -> str:
+    """The one place the pattern string is built.  "gpt2": the GPT-2 pattern; with a digit group G, \\p{N}+ replaced by
+    \\p{N}{1,G}.  "cl100k": the GPT-4 / Llama-3 pattern with \\p{N}{1,G} (None: 3)."""
+    if check_pretokenizer(pretokenizer):
+        return _CL100K_SPLIT % (group or CL100K_DIGIT_GROUP)
     return _GPT2_SPLIT if not group else _GPT2_SPLIT.replace(r"\p{N}+", r"\p{N}{1,%d}" % group, 1)
+
+
+def check_pretokenizer(name) -> int:
+    """A pre-tokeniser name as the library's option `split_pattern` (0: "gpt2", 1: "cl100k").  ValueError for anything else."""
+    if not isinstance(name, str) or name not in PRETOKENIZERS:
+        raise ValueError(f"pretokenizer must be one of {PRETOKENIZERS!r}, got {name!r}")
+    return PRETOKENIZERS.index(name)
+
+
+def read_pretokenizer(model_dir: str | Path) -> tuple[str, int | None]:
+    """(pretokenizer, digit_group) a saved model was trained with: pretokenizer.json in its directory; ("gpt2", None) when
+    there is none."""
+    f = Path(model_dir) / PRETOKENIZER_FILE
+    if not f.exists():
+        return "gpt2", None
+    with open(f, encoding="utf-8") as fh:
+        d = json.load(fh)
+    name = d.get("pattern", "gpt2")
+    group = check_digit_group(d.get("digit_group")) or None
+    return name, (group or CL100K_DIGIT_GROUP) if check_pretokenizer(name) else group
 
 
 def read_digit_group(model_dir: str | Path) -> int | None:
     """The digit group a saved model was trained with: pretokenizer.json in its directory, None when there is none."""
-    f = Path(model_dir) / PRETOKENIZER_FILE
-    if not f.exists():
-        return None
-    with open(f, encoding="utf-8") as fh:
-        return check_digit_group(json.load(fh).get("digit_group")) or None
+    return read_pretokenizer(model_dir)[1]
 
 
 def check_digit_group(n) -> int:
@@ -80,6 +104,11 @@ class BBPETrainerConfig:
             than G digits.  Part of the model: train and train_from set BBPEModel.digit_group, save / save_lossless store it
             (pretokenizer.json) and BBPETokenizer reads it.  With a group no special token may begin with a \\p{N}
             character (ValueError): it could match at a group boundary, where the device rule never looks.
+        pretokenizer: "gpt2" (the reference's pattern) or "cl100k": the split of GPT-4, Llama-3 and Qwen2 -- contractions in
+            either case, one character that is no letter, digit, CR or LF in front of a letter run, digits in groups of
+            digit_group (None: 3) without a space in front, newlines kept with the punctuation or the whitespace before
+            them.  Part of the model like digit_group (BBPEModel.pretokenizer, pretokenizer.json, BBPETokenizer).  With
+            "cl100k" no special token may begin with a \\s or a \\p{N} character (ValueError).
     """
 
     vocab_size: int = 32000
@@ -90,6 +119,7 @@ class BBPETrainerConfig:
     special_tokens: Sequence[str] = field(default_factory=lambda: ["[PAD]", "[UNK]", "[BOS]", "[EOS]"])
     max_token_length: int | None = None
     digit_group: int | None = None
+    pretokenizer: str = "gpt2"
 
 
 def max_token_bytes(config: BBPETrainerConfig) -> int:
@@ -103,26 +133,41 @@ def max_token_bytes(config: BBPETrainerConfig) -> int:
     return int(n)
 
 
-def digit_group(config: BBPETrainerConfig) -> int:
-    """config.digit_group as the library's option `digit_group` (0: none), checked together with the special tokens."""
+def pretokenizer(config: BBPETrainerConfig) -> tuple[int, int]:
+    """config.pretokenizer and config.digit_group as the library's options (`split_pattern`, `digit_group`; 0: none), checked
+    together with the special tokens: THE validation of the pre-tokeniser's settings."""
+    pattern = check_pretokenizer(getattr(config, "pretokenizer", "gpt2"))
     group = check_digit_group(getattr(config, "digit_group", None))
+    if pattern and not group:
+        group = CL100K_DIGIT_GROUP
     if group:
         for tok in config.special_tokens:
             if regex.match(r"\p{N}", tok):
                 raise ValueError(f"special token {tok!r} begins with a digit (\\p{{N}}): not allowed with digit_group = {group}")
-    return group
+    if pattern:
+        for tok in config.special_tokens:
+            if regex.match(r"\s", tok):
+                raise ValueError(f"special token {tok!r} begins with whitespace (\\s): not allowed with pretokenizer = {PRETOKENIZERS[pattern]!r}")
+    return pattern, group
+
+
+def digit_group(config: BBPETrainerConfig) -> int:
+    """The digit group of pretokenizer(config): 0 for none; with "cl100k" never 0 (None means 3)."""
+    return pretokenizer(config)[1]
 
 
 class BBPEModel:
     """Result container (reference trainer.py:41-52): copies of vocab, merges, special tokens; digit_group (not in the
-    reference): the digit group of the pre-tokenisation the model was trained with, None for the GPT-2 pattern."""
+    reference): the digit group of the pre-tokenisation the model was trained with, None for the GPT-2 pattern; pretokenizer:
+    "gpt2" or "cl100k" (digit_group is then never None)."""
 
     def __init__(self, vocab: Mapping[bytes, int], merges: Sequence[tuple[bytes, bytes]],
-                 special_tokens: Sequence[str], digit_group: int | None = None) -> None:
+                 special_tokens: Sequence[str], digit_group: int | None = None, pretokenizer: str = "gpt2") -> None:
         self.vocab: dict[bytes, int] = dict(vocab)
         self.merges: list[tuple[bytes, bytes]] = list(merges)
         self.special_tokens: list[str] = list(special_tokens)
-        self.digit_group: int | None = check_digit_group(digit_group) or None
+        self.pretokenizer: str = PRETOKENIZERS[check_pretokenizer(pretokenizer)]
+        self.digit_group: int | None = check_digit_group(digit_group) or (CL100K_DIGIT_GROUP if self.pretokenizer == "cl100k" else None)
 
     @classmethod
     def from_file_lossless(cls, model_dir: str | Path) -> "BBPEModel":
@@ -141,7 +186,8 @@ class BBPEModel:
         if (d / "special_tokens.json").exists():
             with open(d / "special_tokens.json", encoding="utf-8") as f:
                 specials = list(json.load(f))
-        return cls(vocab=vocab, merges=merges, special_tokens=specials, digit_group=read_digit_group(d))
+        name, group = read_pretokenizer(d)
+        return cls(vocab=vocab, merges=merges, special_tokens=specials, digit_group=group, pretokenizer=name)
 
 
 def _utf8_cut(window: bytes, pos: int) -> int:
@@ -205,23 +251,28 @@ class BBPETrainer:
 
     def _context(self):
         """A device context for a merge loop of this trainer: the maximum token length, when set, goes in as an option before
-        any words are loaded (the library reads it at the load), the digit group before any text is pre-tokenised."""
+        any words are loaded (the library reads it at the load), the digit group and the split pattern before any text is
+        pre-tokenised."""
         from . import _native  # fails loudly when libyabpe.so / a GPU is missing
 
-        limit, group = max_token_bytes(self.config), digit_group(self.config)
+        limit, (pattern, group) = max_token_bytes(self.config), pretokenizer(self.config)
         ctx = _native.Context()
         try:
             if limit:
                 ctx.set_option("max_token_bytes", limit)
             if group:
                 ctx.set_option("digit_group", group)
+            if pattern:
+                ctx.set_option("split_pattern", pattern)
         except BaseException:
             ctx.close()
             raise
         return ctx
 
     def _model(self, vocab, merges) -> BBPEModel:
-        return BBPEModel(vocab=vocab, merges=merges, special_tokens=list(self.config.special_tokens), digit_group=self.config.digit_group)
+        pattern, group = pretokenizer(self.config)
+        return BBPEModel(vocab=vocab, merges=merges, special_tokens=list(self.config.special_tokens), digit_group=group or None,
+                         pretokenizer=PRETOKENIZERS[pattern])
 
     # ------------------------------------------------------------------ train / save (trainer.py:63-117)
     def train(self, files: Sequence[str | Path], batch_bytes: int | None = None) -> BBPEModel:
@@ -229,7 +280,7 @@ class BBPETrainer:
         the device pre-tokeniser in batches of whole chunks of at most that many bytes and their pre-tokens are pooled on
         the device batch by batch -- for corpora larger than host or device memory.  The model is the same."""
         max_token_bytes(self.config)  # (a bad limit fails before any file is read or any device call is made)
-        digit_group(self.config)      # (and so does a bad digit group, or a special it does not allow)
+        pretokenizer(self.config)     # (and so does a bad pre-tokeniser or digit group, or a special they do not allow)
         if not files:
             raise ValueError("At least one file must be provided")
         paths = [Path(f) if isinstance(f, str) else f for f in files]
@@ -430,13 +481,17 @@ class BBPETrainer:
         config.max_token_length constrains only the merges learned here: the model's own merges are replayed whatever their
         length (the limit is not part of a saved model)."""
         max_token_bytes(self.config)  # (a bad limit fails before any file is read or any device call is made)
-        digit_group(self.config)      # (and so does a bad digit group, or a special it does not allow)
+        pretokenizer(self.config)     # (and so does a bad pre-tokeniser or digit group, or a special they do not allow)
         if not files:
             raise ValueError("At least one file must be provided")
         paths = [Path(f) if isinstance(f, str) else f for f in files]
-        if getattr(model, "digit_group", None) != (self.config.digit_group or None):
+        pattern, group = pretokenizer(self.config)
+        if getattr(model, "pretokenizer", "gpt2") != PRETOKENIZERS[pattern]:
+            raise ValueError(f"cannot continue from this model: it was trained with pretokenizer = {getattr(model, 'pretokenizer', 'gpt2')!r}, "
+                             f"the trainer's is {PRETOKENIZERS[pattern]!r} (its merges would be replayed over words it never saw)")
+        if getattr(model, "digit_group", None) != (group or None):
             raise ValueError(f"cannot continue from this model: it was trained with digit_group = {getattr(model, 'digit_group', None)!r}, "
-                             f"the trainer's is {self.config.digit_group!r} (its merges would be replayed over words it never saw)")
+                             f"the trainer's is {group or None!r} (its merges would be replayed over words it never saw)")
         toks, triples = self._resumable(model)
         old_merges = [(bytes(l), bytes(r)) for l, r in model.merges]
         num_merges = max(0, self.config.vocab_size - len(self._base_tokens()) - len(old_merges))
@@ -510,7 +565,7 @@ class BBPETrainer:
 
     def save(self, output_dir: str | Path) -> None:
         """vocab.json / merges.txt / special_tokens.json in the reference's format (trainer.py:94-117); with a digit group
-        also pretokenizer.json ({"digit_group": G})."""
+        also pretokenizer.json ({"digit_group": G}), with the cl100k pattern {"pattern": "cl100k", "digit_group": G}."""
         if not self._vocab:
             raise ValueError("Model has not been trained yet. Call train() first.")
         out = Path(output_dir)
@@ -525,10 +580,13 @@ class BBPETrainer:
         self._save_pretokenizer(out)
 
     def _save_pretokenizer(self, out: Path) -> None:
-        """pretokenizer.json, only when the model was trained with a digit group (without one the directory holds exactly
-        the files it always held; a file left there by an earlier save is removed)."""
-        group = digit_group(self.config)
-        if group:
+        """pretokenizer.json, only when the model was trained with a digit group or the cl100k pattern (without them the
+        directory holds exactly the files it always held; a file left there by an earlier save is removed)."""
+        pattern, group = pretokenizer(self.config)
+        if pattern:
+            with open(out / PRETOKENIZER_FILE, "w", encoding="utf-8") as f:
+                json.dump({"pattern": PRETOKENIZERS[pattern], "digit_group": group}, f)
+        elif group:
             with open(out / PRETOKENIZER_FILE, "w", encoding="utf-8") as f:
                 json.dump({"digit_group": group}, f)
         elif (out / PRETOKENIZER_FILE).exists():
@@ -578,7 +636,8 @@ class BBPETrainer:
             return chunk_ranges(size, self.config.chunk_size_bytes, read)
 
     def _split_pattern(self) -> "regex.Pattern[str]":
-        pat = split_pattern(digit_group(self.config))
+        pattern, group = pretokenizer(self.config)
+        pat = split_pattern(group, PRETOKENIZERS[pattern])
         if self.config.special_tokens:  # specials first, in config order, kept as words (trainer.py:165-167)
             pat = "|".join(regex.escape(t) for t in self.config.special_tokens) + "|" + pat
         return regex.compile(pat)
