@@ -228,49 +228,42 @@ class Context:
         self._base = list(tokens)
         self._chk(lib().yabpe_set_vocab(self._h, blob.ctypes.data, off.ctypes.data, len(tokens)))
 
+    def _load(self, flat, off, n_words: int | None, freq, dedup: bool, triples=None) -> None:
+        """yabpe_load_words; with `triples` ((left, right, merged) u32 arrays) yabpe_load_words_resumed.  flat, off, freq: host
+        arrays (u8 bytes, n + 1 u64 offsets, n u64 counts or None) when n_words is None, else addresses (freq 0: no counts).
+        The arrays handed to the library stay in self._keep, so they outlive the call."""
+        if n_words is None:
+            flat, off = np.ascontiguousarray(flat, dtype=np.uint8), np.ascontiguousarray(off, dtype=np.uint64)
+            freq = None if freq is None else np.ascontiguousarray(freq, dtype=np.uint64)
+            n_words = len(off) - 1
+            assert freq is None or len(freq) == n_words
+            words = (flat.ctypes.data if flat.size else None, off.ctypes.data, None if freq is None else freq.ctypes.data)
+        else:
+            words = (c_void_p(flat), c_void_p(off), c_void_p(freq) if freq else None)
+        l, r, m = (np.ascontiguousarray(x, dtype=np.uint32) for x in (triples if triples is not None else ((), (), ())))
+        self._keep = (flat, off, freq, l, r, m)
+        if triples is None:
+            self._chk(lib().yabpe_load_words(self._h, *words, n_words, LOAD_DEDUP if dedup else 0))
+        else:
+            self._chk(lib().yabpe_load_words_resumed(self._h, *words, n_words, LOAD_DEDUP if dedup else 0,
+                                                     *(x.ctypes.data if len(l) else None for x in (l, r, m)), len(l)))
+
     def load_words(self, flat, off, freq=None, dedup: bool = False) -> None:
-        """flat: u8 bytes, off: u64 offsets (n+1), freq: optional u64 counts.  numpy arrays (host) or
-        integer device addresses wrapped as (ptr, n) via load_words_ptr."""
-        flat = np.ascontiguousarray(flat, dtype=np.uint8)
-        off = np.ascontiguousarray(off, dtype=np.uint64)
-        n = len(off) - 1
-        fq = None
-        if freq is not None:
-            fq = np.ascontiguousarray(freq, dtype=np.uint64)
-            assert len(fq) == n
-        self._keep = (flat, off, fq)
-        self._chk(lib().yabpe_load_words(self._h, flat.ctypes.data if flat.size else None, off.ctypes.data,
-                                         fq.ctypes.data if fq is not None else None, n, LOAD_DEDUP if dedup else 0))
+        """flat: u8 bytes, off: u64 offsets (n+1), freq: optional u64 counts: numpy arrays on the host."""
+        self._load(flat, off, None, freq, dedup)
 
     def load_words_ptr(self, bytes_ptr: int, off_ptr: int, n_words: int, freq_ptr: int = 0, dedup: bool = False) -> None:
         """Device (or host) addresses, e.g. from synth_generate() or torch tensors' data_ptr()."""
-        self._chk(lib().yabpe_load_words(self._h, c_void_p(bytes_ptr), c_void_p(off_ptr),
-                                         c_void_p(freq_ptr) if freq_ptr else None, n_words, LOAD_DEDUP if dedup else 0))
+        self._load(bytes_ptr, off_ptr, n_words, freq_ptr, dedup)
 
     # -- continuing from a trained model: `triples` = (left, right, merged) u32 arrays (merge_triples), after set_vocab with
     # all of the model's tokens
     def load_words_resumed(self, flat, off, freq, triples, dedup: bool = False) -> None:
-        flat = np.ascontiguousarray(flat, dtype=np.uint8)
-        off = np.ascontiguousarray(off, dtype=np.uint64)
-        n = len(off) - 1
-        fq = None
-        if freq is not None:
-            fq = np.ascontiguousarray(freq, dtype=np.uint64)
-            assert len(fq) == n
-        l, r, m = (np.ascontiguousarray(x, dtype=np.uint32) for x in triples)
-        self._keep = (flat, off, fq, l, r, m)
-        self._chk(lib().yabpe_load_words_resumed(self._h, flat.ctypes.data if flat.size else None, off.ctypes.data,
-                                                 fq.ctypes.data if fq is not None else None, n, LOAD_DEDUP if dedup else 0,
-                                                 l.ctypes.data if len(l) else None, r.ctypes.data if len(l) else None,
-                                                 m.ctypes.data if len(l) else None, len(l)))
+        self._load(flat, off, None, freq, dedup, triples)
 
     def load_words_resumed_ptr(self, bytes_ptr: int, off_ptr: int, n_words: int, triples, freq_ptr: int = 0, dedup: bool = True) -> None:
         """Device (or host) addresses for the words, e.g. the results of pretokenize()."""
-        l, r, m = (np.ascontiguousarray(x, dtype=np.uint32) for x in triples)
-        self._keep = (l, r, m)
-        self._chk(lib().yabpe_load_words_resumed(self._h, c_void_p(bytes_ptr), c_void_p(off_ptr), c_void_p(freq_ptr) if freq_ptr else None,
-                                                 n_words, LOAD_DEDUP if dedup else 0, l.ctypes.data if len(l) else None,
-                                                 r.ctypes.data if len(l) else None, m.ctypes.data if len(l) else None, len(l)))
+        self._load(bytes_ptr, off_ptr, n_words, freq_ptr, dedup, triples)
 
     def resume_stats(self) -> dict:
         s = ResumeStats()
@@ -720,6 +713,19 @@ def merge_triples(base_tokens, merges):
     return toks, (left, right, merged)
 
 
+def decode_merges(base_tokens, left, right, merged):
+    """The inverse of merge_triples: (left, right, merged) id arrays over the base token list -> ({token: id}, [(bytes, bytes)])."""
+    toks = list(base_tokens)
+    merges: list[tuple[bytes, bytes]] = []
+    for l, r, m in zip(left.tolist(), right.tolist(), merged.tolist()):
+        merges.append((toks[l], toks[r]))
+        if m == len(toks):  # a fresh id; otherwise the bytes already existed (trainer.py:298-300)
+            toks.append(toks[l] + toks[r])
+        else:
+            assert toks[m] == toks[l] + toks[r], "merged id does not name left+right"
+    return {t: i for i, t in enumerate(toks)}, merges
+
+
 def train_words(words_flat, words_off, freq, base_tokens: list[bytes], num_merges: int, min_frequency: int,
                 dedup: bool = False, options: dict | None = None, want_stats: bool = False):
     """Convenience used by tests/bench: returns (vocab, merges[, stats]) like _merge_loop."""
@@ -730,13 +736,5 @@ def train_words(words_flat, words_off, freq, base_tokens: list[bytes], num_merge
         ctx.load_words(words_flat, words_off, freq, dedup=dedup)
         left, right, merged, count = ctx.train(num_merges, min_frequency)
         stats = ctx.stats() if want_stats else None
-    toks = list(base_tokens)
-    merges = []
-    for l, r, m in zip(left.tolist(), right.tolist(), merged.tolist()):
-        merges.append((toks[l], toks[r]))
-        if m == len(toks):
-            toks.append(toks[l] + toks[r])
-        else:
-            assert toks[m] == toks[l] + toks[r], "merged id does not name left+right"
-    vocab = {t: i for i, t in enumerate(toks)}
+    vocab, merges = decode_merges(base_tokens, left, right, merged)
     return (vocab, merges, stats) if want_stats else (vocab, merges)

@@ -148,6 +148,15 @@ def plan_chunk_shards(sizes: Sequence[int], world: int) -> list[tuple[int, int]]
     return [(min(bounds[r], len(sizes)), min(bounds[r + 1], len(sizes))) for r in range(world)]
 
 
+def _train_my_words(ctx, dev_text: int, dev_off: int, n_words: int, config, num_merges: int):
+    """Loads this rank's pre-tokens (pooled), or nothing in the same layout as the peers, and joins the merge loop."""
+    if n_words:
+        ctx.load_words_ptr(dev_text, dev_off, n_words, dedup=True)
+    else:
+        ctx.load_words(np.zeros(0, np.uint8), np.zeros(1, np.uint64), None, dedup=True)
+    return ctx.train(num_merges, max(0, int(config.min_frequency)))  # (<= 0: merge to exhaustion, as BBPETrainer.train does)
+
+
 def train_text_sharded(ctx_factory, files, config, rank: int, world: int, transport: str = "rccl", options: dict | None = None):
     """BBPETrainer.train() over several GPUs, text in, model out (BASELINE configs[4] shape): every rank reads ITS chunks
     of the files, pre-tokenises them on its GPU (yabpe_pretokenize), pools equal pre-tokens locally and joins the
@@ -156,46 +165,29 @@ def train_text_sharded(ctx_factory, files, config, rank: int, world: int, transp
     from pathlib import Path
 
     from . import _native
-    from .trainer import PRETOKENIZERS, BBPEModel, BBPETrainer, max_token_bytes, pretokenizer
+    from .trainer import BBPETrainer, check_files, device_options, read_chunks, utf8_error
 
-    limit, (pattern, group) = max_token_bytes(config), pretokenizer(config)  # (ValueError before any file is read)
+    device_options(config)  # (ValueError before any file is read)
     tr = BBPETrainer(config)
     paths = [Path(f) for f in files]
-    for p in paths:
-        if not p.exists():
-            raise FileNotFoundError(f"File not found: {p}")
+    check_files(paths)
     chunks = [(p, a, b) for p in paths for a, b in tr._chunk_ranges(p)]
     c0, c1 = plan_chunk_shards([b - a for _, a, b in chunks], world)[rank] if chunks else (0, 0)
-    pieces, starts, total = [], [], 0
-    for p, a, b in chunks[c0:c1]:
-        starts.append(total)
-        pieces.append(np.fromfile(p, dtype=np.uint8, count=b - a, offset=a))
-        total += b - a
+    text, starts = read_chunks(chunks[c0:c1])
     base = tr._base_tokens()
-    specials = list(config.special_tokens)
-    num_merges = max(0, config.vocab_size - len(base))
     with ctx_factory() as ctx:
-        for k, v in (options or {}).items():
+        for k, v in [*(options or {}).items(), *device_options(config).items()]:  # (the config's: the same on every rank)
             ctx.set_option(k, v)
-        if limit:  # config.max_token_length: the same on every rank, so every replica leaves out the same pairs
-            ctx.set_option("max_token_bytes", limit)
-        if group:  # config.digit_group: the same on every rank, so every rank cuts its chunks' digit runs alike
-            ctx.set_option("digit_group", group)
-        if pattern:  # config.pretokenizer: likewise
-            ctx.set_option("split_pattern", pattern)
         ctx.set_vocab(base)
         attach(ctx, rank, world, transport)
         err = None
-        n_words = 0
-        if total:
-            text = pieces[0] if len(pieces) == 1 else np.concatenate(pieces)
+        dev_text, dev_off, n_words = 0, 0, 0
+        if len(text):
             try:
-                dev_text, dev_off, n_words = ctx.pretokenize(text, chunk_starts=starts, special_tokens=specials)
+                dev_text, dev_off, n_words = ctx.pretokenize(text, chunk_starts=starts, special_tokens=list(config.special_tokens))
             except _native.Utf8Error as e:
-                k = max(i for i, s0 in enumerate(starts) if s0 <= e.position)
-                p, a, _ = chunks[c0 + k]
-                err = (c0 + k, f"File {p} contains invalid UTF-8 at position {a + e.position - starts[k]}.")
-        if world > 1:  # every rank must learn about a bad chunk anywhere, or the others would wait in the merge loop
+                err = (rank, str(utf8_error(chunks[c0:c1], starts, e)))  # (the chunks go to the ranks in order)
+        if world > 1:  # every rank must learn about the first bad chunk anywhere, or the others would wait in the merge loop
             import torch.distributed as dist
 
             errs = [None] * world
@@ -203,13 +195,8 @@ def train_text_sharded(ctx_factory, files, config, rank: int, world: int, transp
             err = min((e for e in errs if e), default=None)
         if err:
             raise ValueError(err[1])
-        if n_words:
-            ctx.load_words_ptr(dev_text, dev_off, n_words, dedup=True)
-        else:
-            ctx.load_words(np.zeros(0, np.uint8), np.zeros(1, np.uint64), None, dedup=True)  # no words here: same layout as the peers
-        left, right, merged, _count = ctx.train(num_merges, int(config.min_frequency))
-    vocab, merges = BBPETrainer._decode_merges(base, left, right, merged)
-    return BBPEModel(vocab=vocab, merges=merges, special_tokens=specials, digit_group=group or None, pretokenizer=PRETOKENIZERS[pattern])
+        left, right, merged, _count = _train_my_words(ctx, dev_text, dev_off, n_words, config, max(0, config.vocab_size - len(base)))
+    return tr._model(*BBPETrainer._decode_merges(base, left, right, merged))
 
 
 def train_device_text_sharded(ctx_factory, make_text, config, rank: int, world: int, transport: str = "rccl", options: dict | None = None):
@@ -217,39 +204,26 @@ def train_device_text_sharded(ctx_factory, make_text, config, rank: int, world: 
     `make_text(ctx) -> (dev_ptr, n_bytes)` runs on every rank; the chunk cuts are the reference's (config.chunk_size_bytes),
     this rank pre-tokenises ITS chunks, pools the pre-tokens and joins the collective merge loop.
     Returns (left, right, merged, count, stats, n_pretokens_here)."""
-    from .trainer import BBPETrainer, chunk_ranges, max_token_bytes, pretokenizer
+    from .trainer import BBPETrainer, chunk_ranges, device_options
 
-    limit, (pattern, group) = max_token_bytes(config), pretokenizer(config)
-    tr = BBPETrainer(config)
-    base = tr._base_tokens()
-    specials = list(config.special_tokens)
-    num_merges = max(0, config.vocab_size - len(base))
+    device_options(config)  # (ValueError before the context is made)
+    base = BBPETrainer(config)._base_tokens()
     with ctx_factory() as ctx:
-        for k, v in (options or {}).items():
+        for k, v in [*(options or {}).items(), *device_options(config).items()]:  # (the config's: the same on every rank)
             ctx.set_option(k, v)
-        if limit:  # config.max_token_length: the same on every rank, so every replica leaves out the same pairs
-            ctx.set_option("max_token_bytes", limit)
-        if group:  # config.digit_group: the same on every rank, so every rank cuts its chunks' digit runs alike
-            ctx.set_option("digit_group", group)
-        if pattern:  # config.pretokenizer: likewise
-            ctx.set_option("split_pattern", pattern)
         ctx.set_vocab(base)
         attach(ctx, rank, world, transport)
         ptr, n_bytes = make_text(ctx)
         ranges = chunk_ranges(n_bytes, config.chunk_size_bytes, lambda off, n: ctx.d2h(ptr + off, n).tobytes())
         c0, c1 = plan_chunk_shards([b - a for a, b in ranges], world)[rank]
         mine = ranges[c0:c1]
-        n_words = 0
+        dev_text, dev_off, n_words = 0, 0, 0
         if mine:
             a0 = mine[0][0]
             assert all(mine[i][1] == mine[i + 1][0] for i in range(len(mine) - 1)), "chunks of valid UTF-8 follow one another"
             dev_text, dev_off, n_words = ctx.pretokenize(ptr + a0, n_bytes=mine[-1][1] - a0, chunk_starts=[a - a0 for a, _ in mine],
-                                                         special_tokens=specials)
-        if n_words:
-            ctx.load_words_ptr(dev_text, dev_off, n_words, dedup=True)
-        else:
-            ctx.load_words(np.zeros(0, np.uint8), np.zeros(1, np.uint64), None, dedup=True)  # no words here: same layout as the peers
-        left, right, merged, count = ctx.train(num_merges, int(config.min_frequency))
+                                                         special_tokens=list(config.special_tokens))
+        left, right, merged, count = _train_my_words(ctx, dev_text, dev_off, n_words, config, max(0, config.vocab_size - len(base)))
         return left, right, merged, count, ctx.stats(), n_words
 
 

@@ -25,7 +25,8 @@ import numpy as np
 import regex
 
 from .synth import rnd_int
-from .trainer import CL100K_DIGIT_GROUP, PRETOKENIZERS, check_digit_group, check_pretokenizer, read_pretokenizer, split_pattern
+from .trainer import (CL100K_DIGIT_GROUP, PRETOKENIZERS, BBPETrainerConfig, check_digit_group, check_pretokenizer, device_options, read_pretokenizer,
+                      split_pattern)
 
 _WORD_CACHE = 8192
 
@@ -376,10 +377,9 @@ class BBPETokenizer:
             from . import _native
 
             self._device_ctx = _native.Context()
-            if self._digit_group:  # (read by every encode call of the context)
-                self._device_ctx.set_option("digit_group", self._digit_group)
-            if self._pretokenizer == "cl100k":
-                self._device_ctx.set_option("split_pattern", 1)
+            settings = BBPETrainerConfig(special_tokens=(), digit_group=self._digit_group, pretokenizer=self._pretokenizer)
+            for name, value in device_options(settings).items():  # (read by every encode call of the context)
+                self._device_ctx.set_option(name, value)
         if model not in self._device_models:
             if model == "encode":
                 ordered = sorted(self._special_tokens, key=len, reverse=True)  # the split pattern's order

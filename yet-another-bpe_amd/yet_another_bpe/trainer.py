@@ -7,12 +7,19 @@ loaded with ctypes by `_native`).  There is no CPU fallback: without the built l
 `_merge_loop` raises.
 
 Host-only steps (file chunking, save format) stay in Python as in the reference.  Pre-tokenisation (UTF-8 decode +
-GPT-2 regex, trainer.py:136-214; with BBPETrainerConfig(pretokenizer="cl100k") the GPT-4 / Llama-3 pattern) exists twice with identical results: `_preprocess_corpus` runs the `regex` module on
-the host and returns Python lists, as the reference's method does; `train()` on a corpus of 1 MiB or more (or with
-YABPE_PRETOKENIZE=gpu) hands the raw file bytes to `yabpe_pretokenize` instead and never builds Python objects per
-pre-token (YABPE_PRETOKENIZE=host forces the host path).  With `batch_bytes` (or YABPE_BATCH_BYTES) the device path reads
-the files batch by batch and pools each batch's pre-tokens into the context's word pool (`yabpe_pool_add`), so neither the
-host nor the device ever holds more text than one batch; the merge loop is loaded from the pool.
+GPT-2 regex, trainer.py:136-214; with BBPETrainerConfig(pretokenizer="cl100k") the GPT-4 / Llama-3 pattern) exists twice with
+identical results: `_preprocess_corpus` runs the `regex` module on the host and returns Python lists, as the reference's
+method does; on a corpus of 1 MiB or more (or with YABPE_PRETOKENIZE=gpu; YABPE_PRETOKENIZE=host forces the host path) the raw
+file bytes go to `yabpe_pretokenize` instead and no Python object is built per pre-token.  With `batch_bytes` (or
+YABPE_BATCH_BYTES) the device path reads the files batch by batch and pools each batch's pre-tokens into the context's word
+pool (`yabpe_pool_add`), so neither the host nor the device ever holds more text than one batch; the merge loop is loaded
+from the pool.
+
+One route from the corpus to the loaded words, for `train` and `train_from` alike: `BBPETrainer._train` chooses host, device
+or batched, `_device_words` reads file chunks `(path, start, stop)` with `read_chunks` and names the file of an invalid byte
+with `utf8_error`, `_run` is the one tail (vocabulary, load -- the resumed load for a continued model --, merge loop, stats).
+`device_options` is the one place a config field becomes an option of the library; the sharded drivers (distributed.py) and
+BBPETokenizer's device context take theirs from it too.
 """
 from __future__ import annotations
 
@@ -240,6 +247,44 @@ def group_chunks(sizes: Sequence[int], batch_bytes: int) -> list[tuple[int, int]
     return batches
 
 
+def device_options(config: BBPETrainerConfig) -> dict[str, int]:
+    """THE place a config field becomes an option of the library (yabpe_set_option): the non-zero ones among max_token_bytes,
+    digit_group and split_pattern, validated.  The maximum token length is read at the load of the words, the digit group
+    and the split pattern by every pre-tokenisation or encode call, so they go in right after the context is made."""
+    limit = max_token_bytes(config)
+    pattern, group = pretokenizer(config)
+    return {k: v for k, v in (("max_token_bytes", limit), ("digit_group", group), ("split_pattern", pattern)) if v}
+
+
+def check_files(paths: Sequence[Path]) -> None:
+    for path in paths:
+        if not path.exists():
+            raise FileNotFoundError(f"File not found: {path}")
+
+
+def read_chunks(chunks: Sequence[tuple[Path, int, int]]) -> tuple[np.ndarray, list[int]]:
+    """The chunks (file, start, stop) read into one u8 buffer, back to back, and each chunk's start in it."""
+    buf = np.empty(sum(stop - start for _p, start, stop in chunks), dtype=np.uint8)
+    starts: list[int] = []
+    pos = 0
+    for path, start, stop in chunks:
+        starts.append(pos)
+        with open(path, "rb") as f:
+            f.seek(start)
+            if f.readinto(memoryview(buf[pos:pos + stop - start])) != stop - start:
+                raise OSError(f"File {path} changed while it was read")
+        pos += stop - start
+    return buf, starts
+
+
+def utf8_error(chunks: Sequence[tuple[Path, int, int]], starts: Sequence[int], e) -> ValueError:
+    """The reference's message for e (a _native.Utf8Error with its position in read_chunks(chunks)' buffer): the file and the
+    position in that file."""
+    k = max(i for i, s0 in enumerate(starts) if s0 <= e.position)
+    path, start, _stop = chunks[k]
+    return ValueError(f"File {path} contains invalid UTF-8 at position {start + e.position - starts[k]}.")
+
+
 class BBPETrainer:
     """Byte-level BPE trainer with the reference's API; the merge loop runs on the GPU."""
 
@@ -250,20 +295,13 @@ class BBPETrainer:
         self.last_stats: dict | None = None  # yabpe_stats of the last merge loop (not in the reference)
 
     def _context(self):
-        """A device context for a merge loop of this trainer: the maximum token length, when set, goes in as an option before
-        any words are loaded (the library reads it at the load), the digit group and the split pattern before any text is
-        pre-tokenised."""
+        """A device context for this trainer's configuration."""
         from . import _native  # fails loudly when libyabpe.so / a GPU is missing
 
-        limit, (pattern, group) = max_token_bytes(self.config), pretokenizer(self.config)
         ctx = _native.Context()
         try:
-            if limit:
-                ctx.set_option("max_token_bytes", limit)
-            if group:
-                ctx.set_option("digit_group", group)
-            if pattern:
-                ctx.set_option("split_pattern", pattern)
+            for name, value in device_options(self.config).items():
+                ctx.set_option(name, value)
         except BaseException:
             ctx.close()
             raise
@@ -278,65 +316,83 @@ class BBPETrainer:
     def train(self, files: Sequence[str | Path], batch_bytes: int | None = None) -> BBPEModel:
         """`batch_bytes` (None: the environment variable YABPE_BATCH_BYTES; unset: everything at once): the files go through
         the device pre-tokeniser in batches of whole chunks of at most that many bytes and their pre-tokens are pooled on
-        the device batch by batch -- for corpora larger than host or device memory.  The model is the same."""
-        max_token_bytes(self.config)  # (a bad limit fails before any file is read or any device call is made)
-        pretokenizer(self.config)     # (and so does a bad pre-tokeniser or digit group, or a special they do not allow)
+        the device batch by batch -- for corpora larger than host or device memory.  The model is the same.
+        An empty corpus gives the base vocabulary only (trainer.py:81-85); so does a zero budget, after the text was
+        pre-tokenised (an invalid byte is still reported)."""
+        device_options(self.config)  # (a bad limit, pre-tokeniser or digit group, or a special they do not allow, fails before any file is read or any device call is made)
         if not files:
             raise ValueError("At least one file must be provided")
         paths = [Path(f) if isinstance(f, str) else f for f in files]
+        return self._train(paths, batch_bytes, self._base_tokens(), None, [], self._init_base_vocab())
+
+    def train_from(self, model, files: Sequence[str | Path], batch_bytes: int | None = None) -> BBPEModel:
+        """Continues training from `model` (a BBPEModel, or anything with .vocab, .merges and .special_tokens) on `files`:
+        more merges on the same corpus, or new merges learned from a new one.  Every existing id is kept; the result is
+        model.merges + the new merges and the extended vocab, exactly what train() gives when the corpus is the one the
+        model was trained on.  The iteration budget is max(0, vocab_size - len(base) - len(model.merges)) (a merge that
+        reused an id cost an iteration too, trainer.py:238).  An empty corpus or a zero budget returns the model unchanged.
+        Pre-tokenisation is train()'s (special tokens are ordinary words), on the device under the same size / environment
+        rule; the words are pooled (the flat layout does not apply).  `batch_bytes`: as train() takes it.
+        config.max_token_length constrains only the merges learned here: the model's own merges are replayed whatever their
+        length (the limit is not part of a saved model)."""
+        device_options(self.config)  # (as in train)
+        if not files:
+            raise ValueError("At least one file must be provided")
+        paths = [Path(f) if isinstance(f, str) else f for f in files]
+        pattern, group = pretokenizer(self.config)
+        if getattr(model, "pretokenizer", "gpt2") != PRETOKENIZERS[pattern]:
+            raise ValueError(f"cannot continue from this model: it was trained with pretokenizer = {getattr(model, 'pretokenizer', 'gpt2')!r}, "
+                             f"the trainer's is {PRETOKENIZERS[pattern]!r} (its merges would be replayed over words it never saw)")
+        if getattr(model, "digit_group", None) != (group or None):
+            raise ValueError(f"cannot continue from this model: it was trained with digit_group = {getattr(model, 'digit_group', None)!r}, "
+                             f"the trainer's is {group or None!r} (its merges would be replayed over words it never saw)")
+        toks, triples = self._resumable(model)
+        old_merges = [(bytes(l), bytes(r)) for l, r in model.merges]
+        check_files(paths)
+        if self._budget(old_merges) == 0:  # nothing to learn: no file is read, whatever batch_bytes says
+            self._vocab, self._merges = dict(model.vocab), old_merges
+            return self._model(self._vocab, self._merges)
+        return self._train(paths, batch_bytes, toks, triples, old_merges, dict(model.vocab))
+
+    def _budget(self, old_merges: Sequence = ()) -> int:
+        """Iterations of the merge loop that the vocabulary size leaves (trainer.py:238)"""
+        return max(0, self.config.vocab_size - len(self._base_tokens()) - len(old_merges))
+
+    def _train(self, paths: Sequence[Path], batch_bytes: int | None, toks: list[bytes], triples, old_merges: list, unchanged: dict) -> BBPEModel:
+        """train and train_from: `toks` the tokens in id order and `triples` the merges that made them (_resumable; None: a
+        fresh model over the base tokens), `old_merges` those merges as bytes, `unchanged` the vocabulary to return when the
+        corpus has no words.  The ONE place the route is chosen -- pre-tokeniser on the host, on the device
+        (YABPE_PRETOKENIZE=gpu, or auto and 1 MiB of files or more), or on the device batch by batch through the word pool
+        -- and the words are handed to _run in one of its two forms.  Same results on every route.  YABPE_LAYOUT=flat (every
+        occurrence resident, no pooling) applies to a fresh model only: a continued one always pools."""
+        flat = triples is None and os.environ.get("YABPE_LAYOUT", "dedup") == "flat"
         mode = os.environ.get("YABPE_PRETOKENIZE", "auto")
         batch = self._batch_bytes(batch_bytes)
-        if batch is not None:
-            if os.environ.get("YABPE_LAYOUT", "dedup") == "flat":
-                raise ValueError("batch_bytes needs the pooled layout: YABPE_LAYOUT=flat keeps every occurrence resident")
-            return self._train_device_batched(paths, batch)
-        if mode == "gpu" or (mode == "auto" and sum(p.stat().st_size for p in paths if p.exists()) >= (1 << 20)):
-            return self._train_device(paths)
-        pretokens = self._pretokenize(paths)
-        if not pretokens:  # empty corpus: base vocab only (trainer.py:81-85)
-            self._vocab = self._init_base_vocab()
-            self._merges = []
-            return self._model(self._vocab, [])
-        # word-frequency pooling (trainer.py:221-225) on the host: the pre-tokens are Python strings here anyway
-        if os.environ.get("YABPE_LAYOUT", "dedup") == "flat":
-            words = [t.encode("utf-8") for t in pretokens]
-            freq = None
+        if batch is not None and flat:
+            raise ValueError("batch_bytes needs the pooled layout: YABPE_LAYOUT=flat keeps every occurrence resident")
+        check_files(paths)
+        num_merges = self._budget(old_merges)
+        vocab, new_merges = unchanged, []
+        if batch is not None or mode == "gpu" or (mode == "auto" and sum(p.stat().st_size for p in paths) >= (1 << 20)):
+            chunks = [(path, start, stop) for path in paths for start, stop in self._chunk_ranges(path)]
+            if chunks:
+                with self._context() as ctx:
+                    words = self._device_words(ctx, chunks, batch, dedup=not flat)
+                    if words[2] and num_merges:
+                        vocab, new_merges = self._run(ctx, toks, words, triples, num_merges)
         else:
-            pooled = Counter(pretokens)
-            words = [t.encode("utf-8") for t in pooled]
-            freq = np.fromiter(pooled.values(), dtype=np.uint64, count=len(pooled))
-        vocab, merges = self._merge_loop_words(words, freq)
-        self._vocab = vocab
-        self._merges = merges
-        return self._model(vocab, merges)
+            pretokens = self._pretokenize(paths)
+            if flat:
+                words, freq = [t.encode("utf-8") for t in pretokens], None
+            else:  # word-frequency pooling (trainer.py:221-225) on the host: the pre-tokens are Python strings here anyway
+                pooled = Counter(pretokens)
+                words, freq = [t.encode("utf-8") for t in pooled], np.fromiter(pooled.values(), dtype=np.uint64, count=len(pooled))
+            if words and num_merges:
+                with self._context() as ctx:
+                    vocab, new_merges = self._run(ctx, toks, self._host_words(words, freq), triples, num_merges)
+        self._vocab, self._merges = vocab, old_merges + new_merges
+        return self._model(self._vocab, self._merges)
 
-    def _train_device(self, paths: Sequence[Path]) -> BBPEModel:
-        """train() with the pre-tokeniser on the GPU: file bytes -> yabpe_pretokenize -> word offsets in HBM ->
-        yabpe_load_words (equal pre-tokens pooled on the device) -> merge loop.  Same results as the host path."""
-        from . import _native  # fails loudly when libyabpe.so / a GPU is missing
-
-        text, chunks, total = self._gather_text(paths)
-        base = self._base_tokens()
-        num_merges = max(0, self.config.vocab_size - len(base))
-        empty = self._model({t: i for i, t in enumerate(base)}, [])
-        if total == 0:
-            self._vocab, self._merges = dict(empty.vocab), []
-            return empty
-        with self._context() as ctx:
-            dev_text, dev_off, n_words = self._pretokenize_device(ctx, text, chunks)
-            if n_words == 0 or num_merges == 0:
-                self._vocab, self._merges = dict(empty.vocab), []
-                return empty
-            ctx.set_vocab(base)
-            ctx.load_words_ptr(dev_text, dev_off, n_words, dedup=os.environ.get("YABPE_LAYOUT", "dedup") != "flat")
-            left, right, merged, _count = ctx.train(num_merges, max(0, int(self.config.min_frequency)))  # (<= 0: merge to exhaustion, as the reference does)
-            self.last_stats = ctx.stats()
-        vocab, merges = self._decode_merges(base, left, right, merged)
-        self._vocab = vocab
-        self._merges = merges
-        return self._model(vocab, merges)
-
-    # ------------------------------------------------------------------ batched device path (the context's word pool)
     @staticmethod
     def _batch_bytes(batch_bytes: int | None) -> int | None:
         if batch_bytes is None:
@@ -350,101 +406,50 @@ class BBPETrainer:
             raise ValueError("batch_bytes needs the device pre-tokeniser (YABPE_PRETOKENIZE=host is set)")
         return int(batch_bytes)
 
-    def _file_chunks(self, paths: Sequence[Path]) -> list[tuple[Path, int, int]]:
-        """The reference's chunks of every file, in order: (file, start, stop)."""
-        chunks: list[tuple[Path, int, int]] = []
-        for path in paths:
-            if not path.exists():
-                raise FileNotFoundError(f"File not found: {path}")
-            chunks.extend((path, start, stop) for start, stop in self._chunk_ranges(path))
-        return chunks
-
-    def _pool_chunks(self, ctx, chunks: Sequence[tuple[Path, int, int]], batch_bytes: int) -> None:
-        """Reads the chunks batch by batch (one batch on the host at a time), pre-tokenises each batch on the device and adds
-        its pre-tokens to ctx's word pool.  Pre-tokens never cross a chunk cut, so the pooled multiset is the one the
-        unbatched path pools."""
+    def _device_words(self, ctx, chunks: Sequence[tuple[Path, int, int]], batch_bytes: int | None, dedup: bool):
+        """The chunks' pre-tokens as device words for _run: file bytes -> yabpe_pretokenize -> word offsets in HBM (equal
+        pre-tokens are pooled by the load when `dedup`).  With `batch_bytes` the chunks are read batch by batch (one batch on
+        the host at a time) and each batch's pre-tokens added to ctx's word pool (yabpe_pool_add); the words are then the
+        pool's, with its counts and nothing left to pool.  Pre-tokens never cross a chunk cut, so the pooled multiset is the
+        same."""
         from . import _native
 
-        specials = list(self.config.special_tokens)
-        for first, end in group_chunks([stop - start for _p, start, stop in chunks], batch_bytes):
-            batch = chunks[first:end]
-            buf = np.empty(sum(stop - start for _p, start, stop in batch), dtype=np.uint8)
-            starts: list[int] = []
-            pos = 0
-            for path, start, stop in batch:
-                starts.append(pos)
-                with open(path, "rb") as f:
-                    f.seek(start)
-                    if f.readinto(memoryview(buf[pos:pos + stop - start])) != stop - start:
-                        raise OSError(f"File {path} changed while it was read")
-                pos += stop - start
+        def pretokenize(part):
+            buf, starts = read_chunks(part)
             try:
-                dev_text, dev_off, n_words = ctx.pretokenize(buf, chunk_starts=starts, special_tokens=specials)
+                return ctx.pretokenize(buf, chunk_starts=starts, special_tokens=list(self.config.special_tokens))
             except _native.Utf8Error as e:
-                k = max(i for i, s0 in enumerate(starts) if s0 <= e.position)
-                path, start, _stop = batch[k]
-                raise ValueError(f"File {path} contains invalid UTF-8 at position {start + e.position - starts[k]}.") from e
-            ctx.pool_add_ptr(dev_text, dev_off, n_words)
+                raise utf8_error(part, starts, e) from e
+
+        if batch_bytes is None:
+            return (*pretokenize(chunks), 0, dedup)
+        for first, end in group_chunks([stop - start for _p, start, stop in chunks], batch_bytes):
+            ctx.pool_add_ptr(*pretokenize(chunks[first:end]))
             ctx.pretokenize_free()
-            del buf
+        dev_bytes, dev_off, dev_freq, n_unique, _n_bytes = ctx.pool_get()
+        return dev_bytes, dev_off, n_unique, dev_freq, False
 
-    def _train_device_batched(self, paths: Sequence[Path], batch_bytes: int) -> BBPEModel:
-        """_train_device with the text going through in batches: files -> [batch -> yabpe_pretokenize -> yabpe_pool_add]* ->
-        yabpe_pool_get -> yabpe_load_words (the pool's counts; nothing left to pool) -> merge loop."""
-        from . import _native  # fails loudly when libyabpe.so / a GPU is missing
-
-        chunks = self._file_chunks(paths)
-        base = self._base_tokens()
-        num_merges = max(0, self.config.vocab_size - len(base))
-        empty = self._model({t: i for i, t in enumerate(base)}, [])
-        if not chunks:
-            self._vocab, self._merges = dict(empty.vocab), []
-            return empty
-        with self._context() as ctx:
-            self._pool_chunks(ctx, chunks, batch_bytes)
-            dev_bytes, dev_off, dev_freq, n_unique, _n_bytes = ctx.pool_get()
-            if n_unique == 0 or num_merges == 0:
-                self._vocab, self._merges = dict(empty.vocab), []
-                return empty
-            ctx.set_vocab(base)
-            ctx.load_words_ptr(dev_bytes, dev_off, n_unique, freq_ptr=dev_freq, dedup=False)
-            ctx.pool_clear()  # (the load copied what it needs)
-            left, right, merged, _count = ctx.train(num_merges, max(0, int(self.config.min_frequency)))
-            self.last_stats = ctx.stats()
-        vocab, merges = self._decode_merges(base, left, right, merged)
-        self._vocab = vocab
-        self._merges = merges
-        return self._model(vocab, merges)
-
-    def _gather_text(self, paths: Sequence[Path]):
-        """The files' chunks joined into one u8 buffer (None when empty), each chunk as (start in the buffer, file, start in
-        the file), and the number of bytes."""
-        pieces: list[np.ndarray] = []
-        chunks: list[tuple[int, Path, int]] = []
-        total = 0
-        for path in paths:
-            if not path.exists():
-                raise FileNotFoundError(f"File not found: {path}")
-            ranges = self._chunk_ranges(path)
-            if not ranges:
-                continue
-            data = np.fromfile(path, dtype=np.uint8)
-            for start, stop in ranges:  # (the reference can skip bytes between chunks, trainer.py:196-197)
-                chunks.append((total, path, start))
-                pieces.append(data[start:stop])
-                total += stop - start
-        text = None if not pieces else pieces[0] if len(pieces) == 1 else np.concatenate(pieces)
-        return text, chunks, total
-
-    def _pretokenize_device(self, ctx, text, chunks):
-        from . import _native
-
-        try:
-            return ctx.pretokenize(text, chunk_starts=[c[0] for c in chunks], special_tokens=list(self.config.special_tokens))
-        except _native.Utf8Error as e:
-            k = max(i for i, c in enumerate(chunks) if c[0] <= e.position)
-            g0, path, f0 = chunks[k]
-            raise ValueError(f"File {path} contains invalid UTF-8 at position {f0 + e.position - g0}.") from e
+    def _run(self, ctx, toks: list[bytes], words, triples, num_merges: int):
+        """The merge loop on ctx, from `toks` (with `triples`: the merges that made them, replayed by the load) over `words`:
+        host arrays (flat, off, freq) or device words (bytes address, offsets address, n, counts address or 0, dedup) -- with
+        counts they are the context's pool, which is cleared once the load has copied what it needs.  -> (vocab, merges)"""
+        ctx.set_vocab(toks)
+        if len(words) == 3:
+            if triples is None:
+                ctx.load_words(*words)
+            else:
+                ctx.load_words_resumed(*words, triples)
+        else:
+            dev_bytes, dev_off, n_words, dev_freq, dedup = words
+            if triples is None:
+                ctx.load_words_ptr(dev_bytes, dev_off, n_words, freq_ptr=dev_freq, dedup=dedup)
+            else:
+                ctx.load_words_resumed_ptr(dev_bytes, dev_off, n_words, triples, freq_ptr=dev_freq, dedup=dedup)
+            if dev_freq:
+                ctx.pool_clear()
+        left, right, merged, _count = ctx.train(num_merges, max(0, int(self.config.min_frequency)))  # (<= 0: merge to exhaustion, as the reference does)
+        self.last_stats = ctx.stats()
+        return self._decode_merges(toks, left, right, merged)
 
     # ------------------------------------------------------------------ continuing from a trained model
     def _resumable(self, model) -> tuple[list[bytes], tuple]:
@@ -470,98 +475,11 @@ class BBPETrainer:
                              f"reproduce its vocab ({len(toks)} tokens replayed, {len(vocab)} in the model){hint}")
         return toks, triples
 
-    def train_from(self, model, files: Sequence[str | Path], batch_bytes: int | None = None) -> BBPEModel:
-        """Continues training from `model` (a BBPEModel, or anything with .vocab, .merges and .special_tokens) on `files`:
-        more merges on the same corpus, or new merges learned from a new one.  Every existing id is kept; the result is
-        model.merges + the new merges and the extended vocab, exactly what train() gives when the corpus is the one the
-        model was trained on.  The iteration budget is max(0, vocab_size - len(base) - len(model.merges)) (a merge that
-        reused an id cost an iteration too, trainer.py:238).  An empty corpus or a zero budget returns the model unchanged.
-        Pre-tokenisation is train()'s (special tokens are ordinary words), on the device under the same size / environment
-        rule; the words are pooled (the flat layout does not apply).  `batch_bytes`: as train() takes it.
-        config.max_token_length constrains only the merges learned here: the model's own merges are replayed whatever their
-        length (the limit is not part of a saved model)."""
-        max_token_bytes(self.config)  # (a bad limit fails before any file is read or any device call is made)
-        pretokenizer(self.config)     # (and so does a bad pre-tokeniser or digit group, or a special they do not allow)
-        if not files:
-            raise ValueError("At least one file must be provided")
-        paths = [Path(f) if isinstance(f, str) else f for f in files]
-        pattern, group = pretokenizer(self.config)
-        if getattr(model, "pretokenizer", "gpt2") != PRETOKENIZERS[pattern]:
-            raise ValueError(f"cannot continue from this model: it was trained with pretokenizer = {getattr(model, 'pretokenizer', 'gpt2')!r}, "
-                             f"the trainer's is {PRETOKENIZERS[pattern]!r} (its merges would be replayed over words it never saw)")
-        if getattr(model, "digit_group", None) != (group or None):
-            raise ValueError(f"cannot continue from this model: it was trained with digit_group = {getattr(model, 'digit_group', None)!r}, "
-                             f"the trainer's is {group or None!r} (its merges would be replayed over words it never saw)")
-        toks, triples = self._resumable(model)
-        old_merges = [(bytes(l), bytes(r)) for l, r in model.merges]
-        num_merges = max(0, self.config.vocab_size - len(self._base_tokens()) - len(old_merges))
-
-        def unchanged() -> BBPEModel:
-            self._vocab, self._merges = dict(model.vocab), list(old_merges)
-            return self._model(self._vocab, self._merges)
-
-        for path in paths:
-            if not path.exists():
-                raise FileNotFoundError(f"File not found: {path}")
-        if num_merges == 0:
-            return unchanged()
-        from . import _native  # fails loudly when libyabpe.so / a GPU is missing
-
-        min_freq = max(0, int(self.config.min_frequency))
-        mode = os.environ.get("YABPE_PRETOKENIZE", "auto")
-        batch = self._batch_bytes(batch_bytes)
-        if batch is not None:
-            file_chunks = self._file_chunks(paths)
-            if not file_chunks:
-                return unchanged()
-            with self._context() as ctx:
-                self._pool_chunks(ctx, file_chunks, batch)
-                dev_bytes, dev_off, dev_freq, n_unique, _n_bytes = ctx.pool_get()
-                if n_unique == 0:
-                    return unchanged()
-                ctx.set_vocab(toks)
-                ctx.load_words_resumed_ptr(dev_bytes, dev_off, n_unique, triples, freq_ptr=dev_freq, dedup=False)
-                ctx.pool_clear()  # (the load copied what it needs)
-                left, right, merged, _count = ctx.train(num_merges, min_freq)
-                self.last_stats = ctx.stats()
-        elif mode == "gpu" or (mode == "auto" and sum(p.stat().st_size for p in paths) >= (1 << 20)):
-            text, chunks, total = self._gather_text(paths)
-            if total == 0:
-                return unchanged()
-            with self._context() as ctx:
-                dev_text, dev_off, n_words = self._pretokenize_device(ctx, text, chunks)
-                if n_words == 0:
-                    return unchanged()
-                ctx.set_vocab(toks)
-                ctx.load_words_resumed_ptr(dev_text, dev_off, n_words, triples, dedup=True)
-                left, right, merged, _count = ctx.train(num_merges, min_freq)
-                self.last_stats = ctx.stats()
-        else:
-            pooled = Counter(self._pretokenize(paths))
-            if not pooled:
-                return unchanged()
-            words = [t.encode("utf-8") for t in pooled]
-            off = np.zeros(len(words) + 1, dtype=np.uint64)
-            np.cumsum([len(w) for w in words], out=off[1:])
-            with self._context() as ctx:
-                ctx.set_vocab(toks)
-                ctx.load_words_resumed(np.frombuffer(b"".join(words), dtype=np.uint8), off,
-                                       np.fromiter(pooled.values(), dtype=np.uint64, count=len(pooled)), triples)
-                left, right, merged, _count = ctx.train(num_merges, min_freq)
-                self.last_stats = ctx.stats()
-        vocab, new_merges = self._decode_merges(toks, left, right, merged)
-        self._vocab, self._merges = vocab, old_merges + new_merges
-        return self._model(self._vocab, self._merges)
-
     @staticmethod
     def _decode_merges(base: Sequence[bytes], left, right, merged):
-        toks = list(base)
-        merges: list[tuple[bytes, bytes]] = []
-        for l, r, m in zip(left.tolist(), right.tolist(), merged.tolist()):
-            merges.append((toks[l], toks[r]))
-            if m == len(toks):  # a fresh id; otherwise the bytes already existed (trainer.py:298-300)
-                toks.append(toks[l] + toks[r])
-        return {t: i for i, t in enumerate(toks)}, merges
+        from ._native import decode_merges
+
+        return decode_merges(base, left, right, merged)
 
     def save(self, output_dir: str | Path) -> None:
         """vocab.json / merges.txt / special_tokens.json in the reference's format (trainer.py:94-117); with a digit group
@@ -656,12 +574,11 @@ class BBPETrainer:
                 raise ValueError(f"File {path} contains invalid UTF-8 at position {start + e.start}.") from e
             return [t for t in pattern.findall(text) if t]
 
+        check_files(files)
         out: list[str] = []
         with ThreadPoolExecutor(max_workers=self.config.max_workers) as pool:
             jobs = []
             for path in files:
-                if not path.exists():
-                    raise FileNotFoundError(f"File not found: {path}")
                 for start, stop in self._chunk_ranges(path):
                     jobs.append(pool.submit(run, path, start, stop))
             for job in jobs:  # submission order => deterministic output order (trainer.py:209)
@@ -678,21 +595,17 @@ class BBPETrainer:
         words = [bytes(s) for s in sequences]
         return self._merge_loop_words(words, None)
 
+    @staticmethod
+    def _host_words(words: Sequence[bytes], freq: np.ndarray | None):
+        """Words on the host as _run takes them: (their bytes back to back, len(words) + 1 offsets, freq)"""
+        off = np.zeros(len(words) + 1, dtype=np.uint64)
+        np.cumsum(np.fromiter((len(w) for w in words), dtype=np.uint64, count=len(words)), out=off[1:])
+        return np.frombuffer(b"".join(words), dtype=np.uint8), off, freq
+
     def _merge_loop_words(self, words: Sequence[bytes], freq: np.ndarray | None):
         max_token_bytes(self.config)
         base = self._base_tokens()
-        num_merges = max(0, self.config.vocab_size - len(base))  # trainer.py:238
-        if not words or num_merges == 0:
+        if not words or self._budget() == 0:
             return {t: i for i, t in enumerate(base)}, []
-        from . import _native  # fails loudly when libyabpe.so / a GPU is missing
-
-        lens = np.fromiter((len(w) for w in words), dtype=np.uint64, count=len(words))
-        off = np.zeros(len(words) + 1, dtype=np.uint64)
-        np.cumsum(lens, out=off[1:])
-        flat = np.frombuffer(b"".join(words), dtype=np.uint8)
         with self._context() as ctx:
-            ctx.set_vocab(base)
-            ctx.load_words(flat, off, freq)
-            left, right, merged, _count = ctx.train(num_merges, max(0, int(self.config.min_frequency)))  # (<= 0: merge to exhaustion, as the reference does)
-            self.last_stats = ctx.stats()
-        return self._decode_merges(base, left, right, merged)
+            return self._run(ctx, base, self._host_words(words, freq), None, self._budget())
