@@ -203,6 +203,14 @@ int yabpe_verify_table(yabpe_ctx *ctx, uint64_t *out_mismatches);
 /* Debug: decode the resident token stream back to bytes and return an order-independent checksum over
    (word bytes, segmentation) plus the number of words/tokens it saw (the long-word buffer included). */
 int yabpe_stream_checksum(yabpe_ctx *ctx, uint64_t *out_sum, uint64_t *out_words, uint64_t *out_tokens);
+/* Debug: copy the resident tile stream to the host as it lies in memory (the checksum above is order-independent and cannot
+   see where a word was placed).  *out_n_tiles and *out_flags are always written; call once with NULL buffers to size them.
+   Every buffer may be NULL: tiles 1024 u16 slots per tile, tile_len and tile_wbase one u32 per tile (tile_wbase only with
+   YABPE_DUMP_WBASE: the layout with frequencies), sig 512 rows of n_tiles u64 (only with YABPE_DUMP_SIG: the skip index is valid). */
+#define YABPE_DUMP_WBASE 0x1u
+#define YABPE_DUMP_SIG 0x2u
+int yabpe_stream_dump(yabpe_ctx *ctx, uint32_t *out_n_tiles, uint32_t *out_flags, uint16_t *tiles, uint32_t *tile_len,
+                      uint32_t *tile_wbase, uint64_t *sig);
 
 /* Synthetic corpus of SURVEY.md 8(d), generated on the device (bit-identical to yet_another_bpe/synth.py).
    Returns device pointers owned by the library (freed by yabpe_synth_free or yabpe_destroy). */

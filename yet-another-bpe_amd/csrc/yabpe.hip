@@ -840,12 +840,19 @@ int retile_flat(yabpe_ctx *c) {
         TRY(dmalloc(c, &c->tile_len_alt, new_n));
         c->tiles_alt_cap = new_n;
     }
-    TRY(fill_u16(c, c->tiles_alt, (uint64_t)new_n * CAP, YB_PAD));
-    HIPCHK(c, hipMemsetAsync(c->tile_len_alt, 0, (size_t)new_n * 4, c->stream));
-    P.base = base;
-    P.new_tiles = c->tiles_alt;
-    P.new_len = c->tile_len_alt;
-    hipLaunchKernelGGL(k_retile<true>, dim3(grid), dim3(BLOCK), 0, c->stream, P);
+    // retile_form 1: new tiles gathered whole (k_retile_gather); 0: fill, then scatter element by element
+    const bool gather = optv(c, "retile_form", 1) != 0;
+    if (gather) {
+        RetileGatherParams G{c->tiles, c->tile_len, c->n_tiles, base, c->tiles_alt, c->tile_len_alt, new_n};
+        hipLaunchKernelGGL(k_retile_gather, dim3(cdiv64(new_n, RETILE_GROUP)), dim3(BLOCK), 0, c->stream, G);
+    } else {
+        TRY(fill_u16(c, c->tiles_alt, (uint64_t)new_n * CAP, YB_PAD));
+        HIPCHK(c, hipMemsetAsync(c->tile_len_alt, 0, (size_t)new_n * 4, c->stream));
+        P.base = base;
+        P.new_tiles = c->tiles_alt;
+        P.new_len = c->tile_len_alt;
+        hipLaunchKernelGGL(k_retile<true>, dim3(grid), dim3(BLOCK), 0, c->stream, P);
+    }
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipStreamSynchronize(c->stream));
     std::swap(c->tiles, c->tiles_alt);
@@ -1255,10 +1262,14 @@ static int load_words_impl(yabpe_ctx *c, const uint8_t *bytes, const uint64_t *w
     }
     uint32_t long_cap = (uint32_t)optv(c, "long_cap", 1 << 16);
     uint32_t *d_long_word = nullptr;
+    // load_form 1: the byte paths write every tile whole (k_load_tiles), nothing to fill or clear first; 0: one thread per word
+    const bool tile_form = !rp && optv(c, "load_form", 1) != 0;
     for (int attempt = 0; attempt < 2; ++attempt) {
-        TRY(fill_u16(c, c->tiles, (uint64_t)c->n_tiles * CAP, YB_PAD));
-        HIPCHK(c, hipMemsetAsync(c->tile_len, 0, (size_t)c->n_tiles * 4, c->stream));
-        if (c->weighted) TRY(fill_u32(c, c->tile_wbase, c->n_tiles, 0xFFFFFFFFu));
+        if (!tile_form) {
+            TRY(fill_u16(c, c->tiles, (uint64_t)c->n_tiles * CAP, YB_PAD));
+            HIPCHK(c, hipMemsetAsync(c->tile_len, 0, (size_t)c->n_tiles * 4, c->stream));
+            if (c->weighted) TRY(fill_u32(c, c->tile_wbase, c->n_tiles, 0xFFFFFFFFu));
+        }
         HIPCHK(c, hipMemsetAsync(&c->scratch64[2], 0, 16, c->stream));  // [2] = long count (u32), [3] = long tokens
         S.release(d_long_word);
         HIPCHK(c, S.get(&d_long_word, long_cap));
@@ -1269,6 +1280,9 @@ static int load_words_impl(yabpe_ctx *c, const uint8_t *bytes, const uint64_t *w
                 LoadTokParams Q{d_wtok, d_wcnt, d_tokoff, d_off, (unsigned long long)off_base, (unsigned long long)n_words, c->tiles, c->tile_len,
                                 c->tile_wbase, P.long_count, P.long_total, d_long_word, long_cap};
                 hipLaunchKernelGGL(k_load_words_tok, dim3(cdiv64(n_words, BLOCK)), dim3(BLOCK), 0, c->stream, Q);
+            } else if (tile_form) {
+                LoadTilesParams T{P, (unsigned long long)(off_base + total_bytes), c->n_tiles};
+                hipLaunchKernelGGL(k_load_tiles, dim3(cdiv64(c->n_tiles, WPB * YB_LOAD_RUN)), dim3(BLOCK), 0, c->stream, T);
             } else {
                 hipLaunchKernelGGL(k_load_words, dim3(cdiv64(n_words, BLOCK)), dim3(BLOCK), 0, c->stream, P);
             }
@@ -2307,6 +2321,25 @@ int yabpe_stream_checksum(yabpe_ctx *c, uint64_t *out_sum, uint64_t *out_words, 
     if (out_sum) *out_sum = r[0];
     if (out_words) *out_words = r[1];
     if (out_tokens) *out_tokens = r[2];
+    return YABPE_OK;
+}
+
+int yabpe_stream_dump(yabpe_ctx *c, uint32_t *out_n_tiles, uint32_t *out_flags, uint16_t *tiles, uint32_t *tile_len, uint32_t *tile_wbase,
+                      uint64_t *sig) {
+    if (!c) return YABPE_E_INVALID;
+    HIPCHK(c, hipSetDevice(c->device));
+    if (!c->have_words) return fail(c, YABPE_E_INVALID, "no corpus loaded");
+    const bool has_sig = c->sig_valid && c->sig != nullptr && c->sig_stride >= c->n_tiles;
+    if (out_n_tiles) *out_n_tiles = c->n_tiles;
+    if (out_flags) *out_flags = (c->tile_wbase ? YABPE_DUMP_WBASE : 0u) | (has_sig ? YABPE_DUMP_SIG : 0u);
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (c->n_tiles == 0) return YABPE_OK;
+    const size_t n = c->n_tiles;
+    if (tiles) HIPCHK(c, hipMemcpy(tiles, c->tiles, n * CAP * sizeof(uint16_t), hipMemcpyDeviceToHost));
+    if (tile_len) HIPCHK(c, hipMemcpy(tile_len, c->tile_len, n * 4, hipMemcpyDeviceToHost));
+    if (tile_wbase && c->tile_wbase) HIPCHK(c, hipMemcpy(tile_wbase, c->tile_wbase, n * 4, hipMemcpyDeviceToHost));
+    if (sig && has_sig)  // (the rows without the padding of their stride)
+        HIPCHK(c, hipMemcpy2D(sig, n * 8, c->sig, (size_t)c->sig_stride * 8, n * 8, SIG_ROWS, hipMemcpyDeviceToHost));
     return YABPE_OK;
 }
 

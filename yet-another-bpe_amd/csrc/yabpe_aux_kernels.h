@@ -494,7 +494,105 @@ __global__ __launch_bounds__(BLOCK) void k_retile(RetileParams P) {
     }
 }
 
-// ================================================================ latency probe (measurement; include/yabpe.h yabpe_latency_probe)
+// The gathering form of the second pass (load_logic.h): a workgroup owns RETILE_GROUP consecutive NEW tiles.  It starts their
+// images as PAD in LDS, finds the first old tile of its range in base[] and walks forward, its waves taking old tiles in
+// turn and dropping each kept element into its image slot; then every new tile leaves whole with 16-byte stores, new_len
+// with a plain store -- nothing to fill or clear beforehand, no global scatter, no global atomic.
+// (Building the group's signatures in the same workgroup was measured and is not here: the 33 KB of signatures in LDS left
+// 3 workgroups per CU instead of 6, and the pass took 3.17 ms where this one and k_build_sig take 1.43 + 1.11.)
+constexpr int RETILE_GROUP = 8;
+struct RetileGatherParams {
+    const uint16_t *tiles;
+    const uint32_t *tile_len;
+    uint32_t n_tiles;
+    const unsigned long long *base;  // exclusive scan of kept, n_tiles + 1 entries
+    uint16_t *new_tiles;
+    uint32_t *new_len;
+    uint32_t new_n;
+};
+
+__global__ __launch_bounds__(BLOCK) void k_retile_gather(RetileGatherParams P) {
+    __shared__ __attribute__((aligned(16))) uint16_t s_img[RETILE_GROUP][CAP];
+    __shared__ __attribute__((aligned(16))) uint16_t s_stage[WPB][8 + CAP + 8];
+    __shared__ uint32_t s_len[RETILE_GROUP];
+    __shared__ uint32_t s_t0;
+    const int lane = threadIdx.x & 63;
+    const int wib = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const uint32_t g0 = blockIdx.x * RETILE_GROUP;
+    const unsigned long long k_lo = (unsigned long long)g0 * SPAN, k_hi = k_lo + (unsigned long long)RETILE_GROUP * SPAN;
+    uint16_t *stg = s_stage[wib];
+    if (lane < 8) {
+        stg[lane] = YB_PAD;
+        stg[8 + CAP + lane] = YB_PAD;
+    }
+    for (int i = threadIdx.x; i < RETILE_GROUP * CAP / 8; i += BLOCK)
+        reinterpret_cast<uint4 *>(&s_img[0][0])[i] = make_uint4(PADPAD, PADPAD, PADPAD, PADPAD);
+    if (threadIdx.x < RETILE_GROUP) s_len[threadIdx.x] = 0u;
+    if (wib == 0) {  // the first old tile that holds a kept element numbered >= k_lo
+        unsigned long long lo = 0, hi = P.n_tiles;
+        while (lo < hi) {
+            const unsigned long long t = lo + (unsigned long long)lane * yb_kary_stride(lo, hi, 64u);
+            bool ge = false;
+            if (t < hi) ge = P.base[t + 1] > k_lo;
+            const unsigned long long m = __ballot(ge);
+            yb_kary_narrow(lo, hi, 64u, m ? (uint32_t)__builtin_ctzll(m) : 64u);
+        }
+        if (lane == 0) s_t0 = (uint32_t)lo;
+    }
+    __syncthreads();
+    TokAt T{stg};
+    NoMerge M;
+    for (uint32_t tile = s_t0 + wib; tile < P.n_tiles; tile += WPB) {
+        const unsigned long long base = P.base[tile];
+        if (base >= k_hi) break;  // (every word of this tile and of the ones behind it starts behind the range)
+        const uint32_t len = P.tile_len[tile];
+        if (len == 0 || P.base[tile + 1] == base) continue;
+        TileRegs r = load_tile(P.tiles, tile, len, lane);
+        wave_sync();
+        stage_tile(stg, r, lane);
+        wave_sync();
+        const int rounds = (len + 63) >> 6;
+        uint32_t outpos = 0;
+        uint32_t carry_ws = 0;  // kept-index where the current word starts
+        for (int k = 0; k < rounds; ++k) {
+            const int p = k * 64 + lane;
+            uint32_t o = 0;
+            const int keep = yb_keep(p, 0u, true, T, M, o);
+            const unsigned long long km = __ballot(keep);
+            const unsigned long long sm = __ballot(keep && o == YB_SEP);
+            const uint32_t kidx = outpos + __popcll(km & lanemask_lt(lane));
+            const unsigned long long lower = sm & lanemask_lt(lane);
+            uint32_t ws = carry_ws;
+            if (lower) {
+                const int j = 63 - __clzll((long long)lower);
+                ws = outpos + __popcll(km & ((j == 63) ? ~0ull : ((2ull << j) - 1ull)));
+            }
+            if (keep) {
+                const YbGatherDest d = yb_gather_dest(base + kidx, base + ws, k_lo, (uint32_t)RETILE_GROUP, (uint32_t)SPAN);
+                if (d.mine && d.slot < (uint32_t)CAP) {
+                    s_img[d.tile][d.slot] = (uint16_t)o;
+                    if (o == YB_SEP) atomicMax(&s_len[d.tile], d.slot + 1u);  // one per word, in LDS
+                }
+            }
+            if (sm) {
+                const int j = 63 - __clzll((long long)sm);
+                carry_ws = outpos + __popcll(km & ((j == 63) ? ~0ull : ((2ull << j) - 1ull)));
+            }
+            outpos += __popcll(km);
+        }
+    }
+    __syncthreads();
+    for (int k = wib; k < RETILE_GROUP; k += WPB) {
+        const uint32_t nt = g0 + k;
+        if (nt >= P.new_n) continue;
+        uint4 *out = reinterpret_cast<uint4 *>(P.new_tiles + (size_t)nt * CAP);
+        out[lane] = reinterpret_cast<const uint4 *>(s_img[k])[lane];
+        out[64 + lane] = reinterpret_cast<const uint4 *>(s_img[k])[64 + lane];
+        if (lane == 0) P.new_len[nt] = s_len[k];
+    }
+}
+
+// ================================================================ latency probe (measurement;include/yabpe.h yabpe_latency_probe)
 // The pieces the per-merge launch is built from, measured on an otherwise idle device: one lane walks a chain of dependent
 // accesses through a table far larger than the caches, so every hop is a full trip to memory.  The chain is the full-period
 // affine map x -> (a x + c) mod 2^k (a = 1 mod 4, c odd: one cycle over all entries): consecutive hops land on unrelated

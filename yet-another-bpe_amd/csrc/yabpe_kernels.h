@@ -23,6 +23,7 @@
 #include <type_traits>
 
 #include "limit_logic.h"
+#include "load_logic.h"
 #include "steal_logic.h"
 #include "tile_logic.h"
 
@@ -2646,6 +2647,119 @@ __global__ __launch_bounds__(BLOCK) void k_load_words(LoadParams P) {
     for (uint32_t j = 0; j < (uint32_t)L; ++j) dst[j] = src[j];
     dst[L] = YB_SEP;
     atomicMax(&P.tile_len[tile], slot + (uint32_t)L + 1);
+}
+
+// The tile-centric form of k_load_words (load_logic.h): a wave owns YB_LOAD_RUN consecutive tiles and writes each one whole --
+// PAD tail, tile_len and tile_wbase included -- so nothing has to be filled or cleared beforehand and no word touches
+// tile_len with an atomic.  Per tile: the image starts as PAD in LDS, the tile's byte window arrives in aligned 16-byte
+// pieces, one lane per word widens its bytes into the image, and the image leaves with two 16-byte stores per lane.
+struct LoadTilesParams {
+    LoadParams L;
+    unsigned long long off_end; // off[n_words]: the corpus is bytes[off_base, off_end)
+    uint32_t n_tiles;
+};
+constexpr int LOAD_PIECES = (SPAN + LMAX - 1 + 2 * (YB_LOAD_STAGE - 1)) / YB_LOAD_STAGE; // yb_load_window_pieces(SPAN, LMAX)
+
+__global__ __launch_bounds__(BLOCK) void k_load_tiles(LoadTilesParams Q) {
+    __shared__ __attribute__((aligned(16))) uint16_t s_img[WPB][CAP];
+    __shared__ __attribute__((aligned(16))) uint8_t s_byte[WPB][LOAD_PIECES * YB_LOAD_STAGE];
+    const LoadParams &P = Q.L;
+    const int lane = threadIdx.x & 63;
+    const int wib = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const unsigned long long run0 = ((unsigned long long)blockIdx.x * WPB + wib) * YB_LOAD_RUN;
+    if (run0 >= Q.n_tiles) return; // (whole waves leave; the kernel has no workgroup barrier)
+    const uint32_t t0 = (uint32_t)run0;
+    const uint32_t t1 = (uint32_t)(run0 + YB_LOAD_RUN < Q.n_tiles ? run0 + YB_LOAD_RUN : Q.n_tiles);
+    const bool weighted = P.tile_wbase != nullptr;
+    uint16_t *img = s_img[wib];
+    uint8_t *sb = s_byte[wib];
+    const uint8_t *c_lo = P.bytes + P.off_base, *c_hi = P.bytes + Q.off_end;
+
+    // ---- the run's first word: 64 probes per step
+    unsigned long long w0 = 0, hi = P.n_words;
+    {
+        const unsigned long long target = (unsigned long long)t0 * SPAN;
+        while (w0 < hi) {
+            const unsigned long long w = w0 + (unsigned long long)lane * yb_kary_stride(w0, hi, 64u);
+            bool ge = false;
+            if (w < hi) ge = yb_load_pos(P.off[w], P.off_base, w) >= target;
+            const unsigned long long m = __ballot(ge);
+            yb_kary_narrow(w0, hi, 64u, m ? (uint32_t)__builtin_ctzll(m) : 64u);
+        }
+    }
+
+    const uint32_t pad2 = PADPAD;
+    for (uint32_t t = t0; t < t1; ++t) {
+        const unsigned long long p0 = (unsigned long long)t * SPAN, p1 = p0 + SPAN;
+        reinterpret_cast<uint4 *>(img)[lane] = make_uint4(pad2, pad2, pad2, pad2);
+        reinterpret_cast<uint4 *>(img)[lane + 64] = make_uint4(pad2, pad2, pad2, pad2);
+        uint32_t len = 0, wbase = 0xFFFFFFFFu;
+        unsigned long long o_first = 0;
+        bool any = false;
+        if (w0 < P.n_words) {
+            o_first = P.off[w0];
+            const unsigned long long pos = yb_load_pos(o_first, P.off_base, w0);
+            any = pos >= p0 && pos < p1;
+        }
+        if (any) { // (else: a tile behind a word longer than its span -- no word starts here)
+            wbase = (uint32_t)w0;
+            const uint8_t *a0 = P.bytes + o_first;
+            const uint8_t *gbase = reinterpret_cast<const uint8_t *>(yb_load_window_base((unsigned long long)reinterpret_cast<uintptr_t>(a0)));
+            for (int pc = lane; pc < LOAD_PIECES; pc += 64) {
+                const uint8_t *g = gbase + pc * YB_LOAD_STAGE;
+                if (g >= c_lo && g + YB_LOAD_STAGE <= c_hi) {
+                    *reinterpret_cast<uint4 *>(sb + pc * YB_LOAD_STAGE) = *reinterpret_cast<const uint4 *>(g);
+                } else {
+                    for (int j = 0; j < YB_LOAD_STAGE; ++j)
+                        if (g + j >= c_lo && g + j < c_hi) sb[pc * YB_LOAD_STAGE + j] = g[j];
+                }
+            }
+            wave_sync();
+            const uint32_t sb0 = (uint32_t)(a0 - gbase); // where the first word's bytes lie in the window
+            uint32_t n_in = 64;
+            while (n_in == 64u) {
+                const unsigned long long w = w0 + lane;
+                bool in = false;
+                unsigned long long o0 = 0, pos = 0;
+                if (w < P.n_words) {
+                    o0 = P.off[w];
+                    pos = yb_load_pos(o0, P.off_base, w);
+                    in = pos >= p0 && pos < p1;
+                }
+                uint32_t len_end = 0;
+                if (in) {
+                    const unsigned long long L = P.off[w + 1] - o0;
+                    const YbLoadWord r = yb_load_word(pos, p0, L, weighted, (uint32_t)LMAX);
+                    len_end = r.len_end;
+                    if (r.kind == YB_LOAD_COPY) {
+                        const uint8_t *src = sb + sb0 + (uint32_t)(o0 - o_first);
+                        uint16_t *dst = img + r.slot;
+                        for (uint32_t j = 0; j < (uint32_t)L; ++j) dst[j] = src[j];
+                        dst[L] = YB_SEP;
+                    } else if (r.kind == YB_LOAD_LONG) {
+                        const uint32_t idx = atomicAdd(P.long_count, 1u);
+                        if (idx < P.long_cap) P.long_word[idx] = (uint32_t)w;
+                        atomicAdd(P.long_total, L);
+                        if (r.sep_only) img[r.slot] = YB_SEP; // placeholder keeps word indices aligned
+                    }
+                }
+                // (slots rise with the word index, so the last word that stores anything ends the tile)
+                const unsigned long long lm = __ballot(len_end != 0u);
+                if (lm) len = (uint32_t)__shfl((int)len_end, 63 - __clzll((long long)lm));
+                n_in = (uint32_t)__popcll(__ballot(in));
+                w0 += n_in;
+            }
+        }
+        wave_sync();
+        uint4 *out = reinterpret_cast<uint4 *>(P.tiles + (size_t)t * CAP);
+        out[lane] = reinterpret_cast<const uint4 *>(img)[lane];
+        out[lane + 64] = reinterpret_cast<const uint4 *>(img)[lane + 64];
+        if (lane == 0) {
+            P.tile_len[t] = len;
+            if (weighted) P.tile_wbase[t] = wbase;
+        }
+        wave_sync(); // (the next tile's PAD must not overtake these reads)
+    }
 }
 
 struct LoadLongParams {

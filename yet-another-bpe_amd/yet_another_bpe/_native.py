@@ -89,7 +89,7 @@ ALLGATHER_FN = ctypes.CFUNCTYPE(c_int, c_void_p, c_void_p, c_void_p, c_uint64)
 SYMBOLS = [
     "yabpe_abi_version", "yabpe_device_count", "yabpe_create", "yabpe_destroy", "yabpe_last_error", "yabpe_set_option",
     "yabpe_set_vocab", "yabpe_load_words", "yabpe_train", "yabpe_n_tokens", "yabpe_token_bytes", "yabpe_stats",
-    "yabpe_iter_log", "yabpe_event_log", "yabpe_latency_probe", "yabpe_verify_table", "yabpe_stream_checksum", "yabpe_synth_generate", "yabpe_synth_generate_lex", "yabpe_synth_free",
+    "yabpe_iter_log", "yabpe_event_log", "yabpe_latency_probe", "yabpe_verify_table", "yabpe_stream_checksum", "yabpe_stream_dump", "yabpe_synth_generate", "yabpe_synth_generate_lex", "yabpe_synth_free",
     "yabpe_memcpy_d2h", "yabpe_memcpy_h2d", "yabpe_pretokenize", "yabpe_pretokenize_free",
     "yabpe_comm_unique_id", "yabpe_comm_init", "yabpe_comm_init_custom", "yabpe_comm_enable_p2p",
     "yabpe_encode_set_model", "yabpe_encode", "yabpe_encode_spans", "yabpe_encode_dropout", "yabpe_encode_free", "yabpe_encode_stats", "yabpe_encode_checksum",
@@ -128,6 +128,7 @@ def lib() -> ctypes.CDLL:
         L.yabpe_event_log.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_uint32, POINTER(c_uint32)]
         L.yabpe_verify_table.argtypes = [c_void_p, POINTER(c_uint64)]
         L.yabpe_stream_checksum.argtypes = [c_void_p, POINTER(c_uint64), POINTER(c_uint64), POINTER(c_uint64)]
+        L.yabpe_stream_dump.argtypes = [c_void_p, POINTER(c_uint32), POINTER(c_uint32), c_void_p, c_void_p, c_void_p, c_void_p]
         L.yabpe_synth_generate.argtypes = [c_void_p, c_uint64, c_uint32, c_uint64, c_void_p, c_uint32, c_int,
                                            POINTER(c_void_p), POINTER(c_void_p), POINTER(c_uint64), POINTER(c_uint64)]
         L.yabpe_synth_generate_lex.argtypes = [c_void_p, c_uint64, c_uint32, c_uint64, c_void_p, c_void_p,
@@ -330,6 +331,21 @@ class Context:
         a, b, c = c_uint64(0), c_uint64(0), c_uint64(0)
         self._chk(lib().yabpe_stream_checksum(self._h, byref(a), byref(b), byref(c)))
         return a.value, b.value, c.value
+
+    def stream_dump(self) -> dict:
+        """The resident tile stream as it lies in memory: n_tiles, tiles (n_tiles x 1024 u16), tile_len, tile_wbase (None in
+        the flat layout) and sig (512 x n_tiles u64, None while the skip index is not valid)."""
+        n, fl = c_uint32(0), c_uint32(0)
+        self._chk(lib().yabpe_stream_dump(self._h, byref(n), byref(fl), None, None, None, None))
+        nt = n.value
+        tiles = np.zeros((nt, 1024), dtype=np.uint16)
+        tlen = np.zeros(nt, dtype=np.uint32)
+        wbase = np.zeros(nt, dtype=np.uint32) if fl.value & 1 else None
+        sig = np.zeros((512, nt), dtype=np.uint64) if fl.value & 2 else None
+        if nt:
+            self._chk(lib().yabpe_stream_dump(self._h, byref(n), byref(fl), tiles.ctypes.data, tlen.ctypes.data,
+                                              None if wbase is None else wbase.ctypes.data, None if sig is None else sig.ctypes.data))
+        return {"n_tiles": nt, "tiles": tiles, "tile_len": tlen, "tile_wbase": wbase, "sig": sig}
 
     def synth_generate(self, target_bytes: int, n_types: int, seed: int, alphabet: bytes, space_prefix: bool):
         """-> (dev_bytes_ptr, dev_off_ptr, n_words, n_bytes); buffers live until close()/synth_free()."""
