@@ -202,6 +202,13 @@ def gpu_sharded(rank, world, dist, scenario, transport="torch"):
         flat, off = helpers.flatten(tie_helpers.stems())
         freq, merges = None, 400
         opts.update({"split": 1, "batch_max": 16, "cand_min_count": 1})
+    elif scenario == "huge_weights":  # word frequencies up to 2^32-1: a rank's own counts can stay below 2^32 while the sums do not
+        from tests import big_count_helpers
+
+        types, freqs = big_count_helpers.named("small2")
+        flat, off = helpers.flatten(list(types))
+        freq, merges = big_count_helpers.freq_array(freqs), 300
+        opts.update({"split": 1, "batch_max": 16, "cand_min_count": 1})
     else:
         raise ValueError(scenario)
     left, right, merged, count, stats = train_sharded(lambda: _native.Context(0), flat, off, freq, base, merges, 1, rank, world,

@@ -124,7 +124,13 @@ def decode(specials, left, right, merged):
 
 def assert_equals_oracle(got, name, mult=1, n_merges=N_MERGES, min_frequency=1, upto=None, what=None):
     """got: (left, right, merged, count) of the device; the oracle's first `upto` merges (all of them by default)."""
-    vocab, merges, ids = expected(name, mult, n_merges, min_frequency)
+    assert_equals(got, expected(name, mult, n_merges, min_frequency), corpus(name)[2], upto, what)
+
+
+def assert_equals(got, want, specials=(), upto=None, what=None):
+    """The comparison of assert_equals_oracle with the oracle's result handed in: want = (vocab, merges, ids) of
+    oracle.train_flat(..., return_ids=True) on the corpus the device was given (tests/test_gpu_big_counts.py brings its own)."""
+    vocab, merges, ids = want
     n = len(merges) if upto is None else upto
     left, right, merged, count = got
     assert len(left) == n, (what, len(left), n)
@@ -132,7 +138,7 @@ def assert_equals_oracle(got, name, mult=1, n_merges=N_MERGES, min_frequency=1, 
         if not np.array_equal(arr, ids[field][:n]):
             k = int(np.flatnonzero(np.asarray(arr) != ids[field][:n])[0])
             raise AssertionError(f"{what}: {field} differs first at merge {k}: device {arr[k]} oracle {ids[field][k]}")
-    v, m = decode(corpus(name)[2], left, right, merged)
+    v, m = decode(specials, left, right, merged)
     assert m == merges[:n], what
     if upto is None:
         assert v == vocab, what

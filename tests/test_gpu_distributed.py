@@ -31,11 +31,17 @@ def _expect(scenario):
         from tests import tie_helpers
 
         return oracle.merge_loop(tie_helpers.stems(), 257 + 400, 1, SP)[1]
+    if scenario == "huge_weights":
+        from tests import big_count_helpers
+
+        types, freqs = big_count_helpers.named("small2")
+        return oracle.train_flat(*helpers.flatten(list(types)), 257 + 300, 1, SP, freq=big_count_helpers.freq_array(freqs))[1]
     words = [b" " * 900, b"ab" * 700, b"xyz" * 50, b"abcabc", b"  ", b"aaa"] * 3 + [b"hello world"] * 5
     return oracle.merge_loop(words, 257 + 120, 1, SP)[1]
 
 
-@pytest.mark.parametrize("scenario", ["corpus_en_flat", "corpus_en_weighted", "synthetic_small_buffers", "synthetic_medium", "synthetic_tight_exchange", "long_words"])
+@pytest.mark.parametrize("scenario", ["corpus_en_flat", "corpus_en_weighted", "synthetic_small_buffers", "synthetic_medium", "synthetic_tight_exchange", "long_words",
+                                      "huge_weights"])
 def test_two_ranks_one_gpu(scenario):
     exp = _expect(scenario)
     outs = dist_workers.spawn(dist_workers.gpu_sharded, 2, scenario, timeout=900)
@@ -60,7 +66,7 @@ def test_two_ranks_walk_the_same_window():
 
 
 @pytest.mark.parametrize("world,scenario", [(2, "corpus_en_flat"), (2, "corpus_en_weighted"), (2, "synthetic_small_buffers"), (2, "synthetic_tight_exchange"),
-                                            (2, "long_words"), (4, "synthetic_medium"), (4, "corpus_en_flat_direct_store")])
+                                            (2, "long_words"), (4, "synthetic_medium"), (4, "corpus_en_flat_direct_store"), (2, "huge_weights")])
 def test_peer_to_peer_exchange(world, scenario):
     """The same scenarios with the exchange going peer to peer (yabpe_comm_enable_p2p: hipIpc-mapped receive buffers, one
     push-and-wait launch per batch instead of an all-gather; the areas are mapped once, at a fixed size -- growing exchange
