@@ -254,15 +254,28 @@ int yabpe_memcpy_h2d(yabpe_ctx *ctx, void *dst_dev, const void *src_host, uint64
  * Split pattern: option "split_pattern" (yabpe_set_option; 0, the default: the GPT-2 pattern; 1: the cl100k pattern of GPT-4,
  * Llama-3 (digit_group 3) and Qwen2 (digit_group 1),
  *   (?i:'s|'t|'re|'ve|'m|'ll|'d)|[^\r\n\p{L}\p{N}]?\p{L}+|\p{N}{1,G}| ?[^\s\p{L}\p{N}]+[\r\n]*|\s*[\r\n]+|\s+(?!\S)|\s+
- * with G = the option "digit_group", which must then be 1 .. 255).  Read by the same four calls; any other value, or 1 with
- * digit_group 0, makes the call return YABPE_E_INVALID.  Against GPT-2: contractions match in either case; one character that
+ * with G = the option "digit_group", which must then be 1 .. 255).  Read by the same four calls; any value but 0, 1 and 3 (below), or 1
+ * with digit_group 0, makes the call return YABPE_E_INVALID.  Against GPT-2: contractions match in either case; one character that
  * is no letter, digit, CR or LF joins the letter run behind it; digits take no space in front; a run of punctuation swallows
  * the CR / LF behind it, and a whitespace run that holds a CR / LF is cut after its last one (csrc/split4_logic.h has the
  * rule per position).  With 1 a special token of yabpe_pretokenize whose first character is \s or \p{N} is rejected
  * (YABPE_E_INVALID, the message names it): whether a token starts at a whitespace character can depend on the whole
  * whitespace run, which is known only after the specials are placed.  The newline rules cost three more kernels in front of
  * the digit groups (two segmented scans, linear on a file of blank lines or a newline and a gigabyte of spaces); with 0
- * nothing of this is launched or allocated, and the GPT-2 kernels are the ones that run. */
+ * nothing of this is launched or allocated, and the GPT-2 kernels are the ones that run.
+ * 3: the o200k_base pattern of GPT-4o, the o-series and gpt-oss (2 is reserved and refused),
+ *   [^\r\n\p{L}\p{N}]?[\p{Lu}\p{Lt}\p{Lm}\p{Lo}\p{M}]*[\p{Ll}\p{Lm}\p{Lo}\p{M}]+(?i:'s|'t|'re|'ve|'m|'ll|'d)?
+ *   |[^\r\n\p{L}\p{N}]?[\p{Lu}\p{Lt}\p{Lm}\p{Lo}\p{M}]+[\p{Ll}\p{Lm}\p{Lo}\p{M}]*(?i:'s|'t|'re|'ve|'m|'ll|'d)?
+ *   |\p{N}{1,G}| ?[^\s\p{L}\p{N}]+[\r\n/]*|\s*[\r\n]+|\s+(?!\S)|\s+
+ * again with G = "digit_group" in 1 .. 255 (3 with digit_group 0: YABPE_E_INVALID).  Against cl100k: a word is cut where its
+ * case changes (HTTPServer | " foo" | Bar), the contraction stays with its word, \p{M} counts as a letter inside a word, and
+ * "/" is kept behind the newlines that follow punctuation.  No rule of it has bounded reach, so the device runs it as a
+ * scanner of 13 states: classes, one backward scan of two look-ahead bits, one forward scan of state-transition functions
+ * (csrc/split5_logic.h; nine kernels in place of the fused pass, one more array of n_bytes, linear on any text).  With 3 a
+ * special token of yabpe_pretokenize is taken wherever the scanner stands at a token boundary at its first byte, so
+ * occurrences must never overlap: rejected (YABPE_E_INVALID, the message names the specials) are a special that contains
+ * another one, a special one of whose proper suffixes begins a special (itself included; equal specials count as one), and,
+ * as with 1, a special whose first character is \s or \p{N}.  "<|endoftext|>", "<|im_start|>" and "<|im_end|>" pass. */
 int yabpe_pretokenize(yabpe_ctx *ctx, const uint8_t *text, uint64_t n_bytes, const uint64_t *chunk_off, uint32_t n_chunks,
                       const uint8_t *special_bytes, const uint32_t *special_off, uint32_t n_special,
                       const uint8_t **out_dev_text, uint64_t **out_dev_word_off, uint64_t *out_n_words, int64_t *out_bad_pos);
@@ -332,7 +345,8 @@ int yabpe_encode_set_model(yabpe_ctx *ctx, const uint8_t *vocab_bytes, const uin
  * pattern, in yabpe_encode, yabpe_encode_spans and yabpe_encode_dropout alike -- BBPETokenizer(digit_group=G).  The specials
  * are split out first and every piece between them is a text of its own, so here a special may begin with a digit.
  * Option "split_pattern" (see yabpe_pretokenize) likewise: 1 gives the pre-tokens of the cl100k pattern in all three calls --
- * BBPETokenizer(pretokenizer="cl100k") -- and here a special may begin with whitespace too. */
+ * BBPETokenizer(pretokenizer="cl100k") -- and here a special may begin with whitespace too; 3 gives those of the o200k_base
+ * pattern -- BBPETokenizer(pretokenizer="o200k_base") -- and here the specials are unrestricted. */
 int yabpe_encode(yabpe_ctx *ctx, const uint8_t *text, uint64_t n_bytes, const uint64_t *doc_off, uint32_t n_docs,
                  uint32_t **out_dev_ids, uint64_t **out_dev_doc_off, uint64_t *out_n_ids, int64_t *out_bad_pos);
 /* yabpe_encode that also says which piece of its document every id was made from.  Arguments, errors and ownership are

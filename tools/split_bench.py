@@ -1,13 +1,15 @@
 #!/usr/bin/env python3
-"""Dev tool: what the cl100k split pattern (option "split_pattern" = 1) costs the device pre-tokeniser against
-the GPT-2 pattern with the same digit group.  Synthetic text resident in HBM, yabpe_pretokenize timed on the host around the
+"""Dev tool: what the cl100k and the o200k_base split pattern (option "split_pattern" = 1 and 3) cost the
+device pre-tokeniser against the GPT-2 pattern with the same digit group.  Synthetic text resident in HBM, yabpe_pretokenize timed on the host around the
 call (it ends in a synchronise; allocation included, as in group_bench.py), every variant in turn inside every repetition so
 that drift hits them alike.
-   python tools/split_bench.py [--mib 1024] [--pattern 0,1] [--digit-group 3] [--text words,mixed,blank,nlspaces] [--reps 7]
+   python tools/split_bench.py [--mib 1024] [--pattern 0,1,3] [--digit-group 3] [--text words,mixed,blank,nlspaces] [--reps 7]
 Texts: `words` and `mixed` as in group_bench.py; `blank` = nothing but U+000A (a file of blank lines: one pre-token, every
 byte inside one newline run); `nlspaces` = one U+000A and then nothing but spaces (every byte behind the first waits for the
 backward scan).  The last two are the cases the newline pass must stay linear on: run them at two sizes and compare the time
-per byte.  YABPE_LIB=<another libyabpe.so> measures another build with --pattern 0.  Prints one JSON line per (text, pattern)."""
+per byte.  The chains of the o200k_base scanner, likewise: `kana` = nothing but U+30A2 (one word of \\p{Lo}), `camel` = "A" U+30A2
+repeated (upper case and \\p{Lo} in turn: one word), `upper` = nothing but "A", `bang` = nothing but "!", `contr` = "'s" repeated
+behind a letter, `nlslash` = U+000A "/" repeated behind a "!".  YABPE_LIB=<another libyabpe.so> measures another build with --pattern 0.  Prints one JSON line per (text, pattern)."""
 import argparse
 import json
 import statistics
@@ -33,14 +35,20 @@ patterns = [int(p) for p in args.pattern.split(",")]
 SP = ["<|endoftext|>"]
 
 
-def fill(ctx, n: int, byte: int, first: int) -> tuple[int, int]:
-    """n bytes of `byte` on the device, the first one `first`: written in pieces over a generated buffer of that size"""
+def fill(ctx, n: int, unit, first: int) -> tuple[int, int]:
+    """About n bytes of `unit` (a byte value or bytes) repeated on the device, whole units only, the first byte `first`: written in
+    pieces over a generated buffer of that size"""
+    unit = bytes([unit]) if isinstance(unit, int) else unit
     pb, _po, _nw, nb = ctx.synth_generate(n, 1_000, 3, b"ab", False)
-    piece = np.full(min(nb, 64 << 20), byte, np.uint8)
+    nb -= nb % len(unit)
+    piece = np.frombuffer(unit * (min(nb, 64 << 20) // len(unit)), np.uint8)
     for a in range(0, nb, len(piece)):
         ctx.h2d(pb + a, piece[:min(len(piece), nb - a)])
     ctx.h2d(pb, np.array([first], np.uint8))
     return pb, nb
+
+
+CHAINS = {"kana": ("ア".encode(), 0xE3), "camel": ("Aア".encode(), 0x41), "upper": (b"A", 0x41), "bang": (b"!", 0x21), "contr": (b"'s", 0x61), "nlslash": (b"\n/", 0x21)}
 
 
 for kind in args.text.split(","):
@@ -54,6 +62,8 @@ for kind in args.text.split(","):
             pb, nb = fill(ctx, args.mib << 20, 0x0A, 0x0A)
         elif kind == "nlspaces":
             pb, nb = fill(ctx, args.mib << 20, 0x20, 0x0A)
+        elif kind in CHAINS:
+            pb, nb = fill(ctx, args.mib << 20, *CHAINS[kind])
         else:
             raise SystemExit(f"unknown text {kind!r}")
         ms = {p: [] for p in patterns}

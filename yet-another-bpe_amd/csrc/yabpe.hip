@@ -33,6 +33,7 @@
 #include "yabpe_replay_kernels.h"
 #include "yabpe_pool_kernels.h"
 #include "unicode_classes.inc"
+#include "unicode_subclasses.inc"
 
 using namespace yb;
 
@@ -150,6 +151,7 @@ struct yabpe_ctx {
     std::vector<void *> synth_bufs;
     std::vector<void *> pretok_bufs;          // staged text / word offsets handed out by yabpe_pretokenize
     uint8_t *pt_cls = nullptr;                // class per code point (unicode_classes.inc expanded), built on first use
+    uint8_t *pt_cls5 = nullptr;               // the o200k_base pattern's table (pt5_table_entry), built on its first use
     // encoder (yabpe_encode_set_model / yabpe_encode)
     bool have_enc_model = false;
     unsigned long long *enc_keys = nullptr;   // pair table: (a << 32 | b) -> enc_vals (rank, result)
@@ -903,12 +905,15 @@ static int digit_group_opt(yabpe_ctx *c, uint32_t *G) {
     return YABPE_OK;
 }
 
-// The option "split_pattern" (split4_logic.h), read by every call that pre-tokenises, after digit_group: 0 the GPT-2 pattern,
-// 1 the cl100k pattern, whose \p{N}{1,G} needs a digit group.
+// The option "split_pattern" (split4_logic.h, split5_logic.h), read by every call that pre-tokenises, after digit_group: 0 the
+// GPT-2 pattern, 1 the cl100k pattern, 3 the o200k_base pattern; the last two need a digit group for their \p{N}{1,G}.  2 is
+// reserved and refused.
 static int split_pattern_opt(yabpe_ctx *c, uint32_t G, uint32_t *pattern) {
     const int64_t v = optv(c, "split_pattern", 0);
-    if (v != 0 && v != 1) return fail(c, YABPE_E_INVALID, "option split_pattern is %lld: 0 (GPT-2) or 1 (cl100k)", (long long)v);
-    if (v == 1 && G == 0) return fail(c, YABPE_E_INVALID, "option split_pattern is 1 (cl100k): digit_group must be 1 .. 255, it is 0");
+    if (v != 0 && v != 1 && v != 3)
+        return fail(c, YABPE_E_INVALID, "option split_pattern is %lld: 0 (GPT-2), 1 (cl100k) or 3 (o200k_base)", (long long)v);
+    if (v && G == 0)
+        return fail(c, YABPE_E_INVALID, "option split_pattern is %lld (%s): digit_group must be 1 .. 255, it is 0", (long long)v, v == 1 ? "cl100k" : "o200k_base");
     *pattern = (uint32_t)v;
     return YABPE_OK;
 }
@@ -935,6 +940,25 @@ static int class_table(yabpe_ctx *c) {
     }
     TRY(dmalloc(c, &c->pt_cls, cls.size()));
     HIPCHK(c, hipMemcpy(c->pt_cls, cls.data(), cls.size(), hipMemcpyHostToDevice));
+    return 0;
+}
+
+// the table of the o200k_base pattern (class, sub-class, U+0020 / U+002F, CR / LF per code point), built on its first use
+static int class_table5(yabpe_ctx *c) {
+    if (c->pt_cls5) return 0;
+    std::vector<uint8_t> sub(0x110000, 0), cls(0x110000);
+    for (unsigned r = 0; r < YB_UNICODE_SUBCLASS_NRUNS; ++r) {
+        const unsigned lo = YB_UNICODE_SUBCLASS_RUNS[r][0];
+        const unsigned hi = r + 1 < YB_UNICODE_SUBCLASS_NRUNS ? YB_UNICODE_SUBCLASS_RUNS[r + 1][0] : 0x110000;
+        memset(sub.data() + lo, (int)YB_UNICODE_SUBCLASS_RUNS[r][1], hi - lo);
+    }
+    for (unsigned r = 0; r < YB_UNICODE_CLASS_NRUNS; ++r) {
+        const unsigned lo = YB_UNICODE_CLASS_RUNS[r][0];
+        const unsigned hi = r + 1 < YB_UNICODE_CLASS_NRUNS ? YB_UNICODE_CLASS_RUNS[r + 1][0] : 0x110000;
+        for (unsigned cp = lo; cp < hi; ++cp) cls[cp] = pt5_table_entry(cp, (uint8_t)YB_UNICODE_CLASS_RUNS[r][1], sub[cp]);
+    }
+    TRY(dmalloc(c, &c->pt_cls5, cls.size()));
+    HIPCHK(c, hipMemcpy(c->pt_cls5, cls.data(), cls.size(), hipMemcpyHostToDevice));
     return 0;
 }
 
@@ -1020,6 +1044,7 @@ void yabpe_destroy(yabpe_ctx *c) {
     for (auto &e : c->wpool_ev)
         if (e) (void)hipEventDestroy(e);
     dfree(c->pt_cls);
+    dfree(c->pt_cls5);
     free_corpus(c);
     free_records(c);
     dfree(c->tt.pool); dfree(c->tt.off); dfree(c->tt.len); dfree(c->tt.rec); dfree(c->tt.vset);
@@ -2486,8 +2511,18 @@ int yabpe_pretokenize(yabpe_ctx *c, const uint8_t *text, uint64_t n_bytes, const
                         (int)std::min<uint64_t>(len, 64), (const char *)b, G);
         // split4_logic.h: whether a token starts at a whitespace character can be open until the scan pass has run
         if (pattern && pt_decode(v, 0, len, &cp) && class_of(cp) == PT_S)
-            return fail(c, YABPE_E_INVALID, "special token %u (\"%.*s\") begins with a \\s character: not allowed with split_pattern = 1", s,
-                        (int)std::min<uint64_t>(len, 64), (const char *)b);
+            return fail(c, YABPE_E_INVALID, "special token %u (\"%.*s\") begins with a \\s character: not allowed with split_pattern = %u", s,
+                        (int)std::min<uint64_t>(len, 64), (const char *)b, pattern);
+    }
+    if (pattern == 3 && n_special) { // split5_logic.h: occurrences must never overlap
+        uint32_t a = 0, b = 0;
+        const int why = s5_specials_check(special_bytes, special_off, n_special, &a, &b);
+        const int la = (int)std::min<uint32_t>(special_off[a + 1] - special_off[a], 64), lb = (int)std::min<uint32_t>(special_off[b + 1] - special_off[b], 64);
+        const char *sa = (const char *)special_bytes + special_off[a], *sb = (const char *)special_bytes + special_off[b];
+        if (why == 1)
+            return fail(c, YABPE_E_INVALID, "special token %u (\"%.*s\") contains special token %u (\"%.*s\"): not allowed with split_pattern = 3", a, la, sa, b, lb, sb);
+        if (why == 2)
+            return fail(c, YABPE_E_INVALID, "an end of special token %u (\"%.*s\") begins special token %u (\"%.*s\"): not allowed with split_pattern = 3", a, la, sa, b, lb, sb);
     }
     std::vector<unsigned long long> chunks;
     if (chunk_off && n_chunks) {
@@ -2500,6 +2535,7 @@ int yabpe_pretokenize(yabpe_ctx *c, const uint8_t *text, uint64_t n_bytes, const
         chunks.push_back(0);
     }
     TRY(class_table(c));
+    if (pattern == 3) TRY(class_table5(c));
     // inputs on the device
     Scratch S(c->device, c->rank);
     const uint8_t *d_text = nullptr;
@@ -2519,7 +2555,7 @@ int yabpe_pretokenize(yabpe_ctx *c, const uint8_t *text, uint64_t n_bytes, const
         sp.off = d_spo;
     }
     PretokOut po{};
-    if (pretokenize(c->stream, d_text, n_bytes, d_chunks, (uint32_t)chunks.size(), c->pt_cls, sp, G, pattern, &po) != 0)
+    if (pretokenize(c->stream, d_text, n_bytes, d_chunks, (uint32_t)chunks.size(), pattern == 3 ? c->pt_cls5 : c->pt_cls, sp, G, pattern, &po) != 0)
         return fail(c, YABPE_E_HIP, "pre-tokeniser failed: %s", hipGetErrorString(hipGetLastError()));
     if (po.bad_pos >= 0) {
         *out_bad_pos = po.bad_pos;
@@ -2824,10 +2860,16 @@ static int encode_front(yabpe_ctx *c, Scratch &S, const uint8_t *d_text, unsigne
     }
     PretokParams P{d_text, meta, flags, n, c->pt_cls, err, PtSpecials{nullptr, nullptr, 0, 0}, 0};
     const uint32_t wgrid = (uint32_t)std::min<unsigned long long>((n + PT_WIN - 1) / PT_WIN, 1u << 20);
-    if (pattern) hipLaunchKernelGGL(k_pt4_fused, dim3(wgrid), dim3(BLOCK), 0, s, P);
+    if (pattern == 3) { // the marks stay where they are; the classes go to an array of their own, which is the meta from here on
+        uint8_t *marks = meta;
+        TRY(class_table5(c));
+        HIPCHK(c, S.get(&meta, n));
+        if (pt_split5(s, S, d_text, marks, meta, flags, n, c->pt_cls5, err, P.sp) != 0)
+            return fail(c, YABPE_E_HIP, "o200k_base split failed: %s", hipGetErrorString(hipGetLastError()));
+    } else if (pattern) hipLaunchKernelGGL(k_pt4_fused, dim3(wgrid), dim3(BLOCK), 0, s, P);
     else hipLaunchKernelGGL(k_pt_fused, dim3(wgrid), dim3(BLOCK), 0, s, P);
     if (sflag) hipLaunchKernelGGL(k_enc_clear, dim3(grid), dim3(BLOCK), 0, s, sflag, n, flags, (uint8_t)(G ? GRP_INSIDE : 0));
-    if (pattern && pt_newlines(s, S, meta, flags, n) != 0) return fail(c, YABPE_E_HIP, "newline rules failed: %s", hipGetErrorString(hipGetLastError()));
+    if (pattern == 1 && pt_newlines(s, S, meta, flags, n) != 0) return fail(c, YABPE_E_HIP, "newline rules failed: %s", hipGetErrorString(hipGetLastError()));
     if (G && pt_group(s, S, meta, flags, n, G) != 0) return fail(c, YABPE_E_HIP, "digit groups failed: %s", hipGetErrorString(hipGetLastError()));
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipEventRecord(c->enc_ev[1], s));

@@ -15,6 +15,8 @@
 //               k_pt_count / k_pt_scatter   flags -> offsets
 // With the option "split_pattern" = 1 (the cl100k pattern, split4_logic.h) the first two are k_pt4_fused / k_pt4_special,
 // and k_nl_windows / k_nl_carry / k_nl_apply (the newline rules: two segmented scans) run in front of the digit groups.
+// With "split_pattern" = 3 (the o200k_base pattern, split5_logic.h) pt_split5 takes the place of all of them: classes, a
+// backward scan of two look-ahead bits, a forward scan of state-transition functions.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -22,6 +24,7 @@
 #include "group_logic.h"
 #include "pretok_logic.h"
 #include "split4_logic.h"
+#include "split5_logic.h"
 #include "yabpe_aux_kernels.h"
 
 namespace yb {
@@ -463,6 +466,275 @@ inline int pt_newlines(hipStream_t s, Scratch &S, const uint8_t *meta, uint8_t *
     return 0;
 }
 
+// ---------------------------------------------------------------- the o200k_base pattern (split5_logic.h; "split_pattern" = 3)
+// No rule of this pattern has bounded reach, so nothing is decided locally: the text becomes classes, the classes become two
+// look-ahead bits by one backward scan, and the characters -- functions over the scanner's 13 states -- are scanned forward.
+//   k_s5_class     text, chunk marks -> meta (class, sub-class, continuation, chunk mark; UTF-8 validation as k_pt_fused does it).
+//                  The marks are read from an array of their own, so no thread reads a byte another one writes.
+//   k_la_windows / k_la_carry / k_la_apply   meta -> meta with PT5_LA: F and UE, scanned right to left (geometry of k_nl_*)
+//   k_s5_aux       text, meta -> flags = the aux byte (class of the next character, contraction length)
+//   k_s5_special   text, meta -> A5_HEAD / A5_LAST on every occurrence of a special (training pattern only)
+//   k_fn_windows / k_fn_carry / k_fn_apply   meta, aux -> flags: per window the composed function; the functions in front of
+//                  every window; per piece the state in front of it, then its 16 flags (0, 1, GRP_INSIDE)
+// As in the digit groups, a piece is read as the passes before left it by the thread that then writes it.
+
+__global__ __launch_bounds__(BLOCK) void k_s5_class(const uint8_t *text, const uint8_t *marks, uint8_t *meta, unsigned long long n,
+                                                    const uint8_t *cls5, unsigned long long *err) {
+    const PtView v{text, marks, n, 0};
+    unsigned long long bad_pos = ~0ull;
+    for (unsigned long long i = (unsigned long long)blockIdx.x * BLOCK + threadIdx.x; i < n; i += (unsigned long long)gridDim.x * BLOCK) {
+        unsigned long long end = n;
+        for (unsigned long long q = i + 1; q < i + 4 && q < n; ++q)
+            if (marks[q] & PT_CHUNK0) {
+                end = q;
+                break;
+            }
+        bool bad = false;
+        meta[i] = (uint8_t)((marks[i] & PT_CHUNK0) | pt_classify(v, i, end, cls5, &bad));
+        if (bad && i < bad_pos) bad_pos = i;
+    }
+    if (bad_pos != ~0ull) atomicMin(err, bad_pos);
+}
+
+// 16 meta bytes at g (a multiple of 16); bytes past the text read as PT_O
+__device__ __forceinline__ void s5_load(const uint8_t *a, unsigned long long g, unsigned long long n, uint32_t fill, uint32_t w[4]) {
+    if (g + GRP_PIECE <= n) {
+        const uint4 x = *reinterpret_cast<const uint4 *>(a + g);
+        w[0] = x.x; w[1] = x.y; w[2] = x.z; w[3] = x.w;
+    } else {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) w[k] = fill * 0x01010101u;
+#pragma unroll
+        for (int k = 0; k < GRP_PIECE; ++k)
+            if (g + k < n) {
+                const int sh = (k & 3) * 8;
+                w[k >> 2] = (w[k >> 2] & ~(0xFFu << sh)) | ((uint32_t)a[g + k] << sh);
+            }
+    }
+}
+
+__device__ __forceinline__ void s5_store(uint8_t *a, unsigned long long g, unsigned long long n, const uint32_t w[4]) {
+    if (g + GRP_PIECE <= n) {
+        *reinterpret_cast<uint4 *>(a + g) = make_uint4(w[0], w[1], w[2], w[3]);
+    } else {
+#pragma unroll
+        for (int k = 0; k < GRP_PIECE; ++k)
+            if (g + k < n) a[g + k] = (uint8_t)(w[k >> 2] >> ((k & 3) * 8));
+    }
+}
+
+// Exclusive scan of one look-ahead value per thread over the workgroup, over the threads BEHIND (nearest last); *total: all of
+// them.  s_w: WPB words.
+__device__ __forceinline__ uint32_t la_block_scan(uint32_t mine, uint32_t *s_w, uint32_t *total) {
+    const int lane = threadIdx.x & 63, wib = threadIdx.x >> 6;
+    uint32_t b = mine;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const uint32_t ub = __shfl_down(b, o);
+        if (lane + o < 64) b = la_comb(ub, b);
+    }
+    const uint32_t pb = __shfl_down(b, 1);
+    if (lane == 0) s_w[wib] = b;
+    __syncthreads();
+    uint32_t bb = LA_KEEP, ab = LA_KEEP;
+#pragma unroll
+    for (int w = WPB - 1; w >= 0; --w) {
+        if (w == wib) bb = ab;
+        ab = la_comb(ab, s_w[w]);
+    }
+    *total = ab;
+    return lane < 63 ? la_comb(bb, pb) : bb;
+}
+
+__global__ __launch_bounds__(BLOCK) void k_la_windows(const uint8_t *meta, unsigned long long n, uint32_t *win) {
+    __shared__ uint32_t s_w[WPB];
+    const unsigned long long n_win = (n + PT_WIN - 1) / PT_WIN;
+    for (unsigned long long w = blockIdx.x; w < n_win; w += gridDim.x) {
+        uint32_t m[4];
+        s5_load(meta, w * PT_WIN + (unsigned long long)threadIdx.x * GRP_PIECE, n, PT_O, m);
+        uint32_t total;
+        (void)la_block_scan(la_piece_state(m), s_w, &total);
+        if (threadIdx.x == 0) win[w] = total;
+        __syncthreads();
+    }
+}
+
+// win[w] = the windows behind w combined, in place (one workgroup; right to left, a tile of BLOCK * 8 windows per iteration)
+constexpr int S5_CARRY_ITEMS = 8;
+constexpr unsigned long long S5_CARRY_TILE = (unsigned long long)BLOCK * S5_CARRY_ITEMS;
+__global__ __launch_bounds__(BLOCK) void k_la_carry(uint32_t *win, unsigned long long n_win) {
+    __shared__ uint32_t s_w[WPB];
+    const unsigned long long n_tiles = (n_win + S5_CARRY_TILE - 1) / S5_CARRY_TILE;
+    uint32_t carry = LA_KEEP;
+    for (unsigned long long t = n_tiles; t-- > 0;) {
+        const unsigned long long base = t * S5_CARRY_TILE + (unsigned long long)threadIdx.x * S5_CARRY_ITEMS;
+        uint32_t v[S5_CARRY_ITEMS], mine = LA_KEEP;
+#pragma unroll
+        for (int k = S5_CARRY_ITEMS - 1; k >= 0; --k) {
+            v[k] = base + k < n_win ? win[base + k] : LA_KEEP;
+            mine = la_comb(mine, v[k]);
+        }
+        uint32_t total;
+        uint32_t run = la_comb(carry, la_block_scan(mine, s_w, &total));
+#pragma unroll
+        for (int k = S5_CARRY_ITEMS - 1; k >= 0; --k) {
+            if (base + k < n_win) win[base + k] = run;
+            run = la_comb(run, v[k]);
+        }
+        carry = la_comb(carry, total);
+        __syncthreads();
+    }
+}
+
+__global__ __launch_bounds__(BLOCK) void k_la_apply(uint8_t *meta, unsigned long long n, const uint32_t *win) {
+    __shared__ uint32_t s_w[WPB];
+    const unsigned long long n_win = (n + PT_WIN - 1) / PT_WIN;
+    for (unsigned long long w = blockIdx.x; w < n_win; w += gridDim.x) {
+        const unsigned long long g = w * PT_WIN + (unsigned long long)threadIdx.x * GRP_PIECE;
+        uint32_t m[4];
+        s5_load(meta, g, n, PT_O, m);
+        uint32_t total;
+        const uint32_t after = la_comb(win[w], la_block_scan(la_piece_state(m), s_w, &total));
+        la_piece_bits(after, m);
+        s5_store(meta, g, n, m);
+        __syncthreads();
+    }
+}
+
+// the aux byte of every byte: the rules look at most 4 bytes ahead (the next character; two suffix letters)
+__global__ __launch_bounds__(BLOCK) void k_s5_aux(const uint8_t *text, const uint8_t *meta, uint8_t *aux, unsigned long long n) {
+    const PtView v{text, meta, n, 0};
+    for (unsigned long long i = (unsigned long long)blockIdx.x * BLOCK + threadIdx.x; i < n; i += (unsigned long long)gridDim.x * BLOCK)
+        aux[i] = s5_aux(v, i);
+}
+
+// every occurrence of a special gets A5_HEAD on its first and A5_LAST on its last byte (occurrences never overlap: the caller
+// has refused the sets in which they could, so every byte is written by one thread at most)
+__global__ __launch_bounds__(BLOCK) void k_s5_special(PretokParams P) {
+    __shared__ uint32_t s_first[8];
+    if (threadIdx.x < 8) s_first[threadIdx.x] = 0u;
+    __syncthreads();
+    if (threadIdx.x < P.sp.n) {
+        const uint32_t o = P.sp.off[threadIdx.x];
+        if (P.sp.off[threadIdx.x + 1] > o) atomicOr(&s_first[P.sp.bytes[o] >> 5], 1u << (P.sp.bytes[o] & 31));
+    }
+    __syncthreads();
+    const PtView v{P.text, P.meta, P.n, 0};
+    for (unsigned long long i = (unsigned long long)blockIdx.x * BLOCK + threadIdx.x; i < P.n; i += (unsigned long long)gridDim.x * BLOCK) {
+        const uint8_t b = v.T(i);
+        if (!((s_first[b >> 5] >> (b & 31)) & 1u)) continue;
+        const uint32_t o = pt_special_at(v, P.sp, i);
+        if (!o) continue;
+        const uint32_t len = pt_special_len(P.sp, o);
+        if (len == 1) {
+            P.flags[i] |= A5_HEAD | A5_LAST;
+        } else {
+            P.flags[i] |= A5_HEAD;
+            P.flags[i + len - 1] |= A5_LAST;
+        }
+    }
+}
+
+// Exclusive scan of one function per thread over the workgroup, in thread order; *total = all of them composed.  s_w: WPB.
+__device__ __forceinline__ S5Fn s5_block_scan(S5Fn mine, S5Fn *s_w, S5Fn *total) {
+    const int lane = threadIdx.x & 63, wib = threadIdx.x >> 6;
+    S5Fn inc = mine;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const S5Fn u = __shfl_up(inc, o);
+        if (lane >= o) inc = s5_then(u, inc);
+    }
+    const S5Fn up = __shfl_up(inc, 1);
+    if (lane == 63) s_w[wib] = inc;
+    __syncthreads();
+    S5Fn before = S5_IDENTITY, all = S5_IDENTITY;
+#pragma unroll
+    for (int w = 0; w < WPB; ++w) {
+        if (w == wib) before = all;
+        all = s5_then(all, s_w[w]);
+    }
+    *total = all;
+    return lane ? s5_then(before, up) : before;
+}
+
+__global__ __launch_bounds__(BLOCK) void k_fn_windows(const uint8_t *meta, const uint8_t *aux, unsigned long long n, S5Fn *win) {
+    __shared__ S5Fn s_w[WPB];
+    const unsigned long long n_win = (n + PT_WIN - 1) / PT_WIN;
+    for (unsigned long long w = blockIdx.x; w < n_win; w += gridDim.x) {
+        const GrpPiece p = grp_load(meta, aux, w * PT_WIN + (unsigned long long)threadIdx.x * GRP_PIECE, n);
+        S5Fn total;
+        (void)s5_block_scan(s5_piece_fn(p.m, p.f), s_w, &total);
+        if (threadIdx.x == 0) win[w] = total;
+        __syncthreads();
+    }
+}
+
+// win[w] = the functions of windows 0 .. w - 1 composed, in place (one workgroup; a tile of BLOCK * 8 windows per iteration)
+__global__ __launch_bounds__(BLOCK) void k_fn_carry(S5Fn *win, unsigned long long n_win) {
+    __shared__ S5Fn s_w[WPB];
+    S5Fn carry = S5_IDENTITY;
+    for (unsigned long long t0 = 0; t0 < n_win; t0 += S5_CARRY_TILE) {
+        const unsigned long long base = t0 + (unsigned long long)threadIdx.x * S5_CARRY_ITEMS;
+        S5Fn v[S5_CARRY_ITEMS], mine = S5_IDENTITY;
+#pragma unroll
+        for (int k = 0; k < S5_CARRY_ITEMS; ++k) {
+            v[k] = base + k < n_win ? win[base + k] : S5_IDENTITY;
+            mine = s5_then(mine, v[k]);
+        }
+        S5Fn total;
+        S5Fn run = s5_then(carry, s5_block_scan(mine, s_w, &total));
+#pragma unroll
+        for (int k = 0; k < S5_CARRY_ITEMS; ++k) {
+            if (base + k < n_win) win[base + k] = run;
+            run = s5_then(run, v[k]);
+        }
+        carry = s5_then(carry, total);
+        __syncthreads();
+    }
+}
+
+__global__ __launch_bounds__(BLOCK) void k_fn_apply(const uint8_t *meta, uint8_t *flags, unsigned long long n, const S5Fn *win) {
+    __shared__ S5Fn s_w[WPB];
+    const unsigned long long n_win = (n + PT_WIN - 1) / PT_WIN;
+    for (unsigned long long w = blockIdx.x; w < n_win; w += gridDim.x) {
+        const unsigned long long g = w * PT_WIN + (unsigned long long)threadIdx.x * GRP_PIECE;
+        GrpPiece p = grp_load(meta, flags, g, n);
+        S5Fn total;
+        const S5Fn before = s5_then(win[w], s5_block_scan(s5_piece_fn(p.m, p.f), s_w, &total));
+        s5_piece_flags(s5_apply(before, S5_S0), p.m, p.f); // (whatever stands in front of the text: its first byte is a constant)
+        s5_store(flags, g, n, p.f);
+        __syncthreads();
+    }
+}
+
+// All passes of the pattern on the chunk marks `marks` (PT_CHUNK0 or 0 per byte) of n > 0 bytes: meta and flags (0, 1,
+// GRP_INSIDE: what pt_group reads) are written, *err as by k_pt_fused; left in flight on s.  sp.n = 0: no special is looked for
+// (encode: the pieces are texts of their own).  The window values belong to S.
+inline int pt_split5(hipStream_t s, Scratch &S, const uint8_t *text, const uint8_t *marks, uint8_t *meta, uint8_t *flags, unsigned long long n,
+                     const uint8_t *cls5, unsigned long long *err, const PtSpecials &sp) {
+    const unsigned long long n_win = (n + PT_WIN - 1) / PT_WIN;
+    uint32_t *la = nullptr;
+    S5Fn *fn = nullptr;
+    YB_RET(S.get(&la, n_win));
+    YB_RET(S.get(&fn, n_win));
+    const uint32_t grid = (uint32_t)std::min<unsigned long long>((n + BLOCK - 1) / BLOCK, 1u << 20);
+    const uint32_t wgrid = (uint32_t)std::min<unsigned long long>(n_win, 1u << 20);
+    hipLaunchKernelGGL(k_s5_class, dim3(grid), dim3(BLOCK), 0, s, text, marks, meta, n, cls5, err);
+    hipLaunchKernelGGL(k_la_windows, dim3(wgrid), dim3(BLOCK), 0, s, (const uint8_t *)meta, n, la);
+    hipLaunchKernelGGL(k_la_carry, dim3(1), dim3(BLOCK), 0, s, la, n_win);
+    hipLaunchKernelGGL(k_la_apply, dim3(wgrid), dim3(BLOCK), 0, s, meta, n, (const uint32_t *)la);
+    hipLaunchKernelGGL(k_s5_aux, dim3(grid), dim3(BLOCK), 0, s, text, (const uint8_t *)meta, flags, n);
+    if (sp.n) {
+        const PretokParams P{text, meta, flags, n, cls5, err, sp, 0};
+        hipLaunchKernelGGL(k_s5_special, dim3(grid), dim3(BLOCK), 0, s, P);
+    }
+    hipLaunchKernelGGL(k_fn_windows, dim3(wgrid), dim3(BLOCK), 0, s, (const uint8_t *)meta, (const uint8_t *)flags, n, fn);
+    hipLaunchKernelGGL(k_fn_carry, dim3(1), dim3(BLOCK), 0, s, fn, n_win);
+    hipLaunchKernelGGL(k_fn_apply, dim3(wgrid), dim3(BLOCK), 0, s, (const uint8_t *)meta, flags, n, (const S5Fn *)fn);
+    YB_RET(hipGetLastError());
+    return 0;
+}
+
 // flags -> offsets, pass 1: number of starts per workgroup of PT_PER_BLOCK bytes
 __global__ __launch_bounds__(BLOCK) void k_pt_count(const uint8_t *flags, unsigned long long n, unsigned long long *block_sums) {
     __shared__ uint32_t s_w[WPB];
@@ -538,7 +810,8 @@ inline int pt_offsets(hipStream_t s, Scratch &S, const uint8_t *flags, const uns
 
 // Runs all passes on `text` (device).  chunk_off: device array of n_chunks chunk starts.  cls: device class table.
 // digit_group: 0, or G of group_logic.h (no special may then begin with a \p{N} character: the caller checks).
-// pattern: 0 GPT-2, 1 cl100k (split4_logic.h; digit_group >= 1, and no special begins with \s either: the caller checks).
+// pattern: 0 GPT-2, 1 cl100k (split4_logic.h; digit_group >= 1, and no special begins with \s either: the caller checks),
+// 3 o200k_base (split5_logic.h; as 1, `cls` is then the table of pt5_table_entry and the caller has run s5_specials_check).
 // Scratch (meta, flags) is allocated and released here; out->off is the caller's to free (dev_free).
 inline int pretokenize(hipStream_t s, const uint8_t *text, unsigned long long n, const unsigned long long *chunk_off, uint32_t n_chunks,
                        const uint8_t *cls, const PtSpecials &sp_dev, uint32_t digit_group, uint32_t pattern, PretokOut *out) {
@@ -563,7 +836,12 @@ inline int pretokenize(hipStream_t s, const uint8_t *text, unsigned long long n,
     PretokParams P{text, meta, flags, n, cls, err, sp_dev, (uint8_t)(digit_group ? GRP_INSIDE : 0)};
     hipLaunchKernelGGL(k_pt_mark_chunks, dim3((n_chunks + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, s, meta, chunk_off, n_chunks, n);
     const uint32_t wgrid = (uint32_t)std::min<unsigned long long>((n + PT_WIN - 1) / PT_WIN, 1u << 20);
-    if (pattern) hipLaunchKernelGGL(k_pt4_fused, dim3(wgrid), dim3(BLOCK), 0, s, P);
+    if (pattern == 3) { // the marks stay where they are; the classes go to an array of their own
+        uint8_t *meta5 = nullptr;
+        YB_RET(S.get(&meta5, n));
+        if (pt_split5(s, S, text, meta, meta5, flags, n, cls, err, sp_dev) != 0) return -1;
+        meta = meta5;
+    } else if (pattern) hipLaunchKernelGGL(k_pt4_fused, dim3(wgrid), dim3(BLOCK), 0, s, P);
     else hipLaunchKernelGGL(k_pt_fused, dim3(wgrid), dim3(BLOCK), 0, s, P);
     unsigned long long h_err = 0;
     YB_RET(hipMemcpyAsync(&h_err, err, 8, hipMemcpyDeviceToHost, s));
@@ -572,11 +850,11 @@ inline int pretokenize(hipStream_t s, const uint8_t *text, unsigned long long n,
         out->bad_pos = (long long)h_err;
         return 0;
     }
-    if (sp_dev.n) {
+    if (sp_dev.n && pattern != 3) {
         if (pattern) hipLaunchKernelGGL(k_pt4_special, dim3(grid), dim3(BLOCK), 0, s, P);
         else hipLaunchKernelGGL(k_pt_special, dim3(grid), dim3(BLOCK), 0, s, P);
     }
-    if (pattern && pt_newlines(s, S, meta, flags, n) != 0) return -1;
+    if (pattern == 1 && pt_newlines(s, S, meta, flags, n) != 0) return -1;
     if (digit_group && pt_group(s, S, meta, flags, n, digit_group) != 0) return -1;
     unsigned long long total = 0;
     if (pt_offsets(s, S, flags, n, ~0ull, &off, &total) != 0) return -1;

@@ -369,7 +369,7 @@ class Context:
 
     def pretokenize(self, text, n_bytes: int | None = None, chunk_starts=None, special_tokens=()):
         """GPT-2 pre-tokenisation on the device (reference trainer.py:136-214; with the option "digit_group" = G the digit
-        runs are cut into groups of G, with the option "split_pattern" = 1 the cl100k pattern is used, include/yabpe.h).  `text`: bytes / u8 array (staged) or a
+        runs are cut into groups of G, with the option "split_pattern" = 1 the cl100k pattern is used, with 3 the o200k_base pattern, include/yabpe.h).  `text`: bytes / u8 array (staged) or a
         device address (then n_bytes is required).  chunk_starts: ascending chunk starts, first one 0.
         -> (dev_text_ptr, dev_word_off_ptr, n_words); raises Utf8Error(position) on malformed UTF-8."""
         keep = None

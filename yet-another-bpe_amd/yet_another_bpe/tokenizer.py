@@ -25,7 +25,7 @@ import numpy as np
 import regex
 
 from .synth import rnd_int
-from .trainer import (CL100K_DIGIT_GROUP, PRETOKENIZERS, BBPETrainerConfig, check_digit_group, check_pretokenizer, device_options, read_pretokenizer,
+from .trainer import (CL100K_DIGIT_GROUP, PRETOKENIZER_NAMES, BBPETrainerConfig, check_digit_group, check_pretokenizer, device_options, read_pretokenizer,
                       split_pattern)
 
 _WORD_CACHE = 8192
@@ -34,8 +34,8 @@ _WORD_CACHE = 8192
 class BBPETokenizer:
     """Applies learned merges, lowest rank first (leftmost on ties), to GPT-2 pre-tokens; with digit_group = G (1 .. 255; not
     in the reference) to the pre-tokens of the pattern whose \\p{N}+ is \\p{N}{1,G} -- the pre-tokenisation of a model trained
-    with BBPETrainerConfig(digit_group=G); with pretokenizer = "cl100k" to those of the GPT-4 / Llama-3 pattern (digit_group
-    None: 3).  Every method, plain Python or on the GPU, follows it."""
+    with BBPETrainerConfig(digit_group=G); with pretokenizer = "cl100k" to those of the GPT-4 / Llama-3 pattern, with
+    "o200k_base" to those of the GPT-4o pattern (digit_group None: 3 for both).  Every method, plain Python or on the GPU, follows it."""
 
     def __init__(self, vocab: dict[bytes, int] | None = None, merges: list[tuple[bytes, bytes]] | None = None,
                  special_tokens: list[str] | None = None, digit_group: int | None = None, pretokenizer: str = "gpt2") -> None:
@@ -45,8 +45,8 @@ class BBPETokenizer:
         self._special_tokens: list[str] = special_tokens or []
         self._special_set = frozenset(self._special_tokens)
         self._rank: dict[tuple[bytes, bytes], int] = {pair: i for i, pair in enumerate(self._merges)}
-        self._pretokenizer: str = PRETOKENIZERS[check_pretokenizer(pretokenizer)]
-        self._digit_group: int | None = check_digit_group(digit_group) or (CL100K_DIGIT_GROUP if self._pretokenizer == "cl100k" else None)
+        self._pretokenizer: str = PRETOKENIZER_NAMES[check_pretokenizer(pretokenizer)]
+        self._digit_group: int | None = check_digit_group(digit_group) or (CL100K_DIGIT_GROUP if self._pretokenizer != "gpt2" else None)
         self._pattern = regex.compile(split_pattern(self._digit_group, self._pretokenizer))
         # specials are split out first, longest first (reference tokenizer.py:100-102)
         self._special_pattern = None

@@ -7,7 +7,8 @@ loaded with ctypes by `_native`).  There is no CPU fallback: without the built l
 `_merge_loop` raises.
 
 Host-only steps (file chunking, save format) stay in Python as in the reference.  Pre-tokenisation (UTF-8 decode +
-GPT-2 regex, trainer.py:136-214; with BBPETrainerConfig(pretokenizer="cl100k") the GPT-4 / Llama-3 pattern) exists twice with
+GPT-2 regex, trainer.py:136-214; with BBPETrainerConfig(pretokenizer="cl100k") the GPT-4 / Llama-3 pattern, with "o200k_base"
+the GPT-4o pattern) exists twice with
 identical results: `_preprocess_corpus` runs the `regex` module on the host and returns Python lists, as the reference's
 method does; on a corpus of 1 MiB or more (or with YABPE_PRETOKENIZE=gpu; YABPE_PRETOKENIZE=host forces the host path) the raw
 file bytes go to `yabpe_pretokenize` instead and no Python object is built per pre-token.  With `batch_bytes` (or
@@ -38,26 +39,37 @@ import regex
 _GPT2_SPLIT = r"""'(?:[sdmt]|ll|ve|re)| ?\p{L}+| ?\p{N}+| ?[^\s\p{L}\p{N}]+|\s+(?!\S)|\s+"""
 # the split of cl100k_base (GPT-4), Llama-3 (G = 3) and Qwen2 (G = 1); %d: the digit group
 _CL100K_SPLIT = r"""(?i:'s|'t|'re|'ve|'m|'ll|'d)|[^\r\n\p{L}\p{N}]?\p{L}+|\p{N}{1,%d}| ?[^\s\p{L}\p{N}]+[\r\n]*|\s*[\r\n]+|\s+(?!\S)|\s+"""
-PRETOKENIZERS = ("gpt2", "cl100k")  # the library's option `split_pattern`: the index
-CL100K_DIGIT_GROUP = 3  # digit_group=None with the cl100k pattern
-# {"digit_group": G} (GPT-2 pattern with a group) or {"pattern": "cl100k", "digit_group": G}, written next to a saved model;
-# the plain GPT-2 pattern writes no file
+# the split of o200k_base (GPT-4o, o-series, gpt-oss): case-aware words that keep their contraction, "/" behind the newlines of
+# a punctuation run; %d: the digit group
+_O200K_SUFFIX = r"""(?i:'s|'t|'re|'ve|'m|'ll|'d)?"""
+_O200K_SPLIT = (r"""[^\r\n\p{L}\p{N}]?[\p{Lu}\p{Lt}\p{Lm}\p{Lo}\p{M}]*[\p{Ll}\p{Lm}\p{Lo}\p{M}]+""" + _O200K_SUFFIX
+                + r"""|[^\r\n\p{L}\p{N}]?[\p{Lu}\p{Lt}\p{Lm}\p{Lo}\p{M}]+[\p{Ll}\p{Lm}\p{Lo}\p{M}]*""" + _O200K_SUFFIX
+                + r"""|\p{N}{1,%d}| ?[^\s\p{L}\p{N}]+[\r\n/]*|\s*[\r\n]+|\s+(?!\S)|\s+""")
+PRETOKENIZERS = ("gpt2", "cl100k", "o200k_base")
+# name -> the library's option `split_pattern` (2 is reserved and refused by the library), and back
+SPLIT_PATTERN_VALUES = {"gpt2": 0, "cl100k": 1, "o200k_base": 3}
+PRETOKENIZER_NAMES = {v: k for k, v in SPLIT_PATTERN_VALUES.items()}
+CL100K_DIGIT_GROUP = 3  # digit_group=None with the cl100k or the o200k_base pattern
+# {"digit_group": G} (GPT-2 pattern with a group) or {"pattern": "cl100k" / "o200k_base", "digit_group": G}, written next to a
+# saved model; the plain GPT-2 pattern writes no file
 PRETOKENIZER_FILE = "pretokenizer.json"
 
 
 def split_pattern(group: int | None = None, pretokenizer: str = "gpt2") -> str:
     """The one place the pattern string is built.  "gpt2": the GPT-2 pattern; with a digit group G, \\p{N}+ replaced by
-    \\p{N}{1,G}.  "cl100k": the GPT-4 / Llama-3 pattern with \\p{N}{1,G} (None: 3)."""
-    if check_pretokenizer(pretokenizer):
-        return _CL100K_SPLIT % (group or CL100K_DIGIT_GROUP)
+    \\p{N}{1,G}.  "cl100k": the GPT-4 / Llama-3 pattern with \\p{N}{1,G} (None: 3).  "o200k_base": the GPT-4o pattern, likewise."""
+    value = check_pretokenizer(pretokenizer)
+    if value:
+        return (_CL100K_SPLIT if value == 1 else _O200K_SPLIT) % (group or CL100K_DIGIT_GROUP)
     return _GPT2_SPLIT if not group else _GPT2_SPLIT.replace(r"\p{N}+", r"\p{N}{1,%d}" % group, 1)
 
 
 def check_pretokenizer(name) -> int:
-    """A pre-tokeniser name as the library's option `split_pattern` (0: "gpt2", 1: "cl100k").  ValueError for anything else."""
-    if not isinstance(name, str) or name not in PRETOKENIZERS:
+    """A pre-tokeniser name as the library's option `split_pattern` (0: "gpt2", 1: "cl100k", 3: "o200k_base").  ValueError for
+    anything else."""
+    if not isinstance(name, str) or name not in SPLIT_PATTERN_VALUES:
         raise ValueError(f"pretokenizer must be one of {PRETOKENIZERS!r}, got {name!r}")
-    return PRETOKENIZERS.index(name)
+    return SPLIT_PATTERN_VALUES[name]
 
 
 def read_pretokenizer(model_dir: str | Path) -> tuple[str, int | None]:
@@ -115,7 +127,11 @@ class BBPETrainerConfig:
             either case, one character that is no letter, digit, CR or LF in front of a letter run, digits in groups of
             digit_group (None: 3) without a space in front, newlines kept with the punctuation or the whitespace before
             them.  Part of the model like digit_group (BBPEModel.pretokenizer, pretokenizer.json, BBPETokenizer).  With
-            "cl100k" no special token may begin with a \\s or a \\p{N} character (ValueError).
+            "cl100k" no special token may begin with a \\s or a \\p{N} character (ValueError).  "o200k_base": the split of
+            GPT-4o, the o-series and gpt-oss -- words cut where the case changes (HTTPServer, foo|Bar), the contraction kept
+            with its word, "/" kept behind the newlines that follow punctuation; digit_group and the first character of a
+            special as with "cl100k", and no special token may contain another one or end with the beginning of one, itself
+            included (ValueError): their occurrences must not overlap.
     """
 
     vocab_size: int = 32000
@@ -154,27 +170,42 @@ def pretokenizer(config: BBPETrainerConfig) -> tuple[int, int]:
     if pattern:
         for tok in config.special_tokens:
             if regex.match(r"\s", tok):
-                raise ValueError(f"special token {tok!r} begins with whitespace (\\s): not allowed with pretokenizer = {PRETOKENIZERS[pattern]!r}")
+                raise ValueError(f"special token {tok!r} begins with whitespace (\\s): not allowed with pretokenizer = {PRETOKENIZER_NAMES[pattern]!r}")
+    if pattern == 3:
+        check_disjoint_specials(config.special_tokens)
     return pattern, group
 
 
+def check_disjoint_specials(tokens: Sequence[str]) -> None:
+    """The o200k_base pattern takes a special wherever its scanner stands at a token boundary, so occurrences must never
+    overlap: ValueError for a special that contains another one, or whose proper suffix begins a special (itself included).
+    Equal specials are one special."""
+    for a in tokens:
+        for b in tokens:
+            if a != b and b in a:
+                raise ValueError(f"special token {a!r} contains special token {b!r}: not allowed with pretokenizer = 'o200k_base'")
+            for k in range(1, min(len(a) - 1, len(b)) + 1):
+                if a[len(a) - k:] == b[:k]:
+                    raise ValueError(f"the end of special token {a!r} begins special token {b!r} ({b[:k]!r}): not allowed with pretokenizer = 'o200k_base'")
+
+
 def digit_group(config: BBPETrainerConfig) -> int:
-    """The digit group of pretokenizer(config): 0 for none; with "cl100k" never 0 (None means 3)."""
+    """The digit group of pretokenizer(config): 0 for none; with "cl100k" or "o200k_base" never 0 (None means 3)."""
     return pretokenizer(config)[1]
 
 
 class BBPEModel:
     """Result container (reference trainer.py:41-52): copies of vocab, merges, special tokens; digit_group (not in the
     reference): the digit group of the pre-tokenisation the model was trained with, None for the GPT-2 pattern; pretokenizer:
-    "gpt2" or "cl100k" (digit_group is then never None)."""
+    "gpt2", or "cl100k" / "o200k_base" (digit_group is then never None)."""
 
     def __init__(self, vocab: Mapping[bytes, int], merges: Sequence[tuple[bytes, bytes]],
                  special_tokens: Sequence[str], digit_group: int | None = None, pretokenizer: str = "gpt2") -> None:
         self.vocab: dict[bytes, int] = dict(vocab)
         self.merges: list[tuple[bytes, bytes]] = list(merges)
         self.special_tokens: list[str] = list(special_tokens)
-        self.pretokenizer: str = PRETOKENIZERS[check_pretokenizer(pretokenizer)]
-        self.digit_group: int | None = check_digit_group(digit_group) or (CL100K_DIGIT_GROUP if self.pretokenizer == "cl100k" else None)
+        self.pretokenizer: str = PRETOKENIZER_NAMES[check_pretokenizer(pretokenizer)]
+        self.digit_group: int | None = check_digit_group(digit_group) or (CL100K_DIGIT_GROUP if self.pretokenizer != "gpt2" else None)
 
     @classmethod
     def from_file_lossless(cls, model_dir: str | Path) -> "BBPEModel":
@@ -310,7 +341,7 @@ class BBPETrainer:
     def _model(self, vocab, merges) -> BBPEModel:
         pattern, group = pretokenizer(self.config)
         return BBPEModel(vocab=vocab, merges=merges, special_tokens=list(self.config.special_tokens), digit_group=group or None,
-                         pretokenizer=PRETOKENIZERS[pattern])
+                         pretokenizer=PRETOKENIZER_NAMES[pattern])
 
     # ------------------------------------------------------------------ train / save (trainer.py:63-117)
     def train(self, files: Sequence[str | Path], batch_bytes: int | None = None) -> BBPEModel:
@@ -340,9 +371,9 @@ class BBPETrainer:
             raise ValueError("At least one file must be provided")
         paths = [Path(f) if isinstance(f, str) else f for f in files]
         pattern, group = pretokenizer(self.config)
-        if getattr(model, "pretokenizer", "gpt2") != PRETOKENIZERS[pattern]:
+        if getattr(model, "pretokenizer", "gpt2") != PRETOKENIZER_NAMES[pattern]:
             raise ValueError(f"cannot continue from this model: it was trained with pretokenizer = {getattr(model, 'pretokenizer', 'gpt2')!r}, "
-                             f"the trainer's is {PRETOKENIZERS[pattern]!r} (its merges would be replayed over words it never saw)")
+                             f"the trainer's is {PRETOKENIZER_NAMES[pattern]!r} (its merges would be replayed over words it never saw)")
         if getattr(model, "digit_group", None) != (group or None):
             raise ValueError(f"cannot continue from this model: it was trained with digit_group = {getattr(model, 'digit_group', None)!r}, "
                              f"the trainer's is {group or None!r} (its merges would be replayed over words it never saw)")
@@ -483,7 +514,7 @@ class BBPETrainer:
 
     def save(self, output_dir: str | Path) -> None:
         """vocab.json / merges.txt / special_tokens.json in the reference's format (trainer.py:94-117); with a digit group
-        also pretokenizer.json ({"digit_group": G}), with the cl100k pattern {"pattern": "cl100k", "digit_group": G}."""
+        also pretokenizer.json ({"digit_group": G}), with another pattern {"pattern": "cl100k" or "o200k_base", "digit_group": G}."""
         if not self._vocab:
             raise ValueError("Model has not been trained yet. Call train() first.")
         out = Path(output_dir)
@@ -498,12 +529,12 @@ class BBPETrainer:
         self._save_pretokenizer(out)
 
     def _save_pretokenizer(self, out: Path) -> None:
-        """pretokenizer.json, only when the model was trained with a digit group or the cl100k pattern (without them the
+        """pretokenizer.json, only when the model was trained with a digit group or another pattern than GPT-2's (without them the
         directory holds exactly the files it always held; a file left there by an earlier save is removed)."""
         pattern, group = pretokenizer(self.config)
         if pattern:
             with open(out / PRETOKENIZER_FILE, "w", encoding="utf-8") as f:
-                json.dump({"pattern": PRETOKENIZERS[pattern], "digit_group": group}, f)
+                json.dump({"pattern": PRETOKENIZER_NAMES[pattern], "digit_group": group}, f)
         elif group:
             with open(out / PRETOKENIZER_FILE, "w", encoding="utf-8") as f:
                 json.dump({"digit_group": group}, f)
@@ -555,7 +586,7 @@ class BBPETrainer:
 
     def _split_pattern(self) -> "regex.Pattern[str]":
         pattern, group = pretokenizer(self.config)
-        pat = split_pattern(group, PRETOKENIZERS[pattern])
+        pat = split_pattern(group, PRETOKENIZER_NAMES[pattern])
         if self.config.special_tokens:  # specials first, in config order, kept as words (trainer.py:165-167)
             pat = "|".join(regex.escape(t) for t in self.config.special_tokens) + "|" + pat
         return regex.compile(pat)
