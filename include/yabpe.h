@@ -281,6 +281,47 @@ int yabpe_pretokenize(yabpe_ctx *ctx, const uint8_t *text, uint64_t n_bytes, con
                       const uint8_t **out_dev_text, uint64_t **out_dev_word_off, uint64_t *out_n_words, int64_t *out_bad_pos);
 int yabpe_pretokenize_free(yabpe_ctx *ctx);
 
+/* Normaliser (the step in front of the pre-tokeniser and of the encoder) ---------------------------------
+ * Unicode NFC on the device: every part [part_off[k], part_off[k+1]) of `text` (the last one ends at n_bytes; part_off == NULL:
+ * one part; read as yabpe_pretokenize reads chunk_off: n_parts ascending starts, the first one 0) is replaced by
+ * unicodedata.normalize("NFC", part) of CPython, Unicode version as csrc/unicode_norm.inc says (generated by
+ * tools/gen_unicode_norm.py from the installed unicodedata).  Parts are normalised independently: a part that begins with a
+ * combining mark does not combine with the part before it.  form: YABPE_NORM_NFC; anything else: YABPE_E_INVALID.
+ * text may be host or device memory.  Results (owned by the library, valid until yabpe_normalize_free, the next
+ * yabpe_normalize or yabpe_destroy): *out_dev_text = *out_n_bytes bytes in device memory, *out_dev_part_off = n_parts + 1
+ * offsets into them (device memory) -- they can be passed on as the chunk starts of yabpe_pretokenize or the document starts
+ * of yabpe_encode.  n_bytes == 0 and empty parts are valid.
+ * The rule (csrc/nfc_logic.h): a SEGMENT starts at every code point with canonical combining class 0 and NFC quick-check Yes,
+ * and at every part start; a segment is clean (NFC leaves it as it is) iff it holds no code point with quick-check No or
+ * Maybe and no adjacent pair with ccc(prev) > ccc(cur) > 0.  A text without such a suspect -- almost every corpus -- costs one
+ * pass: *out_dev_text is then `text` itself when that is a device pointer (else the staged copy) and the offsets are
+ * unchanged.  Otherwise only the dirty segments are walked (one lane each, forward), everything else is copied; the result
+ * is at most 3 n_bytes long.
+ * Malformed UTF-8: YABPE_E_UTF8 and *out_bad_pos = UnicodeDecodeError.start of the first bad part, as yabpe_pretokenize
+ * reports it (a part cut inside a sequence is malformed on both sides).
+ * Cap: a dirty segment of more than 16,384 input code points (a base with thousands of combining marks; the Stream-Safe
+ * format of UAX #15 allows 30) makes the call fail with YABPE_E_CAPACITY, *out_bad_pos = the byte position of the segment's
+ * start in the INPUT.  Clean segments have no cap. */
+#define YABPE_NORM_NFC 1u
+int yabpe_normalize(yabpe_ctx *ctx, const uint8_t *text, uint64_t n_bytes, const uint64_t *part_off, uint32_t n_parts,
+                    uint32_t form, const uint8_t **out_dev_text, uint64_t **out_dev_part_off, uint64_t *out_n_bytes,
+                    int64_t *out_bad_pos);
+int yabpe_normalize_free(yabpe_ctx *ctx);
+/* What the last yabpe_normalize saw, and the device time of its phases (HIP events around each phase's launches). */
+typedef struct yabpe_normalize_stats_t {
+    uint64_t n_bytes_in, n_bytes_out, n_parts;
+    uint64_t n_suspects;       /* code points that fail the quick check (0: the clean path) */
+    uint64_t n_dirty;          /* segments that hold one */
+    uint64_t n_dirty_long;     /* ... of them longer than 32 code points after decomposition (one wave each) */
+    uint64_t n_copied;         /* bytes the copy pass moved (0 on the clean path) */
+    double class_ms;           /* part marks, UTF-8 check, suspects */
+    double find_ms;            /* meta bytes, max-scan of the segment starts, the list of dirty segments */
+    double segments_ms;        /* lengths of the dirty segments and their scan */
+    double write_ms;           /* copy, the segments' bytes, the part offsets */
+    double total_ms;           /* first to last event, host gaps in between included */
+} yabpe_normalize_stats_t;
+int yabpe_normalize_stats(yabpe_ctx *ctx, yabpe_normalize_stats_t *out);
+
 /* Word pool (corpora larger than device memory) -----------------------------------------------------
  * The word-frequency pooling of trainer.py:221-225 (word_freq[word_tuple] += 1 over all sequences) as a structure that
  * persists across calls: the context keeps the multiset of distinct byte strings seen so far with u64 counts, on the device.

@@ -32,8 +32,10 @@
 #include "yabpe_layout_kernels.h"
 #include "yabpe_replay_kernels.h"
 #include "yabpe_pool_kernels.h"
+#include "yabpe_norm_kernels.h"
 #include "unicode_classes.inc"
 #include "unicode_subclasses.inc"
+#include "unicode_norm.inc"
 
 using namespace yb;
 
@@ -152,6 +154,12 @@ struct yabpe_ctx {
     std::vector<void *> pretok_bufs;          // staged text / word offsets handed out by yabpe_pretokenize
     uint8_t *pt_cls = nullptr;                // class per code point (unicode_classes.inc expanded), built on first use
     uint8_t *pt_cls5 = nullptr;               // the o200k_base pattern's table (pt5_table_entry), built on its first use
+    // normaliser (yabpe_normalize): the tables of unicode_norm.inc, built on first use, and the results of the last call
+    uint16_t *nfc_prop = nullptr;
+    uint32_t *nfc_decomp = nullptr, *nfc_pairs = nullptr;
+    std::vector<void *> norm_bufs;
+    yabpe_normalize_stats_t norm_stats{};
+    hipEvent_t norm_ev[5] = {};
     // encoder (yabpe_encode_set_model / yabpe_encode)
     bool have_enc_model = false;
     unsigned long long *enc_keys = nullptr;   // pair table: (a << 32 | b) -> enc_vals (rank, result)
@@ -1045,6 +1053,10 @@ void yabpe_destroy(yabpe_ctx *c) {
         if (e) (void)hipEventDestroy(e);
     dfree(c->pt_cls);
     dfree(c->pt_cls5);
+    yabpe_normalize_free(c);
+    dfree(c->nfc_prop); dfree(c->nfc_decomp); dfree(c->nfc_pairs);
+    for (auto &e : c->norm_ev)
+        if (e) (void)hipEventDestroy(e);
     free_corpus(c);
     free_records(c);
     dfree(c->tt.pool); dfree(c->tt.off); dfree(c->tt.len); dfree(c->tt.rec); dfree(c->tt.vset);
@@ -2573,6 +2585,231 @@ int yabpe_pretokenize_free(yabpe_ctx *c) {
     if (!c) return YABPE_E_INVALID;
     for (void *p : c->pretok_bufs) dfree(p);
     c->pretok_bufs.clear();
+    return YABPE_OK;
+}
+
+// ---------------------------------------------------------------------------------------------- normaliser
+// the tables of unicode_norm.inc on the device (the property per code point expanded to 0x110000 entries), built on first use
+static int nfc_tables(yabpe_ctx *c, NfcTables *T) {
+    if (!c->nfc_prop) {
+        if (YB_NFC_PROP_NRUNS < 2 || YB_NFC_PROP_RUNS[0][1] != 0 || YB_NFC_PROP_RUNS[1][0] < NFC_FIRST || YB_NFC_DECOMP[0][0] < NFC_FIRST_DECOMP)
+            return fail(c, YABPE_E_INTERNAL, "unicode_norm.inc: a code point below U+%04X has a property", NFC_FIRST);
+        std::vector<uint16_t> prop(0x110000, 0);
+        for (unsigned r = 0; r < YB_NFC_PROP_NRUNS; ++r) {
+            const unsigned lo = YB_NFC_PROP_RUNS[r][0];
+            const unsigned hi = r + 1 < YB_NFC_PROP_NRUNS ? YB_NFC_PROP_RUNS[r + 1][0] : 0x110000;
+            std::fill(prop.begin() + lo, prop.begin() + hi, (uint16_t)YB_NFC_PROP_RUNS[r][1]);
+        }
+        uint16_t *d_prop = nullptr;
+        uint32_t *d_dec = nullptr, *d_pairs = nullptr;
+        Scratch S(c->device, c->rank);
+        HIPCHK(c, S.get(&d_prop, prop.size()));
+        HIPCHK(c, S.get(&d_dec, (uint64_t)YB_NFC_NDECOMP * 5));
+        HIPCHK(c, S.get(&d_pairs, (uint64_t)YB_NFC_NPAIRS * 3));
+        HIPCHK(c, hipMemcpy(d_prop, prop.data(), prop.size() * 2, hipMemcpyHostToDevice));
+        HIPCHK(c, hipMemcpy(d_dec, YB_NFC_DECOMP, sizeof(YB_NFC_DECOMP), hipMemcpyHostToDevice));
+        HIPCHK(c, hipMemcpy(d_pairs, YB_NFC_PAIRS, sizeof(YB_NFC_PAIRS), hipMemcpyHostToDevice));
+        c->nfc_prop = S.take(d_prop);
+        c->nfc_decomp = S.take(d_dec);
+        c->nfc_pairs = S.take(d_pairs);
+    }
+    *T = NfcTables{c->nfc_prop, c->nfc_decomp, c->nfc_pairs, YB_NFC_NDECOMP, YB_NFC_NPAIRS};
+    return 0;
+}
+
+int yabpe_normalize_free(yabpe_ctx *c) {
+    if (!c) return YABPE_E_INVALID;
+    for (void *p : c->norm_bufs) dfree(p);
+    c->norm_bufs.clear();
+    return YABPE_OK;
+}
+
+int yabpe_normalize_stats(yabpe_ctx *c, yabpe_normalize_stats_t *out) {
+    if (!c || !out) return YABPE_E_INVALID;
+    *out = c->norm_stats;
+    return YABPE_OK;
+}
+
+// norm_ev[0..1] around the class pass, [1..2] the search for the dirty segments, [2..3] their lengths, [3..4] the write passes
+static void normalize_times(yabpe_ctx *c, int last) {
+    float ms[5] = {0, 0, 0, 0, 0};
+    for (int k = 0; k < last; ++k) (void)hipEventElapsedTime(&ms[k], c->norm_ev[k], c->norm_ev[k + 1]);
+    (void)hipEventElapsedTime(&ms[4], c->norm_ev[0], c->norm_ev[last]);
+    c->norm_stats.class_ms = ms[0];
+    c->norm_stats.find_ms = ms[1];
+    c->norm_stats.segments_ms = ms[2];
+    c->norm_stats.write_ms = ms[3];
+    c->norm_stats.total_ms = ms[4];
+}
+
+int yabpe_normalize(yabpe_ctx *c, const uint8_t *text, uint64_t n_bytes, const uint64_t *part_off, uint32_t n_parts, uint32_t form,
+                    const uint8_t **out_dev_text, uint64_t **out_dev_part_off, uint64_t *out_n_bytes, int64_t *out_bad_pos) {
+    if (!c || !out_dev_text || !out_dev_part_off || !out_n_bytes || !out_bad_pos) return YABPE_E_INVALID;
+    HIPCHK(c, hipSetDevice(c->device));
+    *out_dev_text = nullptr; *out_dev_part_off = nullptr; *out_n_bytes = 0; *out_bad_pos = -1;
+    if (form != YABPE_NORM_NFC) return fail(c, YABPE_E_INVALID, "normalisation form %u: only YABPE_NORM_NFC (1) is there", form);
+    if (n_bytes && !text) return fail(c, YABPE_E_INVALID, "text is NULL");
+    std::vector<unsigned long long> parts;
+    if (part_off && n_parts) {
+        for (uint32_t k = 0; k < n_parts; ++k) {
+            if (part_off[k] > n_bytes || (k && part_off[k] < part_off[k - 1])) return fail(c, YABPE_E_INVALID, "part offsets must ascend inside the text");
+            parts.push_back(part_off[k]);
+        }
+        if (parts[0] != 0) return fail(c, YABPE_E_INVALID, "the first part must start at 0");
+    } else {
+        parts.push_back(0);
+    }
+    const uint32_t np = (uint32_t)parts.size();
+    parts.push_back(n_bytes);  // (the offsets of the clean path: the input's, with the end)
+    NfcTables T{};
+    TRY(nfc_tables(c, &T));
+    yabpe_normalize_free(c);
+    c->norm_stats = yabpe_normalize_stats_t{};
+    c->norm_stats.n_bytes_in = n_bytes;
+    c->norm_stats.n_parts = np;
+    for (auto &e : c->norm_ev)
+        if (!e) HIPCHK(c, hipEventCreate(&e));
+    hipStream_t s = c->stream;
+    const unsigned long long n = n_bytes;
+    Scratch S(c->device, c->rank);
+    const uint8_t *d_text = nullptr;
+    TRY(to_device(c, S, text, n_bytes, 1, &d_text));
+    unsigned long long *d_parts = nullptr;
+    HIPCHK(c, S.get(&d_parts, parts.size()));
+    HIPCHK(c, hipMemcpyAsync(d_parts, parts.data(), parts.size() * 8, hipMemcpyHostToDevice, s));
+    // the result of the clean path (and of an empty text): the input and its offsets
+    auto hand_out_input = [&]() {
+        if (d_text != text && n) c->norm_bufs.push_back(S.take(const_cast<uint8_t *>(d_text)));  // (the staged text is handed out)
+        c->norm_bufs.push_back(S.take(d_parts));
+        *out_dev_text = n ? d_text : nullptr;
+        *out_dev_part_off = (uint64_t *)d_parts;
+        *out_n_bytes = n;
+        c->norm_stats.n_bytes_out = n;
+    };
+    if (n == 0) {
+        HIPCHK(c, hipStreamSynchronize(s));
+        hand_out_input();
+        return YABPE_OK;
+    }
+    // ---- class: part marks, UTF-8 check, suspects
+    uint8_t *marks = nullptr;
+    unsigned long long *ctr = nullptr;  // [0] first malformed byte, [1] suspects, [2] first segment over the cap, [3] long segments, [4] bytes copied
+    HIPCHK(c, S.get(&marks, n));
+    HIPCHK(c, S.get(&ctr, 5));
+    const unsigned long long ctr0[5] = {~0ull, 0, ~0ull, 0, 0};
+    unsigned long long h_ctr[5] = {0, 0, 0, 0, 0};
+    HIPCHK(c, hipEventRecord(c->norm_ev[0], s));
+    HIPCHK(c, hipMemsetAsync(marks, 0, n, s));
+    HIPCHK(c, hipMemcpyAsync(ctr, ctr0, sizeof(ctr0), hipMemcpyHostToDevice, s));
+    hipLaunchKernelGGL(k_pt_mark_chunks, dim3((np + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, s, marks, (const unsigned long long *)d_parts, np, n);
+    const unsigned long long n_pieces = (n + NFC_PIECE - 1) / NFC_PIECE;
+    const uint32_t cgrid = (uint32_t)std::min<unsigned long long>((n_pieces + BLOCK - 1) / BLOCK, (unsigned long long)c->n_cu * 16);
+    hipLaunchKernelGGL(k_nfc_class, dim3(cgrid), dim3(BLOCK), 0, s, d_text, (const uint8_t *)marks, (uint8_t *)nullptr, n, T, ctr);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipEventRecord(c->norm_ev[1], s));
+    HIPCHK(c, hipMemcpyAsync(h_ctr, ctr, 16, hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipStreamSynchronize(s));
+    if (h_ctr[0] != ~0ull) {
+        *out_bad_pos = (int64_t)h_ctr[0];
+        return fail(c, YABPE_E_UTF8, "invalid UTF-8 at byte %lld", (long long)h_ctr[0]);
+    }
+    c->norm_stats.n_suspects = h_ctr[1];
+    if (h_ctr[1] == 0) {  // the text is NFC
+        normalize_times(c, 1);
+        hand_out_input();
+        return YABPE_OK;
+    }
+    // ---- find: the meta bytes, the segment start of every suspect, the list of dirty segments
+    uint8_t *meta = nullptr, *flags = nullptr;
+    HIPCHK(c, S.get(&meta, n));
+    HIPCHK(c, S.get(&flags, n + 8));
+    HIPCHK(c, hipMemsetAsync(flags, 0, n + 8, s));
+    HIPCHK(c, hipMemsetAsync(ctr + 1, 0, 8, s));
+    hipLaunchKernelGGL(k_nfc_class, dim3(cgrid), dim3(BLOCK), 0, s, d_text, (const uint8_t *)marks, meta, n, T, ctr);
+    const unsigned long long n_win = (n + NFC_WIN - 1) / NFC_WIN;
+    const uint32_t wgrid = (uint32_t)std::min<unsigned long long>(n_win, 1u << 20);
+    NfcPos *win = nullptr;
+    HIPCHK(c, S.get(&win, n_win));
+    hipLaunchKernelGGL(k_nfc_windows, dim3(wgrid), dim3(BLOCK), 0, s, (const uint8_t *)meta, n, win);
+    hipLaunchKernelGGL(k_nfc_carry, dim3(1), dim3(BLOCK), 0, s, win, n_win);
+    hipLaunchKernelGGL(k_nfc_apply, dim3(wgrid), dim3(BLOCK), 0, s, (const uint8_t *)meta, n, (const NfcPos *)win, flags);
+    HIPCHK(c, hipGetLastError());
+    unsigned long long *dstart = nullptr, n_dirty = 0;
+    if (pt_offsets(s, S, flags, n, ~0ull, &dstart, &n_dirty) != 0) return fail(c, YABPE_E_HIP, "normaliser: list of dirty segments: %s", hipGetErrorString(hipGetLastError()));
+    HIPCHK(c, hipEventRecord(c->norm_ev[2], s));
+    HIPCHK(c, hipStreamSynchronize(s));  // (the scatter still reads the flags; the blocks go back to a cache other streams draw from)
+    S.release(flags);
+    S.release(win);
+    S.release(marks);
+    c->norm_stats.n_dirty = n_dirty;
+    if (n_dirty == 0) return fail(c, YABPE_E_INTERNAL, "normaliser: %llu suspects and no dirty segment", h_ctr[1]);
+    // ---- segments: lengths of the short ones, then of those that need the long path; the scan of out - in
+    NfcSegParams P{};
+    P.text = d_text; P.meta = meta; P.n = n; P.T = T; P.dstart = dstart; P.n_dirty = n_dirty; P.ctr = ctr + 2;
+    unsigned long long *shift = nullptr, *loff = nullptr;
+    HIPCHK(c, S.get(&P.dend, n_dirty));
+    HIPCHK(c, S.get(&P.delta, n_dirty));
+    HIPCHK(c, S.get(&P.nent, n_dirty));
+    HIPCHK(c, S.get(&P.long_list, n_dirty));
+    HIPCHK(c, S.get(&shift, n_dirty + 1));
+    const uint32_t sgrid = (uint32_t)std::min<unsigned long long>((n_dirty + BLOCK - 1) / BLOCK, 1u << 20);
+    hipLaunchKernelGGL(k_nfc_short, dim3(sgrid), dim3(BLOCK), 0, s, P, 0);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(h_ctr + 2, ctr + 2, 16, hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipStreamSynchronize(s));
+    if (h_ctr[2] != ~0ull) {
+        *out_bad_pos = (int64_t)h_ctr[2];
+        return fail(c, YABPE_E_CAPACITY, "the segment that starts at byte %lld holds more than %u code points to normalise together (a base and its "
+                    "combining marks): over the cap of %u", (long long)h_ctr[2], NFC_CAP, NFC_CAP);
+    }
+    const unsigned long long n_long = h_ctr[3];
+    c->norm_stats.n_dirty_long = n_long;
+    uint32_t lgrid = 0;
+    if (n_long) {
+        HIPCHK(c, S.get(&loff, n_dirty + 1));
+        if (exclusive_scan<uint32_t>(s, P.nent, n_dirty, loff, n_dirty + 1) != 0) return fail(c, YABPE_E_HIP, "normaliser: scan of the long segments");
+        unsigned long long n_ent = 0;
+        HIPCHK(c, hipMemcpyAsync(&n_ent, loff + n_dirty, 8, hipMemcpyDeviceToHost, s));
+        HIPCHK(c, hipStreamSynchronize(s));
+        HIPCHK(c, S.get(&P.gbuf, n_ent));
+        HIPCHK(c, S.get(&P.gtmp, n_ent));
+        P.loff = loff;
+        lgrid = (uint32_t)std::min<unsigned long long>((n_long + WPB - 1) / WPB, 1u << 20);
+        hipLaunchKernelGGL(k_nfc_long, dim3(lgrid), dim3(BLOCK), 0, s, P, n_long, 0);
+        HIPCHK(c, hipGetLastError());
+    }
+    if (exclusive_scan<unsigned long long>(s, P.delta, n_dirty, shift, n_dirty + 1) != 0) return fail(c, YABPE_E_HIP, "normaliser: scan of the lengths");
+    unsigned long long grown = 0;
+    HIPCHK(c, hipMemcpyAsync(&grown, shift + n_dirty, 8, hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipEventRecord(c->norm_ev[3], s));
+    HIPCHK(c, hipStreamSynchronize(s));
+    const unsigned long long n_out = n + grown;  // (mod 2^64: the segments may have shrunk)
+    if (n_out > 3 * n) return fail(c, YABPE_E_INTERNAL, "normaliser: %llu bytes out of %llu", n_out, n);
+    // ---- write
+    uint8_t *out = nullptr;
+    unsigned long long *out_off = nullptr;
+    HIPCHK(c, S.get(&out, n_out));
+    HIPCHK(c, S.get(&out_off, (uint64_t)np + 1));
+    P.shift = shift;
+    P.out = out;
+    hipLaunchKernelGGL(k_nfc_copy, dim3(wgrid), dim3(BLOCK), 0, s, d_text, n, (const unsigned long long *)dstart, (const unsigned long long *)P.dend,
+                       (const unsigned long long *)shift, n_dirty, out, ctr + 4);
+    hipLaunchKernelGGL(k_nfc_short, dim3(sgrid), dim3(BLOCK), 0, s, P, 1);
+    if (n_long) hipLaunchKernelGGL(k_nfc_long, dim3(lgrid), dim3(BLOCK), 0, s, P, n_long, 1);
+    hipLaunchKernelGGL(k_nfc_offsets, dim3(np / BLOCK + 1), dim3(BLOCK), 0, s, (const unsigned long long *)d_parts, np, n_out,
+                       (const unsigned long long *)dstart, (const unsigned long long *)shift, n_dirty, out_off);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipEventRecord(c->norm_ev[4], s));
+    HIPCHK(c, hipMemcpyAsync(h_ctr + 4, ctr + 4, 8, hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipStreamSynchronize(s));
+    normalize_times(c, 4);
+    c->norm_stats.n_copied = h_ctr[4];
+    c->norm_stats.n_bytes_out = n_out;
+    c->norm_bufs.push_back(S.take(out));
+    c->norm_bufs.push_back(S.take(out_off));
+    *out_dev_text = out;
+    *out_dev_part_off = (uint64_t *)out_off;
+    *out_n_bytes = n_out;
     return YABPE_OK;
 }
 

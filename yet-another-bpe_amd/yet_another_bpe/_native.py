@@ -29,8 +29,18 @@ class Utf8Error(ValueError):
         self.position = position
 
 
+class SegmentTooLong(ValueError):
+    """yabpe_normalize met a run of code points that normalise together (a base and its combining marks) over the cap;
+    .position = the byte where that segment starts inside the buffer."""
+
+    def __init__(self, position: int, msg: str):
+        super().__init__(msg)
+        self.position = position
+
+
 E_CAPACITY = -4
 E_UTF8 = -7
+NORM_NFC = 1  # yabpe_normalize: form
 
 
 class Stats(ctypes.Structure):
@@ -77,6 +87,11 @@ class PoolStats(ctypes.Structure):
         (n, c_double) for n in ("pool_ms", "probe_ms", "append_ms", "total_ms")]
 
 
+class NormalizeStats(ctypes.Structure):
+    _fields_ = [(n, c_uint64) for n in ("n_bytes_in", "n_bytes_out", "n_parts", "n_suspects", "n_dirty", "n_dirty_long", "n_copied")] + [
+        (n, c_double) for n in ("class_ms", "find_ms", "segments_ms", "write_ms", "total_ms")]
+
+
 class Latency(ctypes.Structure):
     _fields_ = [(n, c_double) for n in ("launch_gap_us", "load_trip_us", "coherent_trip_us", "atomic_trip_us")]
 
@@ -97,6 +112,7 @@ SYMBOLS = [
     "yabpe_load_words_resumed", "yabpe_resume_stats",
     "yabpe_layout_pad", "yabpe_layout_pack", "yabpe_layout_free", "yabpe_layout_stats",
     "yabpe_pool_add", "yabpe_pool_get", "yabpe_pool_clear", "yabpe_pool_stats",
+    "yabpe_normalize", "yabpe_normalize_free", "yabpe_normalize_stats",
 ]
 
 
@@ -168,6 +184,10 @@ def lib() -> ctypes.CDLL:
         L.yabpe_pool_get.argtypes = [c_void_p, POINTER(c_void_p), POINTER(c_void_p), POINTER(c_void_p), POINTER(c_uint64), POINTER(c_uint64)]
         L.yabpe_pool_clear.argtypes = [c_void_p]
         L.yabpe_pool_stats.argtypes = [c_void_p, POINTER(PoolStats)]
+        L.yabpe_normalize.argtypes = [c_void_p, c_void_p, c_uint64, c_void_p, c_uint32, c_uint32, POINTER(c_void_p), POINTER(c_void_p),
+                                      POINTER(c_uint64), POINTER(ctypes.c_int64)]
+        L.yabpe_normalize_free.argtypes = [c_void_p]
+        L.yabpe_normalize_stats.argtypes = [c_void_p, POINTER(NormalizeStats)]
         if L.yabpe_abi_version() != 2:
             raise ImportError("libyabpe.so ABI version mismatch")
         _lib = L
@@ -394,6 +414,43 @@ class Context:
 
     def pretokenize_free(self) -> None:
         self._chk(lib().yabpe_pretokenize_free(self._h))
+
+    # -- Unicode normalisation in front of pretokenize() / encode() (include/yabpe.h: yabpe_normalize)
+    def normalize(self, text, n_bytes: int | None = None, part_starts=None, form: int = NORM_NFC):
+        """NFC of every part of `text` on the device.  `text`: bytes / u8 array (staged) or a device address (then n_bytes is
+        required).  part_starts: ascending part starts, the first one 0 (None: one part); parts are normalised independently.
+        -> (dev_text_ptr, dev_part_off_ptr u64[n_parts + 1], n_bytes_out); the buffers live until the next normalize,
+        normalize_free() or close().  A text that is NFC already comes back as it is (a device address: the same address).
+        Raises Utf8Error(position) on malformed UTF-8 and SegmentTooLong(position) over the cap, positions in the input."""
+        keep = None
+        if isinstance(text, int):
+            ptr, n = c_void_p(text), int(n_bytes)
+        else:
+            keep = np.frombuffer(text, dtype=np.uint8) if not isinstance(text, np.ndarray) else np.ascontiguousarray(text, dtype=np.uint8)
+            ptr, n = c_void_p(keep.ctypes.data if keep.size else 0), int(keep.size)
+        st = np.ascontiguousarray(part_starts if part_starts is not None and len(part_starts) else [0], dtype=np.uint64)
+        dt, do, nb, bad = c_void_p(), c_void_p(), c_uint64(0), ctypes.c_int64(-1)
+        rc = lib().yabpe_normalize(self._h, ptr, n, st.ctypes.data, len(st), int(form), byref(dt), byref(do), byref(nb), byref(bad))
+        if rc == E_UTF8:
+            raise Utf8Error(bad.value)
+        if rc == E_CAPACITY and bad.value >= 0:
+            raise SegmentTooLong(bad.value, lib().yabpe_last_error(self._h).decode())
+        self._chk(rc)
+        return dt.value or 0, do.value, nb.value
+
+    def normalize_to_host(self, text, n_bytes: int | None = None, part_starts=None, form: int = NORM_NFC):
+        """-> (text u8[n_bytes_out], part_off u64[n_parts + 1]) copied to the host."""
+        n_parts = len(part_starts) if part_starts is not None and len(part_starts) else 1
+        dt, do, nb = self.normalize(text, n_bytes, part_starts, form)
+        return (self.d2h(dt, nb) if nb else np.zeros(0, np.uint8)), self.d2h(do, 8 * (n_parts + 1), np.uint64)
+
+    def normalize_free(self) -> None:
+        self._chk(lib().yabpe_normalize_free(self._h))
+
+    def normalize_stats(self) -> dict:
+        s = NormalizeStats()
+        self._chk(lib().yabpe_normalize_stats(self._h, byref(s)))
+        return {f: getattr(s, f) for f, _ in NormalizeStats._fields_}
 
     # -- encoding with a trained model (BBPETokenizer.encode on the device)
     def encode_set_model(self, vocab: dict, merges, specials_ordered, unk_id: int) -> None:

@@ -148,6 +148,18 @@ def plan_chunk_shards(sizes: Sequence[int], world: int) -> list[tuple[int, int]]
     return [(min(bounds[r], len(sizes)), min(bounds[r + 1], len(sizes))) for r in range(world)]
 
 
+def _pretokenize_my_chunks(ctx, text, n_bytes, starts, config):
+    """This rank's chunks -> (device text, device word offsets, n_words): with config.normalizer yabpe_normalize runs in front of
+    yabpe_pretokenize (chunk by chunk; the normalised text stays the context's), as BBPETrainer._device_words does it."""
+    from .trainer import check_normalizer
+
+    form = check_normalizer(getattr(config, "normalizer", None))
+    if form:
+        text, dev_starts, n_bytes = ctx.normalize(text, n_bytes=n_bytes, part_starts=starts, form=form)
+        starts = ctx.d2h(dev_starts, 8 * len(starts), np.uint64)
+    return ctx.pretokenize(text, n_bytes=n_bytes, chunk_starts=starts, special_tokens=list(config.special_tokens))
+
+
 def _train_my_words(ctx, dev_text: int, dev_off: int, n_words: int, config, num_merges: int):
     """Loads this rank's pre-tokens (pooled), or nothing in the same layout as the peers, and joins the merge loop."""
     if n_words:
@@ -165,7 +177,7 @@ def train_text_sharded(ctx_factory, files, config, rank: int, world: int, transp
     from pathlib import Path
 
     from . import _native
-    from .trainer import BBPETrainer, check_files, device_options, read_chunks, utf8_error
+    from .trainer import BBPETrainer, check_files, device_options, read_chunks, segment_error, utf8_error
 
     device_options(config)  # (ValueError before any file is read)
     tr = BBPETrainer(config)
@@ -184,9 +196,11 @@ def train_text_sharded(ctx_factory, files, config, rank: int, world: int, transp
         dev_text, dev_off, n_words = 0, 0, 0
         if len(text):
             try:
-                dev_text, dev_off, n_words = ctx.pretokenize(text, chunk_starts=starts, special_tokens=list(config.special_tokens))
+                dev_text, dev_off, n_words = _pretokenize_my_chunks(ctx, text, None, starts, config)
             except _native.Utf8Error as e:
                 err = (rank, str(utf8_error(chunks[c0:c1], starts, e)))  # (the chunks go to the ranks in order)
+            except _native.SegmentTooLong as e:
+                err = (rank, str(segment_error(chunks[c0:c1], starts, e)))
         if world > 1:  # every rank must learn about the first bad chunk anywhere, or the others would wait in the merge loop
             import torch.distributed as dist
 
@@ -221,8 +235,7 @@ def train_device_text_sharded(ctx_factory, make_text, config, rank: int, world: 
         if mine:
             a0 = mine[0][0]
             assert all(mine[i][1] == mine[i + 1][0] for i in range(len(mine) - 1)), "chunks of valid UTF-8 follow one another"
-            dev_text, dev_off, n_words = ctx.pretokenize(ptr + a0, n_bytes=mine[-1][1] - a0, chunk_starts=[a - a0 for a, _ in mine],
-                                                         special_tokens=list(config.special_tokens))
+            dev_text, dev_off, n_words = _pretokenize_my_chunks(ctx, ptr + a0, mine[-1][1] - a0, [a - a0 for a, _ in mine], config)
         left, right, merged, count = _train_my_words(ctx, dev_text, dev_off, n_words, config, max(0, config.vocab_size - len(base)))
         return left, right, merged, count, ctx.stats(), n_words
 

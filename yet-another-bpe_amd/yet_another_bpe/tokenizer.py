@@ -25,8 +25,8 @@ import numpy as np
 import regex
 
 from .synth import rnd_int
-from .trainer import (CL100K_DIGIT_GROUP, PRETOKENIZER_NAMES, BBPETrainerConfig, check_digit_group, check_pretokenizer, device_options, read_pretokenizer,
-                      split_pattern)
+from .trainer import (CL100K_DIGIT_GROUP, NORMALIZERS, PRETOKENIZER_NAMES, BBPETrainerConfig, check_digit_group, check_normalized_specials,
+                      check_normalizer, check_pretokenizer, device_options, normalize_text, read_normalizer, read_pretokenizer, split_pattern)
 
 _WORD_CACHE = 8192
 
@@ -35,10 +35,15 @@ class BBPETokenizer:
     """Applies learned merges, lowest rank first (leftmost on ties), to GPT-2 pre-tokens; with digit_group = G (1 .. 255; not
     in the reference) to the pre-tokens of the pattern whose \\p{N}+ is \\p{N}{1,G} -- the pre-tokenisation of a model trained
     with BBPETrainerConfig(digit_group=G); with pretokenizer = "cl100k" to those of the GPT-4 / Llama-3 pattern, with
-    "o200k_base" to those of the GPT-4o pattern (digit_group None: 3 for both).  Every method, plain Python or on the GPU, follows it."""
+    "o200k_base" to those of the GPT-4o pattern (digit_group None: 3 for both).  Every method, plain Python or on the GPU, follows it.
+    With normalizer = "nfc" every method that takes text replaces each document by unicodedata.normalize("NFC", document) first
+    (on the GPU: yabpe_normalize in front of the encode call), so encode(x) == encode(normalize(x)); the specials are matched in
+    the normalised text (a special that is not NFC itself: ValueError), and the spans of the *_with_offsets methods, in bytes
+    and in characters, refer to the normalised document, which normalize() / normalize_array() return.  Decoding is untouched."""
 
     def __init__(self, vocab: dict[bytes, int] | None = None, merges: list[tuple[bytes, bytes]] | None = None,
-                 special_tokens: list[str] | None = None, digit_group: int | None = None, pretokenizer: str = "gpt2") -> None:
+                 special_tokens: list[str] | None = None, digit_group: int | None = None, pretokenizer: str = "gpt2",
+                 normalizer: str | None = None) -> None:
         self._vocab: dict[bytes, int] = vocab or {}
         self._vocab_inv: dict[int, bytes] = {i: t for t, i in self._vocab.items()}
         self._merges: list[tuple[bytes, bytes]] = merges or []
@@ -48,6 +53,8 @@ class BBPETokenizer:
         self._pretokenizer: str = PRETOKENIZER_NAMES[check_pretokenizer(pretokenizer)]
         self._digit_group: int | None = check_digit_group(digit_group) or (CL100K_DIGIT_GROUP if self._pretokenizer != "gpt2" else None)
         self._pattern = regex.compile(split_pattern(self._digit_group, self._pretokenizer))
+        self._normalizer: str | None = NORMALIZERS[check_normalizer(normalizer)]
+        check_normalized_specials(self._special_tokens, self._normalizer)
         # specials are split out first, longest first (reference tokenizer.py:100-102)
         self._special_pattern = None
         if self._special_tokens:
@@ -79,7 +86,7 @@ class BBPETokenizer:
             with open(sp, encoding="utf-8") as f:
                 specials = list(json.load(f))
         name, group = read_pretokenizer(d)
-        return cls(vocab=vocab, merges=merges, special_tokens=specials, digit_group=group, pretokenizer=name)
+        return cls(vocab=vocab, merges=merges, special_tokens=specials, digit_group=group, pretokenizer=name, normalizer=read_normalizer(d))
 
     @classmethod
     def from_file_lossless(cls, model_dir: str | Path) -> "BBPETokenizer":
@@ -98,7 +105,7 @@ class BBPETokenizer:
             with open(d / "special_tokens.json", encoding="utf-8") as f:
                 specials = list(json.load(f))
         name, group = read_pretokenizer(d)
-        return cls(vocab=vocab, merges=merges, special_tokens=specials, digit_group=group, pretokenizer=name)
+        return cls(vocab=vocab, merges=merges, special_tokens=specials, digit_group=group, pretokenizer=name, normalizer=read_normalizer(d))
 
     # ------------------------------------------------------------------ encode
     def _word_parts(self, data: bytes) -> list[bytes]:
@@ -133,7 +140,12 @@ class BBPETokenizer:
         for pre in self._pattern.findall(text):
             out.extend(self._word_ids(pre))
 
+    def normalize(self, text: str) -> str:
+        """The document the ids and spans of `text` refer to: `text` as the model's normaliser leaves it (none: as it is)."""
+        return normalize_text(text, self._normalizer)
+
     def encode(self, text: str) -> list[int]:
+        text = self.normalize(text)
         if not text:
             return []
         ids: list[int] = []
@@ -203,6 +215,7 @@ class BBPETokenizer:
         Nothing is cached: every occurrence of a word draws on its own."""
         T = self._dropout_threshold(p)
         seed, doc = self._u64(seed, "seed"), self._u64(doc, "doc")
+        text = self.normalize(text)
         if not text:
             return []
         kd = rnd_int(seed, 0x64, doc)
@@ -274,6 +287,7 @@ class BBPETokenizer:
         (lead(start + 1) - 1, lead(end))."""
         if unit not in ("char", "byte"):
             raise ValueError(f"unit must be 'char' or 'byte', not {unit!r}")
+        text = self.normalize(text)
         if not text:
             return [], []
         ids, spans = self._byte_spans(text)
@@ -401,6 +415,30 @@ class BBPETokenizer:
         starts[1:] = np.cumsum([len(b) for b in blobs], dtype=np.uint64)[:-1]
         return b"".join(blobs), starts
 
+    def _device_text(self, ctx, inp):
+        """What the encode calls of ctx take as (text, n_bytes, doc_starts) for _device_input's buffer: the buffer itself, or with
+        a normaliser the normalised text in device memory (yabpe_normalize; the context's until its next normalize) and the
+        documents' starts in it."""
+        text = np.frombuffer(inp[0], dtype=np.uint8)
+        form = check_normalizer(self._normalizer)
+        if not form or not text.size:
+            return text, None, inp[1]
+        dev_text, dev_starts, n_bytes = ctx.normalize(text, part_starts=inp[1], form=form)
+        starts = ctx.d2h(dev_starts, 8 * len(inp[1]), np.uint64)
+        return (dev_text, n_bytes, starts) if n_bytes else (np.zeros(0, np.uint8), None, starts)
+
+    def normalize_array(self, texts) -> tuple[np.ndarray, np.ndarray]:
+        """normalize() of every document on the GPU: `texts` as encode_array takes them -> (text np.uint8[n], text_off
+        np.uint64[n_docs + 1]): text[text_off[d]:text_off[d + 1]] is normalize(texts[d]) as UTF-8 -- the documents the spans of
+        encode_array_with_offsets refer to.  Without a normaliser the documents come back as they are."""
+        inp = self._device_input(texts)
+        if inp is None:
+            return np.zeros(0, np.uint8), np.zeros(1, np.uint64)
+        form = check_normalizer(self._normalizer)
+        if not form:
+            return np.frombuffer(inp[0], dtype=np.uint8).copy(), np.append(np.asarray(inp[1], dtype=np.uint64), np.uint64(len(inp[0])))
+        return self._device().normalize_to_host(np.frombuffer(inp[0], dtype=np.uint8), part_starts=inp[1], form=form)
+
     def encode_array(self, texts) -> tuple[np.ndarray, np.ndarray]:
         """Encodes on the GPU: `texts` is a sequence of str (one document each) or one bytes buffer (one document).
         -> (ids np.uint32[n], doc_off np.uint64[n_docs + 1]): document d's ids are ids[doc_off[d]:doc_off[d + 1]], equal to
@@ -408,7 +446,9 @@ class BBPETokenizer:
         inp = self._device_input(texts)
         if inp is None:
             return np.zeros(0, np.uint32), np.zeros(1, np.uint64)
-        return self._device().encode_to_host(np.frombuffer(inp[0], dtype=np.uint8), doc_starts=inp[1])
+        ctx = self._device()
+        text, n_bytes, starts = self._device_text(ctx, inp)
+        return ctx.encode_to_host(text, n_bytes, doc_starts=starts)
 
     def encode_batch_device(self, texts: Sequence[str]) -> list[list[int]]:
         """encode_batch(texts), computed on the GPU in one call."""
@@ -425,7 +465,9 @@ class BBPETokenizer:
         inp = self._device_input(texts)
         if inp is None:
             return np.zeros(0, np.uint32), np.zeros(1, np.uint64), np.zeros((0, 2), np.uint64)
-        return self._device().encode_spans_to_host(np.frombuffer(inp[0], dtype=np.uint8), doc_starts=inp[1], chars=unit == "char")
+        ctx = self._device()
+        text, n_bytes, starts = self._device_text(ctx, inp)
+        return ctx.encode_spans_to_host(text, n_bytes, doc_starts=starts, chars=unit == "char")
 
     def encode_batch_device_with_offsets(self, texts: Sequence[str], unit: str = "char"):
         """encode_batch_with_offsets(texts, unit), computed on the GPU in one call."""
@@ -436,10 +478,10 @@ class BBPETokenizer:
     def _device_encode_for_layout(self, ctx, inp, dropout, seed):
         """-> the device results the layout passes read: yabpe_encode's, or yabpe_encode_dropout's when dropout > 0"""
         T, seed = self._dropout_threshold(dropout), self._u64(seed, "seed")
-        text = np.frombuffer(inp[0], dtype=np.uint8)
+        text, n_bytes, starts = self._device_text(ctx, inp)
         if T == 0:
-            return ctx.encode(text, doc_starts=inp[1])
-        return ctx.encode_dropout(text, T, seed, doc_starts=inp[1])
+            return ctx.encode(text, n_bytes, doc_starts=starts)
+        return ctx.encode_dropout(text, T, seed, n_bytes, doc_starts=starts)
 
     def encode_array_dropout(self, texts, p: float, seed: int = 0) -> tuple[np.ndarray, np.ndarray]:
         """encode_batch_dropout(texts, p, seed) on the GPU, id for id: `texts` and the results as encode_array's (one bytes
@@ -448,7 +490,9 @@ class BBPETokenizer:
         inp = self._device_input(texts)
         if inp is None:
             return np.zeros(0, np.uint32), np.zeros(1, np.uint64)
-        return self._device().encode_dropout_to_host(np.frombuffer(inp[0], dtype=np.uint8), T, seed, doc_starts=inp[1])
+        ctx = self._device()
+        text, n_bytes, starts = self._device_text(ctx, inp)
+        return ctx.encode_dropout_to_host(text, T, seed, n_bytes, doc_starts=starts)
 
     def encode_batch_device_dropout(self, texts: Sequence[str], p: float, seed: int = 0) -> list[list[int]]:
         """encode_batch_dropout(texts, p, seed), computed on the GPU in one call."""
@@ -542,6 +586,10 @@ class BBPETokenizer:
     @property
     def pretokenizer(self) -> str:
         return self._pretokenizer
+
+    @property
+    def normalizer(self) -> str | None:
+        return self._normalizer
 
     @property
     def special_tokens(self) -> list[str]:

@@ -26,6 +26,7 @@ from __future__ import annotations
 
 import json
 import os
+import unicodedata
 from collections import Counter
 from collections.abc import Mapping, Sequence
 from concurrent.futures import ThreadPoolExecutor
@@ -53,6 +54,9 @@ CL100K_DIGIT_GROUP = 3  # digit_group=None with the cl100k or the o200k_base pat
 # {"digit_group": G} (GPT-2 pattern with a group) or {"pattern": "cl100k" / "o200k_base", "digit_group": G}, written next to a
 # saved model; the plain GPT-2 pattern writes no file
 PRETOKENIZER_FILE = "pretokenizer.json"
+# the normalisers: None, or "nfc" -- every chunk (training) and every document (encoding) is replaced by its Unicode NFC form
+# (unicodedata.normalize("NFC", ...)) before anything else looks at it; pretokenizer.json gains "normalizer": "nfc"
+NORMALIZERS = (None, "nfc")
 
 
 def split_pattern(group: int | None = None, pretokenizer: str = "gpt2") -> str:
@@ -83,6 +87,41 @@ def read_pretokenizer(model_dir: str | Path) -> tuple[str, int | None]:
     name = d.get("pattern", "gpt2")
     group = check_digit_group(d.get("digit_group")) or None
     return name, (group or CL100K_DIGIT_GROUP) if check_pretokenizer(name) else group
+
+
+def check_normalizer(name) -> int:
+    """A normaliser name as the form argument of the library's yabpe_normalize (0: none, 1: "nfc").  ValueError for anything
+    but None or "nfc"."""
+    if name is None:
+        return 0
+    if not isinstance(name, str) or name != "nfc":
+        raise ValueError(f"normalizer must be one of {NORMALIZERS!r}, got {name!r}")
+    return 1
+
+
+def check_normalized_specials(tokens: Sequence[str], name) -> None:
+    """With a normaliser the specials are matched in the normalised text, so a special that is not normalised itself could
+    never match: ValueError."""
+    if check_normalizer(name):
+        for tok in tokens:
+            if unicodedata.normalize("NFC", tok) != tok:
+                raise ValueError(f"special token {tok!r} is not in NFC: with normalizer = 'nfc' it could never match the normalised text")
+
+
+def normalize_text(text: str, name) -> str:
+    """THE host-side normaliser: `text` as the normaliser `name` leaves it (None: as it is)."""
+    return unicodedata.normalize("NFC", text) if name else text
+
+
+def read_normalizer(model_dir: str | Path) -> str | None:
+    """The normaliser a saved model was trained with: pretokenizer.json in its directory, None when it names none."""
+    f = Path(model_dir) / PRETOKENIZER_FILE
+    if not f.exists():
+        return None
+    with open(f, encoding="utf-8") as fh:
+        name = json.load(fh).get("normalizer")
+    check_normalizer(name)
+    return name
 
 
 def read_digit_group(model_dir: str | Path) -> int | None:
@@ -132,6 +171,13 @@ class BBPETrainerConfig:
             with its word, "/" kept behind the newlines that follow punctuation; digit_group and the first character of a
             special as with "cl100k", and no special token may contain another one or end with the beginning of one, itself
             included (ValueError): their occurrences must not overlap.
+        normalizer: None, or "nfc": every chunk _chunk_ranges cuts is replaced by unicodedata.normalize("NFC", chunk) before
+            the special tokens and the split pattern see it (on the device: yabpe_normalize in front of yabpe_pretokenize);
+            chunks are normalised independently.  What Qwen2's tokenizer does in front of the cl100k split.  Part of the
+            model like the pattern (BBPEModel.normalizer, "normalizer" in pretokenizer.json, BBPETokenizer).  Specials are
+            matched in the normalised text: a special token that is not NFC itself is a ValueError, and "<|endoftext|>"
+            followed by U+0338 normalises to "<|endoftext|" + U+226F and is then no special.  A run of more than 16,384
+            code points that normalise together (a base with its combining marks) is a ValueError that names the file.
     """
 
     vocab_size: int = 32000
@@ -143,6 +189,7 @@ class BBPETrainerConfig:
     max_token_length: int | None = None
     digit_group: int | None = None
     pretokenizer: str = "gpt2"
+    normalizer: str | None = None
 
 
 def max_token_bytes(config: BBPETrainerConfig) -> int:
@@ -173,6 +220,7 @@ def pretokenizer(config: BBPETrainerConfig) -> tuple[int, int]:
                 raise ValueError(f"special token {tok!r} begins with whitespace (\\s): not allowed with pretokenizer = {PRETOKENIZER_NAMES[pattern]!r}")
     if pattern == 3:
         check_disjoint_specials(config.special_tokens)
+    check_normalized_specials(config.special_tokens, getattr(config, "normalizer", None))
     return pattern, group
 
 
@@ -197,15 +245,17 @@ def digit_group(config: BBPETrainerConfig) -> int:
 class BBPEModel:
     """Result container (reference trainer.py:41-52): copies of vocab, merges, special tokens; digit_group (not in the
     reference): the digit group of the pre-tokenisation the model was trained with, None for the GPT-2 pattern; pretokenizer:
-    "gpt2", or "cl100k" / "o200k_base" (digit_group is then never None)."""
+    "gpt2", or "cl100k" / "o200k_base" (digit_group is then never None); normalizer: None or "nfc"."""
 
     def __init__(self, vocab: Mapping[bytes, int], merges: Sequence[tuple[bytes, bytes]],
-                 special_tokens: Sequence[str], digit_group: int | None = None, pretokenizer: str = "gpt2") -> None:
+                 special_tokens: Sequence[str], digit_group: int | None = None, pretokenizer: str = "gpt2",
+                 normalizer: str | None = None) -> None:
         self.vocab: dict[bytes, int] = dict(vocab)
         self.merges: list[tuple[bytes, bytes]] = list(merges)
         self.special_tokens: list[str] = list(special_tokens)
         self.pretokenizer: str = PRETOKENIZER_NAMES[check_pretokenizer(pretokenizer)]
         self.digit_group: int | None = check_digit_group(digit_group) or (CL100K_DIGIT_GROUP if self.pretokenizer != "gpt2" else None)
+        self.normalizer: str | None = NORMALIZERS[check_normalizer(normalizer)]
 
     @classmethod
     def from_file_lossless(cls, model_dir: str | Path) -> "BBPEModel":
@@ -225,7 +275,7 @@ class BBPEModel:
             with open(d / "special_tokens.json", encoding="utf-8") as f:
                 specials = list(json.load(f))
         name, group = read_pretokenizer(d)
-        return cls(vocab=vocab, merges=merges, special_tokens=specials, digit_group=group, pretokenizer=name)
+        return cls(vocab=vocab, merges=merges, special_tokens=specials, digit_group=group, pretokenizer=name, normalizer=read_normalizer(d))
 
 
 def _utf8_cut(window: bytes, pos: int) -> int:
@@ -316,6 +366,14 @@ def utf8_error(chunks: Sequence[tuple[Path, int, int]], starts: Sequence[int], e
     return ValueError(f"File {path} contains invalid UTF-8 at position {start + e.position - starts[k]}.")
 
 
+def segment_error(chunks: Sequence[tuple[Path, int, int]], starts: Sequence[int], e) -> ValueError:
+    """The same for a _native.SegmentTooLong of the normaliser: the file and the position where the run starts."""
+    k = max(i for i, s0 in enumerate(starts) if s0 <= e.position)
+    path, start, _stop = chunks[k]
+    return ValueError(f"File {path} holds a run of code points that normalise together over the normaliser's cap at position "
+                      f"{start + e.position - starts[k]}: {e}")
+
+
 class BBPETrainer:
     """Byte-level BPE trainer with the reference's API; the merge loop runs on the GPU."""
 
@@ -341,7 +399,7 @@ class BBPETrainer:
     def _model(self, vocab, merges) -> BBPEModel:
         pattern, group = pretokenizer(self.config)
         return BBPEModel(vocab=vocab, merges=merges, special_tokens=list(self.config.special_tokens), digit_group=group or None,
-                         pretokenizer=PRETOKENIZER_NAMES[pattern])
+                         pretokenizer=PRETOKENIZER_NAMES[pattern], normalizer=getattr(self.config, "normalizer", None))
 
     # ------------------------------------------------------------------ train / save (trainer.py:63-117)
     def train(self, files: Sequence[str | Path], batch_bytes: int | None = None) -> BBPEModel:
@@ -377,6 +435,9 @@ class BBPETrainer:
         if getattr(model, "digit_group", None) != (group or None):
             raise ValueError(f"cannot continue from this model: it was trained with digit_group = {getattr(model, 'digit_group', None)!r}, "
                              f"the trainer's is {group or None!r} (its merges would be replayed over words it never saw)")
+        if getattr(model, "normalizer", None) != getattr(self.config, "normalizer", None):
+            raise ValueError(f"cannot continue from this model: it was trained with normalizer = {getattr(model, 'normalizer', None)!r}, "
+                             f"the trainer's is {getattr(self.config, 'normalizer', None)!r} (its merges would be replayed over words it never saw)")
         toks, triples = self._resumable(model)
         old_merges = [(bytes(l), bytes(r)) for l, r in model.merges]
         check_files(paths)
@@ -438,25 +499,37 @@ class BBPETrainer:
         return int(batch_bytes)
 
     def _device_words(self, ctx, chunks: Sequence[tuple[Path, int, int]], batch_bytes: int | None, dedup: bool):
-        """The chunks' pre-tokens as device words for _run: file bytes -> yabpe_pretokenize -> word offsets in HBM (equal
+        """The chunks' pre-tokens as device words for _run: file bytes -> (with a normaliser: yabpe_normalize, chunk by chunk
+        -> the normalised text and the chunk starts in it ->) yabpe_pretokenize -> word offsets in HBM (equal
         pre-tokens are pooled by the load when `dedup`).  With `batch_bytes` the chunks are read batch by batch (one batch on
         the host at a time) and each batch's pre-tokens added to ctx's word pool (yabpe_pool_add); the words are then the
         pool's, with its counts and nothing left to pool.  Pre-tokens never cross a chunk cut, so the pooled multiset is the
         same."""
         from . import _native
 
+        form = check_normalizer(getattr(self.config, "normalizer", None))
+
         def pretokenize(part):
             buf, starts = read_chunks(part)
             try:
-                return ctx.pretokenize(buf, chunk_starts=starts, special_tokens=list(self.config.special_tokens))
-            except _native.Utf8Error as e:
+                if not form:
+                    return ctx.pretokenize(buf, chunk_starts=starts, special_tokens=list(self.config.special_tokens))
+                # the normalised text stays the context's until normalize_free (the words are offsets into it)
+                dev_text, dev_starts, n_bytes = ctx.normalize(buf, part_starts=starts, form=form)
+                new_starts = ctx.d2h(dev_starts, 8 * len(starts), np.uint64)
+                return ctx.pretokenize(dev_text, n_bytes=n_bytes, chunk_starts=new_starts, special_tokens=list(self.config.special_tokens))
+            except _native.Utf8Error as e:  # (positions in buf: the normaliser validates the text it is given)
                 raise utf8_error(part, starts, e) from e
+            except _native.SegmentTooLong as e:
+                raise segment_error(part, starts, e) from e
 
         if batch_bytes is None:
             return (*pretokenize(chunks), 0, dedup)
         for first, end in group_chunks([stop - start for _p, start, stop in chunks], batch_bytes):
             ctx.pool_add_ptr(*pretokenize(chunks[first:end]))
             ctx.pretokenize_free()
+            if form:
+                ctx.normalize_free()
         dev_bytes, dev_off, dev_freq, n_unique, _n_bytes = ctx.pool_get()
         return dev_bytes, dev_off, n_unique, dev_freq, False
 
@@ -529,15 +602,16 @@ class BBPETrainer:
         self._save_pretokenizer(out)
 
     def _save_pretokenizer(self, out: Path) -> None:
-        """pretokenizer.json, only when the model was trained with a digit group or another pattern than GPT-2's (without them the
-        directory holds exactly the files it always held; a file left there by an earlier save is removed)."""
+        """pretokenizer.json, only when the model was trained with a digit group, another pattern than GPT-2's or a normaliser
+        (without them the directory holds exactly the files it always held; a file left there by an earlier save is
+        removed).  "normalizer" is written only when one is set."""
         pattern, group = pretokenizer(self.config)
-        if pattern:
+        d = {"pattern": PRETOKENIZER_NAMES[pattern], "digit_group": group} if pattern else {"digit_group": group} if group else {}
+        if getattr(self.config, "normalizer", None):
+            d["normalizer"] = self.config.normalizer
+        if d:
             with open(out / PRETOKENIZER_FILE, "w", encoding="utf-8") as f:
-                json.dump({"pattern": PRETOKENIZER_NAMES[pattern], "digit_group": group}, f)
-        elif group:
-            with open(out / PRETOKENIZER_FILE, "w", encoding="utf-8") as f:
-                json.dump({"digit_group": group}, f)
+                json.dump(d, f)
         elif (out / PRETOKENIZER_FILE).exists():
             (out / PRETOKENIZER_FILE).unlink()
 
@@ -603,7 +677,7 @@ class BBPETrainer:
                 text = raw.decode("utf-8")
             except UnicodeDecodeError as e:
                 raise ValueError(f"File {path} contains invalid UTF-8 at position {start + e.start}.") from e
-            return [t for t in pattern.findall(text) if t]
+            return [t for t in pattern.findall(normalize_text(text, getattr(self.config, "normalizer", None))) if t]
 
         check_files(files)
         out: list[str] = []
