@@ -29,7 +29,7 @@ enum {
     YABPE_E_INVALID = -1,  /* bad argument / call order */
     YABPE_E_NODEVICE = -2, /* no HIP device */
     YABPE_E_HIP = -3,      /* HIP runtime error (message has the call) */
-    YABPE_E_CAPACITY = -4, /* a documented limit was hit (token ids are u16: at most 65534 tokens) */
+    YABPE_E_CAPACITY = -4, /* a documented limit was hit (token ids: at most 65534 tokens with id_bits = 16, 2^24 - 2 with 32) */
     YABPE_E_INTERNAL = -5, /* device-side invariant violated */
     YABPE_E_COMM = -6,     /* RCCL error */
     YABPE_E_UTF8 = -7      /* yabpe_pretokenize: the text is not valid UTF-8 (position reported) */
@@ -53,6 +53,19 @@ const char *yabpe_last_error(const yabpe_ctx *ctx);
 /* Tunables by name (see DESIGN.md "Tunables"): "check_interval", "retile_pct", "apply_blocks", "event_sample",
    "table_min_log2", "skip_index", "cand_argmax", "verify" ... */
 int yabpe_set_option(yabpe_ctx *ctx, const char *name, int64_t value);
+/* Option "id_bits": the id width of the merge loop, 16 (the default) or 32; anything else: YABPE_E_INVALID.  Read by
+ * yabpe_set_vocab and fixed from then on: setting another value afterwards is YABPE_E_INVALID (the value it has is accepted).
+ * With 16 every call is what it always was: ids 0 .. 65,533, and a job that needs one more id ends in YABPE_E_CAPACITY.
+ * With 32 ids run 0 .. 2^24 - 3 (the bound of yabpe_decode_set_model's table, so a trained model can always be
+ * decoded on the device); past it yabpe_train returns YABPE_E_CAPACITY as before.  The token stream is u32 with 32-bit SEP /
+ * PAD, the pair key a u64 (left << 24 | right), the token-side capacities follow the request.  One layout, the pooled one: a
+ * load without word_freq and without YABPE_LOAD_DEDUP gives every word the weight 1 -- the same arithmetic and the same
+ * model; yabpe_load_words_resumed, "max_token_bytes", word_freq up to 2^32 - 1 and long words work as they do at 16 bits.  One
+ * form: one merge per launch over the whole live stream, the selection a launch of its own.  yabpe_n_tokens,
+ * yabpe_token_bytes, yabpe_stats (its pool_growths counts the growths of the token byte pool), yabpe_resume_stats and
+ * yabpe_verify_table serve both widths.  Refused with YABPE_E_INVALID and a message: yabpe_stream_dump and
+ * yabpe_stream_checksum (their slots are u16), and every communicator (yabpe_comm_init / yabpe_comm_init_custom on a context
+ * with id_bits = 32, or id_bits = 32 on a context that has one): training with u32 ids is single-device. */
 
 /* Base vocabulary ------------------------------------------------------------------------------------
  * Result of _init_base_vocab (trainer.py:119-134): ids 0..n_tokens-1, token i = tok_bytes[tok_off[i]..tok_off[i+1]).
@@ -177,6 +190,8 @@ typedef struct yabpe_stats_t {
     uint64_t dense_launches, dense_merges;
     /* sparse launches over a stream of more chunks than workgroups: pieces of the second round taken from the shared counter */
     uint64_t scan_skip_pieces_taken;
+    /* id_bits = 32: times the token byte pool (option "pool_bytes": its first size) had to grow */
+    uint64_t pool_growths;
 } yabpe_stats_t;
 int yabpe_stats(yabpe_ctx *ctx, yabpe_stats_t *out);
 /* Per-iteration log of the last yabpe_train call: sites merged M_i and live slots read by iteration i. */

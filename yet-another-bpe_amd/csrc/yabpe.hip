@@ -33,6 +33,7 @@
 #include "yabpe_replay_kernels.h"
 #include "yabpe_pool_kernels.h"
 #include "yabpe_norm_kernels.h"
+#include "yabpe_id32_kernels.h"
 #include "unicode_classes.inc"
 #include "unicode_subclasses.inc"
 #include "unicode_norm.inc"
@@ -254,6 +255,19 @@ struct yabpe_ctx {
     uint32_t p2p_cap = 0;                      // records a slot holds (fixed for the job: the areas are mapped once)
     hipEvent_t p2p_e0 = nullptr, p2p_e1 = nullptr;  // (statistics: every 64th exchange is timed)
     bool p2p_pending = false;                  // an event pair was recorded and not read yet
+    // u32-id merge loop (option "id_bits" = 32): its own stream, long-word buffer and pair table; tile_len,
+    // tile_wbase, wfreq, long_off / long_len / long_freq, the token table and the state are the fields above
+    int id_bits = 16;
+    bool id_bits_fixed = false;                // yabpe_set_vocab has read the option
+    uint32_t *tiles32 = nullptr, *tiles32_alt = nullptr, *long_tok32 = nullptr;
+    uint32_t tiles32_alt_cap = 0;
+    PairTable32 table32{};
+    Best32 *partials32 = nullptr;
+    uint32_t tok_cap32 = 0;                    // ids the token arrays hold
+    uint64_t pool_growths32 = 0;
+    Cand32 *cand32_state = nullptr;            // candidate list of the u32 selection (tables of "cand_min_slots" slots or more)
+    uint32_t *cand32_list = nullptr;
+    uint32_t cand32_cap = 0;
 };
 
 namespace {
@@ -902,6 +916,8 @@ int check_starts(yabpe_ctx *c, const uint64_t *starts, uint32_t n, uint64_t limi
 }
 }  // namespace
 
+#include "yabpe_id32_host.h"
+
 // =================================================================================================== C ABI
 extern "C" {
 
@@ -1058,6 +1074,10 @@ void yabpe_destroy(yabpe_ctx *c) {
     for (auto &e : c->norm_ev)
         if (e) (void)hipEventDestroy(e);
     free_corpus(c);
+    id32_free_corpus(c);
+    dfree(c->partials32);
+    dfree(c->cand32_state);
+    dfree(c->cand32_list);
     free_records(c);
     dfree(c->tt.pool); dfree(c->tt.off); dfree(c->tt.len); dfree(c->tt.rec); dfree(c->tt.vset);
     dfree(c->partials);
@@ -1087,6 +1107,13 @@ void yabpe_destroy(yabpe_ctx *c) {
 
 int yabpe_set_option(yabpe_ctx *c, const char *name, int64_t value) {
     if (!c || !name) return YABPE_E_INVALID;
+    if (strcmp(name, "id_bits") == 0) {  // the id width of the merge loop: read by yabpe_set_vocab, fixed from then on
+        if (value != 16 && value != 32) return fail(c, YABPE_E_INVALID, "option id_bits is %lld: 16 or 32", (long long)value);
+        if (c->id_bits_fixed && value != c->id_bits)
+            return fail(c, YABPE_E_INVALID, "option id_bits cannot change after yabpe_set_vocab (it is %d)", c->id_bits);
+        if (value == 32 && c->multi) return fail(c, YABPE_E_INVALID, "id_bits = 32 is single-device: this context has a communicator attached");
+        if (!c->id_bits_fixed) c->id_bits = (int)value;
+    }
     c->opt[name] = value;
     return YABPE_OK;
 }
@@ -1099,6 +1126,7 @@ int yabpe_set_vocab(yabpe_ctx *c, const uint8_t *tok_bytes, const uint32_t *tok_
     for (uint32_t b = 0; b < 256; ++b)
         if (tok_off[b + 1] - tok_off[b] != 1 || tok_bytes[tok_off[b]] != b)
             return fail(c, YABPE_E_INVALID, "token %u must be the single byte %u (trainer.py:123-125)", b, b);
+    if (c->id_bits == 32) return id32_set_vocab(c, tok_bytes, tok_off, n_tokens);
     if (n_tokens >= YB_MAX_TOKENS) return fail(c, YABPE_E_CAPACITY, "base vocabulary too large for u16 token ids");
     const uint32_t pool_cap = (uint32_t)optv(c, "pool_bytes", 64 << 20) & ~3u;
     const uint32_t vset_cap = 1u << 18;
@@ -1157,6 +1185,7 @@ int yabpe_set_vocab(yabpe_ctx *c, const uint8_t *tok_bytes, const uint32_t *tok_
     TRY(state_push(c));
     c->base_tokens = n_tokens;
     c->have_vocab = true;
+    c->id_bits_fixed = true;
     return YABPE_OK;
 }
 
@@ -1455,6 +1484,7 @@ static int load_words_impl(yabpe_ctx *c, const uint8_t *bytes, const uint64_t *w
 int yabpe_load_words(yabpe_ctx *c, const uint8_t *bytes, const uint64_t *word_off, const uint64_t *word_freq,
                      uint64_t n_words, uint32_t flags) {
     if (!c) return YABPE_E_INVALID;
+    if (c->id_bits == 32) return id32_load(c, bytes, word_off, word_freq, n_words, flags, nullptr, nullptr, nullptr, 0);
     return load_words_impl(c, bytes, word_off, word_freq, n_words, flags, nullptr);
 }
 
@@ -1464,6 +1494,11 @@ int yabpe_load_words_resumed(yabpe_ctx *c, const uint8_t *bytes, const uint64_t 
     if (!c) return YABPE_E_INVALID;
     HIPCHK(c, hipSetDevice(c->device));
     if (!c->have_vocab) return fail(c, YABPE_E_INVALID, "call yabpe_set_vocab first (with all of the model's tokens)");
+    if (c->id_bits == 32) {
+        if (n_merges && !word_freq && !(flags & YABPE_LOAD_DEDUP))
+            return fail(c, YABPE_E_INVALID, "a resumed load needs the pooled layout: pass word_freq or YABPE_LOAD_DEDUP");
+        return id32_load(c, bytes, word_off, word_freq, n_words, flags, merge_left, merge_right, merge_merged, n_merges);
+    }
     if (n_merges == 0) return load_words_impl(c, bytes, word_off, word_freq, n_words, flags, nullptr);
     if (!word_freq && !(flags & YABPE_LOAD_DEDUP))
         return fail(c, YABPE_E_INVALID, "a resumed load needs the pooled layout: pass word_freq or YABPE_LOAD_DEDUP");
@@ -1724,6 +1759,7 @@ int yabpe_train(yabpe_ctx *c, uint32_t num_merges, uint64_t min_frequency, uint3
     HIPCHK(c, hipSetDevice(c->device));
     if (!c->have_words) return fail(c, YABPE_E_INVALID, "call yabpe_load_words first");
     if (out_n_merges) *out_n_merges = 0;
+    if (c->id_bits == 32) return id32_train(c, num_merges, min_frequency, out_left, out_right, out_merged, out_count, out_n_merges);
     TRY(state_pull(c));
     DevState *h = c->st_host;
     // The u16 id space bounds the vocabulary at YB_MAX_TOKENS; the reference has no such bound (trainer.py:238, 298-300).  A
@@ -2216,6 +2252,7 @@ int yabpe_stats(yabpe_ctx *c, yabpe_stats_t *out) {
     c->stats.scan_skip_launches = c->scan_skip_launches;
     c->stats.scan_skip_tiles_read = 0;
     c->stats.scan_skip_pieces_taken = 0;
+    c->stats.pool_growths = c->pool_growths32;
     if (c->blk_read) {
         std::vector<unsigned long long> br(2 * MAX_LISTS);
         HIPCHK(c, hipMemcpy(br.data(), c->blk_read, 2 * MAX_LISTS * 8, hipMemcpyDeviceToHost));
@@ -2303,6 +2340,7 @@ int yabpe_verify_table(yabpe_ctx *c, uint64_t *out_mismatches) {
     if (!c || !out_mismatches) return YABPE_E_INVALID;
     HIPCHK(c, hipSetDevice(c->device));
     if (!c->have_words) return fail(c, YABPE_E_INVALID, "no corpus loaded");
+    if (c->id_bits == 32) return id32_verify(c, out_mismatches);
     PairTable scratch{};
     HIPCHK(c, hipMemsetAsync(&c->scratch64[4], 0, 16, c->stream));  // [4] entries, [5] mismatches
     TRY(table_alloc(c, scratch, c->table_cap, &c->scratch64[4]));
@@ -2340,6 +2378,7 @@ int yabpe_stream_checksum(yabpe_ctx *c, uint64_t *out_sum, uint64_t *out_words, 
     if (!c) return YABPE_E_INVALID;
     HIPCHK(c, hipSetDevice(c->device));
     if (!c->have_words) return fail(c, YABPE_E_INVALID, "no corpus loaded");
+    if (c->id_bits == 32) return fail(c, YABPE_E_INVALID, "yabpe_stream_checksum reads the u16 stream: not available with id_bits = 32");
     HIPCHK(c, hipMemsetAsync(&c->scratch64[4], 0, 24, c->stream));
     if (c->n_tiles) {
         ChecksumParams P{c->tiles, c->tile_len, c->tile_wbase, c->wfreq, c->n_tiles, c->tt,
@@ -2365,6 +2404,7 @@ int yabpe_stream_dump(yabpe_ctx *c, uint32_t *out_n_tiles, uint32_t *out_flags, 
                       uint64_t *sig) {
     if (!c) return YABPE_E_INVALID;
     HIPCHK(c, hipSetDevice(c->device));
+    if (c->id_bits == 32) return fail(c, YABPE_E_INVALID, "yabpe_stream_dump hands out u16 slots: not available with id_bits = 32");
     if (!c->have_words) return fail(c, YABPE_E_INVALID, "no corpus loaded");
     const bool has_sig = c->sig_valid && c->sig != nullptr && c->sig_stride >= c->n_tiles;
     if (out_n_tiles) *out_n_tiles = c->n_tiles;
@@ -3803,6 +3843,7 @@ int yabpe_comm_unique_id(uint8_t out_id[128]) {
 static int comm_attach(yabpe_ctx *c, int rank, int n_ranks) {
     if (c->have_words) return fail(c, YABPE_E_INVALID, "attach the communicator before yabpe_load_words");
     if (c->comm || c->ag_fn) return fail(c, YABPE_E_INVALID, "communicator already attached");
+    if (c->id_bits == 32) return fail(c, YABPE_E_INVALID, "id_bits = 32 is single-device: no communicator can be attached");
     c->rank = rank;
     c->n_ranks = n_ranks;
     return 0;

@@ -1,0 +1,668 @@
+// yabpe_id32_host.h -- host driver of the u32-id merge loop (option id_bits = 32).  Included by yabpe.hip
+// after its helpers; the kernels are in yabpe_id32_kernels.h.  The entry points of the C ABI branch here when the context's
+// id width is 32: set_vocab, the two loads, train, verify_table.  Everything else about a context (options, token bytes,
+// stats, the pre-tokeniser, the word pool, encode / decode) is shared.
+#pragma once
+
+namespace {
+
+constexpr uint32_t ID32_POOL_MAX = 0xF0000000u;  // token byte pool: offsets are u32
+
+void id32_table_free(PairTable32 &t) {
+    dfree(t.keys);
+    dfree(t.cnt);
+    t.keys = nullptr;
+    t.cnt = nullptr;
+}
+
+void id32_free_corpus(yabpe_ctx *c) {
+    dfree(c->tiles32); dfree(c->tiles32_alt); dfree(c->long_tok32);
+    c->tiles32 = c->tiles32_alt = c->long_tok32 = nullptr;
+    c->tiles32_alt_cap = 0;
+    id32_table_free(c->table32);
+}
+
+int id32_table_alloc(yabpe_ctx *c, PairTable32 &t, uint64_t cap, unsigned long long *entries_ctr) {
+    uint64_t p2 = 1024;
+    while (p2 < cap) p2 <<= 1;
+    if (p2 > (1ull << 31)) return fail(c, YABPE_E_CAPACITY, "pair table past 2^31 slots");
+    TRY(dmalloc(c, &t.keys, p2));
+    TRY(dmalloc(c, &t.cnt, p2));
+    t.mask = (uint32_t)(p2 - 1);
+    t.max_probe = (uint32_t)std::min<uint64_t>(p2, 2048);
+    t.entries = entries_ctr;
+    t.cs = nullptr;  // (the candidate list belongs to the main table of a training call: id32_cand_attach)
+    t.cand_list = nullptr;
+    t.cand_cap = 0;
+    HIPCHK(c, hipMemsetAsync(t.keys, 0xFF, p2 * 8, c->stream));
+    HIPCHK(c, hipMemsetAsync(t.cnt, 0, p2 * 8, c->stream));
+    return 0;
+}
+
+Stream32 id32_stream(yabpe_ctx *c) { return Stream32{c->tiles32, c->tile_len, c->tile_wbase, c->wfreq, c->n_tiles}; }
+Long32 id32_long(yabpe_ctx *c) { return Long32{c->long_tok32, c->long_off, c->long_len, c->long_freq, c->n_long}; }
+uint32_t id32_grid(yabpe_ctx *c) {  // workgroups of a pass over the tile stream: all resident at once
+    return (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(cdiv64(c->n_tiles, WPB), (uint64_t)std::max(1, c->n_cu) * 4));
+}
+
+int id32_count(yabpe_ctx *c, PairTable32 t) {
+    if (c->n_tiles) {
+        hipLaunchKernelGGL(k32_count, dim3(id32_grid(c)), dim3(BLOCK), 0, c->stream, Count32Params{id32_stream(c), t, c->st});
+        HIPCHK(c, hipGetLastError());
+    }
+    if (c->n_long) {
+        hipLaunchKernelGGL(k32_count_long, dim3(c->n_long), dim3(BLOCK), 0, c->stream, CountLong32Params{id32_long(c), t, c->st});
+        HIPCHK(c, hipGetLastError());
+    }
+    return 0;
+}
+
+// The candidate list for the main table as it stands now: kept when the table has at least "cand_min_slots" slots (smaller
+// tables are scanned whole by every selection), emptied and marked invalid -- the next selection scans the table and lists.
+int id32_cand_attach(yabpe_ctx *c) {
+    PairTable32 &t = c->table32;
+    t.cs = nullptr;
+    t.cand_list = nullptr;
+    t.cand_cap = 0;
+    if (!optv(c, "cand_argmax", 1) || (uint64_t)t.mask + 1 < (uint64_t)std::max<int64_t>(0, optv(c, "cand_min_slots", 1 << 18))) return 0;
+    const uint32_t cap = (uint32_t)std::min<int64_t>(1 << 24, std::max<int64_t>(16, optv(c, "cand_cap", 1 << 17)));
+    if (!c->cand32_state) {
+        TRY(dmalloc(c, &c->cand32_state, 1));
+        HIPCHK(c, hipMemsetAsync(c->cand32_state, 0, sizeof(Cand32), c->stream));
+        const long long T0 = 1ll << 62;  // (above every count: the first scan finds the best count and sets T from it)
+        HIPCHK(c, hipMemcpyAsync(&c->cand32_state->T, &T0, 8, hipMemcpyHostToDevice, c->stream));
+    }
+    if (c->cand32_cap != cap) {
+        dfree(c->cand32_list);
+        c->cand32_list = nullptr;
+        TRY(dmalloc(c, &c->cand32_list, cap));
+        c->cand32_cap = cap;
+    }
+    HIPCHK(c, hipMemsetAsync(&c->cand32_state->n, 0, 16, c->stream));  // n, overflow, valid, pad
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    t.cs = c->cand32_state;
+    t.cand_list = c->cand32_list;
+    t.cand_cap = cap;
+    return 0;
+}
+
+// a fresh table of at least min_cap slots counted from the stream; grows until no probe sequence ran out and the load is <= 1/2
+int id32_table_rebuild(yabpe_ctx *c, uint64_t min_cap) {
+    uint64_t cap = std::max<uint64_t>(min_cap, 1024);
+    for (int attempt = 0; attempt < 24; ++attempt) {
+        id32_table_free(c->table32);
+        HIPCHK(c, hipMemsetAsync(&c->st->table_entries, 0, 8, c->stream));
+        HIPCHK(c, hipMemsetAsync(&c->st->halt_req, 0, 4, c->stream));
+        TRY(id32_table_alloc(c, c->table32, cap, &c->st->table_entries));
+        TRY(id32_count(c, c->table32));
+        TRY(state_pull(c));
+        const uint64_t have = (uint64_t)c->table32.mask + 1;
+        if (c->st_host->halt_req == HALT_NONE && c->st_host->table_entries * 2 <= have) {
+            c->table_cap = have;
+            c->stats.table_rebuilds++;
+            return 0;
+        }
+        cap = have * 2;
+    }
+    return fail(c, YABPE_E_CAPACITY, "pair table cannot hold the corpus' pairs");
+}
+
+// the same pairs in a table of at least new_cap slots (counts of zero are dropped); a recount if a probe sequence runs out
+int id32_table_grow(yabpe_ctx *c, uint64_t new_cap) {
+    PairTable32 nt{};
+    HIPCHK(c, hipMemsetAsync(&c->st->table_entries, 0, 8, c->stream));
+    TRY(id32_table_alloc(c, nt, new_cap, &c->st->table_entries));
+    const uint64_t old_cap = (uint64_t)c->table32.mask + 1;
+    hipLaunchKernelGGL(k32_rehash, dim3((uint32_t)std::min<uint64_t>(1024, cdiv64(old_cap, BLOCK))), dim3(BLOCK), 0, c->stream,
+                       Rehash32Params{c->table32, nt, c->st});
+    HIPCHK(c, hipGetLastError());
+    TRY(state_pull(c));
+    id32_table_free(c->table32);
+    c->table32 = nt;
+    c->table_cap = (uint64_t)nt.mask + 1;
+    c->stats.table_rebuilds++;
+    if (c->st_host->halt_req != HALT_NONE) return id32_table_rebuild(c, c->table_cap * 2);
+    return 0;
+}
+
+// ---------------------------------------------------------------------------------------------- vocab
+int id32_upload_vset(yabpe_ctx *c, const std::vector<TokRec> &rec, uint32_t n_tokens, uint32_t vset_cap) {
+    std::vector<unsigned long long> vset(vset_cap, VSET_EMPTY);
+    const uint32_t mask = vset_cap - 1;
+    for (uint32_t i = 0; i < n_tokens; ++i) {
+        uint32_t s = yb_vset_home(rec[i].hash, rec[i].len) & mask;
+        while (vset[s] != VSET_EMPTY) s = (s + 1) & mask;
+        vset[s] = yb_vset_entry(i, rec[i].hash);
+    }
+    dfree(c->tt.vset);
+    c->tt.vset = nullptr;
+    TRY(dmalloc(c, &c->tt.vset, vset_cap));
+    HIPCHK(c, hipMemcpy(c->tt.vset, vset.data(), (size_t)vset_cap * 8, hipMemcpyHostToDevice));
+    c->tt.vset_mask = mask;
+    return 0;
+}
+
+int id32_set_vocab(yabpe_ctx *c, const uint8_t *tok_bytes, const uint32_t *tok_off, uint32_t n_tokens) {
+    if (n_tokens >= YbW32::MAX_TOKENS) return fail(c, YABPE_E_CAPACITY, "base vocabulary too large: ids run 0 .. 2^24 - 3");
+    std::vector<uint32_t> off(n_tokens), len(n_tokens), order(n_tokens);
+    std::vector<uint8_t> pool;
+    for (uint32_t i = 0; i < n_tokens; ++i) {
+        len[i] = tok_off[i + 1] - tok_off[i];
+        off[i] = (uint32_t)pool.size();
+        pool.insert(pool.end(), tok_bytes + tok_off[i], tok_bytes + tok_off[i + 1]);
+        pool.resize((pool.size() + 3) & ~(size_t)3, 0);
+        order[i] = i;
+    }
+    // the token-side capacities follow the request: the pool starts at the option and grows, the records grow with yabpe_train
+    uint64_t pool_cap = (uint64_t)optv(c, "pool_bytes", 64 << 20) & ~3ull;
+    while (pool_cap < (uint64_t)pool.size() + 64) pool_cap = pool_cap * 2 + 64;
+    if (pool_cap > ID32_POOL_MAX) return fail(c, YABPE_E_CAPACITY, "base vocabulary bytes exceed the token pool");
+    const uint32_t tok_cap = (uint32_t)std::min<uint64_t>(YbW32::MAX_TOKENS, (uint64_t)n_tokens + 4096);
+    uint32_t vset_cap = 1u << 14;
+    while (vset_cap < 2 * tok_cap) vset_cap <<= 1;
+    auto cmp = [&](uint32_t x, uint32_t y) {
+        uint32_t n = std::min(len[x], len[y]);
+        int d = memcmp(pool.data() + off[x], pool.data() + off[y], n);
+        if (d) return d < 0;
+        return len[x] < len[y];
+    };
+    std::sort(order.begin(), order.end(), cmp);
+    for (uint32_t r = 1; r < n_tokens; ++r)
+        if (!cmp(order[r - 1], order[r])) return fail(c, YABPE_E_INVALID, "duplicate token bytes in the base vocabulary (trainer.py:130)");
+    std::vector<TokRec> rec(n_tokens);
+    for (uint32_t i = 0; i < n_tokens; ++i) {
+        rec[i].rank = 0;  // (the u32 selection compares bytes: no lexrank to keep)
+        rec[i].len = len[i];
+        rec[i].hash = yb_hash_bytes(pool.data() + off[i], len[i]);
+        rec[i].pre8 = yb_pre8(pool.data() + off[i], len[i]);
+        rec[i].pad = 0;
+    }
+    dfree(c->tt.pool); dfree(c->tt.off); dfree(c->tt.len); dfree(c->tt.rec);
+    c->tt.pool = nullptr; c->tt.off = c->tt.len = nullptr; c->tt.rec = nullptr;
+    TRY(dmalloc(c, &c->tt.pool, pool_cap));
+    TRY(dmalloc(c, &c->tt.off, tok_cap));
+    TRY(dmalloc(c, &c->tt.len, tok_cap));
+    TRY(dmalloc(c, &c->tt.rec, tok_cap));
+    c->tt.pool_cap = (uint32_t)pool_cap;
+    c->tok_cap32 = tok_cap;
+    TRY(id32_upload_vset(c, rec, n_tokens, vset_cap));
+    HIPCHK(c, hipMemset(c->tt.pool, 0, pool_cap));
+    HIPCHK(c, hipMemcpy(c->tt.pool, pool.data(), pool.size(), hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(c->tt.off, off.data(), (size_t)n_tokens * 4, hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(c->tt.len, len.data(), (size_t)n_tokens * 4, hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(c->tt.rec, rec.data(), (size_t)n_tokens * sizeof(TokRec), hipMemcpyHostToDevice));
+    TRY(state_pull(c));
+    DevState *h = c->st_host;
+    memset(h, 0, sizeof(DevState));
+    h->n_tokens = n_tokens;
+    h->pool_used = (uint32_t)pool.size();
+    TRY(state_push(c));
+    c->base_tokens = n_tokens;
+    c->have_vocab = true;
+    c->id_bits_fixed = true;
+    c->pool_growths32 = 0;
+    return YABPE_OK;
+}
+
+// room for `need` token ids: records, offsets, lengths and the byte-string set (at most half full)
+int id32_ensure_tokens(yabpe_ctx *c, uint64_t need) {
+    need = std::min<uint64_t>(need, YbW32::MAX_TOKENS);
+    if (need <= c->tok_cap32) return 0;
+    const uint32_t ncap = (uint32_t)std::min<uint64_t>(YbW32::MAX_TOKENS, std::max<uint64_t>(need, (uint64_t)c->tok_cap32 * 2));
+    TRY(state_pull(c));
+    const uint32_t n = c->st_host->n_tokens;
+    uint32_t *noff = nullptr, *nlen = nullptr;
+    TokRec *nrec = nullptr;
+    TRY(dmalloc(c, &noff, ncap)); TRY(dmalloc(c, &nlen, ncap)); TRY(dmalloc(c, &nrec, ncap));
+    HIPCHK(c, hipMemcpy(noff, c->tt.off, (size_t)n * 4, hipMemcpyDeviceToDevice));
+    HIPCHK(c, hipMemcpy(nlen, c->tt.len, (size_t)n * 4, hipMemcpyDeviceToDevice));
+    HIPCHK(c, hipMemcpy(nrec, c->tt.rec, (size_t)n * sizeof(TokRec), hipMemcpyDeviceToDevice));
+    dfree(c->tt.off); dfree(c->tt.len); dfree(c->tt.rec);
+    c->tt.off = noff; c->tt.len = nlen; c->tt.rec = nrec;
+    c->tok_cap32 = ncap;
+    uint32_t vset_cap = c->tt.vset_mask + 1;
+    if (vset_cap < 2 * (uint64_t)ncap) {
+        while (vset_cap < 2 * (uint64_t)ncap) vset_cap <<= 1;
+        std::vector<TokRec> rec(n);
+        HIPCHK(c, hipMemcpy(rec.data(), c->tt.rec, (size_t)n * sizeof(TokRec), hipMemcpyDeviceToHost));
+        TRY(id32_upload_vset(c, rec, n, vset_cap));
+    }
+    c->st_host->tok_len = c->tt.len;  // (the pair table's insert reads the lengths through the state)
+    TRY(state_push(c));
+    return 0;
+}
+
+int id32_grow_pool(yabpe_ctx *c) {
+    const uint64_t ncap = std::min<uint64_t>(ID32_POOL_MAX, (uint64_t)c->tt.pool_cap * 2 + 1024) & ~3ull;
+    if (ncap <= c->tt.pool_cap) return fail(c, YABPE_E_CAPACITY, "token byte pool exhausted (4 GiB of token bytes)");
+    uint8_t *np = nullptr;
+    TRY(dmalloc(c, &np, ncap));
+    HIPCHK(c, hipMemset(np, 0, ncap));
+    HIPCHK(c, hipMemcpy(np, c->tt.pool, c->tt.pool_cap, hipMemcpyDeviceToDevice));
+    dfree(c->tt.pool);
+    c->tt.pool = np;
+    c->tt.pool_cap = (uint32_t)ncap;
+    c->pool_growths32++;
+    return 0;
+}
+
+// ---------------------------------------------------------------------------------------------- corpus
+// merges != NULL: a resumed load (the words are rewritten by the model's merges before they are tiled)
+int id32_load(yabpe_ctx *c, const uint8_t *bytes, const uint64_t *word_off, const uint64_t *word_freq, uint64_t n_words, uint32_t flags,
+              const uint32_t *ml, const uint32_t *mr, const uint32_t *mm, uint32_t n_merges) {
+    HIPCHK(c, hipSetDevice(c->device));
+    if (!c->have_vocab) return fail(c, YABPE_E_INVALID, "call yabpe_set_vocab first");
+    if (!word_off) return fail(c, YABPE_E_INVALID, "word_off is NULL");
+    if (c->multi) return fail(c, YABPE_E_INVALID, "id_bits = 32 is single-device: this context has a communicator attached");
+    if (n_words >= 0xFFFFFFFFull) return fail(c, YABPE_E_CAPACITY, "more than 2^32-2 words per context");
+    const int64_t max_token_bytes = optv(c, "max_token_bytes", 0);
+    if (!yb_limit_valid(max_token_bytes))
+        return fail(c, YABPE_E_INVALID, "max_token_bytes is %lld: 0 (no limit) or a length of at least %u bytes", (long long)max_token_bytes, YB_LIMIT_MIN);
+    TRY(state_pull(c));
+    const uint32_t n_tokens = c->st_host->n_tokens;
+    Rp32Table rp{nullptr, nullptr, 0, nullptr, 0};
+    Scratch S(c->device, c->rank);
+    if (n_merges) {
+        if (!ml || !mr || !mm) return fail(c, YABPE_E_INVALID, "merge triples are NULL");
+        std::vector<uint32_t> len(n_tokens);
+        HIPCHK(c, hipMemcpy(len.data(), c->tt.len, (size_t)n_tokens * 4, hipMemcpyDeviceToHost));
+        std::vector<Rp32Entry> ent((size_t)n_merges + 1);
+        for (uint32_t i = 0; i < n_merges; ++i) {
+            const uint32_t l = ml[i], r = mr[i], m = mm[i];
+            if (l >= n_tokens || r >= n_tokens || m >= n_tokens)
+                return fail(c, YABPE_E_INVALID, "merge %u names token id %u, the vocabulary has %u", i, std::max(l, std::max(r, m)), n_tokens);
+            if (len[m] != len[l] + len[r])
+                return fail(c, YABPE_E_INVALID, "merge %u: token %u has %u bytes, its operands %u + %u", i, m, len[m], len[l], len[r]);
+            ent[i] = Rp32Entry{YbW32::key(l, r), i, m};
+        }
+        std::sort(ent.begin(), ent.begin() + n_merges, [](const Rp32Entry &x, const Rp32Entry &y) { return x.key != y.key ? x.key < y.key : x.rank < y.rank; });
+        ent[n_merges] = Rp32Entry{EMPTY32, 0xFFFFFFFFu, 0xFFFFFFFFu};
+        size_t cap = 16;
+        while (cap < 2 * (size_t)n_merges) cap <<= 1;
+        std::vector<unsigned long long> idx_key(cap, EMPTY32);
+        std::vector<uint32_t> idx_first(cap, 0u);
+        auto h48 = [](unsigned long long k) { k ^= k >> 29; k *= 0xBF58476D1CE4E5B9ull; k ^= k >> 32; return (uint32_t)k; };
+        for (uint32_t i = 0; i < n_merges; ++i) {
+            if (i && ent[i - 1].key == ent[i].key) continue;
+            uint32_t s = h48(ent[i].key) & (uint32_t)(cap - 1);
+            while (idx_key[s] != EMPTY32) s = (s + 1) & (uint32_t)(cap - 1);
+            idx_key[s] = ent[i].key;
+            idx_first[s] = i;
+        }
+        unsigned long long *d_key = nullptr;
+        uint32_t *d_first = nullptr;
+        Rp32Entry *d_ent = nullptr;
+        HIPCHK(c, S.get(&d_key, cap)); HIPCHK(c, S.get(&d_first, cap)); HIPCHK(c, S.get(&d_ent, ent.size()));
+        HIPCHK(c, hipMemcpy(d_key, idx_key.data(), cap * 8, hipMemcpyHostToDevice));
+        HIPCHK(c, hipMemcpy(d_first, idx_first.data(), cap * 4, hipMemcpyHostToDevice));
+        HIPCHK(c, hipMemcpy(d_ent, ent.data(), ent.size() * sizeof(Rp32Entry), hipMemcpyHostToDevice));
+        rp = Rp32Table{d_key, d_first, (uint32_t)(cap - 1), d_ent, n_merges};
+    }
+    free_corpus(c);
+    id32_free_corpus(c);
+    struct Events {
+        hipEvent_t ev0 = nullptr, ev1 = nullptr, ev_seg = nullptr;
+        ~Events() {
+            if (ev0) (void)hipEventDestroy(ev0);
+            if (ev1) (void)hipEventDestroy(ev1);
+            if (ev_seg) (void)hipEventDestroy(ev_seg);
+        }
+    } evs;
+    HIPCHK(c, hipEventCreate(&evs.ev0)); HIPCHK(c, hipEventCreate(&evs.ev1)); HIPCHK(c, hipEventCreate(&evs.ev_seg));
+
+    // ---- inputs on the device, equal words pooled (trainer.py:221-225)
+    const unsigned long long *d_off = nullptr, *d_freq = nullptr;
+    const uint8_t *d_bytes = bytes;
+    uint64_t total_bytes = 0, off_base = 0;
+    if (is_device_ptr(word_off)) {
+        HIPCHK(c, hipMemcpy(&total_bytes, word_off + n_words, 8, hipMemcpyDeviceToHost));
+        HIPCHK(c, hipMemcpy(&off_base, word_off, 8, hipMemcpyDeviceToHost));
+        total_bytes -= off_base;
+    } else {
+        off_base = word_off[0];
+        total_bytes = word_off[n_words] - off_base;
+    }
+    TRY(to_device(c, S, (const unsigned long long *)word_off, (n_words + 1) * 8, 1, &d_off));
+    if (total_bytes && !bytes) return fail(c, YABPE_E_INVALID, "bytes is NULL");
+    if (total_bytes) {
+        TRY(to_device(c, S, bytes + off_base, total_bytes, 1, &d_bytes));
+        d_bytes -= off_base;
+    }
+    if (word_freq) TRY(to_device(c, S, (const unsigned long long *)word_freq, n_words * 8, 1, &d_freq));
+    HIPCHK(c, hipEventRecord(evs.ev0, c->stream));
+    c->n_words_input = n_words;
+    if ((flags & YABPE_LOAD_DEDUP) && n_words > 0) {
+        DedupOut dd{};
+        int r = dedup_words(c->stream, d_bytes, d_off, d_freq, n_words, &dd);
+        if (r != 0) return fail(c, YABPE_E_HIP, "device dedup failed (%d): %s", r, hipGetErrorString(hipGetLastError()));
+        // (the staged inputs stay in S until the load returns; the rp table is among them)
+        S.adopt(dd.bytes); S.adopt(dd.off); S.adopt(dd.freq);
+        d_bytes = dd.bytes; d_off = dd.off; d_freq = dd.freq;
+        n_words = dd.n_unique;
+        total_bytes = dd.total_bytes;
+        off_base = 0;
+    }
+    c->weighted = true;  // one layout: a word without a count weighs 1
+    c->n_words = n_words;
+
+    // ---- words as u32 ids (replayed), their places
+    uint32_t *d_wtok = nullptr, *d_wcnt = nullptr, *d_slots = nullptr, *d_short = nullptr, *d_lng = nullptr, *d_llen = nullptr;
+    unsigned long long *d_pos = nullptr, *d_srank = nullptr, *d_lrank = nullptr, *d_lpos = nullptr;
+    HIPCHK(c, S.get(&d_wtok, total_bytes + 1)); HIPCHK(c, S.get(&d_wcnt, n_words + 1));
+    HIPCHK(c, S.get(&d_slots, n_words + 1)); HIPCHK(c, S.get(&d_short, n_words + 1));
+    HIPCHK(c, S.get(&d_lng, n_words + 1)); HIPCHK(c, S.get(&d_llen, n_words + 1));
+    HIPCHK(c, S.get(&d_pos, n_words + 1)); HIPCHK(c, S.get(&d_srank, n_words + 1));
+    HIPCHK(c, S.get(&d_lrank, n_words + 1)); HIPCHK(c, S.get(&d_lpos, n_words + 1));
+    HIPCHK(c, hipMemsetAsync(&c->scratch64[1], 0, 16, c->stream));  // [1] frequency overflow, [2] word too long
+    unsigned long long tot[4] = {0, 0, 0, 0};  // slots, short words, long words, long tokens
+    if (n_words) {
+        const uint32_t wg = cdiv64(n_words, BLOCK);
+        hipLaunchKernelGGL(k32_words, dim3(wg), dim3(BLOCK), 0, c->stream,
+                           Words32Params{d_bytes, d_off, (unsigned long long)off_base, (unsigned long long)n_words, d_wtok, d_wcnt, rp, (uint32_t *)&c->scratch64[2]});
+        HIPCHK(c, hipGetLastError());
+        hipLaunchKernelGGL(k32_word_slots, dim3(wg), dim3(BLOCK), 0, c->stream, Slots32Params{d_wcnt, (unsigned long long)n_words, d_slots, d_short, d_lng, d_llen});
+        HIPCHK(c, hipGetLastError());
+        const uint32_t *in[4] = {d_slots, d_short, d_lng, d_llen};
+        unsigned long long *out[4] = {d_pos, d_srank, d_lrank, d_lpos};
+        for (int k = 0; k < 4; ++k) {
+            if (exclusive_scan<uint32_t>(c->stream, in[k], n_words, out[k], (unsigned long long)n_words + 1) != 0)
+                return fail(c, YABPE_E_HIP, "scan of the word places failed: %s", hipGetErrorString(hipGetLastError()));
+            HIPCHK(c, hipMemcpyAsync(&tot[k], out[k] + n_words, 8, hipMemcpyDeviceToHost, c->stream));
+        }
+        unsigned long long flagsd[2] = {0, 0};
+        HIPCHK(c, hipMemcpyAsync(flagsd, &c->scratch64[1], 16, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        if (flagsd[1] & 0xFFFFFFFFull) return fail(c, YABPE_E_CAPACITY, "a single word longer than 2^32-1 bytes");
+    }
+    HIPCHK(c, hipEventRecord(evs.ev_seg, c->stream));
+    const uint64_t n_tiles64 = (tot[0] + SPAN32 - 1) / SPAN32;
+    if (n_tiles64 >= 0xFFFFFFF0ull || tot[1] >= 0xFFFFFFFFull) return fail(c, YABPE_E_CAPACITY, "corpus too large for one context");
+    c->n_tiles = (uint32_t)n_tiles64;
+    c->n_long = (uint32_t)tot[2];
+    c->long_tokens = tot[3];
+    c->tiles_cap = c->n_tiles;
+    TRY(dmalloc(c, &c->tiles32, (uint64_t)c->n_tiles * CAP32 + 1));
+    TRY(dmalloc(c, &c->tile_len, (uint64_t)c->n_tiles + 1));
+    TRY(dmalloc(c, &c->tile_wbase, (uint64_t)c->n_tiles + 1));
+    TRY(dmalloc(c, &c->wfreq, tot[1] + 1));
+    TRY(dmalloc(c, &c->long_tok32, tot[3] + 1));
+    TRY(dmalloc(c, &c->long_off, (uint64_t)c->n_long + 1));
+    TRY(dmalloc(c, &c->long_len, (uint64_t)c->n_long + 1));
+    TRY(dmalloc(c, &c->long_freq, (uint64_t)c->n_long + 1));
+    if (n_words) {
+        if (c->n_tiles) {
+            hipLaunchKernelGGL(k32_build_tiles, dim3(c->n_tiles), dim3(BLOCK), 0, c->stream,
+                               Tiles32Params{d_wtok, d_wcnt, d_off, (unsigned long long)off_base, (unsigned long long)n_words, d_pos, d_srank, c->tiles32, c->tile_len, c->tile_wbase, c->n_tiles});
+            HIPCHK(c, hipGetLastError());
+        }
+        hipLaunchKernelGGL(k32_place_words, dim3(cdiv64(n_words, BLOCK)), dim3(BLOCK), 0, c->stream,
+                           Place32Params{d_wtok, d_wcnt, d_off, (unsigned long long)off_base, (unsigned long long)n_words, d_freq, d_short, d_lng, d_srank, d_lrank, d_lpos,
+                                         c->wfreq, c->long_tok32, c->long_off, c->long_len, c->long_freq, (uint32_t *)&c->scratch64[1]});
+        HIPCHK(c, hipGetLastError());
+        unsigned long long ov = 0;
+        HIPCHK(c, hipMemcpyAsync(&ov, &c->scratch64[1], 8, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        if (ov & 0xFFFFFFFFull) return fail(c, YABPE_E_CAPACITY, "a word frequency exceeds 2^32-1");
+    }
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    S.release();
+    const uint64_t total_tokens = tot[0] - tot[1] + tot[3];
+    c->tokens_initial = total_tokens;
+
+    // ---- state + initial pair count (trainer.py:227-235)
+    TRY(state_pull(c));
+    DevState *h = c->st_host;
+    h->iter = 0; h->done = 0; h->halt = 0; h->halt_req = 0; h->sites = 0;
+    h->tokens_now = total_tokens;
+    h->table_entries = 0;
+    h->live_slots = tot[0];
+    h->tok_len = c->tt.len;
+    h->max_token_bytes = (uint32_t)max_token_bytes;
+    TRY(state_push(c));
+    TRY(id32_table_rebuild(c, (uint64_t)1 << std::min<int64_t>(30, std::max<int64_t>(10, optv(c, "table_min_log2", 16)))));
+    c->stats = yabpe_stats_t{};
+    HIPCHK(c, hipEventRecord(evs.ev1, c->stream));
+    HIPCHK(c, hipEventSynchronize(evs.ev1));
+    float ms = 0, sms = 0;
+    HIPCHK(c, hipEventElapsedTime(&ms, evs.ev0, evs.ev1));
+    HIPCHK(c, hipEventElapsedTime(&sms, evs.ev0, evs.ev_seg));
+    c->resume_stats = yabpe_resume_stats_t{};
+    c->resume_stats.n_unique = n_words;
+    c->resume_stats.n_long = c->n_long;
+    c->resume_stats.tokens = total_tokens;
+    c->resume_stats.segment_ms = sms;
+    c->resume_stats.build_ms = ms - sms;
+    c->stats.load_ms = ms;
+    c->cand_rebuilds = c->cand_rescans = 0;
+    c->fused_launches = 0;
+    c->exchanges = 0;
+    c->scan_skip_launches = 0;
+    c->have_words = true;
+    return YABPE_OK;
+}
+
+// ---------------------------------------------------------------------------------------------- repack
+// The live slots packed again word by word into ceil(live / SPAN32) tiles (k32_repack: plan, then move).
+int id32_repack(yabpe_ctx *c) {
+    const uint32_t n = c->n_tiles;
+    Scratch S(c->device, c->rank);
+    unsigned long long *d_base = nullptr, *d_first = nullptr;
+    HIPCHK(c, S.get(&d_base, (uint64_t)n + 1));
+    if (exclusive_scan<uint32_t>(c->stream, c->tile_len, n, d_base, (unsigned long long)n + 1) != 0)
+        return fail(c, YABPE_E_HIP, "scan of the tile lengths failed: %s", hipGetErrorString(hipGetLastError()));
+    unsigned long long total = 0;
+    HIPCHK(c, hipMemcpyAsync(&total, d_base + n, 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    const uint32_t n_new = (uint32_t)((total + SPAN32 - 1) / SPAN32);
+    if (n_new >= n || n_new == 0) return 0;
+    uint32_t *nlen = nullptr, *nwb = nullptr;
+    if (c->tiles32_alt_cap < n_new) {
+        dfree(c->tiles32_alt);
+        c->tiles32_alt = nullptr;
+        c->tiles32_alt_cap = 0;
+        TRY(dmalloc(c, &c->tiles32_alt, (uint64_t)n_new * CAP32 + 1));
+        c->tiles32_alt_cap = n_new;
+    }
+    HIPCHK(c, S.get(&d_first, (uint64_t)n_new + 1));
+    TRY(dmalloc(c, &nlen, (uint64_t)n_new + 1));
+    TRY(dmalloc(c, &nwb, (uint64_t)n_new + 1));
+    HIPCHK(c, hipMemsetAsync(d_first, 0xFF, ((size_t)n_new + 1) * 8, c->stream));
+    HIPCHK(c, hipMemsetAsync(nwb, 0xFF, ((size_t)n_new + 1) * 4, c->stream));
+    HIPCHK(c, hipMemsetAsync(nlen, 0, ((size_t)n_new + 1) * 4, c->stream));
+    const Repack32Params P{id32_stream(c), d_base, d_first, c->tiles32_alt, nlen, nwb, n_new};
+    hipLaunchKernelGGL(k32_repack<false>, dim3(id32_grid(c)), dim3(BLOCK), 0, c->stream, P);
+    hipLaunchKernelGGL(k32_repack<true>, dim3(id32_grid(c)), dim3(BLOCK), 0, c->stream, P);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    std::swap(c->tiles32, c->tiles32_alt);
+    std::swap(c->tiles_cap, c->tiles32_alt_cap);
+    dfree(c->tile_len); dfree(c->tile_wbase);
+    c->tile_len = nlen;
+    c->tile_wbase = nwb;
+    c->n_tiles = n_new;
+    c->stats.retiles++;
+    return 0;
+}
+
+int id32_refresh_live(yabpe_ctx *c) {
+    HIPCHK(c, hipMemsetAsync(&c->scratch64[0], 0, 8, c->stream));
+    if (c->n_tiles) {
+        hipLaunchKernelGGL(k32_sum_len, dim3((uint32_t)std::min<uint64_t>(1024, cdiv64(c->n_tiles, BLOCK))), dim3(BLOCK), 0, c->stream, c->tile_len, c->n_tiles, &c->scratch64[0]);
+        HIPCHK(c, hipGetLastError());
+    }
+    unsigned long long v = 0;
+    HIPCHK(c, hipMemcpyAsync(&v, &c->scratch64[0], 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    c->st_host->live_slots = v;
+    return 0;
+}
+
+// ---------------------------------------------------------------------------------------------- verify
+int id32_verify(yabpe_ctx *c, uint64_t *out_mismatches) {
+    PairTable32 scratch{};
+    HIPCHK(c, hipMemsetAsync(&c->scratch64[4], 0, 16, c->stream));  // [4] entries, [5] mismatches
+    TRY(id32_table_alloc(c, scratch, (uint64_t)c->table32.mask + 1, &c->scratch64[4]));
+    scratch.max_probe = scratch.mask + 1;  // (the recount must not give up where the main table did not)
+    TRY(id32_count(c, scratch));
+    const uint32_t grid = (uint32_t)std::min<uint64_t>(1024, cdiv64((uint64_t)scratch.mask + 1, BLOCK));
+    hipLaunchKernelGGL(k32_table_compare, dim3(grid), dim3(BLOCK), 0, c->stream, Compare32Params{c->table32, scratch, &c->scratch64[5], 0u});
+    hipLaunchKernelGGL(k32_table_compare, dim3(grid), dim3(BLOCK), 0, c->stream, Compare32Params{scratch, c->table32, &c->scratch64[5], 1u});
+    HIPCHK(c, hipGetLastError());
+    unsigned long long mm = 0;
+    HIPCHK(c, hipMemcpyAsync(&mm, &c->scratch64[5], 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    id32_table_free(scratch);
+    HIPCHK(c, hipMemsetAsync(&c->st->halt_req, 0, 4, c->stream));
+    *out_mismatches = mm;
+    return YABPE_OK;
+}
+
+// ---------------------------------------------------------------------------------------------- train
+int id32_train(yabpe_ctx *c, uint32_t num_merges, uint64_t min_frequency, uint32_t *out_left, uint32_t *out_right, uint32_t *out_merged,
+               uint64_t *out_count, uint32_t *out_n_merges) {
+    TRY(state_pull(c));
+    DevState *h = c->st_host;
+    const uint32_t rec_base = h->iter;
+    if ((uint64_t)rec_base + num_merges > 0xFFFFFFF0ull) return fail(c, YABPE_E_CAPACITY, "more than 2^32 merges in one context");
+    h->num_merges = rec_base + num_merges;
+    h->min_freq = min_frequency;
+    h->done = 0; h->halt = 0; h->halt_req = 0;
+    TRY(state_push(c));
+    c->rec_n = 0;
+    c->log_sites.clear(); c->log_live.clear();
+    c->ev_iter.clear(); c->ev_us.clear(); c->ev_scan_us.clear();
+    if (num_merges == 0) return YABPE_OK;
+    // token-side capacities follow the request (every merge may take an id), the per-merge records too
+    TRY(id32_ensure_tokens(c, (uint64_t)h->n_tokens + num_merges));
+    if (c->rec_cap < num_merges) {
+        free_records(c);
+        TRY(dmalloc(c, &c->rec_left, num_merges)); TRY(dmalloc(c, &c->rec_right, num_merges)); TRY(dmalloc(c, &c->rec_merged, num_merges));
+        TRY(dmalloc(c, &c->rec_count, num_merges)); TRY(dmalloc(c, &c->rec_sites, num_merges)); TRY(dmalloc(c, &c->rec_live, num_merges));
+        c->rec_cap = num_merges;
+    }
+    HIPCHK(c, hipMemsetAsync(c->rec_sites, 0, (size_t)c->rec_cap * 8, c->stream));
+    if (!c->sel_ticket) {
+        TRY(dmalloc(c, &c->sel_ticket, TICKET_WORDS));
+        HIPCHK(c, hipMemsetAsync(c->sel_ticket, 0, TICKET_WORDS * 4, c->stream));
+    }
+    if (!c->partials32) TRY(dmalloc(c, &c->partials32, SEL32_MAX_BLOCKS));
+    const uint32_t check = (uint32_t)std::max<int64_t>(1, optv(c, "check_interval", 32));
+    const double retile_frac = (double)optv(c, "retile_pct", 60) / 100.0;
+    const uint64_t retile_min_tiles = (uint64_t)std::max<int64_t>(2, optv(c, "retile_min_tiles", 4096));
+    const uint32_t id_limit = (uint32_t)std::min<int64_t>(YbW32::MAX_TOKENS, std::max<int64_t>(256, optv(c, "id32_limit", YbW32::MAX_TOKENS)));
+    struct Events {  // (destroyed on every way out)
+        hipEvent_t t0 = nullptr, t1 = nullptr;
+        ~Events() {
+            if (t0) (void)hipEventDestroy(t0);
+            if (t1) (void)hipEventDestroy(t1);
+        }
+    } T;
+    HIPCHK(c, hipEventCreate(&T.t0));
+    HIPCHK(c, hipEventCreate(&T.t1));
+    HIPCHK(c, hipEventRecord(T.t0, c->stream));
+    uint64_t stream_bytes = 0, launches = 0;
+    TRY(id32_cand_attach(c));
+    uint32_t idle_rounds = 0;
+    for (;;) {
+        // one round: `check` merges, each a selection and an apply pass; kernels of a finished or halted job return at once
+        const uint64_t cap = (uint64_t)c->table32.mask + 1;
+        const uint32_t sel_grid = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(SEL32_MAX_BLOCKS, cap / (BLOCK * 16)));
+        const Select32Params SP{c->table32, c->tt, c->st, c->partials32, c->sel_ticket, c->rec_left, c->rec_right, c->rec_merged, c->rec_count,
+                                rec_base, c->tok_cap32, id_limit};
+        const Apply32Params AP{id32_stream(c), c->table32, c->st, c->rec_sites, rec_base};
+        const ApplyLong32Params LP{id32_long(c), c->table32, c->st, c->rec_sites, rec_base};
+        const uint32_t left = num_merges - (h->iter - rec_base);
+        const uint32_t round = std::min(check, left + 1);  // (+ 1: the selection that sees the limit and sets done)
+        for (uint32_t k = 0; k < round; ++k) {
+            hipLaunchKernelGGL(k32_select, dim3(sel_grid), dim3(BLOCK), 0, c->stream, SP);
+            if (c->n_tiles) hipLaunchKernelGGL(k32_apply, dim3(id32_grid(c)), dim3(BLOCK), 0, c->stream, AP);
+            if (c->n_long) hipLaunchKernelGGL(k32_apply_long, dim3(cdiv64(c->n_long, 64)), dim3(64), 0, c->stream, LP);
+        }
+        HIPCHK(c, hipGetLastError());
+        const uint32_t before = h->iter;
+        TRY(state_pull(c));
+        // (a selection whose candidate list drained commits nothing; the one after it scans the whole table and does)
+        idle_rounds = (h->iter == before && h->halt == HALT_NONE && !h->done) ? idle_rounds + 1 : 0;
+        if (idle_rounds >= 4) return fail(c, YABPE_E_INTERNAL, "the selection made no progress after %u merges", h->iter - rec_base);
+        launches += h->iter - before;
+        stream_bytes += (uint64_t)(h->iter - before) * (h->live_slots * 4 + (uint64_t)c->n_tiles * 8);
+        if (h->halt != HALT_NONE) {
+            const uint32_t why = h->halt;
+            if (why == HALT_VOCAB_FULL) {
+                if (h->n_tokens >= id_limit) return fail(c, YABPE_E_CAPACITY, "u32 token id space exhausted (ids run 0 .. 2^24 - 3) after %u merges", h->iter - rec_base);
+                TRY(id32_ensure_tokens(c, (uint64_t)h->n_tokens + (num_merges - (h->iter - rec_base))));
+                TRY(state_pull(c));
+            } else if (why == HALT_POOL_FULL) {
+                TRY(id32_grow_pool(c));
+            } else if (why == HALT_TABLE_FULL) {
+                // a probe sequence ran out during an apply pass: its deltas are lost, the stream is whole -- a larger table, recounted
+                TRY(id32_table_rebuild(c, ((uint64_t)c->table32.mask + 1) * 2));
+                TRY(id32_cand_attach(c));
+                TRY(state_pull(c));
+            } else {
+                return fail(c, YABPE_E_INTERNAL, "device halt %u after %u merges", why, h->iter - rec_base);
+            }
+            h->halt = HALT_NONE;
+            h->halt_req = HALT_NONE;
+            TRY(state_push(c));
+            continue;
+        }
+        if (h->done || h->iter - rec_base >= num_merges) {
+            // (the last committed merge has been applied: every selection is followed by its apply pass)
+            if (h->halt_req == HALT_TABLE_FULL) {
+                TRY(id32_table_rebuild(c, ((uint64_t)c->table32.mask + 1) * 2));
+                TRY(state_pull(c));
+                h->halt_req = HALT_NONE;
+                TRY(state_push(c));
+            }
+            break;
+        }
+        if (h->table_entries * 100 > ((uint64_t)c->table32.mask + 1) * (uint64_t)optv(c, "table_load_pct", 30)) {
+            TRY(id32_table_grow(c, std::max<uint64_t>(h->table_entries * 4, 1024)));
+            TRY(id32_cand_attach(c));
+            TRY(state_pull(c));
+        }
+        TRY(id32_refresh_live(c));
+        TRY(state_push(c));
+        if (c->n_tiles >= retile_min_tiles && (double)h->live_slots < retile_frac * (double)c->n_tiles * SPAN32) TRY(id32_repack(c));
+    }
+    HIPCHK(c, hipEventRecord(T.t1, c->stream));
+    HIPCHK(c, hipEventSynchronize(T.t1));
+    float ms = 0;
+    HIPCHK(c, hipEventElapsedTime(&ms, T.t0, T.t1));
+    c->stats.train_ms += ms;
+    if (c->table32.cs) {  // scans of the whole table that (re)built the list; selections that found it drained
+        Cand32 hs{};
+        HIPCHK(c, hipMemcpy(&hs, c->cand32_state, sizeof hs, hipMemcpyDeviceToHost));
+        c->cand_rebuilds = hs.rebuilds;
+        c->cand_rescans = hs.drains;
+    }
+    c->table32.cs = nullptr;  // (verify, rehash and recount see a plain table; the next call attaches the list again)
+    c->stats.dense_launches += launches;
+    c->stats.dense_merges += launches;
+    c->stats.dense_actual_bytes_sampled += stream_bytes;  // (every launch counted: bytes of live slots + tile lengths read)
+    TRY(state_pull(c));
+    h->tokens_now -= h->sites;
+    h->sites = 0;
+    TRY(state_push(c));
+    const uint32_t n = h->iter - rec_base;
+    c->rec_n = n;
+    c->log_sites.assign(n, 0);
+    c->log_live.assign(n, 0);
+    if (n) {
+        HIPCHK(c, hipMemcpy(c->log_sites.data(), c->rec_sites, (size_t)n * 8, hipMemcpyDeviceToHost));
+        if (out_left) HIPCHK(c, hipMemcpy(out_left, c->rec_left, (size_t)n * 4, hipMemcpyDeviceToHost));
+        if (out_right) HIPCHK(c, hipMemcpy(out_right, c->rec_right, (size_t)n * 4, hipMemcpyDeviceToHost));
+        if (out_merged) HIPCHK(c, hipMemcpy(out_merged, c->rec_merged, (size_t)n * 4, hipMemcpyDeviceToHost));
+        if (out_count) HIPCHK(c, hipMemcpy(out_count, c->rec_count, (size_t)n * 8, hipMemcpyDeviceToHost));
+    }
+    if (out_n_merges) *out_n_merges = n;
+    if (optv(c, "verify", 0)) {
+        uint64_t mm = 0;
+        TRY(id32_verify(c, &mm));
+        if (mm) return fail(c, YABPE_E_INTERNAL, "incremental pair table differs from a recount in %llu keys", (unsigned long long)mm);
+    }
+    return YABPE_OK;
+}
+
+}  // namespace

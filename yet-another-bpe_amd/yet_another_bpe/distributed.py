@@ -177,9 +177,10 @@ def train_text_sharded(ctx_factory, files, config, rank: int, world: int, transp
     from pathlib import Path
 
     from . import _native
-    from .trainer import BBPETrainer, check_files, device_options, read_chunks, segment_error, utf8_error
+    from .trainer import BBPETrainer, check_files, check_sharded_budget, device_options, read_chunks, segment_error, utf8_error
 
     device_options(config)  # (ValueError before any file is read)
+    check_sharded_budget(config.vocab_size)
     tr = BBPETrainer(config)
     paths = [Path(f) for f in files]
     check_files(paths)
@@ -218,9 +219,10 @@ def train_device_text_sharded(ctx_factory, make_text, config, rank: int, world: 
     `make_text(ctx) -> (dev_ptr, n_bytes)` runs on every rank; the chunk cuts are the reference's (config.chunk_size_bytes),
     this rank pre-tokenises ITS chunks, pools the pre-tokens and joins the collective merge loop.
     Returns (left, right, merged, count, stats, n_pretokens_here)."""
-    from .trainer import BBPETrainer, chunk_ranges, device_options
+    from .trainer import BBPETrainer, check_sharded_budget, chunk_ranges, device_options
 
     device_options(config)  # (ValueError before the context is made)
+    check_sharded_budget(config.vocab_size)
     base = BBPETrainer(config)._base_tokens()
     with ctx_factory() as ctx:
         for k, v in [*(options or {}).items(), *device_options(config).items()]:  # (the config's: the same on every rank)

@@ -192,6 +192,32 @@ class BBPETrainerConfig:
     normalizer: str | None = None
 
 
+U16_TOKENS = 65_534  # tokens the u16 merge loop holds (ids 0 .. 65,533)
+ID32_TOKENS = (1 << 24) - 2  # ... and the u32 one (ids 0 .. 2^24 - 3: the decode table's bound)
+
+
+def id_bits_mode() -> str:
+    """YABPE_ID_BITS: "auto" (the default: the u16 path while ids are left, then the u32 path), "16" (the u16 path only: a
+    job that needs more ids ends in its capacity error) or "32" (the whole job on the u32 path)."""
+    mode = os.environ.get("YABPE_ID_BITS", "auto").strip().lower() or "auto"
+    if mode not in ("16", "32", "auto"):
+        raise ValueError(f"YABPE_ID_BITS is {mode!r}: 16, 32 or auto")
+    return mode
+
+
+def stage1_merges(n_tokens: int, budget: int) -> int:
+    """Merges to ask of the u16 path: as many as ids are left (a merge that reuses an id takes none, so the caller asks again
+    while this is positive), at most the budget."""
+    return max(0, min(int(budget), U16_TOKENS - int(n_tokens)))
+
+
+def check_sharded_budget(vocab_size: int) -> None:
+    """The multi-GPU drivers run the u16 merge loop only."""
+    if int(vocab_size) > U16_TOKENS:
+        raise ValueError(f"vocab_size = {vocab_size}: training on several GPUs holds at most {U16_TOKENS:,} tokens (u16 ids); "
+                         "the u32 merge loop (id_bits = 32) is single-device")
+
+
 def max_token_bytes(config: BBPETrainerConfig) -> int:
     """config.max_token_length as the library's option `max_token_bytes` (0: no limit).  ValueError for anything but None or
     an integer >= 2 (two single bytes must be able to merge); bool is not an integer here."""
@@ -533,27 +559,102 @@ class BBPETrainer:
         dev_bytes, dev_off, dev_freq, n_unique, _n_bytes = ctx.pool_get()
         return dev_bytes, dev_off, n_unique, dev_freq, False
 
-    def _run(self, ctx, toks: list[bytes], words, triples, num_merges: int):
-        """The merge loop on ctx, from `toks` (with `triples`: the merges that made them, replayed by the load) over `words`:
-        host arrays (flat, off, freq) or device words (bytes address, offsets address, n, counts address or 0, dedup) -- with
-        counts they are the context's pool, which is cleared once the load has copied what it needs.  -> (vocab, merges)"""
+    def _load(self, ctx, toks: list[bytes], words, triples, pooled: bool = False) -> None:
+        """set_vocab + the load of `words` on ctx: host arrays (flat, off, freq) or device words (bytes address, offsets
+        address, n, counts address or 0, dedup); with `triples` the resumed load.  pooled: equal words are pooled even where
+        the words come without counts and without `dedup` (the u32 path's resumed load needs it)."""
         ctx.set_vocab(toks)
         if len(words) == 3:
+            dedup = pooled and words[2] is None
             if triples is None:
-                ctx.load_words(*words)
+                ctx.load_words(*words, dedup=dedup)
             else:
-                ctx.load_words_resumed(*words, triples)
+                ctx.load_words_resumed(*words, triples, dedup=dedup)
         else:
             dev_bytes, dev_off, n_words, dev_freq, dedup = words
+            dedup = dedup or (pooled and not dev_freq)
             if triples is None:
                 ctx.load_words_ptr(dev_bytes, dev_off, n_words, freq_ptr=dev_freq, dedup=dedup)
             else:
                 ctx.load_words_resumed_ptr(dev_bytes, dev_off, n_words, triples, freq_ptr=dev_freq, dedup=dedup)
-            if dev_freq:
+
+    def _run(self, ctx, toks: list[bytes], words, triples, num_merges: int):
+        """The merge loop on ctx, from `toks` (with `triples`: the merges that made them, replayed by the load) over `words`:
+        host arrays (flat, off, freq) or device words (bytes address, offsets address, n, counts address or 0, dedup) -- with
+        counts they are the context's pool, which is cleared once the last load has copied what it needs.  -> (vocab, merges)
+        The ONE place the id width is chosen (YABPE_ID_BITS, id_bits_mode): a budget that fits in 65,534 ids runs as it always
+        did.  A larger one runs on the u16 path while ids are left (stage 1: stage1_merges per yabpe_train call, again after
+        merges that reused an id; a call that returns fewer merges than asked hit a stop rule and ends the job), then the same
+        words are loaded into a second context with id_bits = 32 through the resumed load, which replays every merge so far,
+        and the u32 path runs the rest (stage 2).  last_stats says what each stage did."""
+        mode = id_bits_mode()
+        min_frequency = max(0, int(self.config.min_frequency))  # (<= 0: merge to exhaustion, as the reference does)
+        is_pool = len(words) == 5 and bool(words[3])
+        if mode == "16" or (mode == "auto" and len(toks) + num_merges <= U16_TOKENS):
+            self._load(ctx, toks, words, triples)
+            if is_pool:
                 ctx.pool_clear()
-        left, right, merged, _count = ctx.train(num_merges, max(0, int(self.config.min_frequency)))  # (<= 0: merge to exhaustion, as the reference does)
-        self.last_stats = ctx.stats()
-        return self._decode_merges(toks, left, right, merged)
+            left, right, merged, _count = ctx.train(num_merges, min_frequency)
+            self.last_stats = ctx.stats()
+            return self._decode_merges(toks, left, right, merged)
+        base = list(toks)
+        done = [np.asarray(x, dtype=np.uint32) for x in (triples if triples is not None else ((), (), ()))]
+        n_tokens, n_done, stages, stopped = len(toks), 0, 0, False
+        if mode == "auto" and stage1_merges(n_tokens, num_merges) > 0:
+            self._load(ctx, base, words, triples)
+            while not stopped and stage1_merges(n_tokens, num_merges - n_done) > 0:
+                ask = stage1_merges(n_tokens, num_merges - n_done)
+                left, right, merged, _count = ctx.train(ask, min_frequency)
+                done = [np.concatenate([d, np.asarray(x, dtype=np.uint32)]) for d, x in zip(done, (left, right, merged))]
+                n_tokens += len({int(m) for m in merged.tolist() if m >= n_tokens})  # (fresh ids; a reused id takes none)
+                n_done += len(left)
+                stages += 1
+                stopped = len(left) < ask
+        stats16 = ctx.stats() if stages else None
+        stats = {"id16_merges": n_done, "id16_stages": stages, "id32_merges": 0, "id32_replayed_merges": 0, "id32_load_ms": 0.0,
+                 "id16_train_ms": stats16["train_ms"] if stats16 else 0.0}
+        if not stopped and n_done < num_merges:
+            # stage 2: every token so far, the words again (pooled), all merges replayed by rank
+            all_toks = self._decode_tokens(base, done, len(triples[0]) if triples is not None else 0)
+            replay = tuple(done) if len(done[0]) else None
+            ctx32 = ctx if not stages else self._context()
+            try:
+                ctx32.set_option("id_bits", 32)
+                self._load(ctx32, all_toks, words, replay, pooled=True)
+                if is_pool:
+                    ctx.pool_clear()
+                rs = ctx32.resume_stats()
+                left, right, merged, _count = ctx32.train(num_merges - n_done, min_frequency)
+                done = [np.concatenate([d, np.asarray(x, dtype=np.uint32)]) for d, x in zip(done, (left, right, merged))]
+                stats.update(ctx32.stats())
+                stats.update(id32_merges=len(left), id32_replayed_merges=0 if replay is None else len(replay[0]),
+                             id32_load_ms=rs["segment_ms"] + rs["build_ms"])
+            finally:
+                if ctx32 is not ctx:
+                    ctx32.close()
+        else:
+            if is_pool:
+                ctx.pool_clear()
+            stats = {**stats16, **stats}
+        self.last_stats = stats
+        skip = len(triples[0]) if triples is not None else 0
+        return self._decode_merges_from(base, done, skip)
+
+    @staticmethod
+    def _decode_tokens(base: Sequence[bytes], triples, n_old: int) -> list[bytes]:
+        """The tokens in id order after `triples` ((left, right, merged) arrays; the first n_old made `base` itself)"""
+        toks = list(base)
+        for l, r, m in zip(triples[0][n_old:].tolist(), triples[1][n_old:].tolist(), triples[2][n_old:].tolist()):
+            if m == len(toks):
+                toks.append(toks[l] + toks[r])
+        return toks
+
+    @staticmethod
+    def _decode_merges_from(base: Sequence[bytes], triples, n_old: int):
+        """(vocab, the merges after the first n_old) of `triples` over `base` (the tokens the first n_old merges made)"""
+        from ._native import decode_merges
+
+        return decode_merges(base, triples[0][n_old:], triples[1][n_old:], triples[2][n_old:])
 
     # ------------------------------------------------------------------ continuing from a trained model
     def _resumable(self, model) -> tuple[list[bytes], tuple]:
