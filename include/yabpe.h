@@ -521,9 +521,35 @@ int yabpe_layout_pad(yabpe_ctx *ctx, const uint32_t *ids, uint64_t n_ids, const 
 int yabpe_layout_pack(yabpe_ctx *ctx, const uint32_t *ids, uint64_t n_ids, const uint64_t *doc_off, uint32_t n_docs,
                       const yabpe_layout_t *layout, uint32_t **out_dev_ids, uint32_t **out_dev_doc, uint32_t **out_dev_pos,
                       uint64_t *out_n_rows);
+/* Overlapping windows (BBPETokenizer.encode_batch_windows on the device): a document longer than a row becomes several rows.
+ * ids, doc_off and layout as the two calls above take them; layout->row_len = max_length, flags: YABPE_LAYOUT_BOS / _EOS /
+ * _PAD_LEFT.  With C = row_len - n_added content slots a row and step = C - stride: row k = 0, 1, ... of document d holds
+ * [bos_id] + ids[k * step : k * step + C] + [eos_id], padded with pad_id at its right end (YABPE_LAYOUT_PAD_LEFT: at its left
+ * end); the last row of a document is the first one with k * step + C >= n.  Every document, an empty one included, has at
+ * least one row: 1 for n <= C, else 1 + ceil((n - C) / step); every row but a document's last is full, and consecutive rows of
+ * a document share exactly stride ids.  Rows are in document order, in window order within a document.
+ * Results (device memory owned by the library, buffers of their own, released as the other layout results are): rows = n_rows
+ * * row_len u32; per row its document (row_doc), k * step (row_start: the index of its first content id in the document) and
+ * its length before padding, BOS / EOS included (row_len).  spans: NULL, or 2 * n_ids u64 as yabpe_encode_spans returns them
+ * (host or device memory); then out->spans = 2 * n_rows * row_len u64, the (start, end) of every slot's id, (0, 0) in BOS, EOS
+ * and pad slots; without spans out->spans = NULL.
+ * YABPE_E_INVALID: row_len <= n_added; stride >= row_len - n_added; YABPE_LAYOUT_TRUNC_LEFT, _DROP_LAST or an unknown flag; a
+ * bad doc_off.  YABPE_E_CAPACITY: more than 2^36 output slots; a document of more than 2^32 - 1 ids.  Every error is found
+ * before a result buffer is allocated.  yabpe_layout_stats: n_truncated_docs = the documents of more than one row,
+ * n_ids_dropped = 0, lengths_ms = row counts + their scan + the row records. */
+typedef struct yabpe_windows_t {
+    uint32_t *rows;       /* n_rows * row_len */
+    uint32_t *row_doc;    /* n_rows */
+    uint32_t *row_start;  /* n_rows */
+    uint32_t *row_len;    /* n_rows */
+    uint64_t *spans;      /* 2 * n_rows * row_len, or NULL */
+    uint64_t n_rows;
+} yabpe_windows_t;
+int yabpe_layout_windows(yabpe_ctx *ctx, const uint32_t *ids, uint64_t n_ids, const uint64_t *doc_off, uint32_t n_docs,
+                         const uint64_t *spans, const yabpe_layout_t *layout, uint32_t stride, yabpe_windows_t *out);
 int yabpe_layout_free(yabpe_ctx *ctx);
-/* What the last yabpe_layout_pad / yabpe_layout_pack saw, and the device time of its phases (HIP events around each phase's
- * launches). */
+/* What the last yabpe_layout_pad / yabpe_layout_pack / yabpe_layout_windows saw, and the device time of its phases (HIP events
+ * around each phase's launches). */
 typedef struct yabpe_layout_stats_t {
     uint64_t n_ids, n_docs;
     uint64_t n_rows, row_len;

@@ -1,11 +1,12 @@
 #!/usr/bin/env python3
-"""Dev tool: the fixed-shape batch layouts (yabpe_layout_pad / yabpe_layout_pack) on the ids of 1 GiB of synth.text_lexicon text
-generated on the device, encoded with a 32,000-merge model trained on the device from that text; documents cut at pre-token
-boundaries to a mean of about 1,000 ids.  Encode once, then both layouts, best of --reps after a warm-up: device time per phase
-from yabpe_layout_stats, bytes read + written over write_ms as GB/s, and that rate against a plain device-to-device
-hipMemcpyAsync of the same number of output bytes (HIP events, same run).  Padded: max_length 1024; packed: seq_len 2048 with an
-EOS.  For comparison, what a user does without the layout calls on a --host-mib sample: encode_array, then a numpy loop per
-document on the host that builds the same padded batch.
+"""Dev tool: the fixed-shape batch layouts (yabpe_layout_pad / yabpe_layout_pack / yabpe_layout_windows) on the ids of 1 GiB of
+synth.text_lexicon text generated on the device, encoded with a 32,000-merge model trained on the device from that text;
+documents cut at pre-token boundaries to a mean of about 1,000 ids.  Encode once, then every layout, best of --reps after a
+warm-up: device time per phase from yabpe_layout_stats, bytes read + written over write_ms as GB/s, and that rate against a plain
+device-to-device hipMemcpyAsync of the same number of output bytes (HIP events, same run).  Padded: max_length 1024; packed:
+seq_len 2048 with an EOS; windows: max_length 1024, stride 128, a BOS, without spans and with the byte spans of
+yabpe_encode_spans.  For comparison, what a user does without the layout calls on a --host-mib sample: encode_array, then a
+numpy loop per document on the host that builds the same padded batch.
    python tools/layout_bench.py [--mib 1024] [--merges 32000] [--reps 3] [--host-mib 64] [--json out.json]"""
 import argparse, ctypes, json, sys, time
 from pathlib import Path
@@ -25,6 +26,7 @@ ap.add_argument("--doc-ids", type=int, default=1000)
 ap.add_argument("--json", default="")
 a = ap.parse_args()
 PAD_LEN, PACK_LEN, EOS = 1024, 2048, 2
+WIN_LEN, WIN_STRIDE, BOS = 1024, 128, 1
 
 
 def copy_ms(n_bytes: int, reps: int) -> float:
@@ -89,13 +91,27 @@ with _native.Context() as gen:
                 "total_ms": round(st["total_ms"], 3), "all_total_ms": all_ms, "bytes_read": read_b, "bytes_written": write_b,
                 "write_GB_per_s": round(rate, 1), "copy_same_output_bytes_ms": round(cp, 3), "copy_GB_per_s": round(cp_rate, 1),
                 "write_rate_vs_copy": round(rate / cp_rate, 3), "write_ms_vs_copy_ms": round(st["write_ms"] / cp, 2),
-                "total_vs_encode_emit_ms": round(st["total_ms"] / enc["emit_ms"], 3)}
+                "total_vs_encode_emit_ms": round(st["total_ms"] / enc["emit_ms"], 3),
+                "write_ns_per_slot": round(st["write_ms"] * 1e6 / max(1, st["n_rows"] * st["row_len"]), 5)}
 
     lens = np.diff(doc_off)
     st, all_ms = timed(lambda: gen.layout_pad(di, ni, dd, n_docs, row_len=PAD_LEN, pad_id=0))
     padded = report(st, all_ms, 4 * int(np.minimum(lens, PAD_LEN).sum()) + 8 * n_docs, 4 * n_docs * PAD_LEN + 4 * n_docs)
     st, all_ms = timed(lambda: gen.layout_pack(di, ni, dd, n_docs, row_len=PACK_LEN, pad_id=0, eos_id=EOS))
     packed = report(st, all_ms, 4 * ni + 8 * (n_docs + 1), 12 * st["n_rows"] * PACK_LEN)
+    # windows: every kept content id is read once per row that holds it, plus one 16-byte record per row
+    C, step = WIN_LEN - 1, WIN_LEN - 1 - WIN_STRIDE
+    win_rows = np.where(lens <= C, 1, 1 + -(-(lens - C) // step))
+    kept = int((lens + (win_rows - 1) * WIN_STRIDE).sum())
+    n_win = int(win_rows.sum())
+    win_kw = dict(row_len=WIN_LEN, stride=WIN_STRIDE, pad_id=0, bos_id=BOS)
+    st, all_ms = timed(lambda: gen.layout_windows(di, ni, dd, n_docs, **win_kw))
+    assert st["n_rows"] == n_win and st["n_pad_slots"] == n_win * WIN_LEN - kept - n_win
+    windows = report(st, all_ms, 4 * kept + 16 * n_win, 4 * n_win * WIN_LEN)
+    di, dd, ds, ni_s = gen.encode_spans(tb, n_bytes=tn, doc_starts=starts)
+    assert ni_s == ni
+    st, all_ms = timed(lambda: gen.layout_windows(di, ni, dd, n_docs, ds, **win_kw))
+    windows_spans = report(st, all_ms, 20 * kept + 16 * n_win, 20 * n_win * WIN_LEN)
     gen.layout_free()
     n_host = int(np.searchsorted(starts, a.host_mib << 20))  # the documents that lie inside the host sample
     sample = gen.d2h(tb, int(starts[n_host]) if n_host < n_docs else tn).tobytes()
@@ -118,7 +134,7 @@ host_s = time.perf_counter() - t0
 assert np.array_equal(rows, rows_dev)
 out = {"text_bytes": tn, "merges": len(merges), "ids": ni, "docs": n_docs, "mean_ids_per_doc": round(ni / n_docs, 1),
        "encode_emit_ms": round(enc["emit_ms"], 3), "encode_total_ms": round(enc["total_ms"], 3), "padded_1024": padded,
-       "packed_2048_eos": packed,
+       "packed_2048_eos": packed, "windows_1024_stride_128_bos": windows, "windows_1024_stride_128_bos_byte_spans": windows_spans,
        "host_sample": {"text_bytes": len(sample), "docs": len(docs), "encode_array_then_numpy_loop_s": round(host_s, 3),
                        "of_which_encode_array_s": round(enc_s, 3), "MB_per_s": round(len(sample) / host_s / 1e6, 1),
                        "encode_array_padded_s": round(dev_s, 3), "encode_array_padded_MB_per_s": round(len(sample) / dev_s / 1e6, 1)}}

@@ -10,6 +10,12 @@
 //             closed form soff[d] = doc_off[d] + n_added * d (soff[n_docs] = n_ids + n_added * n_docs).
 //             Rule 2 (lay_find_doc / lay_pack_slot): which (doc, pos) a stream position belongs to, given soff.  A document
 //             with an empty seq has soff[d] == soff[d + 1] and owns no position: the search takes the LAST d with soff[d] <= g.
+//   windows   (encode_batch_windows) with C = row_len - n_added content slots a row and step = C - stride: row k of document d
+//             holds [bos] + ids[k * step : k * step + C] + [eos], padded like a padded row; the last row is the first one with
+//             k * step + C >= n, so every document owns at least one row and only its last row can be short.
+//             Rule 3 (lay_win_rows / lay_win_content / lay_win_slot): how many rows a document has, how many content ids row
+//             k keeps, which source id a slot holds.  The first output row of document d is the exclusive scan of the row
+//             counts; it ascends strictly, so the document of an output row is Rule 2's search (lay_find_doc) as it is.
 #pragma once
 #include <stdint.h>
 
@@ -19,6 +25,7 @@
 constexpr uint32_t LAY_BOS = 0x01u, LAY_EOS = 0x02u, LAY_TRUNC_LEFT = 0x04u, LAY_PAD_LEFT = 0x08u, LAY_DROP_LAST = 0x10u;
 constexpr uint32_t LAY_PAD_FLAGS = LAY_BOS | LAY_EOS | LAY_TRUNC_LEFT | LAY_PAD_LEFT;
 constexpr uint32_t LAY_PACK_FLAGS = LAY_BOS | LAY_EOS | LAY_DROP_LAST;
+constexpr uint32_t LAY_WIN_FLAGS = LAY_BOS | LAY_EOS | LAY_PAD_LEFT;
 constexpr uint32_t LAY_NO_DOC = 0xFFFFFFFFu;                   // `doc` of a packed slot past the end of the stream
 constexpr unsigned long long LAY_MAX_SLOTS = 1ull << 36;       // output slots one call addresses at most
 
@@ -74,4 +81,28 @@ YB_HD unsigned long long lay_pack_slot(unsigned long long g, uint32_t d, unsigne
 // rows of a packed batch over a stream of `total` positions
 YB_HD unsigned long long lay_pack_rows(unsigned long long total, uint32_t row_len, uint32_t flags) {
     return flags & LAY_DROP_LAST ? total / row_len : (total + row_len - 1) / row_len;
+}
+
+// Rule 3.  Rows of a document of n ids: C >= 1 content slots a row, consecutive rows step = C - stride >= 1 ids apart.
+YB_HD unsigned long long lay_win_rows(unsigned long long n, unsigned long long C, unsigned long long step) {
+    return n <= C ? 1ull : 1ull + (n - C + step - 1) / step;
+}
+
+// content ids row k of that document keeps (k < lay_win_rows(n, C, step), so k * step <= n): C, less only in the last row
+YB_HD unsigned long long lay_win_content(unsigned long long n, unsigned long long k, unsigned long long C, unsigned long long step) {
+    const unsigned long long left = n - k * step;
+    return left < C ? left : C;
+}
+
+// Slot `col` of a window row whose `content` ids start at ids[first]: the index of the id it holds, or LAY_SLOT_PAD / _BOS /
+// _EOS -- a padded row of exactly those ids (content <= C: nothing is cut).
+YB_HD unsigned long long lay_win_row_slot(unsigned long long first, unsigned long long content, uint32_t row_len, uint32_t flags, uint32_t col) {
+    return lay_pad_slot(first, content, row_len, flags & LAY_WIN_FLAGS, col);
+}
+
+// Slot `col` of row k of a document whose n ids start at ids[start].
+YB_HD unsigned long long lay_win_slot(unsigned long long start, unsigned long long n, unsigned long long k, uint32_t row_len, uint32_t stride,
+                                      uint32_t flags, uint32_t col) {
+    const unsigned long long C = row_len - lay_n_added(flags), step = C - stride;
+    return lay_win_row_slot(start + k * step, lay_win_content(n, k, C, step), row_len, flags, col);
 }

@@ -186,8 +186,9 @@ struct yabpe_ctx {
     unsigned long long *dec_doc = nullptr;
     yabpe_decode_stats_t dec_stats{};
     hipEvent_t dec_ev[7] = {};
-    // fixed-shape batches (yabpe_layout_pad / yabpe_layout_pack)
-    uint32_t *lay_buf[3] = {};                // results of the last layout call: rows, lengths / ids, doc, pos
+    // fixed-shape batches (yabpe_layout_pad / yabpe_layout_pack / yabpe_layout_windows)
+    uint32_t *lay_buf[5] = {};                // results of the last layout call: rows, lengths / ids, doc, pos /
+                                              // rows, row_doc, row_start, row_len, spans (u64 pairs)
     yabpe_layout_stats_t lay_stats{};
     hipEvent_t lay_ev[4] = {};
     // resumed load (yabpe_load_words_resumed)
@@ -3695,7 +3696,7 @@ static int layout_begin(yabpe_ctx *c, Scratch &S, const uint32_t *ids, uint64_t 
     return 0;
 }
 
-// lay_ev[0..1] around the lengths pass, [2..3] around the write pass
+// lay_ev[0..1] around the lengths pass (windows: count + scan + rows), [2..3] around the write pass
 static void layout_times(yabpe_ctx *c) {
     float ms[3] = {0, 0, 0};
     (void)hipEventElapsedTime(&ms[0], c->lay_ev[0], c->lay_ev[1]);
@@ -3795,7 +3796,7 @@ int yabpe_layout_pack(yabpe_ctx *c, const uint32_t *ids, uint64_t n_ids, const u
     HIPCHK(c, hipStreamSynchronize(s));
     if (longest > 0xFFFFFFFFull) return fail(c, YABPE_E_CAPACITY, "a document of %llu stream entries: positions are u32", longest);
     // ---- write
-    for (auto &p : c->lay_buf) TRY(dmalloc(c, &p, n_slots));
+    for (int k = 0; k < 3; ++k) TRY(dmalloc(c, &c->lay_buf[k], n_slots));
     HIPCHK(c, hipEventRecord(c->lay_ev[2], s));
     if (n_slots)
         hipLaunchKernelGGL(k_lay_pack_write, dim3(cdiv64(n_slots, LAY_PIECE)), dim3(BLOCK), 0, s,
@@ -3818,6 +3819,82 @@ int yabpe_layout_pack(yabpe_ctx *c, const uint32_t *ids, uint64_t n_ids, const u
     *out_dev_doc = c->lay_buf[1];
     *out_dev_pos = c->lay_buf[2];
     *out_n_rows = n_rows;
+    return YABPE_OK;
+}
+
+int yabpe_layout_windows(yabpe_ctx *c, const uint32_t *ids, uint64_t n_ids, const uint64_t *doc_off, uint32_t n_docs, const uint64_t *spans,
+                         const yabpe_layout_t *lay, uint32_t stride, yabpe_windows_t *out) {
+    if (!c || !out) return YABPE_E_INVALID;
+    HIPCHK(c, hipSetDevice(c->device));
+    *out = yabpe_windows_t{};
+    const uint32_t added = lay ? lay_n_added(lay->flags & LAY_WIN_FLAGS) : 0u;
+    if (lay && lay->row_len <= added) return fail(c, YABPE_E_INVALID, "row_len %u leaves no slot for content beside BOS and EOS", lay->row_len);
+    if (lay && stride >= lay->row_len - added)
+        return fail(c, YABPE_E_INVALID, "stride %u: consecutive rows of %u content slots must advance by at least one", stride, lay->row_len - added);
+    Scratch S(c->device, c->rank);
+    const uint32_t *d_ids = nullptr;
+    const unsigned long long *d_docs = nullptr;
+    TRY(layout_begin(c, S, ids, n_ids, doc_off, &n_docs, lay, LAY_WIN_FLAGS, &d_ids, &d_docs));
+    const ulonglong2 *d_spans = nullptr;
+    if (spans) TRY(to_device(c, S, (const ulonglong2 *)spans, n_ids * 16, 16, &d_spans));
+    const uint32_t L = lay->row_len, C = L - added, step = C - stride;
+    hipStream_t s = c->stream;
+    // ---- count + scan: the rows of every document, their exclusive scan, the call's counters
+    unsigned long long *counters = nullptr, *cnt = nullptr, *row_off = nullptr;
+    HIPCHK(c, S.get(&counters, 4));
+    HIPCHK(c, S.get(&cnt, n_docs));
+    HIPCHK(c, S.get(&row_off, (uint64_t)n_docs + 1));
+    HIPCHK(c, hipEventRecord(c->lay_ev[0], s));
+    HIPCHK(c, hipMemsetAsync(counters, 0, 32, s));
+    hipLaunchKernelGGL(k_lay_win_count, dim3(cdiv64(n_docs, BLOCK)), dim3(BLOCK), 0, s,
+                       LayWinCountParams{d_docs, n_docs, n_ids, C, step, added, cnt, counters});
+    HIPCHK(c, hipGetLastError());
+    if (exclusive_scan<unsigned long long>(s, cnt, n_docs, row_off, (unsigned long long)n_docs + 1) != 0)
+        return fail(c, YABPE_E_HIP, "scan of the row counts failed");
+    unsigned long long h_cnt[4] = {0, 0, 0, 0}, n_rows = 0;
+    HIPCHK(c, hipMemcpyAsync(h_cnt, counters, 32, hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipMemcpyAsync(&n_rows, row_off + n_docs, 8, hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipStreamSynchronize(s));
+    if (h_cnt[0] > 0xFFFFFFFFull) return fail(c, YABPE_E_CAPACITY, "a document of %llu ids: row_start is u32", h_cnt[0]);
+    if (n_rows > LAY_MAX_SLOTS / L) return fail(c, YABPE_E_CAPACITY, "%llu rows of %u slots: at most 2^36 slots in one call", n_rows, L);
+    const unsigned long long n_slots = n_rows * L;
+    // ---- rows: the record of every output row
+    ulonglong2 *rec = nullptr;
+    HIPCHK(c, S.get(&rec, n_rows));
+    TRY(dmalloc(c, &c->lay_buf[0], n_slots));
+    for (int k = 1; k < 4; ++k) TRY(dmalloc(c, &c->lay_buf[k], n_rows));
+    if (spans) TRY(dmalloc(c, &c->lay_buf[4], 4 * n_slots));  // (16 B a slot)
+    hipLaunchKernelGGL(k_lay_win_rows, dim3(cdiv64(n_rows, BLOCK)), dim3(BLOCK), 0, s,
+                       LayWinRowsParams{d_docs, n_docs, n_ids, row_off, n_rows, C, step, added, c->lay_buf[1], c->lay_buf[2], c->lay_buf[3], rec});
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipEventRecord(c->lay_ev[1], s));
+    // ---- write
+    HIPCHK(c, hipEventRecord(c->lay_ev[2], s));
+    const LayWinParams W{d_ids, rec, n_rows, L, lay->flags, LayConst{lay->pad_id, lay->bos_id, lay->eos_id}, c->lay_buf[0], n_slots,
+                         d_spans, (ulonglong2 *)c->lay_buf[4]};
+    if (spans)
+        hipLaunchKernelGGL(k_lay_win_write<true>, dim3(cdiv64(n_slots, LAY_PIECE)), dim3(BLOCK), 0, s, W);
+    else
+        hipLaunchKernelGGL(k_lay_win_write<false>, dim3(cdiv64(n_slots, LAY_PIECE)), dim3(BLOCK), 0, s, W);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipEventRecord(c->lay_ev[3], s));
+    const hipError_t se = hipStreamSynchronize(s);
+    if (se != hipSuccess) {
+        yabpe_layout_free(c);
+        return fail(c, YABPE_E_HIP, "layout kernels failed: %s", hipGetErrorString(se));
+    }
+    auto &st = c->lay_stats;
+    st.n_rows = n_rows;
+    st.row_len = L;
+    st.n_truncated_docs = h_cnt[1];
+    st.n_pad_slots = n_slots - h_cnt[3];
+    layout_times(c);
+    out->rows = c->lay_buf[0];
+    out->row_doc = c->lay_buf[1];
+    out->row_start = c->lay_buf[2];
+    out->row_len = c->lay_buf[3];
+    out->spans = (uint64_t *)c->lay_buf[4];
+    out->n_rows = n_rows;
     return YABPE_OK;
 }
 

@@ -12,6 +12,15 @@
 //             finds the piece's first and last document by binary search in soff and stages that window in LDS; a window of
 //             more than LAY_STAGE offsets (many tiny documents in one piece) is searched in global memory instead.  The pad
 //             tail of the last packed row is written by the same kernel.
+//
+// Windows (yabpe_layout_windows; contract: BBPETokenizer.encode_batch_windows): a document becomes lay_win_rows rows, so the
+// first row of a document has no closed form:
+//   count     k_lay_win_count: one thread per document writes its row count; per call the longest document, the documents of
+//             more than one row and the slots kept (one atomic per counter and workgroup).  exclusive_scan -> row_off.
+//   rows      k_lay_win_rows: one thread per output row searches row_off once and writes row_doc, row_start, row_len and the
+//             row's record (first source id, content ids kept).
+//   write     k_lay_win_write: k_lay_pad_write's shape with one record read per row touched; <true> also stores the 16-byte
+//             span of every slot.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -35,6 +44,26 @@ struct LayLenParams {
     unsigned long long *counters;   // [0] longest sequence; padded also [1] truncated documents [2] ids dropped [3] slots kept
 };
 
+// The call's counters over a workgroup: v[0] by maximum, v[1..3] by sum; thread 0 holds the result afterwards.
+__device__ __forceinline__ void lay_reduce(unsigned long long (&v)[4], unsigned long long (*s_red)[4]) {
+    const int lane = threadIdx.x & 63, wib = threadIdx.x >> 6;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const unsigned long long m = __shfl_xor(v[0], o);
+        v[0] = m > v[0] ? m : v[0];
+#pragma unroll
+        for (int k = 1; k < 4; ++k) v[k] += __shfl_xor(v[k], o);
+    }
+    if (lane == 0)
+        for (int k = 0; k < 4; ++k) s_red[wib][k] = v[k];
+    __syncthreads();
+    if (threadIdx.x == 0)
+        for (int w = 1; w < WPB; ++w) {
+            v[0] = s_red[w][0] > v[0] ? s_red[w][0] : v[0];
+            for (int k = 1; k < 4; ++k) v[k] += s_red[w][k];
+        }
+}
+
 template <bool PACK>
 __global__ __launch_bounds__(BLOCK) void k_lay_lengths(LayLenParams P) {
     __shared__ unsigned long long s_red[WPB][4];
@@ -56,22 +85,8 @@ __global__ __launch_bounds__(BLOCK) void k_lay_lengths(LayLenParams P) {
             v[3] = kept;
         }
     }
-    const int lane = threadIdx.x & 63, wib = threadIdx.x >> 6;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const unsigned long long m = __shfl_xor(v[0], o);
-        v[0] = m > v[0] ? m : v[0];
-#pragma unroll
-        for (int k = 1; k < 4; ++k) v[k] += __shfl_xor(v[k], o);
-    }
-    if (lane == 0)
-        for (int k = 0; k < 4; ++k) s_red[wib][k] = v[k];
-    __syncthreads();
+    lay_reduce(v, s_red);
     if (threadIdx.x == 0) {
-        for (int w = 1; w < WPB; ++w) {
-            v[0] = s_red[w][0] > v[0] ? s_red[w][0] : v[0];
-            for (int k = 1; k < 4; ++k) v[k] += s_red[w][k];
-        }
         atomicMax(&P.counters[0], v[0]);
         if (!PACK)
             for (int k = 1; k < 4; ++k)
@@ -217,6 +232,137 @@ __global__ __launch_bounds__(BLOCK) void k_lay_pack_write(LayPackParams P) {
         lay_pack_lane(P, s_off, d0, d0, d1, g0, g1);
     else
         lay_pack_lane(P, P.soff, 0, d0, d1, g0, g1);
+}
+
+// ---- windows (yabpe_layout_windows): C content slots a row, consecutive rows of a document step ids apart
+struct LayWinCountParams {
+    const unsigned long long *doc;  // n_docs document starts
+    uint32_t n_docs;
+    unsigned long long n_ids;
+    uint32_t C, step, added;
+    unsigned long long *rows;       // out: rows per document (their exclusive scan is row_off)
+    unsigned long long *counters;   // [0] longest document (ids) [1] documents of more than one row [3] slots kept
+};
+
+__global__ __launch_bounds__(BLOCK) void k_lay_win_count(LayWinCountParams P) {
+    __shared__ unsigned long long s_red[WPB][4];
+    const unsigned long long d = (unsigned long long)blockIdx.x * BLOCK + threadIdx.x;
+    unsigned long long v[4] = {0, 0, 0, 0}; // max, more than one row, (unused), kept
+    if (d < P.n_docs) {
+        const unsigned long long a = P.doc[d], b = d + 1 < P.n_docs ? P.doc[d + 1] : P.n_ids;
+        const unsigned long long n = b - a, rows = lay_win_rows(n, P.C, P.step);
+        P.rows[d] = rows;
+        v[0] = n;
+        v[1] = rows > 1 ? 1u : 0u;
+        v[3] = rows * P.added + (rows - 1) * P.C + lay_win_content(n, rows - 1, P.C, P.step); // every row but the last is full
+    }
+    lay_reduce(v, s_red);
+    if (threadIdx.x == 0) {
+        atomicMax(&P.counters[0], v[0]);
+        for (int k = 1; k < 4; ++k)
+            if (v[k]) atomicAdd(&P.counters[k], v[k]);
+    }
+}
+
+struct LayWinRowsParams {
+    const unsigned long long *doc;      // n_docs document starts
+    uint32_t n_docs;
+    unsigned long long n_ids;
+    const unsigned long long *row_off;  // n_docs + 1: the first output row of every document
+    unsigned long long n_rows;          // row_off[n_docs]
+    uint32_t C, step, added;
+    uint32_t *row_doc, *row_start, *row_len; // out, per output row
+    ulonglong2 *rec;                    // out, per output row: (index into ids of its first content id, content ids it keeps)
+};
+
+__global__ __launch_bounds__(BLOCK) void k_lay_win_rows(LayWinRowsParams P) {
+    const unsigned long long r = (unsigned long long)blockIdx.x * BLOCK + threadIdx.x;
+    if (r >= P.n_rows) return;
+    const uint32_t d = lay_find_doc(P.row_off, 0, 0, P.n_docs - 1, r);
+    const unsigned long long k = r - P.row_off[d];
+    const unsigned long long a = P.doc[d], b = d + 1 < P.n_docs ? P.doc[d + 1] : P.n_ids;
+    const unsigned long long content = lay_win_content(b - a, k, P.C, P.step);
+    P.row_doc[r] = d;
+    P.row_start[r] = (uint32_t)(k * P.step);
+    P.row_len[r] = (uint32_t)content + P.added;
+    P.rec[r] = make_ulonglong2(a + k * P.step, content);
+}
+
+struct LayWinParams {
+    const uint32_t *ids;
+    const ulonglong2 *rec;          // n_rows row records (k_lay_win_rows)
+    unsigned long long n_rows;
+    uint32_t row_len, flags;
+    LayConst K;
+    uint32_t *rows;                 // out: n_rows * row_len slots
+    unsigned long long n_slots;
+    const ulonglong2 *spans;        // SPANS: one (start, end) per id ...
+    ulonglong2 *out_spans;          // ... and per output slot
+};
+
+// (row, col) of flat slot f; narrow (uniform): the 32-bit division
+__device__ __forceinline__ void lay_row_col(unsigned long long f, uint32_t row_len, bool narrow, unsigned long long *row, uint32_t *col) {
+    if (narrow) {
+        *row = (uint32_t)f / row_len;
+        *col = (uint32_t)f % row_len;
+    } else {
+        *row = f / row_len;
+        *col = (uint32_t)(f % row_len);
+    }
+}
+
+// k_lay_pad_write's shape: a row's ids are those of its record instead of a whole document.  SPANS: also the span of every slot,
+// in a pass of its own over the same 256 slots of a wave and step: lane l takes the slots l, 64 + l, 128 + l and 192 + l, so the
+// 16-byte loads and stores of a wave lie end to end (4 consecutive slots a lane would put 64 bytes between neighbouring lanes).
+template <bool SPANS>
+__global__ __launch_bounds__(BLOCK) void k_lay_win_write(LayWinParams P) {
+    const unsigned long long f0 = (unsigned long long)blockIdx.x * LAY_PIECE;
+    const bool narrow = P.n_slots <= 0xFFFFFFFFull; // (uniform: the 32-bit division then)
+    const uint32_t lane = threadIdx.x & 63;
+#pragma unroll
+    for (int s = 0; s < LAY_VPT; ++s) {
+        const unsigned long long f = f0 + ((unsigned long long)s * BLOCK + threadIdx.x) * 4;
+        const unsigned long long fw = f - 4ull * lane; // the wave's first slot
+        if ((SPANS ? fw : f) >= P.n_slots) break;
+        if (!SPANS || f < P.n_slots) {
+            unsigned long long row;
+            uint32_t col;
+            lay_row_col(f, P.row_len, narrow, &row, &col);
+            ulonglong2 rec = P.rec[row];
+            uint32_t v[4] = {0, 0, 0, 0};
+#pragma unroll
+            for (int k = 0; k < 4; ++k) { // (past the last slot col runs on past the row's end: a pad slot that is never stored)
+                v[k] = lay_value(P.ids, lay_win_row_slot(rec.x, rec.y, P.row_len, P.flags, col), P.K);
+                if (++col == P.row_len && row + 1 < P.n_rows) { // the next slot opens the next row
+                    col = 0;
+                    rec = P.rec[++row];
+                }
+            }
+            lay_store4(P.rows, f, P.n_slots, v);
+        }
+        if (SPANS) {
+            unsigned long long sa[4] = {0, 0, 0, 0}, sb[4] = {0, 0, 0, 0}; // the slots' (start, end)
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const unsigned long long g = fw + 64 * k + lane;
+                if (g < P.n_slots) {
+                    unsigned long long row;
+                    uint32_t col;
+                    lay_row_col(g, P.row_len, narrow, &row, &col);
+                    const ulonglong2 rec = P.rec[row];
+                    const unsigned long long slot = lay_win_row_slot(rec.x, rec.y, P.row_len, P.flags, col);
+                    if (slot < LAY_SLOT_EOS) {
+                        const ulonglong2 sp = P.spans[slot];
+                        sa[k] = sp.x;
+                        sb[k] = sp.y;
+                    }
+                }
+            }
+#pragma unroll
+            for (int k = 0; k < 4; ++k)
+                if (fw + 64 * k + lane < P.n_slots) P.out_spans[fw + 64 * k + lane] = make_ulonglong2(sa[k], sb[k]);
+        }
+    }
 }
 
 } // namespace yb

@@ -78,6 +78,11 @@ class Layout(ctypes.Structure):
     _fields_ = [(n, c_uint32) for n in ("row_len", "pad_id", "bos_id", "eos_id", "flags")]
 
 
+class Windows(ctypes.Structure):
+    """yabpe_windows_t"""
+    _fields_ = [(n, c_void_p) for n in ("rows", "row_doc", "row_start", "row_len", "spans")] + [("n_rows", c_uint64)]
+
+
 class ResumeStats(ctypes.Structure):
     _fields_ = [(n, c_uint64) for n in ("n_unique", "n_long", "tokens")] + [(n, c_double) for n in ("segment_ms", "build_ms")]
 
@@ -111,7 +116,7 @@ SYMBOLS = [
     "yabpe_encode_set_model", "yabpe_encode", "yabpe_encode_spans", "yabpe_encode_dropout", "yabpe_encode_free", "yabpe_encode_stats", "yabpe_encode_checksum",
     "yabpe_decode_set_model", "yabpe_decode", "yabpe_decode_free", "yabpe_decode_stats",
     "yabpe_load_words_resumed", "yabpe_resume_stats",
-    "yabpe_layout_pad", "yabpe_layout_pack", "yabpe_layout_free", "yabpe_layout_stats",
+    "yabpe_layout_pad", "yabpe_layout_pack", "yabpe_layout_windows", "yabpe_layout_free", "yabpe_layout_stats",
     "yabpe_pool_add", "yabpe_pool_get", "yabpe_pool_clear", "yabpe_pool_stats",
     "yabpe_normalize", "yabpe_normalize_free", "yabpe_normalize_stats",
 ]
@@ -179,6 +184,7 @@ def lib() -> ctypes.CDLL:
                                        POINTER(c_uint32)]
         L.yabpe_layout_pack.argtypes = [c_void_p, c_void_p, c_uint64, c_void_p, c_uint32, POINTER(Layout), POINTER(c_void_p), POINTER(c_void_p),
                                         POINTER(c_void_p), POINTER(c_uint64)]
+        L.yabpe_layout_windows.argtypes = [c_void_p, c_void_p, c_uint64, c_void_p, c_uint32, c_void_p, POINTER(Layout), c_uint32, POINTER(Windows)]
         L.yabpe_layout_free.argtypes = [c_void_p]
         L.yabpe_layout_stats.argtypes = [c_void_p, POINTER(LayoutStats)]
         L.yabpe_pool_add.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_uint64]
@@ -581,7 +587,7 @@ class Context:
         self._chk(lib().yabpe_decode_stats(self._h, byref(s)))
         return {f: getattr(s, f) for f, _ in DecodeStats._fields_}
 
-    # -- fixed-shape batches (BBPETokenizer.encode_batch_padded / encode_batch_packed on the device)
+    # -- fixed-shape batches (BBPETokenizer.encode_batch_padded / encode_batch_packed / encode_batch_windows on the device)
     @staticmethod
     def _layout_args(ids, n_ids, doc_starts, n_docs, row_len, pad_id, bos_id, eos_id, flags):
         """ids / doc_starts as decode() takes them -> (keep-alive arrays, ids pointer, n_ids, starts pointer, n_docs, Layout)"""
@@ -637,6 +643,38 @@ class Context:
         di, dd, dp, nr = self.layout_pack(ids, n_ids, doc_starts, n_docs, **kw)
         rl = int(kw.get("row_len", 0))
         return tuple(self.d2h(p, 4 * nr * rl, np.uint32).reshape(nr, rl) if nr else np.zeros((0, rl), np.uint32) for p in (di, dd, dp))
+
+    def layout_windows(self, ids, n_ids: int | None = None, doc_starts=None, n_docs: int | None = None, spans=None, row_len: int = 0,
+                       stride: int = 0, pad_id: int = 0, bos_id: int | None = None, eos_id: int | None = None, pad_left: bool = False,
+                       flags: int = 0):
+        """Rows of row_len with consecutive rows of a document sharing `stride` ids (yabpe_layout_windows); ids, doc_starts and
+        the ids of the layout as layout_pad takes them.  spans: None, or what encode_spans returns next to the ids -- a u64
+        array [n_ids, 2] (staged) or a device address.
+        -> (dev_rows_ptr u32[n_rows * row_len], dev_row_doc_ptr, dev_row_start_ptr, dev_lengths_ptr: u32[n_rows] each,
+        dev_spans_ptr u64[n_rows * row_len * 2] or 0 without spans, n_rows); the buffers live until the next layout call,
+        layout_free() or close()."""
+        _keep, ptr, n, dptr, nd, lay = self._layout_args(ids, n_ids, doc_starts, n_docs, row_len, pad_id, bos_id, eos_id,
+                                                         flags | (LAYOUT_PAD_LEFT if pad_left else 0))
+        if spans is None or isinstance(spans, int):
+            sptr = c_void_p(spans or 0)
+        else:
+            keep_spans = np.ascontiguousarray(spans, dtype=np.uint64)
+            if keep_spans.size != 2 * n:
+                raise ValueError(f"spans must hold one (start, end) per id: {keep_spans.size} values for {n} ids")
+            if not keep_spans.size:
+                keep_spans = np.zeros(2, np.uint64)  # (no ids: never read, but not NULL -- the call still returns spans)
+            sptr = c_void_p(keep_spans.ctypes.data)
+        w = Windows()
+        self._chk(lib().yabpe_layout_windows(self._h, ptr, n, dptr, nd, sptr, byref(lay), int(stride), byref(w)))
+        return w.rows or 0, w.row_doc or 0, w.row_start or 0, w.row_len or 0, w.spans or 0, w.n_rows
+
+    def layout_windows_to_host(self, ids, n_ids: int | None = None, doc_starts=None, n_docs: int | None = None, spans=None, **kw):
+        """-> (rows u32[n_rows, row_len], row_doc, row_start, lengths: u32[n_rows] each) copied to the host, with spans also
+        the slots' spans u64[n_rows, row_len, 2]."""
+        dr, dd, ds, dl, dsp, nr = self.layout_windows(ids, n_ids, doc_starts, n_docs, spans, **kw)
+        rl = int(kw.get("row_len", 0))
+        out = (self.d2h(dr, 4 * nr * rl, np.uint32).reshape(nr, rl),) + tuple(self.d2h(p, 4 * nr, np.uint32) for p in (dd, ds, dl))
+        return out + (self.d2h(dsp, 16 * nr * rl, np.uint64).reshape(nr, rl, 2),) if spans is not None else out
 
     def layout_free(self) -> None:
         self._chk(lib().yabpe_layout_free(self._h))

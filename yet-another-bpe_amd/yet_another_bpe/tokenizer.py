@@ -385,6 +385,63 @@ class BBPETokenizer:
         cut = lambda flat, filler: [(flat + [filler] * fill)[r * seq_len:(r + 1) * seq_len] for r in range(n_rows)]  # noqa: E731
         return cut(stream, pad), cut(doc, 0xFFFFFFFF), cut(pos, 0)
 
+    def _windows_args(self, max_length, stride, pad_id, bos_id, eos_id, padding_side, offsets, dropout, seed):
+        pad, bos, eos, added = self._layout_ids(pad_id, bos_id, eos_id)
+        max_length = self._row_length(max_length, "max_length", added + 1)  # (at least one content slot a row)
+        try:
+            stride = operator.index(stride)
+        except TypeError:
+            raise ValueError(f"stride must be an integer, not {stride!r}") from None
+        if not 0 <= stride < max_length - added:
+            raise ValueError(f"stride must be in [0, {max_length - added - 1}] (max_length less BOS, EOS and one), not {stride}")
+        if padding_side not in ("left", "right"):
+            raise ValueError(f"padding_side must be 'left' or 'right', not {padding_side!r}")
+        if offsets not in (None, "char", "byte"):
+            raise ValueError(f"offsets must be None, 'char' or 'byte', not {offsets!r}")
+        T, seed = self._dropout_threshold(dropout), self._u64(seed, "seed")
+        if offsets is not None and T:
+            raise ValueError("offsets cannot be combined with dropout > 0: the dropout encoder produces no spans")
+        return max_length, stride, pad, bos, eos, added
+
+    def encode_batch_windows(self, texts: Sequence[str], max_length: int, stride: int = 0, *, pad_id: int | None = None,
+                             bos_id: int | None = None, eos_id: int | None = None, padding_side: str = "right",
+                             offsets: str | None = None, dropout: float = 0.0, seed: int = 0):
+        """Rows of max_length ids in which a long text takes several rows (the stride / overflowing-tokens form)
+        -> (rows, row_doc, row_start, lengths), with offsets "char" or "byte" also the spans of every slot.
+        With C = max_length - n_added content slots a row and step = C - stride: row k = 0, 1, ... of text d holds
+        [bos_id] + encode(texts[d])[k * step : k * step + C] + [eos_id], padded with pad_id to max_length at its right end
+        (padding_side "left": at its left end); the last row is the first one with k * step + C >= n.  So every text, an empty
+        one included, has at least one row -- 1 for n <= C, else 1 + ceil((n - C) / step) -- every row but a text's last is
+        full, and consecutive rows of a text share exactly `stride` content ids.  Rows are in text order, in window order
+        within a text.  row_doc[r] = the index into texts, row_start[r] = k * step (the index of the row's first content id in
+        encode(texts[d])), lengths[r] = the row's length before padding, BOS / EOS included.
+        offsets: a fifth result, offsets[r][c] = (start, end) of the slot's id as encode_with_offsets(texts[d], offsets) gives
+        it, (0, 0) in BOS, EOS and pad slots.  dropout > 0 (not with offsets): the content ids are
+        encode_batch_dropout(texts, dropout, seed)."""
+        L, stride, pad, bos, eos, added = self._windows_args(max_length, stride, pad_id, bos_id, eos_id, padding_side, offsets, dropout, seed)
+        if offsets is None:
+            docs = [(ids, None) for ids in self._encode_batch_for_layout(texts, dropout, seed)]
+        else:
+            docs = self.encode_batch_with_offsets(texts, offsets)
+        C = L - added
+        step = C - stride
+        rows, row_doc, row_start, lengths, spans = [], [], [], [], []
+        for d, (ids, sp) in enumerate(docs):
+            for s in range(0, len(ids) + step, step):  # (left by the break below: the first row that reaches the end)
+                seq = ([bos] if bos is not None else []) + list(ids[s:s + C]) + ([eos] if eos is not None else [])
+                fill = L - len(seq)
+                rows.append(seq + [pad] * fill if padding_side == "right" else [pad] * fill + seq)
+                row_doc.append(d)
+                row_start.append(s)
+                lengths.append(len(seq))
+                if sp is not None:
+                    seq_sp = [(0, 0)] * (bos is not None) + [tuple(p) for p in sp[s:s + C]] + [(0, 0)] * (eos is not None)
+                    spans.append(seq_sp + [(0, 0)] * fill if padding_side == "right" else [(0, 0)] * fill + seq_sp)
+                if s + C >= len(ids):
+                    break
+        out = (rows, row_doc, row_start, lengths)
+        return out if offsets is None else out + (spans,)
+
     # ------------------------------------------------------------------ encode on the GPU (yabpe_encode; same ids as encode)
     def _device(self, model: str = "encode"):
         if self._device_ctx is None:
@@ -531,6 +588,28 @@ class BBPETokenizer:
         ctx = self._device()
         di, dd, ni = self._device_encode_for_layout(ctx, inp, dropout, seed)
         return ctx.layout_pack_to_host(di, ni, dd, len(inp[1]), row_len=seq_len, pad_id=pad, bos_id=bos, eos_id=eos, drop_last=drop_last)
+
+    def encode_array_windows(self, texts, max_length: int, stride: int = 0, *, pad_id: int | None = None, bos_id: int | None = None,
+                             eos_id: int | None = None, padding_side: str = "right", offsets: str | None = None,
+                             dropout: float = 0.0, seed: int = 0):
+        """encode_batch_windows(texts, ...), computed on the GPU: yabpe_encode (offsets: yabpe_encode_spans; dropout > 0:
+        yabpe_encode_dropout with this seed), then yabpe_layout_windows on its device results.  `texts` as encode_array takes
+        them.  -> (ids np.uint32[n_rows, max_length], row_doc, row_start, lengths: np.uint32[n_rows] each), with offsets also
+        np.uint64[n_rows, max_length, 2] -- with a normaliser the spans refer to the normalised text, as
+        encode_array_with_offsets' do."""
+        L, stride, pad, bos, eos, _added = self._windows_args(max_length, stride, pad_id, bos_id, eos_id, padding_side, offsets, dropout, seed)
+        inp = self._device_input(texts)
+        if inp is None:
+            out = (np.zeros((0, L), np.uint32),) + tuple(np.zeros(0, np.uint32) for _ in range(3))
+            return out if offsets is None else out + (np.zeros((0, L, 2), np.uint64),)
+        ctx = self._device()
+        kw = dict(row_len=L, stride=stride, pad_id=pad, bos_id=bos, eos_id=eos, pad_left=padding_side == "left")
+        if offsets is None:
+            di, dd, ni = self._device_encode_for_layout(ctx, inp, dropout, seed)
+            return ctx.layout_windows_to_host(di, ni, dd, len(inp[1]), **kw)
+        text, n_bytes, starts = self._device_text(ctx, inp)
+        di, dd, ds, ni = ctx.encode_spans(text, n_bytes, doc_starts=starts, chars=offsets == "char")
+        return ctx.layout_windows_to_host(di, ni, dd, len(inp[1]), ds or np.zeros((0, 2), np.uint64), **kw)
 
     # ------------------------------------------------------------------ decode (tokenizer.py:324-349)
     def decode(self, ids: Sequence[int]) -> str:
