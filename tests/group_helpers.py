@@ -9,6 +9,9 @@ import regex
 from tests.test_pretok_model import EDGE
 
 WIN = 4096  # GRP_WIN / PT_WIN of the kernels
+# Whole-text lengths at which the shared scan code (csrc/yabpe_scan_kernels.h) takes another path: the guarded tail of the piece
+# load and store, the last window, and exactly one tile of 2,048 windows of the carry kernels, and one window more.
+TEXT_LENGTHS = (1, 15, 16, 17, WIN - 1, WIN, WIN + 1, 2048 * WIN, 2048 * WIN + 1)
 
 
 def grouped_pattern(G: int) -> str:

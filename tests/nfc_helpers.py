@@ -9,6 +9,8 @@ import numpy as np
 
 WIN, PIECE, SHORT, CAP = 4096, 16, 32, 16384   # nfc_logic.h (the model test checks them against the header)
 CARRY_TILE = 256 * 8                           # window states per iteration of the carry kernel
+# whole-text lengths at which the shared scan code takes another path (tests/group_helpers.py)
+TEXT_LENGTHS = (1, 15, 16, 17, WIN - 1, WIN, WIN + 1, CARRY_TILE * WIN, CARRY_TILE * WIN + 1)
 
 
 def nfc(s: str) -> str:

@@ -11,6 +11,8 @@ import regex
 WIN = 4096        # PT_WIN of the kernels
 PIECE = 16        # bytes per thread
 CARRY = 2048      # windows per iteration of k_la_carry / k_fn_carry
+# whole-text lengths at which the shared scan code takes another path (tests/group_helpers.py)
+TEXT_LENGTHS = (1, 15, 16, 17, WIN - 1, WIN, WIN + 1, CARRY * WIN, CARRY * WIN + 1)
 GS = (1, 3, 255)
 
 _SUFFIX = r"(?i:'s|'t|'re|'ve|'m|'ll|'d)?"

@@ -3,14 +3,11 @@ memory and no LDS, and the merge kernel keeps the registers of a full-occupancy 
 from __future__ import annotations
 
 import re
-import shutil
-import subprocess
-from pathlib import Path
 
 import pytest
 
-CSRC = Path(__file__).resolve().parent.parent / "yet-another-bpe_amd" / "csrc"
-HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+from tests import kernel_resources
+
 # (itanium names: template kernels carry their arguments)
 KERNELS = [r"_ZN2yb\d+k_drop_wordsILb0EE", r"_ZN2yb\d+k_drop_wordsILb1EE", r"_ZN2yb\d+k_drop_long_listE", r"_ZN2yb\d+k_drop_longE",
            r"_ZN2yb\d+k_drop_long_emitE"]
@@ -18,22 +15,7 @@ KERNELS = [r"_ZN2yb\d+k_drop_wordsILb0EE", r"_ZN2yb\d+k_drop_wordsILb1EE", r"_ZN
 
 @pytest.fixture(scope="module")
 def resources():
-    if not Path(HIPCC).exists():
-        pytest.skip("no hipcc")
-    flags = re.search(r"^CXXFLAGS \?= (.*)$", (CSRC / "Makefile").read_text(), re.M).group(1).split()
-    out = subprocess.run([HIPCC, "--offload-arch=gfx950", *flags, "-Rpass-analysis=kernel-resource-usage", "-c", "-o", "/dev/null", "yabpe.hip"],
-                         cwd=CSRC, capture_output=True, text=True, timeout=900)
-    assert out.returncode == 0, out.stderr[-2000:]
-    res, cur = {}, None
-    for line in out.stderr.splitlines():
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            cur = res.setdefault(m.group(1), {})
-            continue
-        m = re.search(r"remark:\s+(VGPRs|ScratchSize \[bytes/lane\]|Occupancy \[waves/SIMD\]|LDS Size \[bytes/block\]): (\d+)", line)
-        if m and cur is not None:
-            cur[m.group(1).split(" ")[0]] = int(m.group(2))
-    return res
+    return kernel_resources.resources()
 
 
 def test_no_dropout_kernel_uses_scratch_memory_or_lds(resources):

@@ -73,6 +73,28 @@ def test_carry_across_many_windows():
         assert nw + 1 == len(exp) and np.array_equal(off, exp)
 
 
+@pytest.mark.parametrize("n", gh.TEXT_LENGTHS)
+def test_whole_text_lengths(n):
+    """Texts of exactly n bytes: the last piece is 1, 15, 16 bytes or one byte into the next; the text ends one byte short of a
+    window, on it, one byte behind it; the carry scan has exactly one full tile of 2,048 windows, and one window more.  A digit
+    run with one letter in it, as in test_carry_across_many_windows: the starts are computed, and matched with regex where the
+    text is short."""
+    from yet_another_bpe import _native
+
+    brk = min(5 * gh.WIN + 2, n // 2)
+    text = np.full(n, ord("7"), np.uint8)
+    text[brk] = ord("x")
+    exp = np.concatenate([np.arange(0, brk, 3), [brk], np.arange(brk + 1, n, 3), [n]]).astype(np.uint64)
+    if n <= 2 * gh.WIN:
+        words = gh.regex_split(text.tobytes(), 3)
+        assert exp.tolist() == np.concatenate([[0], np.cumsum([len(w) for w in words])]).tolist()
+    with _native.Context() as ctx:
+        ctx.set_option("digit_group", 3)
+        _dt, do, nw = ctx.pretokenize(text)
+        off = ctx.d2h(do, (nw + 1) * 8).view(np.uint64)
+        assert nw + 1 == len(exp) and np.array_equal(off, exp)
+
+
 def test_option_is_read_per_call():
     from tests.test_pretok_model import regex_split as gpt2_split
     from yet_another_bpe import _native

@@ -67,6 +67,23 @@ def test_carry_edge():
             assert check_parts(ctx, [s])["n_dirty"] == 12
 
 
+@pytest.mark.parametrize("n", nh.TEXT_LENGTHS)
+def test_whole_text_lengths(n):
+    """Texts of exactly n bytes (nh.TEXT_LENGTHS) against unicodedata: a train of 4-byte dirty segments up to the last byte, as in
+    nh.carry_cases (short texts are nothing but the train), and the same text with a dirty segment at its first byte."""
+    from yet_another_bpe import _native
+
+    unit = "e\u0301y"  # 4 bytes, not NFC
+    tail = unit * 12 + "z" if n >= 64 else "x" * (n % 4) + unit * (n // 4)
+    strings = ["x" * (n - len(tail.encode())) + tail]
+    if n >= 64:
+        strings.append(unit + strings[0][4:])
+    with _native.Context() as ctx:
+        for s in strings:
+            assert len(s.encode()) == n
+            assert check_parts(ctx, [s])["n_dirty"] == s.count(unit)
+
+
 def test_clean_path_returns_the_input():
     from yet_another_bpe import _native
 

@@ -91,6 +91,31 @@ def test_runs_longer_than_one_carry_iteration():
             assert off == exp, (off[:6], exp)
 
 
+@pytest.mark.parametrize("n", sh.TEXT_LENGTHS)
+def test_whole_text_lengths(n):
+    """Texts of exactly n bytes (sh.TEXT_LENGTHS).  Short ones: newline and whitespace runs cut to n bytes, against regex.  All of
+    them, where they are long enough: the two run kinds of test_runs_longer_than_one_carry_iteration filled to n bytes, offsets
+    computed (and matched with regex where the text is short)."""
+    from yet_another_bpe import _native
+
+    with _native.Context() as ctx:
+        cl100k(ctx, 3)
+        if n <= 2 * sh.WIN:
+            for p in (".\n" + "\n" * n, "\n" + " " * n, "a\n" + " \n" * n, "ab 12 \n\n  x" * n, "\n \n" * n):
+                data = p.encode("utf-8")[:n]
+                assert device_split(ctx, data) == sh.regex_split(data, 3), (n, p[:12])
+        if n >= 4:
+            for data, exp in ((b"." + b"\n" * (n - 3) + b" x", [0, n - 2, n]), (b"\n" + b" " * (n - 2) + b"x", [0, 1, n - 2, n])):
+                assert len(data) == n
+                if n <= 2 * sh.WIN:
+                    words = sh.regex_split(data, 3)
+                    assert exp == np.concatenate([[0], np.cumsum([len(w) for w in words])]).tolist()
+                _dt, do, nw = ctx.pretokenize(data)
+                off = ctx.d2h(do, (nw + 1) * 8).view(np.uint64).tolist()
+                ctx.pretokenize_free()
+                assert off == exp, (n, off[:6], exp)
+
+
 def test_malformed_utf8_reports_the_same_position():
     from yet_another_bpe import _native
 

@@ -101,6 +101,29 @@ def test_chains_longer_than_one_carry_iteration():
             assert len(off) == len(exp) + 1 and off[:-1] == exp, (s[:12], off[:6], exp[:6], off[-4:], exp[-3:])
 
 
+@pytest.mark.parametrize("n", sh.TEXT_LENGTHS)
+def test_whole_text_lengths(n):
+    """Texts of exactly n bytes (sh.TEXT_LENGTHS), for the backward look-ahead scan and the forward function scan.  Short ones:
+    chains of each kind cut to n bytes, against regex.  All of them, where they are long enough: three run kinds of sh.long_runs
+    filled to n bytes, offsets computed (and matched with regex where the text is short)."""
+    from yet_another_bpe import _native
+
+    with _native.Context() as ctx:
+        o200k(ctx, 3)
+        if n <= 2 * sh.WIN:
+            for p in ("aA" + "A" * n, "\n" + " " * n, "a" + "'s" * n, "!" + "\n/" * n, "AB ab's 12345 !?\n\n  x" * n, "a\n" + " \n" * n, "Ab" * n):
+                data = p.encode("utf-8")[:n]
+                assert device_split(ctx, data) == sh.regex_split(data, 3), (n, p[:12])
+        if n >= 6:
+            for s, exp in (("a" + "A" * (n - 2) + "b", [0, 1]), ("\n" + " " * (n - 2) + "x", [0, 1, n - 2]), (". " + "!" * (n - 5) + "\n/a", [0, 1, n - 1])):
+                data = s.encode("utf-8")
+                assert len(data) == n
+                if n <= 2 * sh.WIN:
+                    assert exp == sh.offsets(sh.regex_split(data, 3))[:-1]
+                off = device_offsets(ctx, data)
+                assert off == exp + [n], (n, s[:6], off[:6], exp)
+
+
 def test_malformed_utf8_reports_the_same_position():
     from yet_another_bpe import _native
 

@@ -3,35 +3,19 @@ csrc/yabpe_pretok_kernels.h) is there exactly once and uses no scratch memory.""
 from __future__ import annotations
 
 import re
-import shutil
-import subprocess
-from pathlib import Path
 
 import pytest
 
-CSRC = Path(__file__).resolve().parent.parent / "yet-another-bpe_amd" / "csrc"
-HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+from tests import kernel_resources
+
 KERNELS = [r"_ZN2yb\d+k_grp_windowsE", r"_ZN2yb\d+k_grp_carryE", r"_ZN2yb\d+k_grp_applyE"]
+# kernel -> (VGPRs at most, waves per SIMD at least): what the build reported before the kernels shared yabpe_scan_kernels.h
+BUDGET = {r"_ZN2yb\d+k_grp_windowsE": (26, 8), r"_ZN2yb\d+k_grp_carryE": (24, 8), r"_ZN2yb\d+k_grp_applyE": (34, 8)}
 
 
 @pytest.fixture(scope="module")
 def resources():
-    if not Path(HIPCC).exists():
-        pytest.skip("no hipcc")
-    flags = re.search(r"^CXXFLAGS \?= (.*)$", (CSRC / "Makefile").read_text(), re.M).group(1).split()
-    out = subprocess.run([HIPCC, "--offload-arch=gfx950", *flags, "-Rpass-analysis=kernel-resource-usage", "-c", "-o", "/dev/null", "yabpe.hip"],
-                         cwd=CSRC, capture_output=True, text=True, timeout=900)
-    assert out.returncode == 0, out.stderr[-2000:]
-    res, cur = {}, None
-    for line in out.stderr.splitlines():
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            cur = res.setdefault(m.group(1), {})
-            continue
-        m = re.search(r"remark:\s+(VGPRs|ScratchSize \[bytes/lane\]|Occupancy \[waves/SIMD\]|LDS Size \[bytes/block\]): (\d+)", line)
-        if m and cur is not None:
-            cur[m.group(1).split(" ")[0]] = int(m.group(2))
-    return res
+    return kernel_resources.resources()
 
 
 def test_no_new_kernel_uses_scratch_memory(resources):
@@ -40,3 +24,11 @@ def test_no_new_kernel_uses_scratch_memory(resources):
         assert len(found) == 1, (k, sorted(found))
         for name, r in found.items():
             assert r["ScratchSize"] == 0, (name, r)
+
+
+def test_register_budget(resources):
+    for k, (vgprs, waves) in BUDGET.items():
+        found = {name: r for name, r in resources.items() if re.match(k, name)}
+        assert len(found) == 1, (k, sorted(found))
+        for name, r in found.items():
+            assert r["VGPRs"] <= vgprs and r["Occupancy"] >= waves, (name, r)

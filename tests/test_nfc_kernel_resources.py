@@ -5,36 +5,20 @@ it: a lane of k_nfc_short or k_nfc_long runs the whole segment routine)."""
 from __future__ import annotations
 
 import re
-import shutil
-import subprocess
-from pathlib import Path
 
 import pytest
 
-CSRC = Path(__file__).resolve().parent.parent / "yet-another-bpe_amd" / "csrc"
-HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+from tests import kernel_resources
+
 PER_BYTE = ["k_nfc_class", "k_nfc_windows", "k_nfc_carry", "k_nfc_apply", "k_nfc_copy", "k_nfc_offsets"]
 SEGMENT = ["k_nfc_short", "k_nfc_long"]
+# scan kernel -> (VGPRs at most, waves per SIMD at least): what the build reported before the kernels shared yabpe_scan_kernels.h
+SCAN_BUDGET = {"k_nfc_windows": (48, 8), "k_nfc_carry": (39, 8), "k_nfc_apply": (56, 8)}
 
 
 @pytest.fixture(scope="module")
 def resources():
-    if not Path(HIPCC).exists():
-        pytest.skip("no hipcc")
-    flags = re.search(r"^CXXFLAGS \?= (.*)$", (CSRC / "Makefile").read_text(), re.M).group(1).split()
-    out = subprocess.run([HIPCC, "--offload-arch=gfx950", *flags, "-Rpass-analysis=kernel-resource-usage", "-c", "-o", "/dev/null", "yabpe.hip"],
-                         cwd=CSRC, capture_output=True, text=True, timeout=900)
-    assert out.returncode == 0, out.stderr[-2000:]
-    res, cur = {}, None
-    for line in out.stderr.splitlines():
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            cur = res.setdefault(m.group(1), {})
-            continue
-        m = re.search(r"remark:\s+(VGPRs|ScratchSize \[bytes/lane\]|Occupancy \[waves/SIMD\]|LDS Size \[bytes/block\]): (\d+)", line)
-        if m and cur is not None:
-            cur[m.group(1).split(" ")[0]] = int(m.group(2))
-    return res
+    return kernel_resources.resources()
 
 
 def found(resources, kernel):
@@ -53,3 +37,10 @@ def test_per_byte_kernels_use_no_scratch_memory(resources):
     for k in SEGMENT:
         for name, r in found(resources, k).items():
             print(name, r)
+
+
+def test_scan_kernels_register_budget(resources):
+    for k, (vgprs, waves) in SCAN_BUDGET.items():
+        assert len(found(resources, k)) == 1, (k, sorted(found(resources, k)))
+        for name, r in found(resources, k).items():
+            assert r["VGPRs"] <= vgprs and r["Occupancy"] >= waves, (name, r)

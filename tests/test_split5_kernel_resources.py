@@ -5,14 +5,11 @@ waves is what they get, not what they need; the others stream bytes once and kee
 from __future__ import annotations
 
 import re
-import shutil
-import subprocess
-from pathlib import Path
 
 import pytest
 
-CSRC = Path(__file__).resolve().parent.parent / "yet-another-bpe_amd" / "csrc"
-HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+from tests import kernel_resources
+
 # kernel -> (VGPRs at most, waves per SIMD at least): what the build reports
 BUDGET = {
     r"_ZN2yb\d+k_s5_classE": (26, 8), r"_ZN2yb\d+k_s5_auxE": (20, 8), r"_ZN2yb\d+k_s5_specialE": (13, 8),
@@ -23,22 +20,7 @@ BUDGET = {
 
 @pytest.fixture(scope="module")
 def resources():
-    if not Path(HIPCC).exists():
-        pytest.skip("no hipcc")
-    flags = re.search(r"^CXXFLAGS \?= (.*)$", (CSRC / "Makefile").read_text(), re.M).group(1).split()
-    out = subprocess.run([HIPCC, "--offload-arch=gfx950", *flags, "-Rpass-analysis=kernel-resource-usage", "-c", "-o", "/dev/null", "yabpe.hip"],
-                         cwd=CSRC, capture_output=True, text=True, timeout=900)
-    assert out.returncode == 0, out.stderr[-2000:]
-    res, cur = {}, None
-    for line in out.stderr.splitlines():
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            cur = res.setdefault(m.group(1), {})
-            continue
-        m = re.search(r"remark:\s+(VGPRs|ScratchSize \[bytes/lane\]|Occupancy \[waves/SIMD\]|LDS Size \[bytes/block\]): (\d+)", line)
-        if m and cur is not None:
-            cur[m.group(1).split(" ")[0]] = int(m.group(2))
-    return res
+    return kernel_resources.resources()
 
 
 def one(resources, pattern):

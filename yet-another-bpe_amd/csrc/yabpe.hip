@@ -2767,14 +2767,8 @@ int yabpe_normalize(yabpe_ctx *c, const uint8_t *text, uint64_t n_bytes, const u
     HIPCHK(c, hipMemsetAsync(flags, 0, n + 8, s));
     HIPCHK(c, hipMemsetAsync(ctr + 1, 0, 8, s));
     hipLaunchKernelGGL(k_nfc_class, dim3(cgrid), dim3(BLOCK), 0, s, d_text, (const uint8_t *)marks, meta, n, T, ctr);
-    const unsigned long long n_win = (n + NFC_WIN - 1) / NFC_WIN;
-    const uint32_t wgrid = (uint32_t)std::min<unsigned long long>(n_win, 1u << 20);
     NfcPos *win = nullptr;
-    HIPCHK(c, S.get(&win, n_win));
-    hipLaunchKernelGGL(k_nfc_windows, dim3(wgrid), dim3(BLOCK), 0, s, (const uint8_t *)meta, n, win);
-    hipLaunchKernelGGL(k_nfc_carry, dim3(1), dim3(BLOCK), 0, s, win, n_win);
-    hipLaunchKernelGGL(k_nfc_apply, dim3(wgrid), dim3(BLOCK), 0, s, (const uint8_t *)meta, n, (const NfcPos *)win, flags);
-    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, nfc_find(s, S, meta, flags, n, &win));
     unsigned long long *dstart = nullptr, n_dirty = 0;
     if (pt_offsets(s, S, flags, n, ~0ull, &dstart, &n_dirty) != 0) return fail(c, YABPE_E_HIP, "normaliser: list of dirty segments: %s", hipGetErrorString(hipGetLastError()));
     HIPCHK(c, hipEventRecord(c->norm_ev[2], s));
@@ -2833,6 +2827,7 @@ int yabpe_normalize(yabpe_ctx *c, const uint8_t *text, uint64_t n_bytes, const u
     HIPCHK(c, S.get(&out_off, (uint64_t)np + 1));
     P.shift = shift;
     P.out = out;
+    const uint32_t wgrid = (uint32_t)std::min<unsigned long long>((n + NFC_WIN - 1) / NFC_WIN, 1u << 20);
     hipLaunchKernelGGL(k_nfc_copy, dim3(wgrid), dim3(BLOCK), 0, s, d_text, n, (const unsigned long long *)dstart, (const unsigned long long *)P.dend,
                        (const unsigned long long *)shift, n_dirty, out, ctr + 4);
     hipLaunchKernelGGL(k_nfc_short, dim3(sgrid), dim3(BLOCK), 0, s, P, 1);

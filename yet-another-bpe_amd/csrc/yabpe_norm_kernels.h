@@ -24,10 +24,11 @@
 
 #include "nfc_logic.h"
 #include "yabpe_aux_kernels.h"
+#include "yabpe_scan_kernels.h"
 
 namespace yb {
 
-static_assert(NFC_WIN == BLOCK * NFC_PIECE, "one piece per thread, one window per workgroup");
+static_assert(NFC_WIN == SCAN_WIN && NFC_PIECE == SCAN_PIECE, "one piece per thread, one window per workgroup");
 
 // 16 bytes at g (a multiple of 16) as four words; bytes past the array read as 0.  wide: the array is 16-byte aligned.
 __device__ __forceinline__ void nfc_load(const uint8_t *a, unsigned long long g, unsigned long long n, bool wide, uint32_t w[4]) {
@@ -90,82 +91,51 @@ __global__ __launch_bounds__(BLOCK) void k_nfc_class(const uint8_t *text, const 
     if ((threadIdx.x & 63) == 0 && suspects) atomicAdd(&ctr[1], suspects);
 }
 
-// Exclusive scan of one state per thread over the workgroup, in thread order; *total = all of them combined.  s_w: WPB states.
-__device__ __forceinline__ NfcPos nfc_block_scan(NfcPos mine, NfcPos *s_w, NfcPos *total) {
-    const int lane = threadIdx.x & 63, wib = threadIdx.x >> 6;
-    NfcPos inc = mine;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const NfcPos u = __shfl_up(inc, o);
-        if (lane >= o) inc = nfc_combine(u, inc);
+// The segment start in front of every byte: a forward scan in the three launches of yabpe_scan_kernels.h.
+struct NfcOp {
+    typedef NfcPos State;
+    __device__ __forceinline__ State identity() const { return 0; }
+    __device__ __forceinline__ State combine(State a, State b) const { return nfc_combine(a, b); }
+};
+
+struct NfcPass { // (no finish: k_nfc_apply has a loop of its own, 1 VGPR cheaper than through scan_apply_body)
+    const uint8_t *meta;
+    unsigned long long n;
+    __device__ __forceinline__ ScanPiece load(unsigned long long g) const { return scan_load(meta, g, n, 0); }
+    __device__ __forceinline__ NfcPos state(const ScanPiece &m, unsigned long long g) const {
+        return nfc_piece_state([&](int k) { return m.byte(k); }, g);
     }
-    const NfcPos up = __shfl_up(inc, 1);
-    if (lane == 63) s_w[wib] = inc;
-    __syncthreads();
-    NfcPos before = 0, all = 0;
-#pragma unroll
-    for (int w = 0; w < WPB; ++w) {
-        if (w == wib) before = all;
-        all = nfc_combine(all, s_w[w]);
-    }
-    *total = all;
-    return lane ? nfc_combine(before, up) : before;
-}
+};
 
 __global__ __launch_bounds__(BLOCK) void k_nfc_windows(const uint8_t *meta, unsigned long long n, NfcPos *win) {
-    __shared__ NfcPos s_w[WPB];
-    const unsigned long long n_win = (n + NFC_WIN - 1) / NFC_WIN;
-    for (unsigned long long w = blockIdx.x; w < n_win; w += gridDim.x) {
-        const unsigned long long g = w * NFC_WIN + (unsigned long long)threadIdx.x * NFC_PIECE;
-        uint32_t m[4];
-        nfc_load(meta, g, n, true, m);
-        NfcPos total;
-        (void)nfc_block_scan(nfc_piece_state([&](int k) { return nfc_byte(m, k); }, g), s_w, &total);
-        if (threadIdx.x == 0) win[w] = total;
-        __syncthreads();
-    }
+    scan_windows_body<SCAN_FWD>(NfcOp{}, NfcPass{meta, n}, n, win);
 }
-
-// win[w] = the states of windows 0 .. w - 1 combined (one workgroup)
-constexpr int NFC_CARRY_ITEMS = 8;
 __global__ __launch_bounds__(BLOCK) void k_nfc_carry(NfcPos *win, unsigned long long n_win) {
-    __shared__ NfcPos s_w[WPB];
-    NfcPos carry = 0;
-    for (unsigned long long t0 = 0; t0 < n_win; t0 += BLOCK * NFC_CARRY_ITEMS) {
-        const unsigned long long base = t0 + (unsigned long long)threadIdx.x * NFC_CARRY_ITEMS;
-        NfcPos v[NFC_CARRY_ITEMS], mine = 0;
-#pragma unroll
-        for (int k = 0; k < NFC_CARRY_ITEMS; ++k) {
-            v[k] = base + k < n_win ? win[base + k] : 0ull;
-            mine = nfc_combine(mine, v[k]);
-        }
-        NfcPos total;
-        NfcPos run = nfc_combine(carry, nfc_block_scan(mine, s_w, &total));
-#pragma unroll
-        for (int k = 0; k < NFC_CARRY_ITEMS; ++k) {
-            if (base + k < n_win) win[base + k] = run;
-            run = nfc_combine(run, v[k]);
-        }
-        carry = nfc_combine(carry, total);
-        __syncthreads();
-    }
+    scan_carry_body<SCAN_FWD, SCAN_WHOLE>(NfcOp{}, win, n_win);
 }
-
 // flags[start of its segment] = 1 for every suspect (flags was zeroed; equal stores race harmlessly)
 __global__ __launch_bounds__(BLOCK) void k_nfc_apply(const uint8_t *meta, unsigned long long n, const NfcPos *win, uint8_t *flags) {
     __shared__ NfcPos s_w[WPB];
+    const NfcOp op;
     const unsigned long long n_win = (n + NFC_WIN - 1) / NFC_WIN;
     for (unsigned long long w = blockIdx.x; w < n_win; w += gridDim.x) {
         const unsigned long long g = w * NFC_WIN + (unsigned long long)threadIdx.x * NFC_PIECE;
-        uint32_t m[4];
-        nfc_load(meta, g, n, true, m);
-        auto get = [&](int k) { return nfc_byte(m, k); };
+        const ScanPiece m = scan_load(meta, g, n, 0);
+        auto get = [&](int k) { return m.byte(k); };
         NfcPos total;
-        const NfcPos before = nfc_combine(win[w], nfc_block_scan(nfc_piece_state(get, g), s_w, &total));
-        if ((m[0] | m[1] | m[2] | m[3]) & (NFC_SUSPECT * 0x01010101u))
+        const NfcPos before = nfc_combine(win[w], scan_block<SCAN_FWD>(op, nfc_piece_state(get, g), s_w, &total));
+        if ((m.w[0] | m.w[1] | m.w[2] | m.w[3]) & (NFC_SUSPECT * 0x01010101u))
             nfc_piece_mark(before, get, g, [&](uint64_t p) { flags[p] = 1; });
         __syncthreads();
     }
+}
+
+// The three steps on the meta bytes of n > 0 bytes, left in flight on s.  *win belongs to S.
+inline hipError_t nfc_find(hipStream_t s, Scratch &S, const uint8_t *meta, uint8_t *flags, unsigned long long n, NfcPos **win) {
+    return scan_launch(
+        S, n, win, [&](dim3 grid, NfcPos *w) { hipLaunchKernelGGL(k_nfc_windows, grid, dim3(BLOCK), 0, s, meta, n, w); },
+        [&](NfcPos *w, unsigned long long n_win) { hipLaunchKernelGGL(k_nfc_carry, dim3(1), dim3(BLOCK), 0, s, w, n_win); },
+        [&](dim3 grid, const NfcPos *w) { hipLaunchKernelGGL(k_nfc_apply, grid, dim3(BLOCK), 0, s, meta, n, w, flags); });
 }
 
 // ---------------------------------------------------------------- dirty segments

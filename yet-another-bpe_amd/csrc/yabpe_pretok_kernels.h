@@ -26,6 +26,7 @@
 #include "split4_logic.h"
 #include "split5_logic.h"
 #include "yabpe_aux_kernels.h"
+#include "yabpe_scan_kernels.h"
 
 namespace yb {
 
@@ -190,17 +191,14 @@ __global__ __launch_bounds__(BLOCK) void k_pt4_special(PretokParams P) { pt_spec
 
 // ---------------------------------------------------------------- digit groups (rules and states: group_logic.h)
 // Whether a pre-token starts at a digit depends on how many digits of its run stand in front of it, however many that
-// is: a segmented scan over the text, in three steps of linear work.  A thread owns GRP_PIECE = 16 bytes (one 16-B load
-// of meta and of flags, kept in registers), a workgroup a window of PT_WIN bytes.
+// is: a segmented scan over the text, forward, in the three launches of yabpe_scan_kernels.h.
 //   k_grp_windows   per window: the combined state of its bytes (does it hold a start; digits counted after the last one)
-//   k_grp_carry     one workgroup: exclusive scan of the window states in place (n / PT_WIN of them) -> the state in front
-//                   of every window
-//   k_grp_apply     per window: exclusive scan of the piece states behind that carry, then every thread walks its piece
-//                   and writes its 16 final flags
+//   k_grp_carry     the state in front of every window
+//   k_grp_apply     per piece the state in front of it, then every thread walks its piece and writes its 16 final flags
 // Every read of the flags as k_pt_fused / k_pt_special / k_enc_clear left them happens in the first two kernels or, in
 // k_grp_apply, by the one thread that afterwards writes those same 16 bytes: a start this pass adds is never taken for
 // one it should count from.
-static_assert(PT_WIN == GRP_WIN && PT_WIN == BLOCK * GRP_PIECE, "one piece per thread, one window per workgroup");
+static_assert(PT_WIN == SCAN_WIN && PT_WIN == GRP_WIN && GRP_PIECE == SCAN_PIECE, "one piece per thread, one window per workgroup");
 
 struct GrpPiece {
     uint32_t m[4], f[4]; // 16 meta bytes, 16 flag bytes
@@ -210,7 +208,8 @@ struct GrpPiece {
     }
 };
 
-// the piece at byte g (a multiple of 16); bytes past the text read as meta PT_O, flag 0
+// The piece at byte g (a multiple of 16); bytes past the text read as meta PT_O, flag 0.  (scan_load for two arrays under one
+// tail guard.  Two calls of scan_load, or one loader for N arrays, cost k_nl_apply 3 VGPRs and the tail twice the branches.)
 __device__ __forceinline__ GrpPiece grp_load(const uint8_t *meta, const uint8_t *flags, unsigned long long g, unsigned long long n) {
     GrpPiece p;
     if (g + GRP_PIECE <= n) {
@@ -234,81 +233,44 @@ __device__ __forceinline__ GrpPiece grp_load(const uint8_t *meta, const uint8_t 
     return p;
 }
 
-// Exclusive scan of one state per thread over the workgroup, in thread order; *total = all of them combined.  s_w: WPB
-// states in LDS, free again after the next __syncthreads().
-__device__ __forceinline__ GrpState grp_block_scan(GrpState mine, uint32_t G, GrpState *s_w, GrpState *total) {
-    const int lane = threadIdx.x & 63, wib = threadIdx.x >> 6;
-    GrpState inc = mine;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const GrpState u = __shfl_up(inc, o);
-        if (lane >= o) inc = grp_combine(u, inc, G);
+struct GrpOp {
+    typedef GrpState State;
+    uint32_t G;
+    __device__ __forceinline__ State identity() const { return 0; }
+    __device__ __forceinline__ State combine(State a, State b) const { return grp_combine(a, b, G); }
+};
+
+struct GrpPass { // (no finish: k_grp_apply has a loop of its own)
+    const uint8_t *meta, *flags;
+    unsigned long long n;
+    uint32_t G;
+    __device__ __forceinline__ GrpPiece load(unsigned long long g) const { return grp_load(meta, flags, g, n); }
+    __device__ __forceinline__ GrpState state(const GrpPiece &p, unsigned long long) const {
+        return grp_piece_state([&](int k, uint8_t *m, uint8_t *f) { p.get(k, m, f); }, G);
     }
-    const GrpState up = __shfl_up(inc, 1);
-    if (lane == 63) s_w[wib] = inc;
-    __syncthreads();
-    GrpState before = 0, all = 0;
-#pragma unroll
-    for (int w = 0; w < WPB; ++w) {
-        if (w == wib) before = all;
-        all = grp_combine(all, s_w[w], G);
-    }
-    *total = all;
-    return lane ? grp_combine(before, up, G) : before;
-}
+};
 
 __global__ __launch_bounds__(BLOCK) void k_grp_windows(const uint8_t *meta, const uint8_t *flags, unsigned long long n, uint32_t G,
                                                        GrpState *win) {
-    __shared__ GrpState s_w[WPB];
-    const unsigned long long n_win = (n + PT_WIN - 1) / PT_WIN;
-    for (unsigned long long w = blockIdx.x; w < n_win; w += gridDim.x) {
-        const GrpPiece p = grp_load(meta, flags, w * PT_WIN + (unsigned long long)threadIdx.x * GRP_PIECE, n);
-        const GrpState mine = grp_piece_state([&](int k, uint8_t *m, uint8_t *f) { p.get(k, m, f); }, G);
-        GrpState total;
-        (void)grp_block_scan(mine, G, s_w, &total);
-        if (threadIdx.x == 0) win[w] = total;
-        __syncthreads();
-    }
+    scan_windows_body<SCAN_FWD>(GrpOp{G}, GrpPass{meta, flags, n, G}, n, win);
 }
-
-// win[w] = the states of windows 0 .. w - 1 combined (one workgroup; a tile of BLOCK * GRP_CARRY_ITEMS states per iteration)
-constexpr int GRP_CARRY_ITEMS = 8;
 __global__ __launch_bounds__(BLOCK) void k_grp_carry(GrpState *win, unsigned long long n_win, uint32_t G) {
-    __shared__ GrpState s_w[WPB];
-    GrpState carry = 0;
-    for (unsigned long long t0 = 0; t0 < n_win; t0 += BLOCK * GRP_CARRY_ITEMS) {
-        const unsigned long long base = t0 + (unsigned long long)threadIdx.x * GRP_CARRY_ITEMS;
-        GrpState v[GRP_CARRY_ITEMS], mine = 0;
-#pragma unroll
-        for (int k = 0; k < GRP_CARRY_ITEMS; ++k) {
-            v[k] = base + k < n_win ? win[base + k] : 0u;
-            mine = grp_combine(mine, v[k], G);
-        }
-        GrpState total;
-        GrpState run = grp_combine(carry, grp_block_scan(mine, G, s_w, &total), G);
-#pragma unroll
-        for (int k = 0; k < GRP_CARRY_ITEMS; ++k) {
-            if (base + k < n_win) win[base + k] = run;
-            run = grp_combine(run, v[k], G);
-        }
-        carry = grp_combine(carry, total, G);
-        __syncthreads();
-    }
+    scan_carry_body<SCAN_FWD, SCAN_WHOLE>(GrpOp{G}, win, n_win);
 }
-
 __global__ __launch_bounds__(BLOCK) void k_grp_apply(const uint8_t *meta, uint8_t *flags, unsigned long long n, uint32_t G,
                                                      const GrpState *win) {
     __shared__ GrpState s_w[WPB];
+    const GrpOp op{G};
     const unsigned long long n_win = (n + PT_WIN - 1) / PT_WIN;
     for (unsigned long long w = blockIdx.x; w < n_win; w += gridDim.x) {
         const unsigned long long g = w * PT_WIN + (unsigned long long)threadIdx.x * GRP_PIECE;
         const GrpPiece p = grp_load(meta, flags, g, n);
         auto get = [&](int k, uint8_t *m, uint8_t *f) { p.get(k, m, f); };
         GrpState total;
-        const GrpState before = grp_combine(win[w], grp_block_scan(grp_piece_state(get, G), G, s_w, &total), G);
+        const GrpState before = op.combine(win[w], scan_block<SCAN_FWD>(op, grp_piece_state(get, G), s_w, &total));
         uint32_t o[4] = {0u, 0u, 0u, 0u};
         grp_piece_flags(before, get, [&](int k, uint8_t f) { o[k >> 2] |= (uint32_t)f << ((k & 3) * 8); }, G);
-        if (g + GRP_PIECE <= n) {
+        if (g + GRP_PIECE <= n) { // (scan_store, written out: the call costs this kernel 2 VGPRs, 36 for 34)
             *reinterpret_cast<uint4 *>(flags + g) = make_uint4(o[0], o[1], o[2], o[3]);
         } else {
 #pragma unroll
@@ -321,26 +283,33 @@ __global__ __launch_bounds__(BLOCK) void k_grp_apply(const uint8_t *meta, uint8_
 
 // The three steps on meta / flags of n > 0 bytes, left in flight on s.  G in [1, GRP_MAX].  The window states belong to S.
 inline int pt_group(hipStream_t s, Scratch &S, const uint8_t *meta, uint8_t *flags, unsigned long long n, uint32_t G) {
-    const unsigned long long n_win = (n + PT_WIN - 1) / PT_WIN;
     GrpState *win = nullptr;
-    YB_RET(S.get(&win, n_win));
-    const uint32_t wgrid = (uint32_t)std::min<unsigned long long>(n_win, 1u << 20);
-    hipLaunchKernelGGL(k_grp_windows, dim3(wgrid), dim3(BLOCK), 0, s, meta, (const uint8_t *)flags, n, G, win);
-    hipLaunchKernelGGL(k_grp_carry, dim3(1), dim3(BLOCK), 0, s, win, n_win, G);
-    hipLaunchKernelGGL(k_grp_apply, dim3(wgrid), dim3(BLOCK), 0, s, meta, flags, n, G, (const GrpState *)win);
-    YB_RET(hipGetLastError());
+    YB_RET(scan_launch(
+        S, n, &win, [&](dim3 grid, GrpState *w) { hipLaunchKernelGGL(k_grp_windows, grid, dim3(BLOCK), 0, s, meta, (const uint8_t *)flags, n, G, w); },
+        [&](GrpState *w, unsigned long long n_win) { hipLaunchKernelGGL(k_grp_carry, dim3(1), dim3(BLOCK), 0, s, w, n_win, G); },
+        [&](dim3 grid, const GrpState *w) { hipLaunchKernelGGL(k_grp_apply, grid, dim3(BLOCK), 0, s, meta, flags, n, G, w); }));
     return 0;
 }
 
 // ---------------------------------------------------------------- newline rules of the cl100k pattern (split4_logic.h)
 // Whether a whitespace character behind a newline starts a pre-token (PT4_PENDING) depends on the whole whitespace run around
-// it, however long: two segmented scans, one in each direction, in the three steps and the geometry of the digit groups.
+// it, however long: two segmented scans, one in each direction, packed in one word and one set of launches.
 //   k_nl_windows   per window: one word with both summaries (what the window does to B behind it, to F in front of it)
-//   k_nl_carry     one workgroup: the forward summaries scanned left to right, the backward ones right to left, in place ->
-//                  per window the value of everything in front of it (bits 0-1) and of everything behind it (bits 2-3)
-//   k_nl_apply     per window: both scans over the pieces between those carries, then every thread resolves its 16 flags
-// As in the digit groups, a piece's flags are read as the passes before left them by the thread that then writes them.
+//   k_nl_carry     the forward summaries scanned left to right, then the backward ones right to left -> per window the value
+//                  of everything in front of it (bits 0-1) and of everything behind it (bits 2-3)
+//   k_nl_apply     per piece both values, then every thread resolves its 16 flags
+struct NlOp {
+    typedef NlState State;
+    __device__ __forceinline__ State identity() const { return NL_KEEP; }
+    __device__ __forceinline__ State combine(State a, State b) const { return nl_comb(a, b); }
+    __device__ __forceinline__ State lo(State x) const { return x & NL_MASK; }
+    __device__ __forceinline__ State hi(State x) const { return x >> NL_BWD; } // (a state has four bits)
+    __device__ __forceinline__ State pack(State l, State h) const { return l | (h << NL_BWD); }
+};
 
+// The windows and the apply kernel keep a scan and loops of their own: both directions share every shuffle step and the one
+// barrier.  Built from the halves of scan_block, k_nl_apply comes out 2 VGPRs above this form (49 for 47), so only the carry
+// kernel, which scans one direction at a time, goes through the bodies of yabpe_scan_kernels.h (k_nl_apply takes its scan_store).
 // Exclusive scans of one state per thread over the workgroup: bits 0-1 over the threads in front (thread order), bits 2-3
 // over the threads behind (nearest last).  *total: all of them, in both senses.  s_w: 2 * WPB words.
 __device__ __forceinline__ NlState nl_block_scan(NlState mine, uint32_t *s_w, NlState *total) {
@@ -383,53 +352,10 @@ __global__ __launch_bounds__(BLOCK) void k_nl_windows(const uint8_t *meta, const
         __syncthreads();
     }
 }
-
-// In place.  A thread reads and writes the same BLOCK-strided words in both halves: no word passes between threads through memory.
-constexpr int NL_CARRY_ITEMS = 8;
-constexpr unsigned long long NL_CARRY_TILE = (unsigned long long)BLOCK * NL_CARRY_ITEMS;
 __global__ __launch_bounds__(BLOCK) void k_nl_carry(NlState *win, unsigned long long n_win) {
-    __shared__ uint32_t s_w[2 * WPB];
-    const unsigned long long n_tiles = (n_win + NL_CARRY_TILE - 1) / NL_CARRY_TILE;
-    uint32_t carry = NL_KEEP;
-    for (unsigned long long t = 0; t < n_tiles; ++t) { // forward: left to right
-        const unsigned long long base = t * NL_CARRY_TILE + (unsigned long long)threadIdx.x * NL_CARRY_ITEMS;
-        uint32_t v[NL_CARRY_ITEMS], mine = NL_KEEP;
-#pragma unroll
-        for (int k = 0; k < NL_CARRY_ITEMS; ++k) {
-            v[k] = base + k < n_win ? win[base + k] : 0u;
-            mine = nl_comb(mine, v[k] & NL_MASK);
-        }
-        NlState total;
-        uint32_t run = nl_comb(carry, nl_block_scan(mine, s_w, &total) & NL_MASK);
-#pragma unroll
-        for (int k = 0; k < NL_CARRY_ITEMS; ++k) {
-            if (base + k < n_win) win[base + k] = (v[k] & ~NL_MASK) | run;
-            run = nl_comb(run, v[k] & NL_MASK);
-        }
-        carry = nl_comb(carry, total & NL_MASK);
-        __syncthreads();
-    }
-    carry = NL_KEEP;
-    for (unsigned long long t = n_tiles; t-- > 0;) { // backward: right to left, the nearest window last
-        const unsigned long long base = t * NL_CARRY_TILE + (unsigned long long)threadIdx.x * NL_CARRY_ITEMS;
-        uint32_t v[NL_CARRY_ITEMS], mine = NL_KEEP;
-#pragma unroll
-        for (int k = NL_CARRY_ITEMS - 1; k >= 0; --k) {
-            v[k] = base + k < n_win ? win[base + k] : 0u;
-            mine = nl_comb(mine, (v[k] >> NL_BWD) & NL_MASK);
-        }
-        NlState total;
-        uint32_t run = nl_comb(carry, nl_block_scan(mine << NL_BWD, s_w, &total) >> NL_BWD);
-#pragma unroll
-        for (int k = NL_CARRY_ITEMS - 1; k >= 0; --k) {
-            if (base + k < n_win) win[base + k] = (v[k] & NL_MASK) | (run << NL_BWD);
-            run = nl_comb(run, (v[k] >> NL_BWD) & NL_MASK);
-        }
-        carry = nl_comb(carry, total >> NL_BWD);
-        __syncthreads();
-    }
+    scan_carry_body<SCAN_FWD, SCAN_LO>(NlOp{}, win, n_win);
+    scan_carry_body<SCAN_BWD, SCAN_HI>(NlOp{}, win, n_win);
 }
-
 __global__ __launch_bounds__(BLOCK) void k_nl_apply(const uint8_t *meta, uint8_t *flags, unsigned long long n, const NlState *win) {
     __shared__ uint32_t s_w[2 * WPB];
     const unsigned long long n_win = (n + PT_WIN - 1) / PT_WIN;
@@ -442,27 +368,18 @@ __global__ __launch_bounds__(BLOCK) void k_nl_apply(const uint8_t *meta, uint8_t
         const uint32_t before = nl_comb(edge & NL_MASK, in & NL_MASK), after = nl_comb(edge >> NL_BWD, in >> NL_BWD);
         uint32_t o[4] = {p.f[0], p.f[1], p.f[2], p.f[3]};
         nl_piece_flags(before, after, q, o);
-        if (g + GRP_PIECE <= n) {
-            *reinterpret_cast<uint4 *>(flags + g) = make_uint4(o[0], o[1], o[2], o[3]);
-        } else {
-#pragma unroll
-            for (int k = 0; k < GRP_PIECE; ++k)
-                if (g + k < n) flags[g + k] = (uint8_t)(o[k >> 2] >> ((k & 3) * 8));
-        }
+        scan_store(flags, g, n, o);
         __syncthreads();
     }
 }
 
 // The three steps on meta / flags of n > 0 bytes, left in flight on s.  The window states belong to S.
 inline int pt_newlines(hipStream_t s, Scratch &S, const uint8_t *meta, uint8_t *flags, unsigned long long n) {
-    const unsigned long long n_win = (n + PT_WIN - 1) / PT_WIN;
     NlState *win = nullptr;
-    YB_RET(S.get(&win, n_win));
-    const uint32_t wgrid = (uint32_t)std::min<unsigned long long>(n_win, 1u << 20);
-    hipLaunchKernelGGL(k_nl_windows, dim3(wgrid), dim3(BLOCK), 0, s, meta, (const uint8_t *)flags, n, win);
-    hipLaunchKernelGGL(k_nl_carry, dim3(1), dim3(BLOCK), 0, s, win, n_win);
-    hipLaunchKernelGGL(k_nl_apply, dim3(wgrid), dim3(BLOCK), 0, s, meta, flags, n, (const NlState *)win);
-    YB_RET(hipGetLastError());
+    YB_RET(scan_launch(
+        S, n, &win, [&](dim3 grid, NlState *w) { hipLaunchKernelGGL(k_nl_windows, grid, dim3(BLOCK), 0, s, meta, (const uint8_t *)flags, n, w); },
+        [&](NlState *w, unsigned long long n_win) { hipLaunchKernelGGL(k_nl_carry, dim3(1), dim3(BLOCK), 0, s, w, n_win); },
+        [&](dim3 grid, const NlState *w) { hipLaunchKernelGGL(k_nl_apply, grid, dim3(BLOCK), 0, s, meta, flags, n, w); }));
     return 0;
 }
 
@@ -471,12 +388,11 @@ inline int pt_newlines(hipStream_t s, Scratch &S, const uint8_t *meta, uint8_t *
 // look-ahead bits by one backward scan, and the characters -- functions over the scanner's 13 states -- are scanned forward.
 //   k_s5_class     text, chunk marks -> meta (class, sub-class, continuation, chunk mark; UTF-8 validation as k_pt_fused does it).
 //                  The marks are read from an array of their own, so no thread reads a byte another one writes.
-//   k_la_windows / k_la_carry / k_la_apply   meta -> meta with PT5_LA: F and UE, scanned right to left (geometry of k_nl_*)
+//   k_la_windows / k_la_carry / k_la_apply   meta -> meta with PT5_LA: F and UE, scanned right to left
 //   k_s5_aux       text, meta -> flags = the aux byte (class of the next character, contraction length)
 //   k_s5_special   text, meta -> A5_HEAD / A5_LAST on every occurrence of a special (training pattern only)
 //   k_fn_windows / k_fn_carry / k_fn_apply   meta, aux -> flags: per window the composed function; the functions in front of
 //                  every window; per piece the state in front of it, then its 16 flags (0, 1, GRP_INSIDE)
-// As in the digit groups, a piece is read as the passes before left it by the thread that then writes it.
 
 __global__ __launch_bounds__(BLOCK) void k_s5_class(const uint8_t *text, const uint8_t *marks, uint8_t *meta, unsigned long long n,
                                                     const uint8_t *cls5, unsigned long long *err) {
@@ -496,109 +412,32 @@ __global__ __launch_bounds__(BLOCK) void k_s5_class(const uint8_t *text, const u
     if (bad_pos != ~0ull) atomicMin(err, bad_pos);
 }
 
-// 16 meta bytes at g (a multiple of 16); bytes past the text read as PT_O
-__device__ __forceinline__ void s5_load(const uint8_t *a, unsigned long long g, unsigned long long n, uint32_t fill, uint32_t w[4]) {
-    if (g + GRP_PIECE <= n) {
-        const uint4 x = *reinterpret_cast<const uint4 *>(a + g);
-        w[0] = x.x; w[1] = x.y; w[2] = x.z; w[3] = x.w;
-    } else {
-#pragma unroll
-        for (int k = 0; k < 4; ++k) w[k] = fill * 0x01010101u;
-#pragma unroll
-        for (int k = 0; k < GRP_PIECE; ++k)
-            if (g + k < n) {
-                const int sh = (k & 3) * 8;
-                w[k >> 2] = (w[k >> 2] & ~(0xFFu << sh)) | ((uint32_t)a[g + k] << sh);
-            }
-    }
-}
+struct LaOp {
+    typedef uint32_t State;
+    __device__ __forceinline__ State identity() const { return LA_KEEP; }
+    __device__ __forceinline__ State combine(State a, State b) const { return la_comb(a, b); }
+};
 
-__device__ __forceinline__ void s5_store(uint8_t *a, unsigned long long g, unsigned long long n, const uint32_t w[4]) {
-    if (g + GRP_PIECE <= n) {
-        *reinterpret_cast<uint4 *>(a + g) = make_uint4(w[0], w[1], w[2], w[3]);
-    } else {
-#pragma unroll
-        for (int k = 0; k < GRP_PIECE; ++k)
-            if (g + k < n) a[g + k] = (uint8_t)(w[k >> 2] >> ((k & 3) * 8));
+struct LaPass {
+    const uint8_t *meta;
+    uint8_t *out; // the meta bytes again (k_la_apply)
+    unsigned long long n;
+    __device__ __forceinline__ ScanPiece load(unsigned long long g) const { return scan_load(meta, g, n, PT_O); }
+    __device__ __forceinline__ uint32_t state(const ScanPiece &m, unsigned long long) const { return la_piece_state(m.w); }
+    __device__ __forceinline__ void finish(uint32_t after, ScanPiece &m, unsigned long long g) const {
+        la_piece_bits(after, m.w);
+        scan_store(out, g, n, m.w);
     }
-}
-
-// Exclusive scan of one look-ahead value per thread over the workgroup, over the threads BEHIND (nearest last); *total: all of
-// them.  s_w: WPB words.
-__device__ __forceinline__ uint32_t la_block_scan(uint32_t mine, uint32_t *s_w, uint32_t *total) {
-    const int lane = threadIdx.x & 63, wib = threadIdx.x >> 6;
-    uint32_t b = mine;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const uint32_t ub = __shfl_down(b, o);
-        if (lane + o < 64) b = la_comb(ub, b);
-    }
-    const uint32_t pb = __shfl_down(b, 1);
-    if (lane == 0) s_w[wib] = b;
-    __syncthreads();
-    uint32_t bb = LA_KEEP, ab = LA_KEEP;
-#pragma unroll
-    for (int w = WPB - 1; w >= 0; --w) {
-        if (w == wib) bb = ab;
-        ab = la_comb(ab, s_w[w]);
-    }
-    *total = ab;
-    return lane < 63 ? la_comb(bb, pb) : bb;
-}
+};
 
 __global__ __launch_bounds__(BLOCK) void k_la_windows(const uint8_t *meta, unsigned long long n, uint32_t *win) {
-    __shared__ uint32_t s_w[WPB];
-    const unsigned long long n_win = (n + PT_WIN - 1) / PT_WIN;
-    for (unsigned long long w = blockIdx.x; w < n_win; w += gridDim.x) {
-        uint32_t m[4];
-        s5_load(meta, w * PT_WIN + (unsigned long long)threadIdx.x * GRP_PIECE, n, PT_O, m);
-        uint32_t total;
-        (void)la_block_scan(la_piece_state(m), s_w, &total);
-        if (threadIdx.x == 0) win[w] = total;
-        __syncthreads();
-    }
+    scan_windows_body<SCAN_BWD>(LaOp{}, LaPass{meta, nullptr, n}, n, win);
 }
-
-// win[w] = the windows behind w combined, in place (one workgroup; right to left, a tile of BLOCK * 8 windows per iteration)
-constexpr int S5_CARRY_ITEMS = 8;
-constexpr unsigned long long S5_CARRY_TILE = (unsigned long long)BLOCK * S5_CARRY_ITEMS;
 __global__ __launch_bounds__(BLOCK) void k_la_carry(uint32_t *win, unsigned long long n_win) {
-    __shared__ uint32_t s_w[WPB];
-    const unsigned long long n_tiles = (n_win + S5_CARRY_TILE - 1) / S5_CARRY_TILE;
-    uint32_t carry = LA_KEEP;
-    for (unsigned long long t = n_tiles; t-- > 0;) {
-        const unsigned long long base = t * S5_CARRY_TILE + (unsigned long long)threadIdx.x * S5_CARRY_ITEMS;
-        uint32_t v[S5_CARRY_ITEMS], mine = LA_KEEP;
-#pragma unroll
-        for (int k = S5_CARRY_ITEMS - 1; k >= 0; --k) {
-            v[k] = base + k < n_win ? win[base + k] : LA_KEEP;
-            mine = la_comb(mine, v[k]);
-        }
-        uint32_t total;
-        uint32_t run = la_comb(carry, la_block_scan(mine, s_w, &total));
-#pragma unroll
-        for (int k = S5_CARRY_ITEMS - 1; k >= 0; --k) {
-            if (base + k < n_win) win[base + k] = run;
-            run = la_comb(run, v[k]);
-        }
-        carry = la_comb(carry, total);
-        __syncthreads();
-    }
+    scan_carry_body<SCAN_BWD, SCAN_WHOLE>(LaOp{}, win, n_win);
 }
-
 __global__ __launch_bounds__(BLOCK) void k_la_apply(uint8_t *meta, unsigned long long n, const uint32_t *win) {
-    __shared__ uint32_t s_w[WPB];
-    const unsigned long long n_win = (n + PT_WIN - 1) / PT_WIN;
-    for (unsigned long long w = blockIdx.x; w < n_win; w += gridDim.x) {
-        const unsigned long long g = w * PT_WIN + (unsigned long long)threadIdx.x * GRP_PIECE;
-        uint32_t m[4];
-        s5_load(meta, g, n, PT_O, m);
-        uint32_t total;
-        const uint32_t after = la_comb(win[w], la_block_scan(la_piece_state(m), s_w, &total));
-        la_piece_bits(after, m);
-        s5_store(meta, g, n, m);
-        __syncthreads();
-    }
+    scan_apply_body<SCAN_BWD>(LaOp{}, LaPass{meta, meta, n}, n, win);
 }
 
 // the aux byte of every byte: the rules look at most 4 bytes ahead (the next character; two suffix letters)
@@ -635,76 +474,32 @@ __global__ __launch_bounds__(BLOCK) void k_s5_special(PretokParams P) {
     }
 }
 
-// Exclusive scan of one function per thread over the workgroup, in thread order; *total = all of them composed.  s_w: WPB.
-__device__ __forceinline__ S5Fn s5_block_scan(S5Fn mine, S5Fn *s_w, S5Fn *total) {
-    const int lane = threadIdx.x & 63, wib = threadIdx.x >> 6;
-    S5Fn inc = mine;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const S5Fn u = __shfl_up(inc, o);
-        if (lane >= o) inc = s5_then(u, inc);
+struct FnOp {
+    typedef S5Fn State;
+    __device__ __forceinline__ State identity() const { return S5_IDENTITY; }
+    __device__ __forceinline__ State combine(State a, State b) const { return s5_then(a, b); }
+};
+
+struct FnPass {
+    const uint8_t *meta, *aux;
+    uint8_t *out; // the aux bytes become the flags (k_fn_apply)
+    unsigned long long n;
+    __device__ __forceinline__ GrpPiece load(unsigned long long g) const { return grp_load(meta, aux, g, n); }
+    __device__ __forceinline__ S5Fn state(const GrpPiece &p, unsigned long long) const { return s5_piece_fn(p.m, p.f); }
+    __device__ __forceinline__ void finish(S5Fn before, GrpPiece &p, unsigned long long g) const {
+        s5_piece_flags(s5_apply(before, S5_S0), p.m, p.f); // (whatever stands in front of the text: its first byte is a constant)
+        scan_store(out, g, n, p.f);
     }
-    const S5Fn up = __shfl_up(inc, 1);
-    if (lane == 63) s_w[wib] = inc;
-    __syncthreads();
-    S5Fn before = S5_IDENTITY, all = S5_IDENTITY;
-#pragma unroll
-    for (int w = 0; w < WPB; ++w) {
-        if (w == wib) before = all;
-        all = s5_then(all, s_w[w]);
-    }
-    *total = all;
-    return lane ? s5_then(before, up) : before;
-}
+};
 
 __global__ __launch_bounds__(BLOCK) void k_fn_windows(const uint8_t *meta, const uint8_t *aux, unsigned long long n, S5Fn *win) {
-    __shared__ S5Fn s_w[WPB];
-    const unsigned long long n_win = (n + PT_WIN - 1) / PT_WIN;
-    for (unsigned long long w = blockIdx.x; w < n_win; w += gridDim.x) {
-        const GrpPiece p = grp_load(meta, aux, w * PT_WIN + (unsigned long long)threadIdx.x * GRP_PIECE, n);
-        S5Fn total;
-        (void)s5_block_scan(s5_piece_fn(p.m, p.f), s_w, &total);
-        if (threadIdx.x == 0) win[w] = total;
-        __syncthreads();
-    }
+    scan_windows_body<SCAN_FWD>(FnOp{}, FnPass{meta, aux, nullptr, n}, n, win);
 }
-
-// win[w] = the functions of windows 0 .. w - 1 composed, in place (one workgroup; a tile of BLOCK * 8 windows per iteration)
 __global__ __launch_bounds__(BLOCK) void k_fn_carry(S5Fn *win, unsigned long long n_win) {
-    __shared__ S5Fn s_w[WPB];
-    S5Fn carry = S5_IDENTITY;
-    for (unsigned long long t0 = 0; t0 < n_win; t0 += S5_CARRY_TILE) {
-        const unsigned long long base = t0 + (unsigned long long)threadIdx.x * S5_CARRY_ITEMS;
-        S5Fn v[S5_CARRY_ITEMS], mine = S5_IDENTITY;
-#pragma unroll
-        for (int k = 0; k < S5_CARRY_ITEMS; ++k) {
-            v[k] = base + k < n_win ? win[base + k] : S5_IDENTITY;
-            mine = s5_then(mine, v[k]);
-        }
-        S5Fn total;
-        S5Fn run = s5_then(carry, s5_block_scan(mine, s_w, &total));
-#pragma unroll
-        for (int k = 0; k < S5_CARRY_ITEMS; ++k) {
-            if (base + k < n_win) win[base + k] = run;
-            run = s5_then(run, v[k]);
-        }
-        carry = s5_then(carry, total);
-        __syncthreads();
-    }
+    scan_carry_body<SCAN_FWD, SCAN_WHOLE>(FnOp{}, win, n_win);
 }
-
 __global__ __launch_bounds__(BLOCK) void k_fn_apply(const uint8_t *meta, uint8_t *flags, unsigned long long n, const S5Fn *win) {
-    __shared__ S5Fn s_w[WPB];
-    const unsigned long long n_win = (n + PT_WIN - 1) / PT_WIN;
-    for (unsigned long long w = blockIdx.x; w < n_win; w += gridDim.x) {
-        const unsigned long long g = w * PT_WIN + (unsigned long long)threadIdx.x * GRP_PIECE;
-        GrpPiece p = grp_load(meta, flags, g, n);
-        S5Fn total;
-        const S5Fn before = s5_then(win[w], s5_block_scan(s5_piece_fn(p.m, p.f), s_w, &total));
-        s5_piece_flags(s5_apply(before, S5_S0), p.m, p.f); // (whatever stands in front of the text: its first byte is a constant)
-        s5_store(flags, g, n, p.f);
-        __syncthreads();
-    }
+    scan_apply_body<SCAN_FWD>(FnOp{}, FnPass{meta, flags, flags, n}, n, win);
 }
 
 // All passes of the pattern on the chunk marks `marks` (PT_CHUNK0 or 0 per byte) of n > 0 bytes: meta and flags (0, 1,
@@ -712,26 +507,23 @@ __global__ __launch_bounds__(BLOCK) void k_fn_apply(const uint8_t *meta, uint8_t
 // (encode: the pieces are texts of their own).  The window values belong to S.
 inline int pt_split5(hipStream_t s, Scratch &S, const uint8_t *text, const uint8_t *marks, uint8_t *meta, uint8_t *flags, unsigned long long n,
                      const uint8_t *cls5, unsigned long long *err, const PtSpecials &sp) {
-    const unsigned long long n_win = (n + PT_WIN - 1) / PT_WIN;
     uint32_t *la = nullptr;
     S5Fn *fn = nullptr;
-    YB_RET(S.get(&la, n_win));
-    YB_RET(S.get(&fn, n_win));
     const uint32_t grid = (uint32_t)std::min<unsigned long long>((n + BLOCK - 1) / BLOCK, 1u << 20);
-    const uint32_t wgrid = (uint32_t)std::min<unsigned long long>(n_win, 1u << 20);
     hipLaunchKernelGGL(k_s5_class, dim3(grid), dim3(BLOCK), 0, s, text, marks, meta, n, cls5, err);
-    hipLaunchKernelGGL(k_la_windows, dim3(wgrid), dim3(BLOCK), 0, s, (const uint8_t *)meta, n, la);
-    hipLaunchKernelGGL(k_la_carry, dim3(1), dim3(BLOCK), 0, s, la, n_win);
-    hipLaunchKernelGGL(k_la_apply, dim3(wgrid), dim3(BLOCK), 0, s, meta, n, (const uint32_t *)la);
+    YB_RET(scan_launch(
+            S, n, &la, [&](dim3 wgrid, uint32_t *w) { hipLaunchKernelGGL(k_la_windows, wgrid, dim3(BLOCK), 0, s, (const uint8_t *)meta, n, w); },
+            [&](uint32_t *w, unsigned long long n_win) { hipLaunchKernelGGL(k_la_carry, dim3(1), dim3(BLOCK), 0, s, w, n_win); },
+            [&](dim3 wgrid, const uint32_t *w) { hipLaunchKernelGGL(k_la_apply, wgrid, dim3(BLOCK), 0, s, meta, n, w); }));
     hipLaunchKernelGGL(k_s5_aux, dim3(grid), dim3(BLOCK), 0, s, text, (const uint8_t *)meta, flags, n);
     if (sp.n) {
         const PretokParams P{text, meta, flags, n, cls5, err, sp, 0};
         hipLaunchKernelGGL(k_s5_special, dim3(grid), dim3(BLOCK), 0, s, P);
     }
-    hipLaunchKernelGGL(k_fn_windows, dim3(wgrid), dim3(BLOCK), 0, s, (const uint8_t *)meta, (const uint8_t *)flags, n, fn);
-    hipLaunchKernelGGL(k_fn_carry, dim3(1), dim3(BLOCK), 0, s, fn, n_win);
-    hipLaunchKernelGGL(k_fn_apply, dim3(wgrid), dim3(BLOCK), 0, s, (const uint8_t *)meta, flags, n, (const S5Fn *)fn);
-    YB_RET(hipGetLastError());
+    YB_RET(scan_launch(
+        S, n, &fn, [&](dim3 wgrid, S5Fn *w) { hipLaunchKernelGGL(k_fn_windows, wgrid, dim3(BLOCK), 0, s, (const uint8_t *)meta, (const uint8_t *)flags, n, w); },
+        [&](S5Fn *w, unsigned long long n_win) { hipLaunchKernelGGL(k_fn_carry, dim3(1), dim3(BLOCK), 0, s, w, n_win); },
+        [&](dim3 wgrid, const S5Fn *w) { hipLaunchKernelGGL(k_fn_apply, wgrid, dim3(BLOCK), 0, s, (const uint8_t *)meta, flags, n, w); }));
     return 0;
 }
 
