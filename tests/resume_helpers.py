@@ -9,6 +9,7 @@ from pathlib import Path
 
 import numpy as np
 
+from tests import helpers
 from yet_another_bpe import _native
 
 HM = Path(__file__).resolve().parent / "hostmodel"
@@ -34,7 +35,8 @@ def literal_replay(word: bytes, merges) -> tuple:
     for left, right in merges:
         if len(w) < 2:
             break
-        w = replace_pair(w, left, right)
+        if left in w:  # (otherwise replace_pair returns w as it is)
+            w = replace_pair(w, left, right)
     return w
 
 
@@ -101,6 +103,26 @@ def resume_naive(words, base, merges, budget: int, min_frequency: int):
         seg[literal_replay(w, merges)] += f
     vocab, new = naive_continue(seg, {t: i for i, t in enumerate(toks)}, budget, min_frequency)
     return vocab, list(merges) + new
+
+
+def resumed_train(words, freq, base, merges, budget, min_frequency, dedup=False, check=True, options=None):
+    """-> (vocab, all merges, resume stats, stats) of a fresh context that continues from (base, merges) on the pooled words
+    (GPU).  options: yabpe_set_option pairs set before the vocabulary (id_bits = 32: the u32 resumed load)."""
+    toks, triples = _native.merge_triples(base, merges)
+    flat, off = helpers.flatten(words)
+    with _native.Context() as ctx:
+        for k, v in (options or {}).items():
+            ctx.set_option(k, v)
+        ctx.set_vocab(toks)
+        ctx.load_words_resumed(flat, off, freq, triples, dedup=dedup)
+        if check:
+            assert ctx.verify_table() == 0
+        left, right, merged, _count = ctx.train(budget, min_frequency)
+        if check:
+            assert ctx.verify_table() == 0
+        rs, st = ctx.resume_stats(), ctx.stats()
+    vocab, new = _native.decode_merges(toks, left, right, merged)
+    return vocab, list(merges) + new, rs, st
 
 
 # ---------------------------------------------------------------- the CPU model of the device's walk

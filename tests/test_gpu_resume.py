@@ -20,24 +20,7 @@ SP = ["<|endoftext|>"]
 E_INVALID, E_CAPACITY = -1, -4
 
 
-def resumed_train(words, freq, base, merges, budget, min_frequency, dedup=False, check=True):
-    """-> (vocab, all merges, resume stats, stats) of a fresh context that continues from (base, merges) on the pooled words."""
-    from yet_another_bpe import _native
-    from yet_another_bpe.trainer import BBPETrainer
-
-    toks, triples = _native.merge_triples(base, merges)
-    flat, off = helpers.flatten(words)
-    with _native.Context() as ctx:
-        ctx.set_vocab(toks)
-        ctx.load_words_resumed(flat, off, freq, triples, dedup=dedup)
-        if check:
-            assert ctx.verify_table() == 0
-        left, right, merged, _count = ctx.train(budget, min_frequency)
-        if check:
-            assert ctx.verify_table() == 0
-        rs, st = ctx.resume_stats(), ctx.stats()
-    vocab, new = BBPETrainer._decode_merges(toks, left, right, merged)
-    return vocab, list(merges) + new, rs, st
+resumed_train = rh.resumed_train  # (shared with tests/test_gpu_id32_resume.py, which sets id_bits = 32)
 
 
 @pytest.mark.parametrize("v1", [1, 100, 743, 4439, 8000])
