@@ -88,8 +88,7 @@ Rccl *rccl() {
     return r.h ? &r : nullptr;
 }
 
-constexpr uint32_t MAX_APPLY_BLOCKS = 8192;
-constexpr uint32_t MAX_LISTS = 2048;  // the sparse launch's scan workgroups at most (blk_read slots)
+// (MAX_APPLY_BLOCKS, MAX_LISTS: train_rules.h)
 // blk_read: [0, MAX_LISTS) tiles read, [MAX_LISTS, 2 MAX_LISTS) second-round pieces taken, then the piece counter's own 128-B line
 constexpr uint32_t BLK_READ_WORDS = 2 * MAX_LISTS + 16;
 thread_local std::string g_create_error;
@@ -206,7 +205,6 @@ struct yabpe_ctx {
     uint32_t blk_used = 0;                    // largest grid that wrote blk_stats since they were last folded
     bool split_mode = false;         // the sparse form (skip index + batches of merges per launch) instead of the streaming one
     uint32_t kmax_now = 1;           // DevState::kmax as last written
-    uint32_t rec_n_live = 0;         // record entries to keep when the record arrays grow
     std::vector<float> ev_scan_us;
     // skip index
     unsigned long long *sig = nullptr;
@@ -459,9 +457,7 @@ int cand_rebuild(yabpe_ctx *c, unsigned long long best_count) {
 }
 
 uint32_t count_grid(yabpe_ctx *c) {
-    uint32_t want = (c->n_tiles + WPB - 1) / WPB;
-    uint32_t cap = (uint32_t)optv(c, "apply_blocks", (int64_t)c->n_cu * c->apply_occ);
-    return std::max(1u, std::min(std::min(want, cap), MAX_APPLY_BLOCKS));
+    return count_grid_rule(c->n_tiles, (uint32_t)c->n_cu, (uint32_t)c->apply_occ, optv(c, "apply_blocks", OPT_UNSET));
 }
 
 int fold_stats(yabpe_ctx *c) {
@@ -915,6 +911,238 @@ int check_starts(yabpe_ctx *c, const uint64_t *starts, uint32_t n, uint64_t limi
         if (starts[d] < starts[d - 1] || starts[d] > limit) return fail(c, YABPE_E_INVALID, "document starts must ascend inside the %s", what);
     return 0;
 }
+
+// ---- what the u16 and the u32 drivers share (yabpe_id32_host.h): the differences between the two stay with the callers
+// N timing events of one call: destroyed on every way out
+template <int N>
+struct Events {
+    hipEvent_t e[N] = {};
+    hipError_t create() {
+        for (hipEvent_t &x : e) {
+            const hipError_t r = hipEventCreate(&x);
+            if (r != hipSuccess) return r;
+        }
+        return hipSuccess;
+    }
+    ~Events() {
+        for (hipEvent_t x : e)
+            if (x) (void)hipEventDestroy(x);
+    }
+};
+
+// The base vocabulary on the host: every token's bytes at a multiple of 4 in the pool (new tokens' bytes are written four
+// at a time); order[r] = the id of byte-order rank r; one TokRec per id with rank 0.
+struct BaseVocab {
+    std::vector<uint32_t> off, len, order;
+    std::vector<uint8_t> pool;
+    std::vector<TokRec> rec;
+};
+void base_vocab_pack(const uint8_t *tok_bytes, const uint32_t *tok_off, uint32_t n_tokens, BaseVocab &V) {
+    V.off.resize(n_tokens); V.len.resize(n_tokens); V.order.resize(n_tokens);
+    for (uint32_t i = 0; i < n_tokens; ++i) {
+        V.len[i] = tok_off[i + 1] - tok_off[i];
+        V.off[i] = (uint32_t)V.pool.size();
+        V.pool.insert(V.pool.end(), tok_bytes + tok_off[i], tok_bytes + tok_off[i + 1]);
+        V.pool.resize((V.pool.size() + 3) & ~(size_t)3, 0);
+        V.order[i] = i;
+    }
+}
+int base_vocab_index(yabpe_ctx *c, BaseVocab &V) {
+    const uint32_t n_tokens = (uint32_t)V.len.size();
+    auto cmp = [&](uint32_t x, uint32_t y) {
+        uint32_t n = std::min(V.len[x], V.len[y]);
+        int d = memcmp(V.pool.data() + V.off[x], V.pool.data() + V.off[y], n);
+        if (d) return d < 0;
+        return V.len[x] < V.len[y];
+    };
+    std::sort(V.order.begin(), V.order.end(), cmp);
+    for (uint32_t r = 1; r < n_tokens; ++r)
+        if (!cmp(V.order[r - 1], V.order[r])) return fail(c, YABPE_E_INVALID, "duplicate token bytes in the base vocabulary (trainer.py:130)");
+    V.rec.resize(n_tokens);
+    for (uint32_t i = 0; i < n_tokens; ++i) {
+        V.rec[i].rank = 0;
+        V.rec[i].len = V.len[i];
+        V.rec[i].hash = yb_hash_bytes(V.pool.data() + V.off[i], V.len[i]);
+        V.rec[i].pre8 = yb_pre8(V.pool.data() + V.off[i], V.len[i]);
+        V.rec[i].pad = 0;
+    }
+    return 0;
+}
+// the byte-string set of tokens [0, n_tokens) in a fresh array of vset_cap slots
+int upload_vset(yabpe_ctx *c, const std::vector<TokRec> &rec, uint32_t n_tokens, uint32_t vset_cap) {
+    std::vector<unsigned long long> vset(vset_cap, VSET_EMPTY);
+    const uint32_t mask = vset_cap - 1;
+    for (uint32_t i = 0; i < n_tokens; ++i) {
+        uint32_t s = yb_vset_home(rec[i].hash, rec[i].len) & mask;
+        while (vset[s] != VSET_EMPTY) s = (s + 1) & mask;
+        vset[s] = yb_vset_entry(i, rec[i].hash);
+    }
+    dfree(c->tt.vset);
+    c->tt.vset = nullptr;
+    TRY(dmalloc(c, &c->tt.vset, vset_cap));
+    HIPCHK(c, hipMemcpy(c->tt.vset, vset.data(), (size_t)vset_cap * 8, hipMemcpyHostToDevice));
+    c->tt.vset_mask = mask;
+    return 0;
+}
+// the token table on the device at the capacities the caller chose, and a state that knows nothing but these tokens
+int base_vocab_upload(yabpe_ctx *c, const BaseVocab &V, uint32_t pool_cap, uint32_t tok_cap, uint32_t vset_cap) {
+    const uint32_t n_tokens = (uint32_t)V.len.size();
+    dfree(c->tt.pool); dfree(c->tt.off); dfree(c->tt.len); dfree(c->tt.rec);
+    c->tt.pool = nullptr; c->tt.off = c->tt.len = nullptr; c->tt.rec = nullptr;
+    TRY(dmalloc(c, &c->tt.pool, pool_cap));
+    TRY(dmalloc(c, &c->tt.off, tok_cap));
+    TRY(dmalloc(c, &c->tt.len, tok_cap));
+    TRY(dmalloc(c, &c->tt.rec, tok_cap));
+    c->tt.pool_cap = pool_cap;
+    TRY(upload_vset(c, V.rec, n_tokens, vset_cap));
+    HIPCHK(c, hipMemset(c->tt.pool, 0, pool_cap));
+    HIPCHK(c, hipMemcpy(c->tt.pool, V.pool.data(), V.pool.size(), hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(c->tt.off, V.off.data(), (size_t)n_tokens * 4, hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(c->tt.len, V.len.data(), (size_t)n_tokens * 4, hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(c->tt.rec, V.rec.data(), (size_t)n_tokens * sizeof(TokRec), hipMemcpyHostToDevice));
+    TRY(state_pull(c));
+    DevState *h = c->st_host;
+    memset(h, 0, sizeof(DevState));
+    h->n_tokens = n_tokens;
+    h->pool_used = (uint32_t)V.pool.size();
+    TRY(state_push(c));
+    c->base_tokens = n_tokens;
+    c->have_vocab = true;
+    c->id_bits_fixed = true;
+    return YABPE_OK;
+}
+
+// A load's arguments, checked before anything of the loaded corpus is given up.  *max_token_bytes: DESIGN.md (m), a property
+// of the load -- read here, fixed until the next load.
+int load_check_args(yabpe_ctx *c, const uint64_t *word_off, uint64_t n_words, int64_t *max_token_bytes) {
+    if (!c->have_vocab) return fail(c, YABPE_E_INVALID, "call yabpe_set_vocab first");
+    if (!word_off) return fail(c, YABPE_E_INVALID, "word_off is NULL");
+    if (n_words >= 0xFFFFFFFFull) return fail(c, YABPE_E_CAPACITY, "more than 2^32-2 words per context");
+    *max_token_bytes = optv(c, "max_token_bytes", 0);
+    if (!yb_limit_valid(*max_token_bytes))
+        return fail(c, YABPE_E_INVALID, "max_token_bytes is %lld: 0 (no limit) or a length of at least %u bytes", (long long)*max_token_bytes, YB_LIMIT_MIN);
+    return 0;
+}
+// The words of a load on the device (offsets stay absolute: `bytes` is biased by -off_base), equal words pooled if asked
+// (trainer.py:221-225).  The staged copies belong to `In`, the pooled words to `S`: a caller that needs nothing else of
+// `In` releases it when `pooled` comes back set.  ev0 is recorded between the staging and the pooling.
+struct LoadInputs {
+    const unsigned long long *off = nullptr, *freq = nullptr;
+    const uint8_t *bytes = nullptr;
+    uint64_t n_words = 0, total_bytes = 0, off_base = 0;
+    bool pooled = false;
+};
+int load_stage_inputs(yabpe_ctx *c, Scratch &In, Scratch &S, const uint8_t *bytes, const uint64_t *word_off, const uint64_t *word_freq,
+                      uint64_t n_words, uint32_t flags, hipEvent_t ev0, LoadInputs *L) {
+    L->bytes = bytes;
+    L->n_words = n_words;
+    if (is_device_ptr(word_off)) {
+        HIPCHK(c, hipMemcpy(&L->total_bytes, word_off + n_words, 8, hipMemcpyDeviceToHost));
+        HIPCHK(c, hipMemcpy(&L->off_base, word_off, 8, hipMemcpyDeviceToHost));
+        L->total_bytes -= L->off_base;
+    } else {
+        L->off_base = word_off[0];
+        L->total_bytes = word_off[n_words] - L->off_base;
+    }
+    TRY(to_device(c, In, (const unsigned long long *)word_off, (n_words + 1) * 8, 1, &L->off));
+    if (L->total_bytes && !bytes) return fail(c, YABPE_E_INVALID, "bytes is NULL");
+    if (L->total_bytes) {
+        TRY(to_device(c, In, bytes + L->off_base, L->total_bytes, 1, &L->bytes));
+        L->bytes -= L->off_base;
+    }
+    if (word_freq) TRY(to_device(c, In, (const unsigned long long *)word_freq, n_words * 8, 1, &L->freq));
+    HIPCHK(c, hipEventRecord(ev0, c->stream));
+    c->n_words_input = n_words;
+    if ((flags & YABPE_LOAD_DEDUP) && n_words > 0) {
+        DedupOut dd{};
+        int r = dedup_words(c->stream, L->bytes, L->off, L->freq, n_words, &dd);
+        if (r != 0) return fail(c, YABPE_E_HIP, "device dedup failed (%d): %s", r, hipGetErrorString(hipGetLastError()));
+        S.adopt(dd.bytes); S.adopt(dd.off); S.adopt(dd.freq);
+        L->bytes = dd.bytes; L->off = dd.off; L->freq = dd.freq;
+        L->n_words = dd.n_unique;
+        L->total_bytes = dd.total_bytes;
+        L->off_base = 0;
+        L->pooled = true;
+    }
+    return 0;
+}
+
+// Room for `need` per-merge records; the first `keep` entries survive a move.
+int reserve_records(yabpe_ctx *c, uint32_t need, uint32_t keep) {
+    if (c->rec_cap >= need) return 0;
+    const uint32_t ncap = std::max<uint32_t>(need, c->rec_cap + c->rec_cap / 2);
+    uint32_t *nl = nullptr, *nr = nullptr, *nm = nullptr;
+    unsigned long long *nc = nullptr, *ns = nullptr, *nv = nullptr;
+    TRY(dmalloc(c, &nl, ncap)); TRY(dmalloc(c, &nr, ncap)); TRY(dmalloc(c, &nm, ncap));
+    TRY(dmalloc(c, &nc, ncap)); TRY(dmalloc(c, &ns, ncap)); TRY(dmalloc(c, &nv, ncap));
+    HIPCHK(c, hipMemsetAsync(ns, 0, (size_t)ncap * 8, c->stream));
+    if (c->rec_cap && keep) {
+        const size_t n = keep;
+        HIPCHK(c, hipMemcpyAsync(nl, c->rec_left, n * 4, hipMemcpyDeviceToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(nr, c->rec_right, n * 4, hipMemcpyDeviceToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(nm, c->rec_merged, n * 4, hipMemcpyDeviceToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(nc, c->rec_count, n * 8, hipMemcpyDeviceToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(ns, c->rec_sites, n * 8, hipMemcpyDeviceToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(nv, c->rec_live, n * 8, hipMemcpyDeviceToDevice, c->stream));
+    }
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    free_records(c);
+    c->rec_left = nl; c->rec_right = nr; c->rec_merged = nm; c->rec_count = nc; c->rec_sites = ns; c->rec_live = nv;
+    c->rec_cap = ncap;
+    return 0;
+}
+
+// The head of a training call: the state told what is asked, the results of the last call forgotten.
+int train_begin(yabpe_ctx *c, uint32_t num_merges, uint64_t min_frequency, uint32_t *rec_base) {
+    TRY(state_pull(c));
+    DevState *h = c->st_host;
+    *rec_base = h->iter;
+    if ((uint64_t)*rec_base + num_merges > 0xFFFFFFF0ull) return fail(c, YABPE_E_CAPACITY, "more than 2^32 merges in one context");
+    h->num_merges = *rec_base + num_merges;
+    h->min_freq = min_frequency;
+    h->done = 0;
+    h->halt = 0;
+    h->halt_req = 0;
+    if (c->id_bits != 32) {  // (the batch the u16 selection keeps; the u32 loop selects one merge per launch)
+        h->n_batch = 0;
+        h->n_select = 0;
+        h->batch_others = 0;
+        h->kmax = 1;
+        h->win_shift = 3;
+    }
+    TRY(state_push(c));
+    c->rec_n = 0;
+    c->log_sites.clear();
+    c->log_live.clear();
+    c->ev_iter.clear();
+    c->ev_us.clear();
+    c->ev_scan_us.clear();
+    return 0;
+}
+// ... and its per-merge records: `first` of them, none kept from the last call, no sites counted yet
+int train_begin_records(yabpe_ctx *c, uint32_t first) {
+    if (c->rec_cap < first) free_records(c);
+    TRY(reserve_records(c, first, 0));
+    HIPCHK(c, hipMemsetAsync(c->rec_sites, 0, (size_t)c->rec_cap * 8, c->stream));
+    return 0;
+}
+// The tail of a training call: the n merges of the call to the caller's arrays, their site (and live-slot) log to the context.
+int train_copy_out(yabpe_ctx *c, uint32_t n, bool live, uint32_t *out_left, uint32_t *out_right, uint32_t *out_merged, uint64_t *out_count,
+                   uint32_t *out_n_merges) {
+    c->rec_n = n;
+    c->log_sites.assign(n, 0);
+    c->log_live.assign(n, 0);
+    if (n) {
+        HIPCHK(c, hipMemcpy(c->log_sites.data(), c->rec_sites, (size_t)n * 8, hipMemcpyDeviceToHost));
+        if (live) HIPCHK(c, hipMemcpy(c->log_live.data(), c->rec_live, (size_t)n * 8, hipMemcpyDeviceToHost));
+        if (out_left) HIPCHK(c, hipMemcpy(out_left, c->rec_left, (size_t)n * 4, hipMemcpyDeviceToHost));
+        if (out_right) HIPCHK(c, hipMemcpy(out_right, c->rec_right, (size_t)n * 4, hipMemcpyDeviceToHost));
+        if (out_merged) HIPCHK(c, hipMemcpy(out_merged, c->rec_merged, (size_t)n * 4, hipMemcpyDeviceToHost));
+        if (out_count) HIPCHK(c, hipMemcpy(out_count, c->rec_count, (size_t)n * 8, hipMemcpyDeviceToHost));
+    }
+    if (out_n_merges) *out_n_merges = n;
+    return 0;
+}
 }  // namespace
 
 #include "yabpe_id32_host.h"
@@ -1129,65 +1357,14 @@ int yabpe_set_vocab(yabpe_ctx *c, const uint8_t *tok_bytes, const uint32_t *tok_
             return fail(c, YABPE_E_INVALID, "token %u must be the single byte %u (trainer.py:123-125)", b, b);
     if (c->id_bits == 32) return id32_set_vocab(c, tok_bytes, tok_off, n_tokens);
     if (n_tokens >= YB_MAX_TOKENS) return fail(c, YABPE_E_CAPACITY, "base vocabulary too large for u16 token ids");
+    // the u16 side: fixed capacities (every id, a set of 2^18 slots), the base vocabulary in at most half the pool, lexranks
     const uint32_t pool_cap = (uint32_t)optv(c, "pool_bytes", 64 << 20) & ~3u;
-    const uint32_t vset_cap = 1u << 18;
-    // every token starts at a multiple of 4 in the pool (new tokens' bytes are written four at a time)
-    std::vector<uint32_t> off(n_tokens), len(n_tokens), order(n_tokens);
-    std::vector<uint8_t> pool;
-    for (uint32_t i = 0; i < n_tokens; ++i) {
-        len[i] = tok_off[i + 1] - tok_off[i];
-        off[i] = (uint32_t)pool.size();
-        pool.insert(pool.end(), tok_bytes + tok_off[i], tok_bytes + tok_off[i + 1]);
-        pool.resize((pool.size() + 3) & ~(size_t)3, 0);
-        order[i] = i;
-    }
-    if (pool.size() > pool_cap / 2) return fail(c, YABPE_E_CAPACITY, "base vocabulary bytes exceed the token pool");
-    dfree(c->tt.pool); dfree(c->tt.off); dfree(c->tt.len); dfree(c->tt.rec); dfree(c->tt.vset);
-    TRY(dmalloc(c, &c->tt.pool, pool_cap));
-    TRY(dmalloc(c, &c->tt.off, YB_MAX_TOKENS));
-    TRY(dmalloc(c, &c->tt.len, YB_MAX_TOKENS));
-    TRY(dmalloc(c, &c->tt.rec, YB_MAX_TOKENS));
-    TRY(dmalloc(c, &c->tt.vset, vset_cap));
-    c->tt.pool_cap = pool_cap;
-    c->tt.vset_mask = vset_cap - 1;
-    std::vector<TokRec> rec(n_tokens);
-    std::vector<unsigned long long> vset(vset_cap, VSET_EMPTY);
-    auto cmp = [&](uint32_t x, uint32_t y) {
-        uint32_t n = std::min(len[x], len[y]);
-        int d = memcmp(pool.data() + off[x], pool.data() + off[y], n);
-        if (d) return d < 0;
-        return len[x] < len[y];
-    };
-    std::sort(order.begin(), order.end(), cmp);
-    for (uint32_t r = 0; r < n_tokens; ++r) {
-        if (r && !cmp(order[r - 1], order[r])) return fail(c, YABPE_E_INVALID, "duplicate token bytes in the base vocabulary (trainer.py:130)");
-        rec[order[r]].rank = r;
-    }
-    for (uint32_t i = 0; i < n_tokens; ++i) {
-        rec[i].len = len[i];
-        rec[i].hash = yb_hash_bytes(pool.data() + off[i], len[i]);
-        rec[i].pre8 = yb_pre8(pool.data() + off[i], len[i]);
-        rec[i].pad = 0;
-        uint32_t s = yb_vset_home(rec[i].hash, len[i]) & c->tt.vset_mask;
-        while (vset[s] != VSET_EMPTY) s = (s + 1) & c->tt.vset_mask;
-        vset[s] = yb_vset_entry(i, rec[i].hash);
-    }
-    HIPCHK(c, hipMemset(c->tt.pool, 0, pool_cap));
-    HIPCHK(c, hipMemcpy(c->tt.pool, pool.data(), pool.size(), hipMemcpyHostToDevice));
-    HIPCHK(c, hipMemcpy(c->tt.off, off.data(), n_tokens * 4, hipMemcpyHostToDevice));
-    HIPCHK(c, hipMemcpy(c->tt.len, len.data(), n_tokens * 4, hipMemcpyHostToDevice));
-    HIPCHK(c, hipMemcpy(c->tt.rec, rec.data(), n_tokens * sizeof(TokRec), hipMemcpyHostToDevice));
-    HIPCHK(c, hipMemcpy(c->tt.vset, vset.data(), (size_t)vset_cap * 8, hipMemcpyHostToDevice));
-    TRY(state_pull(c));
-    DevState *h = c->st_host;
-    memset(h, 0, sizeof(DevState));
-    h->n_tokens = n_tokens;
-    h->pool_used = (uint32_t)pool.size();
-    TRY(state_push(c));
-    c->base_tokens = n_tokens;
-    c->have_vocab = true;
-    c->id_bits_fixed = true;
-    return YABPE_OK;
+    BaseVocab V;
+    base_vocab_pack(tok_bytes, tok_off, n_tokens, V);
+    if (V.pool.size() > pool_cap / 2) return fail(c, YABPE_E_CAPACITY, "base vocabulary bytes exceed the token pool");
+    TRY(base_vocab_index(c, V));
+    for (uint32_t r = 0; r < n_tokens; ++r) V.rec[V.order[r]].rank = r;
+    return base_vocab_upload(c, V, pool_cap, YB_MAX_TOKENS, 1u << 18);
 }
 
 // ---------------------------------------------------------------------------------------------- corpus
@@ -1196,65 +1373,24 @@ int yabpe_set_vocab(yabpe_ctx *c, const uint8_t *tok_bytes, const uint32_t *tok_
 static int load_words_impl(yabpe_ctx *c, const uint8_t *bytes, const uint64_t *word_off, const uint64_t *word_freq,
                            uint64_t n_words, uint32_t flags, const RpTable *rp) {
     HIPCHK(c, hipSetDevice(c->device));
-    if (!c->have_vocab) return fail(c, YABPE_E_INVALID, "call yabpe_set_vocab first");
-    if (!word_off) return fail(c, YABPE_E_INVALID, "word_off is NULL");
-    if (n_words >= 0xFFFFFFFFull) return fail(c, YABPE_E_CAPACITY, "more than 2^32-2 words per context");
-    // maximum token length: a property of the load -- read here, fixed until the next load
-    const int64_t max_token_bytes = optv(c, "max_token_bytes", 0);
-    if (!yb_limit_valid(max_token_bytes))
-        return fail(c, YABPE_E_INVALID, "max_token_bytes is %lld: 0 (no limit) or a length of at least %u bytes", (long long)max_token_bytes, YB_LIMIT_MIN);
+    int64_t max_token_bytes = 0;
+    TRY(load_check_args(c, word_off, n_words, &max_token_bytes));
     free_corpus(c);
-    struct Events {  // (destroyed on every way out)
-        hipEvent_t ev0 = nullptr, ev1 = nullptr, ev_seg = nullptr;
-        ~Events() {
-            if (ev0) (void)hipEventDestroy(ev0);
-            if (ev1) (void)hipEventDestroy(ev1);
-            if (ev_seg) (void)hipEventDestroy(ev_seg);
-        }
-    } evs;
-    hipEvent_t &ev0 = evs.ev0, &ev1 = evs.ev1, &ev_seg = evs.ev_seg;
-    HIPCHK(c, hipEventCreate(&ev0));
-    HIPCHK(c, hipEventCreate(&ev1));
-    Scratch S(c->device, c->rank);  // every temporary of the load: staged inputs, pooled words, walk buffers, long-word lists
-
-    // ---- make inputs device-resident
-    const unsigned long long *d_off = nullptr;
-    const uint8_t *d_bytes = bytes;
-    const unsigned long long *d_freq = nullptr;
-    uint64_t total_bytes = 0, off_base = 0;
-    if (is_device_ptr(word_off)) {
-        HIPCHK(c, hipMemcpy(&total_bytes, word_off + n_words, 8, hipMemcpyDeviceToHost));
-        HIPCHK(c, hipMemcpy(&off_base, word_off, 8, hipMemcpyDeviceToHost));
-        total_bytes -= off_base;
-    } else {
-        off_base = word_off[0];
-        total_bytes = word_off[n_words] - off_base;
-    }
-    TRY(to_device(c, S, (const unsigned long long *)word_off, (n_words + 1) * 8, 1, &d_off));
-    if (total_bytes && !bytes) return fail(c, YABPE_E_INVALID, "bytes is NULL");
-    if (total_bytes) {
-        TRY(to_device(c, S, bytes + off_base, total_bytes, 1, &d_bytes));
-        d_bytes -= off_base;  // offsets stay absolute
-    }
-    if (word_freq) TRY(to_device(c, S, (const unsigned long long *)word_freq, n_words * 8, 1, &d_freq));
+    Events<3> evs;  // start, end, (resumed load) replay done
+    HIPCHK(c, evs.create());
+    const hipEvent_t ev0 = evs.e[0], ev1 = evs.e[1], ev_seg = evs.e[2];
+    Scratch In(c->device, c->rank);  // the staged inputs
+    Scratch S(c->device, c->rank);   // every other temporary of the load: pooled words, walk buffers, long-word lists
+    LoadInputs L;
+    TRY(load_stage_inputs(c, In, S, bytes, word_off, word_freq, n_words, flags, ev0, &L));
+    if (L.pooled) In.release();  // (the u16 load gives the staged inputs up at once: the pooled words replace them)
+    const unsigned long long *d_off = L.off, *d_freq = L.freq;
+    const uint8_t *d_bytes = L.bytes;
+    n_words = L.n_words;
+    const uint64_t total_bytes = L.total_bytes, off_base = L.off_base;
     uint32_t *d_wcnt = nullptr;             // resumed load: tokens per word after the replay ...
     uint16_t *d_wtok = nullptr;             // ... the tokens, word w's where its bytes start ...
     unsigned long long *d_tokoff = nullptr; // ... and the exclusive scan of the counts
-    HIPCHK(c, hipEventRecord(ev0, c->stream));
-
-    c->n_words_input = n_words;
-    // ---- optional device-side pooling of equal words (trainer.py:221-225)
-    DedupOut dd{};
-    if ((flags & YABPE_LOAD_DEDUP) && n_words > 0) {
-        int r = dedup_words(c->stream, d_bytes, d_off, d_freq, n_words, &dd);
-        if (r != 0) return fail(c, YABPE_E_HIP, "device dedup failed (%d): %s", r, hipGetErrorString(hipGetLastError()));
-        S.release();  // (the staged inputs: the pooled words replace them)
-        S.adopt(dd.bytes); S.adopt(dd.off); S.adopt(dd.freq);
-        d_bytes = dd.bytes; d_off = dd.off; d_freq = dd.freq;
-        n_words = dd.n_unique;
-        total_bytes = dd.total_bytes;
-        off_base = 0;
-    }
     // (a rank that holds no words must still run the layout its peers run: the collectives differ between the layouts)
     c->weighted = d_freq != nullptr || (flags & YABPE_LOAD_DEDUP) != 0;
     c->n_words = n_words;
@@ -1263,7 +1399,6 @@ static int load_words_impl(yabpe_ctx *c, const uint8_t *bytes, const uint64_t *w
     // ---- resumed load: every word rewritten by the model's merges (replay_logic.h), then placed by its token count
     uint64_t total_tokens = total_bytes;
     if (rp) {
-        HIPCHK(c, hipEventCreate(&ev_seg));
         c->resume_stats = yabpe_resume_stats_t{};
         c->resume_stats.n_unique = n_words;
         if (n_words) {
@@ -1414,6 +1549,7 @@ static int load_words_impl(yabpe_ctx *c, const uint8_t *bytes, const uint64_t *w
         }
     }
     HIPCHK(c, hipStreamSynchronize(c->stream));
+    In.release();
     S.release();  // (before the pair table is built)
 
     // ---- state + initial pair count (trainer.py:227-235)
@@ -1565,170 +1701,281 @@ static int launch_select(yabpe_ctx *c, uint32_t rec_base) {
     return 0;
 }
 
+// ---- the u16 merge loop's driver: one run state, the launches, the steps of a round (the decisions are train_rules.h's)
+extern "C++" {
+namespace {
+
+// Every option the loop reads, looked up once at the top of the call.  An option cannot change during a call (one thread,
+// one context), so reading it here and not at every launch changes no behaviour.
+struct TrainOpts {
+    uint32_t check, ev_sample, ev_sample_dense;
+    uint64_t retile_min_tiles;
+    int64_t retile_pct, split, split_pct, batch_max, cand_rebuild_every, cand_target, sig_rebuild_every, sig_rebuild_pct;
+    int64_t apply_blocks, full_wpb, wide_sites_per_cu, full_skip_blocks, chunk_steal, agg_small;
+    int64_t delta_granule, delta_headroom_pct, delta_margin, delta_floor, p2p_timeout_ms, table_load_pct, table_grow_x;
+    bool trace_host, trace_exchange, fused, rank_rides, hist, delta_adapt;
+};
+TrainOpts train_opts(yabpe_ctx *c) {
+    TrainOpts O{};
+    O.check = (uint32_t)std::max<int64_t>(1, optv(c, "check_interval", 32));
+    O.ev_sample = (uint32_t)std::max<int64_t>(0, optv(c, "event_sample", 0));
+    O.ev_sample_dense = (uint32_t)std::max<int64_t>(0, optv(c, "event_sample_dense", (int64_t)O.ev_sample));  // fused k_apply launches
+    O.retile_min_tiles = (uint64_t)optv(c, "retile_min_tiles", 4096);
+    O.retile_pct = optv(c, "retile_pct", 60);
+    O.split = optv(c, "split", -1);
+    O.split_pct = optv(c, "split_pct", 100);
+    O.batch_max = optv(c, "batch_max", KMAX);
+    O.cand_rebuild_every = optv(c, "cand_rebuild_every", 512);
+    O.cand_target = optv(c, "cand_target", 768);
+    O.sig_rebuild_every = optv(c, "sig_rebuild_every", 16384);
+    O.sig_rebuild_pct = optv(c, "sig_rebuild_pct", 20);
+    O.apply_blocks = optv(c, "apply_blocks", OPT_UNSET);
+    O.full_wpb = optv(c, "full_wpb", 0);
+    O.wide_sites_per_cu = optv(c, "wide_sites_per_cu", 20);
+    O.full_skip_blocks = optv(c, "full_skip_blocks", OPT_UNSET);
+    O.chunk_steal = optv(c, "chunk_steal", 1);
+    O.agg_small = optv(c, "agg_small", 1);
+    O.delta_granule = optv(c, "delta_granule", 1024);
+    O.delta_headroom_pct = optv(c, "delta_headroom_pct", 200);
+    O.delta_margin = optv(c, "delta_margin", 1024);
+    O.delta_floor = optv(c, "delta_floor", 2048);
+    O.p2p_timeout_ms = optv(c, "p2p_timeout_ms", 20000);
+    O.table_load_pct = optv(c, "table_load_pct", 30);
+    O.table_grow_x = optv(c, "table_grow_x", 8);
+    O.trace_host = optv(c, "trace_host", 0) != 0;  // (debugging a stuck multi-GPU job: where is this rank's host?)
+    O.trace_exchange = optv(c, "trace_exchange", 0) != 0;
+    O.fused = optv(c, "fused", 1) != 0;
+    O.rank_rides = optv(c, "rank_rides", 1) != 0;
+    O.hist = optv(c, "hist", 1) != 0;
+    O.delta_adapt = optv(c, "delta_adapt", 1) != 0;
+    return O;
+}
+
+struct TrainRun {
+    yabpe_ctx *c;
+    DevState *h;  // the pinned copy of the device state, as of the last pull
+    TrainOpts O;
+    uint32_t num_merges, rec_base;
+    // progress
+    uint32_t i = 0;  // merges selected so far in this call (read back from the device between rounds of launches)
+    bool first_round = true;
+    bool skip_cand_once = false;  // the last round hit HALT_RESCAN: finish its merge with the full scan
+    // form of this round
+    bool sparse_global = false;  // the sparse form has been called for (by any rank)
+    bool sparse_now = false, fuse = false;
+    uint32_t kmax = 1, n_launch = 0, apply_grid = 0;
+    // candidate list
+    unsigned long long prev_best = 0;
+    uint32_t cand_n_all = 0;  // length of the list at the last read (multi-GPU: of the longest replica's)
+    // measurement marks: where the sparse phase and the second half of the call's merges begin
+    Events<4> ev;  // start, end, split, tail
+    bool split_marked = false, tail_marked = false;
+    uint32_t split_at = 0, tail_at = 0;
+    uint32_t dense_applied = 0;  // merges the streaming launches applied (what was selected when the form changed, less the pending batch)
+    uint64_t launches_sparse = 0, launches_at_tail = 0, launches_dense = 0;
+    uint64_t tokens_at_start = 0;
+    // event sampling
+    size_t ev_next = 0;
+    uint64_t launch_no = 0;
+};
+enum RoundNext { ROUND_NEXT, ROUND_AGAIN, ROUND_STOP };
+
+__attribute__((format(printf, 2, 3))) void trace(const TrainRun &R, const char *fmt, ...) {
+    if (!R.O.trace_host) return;
+    fprintf(stderr, "[yabpe r%d] ", R.c->rank);
+    va_list ap;
+    va_start(ap, fmt);
+    vfprintf(stderr, fmt, ap);
+    va_end(ap);
+    fprintf(stderr, "\n");
+    fflush(stderr);
+}
+
+// the event pair of every Nth LAUNCH (iter_rel: the merges selected so far, a lower bound in the fused forms), else NULL
+EventPair *sample_launch(TrainRun &R, uint32_t iter_rel) {
+    yabpe_ctx *c = R.c;
+    const uint32_t every = c->split_mode ? R.O.ev_sample : R.O.ev_sample_dense;
+    if (!every || (R.launch_no++ % every) != 0) return nullptr;
+    if (R.ev_next == c->events.size()) {
+        EventPair n{};
+        if (hipEventCreate(&n.e0) != hipSuccess || hipEventCreate(&n.e1) != hipSuccess || hipEventCreate(&n.e2) != hipSuccess) return nullptr;
+        c->events.push_back(n);
+    }
+    c->events[R.ev_next].iter_rel = iter_rel;
+    return &c->events[R.ev_next++];
+}
+// the launches from merge i on did nothing: timed again in the re-run
+void unsample_from(TrainRun &R) {
+    while (R.ev_next > 0 && R.c->events[R.ev_next - 1].iter_rel >= R.i) --R.ev_next;
+}
+
 // Can the apply launch of the merges that are selected now end with the selection of the next ones?
-static bool can_fuse(yabpe_ctx *c) {
-    if (!c->use_cand || !optv(c, "fused", 1)) return false;
+bool can_fuse(const TrainRun &R) {
+    const yabpe_ctx *c = R.c;
+    if (!c->use_cand || !R.O.fused) return false;
     if (c->multi) return true;        // the selection rides on the launch that applies the exchanged records (k_delta_apply)
     if (!c->n_tiles) return false;
     if (!c->split_mode) return true;  // k_apply
     return c->sig && c->sig_valid;    // k_scan_skip
 }
 
-// Applies the selected merges (DevState::batch) to the token stream and the pair table (trainer.py:254-294).  fuse: the
-// launch that finishes the apply also selects the next merges (its last workgroup; see fused_select_tail) -- one launch per batch.
-static int launch_apply(yabpe_ctx *c, uint32_t rec_base, uint32_t tokens_upper, uint32_t apply_grid, EventPair *ev, bool fuse) {
-    RankParams R{c->tt, c->st};
-    const uint32_t rank_blocks = cdiv64(std::min<uint32_t>(tokens_upper, YB_MAX_TOKENS), BLOCK);
-    // lexrank maintenance rides on the apply launch (extra workgroups) whenever there is one over the tiles
-    const bool sparse = c->split_mode && c->sig && c->sig_valid;
-    const bool rank_rides = c->n_tiles && (fuse || optv(c, "rank_rides", 1)) && (c->split_mode ? sparse : true);
-    if (!rank_rides) hipLaunchKernelGGL(k_rank_update, dim3(rank_blocks), dim3(BLOCK), 0, c->stream, R);
-    // where the apply pass puts its pair-count updates: the pair table, or (multi-GPU) this rank's send buffer as records
-    PairTable out_table = c->table;
-    if (c->multi) {
-        out_table = PairTable{};
-        out_table.sink_hdr = reinterpret_cast<DeltaHdr *>(c->xsend);
-        out_table.sink_rec = reinterpret_cast<DeltaRec *>(c->xsend + 16);
-        out_table.sink_cap = c->xeff;  // (what this exchange transmits: a rank with more records than that reports it by its count)
+// What the launches that apply one selection share.
+struct ApplyJob {
+    RankParams rank;
+    uint32_t rank_blocks;  // workgroups of the lexrank maintenance ...
+    bool rank_rides;       // ... riding on the launch over the tiles as extra workgroups
+    PairTable out_table;   // where the pair-count updates go: the pair table, or (multi-GPU) this rank's send buffer as records
+    bool fuse;             // the launch that finishes the apply also selects the next merges (its last workgroup: fused_select_tail)
+    bool fuse_kernel;      // ... and that launch is the one over the tiles (single GPU)
+    LongParams LW;
+    uint32_t long_group, long_blocks;  // long words per workgroup; workgroups of theirs riding like the lexranks (0: launched on their own)
+    uint32_t rr_blocks() const { return rank_rides ? rank_blocks : 0u; }
+};
+// the fused selection folds the per-workgroup counters of THIS launch too: it must know the larger grid
+FuseParams fuse_params(const TrainRun &R, const ApplyJob &J, uint32_t grid_now) {
+    FuseParams F{};
+    if (J.fuse_kernel) {
+        F.ticket = R.c->sel_ticket;
+        F.sel = select_params(R.c, R.rec_base, 0u, std::max(R.c->blk_used, grid_now));
     }
-    const bool fuse_kernel = fuse && !c->multi;  // the apply launch itself ends with the selection
+    return F;
+}
+ApplyParams apply_params(const yabpe_ctx *c, const ApplyJob &J) {
+    return ApplyParams{c->tiles, c->tile_len, c->tile_wbase, c->wfreq, c->n_tiles, J.out_table, c->st, c->blk_stats,
+                       c->split_mode ? c->sig : nullptr, c->sig_stride, (uint32_t)AGG_N - 1u, 1u};  // signatures are maintained in the sparse form only
+}
+
+// streaming form: one merge per launch, one coalesced pass over the live stream
+int launch_streaming(TrainRun &R, const ApplyJob &J, uint32_t tokens_upper) {
+    yabpe_ctx *c = R.c;
+    const ApplyParams P = apply_params(c, J);
+    const uint32_t apply_grid = R.apply_grid;
+    const FuseParams F = fuse_params(R, J, apply_grid);
+    const uint32_t long_first = apply_grid + J.rr_blocks(), grid = long_first + J.long_blocks;
+    c->blk_used = std::max(c->blk_used, apply_grid);
+    if (c->weighted)
+        hipLaunchKernelGGL(k_apply<true>, dim3(grid), dim3(BLOCK), 0, c->stream, P, apply_grid, J.rank, F, J.LW, long_first);
+    else if (R.O.hist && tokens_upper <= (uint32_t)HIST_V)  // (every token id this launch can meet indexes the direct store)
+        hipLaunchKernelGGL((k_apply<false, true>), dim3(grid), dim3(BLOCK), 0, c->stream, P, apply_grid, J.rank, F, J.LW, long_first);
+    else
+        hipLaunchKernelGGL(k_apply<false>, dim3(grid), dim3(BLOCK), 0, c->stream, P, apply_grid, J.rank, F, J.LW, long_first);
+    return 0;
+}
+
+template <int NW>
+void launch_scan_skip(yabpe_ctx *c, uint32_t grid, const ScanSkipParams &SQ) {
+    if (c->weighted)
+        hipLaunchKernelGGL((k_scan_skip<true, NW>), dim3(grid), dim3(NW * 64), 0, c->stream, c->st, SQ);
+    else
+        hipLaunchKernelGGL((k_scan_skip<false, NW>), dim3(grid), dim3(NW * 64), 0, c->stream, c->st, SQ);
+}
+// sparse form: skip index + rewrite of the tiles that pass, a batch of merges per launch (the shape: sparse_geom_rule)
+int launch_sparse(TrainRun &R, const ApplyJob &J) {
+    yabpe_ctx *c = R.c;
+    const TrainOpts &O = R.O;
+    if (!(c->sig && c->sig_valid)) return fail(c, YABPE_E_INTERNAL, "sparse form without signatures");
+    const SparseGeom g = sparse_geom_rule(c->n_tiles, (uint32_t)c->n_cu, c->st_host->best_count, c->weighted, c->kmax_now, O.full_wpb,
+                                          O.wide_sites_per_cu, O.full_skip_blocks, O.chunk_steal, O.agg_small);
+    if (!c->blk_read) {
+        TRY(dmalloc(c, &c->blk_read, BLK_READ_WORDS));
+        HIPCHK(c, hipMemsetAsync(c->blk_read, 0, BLK_READ_WORDS * 8, c->stream));
+    }
+    ApplyParams P = apply_params(c, J);
+    P.agg_mask = g.agg_mask;
+    const ScanSkipParams SQ{P, c->blk_read, g.scan_grid, g.kt, g.chunk, J.rank, fuse_params(R, J, g.scan_grid), J.LW, g.scan_grid + J.rr_blocks(),
+                            g.piece, g.n_pieces, g.pieces ? c->blk_read + 2 * MAX_LISTS : nullptr,
+                            g.pieces ? ++c->piece_tag : 0ull, c->blk_read + MAX_LISTS};
+    c->blk_used = std::max(c->blk_used, g.scan_grid);
+    const uint32_t grid = g.scan_grid + J.rr_blocks() + J.long_blocks;
+    if (g.nw == 16) launch_scan_skip<16>(c, grid, SQ);
+    else launch_scan_skip<8>(c, grid, SQ);
+    c->scan_skip_launches++;
+    return 0;
+}
+
+// Multi-GPU, per batch: the apply launch left this rank's updates as [header | records] in its send buffer (the aggregator
+// flush writes them there: no delta table, no extraction pass); ONE all-gather; ONE launch adds every rank's records to
+// the replica and -- fused form -- selects the next merges in its last workgroup.
+int launch_exchange(TrainRun &R, const ApplyJob &J) {
+    yabpe_ctx *c = R.c;
+    const uint64_t xbytes = 16 + (uint64_t)c->xeff * sizeof(DeltaRec);  // [header | xeff records] per rank, packed at that stride
+    const uint8_t *recv = c->xrecv;
+    uint64_t rstride = xbytes;
+    if (c->p2p) {  // push into the peers' memory, wait for theirs: one small launch, no collective
+        XchgParams X{};
+        X.send = c->xsend;
+        for (int r = 0; r < c->n_ranks; ++r) X.peer[r] = c->p2p_peer[r];
+        X.flags_off = c->p2p_flags_off;
+        X.half_bytes = c->p2p_half;
+        X.stride = c->p2p_stride;
+        X.seq = ++c->p2p_seq;
+        X.rank = (uint32_t)c->rank;
+        X.n_ranks = (uint32_t)c->n_ranks;
+        X.cap = c->xeff;
+        X.timeout_ticks = (unsigned long long)R.O.p2p_timeout_ms * 100000ull;
+        X.st = c->st;
+        const bool timed = !c->p2p_pending && c->p2p_e0;  // (one exchange per round of launches is timed)
+        if (timed) HIPCHK(c, hipEventRecord(c->p2p_e0, c->stream));
+        hipLaunchKernelGGL(k_xchg_push, dim3((uint32_t)c->n_ranks), dim3(BLOCK), 0, c->stream, X);
+        if (timed) {
+            HIPCHK(c, hipEventRecord(c->p2p_e1, c->stream));
+            c->p2p_pending = true;  // (read at the end of this round of launches)
+        }
+        recv = c->p2p_area + (X.seq & 1ull) * c->p2p_half;
+        rstride = c->p2p_stride;
+    } else {
+        TRY(comm_allgather(c, c->xsend, c->xrecv, xbytes));
+    }
+    c->xeff_sum += c->xeff;
+    DeltaApplyParams DA{recv, (uint32_t)c->n_ranks, c->xeff, rstride, c->table, c->st, FuseParams{}, c->p2p ? 1u : 0u};
+    if (J.fuse) {
+        DA.F.ticket = c->sel_ticket;
+        DA.F.sel = select_params(c, R.rec_base, 0u, c->blk_used);
+    }
+    hipLaunchKernelGGL(k_delta_apply, dim3(cdiv64((uint64_t)c->n_ranks * c->xeff, DELTA_RPW)), dim3(BLOCK), 0, c->stream, DA);
+    c->exchanges++;
+    return 0;
+}
+
+// Applies the selected merges (DevState::batch) to the token stream and the pair table (trainer.py:254-294): the lexranks
+// and the long words (more than 63 tokens: outside the tile stream) ride on the launch over the tiles where there is one,
+// else they are launched on their own; then the exchange.  fuse: one launch per batch, see ApplyJob.
+int launch_merges(TrainRun &R, uint32_t tokens_upper, EventPair *ev, bool fuse) {
+    yabpe_ctx *c = R.c;
+    ApplyJob J{};
+    J.rank = RankParams{c->tt, c->st};
+    J.rank_blocks = cdiv64(std::min<uint32_t>(tokens_upper, YB_MAX_TOKENS), BLOCK);
+    const bool sparse = c->split_mode && c->sig && c->sig_valid;
+    J.rank_rides = c->n_tiles && (fuse || R.O.rank_rides) && (c->split_mode ? sparse : true);
+    if (!J.rank_rides) hipLaunchKernelGGL(k_rank_update, dim3(J.rank_blocks), dim3(BLOCK), 0, c->stream, J.rank);
+    J.out_table = c->table;
+    if (c->multi) {
+        J.out_table = PairTable{};
+        J.out_table.sink_hdr = reinterpret_cast<DeltaHdr *>(c->xsend);
+        J.out_table.sink_rec = reinterpret_cast<DeltaRec *>(c->xsend + 16);
+        J.out_table.sink_cap = c->xeff;  // (what this exchange transmits: a rank with more records than that reports it by its count)
+    }
+    J.fuse = fuse;
+    J.fuse_kernel = fuse && !c->multi;
     if (ev) {
         ev->split = c->split_mode;
         HIPCHK(c, hipEventRecord(ev->e0, c->stream));
     }
-    // the long words (more than 63 tokens: outside the tile stream) ride on the fused launch as extra workgroups, like the
-    // lexrank maintenance: one signature word per long word and merge, the few words that pass are rewritten
+    // one signature word per long word and merge, the few words that pass are rewritten
     // (words per workgroup: about two workgroups per CU while there are few long words, BLOCK when there are many)
-    const uint32_t long_group = (uint32_t)std::min<uint64_t>(BLOCK, std::max<uint64_t>(32, cdiv64(c->n_long, 2ull * std::max(1, c->n_cu))));
-    const LongParams LW{c->long_tok, c->long_off, c->long_len, c->long_freq, c->n_long, out_table, c->st, c->long_sig, c->long_sig_stride, long_group};
-    const bool long_rides = fuse_kernel && c->n_long && c->n_tiles && rank_rides;
-    const uint32_t long_blocks = long_rides ? cdiv64(c->n_long, long_group) : 0u;
-    if (fuse_kernel && c->n_long && !long_rides)  // (no tile launch to ride on: on their own, first -- the fused launch must be the last one to touch the table)
-        hipLaunchKernelGGL(k_apply_long, dim3(cdiv64(c->n_long, long_group)), dim3(BLOCK), 0, c->stream, LW);
-    // the fused selection folds the per-workgroup counters of THIS launch too: it must know the larger grid
-    auto fuse_params = [&](uint32_t grid_now) {
-        FuseParams F{};
-        if (fuse_kernel) {
-            F.ticket = c->sel_ticket;
-            F.sel = select_params(c, rec_base, 0u, std::max(c->blk_used, grid_now));
-        }
-        return F;
-    };
-    if (c->n_tiles) {
-        ApplyParams P{c->tiles, c->tile_len, c->tile_wbase, c->wfreq, c->n_tiles, out_table, c->st, c->blk_stats,
-                      c->split_mode ? c->sig : nullptr, c->sig_stride, (uint32_t)AGG_N - 1u, 1u};  // signatures are maintained in the sparse form only
-        if (!c->split_mode) {
-            // streaming form: one merge per launch, one coalesced pass over the live stream
-            const FuseParams F = fuse_params(apply_grid);
-            const uint32_t rr_blocks = rank_rides ? rank_blocks : 0u;
-            c->blk_used = std::max(c->blk_used, apply_grid);
-            if (c->weighted)
-                hipLaunchKernelGGL(k_apply<true>, dim3(apply_grid + rr_blocks + long_blocks), dim3(BLOCK), 0, c->stream, P, apply_grid, R, F, LW, apply_grid + rr_blocks);
-            else if (optv(c, "hist", 1) && tokens_upper <= (uint32_t)HIST_V)  // (every token id this launch can meet indexes the direct store)
-                hipLaunchKernelGGL((k_apply<false, true>), dim3(apply_grid + rr_blocks + long_blocks), dim3(BLOCK), 0, c->stream, P, apply_grid, R, F, LW, apply_grid + rr_blocks);
-            else
-                hipLaunchKernelGGL(k_apply<false>, dim3(apply_grid + rr_blocks + long_blocks), dim3(BLOCK), 0, c->stream, P, apply_grid, R, F, LW, apply_grid + rr_blocks);
-            if (ev) HIPCHK(c, hipEventRecord(ev->e1, c->stream));
-        } else {
-            // sparse form: skip index + rewrite of the tiles that pass, a batch of merges per launch.
-            // A grid that is resident all at once (no second round of workgroups behind the first): each thread tests kt
-            // tiles' signatures per merge, a workgroup owns `chunk` consecutive tiles at a time.  Wide workgroups
-            // (full_wpb waves, 16 waves per CU either way): a merge late in a job has its sites in a few word types, so
-            // every workgroup with a site adds to the SAME few table counts -- same-address atomics are served one after
-            // the other, and the queue is as long as there are workgroups; a wider workgroup also evens out how many
-            // matched tiles a wave has to rewrite.  (0 = by the merge: 16 waves once a merge has so few sites that the
-            // queue on the hot counts is what is left -- and the whole stream fits one round of such workgroups -- else 8)
-            if (!sparse) return fail(c, YABPE_E_INTERNAL, "sparse form without signatures");
-            int64_t wpb_opt = optv(c, "full_wpb", 0);
-            if (wpb_opt <= 0)
-                wpb_opt = (c->st_host->best_count <= (unsigned long long)optv(c, "wide_sites_per_cu", 20) * c->n_cu && (c->n_tiles + 2047u) / 2048u <= c->n_cu) ? 16 : 8;
-            const uint32_t nw = wpb_opt >= 16 ? 16u : 8u;  // (a 4-wave form existed until round 3: never chosen, pruned)
-            const uint32_t nt = nw * 64u;
-            const uint32_t target = (uint32_t)std::max<int64_t>(1, optv(c, "full_skip_blocks", (int64_t)c->n_cu * (16 / nw)));
-            // tiles per workgroup: what fills `target` workgroups, in whole waves of signature tests, at most kt_max per thread
-            const uint32_t ktm = (uint32_t)scan_kt_max((int)nw);
-            const uint32_t chunk = std::min<uint32_t>(nt * ktm, std::max<uint32_t>(64u, (uint32_t)(((uint64_t)(c->n_tiles + target - 1) / target + 63u) / 64u * 64u)));
-            const uint32_t kt = (chunk + nt - 1) / nt;
-            const uint32_t n_chunks = (c->n_tiles + chunk - 1) / chunk;
-            const uint32_t scan_grid = std::max(1u, std::min<uint32_t>(std::min<uint32_t>(n_chunks, target), MAX_LISTS));
-            if (!c->blk_read) {
-                TRY(dmalloc(c, &c->blk_read, BLK_READ_WORDS));
-                HIPCHK(c, hipMemsetAsync(c->blk_read, 0, BLK_READ_WORDS * 8, c->stream));
-            }
-            // a stream of more chunks than workgroups (the early sparse merges: the chunk is capped by the registers of the
-            // signature sweep): the tiles behind the first round go out in pieces, to whoever finishes first (steal_logic.h)
-            const uint32_t rest = c->n_tiles - std::min<uint64_t>(c->n_tiles, (uint64_t)scan_grid * chunk);
-            const bool pieces = rest && nw == 8 && optv(c, "chunk_steal", 1);  // (the 16-wave form has no counter path: chosen where ONE round covers the stream)
-            const uint32_t piece = !rest ? 0u : pieces ? yb_piece_tiles(rest, scan_grid, chunk) : chunk;
-            // (a sparse merge leaves a workgroup a few dozen deltas: a quarter of the aggregator per merge of the batch is
-            // plenty -- less to initialise and to flush; the count of the LAST batch's merges bounds this batch's)
-            if (optv(c, "agg_small", 1) && !c->weighted && c->st_host->best_count * 4 < 48ull * std::max<uint32_t>(1u, c->n_cu * 3))
-                P.agg_mask = (uint32_t)(c->kmax_now > 2 ? AGG_N : nw >= 16 ? AGG_N / 2 : AGG_N / 4) - 1u;
-            const uint32_t rr_blocks = rank_rides ? rank_blocks : 0u;
-            ScanSkipParams SQ{P, c->blk_read, scan_grid, kt, chunk, R, fuse_params(scan_grid), LW, scan_grid + rr_blocks,
-                              piece, pieces ? yb_piece_count(rest, piece) : 0u, pieces ? c->blk_read + 2 * MAX_LISTS : nullptr,
-                              pieces ? ++c->piece_tag : 0ull, c->blk_read + MAX_LISTS};
-            c->blk_used = std::max(c->blk_used, scan_grid);
-            const uint32_t grid = scan_grid + rr_blocks + long_blocks;
-#define YB_LAUNCH_SPARSE(NW_)                                                                                        \
-    do {                                                                                                             \
-        if (c->weighted)                                                                                             \
-            hipLaunchKernelGGL((k_scan_skip<true, NW_>), dim3(grid), dim3(NW_ * 64), 0, c->stream, c->st, SQ);      \
-        else                                                                                                         \
-            hipLaunchKernelGGL((k_scan_skip<false, NW_>), dim3(grid), dim3(NW_ * 64), 0, c->stream, c->st, SQ);     \
-    } while (0)
-            if (nw == 16) YB_LAUNCH_SPARSE(16);
-            else YB_LAUNCH_SPARSE(8);
-#undef YB_LAUNCH_SPARSE
-            c->scan_skip_launches++;
-            if (ev) HIPCHK(c, hipEventRecord(ev->e1, c->stream));
-        }
-    } else if (ev) {
+    J.long_group = (uint32_t)std::min<uint64_t>(BLOCK, std::max<uint64_t>(32, cdiv64(c->n_long, 2ull * std::max(1, c->n_cu))));
+    J.LW = LongParams{c->long_tok, c->long_off, c->long_len, c->long_freq, c->n_long, J.out_table, c->st, c->long_sig, c->long_sig_stride, J.long_group};
+    const bool long_rides = J.fuse_kernel && c->n_long && c->n_tiles && J.rank_rides;
+    J.long_blocks = long_rides ? cdiv64(c->n_long, J.long_group) : 0u;
+    if (J.fuse_kernel && c->n_long && !long_rides)  // (no tile launch to ride on: on their own, first -- the fused launch must be the last one to touch the table)
+        hipLaunchKernelGGL(k_apply_long, dim3(cdiv64(c->n_long, J.long_group)), dim3(BLOCK), 0, c->stream, J.LW);
+    if (c->n_tiles) TRY(c->split_mode ? launch_sparse(R, J) : launch_streaming(R, J, tokens_upper));
+    if (ev) {
         HIPCHK(c, hipEventRecord(ev->e1, c->stream));
+        HIPCHK(c, hipEventRecord(ev->e2, c->stream));
     }
-    if (ev) HIPCHK(c, hipEventRecord(ev->e2, c->stream));
-    if (!fuse_kernel && c->n_long) hipLaunchKernelGGL(k_apply_long, dim3(cdiv64(c->n_long, long_group)), dim3(BLOCK), 0, c->stream, LW);
-    if (c->multi) {
-        // Per batch: the apply launch above left this rank's updates as [header | records] in its send buffer (the
-        // aggregator flush writes them there: no delta table, no extraction pass); ONE all-gather; ONE launch adds every
-        // rank's records to the replica and -- fused form -- selects the next merges in its last workgroup.
-        const uint64_t xbytes = 16 + (uint64_t)c->xeff * sizeof(DeltaRec);  // [header | xeff records] per rank, packed at that stride
-        const uint8_t *recv = c->xrecv;
-        uint64_t rstride = xbytes;
-        if (c->p2p) {  // push into the peers' memory, wait for theirs: one small launch, no collective
-            XchgParams X{};
-            X.send = c->xsend;
-            for (int r = 0; r < c->n_ranks; ++r) X.peer[r] = c->p2p_peer[r];
-            X.flags_off = c->p2p_flags_off;
-            X.half_bytes = c->p2p_half;
-            X.stride = c->p2p_stride;
-            X.seq = ++c->p2p_seq;
-            X.rank = (uint32_t)c->rank;
-            X.n_ranks = (uint32_t)c->n_ranks;
-            X.cap = c->xeff;
-            X.timeout_ticks = (unsigned long long)optv(c, "p2p_timeout_ms", 20000) * 100000ull;
-            X.st = c->st;
-            const bool timed = !c->p2p_pending && c->p2p_e0;  // (one exchange per round of launches is timed)
-            if (timed) HIPCHK(c, hipEventRecord(c->p2p_e0, c->stream));
-            hipLaunchKernelGGL(k_xchg_push, dim3((uint32_t)c->n_ranks), dim3(BLOCK), 0, c->stream, X);
-            if (timed) {
-                HIPCHK(c, hipEventRecord(c->p2p_e1, c->stream));
-                c->p2p_pending = true;  // (read at the end of this round of launches)
-            }
-            recv = c->p2p_area + (X.seq & 1ull) * c->p2p_half;
-            rstride = c->p2p_stride;
-        } else {
-            TRY(comm_allgather(c, c->xsend, c->xrecv, xbytes));
-        }
-        c->xeff_sum += c->xeff;
-        DeltaApplyParams DA{recv, (uint32_t)c->n_ranks, c->xeff, rstride, c->table, c->st, FuseParams{}, c->p2p ? 1u : 0u};
-        if (fuse) {
-            DA.F.ticket = c->sel_ticket;
-            DA.F.sel = select_params(c, rec_base, 0u, c->blk_used);
-        }
-        hipLaunchKernelGGL(k_delta_apply, dim3(cdiv64((uint64_t)c->n_ranks * c->xeff, DELTA_RPW)), dim3(BLOCK), 0, c->stream, DA);
-        c->exchanges++;
-    }
+    if (!J.fuse_kernel && c->n_long) hipLaunchKernelGGL(k_apply_long, dim3(cdiv64(c->n_long, J.long_group)), dim3(BLOCK), 0, c->stream, J.LW);
+    if (c->multi) TRY(launch_exchange(R, J));
     if (fuse) {
         c->blk_used = 0;  // folded by the selection at the end of that launch
         c->fused_launches++;
@@ -1737,22 +1984,340 @@ static int launch_apply(yabpe_ctx *c, uint32_t rec_base, uint32_t tokens_upper, 
     return 0;
 }
 
-namespace {
-// the timing events of one yabpe_train call: destroyed on every way out
-struct TrainEvents {
-    hipEvent_t t0 = nullptr, t1 = nullptr, t_split = nullptr, t_tail = nullptr;
-    int create() {
-        return (hipEventCreate(&t0) == hipSuccess && hipEventCreate(&t1) == hipSuccess && hipEventCreate(&t_split) == hipSuccess &&
-                hipEventCreate(&t_tail) == hipSuccess) ? 0 : -1;
+// ---- a round: prepare, launch, read, recover, housekeeping
+// The argmax grid sized to the table, the form, the measurement marks, the candidate list and the signatures kept up, the
+// batch limit on the device, records for everything the round can select.
+int round_prepare(TrainRun &R) {
+    yabpe_ctx *c = R.c;
+    DevState *h = R.h;
+    const TrainOpts &O = R.O;
+    const uint32_t i = R.i;
+    const uint32_t want_partials = partials_rule(c->table_cap);
+    if (want_partials != c->n_partials) {
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        dfree(c->partials);
+        c->partials = nullptr;
+        c->n_partials_cap = std::max<uint32_t>(want_partials, 64);
+        TRY(dmalloc(c, &c->partials, c->n_partials_cap));
+        c->n_partials = want_partials;
     }
-    ~TrainEvents() {
-        if (t0) (void)hipEventDestroy(t0);
-        if (t1) (void)hipEventDestroy(t1);
-        if (t_split) (void)hipEventDestroy(t_split);
-        if (t_tail) (void)hipEventDestroy(t_tail);
+    R.apply_grid = count_grid_rule(c->n_tiles, (uint32_t)c->n_cu, (uint32_t)c->apply_occ, O.apply_blocks);
+    R.sparse_now = sparse_now_rule(O.split, R.sparse_global);
+    c->split_mode = R.sparse_now && c->n_tiles;  // (a rank without tiles launches no apply kernel, but selects like the others)
+    if (!R.tail_marked && i >= R.num_merges / 2) {
+        R.tail_marked = true;
+        R.tail_at = i;
+        R.launches_at_tail = R.launches_sparse;
+        HIPCHK(c, hipEventRecord(R.ev.e[3], c->stream));
     }
-};
+    if (c->split_mode && !R.split_marked) {
+        R.split_marked = true;
+        R.split_at = i;
+        R.dense_applied = i - std::min<uint32_t>(i, c->pending ? h->n_batch : 0u);
+        R.launches_dense = h->n_select - std::min<uint32_t>(h->n_select, c->pending ? 1u : 0u);  // (selections that committed a batch = launches with work; launches queued behind a stop flag return at once)
+        HIPCHK(c, hipEventRecord(R.ev.e[2], c->stream));
+    }
+    if (R.skip_cand_once) {
+        c->use_cand = false;
+        R.skip_cand_once = false;
+    } else if (h->iter > R.rec_base) {
+        if (cand_rebuild_rule(c->use_cand, i, c->cand_built_at, O.cand_rebuild_every, h->best_count, c->table.cand_T, R.prev_best, R.cand_n_all, O.cand_target)) {
+            trace(R, "cand_rebuild at %u", i);
+            TRY(cand_rebuild(c, h->best_count));
+            c->cand_built_at = i;
+            c->cand_best_at_build = h->best_count;
+        }
+        R.prev_best = h->best_count;
+    }
+    if (c->split_mode && sig_rebuild_rule(c->sig_valid, i, c->sig_built_at, O.sig_rebuild_every, c->sig_tokens_at_build, h->tokens_now, O.sig_rebuild_pct)) {
+        trace(R, "build_signatures at %u", i);
+        TRY(build_signatures(c));
+        c->sig_valid = true;
+        c->sig_built_at = i;
+    }
+    R.kmax = round_kmax_rule(R.sparse_now, O.batch_max);
+    if (R.kmax != c->kmax_now) {
+        HIPCHK(c, hipMemcpyAsync(&c->st->kmax, &R.kmax, sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+        c->kmax_now = R.kmax;
+        h->kmax = R.kmax;
+    }
+    R.n_launch = round_launches_rule(R.first_round, R.sparse_now, O.check);
+    R.first_round = false;
+    TRY(reserve_records(c, round_records_rule(R.num_merges, i, R.n_launch, R.kmax), i));
+    return 0;
+}
+
+// Fused form: one launch applies the pending merges and selects the next ones; otherwise a merge is a selection launch
+// followed by its apply launch(es).  `i` counts selected merges exactly while one launch selects one merge (streaming
+// form, unfused); in the sparse form a launch selects a batch and `i` is a lower bound until the next read.
+int round_launch(TrainRun &R) {
+    yabpe_ctx *c = R.c;
+    const uint32_t num_merges = R.num_merges, kmax = R.kmax;
+    uint32_t &i = R.i;
+    const bool fuse = R.fuse = can_fuse(R);
+    const uint32_t tok_upper0 = R.h->n_tokens;
+    uint32_t launched = 0;
+    if (c->pending && !fuse) {  // leave the fused form: the selected merges are applied on their own
+        TRY(launch_merges(R, tok_upper0 + kmax, sample_launch(R, i ? i - 1 : 0), false));
+        c->pending = false;
+    }
+    if (fuse && !c->pending && i < num_merges) {  // enter it: a selection on its own
+        TRY(launch_select(c, R.rec_base));
+        c->pending = true;
+        ++i;
+    }
+    for (uint32_t l = 0; l < R.n_launch && i < num_merges + (fuse ? 1u : 0u); ++l) {
+        ++launched;
+        const uint32_t tok_upper = tok_upper_rule(tok_upper0, launched, kmax);
+        if (fuse) {
+            // (i == num_merges: every merge is selected, the last ones are pending -- this launch applies them and its
+            // selection finds the limit reached: done.  An apply launch must never run twice on one selection: in the
+            // multi-GPU form the send buffer would still hold the records of the first time.)
+            const bool last = i >= num_merges;
+            TRY(launch_merges(R, tok_upper, sample_launch(R, i - 1), true));
+            if (kmax == 1) ++i; else if (R.sparse_now) ++R.launches_sparse;  // (a batch per launch: i stays a lower bound until the next read)
+            if (last) break;
+        } else {
+            TRY(launch_select(c, R.rec_base));
+            TRY(launch_merges(R, tok_upper, sample_launch(R, i), false));
+            ++i;
+        }
+    }
+    trace(R, "round of %u launches queued (p2p seq %llu), waiting", launched, (unsigned long long)c->p2p_seq);
+    return 0;
+}
+
+// What the device really did: the state, the timed exchange, the next exchange's size, this shard's wish for the sparse
+// form -- and (multi-GPU) the ranks' agreement on all of it.
+int round_read(TrainRun &R) {
+    yabpe_ctx *c = R.c;
+    DevState *h = R.h;
+    const TrainOpts &O = R.O;
+    TRY(fold_stats(c));
+    TRY(state_pull(c));
+    R.i = h->iter - R.rec_base;
+    trace(R, "round done: %u merges, halt %u req %u done %u", R.i, h->halt, h->halt_req, h->done);
+    if (c->p2p_pending) {  // (the stream is idle: the pair has completed)
+        float xms = 0;
+        if (hipEventElapsedTime(&xms, c->p2p_e0, c->p2p_e1) == hipSuccess) {
+            c->stats.exchange_ms_sampled += xms;
+            c->stats.exchanges_sampled += 1;
+        } else {
+            (void)hipGetLastError();
+        }
+        c->p2p_pending = false;
+    }
+    if (h->halt_req && !h->halt) h->halt = h->halt_req;  // raised by the last apply of the batch
+    if (h->done || h->halt) c->pending = false;          // the last selection of the batch did not select
+    if (c->multi && c->xrecv) {
+        // what the exchanges of this round really carried (the largest count of any rank, the same number on every rank)
+        const uint32_t seen = h->xmax;
+        c->exchange_max_records = std::max<uint64_t>(c->exchange_max_records, seen);
+        c->xseen[3] = c->xseen[2]; c->xseen[2] = c->xseen[1]; c->xseen[1] = c->xseen[0]; c->xseen[0] = seen;
+        // (nothing shrinks during the first rounds of a job, whose merges differ most from one another)
+        if (O.delta_adapt && h->halt != HALT_DELTA_FULL && h->iter - R.rec_base >= 4 * O.check)
+            c->xeff = xeff_next_rule(c->xseen, c->xcap, O.delta_headroom_pct, O.delta_margin, O.delta_granule, O.delta_floor);
+        if (O.trace_exchange && c->rank == 0) fprintf(stderr, "[yabpe] exchange: merges %u records<= %u next %u halt %u\n", h->iter - R.rec_base, seen, c->xeff, h->halt);
+        HIPCHK(c, hipMemsetAsync(&c->st->xmax, 0, sizeof(uint32_t), c->stream));
+        h->xmax = 0;
+    }
+    R.cand_n_all = h->cand_n;
+    unsigned long long want_sparse = want_sparse_rule(c->n_tiles, h->iter > R.rec_base, c->weighted, h->sites, h->best_count, O.split_pct) ? 1 : 0;
+    if (c->multi) {  // replicas must be in lockstep: same merge count, same flags
+        unsigned long long sig = ((unsigned long long)h->iter << 8) | (h->done ? 1u : 0u) | ((unsigned long long)(h->halt & 0x3f) << 1);
+        // ... and agree on what must not differ between them: the batch limit follows the form (any rank sparse: all of
+        // them), the candidate list is rebuilt for the longest replica's length
+        unsigned long long v[3] = {sig, h->cand_n, want_sparse};
+        trace(R, "comm_max3");
+        TRY(comm_max3(c, v));
+        trace(R, "comm_max3 back");
+        if (v[0] != sig) return fail(c, YABPE_E_COMM, "ranks diverged (iter/flags %llx vs max %llx)", sig, v[0]);
+        R.cand_n_all = (uint32_t)v[1];
+        want_sparse = v[2];
+    }
+    if (want_sparse) R.sparse_global = true;
+    return 0;
+}
+
+// Services a halt.  *next: run the round again (after a repair), stop (the call's merges are done), or go on.
+int round_recover(TrainRun &R, RoundNext *next) {
+    yabpe_ctx *c = R.c;
+    DevState *h = R.h;
+    *next = ROUND_AGAIN;
+    if (h->halt == HALT_RESCAN) {  // the candidate set could not prove the maximum: redo that merge with the full scan
+        h->halt = 0; h->halt_req = 0;
+        TRY(state_push(c));
+        c->cand_rescans++;
+        R.skip_cand_once = true;
+        unsample_from(R);
+        return 0;
+    }
+    if (h->halt == HALT_TABLE_FULL || h->halt == HALT_DELTA_FULL) {
+        // the streams are consistent (the apply pass finished everywhere); only table updates were lost:
+        // rebuild the table from the token streams, bigger
+        const bool delta_full = h->halt == HALT_DELTA_FULL;
+        h->halt = 0; h->halt_req = 0;
+        TRY(state_push(c));
+        if (delta_full) {
+            if (c->xeff < c->xcap) {
+                c->xeff = xeff_after_full_rule(c->xeff, c->xcap);  // (the buffers hold more: no reallocation)
+            } else {
+                trace(R, "comm_buffers %u -> %u", c->xcap, c->xcap * 4);
+                TRY(comm_buffers(c, c->xcap * 4));
+            }
+            c->exchange_growths++;
+        }
+        trace(R, "table_rebuild (delta_full %d)", (int)delta_full);
+        TRY(table_rebuild(c, delta_full ? c->table_cap : c->table_cap * 4));
+        trace(R, "table_rebuild back");
+        TRY(state_pull(c));
+        R.i = h->iter - R.rec_base;  // resume after the last recorded merge
+        unsample_from(R);
+        return 0;
+    }
+    if (h->halt == HALT_COMM) {
+        // what this rank's receive area holds: the exchange it waited for last, and the flags of both halves per sender
+        std::string seen;
+        if (c->p2p && c->p2p_area) {
+            std::vector<unsigned long long> fl(2 * (size_t)c->n_ranks);
+            if (hipMemcpy(fl.data(), c->p2p_area + c->p2p_flags_off, fl.size() * 8, hipMemcpyDeviceToHost) == hipSuccess)
+                for (size_t q = 0; q < fl.size(); ++q) seen += (q ? " " : "") + std::to_string(fl[q]);
+            else
+                (void)hipGetLastError();
+        }
+        return fail(c, YABPE_E_COMM, "a peer's records did not arrive within the time limit (peer-to-peer exchange) after %u merges; rank %d launched exchange %llu, "
+                    "flags in its receive area [half][sender]: %s", h->iter - R.rec_base, c->rank, (unsigned long long)c->p2p_seq, seen.c_str());
+    }
+    if (h->halt) {
+        const char *why = h->halt == HALT_POOL_FULL ? "token byte pool exhausted (option pool_bytes)"
+                          : h->halt == HALT_VOCAB_FULL ? "u16 token id space exhausted"
+                                                       : "device halt";
+        return fail(c, YABPE_E_CAPACITY, "%s after %u merges", why, h->iter - R.rec_base);
+    }
+    *next = (h->done || (R.i >= R.num_merges && !c->pending)) ? ROUND_STOP : ROUND_NEXT;
+    return 0;
+}
+
+// between rounds: the table's load and the stream's fill (the same decisions on every rank)
+int round_housekeeping(TrainRun &R) {
+    yabpe_ctx *c = R.c;
+    DevState *h = R.h;
+    if (table_grow_rule(h->table_entries, c->table_cap, R.O.table_load_pct)) {
+        trace(R, "table_grow");
+        TRY(table_grow(c, table_grow_target_rule(h->table_entries, R.O.table_grow_x, 1ull << 16)));
+        trace(R, "table_grow back");
+    }
+    if (!c->weighted && retile_rule(c->n_tiles, R.O.retile_min_tiles, h->live_slots, R.O.retile_pct, SPAN)) {
+        trace(R, "retile");
+        TRY(retile_flat(c));
+    }
+    return 0;
+}
+
+// ---- the end of a call
+// stops the clock, closes the log of the last iteration (the remaining sites folded into T_i), hands the merges out
+int train_close(TrainRun &R, uint32_t *out_left, uint32_t *out_right, uint32_t *out_merged, uint64_t *out_count, uint32_t *out_n_merges) {
+    yabpe_ctx *c = R.c;
+    DevState *h = R.h;
+    HIPCHK(c, hipEventRecord(R.ev.e[1], c->stream));
+    HIPCHK(c, hipEventSynchronize(R.ev.e[1]));
+    TRY(state_pull(c));
+    const uint32_t n = h->iter - R.rec_base;
+    TRY(train_copy_out(c, n, true, out_left, out_right, out_merged, out_count, out_n_merges));
+    if (n) c->log_sites[n - 1] += h->sites;  // (already closed by the selection when the last launch was a fused one: then h->sites is 0)
+    uint64_t sites_all = 0;
+    for (uint32_t k = 0; k < n; ++k) sites_all += c->log_sites[k];
+    R.tokens_at_start = h->tokens_now - h->sites + sites_all;
+    h->tokens_now -= h->sites;
+    h->sites = 0;
+    TRY(state_push(c));
+    return 0;
+}
+
+// everything that only feeds yabpe_stats_t: the phases' times, the algorithmic (A_i = 2 * (T_i + W)) and
+// actual byte sums, the sampled launches
+int train_account(TrainRun &R) {
+    yabpe_ctx *c = R.c;
+    DevState *h = R.h;
+    const uint32_t n = c->rec_n;
+    const hipEvent_t t0 = R.ev.e[0], t1 = R.ev.e[1];
+    float ms = 0;
+    HIPCHK(c, hipEventElapsedTime(&ms, t0, t1));
+    if (R.split_marked) {
+        float sms = 0;
+        HIPCHK(c, hipEventElapsedTime(&sms, R.ev.e[2], t1));
+        c->stats.sparse_ms += sms;
+        c->stats.sparse_merges += n > R.split_at ? n - R.split_at : 0;
+        c->stats.sparse_launches += R.launches_sparse;
+    }
+    if (R.tail_marked) {
+        float tms = 0;
+        HIPCHK(c, hipEventElapsedTime(&tms, R.ev.e[3], t1));
+        c->stats.tail_ms += tms;
+        c->stats.tail_merges += n > R.tail_at ? n - R.tail_at : 0;
+        c->stats.tail_launches += R.launches_sparse - R.launches_at_tail;
+    }
+    c->stats.train_ms += ms;
+    uint64_t T_ = R.tokens_at_start;
+    std::vector<uint64_t> Ti(n);
+    for (uint32_t k = 0; k < n; ++k) {
+        Ti[k] = T_;
+        c->stats.algo_bytes_total += 2 * (T_ + c->n_words_input);
+        T_ -= c->log_sites[k];
+    }
+    // the streaming phase as a whole: its launches, the merges they applied, their algorithmic bytes; a launch applies a batch,
+    // so the event-timed launches get the phase's bytes per launch (merge indices of sampled launches are lower bounds)
+    uint32_t dense_applied = R.dense_applied;
+    uint64_t launches_dense = R.launches_dense;
+    if (!R.split_marked) {
+        dense_applied = n - std::min<uint32_t>(n, (c->pending && !h->done) ? h->n_batch : 0u);
+        launches_dense = h->n_select - std::min<uint32_t>(h->n_select, (c->pending && !h->done) ? 1u : 0u);
+    }
+    dense_applied = std::min(dense_applied, n);
+    uint64_t dense_algo = 0, dense_actual = 0, dense_sampled_now = 0;
+    for (uint32_t k = 0; k < dense_applied; ++k) {
+        dense_algo += 2 * (Ti[k] + c->n_words_input);
+        dense_actual += 2 * c->log_live[k] + 4ull * c->n_tiles;
+    }
+    // (actual: a pass reads the stream once for all the merges of its batch -- the first merge's live slots)
+    c->stats.dense_launches += launches_dense;
+    c->stats.dense_merges += dense_applied;
+    for (size_t e = 0; e < R.ev_next; ++e) {
+        const EventPair &E = c->events[e];
+        const uint32_t k = E.iter_rel;
+        if (k >= n) continue;
+        float ems = 0, sms = 0;
+        if (hipEventElapsedTime(&ems, E.e0, E.e2) != hipSuccess) { (void)hipGetLastError(); continue; }
+        if (hipEventElapsedTime(&sms, E.e0, E.e1) != hipSuccess) { (void)hipGetLastError(); continue; }
+        c->stats.apply_ms_sampled += ems;
+        c->ev_iter.push_back(k);
+        c->ev_us.push_back(ems * 1000.0f);
+        c->ev_scan_us.push_back(sms * 1000.0f);
+        c->stats.apply_launches_sampled += 1;
+        // streaming form: one pass over the live stream + rewrite (+ selection when fused), a batch of merges.  (A launch queued
+        // behind a stop flag -- the rest of a round after a rescan request -- returns in microseconds: not a pass.)
+        if (!E.split && ems >= 0.02f) {
+            c->stats.dense_ms_sampled += ems;
+            dense_sampled_now += 1;
+        }
+        if (E.split) {  // (sparse form: the merge index of a sampled launch is a lower bound -- launches select batches)
+            c->stats.scan_ms_sampled += sms;
+            c->stats.scan_launches_sampled += 1;
+            c->stats.scan_algo_bytes_sampled += 2 * (Ti[k] + c->n_words_input);
+            c->stats.scan_actual_bytes_sampled += 2 * c->log_live[k] + 4ull * c->n_tiles;
+        }
+        c->stats.apply_algo_bytes_sampled += 2 * (Ti[k] + c->n_words_input);
+        c->stats.apply_actual_bytes_sampled += 2 * c->log_live[k] + 4ull * c->n_tiles;
+    }
+    if (launches_dense && dense_sampled_now) {
+        c->stats.dense_launches_sampled += dense_sampled_now;
+        c->stats.dense_algo_bytes_sampled += dense_algo * dense_sampled_now / launches_dense;
+        c->stats.dense_actual_bytes_sampled += dense_applied ? dense_actual / dense_applied * dense_sampled_now : 0;  // (one read of the live stream per launch)
+    }
+    return 0;
+}
 }  // namespace
+}  // extern "C++"
 
 int yabpe_train(yabpe_ctx *c, uint32_t num_merges, uint64_t min_frequency, uint32_t *out_left, uint32_t *out_right,
                 uint32_t *out_merged, uint64_t *out_count, uint32_t *out_n_merges) {
@@ -1761,442 +2326,35 @@ int yabpe_train(yabpe_ctx *c, uint32_t num_merges, uint64_t min_frequency, uint3
     if (!c->have_words) return fail(c, YABPE_E_INVALID, "call yabpe_load_words first");
     if (out_n_merges) *out_n_merges = 0;
     if (c->id_bits == 32) return id32_train(c, num_merges, min_frequency, out_left, out_right, out_merged, out_count, out_n_merges);
-    TRY(state_pull(c));
-    DevState *h = c->st_host;
     // The u16 id space bounds the vocabulary at YB_MAX_TOKENS; the reference has no such bound (trainer.py:238, 298-300).  A
     // merge that re-creates the bytes of an existing token takes no id (trainer.py:298), so the number of merges a job can run
     // is not bounded by the ids that are left: the request stands as it is, and only when the loop needs an id past the last
-    // one does the selection stop it (HALT_VOCAB_FULL -> YABPE_E_CAPACITY below) -- reported, never silently truncated.
-    // Most such jobs end long before (no pairs left, min_frequency); the per-merge records grow as the loop proceeds.
-    const uint32_t rec_base = h->iter;
-    if ((uint64_t)rec_base + num_merges > 0xFFFFFFF0ull) return fail(c, YABPE_E_CAPACITY, "more than 2^32 merges in one context");
-    h->num_merges = rec_base + num_merges;
-    h->min_freq = min_frequency;
-    h->done = 0;
-    h->halt = 0;
-    h->halt_req = 0;
-    h->n_batch = 0;
-    h->n_select = 0;
-    h->batch_others = 0;
-    h->kmax = 1;
-    h->win_shift = 3;
-    TRY(state_push(c));
+    // one does the selection stop it (HALT_VOCAB_FULL -> YABPE_E_CAPACITY in round_recover) -- reported, never silently
+    // truncated.  Most such jobs end long before (no pairs left, min_frequency); the per-merge records grow as the loop proceeds.
+    TrainRun R{};
+    R.c = c;
+    R.h = c->st_host;
+    R.num_merges = num_merges;
+    TRY(train_begin(c, num_merges, min_frequency, &R.rec_base));
     c->kmax_now = 1;
-    c->rec_n = 0;
-    c->log_sites.clear();
-    c->log_live.clear();
-    c->ev_iter.clear();
-    c->ev_us.clear();
-    c->ev_scan_us.clear();
     c->split_mode = false;
     c->sig_valid = false;
     if (num_merges == 0) return YABPE_OK;
-
-    // per-merge records: a job cannot run more merges than it has ids for plus the (rare) merges that reuse one; room for the
-    // ids, grown below if a job really gets past that
-    auto ensure_records = [&](uint32_t need) -> int {
-        if (c->rec_cap >= need) return 0;
-        const uint32_t ncap = std::max<uint32_t>(need, c->rec_cap + c->rec_cap / 2);
-        uint32_t *nl = nullptr, *nr = nullptr, *nm = nullptr;
-        unsigned long long *nc = nullptr, *ns = nullptr, *nv = nullptr;
-        TRY(dmalloc(c, &nl, ncap)); TRY(dmalloc(c, &nr, ncap)); TRY(dmalloc(c, &nm, ncap));
-        TRY(dmalloc(c, &nc, ncap)); TRY(dmalloc(c, &ns, ncap)); TRY(dmalloc(c, &nv, ncap));
-        HIPCHK(c, hipMemsetAsync(ns, 0, (size_t)ncap * 8, c->stream));
-        if (c->rec_cap && c->rec_n_live) {
-            const size_t n = c->rec_n_live;
-            HIPCHK(c, hipMemcpyAsync(nl, c->rec_left, n * 4, hipMemcpyDeviceToDevice, c->stream));
-            HIPCHK(c, hipMemcpyAsync(nr, c->rec_right, n * 4, hipMemcpyDeviceToDevice, c->stream));
-            HIPCHK(c, hipMemcpyAsync(nm, c->rec_merged, n * 4, hipMemcpyDeviceToDevice, c->stream));
-            HIPCHK(c, hipMemcpyAsync(nc, c->rec_count, n * 8, hipMemcpyDeviceToDevice, c->stream));
-            HIPCHK(c, hipMemcpyAsync(ns, c->rec_sites, n * 8, hipMemcpyDeviceToDevice, c->stream));
-            HIPCHK(c, hipMemcpyAsync(nv, c->rec_live, n * 8, hipMemcpyDeviceToDevice, c->stream));
-        }
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        free_records(c);
-        c->rec_left = nl; c->rec_right = nr; c->rec_merged = nm; c->rec_count = nc; c->rec_sites = ns; c->rec_live = nv;
-        c->rec_cap = ncap;
-        return 0;
-    };
-    c->rec_n_live = 0;
-    const uint32_t rec_first = (uint32_t)std::min<uint64_t>(num_merges, (uint64_t)YB_MAX_TOKENS + 4096);
-    if (c->rec_cap < rec_first) { free_records(c); }
-    TRY(ensure_records(rec_first));
-    HIPCHK(c, hipMemsetAsync(c->rec_sites, 0, (size_t)c->rec_cap * 8, c->stream));
-
-    const uint32_t check = (uint32_t)std::max<int64_t>(1, optv(c, "check_interval", 32));
-    const uint32_t ev_sample = (uint32_t)std::max<int64_t>(0, optv(c, "event_sample", 0));
-    const uint32_t ev_sample_dense = (uint32_t)std::max<int64_t>(0, optv(c, "event_sample_dense", (int64_t)ev_sample));  // fused k_apply launches
-    const double retile_frac = (double)optv(c, "retile_pct", 60) / 100.0;
-    const uint64_t retile_min_tiles = (uint64_t)optv(c, "retile_min_tiles", 4096);
-    size_t ev_next = 0;
-
-    TrainEvents T;
-    if (T.create() != 0) return fail(c, YABPE_E_HIP, "event creation failed");
-    HIPCHK(c, hipEventRecord(T.t0, c->stream));
-    bool split_marked = false, tail_marked = false;
-    uint32_t split_at = 0, tail_at = 0;
-
-    uint32_t i = 0;  // merges selected so far in this call (read back from the device between batches of launches)
-    const bool trace_host = optv(c, "trace_host", 0) != 0;  // (debugging a stuck multi-GPU job: where is this rank's host?)
-#define YB_TRACE(...) do { if (trace_host) { fprintf(stderr, "[yabpe r%d] ", c->rank); fprintf(stderr, __VA_ARGS__); fprintf(stderr, "\n"); fflush(stderr); } } while (0)
-    bool finished = false;
-    bool skip_cand_once = false;
-    bool first_round = true;
-    unsigned long long prev_best = 0;
-    uint64_t launches_sparse = 0, launches_at_tail = 0, launches_dense = 0, launch_no = 0;
-    uint32_t dense_applied = 0;  // merges the streaming launches applied (what was selected when the form changed, less the pending batch)
-    uint32_t cand_n_all = 0;  // length of the candidate list at the last read (multi-GPU: of the longest replica's)
-    bool sparse_global = false;  // the sparse form has been called for (by any rank)
+    TRY(train_begin_records(c, rec_first_rule(num_merges)));
+    R.O = train_opts(c);
+    if (R.ev.create() != hipSuccess) return fail(c, YABPE_E_HIP, "event creation failed");
+    HIPCHK(c, hipEventRecord(R.ev.e[0], c->stream));
     c->use_cand = false;
     c->pending = false;
-    while (!finished) {
-        // (re)size the argmax grid to the table
-        uint32_t want_partials = (uint32_t)std::min<uint64_t>(1024, std::max<uint64_t>(1, c->table_cap / (BLOCK * 8)));
-        if (want_partials != c->n_partials) {
-            HIPCHK(c, hipStreamSynchronize(c->stream));
-            dfree(c->partials);
-            c->partials = nullptr;
-            c->n_partials_cap = std::max<uint32_t>(want_partials, 64);
-            TRY(dmalloc(c, &c->partials, c->n_partials_cap));
-            c->n_partials = want_partials;
-        }
-        const uint32_t apply_grid = count_grid(c);
-        // sites per merge never increase (the best count is monotone): once they are sparse relative to the
-        // number of tiles, switch from the streaming kernel to the skip index + rewrite for good
-        const int64_t split_opt = optv(c, "split", -1);  // -1 auto (see want_sparse below: for good, and for all ranks), 0 never, 1 always
-        const bool sparse_now = split_opt >= 0 ? split_opt == 1 : sparse_global;
-        c->split_mode = sparse_now && c->n_tiles;  // (a rank without tiles launches no apply kernel, but selects like the others)
-        if (!tail_marked && i >= num_merges / 2) {  // (measurement: the second half of this call's merges)
-            tail_marked = true;
-            tail_at = i;
-            launches_at_tail = launches_sparse;
-            HIPCHK(c, hipEventRecord(T.t_tail, c->stream));
-        }
-        if (c->split_mode && !split_marked) {  // (measurement: where the streaming phase ends and the sparse phase begins)
-            split_marked = true;
-            split_at = i;
-            dense_applied = i - std::min<uint32_t>(i, c->pending ? h->n_batch : 0u);
-            launches_dense = h->n_select - std::min<uint32_t>(h->n_select, c->pending ? 1u : 0u);  // (selections that committed a batch = launches with work; launches queued behind a stop flag return at once)
-            HIPCHK(c, hipEventRecord(T.t_split, c->stream));
-        }
-        if (skip_cand_once) {  // the last batch hit HALT_RESCAN: finish it with the full scan
-            c->use_cand = false;
-            skip_cand_once = false;
-        } else if (h->iter > rec_base) {
-            // The list stays exact for as long as the maximum stays >= its threshold T (slots that rise are appended by
-            // the argmax itself), so it is rebuilt -- a scan of the whole table -- only now and then: when there is none
-            // (start, table rebuilt or grown, fallback), and every `cand_rebuild_every` merges to keep it short.
-            const uint32_t every = (uint32_t)std::max<int64_t>(1, optv(c, "cand_rebuild_every", 512));
-            // ... and before the maximum can reach T within the next two batches at the pace of the last one: a fallback
-            // costs the rest of a batch.  Early in a run the best count falls fast, so the list is rebuilt every batch
-            // there; late in the run hardly ever.  A list that has grown long (appended slots) is rebuilt too: the fused
-            // selection is one workgroup reading all of it.
-            const unsigned long long drop = prev_best > h->best_count ? prev_best - h->best_count : 0;
-            const bool near_T = h->best_count < c->table.cand_T + 2 * drop + 1;
-            // (multi-GPU: a pair can be listed more often on one replica than on another -- the longest list decides for all,
-            // every rank must rebuild at the same merges or their thresholds T drift apart)
-            const bool long_list = cand_n_all > std::max<uint32_t>(4u * BLOCK - 64u, (uint32_t)optv(c, "cand_target", 768));  // (one pass of the fused selection: 4 entries per thread)
-            if (!c->use_cand || i - c->cand_built_at >= every || i < c->cand_built_at || near_T || long_list) {
-                YB_TRACE("cand_rebuild at %u", i);
-                TRY(cand_rebuild(c, h->best_count));
-                c->cand_built_at = i;
-                c->cand_best_at_build = h->best_count;
-            }
-            prev_best = h->best_count;
-        }
-        if (c->split_mode) {
-            // signatures are built when the sparse form starts and refreshed now and then
-            // (rewrites only ever ADD bits: every merged site leaves up to two new pairs and three stale ones behind)
-            const uint32_t every = (uint32_t)std::max<int64_t>(1, optv(c, "sig_rebuild_every", 16384));
-            const uint64_t merged_since = c->sig_tokens_at_build > h->tokens_now ? c->sig_tokens_at_build - h->tokens_now : 0;
-            const bool stale = merged_since * 100 > c->sig_tokens_at_build * (uint64_t)optv(c, "sig_rebuild_pct", 20);
-            if (!c->sig_valid || i - c->sig_built_at >= every || i < c->sig_built_at || stale) {
-                YB_TRACE("build_signatures at %u", i);
-                TRY(build_signatures(c));
-                c->sig_valid = true;
-                c->sig_built_at = i;
-            }
-        }
-        // merges one selection may take: a batch in the sparse form.  The streaming form applies one merge per pass: a pass that
-        // applies a batch was built and measured (DESIGN (c)) -- a tenth slower per pass, and the first merges of a job hardly ever
-        // batch (they are the consecutive pairs of the most frequent words: rule (1))
-        const uint32_t kmax = sparse_now ? (uint32_t)std::max<int64_t>(1, std::min<int64_t>(KMAX, optv(c, "batch_max", KMAX))) : 1u;
-        if (kmax != c->kmax_now) {
-            HIPCHK(c, hipMemcpyAsync(&c->st->kmax, &kmax, sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
-            c->kmax_now = kmax;
-            h->kmax = kmax;
-        }
-        // records for everything the launches of this round can select
-        const uint32_t n_launch = (first_round && !sparse_now) ? std::min<uint32_t>(check, 8) : check;  // (the same on every rank: a launch is an exchange)
-        first_round = false;
-        c->rec_n_live = i;
-        TRY(ensure_records((uint32_t)std::min<uint64_t>(num_merges, (uint64_t)i + (uint64_t)(n_launch + 2) * kmax)));
-        auto sample = [&](uint32_t iter_rel) -> EventPair * {  // (every Nth LAUNCH; iter_rel: the merges selected so far, a lower bound in the fused forms)
-            const uint32_t every = c->split_mode ? ev_sample : ev_sample_dense;
-            if (!every || (launch_no++ % every) != 0) return nullptr;
-            if (ev_next == c->events.size()) {
-                EventPair n{};
-                if (hipEventCreate(&n.e0) != hipSuccess || hipEventCreate(&n.e1) != hipSuccess || hipEventCreate(&n.e2) != hipSuccess) return nullptr;
-                c->events.push_back(n);
-            }
-            c->events[ev_next].iter_rel = iter_rel;
-            return &c->events[ev_next++];
-        };
-        // Fused form: one launch applies the pending merges and selects the next ones; otherwise a merge is a selection
-        // launch followed by its apply launch(es).  `i` counts selected merges exactly while one launch selects one merge
-        // (streaming form, unfused); in the sparse form a launch selects a batch and `i` is a lower bound until the next read.
-        const bool fuse = can_fuse(c);
-        const uint32_t tok_upper0 = h->n_tokens;
-        uint32_t launched = 0;
-        if (c->pending && !fuse) {  // leave the fused form: the selected merges are applied on their own
-            TRY(launch_apply(c, rec_base, tok_upper0 + kmax, apply_grid, sample(i ? i - 1 : 0), false));
-            c->pending = false;
-        }
-        if (fuse && !c->pending && i < num_merges) {  // enter it: a selection on its own
-            TRY(launch_select(c, rec_base));
-            c->pending = true;
-            ++i;
-        }
-        for (uint32_t l = 0; l < n_launch && i < num_merges + (fuse ? 1u : 0u); ++l) {
-            ++launched;
-            const uint32_t tok_upper = tok_upper0 + (launched + 1u) * kmax + 1u;
-            if (fuse) {
-                // (i == num_merges: every merge is selected, the last ones are pending -- this launch applies them and its
-                // selection finds the limit reached: done.  An apply launch must never run twice on one selection: in the
-                // multi-GPU form the send buffer would still hold the records of the first time.)
-                const bool last = i >= num_merges;
-                TRY(launch_apply(c, rec_base, tok_upper, apply_grid, sample(i - 1), true));
-                if (kmax == 1) ++i; else if (sparse_now) ++launches_sparse;  // (a batch per launch: i stays a lower bound until the next read)
-                if (last) break;
-            } else {
-                TRY(launch_select(c, rec_base));
-                TRY(launch_apply(c, rec_base, tok_upper, apply_grid, sample(i), false));
-                ++i;
-            }
-        }
-        YB_TRACE("round of %u launches queued (p2p seq %llu), waiting", launched, (unsigned long long)c->p2p_seq);
-        TRY(fold_stats(c));
-        TRY(state_pull(c));
-        i = h->iter - rec_base;                              // what the device really selected
-        YB_TRACE("round done: %u merges, halt %u req %u done %u", i, h->halt, h->halt_req, h->done);
-        if (c->p2p_pending) {  // (the stream is idle: the pair has completed)
-            float xms = 0;
-            if (hipEventElapsedTime(&xms, c->p2p_e0, c->p2p_e1) == hipSuccess) {
-                c->stats.exchange_ms_sampled += xms;
-                c->stats.exchanges_sampled += 1;
-            } else {
-                (void)hipGetLastError();
-            }
-            c->p2p_pending = false;
-        }
-        if (h->halt_req && !h->halt) h->halt = h->halt_req;  // raised by the last apply of the batch
-        if (h->done || h->halt) c->pending = false;          // the last selection of the batch did not select
-        if (c->multi && c->xrecv) {
-            // what the exchanges of this batch really carried (the largest count of any rank, the same number on every rank):
-            // the next batch transmits twice that plus a margin, never less than 2,048 records, never more than the buffers hold
-            const uint32_t seen = h->xmax;
-            c->exchange_max_records = std::max<uint64_t>(c->exchange_max_records, seen);
-            c->xseen[3] = c->xseen[2]; c->xseen[2] = c->xseen[1]; c->xseen[1] = c->xseen[0]; c->xseen[0] = seen;
-            if (optv(c, "delta_adapt", 1) && h->halt != HALT_DELTA_FULL && h->iter - rec_base >= 4 * check) {
-                // (an overflow costs a recount of the whole stream: twice the largest count of the last four batches, and
-                // nothing shrinks during the first batches of a job, whose merges differ most from one another)
-                const uint64_t recent = std::max(std::max(c->xseen[0], c->xseen[1]), std::max(c->xseen[2], c->xseen[3]));
-                const uint64_t gran = (uint64_t)std::max<int64_t>(1, optv(c, "delta_granule", 1024));
-                const uint64_t raw = recent * (uint64_t)std::max<int64_t>(1, optv(c, "delta_headroom_pct", 200)) / 100ull + (uint64_t)std::max<int64_t>(0, optv(c, "delta_margin", 1024));
-                const uint64_t want = ((raw + gran - 1) / gran) * gran;
-                c->xeff = (uint32_t)std::min<uint64_t>(c->xcap, std::max<uint64_t>(want, std::min<uint64_t>((uint64_t)std::max<int64_t>(1, optv(c, "delta_floor", 2048)), c->xcap)));
-            }
-            if (optv(c, "trace_exchange", 0) && c->rank == 0) fprintf(stderr, "[yabpe] exchange: merges %u records<= %u next %u halt %u\n", h->iter - rec_base, seen, c->xeff, h->halt);
-            HIPCHK(c, hipMemsetAsync(&c->st->xmax, 0, sizeof(uint32_t), c->stream));
-            h->xmax = 0;
-        }
-        cand_n_all = h->cand_n;
-        // does this rank's shard call for the sparse form?  (sites per merge never increase -- the best count is monotone: once
-        // they are sparse relative to the number of tiles.  Pooled words: the count is weighted, what matters is how many
-        // resident sites the last merge had.)
-        unsigned long long want_sparse = (c->n_tiles && h->iter > rec_base &&
-                 (c->weighted && h->sites ? h->sites : h->best_count) * 100 < (unsigned long long)c->n_tiles * (unsigned long long)optv(c, "split_pct", 100)) ? 1 : 0;
-        if (c->multi) {  // replicas must be in lockstep: same merge count, same flags
-            unsigned long long sig = ((unsigned long long)h->iter << 8) | (h->done ? 1u : 0u) | ((unsigned long long)(h->halt & 0x3f) << 1);
-            // ... and agree on what must not differ between them: the batch limit follows the form (any rank sparse: all of
-            // them), the candidate list is rebuilt for the longest replica's length
-            unsigned long long v[3] = {sig, h->cand_n, want_sparse};
-            YB_TRACE("comm_max3");
-            TRY(comm_max3(c, v));
-            YB_TRACE("comm_max3 back");
-            if (v[0] != sig) return fail(c, YABPE_E_COMM, "ranks diverged (iter/flags %llx vs max %llx)", sig, v[0]);
-            cand_n_all = (uint32_t)v[1];
-            want_sparse = v[2];
-        }
-        if (want_sparse) sparse_global = true;
-        if (h->halt == HALT_RESCAN) {  // the candidate set could not prove the maximum: redo that merge with the full scan
-            h->halt = 0; h->halt_req = 0;
-            TRY(state_push(c));
-            c->cand_rescans++;
-            skip_cand_once = true;
-            while (ev_next > 0 && c->events[ev_next - 1].iter_rel >= i) --ev_next;  // those launches did nothing: timed again in the re-run
-            continue;
-        }
-        if (h->halt) {
-            if (h->halt == HALT_TABLE_FULL || h->halt == HALT_DELTA_FULL) {
-                // the streams are consistent (the apply pass finished everywhere); only table updates were lost:
-                // rebuild the table from the token streams, bigger
-                const bool delta_full = h->halt == HALT_DELTA_FULL;
-                h->halt = 0; h->halt_req = 0;
-                TRY(state_push(c));
-                if (delta_full) {  // a merge produced more records on some rank than an exchange transmits: 4x for everybody
-                    if (c->xeff < c->xcap) {
-                        c->xeff = (uint32_t)std::min<uint64_t>(c->xcap, 4ull * c->xeff);  // (the buffers hold more: no reallocation)
-                    } else {
-                        YB_TRACE("comm_buffers %u -> %u", c->xcap, c->xcap * 4);
-                        TRY(comm_buffers(c, c->xcap * 4));
-                    }
-                    c->exchange_growths++;
-                }
-                YB_TRACE("table_rebuild (delta_full %d)", (int)delta_full);
-                TRY(table_rebuild(c, delta_full ? c->table_cap : c->table_cap * 4));
-                YB_TRACE("table_rebuild back");
-                TRY(state_pull(c));
-                i = h->iter - rec_base;  // resume after the last recorded merge
-                while (ev_next > 0 && c->events[ev_next - 1].iter_rel >= i) --ev_next;
-                continue;
-            }
-            if (h->halt == HALT_COMM) {
-                // what this rank's receive area holds: the exchange it waited for last, and the flags of both halves per sender
-                std::string seen;
-                if (c->p2p && c->p2p_area) {
-                    std::vector<unsigned long long> fl(2 * (size_t)c->n_ranks);
-                    if (hipMemcpy(fl.data(), c->p2p_area + c->p2p_flags_off, fl.size() * 8, hipMemcpyDeviceToHost) == hipSuccess)
-                        for (size_t q = 0; q < fl.size(); ++q) seen += (q ? " " : "") + std::to_string(fl[q]);
-                    else
-                        (void)hipGetLastError();
-                }
-                return fail(c, YABPE_E_COMM, "a peer's records did not arrive within the time limit (peer-to-peer exchange) after %u merges; rank %d launched exchange %llu, "
-                            "flags in its receive area [half][sender]: %s", h->iter - rec_base, c->rank, (unsigned long long)c->p2p_seq, seen.c_str());
-            }
-            const char *why = h->halt == HALT_POOL_FULL ? "token byte pool exhausted (option pool_bytes)"
-                              : h->halt == HALT_VOCAB_FULL ? "u16 token id space exhausted"
-                                                           : "device halt";
-            return fail(c, YABPE_E_CAPACITY, "%s after %u merges", why, h->iter - rec_base);
-        }
-        if (h->done || (i >= num_merges && !c->pending)) {
-            finished = true;
-            break;
-        }
-        // housekeeping between batches
-        // kept at 12-30 % load: a key that is not at its home slot costs the flush of every merge a dependent trip (the
-        // 1 GiB job: 1.60 s at 50-70 % load, 1.42 s at 12-30 %), and the table is scanned only now and then (candidate
-        // rebuilds).  Same decision on every rank.
-        if (h->table_entries * 100 > c->table_cap * (uint64_t)optv(c, "table_load_pct", 30))
-        {
-            YB_TRACE("table_grow");
-            TRY(table_grow(c, std::max<uint64_t>(h->table_entries * (uint64_t)std::max<int64_t>(2, optv(c, "table_grow_x", 8)), 1ull << 16)));
-            YB_TRACE("table_grow back");
-        }
-        if (c->n_tiles >= retile_min_tiles && !c->weighted &&
-            (double)h->live_slots < retile_frac * (double)c->n_tiles * SPAN) {
-            YB_TRACE("retile");
-            TRY(retile_flat(c));
-        }
+    for (RoundNext next = ROUND_NEXT; next != ROUND_STOP;) {
+        TRY(round_prepare(R));
+        TRY(round_launch(R));
+        TRY(round_read(R));
+        TRY(round_recover(R, &next));
+        if (next == ROUND_NEXT) TRY(round_housekeeping(R));
     }
-    HIPCHK(c, hipEventRecord(T.t1, c->stream));
-    HIPCHK(c, hipEventSynchronize(T.t1));
-    float ms = 0;
-    HIPCHK(c, hipEventElapsedTime(&ms, T.t0, T.t1));
-    if (split_marked) {
-        float sms = 0;
-        HIPCHK(c, hipEventElapsedTime(&sms, T.t_split, T.t1));
-        c->stats.sparse_ms += sms;
-        c->stats.sparse_merges += (h->iter - rec_base) > split_at ? (h->iter - rec_base) - split_at : 0;
-        c->stats.sparse_launches += launches_sparse;
-    }
-    if (tail_marked) {
-        float tms = 0;
-        HIPCHK(c, hipEventElapsedTime(&tms, T.t_tail, T.t1));
-        c->stats.tail_ms += tms;
-        c->stats.tail_merges += (h->iter - rec_base) > tail_at ? (h->iter - rec_base) - tail_at : 0;
-        c->stats.tail_launches += launches_sparse - launches_at_tail;
-    }
-    c->stats.train_ms += ms;
-
-    // close the log of the last iteration and fold the remaining sites into T_i
-    TRY(state_pull(c));
-    const uint32_t n = h->iter - rec_base;
-    c->rec_n = n;
-    c->log_sites.assign(n, 0);
-    c->log_live.assign(n, 0);
-    if (n) {
-        HIPCHK(c, hipMemcpy(c->log_sites.data(), c->rec_sites, (size_t)n * 8, hipMemcpyDeviceToHost));
-        HIPCHK(c, hipMemcpy(c->log_live.data(), c->rec_live, (size_t)n * 8, hipMemcpyDeviceToHost));
-        c->log_sites[n - 1] += h->sites;  // (already closed by the selection when the last launch was a fused one: then h->sites is 0)
-    }
-    const uint64_t tokens_at_start = h->tokens_now - h->sites + [&] { uint64_t s = 0; for (uint32_t k = 0; k < n; ++k) s += c->log_sites[k]; return s; }();
-    h->tokens_now -= h->sites;
-    h->sites = 0;
-    TRY(state_push(c));
-    // algorithmic bytes: A_i = 2 * (T_i + W)
-    {
-        uint64_t T_ = tokens_at_start;
-        std::vector<uint64_t> Ti(n);
-        for (uint32_t k = 0; k < n; ++k) {
-            Ti[k] = T_;
-            c->stats.algo_bytes_total += 2 * (T_ + c->n_words_input);
-            T_ -= c->log_sites[k];
-        }
-        // the streaming phase as a whole: its launches, the merges they applied, their algorithmic bytes; a launch applies a batch,
-        // so the event-timed launches get the phase's bytes per launch (merge indices of sampled launches are lower bounds)
-        if (!split_marked) {
-            dense_applied = n - std::min<uint32_t>(n, (c->pending && !h->done) ? h->n_batch : 0u);
-            launches_dense = h->n_select - std::min<uint32_t>(h->n_select, (c->pending && !h->done) ? 1u : 0u);
-        }
-        dense_applied = std::min(dense_applied, n);
-        uint64_t dense_algo = 0, dense_actual = 0, dense_sampled_now = 0;
-        for (uint32_t k = 0; k < dense_applied; ++k) {
-            dense_algo += 2 * (Ti[k] + c->n_words_input);
-            dense_actual += 2 * c->log_live[k] + 4ull * c->n_tiles;
-        }
-        // (actual: a pass reads the stream once for all the merges of its batch -- the first merge's live slots)
-        c->stats.dense_launches += launches_dense;
-        c->stats.dense_merges += dense_applied;
-        for (size_t e = 0; e < ev_next; ++e) {
-            uint32_t k = c->events[e].iter_rel;
-            if (k >= n) continue;
-            float ems = 0, sms = 0;
-            if (hipEventElapsedTime(&ems, c->events[e].e0, c->events[e].e2) != hipSuccess) { (void)hipGetLastError(); continue; }
-            if (hipEventElapsedTime(&sms, c->events[e].e0, c->events[e].e1) != hipSuccess) { (void)hipGetLastError(); continue; }
-            c->stats.apply_ms_sampled += ems;
-            c->ev_iter.push_back(k);
-            c->ev_us.push_back(ems * 1000.0f);
-            c->ev_scan_us.push_back(sms * 1000.0f);
-            c->stats.apply_launches_sampled += 1;
-            // streaming form: one pass over the live stream + rewrite (+ selection when fused), a batch of merges.  (A launch queued
-            // behind a stop flag -- the rest of a round after a rescan request -- returns in microseconds: not a pass.)
-            if (!c->events[e].split && ems >= 0.02f) {
-                c->stats.dense_ms_sampled += ems;
-                dense_sampled_now += 1;
-            }
-            if (c->events[e].split) {  // (sparse form: the merge index of a sampled launch is a lower bound -- launches select batches)
-                c->stats.scan_ms_sampled += sms;
-                c->stats.scan_launches_sampled += 1;
-                c->stats.scan_algo_bytes_sampled += 2 * (Ti[k] + c->n_words_input);
-                c->stats.scan_actual_bytes_sampled += 2 * c->log_live[k] + 4ull * c->n_tiles;
-            }
-            c->stats.apply_algo_bytes_sampled += 2 * (Ti[k] + c->n_words_input);
-            c->stats.apply_actual_bytes_sampled += 2 * c->log_live[k] + 4ull * c->n_tiles;
-        }
-        if (launches_dense && dense_sampled_now) {
-            c->stats.dense_launches_sampled += dense_sampled_now;
-            c->stats.dense_algo_bytes_sampled += dense_algo * dense_sampled_now / launches_dense;
-            c->stats.dense_actual_bytes_sampled += dense_applied ? dense_actual / dense_applied * dense_sampled_now : 0;  // (one read of the live stream per launch)
-        }
-    }
-    if (n) {
-        if (out_left) HIPCHK(c, hipMemcpy(out_left, c->rec_left, (size_t)n * 4, hipMemcpyDeviceToHost));
-        if (out_right) HIPCHK(c, hipMemcpy(out_right, c->rec_right, (size_t)n * 4, hipMemcpyDeviceToHost));
-        if (out_merged) HIPCHK(c, hipMemcpy(out_merged, c->rec_merged, (size_t)n * 4, hipMemcpyDeviceToHost));
-        if (out_count) HIPCHK(c, hipMemcpy(out_count, c->rec_count, (size_t)n * 8, hipMemcpyDeviceToHost));
-    }
-    if (out_n_merges) *out_n_merges = n;
+    TRY(train_close(R, out_left, out_right, out_merged, out_count, out_n_merges));
+    TRY(train_account(R));
     if (optv(c, "verify", 0)) {
         uint64_t mm = 0;
         TRY(yabpe_verify_table(c, &mm));

@@ -126,80 +126,21 @@ int id32_table_grow(yabpe_ctx *c, uint64_t new_cap) {
 }
 
 // ---------------------------------------------------------------------------------------------- vocab
-int id32_upload_vset(yabpe_ctx *c, const std::vector<TokRec> &rec, uint32_t n_tokens, uint32_t vset_cap) {
-    std::vector<unsigned long long> vset(vset_cap, VSET_EMPTY);
-    const uint32_t mask = vset_cap - 1;
-    for (uint32_t i = 0; i < n_tokens; ++i) {
-        uint32_t s = yb_vset_home(rec[i].hash, rec[i].len) & mask;
-        while (vset[s] != VSET_EMPTY) s = (s + 1) & mask;
-        vset[s] = yb_vset_entry(i, rec[i].hash);
-    }
-    dfree(c->tt.vset);
-    c->tt.vset = nullptr;
-    TRY(dmalloc(c, &c->tt.vset, vset_cap));
-    HIPCHK(c, hipMemcpy(c->tt.vset, vset.data(), (size_t)vset_cap * 8, hipMemcpyHostToDevice));
-    c->tt.vset_mask = mask;
-    return 0;
-}
-
 int id32_set_vocab(yabpe_ctx *c, const uint8_t *tok_bytes, const uint32_t *tok_off, uint32_t n_tokens) {
     if (n_tokens >= YbW32::MAX_TOKENS) return fail(c, YABPE_E_CAPACITY, "base vocabulary too large: ids run 0 .. 2^24 - 3");
-    std::vector<uint32_t> off(n_tokens), len(n_tokens), order(n_tokens);
-    std::vector<uint8_t> pool;
-    for (uint32_t i = 0; i < n_tokens; ++i) {
-        len[i] = tok_off[i + 1] - tok_off[i];
-        off[i] = (uint32_t)pool.size();
-        pool.insert(pool.end(), tok_bytes + tok_off[i], tok_bytes + tok_off[i + 1]);
-        pool.resize((pool.size() + 3) & ~(size_t)3, 0);
-        order[i] = i;
-    }
-    // the token-side capacities follow the request: the pool starts at the option and grows, the records grow with yabpe_train
+    BaseVocab V;
+    base_vocab_pack(tok_bytes, tok_off, n_tokens, V);
+    // the u32 side: the token-side capacities follow the request (the pool starts at the option and grows, up to
+    // ID32_POOL_MAX; the records grow with yabpe_train), rank 0 everywhere -- the u32 selection compares bytes
     uint64_t pool_cap = (uint64_t)optv(c, "pool_bytes", 64 << 20) & ~3ull;
-    while (pool_cap < (uint64_t)pool.size() + 64) pool_cap = pool_cap * 2 + 64;
+    while (pool_cap < (uint64_t)V.pool.size() + 64) pool_cap = pool_cap * 2 + 64;
     if (pool_cap > ID32_POOL_MAX) return fail(c, YABPE_E_CAPACITY, "base vocabulary bytes exceed the token pool");
     const uint32_t tok_cap = (uint32_t)std::min<uint64_t>(YbW32::MAX_TOKENS, (uint64_t)n_tokens + 4096);
     uint32_t vset_cap = 1u << 14;
     while (vset_cap < 2 * tok_cap) vset_cap <<= 1;
-    auto cmp = [&](uint32_t x, uint32_t y) {
-        uint32_t n = std::min(len[x], len[y]);
-        int d = memcmp(pool.data() + off[x], pool.data() + off[y], n);
-        if (d) return d < 0;
-        return len[x] < len[y];
-    };
-    std::sort(order.begin(), order.end(), cmp);
-    for (uint32_t r = 1; r < n_tokens; ++r)
-        if (!cmp(order[r - 1], order[r])) return fail(c, YABPE_E_INVALID, "duplicate token bytes in the base vocabulary (trainer.py:130)");
-    std::vector<TokRec> rec(n_tokens);
-    for (uint32_t i = 0; i < n_tokens; ++i) {
-        rec[i].rank = 0;  // (the u32 selection compares bytes: no lexrank to keep)
-        rec[i].len = len[i];
-        rec[i].hash = yb_hash_bytes(pool.data() + off[i], len[i]);
-        rec[i].pre8 = yb_pre8(pool.data() + off[i], len[i]);
-        rec[i].pad = 0;
-    }
-    dfree(c->tt.pool); dfree(c->tt.off); dfree(c->tt.len); dfree(c->tt.rec);
-    c->tt.pool = nullptr; c->tt.off = c->tt.len = nullptr; c->tt.rec = nullptr;
-    TRY(dmalloc(c, &c->tt.pool, pool_cap));
-    TRY(dmalloc(c, &c->tt.off, tok_cap));
-    TRY(dmalloc(c, &c->tt.len, tok_cap));
-    TRY(dmalloc(c, &c->tt.rec, tok_cap));
-    c->tt.pool_cap = (uint32_t)pool_cap;
+    TRY(base_vocab_index(c, V));
+    TRY(base_vocab_upload(c, V, (uint32_t)pool_cap, tok_cap, vset_cap));
     c->tok_cap32 = tok_cap;
-    TRY(id32_upload_vset(c, rec, n_tokens, vset_cap));
-    HIPCHK(c, hipMemset(c->tt.pool, 0, pool_cap));
-    HIPCHK(c, hipMemcpy(c->tt.pool, pool.data(), pool.size(), hipMemcpyHostToDevice));
-    HIPCHK(c, hipMemcpy(c->tt.off, off.data(), (size_t)n_tokens * 4, hipMemcpyHostToDevice));
-    HIPCHK(c, hipMemcpy(c->tt.len, len.data(), (size_t)n_tokens * 4, hipMemcpyHostToDevice));
-    HIPCHK(c, hipMemcpy(c->tt.rec, rec.data(), (size_t)n_tokens * sizeof(TokRec), hipMemcpyHostToDevice));
-    TRY(state_pull(c));
-    DevState *h = c->st_host;
-    memset(h, 0, sizeof(DevState));
-    h->n_tokens = n_tokens;
-    h->pool_used = (uint32_t)pool.size();
-    TRY(state_push(c));
-    c->base_tokens = n_tokens;
-    c->have_vocab = true;
-    c->id_bits_fixed = true;
     c->pool_growths32 = 0;
     return YABPE_OK;
 }
@@ -225,7 +166,7 @@ int id32_ensure_tokens(yabpe_ctx *c, uint64_t need) {
         while (vset_cap < 2 * (uint64_t)ncap) vset_cap <<= 1;
         std::vector<TokRec> rec(n);
         HIPCHK(c, hipMemcpy(rec.data(), c->tt.rec, (size_t)n * sizeof(TokRec), hipMemcpyDeviceToHost));
-        TRY(id32_upload_vset(c, rec, n, vset_cap));
+        TRY(upload_vset(c, rec, n, vset_cap));
     }
     c->st_host->tok_len = c->tt.len;  // (the pair table's insert reads the lengths through the state)
     TRY(state_push(c));
@@ -251,13 +192,9 @@ int id32_grow_pool(yabpe_ctx *c) {
 int id32_load(yabpe_ctx *c, const uint8_t *bytes, const uint64_t *word_off, const uint64_t *word_freq, uint64_t n_words, uint32_t flags,
               const uint32_t *ml, const uint32_t *mr, const uint32_t *mm, uint32_t n_merges) {
     HIPCHK(c, hipSetDevice(c->device));
-    if (!c->have_vocab) return fail(c, YABPE_E_INVALID, "call yabpe_set_vocab first");
-    if (!word_off) return fail(c, YABPE_E_INVALID, "word_off is NULL");
+    int64_t max_token_bytes = 0;
+    TRY(load_check_args(c, word_off, n_words, &max_token_bytes));
     if (c->multi) return fail(c, YABPE_E_INVALID, "id_bits = 32 is single-device: this context has a communicator attached");
-    if (n_words >= 0xFFFFFFFFull) return fail(c, YABPE_E_CAPACITY, "more than 2^32-2 words per context");
-    const int64_t max_token_bytes = optv(c, "max_token_bytes", 0);
-    if (!yb_limit_valid(max_token_bytes))
-        return fail(c, YABPE_E_INVALID, "max_token_bytes is %lld: 0 (no limit) or a length of at least %u bytes", (long long)max_token_bytes, YB_LIMIT_MIN);
     TRY(state_pull(c));
     const uint32_t n_tokens = c->st_host->n_tokens;
     Rp32Table rp{nullptr, nullptr, 0, nullptr, 0};
@@ -300,48 +237,16 @@ int id32_load(yabpe_ctx *c, const uint8_t *bytes, const uint64_t *word_off, cons
     }
     free_corpus(c);
     id32_free_corpus(c);
-    struct Events {
-        hipEvent_t ev0 = nullptr, ev1 = nullptr, ev_seg = nullptr;
-        ~Events() {
-            if (ev0) (void)hipEventDestroy(ev0);
-            if (ev1) (void)hipEventDestroy(ev1);
-            if (ev_seg) (void)hipEventDestroy(ev_seg);
-        }
-    } evs;
-    HIPCHK(c, hipEventCreate(&evs.ev0)); HIPCHK(c, hipEventCreate(&evs.ev1)); HIPCHK(c, hipEventCreate(&evs.ev_seg));
-
-    // ---- inputs on the device, equal words pooled (trainer.py:221-225)
-    const unsigned long long *d_off = nullptr, *d_freq = nullptr;
-    const uint8_t *d_bytes = bytes;
-    uint64_t total_bytes = 0, off_base = 0;
-    if (is_device_ptr(word_off)) {
-        HIPCHK(c, hipMemcpy(&total_bytes, word_off + n_words, 8, hipMemcpyDeviceToHost));
-        HIPCHK(c, hipMemcpy(&off_base, word_off, 8, hipMemcpyDeviceToHost));
-        total_bytes -= off_base;
-    } else {
-        off_base = word_off[0];
-        total_bytes = word_off[n_words] - off_base;
-    }
-    TRY(to_device(c, S, (const unsigned long long *)word_off, (n_words + 1) * 8, 1, &d_off));
-    if (total_bytes && !bytes) return fail(c, YABPE_E_INVALID, "bytes is NULL");
-    if (total_bytes) {
-        TRY(to_device(c, S, bytes + off_base, total_bytes, 1, &d_bytes));
-        d_bytes -= off_base;
-    }
-    if (word_freq) TRY(to_device(c, S, (const unsigned long long *)word_freq, n_words * 8, 1, &d_freq));
-    HIPCHK(c, hipEventRecord(evs.ev0, c->stream));
-    c->n_words_input = n_words;
-    if ((flags & YABPE_LOAD_DEDUP) && n_words > 0) {
-        DedupOut dd{};
-        int r = dedup_words(c->stream, d_bytes, d_off, d_freq, n_words, &dd);
-        if (r != 0) return fail(c, YABPE_E_HIP, "device dedup failed (%d): %s", r, hipGetErrorString(hipGetLastError()));
-        // (the staged inputs stay in S until the load returns; the rp table is among them)
-        S.adopt(dd.bytes); S.adopt(dd.off); S.adopt(dd.freq);
-        d_bytes = dd.bytes; d_off = dd.off; d_freq = dd.freq;
-        n_words = dd.n_unique;
-        total_bytes = dd.total_bytes;
-        off_base = 0;
-    }
+    Events<3> evs;  // start, end, words replayed
+    HIPCHK(c, evs.create());
+    // ---- inputs on the device, equal words pooled: all of it stays in S until the load returns (the u32 load keeps the
+    // staged inputs after the pooling: the rp table sits in the same Scratch)
+    LoadInputs L;
+    TRY(load_stage_inputs(c, S, S, bytes, word_off, word_freq, n_words, flags, evs.e[0], &L));
+    const unsigned long long *d_off = L.off, *d_freq = L.freq;
+    const uint8_t *d_bytes = L.bytes;
+    n_words = L.n_words;
+    const uint64_t total_bytes = L.total_bytes, off_base = L.off_base;
     c->weighted = true;  // one layout: a word without a count weighs 1
     c->n_words = n_words;
 
@@ -374,7 +279,7 @@ int id32_load(yabpe_ctx *c, const uint8_t *bytes, const uint64_t *word_off, cons
         HIPCHK(c, hipStreamSynchronize(c->stream));
         if (flagsd[1] & 0xFFFFFFFFull) return fail(c, YABPE_E_CAPACITY, "a single word longer than 2^32-1 bytes");
     }
-    HIPCHK(c, hipEventRecord(evs.ev_seg, c->stream));
+    HIPCHK(c, hipEventRecord(evs.e[2], c->stream));
     const uint64_t n_tiles64 = (tot[0] + SPAN32 - 1) / SPAN32;
     if (n_tiles64 >= 0xFFFFFFF0ull || tot[1] >= 0xFFFFFFFFull) return fail(c, YABPE_E_CAPACITY, "corpus too large for one context");
     c->n_tiles = (uint32_t)n_tiles64;
@@ -421,11 +326,11 @@ int id32_load(yabpe_ctx *c, const uint8_t *bytes, const uint64_t *word_off, cons
     TRY(state_push(c));
     TRY(id32_table_rebuild(c, (uint64_t)1 << std::min<int64_t>(30, std::max<int64_t>(10, optv(c, "table_min_log2", 16)))));
     c->stats = yabpe_stats_t{};
-    HIPCHK(c, hipEventRecord(evs.ev1, c->stream));
-    HIPCHK(c, hipEventSynchronize(evs.ev1));
+    HIPCHK(c, hipEventRecord(evs.e[1], c->stream));
+    HIPCHK(c, hipEventSynchronize(evs.e[1]));
     float ms = 0, sms = 0;
-    HIPCHK(c, hipEventElapsedTime(&ms, evs.ev0, evs.ev1));
-    HIPCHK(c, hipEventElapsedTime(&sms, evs.ev0, evs.ev_seg));
+    HIPCHK(c, hipEventElapsedTime(&ms, evs.e[0], evs.e[1]));
+    HIPCHK(c, hipEventElapsedTime(&sms, evs.e[0], evs.e[2]));
     c->resume_stats = yabpe_resume_stats_t{};
     c->resume_stats.n_unique = n_words;
     c->resume_stats.n_long = c->n_long;
@@ -520,46 +425,26 @@ int id32_verify(yabpe_ctx *c, uint64_t *out_mismatches) {
 // ---------------------------------------------------------------------------------------------- train
 int id32_train(yabpe_ctx *c, uint32_t num_merges, uint64_t min_frequency, uint32_t *out_left, uint32_t *out_right, uint32_t *out_merged,
                uint64_t *out_count, uint32_t *out_n_merges) {
-    TRY(state_pull(c));
+    uint32_t rec_base = 0;
+    TRY(train_begin(c, num_merges, min_frequency, &rec_base));
     DevState *h = c->st_host;
-    const uint32_t rec_base = h->iter;
-    if ((uint64_t)rec_base + num_merges > 0xFFFFFFF0ull) return fail(c, YABPE_E_CAPACITY, "more than 2^32 merges in one context");
-    h->num_merges = rec_base + num_merges;
-    h->min_freq = min_frequency;
-    h->done = 0; h->halt = 0; h->halt_req = 0;
-    TRY(state_push(c));
-    c->rec_n = 0;
-    c->log_sites.clear(); c->log_live.clear();
-    c->ev_iter.clear(); c->ev_us.clear(); c->ev_scan_us.clear();
     if (num_merges == 0) return YABPE_OK;
-    // token-side capacities follow the request (every merge may take an id), the per-merge records too
+    // token-side capacities follow the request (every merge may take an id), the per-merge records too: all of them at
+    // once, where the u16 loop starts with its id space's worth and grows
     TRY(id32_ensure_tokens(c, (uint64_t)h->n_tokens + num_merges));
-    if (c->rec_cap < num_merges) {
-        free_records(c);
-        TRY(dmalloc(c, &c->rec_left, num_merges)); TRY(dmalloc(c, &c->rec_right, num_merges)); TRY(dmalloc(c, &c->rec_merged, num_merges));
-        TRY(dmalloc(c, &c->rec_count, num_merges)); TRY(dmalloc(c, &c->rec_sites, num_merges)); TRY(dmalloc(c, &c->rec_live, num_merges));
-        c->rec_cap = num_merges;
-    }
-    HIPCHK(c, hipMemsetAsync(c->rec_sites, 0, (size_t)c->rec_cap * 8, c->stream));
+    TRY(train_begin_records(c, num_merges));
     if (!c->sel_ticket) {
         TRY(dmalloc(c, &c->sel_ticket, TICKET_WORDS));
         HIPCHK(c, hipMemsetAsync(c->sel_ticket, 0, TICKET_WORDS * 4, c->stream));
     }
     if (!c->partials32) TRY(dmalloc(c, &c->partials32, SEL32_MAX_BLOCKS));
     const uint32_t check = (uint32_t)std::max<int64_t>(1, optv(c, "check_interval", 32));
-    const double retile_frac = (double)optv(c, "retile_pct", 60) / 100.0;
+    const int64_t retile_pct = optv(c, "retile_pct", 60), table_load_pct = optv(c, "table_load_pct", 30);
     const uint64_t retile_min_tiles = (uint64_t)std::max<int64_t>(2, optv(c, "retile_min_tiles", 4096));
     const uint32_t id_limit = (uint32_t)std::min<int64_t>(YbW32::MAX_TOKENS, std::max<int64_t>(256, optv(c, "id32_limit", YbW32::MAX_TOKENS)));
-    struct Events {  // (destroyed on every way out)
-        hipEvent_t t0 = nullptr, t1 = nullptr;
-        ~Events() {
-            if (t0) (void)hipEventDestroy(t0);
-            if (t1) (void)hipEventDestroy(t1);
-        }
-    } T;
-    HIPCHK(c, hipEventCreate(&T.t0));
-    HIPCHK(c, hipEventCreate(&T.t1));
-    HIPCHK(c, hipEventRecord(T.t0, c->stream));
+    Events<2> T;  // start, end
+    HIPCHK(c, T.create());
+    HIPCHK(c, hipEventRecord(T.e[0], c->stream));
     uint64_t stream_bytes = 0, launches = 0;
     TRY(id32_cand_attach(c));
     uint32_t idle_rounds = 0;
@@ -617,19 +502,19 @@ int id32_train(yabpe_ctx *c, uint32_t num_merges, uint64_t min_frequency, uint32
             }
             break;
         }
-        if (h->table_entries * 100 > ((uint64_t)c->table32.mask + 1) * (uint64_t)optv(c, "table_load_pct", 30)) {
-            TRY(id32_table_grow(c, std::max<uint64_t>(h->table_entries * 4, 1024)));
+        if (table_grow_rule(h->table_entries, (uint64_t)c->table32.mask + 1, table_load_pct)) {  // (the u16 loop's load rule; the target is this loop's own)
+            TRY(id32_table_grow(c, table_grow_target_rule(h->table_entries, 4, 1024)));
             TRY(id32_cand_attach(c));
             TRY(state_pull(c));
         }
         TRY(id32_refresh_live(c));
         TRY(state_push(c));
-        if (c->n_tiles >= retile_min_tiles && (double)h->live_slots < retile_frac * (double)c->n_tiles * SPAN32) TRY(id32_repack(c));
+        if (retile_rule(c->n_tiles, retile_min_tiles, h->live_slots, retile_pct, SPAN32)) TRY(id32_repack(c));
     }
-    HIPCHK(c, hipEventRecord(T.t1, c->stream));
-    HIPCHK(c, hipEventSynchronize(T.t1));
+    HIPCHK(c, hipEventRecord(T.e[1], c->stream));
+    HIPCHK(c, hipEventSynchronize(T.e[1]));
     float ms = 0;
-    HIPCHK(c, hipEventElapsedTime(&ms, T.t0, T.t1));
+    HIPCHK(c, hipEventElapsedTime(&ms, T.e[0], T.e[1]));
     c->stats.train_ms += ms;
     if (c->table32.cs) {  // scans of the whole table that (re)built the list; selections that found it drained
         Cand32 hs{};
@@ -645,18 +530,7 @@ int id32_train(yabpe_ctx *c, uint32_t num_merges, uint64_t min_frequency, uint32
     h->tokens_now -= h->sites;
     h->sites = 0;
     TRY(state_push(c));
-    const uint32_t n = h->iter - rec_base;
-    c->rec_n = n;
-    c->log_sites.assign(n, 0);
-    c->log_live.assign(n, 0);
-    if (n) {
-        HIPCHK(c, hipMemcpy(c->log_sites.data(), c->rec_sites, (size_t)n * 8, hipMemcpyDeviceToHost));
-        if (out_left) HIPCHK(c, hipMemcpy(out_left, c->rec_left, (size_t)n * 4, hipMemcpyDeviceToHost));
-        if (out_right) HIPCHK(c, hipMemcpy(out_right, c->rec_right, (size_t)n * 4, hipMemcpyDeviceToHost));
-        if (out_merged) HIPCHK(c, hipMemcpy(out_merged, c->rec_merged, (size_t)n * 4, hipMemcpyDeviceToHost));
-        if (out_count) HIPCHK(c, hipMemcpy(out_count, c->rec_count, (size_t)n * 8, hipMemcpyDeviceToHost));
-    }
-    if (out_n_merges) *out_n_merges = n;
+    TRY(train_copy_out(c, h->iter - rec_base, false, out_left, out_right, out_merged, out_count, out_n_merges));  // (no live-slot log: rec_live is the u16 selection's)
     if (optv(c, "verify", 0)) {
         uint64_t mm = 0;
         TRY(id32_verify(c, &mm));

@@ -26,15 +26,15 @@
 #include "load_logic.h"
 #include "steal_logic.h"
 #include "tile_logic.h"
+#include "train_rules.h"  // WPB, BLOCK, AGG_N, KMAX, scan_kt_max: shared with the host's launch rules
 
 namespace yb {
 
 constexpr int CAP = 1024;            // u16 slots per tile (2 KiB = 2 x 16 B per lane of a wave)
 constexpr int LMAX = 64;             // longest word (tokens + SEP) kept in the tile stream
 constexpr int SPAN = CAP - LMAX + 1; // packed positions owned by one tile when (re)tiling
-constexpr int WPB = 4;               // waves per workgroup
-constexpr int BLOCK = WPB * 64;
-constexpr int AGG_N = 1024;          // LDS delta-aggregator entries per workgroup
+// WPB (waves per workgroup), BLOCK, AGG_N (LDS delta-aggregator entries per workgroup), KMAX and scan_kt_max() are
+// train_rules.h's: the host's launch rules are built on them
 constexpr uint32_t EMPTY = 0xFFFFFFFFu;
 constexpr uint32_t PADPAD = (YB_PAD << 16) | YB_PAD;
 constexpr int LONG_CH = 1024;        // long-word path: tokens per LDS chunk (the block rides on the per-batch launches: its LDS counts against theirs)
@@ -44,11 +44,11 @@ constexpr int SIG_TILES = 8;         // k_build_sig: tiles whose signatures one 
 constexpr int MAX_LISTS_PROF = 4096;
 constexpr int SCAN_CHUNK = 256;      // k_scan_skip: consecutive tiles examined by one workgroup at a time (x kt)
 constexpr int SCAN_KT_MAX = 4;       // ... kt <= 4 signature tests per thread, so that the whole grid is resident at once
-constexpr int scan_kt_max(int nw) { return nw >= 16 ? 2 : 4; } // (a workgroup's hit list lives in LDS: 64 * nw * kt entries)
+// (per workgroup width: scan_kt_max(nw), train_rules.h)
 
 enum : uint32_t { HALT_NONE = 0, HALT_TABLE_FULL = 1, HALT_POOL_FULL = 2, HALT_VOCAB_FULL = 3, HALT_DELTA_FULL = 4, HALT_RESCAN = 5, HALT_COMM = 6 };
 
-constexpr int KMAX = 16; // merges one sparse launch applies at most (a batch, see select_batch)
+// a batch: at most KMAX merges per sparse launch (see select_batch)
 struct BatchMerge {
     uint32_t a, b, c, is_new; // the pair, the merged token, whether the merge created it
 };
