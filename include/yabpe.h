@@ -547,9 +547,48 @@ typedef struct yabpe_windows_t {
 } yabpe_windows_t;
 int yabpe_layout_windows(yabpe_ctx *ctx, const uint32_t *ids, uint64_t n_ids, const uint64_t *doc_off, uint32_t n_docs,
                          const uint64_t *spans, const yabpe_layout_t *layout, uint32_t stride, yabpe_windows_t *out);
+/* Text pairs (BBPETokenizer.encode_batch_pairs on the device): documents 2p and 2p + 1 are the two sides A, B of pair p and
+ * share rows.  ids, doc_off and spans as yabpe_layout_windows takes them (host or device memory; the encoder's results pass
+ * straight in and are left alone); no model is needed.  layout->row_len = max_length, flags: YABPE_LAYOUT_BOS / _EOS /
+ * _PAD_LEFT.  n_added = BOS + EOS + pairs->n_sep (0, 1 or 2 copies of sep_id between the sides), C = row_len - n_added.
+ * A row holds [bos_id] + A[:ka] + [sep_id] * n_sep + B[s : s + kb] + [eos_id], padded with pad_id at its right end
+ * (YABPE_LAYOUT_PAD_LEFT: at its left end).  The truncation modes give row p = pair p with s = 0; ids leave from the END of a
+ * side and every row fits:
+ *   YABPE_PAIRS_LONGEST_FIRST  while ka + kb > C the longer side loses its last id, the second when both are equally long;
+ *   YABPE_PAIRS_ONLY_FIRST     the first gives up the excess la + lb - C, down to zero ids; a second still longer than C is
+ *                              cut to C;    YABPE_PAIRS_ONLY_SECOND: the mirror image.
+ *   YABPE_PAIRS_WINDOWS        (0 <= stride <= C - 1) ka = min(la, C - stride - 1) in every row of the pair; the second side
+ *       is windowed as yabpe_layout_windows does with Cb = C - ka content slots and step = Cb - stride: row k has s = k * step
+ *       and kb = min(Cb, lb - s), the last row is the first with s + Cb >= lb; at least one row a pair.  Rows are in pair
+ *       order, in window order within a pair.
+ * Results (device memory owned by the library, buffers of their own: a later yabpe_encode leaves them valid; released by
+ * yabpe_layout_free, the next layout call or yabpe_destroy): rows and types (0: BOS, the first side, separators, padding; 1:
+ * the second side and EOS) per slot; per row its pair, s, ka and kb (the length before padding is ka + kb + n_added); with
+ * spans (2 * n_ids u64 as yabpe_encode_spans returns them) out->spans = the (start, end) of every slot's id in its own
+ * document, (0, 0) in BOS, separator, EOS and pad slots; without, out->spans = NULL.  n_docs = 0: no rows.
+ * YABPE_E_INVALID: an odd n_docs; row_len <= n_added; n_sep > 2; an unknown mode; stride != 0 outside windows mode; stride >=
+ * C in windows mode; YABPE_LAYOUT_TRUNC_LEFT, _DROP_LAST or an unknown flag; a bad doc_off.  YABPE_E_CAPACITY: more than 2^36
+ * output slots; a document of more than 2^32 - 1 ids.  Every error is found before a result buffer is allocated.
+ * yabpe_layout_stats: n_docs counts documents (two a pair); n_truncated_docs = the pairs that lost an id or took more than one
+ * row; n_ids_dropped = the ids cut away in the truncation modes, 0 in windows mode; lengths_ms = the counters, in windows mode
+ * the row counts and their scan, and the row records. */
+#define YABPE_PAIRS_LONGEST_FIRST 0u
+#define YABPE_PAIRS_ONLY_FIRST    1u
+#define YABPE_PAIRS_ONLY_SECOND   2u
+#define YABPE_PAIRS_WINDOWS       3u
+typedef struct yabpe_pairs_t { uint32_t sep_id, n_sep, mode, stride; } yabpe_pairs_t;
+typedef struct yabpe_pair_rows_t {
+    uint32_t *rows;        /* n_rows * row_len */
+    uint8_t  *types;       /* n_rows * row_len */
+    uint32_t *row_pair, *row_start, *first_len, *second_len;   /* n_rows each */
+    uint64_t *spans;       /* 2 * n_rows * row_len, or NULL */
+    uint64_t n_rows;
+} yabpe_pair_rows_t;
+int yabpe_layout_pairs(yabpe_ctx *ctx, const uint32_t *ids, uint64_t n_ids, const uint64_t *doc_off, uint32_t n_docs,
+                       const uint64_t *spans, const yabpe_layout_t *layout, const yabpe_pairs_t *pairs, yabpe_pair_rows_t *out);
 int yabpe_layout_free(yabpe_ctx *ctx);
-/* What the last yabpe_layout_pad / yabpe_layout_pack / yabpe_layout_windows saw, and the device time of its phases (HIP events
- * around each phase's launches). */
+/* What the last yabpe_layout_pad / yabpe_layout_pack / yabpe_layout_windows / yabpe_layout_pairs saw, and the device time of
+ * its phases (HIP events around each phase's launches). */
 typedef struct yabpe_layout_stats_t {
     uint64_t n_ids, n_docs;
     uint64_t n_rows, row_len;

@@ -7,7 +7,12 @@ device-to-device hipMemcpyAsync of the same number of output bytes (HIP events, 
 seq_len 2048 with an EOS; windows: max_length 1024, stride 128, a BOS, without spans and with the byte spans of
 yabpe_encode_spans.  For comparison, what a user does without the layout calls on a --host-mib sample: encode_array, then a
 numpy loop per document on the host that builds the same padded batch.
-   python tools/layout_bench.py [--mib 1024] [--merges 32000] [--reps 3] [--host-mib 64] [--json out.json]"""
+--pairs: only yabpe_layout_pairs, on the same ids with the documents paired two by two, <s> A </s></s> B </s>: longest_first at
+the max_length that cuts about half the pairs, and windows at max_length 1536 with stride 128 (about three rows a pair: the
+first side of about 1,000 ids is in every row), each without and with byte spans;
+the device time of the phases and the output bytes per second of the write pass (4 B of ids + 1 B of type a slot, + 16 B with
+spans), next to the same figure of yabpe_layout_windows at the same row length and stride on the same ids.
+   python tools/layout_bench.py [--mib 1024] [--merges 32000] [--reps 3] [--host-mib 64] [--pairs] [--json out.json]"""
 import argparse, ctypes, json, sys, time
 from pathlib import Path
 REPO = Path(__file__).resolve().parent.parent
@@ -23,10 +28,19 @@ ap.add_argument("--merges", type=int, default=32000)
 ap.add_argument("--reps", type=int, default=3)
 ap.add_argument("--host-mib", type=int, default=64)
 ap.add_argument("--doc-ids", type=int, default=1000)
+ap.add_argument("--pairs", action="store_true")
 ap.add_argument("--json", default="")
 a = ap.parse_args()
 PAD_LEN, PACK_LEN, EOS = 1024, 2048, 2
 WIN_LEN, WIN_STRIDE, BOS = 1024, 128, 1
+PAIR_WIN_LEN, PAIR_STRIDE, SEP, PAIR_ADDED = 1536, 128, 3, 4  # <s> A </s></s> B </s>
+
+
+def emit(out: dict) -> None:
+    print(json.dumps(out))
+    if a.json:
+        Path(a.json).parent.mkdir(parents=True, exist_ok=True)
+        Path(a.json).write_text(json.dumps(out, indent=1))
 
 
 def copy_ms(n_bytes: int, reps: int) -> float:
@@ -95,6 +109,42 @@ with _native.Context() as gen:
                 "write_ns_per_slot": round(st["write_ms"] * 1e6 / max(1, st["n_rows"] * st["row_len"]), 5)}
 
     lens = np.diff(doc_off)
+    if a.pairs:
+        n_even = n_docs - n_docs % 2  # (an odd last document joins the one before it: the last document ends at n_ids)
+        sums = lens[:n_even].copy()
+        sums[-1] = ni - doc_off[n_even - 1]
+        la, lb = sums[0::2], sums[1::2]
+        sums = la + lb
+        Cb = PAIR_WIN_LEN - PAIR_ADDED - np.minimum(la, PAIR_WIN_LEN - PAIR_ADDED - PAIR_STRIDE - 1)
+        n_pair_win = int(np.where(lb <= Cb, 1, 1 + -(-(lb - Cb) // (Cb - PAIR_STRIDE))).sum())
+        assert n_pair_win * PAIR_WIN_LEN < 1 << 32, f"{n_pair_win} window rows: first sides too long for max_length {PAIR_WIN_LEN}"
+        cut_len = int(np.median(sums)) + PAIR_ADDED
+        di, dd, ds, ni_s = gen.encode_spans(tb, n_bytes=tn, doc_starts=starts)
+        assert ni_s == ni
+
+        def phases(st, all_ms, slot_bytes):
+            out_b = slot_bytes * st["n_rows"] * st["row_len"]
+            return {"rows": st["n_rows"], "row_len": st["row_len"], "truncated": st["n_truncated_docs"], "ids_dropped": st["n_ids_dropped"],
+                    "pad_slots": st["n_pad_slots"], "lengths_ms": round(st["lengths_ms"], 3), "write_ms": round(st["write_ms"], 3),
+                    "total_ms": round(st["total_ms"], 3), "all_total_ms": all_ms, "write_pass_output_bytes": out_b,
+                    "write_pass_output_GB_per_s": round(out_b / st["write_ms"] / 1e6, 1)}
+
+        out = {"text_bytes": tn, "merges": len(merges), "ids": ni, "pairs": n_even // 2, "median_ids_per_pair": int(np.median(sums))}
+        for name, L, mode, stride in ((f"longest_first_{cut_len}", cut_len, "longest_first", 0),
+                                      (f"windows_{PAIR_WIN_LEN}_stride_{PAIR_STRIDE}", PAIR_WIN_LEN, "windows", PAIR_STRIDE)):
+            kw = dict(row_len=L, mode=mode, stride=stride, sep_id=SEP, n_sep=2, pad_id=0, bos_id=BOS, eos_id=EOS)
+            for spans, tag in ((None, ""), (ds, "_byte_spans")):
+                st, all_ms = timed(lambda: gen.layout_pairs(di, ni, dd, n_even, spans, **kw))
+                assert mode != "windows" or st["n_rows"] == n_pair_win
+                pairs = phases(st, all_ms, 21 if spans else 5)
+                st, all_ms = timed(lambda: gen.layout_windows(di, ni, dd, n_docs, spans, row_len=L, stride=stride, pad_id=0, bos_id=BOS))
+                yard = phases(st, all_ms, 20 if spans else 4)
+                pairs["write_rate_vs_layout_windows"] = round(pairs["write_pass_output_GB_per_s"] / yard["write_pass_output_GB_per_s"], 3)
+                out["pairs_" + name + tag] = pairs
+                out["layout_windows_" + str(L) + "_stride_" + str(stride) + tag] = yard
+        gen.layout_free()
+        emit(out)
+        sys.exit(0)
     st, all_ms = timed(lambda: gen.layout_pad(di, ni, dd, n_docs, row_len=PAD_LEN, pad_id=0))
     padded = report(st, all_ms, 4 * int(np.minimum(lens, PAD_LEN).sum()) + 8 * n_docs, 4 * n_docs * PAD_LEN + 4 * n_docs)
     st, all_ms = timed(lambda: gen.layout_pack(di, ni, dd, n_docs, row_len=PACK_LEN, pad_id=0, eos_id=EOS))
@@ -138,7 +188,4 @@ out = {"text_bytes": tn, "merges": len(merges), "ids": ni, "docs": n_docs, "mean
        "host_sample": {"text_bytes": len(sample), "docs": len(docs), "encode_array_then_numpy_loop_s": round(host_s, 3),
                        "of_which_encode_array_s": round(enc_s, 3), "MB_per_s": round(len(sample) / host_s / 1e6, 1),
                        "encode_array_padded_s": round(dev_s, 3), "encode_array_padded_MB_per_s": round(len(sample) / dev_s / 1e6, 1)}}
-print(json.dumps(out))
-if a.json:
-    Path(a.json).parent.mkdir(parents=True, exist_ok=True)
-    Path(a.json).write_text(json.dumps(out, indent=1))
+emit(out)

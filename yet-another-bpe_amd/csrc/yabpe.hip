@@ -185,9 +185,10 @@ struct yabpe_ctx {
     unsigned long long *dec_doc = nullptr;
     yabpe_decode_stats_t dec_stats{};
     hipEvent_t dec_ev[7] = {};
-    // fixed-shape batches (yabpe_layout_pad / yabpe_layout_pack / yabpe_layout_windows)
-    uint32_t *lay_buf[5] = {};                // results of the last layout call: rows, lengths / ids, doc, pos /
-                                              // rows, row_doc, row_start, row_len, spans (u64 pairs)
+    // fixed-shape batches (yabpe_layout_pad / yabpe_layout_pack / yabpe_layout_windows / yabpe_layout_pairs)
+    uint32_t *lay_buf[7] = {};                // results of the last layout call: rows, lengths / ids, doc, pos /
+                                              // rows, row_doc, row_start, row_len, spans (u64 pairs) /
+                                              // rows, row_pair, row_start, first_len, spans, second_len, types (bytes)
     yabpe_layout_stats_t lay_stats{};
     hipEvent_t lay_ev[4] = {};
     // resumed load (yabpe_load_words_resumed)
@@ -4046,6 +4047,109 @@ int yabpe_layout_windows(yabpe_ctx *c, const uint32_t *ids, uint64_t n_ids, cons
     out->row_doc = c->lay_buf[1];
     out->row_start = c->lay_buf[2];
     out->row_len = c->lay_buf[3];
+    out->spans = (uint64_t *)c->lay_buf[4];
+    out->n_rows = n_rows;
+    return YABPE_OK;
+}
+
+int yabpe_layout_pairs(yabpe_ctx *c, const uint32_t *ids, uint64_t n_ids, const uint64_t *doc_off, uint32_t n_docs, const uint64_t *spans,
+                       const yabpe_layout_t *lay, const yabpe_pairs_t *pairs, yabpe_pair_rows_t *out) {
+    if (!c || !out) return YABPE_E_INVALID;
+    HIPCHK(c, hipSetDevice(c->device));
+    *out = yabpe_pair_rows_t{};
+    if (!lay) return fail(c, YABPE_E_INVALID, "layout is NULL");
+    if (!pairs) return fail(c, YABPE_E_INVALID, "pairs is NULL");
+    if (lay->flags & ~LAY_PAIR_FLAGS)
+        return fail(c, YABPE_E_INVALID, "layout flags 0x%x do not belong to this call (it takes 0x%x)", lay->flags & ~LAY_PAIR_FLAGS, LAY_PAIR_FLAGS);
+    if (pairs->n_sep > LAY_PAIRS_MAX_SEP) return fail(c, YABPE_E_INVALID, "n_sep %u: at most %u separators between the two sides", pairs->n_sep, LAY_PAIRS_MAX_SEP);
+    if (pairs->mode > LAY_PAIRS_WINDOWS) return fail(c, YABPE_E_INVALID, "unknown pairs mode %u", pairs->mode);
+    const uint32_t added = lay_n_added(lay->flags & LAY_PAIR_FLAGS) + pairs->n_sep;
+    if (lay->row_len <= added)
+        return fail(c, YABPE_E_INVALID, "row_len %u leaves no slot for content beside BOS, EOS and %u separators", lay->row_len, pairs->n_sep);
+    const uint32_t L = lay->row_len, C = L - added;
+    if (pairs->mode != LAY_PAIRS_WINDOWS && pairs->stride) return fail(c, YABPE_E_INVALID, "stride %u: only windows mode takes a stride", pairs->stride);
+    if (pairs->stride >= C)
+        return fail(c, YABPE_E_INVALID, "stride %u: a row of %u content slots must keep one more than the stride for the second side", pairs->stride, C);
+    if (n_docs & 1u) return fail(c, YABPE_E_INVALID, "%u documents: documents 2p and 2p + 1 are pair p, so their number is even", n_docs);
+    const uint32_t n_pairs = n_docs / 2;
+    if ((unsigned long long)n_pairs * L > LAY_MAX_SLOTS) // (every pair has at least one row)
+        return fail(c, YABPE_E_CAPACITY, "%u pairs in rows of %u slots: at most 2^36 slots in one call", n_pairs, L);
+    if (n_docs == 0) { // no pairs: no rows
+        yabpe_layout_free(c);
+        c->lay_stats = yabpe_layout_stats_t{};
+        c->lay_stats.row_len = L;
+        return YABPE_OK;
+    }
+    Scratch S(c->device, c->rank);
+    const uint32_t *d_ids = nullptr;
+    const unsigned long long *d_docs = nullptr;
+    TRY(layout_begin(c, S, ids, n_ids, doc_off, &n_docs, lay, LAY_PAIR_FLAGS, &d_ids, &d_docs));
+    const ulonglong2 *d_spans = nullptr;
+    if (spans) TRY(to_device(c, S, (const ulonglong2 *)spans, n_ids * 16, 16, &d_spans));
+    const bool windows = pairs->mode == LAY_PAIRS_WINDOWS;
+    const LayPairShape shape{C, pairs->mode, pairs->stride, pairs->n_sep, added};
+    hipStream_t s = c->stream;
+    // ---- count (+ scan in windows mode: elsewhere a pair has one row and the scan would be the identity)
+    unsigned long long *counters = nullptr, *cnt = nullptr, *row_off = nullptr;
+    HIPCHK(c, S.get(&counters, 4));
+    if (windows) {
+        HIPCHK(c, S.get(&cnt, n_pairs));
+        HIPCHK(c, S.get(&row_off, (uint64_t)n_pairs + 1));
+    }
+    HIPCHK(c, hipEventRecord(c->lay_ev[0], s));
+    HIPCHK(c, hipMemsetAsync(counters, 0, 32, s));
+    hipLaunchKernelGGL(k_lay_pair_count, dim3(cdiv64(n_pairs, BLOCK)), dim3(BLOCK), 0, s, LayPairCountParams{d_docs, n_docs, n_ids, shape, cnt, counters});
+    HIPCHK(c, hipGetLastError());
+    unsigned long long h_cnt[4] = {0, 0, 0, 0}, n_rows = n_pairs;
+    if (windows) {
+        if (exclusive_scan<unsigned long long>(s, cnt, n_pairs, row_off, (unsigned long long)n_pairs + 1) != 0)
+            return fail(c, YABPE_E_HIP, "scan of the row counts failed");
+        HIPCHK(c, hipMemcpyAsync(&n_rows, row_off + n_pairs, 8, hipMemcpyDeviceToHost, s));
+    }
+    HIPCHK(c, hipMemcpyAsync(h_cnt, counters, 32, hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipStreamSynchronize(s));
+    if (h_cnt[0] > 0xFFFFFFFFull) return fail(c, YABPE_E_CAPACITY, "a document of %llu ids: row_start and the kept lengths are u32", h_cnt[0]);
+    if (n_rows > LAY_MAX_SLOTS / L) return fail(c, YABPE_E_CAPACITY, "%llu rows of %u slots: at most 2^36 slots in one call", n_rows, L);
+    const unsigned long long n_slots = n_rows * L;
+    // ---- rows: the record of every output row
+    LayPairRec *rec = nullptr;
+    HIPCHK(c, S.get(&rec, n_rows));
+    TRY(dmalloc(c, &c->lay_buf[0], n_slots));
+    for (int k : {1, 2, 3, 5}) TRY(dmalloc(c, &c->lay_buf[k], n_rows));
+    TRY(dmalloc(c, &c->lay_buf[6], (n_slots + 3) / 4));       // (a byte a slot)
+    if (spans) TRY(dmalloc(c, &c->lay_buf[4], 4 * n_slots));  // (16 B a slot)
+    hipLaunchKernelGGL(k_lay_pair_rows, dim3(cdiv64(n_rows, BLOCK)), dim3(BLOCK), 0, s,
+                       LayPairRowsParams{d_docs, n_docs, n_ids, row_off, n_rows, shape, c->lay_buf[1], c->lay_buf[2], c->lay_buf[3], c->lay_buf[5], rec});
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipEventRecord(c->lay_ev[1], s));
+    // ---- write
+    HIPCHK(c, hipEventRecord(c->lay_ev[2], s));
+    const LayPairParams W{d_ids, rec, n_rows, L, lay->flags, pairs->n_sep, pairs->sep_id, LayConst{lay->pad_id, lay->bos_id, lay->eos_id},
+                          c->lay_buf[0], (uint8_t *)c->lay_buf[6], n_slots, d_spans, (ulonglong2 *)c->lay_buf[4]};
+    if (spans)
+        hipLaunchKernelGGL(k_lay_pair_write<true>, dim3(cdiv64(n_slots, LAY_PIECE)), dim3(BLOCK), 0, s, W);
+    else
+        hipLaunchKernelGGL(k_lay_pair_write<false>, dim3(cdiv64(n_slots, LAY_PIECE)), dim3(BLOCK), 0, s, W);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipEventRecord(c->lay_ev[3], s));
+    const hipError_t se = hipStreamSynchronize(s);
+    if (se != hipSuccess) {
+        yabpe_layout_free(c);
+        return fail(c, YABPE_E_HIP, "layout kernels failed: %s", hipGetErrorString(se));
+    }
+    auto &st = c->lay_stats;
+    st.n_rows = n_rows;
+    st.row_len = L;
+    st.n_truncated_docs = h_cnt[1];
+    st.n_ids_dropped = h_cnt[2];
+    st.n_pad_slots = n_slots - h_cnt[3];
+    layout_times(c);
+    out->rows = c->lay_buf[0];
+    out->types = (uint8_t *)c->lay_buf[6];
+    out->row_pair = c->lay_buf[1];
+    out->row_start = c->lay_buf[2];
+    out->first_len = c->lay_buf[3];
+    out->second_len = c->lay_buf[5];
     out->spans = (uint64_t *)c->lay_buf[4];
     out->n_rows = n_rows;
     return YABPE_OK;

@@ -21,6 +21,16 @@
 //             row's record (first source id, content ids kept).
 //   write     k_lay_win_write: k_lay_pad_write's shape with one record read per row touched; <true> also stores the 16-byte
 //             span of every slot.
+//
+// Pairs (yabpe_layout_pairs; contract: BBPETokenizer.encode_batch_pairs): documents 2p and 2p + 1 share a row, cut by one of
+// three truncation rules (one row a pair) or with the second side windowed behind the whole first (Rule 4 of layout_logic.h):
+//   count     k_lay_pair_count: one thread per pair: the call's counters and, in windows mode only, its row count.  The
+//             truncation modes have one row a pair, so their row_off is the identity and no scan runs.
+//   rows      k_lay_pair_rows: one thread per output row (windows mode: one search in row_off) writes row_pair, row_start,
+//             first_len, second_len and the row's record (where each side's kept ids start, how many they are).
+//   write     k_lay_pair_write: k_lay_win_write's shape; next to the 16 bytes of ids a thread stores its 4 slots' type bytes
+//             as one aligned u32.  <true> also stores the 16-byte span of every slot.
+// No workgroup waits for another; every loop runs over LAY_VPT steps or a search in an array whose length is given.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -352,6 +362,168 @@ __global__ __launch_bounds__(BLOCK) void k_lay_win_write(LayWinParams P) {
                     const ulonglong2 rec = P.rec[row];
                     const unsigned long long slot = lay_win_row_slot(rec.x, rec.y, P.row_len, P.flags, col);
                     if (slot < LAY_SLOT_EOS) {
+                        const ulonglong2 sp = P.spans[slot];
+                        sa[k] = sp.x;
+                        sb[k] = sp.y;
+                    }
+                }
+            }
+#pragma unroll
+            for (int k = 0; k < 4; ++k)
+                if (fw + 64 * k + lane < P.n_slots) P.out_spans[fw + 64 * k + lane] = make_ulonglong2(sa[k], sb[k]);
+        }
+    }
+}
+
+// ---- pairs (yabpe_layout_pairs): documents 2p and 2p + 1 share rows of C content slots (Rule 4 of layout_logic.h)
+struct LayPairShape {
+    uint32_t C, mode, stride, n_sep, added; // added = BOS + EOS + n_sep
+};
+
+// the ids of pair p: the first side is ids[*a, *b), the second ids[*b, *e)
+__device__ __forceinline__ void lay_pair_docs(const unsigned long long *doc, uint32_t n_docs, unsigned long long n_ids, unsigned long long p,
+                                              unsigned long long *a, unsigned long long *b, unsigned long long *e) {
+    *a = doc[2 * p];
+    *b = doc[2 * p + 1];
+    *e = 2 * p + 2 < n_docs ? doc[2 * p + 2] : n_ids;
+}
+
+struct LayPairCountParams {
+    const unsigned long long *doc;  // n_docs = 2 * n_pairs document starts
+    uint32_t n_docs;
+    unsigned long long n_ids;
+    LayPairShape S;
+    unsigned long long *rows;       // out, windows mode: rows per pair (their exclusive scan is row_off); else NULL
+    unsigned long long *counters;   // [0] longest document (ids) [1] pairs that lost an id or took several rows [2] ids dropped [3] slots kept
+};
+
+__global__ __launch_bounds__(BLOCK) void k_lay_pair_count(LayPairCountParams P) {
+    __shared__ unsigned long long s_red[WPB][4];
+    const unsigned long long p = (unsigned long long)blockIdx.x * BLOCK + threadIdx.x;
+    unsigned long long v[4] = {0, 0, 0, 0}; // max, cut, dropped, kept
+    if (2 * p < P.n_docs) {
+        unsigned long long a, b, e;
+        lay_pair_docs(P.doc, P.n_docs, P.n_ids, p, &a, &b, &e);
+        const unsigned long long la = b - a, lb = e - b;
+        v[0] = la > lb ? la : lb;
+        if (P.S.mode == LAY_PAIRS_WINDOWS) {
+            const unsigned long long ka = lay_pair_first(la, P.S.C, P.S.stride), Cb = P.S.C - ka, step = Cb - P.S.stride;
+            const unsigned long long rows = lay_win_rows(lb, Cb, step);
+            P.rows[p] = rows;
+            v[1] = rows > 1 || ka < la ? 1u : 0u;
+            v[3] = rows * (P.S.added + ka) + (rows - 1) * Cb + lay_win_content(lb, rows - 1, Cb, step); // every row but the last is full
+        } else {
+            unsigned long long ka, kb;
+            lay_pair_keep(la, lb, P.S.C, P.S.mode, &ka, &kb);
+            v[1] = ka + kb < la + lb ? 1u : 0u;
+            v[2] = la + lb - ka - kb;
+            v[3] = P.S.added + ka + kb;
+        }
+    }
+    lay_reduce(v, s_red);
+    if (threadIdx.x == 0) {
+        atomicMax(&P.counters[0], v[0]);
+        for (int k = 1; k < 4; ++k)
+            if (v[k]) atomicAdd(&P.counters[k], v[k]);
+    }
+}
+
+// what the write pass needs of an output row
+struct LayPairRec {
+    unsigned long long a0, b0;      // index into ids of the first id it keeps of the first side, of the second side
+    uint32_t ka, kb;                // ids kept of each
+};
+
+struct LayPairRowsParams {
+    const unsigned long long *doc;      // n_docs document starts
+    uint32_t n_docs;
+    unsigned long long n_ids;
+    const unsigned long long *row_off;  // windows mode: n_pairs + 1, the first output row of every pair; else NULL (row p = pair p)
+    unsigned long long n_rows;
+    LayPairShape S;
+    uint32_t *row_pair, *row_start, *first_len, *second_len; // out, per output row
+    LayPairRec *rec;                    // out, per output row
+};
+
+__global__ __launch_bounds__(BLOCK) void k_lay_pair_rows(LayPairRowsParams P) {
+    const unsigned long long r = (unsigned long long)blockIdx.x * BLOCK + threadIdx.x;
+    if (r >= P.n_rows) return;
+    unsigned long long p = r, k = 0;
+    if (P.row_off) {
+        p = lay_find_doc(P.row_off, 0, 0, P.n_docs / 2 - 1, r);
+        k = r - P.row_off[p];
+    }
+    unsigned long long a, b, e, ka, s, kb;
+    lay_pair_docs(P.doc, P.n_docs, P.n_ids, p, &a, &b, &e);
+    lay_pair_row(b - a, e - b, k, P.S.C, P.S.mode, P.S.stride, &ka, &s, &kb);
+    P.row_pair[r] = (uint32_t)p;
+    P.row_start[r] = (uint32_t)s;
+    P.first_len[r] = (uint32_t)ka;
+    P.second_len[r] = (uint32_t)kb;
+    P.rec[r] = LayPairRec{a, b + s, (uint32_t)ka, (uint32_t)kb};
+}
+
+struct LayPairParams {
+    const uint32_t *ids;
+    const LayPairRec *rec;          // n_rows row records (k_lay_pair_rows)
+    unsigned long long n_rows;
+    uint32_t row_len, flags, n_sep, sep_id;
+    LayConst K;
+    uint32_t *rows;                 // out: n_rows * row_len slots
+    uint8_t *types;                 // out: one byte per slot
+    unsigned long long n_slots;
+    const ulonglong2 *spans;        // SPANS: one (start, end) per id ...
+    ulonglong2 *out_spans;          // ... and per output slot
+};
+
+// k_lay_win_write's shape with two source runs a row.  The 4 slots a thread owns per step are 16 bytes of ids and 4 bytes of types:
+// the flat index of the first is a multiple of 4, so both stores are aligned whatever row_len is, and a wave's type bytes lie
+// end to end (256 B a step).  The last 1..3 slots of the output are stored one by one.
+template <bool SPANS>
+__global__ __launch_bounds__(BLOCK) void k_lay_pair_write(LayPairParams P) {
+    const unsigned long long f0 = (unsigned long long)blockIdx.x * LAY_PIECE;
+    const bool narrow = P.n_slots <= 0xFFFFFFFFull; // (uniform: the 32-bit division then)
+    const uint32_t lane = threadIdx.x & 63;
+#pragma unroll
+    for (int s = 0; s < LAY_VPT; ++s) {
+        const unsigned long long f = f0 + ((unsigned long long)s * BLOCK + threadIdx.x) * 4;
+        const unsigned long long fw = f - 4ull * lane; // the wave's first slot
+        if ((SPANS ? fw : f) >= P.n_slots) break;
+        if (!SPANS || f < P.n_slots) {
+            unsigned long long row;
+            uint32_t col;
+            lay_row_col(f, P.row_len, narrow, &row, &col);
+            LayPairRec rec = P.rec[row];
+            uint32_t v[4] = {0, 0, 0, 0}, t[4] = {0, 0, 0, 0};
+#pragma unroll
+            for (int k = 0; k < 4; ++k) { // (past the last slot col runs on past the row's end: a pad slot that is never stored)
+                const unsigned long long slot = lay_pair_slot(rec.a0, rec.ka, rec.b0, rec.kb, P.n_sep, P.row_len, P.flags, col, &t[k]);
+                v[k] = slot == LAY_SLOT_SEP ? P.sep_id : lay_value(P.ids, slot, P.K);
+                if (++col == P.row_len && row + 1 < P.n_rows) { // the next slot opens the next row
+                    col = 0;
+                    rec = P.rec[++row];
+                }
+            }
+            lay_store4(P.rows, f, P.n_slots, v);
+            if (f + 4 <= P.n_slots) {
+                *reinterpret_cast<uint32_t *>(P.types + f) = t[0] | t[1] << 8 | t[2] << 16 | t[3] << 24;
+            } else {
+                for (int k = 0; k < 4; ++k)
+                    if (f + k < P.n_slots) P.types[f + k] = (uint8_t)t[k];
+            }
+        }
+        if (SPANS) {
+            unsigned long long sa[4] = {0, 0, 0, 0}, sb[4] = {0, 0, 0, 0}; // the slots' (start, end)
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const unsigned long long g = fw + 64 * k + lane;
+                if (g < P.n_slots) {
+                    unsigned long long row;
+                    uint32_t col, type;
+                    lay_row_col(g, P.row_len, narrow, &row, &col);
+                    const LayPairRec rec = P.rec[row];
+                    const unsigned long long slot = lay_pair_slot(rec.a0, rec.ka, rec.b0, rec.kb, P.n_sep, P.row_len, P.flags, col, &type);
+                    if (slot < LAY_SLOT_SEP) {
                         const ulonglong2 sp = P.spans[slot];
                         sa[k] = sp.x;
                         sb[k] = sp.y;

@@ -83,6 +83,16 @@ class Windows(ctypes.Structure):
     _fields_ = [(n, c_void_p) for n in ("rows", "row_doc", "row_start", "row_len", "spans")] + [("n_rows", c_uint64)]
 
 
+class Pairs(ctypes.Structure):
+    """yabpe_pairs_t"""
+    _fields_ = [(n, c_uint32) for n in ("sep_id", "n_sep", "mode", "stride")]
+
+
+class PairRows(ctypes.Structure):
+    """yabpe_pair_rows_t"""
+    _fields_ = [(n, c_void_p) for n in ("rows", "types", "row_pair", "row_start", "first_len", "second_len", "spans")] + [("n_rows", c_uint64)]
+
+
 class ResumeStats(ctypes.Structure):
     _fields_ = [(n, c_uint64) for n in ("n_unique", "n_long", "tokens")] + [(n, c_double) for n in ("segment_ms", "build_ms")]
 
@@ -116,7 +126,7 @@ SYMBOLS = [
     "yabpe_encode_set_model", "yabpe_encode", "yabpe_encode_spans", "yabpe_encode_dropout", "yabpe_encode_free", "yabpe_encode_stats", "yabpe_encode_checksum",
     "yabpe_decode_set_model", "yabpe_decode", "yabpe_decode_free", "yabpe_decode_stats",
     "yabpe_load_words_resumed", "yabpe_resume_stats",
-    "yabpe_layout_pad", "yabpe_layout_pack", "yabpe_layout_windows", "yabpe_layout_free", "yabpe_layout_stats",
+    "yabpe_layout_pad", "yabpe_layout_pack", "yabpe_layout_windows", "yabpe_layout_pairs", "yabpe_layout_free", "yabpe_layout_stats",
     "yabpe_pool_add", "yabpe_pool_get", "yabpe_pool_clear", "yabpe_pool_stats",
     "yabpe_normalize", "yabpe_normalize_free", "yabpe_normalize_stats",
 ]
@@ -185,6 +195,7 @@ def lib() -> ctypes.CDLL:
         L.yabpe_layout_pack.argtypes = [c_void_p, c_void_p, c_uint64, c_void_p, c_uint32, POINTER(Layout), POINTER(c_void_p), POINTER(c_void_p),
                                         POINTER(c_void_p), POINTER(c_uint64)]
         L.yabpe_layout_windows.argtypes = [c_void_p, c_void_p, c_uint64, c_void_p, c_uint32, c_void_p, POINTER(Layout), c_uint32, POINTER(Windows)]
+        L.yabpe_layout_pairs.argtypes = [c_void_p, c_void_p, c_uint64, c_void_p, c_uint32, c_void_p, POINTER(Layout), POINTER(Pairs), POINTER(PairRows)]
         L.yabpe_layout_free.argtypes = [c_void_p]
         L.yabpe_layout_stats.argtypes = [c_void_p, POINTER(LayoutStats)]
         L.yabpe_pool_add.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_uint64]
@@ -205,6 +216,7 @@ LOAD_DEDUP = 0x1
 SPANS_CHARS = 0x1  # yabpe_encode_spans: code points instead of bytes
 LAYOUT_BOS, LAYOUT_EOS, LAYOUT_TRUNC_LEFT, LAYOUT_PAD_LEFT, LAYOUT_DROP_LAST = 0x01, 0x02, 0x04, 0x08, 0x10  # yabpe_layout_t.flags
 LAYOUT_NO_DOC = 0xFFFFFFFF  # `doc` of a packed slot past the end of the stream
+PAIRS_MODES = {"longest_first": 0, "only_first": 1, "only_second": 2, "windows": 3}  # yabpe_pairs_t.mode (YABPE_PAIRS_*)
 
 
 class Context:
@@ -675,6 +687,44 @@ class Context:
         rl = int(kw.get("row_len", 0))
         out = (self.d2h(dr, 4 * nr * rl, np.uint32).reshape(nr, rl),) + tuple(self.d2h(p, 4 * nr, np.uint32) for p in (dd, ds, dl))
         return out + (self.d2h(dsp, 16 * nr * rl, np.uint64).reshape(nr, rl, 2),) if spans is not None else out
+
+    def layout_pairs(self, ids, n_ids: int | None = None, doc_starts=None, n_docs: int | None = None, spans=None, row_len: int = 0,
+                     mode="longest_first", stride: int = 0, sep_id: int | None = None, n_sep: int = 1, pad_id: int = 0,
+                     bos_id: int | None = None, eos_id: int | None = None, pad_left: bool = False, flags: int = 0):
+        """Documents 2p and 2p + 1 as the two sides of pair p in rows of row_len (yabpe_layout_pairs); ids, doc_starts, spans
+        and the ids of the layout as layout_windows takes them (an empty doc_starts array: no pairs).  mode: a name of
+        PAIRS_MODES or a YABPE_PAIRS_* value; sep_id None: no separator, else n_sep copies of it between the sides.
+        -> (dev_rows_ptr u32[n_rows * row_len], dev_types_ptr u8[n_rows * row_len], dev_row_pair_ptr, dev_row_start_ptr,
+        dev_first_len_ptr, dev_second_len_ptr: u32[n_rows] each, dev_spans_ptr u64[n_rows * row_len * 2] or 0 without spans,
+        n_rows); the buffers live until the next layout call, layout_free() or close()."""
+        _keep, ptr, n, dptr, nd, lay = self._layout_args(ids, n_ids, doc_starts, n_docs, row_len, pad_id, bos_id, eos_id,
+                                                         flags | (LAYOUT_PAD_LEFT if pad_left else 0))
+        if doc_starts is not None and not isinstance(doc_starts, int) and len(doc_starts) == 0:
+            nd = 0
+        if spans is None or isinstance(spans, int):
+            sptr = c_void_p(spans or 0)
+        else:
+            keep_spans = np.ascontiguousarray(spans, dtype=np.uint64)
+            if keep_spans.size != 2 * n:
+                raise ValueError(f"spans must hold one (start, end) per id: {keep_spans.size} values for {n} ids")
+            if not keep_spans.size:
+                keep_spans = np.zeros(2, np.uint64)  # (no ids: never read, but not NULL -- the call still returns spans)
+            sptr = c_void_p(keep_spans.ctypes.data)
+        pairs = Pairs(int(sep_id or 0), int(n_sep) if sep_id is not None else 0, PAIRS_MODES[mode] if isinstance(mode, str) else int(mode),
+                      int(stride))
+        w = PairRows()
+        self._chk(lib().yabpe_layout_pairs(self._h, ptr, n, dptr, nd, sptr, byref(lay), byref(pairs), byref(w)))
+        return (w.rows or 0, w.types or 0, w.row_pair or 0, w.row_start or 0, w.first_len or 0, w.second_len or 0, w.spans or 0, w.n_rows)
+
+    def layout_pairs_to_host(self, ids, n_ids: int | None = None, doc_starts=None, n_docs: int | None = None, spans=None, **kw):
+        """-> (rows u32[n_rows, row_len], types u8[n_rows, row_len], row_pair, row_start, first_len, second_len: u32[n_rows]
+        each) copied to the host, with spans also the slots' spans u64[n_rows, row_len, 2]."""
+        dr, dt, *per_row, dsp, nr = self.layout_pairs(ids, n_ids, doc_starts, n_docs, spans, **kw)
+        rl = int(kw.get("row_len", 0))
+        get = lambda p, nbytes, dt_: self.d2h(p, nbytes, dt_) if nbytes else np.zeros(0, dt_)  # noqa: E731
+        out = (get(dr, 4 * nr * rl, np.uint32).reshape(nr, rl), get(dt, nr * rl, np.uint8).reshape(nr, rl)) + tuple(
+            get(p, 4 * nr, np.uint32) for p in per_row)
+        return out + (get(dsp, 16 * nr * rl, np.uint64).reshape(nr, rl, 2),) if spans is not None else out
 
     def layout_free(self) -> None:
         self._chk(lib().yabpe_layout_free(self._h))

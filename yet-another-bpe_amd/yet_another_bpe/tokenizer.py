@@ -442,6 +442,131 @@ class BBPETokenizer:
         out = (rows, row_doc, row_start, lengths)
         return out if offsets is None else out + (spans,)
 
+    PAIR_TRUNCATIONS = ("longest_first", "only_first", "only_second", "windows")
+
+    @staticmethod
+    def _pair_texts(firsts, seconds) -> tuple[list[str], list[str]]:
+        """the two sides as lists: sequences of str of equal length (one str is not a sequence of texts)"""
+        sides = []
+        for name, side in (("firsts", firsts), ("seconds", seconds)):
+            if isinstance(side, (str, bytes, bytearray, memoryview)):
+                raise ValueError(f"{name} must be a sequence of str, not one {type(side).__name__}")
+            try:
+                side = list(side)
+            except TypeError:
+                raise ValueError(f"{name} must be a sequence of str, not {side!r}") from None
+            if not all(isinstance(t, str) for t in side):
+                raise ValueError(f"{name} must hold str only")
+            sides.append(side)
+        if len(sides[0]) != len(sides[1]):
+            raise ValueError(f"firsts and seconds must be equally long: {len(sides[0])} and {len(sides[1])} texts")
+        return sides[0], sides[1]
+
+    def _pairs_args(self, max_length, truncation, stride, sep_id, n_sep, pad_id, bos_id, eos_id, padding_side, offsets):
+        """-> (max_length, stride, pad, bos, eos, sep or None, n_sep that counts, n_added)"""
+        pad, bos, eos, added = self._layout_ids(pad_id, bos_id, eos_id)
+        sep = None if sep_id is None else self._layout_ids(sep_id, None, None)[0]  # (validated as the other ids are)
+        if isinstance(n_sep, bool) or n_sep not in (0, 1, 2):
+            raise ValueError(f"n_sep must be 0, 1 or 2, not {n_sep!r}")
+        n_sep = int(n_sep) if sep is not None else 0
+        if n_sep == 0:
+            sep = None
+        added += n_sep
+        if truncation not in self.PAIR_TRUNCATIONS:
+            raise ValueError(f"truncation must be one of {self.PAIR_TRUNCATIONS}, not {truncation!r}")
+        max_length = self._row_length(max_length, "max_length", added + 1)  # (at least one content slot a row)
+        try:
+            stride = operator.index(stride)
+        except TypeError:
+            raise ValueError(f"stride must be an integer, not {stride!r}") from None
+        if truncation != "windows" and stride != 0:
+            raise ValueError(f"stride must be 0 with truncation {truncation!r}: only 'windows' makes several rows of a pair")
+        if not 0 <= stride < max_length - added:
+            raise ValueError(f"stride must be in [0, {max_length - added - 1}] (max_length less the added ids and one), not {stride}")
+        if padding_side not in ("left", "right"):
+            raise ValueError(f"padding_side must be 'left' or 'right', not {padding_side!r}")
+        if offsets not in (None, "char", "byte"):
+            raise ValueError(f"offsets must be None, 'char' or 'byte', not {offsets!r}")
+        return max_length, stride, pad, bos, eos, sep, n_sep, added
+
+    def encode_batch_pairs(self, firsts: Sequence[str], seconds: Sequence[str], max_length: int, *, truncation: str = "longest_first",
+                           stride: int = 0, sep_id: int | None = None, n_sep: int = 1, pad_id: int | None = None,
+                           bos_id: int | None = None, eos_id: int | None = None, padding_side: str = "right",
+                           offsets: str | None = None):
+        """Two texts in one row (the text_pair form: question + context, query + passage)
+        -> (rows, type_ids, row_pair, row_start, first_len, second_len), with offsets "char" or "byte" also the spans of every
+        slot.  firsts and seconds are sequences of str of equal length.  With A = encode(firsts[p]), B = encode(seconds[p]), la
+        and lb their lengths, n_added = (bos given) + (eos given) + n_sep (n_sep 0, 1 or 2; it counts only with a sep_id) and C
+        = max_length - n_added >= 1 content slots, a row is [bos_id] + A[:ka] + [sep_id] * n_sep + B[s : s + kb] + [eos_id],
+        padded with pad_id to max_length at its right end (padding_side "left": at its left end).  pad_id, bos_id, eos_id and
+        sep_id as encode_batch_padded takes its ids.
+        The truncation modes give one row per pair (row p is pair p, s = 0, stride must be 0); ids leave from the END of a side,
+        every row fits and nothing raises because a side is too long:
+          "longest_first"  while ka + kb > C: drop the last id of the longer side, of the second when both are equally long;
+          "only_first"     the first gives up the excess la + lb - C, down to zero ids; a second alone longer than C is cut to C;
+          "only_second"    the mirror image.
+        "windows" (0 <= stride <= C - 1; the extractive-QA form): ka = min(la, C - stride - 1) in every row of the pair, and
+        the second side is windowed as encode_batch_windows does with Cb = C - ka content slots and step = Cb - stride: row k has
+        s = k * step and kb = min(Cb, lb - s), the last row is the first with s + Cb >= lb; every pair has at least one row.
+        Rows are in pair order, in window order within a pair.
+        type_ids[r][c] = 0 in BOS, the first side, the separators and padding, 1 in the second side and EOS.  row_pair[r] = the
+        pair, row_start[r] = s, first_len[r] = ka, second_len[r] = kb (the length before padding is ka + kb + n_added).
+        offsets: spans[r][c] = (start, end) of the slot's id IN ITS OWN TEXT, as encode_with_offsets gives it (type_ids says
+        which text that is), (0, 0) in BOS, separator, EOS and pad slots.
+        Out of scope: max_length=None, dropout, truncation from the left, windows over the first side."""
+        L, stride, pad, bos, eos, sep, n_sep, added = self._pairs_args(max_length, truncation, stride, sep_id, n_sep, pad_id, bos_id, eos_id,
+                                                                       padding_side, offsets)
+        firsts, seconds = self._pair_texts(firsts, seconds)
+        if offsets is None:
+            sides = [[(ids, None) for ids in self.encode_batch(side)] for side in (firsts, seconds)]
+        else:
+            sides = [self.encode_batch_with_offsets(side, offsets) for side in (firsts, seconds)]
+        C = L - added
+        rows, types, row_pair, row_start, first_len, second_len, spans = [], [], [], [], [], [], []
+        for p, ((A, spa), (B, spb)) in enumerate(zip(*sides)):
+            la, lb = len(A), len(B)
+            if truncation == "windows":
+                ka = min(la, C - stride - 1)
+                Cb = C - ka
+                step = Cb - stride
+                cuts = []
+                for s in range(0, lb + step, step):  # (left by the break below: the first row that reaches the end)
+                    cuts.append((s, min(Cb, lb - s)))
+                    if s + Cb >= lb:
+                        break
+            else:
+                ka, kb = la, lb
+                if truncation == "longest_first":
+                    while ka + kb > C:
+                        if ka > kb:
+                            ka -= 1
+                        else:
+                            kb -= 1
+                else:
+                    excess = max(0, la + lb - C)
+                    if truncation == "only_first":
+                        ka, kb = max(0, la - excess), min(lb, C)
+                    else:
+                        ka, kb = min(la, C), max(0, lb - excess)
+                cuts = [(0, kb)]
+            n_bos, n_eos = int(bos is not None), int(eos is not None)
+            for s, kb in cuts:
+                seq = [bos] * n_bos + list(A[:ka]) + [sep] * n_sep + list(B[s:s + kb]) + [eos] * n_eos
+                typ = [0] * (n_bos + ka + n_sep) + [1] * (kb + n_eos)
+                fill = L - len(seq)
+                rows.append(seq + [pad] * fill if padding_side == "right" else [pad] * fill + seq)
+                types.append(typ + [0] * fill if padding_side == "right" else [0] * fill + typ)
+                row_pair.append(p)
+                row_start.append(s)
+                first_len.append(ka)
+                second_len.append(kb)
+                if offsets is not None:
+                    seq_sp = ([(0, 0)] * n_bos + [tuple(x) for x in spa[:ka]] + [(0, 0)] * n_sep + [tuple(x) for x in spb[s:s + kb]]
+                              + [(0, 0)] * n_eos)
+                    spans.append(seq_sp + [(0, 0)] * fill if padding_side == "right" else [(0, 0)] * fill + seq_sp)
+        out = (rows, types, row_pair, row_start, first_len, second_len)
+        return out if offsets is None else out + (spans,)
+
     # ------------------------------------------------------------------ encode on the GPU (yabpe_encode; same ids as encode)
     def _device(self, model: str = "encode"):
         if self._device_ctx is None:
@@ -610,6 +735,32 @@ class BBPETokenizer:
         text, n_bytes, starts = self._device_text(ctx, inp)
         di, dd, ds, ni = ctx.encode_spans(text, n_bytes, doc_starts=starts, chars=offsets == "char")
         return ctx.layout_windows_to_host(di, ni, dd, len(inp[1]), ds or np.zeros((0, 2), np.uint64), **kw)
+
+    def encode_array_pairs(self, firsts: Sequence[str], seconds: Sequence[str], max_length: int, *, truncation: str = "longest_first",
+                           stride: int = 0, sep_id: int | None = None, n_sep: int = 1, pad_id: int | None = None,
+                           bos_id: int | None = None, eos_id: int | None = None, padding_side: str = "right",
+                           offsets: str | None = None):
+        """encode_batch_pairs(firsts, seconds, ...), computed on the GPU: ONE yabpe_encode call (offsets: yabpe_encode_spans)
+        over the 2 n texts first, second, first, second, ..., then yabpe_layout_pairs on its device results (the ragged ids
+        never visit the host).  -> (ids np.uint32[n_rows, max_length], type_ids np.uint8[n_rows, max_length], row_pair,
+        row_start, first_len, second_len: np.uint32[n_rows] each), with offsets also np.uint64[n_rows, max_length, 2] -- with
+        a normaliser the spans refer to the normalised texts, as encode_array_with_offsets' do."""
+        L, stride, pad, bos, eos, sep, n_sep, _added = self._pairs_args(max_length, truncation, stride, sep_id, n_sep, pad_id, bos_id, eos_id,
+                                                                        padding_side, offsets)
+        firsts, seconds = self._pair_texts(firsts, seconds)
+        inp = self._device_input([t for pair in zip(firsts, seconds) for t in pair])
+        if inp is None:
+            out = (np.zeros((0, L), np.uint32), np.zeros((0, L), np.uint8)) + tuple(np.zeros(0, np.uint32) for _ in range(4))
+            return out if offsets is None else out + (np.zeros((0, L, 2), np.uint64),)
+        ctx = self._device()
+        kw = dict(row_len=L, mode=truncation, stride=stride, sep_id=sep, n_sep=n_sep, pad_id=pad, bos_id=bos, eos_id=eos,
+                  pad_left=padding_side == "left")
+        text, n_bytes, starts = self._device_text(ctx, inp)
+        if offsets is None:
+            di, dd, ni = ctx.encode(text, n_bytes, doc_starts=starts)
+            return ctx.layout_pairs_to_host(di, ni, dd, len(inp[1]), **kw)
+        di, dd, ds, ni = ctx.encode_spans(text, n_bytes, doc_starts=starts, chars=offsets == "char")
+        return ctx.layout_pairs_to_host(di, ni, dd, len(inp[1]), ds or np.zeros((0, 2), np.uint64), **kw)
 
     # ------------------------------------------------------------------ decode (tokenizer.py:324-349)
     def decode(self, ids: Sequence[int]) -> str:
