@@ -223,6 +223,8 @@ struct yabpe_ctx {
     unsigned long long cand_best_at_build = 0;
     uint32_t *sel_ticket = nullptr;  // finished-workgroup counters (TICKET_WORDS; the last workgroup selects; they reset themselves)
     unsigned long long *cand = nullptr;
+    unsigned long long *cand_bits = nullptr;  // "listed" bit per slot of c->table (written whole by every k_cand_rebuild)
+    uint64_t cand_bits_cap = 0;               // table capacity it was sized to
     bool use_cand = false;
     uint64_t cand_rebuilds = 0, cand_rescans = 0;
     double cand_margin = 0.2;        // T = best count x (1 - margin); adapted so that the list stays short
@@ -366,6 +368,7 @@ void table_free(PairTable &t) {
     t.cnt = nullptr;
     t.cand_cs = nullptr;
     t.cand_list = nullptr;
+    t.cand_bits = nullptr;
     t.cand_T = 0;
     t.sink_rec = nullptr;
     t.sink_hdr = nullptr;
@@ -386,18 +389,24 @@ int table_alloc(yabpe_ctx *c, PairTable &t, uint64_t cap, unsigned long long *en
     // (the candidate list is attached to the main table only, once it is built: cand_attach / cand_rebuild)
     t.cand_cs = nullptr;
     t.cand_list = nullptr;
+    t.cand_bits = nullptr;
     t.cand_T = 0;
     HIPCHK(c, hipMemsetAsync(t.keys, 0xFF, cap * sizeof(uint32_t), c->stream));
     HIPCHK(c, hipMemsetAsync(t.cnt, 0, cap * sizeof(unsigned long long), c->stream));
     return 0;
 }
 
-// bitmap of the candidate argmax for the main table (cleared; the candidate list is rebuilt by the caller's next check)
+// The main table has new slots (rebuilt, grown): the candidate list is detached and its "listed" bitmap, which names slots,
+// goes with it; the caller's next check rebuilds both (cand_rebuild) at the new capacity.
 int cand_attach(yabpe_ctx *c) {
     c->use_cand = false;
     PairTable &t = c->table;
     t.cand_cs = nullptr;
     t.cand_list = nullptr;
+    t.cand_bits = nullptr;
+    dfree(c->cand_bits);
+    c->cand_bits = nullptr;
+    c->cand_bits_cap = 0;
     if (!optv(c, "cand_argmax", 1)) return 0;
     if (!c->sel_ticket) {
         TRY(dmalloc(c, &c->sel_ticket, TICKET_WORDS));
@@ -417,7 +426,15 @@ int cand_rebuild(yabpe_ctx *c, unsigned long long best_count) {
     c->use_cand = false;
     c->table.cand_cs = nullptr;
     c->table.cand_list = nullptr;
+    c->table.cand_bits = nullptr;
     if (!optv(c, "cand_argmax", 1) || !c->cand_state || best_count < (unsigned long long)optv(c, "cand_min_count", 16)) return 0;
+    if (!c->cand_bits || c->cand_bits_cap != c->table.cap) {  // (k_cand_rebuild writes every word: nothing to clear)
+        dfree(c->cand_bits);
+        c->cand_bits = nullptr;
+        c->cand_bits_cap = 0;
+        TRY(dmalloc(c, &c->cand_bits, yb_cand_bitmap_words(c->table.cap)));
+        c->cand_bits_cap = c->table.cap;
+    }
     const uint32_t target = (uint32_t)std::max<int64_t>(64, optv(c, "cand_target", 768));
     const uint32_t grid = (uint32_t)std::min<uint64_t>(1024, std::max<uint64_t>(1, c->table_cap / (BLOCK * 8)));
     CandState h{};
@@ -428,6 +445,7 @@ int cand_rebuild(yabpe_ctx *c, unsigned long long best_count) {
         HIPCHK(c, hipMemcpyAsync(c->cand_state, &h, sizeof h, hipMemcpyHostToDevice, c->stream));
         PairTable t = c->table;
         t.cand_list = c->cand;
+        t.cand_bits = c->cand_bits;
         t.cand_cs = c->cand_state;
         t.cand_T = h.T;
         {
@@ -452,6 +470,7 @@ int cand_rebuild(yabpe_ctx *c, unsigned long long best_count) {
     if (c->use_cand) {
         c->table.cand_cs = c->cand_state;
         c->table.cand_list = c->cand;
+        c->table.cand_bits = c->cand_bits;
         c->table.cand_T = h.T;
     }
     return 0;
@@ -1318,6 +1337,7 @@ void yabpe_destroy(yabpe_ctx *c) {
     dfree(c->cand_state);
     dfree(c->sel_ticket);
     dfree(c->cand);
+    dfree(c->cand_bits);
     dfree(c->xsend);
     dfree(c->xrecv);
     dfree(c->xsmall);

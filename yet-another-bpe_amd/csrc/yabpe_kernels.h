@@ -14,7 +14,7 @@
 //   select_eval   the next merges: exact argmax over a candidate list by (count, lexrank[left], lexrank[right])
 //                 (trainer.py:246), stop rules, merged-token creation / byte-string identity (trainer.py:241-251, 296-300);
 //                 run by the LAST workgroup of the launch that applied the previous batch (fused_select_tail).
-//                 select_body: one merge, as a launch of its own; both end in sel_stop, a single merge in commit_merge.
+//                 select_body: one merge, as a launch of its own; both apply sel_stop, a single merge ends in commit_merge.
 //   rank blocks   extra workgroups of every launch keep lexrank[] = rank of every token's bytes in Python bytes order
 #pragma once
 #include <hip/hip_runtime.h>
@@ -24,6 +24,7 @@
 
 #include "limit_logic.h"
 #include "load_logic.h"
+#include "select_logic.h"
 #include "steal_logic.h"
 #include "tile_logic.h"
 #include "train_rules.h"  // WPB, BLOCK, AGG_N, KMAX, scan_kt_max: shared with the host's launch rules
@@ -114,6 +115,7 @@ struct PairTable {
     // candidate argmax (main table only, else NULL): a count that rises to >= cand_T puts its slot on the candidate list
     CandState *cand_cs;          // list length / overflow flag
     unsigned long long *cand_list; // entries: slot | key << 32
+    unsigned long long *cand_bits; // one "listed" bit per slot (cap / 64 words): no slot is on the list twice
     unsigned long long cand_T;
     // multi-GPU: not a table at all but this rank's send buffer -- every update becomes a (key, delta) record that all
     // ranks add to their replicas after the exchange (k_delta_apply).  keys / cnt are unused then.
@@ -244,13 +246,16 @@ __device__ __forceinline__ uint32_t ld_coherent(const uint32_t *p) { return __hi
 
 // The count of slot s rose from `old` to `now`: the add that takes it across the threshold of the candidate argmax puts the slot
 // on the list.  Adds to one address are totally ordered, so exactly one adder sees the crossing; a count that falls below the
-// threshold and crosses again is listed twice, which is harmless (the same slot, the same count).  (Until round 2 every adder
-// that saw a count >= T tried to list it and a bitmap kept the list free of repeats: one more dependent atomic in the flush of
-// exactly the workgroups that finish last.)  Invariant kept between two rebuilds of the list: every slot whose count is
-// >= cand_T is on it.  Counts only go up through the two functions below, so nothing else has to look at the table.
-// (Signed comparisons: a count can be transiently negative while the deltas of one merge arrive in any order.)
+// threshold and crosses again is NOT listed twice: the crossing sets the slot's "listed" bit with one returning OR and
+// appends only if the bit was clear (select_logic.h), so the selection's window is a plain count of list entries.  The OR
+// is issued by crossings only -- a handful per launch.  (Until round 2 every adder that saw a count >= T took the bitmap:
+// one more dependent atomic in the flush of exactly the workgroups that finish last.)  Invariants kept between two
+// rebuilds of the list: every slot whose count is >= cand_T is on it, and no slot is on it twice.  Counts only go up
+// through the two functions below, so nothing else has to look at the table.  Both returning atomics are consumed inside
+// this rare branch (the bit decides, the index addresses the store): no destination register is pending where it rejoins.
 __device__ __forceinline__ void cand_note(const PairTable &t, uint32_t s, uint32_t key, unsigned long long old, unsigned long long now) {
-    if ((long long)now < (long long)t.cand_T || (long long)old >= (long long)t.cand_T || (long long)now <= 0) return;
+    if (!yb_cand_crosses(old, now, t.cand_T)) return;
+    if (!yb_cand_lists(atomicOr(&t.cand_bits[yb_cand_word(s)], yb_cand_bit(s)), s)) return;
     const uint32_t idx = atomicAdd(&t.cand_cs->n, 1u);
     if (idx < CAND_CAP)
         st_coherent(&t.cand_list[idx], (unsigned long long)s | ((unsigned long long)key << 32));
@@ -1954,7 +1959,7 @@ __device__ __forceinline__ int cmp_pre8(unsigned long long px, uint32_t lx, unsi
 // DevState snapshot, apply the same stop rules and commit a single merge the same way.  All of it runs in one thread or one
 // wave of the selecting workgroup.
 
-// The DevState fields a selection reads, loaded by ONE thread (thread 0; the others keep zeros).  list: a candidate list is
+// The DevState fields a selection reads, loaded by ONE thread (the others keep zeros).  list: a candidate list is
 // attached -- without one, T = 0 and no overflow, so the stop rules never ask for a rescan.
 struct SelState {
     uint32_t iter, done, halt, halt_req, n_tokens, pool_used, num_merges, cand_over, cand_n;
@@ -2192,24 +2197,33 @@ __device__ __forceinline__ void select_body(const SelectParams &P) {
 
 // ---------------------------------------------------------------- the fused selection (tail of every per-batch launch)
 // Same contract as select_body, for a BATCH of merges and built for the critical path: four round trips (list + state, counts, token records
-// of the window, byte-string set probes) and, between them, one workgroup-wide maximum, the window (distinct pairs with
-// count >= max - delta, LDS hash set) and then ONE WAVE that sorts the window, walks it under the batch rule with
-// wave-level votes (no workgroup barriers), probes the byte-string set for every accepted merge side by side and commits.
+// of the window, byte-string set probes) and, between them, one workgroup-wide maximum, the window (the list entries with
+// count >= max - delta: the list holds no pair twice, so ballots count and place them), the window's order and the batch
+// rule for all entries side by side, and then ONE WAVE that cuts the batch and commits.  What does not depend on the rule
+// runs beside it: the stop rules in a thread of the last wave while the token records are on their way, the byte-string-set
+// probe of a position in the thread that learns the position while the rule is evaluated.
 // More than WIN pairs tying at the top, or a first merge whose bytes may exist already (a full byte compare decides), end in
 // a batch of one.
 // s_win: LDS for WIN window entries (8 KiB), the caller's -- a kernel whose own tables are dead by now lends them.
 __device__ __forceinline__ void select_eval(const SelectParams &P, WinEnt *s_win) {
     __shared__ AccEnt s_acc[KMAX];
-    __shared__ __attribute__((aligned(16))) uint32_t s_hset[2 * WIN]; // (the window's hash set; afterwards the packed sort keys live here)
+    __shared__ __attribute__((aligned(16))) unsigned long long s_pk[WIN]; // the packed sort keys of the window
     __shared__ unsigned long long s_red[WPB], s_fold[2];
     __shared__ uint32_t s_nwin;
     struct TopEnt { unsigned long long cnt; uint32_t key, win; }; // the entry at a position of the selection order
+    // the byte-string set's answer for the merged token of a position: probed by the thread that owns the position
+    struct ProbeEnt { unsigned long long H, ve; uint32_t slot, len; };
+    // what the stop rules leave for the wave that commits
+    struct StopEnt { unsigned long long live_slots; uint32_t flag, iter, num_merges, n_tokens, pool_used, pad; };
     __shared__ unsigned long long s_lim[2];
     __shared__ uint32_t s_flags[2];
-    unsigned long long *s_pk = reinterpret_cast<unsigned long long *>(s_hset); // [WIN]
     __shared__ TopEnt s_top[KMAX];
+    __shared__ ProbeEnt s_probe[KMAX];
+    __shared__ StopEnt s_stop;
     static_assert(BLOCK == 2 * WIN, "two threads rank one window entry");
-    constexpr uint32_t HSET = 2 * WIN;
+    // The thread that holds the state and applies the stop rules: the first of the LAST wave.  A window has at most WIN =
+    // BLOCK / 2 entries, so that wave loads no token records (round trip 3): it runs the stop rules meanwhile.
+    constexpr int S_TID = BLOCK - 64;
     DevState *st = P.st;
     const int tid = threadIdx.x;
     const int lane = tid & 63;
@@ -2222,12 +2236,14 @@ __device__ __forceinline__ void select_eval(const SelectParams &P, WinEnt *s_win
     const uint32_t kmax = min(st->kmax, (uint32_t)KMAX);
     SelState S{};
     if (tid == 0) {
-        S = sel_state_load(P, true);
         s_fold[0] = 0;
         s_fold[1] = 0;
         s_nwin = 0;
         s_flags[0] = 0u; // positions of the selection order that fail the batch rule
         s_flags[1] = 0u; // positions that hold a run merge (p == q)
+    }
+    if (tid == S_TID) {
+        S = sel_state_load(P, true);
         s_lim[0] = S.candT;
         s_lim[1] = S.min_freq;
     }
@@ -2238,12 +2254,14 @@ __device__ __forceinline__ void select_eval(const SelectParams &P, WinEnt *s_win
         vx[k] = i < P.n_blk ? ld_coherent(&P.blk_stats[2 * i]) : 0ull;
         vy[k] = i < P.n_blk ? ld_coherent(&P.blk_stats[2 * i + 1]) : 0ull;
     }
-    for (uint32_t hidx = tid; hidx < HSET; hidx += BLOCK) s_hset[hidx] = EMPTY;
     // ---- round trip 2: the counts (the slot rides in the list entry)
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
-        cn[k] = 0ull;
-        if ((uint32_t)(tid + k * BLOCK) < n_list) cn[k] = ld_coherent(pt_count_ptr(P.table, e[k]));
+        // (no branch around the load: past the list's end it reads slot 0 and drops the value.  Under four divergent branches
+        // the compiler waits for each load at its join -- four dependent trips where one does)
+        const bool listed = (uint32_t)(tid + k * BLOCK) < n_list;
+        cn[k] = ld_coherent(pt_count_ptr(P.table, listed ? e[k] : 0ull));
+        if (!listed) cn[k] = 0ull;
     }
     // (the counters are summed while the counts are on their way)
     unsigned long long fa = 0, ff = 0;
@@ -2284,7 +2302,7 @@ __device__ __forceinline__ void select_eval(const SelectParams &P, WinEnt *s_win
     }
     YB_SEL_STAMP(10);
     cmax = best_wave_reduce(Best{cmax, 0u, 0u, 0u, 0u}).cnt;
-    __syncthreads(); // (s_fold / s_nwin / s_hset initialised)
+    __syncthreads(); // (s_fold / s_nwin initialised)
     if (lane == 0) {
         s_red[tid >> 6] = cmax;
         if (fa | ff) {
@@ -2296,59 +2314,62 @@ __device__ __forceinline__ void select_eval(const SelectParams &P, WinEnt *s_win
 #pragma unroll
     for (int w = 0; w < WPB; ++w) cmax = s_red[w] > cmax ? s_red[w] : cmax;
     YB_SEL_STAMP(12);
-    // ---- the window: the DISTINCT pairs with count >= L = cmax - delta (whole count levels by construction; a pair may be
-    // listed more than once, and how often differs between the replicas of a multi-GPU job: the set keeps repeats out, so every
-    // rank walks the same window).  More than WIN of them: a quarter of the distance, again.
-    unsigned long long L = 0ull;
-    uint32_t n_win = 0;
-    uint32_t wshift = min(max(st->win_shift, 1u), 20u), narrowed = 0;
-    if (cmax) {
-        unsigned long long delta = kmax > 1u ? min(max((unsigned long long)kmax, cmax >> wshift), 1ull << 31) : 0ull;
-        for (int attempt = 0; attempt < 8; ++attempt) {
-            L = cmax > delta ? cmax - delta : 1ull;
-            // (never below the list's threshold: only pairs with count >= T are on EVERY replica's list -- a pair below it may be
-            // listed on one rank and not on another, and the window's size decides how far a batch can go)
-            if (kmax > 1u && L < s_lim[0] && cmax >= s_lim[0]) L = s_lim[0];
-            auto put = [&](unsigned long long ent, unsigned long long c) {
-                const uint32_t key = (uint32_t)(ent >> 32);
-                uint32_t h = hash32(key) & (HSET - 1u);
-                for (uint32_t probe = 0; probe < HSET; ++probe) {
-                    const uint32_t was = atomicCAS(&s_hset[h], EMPTY, key);
-                    if (was == key) return; // listed twice
-                    if (was == EMPTY) {
-                        const uint32_t idx = atomicAdd(&s_nwin, 1u);
-                        if (idx < (uint32_t)WIN) {
-                            s_win[idx].cnt = c;
-                            s_win[idx].key = key;
-                            s_win[idx].slot = (uint32_t)ent;
-                        }
-                        return;
-                    }
-                    h = (h + 1u) & (HSET - 1u);
-                }
-                s_nwin = WIN + 1u; // (the set is full: more distinct pairs than a window holds)
-            };
-#pragma unroll
-            for (int k = 0; k < 4; ++k)
-                if (cn[k] >= L) put(e[k], cn[k]);
-            for (uint32_t ti = 4u * BLOCK + tid; ti < n_list; ti += BLOCK) {
-                const unsigned long long ent = ld_coherent(&P.table.cand_list[ti]);
-                const long long c = (long long)ld_coherent(pt_count_ptr(P.table, ent));
-                if (c > 0 && (unsigned long long)c >= L) put(ent, (unsigned long long)c);
-            }
-            __syncthreads();
-            n_win = s_nwin;
-            if (n_win <= (uint32_t)WIN) break;
-            n_win = 0;
-            if (delta == 0ull) break; // more than WIN pairs tie at the top: no window
-            delta >>= 2;
-            narrowed += 2;
+    // ---- the window: the list entries with count >= L = cmax - delta (whole count levels by construction).  The list holds
+    // every pair once (cand_note), so the entries that qualify ARE the distinct pairs: every thread knows its up-to-four, a
+    // ballot per k counts a wave's and places them, and the waves take their places in the window with one LDS add each.
+    // The window is a SET -- it is ordered by (count, lexranks) afterwards -- so neither the order of the list nor the order
+    // in which the waves arrive shows in the result: every rank of a multi-GPU job walks the same window.  More than WIN
+    // entries: a quarter of the distance, again (yb_win_search, select_logic.h).
+    const uint32_t wshift = min(max(st->win_shift, 1u), 20u);
+    const YbWindow wnd = yb_win_search(cmax, kmax, wshift, s_lim[0], (uint32_t)WIN, [&](unsigned long long Lf, int attempt) -> uint32_t {
+        if (attempt) {
             __syncthreads(); // (everybody has read s_nwin)
-            for (uint32_t hidx = tid; hidx < HSET; hidx += BLOCK) s_hset[hidx] = EMPTY;
             if (tid == 0) s_nwin = 0;
             __syncthreads();
         }
-    }
+        auto place = [&](bool in, unsigned long long ent, unsigned long long c, unsigned long long b, uint32_t at) {
+            const uint32_t idx = at + bits_below_lane(b);
+            if (in && idx < (uint32_t)WIN) {
+                s_win[idx].cnt = c;
+                s_win[idx].key = (uint32_t)(ent >> 32);
+                s_win[idx].slot = (uint32_t)ent;
+            }
+        };
+        unsigned long long b[4];
+        uint32_t tot = 0, at = 0;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) { // (Lf >= 1, and cn is 0 past the list's end)
+            b[k] = __ballot(cn[k] >= Lf);
+            tot += (uint32_t)__popcll(b[k]);
+        }
+        if (lane == 0 && tot) at = atomicAdd(&s_nwin, tot);
+        at = __builtin_amdgcn_readfirstlane(at);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            place(cn[k] >= Lf, e[k], cn[k], b[k], at);
+            at += (uint32_t)__popcll(b[k]);
+        }
+        // (a long list: rare, the host rebuilds it before.  Whole waves walk it, so that every lane meets the ballot.)
+        for (uint32_t t0 = 4u * BLOCK + (uint32_t)(tid & ~63); t0 < n_list; t0 += BLOCK) {
+            const uint32_t ti = t0 + (uint32_t)lane;
+            unsigned long long ent = 0ull;
+            long long c = 0;
+            if (ti < n_list) {
+                ent = ld_coherent(&P.table.cand_list[ti]);
+                c = (long long)ld_coherent(pt_count_ptr(P.table, ent));
+            }
+            const bool in = c > 0 && (unsigned long long)c >= Lf;
+            const unsigned long long bb = __ballot(in);
+            uint32_t at2 = 0;
+            if (lane == 0 && bb) at2 = atomicAdd(&s_nwin, (uint32_t)__popcll(bb));
+            place(in, ent, (unsigned long long)c, bb, __builtin_amdgcn_readfirstlane(at2));
+        }
+        __syncthreads();
+        return s_nwin;
+    });
+    const unsigned long long L = wnd.L;
+    const uint32_t narrowed = wnd.narrowed;
+    uint32_t n_win = wnd.n;
     if (cmax && n_win == 0) {
         // More than WIN distinct pairs tie at the top (small counts late in a small job): no walk -- the greatest of them by
         // (lexrank, lexrank) is the merge (trainer.py:246), found the plain way; it becomes a window of one.
@@ -2383,6 +2404,18 @@ __device__ __forceinline__ void select_eval(const SelectParams &P, WinEnt *s_win
         n_win = 1;
     }
     YB_SEL_STAMP(13);
+    // ---- the stop rules, beside round trip 3: they ask for the folded counters and cmax only.  What the committing wave needs of
+    // the state goes through LDS; the barriers behind the ranking put these stores in front of the commit's.
+    if (tid == S_TID) {
+        s_stop.flag = sel_stop(P, S, s_fold[0], s_fold[1], cmax);
+        s_stop.iter = S.iter;
+        s_stop.num_merges = S.num_merges;
+        s_stop.n_tokens = S.n_tokens;
+        s_stop.pool_used = S.pool_used;
+        s_stop.live_slots = S.live_slots;
+        // next time: a narrower window after an overflow, a wider one when this one held few pairs
+        if (kmax > 1u) st->win_shift = narrowed ? min(wshift + narrowed, 20u) : (n_win < 4u * kmax && wshift > 1u) ? wshift - 1u : wshift;
+    }
     // ---- round trip 3: the two token records of every window entry (one entry per thread)
     if ((uint32_t)tid < n_win) {
         const uint32_t key = s_win[tid].key;
@@ -2414,6 +2447,7 @@ __device__ __forceinline__ void select_eval(const SelectParams &P, WinEnt *s_win
     const uint32_t wt = (uint32_t)(tid >> 6) * 32u + ((uint32_t)lane & 31u), whalf = (uint32_t)lane >> 5; // (BLOCK == 2 * WIN)
     uint32_t my_pos = 0xffffu, my_key = 0u;
     unsigned long long my_cnt = 0ull;
+    ProbeEnt my_probe{0ull, VSET_EMPTY, 0u, 0u};
     {
         const unsigned long long mine = s_pk[wt];
         const ulonglong2 *pk2 = reinterpret_cast<const ulonglong2 *>(s_pk) + whalf * (uint32_t)(WIN / 4);
@@ -2429,8 +2463,17 @@ __device__ __forceinline__ void select_eval(const SelectParams &P, WinEnt *s_win
             my_key = s_win[wt].key;
             my_cnt = s_win[wt].cnt;
             if (my_pos < (uint32_t)KMAX) {
+                const WinEnt &w = s_win[wt];
+                const uint32_t lx = w.lx, ly = w.ly;
+                const unsigned long long px = w.px, py = w.py;
                 s_top[my_pos] = TopEnt{my_cnt, my_key, wt};
-                s_acc[my_pos] = AccEnt{my_key >> 16, my_key & 0xffffu, s_win[wt].lx + s_win[wt].ly, wt, pre8_concat(s_win[wt].px, s_win[wt].lx, s_win[wt].py)};
+                s_acc[my_pos] = AccEnt{my_key >> 16, my_key & 0xffffu, lx + ly, wt, pre8_concat(px, lx, py)};
+                // round trip 4, issued here: the first probe of the byte-string set for this position's merged token.  It
+                // is in flight while the batch rule is evaluated; the wave that commits cuts the batch from what has arrived.
+                my_probe.len = lx + ly;
+                my_probe.H = yb_hash_concat(w.hx, w.hy, ly);
+                my_probe.slot = yb_vset_home(my_probe.H, my_probe.len) & P.tt.vset_mask;
+                my_probe.ve = ld_coherent(&P.tt.vset[my_probe.slot]);
             }
         }
     }
@@ -2476,19 +2519,18 @@ __device__ __forceinline__ void select_eval(const SelectParams &P, WinEnt *s_win
             const uint32_t rl = s_win[wt].rk >> 16, rp = s_win[cwin].rk >> 16; // lexranks of my left token and of p
             if (left_new_blocks || ((ra & below) != 0u && (rl > rp || (rl == rp && right_new_ge)))) atomicOr(&s_flags[0], 1u << j2);
         }
+        if (my_pos < (uint32_t)KMAX) s_probe[my_pos] = my_probe; // (the probe has had the rule's time to arrive)
     }
     __syncthreads();
     YB_SEL_STAMP(14);
     if (tid >= 64) return; // ---- from here on: wave 0 alone, wave-level synchronisation only
-    // ---- stop rules and the first merge (lane 0 holds the state)
-    uint32_t flag = 0; // 1: nothing selected (done / halt)
-    if (lane == 0) {
-        flag = sel_stop(P, S, s_fold[0], s_fold[1], cmax);
-        // next time: a narrower window after an overflow, a wider one when this one held few pairs
-        if (kmax > 1u) st->win_shift = narrowed ? min(wshift + narrowed, 20u) : (n_win < 4u * kmax && wshift > 1u) ? wshift - 1u : wshift;
-    }
-    flag = __builtin_amdgcn_readfirstlane(flag);
-    if (flag) return;
+    // ---- what the stop rules decided (1: nothing selected -- done / halt) and the state they left
+    if (__builtin_amdgcn_readfirstlane(s_stop.flag)) return;
+    S.iter = s_stop.iter;
+    S.num_merges = s_stop.num_merges;
+    S.n_tokens = s_stop.n_tokens;
+    S.pool_used = s_stop.pool_used;
+    S.live_slots = s_stop.live_slots;
     YB_SEL_STAMP(3);
     // ---- the batch: positions [0, nacc) -- up to the first position that fails, the first run merge included, the limits
     const uint32_t it0 = __builtin_amdgcn_readfirstlane(S.iter), num_merges = __builtin_amdgcn_readfirstlane(S.num_merges);
@@ -2507,16 +2549,17 @@ __device__ __forceinline__ void select_eval(const SelectParams &P, WinEnt *s_win
         }
     }
     YB_STOP(it0, why, nacc, n_win);
-    // ---- round trip 4: the merged tokens: one probe of the byte-string set each, side by side (lane k: merge k)
+    // ---- round trip 4 has arrived (s_probe: one probe of the byte-string set per position, lane k: merge k); only a key that
+    // sits displaced from its home slot is probed further here (rare)
     unsigned long long Hk = 0ull, ve = VSET_EMPTY;
     uint32_t Lk = 0, vslot = 0, wk = 0;
     if ((uint32_t)lane < nacc) {
         wk = s_acc[lane].win;
-        const uint32_t lxk = s_win[wk].lx, lyk = s_win[wk].ly;
-        Lk = lxk + lyk;
-        Hk = yb_hash_concat(s_win[wk].hx, s_win[wk].hy, lyk);
-        vslot = yb_vset_home(Hk, Lk) & P.tt.vset_mask;
-        ve = ld_coherent(&P.tt.vset[vslot]);
+        const ProbeEnt pe = s_probe[lane];
+        Lk = pe.len;
+        Hk = pe.H;
+        vslot = pe.slot;
+        ve = pe.ve;
         while (ve != VSET_EMPTY && (ve >> 32) != (Hk >> 32)) {
             vslot = (vslot + 1) & P.tt.vset_mask;
             ve = ld_coherent(&P.tt.vset[vslot]);
@@ -2909,14 +2952,27 @@ __global__ __launch_bounds__(BLOCK) void k_argmax_cand(CandParams P) {
     select_body(P.sel);
 }
 
-// list = every slot with count >= cs->T (the bitmap was cleared by the host)
+// list = every slot with count >= cs->T, and the "listed" bitmap with it: a wave covers 64 consecutive slots, so its ballot
+// IS the bitmap's word -- every word of the bitmap is written here (no clear in front, no atomics on it), and the list's
+// length takes one add per wave.
 __global__ __launch_bounds__(BLOCK) void k_cand_rebuild(CandParams P) {
     const unsigned long long T = P.cs->T;
-    for (uint32_t s = blockIdx.x * BLOCK + threadIdx.x; s < P.table.cap; s += gridDim.x * BLOCK) {
-        const long long cn = (long long)P.table.cnt[s];
-        if (cn <= 0 || (unsigned long long)cn < T) continue;
-        const uint32_t idx = atomicAdd(&P.cs->n, 1u);
-        if (idx < CAND_CAP) P.table.cand_list[idx] = (unsigned long long)s | ((unsigned long long)P.table.keys[s] << 32); else P.cs->overflow = 1u;
+    const uint32_t lane = threadIdx.x & 63u;
+    // (64-bit: the last stride of a table near 2^32 slots must not wrap)
+    for (unsigned long long s0 = (unsigned long long)blockIdx.x * BLOCK + (threadIdx.x & ~63u); s0 < P.table.cap; s0 += (unsigned long long)gridDim.x * BLOCK) {
+        const uint32_t s = (uint32_t)s0 + lane;
+        const bool lists = s0 + lane < P.table.cap && yb_cand_rebuild_lists(P.table.cnt[s], T);
+        const unsigned long long word = __ballot(lists);
+        uint32_t base = 0;
+        if (lane == 0) {
+            P.table.cand_bits[yb_cand_word((uint32_t)s0)] = word;
+            if (word) base = atomicAdd(&P.cs->n, (uint32_t)__popcll(word));
+        }
+        base = __builtin_amdgcn_readfirstlane(base);
+        if (lists) {
+            const uint32_t idx = base + bits_below_lane(word);
+            if (idx < CAND_CAP) P.table.cand_list[idx] = (unsigned long long)s | ((unsigned long long)P.table.keys[s] << 32); else P.cs->overflow = 1u;
+        }
     }
 }
 
