@@ -337,6 +337,33 @@ typedef struct yabpe_normalize_stats_t {
 } yabpe_normalize_stats_t;
 int yabpe_normalize_stats(yabpe_ctx *ctx, yabpe_normalize_stats_t *out);
 
+/* Text with invalid UTF-8 (the step in front of the normaliser) ---------------------------------------
+ * errors="replace" / "ignore" on the device: every part [part_off[k], part_off[k+1]) of `text` (read as yabpe_normalize reads
+ * them: n_parts ascending starts, the first one 0, the last part ends at n_bytes; part_off == NULL: one part) is replaced by
+ * part.decode("utf-8", errors).encode("utf-8") of CPython: every maximal subpart of an ill-formed sequence becomes U+FFFD
+ * (EF BF BD, YABPE_UTF8_REPLACE) or is dropped (YABPE_UTF8_IGNORE); any other mode: YABPE_E_INVALID.  Parts are texts of
+ * their own: a sequence cut off by a part's end is ill-formed there and never joins the next part (csrc/utf8_logic.h).
+ * text may be host or device memory.  Results (owned by the library, valid until yabpe_utf8_repair_free, the next
+ * yabpe_utf8_repair or yabpe_destroy): *out_dev_text = *out_n_bytes bytes in device memory (at most 3 x n_bytes, possibly 0),
+ * *out_dev_part_off = n_parts + 1 offsets into them (device memory) -- they can be passed on to yabpe_normalize,
+ * yabpe_pretokenize or yabpe_encode.  n_bytes == 0 and empty parts are valid.  A text without an ill-formed byte comes back
+ * after one pass as it is: *out_dev_text = text when that is device memory (else its staged copy), the offsets the input's. */
+#define YABPE_UTF8_REPLACE 1u
+#define YABPE_UTF8_IGNORE 2u
+int yabpe_utf8_repair(yabpe_ctx *ctx, const uint8_t *text, uint64_t n_bytes, const uint64_t *part_off, uint32_t n_parts,
+                      uint32_t mode, const uint8_t **out_dev_text, uint64_t **out_dev_part_off, uint64_t *out_n_bytes);
+int yabpe_utf8_repair_free(yabpe_ctx *ctx);
+/* What the last yabpe_utf8_repair saw, and the device time of its passes (HIP events around each pass's launches). */
+typedef struct yabpe_utf8_stats_t {
+    uint64_t n_bytes_in, n_bytes_out, n_parts;
+    uint64_t n_subparts;       /* maximal subparts replaced or dropped (0: the valid path) */
+    int64_t first_bad_pos;     /* byte position of the first one in the input, -1: none */
+    double check_ms;           /* part lookup, charges, tile sums */
+    double write_ms;           /* scan of the tile sums, the text, the part offsets */
+    double total_ms;           /* first to last event, host gaps in between included */
+} yabpe_utf8_stats_t;
+int yabpe_utf8_repair_stats(yabpe_ctx *ctx, yabpe_utf8_stats_t *out);
+
 /* Word pool (corpora larger than device memory) -----------------------------------------------------
  * The word-frequency pooling of trainer.py:221-225 (word_freq[word_tuple] += 1 over all sequences) as a structure that
  * persists across calls: the context keeps the multiset of distinct byte strings seen so far with u64 counts, on the device.

@@ -33,6 +33,7 @@
 #include "yabpe_replay_kernels.h"
 #include "yabpe_pool_kernels.h"
 #include "yabpe_norm_kernels.h"
+#include "yabpe_utf8_kernels.h"
 #include "yabpe_id32_kernels.h"
 #include "unicode_classes.inc"
 #include "unicode_subclasses.inc"
@@ -160,6 +161,10 @@ struct yabpe_ctx {
     std::vector<void *> norm_bufs;
     yabpe_normalize_stats_t norm_stats{};
     hipEvent_t norm_ev[5] = {};
+    // invalid UTF-8 replaced or dropped (yabpe_utf8_repair): the results of the last call
+    std::vector<void *> utf8_bufs;
+    yabpe_utf8_stats_t utf8_stats{};
+    hipEvent_t utf8_ev[3] = {};
     // encoder (yabpe_encode_set_model / yabpe_encode)
     bool have_enc_model = false;
     unsigned long long *enc_keys = nullptr;   // pair table: (a << 32 | b) -> enc_vals (rank, result)
@@ -1321,6 +1326,9 @@ void yabpe_destroy(yabpe_ctx *c) {
     yabpe_normalize_free(c);
     dfree(c->nfc_prop); dfree(c->nfc_decomp); dfree(c->nfc_pairs);
     for (auto &e : c->norm_ev)
+        if (e) (void)hipEventDestroy(e);
+    yabpe_utf8_repair_free(c);
+    for (auto &e : c->utf8_ev)
         if (e) (void)hipEventDestroy(e);
     free_corpus(c);
     id32_free_corpus(c);
@@ -3022,6 +3030,131 @@ int yabpe_normalize(yabpe_ctx *c, const uint8_t *text, uint64_t n_bytes, const u
     c->norm_stats.n_bytes_out = n_out;
     c->norm_bufs.push_back(S.take(out));
     c->norm_bufs.push_back(S.take(out_off));
+    *out_dev_text = out;
+    *out_dev_part_off = (uint64_t *)out_off;
+    *out_n_bytes = n_out;
+    return YABPE_OK;
+}
+
+// ---------------------------------------------------------------------------------------------- invalid UTF-8
+int yabpe_utf8_repair_free(yabpe_ctx *c) {
+    if (!c) return YABPE_E_INVALID;
+    for (void *p : c->utf8_bufs) dfree(p);
+    c->utf8_bufs.clear();
+    return YABPE_OK;
+}
+
+int yabpe_utf8_repair_stats(yabpe_ctx *c, yabpe_utf8_stats_t *out) {
+    if (!c || !out) return YABPE_E_INVALID;
+    *out = c->utf8_stats;
+    return YABPE_OK;
+}
+
+// utf8_ev[0..1] around the check pass, [1..2] the scan and the write pass
+static void utf8_times(yabpe_ctx *c, int last) {
+    float ms[3] = {0, 0, 0};
+    for (int k = 0; k < last; ++k) (void)hipEventElapsedTime(&ms[k], c->utf8_ev[k], c->utf8_ev[k + 1]);
+    (void)hipEventElapsedTime(&ms[2], c->utf8_ev[0], c->utf8_ev[last]);
+    c->utf8_stats.check_ms = ms[0];
+    c->utf8_stats.write_ms = ms[1];
+    c->utf8_stats.total_ms = ms[2];
+}
+
+int yabpe_utf8_repair(yabpe_ctx *c, const uint8_t *text, uint64_t n_bytes, const uint64_t *part_off, uint32_t n_parts, uint32_t mode,
+                      const uint8_t **out_dev_text, uint64_t **out_dev_part_off, uint64_t *out_n_bytes) {
+    if (!c || !out_dev_text || !out_dev_part_off || !out_n_bytes) return YABPE_E_INVALID;
+    HIPCHK(c, hipSetDevice(c->device));
+    *out_dev_text = nullptr; *out_dev_part_off = nullptr; *out_n_bytes = 0;
+    if (mode != YABPE_UTF8_REPLACE && mode != YABPE_UTF8_IGNORE)
+        return fail(c, YABPE_E_INVALID, "utf8 mode %u: YABPE_UTF8_REPLACE (1) or YABPE_UTF8_IGNORE (2)", mode);
+    if (n_bytes && !text) return fail(c, YABPE_E_INVALID, "text is NULL");
+    std::vector<unsigned long long> parts;
+    if (part_off && n_parts) {
+        for (uint32_t k = 0; k < n_parts; ++k) {
+            if (part_off[k] > n_bytes || (k && part_off[k] < part_off[k - 1])) return fail(c, YABPE_E_INVALID, "part offsets must ascend inside the text");
+            parts.push_back(part_off[k]);
+        }
+        if (parts[0] != 0) return fail(c, YABPE_E_INVALID, "the first part must start at 0");
+    } else {
+        parts.push_back(0);
+    }
+    const uint32_t np = (uint32_t)parts.size();
+    parts.push_back(n_bytes);  // (the offsets of the valid path: the input's, with the end)
+    yabpe_utf8_repair_free(c);
+    c->utf8_stats = yabpe_utf8_stats_t{};
+    c->utf8_stats.n_bytes_in = n_bytes;
+    c->utf8_stats.n_parts = np;
+    c->utf8_stats.first_bad_pos = -1;
+    for (auto &e : c->utf8_ev)
+        if (!e) HIPCHK(c, hipEventCreate(&e));
+    hipStream_t s = c->stream;
+    const unsigned long long n = n_bytes;
+    Scratch S(c->device, c->rank);
+    const uint8_t *d_text = nullptr;
+    TRY(to_device(c, S, text, n_bytes, 1, &d_text));
+    unsigned long long *d_parts = nullptr;
+    HIPCHK(c, S.get(&d_parts, parts.size()));
+    HIPCHK(c, hipMemcpyAsync(d_parts, parts.data(), parts.size() * 8, hipMemcpyHostToDevice, s));
+    // the result of the valid path (and of an empty text): the input and its offsets
+    auto hand_out_input = [&]() {
+        if (d_text != text && n) c->utf8_bufs.push_back(S.take(const_cast<uint8_t *>(d_text)));  // (the staged text is handed out)
+        c->utf8_bufs.push_back(S.take(d_parts));
+        *out_dev_text = n ? d_text : nullptr;
+        *out_dev_part_off = (uint64_t *)d_parts;
+        *out_n_bytes = n;
+        c->utf8_stats.n_bytes_out = n;
+    };
+    if (n == 0) {
+        HIPCHK(c, hipStreamSynchronize(s));
+        hand_out_input();
+        return YABPE_OK;
+    }
+    // ---- check: the charge of every byte, per tile the output bytes and the subparts
+    const unsigned long long nt = (n + U8_TILE - 1) / U8_TILE;
+    if (nt > 0x7FFFFFFFull) return fail(c, YABPE_E_CAPACITY, "utf8: %llu bytes are more tiles than one launch takes", n);
+    uint32_t *osum = nullptr, *tbad = nullptr;
+    unsigned long long *ctr = nullptr;  // [0] first ill-formed byte, [1] subparts
+    HIPCHK(c, S.get(&osum, nt));
+    HIPCHK(c, S.get(&tbad, nt));
+    HIPCHK(c, S.get(&ctr, 2));
+    const unsigned long long ctr0[2] = {~0ull, 0};
+    unsigned long long h_ctr[2] = {0, 0};
+    HIPCHK(c, hipEventRecord(c->utf8_ev[0], s));
+    HIPCHK(c, hipMemcpyAsync(ctr, ctr0, sizeof(ctr0), hipMemcpyHostToDevice, s));
+    const U8CheckParams C{d_text, n, d_parts, np, mode, osum, tbad, ctr};
+    hipLaunchKernelGGL(k_u8_check, dim3((uint32_t)nt), dim3(BLOCK), 0, s, C);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipEventRecord(c->utf8_ev[1], s));
+    HIPCHK(c, hipMemcpyAsync(h_ctr, ctr, sizeof(h_ctr), hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipStreamSynchronize(s));
+    c->utf8_stats.n_subparts = h_ctr[1];
+    if (h_ctr[1] == 0) {  // the text is valid UTF-8, part by part
+        utf8_times(c, 1);
+        hand_out_input();
+        return YABPE_OK;
+    }
+    c->utf8_stats.first_bad_pos = (int64_t)h_ctr[0];
+    // ---- write: every tile at its base, the part offsets with it
+    unsigned long long *rbase = nullptr;
+    HIPCHK(c, S.get(&rbase, nt + 1));
+    if (exclusive_scan<uint32_t>(s, osum, nt, rbase, nt + 1) != 0) return fail(c, YABPE_E_HIP, "utf8: scan of the tile sums");
+    unsigned long long n_out = 0;
+    HIPCHK(c, hipMemcpyAsync(&n_out, rbase + nt, 8, hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipStreamSynchronize(s));
+    if (n_out > 3 * n) return fail(c, YABPE_E_INTERNAL, "utf8: %llu bytes out of %llu", n_out, n);
+    uint8_t *out = nullptr;
+    unsigned long long *out_off = nullptr;
+    HIPCHK(c, S.get(&out, n_out));
+    HIPCHK(c, S.get(&out_off, (uint64_t)np + 1));
+    const U8WriteParams W{d_text, n, d_parts, np, mode, rbase, tbad, out, out_off};
+    hipLaunchKernelGGL(k_u8_write, dim3((uint32_t)nt), dim3(BLOCK), 0, s, W);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipEventRecord(c->utf8_ev[2], s));
+    HIPCHK(c, hipStreamSynchronize(s));
+    utf8_times(c, 2);
+    c->utf8_stats.n_bytes_out = n_out;
+    c->utf8_bufs.push_back(S.take(out));
+    c->utf8_bufs.push_back(S.take(out_off));
     *out_dev_text = out;
     *out_dev_part_off = (uint64_t *)out_off;
     *out_n_bytes = n_out;

@@ -41,6 +41,7 @@ class SegmentTooLong(ValueError):
 E_CAPACITY = -4
 E_UTF8 = -7
 NORM_NFC = 1  # yabpe_normalize: form
+UTF8_MODES = {"replace": 1, "ignore": 2}  # yabpe_utf8_repair: mode (YABPE_UTF8_*)
 
 
 class Stats(ctypes.Structure):
@@ -108,6 +109,11 @@ class NormalizeStats(ctypes.Structure):
         (n, c_double) for n in ("class_ms", "find_ms", "segments_ms", "write_ms", "total_ms")]
 
 
+class Utf8Stats(ctypes.Structure):
+    _fields_ = [(n, c_uint64) for n in ("n_bytes_in", "n_bytes_out", "n_parts", "n_subparts")] + [("first_bad_pos", c_int64)] + [
+        (n, c_double) for n in ("check_ms", "write_ms", "total_ms")]
+
+
 class Latency(ctypes.Structure):
     _fields_ = [(n, c_double) for n in ("launch_gap_us", "load_trip_us", "coherent_trip_us", "atomic_trip_us")]
 
@@ -129,6 +135,7 @@ SYMBOLS = [
     "yabpe_layout_pad", "yabpe_layout_pack", "yabpe_layout_windows", "yabpe_layout_pairs", "yabpe_layout_free", "yabpe_layout_stats",
     "yabpe_pool_add", "yabpe_pool_get", "yabpe_pool_clear", "yabpe_pool_stats",
     "yabpe_normalize", "yabpe_normalize_free", "yabpe_normalize_stats",
+    "yabpe_utf8_repair", "yabpe_utf8_repair_free", "yabpe_utf8_repair_stats",
 ]
 
 
@@ -206,6 +213,10 @@ def lib() -> ctypes.CDLL:
                                       POINTER(c_uint64), POINTER(ctypes.c_int64)]
         L.yabpe_normalize_free.argtypes = [c_void_p]
         L.yabpe_normalize_stats.argtypes = [c_void_p, POINTER(NormalizeStats)]
+        L.yabpe_utf8_repair.argtypes = [c_void_p, c_void_p, c_uint64, c_void_p, c_uint32, c_uint32, POINTER(c_void_p), POINTER(c_void_p),
+                                        POINTER(c_uint64)]
+        L.yabpe_utf8_repair_free.argtypes = [c_void_p]
+        L.yabpe_utf8_repair_stats.argtypes = [c_void_p, POINTER(Utf8Stats)]
         if L.yabpe_abi_version() != 2:
             raise ImportError("libyabpe.so ABI version mismatch")
         _lib = L
@@ -470,6 +481,38 @@ class Context:
         s = NormalizeStats()
         self._chk(lib().yabpe_normalize_stats(self._h, byref(s)))
         return {f: getattr(s, f) for f, _ in NormalizeStats._fields_}
+
+    # -- errors="replace" / "ignore" in front of normalize() / pretokenize() / encode() (include/yabpe.h: yabpe_utf8_repair)
+    def utf8_repair(self, text, n_bytes: int | None = None, part_starts=None, mode: int = UTF8_MODES["replace"]):
+        """part.decode("utf-8", errors).encode() of every part of `text` on the device.  `text`: bytes / u8 array (staged) or a
+        device address (then n_bytes is required).  part_starts: ascending part starts, the first one 0 (None: one part); a
+        sequence cut off by a part's end is ill-formed there.  mode: UTF8_MODES["replace"] or ["ignore"].
+        -> (dev_text_ptr, dev_part_off_ptr u64[n_parts + 1], n_bytes_out); the buffers live until the next utf8_repair,
+        utf8_repair_free() or close().  A text that is valid comes back as it is (a device address: the same address)."""
+        keep = None
+        if isinstance(text, int):
+            ptr, n = c_void_p(text), int(n_bytes)
+        else:
+            keep = np.frombuffer(text, dtype=np.uint8) if not isinstance(text, np.ndarray) else np.ascontiguousarray(text, dtype=np.uint8)
+            ptr, n = c_void_p(keep.ctypes.data if keep.size else 0), int(keep.size)
+        st = np.ascontiguousarray(part_starts if part_starts is not None and len(part_starts) else [0], dtype=np.uint64)
+        dt, do, nb = c_void_p(), c_void_p(), c_uint64(0)
+        self._chk(lib().yabpe_utf8_repair(self._h, ptr, n, st.ctypes.data, len(st), int(mode), byref(dt), byref(do), byref(nb)))
+        return dt.value or 0, do.value, nb.value
+
+    def utf8_repair_to_host(self, text, n_bytes: int | None = None, part_starts=None, mode: int = UTF8_MODES["replace"]):
+        """-> (text u8[n_bytes_out], part_off u64[n_parts + 1]) copied to the host."""
+        n_parts = len(part_starts) if part_starts is not None and len(part_starts) else 1
+        dt, do, nb = self.utf8_repair(text, n_bytes, part_starts, mode)
+        return (self.d2h(dt, nb) if nb else np.zeros(0, np.uint8)), self.d2h(do, 8 * (n_parts + 1), np.uint64)
+
+    def utf8_repair_free(self) -> None:
+        self._chk(lib().yabpe_utf8_repair_free(self._h))
+
+    def utf8_repair_stats(self) -> dict:
+        s = Utf8Stats()
+        self._chk(lib().yabpe_utf8_repair_stats(self._h, byref(s)))
+        return {f: getattr(s, f) for f, _ in Utf8Stats._fields_}
 
     # -- encoding with a trained model (BBPETokenizer.encode on the device)
     def encode_set_model(self, vocab: dict, merges, specials_ordered, unk_id: int) -> None:

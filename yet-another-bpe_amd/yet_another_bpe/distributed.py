@@ -149,14 +149,28 @@ def plan_chunk_shards(sizes: Sequence[int], world: int) -> list[tuple[int, int]]
 
 
 def _pretokenize_my_chunks(ctx, text, n_bytes, starts, config):
-    """This rank's chunks -> (device text, device word offsets, n_words): with config.normalizer yabpe_normalize runs in front of
-    yabpe_pretokenize (chunk by chunk; the normalised text stays the context's), as BBPETrainer._device_words does it."""
-    from .trainer import check_normalizer
+    """This rank's chunks -> (device text, device word offsets, n_words): with config.errors = "replace" / "ignore"
+    yabpe_utf8_repair, then with config.normalizer yabpe_normalize run in front of
+    yabpe_pretokenize (chunk by chunk; their texts stay the context's), as BBPETrainer._device_words does it.  A
+    _native.SegmentTooLong raised after a repair carries .repaired_starts (the chunks' starts in the repaired text)."""
+    from . import _native
+    from .trainer import check_errors, check_normalizer
 
     form = check_normalizer(getattr(config, "normalizer", None))
-    if form:
-        text, dev_starts, n_bytes = ctx.normalize(text, n_bytes=n_bytes, part_starts=starts, form=form)
-        starts = ctx.d2h(dev_starts, 8 * len(starts), np.uint64)
+    repair = check_errors(getattr(config, "errors", "strict"))
+    n_chunks = len(starts)
+    if repair:
+        text, dev_starts, n_bytes = ctx.utf8_repair(text, n_bytes=n_bytes, part_starts=starts, mode=repair)
+        starts = ctx.d2h(dev_starts, 8 * n_chunks, np.uint64)
+    if form and (n_bytes is None or n_bytes):
+        try:
+            text, dev_starts, n_bytes = ctx.normalize(text, n_bytes=n_bytes, part_starts=starts, form=form)
+        except _native.SegmentTooLong as e:
+            e.repaired_starts = starts if repair else None
+            raise
+        starts = ctx.d2h(dev_starts, 8 * n_chunks, np.uint64)
+    if n_bytes == 0:  # (every byte was dropped: no words)
+        text, n_bytes = np.zeros(0, np.uint8), None
     return ctx.pretokenize(text, n_bytes=n_bytes, chunk_starts=starts, special_tokens=list(config.special_tokens))
 
 
@@ -177,7 +191,8 @@ def train_text_sharded(ctx_factory, files, config, rank: int, world: int, transp
     from pathlib import Path
 
     from . import _native
-    from .trainer import BBPETrainer, check_files, check_sharded_budget, device_options, read_chunks, segment_error, utf8_error
+    from .trainer import (BBPETrainer, check_files, check_sharded_budget, device_options, read_chunks, repaired_segment_error, segment_error,
+                          utf8_error)
 
     device_options(config)  # (ValueError before any file is read)
     check_sharded_budget(config.vocab_size)
@@ -201,7 +216,8 @@ def train_text_sharded(ctx_factory, files, config, rank: int, world: int, transp
             except _native.Utf8Error as e:
                 err = (rank, str(utf8_error(chunks[c0:c1], starts, e)))  # (the chunks go to the ranks in order)
             except _native.SegmentTooLong as e:
-                err = (rank, str(segment_error(chunks[c0:c1], starts, e)))
+                moved = getattr(e, "repaired_starts", None)
+                err = (rank, str(segment_error(chunks[c0:c1], starts, e) if moved is None else repaired_segment_error(chunks[c0:c1], moved, e)))
         if world > 1:  # every rank must learn about the first bad chunk anywhere, or the others would wait in the merge loop
             import torch.distributed as dist
 

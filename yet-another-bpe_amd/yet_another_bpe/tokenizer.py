@@ -25,8 +25,8 @@ import numpy as np
 import regex
 
 from .synth import rnd_int
-from .trainer import (CL100K_DIGIT_GROUP, NORMALIZERS, PRETOKENIZER_NAMES, BBPETrainerConfig, check_digit_group, check_normalized_specials,
-                      check_normalizer, check_pretokenizer, device_options, normalize_text, read_normalizer, read_pretokenizer, split_pattern)
+from .trainer import (CL100K_DIGIT_GROUP, NORMALIZERS, PRETOKENIZER_NAMES, BBPETrainerConfig, check_digit_group, check_errors,
+                      check_normalized_specials, check_normalizer, check_pretokenizer, device_options, normalize_text, read_normalizer, read_pretokenizer, split_pattern)
 
 _WORD_CACHE = 8192
 
@@ -597,39 +597,50 @@ class BBPETokenizer:
         starts[1:] = np.cumsum([len(b) for b in blobs], dtype=np.uint64)[:-1]
         return b"".join(blobs), starts
 
-    def _device_text(self, ctx, inp):
+    def _device_text(self, ctx, inp, errors: str = "strict"):
         """What the encode calls of ctx take as (text, n_bytes, doc_starts) for _device_input's buffer: the buffer itself, or with
-        a normaliser the normalised text in device memory (yabpe_normalize; the context's until its next normalize) and the
-        documents' starts in it."""
-        text = np.frombuffer(inp[0], dtype=np.uint8)
-        form = check_normalizer(self._normalizer)
-        if not form or not text.size:
-            return text, None, inp[1]
-        dev_text, dev_starts, n_bytes = ctx.normalize(text, part_starts=inp[1], form=form)
-        starts = ctx.d2h(dev_starts, 8 * len(inp[1]), np.uint64)
-        return (dev_text, n_bytes, starts) if n_bytes else (np.zeros(0, np.uint8), None, starts)
+        errors = "replace" / "ignore" the repaired text (yabpe_utf8_repair; the context's until its next repair), or with a
+        normaliser the normalised text made from either (yabpe_normalize; the context's until its next normalize), in device
+        memory, and the documents' starts in it."""
+        text, n_bytes, starts = np.frombuffer(inp[0], dtype=np.uint8), None, inp[1]
+        repair, form = check_errors(errors), check_normalizer(self._normalizer)
+        if repair and text.size:
+            text, dev_starts, n_bytes = ctx.utf8_repair(text, part_starts=starts, mode=repair)
+            starts = ctx.d2h(dev_starts, 8 * len(inp[1]), np.uint64)
+        if form and (text.size if n_bytes is None else n_bytes):
+            text, dev_starts, n_bytes = ctx.normalize(text, n_bytes=n_bytes, part_starts=starts, form=form)
+            starts = ctx.d2h(dev_starts, 8 * len(inp[1]), np.uint64)
+        return (np.zeros(0, np.uint8), None, starts) if n_bytes == 0 else (text, n_bytes, starts)
 
-    def normalize_array(self, texts) -> tuple[np.ndarray, np.ndarray]:
+    def normalize_array(self, texts, *, errors: str = "strict") -> tuple[np.ndarray, np.ndarray]:
         """normalize() of every document on the GPU: `texts` as encode_array takes them -> (text np.uint8[n], text_off
         np.uint64[n_docs + 1]): text[text_off[d]:text_off[d + 1]] is normalize(texts[d]) as UTF-8 -- the documents the spans of
-        encode_array_with_offsets refer to.  Without a normaliser the documents come back as they are."""
+        encode_array_with_offsets refer to.  Without a normaliser the documents come back as they are.  errors: as encode_array
+        takes it -- the document is then normalize(data.decode("utf-8", errors)), the repaired and then normalised one."""
         inp = self._device_input(texts)
         if inp is None:
             return np.zeros(0, np.uint8), np.zeros(1, np.uint64)
-        form = check_normalizer(self._normalizer)
-        if not form:
+        repair, form = check_errors(errors), check_normalizer(self._normalizer)
+        if not form and not repair:
             return np.frombuffer(inp[0], dtype=np.uint8).copy(), np.append(np.asarray(inp[1], dtype=np.uint64), np.uint64(len(inp[0])))
-        return self._device().normalize_to_host(np.frombuffer(inp[0], dtype=np.uint8), part_starts=inp[1], form=form)
+        ctx = self._device()
+        text, n_bytes, starts = self._device_text(ctx, inp, errors)
+        if n_bytes is None:  # (nothing to do on the device, or nothing left)
+            return np.ascontiguousarray(text).copy(), np.append(np.asarray(starts, dtype=np.uint64), np.uint64(len(text)))
+        return ctx.d2h(text, n_bytes), np.append(np.asarray(starts, dtype=np.uint64), np.uint64(n_bytes))
 
-    def encode_array(self, texts) -> tuple[np.ndarray, np.ndarray]:
+    def encode_array(self, texts, *, errors: str = "strict") -> tuple[np.ndarray, np.ndarray]:
         """Encodes on the GPU: `texts` is a sequence of str (one document each) or one bytes buffer (one document).
         -> (ids np.uint32[n], doc_off np.uint64[n_docs + 1]): document d's ids are ids[doc_off[d]:doc_off[d + 1]], equal to
-        encode(texts[d]).  Malformed UTF-8 in a bytes buffer raises _native.Utf8Error (.position = UnicodeDecodeError.start)."""
+        encode(texts[d]).  Malformed UTF-8 in a bytes buffer raises _native.Utf8Error (.position = UnicodeDecodeError.start)
+        under errors = "strict"; with "replace" or "ignore" the result is encode(data.decode("utf-8", errors)), repaired on the
+        GPU (a str cannot hold ill-formed UTF-8, so the option only matters for a bytes buffer)."""
         inp = self._device_input(texts)
         if inp is None:
+            check_errors(errors)
             return np.zeros(0, np.uint32), np.zeros(1, np.uint64)
         ctx = self._device()
-        text, n_bytes, starts = self._device_text(ctx, inp)
+        text, n_bytes, starts = self._device_text(ctx, inp, errors)
         return ctx.encode_to_host(text, n_bytes, doc_starts=starts)
 
     def encode_batch_device(self, texts: Sequence[str]) -> list[list[int]]:
@@ -638,17 +649,19 @@ class BBPETokenizer:
         ids, off = ids.tolist(), off.tolist()
         return [ids[off[d]:off[d + 1]] for d in range(len(off) - 1)]
 
-    def encode_array_with_offsets(self, texts, unit: str = "char") -> tuple[np.ndarray, np.ndarray, np.ndarray]:
+    def encode_array_with_offsets(self, texts, unit: str = "char", *, errors: str = "strict") -> tuple[np.ndarray, np.ndarray, np.ndarray]:
         """encode_array(texts) plus every id's span, computed on the GPU in the same call.
         -> (ids np.uint32[n], doc_off np.uint64[n_docs + 1], offsets np.uint64[n, 2]): offsets[k] = (start, end) of id k in its
-        own document, as encode_with_offsets(texts[d], unit) gives them."""
+        own document, as encode_with_offsets(texts[d], unit) gives them.  errors: as encode_array takes it; the spans refer to
+        the repaired, then normalised document, which normalize_array(texts, errors=errors) returns."""
         if unit not in ("char", "byte"):
             raise ValueError(f"unit must be 'char' or 'byte', not {unit!r}")
         inp = self._device_input(texts)
         if inp is None:
+            check_errors(errors)
             return np.zeros(0, np.uint32), np.zeros(1, np.uint64), np.zeros((0, 2), np.uint64)
         ctx = self._device()
-        text, n_bytes, starts = self._device_text(ctx, inp)
+        text, n_bytes, starts = self._device_text(ctx, inp, errors)
         return ctx.encode_spans_to_host(text, n_bytes, doc_starts=starts, chars=unit == "char")
 
     def encode_batch_device_with_offsets(self, texts: Sequence[str], unit: str = "char"):

@@ -24,8 +24,10 @@ BBPETokenizer's device context take theirs from it too.
 """
 from __future__ import annotations
 
+import codecs
 import json
 import os
+import threading
 import unicodedata
 from collections import Counter
 from collections.abc import Mapping, Sequence
@@ -97,6 +99,39 @@ def check_normalizer(name) -> int:
     if not isinstance(name, str) or name != "nfc":
         raise ValueError(f"normalizer must be one of {NORMALIZERS!r}, got {name!r}")
     return 1
+
+
+ERRORS = ("strict", "replace", "ignore")  # BBPETrainerConfig.errors; the index is the mode of the library's yabpe_utf8_repair
+
+
+def check_errors(name) -> int:
+    """An errors= name as the mode argument of the library's yabpe_utf8_repair (0: "strict", no repair; 1: "replace";
+    2: "ignore").  ValueError for anything else."""
+    if not isinstance(name, str) or name not in ERRORS:
+        raise ValueError(f"errors must be one of {ERRORS!r}, got {name!r}")
+    return ERRORS.index(name)
+
+
+_DECODE_COUNT = threading.local()
+
+
+def _counting_handler(replacement: str):
+    def handler(e):
+        _DECODE_COUNT.n = getattr(_DECODE_COUNT, "n", 0) + 1
+        return replacement, e.end
+    return handler
+
+
+# bytes.decode's "replace" and "ignore" handlers, counting their calls (one per maximal subpart) per thread
+codecs.register_error("yabpe_replace", _counting_handler("\ufffd"))
+codecs.register_error("yabpe_ignore", _counting_handler(""))
+
+
+def decode_counting(raw: bytes, errors: str) -> tuple[str, int]:
+    """raw.decode("utf-8", errors) for errors = "replace" or "ignore", and the number of subparts replaced or dropped."""
+    _DECODE_COUNT.n = 0
+    text = raw.decode("utf-8", errors="yabpe_" + errors)
+    return text, _DECODE_COUNT.n
 
 
 def check_normalized_specials(tokens: Sequence[str], name) -> None:
@@ -178,6 +213,13 @@ class BBPETrainerConfig:
             matched in the normalised text: a special token that is not NFC itself is a ValueError, and "<|endoftext|>"
             followed by U+0338 normalises to "<|endoftext|" + U+226F and is then no special.  A run of more than 16,384
             code points that normalise together (a base with its combining marks) is a ValueError that names the file.
+        errors: "strict" (the reference: an invalid byte is a ValueError that names the file and the position), or "replace" /
+            "ignore" as bytes.decode and open() take them: every chunk _chunk_ranges cuts is replaced by
+            chunk.decode("utf-8", errors).encode() before the normaliser, the special tokens and the split pattern see it (on
+            the device: yabpe_utf8_repair in front of yabpe_normalize / yabpe_pretokenize).  Chunks are repaired
+            independently: a sequence cut off by a chunk's end is ill-formed there.  A property of how the files are read,
+            NOT of the model: not stored by save / save_lossless, not carried by BBPEModel, not compared by train_from.
+            BBPETrainer.utf8_replaced holds the number of subparts replaced or dropped by the last call.
     """
 
     vocab_size: int = 32000
@@ -190,6 +232,7 @@ class BBPETrainerConfig:
     digit_group: int | None = None
     pretokenizer: str = "gpt2"
     normalizer: str | None = None
+    errors: str = "strict"
 
 
 U16_TOKENS = 65_534  # tokens the u16 merge loop holds (ids 0 .. 65,533)
@@ -360,6 +403,7 @@ def device_options(config: BBPETrainerConfig) -> dict[str, int]:
     and the split pattern by every pre-tokenisation or encode call, so they go in right after the context is made."""
     limit = max_token_bytes(config)
     pattern, group = pretokenizer(config)
+    check_errors(getattr(config, "errors", "strict"))
     return {k: v for k, v in (("max_token_bytes", limit), ("digit_group", group), ("split_pattern", pattern)) if v}
 
 
@@ -400,6 +444,15 @@ def segment_error(chunks: Sequence[tuple[Path, int, int]], starts: Sequence[int]
                       f"{start + e.position - starts[k]}: {e}")
 
 
+def repaired_segment_error(chunks: Sequence[tuple[Path, int, int]], starts: Sequence[int], e) -> ValueError:
+    """The same after errors="replace" / "ignore": e's position is one in the REPAIRED text (`starts`: the chunks' starts in it),
+    which no longer maps to a file position -- the file, the chunk's byte range and the position inside the repaired chunk."""
+    k = max(i for i, s0 in enumerate(starts) if s0 <= e.position)
+    path, start, stop = chunks[k]
+    return ValueError(f"File {path} holds a run of code points that normalise together over the normaliser's cap in the chunk of bytes "
+                      f"{start} to {stop}, at position {e.position - int(starts[k])} of that chunk after its invalid UTF-8 was repaired: {e}")
+
+
 class BBPETrainer:
     """Byte-level BPE trainer with the reference's API; the merge loop runs on the GPU."""
 
@@ -408,6 +461,7 @@ class BBPETrainer:
         self._vocab: dict[bytes, int] = {}
         self._merges: list[tuple[bytes, bytes]] = []
         self.last_stats: dict | None = None  # yabpe_stats of the last merge loop (not in the reference)
+        self.utf8_replaced: int = 0  # subparts of invalid UTF-8 replaced or dropped by the last train / train_from (0 under "strict")
 
     def _context(self):
         """A device context for this trainer's configuration."""
@@ -468,7 +522,7 @@ class BBPETrainer:
         old_merges = [(bytes(l), bytes(r)) for l, r in model.merges]
         check_files(paths)
         if self._budget(old_merges) == 0:  # nothing to learn: no file is read, whatever batch_bytes says
-            self._vocab, self._merges = dict(model.vocab), old_merges
+            self._vocab, self._merges, self.utf8_replaced = dict(model.vocab), old_merges, 0
             return self._model(self._vocab, self._merges)
         return self._train(paths, batch_bytes, toks, triples, old_merges, dict(model.vocab))
 
@@ -485,6 +539,7 @@ class BBPETrainer:
         occurrence resident, no pooling) applies to a fresh model only: a continued one always pools."""
         flat = triples is None and os.environ.get("YABPE_LAYOUT", "dedup") == "flat"
         mode = os.environ.get("YABPE_PRETOKENIZE", "auto")
+        self.utf8_replaced = 0
         batch = self._batch_bytes(batch_bytes)
         if batch is not None and flat:
             raise ValueError("batch_bytes needs the pooled layout: YABPE_LAYOUT=flat keeps every occurrence resident")
@@ -525,7 +580,8 @@ class BBPETrainer:
         return int(batch_bytes)
 
     def _device_words(self, ctx, chunks: Sequence[tuple[Path, int, int]], batch_bytes: int | None, dedup: bool):
-        """The chunks' pre-tokens as device words for _run: file bytes -> (with a normaliser: yabpe_normalize, chunk by chunk
+        """The chunks' pre-tokens as device words for _run: file bytes -> (with errors = "replace" / "ignore": yabpe_utf8_repair,
+        chunk by chunk -> the repaired text and the chunk starts in it ->) (with a normaliser: yabpe_normalize, chunk by chunk
         -> the normalised text and the chunk starts in it ->) yabpe_pretokenize -> word offsets in HBM (equal
         pre-tokens are pooled by the load when `dedup`).  With `batch_bytes` the chunks are read batch by batch (one batch on
         the host at a time) and each batch's pre-tokens added to ctx's word pool (yabpe_pool_add); the words are then the
@@ -534,20 +590,29 @@ class BBPETrainer:
         from . import _native
 
         form = check_normalizer(getattr(self.config, "normalizer", None))
+        repair = check_errors(getattr(self.config, "errors", "strict"))
 
         def pretokenize(part):
             buf, starts = read_chunks(part)
+            text, n_bytes, cur = buf, None, starts  # what the next step reads: host buffer, or device address and length
             try:
-                if not form:
-                    return ctx.pretokenize(buf, chunk_starts=starts, special_tokens=list(self.config.special_tokens))
-                # the normalised text stays the context's until normalize_free (the words are offsets into it)
-                dev_text, dev_starts, n_bytes = ctx.normalize(buf, part_starts=starts, form=form)
-                new_starts = ctx.d2h(dev_starts, 8 * len(starts), np.uint64)
-                return ctx.pretokenize(dev_text, n_bytes=n_bytes, chunk_starts=new_starts, special_tokens=list(self.config.special_tokens))
+                if repair:
+                    # the repaired text stays the context's until utf8_repair_free (the words are offsets into it, or into
+                    # the normalised text made from it)
+                    text, dev_starts, n_bytes = ctx.utf8_repair(buf, part_starts=starts, mode=repair)
+                    cur = ctx.d2h(dev_starts, 8 * len(starts), np.uint64)
+                    self.utf8_replaced += int(ctx.utf8_repair_stats()["n_subparts"])
+                if form and (n_bytes is None or n_bytes):
+                    # the normalised text stays the context's until normalize_free (the words are offsets into it)
+                    text, dev_starts, n_bytes = ctx.normalize(text, n_bytes=n_bytes, part_starts=cur, form=form)
+                    cur = ctx.d2h(dev_starts, 8 * len(starts), np.uint64)
+                if n_bytes == 0:  # (every byte was dropped: no words)
+                    text, n_bytes = np.zeros(0, np.uint8), None
+                return ctx.pretokenize(text, n_bytes=n_bytes, chunk_starts=cur, special_tokens=list(self.config.special_tokens))
             except _native.Utf8Error as e:  # (positions in buf: the normaliser validates the text it is given)
                 raise utf8_error(part, starts, e) from e
             except _native.SegmentTooLong as e:
-                raise segment_error(part, starts, e) from e
+                raise (repaired_segment_error(part, cur, e) if repair else segment_error(part, starts, e)) from e
 
         if batch_bytes is None:
             return (*pretokenize(chunks), 0, dedup)
@@ -556,6 +621,8 @@ class BBPETrainer:
             ctx.pretokenize_free()
             if form:
                 ctx.normalize_free()
+            if repair:
+                ctx.utf8_repair_free()
         dev_bytes, dev_off, dev_freq, n_unique, _n_bytes = ctx.pool_get()
         return dev_bytes, dev_off, n_unique, dev_freq, False
 
@@ -769,13 +836,19 @@ class BBPETrainer:
     def _pretokenize(self, files: Sequence[Path]) -> list[str]:
         """All non-empty pre-tokens as strings, in file / chunk order."""
         pattern = self._split_pattern()
+        errors = ERRORS[check_errors(getattr(self.config, "errors", "strict"))]
+        replaced: list[int] = []  # per chunk (list.append is atomic)
 
         def run(path: Path, start: int, stop: int) -> list[str]:
             with open(path, "rb") as f:
                 f.seek(start)
                 raw = f.read(stop - start)
             try:
-                text = raw.decode("utf-8")
+                if errors == "strict":
+                    text = raw.decode("utf-8")
+                else:
+                    text, n = decode_counting(raw, errors)
+                    replaced.append(n)
             except UnicodeDecodeError as e:
                 raise ValueError(f"File {path} contains invalid UTF-8 at position {start + e.start}.") from e
             return [t for t in pattern.findall(normalize_text(text, getattr(self.config, "normalizer", None))) if t]
@@ -789,6 +862,7 @@ class BBPETrainer:
                     jobs.append(pool.submit(run, path, start, stop))
             for job in jobs:  # submission order => deterministic output order (trainer.py:209)
                 out.extend(job.result())
+        self.utf8_replaced = sum(replaced)
         return out
 
     def _preprocess_corpus(self, files: Sequence[Path]) -> list[list[int]]:
