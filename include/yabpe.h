@@ -364,6 +364,43 @@ typedef struct yabpe_utf8_stats_t {
 } yabpe_utf8_stats_t;
 int yabpe_utf8_repair_stats(yabpe_ctx *ctx, yabpe_utf8_stats_t *out);
 
+/* Lower-case text (the step between the repair and the normaliser) -----------------------------------
+ * str.lower() on the device: every part [part_off[k], part_off[k+1]) of `text` (read as yabpe_normalize reads them: n_parts
+ * ascending starts, the first one 0, the last part ends at n_bytes; part_off == NULL: one part) is replaced by part.lower()
+ * of CPython, Unicode version as csrc/unicode_case.inc says (generated by tools/gen_unicode_case.py from the installed
+ * interpreter).  Parts are lowered independently: the final-sigma rule -- the one rule of str.lower() that looks at the
+ * neighbours -- never looks across a part boundary (csrc/case_logic.h).
+ * text may be host or device memory.  Results (owned by the library, valid until yabpe_lowercase_free, the next
+ * yabpe_lowercase or yabpe_destroy): *out_dev_text = *out_n_bytes bytes in device memory (at most 1.5 x n_bytes, possibly 0),
+ * *out_dev_part_off = n_parts + 1 offsets into them (device memory) -- they can be passed on to yabpe_normalize,
+ * yabpe_pretokenize or yabpe_encode.  n_bytes == 0 and empty parts are valid.  One pass counts what changes; then
+ *   path 0  nothing does: *out_dev_text = text when that is 16-byte aligned device memory (else its staged copy), the offsets
+ *           the input's;
+ *   path 1  no code point changes its UTF-8 length and there is no capital sigma: one pass of the same size, the offsets the
+ *           input's;
+ *   path 2  otherwise: two scans for the final sigmas, a scan of the window sizes, a shifted write.
+ * No path has a cap, and none is more than linear in n_bytes whatever the text holds.
+ * Malformed UTF-8: YABPE_E_UTF8 and *out_bad_pos = UnicodeDecodeError.start of the first bad part, as yabpe_pretokenize
+ * reports it (a part cut inside a sequence is malformed on both sides). */
+int yabpe_lowercase(yabpe_ctx *ctx, const uint8_t *text, uint64_t n_bytes, const uint64_t *part_off, uint32_t n_parts,
+                    const uint8_t **out_dev_text, uint64_t **out_dev_part_off, uint64_t *out_n_bytes, int64_t *out_bad_pos);
+int yabpe_lowercase_free(yabpe_ctx *ctx);
+/* What the last yabpe_lowercase saw, and the device time of its phases (HIP events around each phase's launches). */
+typedef struct yabpe_lowercase_stats_t {
+    uint64_t n_bytes_in, n_bytes_out, n_parts;
+    uint64_t n_changed;        /* code points that change (0: path 0) */
+    uint64_t n_resized;        /* ... of them whose UTF-8 length changes */
+    uint64_t n_sigma;          /* capital sigmas */
+    uint64_t n_final_sigma;    /* ... of them that became final sigmas */
+    uint64_t path;             /* 0 same pointer, 1 same size, 2 general */
+    uint64_t n_copied;         /* bytes a write pass stored (0 on path 0) */
+    double check_ms;           /* part marks, UTF-8 check, counters, window sizes */
+    double scan_ms;            /* path 2: the two final-sigma scans, the scan of the window sizes */
+    double write_ms;           /* path 1: the same-size pass; path 2: the shifted write and the part offsets */
+    double total_ms;           /* first to last event, host gaps in between included */
+} yabpe_lowercase_stats_t;
+int yabpe_lowercase_stats(yabpe_ctx *ctx, yabpe_lowercase_stats_t *out);
+
 /* Word pool (corpora larger than device memory) -----------------------------------------------------
  * The word-frequency pooling of trainer.py:221-225 (word_freq[word_tuple] += 1 over all sequences) as a structure that
  * persists across calls: the context keeps the multiset of distinct byte strings seen so far with u64 counts, on the device.

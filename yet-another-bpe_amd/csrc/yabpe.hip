@@ -34,10 +34,12 @@
 #include "yabpe_pool_kernels.h"
 #include "yabpe_norm_kernels.h"
 #include "yabpe_utf8_kernels.h"
+#include "yabpe_case_kernels.h"
 #include "yabpe_id32_kernels.h"
 #include "unicode_classes.inc"
 #include "unicode_subclasses.inc"
 #include "unicode_norm.inc"
+#include "unicode_case.inc"
 
 using namespace yb;
 
@@ -165,6 +167,11 @@ struct yabpe_ctx {
     std::vector<void *> utf8_bufs;
     yabpe_utf8_stats_t utf8_stats{};
     hipEvent_t utf8_ev[3] = {};
+    // lower-casing (yabpe_lowercase): the table of unicode_case.inc, built on first use, and the results of the last call
+    uint32_t *case_tab = nullptr;
+    std::vector<void *> case_bufs;
+    yabpe_lowercase_stats_t case_stats{};
+    hipEvent_t case_ev[4] = {};
     // encoder (yabpe_encode_set_model / yabpe_encode)
     bool have_enc_model = false;
     unsigned long long *enc_keys = nullptr;   // pair table: (a << 32 | b) -> enc_vals (rank, result)
@@ -1329,6 +1336,10 @@ void yabpe_destroy(yabpe_ctx *c) {
         if (e) (void)hipEventDestroy(e);
     yabpe_utf8_repair_free(c);
     for (auto &e : c->utf8_ev)
+        if (e) (void)hipEventDestroy(e);
+    yabpe_lowercase_free(c);
+    dfree(c->case_tab);
+    for (auto &e : c->case_ev)
         if (e) (void)hipEventDestroy(e);
     free_corpus(c);
     id32_free_corpus(c);
@@ -3155,6 +3166,190 @@ int yabpe_utf8_repair(yabpe_ctx *c, const uint8_t *text, uint64_t n_bytes, const
     c->utf8_stats.n_bytes_out = n_out;
     c->utf8_bufs.push_back(S.take(out));
     c->utf8_bufs.push_back(S.take(out_off));
+    *out_dev_text = out;
+    *out_dev_part_off = (uint64_t *)out_off;
+    *out_n_bytes = n_out;
+    return YABPE_OK;
+}
+
+// ---------------------------------------------------------------------------------------------- lower-casing
+// the table of unicode_case.inc on the device (one entry per code point, case_logic.h), built on first use
+static int case_tables(yabpe_ctx *c, CaseTables *T) {
+    if (!c->case_tab) {
+        std::vector<uint32_t> tab(CASE_NCP);
+        if (!case_expand(tab.data(), YB_CASE_LOWER, YB_CASE_NLOWER, YB_CASE_TWO, YB_CASE_CASED, YB_CASE_NCASED, YB_CASE_IGNORABLE, YB_CASE_NIGNORABLE))
+            return fail(c, YABPE_E_INTERNAL, "unicode_case.inc: the code point that lowers to two, or the sigma, is not what case_logic.h names");
+        uint32_t *d_tab = nullptr;
+        Scratch S(c->device, c->rank);
+        HIPCHK(c, S.get(&d_tab, tab.size()));
+        HIPCHK(c, hipMemcpy(d_tab, tab.data(), tab.size() * 4, hipMemcpyHostToDevice));
+        c->case_tab = S.take(d_tab);
+    }
+    *T = CaseTables{c->case_tab};
+    return 0;
+}
+
+int yabpe_lowercase_free(yabpe_ctx *c) {
+    if (!c) return YABPE_E_INVALID;
+    for (void *p : c->case_bufs) dfree(p);
+    c->case_bufs.clear();
+    return YABPE_OK;
+}
+
+int yabpe_lowercase_stats(yabpe_ctx *c, yabpe_lowercase_stats_t *out) {
+    if (!c || !out) return YABPE_E_INVALID;
+    *out = c->case_stats;
+    return YABPE_OK;
+}
+
+// case_ev[0..1] around the check pass, [1..2] the scans, [2..3] the write pass (path 1: [1..2] the write pass)
+static void lowercase_times(yabpe_ctx *c, int last) {
+    float ms[4] = {0, 0, 0, 0};
+    for (int k = 0; k < last; ++k) (void)hipEventElapsedTime(&ms[k], c->case_ev[k], c->case_ev[k + 1]);
+    (void)hipEventElapsedTime(&ms[3], c->case_ev[0], c->case_ev[last]);
+    c->case_stats.check_ms = ms[0];
+    c->case_stats.scan_ms = last == 3 ? ms[1] : 0.0;
+    c->case_stats.write_ms = last == 3 ? ms[2] : ms[1];
+    c->case_stats.total_ms = ms[3];
+}
+
+int yabpe_lowercase(yabpe_ctx *c, const uint8_t *text, uint64_t n_bytes, const uint64_t *part_off, uint32_t n_parts,
+                    const uint8_t **out_dev_text, uint64_t **out_dev_part_off, uint64_t *out_n_bytes, int64_t *out_bad_pos) {
+    if (!c || !out_dev_text || !out_dev_part_off || !out_n_bytes || !out_bad_pos) return YABPE_E_INVALID;
+    HIPCHK(c, hipSetDevice(c->device));
+    *out_dev_text = nullptr; *out_dev_part_off = nullptr; *out_n_bytes = 0; *out_bad_pos = -1;
+    if (n_bytes && !text) return fail(c, YABPE_E_INVALID, "text is NULL");
+    std::vector<unsigned long long> parts;
+    if (part_off && n_parts) {
+        for (uint32_t k = 0; k < n_parts; ++k) {
+            if (part_off[k] > n_bytes || (k && part_off[k] < part_off[k - 1])) return fail(c, YABPE_E_INVALID, "part offsets must ascend inside the text");
+            parts.push_back(part_off[k]);
+        }
+        if (parts[0] != 0) return fail(c, YABPE_E_INVALID, "the first part must start at 0");
+    } else {
+        parts.push_back(0);
+    }
+    const uint32_t np = (uint32_t)parts.size();
+    parts.push_back(n_bytes);  // (the offsets of paths 0 and 1: the input's, with the end)
+    CaseTables T{};
+    TRY(case_tables(c, &T));
+    yabpe_lowercase_free(c);
+    c->case_stats = yabpe_lowercase_stats_t{};
+    c->case_stats.n_bytes_in = n_bytes;
+    c->case_stats.n_parts = np;
+    for (auto &e : c->case_ev)
+        if (!e) HIPCHK(c, hipEventCreate(&e));
+    hipStream_t s = c->stream;
+    const unsigned long long n = n_bytes;
+    Scratch S(c->device, c->rank);
+    const uint8_t *d_text = nullptr;
+    TRY(to_device(c, S, text, n_bytes, 16, &d_text));
+    unsigned long long *d_parts = nullptr;
+    HIPCHK(c, S.get(&d_parts, parts.size()));
+    HIPCHK(c, hipMemcpyAsync(d_parts, parts.data(), parts.size() * 8, hipMemcpyHostToDevice, s));
+    // the result of path 0 (and of an empty text): the input and its offsets
+    auto hand_out_input = [&]() {
+        if (d_text != text && n) c->case_bufs.push_back(S.take(const_cast<uint8_t *>(d_text)));  // (the staged text is handed out)
+        c->case_bufs.push_back(S.take(d_parts));
+        *out_dev_text = n ? d_text : nullptr;
+        *out_dev_part_off = (uint64_t *)d_parts;
+        *out_n_bytes = n;
+        c->case_stats.n_bytes_out = n;
+    };
+    if (n == 0) {
+        HIPCHK(c, hipStreamSynchronize(s));
+        hand_out_input();
+        return YABPE_OK;
+    }
+    // ---- check: part marks, UTF-8, what changes, the bytes every window writes
+    const unsigned long long n_win = (n + CASE_WIN - 1) / CASE_WIN;
+    const dim3 wgrid((uint32_t)std::min<unsigned long long>(n_win, (unsigned long long)c->n_cu * 16));  // (a few atomics per workgroup)
+    uint8_t *marks = nullptr;
+    uint32_t *wout = nullptr;
+    unsigned long long *ctr = nullptr;  // [0] first malformed byte, [1] changing code points, [2] length changers, [3] sigmas, [4] final sigmas
+    if (np > 1) {  // (one part: no marks, the kernels know that it starts at byte 0)
+        HIPCHK(c, S.get(&marks, n));
+    }
+    HIPCHK(c, S.get(&wout, n_win));
+    HIPCHK(c, S.get(&ctr, 5));
+    const unsigned long long ctr0[5] = {~0ull, 0, 0, 0, 0};
+    unsigned long long h_ctr[5] = {0, 0, 0, 0, 0};
+    HIPCHK(c, hipEventRecord(c->case_ev[0], s));
+    HIPCHK(c, hipMemcpyAsync(ctr, ctr0, sizeof(ctr0), hipMemcpyHostToDevice, s));
+    if (marks) {
+        HIPCHK(c, hipMemsetAsync(marks, 0, n, s));
+        hipLaunchKernelGGL(k_pt_mark_chunks, dim3((np + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, s, marks, (const unsigned long long *)d_parts, np, n);
+    }
+    const CaseCheckParams C{d_text, marks, n, T, wout, ctr};
+    hipLaunchKernelGGL(k_case_check, wgrid, dim3(BLOCK), 0, s, C);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipEventRecord(c->case_ev[1], s));
+    HIPCHK(c, hipMemcpyAsync(h_ctr, ctr, 32, hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipStreamSynchronize(s));
+    if (h_ctr[0] != ~0ull) {
+        *out_bad_pos = (int64_t)h_ctr[0];
+        return fail(c, YABPE_E_UTF8, "invalid UTF-8 at byte %lld", (long long)h_ctr[0]);
+    }
+    c->case_stats.n_changed = h_ctr[1];
+    c->case_stats.n_resized = h_ctr[2];
+    c->case_stats.n_sigma = h_ctr[3];
+    if (h_ctr[1] == 0) {  // the text is lower case
+        lowercase_times(c, 1);
+        hand_out_input();
+        return YABPE_OK;
+    }
+    if (h_ctr[2] == 0 && h_ctr[3] == 0) {  // ---- same size
+        uint8_t *out = nullptr;
+        HIPCHK(c, S.get(&out, n));
+        const unsigned long long n_pieces = (n + CASE_PIECE - 1) / CASE_PIECE;
+        const uint32_t grid = (uint32_t)std::min<unsigned long long>((n_pieces + BLOCK - 1) / BLOCK, (unsigned long long)c->n_cu * 16);
+        hipLaunchKernelGGL(k_case_same, dim3(grid), dim3(BLOCK), 0, s, d_text, n, T, out);
+        HIPCHK(c, hipGetLastError());
+        HIPCHK(c, hipEventRecord(c->case_ev[2], s));
+        HIPCHK(c, hipStreamSynchronize(s));
+        lowercase_times(c, 2);
+        c->case_stats.path = 1;
+        c->case_stats.n_copied = n;
+        c->case_stats.n_bytes_out = n;
+        c->case_bufs.push_back(S.take(out));
+        c->case_bufs.push_back(S.take(d_parts));
+        *out_dev_text = out;
+        *out_dev_part_off = (uint64_t *)d_parts;
+        *out_n_bytes = n;
+        return YABPE_OK;
+    }
+    // ---- general: the final sigmas, the base of every window
+    uint16_t *fin = nullptr;
+    if (h_ctr[3]) {
+        HIPCHK(c, S.get(&fin, (n + CASE_PIECE - 1) / CASE_PIECE));
+        HIPCHK(c, case_sigma_scans(s, S, d_text, marks, n, T, fin));
+    }
+    unsigned long long *rbase = nullptr;
+    HIPCHK(c, S.get(&rbase, n_win + 1));
+    if (exclusive_scan<uint32_t>(s, wout, n_win, rbase, n_win + 1) != 0) return fail(c, YABPE_E_HIP, "lowercase: scan of the window sizes");
+    unsigned long long n_out = 0;
+    HIPCHK(c, hipMemcpyAsync(&n_out, rbase + n_win, 8, hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipEventRecord(c->case_ev[2], s));
+    HIPCHK(c, hipStreamSynchronize(s));
+    if (n_out > n + n / 2 + 1) return fail(c, YABPE_E_INTERNAL, "lowercase: %llu bytes out of %llu", n_out, n);
+    // ---- write: every window at its base, the part offsets with it
+    uint8_t *out = nullptr;
+    unsigned long long *out_off = nullptr;
+    HIPCHK(c, S.get(&out, n_out + 16));
+    HIPCHK(c, S.get(&out_off, (uint64_t)np + 1));
+    const CaseWriteParams W{d_text, n, T, fin, d_parts, np, rbase, out, out_off, ctr + 4};
+    hipLaunchKernelGGL(k_case_write, wgrid, dim3(BLOCK), 0, s, W);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipEventRecord(c->case_ev[3], s));
+    HIPCHK(c, hipMemcpyAsync(h_ctr + 4, ctr + 4, 8, hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipStreamSynchronize(s));
+    lowercase_times(c, 3);
+    c->case_stats.path = 2;
+    c->case_stats.n_final_sigma = h_ctr[4];
+    c->case_stats.n_copied = n_out;
+    c->case_stats.n_bytes_out = n_out;
+    c->case_bufs.push_back(S.take(out));
+    c->case_bufs.push_back(S.take(out_off));
     *out_dev_text = out;
     *out_dev_part_off = (uint64_t *)out_off;
     *out_n_bytes = n_out;

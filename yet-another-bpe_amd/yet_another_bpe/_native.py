@@ -114,6 +114,11 @@ class Utf8Stats(ctypes.Structure):
         (n, c_double) for n in ("check_ms", "write_ms", "total_ms")]
 
 
+class LowercaseStats(ctypes.Structure):
+    _fields_ = [(n, c_uint64) for n in ("n_bytes_in", "n_bytes_out", "n_parts", "n_changed", "n_resized", "n_sigma", "n_final_sigma", "path",
+                                        "n_copied")] + [(n, c_double) for n in ("check_ms", "scan_ms", "write_ms", "total_ms")]
+
+
 class Latency(ctypes.Structure):
     _fields_ = [(n, c_double) for n in ("launch_gap_us", "load_trip_us", "coherent_trip_us", "atomic_trip_us")]
 
@@ -136,6 +141,7 @@ SYMBOLS = [
     "yabpe_pool_add", "yabpe_pool_get", "yabpe_pool_clear", "yabpe_pool_stats",
     "yabpe_normalize", "yabpe_normalize_free", "yabpe_normalize_stats",
     "yabpe_utf8_repair", "yabpe_utf8_repair_free", "yabpe_utf8_repair_stats",
+    "yabpe_lowercase", "yabpe_lowercase_free", "yabpe_lowercase_stats",
 ]
 
 
@@ -217,6 +223,10 @@ def lib() -> ctypes.CDLL:
                                         POINTER(c_uint64)]
         L.yabpe_utf8_repair_free.argtypes = [c_void_p]
         L.yabpe_utf8_repair_stats.argtypes = [c_void_p, POINTER(Utf8Stats)]
+        L.yabpe_lowercase.argtypes = [c_void_p, c_void_p, c_uint64, c_void_p, c_uint32, POINTER(c_void_p), POINTER(c_void_p),
+                                      POINTER(c_uint64), POINTER(ctypes.c_int64)]
+        L.yabpe_lowercase_free.argtypes = [c_void_p]
+        L.yabpe_lowercase_stats.argtypes = [c_void_p, POINTER(LowercaseStats)]
         if L.yabpe_abi_version() != 2:
             raise ImportError("libyabpe.so ABI version mismatch")
         _lib = L
@@ -513,6 +523,42 @@ class Context:
         s = Utf8Stats()
         self._chk(lib().yabpe_utf8_repair_stats(self._h, byref(s)))
         return {f: getattr(s, f) for f, _ in Utf8Stats._fields_}
+
+    # -- str.lower() between utf8_repair() and normalize() (include/yabpe.h: yabpe_lowercase)
+    def lowercase(self, text, n_bytes: int | None = None, part_starts=None):
+        """part.lower() of every part of `text` on the device.  `text`: bytes / u8 array (staged) or a device address (then
+        n_bytes is required).  part_starts: ascending part starts, the first one 0 (None: one part); parts are lowered
+        independently (the final-sigma rule does not look across a part boundary).
+        -> (dev_text_ptr, dev_part_off_ptr u64[n_parts + 1], n_bytes_out); the buffers live until the next lowercase,
+        lowercase_free() or close().  A text that is lower case already comes back as it is (a 16-byte aligned device
+        address: the same address).  Raises Utf8Error(position) on malformed UTF-8, the position in the input."""
+        keep = None
+        if isinstance(text, int):
+            ptr, n = c_void_p(text), int(n_bytes)
+        else:
+            keep = np.frombuffer(text, dtype=np.uint8) if not isinstance(text, np.ndarray) else np.ascontiguousarray(text, dtype=np.uint8)
+            ptr, n = c_void_p(keep.ctypes.data if keep.size else 0), int(keep.size)
+        st = np.ascontiguousarray(part_starts if part_starts is not None and len(part_starts) else [0], dtype=np.uint64)
+        dt, do, nb, bad = c_void_p(), c_void_p(), c_uint64(0), ctypes.c_int64(-1)
+        rc = lib().yabpe_lowercase(self._h, ptr, n, st.ctypes.data, len(st), byref(dt), byref(do), byref(nb), byref(bad))
+        if rc == E_UTF8:
+            raise Utf8Error(bad.value)
+        self._chk(rc)
+        return dt.value or 0, do.value, nb.value
+
+    def lowercase_to_host(self, text, n_bytes: int | None = None, part_starts=None):
+        """-> (text u8[n_bytes_out], part_off u64[n_parts + 1]) copied to the host."""
+        n_parts = len(part_starts) if part_starts is not None and len(part_starts) else 1
+        dt, do, nb = self.lowercase(text, n_bytes, part_starts)
+        return (self.d2h(dt, nb) if nb else np.zeros(0, np.uint8)), self.d2h(do, 8 * (n_parts + 1), np.uint64)
+
+    def lowercase_free(self) -> None:
+        self._chk(lib().yabpe_lowercase_free(self._h))
+
+    def lowercase_stats(self) -> dict:
+        s = LowercaseStats()
+        self._chk(lib().yabpe_lowercase_stats(self._h, byref(s)))
+        return {f: getattr(s, f) for f, _ in LowercaseStats._fields_}
 
     # -- encoding with a trained model (BBPETokenizer.encode on the device)
     def encode_set_model(self, vocab: dict, merges, specials_ordered, unk_id: int) -> None:

@@ -150,17 +150,21 @@ def plan_chunk_shards(sizes: Sequence[int], world: int) -> list[tuple[int, int]]
 
 def _pretokenize_my_chunks(ctx, text, n_bytes, starts, config):
     """This rank's chunks -> (device text, device word offsets, n_words): with config.errors = "replace" / "ignore"
-    yabpe_utf8_repair, then with config.normalizer yabpe_normalize run in front of
+    yabpe_utf8_repair, then with config.lowercase yabpe_lowercase, then with config.normalizer yabpe_normalize run in front of
     yabpe_pretokenize (chunk by chunk; their texts stay the context's), as BBPETrainer._device_words does it.  A
     _native.SegmentTooLong raised after a repair carries .repaired_starts (the chunks' starts in the repaired text)."""
     from . import _native
-    from .trainer import check_errors, check_normalizer
+    from .trainer import check_errors, check_lowercase, check_normalizer
 
     form = check_normalizer(getattr(config, "normalizer", None))
     repair = check_errors(getattr(config, "errors", "strict"))
+    lower = check_lowercase(getattr(config, "lowercase", False))
     n_chunks = len(starts)
     if repair:
         text, dev_starts, n_bytes = ctx.utf8_repair(text, n_bytes=n_bytes, part_starts=starts, mode=repair)
+        starts = ctx.d2h(dev_starts, 8 * n_chunks, np.uint64)
+    if lower and (n_bytes is None or n_bytes):
+        text, dev_starts, n_bytes = ctx.lowercase(text, n_bytes=n_bytes, part_starts=starts)
         starts = ctx.d2h(dev_starts, 8 * n_chunks, np.uint64)
     if form and (n_bytes is None or n_bytes):
         try:

@@ -26,7 +26,8 @@ import regex
 
 from .synth import rnd_int
 from .trainer import (CL100K_DIGIT_GROUP, NORMALIZERS, PRETOKENIZER_NAMES, BBPETrainerConfig, check_digit_group, check_errors,
-                      check_normalized_specials, check_normalizer, check_pretokenizer, device_options, normalize_text, read_normalizer, read_pretokenizer, split_pattern)
+                      check_lowercase, check_lowercase_specials, check_normalized_specials, check_normalizer, check_pretokenizer, device_options,
+                      lowercase_text, normalize_text, read_lowercase, read_normalizer, read_pretokenizer, split_pattern)
 
 _WORD_CACHE = 8192
 
@@ -39,11 +40,16 @@ class BBPETokenizer:
     With normalizer = "nfc" every method that takes text replaces each document by unicodedata.normalize("NFC", document) first
     (on the GPU: yabpe_normalize in front of the encode call), so encode(x) == encode(normalize(x)); the specials are matched in
     the normalised text (a special that is not NFC itself: ValueError), and the spans of the *_with_offsets methods, in bytes
-    and in characters, refer to the normalised document, which normalize() / normalize_array() return.  Decoding is untouched."""
+    and in characters, refer to the normalised document, which normalize() / normalize_array() return.  Decoding is untouched.
+    With lowercase = True every method that takes text replaces each document by document.lower() first -- before the
+    normaliser, so with "nfc" as well a document becomes NFC(document.lower()) (on the GPU: yabpe_lowercase in front of
+    yabpe_normalize and the encode call).  Lower-then-NFC is idempotent, so encode(x) == encode(normalize(x)) still holds; the
+    specials are matched in the lowered text (a special that is not lower case itself: ValueError), the spans refer to the
+    lowered, then normalised document, which normalize() / normalize_array() return, and decoding is untouched."""
 
     def __init__(self, vocab: dict[bytes, int] | None = None, merges: list[tuple[bytes, bytes]] | None = None,
                  special_tokens: list[str] | None = None, digit_group: int | None = None, pretokenizer: str = "gpt2",
-                 normalizer: str | None = None) -> None:
+                 normalizer: str | None = None, lowercase: bool = False) -> None:
         self._vocab: dict[bytes, int] = vocab or {}
         self._vocab_inv: dict[int, bytes] = {i: t for t, i in self._vocab.items()}
         self._merges: list[tuple[bytes, bytes]] = merges or []
@@ -55,6 +61,8 @@ class BBPETokenizer:
         self._pattern = regex.compile(split_pattern(self._digit_group, self._pretokenizer))
         self._normalizer: str | None = NORMALIZERS[check_normalizer(normalizer)]
         check_normalized_specials(self._special_tokens, self._normalizer)
+        self._lowercase: bool = check_lowercase(lowercase)
+        check_lowercase_specials(self._special_tokens, self._lowercase)
         # specials are split out first, longest first (reference tokenizer.py:100-102)
         self._special_pattern = None
         if self._special_tokens:
@@ -86,7 +94,8 @@ class BBPETokenizer:
             with open(sp, encoding="utf-8") as f:
                 specials = list(json.load(f))
         name, group = read_pretokenizer(d)
-        return cls(vocab=vocab, merges=merges, special_tokens=specials, digit_group=group, pretokenizer=name, normalizer=read_normalizer(d))
+        return cls(vocab=vocab, merges=merges, special_tokens=specials, digit_group=group, pretokenizer=name, normalizer=read_normalizer(d),
+                   lowercase=read_lowercase(d))
 
     @classmethod
     def from_file_lossless(cls, model_dir: str | Path) -> "BBPETokenizer":
@@ -105,7 +114,8 @@ class BBPETokenizer:
             with open(d / "special_tokens.json", encoding="utf-8") as f:
                 specials = list(json.load(f))
         name, group = read_pretokenizer(d)
-        return cls(vocab=vocab, merges=merges, special_tokens=specials, digit_group=group, pretokenizer=name, normalizer=read_normalizer(d))
+        return cls(vocab=vocab, merges=merges, special_tokens=specials, digit_group=group, pretokenizer=name, normalizer=read_normalizer(d),
+                   lowercase=read_lowercase(d))
 
     # ------------------------------------------------------------------ encode
     def _word_parts(self, data: bytes) -> list[bytes]:
@@ -141,8 +151,9 @@ class BBPETokenizer:
             out.extend(self._word_ids(pre))
 
     def normalize(self, text: str) -> str:
-        """The document the ids and spans of `text` refer to: `text` as the model's normaliser leaves it (none: as it is)."""
-        return normalize_text(text, self._normalizer)
+        """The document the ids and spans of `text` refer to: `text` lowered when the model lowers, then as the model's
+        normaliser leaves it (neither: as it is)."""
+        return normalize_text(lowercase_text(text, self._lowercase), self._normalizer)
 
     def encode(self, text: str) -> list[int]:
         text = self.normalize(text)
@@ -599,13 +610,17 @@ class BBPETokenizer:
 
     def _device_text(self, ctx, inp, errors: str = "strict"):
         """What the encode calls of ctx take as (text, n_bytes, doc_starts) for _device_input's buffer: the buffer itself, or with
-        errors = "replace" / "ignore" the repaired text (yabpe_utf8_repair; the context's until its next repair), or with a
+        errors = "replace" / "ignore" the repaired text (yabpe_utf8_repair; the context's until its next repair), or with
+        lowercase the lowered text made from either (yabpe_lowercase; the context's until its next lowercase), or with a
         normaliser the normalised text made from either (yabpe_normalize; the context's until its next normalize), in device
         memory, and the documents' starts in it."""
         text, n_bytes, starts = np.frombuffer(inp[0], dtype=np.uint8), None, inp[1]
         repair, form = check_errors(errors), check_normalizer(self._normalizer)
         if repair and text.size:
             text, dev_starts, n_bytes = ctx.utf8_repair(text, part_starts=starts, mode=repair)
+            starts = ctx.d2h(dev_starts, 8 * len(inp[1]), np.uint64)
+        if self._lowercase and (text.size if n_bytes is None else n_bytes):
+            text, dev_starts, n_bytes = ctx.lowercase(text, n_bytes=n_bytes, part_starts=starts)
             starts = ctx.d2h(dev_starts, 8 * len(inp[1]), np.uint64)
         if form and (text.size if n_bytes is None else n_bytes):
             text, dev_starts, n_bytes = ctx.normalize(text, n_bytes=n_bytes, part_starts=starts, form=form)
@@ -615,13 +630,13 @@ class BBPETokenizer:
     def normalize_array(self, texts, *, errors: str = "strict") -> tuple[np.ndarray, np.ndarray]:
         """normalize() of every document on the GPU: `texts` as encode_array takes them -> (text np.uint8[n], text_off
         np.uint64[n_docs + 1]): text[text_off[d]:text_off[d + 1]] is normalize(texts[d]) as UTF-8 -- the documents the spans of
-        encode_array_with_offsets refer to.  Without a normaliser the documents come back as they are.  errors: as encode_array
+        encode_array_with_offsets refer to.  Without a normaliser and without lowercase the documents come back as they are.  errors: as encode_array
         takes it -- the document is then normalize(data.decode("utf-8", errors)), the repaired and then normalised one."""
         inp = self._device_input(texts)
         if inp is None:
             return np.zeros(0, np.uint8), np.zeros(1, np.uint64)
         repair, form = check_errors(errors), check_normalizer(self._normalizer)
-        if not form and not repair:
+        if not form and not repair and not self._lowercase:
             return np.frombuffer(inp[0], dtype=np.uint8).copy(), np.append(np.asarray(inp[1], dtype=np.uint64), np.uint64(len(inp[0])))
         ctx = self._device()
         text, n_bytes, starts = self._device_text(ctx, inp, errors)
@@ -833,6 +848,10 @@ class BBPETokenizer:
     @property
     def normalizer(self) -> str | None:
         return self._normalizer
+
+    @property
+    def lowercase(self) -> bool:
+        return self._lowercase
 
     @property
     def special_tokens(self) -> list[str]:

@@ -148,6 +148,38 @@ def normalize_text(text: str, name) -> str:
     return unicodedata.normalize("NFC", text) if name else text
 
 
+def check_lowercase(flag) -> bool:
+    """The lowercase setting: a bool and nothing else (1, "true" and None are a ValueError)."""
+    if not isinstance(flag, bool):
+        raise ValueError(f"lowercase must be True or False, got {flag!r}")
+    return flag
+
+
+def check_lowercase_specials(tokens: Sequence[str], flag) -> None:
+    """With lowercase the specials are matched in the lowered text, so a special that is not lower case itself could never
+    match: ValueError."""
+    if check_lowercase(flag):
+        for tok in tokens:
+            if tok.lower() != tok:
+                raise ValueError(f"special token {tok!r} is not lower case: with lowercase = True it could never match the lowered text "
+                                 "(the default special_tokens [PAD], [UNK], [BOS], [EOS] are upper case: pass lower-case ones)")
+
+
+def lowercase_text(text: str, flag) -> str:
+    """THE host-side lower-casing: `text` as the setting leaves it (False: as it is).  It runs before normalize_text."""
+    return text.lower() if flag else text
+
+
+def read_lowercase(model_dir: str | Path) -> bool:
+    """Whether a saved model was trained on lowered text: pretokenizer.json in its directory, False when it does not say."""
+    f = Path(model_dir) / PRETOKENIZER_FILE
+    if not f.exists():
+        return False
+    with open(f, encoding="utf-8") as fh:
+        flag = json.load(fh).get("lowercase", False)
+    return check_lowercase(flag)
+
+
 def read_normalizer(model_dir: str | Path) -> str | None:
     """The normaliser a saved model was trained with: pretokenizer.json in its directory, None when it names none."""
     f = Path(model_dir) / PRETOKENIZER_FILE
@@ -220,6 +252,14 @@ class BBPETrainerConfig:
             independently: a sequence cut off by a chunk's end is ill-formed there.  A property of how the files are read,
             NOT of the model: not stored by save / save_lossless, not carried by BBPEModel, not compared by train_from.
             BBPETrainer.utf8_replaced holds the number of subparts replaced or dropped by the last call.
+        lowercase: False, or True: every chunk _chunk_ranges cuts is replaced by chunk.lower() (str.lower() of CPython: the full
+            Unicode mapping with the final-sigma rule, no locale) after the repair of invalid UTF-8 and before the normaliser,
+            the special tokens and the split pattern see it (on the device: yabpe_lowercase between yabpe_utf8_repair and
+            yabpe_normalize); with normalizer = "nfc" a chunk becomes NFC(chunk.lower()).  Chunks are lowered independently:
+            the final-sigma rule never looks across a chunk cut.  The front end of uncased models.  Part of the model like
+            the normaliser (BBPEModel.lowercase, "lowercase" in pretokenizer.json, BBPETokenizer).  Specials are matched in
+            the lowered text: a special token that is not lower case itself is a ValueError -- the default special_tokens
+            are upper case, so lower-case ones must be passed.  Must be a bool.
     """
 
     vocab_size: int = 32000
@@ -233,6 +273,7 @@ class BBPETrainerConfig:
     pretokenizer: str = "gpt2"
     normalizer: str | None = None
     errors: str = "strict"
+    lowercase: bool = False
 
 
 U16_TOKENS = 65_534  # tokens the u16 merge loop holds (ids 0 .. 65,533)
@@ -290,6 +331,7 @@ def pretokenizer(config: BBPETrainerConfig) -> tuple[int, int]:
     if pattern == 3:
         check_disjoint_specials(config.special_tokens)
     check_normalized_specials(config.special_tokens, getattr(config, "normalizer", None))
+    check_lowercase_specials(config.special_tokens, getattr(config, "lowercase", False))
     return pattern, group
 
 
@@ -314,17 +356,19 @@ def digit_group(config: BBPETrainerConfig) -> int:
 class BBPEModel:
     """Result container (reference trainer.py:41-52): copies of vocab, merges, special tokens; digit_group (not in the
     reference): the digit group of the pre-tokenisation the model was trained with, None for the GPT-2 pattern; pretokenizer:
-    "gpt2", or "cl100k" / "o200k_base" (digit_group is then never None); normalizer: None or "nfc"."""
+    "gpt2", or "cl100k" / "o200k_base" (digit_group is then never None); normalizer: None or "nfc"; lowercase: whether the text
+    was lowered in front of the normaliser."""
 
     def __init__(self, vocab: Mapping[bytes, int], merges: Sequence[tuple[bytes, bytes]],
                  special_tokens: Sequence[str], digit_group: int | None = None, pretokenizer: str = "gpt2",
-                 normalizer: str | None = None) -> None:
+                 normalizer: str | None = None, lowercase: bool = False) -> None:
         self.vocab: dict[bytes, int] = dict(vocab)
         self.merges: list[tuple[bytes, bytes]] = list(merges)
         self.special_tokens: list[str] = list(special_tokens)
         self.pretokenizer: str = PRETOKENIZER_NAMES[check_pretokenizer(pretokenizer)]
         self.digit_group: int | None = check_digit_group(digit_group) or (CL100K_DIGIT_GROUP if self.pretokenizer != "gpt2" else None)
         self.normalizer: str | None = NORMALIZERS[check_normalizer(normalizer)]
+        self.lowercase: bool = check_lowercase(lowercase)
 
     @classmethod
     def from_file_lossless(cls, model_dir: str | Path) -> "BBPEModel":
@@ -344,7 +388,8 @@ class BBPEModel:
             with open(d / "special_tokens.json", encoding="utf-8") as f:
                 specials = list(json.load(f))
         name, group = read_pretokenizer(d)
-        return cls(vocab=vocab, merges=merges, special_tokens=specials, digit_group=group, pretokenizer=name, normalizer=read_normalizer(d))
+        return cls(vocab=vocab, merges=merges, special_tokens=specials, digit_group=group, pretokenizer=name, normalizer=read_normalizer(d),
+                   lowercase=read_lowercase(d))
 
 
 def _utf8_cut(window: bytes, pos: int) -> int:
@@ -479,7 +524,8 @@ class BBPETrainer:
     def _model(self, vocab, merges) -> BBPEModel:
         pattern, group = pretokenizer(self.config)
         return BBPEModel(vocab=vocab, merges=merges, special_tokens=list(self.config.special_tokens), digit_group=group or None,
-                         pretokenizer=PRETOKENIZER_NAMES[pattern], normalizer=getattr(self.config, "normalizer", None))
+                         pretokenizer=PRETOKENIZER_NAMES[pattern], normalizer=getattr(self.config, "normalizer", None),
+                         lowercase=getattr(self.config, "lowercase", False))
 
     # ------------------------------------------------------------------ train / save (trainer.py:63-117)
     def train(self, files: Sequence[str | Path], batch_bytes: int | None = None) -> BBPEModel:
@@ -518,6 +564,9 @@ class BBPETrainer:
         if getattr(model, "normalizer", None) != getattr(self.config, "normalizer", None):
             raise ValueError(f"cannot continue from this model: it was trained with normalizer = {getattr(model, 'normalizer', None)!r}, "
                              f"the trainer's is {getattr(self.config, 'normalizer', None)!r} (its merges would be replayed over words it never saw)")
+        if getattr(model, "lowercase", False) != getattr(self.config, "lowercase", False):
+            raise ValueError(f"cannot continue from this model: it was trained with lowercase = {getattr(model, 'lowercase', False)!r}, "
+                             f"the trainer's is {getattr(self.config, 'lowercase', False)!r} (its merges would be replayed over words it never saw)")
         toks, triples = self._resumable(model)
         old_merges = [(bytes(l), bytes(r)) for l, r in model.merges]
         check_files(paths)
@@ -581,7 +630,8 @@ class BBPETrainer:
 
     def _device_words(self, ctx, chunks: Sequence[tuple[Path, int, int]], batch_bytes: int | None, dedup: bool):
         """The chunks' pre-tokens as device words for _run: file bytes -> (with errors = "replace" / "ignore": yabpe_utf8_repair,
-        chunk by chunk -> the repaired text and the chunk starts in it ->) (with a normaliser: yabpe_normalize, chunk by chunk
+        chunk by chunk -> the repaired text and the chunk starts in it ->) (with lowercase: yabpe_lowercase, chunk by chunk -> the
+        lowered text and the chunk starts in it ->) (with a normaliser: yabpe_normalize, chunk by chunk
         -> the normalised text and the chunk starts in it ->) yabpe_pretokenize -> word offsets in HBM (equal
         pre-tokens are pooled by the load when `dedup`).  With `batch_bytes` the chunks are read batch by batch (one batch on
         the host at a time) and each batch's pre-tokens added to ctx's word pool (yabpe_pool_add); the words are then the
@@ -591,6 +641,7 @@ class BBPETrainer:
 
         form = check_normalizer(getattr(self.config, "normalizer", None))
         repair = check_errors(getattr(self.config, "errors", "strict"))
+        lower = check_lowercase(getattr(self.config, "lowercase", False))
 
         def pretokenize(part):
             buf, starts = read_chunks(part)
@@ -602,6 +653,11 @@ class BBPETrainer:
                     text, dev_starts, n_bytes = ctx.utf8_repair(buf, part_starts=starts, mode=repair)
                     cur = ctx.d2h(dev_starts, 8 * len(starts), np.uint64)
                     self.utf8_replaced += int(ctx.utf8_repair_stats()["n_subparts"])
+                if lower and (n_bytes is None or n_bytes):
+                    # the lowered text stays the context's until lowercase_free (the words are offsets into it, or into the
+                    # normalised text made from it)
+                    text, dev_starts, n_bytes = ctx.lowercase(text, n_bytes=n_bytes, part_starts=cur)
+                    cur = ctx.d2h(dev_starts, 8 * len(starts), np.uint64)
                 if form and (n_bytes is None or n_bytes):
                     # the normalised text stays the context's until normalize_free (the words are offsets into it)
                     text, dev_starts, n_bytes = ctx.normalize(text, n_bytes=n_bytes, part_starts=cur, form=form)
@@ -609,10 +665,13 @@ class BBPETrainer:
                 if n_bytes == 0:  # (every byte was dropped: no words)
                     text, n_bytes = np.zeros(0, np.uint8), None
                 return ctx.pretokenize(text, n_bytes=n_bytes, chunk_starts=cur, special_tokens=list(self.config.special_tokens))
-            except _native.Utf8Error as e:  # (positions in buf: the normaliser validates the text it is given)
+            except _native.Utf8Error as e:  # (positions in buf: the first step that reads the text validates it)
                 raise utf8_error(part, starts, e) from e
             except _native.SegmentTooLong as e:
-                raise (repaired_segment_error(part, cur, e) if repair else segment_error(part, starts, e)) from e
+                # (a position in the text the normaliser read, `cur` the chunks' starts in it.  Lowered text: the chunk is the
+                # right one, the position inside it counts the lowered bytes -- the file's, give or take what the 25 code
+                # points that change length did in front of it)
+                raise (repaired_segment_error(part, cur, e) if repair else segment_error(part, [int(s0) for s0 in cur], e)) from e
 
         if batch_bytes is None:
             return (*pretokenize(chunks), 0, dedup)
@@ -621,6 +680,8 @@ class BBPETrainer:
             ctx.pretokenize_free()
             if form:
                 ctx.normalize_free()
+            if lower:
+                ctx.lowercase_free()
             if repair:
                 ctx.utf8_repair_free()
         dev_bytes, dev_off, dev_freq, n_unique, _n_bytes = ctx.pool_get()
@@ -770,13 +831,15 @@ class BBPETrainer:
         self._save_pretokenizer(out)
 
     def _save_pretokenizer(self, out: Path) -> None:
-        """pretokenizer.json, only when the model was trained with a digit group, another pattern than GPT-2's or a normaliser
-        (without them the directory holds exactly the files it always held; a file left there by an earlier save is
-        removed).  "normalizer" is written only when one is set."""
+        """pretokenizer.json, only when the model was trained with a digit group, another pattern than GPT-2's, a normaliser or
+        lowercase (without them the directory holds exactly the files it always held; a file left there by an earlier save
+        is removed).  "normalizer" is written only when one is set, "lowercase" only when it is."""
         pattern, group = pretokenizer(self.config)
         d = {"pattern": PRETOKENIZER_NAMES[pattern], "digit_group": group} if pattern else {"digit_group": group} if group else {}
         if getattr(self.config, "normalizer", None):
             d["normalizer"] = self.config.normalizer
+        if check_lowercase(getattr(self.config, "lowercase", False)):
+            d["lowercase"] = True
         if d:
             with open(out / PRETOKENIZER_FILE, "w", encoding="utf-8") as f:
                 json.dump(d, f)
@@ -851,6 +914,7 @@ class BBPETrainer:
                     replaced.append(n)
             except UnicodeDecodeError as e:
                 raise ValueError(f"File {path} contains invalid UTF-8 at position {start + e.start}.") from e
+            text = lowercase_text(text, getattr(self.config, "lowercase", False))
             return [t for t in pattern.findall(normalize_text(text, getattr(self.config, "normalizer", None))) if t]
 
         check_files(files)
