@@ -152,7 +152,8 @@ def _pretokenize_my_chunks(ctx, text, n_bytes, starts, config):
     """This rank's chunks -> (device text, device word offsets, n_words): with config.errors = "replace" / "ignore"
     yabpe_utf8_repair, then with config.lowercase yabpe_lowercase, then with config.normalizer yabpe_normalize run in front of
     yabpe_pretokenize (chunk by chunk; their texts stay the context's), as BBPETrainer._device_words does it.  A
-    _native.SegmentTooLong raised after a repair carries .repaired_starts (the chunks' starts in the repaired text)."""
+    _native.SegmentTooLong carries .read_starts (the chunks' starts in the text the normaliser read: repaired and lowered, so
+    not the starts that came in) and .repaired (whether a repair ran in front of it)."""
     from . import _native
     from .trainer import check_errors, check_lowercase, check_normalizer
 
@@ -170,7 +171,7 @@ def _pretokenize_my_chunks(ctx, text, n_bytes, starts, config):
         try:
             text, dev_starts, n_bytes = ctx.normalize(text, n_bytes=n_bytes, part_starts=starts, form=form)
         except _native.SegmentTooLong as e:
-            e.repaired_starts = starts if repair else None
+            e.read_starts, e.repaired = [int(s0) for s0 in starts], bool(repair)
             raise
         starts = ctx.d2h(dev_starts, 8 * n_chunks, np.uint64)
     if n_bytes == 0:  # (every byte was dropped: no words)
@@ -220,8 +221,7 @@ def train_text_sharded(ctx_factory, files, config, rank: int, world: int, transp
             except _native.Utf8Error as e:
                 err = (rank, str(utf8_error(chunks[c0:c1], starts, e)))  # (the chunks go to the ranks in order)
             except _native.SegmentTooLong as e:
-                moved = getattr(e, "repaired_starts", None)
-                err = (rank, str(segment_error(chunks[c0:c1], starts, e) if moved is None else repaired_segment_error(chunks[c0:c1], moved, e)))
+                err = (rank, str((repaired_segment_error if e.repaired else segment_error)(chunks[c0:c1], e.read_starts, e)))
         if world > 1:  # every rank must learn about the first bad chunk anywhere, or the others would wait in the merge loop
             import torch.distributed as dist
 

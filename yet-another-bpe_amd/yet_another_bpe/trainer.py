@@ -481,12 +481,19 @@ def utf8_error(chunks: Sequence[tuple[Path, int, int]], starts: Sequence[int], e
     return ValueError(f"File {path} contains invalid UTF-8 at position {start + e.position - starts[k]}.")
 
 
+def _segment_reason(e) -> str:
+    """The library's words for a _native.SegmentTooLong without its position in the buffer the normaliser read: that buffer is
+    the whole corpus, one batch or one rank's chunks, and the message must be the same on every route."""
+    return regex.sub(r"^the segment that starts at byte \d+ holds", "it holds", str(e))
+
+
 def segment_error(chunks: Sequence[tuple[Path, int, int]], starts: Sequence[int], e) -> ValueError:
-    """The same for a _native.SegmentTooLong of the normaliser: the file and the position where the run starts."""
+    """The same for a _native.SegmentTooLong of the normaliser: the file and the position where the run starts (`starts`: the
+    chunks' starts in the text the normaliser read)."""
     k = max(i for i, s0 in enumerate(starts) if s0 <= e.position)
     path, start, _stop = chunks[k]
     return ValueError(f"File {path} holds a run of code points that normalise together over the normaliser's cap at position "
-                      f"{start + e.position - starts[k]}: {e}")
+                      f"{start + e.position - int(starts[k])}: {_segment_reason(e)}")
 
 
 def repaired_segment_error(chunks: Sequence[tuple[Path, int, int]], starts: Sequence[int], e) -> ValueError:
@@ -495,7 +502,7 @@ def repaired_segment_error(chunks: Sequence[tuple[Path, int, int]], starts: Sequ
     k = max(i for i, s0 in enumerate(starts) if s0 <= e.position)
     path, start, stop = chunks[k]
     return ValueError(f"File {path} holds a run of code points that normalise together over the normaliser's cap in the chunk of bytes "
-                      f"{start} to {stop}, at position {e.position - int(starts[k])} of that chunk after its invalid UTF-8 was repaired: {e}")
+                      f"{start} to {stop}, at position {e.position - int(starts[k])} of that chunk after its invalid UTF-8 was repaired: {_segment_reason(e)}")
 
 
 class BBPETrainer:
