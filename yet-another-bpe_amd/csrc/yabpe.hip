@@ -944,6 +944,99 @@ int check_starts(yabpe_ctx *c, const uint64_t *starts, uint32_t n, uint64_t limi
     return 0;
 }
 
+// the chunk starts of the pre-tokeniser (what = "chunk") and the part starts of the text passes ("part"): *v = the host
+// table, validated before a kernel indexes with it, or {0} when none is given
+int offset_table(yabpe_ctx *c, const uint64_t *off, uint32_t n, uint64_t n_bytes, const char *what, std::vector<unsigned long long> *v) {
+    v->clear();
+    if (!off || !n) {
+        v->push_back(0);
+        return 0;
+    }
+    for (uint32_t k = 0; k < n; ++k) {
+        if (off[k] > n_bytes || (k && off[k] < off[k - 1])) return fail(c, YABPE_E_INVALID, "%s offsets must ascend inside the text", what);
+        v->push_back(off[k]);
+    }
+    if ((*v)[0] != 0) return fail(c, YABPE_E_INVALID, "the first %s must start at 0", what);
+    return 0;
+}
+
+// the results a driver handed out and the context owns until that driver's next call or its *_free
+void free_bufs(std::vector<void *> &bufs) {
+    for (void *p : bufs) dfree(p);
+    bufs.clear();
+}
+
+// ms[k] = ev[k] .. ev[k + 1] for every k < last (the rest stays as it is); -> ev[0] .. ev[last]
+float pass_times(const hipEvent_t *ev, int last, float *ms) {
+    float total = 0;
+    for (int k = 0; k < last; ++k) (void)hipEventElapsedTime(&ms[k], ev[k], ev[k + 1]);
+    (void)hipEventElapsedTime(&total, ev[0], ev[last]);
+    return total;
+}
+
+// The front and the hand-out of the text-to-text passes (yabpe_normalize, yabpe_utf8_repair, yabpe_lowercase).  A pass runs
+// its own argument checks, check(), builds its device tables, begin(), its kernels, and ends with hand_out_input() (the
+// text needs no change, or is empty) or hand_out().  A call that check() refuses has freed nothing.
+struct TextPass {
+    yabpe_ctx *c;
+    std::vector<void *> &bufs;  // the pass's results in the context: those of the last call go in begin(), the new ones are pushed here
+    const uint8_t **out_text;
+    uint64_t **out_off;
+    uint64_t *out_n, *stat_n_out = nullptr;  // (the stats' n_bytes_out)
+    Scratch S;
+    std::vector<unsigned long long> parts;  // the part starts and the end: the offsets of an unchanged text
+    const uint8_t *text = nullptr, *d_text = nullptr;
+    unsigned long long n = 0, *d_parts = nullptr;
+    uint32_t np = 0;
+
+    TextPass(yabpe_ctx *c_, std::vector<void *> &bufs_, const uint8_t **out_text_, uint64_t **out_off_, uint64_t *out_n_)
+        : c(c_), bufs(bufs_), out_text(out_text_), out_off(out_off_), out_n(out_n_), S(c_->device, c_->rank) {
+        *out_text = nullptr; *out_off = nullptr; *out_n = 0;
+    }
+    int check(const uint8_t *text_, uint64_t n_bytes, const uint64_t *part_off, uint32_t n_parts) {
+        if (n_bytes && !text_) return fail(c, YABPE_E_INVALID, "text is NULL");
+        TRY(offset_table(c, part_off, n_parts, n_bytes, "part", &parts));
+        text = text_;
+        n = n_bytes;
+        np = (uint32_t)parts.size();
+        parts.push_back(n_bytes);
+        return 0;
+    }
+    // the last call's results freed, the stats reset, the events there; the text (at `align`) and the part table on the device
+    template <class Stats, int NE>
+    int begin(Stats &stats, hipEvent_t (&ev)[NE], uintptr_t align) {
+        free_bufs(bufs);
+        stats = Stats{};
+        stats.n_bytes_in = n;
+        stats.n_parts = np;
+        stat_n_out = &stats.n_bytes_out;
+        for (auto &e : ev)
+            if (!e) HIPCHK(c, hipEventCreate(&e));
+        TRY(to_device(c, S, text, n, align, &d_text));
+        HIPCHK(c, S.get(&d_parts, parts.size()));
+        HIPCHK(c, hipMemcpyAsync(d_parts, parts.data(), parts.size() * 8, hipMemcpyHostToDevice, c->stream));
+        return 0;
+    }
+    // the new text with its offsets (lowercase's same-size path: the input's, d_parts)
+    int hand_out(uint8_t *out, unsigned long long *off, unsigned long long n_out) {
+        bufs.push_back(S.take(out));
+        return hand_out_as(out, off, n_out);
+    }
+    // the input and its offsets: the result when nothing changes, and of an empty text (then only the table upload is in flight)
+    int hand_out_input() {
+        if (n == 0) HIPCHK(c, hipStreamSynchronize(c->stream));
+        if (d_text != text && n) bufs.push_back(S.take(const_cast<uint8_t *>(d_text)));  // (the staged text is handed out)
+        return hand_out_as(n ? d_text : nullptr, d_parts, n);
+    }
+    int hand_out_as(const uint8_t *out, unsigned long long *off, unsigned long long n_out) {
+        bufs.push_back(S.take(off));
+        *out_text = out;
+        *out_off = (uint64_t *)off;
+        *out_n = *stat_n_out = n_out;
+        return YABPE_OK;
+    }
+};
+
 // ---- what the u16 and the u32 drivers share (yabpe_id32_host.h): the differences between the two stay with the callers
 // N timing events of one call: destroyed on every way out
 template <int N>
@@ -2728,8 +2821,7 @@ int yabpe_synth_generate_lex(yabpe_ctx *c, uint64_t target_bytes, uint32_t n_typ
 
 int yabpe_synth_free(yabpe_ctx *c) {
     if (!c) return YABPE_E_INVALID;
-    for (void *p : c->synth_bufs) dfree(p);
-    c->synth_bufs.clear();
+    free_bufs(c->synth_bufs);
     return YABPE_OK;
 }
 
@@ -2776,15 +2868,7 @@ int yabpe_pretokenize(yabpe_ctx *c, const uint8_t *text, uint64_t n_bytes, const
             return fail(c, YABPE_E_INVALID, "an end of special token %u (\"%.*s\") begins special token %u (\"%.*s\"): not allowed with split_pattern = 3", a, la, sa, b, lb, sb);
     }
     std::vector<unsigned long long> chunks;
-    if (chunk_off && n_chunks) {
-        for (uint32_t k = 0; k < n_chunks; ++k) {
-            if (chunk_off[k] > n_bytes || (k && chunk_off[k] < chunk_off[k - 1])) return fail(c, YABPE_E_INVALID, "chunk offsets must ascend inside the text");
-            chunks.push_back(chunk_off[k]);
-        }
-        if (chunks[0] != 0) return fail(c, YABPE_E_INVALID, "the first chunk must start at 0");
-    } else {
-        chunks.push_back(0);
-    }
+    TRY(offset_table(c, chunk_off, n_chunks, n_bytes, "chunk", &chunks));
     TRY(class_table(c));
     if (pattern == 3) TRY(class_table5(c));
     // inputs on the device
@@ -2822,8 +2906,7 @@ int yabpe_pretokenize(yabpe_ctx *c, const uint8_t *text, uint64_t n_bytes, const
 
 int yabpe_pretokenize_free(yabpe_ctx *c) {
     if (!c) return YABPE_E_INVALID;
-    for (void *p : c->pretok_bufs) dfree(p);
-    c->pretok_bufs.clear();
+    free_bufs(c->pretok_bufs);
     return YABPE_OK;
 }
 
@@ -2858,8 +2941,7 @@ static int nfc_tables(yabpe_ctx *c, NfcTables *T) {
 
 int yabpe_normalize_free(yabpe_ctx *c) {
     if (!c) return YABPE_E_INVALID;
-    for (void *p : c->norm_bufs) dfree(p);
-    c->norm_bufs.clear();
+    free_bufs(c->norm_bufs);
     return YABPE_OK;
 }
 
@@ -2871,65 +2953,32 @@ int yabpe_normalize_stats(yabpe_ctx *c, yabpe_normalize_stats_t *out) {
 
 // norm_ev[0..1] around the class pass, [1..2] the search for the dirty segments, [2..3] their lengths, [3..4] the write passes
 static void normalize_times(yabpe_ctx *c, int last) {
-    float ms[5] = {0, 0, 0, 0, 0};
-    for (int k = 0; k < last; ++k) (void)hipEventElapsedTime(&ms[k], c->norm_ev[k], c->norm_ev[k + 1]);
-    (void)hipEventElapsedTime(&ms[4], c->norm_ev[0], c->norm_ev[last]);
+    float ms[4] = {0, 0, 0, 0};
+    c->norm_stats.total_ms = pass_times(c->norm_ev, last, ms);
     c->norm_stats.class_ms = ms[0];
     c->norm_stats.find_ms = ms[1];
     c->norm_stats.segments_ms = ms[2];
     c->norm_stats.write_ms = ms[3];
-    c->norm_stats.total_ms = ms[4];
 }
 
 int yabpe_normalize(yabpe_ctx *c, const uint8_t *text, uint64_t n_bytes, const uint64_t *part_off, uint32_t n_parts, uint32_t form,
                     const uint8_t **out_dev_text, uint64_t **out_dev_part_off, uint64_t *out_n_bytes, int64_t *out_bad_pos) {
     if (!c || !out_dev_text || !out_dev_part_off || !out_n_bytes || !out_bad_pos) return YABPE_E_INVALID;
     HIPCHK(c, hipSetDevice(c->device));
-    *out_dev_text = nullptr; *out_dev_part_off = nullptr; *out_n_bytes = 0; *out_bad_pos = -1;
+    *out_bad_pos = -1;
+    TextPass tp(c, c->norm_bufs, out_dev_text, out_dev_part_off, out_n_bytes);
     if (form != YABPE_NORM_NFC) return fail(c, YABPE_E_INVALID, "normalisation form %u: only YABPE_NORM_NFC (1) is there", form);
-    if (n_bytes && !text) return fail(c, YABPE_E_INVALID, "text is NULL");
-    std::vector<unsigned long long> parts;
-    if (part_off && n_parts) {
-        for (uint32_t k = 0; k < n_parts; ++k) {
-            if (part_off[k] > n_bytes || (k && part_off[k] < part_off[k - 1])) return fail(c, YABPE_E_INVALID, "part offsets must ascend inside the text");
-            parts.push_back(part_off[k]);
-        }
-        if (parts[0] != 0) return fail(c, YABPE_E_INVALID, "the first part must start at 0");
-    } else {
-        parts.push_back(0);
-    }
-    const uint32_t np = (uint32_t)parts.size();
-    parts.push_back(n_bytes);  // (the offsets of the clean path: the input's, with the end)
+    TRY(tp.check(text, n_bytes, part_off, n_parts));
     NfcTables T{};
     TRY(nfc_tables(c, &T));
-    yabpe_normalize_free(c);
-    c->norm_stats = yabpe_normalize_stats_t{};
-    c->norm_stats.n_bytes_in = n_bytes;
-    c->norm_stats.n_parts = np;
-    for (auto &e : c->norm_ev)
-        if (!e) HIPCHK(c, hipEventCreate(&e));
+    TRY(tp.begin(c->norm_stats, c->norm_ev, 1));
+    if (tp.n == 0) return tp.hand_out_input();
+    Scratch &S = tp.S;
     hipStream_t s = c->stream;
-    const unsigned long long n = n_bytes;
-    Scratch S(c->device, c->rank);
-    const uint8_t *d_text = nullptr;
-    TRY(to_device(c, S, text, n_bytes, 1, &d_text));
-    unsigned long long *d_parts = nullptr;
-    HIPCHK(c, S.get(&d_parts, parts.size()));
-    HIPCHK(c, hipMemcpyAsync(d_parts, parts.data(), parts.size() * 8, hipMemcpyHostToDevice, s));
-    // the result of the clean path (and of an empty text): the input and its offsets
-    auto hand_out_input = [&]() {
-        if (d_text != text && n) c->norm_bufs.push_back(S.take(const_cast<uint8_t *>(d_text)));  // (the staged text is handed out)
-        c->norm_bufs.push_back(S.take(d_parts));
-        *out_dev_text = n ? d_text : nullptr;
-        *out_dev_part_off = (uint64_t *)d_parts;
-        *out_n_bytes = n;
-        c->norm_stats.n_bytes_out = n;
-    };
-    if (n == 0) {
-        HIPCHK(c, hipStreamSynchronize(s));
-        hand_out_input();
-        return YABPE_OK;
-    }
+    const uint8_t *d_text = tp.d_text;
+    unsigned long long *const d_parts = tp.d_parts;
+    const unsigned long long n = tp.n;
+    const uint32_t np = tp.np;
     // ---- class: part marks, UTF-8 check, suspects
     uint8_t *marks = nullptr;
     unsigned long long *ctr = nullptr;  // [0] first malformed byte, [1] suspects, [2] first segment over the cap, [3] long segments, [4] bytes copied
@@ -2955,8 +3004,7 @@ int yabpe_normalize(yabpe_ctx *c, const uint8_t *text, uint64_t n_bytes, const u
     c->norm_stats.n_suspects = h_ctr[1];
     if (h_ctr[1] == 0) {  // the text is NFC
         normalize_times(c, 1);
-        hand_out_input();
-        return YABPE_OK;
+        return tp.hand_out_input();
     }
     // ---- find: the meta bytes, the segment start of every suspect, the list of dirty segments
     uint8_t *meta = nullptr, *flags = nullptr;
@@ -3038,20 +3086,13 @@ int yabpe_normalize(yabpe_ctx *c, const uint8_t *text, uint64_t n_bytes, const u
     HIPCHK(c, hipStreamSynchronize(s));
     normalize_times(c, 4);
     c->norm_stats.n_copied = h_ctr[4];
-    c->norm_stats.n_bytes_out = n_out;
-    c->norm_bufs.push_back(S.take(out));
-    c->norm_bufs.push_back(S.take(out_off));
-    *out_dev_text = out;
-    *out_dev_part_off = (uint64_t *)out_off;
-    *out_n_bytes = n_out;
-    return YABPE_OK;
+    return tp.hand_out(out, out_off, n_out);
 }
 
 // ---------------------------------------------------------------------------------------------- invalid UTF-8
 int yabpe_utf8_repair_free(yabpe_ctx *c) {
     if (!c) return YABPE_E_INVALID;
-    for (void *p : c->utf8_bufs) dfree(p);
-    c->utf8_bufs.clear();
+    free_bufs(c->utf8_bufs);
     return YABPE_OK;
 }
 
@@ -3063,63 +3104,29 @@ int yabpe_utf8_repair_stats(yabpe_ctx *c, yabpe_utf8_stats_t *out) {
 
 // utf8_ev[0..1] around the check pass, [1..2] the scan and the write pass
 static void utf8_times(yabpe_ctx *c, int last) {
-    float ms[3] = {0, 0, 0};
-    for (int k = 0; k < last; ++k) (void)hipEventElapsedTime(&ms[k], c->utf8_ev[k], c->utf8_ev[k + 1]);
-    (void)hipEventElapsedTime(&ms[2], c->utf8_ev[0], c->utf8_ev[last]);
+    float ms[2] = {0, 0};
+    c->utf8_stats.total_ms = pass_times(c->utf8_ev, last, ms);
     c->utf8_stats.check_ms = ms[0];
     c->utf8_stats.write_ms = ms[1];
-    c->utf8_stats.total_ms = ms[2];
 }
 
 int yabpe_utf8_repair(yabpe_ctx *c, const uint8_t *text, uint64_t n_bytes, const uint64_t *part_off, uint32_t n_parts, uint32_t mode,
                       const uint8_t **out_dev_text, uint64_t **out_dev_part_off, uint64_t *out_n_bytes) {
     if (!c || !out_dev_text || !out_dev_part_off || !out_n_bytes) return YABPE_E_INVALID;
     HIPCHK(c, hipSetDevice(c->device));
-    *out_dev_text = nullptr; *out_dev_part_off = nullptr; *out_n_bytes = 0;
+    TextPass tp(c, c->utf8_bufs, out_dev_text, out_dev_part_off, out_n_bytes);
     if (mode != YABPE_UTF8_REPLACE && mode != YABPE_UTF8_IGNORE)
         return fail(c, YABPE_E_INVALID, "utf8 mode %u: YABPE_UTF8_REPLACE (1) or YABPE_UTF8_IGNORE (2)", mode);
-    if (n_bytes && !text) return fail(c, YABPE_E_INVALID, "text is NULL");
-    std::vector<unsigned long long> parts;
-    if (part_off && n_parts) {
-        for (uint32_t k = 0; k < n_parts; ++k) {
-            if (part_off[k] > n_bytes || (k && part_off[k] < part_off[k - 1])) return fail(c, YABPE_E_INVALID, "part offsets must ascend inside the text");
-            parts.push_back(part_off[k]);
-        }
-        if (parts[0] != 0) return fail(c, YABPE_E_INVALID, "the first part must start at 0");
-    } else {
-        parts.push_back(0);
-    }
-    const uint32_t np = (uint32_t)parts.size();
-    parts.push_back(n_bytes);  // (the offsets of the valid path: the input's, with the end)
-    yabpe_utf8_repair_free(c);
-    c->utf8_stats = yabpe_utf8_stats_t{};
-    c->utf8_stats.n_bytes_in = n_bytes;
-    c->utf8_stats.n_parts = np;
+    TRY(tp.check(text, n_bytes, part_off, n_parts));
+    TRY(tp.begin(c->utf8_stats, c->utf8_ev, 1));
     c->utf8_stats.first_bad_pos = -1;
-    for (auto &e : c->utf8_ev)
-        if (!e) HIPCHK(c, hipEventCreate(&e));
+    if (tp.n == 0) return tp.hand_out_input();
+    Scratch &S = tp.S;
     hipStream_t s = c->stream;
-    const unsigned long long n = n_bytes;
-    Scratch S(c->device, c->rank);
-    const uint8_t *d_text = nullptr;
-    TRY(to_device(c, S, text, n_bytes, 1, &d_text));
-    unsigned long long *d_parts = nullptr;
-    HIPCHK(c, S.get(&d_parts, parts.size()));
-    HIPCHK(c, hipMemcpyAsync(d_parts, parts.data(), parts.size() * 8, hipMemcpyHostToDevice, s));
-    // the result of the valid path (and of an empty text): the input and its offsets
-    auto hand_out_input = [&]() {
-        if (d_text != text && n) c->utf8_bufs.push_back(S.take(const_cast<uint8_t *>(d_text)));  // (the staged text is handed out)
-        c->utf8_bufs.push_back(S.take(d_parts));
-        *out_dev_text = n ? d_text : nullptr;
-        *out_dev_part_off = (uint64_t *)d_parts;
-        *out_n_bytes = n;
-        c->utf8_stats.n_bytes_out = n;
-    };
-    if (n == 0) {
-        HIPCHK(c, hipStreamSynchronize(s));
-        hand_out_input();
-        return YABPE_OK;
-    }
+    const uint8_t *d_text = tp.d_text;
+    unsigned long long *const d_parts = tp.d_parts;
+    const unsigned long long n = tp.n;
+    const uint32_t np = tp.np;
     // ---- check: the charge of every byte, per tile the output bytes and the subparts
     const unsigned long long nt = (n + U8_TILE - 1) / U8_TILE;
     if (nt > 0x7FFFFFFFull) return fail(c, YABPE_E_CAPACITY, "utf8: %llu bytes are more tiles than one launch takes", n);
@@ -3141,8 +3148,7 @@ int yabpe_utf8_repair(yabpe_ctx *c, const uint8_t *text, uint64_t n_bytes, const
     c->utf8_stats.n_subparts = h_ctr[1];
     if (h_ctr[1] == 0) {  // the text is valid UTF-8, part by part
         utf8_times(c, 1);
-        hand_out_input();
-        return YABPE_OK;
+        return tp.hand_out_input();
     }
     c->utf8_stats.first_bad_pos = (int64_t)h_ctr[0];
     // ---- write: every tile at its base, the part offsets with it
@@ -3163,13 +3169,7 @@ int yabpe_utf8_repair(yabpe_ctx *c, const uint8_t *text, uint64_t n_bytes, const
     HIPCHK(c, hipEventRecord(c->utf8_ev[2], s));
     HIPCHK(c, hipStreamSynchronize(s));
     utf8_times(c, 2);
-    c->utf8_stats.n_bytes_out = n_out;
-    c->utf8_bufs.push_back(S.take(out));
-    c->utf8_bufs.push_back(S.take(out_off));
-    *out_dev_text = out;
-    *out_dev_part_off = (uint64_t *)out_off;
-    *out_n_bytes = n_out;
-    return YABPE_OK;
+    return tp.hand_out(out, out_off, n_out);
 }
 
 // ---------------------------------------------------------------------------------------------- lower-casing
@@ -3191,8 +3191,7 @@ static int case_tables(yabpe_ctx *c, CaseTables *T) {
 
 int yabpe_lowercase_free(yabpe_ctx *c) {
     if (!c) return YABPE_E_INVALID;
-    for (void *p : c->case_bufs) dfree(p);
-    c->case_bufs.clear();
+    free_bufs(c->case_bufs);
     return YABPE_OK;
 }
 
@@ -3204,63 +3203,30 @@ int yabpe_lowercase_stats(yabpe_ctx *c, yabpe_lowercase_stats_t *out) {
 
 // case_ev[0..1] around the check pass, [1..2] the scans, [2..3] the write pass (path 1: [1..2] the write pass)
 static void lowercase_times(yabpe_ctx *c, int last) {
-    float ms[4] = {0, 0, 0, 0};
-    for (int k = 0; k < last; ++k) (void)hipEventElapsedTime(&ms[k], c->case_ev[k], c->case_ev[k + 1]);
-    (void)hipEventElapsedTime(&ms[3], c->case_ev[0], c->case_ev[last]);
+    float ms[3] = {0, 0, 0};
+    c->case_stats.total_ms = pass_times(c->case_ev, last, ms);
     c->case_stats.check_ms = ms[0];
     c->case_stats.scan_ms = last == 3 ? ms[1] : 0.0;
     c->case_stats.write_ms = last == 3 ? ms[2] : ms[1];
-    c->case_stats.total_ms = ms[3];
 }
 
 int yabpe_lowercase(yabpe_ctx *c, const uint8_t *text, uint64_t n_bytes, const uint64_t *part_off, uint32_t n_parts,
                     const uint8_t **out_dev_text, uint64_t **out_dev_part_off, uint64_t *out_n_bytes, int64_t *out_bad_pos) {
     if (!c || !out_dev_text || !out_dev_part_off || !out_n_bytes || !out_bad_pos) return YABPE_E_INVALID;
     HIPCHK(c, hipSetDevice(c->device));
-    *out_dev_text = nullptr; *out_dev_part_off = nullptr; *out_n_bytes = 0; *out_bad_pos = -1;
-    if (n_bytes && !text) return fail(c, YABPE_E_INVALID, "text is NULL");
-    std::vector<unsigned long long> parts;
-    if (part_off && n_parts) {
-        for (uint32_t k = 0; k < n_parts; ++k) {
-            if (part_off[k] > n_bytes || (k && part_off[k] < part_off[k - 1])) return fail(c, YABPE_E_INVALID, "part offsets must ascend inside the text");
-            parts.push_back(part_off[k]);
-        }
-        if (parts[0] != 0) return fail(c, YABPE_E_INVALID, "the first part must start at 0");
-    } else {
-        parts.push_back(0);
-    }
-    const uint32_t np = (uint32_t)parts.size();
-    parts.push_back(n_bytes);  // (the offsets of paths 0 and 1: the input's, with the end)
+    *out_bad_pos = -1;
+    TextPass tp(c, c->case_bufs, out_dev_text, out_dev_part_off, out_n_bytes);
+    TRY(tp.check(text, n_bytes, part_off, n_parts));
     CaseTables T{};
     TRY(case_tables(c, &T));
-    yabpe_lowercase_free(c);
-    c->case_stats = yabpe_lowercase_stats_t{};
-    c->case_stats.n_bytes_in = n_bytes;
-    c->case_stats.n_parts = np;
-    for (auto &e : c->case_ev)
-        if (!e) HIPCHK(c, hipEventCreate(&e));
+    TRY(tp.begin(c->case_stats, c->case_ev, 16));
+    if (tp.n == 0) return tp.hand_out_input();
+    Scratch &S = tp.S;
     hipStream_t s = c->stream;
-    const unsigned long long n = n_bytes;
-    Scratch S(c->device, c->rank);
-    const uint8_t *d_text = nullptr;
-    TRY(to_device(c, S, text, n_bytes, 16, &d_text));
-    unsigned long long *d_parts = nullptr;
-    HIPCHK(c, S.get(&d_parts, parts.size()));
-    HIPCHK(c, hipMemcpyAsync(d_parts, parts.data(), parts.size() * 8, hipMemcpyHostToDevice, s));
-    // the result of path 0 (and of an empty text): the input and its offsets
-    auto hand_out_input = [&]() {
-        if (d_text != text && n) c->case_bufs.push_back(S.take(const_cast<uint8_t *>(d_text)));  // (the staged text is handed out)
-        c->case_bufs.push_back(S.take(d_parts));
-        *out_dev_text = n ? d_text : nullptr;
-        *out_dev_part_off = (uint64_t *)d_parts;
-        *out_n_bytes = n;
-        c->case_stats.n_bytes_out = n;
-    };
-    if (n == 0) {
-        HIPCHK(c, hipStreamSynchronize(s));
-        hand_out_input();
-        return YABPE_OK;
-    }
+    const uint8_t *d_text = tp.d_text;
+    unsigned long long *const d_parts = tp.d_parts;
+    const unsigned long long n = tp.n;
+    const uint32_t np = tp.np;
     // ---- check: part marks, UTF-8, what changes, the bytes every window writes
     const unsigned long long n_win = (n + CASE_WIN - 1) / CASE_WIN;
     const dim3 wgrid((uint32_t)std::min<unsigned long long>(n_win, (unsigned long long)c->n_cu * 16));  // (a few atomics per workgroup)
@@ -3295,8 +3261,7 @@ int yabpe_lowercase(yabpe_ctx *c, const uint8_t *text, uint64_t n_bytes, const u
     c->case_stats.n_sigma = h_ctr[3];
     if (h_ctr[1] == 0) {  // the text is lower case
         lowercase_times(c, 1);
-        hand_out_input();
-        return YABPE_OK;
+        return tp.hand_out_input();
     }
     if (h_ctr[2] == 0 && h_ctr[3] == 0) {  // ---- same size
         uint8_t *out = nullptr;
@@ -3310,13 +3275,7 @@ int yabpe_lowercase(yabpe_ctx *c, const uint8_t *text, uint64_t n_bytes, const u
         lowercase_times(c, 2);
         c->case_stats.path = 1;
         c->case_stats.n_copied = n;
-        c->case_stats.n_bytes_out = n;
-        c->case_bufs.push_back(S.take(out));
-        c->case_bufs.push_back(S.take(d_parts));
-        *out_dev_text = out;
-        *out_dev_part_off = (uint64_t *)d_parts;
-        *out_n_bytes = n;
-        return YABPE_OK;
+        return tp.hand_out(out, d_parts, n);  // (the input's offsets)
     }
     // ---- general: the final sigmas, the base of every window
     uint16_t *fin = nullptr;
@@ -3347,13 +3306,7 @@ int yabpe_lowercase(yabpe_ctx *c, const uint8_t *text, uint64_t n_bytes, const u
     c->case_stats.path = 2;
     c->case_stats.n_final_sigma = h_ctr[4];
     c->case_stats.n_copied = n_out;
-    c->case_stats.n_bytes_out = n_out;
-    c->case_bufs.push_back(S.take(out));
-    c->case_bufs.push_back(S.take(out_off));
-    *out_dev_text = out;
-    *out_dev_part_off = (uint64_t *)out_off;
-    *out_n_bytes = n_out;
-    return YABPE_OK;
+    return tp.hand_out(out, out_off, n_out);
 }
 
 // ---------------------------------------------------------------------------------------------- word pool

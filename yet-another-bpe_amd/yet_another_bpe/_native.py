@@ -240,6 +240,24 @@ LAYOUT_NO_DOC = 0xFFFFFFFF  # `doc` of a packed slot past the end of the stream
 PAIRS_MODES = {"longest_first": 0, "only_first": 1, "only_second": 2, "windows": 3}  # yabpe_pairs_t.mode (YABPE_PAIRS_*)
 
 
+def _text_arg(text, n_bytes):
+    """A text argument -- bytes / u8 array (the library stages it) or a device address (then n_bytes is required) -> (the array
+    that must outlive the call or None, pointer, length)"""
+    if isinstance(text, int):
+        return None, c_void_p(text), int(n_bytes)
+    keep = np.frombuffer(text, dtype=np.uint8) if not isinstance(text, np.ndarray) else np.ascontiguousarray(text, dtype=np.uint8)
+    return keep, c_void_p(keep.ctypes.data if keep.size else 0), int(keep.size)
+
+
+def _starts_arg(starts) -> np.ndarray:
+    """Ascending chunk / part / document starts as the u64 table a driver takes (None or empty: one, at 0)"""
+    return np.ascontiguousarray(starts if starts is not None and len(starts) else [0], dtype=np.uint64)
+
+
+def _stats_dict(s: ctypes.Structure) -> dict:
+    return {f: getattr(s, f) for f, _ in s._fields_}
+
+
 class Context:
     """One GPU context == one merge-loop run (or several yabpe_train continuations)."""
 
@@ -329,7 +347,7 @@ class Context:
     def resume_stats(self) -> dict:
         s = ResumeStats()
         self._chk(lib().yabpe_resume_stats(self._h, byref(s)))
-        return {f: getattr(s, f) for f, _ in ResumeStats._fields_}
+        return _stats_dict(s)
 
     def train(self, num_merges: int, min_frequency: int):
         left = np.zeros(max(num_merges, 1), dtype=np.uint32)
@@ -357,7 +375,7 @@ class Context:
     def stats(self) -> dict:
         s = Stats()
         self._chk(lib().yabpe_stats(self._h, byref(s)))
-        return {f: getattr(s, f) for f, _ in Stats._fields_}
+        return _stats_dict(s)
 
     def iter_log(self):
         n = c_uint32(0)
@@ -380,7 +398,7 @@ class Context:
         """Measured latency pieces of one sparse merge on this device (include/yabpe.h yabpe_latency_t), microseconds."""
         s = Latency()
         self._chk(lib().yabpe_latency_probe(self._h, byref(s)))
-        return {f: getattr(s, f) for f, _ in Latency._fields_}
+        return _stats_dict(s)
 
     def verify_table(self) -> int:
         m = c_uint64(0)
@@ -432,13 +450,8 @@ class Context:
         runs are cut into groups of G, with the option "split_pattern" = 1 the cl100k pattern is used, with 3 the o200k_base pattern, include/yabpe.h).  `text`: bytes / u8 array (staged) or a
         device address (then n_bytes is required).  chunk_starts: ascending chunk starts, first one 0.
         -> (dev_text_ptr, dev_word_off_ptr, n_words); raises Utf8Error(position) on malformed UTF-8."""
-        keep = None
-        if isinstance(text, int):
-            ptr, n = c_void_p(text), int(n_bytes)
-        else:
-            keep = np.frombuffer(text, dtype=np.uint8) if not isinstance(text, np.ndarray) else np.ascontiguousarray(text, dtype=np.uint8)
-            ptr, n = c_void_p(keep.ctypes.data if keep.size else 0), int(keep.size)
-        ch = np.ascontiguousarray(chunk_starts if chunk_starts is not None and len(chunk_starts) else [0], dtype=np.uint64)
+        _keep, ptr, n = _text_arg(text, n_bytes)
+        ch = _starts_arg(chunk_starts)
         sb = [t.encode("utf-8") if isinstance(t, str) else bytes(t) for t in special_tokens]
         spb = np.frombuffer(b"".join(sb) or b"\0", dtype=np.uint8)
         spo = np.zeros(len(sb) + 1, dtype=np.uint32)
@@ -455,6 +468,11 @@ class Context:
     def pretokenize_free(self) -> None:
         self._chk(lib().yabpe_pretokenize_free(self._h))
 
+    # -- the text passes in front of pretokenize() / encode(): text in, text and part offsets out
+    def _pass_to_host(self, dt: int, do: int, nb: int, n_parts: int):
+        """A pass's device results -> (text u8[nb], part_off u64[n_parts + 1]) copied to the host."""
+        return (self.d2h(dt, nb) if nb else np.zeros(0, np.uint8)), self.d2h(do, 8 * (n_parts + 1), np.uint64)
+
     # -- Unicode normalisation in front of pretokenize() / encode() (include/yabpe.h: yabpe_normalize)
     def normalize(self, text, n_bytes: int | None = None, part_starts=None, form: int = NORM_NFC):
         """NFC of every part of `text` on the device.  `text`: bytes / u8 array (staged) or a device address (then n_bytes is
@@ -462,13 +480,8 @@ class Context:
         -> (dev_text_ptr, dev_part_off_ptr u64[n_parts + 1], n_bytes_out); the buffers live until the next normalize,
         normalize_free() or close().  A text that is NFC already comes back as it is (a device address: the same address).
         Raises Utf8Error(position) on malformed UTF-8 and SegmentTooLong(position) over the cap, positions in the input."""
-        keep = None
-        if isinstance(text, int):
-            ptr, n = c_void_p(text), int(n_bytes)
-        else:
-            keep = np.frombuffer(text, dtype=np.uint8) if not isinstance(text, np.ndarray) else np.ascontiguousarray(text, dtype=np.uint8)
-            ptr, n = c_void_p(keep.ctypes.data if keep.size else 0), int(keep.size)
-        st = np.ascontiguousarray(part_starts if part_starts is not None and len(part_starts) else [0], dtype=np.uint64)
+        _keep, ptr, n = _text_arg(text, n_bytes)
+        st = _starts_arg(part_starts)
         dt, do, nb, bad = c_void_p(), c_void_p(), c_uint64(0), ctypes.c_int64(-1)
         rc = lib().yabpe_normalize(self._h, ptr, n, st.ctypes.data, len(st), int(form), byref(dt), byref(do), byref(nb), byref(bad))
         if rc == E_UTF8:
@@ -480,9 +493,7 @@ class Context:
 
     def normalize_to_host(self, text, n_bytes: int | None = None, part_starts=None, form: int = NORM_NFC):
         """-> (text u8[n_bytes_out], part_off u64[n_parts + 1]) copied to the host."""
-        n_parts = len(part_starts) if part_starts is not None and len(part_starts) else 1
-        dt, do, nb = self.normalize(text, n_bytes, part_starts, form)
-        return (self.d2h(dt, nb) if nb else np.zeros(0, np.uint8)), self.d2h(do, 8 * (n_parts + 1), np.uint64)
+        return self._pass_to_host(*self.normalize(text, n_bytes, part_starts, form), len(_starts_arg(part_starts)))
 
     def normalize_free(self) -> None:
         self._chk(lib().yabpe_normalize_free(self._h))
@@ -490,7 +501,7 @@ class Context:
     def normalize_stats(self) -> dict:
         s = NormalizeStats()
         self._chk(lib().yabpe_normalize_stats(self._h, byref(s)))
-        return {f: getattr(s, f) for f, _ in NormalizeStats._fields_}
+        return _stats_dict(s)
 
     # -- errors="replace" / "ignore" in front of normalize() / pretokenize() / encode() (include/yabpe.h: yabpe_utf8_repair)
     def utf8_repair(self, text, n_bytes: int | None = None, part_starts=None, mode: int = UTF8_MODES["replace"]):
@@ -499,22 +510,15 @@ class Context:
         sequence cut off by a part's end is ill-formed there.  mode: UTF8_MODES["replace"] or ["ignore"].
         -> (dev_text_ptr, dev_part_off_ptr u64[n_parts + 1], n_bytes_out); the buffers live until the next utf8_repair,
         utf8_repair_free() or close().  A text that is valid comes back as it is (a device address: the same address)."""
-        keep = None
-        if isinstance(text, int):
-            ptr, n = c_void_p(text), int(n_bytes)
-        else:
-            keep = np.frombuffer(text, dtype=np.uint8) if not isinstance(text, np.ndarray) else np.ascontiguousarray(text, dtype=np.uint8)
-            ptr, n = c_void_p(keep.ctypes.data if keep.size else 0), int(keep.size)
-        st = np.ascontiguousarray(part_starts if part_starts is not None and len(part_starts) else [0], dtype=np.uint64)
+        _keep, ptr, n = _text_arg(text, n_bytes)
+        st = _starts_arg(part_starts)
         dt, do, nb = c_void_p(), c_void_p(), c_uint64(0)
         self._chk(lib().yabpe_utf8_repair(self._h, ptr, n, st.ctypes.data, len(st), int(mode), byref(dt), byref(do), byref(nb)))
         return dt.value or 0, do.value, nb.value
 
     def utf8_repair_to_host(self, text, n_bytes: int | None = None, part_starts=None, mode: int = UTF8_MODES["replace"]):
         """-> (text u8[n_bytes_out], part_off u64[n_parts + 1]) copied to the host."""
-        n_parts = len(part_starts) if part_starts is not None and len(part_starts) else 1
-        dt, do, nb = self.utf8_repair(text, n_bytes, part_starts, mode)
-        return (self.d2h(dt, nb) if nb else np.zeros(0, np.uint8)), self.d2h(do, 8 * (n_parts + 1), np.uint64)
+        return self._pass_to_host(*self.utf8_repair(text, n_bytes, part_starts, mode), len(_starts_arg(part_starts)))
 
     def utf8_repair_free(self) -> None:
         self._chk(lib().yabpe_utf8_repair_free(self._h))
@@ -522,7 +526,7 @@ class Context:
     def utf8_repair_stats(self) -> dict:
         s = Utf8Stats()
         self._chk(lib().yabpe_utf8_repair_stats(self._h, byref(s)))
-        return {f: getattr(s, f) for f, _ in Utf8Stats._fields_}
+        return _stats_dict(s)
 
     # -- str.lower() between utf8_repair() and normalize() (include/yabpe.h: yabpe_lowercase)
     def lowercase(self, text, n_bytes: int | None = None, part_starts=None):
@@ -532,13 +536,8 @@ class Context:
         -> (dev_text_ptr, dev_part_off_ptr u64[n_parts + 1], n_bytes_out); the buffers live until the next lowercase,
         lowercase_free() or close().  A text that is lower case already comes back as it is (a 16-byte aligned device
         address: the same address).  Raises Utf8Error(position) on malformed UTF-8, the position in the input."""
-        keep = None
-        if isinstance(text, int):
-            ptr, n = c_void_p(text), int(n_bytes)
-        else:
-            keep = np.frombuffer(text, dtype=np.uint8) if not isinstance(text, np.ndarray) else np.ascontiguousarray(text, dtype=np.uint8)
-            ptr, n = c_void_p(keep.ctypes.data if keep.size else 0), int(keep.size)
-        st = np.ascontiguousarray(part_starts if part_starts is not None and len(part_starts) else [0], dtype=np.uint64)
+        _keep, ptr, n = _text_arg(text, n_bytes)
+        st = _starts_arg(part_starts)
         dt, do, nb, bad = c_void_p(), c_void_p(), c_uint64(0), ctypes.c_int64(-1)
         rc = lib().yabpe_lowercase(self._h, ptr, n, st.ctypes.data, len(st), byref(dt), byref(do), byref(nb), byref(bad))
         if rc == E_UTF8:
@@ -548,9 +547,7 @@ class Context:
 
     def lowercase_to_host(self, text, n_bytes: int | None = None, part_starts=None):
         """-> (text u8[n_bytes_out], part_off u64[n_parts + 1]) copied to the host."""
-        n_parts = len(part_starts) if part_starts is not None and len(part_starts) else 1
-        dt, do, nb = self.lowercase(text, n_bytes, part_starts)
-        return (self.d2h(dt, nb) if nb else np.zeros(0, np.uint8)), self.d2h(do, 8 * (n_parts + 1), np.uint64)
+        return self._pass_to_host(*self.lowercase(text, n_bytes, part_starts), len(_starts_arg(part_starts)))
 
     def lowercase_free(self) -> None:
         self._chk(lib().yabpe_lowercase_free(self._h))
@@ -558,7 +555,7 @@ class Context:
     def lowercase_stats(self) -> dict:
         s = LowercaseStats()
         self._chk(lib().yabpe_lowercase_stats(self._h, byref(s)))
-        return {f: getattr(s, f) for f, _ in LowercaseStats._fields_}
+        return _stats_dict(s)
 
     # -- encoding with a trained model (BBPETokenizer.encode on the device)
     def encode_set_model(self, vocab: dict, merges, specials_ordered, unk_id: int) -> None:
@@ -572,13 +569,8 @@ class Context:
     def _encode_call(self, text, n_bytes, doc_starts, flags, dropout=None):
         """yabpe_encode (flags None), yabpe_encode_spans or yabpe_encode_dropout (dropout = (threshold, seed))
         -> (dev ids, dev doc_off, dev spans or None, n_ids)"""
-        keep = None
-        if isinstance(text, int):
-            ptr, n = c_void_p(text), int(n_bytes)
-        else:
-            keep = np.frombuffer(text, dtype=np.uint8) if not isinstance(text, np.ndarray) else np.ascontiguousarray(text, dtype=np.uint8)
-            ptr, n = c_void_p(keep.ctypes.data if keep.size else 0), int(keep.size)
-        docs = np.ascontiguousarray(doc_starts if doc_starts is not None and len(doc_starts) else [0], dtype=np.uint64)
+        _keep, ptr, n = _text_arg(text, n_bytes)
+        docs = _starts_arg(doc_starts)
         di, dd, ds, ni, bad = c_void_p(), c_void_p(), c_void_p(), c_uint64(0), ctypes.c_int64(-1)
         if dropout is not None:
             rc = lib().yabpe_encode_dropout(self._h, ptr, n, docs.ctypes.data, len(docs), int(dropout[0]), int(dropout[1]), byref(di), byref(dd),
@@ -639,7 +631,7 @@ class Context:
     def encode_stats(self) -> dict:
         s = EncodeStats()
         self._chk(lib().yabpe_encode_stats(self._h, byref(s)))
-        return {f: getattr(s, f) for f, _ in EncodeStats._fields_}
+        return _stats_dict(s)
 
     def encode_checksum(self) -> tuple[int, int, int]:
         a, b, c = c_uint64(0), c_uint64(0), c_uint64(0)
@@ -666,7 +658,7 @@ class Context:
         if isinstance(doc_starts, int):
             dptr, nd = c_void_p(doc_starts), int(n_docs)
         else:
-            docs = np.ascontiguousarray(doc_starts if doc_starts is not None and len(doc_starts) else [0], dtype=np.uint64)
+            docs = _starts_arg(doc_starts)
             dptr, nd = c_void_p(docs.ctypes.data), len(docs)
         dt, do, nb = c_void_p(), c_void_p(), c_uint64(0)
         self._chk(lib().yabpe_decode(self._h, ptr, n, dptr, nd, byref(dt), byref(do), byref(nb)))
@@ -686,7 +678,7 @@ class Context:
     def decode_stats(self) -> dict:
         s = DecodeStats()
         self._chk(lib().yabpe_decode_stats(self._h, byref(s)))
-        return {f: getattr(s, f) for f, _ in DecodeStats._fields_}
+        return _stats_dict(s)
 
     # -- fixed-shape batches (BBPETokenizer.encode_batch_padded / encode_batch_packed / encode_batch_windows on the device)
     @staticmethod
@@ -701,7 +693,7 @@ class Context:
         if isinstance(doc_starts, int):
             dptr, nd = c_void_p(doc_starts), int(n_docs)
         else:
-            docs = np.ascontiguousarray(doc_starts if doc_starts is not None and len(doc_starts) else [0], dtype=np.uint64)
+            docs = _starts_arg(doc_starts)
             dptr, nd = c_void_p(docs.ctypes.data), len(docs)
         flags = int(flags) | (LAYOUT_BOS if bos_id is not None else 0) | (LAYOUT_EOS if eos_id is not None else 0)
         return (keep, docs), ptr, n, dptr, nd, Layout(int(row_len), int(pad_id), int(bos_id or 0), int(eos_id or 0), flags)
@@ -821,7 +813,7 @@ class Context:
     def layout_stats(self) -> dict:
         s = LayoutStats()
         self._chk(lib().yabpe_layout_stats(self._h, byref(s)))
-        return {f: getattr(s, f) for f, _ in LayoutStats._fields_}
+        return _stats_dict(s)
 
     # -- the persistent word pool (corpora larger than device memory: words go in call by call, the merge loop loads the pool)
     def pool_add(self, flat, off, freq=None) -> None:
@@ -866,7 +858,7 @@ class Context:
     def pool_stats(self) -> dict:
         s = PoolStats()
         self._chk(lib().yabpe_pool_stats(self._h, byref(s)))
-        return {f: getattr(s, f) for f, _ in PoolStats._fields_}
+        return _stats_dict(s)
 
     def h2d(self, dev_ptr: int, arr: np.ndarray) -> None:
         arr = np.ascontiguousarray(arr)

@@ -149,33 +149,13 @@ def plan_chunk_shards(sizes: Sequence[int], world: int) -> list[tuple[int, int]]
 
 
 def _pretokenize_my_chunks(ctx, text, n_bytes, starts, config):
-    """This rank's chunks -> (device text, device word offsets, n_words): with config.errors = "replace" / "ignore"
-    yabpe_utf8_repair, then with config.lowercase yabpe_lowercase, then with config.normalizer yabpe_normalize run in front of
-    yabpe_pretokenize (chunk by chunk; their texts stay the context's), as BBPETrainer._device_words does it.  A
-    _native.SegmentTooLong carries .read_starts (the chunks' starts in the text the normaliser read: repaired and lowered, so
-    not the starts that came in) and .repaired (whether a repair ran in front of it)."""
-    from . import _native
-    from .trainer import check_errors, check_lowercase, check_normalizer
+    """This rank's chunks -> (device text, device word offsets, n_words): trainer.device_text_front with the config's
+    settings, chunk by chunk, in front of yabpe_pretokenize, as BBPETrainer._device_words does it."""
+    from .trainer import check_errors, check_lowercase, check_normalizer, device_text_front
 
-    form = check_normalizer(getattr(config, "normalizer", None))
-    repair = check_errors(getattr(config, "errors", "strict"))
-    lower = check_lowercase(getattr(config, "lowercase", False))
-    n_chunks = len(starts)
-    if repair:
-        text, dev_starts, n_bytes = ctx.utf8_repair(text, n_bytes=n_bytes, part_starts=starts, mode=repair)
-        starts = ctx.d2h(dev_starts, 8 * n_chunks, np.uint64)
-    if lower and (n_bytes is None or n_bytes):
-        text, dev_starts, n_bytes = ctx.lowercase(text, n_bytes=n_bytes, part_starts=starts)
-        starts = ctx.d2h(dev_starts, 8 * n_chunks, np.uint64)
-    if form and (n_bytes is None or n_bytes):
-        try:
-            text, dev_starts, n_bytes = ctx.normalize(text, n_bytes=n_bytes, part_starts=starts, form=form)
-        except _native.SegmentTooLong as e:
-            e.read_starts, e.repaired = [int(s0) for s0 in starts], bool(repair)
-            raise
-        starts = ctx.d2h(dev_starts, 8 * n_chunks, np.uint64)
-    if n_bytes == 0:  # (every byte was dropped: no words)
-        text, n_bytes = np.zeros(0, np.uint8), None
+    text, n_bytes, starts = device_text_front(ctx, text, n_bytes, starts, form=check_normalizer(getattr(config, "normalizer", None)),
+                                              repair=check_errors(getattr(config, "errors", "strict")),
+                                              lower=check_lowercase(getattr(config, "lowercase", False)))
     return ctx.pretokenize(text, n_bytes=n_bytes, chunk_starts=starts, special_tokens=list(config.special_tokens))
 
 

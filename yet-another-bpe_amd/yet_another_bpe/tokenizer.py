@@ -27,7 +27,7 @@ import regex
 from .synth import rnd_int
 from .trainer import (CL100K_DIGIT_GROUP, NORMALIZERS, PRETOKENIZER_NAMES, BBPETrainerConfig, check_digit_group, check_errors,
                       check_lowercase, check_lowercase_specials, check_normalized_specials, check_normalizer, check_pretokenizer, device_options,
-                      lowercase_text, normalize_text, read_lowercase, read_normalizer, read_pretokenizer, split_pattern)
+                      device_text_front, lowercase_text, normalize_text, read_lowercase, read_normalizer, read_pretokenizer, split_pattern)
 
 _WORD_CACHE = 8192
 
@@ -609,23 +609,11 @@ class BBPETokenizer:
         return b"".join(blobs), starts
 
     def _device_text(self, ctx, inp, errors: str = "strict"):
-        """What the encode calls of ctx take as (text, n_bytes, doc_starts) for _device_input's buffer: the buffer itself, or with
-        errors = "replace" / "ignore" the repaired text (yabpe_utf8_repair; the context's until its next repair), or with
-        lowercase the lowered text made from either (yabpe_lowercase; the context's until its next lowercase), or with a
-        normaliser the normalised text made from either (yabpe_normalize; the context's until its next normalize), in device
-        memory, and the documents' starts in it."""
-        text, n_bytes, starts = np.frombuffer(inp[0], dtype=np.uint8), None, inp[1]
-        repair, form = check_errors(errors), check_normalizer(self._normalizer)
-        if repair and text.size:
-            text, dev_starts, n_bytes = ctx.utf8_repair(text, part_starts=starts, mode=repair)
-            starts = ctx.d2h(dev_starts, 8 * len(inp[1]), np.uint64)
-        if self._lowercase and (text.size if n_bytes is None else n_bytes):
-            text, dev_starts, n_bytes = ctx.lowercase(text, n_bytes=n_bytes, part_starts=starts)
-            starts = ctx.d2h(dev_starts, 8 * len(inp[1]), np.uint64)
-        if form and (text.size if n_bytes is None else n_bytes):
-            text, dev_starts, n_bytes = ctx.normalize(text, n_bytes=n_bytes, part_starts=starts, form=form)
-            starts = ctx.d2h(dev_starts, 8 * len(inp[1]), np.uint64)
-        return (np.zeros(0, np.uint8), None, starts) if n_bytes == 0 else (text, n_bytes, starts)
+        """What the encode calls of ctx take as (text, n_bytes, doc_starts) for _device_input's buffer: the buffer itself, or what
+        trainer.device_text_front makes of it, document by document, with errors = "replace" / "ignore", lowercase and the
+        normaliser."""
+        return device_text_front(ctx, np.frombuffer(inp[0], dtype=np.uint8), None, inp[1], repair=check_errors(errors),
+                                 lower=self._lowercase, form=check_normalizer(self._normalizer))
 
     def normalize_array(self, texts, *, errors: str = "strict") -> tuple[np.ndarray, np.ndarray]:
         """normalize() of every document on the GPU: `texts` as encode_array takes them -> (text np.uint8[n], text_off

@@ -20,7 +20,8 @@ One route from the corpus to the loaded words, for `train` and `train_from` alik
 or batched, `_device_words` reads file chunks `(path, start, stop)` with `read_chunks` and names the file of an invalid byte
 with `utf8_error`, `_run` is the one tail (vocabulary, load -- the resumed load for a continued model --, merge loop, stats).
 `device_options` is the one place a config field becomes an option of the library; the sharded drivers (distributed.py) and
-BBPETokenizer's device context take theirs from it too.
+BBPETokenizer's device context take theirs from it too.  `device_text_front` is the one chain of text passes in front of the
+pre-tokeniser and the encoders (errors=, lowercase, normalizer): `_device_words`, the sharded driver and BBPETokenizer call it.
 """
 from __future__ import annotations
 
@@ -168,6 +169,38 @@ def check_lowercase_specials(tokens: Sequence[str], flag) -> None:
 def lowercase_text(text: str, flag) -> str:
     """THE host-side lower-casing: `text` as the setting leaves it (False: as it is).  It runs before normalize_text."""
     return text.lower() if flag else text
+
+
+def device_text_front(ctx, text, n_bytes, starts, *, repair: int, lower: bool, form: int):
+    """THE chain of text passes in front of yabpe_pretokenize and the encoders, part by part (a chunk in training, a document
+    in encoding): with `repair` (check_errors) yabpe_utf8_repair, then with `lower` (check_lowercase) yabpe_lowercase, then with
+    `form` (check_normalizer) yabpe_normalize.  `text`: a host u8 array (n_bytes None) or a device address; `starts`: the
+    parts' starts in it.  -> (text, n_bytes, starts) as the next call takes them: the last pass's text in device memory (the
+    context's until that pass's next call or its *_free; the words or ids made from it are offsets into it) and the parts'
+    starts in it, read back after every pass; a text with nothing left is (an empty host array, None, starts).  The repair
+    runs on an empty text too; the other two are skipped once no bytes are left.  _native.Utf8Error (the first pass that reads
+    the text validates it: positions in the input) passes through; _native.SegmentTooLong leaves with .read_starts (the
+    parts' starts in the text the normaliser read: repaired and lowered, so not the ones that came in) and .repaired (whether
+    a repair ran in front of it)."""
+    from . import _native
+
+    n_parts = len(starts)
+    if repair:
+        text, dev_starts, n_bytes = ctx.utf8_repair(text, n_bytes=n_bytes, part_starts=starts, mode=repair)
+        starts = ctx.d2h(dev_starts, 8 * n_parts, np.uint64)
+    if lower and (n_bytes is None or n_bytes):
+        text, dev_starts, n_bytes = ctx.lowercase(text, n_bytes=n_bytes, part_starts=starts)
+        starts = ctx.d2h(dev_starts, 8 * n_parts, np.uint64)
+    if form and (n_bytes is None or n_bytes):
+        try:
+            text, dev_starts, n_bytes = ctx.normalize(text, n_bytes=n_bytes, part_starts=starts, form=form)
+        except _native.SegmentTooLong as e:
+            e.read_starts, e.repaired = [int(s0) for s0 in starts], bool(repair)
+            raise
+        starts = ctx.d2h(dev_starts, 8 * n_parts, np.uint64)
+    if n_bytes == 0:  # (every byte was dropped)
+        text, n_bytes = np.zeros(0, np.uint8), None
+    return text, n_bytes, starts
 
 
 def read_lowercase(model_dir: str | Path) -> bool:
@@ -636,14 +669,11 @@ class BBPETrainer:
         return int(batch_bytes)
 
     def _device_words(self, ctx, chunks: Sequence[tuple[Path, int, int]], batch_bytes: int | None, dedup: bool):
-        """The chunks' pre-tokens as device words for _run: file bytes -> (with errors = "replace" / "ignore": yabpe_utf8_repair,
-        chunk by chunk -> the repaired text and the chunk starts in it ->) (with lowercase: yabpe_lowercase, chunk by chunk -> the
-        lowered text and the chunk starts in it ->) (with a normaliser: yabpe_normalize, chunk by chunk
-        -> the normalised text and the chunk starts in it ->) yabpe_pretokenize -> word offsets in HBM (equal
-        pre-tokens are pooled by the load when `dedup`).  With `batch_bytes` the chunks are read batch by batch (one batch on
-        the host at a time) and each batch's pre-tokens added to ctx's word pool (yabpe_pool_add); the words are then the
-        pool's, with its counts and nothing left to pool.  Pre-tokens never cross a chunk cut, so the pooled multiset is the
-        same."""
+        """The chunks' pre-tokens as device words for _run: file bytes -> device_text_front, chunk by chunk -> yabpe_pretokenize
+        -> word offsets in HBM (equal pre-tokens are pooled by the load when `dedup`).  With `batch_bytes` the chunks are
+        read batch by batch (one batch on the host at a time) and each batch's pre-tokens added to ctx's word pool
+        (yabpe_pool_add); the words are then the pool's, with its counts and nothing left to pool.  Pre-tokens never cross a
+        chunk cut, so the pooled multiset is the same."""
         from . import _native
 
         form = check_normalizer(getattr(self.config, "normalizer", None))
@@ -652,33 +682,18 @@ class BBPETrainer:
 
         def pretokenize(part):
             buf, starts = read_chunks(part)
-            text, n_bytes, cur = buf, None, starts  # what the next step reads: host buffer, or device address and length
             try:
+                text, n_bytes, cur = device_text_front(ctx, buf, None, starts, repair=repair, lower=lower, form=form)
                 if repair:
-                    # the repaired text stays the context's until utf8_repair_free (the words are offsets into it, or into
-                    # the normalised text made from it)
-                    text, dev_starts, n_bytes = ctx.utf8_repair(buf, part_starts=starts, mode=repair)
-                    cur = ctx.d2h(dev_starts, 8 * len(starts), np.uint64)
                     self.utf8_replaced += int(ctx.utf8_repair_stats()["n_subparts"])
-                if lower and (n_bytes is None or n_bytes):
-                    # the lowered text stays the context's until lowercase_free (the words are offsets into it, or into the
-                    # normalised text made from it)
-                    text, dev_starts, n_bytes = ctx.lowercase(text, n_bytes=n_bytes, part_starts=cur)
-                    cur = ctx.d2h(dev_starts, 8 * len(starts), np.uint64)
-                if form and (n_bytes is None or n_bytes):
-                    # the normalised text stays the context's until normalize_free (the words are offsets into it)
-                    text, dev_starts, n_bytes = ctx.normalize(text, n_bytes=n_bytes, part_starts=cur, form=form)
-                    cur = ctx.d2h(dev_starts, 8 * len(starts), np.uint64)
-                if n_bytes == 0:  # (every byte was dropped: no words)
-                    text, n_bytes = np.zeros(0, np.uint8), None
                 return ctx.pretokenize(text, n_bytes=n_bytes, chunk_starts=cur, special_tokens=list(self.config.special_tokens))
-            except _native.Utf8Error as e:  # (positions in buf: the first step that reads the text validates it)
+            except _native.Utf8Error as e:  # (positions in buf)
                 raise utf8_error(part, starts, e) from e
             except _native.SegmentTooLong as e:
-                # (a position in the text the normaliser read, `cur` the chunks' starts in it.  Lowered text: the chunk is the
-                # right one, the position inside it counts the lowered bytes -- the file's, give or take what the 25 code
-                # points that change length did in front of it)
-                raise (repaired_segment_error(part, cur, e) if repair else segment_error(part, [int(s0) for s0 in cur], e)) from e
+                # (a position in the text the normaliser read.  Lowered text: the chunk is the right one, the position inside it
+                # counts the lowered bytes -- the file's, give or take what the 25 code points that change length did in front
+                # of it)
+                raise (repaired_segment_error if e.repaired else segment_error)(part, e.read_starts, e) from e
 
         if batch_bytes is None:
             return (*pretokenize(chunks), 0, dedup)
