@@ -1,5 +1,6 @@
 """Build-time guard (no GPU needed: hipcc cross-compiles): each kernel of the windows layout (yabpe_layout_windows,
-csrc/yabpe_layout_kernels.h) is there exactly once per instantiation and uses no scratch memory."""
+csrc/yabpe_layout_kernels.h) is there exactly once per instantiation, uses no scratch memory and no more registers than before the
+write kernel became the one it shares with the pairs layout."""
 from __future__ import annotations
 
 import re
@@ -9,7 +10,9 @@ import pytest
 from tests import kernel_resources
 
 # (itanium names: template kernels carry their arguments)
-KERNELS = [r"_ZN2yb\d+k_lay_win_countE", r"_ZN2yb\d+k_lay_win_rowsE", r"_ZN2yb\d+k_lay_win_writeILb0EE", r"_ZN2yb\d+k_lay_win_writeILb1EE"]
+KERNELS = [r"_ZN2yb\d+k_lay_win_countE", r"_ZN2yb\d+k_lay_win_rowsE", r"_ZN2yb\d+k_lay_rows_writeINS_\d+LayWinRowELb0EE",
+           r"_ZN2yb\d+k_lay_rows_writeINS_\d+LayWinRowELb1EE"]
+VGPRS = {KERNELS[0]: 29, KERNELS[2]: 20, KERNELS[3]: 38}  # count, write, write with spans
 
 
 @pytest.fixture(scope="module")
@@ -31,3 +34,10 @@ def test_the_write_kernel_keeps_no_workgroup_state(resources):
     for k in KERNELS[2:]:
         (r,) = [r for name, r in resources.items() if re.match(k, name)]
         assert r["LDS"] == 0, (k, r)
+
+
+def test_no_kernel_needs_more_registers_than_before(resources):
+    """Upper bounds: the VGPRs of each kernel before windows and pairs shared their write kernel."""
+    for k, most in VGPRS.items():
+        (r,) = [r for name, r in resources.items() if re.match(k, name)]
+        assert r["VGPRs"] <= most, (k, r)

@@ -102,6 +102,20 @@ struct EventPair {
     bool split;
 };
 
+// The slots of yabpe_ctx::lay_buf, u32 arrays unless said otherwise.  yabpe_layout_pad: ROWS, ROW_DOC (the kept lengths);
+// yabpe_layout_pack: ROWS, ROW_DOC, ROW_START (ids, doc, pos: a slot each); yabpe_layout_windows: ROWS .. ROW_LEN, SPANS;
+// yabpe_layout_pairs: all seven (ROW_DOC = row_pair, ROW_LEN = first_len).
+enum LayBuf {
+    LB_ROWS,        // the ids of every output slot
+    LB_ROW_DOC,     // per row: the document (pair) it comes from
+    LB_ROW_START,   // per row: the index in its document (second side) of its first content id
+    LB_ROW_LEN,     // per row: the slots it fills (pairs: the ids it keeps of the first side)
+    LB_SPANS,       // with spans: a (start, end) u64 pair per output slot
+    LB_SECOND_LEN,  // per row: the ids it keeps of the second side
+    LB_TYPES,       // a byte per output slot
+    LB_COUNT
+};
+
 }  // namespace
 
 struct yabpe_ctx {
@@ -198,9 +212,7 @@ struct yabpe_ctx {
     yabpe_decode_stats_t dec_stats{};
     hipEvent_t dec_ev[7] = {};
     // fixed-shape batches (yabpe_layout_pad / yabpe_layout_pack / yabpe_layout_windows / yabpe_layout_pairs)
-    uint32_t *lay_buf[7] = {};                // results of the last layout call: rows, lengths / ids, doc, pos /
-                                              // rows, row_doc, row_start, row_len, spans (u64 pairs) /
-                                              // rows, row_pair, row_start, first_len, spans, second_len, types (bytes)
+    uint32_t *lay_buf[LB_COUNT] = {};         // results of the last layout call, by LayBuf (which says what each call keeps where)
     yabpe_layout_stats_t lay_stats{};
     hipEvent_t lay_ev[4] = {};
     // resumed load (yabpe_load_words_resumed)
@@ -1034,6 +1046,131 @@ struct TextPass {
         *out_off = (uint64_t *)off;
         *out_n = *stat_n_out = n_out;
         return YABPE_OK;
+    }
+};
+
+// ---- fixed-shape batches (yabpe_layout_pad / _pack / _windows / _pairs)
+// flags outside mode_flags, the ones the call takes (an unknown flag is one of them)
+int layout_flags(yabpe_ctx *c, const yabpe_layout_t *lay, uint32_t mode_flags) {
+    if (lay->flags & ~mode_flags)
+        return fail(c, YABPE_E_INVALID, "layout flags 0x%x do not belong to this call (it takes 0x%x)", lay->flags & ~mode_flags, mode_flags);
+    return 0;
+}
+
+// What the four layout calls share, as steps a call runs in order (between them: its own checks, buffers and kernels):
+// begin(), count_begin(), [row_offsets(), row_budget(), write()], end().  lay_ev[0..1] bracket the lengths pass (windows and
+// pairs: count + scan + rows), [2..3] the write kernel.  A call that its own checks or begin()'s refuse has freed nothing.
+struct LayoutCall {
+    yabpe_ctx *c;
+    Scratch S;
+    hipStream_t s;
+    const yabpe_layout_t *lay = nullptr;
+    const uint32_t *d_ids = nullptr;
+    const unsigned long long *d_docs = nullptr;
+    const ulonglong2 *d_spans = nullptr;            // NULL: the call stores no spans
+    unsigned long long *counters = nullptr;         // 4 on the device; h_cnt: their values once row_offsets() has run
+    unsigned long long h_cnt[4] = {0, 0, 0, 0};
+
+    explicit LayoutCall(yabpe_ctx *c_) : c(c_), S(c_->device, c_->rank), s(c_->stream) {}
+    LayConst K() const { return LayConst{lay->pad_id, lay->bos_id, lay->eos_id}; }
+
+    // The arguments checked (mode_flags: the flags the call takes), the last layout released, the stats reset; the ids, the
+    // validated document starts and the spans (if any) on the device, the counters allocated.
+    int begin(const uint32_t *ids, uint64_t n_ids, const uint64_t *doc_off, uint32_t *n_docs, const uint64_t *spans, const yabpe_layout_t *lay_,
+              uint32_t mode_flags) {
+        if (!lay_) return fail(c, YABPE_E_INVALID, "layout is NULL");
+        if (lay_->flags & ~(LAY_PAD_FLAGS | LAY_PACK_FLAGS)) return fail(c, YABPE_E_INVALID, "unknown layout flags 0x%x", lay_->flags);
+        TRY(layout_flags(c, lay_, mode_flags));
+        if (n_ids && !ids) return fail(c, YABPE_E_INVALID, "ids is NULL");
+        if (!doc_off && *n_docs > 1) return fail(c, YABPE_E_INVALID, "doc_off is NULL with %u documents", *n_docs);
+        // the document starts on the host (validated: the kernels index the ids with them) and on the device
+        const bool docs_dev = doc_off && is_device_ptr(doc_off);
+        if (!doc_off) *n_docs = 1;
+        std::vector<uint64_t> h_docs(*n_docs, 0);
+        if (doc_off && *n_docs) {
+            if (docs_dev) HIPCHK(c, hipMemcpy(h_docs.data(), doc_off, (size_t)*n_docs * 8, hipMemcpyDeviceToHost));
+            else memcpy(h_docs.data(), doc_off, (size_t)*n_docs * 8);
+        }
+        TRY(check_starts(c, h_docs.data(), *n_docs, n_ids, "ids"));
+        yabpe_layout_free(c);
+        c->lay_stats = yabpe_layout_stats_t{};
+        c->lay_stats.n_ids = n_ids;
+        c->lay_stats.n_docs = *n_docs;
+        lay = lay_;
+        for (auto &e : c->lay_ev)
+            if (!e) HIPCHK(c, hipEventCreate(&e));
+        TRY(to_device(c, S, ids, n_ids * 4, 4, &d_ids));
+        TRY(to_device(c, S, docs_dev ? (const unsigned long long *)doc_off : (const unsigned long long *)h_docs.data(), (uint64_t)*n_docs * 8, 8, &d_docs));
+        if (spans) TRY(to_device(c, S, (const ulonglong2 *)spans, n_ids * 16, 16, &d_spans));
+        HIPCHK(c, S.get(&counters, 4));
+        return 0;
+    }
+    // the lengths pass starts: its event, the counters zeroed (the call's own buffers are allocated before, outside the bracket)
+    int count_begin() {
+        HIPCHK(c, hipEventRecord(c->lay_ev[0], s));
+        HIPCHK(c, hipMemsetAsync(counters, 0, 32, s));
+        return 0;
+    }
+    // Row offsets: the exclusive scan of cnt[n] into row_off[n + 1] and its total -> *n_rows (cnt NULL: one row each, *n_rows
+    // stays as it is); the counters -> h_cnt.  The stream is idle afterwards.
+    int row_offsets(const unsigned long long *cnt, uint32_t n, unsigned long long *row_off, unsigned long long *n_rows) {
+        if (cnt) {
+            if (exclusive_scan<unsigned long long>(s, cnt, n, row_off, (unsigned long long)n + 1) != 0)
+                return fail(c, YABPE_E_HIP, "scan of the row counts failed");
+            HIPCHK(c, hipMemcpyAsync(n_rows, row_off + n, 8, hipMemcpyDeviceToHost, s));
+        }
+        HIPCHK(c, hipMemcpyAsync(h_cnt, counters, 32, hipMemcpyDeviceToHost, s));
+        HIPCHK(c, hipStreamSynchronize(s));
+        return 0;
+    }
+    // Row budget: the longest document (h_cnt[0]) fits the u32 per-row arrays (`u32_fields` names them), n_rows rows fit one call
+    int row_budget(const char *u32_fields, unsigned long long n_rows, unsigned long long *n_slots) {
+        if (h_cnt[0] > 0xFFFFFFFFull) return fail(c, YABPE_E_CAPACITY, "a document of %llu ids: %s u32", h_cnt[0], u32_fields);
+        if (n_rows > LAY_MAX_SLOTS / lay->row_len)
+            return fail(c, YABPE_E_CAPACITY, "%llu rows of %u slots: at most 2^36 slots in one call", n_rows, lay->row_len);
+        *n_slots = n_rows * lay->row_len;
+        return 0;
+    }
+    // The lengths pass ends behind the rows kernel; the record-driven write of windows and pairs into the slots of lay_buf
+    // (n_slots >= 1: a document has at least one row).
+    template <class Row>
+    int write(const Row &R, const typename Row::Rec *rec, unsigned long long n_rows, unsigned long long n_slots) {
+        HIPCHK(c, hipGetLastError());
+        HIPCHK(c, hipEventRecord(c->lay_ev[1], s));
+        HIPCHK(c, hipEventRecord(c->lay_ev[2], s));
+        const LayRowsParams<Row> W{d_ids, rec, n_rows, lay->row_len, lay->flags, R, K(), c->lay_buf[LB_ROWS], (uint8_t *)c->lay_buf[LB_TYPES], n_slots,
+                                   d_spans, (ulonglong2 *)c->lay_buf[LB_SPANS]};
+        if (d_spans)
+            hipLaunchKernelGGL((k_lay_rows_write<Row, true>), dim3(cdiv64(n_slots, LAY_PIECE)), dim3(BLOCK), 0, s, W);
+        else
+            hipLaunchKernelGGL((k_lay_rows_write<Row, false>), dim3(cdiv64(n_slots, LAY_PIECE)), dim3(BLOCK), 0, s, W);
+        return 0;
+    }
+    // the write pass ends: every call's success path synchronises here; the times of the passes
+    int end() {
+        HIPCHK(c, hipGetLastError());
+        HIPCHK(c, hipEventRecord(c->lay_ev[3], s));
+        const hipError_t se = hipStreamSynchronize(s);
+        if (se != hipSuccess) {
+            yabpe_layout_free(c);
+            return fail(c, YABPE_E_HIP, "layout kernels failed: %s", hipGetErrorString(se));
+        }
+        float ms[3] = {0, 0, 0};
+        c->lay_stats.total_ms = pass_times(c->lay_ev, 3, ms);
+        c->lay_stats.lengths_ms = ms[0];
+        c->lay_stats.write_ms = ms[2];
+        return 0;
+    }
+    // ... and the stats of a call whose count kernel sums the counters (pad, windows, pairs)
+    int end(unsigned long long n_rows, unsigned long long row_len, unsigned long long n_slots) {
+        TRY(end());
+        auto &st = c->lay_stats;
+        st.n_rows = n_rows;
+        st.row_len = row_len;
+        st.n_truncated_docs = h_cnt[1];
+        st.n_ids_dropped = h_cnt[2];
+        st.n_pad_slots = n_slots - h_cnt[3];
+        return 0;
     }
 };
 
@@ -4121,47 +4258,6 @@ int yabpe_layout_free(yabpe_ctx *c) {
     return YABPE_OK;
 }
 
-// What both layout calls begin with: the arguments checked (mode_flags: the flags the call takes), the last layout released,
-// the stats reset, the ids and the validated document starts on the device.
-static int layout_begin(yabpe_ctx *c, Scratch &S, const uint32_t *ids, uint64_t n_ids, const uint64_t *doc_off, uint32_t *n_docs,
-                        const yabpe_layout_t *lay, uint32_t mode_flags, const uint32_t **d_ids, const unsigned long long **d_docs) {
-    if (!lay) return fail(c, YABPE_E_INVALID, "layout is NULL");
-    if (lay->flags & ~(LAY_PAD_FLAGS | LAY_PACK_FLAGS)) return fail(c, YABPE_E_INVALID, "unknown layout flags 0x%x", lay->flags);
-    if (lay->flags & ~mode_flags)
-        return fail(c, YABPE_E_INVALID, "layout flags 0x%x do not belong to this call (it takes 0x%x)", lay->flags & ~mode_flags, mode_flags);
-    if (n_ids && !ids) return fail(c, YABPE_E_INVALID, "ids is NULL");
-    if (!doc_off && *n_docs > 1) return fail(c, YABPE_E_INVALID, "doc_off is NULL with %u documents", *n_docs);
-    // the document starts on the host (validated: the kernels index the ids with them) and on the device
-    const bool docs_dev = doc_off && is_device_ptr(doc_off);
-    if (!doc_off) *n_docs = 1;
-    std::vector<uint64_t> h_docs(*n_docs, 0);
-    if (doc_off && *n_docs) {
-        if (docs_dev) HIPCHK(c, hipMemcpy(h_docs.data(), doc_off, (size_t)*n_docs * 8, hipMemcpyDeviceToHost));
-        else memcpy(h_docs.data(), doc_off, (size_t)*n_docs * 8);
-    }
-    TRY(check_starts(c, h_docs.data(), *n_docs, n_ids, "ids"));
-    yabpe_layout_free(c);
-    c->lay_stats = yabpe_layout_stats_t{};
-    c->lay_stats.n_ids = n_ids;
-    c->lay_stats.n_docs = *n_docs;
-    for (auto &e : c->lay_ev)
-        if (!e) HIPCHK(c, hipEventCreate(&e));
-    TRY(to_device(c, S, ids, n_ids * 4, 4, d_ids));
-    TRY(to_device(c, S, docs_dev ? (const unsigned long long *)doc_off : (const unsigned long long *)h_docs.data(), (uint64_t)*n_docs * 8, 8, d_docs));
-    return 0;
-}
-
-// lay_ev[0..1] around the lengths pass (windows: count + scan + rows), [2..3] around the write pass
-static void layout_times(yabpe_ctx *c) {
-    float ms[3] = {0, 0, 0};
-    (void)hipEventElapsedTime(&ms[0], c->lay_ev[0], c->lay_ev[1]);
-    (void)hipEventElapsedTime(&ms[1], c->lay_ev[2], c->lay_ev[3]);
-    (void)hipEventElapsedTime(&ms[2], c->lay_ev[0], c->lay_ev[3]);
-    c->lay_stats.lengths_ms = ms[0];
-    c->lay_stats.write_ms = ms[1];
-    c->lay_stats.total_ms = ms[2];
-}
-
 int yabpe_layout_pad(yabpe_ctx *c, const uint32_t *ids, uint64_t n_ids, const uint64_t *doc_off, uint32_t n_docs, const yabpe_layout_t *lay,
                      uint32_t **out_dev_rows, uint32_t **out_dev_len, uint32_t *out_row_len) {
     if (!c || !out_dev_rows || !out_dev_len || !out_row_len) return YABPE_E_INVALID;
@@ -4171,53 +4267,31 @@ int yabpe_layout_pad(yabpe_ctx *c, const uint32_t *ids, uint64_t n_ids, const ui
         return fail(c, YABPE_E_INVALID, "row_len %u cannot hold BOS and EOS", lay->row_len);
     if (lay && (unsigned long long)lay->row_len * n_docs > LAY_MAX_SLOTS)
         return fail(c, YABPE_E_CAPACITY, "%u rows of %u slots: at most 2^36 slots in one call", n_docs, lay->row_len);
-    Scratch S(c->device, c->rank);
-    const uint32_t *d_ids = nullptr;
-    const unsigned long long *d_docs = nullptr;
-    TRY(layout_begin(c, S, ids, n_ids, doc_off, &n_docs, lay, LAY_PAD_FLAGS, &d_ids, &d_docs));
-    hipStream_t s = c->stream;
+    LayoutCall Q(c);
+    TRY(Q.begin(ids, n_ids, doc_off, &n_docs, nullptr, lay, LAY_PAD_FLAGS));
     // ---- lengths: kept length per document, the longest sequence, what the cut drops
-    unsigned long long *counters = nullptr;
-    HIPCHK(c, S.get(&counters, 4));
-    TRY(dmalloc(c, &c->lay_buf[1], n_docs));
-    HIPCHK(c, hipEventRecord(c->lay_ev[0], s));
-    HIPCHK(c, hipMemsetAsync(counters, 0, 32, s));
-    hipLaunchKernelGGL(k_lay_lengths<false>, dim3(cdiv64(n_docs, BLOCK)), dim3(BLOCK), 0, s,
-                       LayLenParams{d_docs, n_docs, n_ids, lay->row_len, lay->flags, c->lay_buf[1], nullptr, counters});
+    TRY(dmalloc(c, &c->lay_buf[LB_ROW_DOC], n_docs));
+    TRY(Q.count_begin());
+    hipLaunchKernelGGL(k_lay_lengths<false>, dim3(cdiv64(n_docs, BLOCK)), dim3(BLOCK), 0, Q.s,
+                       LayLenParams{Q.d_docs, n_docs, n_ids, lay->row_len, lay->flags, c->lay_buf[LB_ROW_DOC], nullptr, Q.counters});
     HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipEventRecord(c->lay_ev[1], s));
-    unsigned long long h_cnt[4] = {0, 0, 0, 0};
-    HIPCHK(c, hipMemcpyAsync(h_cnt, counters, 32, hipMemcpyDeviceToHost, s));
-    HIPCHK(c, hipStreamSynchronize(s));
-    const unsigned long long L = lay->row_len ? lay->row_len : h_cnt[0];
+    HIPCHK(c, hipEventRecord(c->lay_ev[1], Q.s));
+    TRY(Q.row_offsets(nullptr, 0, nullptr, nullptr));
+    const unsigned long long L = lay->row_len ? lay->row_len : Q.h_cnt[0];
     const unsigned long long n_slots = L * n_docs;
     if (L > 0xFFFFFFFFull || n_slots > LAY_MAX_SLOTS) {
         yabpe_layout_free(c);
         return fail(c, YABPE_E_CAPACITY, "%u rows of %llu slots (the longest sequence): at most 2^36 slots of at most 2^32 - 1 a row", n_docs, L);
     }
     // ---- write
-    TRY(dmalloc(c, &c->lay_buf[0], n_slots));
-    HIPCHK(c, hipEventRecord(c->lay_ev[2], s));
+    TRY(dmalloc(c, &c->lay_buf[LB_ROWS], n_slots));
+    HIPCHK(c, hipEventRecord(c->lay_ev[2], Q.s));
     if (n_slots)
-        hipLaunchKernelGGL(k_lay_pad_write, dim3(cdiv64(n_slots, LAY_PIECE)), dim3(BLOCK), 0, s,
-                           LayPadParams{d_ids, d_docs, n_docs, n_ids, (uint32_t)L, lay->flags, LayConst{lay->pad_id, lay->bos_id, lay->eos_id},
-                                        c->lay_buf[0], n_slots});
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipEventRecord(c->lay_ev[3], s));
-    const hipError_t se = hipStreamSynchronize(s);
-    if (se != hipSuccess) {
-        yabpe_layout_free(c);
-        return fail(c, YABPE_E_HIP, "layout kernels failed: %s", hipGetErrorString(se));
-    }
-    auto &st = c->lay_stats;
-    st.n_rows = n_docs;
-    st.row_len = L;
-    st.n_truncated_docs = h_cnt[1];
-    st.n_ids_dropped = h_cnt[2];
-    st.n_pad_slots = n_slots - h_cnt[3];
-    layout_times(c);
-    *out_dev_rows = c->lay_buf[0];
-    *out_dev_len = c->lay_buf[1];
+        hipLaunchKernelGGL(k_lay_pad_write, dim3(cdiv64(n_slots, LAY_PIECE)), dim3(BLOCK), 0, Q.s,
+                           LayPadParams{Q.d_ids, Q.d_docs, n_docs, n_ids, (uint32_t)L, lay->flags, Q.K(), c->lay_buf[LB_ROWS], n_slots});
+    TRY(Q.end(n_docs, L, n_slots));
+    *out_dev_rows = c->lay_buf[LB_ROWS];
+    *out_dev_len = c->lay_buf[LB_ROW_DOC];
     *out_row_len = (uint32_t)L;
     return YABPE_OK;
 }
@@ -4228,51 +4302,37 @@ int yabpe_layout_pack(yabpe_ctx *c, const uint32_t *ids, uint64_t n_ids, const u
     HIPCHK(c, hipSetDevice(c->device));
     *out_dev_ids = nullptr; *out_dev_doc = nullptr; *out_dev_pos = nullptr; *out_n_rows = 0;
     if (lay && lay->row_len == 0) return fail(c, YABPE_E_INVALID, "row_len is 0: a packed row holds at least one slot");
-    Scratch S(c->device, c->rank);
-    const uint32_t *d_ids = nullptr;
-    const unsigned long long *d_docs = nullptr;
-    TRY(layout_begin(c, S, ids, n_ids, doc_off, &n_docs, lay, LAY_PACK_FLAGS, &d_ids, &d_docs));
+    LayoutCall Q(c);
+    TRY(Q.begin(ids, n_ids, doc_off, &n_docs, nullptr, lay, LAY_PACK_FLAGS));
     const unsigned long long total = n_ids + (unsigned long long)lay_n_added(lay->flags) * n_docs;
     if (total > LAY_MAX_SLOTS) return fail(c, YABPE_E_CAPACITY, "a stream of %llu entries: at most 2^36 slots in one call", total);
     const unsigned long long n_rows = lay_pack_rows(total, lay->row_len, lay->flags), n_slots = n_rows * lay->row_len;
-    hipStream_t s = c->stream;
     // ---- lengths: the stream offsets (closed form) and the longest sequence
-    unsigned long long *counters = nullptr, *soff = nullptr;
-    HIPCHK(c, S.get(&counters, 4));
-    HIPCHK(c, S.get(&soff, (uint64_t)n_docs + 1));
-    HIPCHK(c, hipEventRecord(c->lay_ev[0], s));
-    HIPCHK(c, hipMemsetAsync(counters, 0, 32, s));
-    hipLaunchKernelGGL(k_lay_lengths<true>, dim3(cdiv64(n_docs, BLOCK)), dim3(BLOCK), 0, s,
-                       LayLenParams{d_docs, n_docs, n_ids, lay->row_len, lay->flags, nullptr, soff, counters});
+    unsigned long long *soff = nullptr;
+    HIPCHK(c, Q.S.get(&soff, (uint64_t)n_docs + 1));
+    TRY(Q.count_begin());
+    hipLaunchKernelGGL(k_lay_lengths<true>, dim3(cdiv64(n_docs, BLOCK)), dim3(BLOCK), 0, Q.s,
+                       LayLenParams{Q.d_docs, n_docs, n_ids, lay->row_len, lay->flags, nullptr, soff, Q.counters});
     HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipEventRecord(c->lay_ev[1], s));
-    unsigned long long longest = 0;
-    HIPCHK(c, hipMemcpyAsync(&longest, counters, 8, hipMemcpyDeviceToHost, s));
-    HIPCHK(c, hipStreamSynchronize(s));
-    if (longest > 0xFFFFFFFFull) return fail(c, YABPE_E_CAPACITY, "a document of %llu stream entries: positions are u32", longest);
+    HIPCHK(c, hipEventRecord(c->lay_ev[1], Q.s));
+    TRY(Q.row_offsets(nullptr, 0, nullptr, nullptr));
+    if (Q.h_cnt[0] > 0xFFFFFFFFull) return fail(c, YABPE_E_CAPACITY, "a document of %llu stream entries: positions are u32", Q.h_cnt[0]);
     // ---- write
-    for (int k = 0; k < 3; ++k) TRY(dmalloc(c, &c->lay_buf[k], n_slots));
-    HIPCHK(c, hipEventRecord(c->lay_ev[2], s));
+    for (int k : {LB_ROWS, LB_ROW_DOC, LB_ROW_START}) TRY(dmalloc(c, &c->lay_buf[k], n_slots));
+    HIPCHK(c, hipEventRecord(c->lay_ev[2], Q.s));
     if (n_slots)
-        hipLaunchKernelGGL(k_lay_pack_write, dim3(cdiv64(n_slots, LAY_PIECE)), dim3(BLOCK), 0, s,
-                           LayPackParams{d_ids, soff, n_docs, total, n_slots, lay->flags, LayConst{lay->pad_id, lay->bos_id, lay->eos_id},
-                                         c->lay_buf[0], c->lay_buf[1], c->lay_buf[2]});
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipEventRecord(c->lay_ev[3], s));
-    const hipError_t se = hipStreamSynchronize(s);
-    if (se != hipSuccess) {
-        yabpe_layout_free(c);
-        return fail(c, YABPE_E_HIP, "layout kernels failed: %s", hipGetErrorString(se));
-    }
+        hipLaunchKernelGGL(k_lay_pack_write, dim3(cdiv64(n_slots, LAY_PIECE)), dim3(BLOCK), 0, Q.s,
+                           LayPackParams{Q.d_ids, soff, n_docs, total, n_slots, lay->flags, Q.K(), c->lay_buf[LB_ROWS], c->lay_buf[LB_ROW_DOC],
+                                         c->lay_buf[LB_ROW_START]});
+    TRY(Q.end());
     auto &st = c->lay_stats;
     st.n_rows = n_rows;
     st.row_len = lay->row_len;
     st.n_ids_dropped = total > n_slots ? total - n_slots : 0;
     st.n_pad_slots = n_slots > total ? n_slots - total : 0;
-    layout_times(c);
-    *out_dev_ids = c->lay_buf[0];
-    *out_dev_doc = c->lay_buf[1];
-    *out_dev_pos = c->lay_buf[2];
+    *out_dev_ids = c->lay_buf[LB_ROWS];
+    *out_dev_doc = c->lay_buf[LB_ROW_DOC];
+    *out_dev_pos = c->lay_buf[LB_ROW_START];
     *out_n_rows = n_rows;
     return YABPE_OK;
 }
@@ -4286,69 +4346,36 @@ int yabpe_layout_windows(yabpe_ctx *c, const uint32_t *ids, uint64_t n_ids, cons
     if (lay && lay->row_len <= added) return fail(c, YABPE_E_INVALID, "row_len %u leaves no slot for content beside BOS and EOS", lay->row_len);
     if (lay && stride >= lay->row_len - added)
         return fail(c, YABPE_E_INVALID, "stride %u: consecutive rows of %u content slots must advance by at least one", stride, lay->row_len - added);
-    Scratch S(c->device, c->rank);
-    const uint32_t *d_ids = nullptr;
-    const unsigned long long *d_docs = nullptr;
-    TRY(layout_begin(c, S, ids, n_ids, doc_off, &n_docs, lay, LAY_WIN_FLAGS, &d_ids, &d_docs));
-    const ulonglong2 *d_spans = nullptr;
-    if (spans) TRY(to_device(c, S, (const ulonglong2 *)spans, n_ids * 16, 16, &d_spans));
+    LayoutCall Q(c);
+    TRY(Q.begin(ids, n_ids, doc_off, &n_docs, spans, lay, LAY_WIN_FLAGS));
     const uint32_t L = lay->row_len, C = L - added, step = C - stride;
-    hipStream_t s = c->stream;
     // ---- count + scan: the rows of every document, their exclusive scan, the call's counters
-    unsigned long long *counters = nullptr, *cnt = nullptr, *row_off = nullptr;
-    HIPCHK(c, S.get(&counters, 4));
-    HIPCHK(c, S.get(&cnt, n_docs));
-    HIPCHK(c, S.get(&row_off, (uint64_t)n_docs + 1));
-    HIPCHK(c, hipEventRecord(c->lay_ev[0], s));
-    HIPCHK(c, hipMemsetAsync(counters, 0, 32, s));
-    hipLaunchKernelGGL(k_lay_win_count, dim3(cdiv64(n_docs, BLOCK)), dim3(BLOCK), 0, s,
-                       LayWinCountParams{d_docs, n_docs, n_ids, C, step, added, cnt, counters});
+    unsigned long long *cnt = nullptr, *row_off = nullptr, n_rows = 0, n_slots = 0;
+    HIPCHK(c, Q.S.get(&cnt, n_docs));
+    HIPCHK(c, Q.S.get(&row_off, (uint64_t)n_docs + 1));
+    TRY(Q.count_begin());
+    hipLaunchKernelGGL(k_lay_win_count, dim3(cdiv64(n_docs, BLOCK)), dim3(BLOCK), 0, Q.s,
+                       LayWinCountParams{Q.d_docs, n_docs, n_ids, C, step, added, cnt, Q.counters});
     HIPCHK(c, hipGetLastError());
-    if (exclusive_scan<unsigned long long>(s, cnt, n_docs, row_off, (unsigned long long)n_docs + 1) != 0)
-        return fail(c, YABPE_E_HIP, "scan of the row counts failed");
-    unsigned long long h_cnt[4] = {0, 0, 0, 0}, n_rows = 0;
-    HIPCHK(c, hipMemcpyAsync(h_cnt, counters, 32, hipMemcpyDeviceToHost, s));
-    HIPCHK(c, hipMemcpyAsync(&n_rows, row_off + n_docs, 8, hipMemcpyDeviceToHost, s));
-    HIPCHK(c, hipStreamSynchronize(s));
-    if (h_cnt[0] > 0xFFFFFFFFull) return fail(c, YABPE_E_CAPACITY, "a document of %llu ids: row_start is u32", h_cnt[0]);
-    if (n_rows > LAY_MAX_SLOTS / L) return fail(c, YABPE_E_CAPACITY, "%llu rows of %u slots: at most 2^36 slots in one call", n_rows, L);
-    const unsigned long long n_slots = n_rows * L;
+    TRY(Q.row_offsets(cnt, n_docs, row_off, &n_rows));
+    TRY(Q.row_budget("row_start is", n_rows, &n_slots));
     // ---- rows: the record of every output row
     ulonglong2 *rec = nullptr;
-    HIPCHK(c, S.get(&rec, n_rows));
-    TRY(dmalloc(c, &c->lay_buf[0], n_slots));
-    for (int k = 1; k < 4; ++k) TRY(dmalloc(c, &c->lay_buf[k], n_rows));
-    if (spans) TRY(dmalloc(c, &c->lay_buf[4], 4 * n_slots));  // (16 B a slot)
-    hipLaunchKernelGGL(k_lay_win_rows, dim3(cdiv64(n_rows, BLOCK)), dim3(BLOCK), 0, s,
-                       LayWinRowsParams{d_docs, n_docs, n_ids, row_off, n_rows, C, step, added, c->lay_buf[1], c->lay_buf[2], c->lay_buf[3], rec});
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipEventRecord(c->lay_ev[1], s));
+    HIPCHK(c, Q.S.get(&rec, n_rows));
+    TRY(dmalloc(c, &c->lay_buf[LB_ROWS], n_slots));
+    for (int k : {LB_ROW_DOC, LB_ROW_START, LB_ROW_LEN}) TRY(dmalloc(c, &c->lay_buf[k], n_rows));
+    if (spans) TRY(dmalloc(c, &c->lay_buf[LB_SPANS], 4 * n_slots));  // (16 B a slot)
+    hipLaunchKernelGGL(k_lay_win_rows, dim3(cdiv64(n_rows, BLOCK)), dim3(BLOCK), 0, Q.s,
+                       LayWinRowsParams{Q.d_docs, n_docs, n_ids, row_off, n_rows, C, step, added, c->lay_buf[LB_ROW_DOC], c->lay_buf[LB_ROW_START],
+                                        c->lay_buf[LB_ROW_LEN], rec});
     // ---- write
-    HIPCHK(c, hipEventRecord(c->lay_ev[2], s));
-    const LayWinParams W{d_ids, rec, n_rows, L, lay->flags, LayConst{lay->pad_id, lay->bos_id, lay->eos_id}, c->lay_buf[0], n_slots,
-                         d_spans, (ulonglong2 *)c->lay_buf[4]};
-    if (spans)
-        hipLaunchKernelGGL(k_lay_win_write<true>, dim3(cdiv64(n_slots, LAY_PIECE)), dim3(BLOCK), 0, s, W);
-    else
-        hipLaunchKernelGGL(k_lay_win_write<false>, dim3(cdiv64(n_slots, LAY_PIECE)), dim3(BLOCK), 0, s, W);
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipEventRecord(c->lay_ev[3], s));
-    const hipError_t se = hipStreamSynchronize(s);
-    if (se != hipSuccess) {
-        yabpe_layout_free(c);
-        return fail(c, YABPE_E_HIP, "layout kernels failed: %s", hipGetErrorString(se));
-    }
-    auto &st = c->lay_stats;
-    st.n_rows = n_rows;
-    st.row_len = L;
-    st.n_truncated_docs = h_cnt[1];
-    st.n_pad_slots = n_slots - h_cnt[3];
-    layout_times(c);
-    out->rows = c->lay_buf[0];
-    out->row_doc = c->lay_buf[1];
-    out->row_start = c->lay_buf[2];
-    out->row_len = c->lay_buf[3];
-    out->spans = (uint64_t *)c->lay_buf[4];
+    TRY(Q.write(LayWinRow{}, rec, n_rows, n_slots));
+    TRY(Q.end(n_rows, L, n_slots));  // (windows drop no ids: that counter stays 0)
+    out->rows = c->lay_buf[LB_ROWS];
+    out->row_doc = c->lay_buf[LB_ROW_DOC];
+    out->row_start = c->lay_buf[LB_ROW_START];
+    out->row_len = c->lay_buf[LB_ROW_LEN];
+    out->spans = (uint64_t *)c->lay_buf[LB_SPANS];
     out->n_rows = n_rows;
     return YABPE_OK;
 }
@@ -4360,11 +4387,10 @@ int yabpe_layout_pairs(yabpe_ctx *c, const uint32_t *ids, uint64_t n_ids, const 
     *out = yabpe_pair_rows_t{};
     if (!lay) return fail(c, YABPE_E_INVALID, "layout is NULL");
     if (!pairs) return fail(c, YABPE_E_INVALID, "pairs is NULL");
-    if (lay->flags & ~LAY_PAIR_FLAGS)
-        return fail(c, YABPE_E_INVALID, "layout flags 0x%x do not belong to this call (it takes 0x%x)", lay->flags & ~LAY_PAIR_FLAGS, LAY_PAIR_FLAGS);
+    TRY(layout_flags(c, lay, LAY_PAIR_FLAGS));  // (ahead of begin(): the checks below read the flags, and no pairs return before it)
     if (pairs->n_sep > LAY_PAIRS_MAX_SEP) return fail(c, YABPE_E_INVALID, "n_sep %u: at most %u separators between the two sides", pairs->n_sep, LAY_PAIRS_MAX_SEP);
     if (pairs->mode > LAY_PAIRS_WINDOWS) return fail(c, YABPE_E_INVALID, "unknown pairs mode %u", pairs->mode);
-    const uint32_t added = lay_n_added(lay->flags & LAY_PAIR_FLAGS) + pairs->n_sep;
+    const uint32_t added = lay_n_added(lay->flags) + pairs->n_sep;
     if (lay->row_len <= added)
         return fail(c, YABPE_E_INVALID, "row_len %u leaves no slot for content beside BOS, EOS and %u separators", lay->row_len, pairs->n_sep);
     const uint32_t L = lay->row_len, C = L - added;
@@ -4381,77 +4407,40 @@ int yabpe_layout_pairs(yabpe_ctx *c, const uint32_t *ids, uint64_t n_ids, const 
         c->lay_stats.row_len = L;
         return YABPE_OK;
     }
-    Scratch S(c->device, c->rank);
-    const uint32_t *d_ids = nullptr;
-    const unsigned long long *d_docs = nullptr;
-    TRY(layout_begin(c, S, ids, n_ids, doc_off, &n_docs, lay, LAY_PAIR_FLAGS, &d_ids, &d_docs));
-    const ulonglong2 *d_spans = nullptr;
-    if (spans) TRY(to_device(c, S, (const ulonglong2 *)spans, n_ids * 16, 16, &d_spans));
-    const bool windows = pairs->mode == LAY_PAIRS_WINDOWS;
+    LayoutCall Q(c);
+    TRY(Q.begin(ids, n_ids, doc_off, &n_docs, spans, lay, LAY_PAIR_FLAGS));
     const LayPairShape shape{C, pairs->mode, pairs->stride, pairs->n_sep, added};
-    hipStream_t s = c->stream;
     // ---- count (+ scan in windows mode: elsewhere a pair has one row and the scan would be the identity)
-    unsigned long long *counters = nullptr, *cnt = nullptr, *row_off = nullptr;
-    HIPCHK(c, S.get(&counters, 4));
-    if (windows) {
-        HIPCHK(c, S.get(&cnt, n_pairs));
-        HIPCHK(c, S.get(&row_off, (uint64_t)n_pairs + 1));
+    unsigned long long *cnt = nullptr, *row_off = nullptr, n_rows = n_pairs, n_slots = 0;
+    if (pairs->mode == LAY_PAIRS_WINDOWS) {
+        HIPCHK(c, Q.S.get(&cnt, n_pairs));
+        HIPCHK(c, Q.S.get(&row_off, (uint64_t)n_pairs + 1));
     }
-    HIPCHK(c, hipEventRecord(c->lay_ev[0], s));
-    HIPCHK(c, hipMemsetAsync(counters, 0, 32, s));
-    hipLaunchKernelGGL(k_lay_pair_count, dim3(cdiv64(n_pairs, BLOCK)), dim3(BLOCK), 0, s, LayPairCountParams{d_docs, n_docs, n_ids, shape, cnt, counters});
+    TRY(Q.count_begin());
+    hipLaunchKernelGGL(k_lay_pair_count, dim3(cdiv64(n_pairs, BLOCK)), dim3(BLOCK), 0, Q.s, LayPairCountParams{Q.d_docs, n_docs, n_ids, shape, cnt, Q.counters});
     HIPCHK(c, hipGetLastError());
-    unsigned long long h_cnt[4] = {0, 0, 0, 0}, n_rows = n_pairs;
-    if (windows) {
-        if (exclusive_scan<unsigned long long>(s, cnt, n_pairs, row_off, (unsigned long long)n_pairs + 1) != 0)
-            return fail(c, YABPE_E_HIP, "scan of the row counts failed");
-        HIPCHK(c, hipMemcpyAsync(&n_rows, row_off + n_pairs, 8, hipMemcpyDeviceToHost, s));
-    }
-    HIPCHK(c, hipMemcpyAsync(h_cnt, counters, 32, hipMemcpyDeviceToHost, s));
-    HIPCHK(c, hipStreamSynchronize(s));
-    if (h_cnt[0] > 0xFFFFFFFFull) return fail(c, YABPE_E_CAPACITY, "a document of %llu ids: row_start and the kept lengths are u32", h_cnt[0]);
-    if (n_rows > LAY_MAX_SLOTS / L) return fail(c, YABPE_E_CAPACITY, "%llu rows of %u slots: at most 2^36 slots in one call", n_rows, L);
-    const unsigned long long n_slots = n_rows * L;
+    TRY(Q.row_offsets(cnt, n_pairs, row_off, &n_rows));
+    TRY(Q.row_budget("row_start and the kept lengths are", n_rows, &n_slots));
     // ---- rows: the record of every output row
     LayPairRec *rec = nullptr;
-    HIPCHK(c, S.get(&rec, n_rows));
-    TRY(dmalloc(c, &c->lay_buf[0], n_slots));
-    for (int k : {1, 2, 3, 5}) TRY(dmalloc(c, &c->lay_buf[k], n_rows));
-    TRY(dmalloc(c, &c->lay_buf[6], (n_slots + 3) / 4));       // (a byte a slot)
-    if (spans) TRY(dmalloc(c, &c->lay_buf[4], 4 * n_slots));  // (16 B a slot)
-    hipLaunchKernelGGL(k_lay_pair_rows, dim3(cdiv64(n_rows, BLOCK)), dim3(BLOCK), 0, s,
-                       LayPairRowsParams{d_docs, n_docs, n_ids, row_off, n_rows, shape, c->lay_buf[1], c->lay_buf[2], c->lay_buf[3], c->lay_buf[5], rec});
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipEventRecord(c->lay_ev[1], s));
+    HIPCHK(c, Q.S.get(&rec, n_rows));
+    TRY(dmalloc(c, &c->lay_buf[LB_ROWS], n_slots));
+    for (int k : {LB_ROW_DOC, LB_ROW_START, LB_ROW_LEN, LB_SECOND_LEN}) TRY(dmalloc(c, &c->lay_buf[k], n_rows));
+    TRY(dmalloc(c, &c->lay_buf[LB_TYPES], (n_slots + 3) / 4));       // (a byte a slot)
+    if (spans) TRY(dmalloc(c, &c->lay_buf[LB_SPANS], 4 * n_slots));  // (16 B a slot)
+    hipLaunchKernelGGL(k_lay_pair_rows, dim3(cdiv64(n_rows, BLOCK)), dim3(BLOCK), 0, Q.s,
+                       LayPairRowsParams{Q.d_docs, n_docs, n_ids, row_off, n_rows, shape, c->lay_buf[LB_ROW_DOC], c->lay_buf[LB_ROW_START],
+                                         c->lay_buf[LB_ROW_LEN], c->lay_buf[LB_SECOND_LEN], rec});
     // ---- write
-    HIPCHK(c, hipEventRecord(c->lay_ev[2], s));
-    const LayPairParams W{d_ids, rec, n_rows, L, lay->flags, pairs->n_sep, pairs->sep_id, LayConst{lay->pad_id, lay->bos_id, lay->eos_id},
-                          c->lay_buf[0], (uint8_t *)c->lay_buf[6], n_slots, d_spans, (ulonglong2 *)c->lay_buf[4]};
-    if (spans)
-        hipLaunchKernelGGL(k_lay_pair_write<true>, dim3(cdiv64(n_slots, LAY_PIECE)), dim3(BLOCK), 0, s, W);
-    else
-        hipLaunchKernelGGL(k_lay_pair_write<false>, dim3(cdiv64(n_slots, LAY_PIECE)), dim3(BLOCK), 0, s, W);
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipEventRecord(c->lay_ev[3], s));
-    const hipError_t se = hipStreamSynchronize(s);
-    if (se != hipSuccess) {
-        yabpe_layout_free(c);
-        return fail(c, YABPE_E_HIP, "layout kernels failed: %s", hipGetErrorString(se));
-    }
-    auto &st = c->lay_stats;
-    st.n_rows = n_rows;
-    st.row_len = L;
-    st.n_truncated_docs = h_cnt[1];
-    st.n_ids_dropped = h_cnt[2];
-    st.n_pad_slots = n_slots - h_cnt[3];
-    layout_times(c);
-    out->rows = c->lay_buf[0];
-    out->types = (uint8_t *)c->lay_buf[6];
-    out->row_pair = c->lay_buf[1];
-    out->row_start = c->lay_buf[2];
-    out->first_len = c->lay_buf[3];
-    out->second_len = c->lay_buf[5];
-    out->spans = (uint64_t *)c->lay_buf[4];
+    TRY(Q.write(LayPairRow{pairs->n_sep, pairs->sep_id}, rec, n_rows, n_slots));
+    TRY(Q.end(n_rows, L, n_slots));
+    out->rows = c->lay_buf[LB_ROWS];
+    out->types = (uint8_t *)c->lay_buf[LB_TYPES];
+    out->row_pair = c->lay_buf[LB_ROW_DOC];
+    out->row_start = c->lay_buf[LB_ROW_START];
+    out->first_len = c->lay_buf[LB_ROW_LEN];
+    out->second_len = c->lay_buf[LB_SECOND_LEN];
+    out->spans = (uint64_t *)c->lay_buf[LB_SPANS];
     out->n_rows = n_rows;
     return YABPE_OK;
 }

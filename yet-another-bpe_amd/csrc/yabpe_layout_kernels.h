@@ -19,8 +19,7 @@
 //             more than one row and the slots kept (one atomic per counter and workgroup).  exclusive_scan -> row_off.
 //   rows      k_lay_win_rows: one thread per output row searches row_off once and writes row_doc, row_start, row_len and the
 //             row's record (first source id, content ids kept).
-//   write     k_lay_win_write: k_lay_pad_write's shape with one record read per row touched; <true> also stores the 16-byte
-//             span of every slot.
+//   write     k_lay_rows_write<LayWinRow, SPANS>: k_lay_pad_write's shape with one record read per row touched.
 //
 // Pairs (yabpe_layout_pairs; contract: BBPETokenizer.encode_batch_pairs): documents 2p and 2p + 1 share a row, cut by one of
 // three truncation rules (one row a pair) or with the second side windowed behind the whole first (Rule 4 of layout_logic.h):
@@ -28,8 +27,11 @@
 //             truncation modes have one row a pair, so their row_off is the identity and no scan runs.
 //   rows      k_lay_pair_rows: one thread per output row (windows mode: one search in row_off) writes row_pair, row_start,
 //             first_len, second_len and the row's record (where each side's kept ids start, how many they are).
-//   write     k_lay_pair_write: k_lay_win_write's shape; next to the 16 bytes of ids a thread stores its 4 slots' type bytes
-//             as one aligned u32.  <true> also stores the 16-byte span of every slot.
+//   write     k_lay_rows_write<LayPairRow, SPANS>: next to the 16 bytes of ids a thread stores its 4 slots' type bytes as one
+//             aligned u32.
+// Windows and pairs share the write kernel: a row policy (LayWinRow / LayPairRow) names the record of a row, the rule that
+// resolves a slot of it and the id a resolved slot holds; SPANS also stores the 16-byte span of every slot.  The three count
+// kernels (k_lay_lengths, k_lay_win_count, k_lay_pair_count) end in lay_commit.
 // No workgroup waits for another; every loop runs over LAY_VPT steps or a search in an array whose length is given.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -54,8 +56,11 @@ struct LayLenParams {
     unsigned long long *counters;   // [0] longest sequence; padded also [1] truncated documents [2] ids dropped [3] slots kept
 };
 
-// The call's counters over a workgroup: v[0] by maximum, v[1..3] by sum; thread 0 holds the result afterwards.
-__device__ __forceinline__ void lay_reduce(unsigned long long (&v)[4], unsigned long long (*s_red)[4]) {
+// How a count kernel ends.  The call's counters over a workgroup: v[0] by maximum, v[1..3] by sum; thread 0 then commits the
+// maximum and (SUMS) the sums that are not zero: one atomic per counter and workgroup.
+template <bool SUMS>
+__device__ __forceinline__ void lay_commit(unsigned long long (&v)[4], unsigned long long *counters) {
+    __shared__ unsigned long long s_red[WPB][4];
     const int lane = threadIdx.x & 63, wib = threadIdx.x >> 6;
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) {
@@ -67,16 +72,19 @@ __device__ __forceinline__ void lay_reduce(unsigned long long (&v)[4], unsigned 
     if (lane == 0)
         for (int k = 0; k < 4; ++k) s_red[wib][k] = v[k];
     __syncthreads();
-    if (threadIdx.x == 0)
-        for (int w = 1; w < WPB; ++w) {
-            v[0] = s_red[w][0] > v[0] ? s_red[w][0] : v[0];
-            for (int k = 1; k < 4; ++k) v[k] += s_red[w][k];
-        }
+    if (threadIdx.x != 0) return;
+    for (int w = 1; w < WPB; ++w) {
+        v[0] = s_red[w][0] > v[0] ? s_red[w][0] : v[0];
+        for (int k = 1; k < 4; ++k) v[k] += s_red[w][k];
+    }
+    atomicMax(&counters[0], v[0]);
+    if (SUMS)
+        for (int k = 1; k < 4; ++k)
+            if (v[k]) atomicAdd(&counters[k], v[k]);
 }
 
 template <bool PACK>
 __global__ __launch_bounds__(BLOCK) void k_lay_lengths(LayLenParams P) {
-    __shared__ unsigned long long s_red[WPB][4];
     const unsigned long long d = (unsigned long long)blockIdx.x * BLOCK + threadIdx.x;
     const uint32_t added = lay_n_added(P.flags);
     unsigned long long v[4] = {0, 0, 0, 0}; // max, truncated, dropped, kept
@@ -95,13 +103,7 @@ __global__ __launch_bounds__(BLOCK) void k_lay_lengths(LayLenParams P) {
             v[3] = kept;
         }
     }
-    lay_reduce(v, s_red);
-    if (threadIdx.x == 0) {
-        atomicMax(&P.counters[0], v[0]);
-        if (!PACK)
-            for (int k = 1; k < 4; ++k)
-                if (v[k]) atomicAdd(&P.counters[k], v[k]);
-    }
+    lay_commit<!PACK>(v, P.counters);
 }
 
 struct LayConst {
@@ -126,6 +128,17 @@ __device__ __forceinline__ void lay_store4(uint32_t *out, unsigned long long f, 
         if (f + k < n_slots) out[f + k] = v[k];
 }
 
+// (row, col) of flat slot f; narrow (uniform): the 32-bit division
+__device__ __forceinline__ void lay_row_col(unsigned long long f, uint32_t row_len, bool narrow, unsigned long long *row, uint32_t *col) {
+    if (narrow) {
+        *row = (uint32_t)f / row_len;
+        *col = (uint32_t)f % row_len;
+    } else {
+        *row = f / row_len;
+        *col = (uint32_t)(f % row_len);
+    }
+}
+
 struct LayPadParams {
     const uint32_t *ids;
     const unsigned long long *doc;  // n_docs document starts
@@ -146,13 +159,7 @@ __global__ __launch_bounds__(BLOCK) void k_lay_pad_write(LayPadParams P) {
         if (f >= P.n_slots) break;
         unsigned long long row;
         uint32_t col;
-        if (narrow) {
-            row = (uint32_t)f / P.row_len;
-            col = (uint32_t)f % P.row_len;
-        } else {
-            row = f / P.row_len;
-            col = (uint32_t)(f % P.row_len);
-        }
+        lay_row_col(f, P.row_len, narrow, &row, &col);
         unsigned long long a = P.doc[row], b = row + 1 < P.n_docs ? P.doc[row + 1] : P.n_ids;
         uint32_t v[4] = {0, 0, 0, 0};
 #pragma unroll
@@ -255,7 +262,6 @@ struct LayWinCountParams {
 };
 
 __global__ __launch_bounds__(BLOCK) void k_lay_win_count(LayWinCountParams P) {
-    __shared__ unsigned long long s_red[WPB][4];
     const unsigned long long d = (unsigned long long)blockIdx.x * BLOCK + threadIdx.x;
     unsigned long long v[4] = {0, 0, 0, 0}; // max, more than one row, (unused), kept
     if (d < P.n_docs) {
@@ -266,12 +272,7 @@ __global__ __launch_bounds__(BLOCK) void k_lay_win_count(LayWinCountParams P) {
         v[1] = rows > 1 ? 1u : 0u;
         v[3] = rows * P.added + (rows - 1) * P.C + lay_win_content(n, rows - 1, P.C, P.step); // every row but the last is full
     }
-    lay_reduce(v, s_red);
-    if (threadIdx.x == 0) {
-        atomicMax(&P.counters[0], v[0]);
-        for (int k = 1; k < 4; ++k)
-            if (v[k]) atomicAdd(&P.counters[k], v[k]);
-    }
+    lay_commit<true>(v, P.counters);
 }
 
 struct LayWinRowsParams {
@@ -298,83 +299,6 @@ __global__ __launch_bounds__(BLOCK) void k_lay_win_rows(LayWinRowsParams P) {
     P.rec[r] = make_ulonglong2(a + k * P.step, content);
 }
 
-struct LayWinParams {
-    const uint32_t *ids;
-    const ulonglong2 *rec;          // n_rows row records (k_lay_win_rows)
-    unsigned long long n_rows;
-    uint32_t row_len, flags;
-    LayConst K;
-    uint32_t *rows;                 // out: n_rows * row_len slots
-    unsigned long long n_slots;
-    const ulonglong2 *spans;        // SPANS: one (start, end) per id ...
-    ulonglong2 *out_spans;          // ... and per output slot
-};
-
-// (row, col) of flat slot f; narrow (uniform): the 32-bit division
-__device__ __forceinline__ void lay_row_col(unsigned long long f, uint32_t row_len, bool narrow, unsigned long long *row, uint32_t *col) {
-    if (narrow) {
-        *row = (uint32_t)f / row_len;
-        *col = (uint32_t)f % row_len;
-    } else {
-        *row = f / row_len;
-        *col = (uint32_t)(f % row_len);
-    }
-}
-
-// k_lay_pad_write's shape: a row's ids are those of its record instead of a whole document.  SPANS: also the span of every slot,
-// in a pass of its own over the same 256 slots of a wave and step: lane l takes the slots l, 64 + l, 128 + l and 192 + l, so the
-// 16-byte loads and stores of a wave lie end to end (4 consecutive slots a lane would put 64 bytes between neighbouring lanes).
-template <bool SPANS>
-__global__ __launch_bounds__(BLOCK) void k_lay_win_write(LayWinParams P) {
-    const unsigned long long f0 = (unsigned long long)blockIdx.x * LAY_PIECE;
-    const bool narrow = P.n_slots <= 0xFFFFFFFFull; // (uniform: the 32-bit division then)
-    const uint32_t lane = threadIdx.x & 63;
-#pragma unroll
-    for (int s = 0; s < LAY_VPT; ++s) {
-        const unsigned long long f = f0 + ((unsigned long long)s * BLOCK + threadIdx.x) * 4;
-        const unsigned long long fw = f - 4ull * lane; // the wave's first slot
-        if ((SPANS ? fw : f) >= P.n_slots) break;
-        if (!SPANS || f < P.n_slots) {
-            unsigned long long row;
-            uint32_t col;
-            lay_row_col(f, P.row_len, narrow, &row, &col);
-            ulonglong2 rec = P.rec[row];
-            uint32_t v[4] = {0, 0, 0, 0};
-#pragma unroll
-            for (int k = 0; k < 4; ++k) { // (past the last slot col runs on past the row's end: a pad slot that is never stored)
-                v[k] = lay_value(P.ids, lay_win_row_slot(rec.x, rec.y, P.row_len, P.flags, col), P.K);
-                if (++col == P.row_len && row + 1 < P.n_rows) { // the next slot opens the next row
-                    col = 0;
-                    rec = P.rec[++row];
-                }
-            }
-            lay_store4(P.rows, f, P.n_slots, v);
-        }
-        if (SPANS) {
-            unsigned long long sa[4] = {0, 0, 0, 0}, sb[4] = {0, 0, 0, 0}; // the slots' (start, end)
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const unsigned long long g = fw + 64 * k + lane;
-                if (g < P.n_slots) {
-                    unsigned long long row;
-                    uint32_t col;
-                    lay_row_col(g, P.row_len, narrow, &row, &col);
-                    const ulonglong2 rec = P.rec[row];
-                    const unsigned long long slot = lay_win_row_slot(rec.x, rec.y, P.row_len, P.flags, col);
-                    if (slot < LAY_SLOT_EOS) {
-                        const ulonglong2 sp = P.spans[slot];
-                        sa[k] = sp.x;
-                        sb[k] = sp.y;
-                    }
-                }
-            }
-#pragma unroll
-            for (int k = 0; k < 4; ++k)
-                if (fw + 64 * k + lane < P.n_slots) P.out_spans[fw + 64 * k + lane] = make_ulonglong2(sa[k], sb[k]);
-        }
-    }
-}
-
 // ---- pairs (yabpe_layout_pairs): documents 2p and 2p + 1 share rows of C content slots (Rule 4 of layout_logic.h)
 struct LayPairShape {
     uint32_t C, mode, stride, n_sep, added; // added = BOS + EOS + n_sep
@@ -398,7 +322,6 @@ struct LayPairCountParams {
 };
 
 __global__ __launch_bounds__(BLOCK) void k_lay_pair_count(LayPairCountParams P) {
-    __shared__ unsigned long long s_red[WPB][4];
     const unsigned long long p = (unsigned long long)blockIdx.x * BLOCK + threadIdx.x;
     unsigned long long v[4] = {0, 0, 0, 0}; // max, cut, dropped, kept
     if (2 * p < P.n_docs) {
@@ -420,12 +343,7 @@ __global__ __launch_bounds__(BLOCK) void k_lay_pair_count(LayPairCountParams P) 
             v[3] = P.S.added + ka + kb;
         }
     }
-    lay_reduce(v, s_red);
-    if (threadIdx.x == 0) {
-        atomicMax(&P.counters[0], v[0]);
-        for (int k = 1; k < 4; ++k)
-            if (v[k]) atomicAdd(&P.counters[k], v[k]);
-    }
+    lay_commit<true>(v, P.counters);
 }
 
 // what the write pass needs of an output row
@@ -463,24 +381,56 @@ __global__ __launch_bounds__(BLOCK) void k_lay_pair_rows(LayPairRowsParams P) {
     P.rec[r] = LayPairRec{a, b + s, (uint32_t)ka, (uint32_t)kb};
 }
 
-struct LayPairParams {
+// ---- the write pass of windows and pairs: one record per output row
+// A row policy has: Rec, the record of a row; TYPES, whether a type byte a slot is stored; slot(), the rule of layout_logic.h that
+// resolves slot `col` of a row; value(), the id a resolved slot holds.
+struct LayWinRow {
+    using Rec = ulonglong2;         // (index into ids of the row's first content id, content ids it keeps)
+    static constexpr bool TYPES = false;
+    __device__ __forceinline__ unsigned long long slot(const Rec &rec, uint32_t row_len, uint32_t flags, uint32_t col, uint32_t *) const {
+        return lay_win_row_slot(rec.x, rec.y, row_len, flags, col);
+    }
+    __device__ __forceinline__ uint32_t value(const uint32_t *ids, unsigned long long slot, const LayConst &K) const {
+        return lay_value(ids, slot, K);
+    }
+};
+
+struct LayPairRow {
+    using Rec = LayPairRec;
+    static constexpr bool TYPES = true;
+    uint32_t n_sep, sep_id;
+    __device__ __forceinline__ unsigned long long slot(const Rec &rec, uint32_t row_len, uint32_t flags, uint32_t col, uint32_t *type) const {
+        return lay_pair_slot(rec.a0, rec.ka, rec.b0, rec.kb, n_sep, row_len, flags, col, type);
+    }
+    __device__ __forceinline__ uint32_t value(const uint32_t *ids, unsigned long long slot, const LayConst &K) const {
+        return slot == LAY_SLOT_SEP ? sep_id : lay_value(ids, slot, K);
+    }
+};
+
+template <class Row>
+struct LayRowsParams {
     const uint32_t *ids;
-    const LayPairRec *rec;          // n_rows row records (k_lay_pair_rows)
+    const typename Row::Rec *rec;   // n_rows row records (k_lay_win_rows / k_lay_pair_rows)
     unsigned long long n_rows;
-    uint32_t row_len, flags, n_sep, sep_id;
+    uint32_t row_len, flags;
+    Row R;
     LayConst K;
     uint32_t *rows;                 // out: n_rows * row_len slots
-    uint8_t *types;                 // out: one byte per slot
+    uint8_t *types;                 // out, Row::TYPES: one byte per slot
     unsigned long long n_slots;
     const ulonglong2 *spans;        // SPANS: one (start, end) per id ...
     ulonglong2 *out_spans;          // ... and per output slot
 };
 
-// k_lay_win_write's shape with two source runs a row.  The 4 slots a thread owns per step are 16 bytes of ids and 4 bytes of types:
-// the flat index of the first is a multiple of 4, so both stores are aligned whatever row_len is, and a wave's type bytes lie
-// end to end (256 B a step).  The last 1..3 slots of the output are stored one by one.
-template <bool SPANS>
-__global__ __launch_bounds__(BLOCK) void k_lay_pair_write(LayPairParams P) {
+// k_lay_pad_write's shape: a row's ids are those of its record instead of a whole document.  The 4 slots a thread owns per step
+// are 16 bytes of ids and (Row::TYPES) 4 bytes of types: the flat index of the first is a multiple of 4, so both stores are aligned
+// whatever row_len is, and a wave's type bytes lie end to end (256 B a step).  The last 1..3 slots of the output are stored one by
+// one.  SPANS: also the span of every slot, in a pass of its own over the same 256 slots of a wave and step: lane l takes the
+// slots l, 64 + l, 128 + l and 192 + l, so the 16-byte loads and stores of a wave lie end to end (4 consecutive slots a lane would
+// put 64 bytes between neighbouring lanes).  A slot below LAY_SLOT_SEP, the lowest of the constants, is a source id and has a span.
+template <class Row, bool SPANS>
+__global__ __launch_bounds__(BLOCK) void k_lay_rows_write(LayRowsParams<Row> P) {
+    using Rec = typename Row::Rec;
     const unsigned long long f0 = (unsigned long long)blockIdx.x * LAY_PIECE;
     const bool narrow = P.n_slots <= 0xFFFFFFFFull; // (uniform: the 32-bit division then)
     const uint32_t lane = threadIdx.x & 63;
@@ -493,23 +443,24 @@ __global__ __launch_bounds__(BLOCK) void k_lay_pair_write(LayPairParams P) {
             unsigned long long row;
             uint32_t col;
             lay_row_col(f, P.row_len, narrow, &row, &col);
-            LayPairRec rec = P.rec[row];
+            Rec rec = P.rec[row];
             uint32_t v[4] = {0, 0, 0, 0}, t[4] = {0, 0, 0, 0};
 #pragma unroll
             for (int k = 0; k < 4; ++k) { // (past the last slot col runs on past the row's end: a pad slot that is never stored)
-                const unsigned long long slot = lay_pair_slot(rec.a0, rec.ka, rec.b0, rec.kb, P.n_sep, P.row_len, P.flags, col, &t[k]);
-                v[k] = slot == LAY_SLOT_SEP ? P.sep_id : lay_value(P.ids, slot, P.K);
+                v[k] = P.R.value(P.ids, P.R.slot(rec, P.row_len, P.flags, col, &t[k]), P.K);
                 if (++col == P.row_len && row + 1 < P.n_rows) { // the next slot opens the next row
                     col = 0;
                     rec = P.rec[++row];
                 }
             }
             lay_store4(P.rows, f, P.n_slots, v);
-            if (f + 4 <= P.n_slots) {
-                *reinterpret_cast<uint32_t *>(P.types + f) = t[0] | t[1] << 8 | t[2] << 16 | t[3] << 24;
-            } else {
-                for (int k = 0; k < 4; ++k)
-                    if (f + k < P.n_slots) P.types[f + k] = (uint8_t)t[k];
+            if (Row::TYPES) {
+                if (f + 4 <= P.n_slots) {
+                    *reinterpret_cast<uint32_t *>(P.types + f) = t[0] | t[1] << 8 | t[2] << 16 | t[3] << 24;
+                } else {
+                    for (int k = 0; k < 4; ++k)
+                        if (f + k < P.n_slots) P.types[f + k] = (uint8_t)t[k];
+                }
             }
         }
         if (SPANS) {
@@ -521,8 +472,8 @@ __global__ __launch_bounds__(BLOCK) void k_lay_pair_write(LayPairParams P) {
                     unsigned long long row;
                     uint32_t col, type;
                     lay_row_col(g, P.row_len, narrow, &row, &col);
-                    const LayPairRec rec = P.rec[row];
-                    const unsigned long long slot = lay_pair_slot(rec.a0, rec.ka, rec.b0, rec.kb, P.n_sep, P.row_len, P.flags, col, &type);
+                    const Rec rec = P.rec[row];
+                    const unsigned long long slot = P.R.slot(rec, P.row_len, P.flags, col, &type);
                     if (slot < LAY_SLOT_SEP) {
                         const ulonglong2 sp = P.spans[slot];
                         sa[k] = sp.x;

@@ -698,6 +698,24 @@ class Context:
         flags = int(flags) | (LAYOUT_BOS if bos_id is not None else 0) | (LAYOUT_EOS if eos_id is not None else 0)
         return (keep, docs), ptr, n, dptr, nd, Layout(int(row_len), int(pad_id), int(bos_id or 0), int(eos_id or 0), flags)
 
+    @staticmethod
+    def _spans_arg(spans, n_ids):
+        """spans: None, a device address, or a u64 array [n_ids, 2] -> (keep-alive array, spans pointer)"""
+        if spans is None or isinstance(spans, int):
+            return None, c_void_p(spans or 0)
+        keep_spans = np.ascontiguousarray(spans, dtype=np.uint64)
+        if keep_spans.size != 2 * n_ids:
+            raise ValueError(f"spans must hold one (start, end) per id: {keep_spans.size} values for {n_ids} ids")
+        if not keep_spans.size:
+            keep_spans = np.zeros(2, np.uint64)  # (no ids: never read, but not NULL -- the call still returns spans)
+        return keep_spans, c_void_p(keep_spans.ctypes.data)
+
+    def _rows_to_host(self, dev_ptr, n_rows, *shape, dtype=np.uint32):
+        """a flat device result -> its host copy [n_rows, *shape] (no elements: nothing to copy, the pointer may be 0)"""
+        n = int(n_rows * np.prod(shape, dtype=np.int64))
+        flat = self.d2h(dev_ptr, n * np.dtype(dtype).itemsize, dtype) if n else np.zeros(0, dtype)
+        return flat.reshape(n_rows, *shape)
+
     def layout_pad(self, ids, n_ids: int | None = None, doc_starts=None, n_docs: int | None = None, row_len: int = 0, pad_id: int = 0,
                    bos_id: int | None = None, eos_id: int | None = None, trunc_left: bool = False, pad_left: bool = False, flags: int = 0):
         """One padded row per document (yabpe_layout_pad).  ids: u32 array (staged) or a device address (n_ids required);
@@ -717,8 +735,7 @@ class Context:
         if n_docs is None:
             n_docs = len(doc_starts) if doc_starts is not None and not isinstance(doc_starts, int) and len(doc_starts) else 1
         dr, dl, rl = self.layout_pad(ids, n_ids, doc_starts, n_docs, **kw)
-        rows = self.d2h(dr, 4 * n_docs * rl, np.uint32) if n_docs * rl else np.zeros(0, np.uint32)
-        return rows.reshape(n_docs, rl), self.d2h(dl, 4 * n_docs, np.uint32)
+        return self._rows_to_host(dr, n_docs, rl), self._rows_to_host(dl, n_docs)
 
     def layout_pack(self, ids, n_ids: int | None = None, doc_starts=None, n_docs: int | None = None, row_len: int = 0, pad_id: int = 0,
                     bos_id: int | None = None, eos_id: int | None = None, drop_last: bool = False, flags: int = 0):
@@ -735,7 +752,7 @@ class Context:
         """-> (ids, doc, pos), each u32[n_rows, row_len], copied to the host."""
         di, dd, dp, nr = self.layout_pack(ids, n_ids, doc_starts, n_docs, **kw)
         rl = int(kw.get("row_len", 0))
-        return tuple(self.d2h(p, 4 * nr * rl, np.uint32).reshape(nr, rl) if nr else np.zeros((0, rl), np.uint32) for p in (di, dd, dp))
+        return tuple(self._rows_to_host(p, nr, rl) for p in (di, dd, dp))
 
     def layout_windows(self, ids, n_ids: int | None = None, doc_starts=None, n_docs: int | None = None, spans=None, row_len: int = 0,
                        stride: int = 0, pad_id: int = 0, bos_id: int | None = None, eos_id: int | None = None, pad_left: bool = False,
@@ -748,15 +765,7 @@ class Context:
         layout_free() or close()."""
         _keep, ptr, n, dptr, nd, lay = self._layout_args(ids, n_ids, doc_starts, n_docs, row_len, pad_id, bos_id, eos_id,
                                                          flags | (LAYOUT_PAD_LEFT if pad_left else 0))
-        if spans is None or isinstance(spans, int):
-            sptr = c_void_p(spans or 0)
-        else:
-            keep_spans = np.ascontiguousarray(spans, dtype=np.uint64)
-            if keep_spans.size != 2 * n:
-                raise ValueError(f"spans must hold one (start, end) per id: {keep_spans.size} values for {n} ids")
-            if not keep_spans.size:
-                keep_spans = np.zeros(2, np.uint64)  # (no ids: never read, but not NULL -- the call still returns spans)
-            sptr = c_void_p(keep_spans.ctypes.data)
+        _keep_spans, sptr = self._spans_arg(spans, n)
         w = Windows()
         self._chk(lib().yabpe_layout_windows(self._h, ptr, n, dptr, nd, sptr, byref(lay), int(stride), byref(w)))
         return w.rows or 0, w.row_doc or 0, w.row_start or 0, w.row_len or 0, w.spans or 0, w.n_rows
@@ -766,8 +775,8 @@ class Context:
         the slots' spans u64[n_rows, row_len, 2]."""
         dr, dd, ds, dl, dsp, nr = self.layout_windows(ids, n_ids, doc_starts, n_docs, spans, **kw)
         rl = int(kw.get("row_len", 0))
-        out = (self.d2h(dr, 4 * nr * rl, np.uint32).reshape(nr, rl),) + tuple(self.d2h(p, 4 * nr, np.uint32) for p in (dd, ds, dl))
-        return out + (self.d2h(dsp, 16 * nr * rl, np.uint64).reshape(nr, rl, 2),) if spans is not None else out
+        out = (self._rows_to_host(dr, nr, rl),) + tuple(self._rows_to_host(p, nr) for p in (dd, ds, dl))
+        return out + (self._rows_to_host(dsp, nr, rl, 2, dtype=np.uint64),) if spans is not None else out
 
     def layout_pairs(self, ids, n_ids: int | None = None, doc_starts=None, n_docs: int | None = None, spans=None, row_len: int = 0,
                      mode="longest_first", stride: int = 0, sep_id: int | None = None, n_sep: int = 1, pad_id: int = 0,
@@ -782,15 +791,7 @@ class Context:
                                                          flags | (LAYOUT_PAD_LEFT if pad_left else 0))
         if doc_starts is not None and not isinstance(doc_starts, int) and len(doc_starts) == 0:
             nd = 0
-        if spans is None or isinstance(spans, int):
-            sptr = c_void_p(spans or 0)
-        else:
-            keep_spans = np.ascontiguousarray(spans, dtype=np.uint64)
-            if keep_spans.size != 2 * n:
-                raise ValueError(f"spans must hold one (start, end) per id: {keep_spans.size} values for {n} ids")
-            if not keep_spans.size:
-                keep_spans = np.zeros(2, np.uint64)  # (no ids: never read, but not NULL -- the call still returns spans)
-            sptr = c_void_p(keep_spans.ctypes.data)
+        _keep_spans, sptr = self._spans_arg(spans, n)
         pairs = Pairs(int(sep_id or 0), int(n_sep) if sep_id is not None else 0, PAIRS_MODES[mode] if isinstance(mode, str) else int(mode),
                       int(stride))
         w = PairRows()
@@ -802,10 +803,8 @@ class Context:
         each) copied to the host, with spans also the slots' spans u64[n_rows, row_len, 2]."""
         dr, dt, *per_row, dsp, nr = self.layout_pairs(ids, n_ids, doc_starts, n_docs, spans, **kw)
         rl = int(kw.get("row_len", 0))
-        get = lambda p, nbytes, dt_: self.d2h(p, nbytes, dt_) if nbytes else np.zeros(0, dt_)  # noqa: E731
-        out = (get(dr, 4 * nr * rl, np.uint32).reshape(nr, rl), get(dt, nr * rl, np.uint8).reshape(nr, rl)) + tuple(
-            get(p, 4 * nr, np.uint32) for p in per_row)
-        return out + (get(dsp, 16 * nr * rl, np.uint64).reshape(nr, rl, 2),) if spans is not None else out
+        out = (self._rows_to_host(dr, nr, rl), self._rows_to_host(dt, nr, rl, dtype=np.uint8)) + tuple(self._rows_to_host(p, nr) for p in per_row)
+        return out + (self._rows_to_host(dsp, nr, rl, 2, dtype=np.uint64),) if spans is not None else out
 
     def layout_free(self) -> None:
         self._chk(lib().yabpe_layout_free(self._h))

@@ -673,13 +673,18 @@ class BBPETokenizer:
         ids, off, spans = ids.tolist(), off.tolist(), [tuple(p) for p in spans.tolist()]
         return [(ids[off[d]:off[d + 1]], spans[off[d]:off[d + 1]]) for d in range(len(off) - 1)]
 
-    def _device_encode_for_layout(self, ctx, inp, dropout, seed):
-        """-> the device results the layout passes read: yabpe_encode's, or yabpe_encode_dropout's when dropout > 0"""
+    def _device_encode_for_layout(self, ctx, inp, dropout=0.0, seed=0, offsets=None):
+        """-> (ids pointer, document starts pointer, n_ids, spans): the device results the layout passes read -- yabpe_encode's,
+        yabpe_encode_dropout's when dropout > 0, or with offsets ("char" / "byte") yabpe_encode_spans'.  spans: None without
+        offsets, else the pointer, or the empty [0, 2] array when there are no ids."""
         T, seed = self._dropout_threshold(dropout), self._u64(seed, "seed")
         text, n_bytes, starts = self._device_text(ctx, inp)
+        if offsets is not None:
+            di, dd, ds, ni = ctx.encode_spans(text, n_bytes, doc_starts=starts, chars=offsets == "char")
+            return di, dd, ni, ds or np.zeros((0, 2), np.uint64)
         if T == 0:
-            return ctx.encode(text, n_bytes, doc_starts=starts)
-        return ctx.encode_dropout(text, T, seed, n_bytes, doc_starts=starts)
+            return ctx.encode(text, n_bytes, doc_starts=starts) + (None,)
+        return ctx.encode_dropout(text, T, seed, n_bytes, doc_starts=starts) + (None,)
 
     def encode_array_dropout(self, texts, p: float, seed: int = 0) -> tuple[np.ndarray, np.ndarray]:
         """encode_batch_dropout(texts, p, seed) on the GPU, id for id: `texts` and the results as encode_array's (one bytes
@@ -711,7 +716,7 @@ class BBPETokenizer:
         if inp is None or L == 0:  # (no rows, or rows of no slots: with BOS / EOS L is at least 1)
             return np.zeros((n_docs, L or 0), np.uint32), np.zeros(n_docs, np.uint32)
         ctx = self._device()
-        di, dd, ni = self._device_encode_for_layout(ctx, inp, dropout, seed)
+        di, dd, ni, _spans = self._device_encode_for_layout(ctx, inp, dropout, seed)
         return ctx.layout_pad_to_host(di, ni, dd, n_docs, row_len=L or 0, pad_id=pad, bos_id=bos, eos_id=eos,
                                       trunc_left=truncation == "left", pad_left=padding_side == "left")
 
@@ -727,7 +732,7 @@ class BBPETokenizer:
         if inp is None:
             return tuple(np.zeros((0, seq_len), np.uint32) for _ in range(3))
         ctx = self._device()
-        di, dd, ni = self._device_encode_for_layout(ctx, inp, dropout, seed)
+        di, dd, ni, _spans = self._device_encode_for_layout(ctx, inp, dropout, seed)
         return ctx.layout_pack_to_host(di, ni, dd, len(inp[1]), row_len=seq_len, pad_id=pad, bos_id=bos, eos_id=eos, drop_last=drop_last)
 
     def encode_array_windows(self, texts, max_length: int, stride: int = 0, *, pad_id: int | None = None, bos_id: int | None = None,
@@ -744,13 +749,9 @@ class BBPETokenizer:
             out = (np.zeros((0, L), np.uint32),) + tuple(np.zeros(0, np.uint32) for _ in range(3))
             return out if offsets is None else out + (np.zeros((0, L, 2), np.uint64),)
         ctx = self._device()
-        kw = dict(row_len=L, stride=stride, pad_id=pad, bos_id=bos, eos_id=eos, pad_left=padding_side == "left")
-        if offsets is None:
-            di, dd, ni = self._device_encode_for_layout(ctx, inp, dropout, seed)
-            return ctx.layout_windows_to_host(di, ni, dd, len(inp[1]), **kw)
-        text, n_bytes, starts = self._device_text(ctx, inp)
-        di, dd, ds, ni = ctx.encode_spans(text, n_bytes, doc_starts=starts, chars=offsets == "char")
-        return ctx.layout_windows_to_host(di, ni, dd, len(inp[1]), ds or np.zeros((0, 2), np.uint64), **kw)
+        di, dd, ni, spans = self._device_encode_for_layout(ctx, inp, dropout, seed, offsets)
+        return ctx.layout_windows_to_host(di, ni, dd, len(inp[1]), spans, row_len=L, stride=stride, pad_id=pad, bos_id=bos, eos_id=eos,
+                                          pad_left=padding_side == "left")
 
     def encode_array_pairs(self, firsts: Sequence[str], seconds: Sequence[str], max_length: int, *, truncation: str = "longest_first",
                            stride: int = 0, sep_id: int | None = None, n_sep: int = 1, pad_id: int | None = None,
@@ -769,14 +770,9 @@ class BBPETokenizer:
             out = (np.zeros((0, L), np.uint32), np.zeros((0, L), np.uint8)) + tuple(np.zeros(0, np.uint32) for _ in range(4))
             return out if offsets is None else out + (np.zeros((0, L, 2), np.uint64),)
         ctx = self._device()
-        kw = dict(row_len=L, mode=truncation, stride=stride, sep_id=sep, n_sep=n_sep, pad_id=pad, bos_id=bos, eos_id=eos,
-                  pad_left=padding_side == "left")
-        text, n_bytes, starts = self._device_text(ctx, inp)
-        if offsets is None:
-            di, dd, ni = ctx.encode(text, n_bytes, doc_starts=starts)
-            return ctx.layout_pairs_to_host(di, ni, dd, len(inp[1]), **kw)
-        di, dd, ds, ni = ctx.encode_spans(text, n_bytes, doc_starts=starts, chars=offsets == "char")
-        return ctx.layout_pairs_to_host(di, ni, dd, len(inp[1]), ds or np.zeros((0, 2), np.uint64), **kw)
+        di, dd, ni, spans = self._device_encode_for_layout(ctx, inp, offsets=offsets)
+        return ctx.layout_pairs_to_host(di, ni, dd, len(inp[1]), spans, row_len=L, mode=truncation, stride=stride, sep_id=sep, n_sep=n_sep,
+                                        pad_id=pad, bos_id=bos, eos_id=eos, pad_left=padding_side == "left")
 
     # ------------------------------------------------------------------ decode (tokenizer.py:324-349)
     def decode(self, ids: Sequence[int]) -> str:
