@@ -1774,6 +1774,15 @@ static int load_words_impl(yabpe_ctx *c, const uint8_t *bytes, const uint64_t *w
         HIPCHK(c, hipMemcpy(&ov, &c->scratch64[1], 8, hipMemcpyDeviceToHost));
         if (ov & 0xFFFFFFFFu) return fail(c, YABPE_E_CAPACITY, "a word frequency exceeds 2^32-1");
     }
+    // every word of the shard is a long one: the tiles counted for their bytes hold no word (a placeholder each in the weighted
+    // layout, read by nobody without a word beside it) -- this rank keeps no tile and launches no apply kernel over them
+    if (c->n_long && c->n_long == n_words) {
+        dfree(c->tiles); dfree(c->tile_len); dfree(c->tile_wbase);
+        c->tiles = nullptr;
+        c->tile_len = c->tile_wbase = nullptr;
+        c->n_tiles = 0;
+        c->tiles_cap = 0;
+    }
     // ---- long words: own buffer, one workgroup per word
     if (c->n_long) {
         std::vector<uint32_t> lw(c->n_long);
