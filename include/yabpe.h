@@ -650,8 +650,35 @@ typedef struct yabpe_pair_rows_t {
 } yabpe_pair_rows_t;
 int yabpe_layout_pairs(yabpe_ctx *ctx, const uint32_t *ids, uint64_t n_ids, const uint64_t *doc_off, uint32_t n_docs,
                        const uint64_t *spans, const yabpe_layout_t *layout, const yabpe_pairs_t *pairs, yabpe_pair_rows_t *out);
+/* Whole documents (BBPETokenizer.encode_batch_fit on the device): rows of row_len slots that hold whole sequences, packed by
+ * best-fit decreasing; no sequence is cut across two rows.  ids, doc_off and layout as the calls above take them (host or device
+ * memory; the encoder's results pass straight in and are left alone); no model is needed.  flags: YABPE_LAYOUT_BOS / _EOS.
+ * With C = row_len: a seq(d) longer than C loses content ids from its end as in yabpe_layout_pad (BOS and EOS survive), n_d =
+ * min(len(seq(d)), C); a document with n_d == 0 takes no slot and is in no row.
+ * Plan: H[k] = the documents with n_d == k.  The state maps a shape (the sequence lengths of a row in placement order, non-
+ * increasing; room(s) = C - sum(s)) to the number of rows that have it.  For k = C down to 1 with n = H[k] sequences left: among
+ * the shapes with a row left and room >= k the one with the smallest room, of several the lexicographically greatest; with t =
+ * room / k, min(rows, n / t) rows of it take t sequences each and, if rows of it and sequences remain, one more row takes the
+ * rest; with no such shape n / t rows of t = C / k sequences open and one row of the n % t left.  Rows: the shapes in descending
+ * tuple order, the rows of a shape consecutive; a row holds its sequences end to end from column 0, then pad_id.  For every k the
+ * documents with n_d == k, in ascending d, take the places of length k in row order, within a row left to right.  The rows use
+ * no more room than best-fit decreasing one document at a time, and the result depends on the documents alone.
+ * Results (device memory owned by the library, buffers of their own, released as the other layout results are): per slot the id,
+ * the document it came from and its index inside seq(d) as yabpe_layout_pack gives them (pad slots: pad_id, 0xFFFFFFFF, 0);
+ * used[r] = the filled slots of row r.  n_docs = 0, or only empty sequences: no rows.
+ * YABPE_E_INVALID: row_len == 0, row_len < n_added or row_len > 2^24 - 1 (the sort keys have three 8-bit digits); any flag but
+ * YABPE_LAYOUT_BOS / _EOS; a bad doc_off.  YABPE_E_CAPACITY: more than 2^36 output slots.  Every error is found before a result
+ * buffer is allocated.  yabpe_layout_stats: n_truncated_docs, n_ids_dropped and n_pad_slots as for yabpe_layout_pad; lengths_ms =
+ * lengths + histogram + sort, write_ms = the output pass, total_ms includes the plan, which runs on the host. */
+typedef struct yabpe_fit_rows_t {
+    uint32_t *ids, *doc, *pos;   /* n_rows * row_len each */
+    uint32_t *used;              /* n_rows */
+    uint64_t n_rows;
+} yabpe_fit_rows_t;
+int yabpe_layout_fit(yabpe_ctx *ctx, const uint32_t *ids, uint64_t n_ids, const uint64_t *doc_off, uint32_t n_docs,
+                     const yabpe_layout_t *layout, yabpe_fit_rows_t *out);
 int yabpe_layout_free(yabpe_ctx *ctx);
-/* What the last yabpe_layout_pad / yabpe_layout_pack / yabpe_layout_windows / yabpe_layout_pairs saw, and the device time of
+/* What the last yabpe_layout_pad / yabpe_layout_pack / yabpe_layout_windows / yabpe_layout_pairs / yabpe_layout_fit saw, and the device time of
  * its phases (HIP events around each phase's launches). */
 typedef struct yabpe_layout_stats_t {
     uint64_t n_ids, n_docs;

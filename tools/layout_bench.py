@@ -12,8 +12,12 @@ the max_length that cuts about half the pairs, and windows at max_length 1536 wi
 first side of about 1,000 ids is in every row), each without and with byte spans;
 the device time of the phases and the output bytes per second of the write pass (4 B of ids + 1 B of type a slot, + 16 B with
 spans), next to the same figure of yabpe_layout_windows at the same row length and stride on the same ids.
-   python tools/layout_bench.py [--mib 1024] [--merges 32000] [--reps 3] [--host-mib 64] [--pairs] [--json out.json]"""
-import argparse, ctypes, json, sys, time
+--fit: only yabpe_layout_fit (whole documents, best-fit decreasing) next to yabpe_layout_pack on the same ids, both at seq_len 2048
+with an EOS: rows and pad slots of both, the device time of the phases, the bytes read + written over write_ms of both write
+passes and their ratio; the plan of the same histogram run once more on the host through the CPU model of the rules
+(tests/hostmodel/fit_model.cpp, the same fit_plan the driver calls) for its shapes, steps and wall time.
+   python tools/layout_bench.py [--mib 1024] [--merges 32000] [--reps 3] [--host-mib 64] [--pairs | --fit] [--json out.json]"""
+import argparse, ctypes, json, subprocess, sys, time
 from pathlib import Path
 REPO = Path(__file__).resolve().parent.parent
 sys.path.insert(0, str(REPO / "yet-another-bpe_amd"))
@@ -29,6 +33,7 @@ ap.add_argument("--reps", type=int, default=3)
 ap.add_argument("--host-mib", type=int, default=64)
 ap.add_argument("--doc-ids", type=int, default=1000)
 ap.add_argument("--pairs", action="store_true")
+ap.add_argument("--fit", action="store_true")
 ap.add_argument("--json", default="")
 a = ap.parse_args()
 PAD_LEN, PACK_LEN, EOS = 1024, 2048, 2
@@ -142,6 +147,43 @@ with _native.Context() as gen:
                 pairs["write_rate_vs_layout_windows"] = round(pairs["write_pass_output_GB_per_s"] / yard["write_pass_output_GB_per_s"], 3)
                 out["pairs_" + name + tag] = pairs
                 out["layout_windows_" + str(L) + "_stride_" + str(stride) + tag] = yard
+        gen.layout_free()
+        emit(out)
+        sys.exit(0)
+    if a.fit:
+        hm = REPO / "tests" / "hostmodel"
+        if not (hm / "libfit_model.so").exists():
+            subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-o", str(hm / "libfit_model.so"), str(hm / "fit_model.cpp")])
+        model = ctypes.CDLL(str(hm / "libfit_model.so"))
+        kept = np.minimum(lens + 1, PACK_LEN)  # n_d: the EOS survives the cut
+        hist = np.bincount(kept, minlength=PACK_LEN + 1).astype(np.uint32)
+        first, place, pl = np.zeros(n_docs + 2, np.uint64), np.zeros(n_docs + 2, np.uint32), np.zeros(4 * (n_docs + 2), np.uint32)
+        ns, npl, nr, steps = ctypes.c_uint32(0), ctypes.c_uint32(0), ctypes.c_uint64(0), ctypes.c_uint64(0)
+        plan_ms = []
+        for _ in range(a.reps + 1):
+            t0 = time.perf_counter()
+            rc = model.fit_model_plan(ctypes.c_void_p(hist.ctypes.data), ctypes.c_uint32(PACK_LEN), ctypes.c_void_p(first.ctypes.data),
+                                      ctypes.c_void_p(place.ctypes.data), ctypes.c_void_p(pl.ctypes.data), ctypes.c_uint32(n_docs + 2),
+                                      ctypes.c_uint32(n_docs + 2), ctypes.byref(ns), ctypes.byref(npl), ctypes.byref(nr), ctypes.byref(steps))
+            plan_ms.append((time.perf_counter() - t0) * 1e3)
+            assert rc == 0
+        kw = dict(row_len=PACK_LEN, pad_id=0, eos_id=EOS)
+        out = {"text_bytes": tn, "merges": len(merges), "ids": ni, "docs": n_docs, "mean_ids_per_doc": round(ni / n_docs, 1), "seq_len": PACK_LEN,
+               "plan": {"shapes": ns.value, "places": npl.value, "steps": steps.value, "rows": nr.value,
+                        "host_wall_ms_best": round(min(plan_ms[1:]), 3), "host_wall_ms_all": [round(t, 3) for t in plan_ms[1:]]}}
+        # bytes a write pass moves: the ids it keeps, the document starts (and the sorted documents), 12 B a slot (and `used`)
+        reads = {"pack": 4 * ni + 8 * (n_docs + 1), "fit": 4 * int((kept - 1).sum()) + 8 * (n_docs + 1) + 4 * n_docs}
+        for name, call in (("pack", gen.layout_pack), ("fit", gen.layout_fit)):
+            st, all_ms = timed(lambda: call(di, ni, dd, n_docs, **kw))
+            n_slots = st["n_rows"] * PACK_LEN
+            moved = reads[name] + 12 * n_slots + (4 * st["n_rows"] if name == "fit" else 0)
+            out[name] = {"rows": st["n_rows"], "pad_slots": st["n_pad_slots"], "fill": round(1 - st["n_pad_slots"] / max(1, n_slots), 5),
+                         "truncated_docs": st["n_truncated_docs"], "ids_dropped": st["n_ids_dropped"], "lengths_ms": round(st["lengths_ms"], 3),
+                         "write_ms": round(st["write_ms"], 3), "total_ms": round(st["total_ms"], 3), "all_total_ms": all_ms,
+                         "host_gap_ms": round(st["total_ms"] - st["lengths_ms"] - st["write_ms"], 3), "write_bytes": moved,
+                         "write_GB_per_s": round(moved / st["write_ms"] / 1e6, 1)}
+        assert out["fit"]["rows"] == nr.value
+        out["fit_write_rate_vs_pack_write"] = round(out["fit"]["write_GB_per_s"] / out["pack"]["write_GB_per_s"], 3)
         gen.layout_free()
         emit(out)
         sys.exit(0)

@@ -30,6 +30,7 @@
 #include "yabpe_dropout_kernels.h"
 #include "yabpe_decode_kernels.h"
 #include "yabpe_layout_kernels.h"
+#include "yabpe_fit_kernels.h"
 #include "yabpe_replay_kernels.h"
 #include "yabpe_pool_kernels.h"
 #include "yabpe_norm_kernels.h"
@@ -104,7 +105,8 @@ struct EventPair {
 
 // The slots of yabpe_ctx::lay_buf, u32 arrays unless said otherwise.  yabpe_layout_pad: ROWS, ROW_DOC (the kept lengths);
 // yabpe_layout_pack: ROWS, ROW_DOC, ROW_START (ids, doc, pos: a slot each); yabpe_layout_windows: ROWS .. ROW_LEN, SPANS;
-// yabpe_layout_pairs: all seven (ROW_DOC = row_pair, ROW_LEN = first_len).
+// yabpe_layout_pairs: all seven (ROW_DOC = row_pair, ROW_LEN = first_len); yabpe_layout_fit: ROWS, ROW_DOC, ROW_START (ids, doc,
+// pos: a slot each) and ROW_LEN (used).
 enum LayBuf {
     LB_ROWS,        // the ids of every output slot
     LB_ROW_DOC,     // per row: the document (pair) it comes from
@@ -1049,7 +1051,7 @@ struct TextPass {
     }
 };
 
-// ---- fixed-shape batches (yabpe_layout_pad / _pack / _windows / _pairs)
+// ---- fixed-shape batches (yabpe_layout_pad / _pack / _windows / _pairs / _fit)
 // flags outside mode_flags, the ones the call takes (an unknown flag is one of them)
 int layout_flags(yabpe_ctx *c, const yabpe_layout_t *lay, uint32_t mode_flags) {
     if (lay->flags & ~mode_flags)
@@ -1057,7 +1059,7 @@ int layout_flags(yabpe_ctx *c, const yabpe_layout_t *lay, uint32_t mode_flags) {
     return 0;
 }
 
-// What the four layout calls share, as steps a call runs in order (between them: its own checks, buffers and kernels):
+// What the layout calls share, as steps a call runs in order (between them: its own checks, buffers and kernels):
 // begin(), count_begin(), [row_offsets(), row_budget(), write()], end().  lay_ev[0..1] bracket the lengths pass (windows and
 // pairs: count + scan + rows), [2..3] the write kernel.  A call that its own checks or begin()'s refuse has freed nothing.
 struct LayoutCall {
@@ -1173,6 +1175,34 @@ struct LayoutCall {
         return 0;
     }
 };
+
+// The documents stably by their keys (fit_logic.h), in `passes` radix passes of 8 bits from the lowest digit; *sorted = the
+// documents in that order (a buffer of S).
+int fit_sort(yabpe_ctx *c, Scratch &S, hipStream_t s, const uint32_t *key, uint32_t n, uint32_t passes, const uint32_t **sorted) {
+    const uint32_t n_tiles = cdiv64(n, FIT_SORT_TILE);
+    const unsigned long long n_counts = (unsigned long long)BLOCK * n_tiles;
+    uint32_t *kbuf[2] = {nullptr, nullptr}, *vbuf[2] = {nullptr, nullptr}, *counts = nullptr;
+    unsigned long long *offs = nullptr;
+    for (int k = 0; k < 2; ++k) {
+        HIPCHK(c, S.get(&kbuf[k], n));
+        HIPCHK(c, S.get(&vbuf[k], n));
+    }
+    HIPCHK(c, S.get(&counts, n_counts));
+    HIPCHK(c, S.get(&offs, n_counts));
+    const uint32_t *kin = key, *vin = nullptr;  // (the first pass reads the identity)
+    for (uint32_t pass = 0; pass < passes; ++pass) {
+        hipLaunchKernelGGL(k_fit_sort_count, dim3(n_tiles), dim3(BLOCK), 0, s, kin, n, pass, counts, n_tiles);
+        HIPCHK(c, hipGetLastError());
+        if (exclusive_scan<uint32_t>(s, counts, n_counts, offs, n_counts) != 0) return fail(c, YABPE_E_HIP, "scan of the digit counts failed");
+        hipLaunchKernelGGL(k_fit_sort_scatter, dim3(n_tiles), dim3(BLOCK), 0, s,
+                           FitScatterParams{kin, vin, n, pass, offs, n_tiles, kbuf[pass & 1], vbuf[pass & 1]});
+        HIPCHK(c, hipGetLastError());
+        kin = kbuf[pass & 1];
+        vin = vbuf[pass & 1];
+    }
+    *sorted = vin;
+    return 0;
+}
 
 // ---- what the u16 and the u32 drivers share (yabpe_id32_host.h): the differences between the two stay with the callers
 // N timing events of one call: destroyed on every way out
@@ -4450,6 +4480,78 @@ int yabpe_layout_pairs(yabpe_ctx *c, const uint32_t *ids, uint64_t n_ids, const 
     out->first_len = c->lay_buf[LB_ROW_LEN];
     out->second_len = c->lay_buf[LB_SECOND_LEN];
     out->spans = (uint64_t *)c->lay_buf[LB_SPANS];
+    out->n_rows = n_rows;
+    return YABPE_OK;
+}
+
+int yabpe_layout_fit(yabpe_ctx *c, const uint32_t *ids, uint64_t n_ids, const uint64_t *doc_off, uint32_t n_docs, const yabpe_layout_t *lay,
+                     yabpe_fit_rows_t *out) {
+    if (!c || !out) return YABPE_E_INVALID;
+    HIPCHK(c, hipSetDevice(c->device));
+    *out = yabpe_fit_rows_t{};
+    if (!lay) return fail(c, YABPE_E_INVALID, "layout is NULL");
+    TRY(layout_flags(c, lay, LAY_FIT_FLAGS));  // (ahead of begin(): the checks below read the flags)
+    if (lay->row_len == 0) return fail(c, YABPE_E_INVALID, "row_len is 0: a row holds at least one slot");
+    if (lay->row_len < lay_n_added(lay->flags)) return fail(c, YABPE_E_INVALID, "row_len %u cannot hold BOS and EOS", lay->row_len);
+    if (lay->row_len > FIT_MAX_ROW) return fail(c, YABPE_E_INVALID, "row_len %u: at most 2^24 - 1 slots a row", lay->row_len);
+    const uint32_t C = lay->row_len;
+    if (n_docs == 0) { // no documents: no rows
+        yabpe_layout_free(c);
+        c->lay_stats = yabpe_layout_stats_t{};
+        c->lay_stats.row_len = C;
+        return YABPE_OK;
+    }
+    LayoutCall Q(c);
+    TRY(Q.begin(ids, n_ids, doc_off, &n_docs, nullptr, lay, LAY_FIT_FLAGS));
+    // ---- lengths: the key n_d of every document, their histogram, the call's counters; then the documents stably by key
+    uint32_t *key = nullptr, *hist = nullptr;
+    HIPCHK(c, Q.S.get(&key, n_docs));
+    HIPCHK(c, Q.S.get(&hist, (uint64_t)C + 1));
+    std::vector<uint32_t> h_hist((size_t)C + 1, 0);
+    TRY(Q.count_begin());
+    HIPCHK(c, hipMemsetAsync(hist, 0, ((size_t)C + 1) * 4, Q.s));
+    const FitLenParams LP{Q.d_docs, n_docs, n_ids, C, lay->flags, key, hist, Q.counters};
+    if (C < (uint32_t)FIT_HIST_LDS)
+        hipLaunchKernelGGL(k_fit_lengths<true>, dim3(cdiv64(n_docs, BLOCK)), dim3(BLOCK), 0, Q.s, LP);
+    else
+        hipLaunchKernelGGL(k_fit_lengths<false>, dim3(cdiv64(n_docs, BLOCK)), dim3(BLOCK), 0, Q.s, LP);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(h_hist.data(), hist, ((size_t)C + 1) * 4, hipMemcpyDeviceToHost, Q.s));
+    TRY(Q.row_offsets(nullptr, 0, nullptr, nullptr));
+    const uint32_t max_key = (uint32_t)std::min<unsigned long long>(Q.h_cnt[0], C);  // 0: every sequence is empty, no rows
+    const uint32_t *sorted = nullptr;
+    if (max_key) TRY(fit_sort(c, Q.S, Q.s, key, n_docs, fit_sort_passes(max_key), &sorted));
+    HIPCHK(c, hipEventRecord(c->lay_ev[1], Q.s));
+    // ---- plan (host, beside the sort): histogram -> shapes, rows, places
+    FitPlan plan;
+    if (max_key) fit_plan(h_hist.data(), C, &plan);
+    const unsigned long long n_rows = plan.n_rows;
+    if (n_rows > LAY_MAX_SLOTS / C) return fail(c, YABPE_E_CAPACITY, "%llu rows of %u slots: at most 2^36 slots in one call", n_rows, C);
+    const unsigned long long n_slots = n_rows * C;
+    unsigned long long *d_first = nullptr;
+    uint32_t *d_place = nullptr;
+    FitPlace *d_pl = nullptr;
+    if (n_rows) {
+        HIPCHK(c, Q.S.get(&d_first, plan.first.size()));
+        HIPCHK(c, Q.S.get(&d_place, plan.place.size()));
+        HIPCHK(c, Q.S.get(&d_pl, plan.pl.size()));
+        HIPCHK(c, hipMemcpyAsync(d_first, plan.first.data(), plan.first.size() * sizeof(unsigned long long), hipMemcpyHostToDevice, Q.s));
+        HIPCHK(c, hipMemcpyAsync(d_place, plan.place.data(), plan.place.size() * sizeof(uint32_t), hipMemcpyHostToDevice, Q.s));
+        HIPCHK(c, hipMemcpyAsync(d_pl, plan.pl.data(), plan.pl.size() * sizeof(FitPlace), hipMemcpyHostToDevice, Q.s));
+    }
+    // ---- write
+    for (int k : {LB_ROWS, LB_ROW_DOC, LB_ROW_START}) TRY(dmalloc(c, &c->lay_buf[k], n_slots));
+    TRY(dmalloc(c, &c->lay_buf[LB_ROW_LEN], n_rows));
+    HIPCHK(c, hipEventRecord(c->lay_ev[2], Q.s));
+    if (n_slots)
+        hipLaunchKernelGGL(k_fit_write, dim3(cdiv64(n_slots, LAY_PIECE)), dim3(BLOCK), 0, Q.s,
+                           FitWriteParams{Q.d_ids, Q.d_docs, n_docs, n_ids, sorted, d_first, d_place, d_pl, plan.n_shapes(), n_slots, C, lay->flags,
+                                          Q.K(), c->lay_buf[LB_ROWS], c->lay_buf[LB_ROW_DOC], c->lay_buf[LB_ROW_START], c->lay_buf[LB_ROW_LEN]});
+    TRY(Q.end(n_rows, C, n_slots));
+    out->ids = c->lay_buf[LB_ROWS];
+    out->doc = c->lay_buf[LB_ROW_DOC];
+    out->pos = c->lay_buf[LB_ROW_START];
+    out->used = c->lay_buf[LB_ROW_LEN];
     out->n_rows = n_rows;
     return YABPE_OK;
 }

@@ -94,6 +94,11 @@ class PairRows(ctypes.Structure):
     _fields_ = [(n, c_void_p) for n in ("rows", "types", "row_pair", "row_start", "first_len", "second_len", "spans")] + [("n_rows", c_uint64)]
 
 
+class FitRows(ctypes.Structure):
+    """yabpe_fit_rows_t"""
+    _fields_ = [(n, c_void_p) for n in ("ids", "doc", "pos", "used")] + [("n_rows", c_uint64)]
+
+
 class ResumeStats(ctypes.Structure):
     _fields_ = [(n, c_uint64) for n in ("n_unique", "n_long", "tokens")] + [(n, c_double) for n in ("segment_ms", "build_ms")]
 
@@ -137,7 +142,7 @@ SYMBOLS = [
     "yabpe_encode_set_model", "yabpe_encode", "yabpe_encode_spans", "yabpe_encode_dropout", "yabpe_encode_free", "yabpe_encode_stats", "yabpe_encode_checksum",
     "yabpe_decode_set_model", "yabpe_decode", "yabpe_decode_free", "yabpe_decode_stats",
     "yabpe_load_words_resumed", "yabpe_resume_stats",
-    "yabpe_layout_pad", "yabpe_layout_pack", "yabpe_layout_windows", "yabpe_layout_pairs", "yabpe_layout_free", "yabpe_layout_stats",
+    "yabpe_layout_pad", "yabpe_layout_pack", "yabpe_layout_windows", "yabpe_layout_pairs", "yabpe_layout_fit", "yabpe_layout_free", "yabpe_layout_stats",
     "yabpe_pool_add", "yabpe_pool_get", "yabpe_pool_clear", "yabpe_pool_stats",
     "yabpe_normalize", "yabpe_normalize_free", "yabpe_normalize_stats",
     "yabpe_utf8_repair", "yabpe_utf8_repair_free", "yabpe_utf8_repair_stats",
@@ -209,6 +214,7 @@ def lib() -> ctypes.CDLL:
                                         POINTER(c_void_p), POINTER(c_uint64)]
         L.yabpe_layout_windows.argtypes = [c_void_p, c_void_p, c_uint64, c_void_p, c_uint32, c_void_p, POINTER(Layout), c_uint32, POINTER(Windows)]
         L.yabpe_layout_pairs.argtypes = [c_void_p, c_void_p, c_uint64, c_void_p, c_uint32, c_void_p, POINTER(Layout), POINTER(Pairs), POINTER(PairRows)]
+        L.yabpe_layout_fit.argtypes = [c_void_p, c_void_p, c_uint64, c_void_p, c_uint32, POINTER(Layout), POINTER(FitRows)]
         L.yabpe_layout_free.argtypes = [c_void_p]
         L.yabpe_layout_stats.argtypes = [c_void_p, POINTER(LayoutStats)]
         L.yabpe_pool_add.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_uint64]
@@ -805,6 +811,25 @@ class Context:
         rl = int(kw.get("row_len", 0))
         out = (self._rows_to_host(dr, nr, rl), self._rows_to_host(dt, nr, rl, dtype=np.uint8)) + tuple(self._rows_to_host(p, nr) for p in per_row)
         return out + (self._rows_to_host(dsp, nr, rl, 2, dtype=np.uint64),) if spans is not None else out
+
+    def layout_fit(self, ids, n_ids: int | None = None, doc_starts=None, n_docs: int | None = None, row_len: int = 0, pad_id: int = 0,
+                   bos_id: int | None = None, eos_id: int | None = None, flags: int = 0):
+        """Whole documents in rows of row_len, packed by best-fit decreasing (yabpe_layout_fit); ids, doc_starts and the ids of
+        the layout as layout_pad takes them (an empty doc_starts array: no documents).
+        -> (dev_ids_ptr, dev_doc_ptr, dev_pos_ptr: u32[n_rows * row_len] each, dev_used_ptr u32[n_rows], n_rows); the buffers
+        live until the next layout call, layout_free() or close()."""
+        _keep, ptr, n, dptr, nd, lay = self._layout_args(ids, n_ids, doc_starts, n_docs, row_len, pad_id, bos_id, eos_id, flags)
+        if doc_starts is not None and not isinstance(doc_starts, int) and len(doc_starts) == 0:
+            nd = 0
+        w = FitRows()
+        self._chk(lib().yabpe_layout_fit(self._h, ptr, n, dptr, nd, byref(lay), byref(w)))
+        return w.ids or 0, w.doc or 0, w.pos or 0, w.used or 0, w.n_rows
+
+    def layout_fit_to_host(self, ids, n_ids: int | None = None, doc_starts=None, n_docs: int | None = None, **kw):
+        """-> (ids, doc, pos: u32[n_rows, row_len] each, used u32[n_rows]) copied to the host."""
+        di, dd, dp, du, nr = self.layout_fit(ids, n_ids, doc_starts, n_docs, **kw)
+        rl = int(kw.get("row_len", 0))
+        return tuple(self._rows_to_host(p, nr, rl) for p in (di, dd, dp)) + (self._rows_to_host(du, nr),)
 
     def layout_free(self) -> None:
         self._chk(lib().yabpe_layout_free(self._h))

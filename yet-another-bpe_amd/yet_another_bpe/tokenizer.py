@@ -396,6 +396,71 @@ class BBPETokenizer:
         cut = lambda flat, filler: [(flat + [filler] * fill)[r * seq_len:(r + 1) * seq_len] for r in range(n_rows)]  # noqa: E731
         return cut(stream, pad), cut(doc, 0xFFFFFFFF), cut(pos, 0)
 
+    def encode_batch_fit(self, texts: Sequence[str], seq_len: int, *, pad_id: int | None = None, bos_id: int | None = None,
+                         eos_id: int | None = None, dropout: float = 0.0,
+                         seed: int = 0) -> tuple[list[list[int]], list[list[int]], list[list[int]], list[int]]:
+        """Whole documents in rows of C = seq_len slots, packed by best-fit decreasing: no seq(d) = [bos_id] + encode(texts[d]) +
+        [eos_id] is cut across two rows -> (ids, doc, pos, used).  A seq longer than C loses content ids from its end (BOS and
+        EOS survive, as in encode_batch_padded); n_d = its length after that; a document with n_d == 0 is in no row.
+        Plan, on H[k] = the documents with n_d == k: the state maps a shape -- the lengths of a row's sequences in placement
+        order, non-increasing, room = C - their sum -- to the rows that have it.  For k = C .. 1 with n = H[k] sequences left:
+        among the shapes with a row left and room >= k the one with the smallest room, of several the greatest tuple; t = room
+        // k; min(rows, n // t) of its rows take t sequences each, then, if rows of it and sequences remain, one more row takes
+        the rest; with no such shape n // t rows of t = C // k sequences open and one row of the n % t left.
+        Rows: the shapes in descending tuple order, the rows of a shape consecutive; a row holds its sequences end to end from
+        column 0.  For every k the documents with n_d == k, in ascending d, take the places of length k in row order, within a
+        row left to right.  doc and pos are encode_batch_packed's; pad slots hold pad_id, 0xFFFFFFFF and 0; used[r] = the filled
+        slots of row r.  dropout > 0: the content ids are encode_batch_dropout(texts, dropout, seed)."""
+        pad, bos, eos, added = self._layout_ids(pad_id, bos_id, eos_id)
+        C = self._row_length(seq_len, "seq_len", max(1, added))
+        seqs = []
+        for ids in self._encode_batch_for_layout(texts, dropout, seed):
+            seqs.append(([bos] if bos is not None else []) + ids[:max(0, C - added)] + ([eos] if eos is not None else []))
+        by_len: dict[int, list[int]] = {}
+        for d, seq in enumerate(seqs):
+            by_len.setdefault(len(seq), []).append(d)
+        count: dict[tuple, int] = {}  # shape -> rows
+
+        def move(src, dst, m):
+            if src is not None:
+                count[src] -= m
+                if not count[src]:
+                    del count[src]
+            if m:
+                count[dst] = count.get(dst, 0) + m
+
+        for k in range(C, 0, -1):
+            n = len(by_len.get(k, ()))
+            while n:
+                fits = [s for s in count if C - sum(s) >= k]
+                if not fits:
+                    t = C // k
+                    move(None, (k,) * t, n // t)
+                    if n % t:
+                        move(None, (k,) * (n % t), 1)
+                    n = 0
+                    continue
+                least = min(C - sum(s) for s in fits)
+                s = max(s for s in fits if C - sum(s) == least)
+                t, m = least // k, count[s]
+                full = min(m, n // t)
+                move(s, s + (k,) * t, full)
+                n -= full * t
+                if full < m and n:
+                    move(s, s + (k,) * n, 1)
+                    n = 0
+        shapes = [s for s in sorted(count, reverse=True) for _ in range(count[s])]
+        taken = {k: iter(docs) for k, docs in by_len.items()}  # the next document of every length
+        rows = [[next(taken[k]) for k in s] for s in shapes]
+        out_ids, out_doc, out_pos, used = [], [], [], []
+        for row in rows:
+            fill = C - sum(len(seqs[d]) for d in row)
+            out_ids.append([i for d in row for i in seqs[d]] + [pad] * fill)
+            out_doc.append([d for d in row for _ in seqs[d]] + [0xFFFFFFFF] * fill)
+            out_pos.append([p for d in row for p in range(len(seqs[d]))] + [0] * fill)
+            used.append(C - fill)
+        return out_ids, out_doc, out_pos, used
+
     def _windows_args(self, max_length, stride, pad_id, bos_id, eos_id, padding_side, offsets, dropout, seed):
         pad, bos, eos, added = self._layout_ids(pad_id, bos_id, eos_id)
         max_length = self._row_length(max_length, "max_length", added + 1)  # (at least one content slot a row)
@@ -734,6 +799,22 @@ class BBPETokenizer:
         ctx = self._device()
         di, dd, ni, _spans = self._device_encode_for_layout(ctx, inp, dropout, seed)
         return ctx.layout_pack_to_host(di, ni, dd, len(inp[1]), row_len=seq_len, pad_id=pad, bos_id=bos, eos_id=eos, drop_last=drop_last)
+
+    def encode_array_fit(self, texts, seq_len: int, *, pad_id: int | None = None, bos_id: int | None = None,
+                         eos_id: int | None = None, dropout: float = 0.0,
+                         seed: int = 0) -> tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray]:
+        """encode_batch_fit(texts, ...), computed on the GPU: yabpe_encode (dropout > 0: yabpe_encode_dropout with this seed),
+        then yabpe_layout_fit on its device results.  `texts` as encode_array takes them.
+        -> (ids, doc, pos: np.uint32[n_rows, seq_len] each, used np.uint32[n_rows])."""
+        pad, bos, eos, added = self._layout_ids(pad_id, bos_id, eos_id)
+        seq_len = self._row_length(seq_len, "seq_len", max(1, added))
+        self._dropout_threshold(dropout), self._u64(seed, "seed")  # (refused before any device work)
+        inp = self._device_input(texts)
+        if inp is None:
+            return tuple(np.zeros((0, seq_len), np.uint32) for _ in range(3)) + (np.zeros(0, np.uint32),)
+        ctx = self._device()
+        di, dd, ni, _spans = self._device_encode_for_layout(ctx, inp, dropout, seed)
+        return ctx.layout_fit_to_host(di, ni, dd, len(inp[1]), row_len=seq_len, pad_id=pad, bos_id=bos, eos_id=eos)
 
     def encode_array_windows(self, texts, max_length: int, stride: int = 0, *, pad_id: int | None = None, bos_id: int | None = None,
                              eos_id: int | None = None, padding_side: str = "right", offsets: str | None = None,
