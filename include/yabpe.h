@@ -495,8 +495,20 @@ int yabpe_encode_spans(yabpe_ctx *ctx, const uint8_t *text, uint64_t n_bytes, co
 int yabpe_encode_dropout(yabpe_ctx *ctx, const uint8_t *text, uint64_t n_bytes, const uint64_t *doc_off, uint32_t n_docs,
                          uint64_t threshold, uint64_t seed, uint32_t **out_dev_ids, uint64_t **out_dev_doc_off,
                          uint64_t *out_n_ids, int64_t *out_bad_pos);
+/* yabpe_encode that also says which piece of its document every id was made from (BBPETokenizer.encode_with_words).  The
+ * pieces of a document, in order: every occurrence of a special token, with an id or without, and every match of the split
+ * pattern in the text between them.  *out_dev_words = *out_n_ids u32 (device memory owned by the library, released as the
+ * ids are): the low 31 bits hold the 0-based index of the id's piece among the pieces of its document, bit 31
+ * (YABPE_WORD_SPECIAL) is set when that piece is a special occurrence.  The indices of a document never decrease; a special
+ * without an id takes an index and emits nothing, which leaves a gap.  Arguments, errors, ownership and release are
+ * yabpe_encode's, the ids and doc_off are bit-identical to its results on the same input, and the options act alike.  A
+ * document of 2^31 pieces or more: YABPE_E_CAPACITY. */
+#define YABPE_WORD_SPECIAL 0x80000000u   /* words[k]: the piece is a special occurrence */
+int yabpe_encode_words(yabpe_ctx *ctx, const uint8_t *text, uint64_t n_bytes, const uint64_t *doc_off, uint32_t n_docs,
+                       uint32_t **out_dev_ids, uint64_t **out_dev_doc_off, uint32_t **out_dev_words, uint64_t *out_n_ids,
+                       int64_t *out_bad_pos);
 int yabpe_encode_free(yabpe_ctx *ctx);
-/* What the last yabpe_encode / yabpe_encode_spans / yabpe_encode_dropout saw (the span work counts into words_ms and emit_ms), and the device time of its phases (HIP events around each phase's launches). */
+/* What the last yabpe_encode /yabpe_encode_spans / yabpe_encode_dropout saw (the span work counts into words_ms and emit_ms), and the device time of its phases (HIP events around each phase's launches). */
 typedef struct yabpe_encode_stats_t {
     uint64_t n_bytes, n_docs;
     uint64_t n_pretokens;      /* pre-tokens, specials included */
@@ -691,6 +703,50 @@ typedef struct yabpe_layout_stats_t {
     double total_ms;           /* first to last event, host gaps in between included */
 } yabpe_layout_stats_t;
 int yabpe_layout_stats(yabpe_ctx *ctx, yabpe_layout_stats_t *out);
+
+/* Masked-language-model batches (BBPETokenizer.mask_tokens on the device, yet_another_bpe/tokenizer.py) --------------
+ * From ragged ids, document d = ids[doc_off[d], doc_off[d + 1]) (the last one ends at n_ids; doc_off: n_docs starts, the first
+ * one 0, ascending; NULL with n_docs <= 1: one document), to the `input_ids` and `labels` of one dynamic-masking draw,
+ * reproducibly from (seed, document index, position).  With rnd(seed, stream, i) of yet_another_bpe/synth.py: Kd =
+ * rnd(seed, 0x6d, first_doc + d) for document d.  For token j of the document (0-based, counted before any cut of a layout
+ * call) the unit is u = j, with YABPE_MASK_WHOLE_WORD u = words[k] & 0x7FFFFFFF, the piece the id was made from.  A token
+ * whose words entry has YABPE_WORD_SPECIAL set is never selected and draws nothing.  Otherwise r = rnd(Kd, 0x73, u), and the
+ * token is selected iff (r >> 32) < select_threshold.  For a selected token the label is the original id, and x = r &
+ * 0xFFFFFFFF decides the input: x < mask_threshold: mask_id; mask_threshold <= x < mask_threshold + random_threshold:
+ * rnd(Kd, 0x72, j) % n_random (drawn per token in whole-word mode too); otherwise the id stays.  For every other token the id
+ * stays and the label is `ignore`.  A threshold is T(x) = min(2^32, int(x * 2^32)) of a probability x.  Every draw is a function
+ * of (seed, first_doc + d, u or j) alone, so all tokens of a word are selected together and replaced in the same way.
+ * ids, doc_off and words may be host or device memory, as in the layout calls; yabpe_encode_words' results go straight in and
+ * are left alone.  words: what yabpe_encode_words returns, flag bit included, or NULL: nothing is protected (invalid with
+ * YABPE_MASK_WHOLE_WORD).  Results (device memory owned by the library, in buffers of their own: a later encode or layout call
+ * leaves them valid; released by yabpe_mask_free, the next yabpe_mask or yabpe_destroy): *out_dev_ids and *out_dev_labels,
+ * n_ids u32 each.  YABPE_E_INVALID: a threshold above 2^32, mask_threshold + random_threshold above 2^32, n_random == 0 with
+ * random_threshold > 0, an unknown flag, YABPE_MASK_WHOLE_WORD without words, a doc_off that does not ascend from 0 inside the
+ * ids.  YABPE_E_CAPACITY: more than 2^36 ids in one call.  Every error is found before a buffer is allocated. */
+#define YABPE_MASK_WHOLE_WORD 0x1u   /* the unit of selection is the piece (words), not the token */
+typedef struct yabpe_mask_t {
+    uint64_t seed, first_doc;
+    uint64_t select_threshold;                 /* Ts, <= 2^32 */
+    uint64_t mask_threshold, random_threshold; /* Tm, Tr; Tm + Tr <= 2^32 */
+    uint32_t mask_id, n_random;                /* n_random >= 1 when Tr > 0 */
+    uint32_t ignore;                           /* the label of an unselected slot (0xFFFFFF9C is -100 as i32) */
+    uint32_t flags;                            /* YABPE_MASK_WHOLE_WORD */
+} yabpe_mask_t;
+int yabpe_mask(yabpe_ctx *ctx, const uint32_t *ids, uint64_t n_ids, const uint64_t *doc_off, uint32_t n_docs,
+               const uint32_t *words, const yabpe_mask_t *mask, uint32_t **out_dev_ids, uint32_t **out_dev_labels);
+int yabpe_mask_free(yabpe_ctx *ctx);
+/* What the last yabpe_mask saw and drew, and its device time. */
+typedef struct yabpe_mask_stats_t {
+    uint64_t n_ids, n_docs;
+    uint64_t n_protected;      /* ids of special occurrences (never selected) */
+    uint64_t n_selected;       /* = n_masked + n_random + n_kept */
+    uint64_t n_masked;         /* inputs that became mask_id */
+    uint64_t n_random;         /* inputs that became a random id */
+    uint64_t n_kept;           /* selected, input unchanged */
+    double mask_ms;            /* the kernel */
+    double total_ms;           /* first to last event (counter reset and read-back included) */
+} yabpe_mask_stats_t;
+int yabpe_mask_stats(yabpe_ctx *ctx, yabpe_mask_stats_t *out);
 
 /* Multi-GPU (one process per GPU; words are sharded by the caller) -----------------
  * Every rank holds its shard of the words and a replica of the pair table.  After each apply pass the ranks

@@ -22,6 +22,7 @@ constexpr unsigned long long ENC_EMPTY = ~0ull;   // free slot of the pair table
 constexpr uint8_t ENC_INSIDE = 0xFF;              // a byte inside a taken special (not its first)
 constexpr uint32_t ENC_MAX_SPECIALS = 254;        // 1 + index must fit below ENC_INSIDE
 constexpr uint32_t ENC_SHORT = 64;                // words of at most this many bytes: one lane per byte
+constexpr uint32_t ENC_WORD_SPECIAL = 0x80000000u; // yabpe_encode_words: the piece of this id is a special occurrence
 
 // ---------------------------------------------------------------- pair table: (a, b) -> (rank, result)
 struct EncTable {

@@ -31,6 +31,7 @@
 #include "yabpe_decode_kernels.h"
 #include "yabpe_layout_kernels.h"
 #include "yabpe_fit_kernels.h"
+#include "yabpe_mask_kernels.h"
 #include "yabpe_replay_kernels.h"
 #include "yabpe_pool_kernels.h"
 #include "yabpe_norm_kernels.h"
@@ -200,6 +201,7 @@ struct yabpe_ctx {
     uint32_t *enc_ids = nullptr;              // results of the last yabpe_encode / yabpe_encode_spans
     unsigned long long *enc_doc = nullptr;
     unsigned long long *enc_spans = nullptr;  // (yabpe_encode_spans only)
+    uint32_t *enc_words = nullptr;            // (yabpe_encode_words only)
     yabpe_encode_stats_t enc_stats{};
     unsigned long long enc_sums[4] = {0, 0, 0, 0};  // checksum, words, tokens, specials taken
     bool enc_done = false;
@@ -217,6 +219,10 @@ struct yabpe_ctx {
     uint32_t *lay_buf[LB_COUNT] = {};         // results of the last layout call, by LayBuf (which says what each call keeps where)
     yabpe_layout_stats_t lay_stats{};
     hipEvent_t lay_ev[4] = {};
+    // masked-language-model batches (yabpe_mask): the results of the last call
+    uint32_t *mask_ids = nullptr, *mask_labels = nullptr;
+    yabpe_mask_stats_t mask_stats{};
+    hipEvent_t mask_ev[4] = {};
     // resumed load (yabpe_load_words_resumed)
     yabpe_resume_stats_t resume_stats{};
     // persistent word pool (yabpe_pool_add / yabpe_pool_get): arena, off / count / hash, slots (pool_logic.h)
@@ -1584,6 +1590,9 @@ void yabpe_destroy(yabpe_ctx *c) {
         if (e) (void)hipEventDestroy(e);
     yabpe_layout_free(c);
     for (auto &e : c->lay_ev)
+        if (e) (void)hipEventDestroy(e);
+    yabpe_mask_free(c);
+    for (auto &e : c->mask_ev)
         if (e) (void)hipEventDestroy(e);
     yabpe_pool_clear(c);
     for (auto &e : c->wpool_ev)
@@ -3730,9 +3739,11 @@ int yabpe_encode_free(yabpe_ctx *c) {
     dfree(c->enc_ids);
     dfree(c->enc_doc);
     dfree(c->enc_spans);
+    dfree(c->enc_words);
     c->enc_ids = nullptr;
     c->enc_doc = nullptr;
     c->enc_spans = nullptr;
+    c->enc_words = nullptr;
     return YABPE_OK;
 }
 
@@ -3799,13 +3810,15 @@ static int encode_front(yabpe_ctx *c, Scratch &S, const uint8_t *d_text, unsigne
     return YABPE_OK;
 }
 
-// yabpe_encode (out_dev_spans == nullptr) and yabpe_encode_spans: one body.
+// yabpe_encode (out_dev_spans == nullptr, out_dev_words == nullptr), yabpe_encode_spans and yabpe_encode_words: one body.
 static int encode_run(yabpe_ctx *c, const uint8_t *text, uint64_t n_bytes, const uint64_t *doc_off, uint32_t n_docs, uint32_t span_flags,
-                      uint32_t **out_dev_ids, uint64_t **out_dev_doc_off, uint64_t **out_dev_spans, uint64_t *out_n_ids, int64_t *out_bad_pos) {
-    const bool spans = out_dev_spans != nullptr, chars = spans && (span_flags & YABPE_SPANS_CHARS);
+                      uint32_t **out_dev_ids, uint64_t **out_dev_doc_off, uint64_t **out_dev_spans, uint32_t **out_dev_words, uint64_t *out_n_ids,
+                      int64_t *out_bad_pos) {
+    const bool spans = out_dev_spans != nullptr, chars = spans && (span_flags & YABPE_SPANS_CHARS), words = out_dev_words != nullptr;
     HIPCHK(c, hipSetDevice(c->device));
     *out_dev_ids = nullptr; *out_dev_doc_off = nullptr; *out_n_ids = 0; *out_bad_pos = -1;
     if (spans) *out_dev_spans = nullptr;
+    if (words) *out_dev_words = nullptr;
     if (span_flags & ~YABPE_SPANS_CHARS) return fail(c, YABPE_E_INVALID, "unknown flags 0x%x", span_flags);
     if (!c->have_enc_model) return fail(c, YABPE_E_INVALID, "no model: call yabpe_encode_set_model first");
     uint32_t G_checked = 0;
@@ -3839,6 +3852,10 @@ static int encode_run(yabpe_ctx *c, const uint8_t *text, uint64_t n_bytes, const
         if (spans) {
             TRY(dmalloc(c, &c->enc_spans, 2));
             *out_dev_spans = (uint64_t *)c->enc_spans;
+        }
+        if (words) {
+            TRY(dmalloc(c, &c->enc_words, 1));
+            *out_dev_words = c->enc_words;
         }
         HIPCHK(c, hipStreamSynchronize(s));
         c->enc_sums[0] = c->enc_sums[1] = c->enc_sums[2] = c->enc_sums[3] = 0;
@@ -3913,7 +3930,26 @@ static int encode_run(yabpe_ctx *c, const uint8_t *text, uint64_t n_bytes, const
     HIPCHK(c, hipMemcpyAsync(c->enc_sums, wsums, 32, hipMemcpyDeviceToHost, s));
     HIPCHK(c, hipStreamSynchronize(s));
     TRY(dmalloc(c, &c->enc_ids, n_ids));
-    hipLaunchKernelGGL(k_enc_emit, dim3(pgrid), dim3(256), 0, s, rep, uoff, uids, id_off, n_pre, c->enc_ids);
+    if (words) { // every document's first pre-token first: the emit pass numbers the pre-tokens from it
+        uint32_t *doc_pre = nullptr;
+        HIPCHK(c, S.get(&doc_pre, (uint64_t)n_docs + 1));
+        hipLaunchKernelGGL(k_enc_docs, dim3((n_docs + 1 + 255) / 256), dim3(256), 0, s, d_docs, n_docs, n, off, n_pre, id_off, doc_ids, doc_pre);
+        if (n_pre >= ENC_WORD_SPECIAL) { // (only then can a document hold 2^31 pieces: the index would reach the flag bit)
+            std::vector<uint32_t> h_pre((size_t)n_docs + 1);
+            HIPCHK(c, hipMemcpyAsync(h_pre.data(), doc_pre, h_pre.size() * 4, hipMemcpyDeviceToHost, s));
+            HIPCHK(c, hipStreamSynchronize(s));
+            for (uint32_t d = 0; d < n_docs; ++d)
+                if (h_pre[d + 1] - h_pre[d] >= ENC_WORD_SPECIAL) {
+                    yabpe_encode_free(c);
+                    return fail(c, YABPE_E_CAPACITY, "document %u has %u pieces: at most 2^31 - 1", d, h_pre[d + 1] - h_pre[d]);
+                }
+        }
+        TRY(dmalloc(c, &c->enc_words, n_ids));
+        hipLaunchKernelGGL(k_enc_emit_words, dim3(pgrid), dim3(256), 0, s, rep, uoff, uids, id_off, off, n_pre, doc_pre, n_docs, sflag, c->enc_ids,
+                           c->enc_words);
+    } else {
+        hipLaunchKernelGGL(k_enc_emit, dim3(pgrid), dim3(256), 0, s, rep, uoff, uids, id_off, n_pre, c->enc_ids);
+    }
     if (spans) {
         TRY(dmalloc(c, &c->enc_spans, 2 * n_ids));
         if (chars) { // the lead-byte prefix of the text, one entry per granule
@@ -3927,7 +3963,7 @@ static int encode_run(yabpe_ctx *c, const uint8_t *text, uint64_t n_bytes, const
                                lead_table, (ulonglong2 *)c->enc_spans);
         }
     }
-    hipLaunchKernelGGL(k_enc_docs, dim3((n_docs + 1 + 255) / 256), dim3(256), 0, s, d_docs, n_docs, n, off, n_pre, id_off, doc_ids);
+    if (!words) hipLaunchKernelGGL(k_enc_docs, dim3((n_docs + 1 + 255) / 256), dim3(256), 0, s, d_docs, n_docs, n, off, n_pre, id_off, doc_ids, (uint32_t *)nullptr);
     (void)hipEventRecord(c->enc_ev[7], s);
     const hipError_t le = hipGetLastError();
     const hipError_t se = hipStreamSynchronize(s);
@@ -3961,6 +3997,7 @@ static int encode_run(yabpe_ctx *c, const uint8_t *text, uint64_t n_bytes, const
     *out_dev_ids = c->enc_ids;
     *out_dev_doc_off = (uint64_t *)c->enc_doc;
     if (spans) *out_dev_spans = (uint64_t *)c->enc_spans;
+    if (words) *out_dev_words = c->enc_words;
     *out_n_ids = n_ids;
     return YABPE_OK;
 }
@@ -3968,13 +4005,19 @@ static int encode_run(yabpe_ctx *c, const uint8_t *text, uint64_t n_bytes, const
 int yabpe_encode(yabpe_ctx *c, const uint8_t *text, uint64_t n_bytes, const uint64_t *doc_off, uint32_t n_docs, uint32_t **out_dev_ids,
                  uint64_t **out_dev_doc_off, uint64_t *out_n_ids, int64_t *out_bad_pos) {
     if (!c || !out_dev_ids || !out_dev_doc_off || !out_n_ids || !out_bad_pos) return YABPE_E_INVALID;
-    return encode_run(c, text, n_bytes, doc_off, n_docs, 0, out_dev_ids, out_dev_doc_off, nullptr, out_n_ids, out_bad_pos);
+    return encode_run(c, text, n_bytes, doc_off, n_docs, 0, out_dev_ids, out_dev_doc_off, nullptr, nullptr, out_n_ids, out_bad_pos);
 }
 
 int yabpe_encode_spans(yabpe_ctx *c, const uint8_t *text, uint64_t n_bytes, const uint64_t *doc_off, uint32_t n_docs, uint32_t flags,
                        uint32_t **out_dev_ids, uint64_t **out_dev_doc_off, uint64_t **out_dev_spans, uint64_t *out_n_ids, int64_t *out_bad_pos) {
     if (!c || !out_dev_ids || !out_dev_doc_off || !out_dev_spans || !out_n_ids || !out_bad_pos) return YABPE_E_INVALID;
-    return encode_run(c, text, n_bytes, doc_off, n_docs, flags, out_dev_ids, out_dev_doc_off, out_dev_spans, out_n_ids, out_bad_pos);
+    return encode_run(c, text, n_bytes, doc_off, n_docs, flags, out_dev_ids, out_dev_doc_off, out_dev_spans, nullptr, out_n_ids, out_bad_pos);
+}
+
+int yabpe_encode_words(yabpe_ctx *c, const uint8_t *text, uint64_t n_bytes, const uint64_t *doc_off, uint32_t n_docs, uint32_t **out_dev_ids,
+                       uint64_t **out_dev_doc_off, uint32_t **out_dev_words, uint64_t *out_n_ids, int64_t *out_bad_pos) {
+    if (!c || !out_dev_ids || !out_dev_doc_off || !out_dev_words || !out_n_ids || !out_bad_pos) return YABPE_E_INVALID;
+    return encode_run(c, text, n_bytes, doc_off, n_docs, 0, out_dev_ids, out_dev_doc_off, nullptr, out_dev_words, out_n_ids, out_bad_pos);
 }
 
 // BBPETokenizer.encode_dropout on the device (yabpe_dropout_kernels.h): the shared front, then per occurrence -- nothing is
@@ -4072,7 +4115,7 @@ int yabpe_encode_dropout(yabpe_ctx *c, const uint8_t *text, uint64_t n_bytes, co
     W.ids = c->enc_ids;
     hipLaunchKernelGGL(k_drop_words<true>, dim3(wg), dim3(BLOCK), 0, s, W);
     if (n_long) hipLaunchKernelGGL(k_drop_long_emit, dim3(lgrid), dim3(64), 0, s, llist, lbase, n_long, ltok, id_off, c->enc_out_id, c->enc_ids);
-    hipLaunchKernelGGL(k_enc_docs, dim3((n_docs + 1 + 255) / 256), dim3(256), 0, s, d_docs, n_docs, n, off, n_pre, id_off, doc_ids);
+    hipLaunchKernelGGL(k_enc_docs, dim3((n_docs + 1 + 255) / 256), dim3(256), 0, s, d_docs, n_docs, n, off, n_pre, id_off, doc_ids, (uint32_t *)nullptr);
     (void)hipEventRecord(c->enc_ev[7], s);
     const hipError_t le = hipGetLastError();
     const hipError_t se = hipStreamSynchronize(s);
@@ -4559,6 +4602,100 @@ int yabpe_layout_fit(yabpe_ctx *c, const uint32_t *ids, uint64_t n_ids, const ui
 int yabpe_layout_stats(yabpe_ctx *c, yabpe_layout_stats_t *out) {
     if (!c || !out) return YABPE_E_INVALID;
     *out = c->lay_stats;
+    return YABPE_OK;
+}
+
+// ---------------------------------------------------------------------------------------------- masked-language-model batches
+int yabpe_mask_free(yabpe_ctx *c) {
+    if (!c) return YABPE_E_INVALID;
+    dfree(c->mask_ids);
+    dfree(c->mask_labels);
+    c->mask_ids = nullptr;
+    c->mask_labels = nullptr;
+    return YABPE_OK;
+}
+
+// BBPETokenizer.mask_tokens on the device (yabpe_mask_kernels.h; the rule: mask_logic.h).  mask_ev[0..3] bracket the call's
+// device work, [1..2] the kernel.  A call that the checks refuse has freed nothing.
+int yabpe_mask(yabpe_ctx *c, const uint32_t *ids, uint64_t n_ids, const uint64_t *doc_off, uint32_t n_docs, const uint32_t *words,
+               const yabpe_mask_t *mask, uint32_t **out_dev_ids, uint32_t **out_dev_labels) {
+    if (!c || !out_dev_ids || !out_dev_labels) return YABPE_E_INVALID;
+    HIPCHK(c, hipSetDevice(c->device));
+    *out_dev_ids = nullptr; *out_dev_labels = nullptr;
+    if (!mask) return fail(c, YABPE_E_INVALID, "mask is NULL");
+    const MaskRule R{mask->select_threshold, mask->mask_threshold, mask->random_threshold, mask->mask_id, mask->n_random};
+    if (!mask_rule_valid(R))
+        return fail(c, YABPE_E_INVALID, "thresholds %llu, %llu, %llu with n_random %u: each at most 2^32, mask + random at most 2^32, n_random >= 1 with random > 0",
+                    (unsigned long long)R.select, (unsigned long long)R.mask, (unsigned long long)R.random, R.n_random);
+    if (mask->flags & ~YABPE_MASK_WHOLE_WORD) return fail(c, YABPE_E_INVALID, "unknown mask flags 0x%x", mask->flags);
+    const bool whole_word = (mask->flags & YABPE_MASK_WHOLE_WORD) != 0;
+    if (whole_word && !words) return fail(c, YABPE_E_INVALID, "YABPE_MASK_WHOLE_WORD needs the words array");
+    if (n_ids && !ids) return fail(c, YABPE_E_INVALID, "ids is NULL");
+    if (n_ids > LAY_MAX_SLOTS) return fail(c, YABPE_E_CAPACITY, "%llu ids: at most 2^36 in one call", (unsigned long long)n_ids);
+    if (!doc_off && n_docs > 1) return fail(c, YABPE_E_INVALID, "doc_off is NULL with %u documents", n_docs);
+    // the document starts on the host (validated: the kernel indexes the table with what it finds in it) and on the device
+    const bool docs_dev = doc_off && is_device_ptr(doc_off);
+    if (!doc_off) n_docs = 1;
+    std::vector<uint64_t> h_docs(n_docs, 0);
+    if (doc_off && n_docs) {
+        if (docs_dev) HIPCHK(c, hipMemcpy(h_docs.data(), doc_off, (size_t)n_docs * 8, hipMemcpyDeviceToHost));
+        else memcpy(h_docs.data(), doc_off, (size_t)n_docs * 8);
+    }
+    TRY(check_starts(c, h_docs.data(), n_docs, n_ids, "ids"));
+    yabpe_mask_free(c);
+    c->mask_stats = yabpe_mask_stats_t{};
+    c->mask_stats.n_ids = n_ids;
+    c->mask_stats.n_docs = n_docs;
+    for (auto &e : c->mask_ev)
+        if (!e) HIPCHK(c, hipEventCreate(&e));
+    hipStream_t s = c->stream;
+    Scratch S(c->device, c->rank);
+    const uint32_t *d_ids = nullptr, *d_words = nullptr;
+    const unsigned long long *d_docs = nullptr;
+    unsigned long long *counters = nullptr;
+    TRY(to_device(c, S, ids, n_ids * 4, 4, &d_ids));
+    TRY(to_device(c, S, docs_dev ? (const unsigned long long *)doc_off : (const unsigned long long *)h_docs.data(), (uint64_t)n_docs * 8, 8, &d_docs));
+    if (words) TRY(to_device(c, S, words, n_ids * 4, 4, &d_words));
+    constexpr uint32_t N_COUNTERS = MASK_SHARDS * MASK_SHARD_STRIDE;  // (the kernel's copies of the counters, summed below)
+    HIPCHK(c, S.get(&counters, N_COUNTERS));
+    TRY(dmalloc(c, &c->mask_ids, n_ids));
+    TRY(dmalloc(c, &c->mask_labels, n_ids));
+    HIPCHK(c, hipEventRecord(c->mask_ev[0], s));
+    HIPCHK(c, hipMemsetAsync(counters, 0, N_COUNTERS * 8, s));
+    HIPCHK(c, hipEventRecord(c->mask_ev[1], s));
+    if (n_ids)
+        hipLaunchKernelGGL(k_mask, dim3(cdiv64(n_ids, MASK_BLOCK)), dim3(MASK_BLOCK), 0, s,
+                           MaskParams{d_ids, n_ids, d_docs, n_docs, n_ids ? d_words : nullptr, mask->seed, mask->first_doc, R, mask->ignore,
+                                      whole_word ? 1u : 0u, c->mask_ids, c->mask_labels, counters});
+    const hipError_t le = hipGetLastError();
+    (void)hipEventRecord(c->mask_ev[2], s);
+    unsigned long long h_all[N_COUNTERS] = {0}, h_cnt[MASK_KINDS] = {0, 0, 0, 0};
+    (void)hipMemcpyAsync(h_all, counters, N_COUNTERS * 8, hipMemcpyDeviceToHost, s);
+    (void)hipEventRecord(c->mask_ev[3], s);
+    const hipError_t se = hipStreamSynchronize(s);
+    if (le != hipSuccess || se != hipSuccess) {
+        yabpe_mask_free(c);
+        return fail(c, YABPE_E_HIP, "mask kernel failed: %s", hipGetErrorString(le != hipSuccess ? le : se));
+    }
+    for (uint32_t b = 0; b < MASK_SHARDS; ++b)
+        for (uint32_t k = 0; k < MASK_KINDS; ++k) h_cnt[k] += h_all[b * MASK_SHARD_STRIDE + k];
+    float ms[3] = {0, 0, 0};
+    auto &st = c->mask_stats;
+    st.total_ms = pass_times(c->mask_ev, 3, ms);
+    st.mask_ms = ms[1];
+    st.n_protected = h_cnt[MASK_PROTECTED];
+    st.n_masked = h_cnt[MASK_MASKED];
+    st.n_random = h_cnt[MASK_RANDOM];
+    st.n_kept = h_cnt[MASK_KEPT];
+    st.n_selected = st.n_masked + st.n_random + st.n_kept;
+    *out_dev_ids = c->mask_ids;
+    *out_dev_labels = c->mask_labels;
+    return YABPE_OK;
+}
+
+int yabpe_mask_stats(yabpe_ctx *c, yabpe_mask_stats_t *out) {
+    if (!c || !out) return YABPE_E_INVALID;
+    *out = c->mask_stats;
     return YABPE_OK;
 }
 

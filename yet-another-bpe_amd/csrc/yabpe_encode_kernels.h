@@ -11,6 +11,8 @@
 //   words     k_enc_words: one wave per unique word -- the ids of its tokens, their number and the checksum fold
 //   emit      k_enc_count / exclusive_scan / k_enc_emit: per pre-token count -> id offsets -> u32 ids; k_enc_docs: the
 //             per-document offsets into the ids
+// With words (yabpe_encode_words): k_enc_docs also writes every document's first pre-token, and k_enc_emit_words takes
+// k_enc_emit's place: beside each id, the index of its pre-token in its document and whether it is a special occurrence.
 // With spans (yabpe_encode_spans): k_enc_words<true> also writes every token's byte offset inside its word, and
 // k_enc_emit_spans writes (start, end) per id, relative to its document; in characters after k_enc_lead_count /
 // exclusive_scan built the lead-byte prefix of the text.
@@ -206,6 +208,40 @@ __global__ void k_enc_emit(const uint32_t *rep, const unsigned long long *uoff, 
     for (unsigned long long k = a; k < e; ++k) ids[k] = src[k - a];
 }
 
+// k_enc_emit that also says which piece of its document every id was made from (yabpe_encode_words): words[k] = the index of
+// pre-token w among the pre-tokens of its document, with ENC_WORD_SPECIAL set when w is a special occurrence.  doc_pre[d] =
+// the first pre-token of document d (k_enc_docs; n_docs + 1 entries, ascending): the document of w is the last d with
+// doc_pre[d] <= w, searched between the documents of the block's first and last pre-token as k_enc_emit_spans does.  A
+// pre-token without ids (a special the vocab lacks) writes nothing and still counts: the indices of its document have a gap.
+__global__ __launch_bounds__(256) void k_enc_emit_words(const uint32_t *rep, const unsigned long long *uoff, const uint32_t *uids,
+                                                        const unsigned long long *id_off, const unsigned long long *off, unsigned long long n,
+                                                        const uint32_t *doc_pre, uint32_t n_docs, const uint8_t *sflag, uint32_t *ids,
+                                                        uint32_t *words) {
+    __shared__ uint32_t s_doc[2];
+    auto doc_of = [&](unsigned long long w, uint32_t lo, uint32_t hi) -> uint32_t { // last d in [lo, hi] with doc_pre[d] <= w
+        while (lo < hi) {
+            const uint32_t mid = lo + (hi - lo + 1) / 2;
+            if (doc_pre[mid] <= w) lo = mid; else hi = mid - 1;
+        }
+        return lo;
+    };
+    const unsigned long long w0 = (unsigned long long)blockIdx.x * blockDim.x, w = w0 + threadIdx.x;
+    if (threadIdx.x < 2) {
+        const unsigned long long wl = w0 + blockDim.x - 1 < n ? w0 + blockDim.x - 1 : n - 1;
+        s_doc[threadIdx.x] = doc_of(threadIdx.x ? wl : w0, 0, n_docs - 1);
+    }
+    __syncthreads();
+    if (w >= n) return;
+    const unsigned long long a = id_off[w], e = id_off[w + 1];
+    if (a == e) return;
+    const uint32_t word = (uint32_t)(w - doc_pre[doc_of(w, s_doc[0], s_doc[1])]) | ((sflag && sflag[off[w]]) ? ENC_WORD_SPECIAL : 0u);
+    const uint32_t *src = uids + uoff[rep[w]];
+    for (unsigned long long k = a; k < e; ++k) {
+        ids[k] = src[k - a];
+        words[k] = word;
+    }
+}
+
 // cnt[g] = the non-continuation bytes of granule g (ENC_GRANULE bytes of text, 16-byte aligned): one 16-byte chunk per
 // thread, four neighbouring lanes make a granule.  Its exclusive scan is enc_lead's table.
 __global__ __launch_bounds__(BLOCK) void k_enc_lead_count(const uint8_t *text, unsigned long long n, uint8_t *cnt) {
@@ -262,9 +298,10 @@ __global__ __launch_bounds__(256) void k_enc_emit_spans(const uint32_t *rep, con
     }
 }
 
-// doc_ids[d] = id offset of the first pre-token at or after document d's start (d == n_docs: the total)
+// doc_ids[d] = id offset of the first pre-token at or after document d's start (d == n_docs: the total); doc_pre (nullptr:
+// not wanted) [d] = that pre-token's index
 __global__ void k_enc_docs(const unsigned long long *doc_start, uint32_t n_docs, unsigned long long n_bytes, const unsigned long long *off,
-                           unsigned long long n_pre, const unsigned long long *id_off, unsigned long long *doc_ids) {
+                           unsigned long long n_pre, const unsigned long long *id_off, unsigned long long *doc_ids, uint32_t *doc_pre) {
     const uint32_t d = blockIdx.x * blockDim.x + threadIdx.x;
     if (d > n_docs) return;
     const unsigned long long pos = d < n_docs ? doc_start[d] : n_bytes;
@@ -274,6 +311,7 @@ __global__ void k_enc_docs(const unsigned long long *doc_start, uint32_t n_docs,
         if (off[mid] >= pos) hi = mid; else lo = mid + 1;
     }
     doc_ids[d] = id_off[lo];
+    if (doc_pre) doc_pre[d] = (uint32_t)lo;
 }
 
 } // namespace yb

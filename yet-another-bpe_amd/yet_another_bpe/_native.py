@@ -74,6 +74,17 @@ class LayoutStats(ctypes.Structure):
         (n, c_double) for n in ("lengths_ms", "write_ms", "total_ms")]
 
 
+class Mask(ctypes.Structure):
+    """yabpe_mask_t"""
+    _fields_ = [(n, c_uint64) for n in ("seed", "first_doc", "select_threshold", "mask_threshold", "random_threshold")] + [
+        (n, c_uint32) for n in ("mask_id", "n_random", "ignore", "flags")]
+
+
+class MaskStats(ctypes.Structure):
+    _fields_ = [(n, c_uint64) for n in ("n_ids", "n_docs", "n_protected", "n_selected", "n_masked", "n_random", "n_kept")] + [
+        (n, c_double) for n in ("mask_ms", "total_ms")]
+
+
 class Layout(ctypes.Structure):
     """yabpe_layout_t"""
     _fields_ = [(n, c_uint32) for n in ("row_len", "pad_id", "bos_id", "eos_id", "flags")]
@@ -139,10 +150,11 @@ SYMBOLS = [
     "yabpe_iter_log", "yabpe_event_log", "yabpe_latency_probe", "yabpe_verify_table", "yabpe_stream_checksum", "yabpe_stream_dump", "yabpe_synth_generate", "yabpe_synth_generate_lex", "yabpe_synth_free",
     "yabpe_memcpy_d2h", "yabpe_memcpy_h2d", "yabpe_pretokenize", "yabpe_pretokenize_free",
     "yabpe_comm_unique_id", "yabpe_comm_init", "yabpe_comm_init_custom", "yabpe_comm_enable_p2p",
-    "yabpe_encode_set_model", "yabpe_encode", "yabpe_encode_spans", "yabpe_encode_dropout", "yabpe_encode_free", "yabpe_encode_stats", "yabpe_encode_checksum",
+    "yabpe_encode_set_model", "yabpe_encode", "yabpe_encode_spans", "yabpe_encode_dropout", "yabpe_encode_words", "yabpe_encode_free", "yabpe_encode_stats", "yabpe_encode_checksum",
     "yabpe_decode_set_model", "yabpe_decode", "yabpe_decode_free", "yabpe_decode_stats",
     "yabpe_load_words_resumed", "yabpe_resume_stats",
     "yabpe_layout_pad", "yabpe_layout_pack", "yabpe_layout_windows", "yabpe_layout_pairs", "yabpe_layout_fit", "yabpe_layout_free", "yabpe_layout_stats",
+    "yabpe_mask", "yabpe_mask_free", "yabpe_mask_stats",
     "yabpe_pool_add", "yabpe_pool_get", "yabpe_pool_clear", "yabpe_pool_stats",
     "yabpe_normalize", "yabpe_normalize_free", "yabpe_normalize_stats",
     "yabpe_utf8_repair", "yabpe_utf8_repair_free", "yabpe_utf8_repair_stats",
@@ -201,6 +213,8 @@ def lib() -> ctypes.CDLL:
                                          POINTER(c_void_p), POINTER(c_uint64), POINTER(ctypes.c_int64)]
         L.yabpe_encode_dropout.argtypes = [c_void_p, c_void_p, c_uint64, c_void_p, c_uint32, c_uint64, c_uint64, POINTER(c_void_p),
                                            POINTER(c_void_p), POINTER(c_uint64), POINTER(ctypes.c_int64)]
+        L.yabpe_encode_words.argtypes = [c_void_p, c_void_p, c_uint64, c_void_p, c_uint32, POINTER(c_void_p), POINTER(c_void_p),
+                                         POINTER(c_void_p), POINTER(c_uint64), POINTER(ctypes.c_int64)]
         L.yabpe_encode_free.argtypes = [c_void_p]
         L.yabpe_encode_stats.argtypes = [c_void_p, POINTER(EncodeStats)]
         L.yabpe_encode_checksum.argtypes = [c_void_p, POINTER(c_uint64), POINTER(c_uint64), POINTER(c_uint64)]
@@ -217,6 +231,9 @@ def lib() -> ctypes.CDLL:
         L.yabpe_layout_fit.argtypes = [c_void_p, c_void_p, c_uint64, c_void_p, c_uint32, POINTER(Layout), POINTER(FitRows)]
         L.yabpe_layout_free.argtypes = [c_void_p]
         L.yabpe_layout_stats.argtypes = [c_void_p, POINTER(LayoutStats)]
+        L.yabpe_mask.argtypes = [c_void_p, c_void_p, c_uint64, c_void_p, c_uint32, c_void_p, POINTER(Mask), POINTER(c_void_p), POINTER(c_void_p)]
+        L.yabpe_mask_free.argtypes = [c_void_p]
+        L.yabpe_mask_stats.argtypes = [c_void_p, POINTER(MaskStats)]
         L.yabpe_pool_add.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_uint64]
         L.yabpe_pool_get.argtypes = [c_void_p, POINTER(c_void_p), POINTER(c_void_p), POINTER(c_void_p), POINTER(c_uint64), POINTER(c_uint64)]
         L.yabpe_pool_clear.argtypes = [c_void_p]
@@ -243,6 +260,9 @@ LOAD_DEDUP = 0x1
 SPANS_CHARS = 0x1  # yabpe_encode_spans: code points instead of bytes
 LAYOUT_BOS, LAYOUT_EOS, LAYOUT_TRUNC_LEFT, LAYOUT_PAD_LEFT, LAYOUT_DROP_LAST = 0x01, 0x02, 0x04, 0x08, 0x10  # yabpe_layout_t.flags
 LAYOUT_NO_DOC = 0xFFFFFFFF  # `doc` of a packed slot past the end of the stream
+WORD_SPECIAL = 0x80000000  # yabpe_encode_words: bit 31 of a words entry (YABPE_WORD_SPECIAL)
+MASK_WHOLE_WORD = 0x1  # yabpe_mask_t.flags
+MASK_IGNORE = 0xFFFFFF9C  # yabpe_mask_t.ignore: -100 as i32, the label a loss skips
 PAIRS_MODES = {"longest_first": 0, "only_first": 1, "only_second": 2, "windows": 3}  # yabpe_pairs_t.mode (YABPE_PAIRS_*)
 
 
@@ -572,13 +592,15 @@ class Context:
                                                a["mb"].ctypes.data, a["mo"].ctypes.data, len(a["mo"]) // 2, a["sb"].ctypes.data,
                                                a["so"].ctypes.data, len(a["so"]) - 1, int(unk_id)))
 
-    def _encode_call(self, text, n_bytes, doc_starts, flags, dropout=None):
-        """yabpe_encode (flags None), yabpe_encode_spans or yabpe_encode_dropout (dropout = (threshold, seed))
-        -> (dev ids, dev doc_off, dev spans or None, n_ids)"""
+    def _encode_call(self, text, n_bytes, doc_starts, flags, dropout=None, words=False):
+        """yabpe_encode (flags None), yabpe_encode_spans, yabpe_encode_dropout (dropout = (threshold, seed)) or yabpe_encode_words
+        (words) -> (dev ids, dev doc_off, dev spans / dev words or None, n_ids)"""
         _keep, ptr, n = _text_arg(text, n_bytes)
         docs = _starts_arg(doc_starts)
         di, dd, ds, ni, bad = c_void_p(), c_void_p(), c_void_p(), c_uint64(0), ctypes.c_int64(-1)
-        if dropout is not None:
+        if words:
+            rc = lib().yabpe_encode_words(self._h, ptr, n, docs.ctypes.data, len(docs), byref(di), byref(dd), byref(ds), byref(ni), byref(bad))
+        elif dropout is not None:
             rc = lib().yabpe_encode_dropout(self._h, ptr, n, docs.ctypes.data, len(docs), int(dropout[0]), int(dropout[1]), byref(di), byref(dd),
                                             byref(ni), byref(bad))
         elif flags is None:
@@ -630,6 +652,21 @@ class Context:
         di, dd, ni = self.encode_dropout(text, threshold, seed, n_bytes, doc_starts)
         ids = self.d2h(di, 4 * ni, np.uint32) if ni else np.zeros(0, np.uint32)
         return ids, self.d2h(dd, 8 * (n_docs + 1), np.uint64)
+
+    def encode_words(self, text, n_bytes: int | None = None, doc_starts=None):
+        """encode() plus the piece of its document every id was made from (yabpe_encode_words).
+        -> (dev_ids_ptr u32, dev_doc_off_ptr u64[n_docs + 1], dev_words_ptr u32[n_ids]: the piece index, WORD_SPECIAL set for a
+        special occurrence, n_ids), owned and released as encode()'s."""
+        return self._encode_call(text, n_bytes, doc_starts, None, words=True)
+
+    def encode_words_to_host(self, text, n_bytes: int | None = None, doc_starts=None):
+        """-> (ids u32[n_ids], doc_off u64[n_docs + 1], words u32[n_ids] without the flag bit, special bool[n_ids]) copied to
+        the host."""
+        n_docs = len(doc_starts) if doc_starts is not None and len(doc_starts) else 1
+        di, dd, dw, ni = self.encode_words(text, n_bytes, doc_starts)
+        ids = self.d2h(di, 4 * ni, np.uint32) if ni else np.zeros(0, np.uint32)
+        words = self.d2h(dw, 4 * ni, np.uint32) if ni else np.zeros(0, np.uint32)
+        return ids, self.d2h(dd, 8 * (n_docs + 1), np.uint64), words & np.uint32(WORD_SPECIAL - 1), (words >> 31).astype(bool)
 
     def encode_free(self) -> None:
         self._chk(lib().yabpe_encode_free(self._h))
@@ -837,6 +874,56 @@ class Context:
     def layout_stats(self) -> dict:
         s = LayoutStats()
         self._chk(lib().yabpe_layout_stats(self._h, byref(s)))
+        return _stats_dict(s)
+
+    # -- masked-language-model batches (BBPETokenizer.mask_tokens on the device)
+    def mask(self, ids, n_ids: int | None = None, doc_starts=None, n_docs: int | None = None, words=None, *, seed: int = 0, first_doc: int = 0,
+             select: int = 0, mask: int = 0, random: int = 0, mask_id: int = 0, n_random: int = 0, ignore: int = MASK_IGNORE,
+             whole_word: bool = False, flags: int = 0):
+        """One masking draw over ragged ids (yabpe_mask).  ids / doc_starts as layout_pad takes them; words: None, a u32 array
+        (staged) or a device address -- what encode_words returns, flag bit included.  select, mask, random: the thresholds
+        Ts, Tm, Tr = min(2^32, int(x * 2^32)).  flags: further YABPE_MASK_* bits as they are.
+        -> (dev_ids_ptr u32[n_ids], dev_labels_ptr u32[n_ids]); the buffers live until the next mask, mask_free() or close()."""
+        keep = docs = keep_words = None
+        if isinstance(ids, int):
+            ptr, n = c_void_p(ids), int(n_ids)
+        else:
+            keep = np.ascontiguousarray(ids, dtype=np.uint32)
+            ptr, n = c_void_p(keep.ctypes.data if keep.size else 0), int(keep.size)
+        if isinstance(doc_starts, int):
+            dptr, nd = c_void_p(doc_starts), int(n_docs)
+        else:
+            docs = _starts_arg(doc_starts)
+            dptr, nd = c_void_p(docs.ctypes.data), len(docs)
+        if words is None or isinstance(words, int):
+            wptr = c_void_p(words or 0)
+        else:
+            keep_words = np.ascontiguousarray(words, dtype=np.uint32)
+            if keep_words.size != n:
+                raise ValueError(f"words must hold one entry per id: {keep_words.size} for {n} ids")
+            if not keep_words.size:
+                keep_words = np.zeros(1, np.uint32)  # (no ids: never read, but not NULL -- the words are given)
+            wptr = c_void_p(keep_words.ctypes.data)
+        m = Mask(int(seed), int(first_doc), int(select), int(mask), int(random), int(mask_id), int(n_random), int(ignore),
+                 int(flags) | (MASK_WHOLE_WORD if whole_word else 0))
+        di, dl = c_void_p(), c_void_p()
+        self._chk(lib().yabpe_mask(self._h, ptr, n, dptr, nd, wptr, byref(m), byref(di), byref(dl)))
+        return di.value or 0, dl.value or 0
+
+    def mask_to_host(self, ids, n_ids: int | None = None, doc_starts=None, n_docs: int | None = None, words=None, **kw):
+        """-> (inputs u32[n_ids], labels i32[n_ids]) copied to the host."""
+        n = int(n_ids) if isinstance(ids, int) else int(np.size(ids))
+        di, dl = self.mask(ids, n_ids, doc_starts, n_docs, words, **kw)
+        if not n:
+            return np.zeros(0, np.uint32), np.zeros(0, np.int32)
+        return self.d2h(di, 4 * n, np.uint32), self.d2h(dl, 4 * n, np.uint32).view(np.int32)
+
+    def mask_free(self) -> None:
+        self._chk(lib().yabpe_mask_free(self._h))
+
+    def mask_stats(self) -> dict:
+        s = MaskStats()
+        self._chk(lib().yabpe_mask_stats(self._h, byref(s)))
         return _stats_dict(s)
 
     # -- the persistent word pool (corpora larger than device memory: words go in call by call, the merge loop loads the pool)

@@ -10,7 +10,9 @@ the same on the GPU (yabpe_encode_spans).  encode_batch_padded / encode_batch_pa
 model consumes; encode_array_padded / encode_array_packed compute the same on the GPU (yabpe_layout_pad / yabpe_layout_pack).
 encode_dropout / encode_batch_dropout segment with BPE-dropout, reproducibly from (seed, document, position);
 encode_array_dropout / encode_batch_device_dropout compute the same ids on the GPU (yabpe_encode_dropout), and the fixed-shape
-forms take dropout= and seed=.
+forms take dropout= and seed=.  encode_with_words also says which piece of its document every id was made from, mask_tokens
+draws a seeded masked-language-model mask over such ids, encode_batch_masked lays both out as padded rows;
+encode_array_with_words / mask_array / encode_array_masked compute the same on the GPU (yabpe_encode_words, yabpe_mask).
 """
 from __future__ import annotations
 
@@ -316,6 +318,130 @@ class BBPETokenizer:
             raise ValueError(f"unit must be 'char' or 'byte', not {unit!r}")
         return [self.encode_with_offsets(t, unit) for t in texts]
 
+    # ------------------------------------------------------------------ encode with the word index of every id
+    def encode_with_words(self, text: str) -> tuple[list[int], list[int], list[bool]]:
+        """-> (encode(text), words, special), one entry per id.  The pieces of the (normalised) document, in order, are every
+        occurrence of a special token, with an id or without, and every match of the split pattern in the text between them
+        -- what _byte_spans walks.  words[k] = the 0-based index of the piece id k was made from, special[k] = that piece is a
+        special occurrence.  words never decreases; a special without an id takes an index and emits nothing: a gap.  The
+        word_ids() of a tokenizer user: whole-word masking and word-level labels align on it."""
+        text = self.normalize(text)
+        ids: list[int] = []
+        words: list[int] = []
+        special: list[bool] = []
+        if not text:
+            return ids, words, special
+        index = 0
+        for part in [text] if self._special_pattern is None else self._special_pattern.split(text):
+            if not part:
+                continue
+            if part in self._special_set:
+                tid = self._vocab.get(part.encode("utf-8"))
+                if tid is not None:
+                    ids.append(tid)
+                    words.append(index)
+                    special.append(True)
+                index += 1
+                continue
+            for pre in self._pattern.findall(part):
+                got = self._word_ids(pre)
+                ids.extend(got)
+                words.extend([index] * len(got))
+                special.extend([False] * len(got))
+                index += 1
+        return ids, words, special
+
+    def encode_batch_with_words(self, texts: Sequence[str]):
+        return [self.encode_with_words(t) for t in texts]
+
+    # ------------------------------------------------------------------ masked-language-model batches
+    IGNORE_LABEL = -100  # the label of a slot the loss skips
+
+    def _mask_args(self, mask_id, p, seed, whole_word, mask_fraction, random_fraction, n_random, first_doc, have_words: bool):
+        """-> (mask id, Ts, Tm, Tr, n_random, seed, first_doc), validated"""
+        Ts, Tm, Tr = (self._dropout_threshold(x) for x in (p, mask_fraction, random_fraction))
+        if Tm + Tr > 1 << 32:
+            raise ValueError(f"mask_fraction + random_fraction must be at most 1, not {mask_fraction!r} + {random_fraction!r}")
+        seed, first_doc = self._u64(seed, "seed"), self._u64(first_doc, "first_doc")
+        if mask_id is None:
+            mask_id = self._vocab.get(b"[MASK]")
+            if mask_id is None:
+                raise ValueError("mask_id is None and the vocab has no b'[MASK]'")
+        mask_id = self._layout_ids(mask_id, None, None)[0]
+        if n_random is None:
+            n_random = max(self._vocab.values(), default=-1) + 1
+        try:
+            n_random = operator.index(n_random)
+        except TypeError:
+            raise ValueError(f"n_random must be an integer in [0, 2^32), not {n_random!r}") from None
+        if not 0 <= n_random < 1 << 32:
+            raise ValueError(f"n_random must be an integer in [0, 2^32), not {n_random!r}")
+        if Tr and not n_random:
+            raise ValueError("n_random must be at least 1 when random_fraction > 0")
+        if whole_word and not have_words:
+            raise ValueError("whole_word=True needs words_batch: the piece index of every id (encode_with_words)")
+        return mask_id, Ts, Tm, Tr, n_random, seed, first_doc
+
+    def mask_tokens(self, ids_batch, words_batch=None, special_batch=None, *, mask_id: int | None = None, p: float = 0.15, seed: int = 0,
+                    whole_word: bool = False, mask_fraction: float = 0.8, random_fraction: float = 0.1, n_random: int | None = None,
+                    first_doc: int = 0) -> tuple[list[list[int]], list[list[int]]]:
+        """One dynamic-masking draw of masked-language-model training -> (inputs, labels), shaped as ids_batch.  The result
+        depends on (ids, words, special, the arguments) alone: with rnd of synth.py, T(x) = min(2^32, int(x * 2^32)), Ts =
+        T(p), Tm = T(mask_fraction), Tr = T(random_fraction) (Tm + Tr > 2^32: ValueError), document d has the key Kd =
+        rnd(seed, 0x6d, first_doc + d).  For token j of the document (0-based): the unit is u = j, with whole_word u =
+        words[j].  A token whose `special` is true is never selected and draws nothing.  Otherwise r = rnd(Kd, 0x73, u), and
+        the token is selected iff (r >> 32) < Ts.  A selected token's label is its id, and x = r & 0xFFFFFFFF decides its
+        input: x < Tm: mask_id; Tm <= x < Tm + Tr: rnd(Kd, 0x72, j) % n_random (per token in whole-word mode too); else the id
+        stays.  An unselected token keeps its id and has the label -100.  So all tokens of a word share selection and kind.
+        mask_id None: the id of b"[MASK]" (none: ValueError); n_random None: max(vocab ids) + 1; whole_word without
+        words_batch: ValueError; without special_batch nothing is protected."""
+        mid, Ts, Tm, Tr, n_random, seed, first_doc = self._mask_args(mask_id, p, seed, whole_word, mask_fraction, random_fraction, n_random,
+                                                                     first_doc, words_batch is not None)
+        inputs, labels = [], []
+        for d, ids in enumerate(ids_batch):
+            kd = rnd_int(seed, 0x6d, first_doc + d)
+            words = words_batch[d] if whole_word else None
+            special = special_batch[d] if special_batch is not None else None
+            row, lab = [], []
+            for j, tid in enumerate(ids):
+                tid = int(tid)
+                new, label = tid, self.IGNORE_LABEL
+                if special is None or not special[j]:
+                    r = rnd_int(kd, 0x73, int(words[j]) if whole_word else j)
+                    if (r >> 32) < Ts:
+                        label, x = tid, r & 0xFFFFFFFF
+                        if x < Tm:
+                            new = mid
+                        elif x < Tm + Tr:
+                            new = rnd_int(kd, 0x72, j) % n_random
+                row.append(new)
+                lab.append(label)
+            inputs.append(row)
+            labels.append(lab)
+        return inputs, labels
+
+    def encode_batch_masked(self, texts: Sequence[str], max_length: int | None = None, *, mask_id: int | None = None, p: float = 0.15,
+                            seed: int = 0, whole_word: bool = False, mask_fraction: float = 0.8, random_fraction: float = 0.1,
+                            n_random: int | None = None, first_doc: int = 0, pad_id: int | None = None, bos_id: int | None = None,
+                            eos_id: int | None = None, truncation: str = "right",
+                            padding_side: str = "right") -> tuple[list[list[int]], list[list[int]], list[int]]:
+        """Masked-language-model rows in one call -> (rows, labels, lengths): encode_batch_with_words, then mask_tokens over the
+        whole documents with their words and specials (the mask is drawn before the cut: a token's fate does not depend on
+        max_length), then the rows laid out as encode_batch_padded lays them out, and the labels the same way with -100 in
+        BOS, EOS and pad slots."""
+        L, pad, bos, eos, added = self._padded_args(max_length, pad_id, bos_id, eos_id, truncation, padding_side)
+        self._mask_args(mask_id, p, seed, whole_word, mask_fraction, random_fraction, n_random, first_doc, True)  # (refused before any work)
+        docs = self.encode_batch_with_words(texts)
+        inputs, labels = self.mask_tokens([d[0] for d in docs], [d[1] for d in docs], [d[2] for d in docs], mask_id=mask_id, p=p, seed=seed,
+                                          whole_word=whole_word, mask_fraction=mask_fraction, random_fraction=random_fraction,
+                                          n_random=n_random, first_doc=first_doc)
+        if L is None:
+            L = max((len(ids) + added for ids in inputs), default=0)
+        ign = self.IGNORE_LABEL
+        rows, lengths = self._padded_rows(inputs, L, added, pad, bos, eos, truncation, padding_side)
+        lab_rows, _ = self._padded_rows(labels, L, added, ign, None if bos is None else ign, None if eos is None else ign, truncation, padding_side)
+        return rows, lab_rows, lengths
+
     # ------------------------------------------------------------------ fixed-shape batches
     def _layout_ids(self, pad_id, bos_id, eos_id) -> tuple[int, int | None, int | None, int]:
         """-> (pad id, bos id or None, eos id or None, n_added); every id given must be an integer in [0, 2^32)"""
@@ -365,6 +491,11 @@ class BBPETokenizer:
         docs = self._encode_batch_for_layout(texts, dropout, seed)
         if L is None:
             L = max((len(ids) + added for ids in docs), default=0)
+        return self._padded_rows(docs, L, added, pad, bos, eos, truncation, padding_side)
+
+    @staticmethod
+    def _padded_rows(docs, L: int, added: int, pad, bos, eos, truncation: str, padding_side: str) -> tuple[list[list[int]], list[int]]:
+        """the rows of encode_batch_padded from the content of every document (ids, or the labels of encode_batch_masked)"""
         rows, lengths = [], []
         for ids in docs:
             keep = min(len(ids), L - added)
@@ -737,6 +868,81 @@ class BBPETokenizer:
         ids, off, spans = self.encode_array_with_offsets(texts, unit)
         ids, off, spans = ids.tolist(), off.tolist(), [tuple(p) for p in spans.tolist()]
         return [(ids[off[d]:off[d + 1]], spans[off[d]:off[d + 1]]) for d in range(len(off) - 1)]
+
+    def encode_array_with_words(self, texts, *, errors: str = "strict") -> tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray]:
+        """encode_array(texts) plus the piece every id was made from, computed on the GPU in the same call (yabpe_encode_words).
+        -> (ids np.uint32[n], doc_off np.uint64[n_docs + 1], words np.uint32[n], special bool[n]): words[k] and special[k] as
+        encode_with_words(texts[d]) gives them for id k of document d.  errors: as encode_array takes it."""
+        inp = self._device_input(texts)
+        if inp is None:
+            check_errors(errors)
+            return np.zeros(0, np.uint32), np.zeros(1, np.uint64), np.zeros(0, np.uint32), np.zeros(0, bool)
+        ctx = self._device()
+        text, n_bytes, starts = self._device_text(ctx, inp, errors)
+        return ctx.encode_words_to_host(text, n_bytes, doc_starts=starts)
+
+    def encode_batch_device_with_words(self, texts: Sequence[str]):
+        """encode_batch_with_words(texts), computed on the GPU in one call."""
+        ids, off, words, special = self.encode_array_with_words(texts)
+        ids, off, words, special = ids.tolist(), off.tolist(), words.tolist(), special.tolist()
+        return [(ids[off[d]:off[d + 1]], words[off[d]:off[d + 1]], special[off[d]:off[d + 1]]) for d in range(len(off) - 1)]
+
+    def mask_array(self, ids, doc_off, words=None, special=None, *, mask_id: int | None = None, p: float = 0.15, seed: int = 0,
+                   whole_word: bool = False, mask_fraction: float = 0.8, random_fraction: float = 0.1, n_random: int | None = None,
+                   first_doc: int = 0) -> tuple[np.ndarray, np.ndarray]:
+        """mask_tokens on the GPU (yabpe_mask), bit for bit: ids, doc_off, words and special as encode_array_with_words returns
+        them (words / special None: as mask_tokens without that batch) -> (inputs np.uint32[n], labels np.int32[n])."""
+        mid, Ts, Tm, Tr, n_random, seed, first_doc = self._mask_args(mask_id, p, seed, whole_word, mask_fraction, random_fraction, n_random,
+                                                                     first_doc, words is not None)
+        ids = np.ascontiguousarray(ids, dtype=np.uint32)
+        off = np.asarray(doc_off, dtype=np.int64)
+        if off.ndim != 1 or len(off) < 2 or off[0] != 0 or off[-1] != len(ids) or np.any(np.diff(off) < 0):
+            raise ValueError("doc_off must be n_docs + 1 ascending offsets from 0 to len(ids)")
+        packed = None
+        if words is not None or special is not None:
+            packed = np.zeros(len(ids), np.uint32) if words is None else np.array(words, dtype=np.uint32)
+            if len(packed) != len(ids) or (special is not None and len(special) != len(ids)):
+                raise ValueError("words and special must hold one entry per id")
+            if np.any(packed >> 31):
+                raise ValueError("a word index must be below 2^31")
+            if special is not None:
+                packed |= np.asarray(special, dtype=bool).astype(np.uint32) << 31
+        from . import _native
+
+        return self._device().mask_to_host(ids, None, off[:-1].astype(np.uint64), None, packed, seed=seed, first_doc=first_doc, select=Ts, mask=Tm,
+                                           random=Tr, mask_id=mid, n_random=n_random, ignore=_native.MASK_IGNORE, whole_word=whole_word)
+
+    def encode_array_masked(self, texts, max_length: int | None = None, *, mask_id: int | None = None, p: float = 0.15, seed: int = 0,
+                            whole_word: bool = False, mask_fraction: float = 0.8, random_fraction: float = 0.1,
+                            n_random: int | None = None, first_doc: int = 0, pad_id: int | None = None, bos_id: int | None = None,
+                            eos_id: int | None = None, truncation: str = "right",
+                            padding_side: str = "right") -> tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """encode_batch_masked(texts, ...), computed on the GPU: yabpe_encode_words, then yabpe_mask on its device results, then
+        yabpe_layout_pad over the masked ids and, once those rows are copied out, over the labels with the ignore value as pad,
+        BOS and EOS id (the ragged arrays never visit the host).  `texts` as encode_array takes them.
+        -> (rows np.uint32[n_docs, L], labels np.int32[n_docs, L], lengths np.uint32[n_docs])."""
+        L, pad, bos, eos, _added = self._padded_args(max_length, pad_id, bos_id, eos_id, truncation, padding_side)
+        mid, Ts, Tm, Tr, n_random, seed, first_doc = self._mask_args(mask_id, p, seed, whole_word, mask_fraction, random_fraction, n_random,
+                                                                     first_doc, True)
+        inp = self._device_input(texts)
+        n_docs = 0 if inp is None else len(inp[1])
+        if inp is None or L == 0:  # (no rows, or rows of no slots: with BOS / EOS L is at least 1)
+            return np.zeros((n_docs, L or 0), np.uint32), np.zeros((n_docs, L or 0), np.int32), np.zeros(n_docs, np.uint32)
+        from . import _native
+
+        ctx = self._device()
+        text, n_bytes, starts = self._device_text(ctx, inp)
+        di, dd, dw, ni = ctx.encode_words(text, n_bytes, doc_starts=starts)
+        mi, ml = ctx.mask(di, ni, dd, n_docs, dw, seed=seed, first_doc=first_doc, select=Ts, mask=Tm, random=Tr, mask_id=mid, n_random=n_random,
+                          ignore=_native.MASK_IGNORE, whole_word=whole_word)
+        cut = {"trunc_left": truncation == "left", "pad_left": padding_side == "left"}
+        rows, lengths = ctx.layout_pad_to_host(mi, ni, dd, n_docs, row_len=L or 0, pad_id=pad, bos_id=bos, eos_id=eos, **cut)
+        ign = _native.MASK_IGNORE
+        if rows.shape[1] == 0:  # (only empty documents and neither BOS nor EOS)
+            return rows, np.zeros(rows.shape, np.int32), lengths
+        labels, _lengths = ctx.layout_pad_to_host(ml, ni, dd, n_docs, row_len=rows.shape[1], pad_id=ign, bos_id=None if bos is None else ign,
+                                                  eos_id=None if eos is None else ign, **cut)
+        return rows, labels.view(np.int32), lengths
 
     def _device_encode_for_layout(self, ctx, inp, dropout=0.0, seed=0, offsets=None):
         """-> (ids pointer, document starts pointer, n_ids, spans): the device results the layout passes read -- yabpe_encode's,
