@@ -43,3 +43,23 @@ extern "C" int replay_model_lookup(const uint32_t *left, const uint32_t *right, 
     rp_build_table(left, right, merged, n_merges, &m);
     return rp_lookup(m.table(), a, b, tmin, rank, res) ? 1 : 0;
 }
+
+// The table at 64-bit keys (the u32 resumed load's): built by the same rp_build_table, read by rp32_lookup.  n_q lookups of
+// one table: found[q] = 1 with rank[q] / res[q], or 0.  displaced: keys of the index that do not sit at their hash's slot;
+// wrapped: those of them whose probe sequence went past the end of the index.  Returns 0.
+extern "C" int replay_model_lookup32(const uint32_t *left, const uint32_t *right, const uint32_t *merged, uint32_t n_merges, const uint32_t *a,
+                                     const uint32_t *b, const uint32_t *tmin, uint32_t n_q, uint8_t *found, uint32_t *rank, uint32_t *res,
+                                     uint32_t *displaced, uint32_t *wrapped) {
+    Rp32TableHost m;
+    rp_build_table(left, right, merged, n_merges, &m);
+    const Rp32Table t{m.table(), m.n_merges()};
+    for (uint32_t q = 0; q < n_q; ++q) found[q] = rp32_lookup(t, a[q], b[q], tmin[q], &rank[q], &res[q]) ? 1 : 0;
+    *displaced = *wrapped = 0;
+    for (uint32_t s = 0; s <= t.mask; ++s) {
+        if (m.idx_key[s] == YbW32::EMPTY) continue;
+        const uint32_t home = yb_hash48(m.idx_key[s]) & t.mask;
+        *displaced += home != s;
+        *wrapped += home > s;
+    }
+    return 0;
+}

@@ -135,6 +135,7 @@ def replay_lib():
     lib = ctypes.CDLL(str(so))
     lib.replay_model.restype = ctypes.c_int
     lib.replay_model_lookup.restype = ctypes.c_int
+    lib.replay_model_lookup32.restype = ctypes.c_int
     return lib
 
 
@@ -153,3 +154,19 @@ def model_replay(lib, words, triples, form: int) -> list[list[int]]:
     assert rc == 0
     o = off.tolist()
     return [out[o[i]:o[i] + int(cnt[i])].tolist() for i in range(len(words))]
+
+
+def model_lookup32(lib, triples, queries):
+    """The table at 64-bit keys, built by the shared builder from `triples`, asked `queries` = [(a, b, tmin)]: a list of
+    (rank, merged) or None per query, then the number of index keys away from their hash's slot and of those that wrapped."""
+    left, right, merged = (np.ascontiguousarray(x, dtype=np.uint32) for x in triples)
+    q = np.array(queries, dtype=np.uint32).reshape(-1, 3)
+    a, b, tmin = (np.ascontiguousarray(q[:, k]) for k in range(3))
+    found = np.zeros(len(q) + 1, dtype=np.uint8)
+    rank, res = np.zeros(len(q) + 1, dtype=np.uint32), np.zeros(len(q) + 1, dtype=np.uint32)
+    displaced, wrapped = ctypes.c_uint32(0), ctypes.c_uint32(0)
+    vp = lambda x: ctypes.c_void_p(x.ctypes.data)  # noqa: E731
+    rc = lib.replay_model_lookup32(vp(left), vp(right), vp(merged), ctypes.c_uint32(len(left)), vp(a), vp(b), vp(tmin), ctypes.c_uint32(len(q)),
+                                   vp(found), vp(rank), vp(res), ctypes.byref(displaced), ctypes.byref(wrapped))
+    assert rc == 0
+    return [(int(rank[i]), int(res[i])) if found[i] else None for i in range(len(q))], displaced.value, wrapped.value

@@ -115,6 +115,63 @@ def test_lookup_smallest_rank_not_below_t(lib):
                                    ctypes.c_uint32(0), ctypes.byref(rank), ctypes.byref(res)) == 0
 
 
+# ---------------------------------------------------------------- the table at 64-bit keys (the u32 resumed load's)
+TOP = (1 << 24) - 3  # the largest u32-loop id
+
+
+def random_triples32():
+    """2,000 triples over 40 ids from the whole id range: about 1,100 keys in an index of 4,096 slots.  The seed is one at
+    which keys are pushed off their slot and a probe sequence runs past the end of the index (asserted below)."""
+    rng = random.Random(17)
+    ids = rng.sample(range(TOP + 1), 40)
+    return [(rng.choice(ids), rng.choice(ids), rng.randrange(TOP + 1)) for _ in range(2000)]
+
+
+CASES32 = {
+    "no merges": [],
+    "one merge": [(97, 98, 256)],
+    "one pair owns three ranks": [(1, 2, 300), (2, 2, 301), (1, 2, 300), (3, 1, 302), (1, 2, 300)],
+    "ids above 65,535": [(TOP, TOP, 70000), (65536, TOP, 70001), (TOP, 65536, 70002), (70000, 70001, TOP), (TOP, TOP, 70000),
+                         (65535, 65536, 70003), (1, 65536, 70004), (65536, 1, 70005)],
+    "2,000 random triples over 40 ids": random_triples32(),
+}
+
+
+@pytest.mark.parametrize("name", list(CASES32))
+def test_lookup_at_64_bit_keys_against_a_dict(lib, name):
+    """rp_build_table at YbW32 keys and rp32_lookup: every listed pair at tmin 0, at each of its ranks and at its last rank
+    + 1, and absent pairs, against {(l, r): sorted ranks}."""
+    triples = CASES32[name]
+    ranks: dict = {}
+    for i, (l, r, _m) in enumerate(triples):
+        ranks.setdefault((l, r), []).append(i)
+    queries = [(0, 0, 0), (TOP, TOP, 0), (65536, 1, 0), (TOP, 0, 7)]
+    for (l, r), rk in ranks.items():
+        queries += [(l, r, 0)] + [(l, r, t) for t in rk] + [(l, r, rk[-1] + 1), (r, l + 1, 0), (l + 1, r, 0)]
+    want = []
+    for a, b, tmin in queries:
+        first = next((t for t in ranks.get((a, b), []) if t >= tmin), None)
+        want.append(None if first is None else (first, triples[first][2]))
+    assert sum(w is None for w in want) >= 4 and (not triples or sum(w is not None for w in want) >= 2 * len(ranks))
+    cols = [np.array([t[k] for t in triples], dtype=np.uint32) for k in range(3)]
+    got, displaced, wrapped = rh.model_lookup32(lib, cols, queries)
+    assert got == want
+    if len(triples) == 2000:
+        assert 1000 < len(ranks) < 1600 and displaced > 0 and wrapped > 0, (len(ranks), displaced, wrapped)
+
+
+def test_the_64_bit_table_under_sanitizers(tmp_path):
+    """The same cases in a stand-alone program (tests/hostmodel/replay_table_check.cpp, its own main) built with the address
+    and undefined-behaviour sanitizers: an out-of-bounds read of the index or the entries ends it."""
+    import subprocess
+
+    exe = tmp_path / "replay_table_check"
+    subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
+                           "-o", str(exe), str(rh.HM / "replay_table_check.cpp")])
+    out = subprocess.run([str(exe)], capture_output=True, text=True)
+    assert out.returncode == 0 and out.stdout.startswith("ok:"), (out.stdout, out.stderr)
+
+
 # ---------------------------------------------------------------- the naive continuation, pinned
 def test_naive_continuation_from_scratch_equals_the_oracle():
     words = helpers.corpus_en_words()

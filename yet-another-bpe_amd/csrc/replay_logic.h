@@ -17,21 +17,34 @@
 #pragma once
 #include <stdint.h>
 
-#include "tile_logic.h" // YB_HD, yb_pairkey
+#include "tile_logic.h" // YB_HD, yb_pairkey, the width traits YbW16 / YbW32, yb_hash48
 
 constexpr uint32_t RP_NONE = 0xFFFFFFFFu; // no rank / no token / free index slot (a pair key is never 0xFFFFFFFF: ids < 0xFFFE)
 constexpr uint32_t RP_SHORT = 64;         // words of at most this many bytes: one lane per byte
 
 // ---------------------------------------------------------------- id-pair table: (left, right) -> its ranks, ascending
-struct RpEntry {
-    uint32_t key, rank, merged; // key = yb_pairkey(left, right)
+// One table for both id widths (tile_logic.h's traits): W::key_t keys, W::EMPTY (RP_NONE at 16 bits) for a free index slot
+// and for the key of the closing entry, rp_index_hash for the slot a key starts at.
+template <class W>
+struct RpEntryT {
+    typename W::key_t key; // W::key(left, right)
+    uint32_t rank, merged;
 };
 
-struct RpTable {
-    const uint32_t *idx_key;   // open addressing, load <= 1/2; RP_NONE = free
-    const uint32_t *idx_first; // first entry of the key in `ent`
-    uint32_t mask;             // capacity - 1 (a power of two)
-    const RpEntry *ent;        // sorted by (key, rank); closed by an entry with key RP_NONE
+template <class W>
+struct RpTableT {
+    const typename W::key_t *idx_key; // open addressing, load <= 1/2; W::EMPTY = free
+    const uint32_t *idx_first;        // first entry of the key in `ent`
+    uint32_t mask;                    // capacity - 1 (a power of two)
+    const RpEntryT<W> *ent;           // sorted by (key, rank); closed by an entry with key W::EMPTY
+};
+typedef RpEntryT<YbW16> RpEntry;
+typedef RpTableT<YbW16> RpTable;
+typedef RpEntryT<YbW32> Rp32Entry;
+// (the u32 load's kernel reads n as "anything to replay", and rp32_lookup bounds its walk over `ent` by it; the u16 kernels'
+// arguments stay as they are)
+struct Rp32Table : RpTableT<YbW32> {
+    uint32_t n; // merges (0: nothing to replay)
 };
 
 YB_HD uint32_t rp_mix(uint32_t x) {
@@ -42,6 +55,8 @@ YB_HD uint32_t rp_mix(uint32_t x) {
     x ^= x >> 16;
     return x;
 }
+YB_HD uint32_t rp_index_hash(YbW16, uint32_t key) { return rp_mix(key); }
+YB_HD uint32_t rp_index_hash(YbW32, unsigned long long key) { return yb_hash48(key); }
 
 // The smallest rank >= tmin of the pair (a, b), and the id that merge writes.
 YB_HD bool rp_lookup(const RpTable &t, uint32_t a, uint32_t b, uint32_t tmin, uint32_t *rank, uint32_t *merged) {
@@ -54,6 +69,30 @@ YB_HD bool rp_lookup(const RpTable &t, uint32_t a, uint32_t b, uint32_t tmin, ui
         s = (s + 1) & t.mask;
     }
     for (uint32_t i = t.idx_first[s]; t.ent[i].key == key; ++i)
+        if (t.ent[i].rank >= tmin) {
+            *rank = t.ent[i].rank;
+            *merged = t.ent[i].merged;
+            return true;
+        }
+    return false;
+}
+// The same at 64-bit keys.  Two bodies on purpose: the one above is the inner loop of k_replay_words, unbounded (it relies on
+// load <= 1/2); this one gives up after mask + 1 probes and never reads past the n entries.
+YB_HD bool rp32_lookup(const Rp32Table &t, uint32_t a, uint32_t b, uint32_t tmin, uint32_t *rank, uint32_t *merged) {
+    const unsigned long long key = YbW32::key(a, b);
+    uint32_t s = yb_hash48(key) & t.mask;
+    bool hit = false;
+    for (uint32_t probe = 0; probe <= t.mask; ++probe) {
+        const unsigned long long k = t.idx_key[s];
+        if (k == key) {
+            hit = true;
+            break;
+        }
+        if (k == YbW32::EMPTY) return false;
+        s = (s + 1) & t.mask;
+    }
+    if (!hit) return false;
+    for (uint32_t i = t.idx_first[s]; i < t.n && t.ent[i].key == key; ++i)
         if (t.ent[i].rank >= tmin) {
             *rank = t.ent[i].rank;
             *merged = t.ent[i].merged;
@@ -189,25 +228,34 @@ inline uint32_t rp_walk_lanes(const uint8_t *w, uint32_t L, const RpTable &t, ui
 #include <algorithm>
 #include <vector>
 
-struct RpTableHost {
-    std::vector<uint32_t> idx_key, idx_first;
-    std::vector<RpEntry> ent;
-    RpTable table() const { return RpTable{idx_key.data(), idx_first.data(), (uint32_t)idx_key.size() - 1u, ent.data()}; }
+template <class W>
+struct RpTableHostT {
+    std::vector<typename W::key_t> idx_key;
+    std::vector<uint32_t> idx_first;
+    std::vector<RpEntryT<W>> ent;
+    uint32_t n_merges() const { return (uint32_t)ent.size() - 1u; }
+    RpTableT<W> table() const { return RpTableT<W>{idx_key.data(), idx_first.data(), (uint32_t)idx_key.size() - 1u, ent.data()}; }
 };
+typedef RpTableHostT<YbW16> RpTableHost;
+typedef RpTableHostT<YbW32> Rp32TableHost;
 
-inline void rp_build_table(const uint32_t *left, const uint32_t *right, const uint32_t *merged, uint32_t n, RpTableHost *m) {
+// The one builder of both widths: entries sorted by (key, rank) and closed by an empty one, an index of at least 16 slots
+// and at least twice the merges, every key at the first free slot from its hash on.
+template <class W>
+inline void rp_build_table(const uint32_t *left, const uint32_t *right, const uint32_t *merged, uint32_t n, RpTableHostT<W> *m) {
+    typedef RpEntryT<W> Entry;
     m->ent.resize((size_t)n + 1);
-    for (uint32_t i = 0; i < n; ++i) m->ent[i] = RpEntry{yb_pairkey(left[i], right[i]), i, merged[i]};
-    std::sort(m->ent.begin(), m->ent.begin() + n, [](const RpEntry &x, const RpEntry &y) { return x.key != y.key ? x.key < y.key : x.rank < y.rank; });
-    m->ent[n] = RpEntry{RP_NONE, RP_NONE, RP_NONE};
+    for (uint32_t i = 0; i < n; ++i) m->ent[i] = Entry{W::key(left[i], right[i]), i, merged[i]};
+    std::sort(m->ent.begin(), m->ent.begin() + n, [](const Entry &x, const Entry &y) { return x.key != y.key ? x.key < y.key : x.rank < y.rank; });
+    m->ent[n] = Entry{W::EMPTY, RP_NONE, RP_NONE};
     size_t cap = 16;
     while (cap < 2 * (size_t)n) cap <<= 1;
-    m->idx_key.assign(cap, RP_NONE);
+    m->idx_key.assign(cap, W::EMPTY);
     m->idx_first.assign(cap, 0u);
     for (uint32_t i = 0; i < n; ++i) {
         if (i && m->ent[i - 1].key == m->ent[i].key) continue;
-        uint32_t s = rp_mix(m->ent[i].key) & (uint32_t)(cap - 1);
-        while (m->idx_key[s] != RP_NONE) s = (s + 1) & (uint32_t)(cap - 1);
+        uint32_t s = rp_index_hash(W(), m->ent[i].key) & (uint32_t)(cap - 1);
+        while (m->idx_key[s] != W::EMPTY) s = (s + 1) & (uint32_t)(cap - 1);
         m->idx_key[s] = m->ent[i].key;
         m->idx_first[s] = i;
     }

@@ -48,6 +48,14 @@ struct YbW32 {
     static YB_HD uint32_t right(key_t k) { return (uint32_t)(k & 0xFFFFFFull); }
 };
 
+// index hash of a 48-bit pair key: the u32 pair table, its LDS aggregator and the u32 replay table (replay_logic.h)
+YB_HD uint32_t yb_hash48(unsigned long long k) {
+    k ^= k >> 29;
+    k *= 0xBF58476D1CE4E5B9ull;
+    k ^= k >> 32;
+    return (uint32_t)k;
+}
+
 template <class W>
 struct YbDeltasT {
     // fixed slots (no runtime-indexed arrays, so the device keeps them in registers):

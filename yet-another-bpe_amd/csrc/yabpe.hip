@@ -121,6 +121,8 @@ enum LayBuf {
 
 }  // namespace
 
+constexpr double CAND_MARGIN_FIRST = 0.2;  // the candidate list's margin at the start of every job (job_reset)
+
 struct yabpe_ctx {
     int device = 0;
     int n_cu = 256;
@@ -259,7 +261,7 @@ struct yabpe_ctx {
     uint64_t cand_bits_cap = 0;               // table capacity it was sized to
     bool use_cand = false;
     uint64_t cand_rebuilds = 0, cand_rescans = 0;
-    double cand_margin = 0.2;        // T = best count x (1 - margin); adapted so that the list stays short
+    double cand_margin = CAND_MARGIN_FIRST;  // T = best count x (1 - margin); adapted so that the list stays short
     uint32_t cand_n_at_build = 0;
     // fused per-merge launch: the apply kernel of merge i ends with the selection of merge i + 1
     bool pending = false;            // a merge has been selected (recorded) and not applied yet
@@ -1313,6 +1315,7 @@ int base_vocab_upload(yabpe_ctx *c, const BaseVocab &V, uint32_t pool_cap, uint3
 // A load's arguments, checked before anything of the loaded corpus is given up.  *max_token_bytes: DESIGN.md (m), a property
 // of the load -- read here, fixed until the next load.
 int load_check_args(yabpe_ctx *c, const uint64_t *word_off, uint64_t n_words, int64_t *max_token_bytes) {
+    HIPCHK(c, hipSetDevice(c->device));
     if (!c->have_vocab) return fail(c, YABPE_E_INVALID, "call yabpe_set_vocab first");
     if (!word_off) return fail(c, YABPE_E_INVALID, "word_off is NULL");
     if (n_words >= 0xFFFFFFFFull) return fail(c, YABPE_E_CAPACITY, "more than 2^32-2 words per context");
@@ -1363,6 +1366,316 @@ int load_stage_inputs(yabpe_ctx *c, Scratch &In, Scratch &S, const uint8_t *byte
         L->pooled = true;
     }
     return 0;
+}
+
+// ---- the load driver (DESIGN.md "Host drivers"): one run state, and the steps that both id widths run.  The u16 load's own
+// steps stand in front of load_words_impl, the u32 load's in yabpe_id32_host.h.
+struct LoadRun {
+    yabpe_ctx *c;
+    Scratch In, S;  // the staged inputs; every other temporary of the load: pooled words, walk buffers, long-word lists
+    Events<3> ev;  // start, end, words replayed
+    LoadInputs L;
+    int64_t max_token_bytes = 0;
+    uint64_t total_tokens = 0;  // tokens of the words: their bytes, or what the replay leaves of them
+    const RpTable *rp = nullptr;             // the u16 resumed load: the model's table, and what the replay wrote:
+    uint32_t *d_wcnt = nullptr;              // tokens per word after the replay ...
+    uint16_t *d_wtok = nullptr;              // ... the tokens, word w's where its bytes start ...
+    unsigned long long *d_tokoff = nullptr;  // ... and the exclusive scan of the counts
+    uint32_t *d_long_word = nullptr;         // the u16 load: the words that go to the long-word buffers
+    explicit LoadRun(yabpe_ctx *c_) : c(c_), In(c_->device, c_->rank), S(c_->device, c_->rank) {}
+};
+
+// The loaded corpus given up, the new words on the device, the context told how many (a rank without words still runs the
+// layout of its peers: the collectives differ).  early_release: the staged inputs go as soon as pooled words replace them.
+int load_begin(LoadRun &R, const uint8_t *bytes, const uint64_t *word_off, const uint64_t *word_freq, uint64_t n_words, uint32_t flags, bool early_release) {
+    yabpe_ctx *c = R.c;
+    free_corpus(c);
+    HIPCHK(c, R.ev.create());
+    TRY(load_stage_inputs(c, R.In, R.S, bytes, word_off, word_freq, n_words, flags, R.ev.e[0], &R.L));
+    if (early_release && R.L.pooled) R.In.release();
+    c->weighted = R.L.freq != nullptr || (flags & YABPE_LOAD_DEDUP) != 0;
+    c->n_words = R.L.n_words;
+    c->tokens_initial = R.total_tokens = R.L.total_bytes;
+    return 0;
+}
+
+// The device state of a fresh job (trainer.py:227-235: the pair count follows; tok_len is in place before the first key enters
+// the table, so that count leaves out what is too long).  live_slots: known already, they travel with this push; NULL: counted later.
+int load_state_reset(yabpe_ctx *c, uint64_t total_tokens, int64_t max_token_bytes, const unsigned long long *live_slots = nullptr) {
+    TRY(state_pull(c));
+    DevState *h = c->st_host;
+    h->iter = 0; h->done = 0; h->halt = 0; h->halt_req = 0; h->sites = 0;
+    h->tokens_now = total_tokens;
+    h->table_entries = 0;
+    if (live_slots) h->live_slots = *live_slots;
+    h->tok_len = c->tt.len;
+    h->max_token_bytes = (uint32_t)max_token_bytes;
+    return state_push(c);
+}
+
+// Everything that starts over with a new corpus.  The whole statistics struct: every field of yabpe_stats_t is either a sum
+// that the calls after a load add to (the times, launches, merges and bytes of the phases, retiles, table_rebuilds -- the
+// load's own rebuild is not counted) or is assigned by yabpe_stats() on every call from the context and the device state
+// (n_words .. table_entries, scan_skip_*, cand_*, fused_launches, exchange*, pool_growths); load_ms is stored by the caller
+// after this.  Then the context's counters behind those fields, and the exchange's adaptive size.
+int job_reset(yabpe_ctx *c) {
+    c->stats = yabpe_stats_t{};
+    c->scan_skip_launches = c->cand_rebuilds = c->cand_rescans = c->fused_launches = c->exchanges = 0;
+    c->cand_margin = CAND_MARGIN_FIRST;  // (as a fresh context: what the last job's counts made of it says nothing about this one's)
+    c->xeff = c->xcap;  // (a new job starts with whole buffers: its first merges are its densest)
+    c->xseen[0] = c->xseen[1] = c->xseen[2] = c->xseen[3] = 0;
+    c->xeff_sum = c->exchange_growths = c->exchange_max_records = 0;
+    if (c->blk_read) HIPCHK(c, hipMemsetAsync(c->blk_read, 0, 2 * MAX_LISTS * 8, c->stream));  // (the statistics; the counter word keeps its tag)
+    return 0;
+}
+
+// The end of a load: the clock read, a new job's counters, the words declared loaded.  replayed: the load recorded ev.e[2]
+// when its words were replayed -- what came before and after it goes to resume_stats, with the long words.
+int load_account(LoadRun &R, bool replayed) {
+    yabpe_ctx *c = R.c;
+    HIPCHK(c, hipEventRecord(R.ev.e[1], c->stream));
+    HIPCHK(c, hipEventSynchronize(R.ev.e[1]));
+    float ms = 0, sms = 0;
+    HIPCHK(c, hipEventElapsedTime(&ms, R.ev.e[0], R.ev.e[1]));
+    if (replayed) {
+        HIPCHK(c, hipEventElapsedTime(&sms, R.ev.e[0], R.ev.e[2]));
+        c->resume_stats.segment_ms = sms;  // (pooling of equal words included)
+        c->resume_stats.build_ms = ms - sms;
+        c->resume_stats.n_long = c->n_long;
+    }
+    TRY(job_reset(c));
+    c->stats.load_ms = ms;
+    c->have_words = true;
+    return YABPE_OK;
+}
+
+// The merge triples of a resumed load against the vocabulary: every id exists, every merged token is as long as its operands.
+int check_merge_triples(yabpe_ctx *c, const uint32_t *left, const uint32_t *right, const uint32_t *merged, uint32_t n_merges) {
+    TRY(state_pull(c));
+    const uint32_t n_tokens = c->st_host->n_tokens;
+    std::vector<uint32_t> len(n_tokens);
+    HIPCHK(c, hipMemcpy(len.data(), c->tt.len, (size_t)n_tokens * 4, hipMemcpyDeviceToHost));
+    for (uint32_t i = 0; i < n_merges; ++i) {
+        const uint32_t l = left[i], r = right[i], m = merged[i];
+        if (l >= n_tokens || r >= n_tokens || m >= n_tokens)
+            return fail(c, YABPE_E_INVALID, "merge %u names token id %u, the vocabulary has %u", i, std::max(l, std::max(r, m)), n_tokens);
+        if (len[m] != len[l] + len[r])
+            return fail(c, YABPE_E_INVALID, "merge %u: token %u has %u bytes, its operands %u + %u", i, m, len[m], len[l], len[r]);
+    }
+    return 0;
+}
+
+// The replay table of either width (rp_build_table) in device memory that S owns.
+template <class W>
+int rp_upload(yabpe_ctx *c, Scratch &S, const RpTableHostT<W> &th, RpTableT<W> *t) {
+    t->mask = (uint32_t)th.idx_key.size() - 1u;
+    TRY(to_device(c, S, th.idx_key.data(), th.idx_key.size() * sizeof(typename W::key_t), 1, &t->idx_key));
+    TRY(to_device(c, S, th.idx_first.data(), th.idx_first.size() * 4, 1, &t->idx_first));
+    return to_device(c, S, th.ent.data(), th.ent.size() * sizeof(RpEntryT<W>), 1, &t->ent);
+}
+
+// ---- the u16 load's own steps over one LoadRun (the steps both widths run: load_begin .. load_account)
+// Resumed load: every word rewritten by the model's merges (replay_logic.h); the tiles step places it by its token count.
+int load_replay(LoadRun &R) {
+    yabpe_ctx *c = R.c;
+    const LoadInputs &L = R.L;
+    const uint64_t n_words = L.n_words;
+    c->resume_stats = yabpe_resume_stats_t{};
+    c->resume_stats.n_unique = n_words;
+    if (n_words) {
+        Scratch &S = R.S;
+        uint32_t *d_llen = nullptr, *d_ltok = nullptr, *d_lnxt = nullptr, *d_lprv = nullptr;
+        unsigned long long *d_lbase = nullptr, *d_lheap = nullptr;
+        HIPCHK(c, S.get(&R.d_wcnt, n_words)); HIPCHK(c, S.get(&R.d_wtok, L.total_bytes));
+        HIPCHK(c, S.get(&R.d_tokoff, n_words + 1));
+        HIPCHK(c, S.get(&d_llen, n_words)); HIPCHK(c, S.get(&d_lbase, n_words + 1));
+        HIPCHK(c, hipMemsetAsync(&c->scratch64[2], 0, 8, c->stream));
+        hipLaunchKernelGGL(k_replay_llen, dim3(cdiv64(n_words, 256)), dim3(256), 0, c->stream, L.off, (unsigned long long)n_words, d_llen, (uint32_t *)&c->scratch64[2]);
+        HIPCHK(c, hipGetLastError());
+        if (exclusive_scan<uint32_t>(c->stream, d_llen, n_words, d_lbase, (unsigned long long)n_words + 1) != 0)
+            return fail(c, YABPE_E_HIP, "scan of the long words failed: %s", hipGetErrorString(hipGetLastError()));
+        unsigned long long long_bytes = 0, too_long = 0;
+        HIPCHK(c, hipMemcpyAsync(&long_bytes, d_lbase + n_words, 8, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipMemcpyAsync(&too_long, &c->scratch64[2], 8, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        if (too_long & 0xFFFFFFFFull) return fail(c, YABPE_E_CAPACITY, "a single word longer than 2^32-1 bytes");
+        if (long_bytes) {
+            HIPCHK(c, S.get(&d_ltok, long_bytes)); HIPCHK(c, S.get(&d_lnxt, long_bytes));
+            HIPCHK(c, S.get(&d_lprv, long_bytes)); HIPCHK(c, S.get(&d_lheap, 3 * long_bytes));
+        }
+        ReplayWordsParams RW{L.bytes, L.off, (unsigned long long)L.off_base, (unsigned long long)n_words, d_lbase, *R.rp, R.d_wcnt, R.d_wtok, d_ltok, d_lnxt, d_lprv, d_lheap};
+        const uint32_t grid = (uint32_t)std::min<uint64_t>(cdiv64(n_words, WPB), (uint64_t)std::max(1, c->n_cu) * 8);
+        hipLaunchKernelGGL(k_replay_words, dim3(grid), dim3(BLOCK), 0, c->stream, RW);
+        HIPCHK(c, hipGetLastError());
+        if (exclusive_scan<uint32_t>(c->stream, R.d_wcnt, n_words, R.d_tokoff, (unsigned long long)n_words + 1) != 0)
+            return fail(c, YABPE_E_HIP, "scan of the token counts failed: %s", hipGetErrorString(hipGetLastError()));
+        unsigned long long tt = 0;
+        HIPCHK(c, hipMemcpyAsync(&tt, R.d_tokoff + n_words, 8, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        R.total_tokens = tt;
+        for (void *p : {(void *)d_llen, (void *)d_lbase, (void *)d_ltok, (void *)d_lnxt, (void *)d_lprv, (void *)d_lheap})
+            S.release(p);  // (the walk buffers: gone before the tiles are allocated)
+    }
+    HIPCHK(c, hipEventRecord(R.ev.e[2], c->stream));
+    c->tokens_initial = R.total_tokens;
+    c->resume_stats.tokens = R.total_tokens;
+    return 0;
+}
+
+// The one place that chooses among the three loaders: the replayed tokens (k_load_words_tok), or the bytes in load_form 1
+// (k_load_tiles: every tile written whole) or 0 (k_load_words: one thread per word into tiles filled beforehand).
+int load_launch_loader(LoadRun &R, bool tile_form, uint32_t long_cap) {
+    yabpe_ctx *c = R.c;
+    const LoadInputs &L = R.L;
+    const LoadParams P{L.bytes, L.off, (unsigned long long)L.off_base, (unsigned long long)L.n_words, c->tiles, c->tile_len, c->tile_wbase,
+                       (uint32_t *)&c->scratch64[2], &c->scratch64[3], R.d_long_word, long_cap};
+    if (R.rp) {
+        LoadTokParams Q{R.d_wtok, R.d_wcnt, R.d_tokoff, L.off, (unsigned long long)L.off_base, (unsigned long long)L.n_words, c->tiles, c->tile_len,
+                        c->tile_wbase, P.long_count, P.long_total, R.d_long_word, long_cap};
+        hipLaunchKernelGGL(k_load_words_tok, dim3(cdiv64(L.n_words, BLOCK)), dim3(BLOCK), 0, c->stream, Q);
+    } else if (tile_form) {
+        LoadTilesParams T{P, (unsigned long long)(L.off_base + L.total_bytes), c->n_tiles};
+        hipLaunchKernelGGL(k_load_tiles, dim3(cdiv64(c->n_tiles, WPB * YB_LOAD_RUN)), dim3(BLOCK), 0, c->stream, T);
+    } else {
+        hipLaunchKernelGGL(k_load_words, dim3(cdiv64(L.n_words, BLOCK)), dim3(BLOCK), 0, c->stream, P);
+    }
+    HIPCHK(c, hipGetLastError());
+    return 0;
+}
+
+// The tiles sized and allocated, the words loaded into them: at most twice, the second time with a long-word list as long
+// as the first attempt asked for.
+int load_tiles(LoadRun &R) {
+    yabpe_ctx *c = R.c;
+    const uint64_t n_words = R.L.n_words;
+    const uint64_t packed = R.total_tokens + n_words;
+    const uint64_t n_tiles64 = (packed + SPAN - 1) / SPAN;
+    if (n_tiles64 >= 0xFFFFFFF0ull) return fail(c, YABPE_E_CAPACITY, "corpus too large for one context");
+    c->n_tiles = (uint32_t)n_tiles64;
+    c->tiles_cap = c->n_tiles;
+    c->tiles_alt_cap = 0;
+    TRY(dmalloc(c, &c->tiles, (uint64_t)c->n_tiles * CAP));
+    TRY(dmalloc(c, &c->tile_len, c->n_tiles));
+    if (c->weighted) {
+        TRY(dmalloc(c, &c->tile_wbase, c->n_tiles));
+        TRY(dmalloc(c, &c->wfreq, n_words));
+        HIPCHK(c, hipMemsetAsync(&c->scratch64[1], 0, 8, c->stream));
+        if (n_words) {
+            hipLaunchKernelGGL(k_freq64_to_32, dim3(cdiv64(n_words, 256)), dim3(256), 0, c->stream, R.L.freq, c->wfreq,
+                               (unsigned long long)n_words, (uint32_t *)&c->scratch64[1]);
+            HIPCHK(c, hipGetLastError());
+        }
+    }
+    uint32_t long_cap = (uint32_t)optv(c, "long_cap", 1 << 16);
+    // load_form 1: the byte paths write every tile whole (k_load_tiles), nothing to fill or clear first; 0: one thread per word
+    const bool tile_form = !R.rp && optv(c, "load_form", 1) != 0;
+    for (int attempt = 0; attempt < 2; ++attempt) {
+        if (!tile_form) {
+            TRY(fill_u16(c, c->tiles, (uint64_t)c->n_tiles * CAP, YB_PAD));
+            HIPCHK(c, hipMemsetAsync(c->tile_len, 0, (size_t)c->n_tiles * 4, c->stream));
+            if (c->weighted) TRY(fill_u32(c, c->tile_wbase, c->n_tiles, 0xFFFFFFFFu));
+        }
+        HIPCHK(c, hipMemsetAsync(&c->scratch64[2], 0, 16, c->stream));  // [2] = long count (u32), [3] = long tokens
+        R.S.release(R.d_long_word);
+        HIPCHK(c, R.S.get(&R.d_long_word, long_cap));
+        if (n_words) TRY(load_launch_loader(R, tile_form, long_cap));
+        unsigned long long host2[2];
+        HIPCHK(c, hipMemcpyAsync(host2, &c->scratch64[2], 16, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        c->n_long = (uint32_t)(host2[0] & 0xFFFFFFFFu);
+        c->long_tokens = host2[1];
+        if (c->n_long <= long_cap) break;
+        long_cap = c->n_long;
+        if (attempt == 1) return fail(c, YABPE_E_INTERNAL, "long-word list overflow");
+    }
+    if (c->weighted) {
+        unsigned long long ov = 0;
+        HIPCHK(c, hipMemcpy(&ov, &c->scratch64[1], 8, hipMemcpyDeviceToHost));
+        if (ov & 0xFFFFFFFFu) return fail(c, YABPE_E_CAPACITY, "a word frequency exceeds 2^32-1");
+    }
+    // every word of the shard is a long one: the tiles counted for their bytes hold no word (a placeholder each in the weighted
+    // layout, read by nobody without a word beside it) -- this rank keeps no tile and launches no apply kernel over them
+    if (c->n_long && c->n_long == n_words) {
+        dfree(c->tiles); dfree(c->tile_len); dfree(c->tile_wbase);
+        c->tiles = nullptr; c->tile_len = c->tile_wbase = nullptr;
+        c->n_tiles = c->tiles_cap = 0;
+    }
+    return 0;
+}
+
+// The long words: a buffer of their own, one workgroup per word.
+int load_long_words(LoadRun &R) {
+    yabpe_ctx *c = R.c;
+    const LoadInputs &L = R.L;
+    uint32_t *const d_long_word = R.d_long_word, *d_ll = nullptr;
+    std::vector<uint32_t> lw(c->n_long);
+    HIPCHK(c, hipMemcpy(lw.data(), d_long_word, (size_t)c->n_long * 4, hipMemcpyDeviceToHost));
+    std::sort(lw.begin(), lw.end());  // deterministic layout
+    HIPCHK(c, hipMemcpy(d_long_word, lw.data(), (size_t)c->n_long * 4, hipMemcpyHostToDevice));
+    // where each long word goes: prefix sum of their lengths, on the device
+    HIPCHK(c, R.S.get(&d_ll, c->n_long));
+    TRY(dmalloc(c, &c->long_off, c->n_long + 1));
+    HIPCHK(c, hipMemsetAsync(&c->scratch64[2], 0, 8, c->stream));
+    if (R.rp)
+        hipLaunchKernelGGL(k_long_lengths_tok, dim3(cdiv64(c->n_long, 256)), dim3(256), 0, c->stream, R.d_wcnt, d_long_word, c->n_long, d_ll);
+    else
+        hipLaunchKernelGGL(k_long_lengths, dim3(cdiv64(c->n_long, 256)), dim3(256), 0, c->stream, L.off, d_long_word, c->n_long, d_ll, (uint32_t *)&c->scratch64[2]);
+    HIPCHK(c, hipGetLastError());
+    if (exclusive_scan<uint32_t>(c->stream, d_ll, c->n_long, c->long_off, (unsigned long long)c->n_long + 1) != 0)
+        return fail(c, YABPE_E_HIP, "long-word scan failed: %s", hipGetErrorString(hipGetLastError()));
+    unsigned long long long_total = 0, too_long = 0;
+    // (on the context's stream: it does not synchronise with the null stream, and a one-block scan returns without waiting)
+    HIPCHK(c, hipMemcpyAsync(&long_total, c->long_off + c->n_long, 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(&too_long, &c->scratch64[2], 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    R.S.release(d_ll);
+    if (too_long & 0xFFFFFFFFull) return fail(c, YABPE_E_CAPACITY, "a single word longer than 2^32-1 bytes");
+    TRY(dmalloc(c, &c->long_tok, long_total));
+    TRY(dmalloc(c, &c->long_len, c->n_long));
+    if (c->weighted) TRY(dmalloc(c, &c->long_freq, c->n_long));
+    if (R.rp) {
+        LoadLongTokParams Q{R.d_wtok, R.d_wcnt, L.off, (unsigned long long)L.off_base, L.freq, d_long_word, c->long_off, c->long_tok, c->long_len, c->long_freq, c->n_long};
+        hipLaunchKernelGGL(k_load_long_tok, dim3(c->n_long), dim3(BLOCK), 0, c->stream, Q);
+    } else {
+        LoadLongParams Q{L.bytes, L.off, L.freq, d_long_word, c->long_off, c->long_tok, c->long_len, c->long_freq, c->n_long};
+        hipLaunchKernelGGL(k_load_long, dim3(c->n_long), dim3(BLOCK), 0, c->stream, Q);
+    }
+    HIPCHK(c, hipGetLastError());
+    if (optv(c, "long_sig", 1)) {  // signatures: a merge whose pair is in no long word then costs 8 bytes per long word
+        c->long_sig_stride = (c->n_long + 31u) & ~31u;
+        TRY(dmalloc(c, &c->long_sig, (uint64_t)SIG_ROWS * c->long_sig_stride));
+        LongParams G{c->long_tok, c->long_off, c->long_len, c->long_freq, c->n_long, PairTable{}, c->st, c->long_sig, c->long_sig_stride};
+        hipLaunchKernelGGL(k_build_sig_long, dim3(c->n_long), dim3(BLOCK), 0, c->stream, G);
+        HIPCHK(c, hipGetLastError());
+    }
+    return 0;
+}
+
+// The temporaries gone, the state of a fresh job, the initial pair count (trainer.py:227-235), the accounts.
+int load_finish(LoadRun &R) {
+    yabpe_ctx *c = R.c;
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    R.In.release(); R.S.release();  // (before the pair table is built)
+    TRY(load_state_reset(c, R.total_tokens, R.max_token_bytes));
+    TRY(refresh_live_slots(c));
+    c->sig_valid = false;
+    // 65,536 possible byte pairs: start at load <= 1/4.  A resumed job's tokens are not bytes: the generic count, and a table
+    // that grows until its load is <= 1/2 (table_rebuild)
+    TRY(table_rebuild(c, 1ull << 18, /*all_bytes=*/R.rp == nullptr));
+    return load_account(R, /*replayed=*/R.rp != nullptr);  // (a plain load leaves resume_stats as the last resumed load wrote it)
+}
+
+// rp != NULL: the words are brought to the state the model's merges leave them in before they are tiled (the table's
+// arrays are device memory; pooled layout only)
+int load_words_impl(yabpe_ctx *c, const uint8_t *bytes, const uint64_t *word_off, const uint64_t *word_freq, uint64_t n_words, uint32_t flags, const RpTable *rp) {
+    LoadRun R(c);
+    R.rp = rp;
+    TRY(load_check_args(c, word_off, n_words, &R.max_token_bytes));
+    TRY(load_begin(R, bytes, word_off, word_freq, n_words, flags, /*early_release=*/true));  // (the pooled words replace the staged inputs at once)
+    if (rp) TRY(load_replay(R));
+    TRY(load_tiles(R));
+    if (c->n_long) TRY(load_long_words(R));
+    return load_finish(R);
 }
 
 // Room for `need` per-merge records; the first `keep` entries survive a move.
@@ -1677,265 +1990,6 @@ int yabpe_set_vocab(yabpe_ctx *c, const uint8_t *tok_bytes, const uint32_t *tok_
 }
 
 // ---------------------------------------------------------------------------------------------- corpus
-// rp != NULL: the words are brought to the state the model's merges leave them in before they are tiled (the table's
-// arrays are device memory; pooled layout only)
-static int load_words_impl(yabpe_ctx *c, const uint8_t *bytes, const uint64_t *word_off, const uint64_t *word_freq,
-                           uint64_t n_words, uint32_t flags, const RpTable *rp) {
-    HIPCHK(c, hipSetDevice(c->device));
-    int64_t max_token_bytes = 0;
-    TRY(load_check_args(c, word_off, n_words, &max_token_bytes));
-    free_corpus(c);
-    Events<3> evs;  // start, end, (resumed load) replay done
-    HIPCHK(c, evs.create());
-    const hipEvent_t ev0 = evs.e[0], ev1 = evs.e[1], ev_seg = evs.e[2];
-    Scratch In(c->device, c->rank);  // the staged inputs
-    Scratch S(c->device, c->rank);   // every other temporary of the load: pooled words, walk buffers, long-word lists
-    LoadInputs L;
-    TRY(load_stage_inputs(c, In, S, bytes, word_off, word_freq, n_words, flags, ev0, &L));
-    if (L.pooled) In.release();  // (the u16 load gives the staged inputs up at once: the pooled words replace them)
-    const unsigned long long *d_off = L.off, *d_freq = L.freq;
-    const uint8_t *d_bytes = L.bytes;
-    n_words = L.n_words;
-    const uint64_t total_bytes = L.total_bytes, off_base = L.off_base;
-    uint32_t *d_wcnt = nullptr;             // resumed load: tokens per word after the replay ...
-    uint16_t *d_wtok = nullptr;             // ... the tokens, word w's where its bytes start ...
-    unsigned long long *d_tokoff = nullptr; // ... and the exclusive scan of the counts
-    // (a rank that holds no words must still run the layout its peers run: the collectives differ between the layouts)
-    c->weighted = d_freq != nullptr || (flags & YABPE_LOAD_DEDUP) != 0;
-    c->n_words = n_words;
-    c->tokens_initial = total_bytes;
-
-    // ---- resumed load: every word rewritten by the model's merges (replay_logic.h), then placed by its token count
-    uint64_t total_tokens = total_bytes;
-    if (rp) {
-        c->resume_stats = yabpe_resume_stats_t{};
-        c->resume_stats.n_unique = n_words;
-        if (n_words) {
-            uint32_t *d_llen = nullptr, *d_ltok = nullptr, *d_lnxt = nullptr, *d_lprv = nullptr;
-            unsigned long long *d_lbase = nullptr, *d_lheap = nullptr;
-            HIPCHK(c, S.get(&d_wcnt, n_words));
-            HIPCHK(c, S.get(&d_wtok, total_bytes));
-            HIPCHK(c, S.get(&d_tokoff, n_words + 1));
-            HIPCHK(c, S.get(&d_llen, n_words));
-            HIPCHK(c, S.get(&d_lbase, n_words + 1));
-            HIPCHK(c, hipMemsetAsync(&c->scratch64[2], 0, 8, c->stream));
-            hipLaunchKernelGGL(k_replay_llen, dim3(cdiv64(n_words, 256)), dim3(256), 0, c->stream, d_off, (unsigned long long)n_words, d_llen, (uint32_t *)&c->scratch64[2]);
-            HIPCHK(c, hipGetLastError());
-            if (exclusive_scan<uint32_t>(c->stream, d_llen, n_words, d_lbase, (unsigned long long)n_words + 1) != 0)
-                return fail(c, YABPE_E_HIP, "scan of the long words failed: %s", hipGetErrorString(hipGetLastError()));
-            unsigned long long long_bytes = 0, too_long = 0;
-            HIPCHK(c, hipMemcpyAsync(&long_bytes, d_lbase + n_words, 8, hipMemcpyDeviceToHost, c->stream));
-            HIPCHK(c, hipMemcpyAsync(&too_long, &c->scratch64[2], 8, hipMemcpyDeviceToHost, c->stream));
-            HIPCHK(c, hipStreamSynchronize(c->stream));
-            if (too_long & 0xFFFFFFFFull) return fail(c, YABPE_E_CAPACITY, "a single word longer than 2^32-1 bytes");
-            if (long_bytes) {
-                HIPCHK(c, S.get(&d_ltok, long_bytes));
-                HIPCHK(c, S.get(&d_lnxt, long_bytes));
-                HIPCHK(c, S.get(&d_lprv, long_bytes));
-                HIPCHK(c, S.get(&d_lheap, 3 * long_bytes));
-            }
-            ReplayWordsParams RW{d_bytes, d_off, (unsigned long long)off_base, (unsigned long long)n_words, d_lbase, *rp, d_wcnt, d_wtok, d_ltok, d_lnxt, d_lprv, d_lheap};
-            const uint32_t grid = (uint32_t)std::min<uint64_t>(cdiv64(n_words, WPB), (uint64_t)std::max(1, c->n_cu) * 8);
-            hipLaunchKernelGGL(k_replay_words, dim3(grid), dim3(BLOCK), 0, c->stream, RW);
-            HIPCHK(c, hipGetLastError());
-            if (exclusive_scan<uint32_t>(c->stream, d_wcnt, n_words, d_tokoff, (unsigned long long)n_words + 1) != 0)
-                return fail(c, YABPE_E_HIP, "scan of the token counts failed: %s", hipGetErrorString(hipGetLastError()));
-            unsigned long long tt = 0;
-            HIPCHK(c, hipMemcpyAsync(&tt, d_tokoff + n_words, 8, hipMemcpyDeviceToHost, c->stream));
-            HIPCHK(c, hipStreamSynchronize(c->stream));
-            total_tokens = tt;
-            for (void *p : {(void *)d_llen, (void *)d_lbase, (void *)d_ltok, (void *)d_lnxt, (void *)d_lprv, (void *)d_lheap})
-                S.release(p);  // (the walk buffers: gone before the tiles are allocated)
-        }
-        HIPCHK(c, hipEventRecord(ev_seg, c->stream));
-        c->tokens_initial = total_tokens;
-        c->resume_stats.tokens = total_tokens;
-    }
-
-    // ---- tiles
-    const uint64_t packed = total_tokens + n_words;
-    const uint64_t n_tiles64 = (packed + SPAN - 1) / SPAN;
-    if (n_tiles64 >= 0xFFFFFFF0ull) return fail(c, YABPE_E_CAPACITY, "corpus too large for one context");
-    c->n_tiles = (uint32_t)n_tiles64;
-    c->tiles_cap = c->n_tiles;
-    c->tiles_alt_cap = 0;
-    TRY(dmalloc(c, &c->tiles, (uint64_t)c->n_tiles * CAP));
-    TRY(dmalloc(c, &c->tile_len, c->n_tiles));
-    if (c->weighted) {
-        TRY(dmalloc(c, &c->tile_wbase, c->n_tiles));
-        TRY(dmalloc(c, &c->wfreq, n_words));
-        HIPCHK(c, hipMemsetAsync(&c->scratch64[1], 0, 8, c->stream));
-        if (n_words) {
-            hipLaunchKernelGGL(k_freq64_to_32, dim3(cdiv64(n_words, 256)), dim3(256), 0, c->stream, d_freq, c->wfreq,
-                               (unsigned long long)n_words, (uint32_t *)&c->scratch64[1]);
-            HIPCHK(c, hipGetLastError());
-        }
-    }
-    uint32_t long_cap = (uint32_t)optv(c, "long_cap", 1 << 16);
-    uint32_t *d_long_word = nullptr;
-    // load_form 1: the byte paths write every tile whole (k_load_tiles), nothing to fill or clear first; 0: one thread per word
-    const bool tile_form = !rp && optv(c, "load_form", 1) != 0;
-    for (int attempt = 0; attempt < 2; ++attempt) {
-        if (!tile_form) {
-            TRY(fill_u16(c, c->tiles, (uint64_t)c->n_tiles * CAP, YB_PAD));
-            HIPCHK(c, hipMemsetAsync(c->tile_len, 0, (size_t)c->n_tiles * 4, c->stream));
-            if (c->weighted) TRY(fill_u32(c, c->tile_wbase, c->n_tiles, 0xFFFFFFFFu));
-        }
-        HIPCHK(c, hipMemsetAsync(&c->scratch64[2], 0, 16, c->stream));  // [2] = long count (u32), [3] = long tokens
-        S.release(d_long_word);
-        HIPCHK(c, S.get(&d_long_word, long_cap));
-        if (n_words) {
-            LoadParams P{d_bytes, d_off, (unsigned long long)off_base, (unsigned long long)n_words, c->tiles, c->tile_len, c->tile_wbase,
-                         (uint32_t *)&c->scratch64[2], &c->scratch64[3], d_long_word, long_cap};
-            if (rp) {
-                LoadTokParams Q{d_wtok, d_wcnt, d_tokoff, d_off, (unsigned long long)off_base, (unsigned long long)n_words, c->tiles, c->tile_len,
-                                c->tile_wbase, P.long_count, P.long_total, d_long_word, long_cap};
-                hipLaunchKernelGGL(k_load_words_tok, dim3(cdiv64(n_words, BLOCK)), dim3(BLOCK), 0, c->stream, Q);
-            } else if (tile_form) {
-                LoadTilesParams T{P, (unsigned long long)(off_base + total_bytes), c->n_tiles};
-                hipLaunchKernelGGL(k_load_tiles, dim3(cdiv64(c->n_tiles, WPB * YB_LOAD_RUN)), dim3(BLOCK), 0, c->stream, T);
-            } else {
-                hipLaunchKernelGGL(k_load_words, dim3(cdiv64(n_words, BLOCK)), dim3(BLOCK), 0, c->stream, P);
-            }
-            HIPCHK(c, hipGetLastError());
-        }
-        unsigned long long host2[2];
-        HIPCHK(c, hipMemcpyAsync(host2, &c->scratch64[2], 16, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        c->n_long = (uint32_t)(host2[0] & 0xFFFFFFFFu);
-        c->long_tokens = host2[1];
-        if (c->n_long <= long_cap) break;
-        long_cap = c->n_long;
-        if (attempt == 1) return fail(c, YABPE_E_INTERNAL, "long-word list overflow");
-    }
-    if (c->weighted) {
-        unsigned long long ov = 0;
-        HIPCHK(c, hipMemcpy(&ov, &c->scratch64[1], 8, hipMemcpyDeviceToHost));
-        if (ov & 0xFFFFFFFFu) return fail(c, YABPE_E_CAPACITY, "a word frequency exceeds 2^32-1");
-    }
-    // every word of the shard is a long one: the tiles counted for their bytes hold no word (a placeholder each in the weighted
-    // layout, read by nobody without a word beside it) -- this rank keeps no tile and launches no apply kernel over them
-    if (c->n_long && c->n_long == n_words) {
-        dfree(c->tiles); dfree(c->tile_len); dfree(c->tile_wbase);
-        c->tiles = nullptr;
-        c->tile_len = c->tile_wbase = nullptr;
-        c->n_tiles = 0;
-        c->tiles_cap = 0;
-    }
-    // ---- long words: own buffer, one workgroup per word
-    if (c->n_long) {
-        std::vector<uint32_t> lw(c->n_long);
-        HIPCHK(c, hipMemcpy(lw.data(), d_long_word, (size_t)c->n_long * 4, hipMemcpyDeviceToHost));
-        std::sort(lw.begin(), lw.end());  // deterministic layout
-        HIPCHK(c, hipMemcpy(d_long_word, lw.data(), (size_t)c->n_long * 4, hipMemcpyHostToDevice));
-        // where each long word goes: prefix sum of their lengths, on the device
-        uint32_t *d_ll = nullptr;
-        HIPCHK(c, S.get(&d_ll, c->n_long));
-        TRY(dmalloc(c, &c->long_off, c->n_long + 1));
-        HIPCHK(c, hipMemsetAsync(&c->scratch64[2], 0, 8, c->stream));
-        if (rp)
-            hipLaunchKernelGGL(k_long_lengths_tok, dim3(cdiv64(c->n_long, 256)), dim3(256), 0, c->stream, d_wcnt, d_long_word, c->n_long, d_ll);
-        else
-            hipLaunchKernelGGL(k_long_lengths, dim3(cdiv64(c->n_long, 256)), dim3(256), 0, c->stream, d_off, d_long_word, c->n_long, d_ll, (uint32_t *)&c->scratch64[2]);
-        HIPCHK(c, hipGetLastError());
-        if (exclusive_scan<uint32_t>(c->stream, d_ll, c->n_long, c->long_off, (unsigned long long)c->n_long + 1) != 0)
-            return fail(c, YABPE_E_HIP, "long-word scan failed: %s", hipGetErrorString(hipGetLastError()));
-        unsigned long long long_total = 0, too_long = 0;
-        // (on the context's stream: it does not synchronise with the null stream, and a one-block scan returns without waiting)
-        HIPCHK(c, hipMemcpyAsync(&long_total, c->long_off + c->n_long, 8, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipMemcpyAsync(&too_long, &c->scratch64[2], 8, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        S.release(d_ll);
-        if (too_long & 0xFFFFFFFFull) return fail(c, YABPE_E_CAPACITY, "a single word longer than 2^32-1 bytes");
-        TRY(dmalloc(c, &c->long_tok, long_total));
-        TRY(dmalloc(c, &c->long_len, c->n_long));
-        if (c->weighted) TRY(dmalloc(c, &c->long_freq, c->n_long));
-        if (rp) {
-            LoadLongTokParams L{d_wtok, d_wcnt, d_off, (unsigned long long)off_base, d_freq, d_long_word, c->long_off, c->long_tok, c->long_len, c->long_freq, c->n_long};
-            hipLaunchKernelGGL(k_load_long_tok, dim3(c->n_long), dim3(BLOCK), 0, c->stream, L);
-        } else {
-            LoadLongParams L{d_bytes, d_off, d_freq, d_long_word, c->long_off, c->long_tok, c->long_len, c->long_freq, c->n_long};
-            hipLaunchKernelGGL(k_load_long, dim3(c->n_long), dim3(BLOCK), 0, c->stream, L);
-        }
-        HIPCHK(c, hipGetLastError());
-        if (optv(c, "long_sig", 1)) {  // signatures: a merge whose pair is in no long word then costs 8 bytes per long word
-            c->long_sig_stride = (c->n_long + 31u) & ~31u;
-            TRY(dmalloc(c, &c->long_sig, (uint64_t)SIG_ROWS * c->long_sig_stride));
-            LongParams S{c->long_tok, c->long_off, c->long_len, c->long_freq, c->n_long, PairTable{}, c->st, c->long_sig, c->long_sig_stride};
-            hipLaunchKernelGGL(k_build_sig_long, dim3(c->n_long), dim3(BLOCK), 0, c->stream, S);
-            HIPCHK(c, hipGetLastError());
-        }
-    }
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    In.release();
-    S.release();  // (before the pair table is built)
-
-    // ---- state + initial pair count (trainer.py:227-235)
-    TRY(state_pull(c));
-    DevState *h = c->st_host;
-    h->iter = 0; h->done = 0; h->halt = 0; h->halt_req = 0; h->sites = 0;
-    h->tokens_now = total_tokens;
-    h->table_entries = 0;
-    h->tok_len = c->tt.len;  // (in place before the first key enters the table: the count below already leaves out what is too long)
-    h->max_token_bytes = (uint32_t)max_token_bytes;
-    TRY(state_push(c));
-    TRY(refresh_live_slots(c));
-    c->sig_valid = false;
-    // 65,536 possible byte pairs: start at load <= 1/4.  A resumed job's tokens are not bytes: the generic count, and a table
-    // that grows until its load is <= 1/2 (table_rebuild)
-    TRY(table_rebuild(c, 1ull << 18, /*all_bytes=*/rp == nullptr));
-    c->stats.table_rebuilds = 0;
-    HIPCHK(c, hipEventRecord(ev1, c->stream));
-    HIPCHK(c, hipEventSynchronize(ev1));
-    float ms = 0;
-    HIPCHK(c, hipEventElapsedTime(&ms, ev0, ev1));
-    if (rp) {
-        float sms = 0;
-        HIPCHK(c, hipEventElapsedTime(&sms, ev0, ev_seg));
-        c->resume_stats.segment_ms = sms;  // (pooling of equal words included)
-        c->resume_stats.build_ms = ms - sms;
-        c->resume_stats.n_long = c->n_long;
-    }
-    c->stats.load_ms = ms;
-    c->stats.retiles = 0;
-    c->stats.train_ms = 0;
-    c->stats.apply_ms_sampled = 0;
-    c->stats.apply_launches_sampled = 0;
-    c->stats.apply_algo_bytes_sampled = 0;
-    c->stats.apply_actual_bytes_sampled = 0;
-    c->stats.dense_ms_sampled = 0;
-    c->stats.dense_launches_sampled = 0;
-    c->stats.dense_launches = 0;
-    c->stats.dense_merges = 0;
-    c->stats.dense_algo_bytes_sampled = 0;
-    c->stats.dense_actual_bytes_sampled = 0;
-    c->stats.sparse_ms = 0;
-    c->stats.sparse_merges = 0;
-    c->stats.sparse_launches = 0;
-    c->stats.tail_ms = 0;
-    c->stats.tail_merges = 0;
-    c->stats.tail_launches = 0;
-    c->stats.exchange_ms_sampled = 0;
-    c->stats.exchanges_sampled = 0;
-    c->stats.scan_ms_sampled = 0;
-    c->stats.scan_launches_sampled = 0;
-    c->stats.scan_algo_bytes_sampled = 0;
-    c->stats.scan_actual_bytes_sampled = 0;
-    c->scan_skip_launches = 0;
-    c->cand_rebuilds = c->cand_rescans = 0;
-    c->fused_launches = 0;
-    c->exchanges = 0;
-    c->xeff = c->xcap;  // (a new job starts with whole buffers: its first merges are its densest)
-    c->xseen[0] = c->xseen[1] = c->xseen[2] = c->xseen[3] = 0;
-    c->xeff_sum = 0;
-    c->exchange_growths = 0;
-    c->exchange_max_records = 0;
-    if (c->blk_read) HIPCHK(c, hipMemsetAsync(c->blk_read, 0, 2 * MAX_LISTS * 8, c->stream));  // (the statistics; the counter word keeps its tag)
-    c->stats.algo_bytes_total = 0;
-    c->have_words = true;
-    return YABPE_OK;
-}
-
 int yabpe_load_words(yabpe_ctx *c, const uint8_t *bytes, const uint64_t *word_off, const uint64_t *word_freq,
                      uint64_t n_words, uint32_t flags) {
     if (!c) return YABPE_E_INVALID;
@@ -1959,29 +2013,12 @@ int yabpe_load_words_resumed(yabpe_ctx *c, const uint8_t *bytes, const uint64_t 
         return fail(c, YABPE_E_INVALID, "a resumed load needs the pooled layout: pass word_freq or YABPE_LOAD_DEDUP");
     if (c->multi) return fail(c, YABPE_E_INVALID, "a resumed load on several GPUs is not supported");
     if (!merge_left || !merge_right || !merge_merged) return fail(c, YABPE_E_INVALID, "merge triples are NULL");
-    TRY(state_pull(c));
-    const uint32_t n_tokens = c->st_host->n_tokens;
-    std::vector<uint32_t> len(n_tokens);
-    HIPCHK(c, hipMemcpy(len.data(), c->tt.len, (size_t)n_tokens * 4, hipMemcpyDeviceToHost));
-    for (uint32_t i = 0; i < n_merges; ++i) {
-        const uint32_t l = merge_left[i], r = merge_right[i], m = merge_merged[i];
-        if (l >= n_tokens || r >= n_tokens || m >= n_tokens)
-            return fail(c, YABPE_E_INVALID, "merge %u names token id %u, the vocabulary has %u", i, std::max(l, std::max(r, m)), n_tokens);
-        if (len[m] != len[l] + len[r])
-            return fail(c, YABPE_E_INVALID, "merge %u: token %u has %u bytes, its operands %u + %u", i, m, len[m], len[l], len[r]);
-    }
+    TRY(check_merge_triples(c, merge_left, merge_right, merge_merged, n_merges));
     RpTableHost th;
     rp_build_table(merge_left, merge_right, merge_merged, n_merges, &th);
     Scratch S(c->device, c->rank);
-    uint32_t *d_key = nullptr, *d_first = nullptr;
-    RpEntry *d_ent = nullptr;
-    HIPCHK(c, S.get(&d_key, th.idx_key.size()));
-    HIPCHK(c, S.get(&d_first, th.idx_first.size()));
-    HIPCHK(c, S.get(&d_ent, th.ent.size()));
-    HIPCHK(c, hipMemcpy(d_key, th.idx_key.data(), th.idx_key.size() * 4, hipMemcpyHostToDevice));
-    HIPCHK(c, hipMemcpy(d_first, th.idx_first.data(), th.idx_first.size() * 4, hipMemcpyHostToDevice));
-    HIPCHK(c, hipMemcpy(d_ent, th.ent.data(), th.ent.size() * sizeof(RpEntry), hipMemcpyHostToDevice));
-    const RpTable t{d_key, d_first, (uint32_t)th.idx_key.size() - 1u, d_ent};
+    RpTable t{};
+    TRY(rp_upload(c, S, th, &t));
     const int rc = load_words_impl(c, bytes, word_off, word_freq, n_words, flags, &t);
     (void)hipStreamSynchronize(c->stream);
     return rc;

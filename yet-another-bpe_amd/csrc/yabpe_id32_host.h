@@ -188,98 +188,54 @@ int id32_grow_pool(yabpe_ctx *c) {
 }
 
 // ---------------------------------------------------------------------------------------------- corpus
-// merges != NULL: a resumed load (the words are rewritten by the model's merges before they are tiled)
-int id32_load(yabpe_ctx *c, const uint8_t *bytes, const uint64_t *word_off, const uint64_t *word_freq, uint64_t n_words, uint32_t flags,
-              const uint32_t *ml, const uint32_t *mr, const uint32_t *mm, uint32_t n_merges) {
-    HIPCHK(c, hipSetDevice(c->device));
-    int64_t max_token_bytes = 0;
-    TRY(load_check_args(c, word_off, n_words, &max_token_bytes));
-    if (c->multi) return fail(c, YABPE_E_INVALID, "id_bits = 32 is single-device: this context has a communicator attached");
-    TRY(state_pull(c));
-    const uint32_t n_tokens = c->st_host->n_tokens;
-    Rp32Table rp{nullptr, nullptr, 0, nullptr, 0};
-    Scratch S(c->device, c->rank);
-    if (n_merges) {
-        if (!ml || !mr || !mm) return fail(c, YABPE_E_INVALID, "merge triples are NULL");
-        std::vector<uint32_t> len(n_tokens);
-        HIPCHK(c, hipMemcpy(len.data(), c->tt.len, (size_t)n_tokens * 4, hipMemcpyDeviceToHost));
-        std::vector<Rp32Entry> ent((size_t)n_merges + 1);
-        for (uint32_t i = 0; i < n_merges; ++i) {
-            const uint32_t l = ml[i], r = mr[i], m = mm[i];
-            if (l >= n_tokens || r >= n_tokens || m >= n_tokens)
-                return fail(c, YABPE_E_INVALID, "merge %u names token id %u, the vocabulary has %u", i, std::max(l, std::max(r, m)), n_tokens);
-            if (len[m] != len[l] + len[r])
-                return fail(c, YABPE_E_INVALID, "merge %u: token %u has %u bytes, its operands %u + %u", i, m, len[m], len[l], len[r]);
-            ent[i] = Rp32Entry{YbW32::key(l, r), i, m};
-        }
-        std::sort(ent.begin(), ent.begin() + n_merges, [](const Rp32Entry &x, const Rp32Entry &y) { return x.key != y.key ? x.key < y.key : x.rank < y.rank; });
-        ent[n_merges] = Rp32Entry{EMPTY32, 0xFFFFFFFFu, 0xFFFFFFFFu};
-        size_t cap = 16;
-        while (cap < 2 * (size_t)n_merges) cap <<= 1;
-        std::vector<unsigned long long> idx_key(cap, EMPTY32);
-        std::vector<uint32_t> idx_first(cap, 0u);
-        auto h48 = [](unsigned long long k) { k ^= k >> 29; k *= 0xBF58476D1CE4E5B9ull; k ^= k >> 32; return (uint32_t)k; };
-        for (uint32_t i = 0; i < n_merges; ++i) {
-            if (i && ent[i - 1].key == ent[i].key) continue;
-            uint32_t s = h48(ent[i].key) & (uint32_t)(cap - 1);
-            while (idx_key[s] != EMPTY32) s = (s + 1) & (uint32_t)(cap - 1);
-            idx_key[s] = ent[i].key;
-            idx_first[s] = i;
-        }
-        unsigned long long *d_key = nullptr;
-        uint32_t *d_first = nullptr;
-        Rp32Entry *d_ent = nullptr;
-        HIPCHK(c, S.get(&d_key, cap)); HIPCHK(c, S.get(&d_first, cap)); HIPCHK(c, S.get(&d_ent, ent.size()));
-        HIPCHK(c, hipMemcpy(d_key, idx_key.data(), cap * 8, hipMemcpyHostToDevice));
-        HIPCHK(c, hipMemcpy(d_first, idx_first.data(), cap * 4, hipMemcpyHostToDevice));
-        HIPCHK(c, hipMemcpy(d_ent, ent.data(), ent.size() * sizeof(Rp32Entry), hipMemcpyHostToDevice));
-        rp = Rp32Table{d_key, d_first, (uint32_t)(cap - 1), d_ent, n_merges};
-    }
-    free_corpus(c);
-    id32_free_corpus(c);
-    Events<3> evs;  // start, end, words replayed
-    HIPCHK(c, evs.create());
-    // ---- inputs on the device, equal words pooled: all of it stays in S until the load returns (the u32 load keeps the
-    // staged inputs after the pooling: the rp table sits in the same Scratch)
-    LoadInputs L;
-    TRY(load_stage_inputs(c, S, S, bytes, word_off, word_freq, n_words, flags, evs.e[0], &L));
-    const unsigned long long *d_off = L.off, *d_freq = L.freq;
-    const uint8_t *d_bytes = L.bytes;
-    n_words = L.n_words;
-    const uint64_t total_bytes = L.total_bytes, off_base = L.off_base;
-    c->weighted = true;  // one layout: a word without a count weighs 1
-    c->n_words = n_words;
-
-    // ---- words as u32 ids (replayed), their places
-    uint32_t *d_wtok = nullptr, *d_wcnt = nullptr, *d_slots = nullptr, *d_short = nullptr, *d_lng = nullptr, *d_llen = nullptr;
-    unsigned long long *d_pos = nullptr, *d_srank = nullptr, *d_lrank = nullptr, *d_lpos = nullptr;
-    HIPCHK(c, S.get(&d_wtok, total_bytes + 1)); HIPCHK(c, S.get(&d_wcnt, n_words + 1));
-    HIPCHK(c, S.get(&d_slots, n_words + 1)); HIPCHK(c, S.get(&d_short, n_words + 1));
-    HIPCHK(c, S.get(&d_lng, n_words + 1)); HIPCHK(c, S.get(&d_llen, n_words + 1));
-    HIPCHK(c, S.get(&d_pos, n_words + 1)); HIPCHK(c, S.get(&d_srank, n_words + 1));
-    HIPCHK(c, S.get(&d_lrank, n_words + 1)); HIPCHK(c, S.get(&d_lpos, n_words + 1));
-    HIPCHK(c, hipMemsetAsync(&c->scratch64[1], 0, 16, c->stream));  // [1] frequency overflow, [2] word too long
+// The u32 load on the load driver's skeleton (LoadRun, the shared steps: yabpe.hip).  What its own two steps hand on:
+struct Words32 {
+    uint32_t *wtok = nullptr, *wcnt = nullptr, *slots = nullptr, *is_short = nullptr, *is_long = nullptr, *long_len = nullptr;
+    unsigned long long *pos = nullptr, *srank = nullptr, *lrank = nullptr, *lpos = nullptr;
     unsigned long long tot[4] = {0, 0, 0, 0};  // slots, short words, long words, long tokens
+};
+
+// words as u32 ids (replayed by rp's merges, if any), their places
+int id32_load_words(LoadRun &R, const Rp32Table &rp, Words32 &W) {
+    yabpe_ctx *c = R.c;
+    const LoadInputs &L = R.L;
+    const uint64_t n_words = L.n_words;
+    Scratch &S = R.S;
+    HIPCHK(c, S.get(&W.wtok, L.total_bytes + 1)); HIPCHK(c, S.get(&W.wcnt, n_words + 1));
+    HIPCHK(c, S.get(&W.slots, n_words + 1)); HIPCHK(c, S.get(&W.is_short, n_words + 1));
+    HIPCHK(c, S.get(&W.is_long, n_words + 1)); HIPCHK(c, S.get(&W.long_len, n_words + 1));
+    HIPCHK(c, S.get(&W.pos, n_words + 1)); HIPCHK(c, S.get(&W.srank, n_words + 1));
+    HIPCHK(c, S.get(&W.lrank, n_words + 1)); HIPCHK(c, S.get(&W.lpos, n_words + 1));
+    HIPCHK(c, hipMemsetAsync(&c->scratch64[1], 0, 16, c->stream));  // [1] frequency overflow, [2] word too long
     if (n_words) {
         const uint32_t wg = cdiv64(n_words, BLOCK);
         hipLaunchKernelGGL(k32_words, dim3(wg), dim3(BLOCK), 0, c->stream,
-                           Words32Params{d_bytes, d_off, (unsigned long long)off_base, (unsigned long long)n_words, d_wtok, d_wcnt, rp, (uint32_t *)&c->scratch64[2]});
+                           Words32Params{L.bytes, L.off, (unsigned long long)L.off_base, (unsigned long long)n_words, W.wtok, W.wcnt, rp, (uint32_t *)&c->scratch64[2]});
         HIPCHK(c, hipGetLastError());
-        hipLaunchKernelGGL(k32_word_slots, dim3(wg), dim3(BLOCK), 0, c->stream, Slots32Params{d_wcnt, (unsigned long long)n_words, d_slots, d_short, d_lng, d_llen});
+        hipLaunchKernelGGL(k32_word_slots, dim3(wg), dim3(BLOCK), 0, c->stream, Slots32Params{W.wcnt, (unsigned long long)n_words, W.slots, W.is_short, W.is_long, W.long_len});
         HIPCHK(c, hipGetLastError());
-        const uint32_t *in[4] = {d_slots, d_short, d_lng, d_llen};
-        unsigned long long *out[4] = {d_pos, d_srank, d_lrank, d_lpos};
+        const uint32_t *in[4] = {W.slots, W.is_short, W.is_long, W.long_len};
+        unsigned long long *out[4] = {W.pos, W.srank, W.lrank, W.lpos};
         for (int k = 0; k < 4; ++k) {
             if (exclusive_scan<uint32_t>(c->stream, in[k], n_words, out[k], (unsigned long long)n_words + 1) != 0)
                 return fail(c, YABPE_E_HIP, "scan of the word places failed: %s", hipGetErrorString(hipGetLastError()));
-            HIPCHK(c, hipMemcpyAsync(&tot[k], out[k] + n_words, 8, hipMemcpyDeviceToHost, c->stream));
+            HIPCHK(c, hipMemcpyAsync(&W.tot[k], out[k] + n_words, 8, hipMemcpyDeviceToHost, c->stream));
         }
         unsigned long long flagsd[2] = {0, 0};
         HIPCHK(c, hipMemcpyAsync(flagsd, &c->scratch64[1], 16, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
         if (flagsd[1] & 0xFFFFFFFFull) return fail(c, YABPE_E_CAPACITY, "a single word longer than 2^32-1 bytes");
     }
-    HIPCHK(c, hipEventRecord(evs.e[2], c->stream));
+    HIPCHK(c, hipEventRecord(R.ev.e[2], c->stream));
+    return 0;
+}
+
+// the tiles and the long-word buffers sized from the totals and allocated, the words written to them
+int id32_load_place(LoadRun &R, const Words32 &W) {
+    yabpe_ctx *c = R.c;
+    const LoadInputs &L = R.L;
+    const uint64_t n_words = L.n_words;
+    const unsigned long long *tot = W.tot;
     const uint64_t n_tiles64 = (tot[0] + SPAN32 - 1) / SPAN32;
     if (n_tiles64 >= 0xFFFFFFF0ull || tot[1] >= 0xFFFFFFFFull) return fail(c, YABPE_E_CAPACITY, "corpus too large for one context");
     c->n_tiles = (uint32_t)n_tiles64;
@@ -297,11 +253,11 @@ int id32_load(yabpe_ctx *c, const uint8_t *bytes, const uint64_t *word_off, cons
     if (n_words) {
         if (c->n_tiles) {
             hipLaunchKernelGGL(k32_build_tiles, dim3(c->n_tiles), dim3(BLOCK), 0, c->stream,
-                               Tiles32Params{d_wtok, d_wcnt, d_off, (unsigned long long)off_base, (unsigned long long)n_words, d_pos, d_srank, c->tiles32, c->tile_len, c->tile_wbase, c->n_tiles});
+                               Tiles32Params{W.wtok, W.wcnt, L.off, (unsigned long long)L.off_base, (unsigned long long)n_words, W.pos, W.srank, c->tiles32, c->tile_len, c->tile_wbase, c->n_tiles});
             HIPCHK(c, hipGetLastError());
         }
         hipLaunchKernelGGL(k32_place_words, dim3(cdiv64(n_words, BLOCK)), dim3(BLOCK), 0, c->stream,
-                           Place32Params{d_wtok, d_wcnt, d_off, (unsigned long long)off_base, (unsigned long long)n_words, d_freq, d_short, d_lng, d_srank, d_lrank, d_lpos,
+                           Place32Params{W.wtok, W.wcnt, L.off, (unsigned long long)L.off_base, (unsigned long long)n_words, L.freq, W.is_short, W.is_long, W.srank, W.lrank, W.lpos,
                                          c->wfreq, c->long_tok32, c->long_off, c->long_len, c->long_freq, (uint32_t *)&c->scratch64[1]});
         HIPCHK(c, hipGetLastError());
         unsigned long long ov = 0;
@@ -309,41 +265,43 @@ int id32_load(yabpe_ctx *c, const uint8_t *bytes, const uint64_t *word_off, cons
         HIPCHK(c, hipStreamSynchronize(c->stream));
         if (ov & 0xFFFFFFFFull) return fail(c, YABPE_E_CAPACITY, "a word frequency exceeds 2^32-1");
     }
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    S.release();
-    const uint64_t total_tokens = tot[0] - tot[1] + tot[3];
-    c->tokens_initial = total_tokens;
-
-    // ---- state + initial pair count (trainer.py:227-235)
-    TRY(state_pull(c));
-    DevState *h = c->st_host;
-    h->iter = 0; h->done = 0; h->halt = 0; h->halt_req = 0; h->sites = 0;
-    h->tokens_now = total_tokens;
-    h->table_entries = 0;
-    h->live_slots = tot[0];
-    h->tok_len = c->tt.len;
-    h->max_token_bytes = (uint32_t)max_token_bytes;
-    TRY(state_push(c));
-    TRY(id32_table_rebuild(c, (uint64_t)1 << std::min<int64_t>(30, std::max<int64_t>(10, optv(c, "table_min_log2", 16)))));
-    c->stats = yabpe_stats_t{};
-    HIPCHK(c, hipEventRecord(evs.e[1], c->stream));
-    HIPCHK(c, hipEventSynchronize(evs.e[1]));
-    float ms = 0, sms = 0;
-    HIPCHK(c, hipEventElapsedTime(&ms, evs.e[0], evs.e[1]));
-    HIPCHK(c, hipEventElapsedTime(&sms, evs.e[0], evs.e[2]));
+    R.total_tokens = tot[0] - tot[1] + tot[3];
+    c->tokens_initial = R.total_tokens;
+    // (the u32 load writes resume_stats on every load, the u16 load only on a resumed one)
     c->resume_stats = yabpe_resume_stats_t{};
     c->resume_stats.n_unique = n_words;
-    c->resume_stats.n_long = c->n_long;
-    c->resume_stats.tokens = total_tokens;
-    c->resume_stats.segment_ms = sms;
-    c->resume_stats.build_ms = ms - sms;
-    c->stats.load_ms = ms;
-    c->cand_rebuilds = c->cand_rescans = 0;
-    c->fused_launches = 0;
-    c->exchanges = 0;
-    c->scan_skip_launches = 0;
-    c->have_words = true;
-    return YABPE_OK;
+    c->resume_stats.tokens = R.total_tokens;
+    return 0;
+}
+
+// n_merges != 0: a resumed load (the words are rewritten by the model's merges before they are tiled)
+int id32_load(yabpe_ctx *c, const uint8_t *bytes, const uint64_t *word_off, const uint64_t *word_freq, uint64_t n_words, uint32_t flags,
+              const uint32_t *ml, const uint32_t *mr, const uint32_t *mm, uint32_t n_merges) {
+    LoadRun R(c);
+    TRY(load_check_args(c, word_off, n_words, &R.max_token_bytes));
+    if (c->multi) return fail(c, YABPE_E_INVALID, "id_bits = 32 is single-device: this context has a communicator attached");
+    Rp32Table rp{{nullptr, nullptr, 0, nullptr}, 0};
+    if (n_merges) {  // (checked and built before the loaded corpus is given up; the table lives in R.S until the load returns)
+        if (!ml || !mr || !mm) return fail(c, YABPE_E_INVALID, "merge triples are NULL");
+        TRY(check_merge_triples(c, ml, mr, mm, n_merges));
+        Rp32TableHost th;
+        rp_build_table(ml, mr, mm, n_merges, &th);
+        TRY(rp_upload<YbW32>(c, R.S, th, &rp));
+        rp.n = n_merges;
+    }
+    id32_free_corpus(c);
+    TRY(load_begin(R, bytes, word_off, word_freq, n_words, flags, /*early_release=*/false));  // (the staged inputs stay until the load returns)
+    c->weighted = true;  // one layout: a word without a count weighs 1
+    Words32 W;
+    TRY(id32_load_words(R, rp, W));
+    TRY(id32_load_place(R, W));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    R.In.release(); R.S.release();
+    TRY(load_state_reset(c, R.total_tokens, R.max_token_bytes, &W.tot[0]));  // (live_slots: the scan's total; u16 sums tile_len)
+    // (its own table builder, at the table_min_log2 size; the u16 load starts at 2^18 slots)
+    TRY(id32_table_rebuild(c, (uint64_t)1 << std::min<int64_t>(30, std::max<int64_t>(10, optv(c, "table_min_log2", 16)))));
+    // (its job_reset also resets the exchange's counters and blk_read: id_bits is fixed and this load refuses a communicator -- unobservable)
+    return load_account(R, /*replayed=*/true);
 }
 
 // ---------------------------------------------------------------------------------------------- repack

@@ -15,6 +15,7 @@
 // lengths they are given.  Nothing waits for another workgroup.
 #pragma once
 #include "yabpe_kernels.h"
+#include "replay_logic.h"
 
 namespace yb {
 
@@ -51,16 +52,9 @@ __device__ __forceinline__ void cand32_append(const PairTable32 &t, uint32_t s) 
     if (idx < t.cand_cap) t.cand_list[idx] = s; else t.cs->overflow = 1u;
 }
 
-__device__ __forceinline__ uint32_t hash48(unsigned long long k) {
-    k ^= k >> 29;
-    k *= 0xBF58476D1CE4E5B9ull;
-    k ^= k >> 32;
-    return (uint32_t)k;
-}
-
 // cnt[key] += d.  A key enters a table only here; with a maximum token length a pair over the limit never does (limit_logic.h).
 __device__ __forceinline__ void gt32_add(const PairTable32 &t, DevState *st, unsigned long long key, long long d) {
-    uint32_t s = hash48(key) & t.mask;
+    uint32_t s = yb_hash48(key) & t.mask;
     for (uint32_t probe = 0; probe < t.max_probe; ++probe) {
         unsigned long long k = __hip_atomic_load(&t.keys[s], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         if (k == EMPTY32) {
@@ -91,7 +85,7 @@ __device__ __forceinline__ void gt32_add(const PairTable32 &t, DevState *st, uns
 
 // count of a key, 0 when absent; *found says which
 __device__ __forceinline__ long long gt32_lookup(const PairTable32 &t, unsigned long long key, bool *found) {
-    uint32_t s = hash48(key) & t.mask;
+    uint32_t s = yb_hash48(key) & t.mask;
     *found = false;
     for (uint32_t probe = 0; probe < t.max_probe; ++probe) {
         const unsigned long long k = t.keys[s];
@@ -117,7 +111,7 @@ __device__ __forceinline__ void agg32_init(Agg32 g) {
     }
 }
 __device__ __forceinline__ void agg32_add(Agg32 g, const PairTable32 &t, DevState *st, unsigned long long key, long long d) {
-    uint32_t s = (hash48(key) >> 7) & (uint32_t)(AGG32_N - 1);
+    uint32_t s = (yb_hash48(key) >> 7) & (uint32_t)(AGG32_N - 1);
     for (int probe = 0; probe < AGG32_PROBE; ++probe) {
         unsigned long long k = g.keys[s];
         if (k == EMPTY32) {
@@ -693,42 +687,7 @@ __global__ __launch_bounds__(BLOCK) void k32_repack(Repack32Params P) {
 }
 
 // ================================================================ load: bytes + offsets -> pooled words of u32 ids -> tiles
-// id-pair table of a resumed load at 64-bit keys: replay_logic.h's table with YbW32 keys
-struct Rp32Entry {
-    unsigned long long key;
-    uint32_t rank, merged;
-};
-struct Rp32Table {
-    const unsigned long long *idx_key; // open addressing, load <= 1/2; EMPTY32 = free
-    const uint32_t *idx_first;         // first entry of the key in `ent`
-    uint32_t mask;
-    const Rp32Entry *ent;              // sorted by (key, rank); closed by an entry with key EMPTY32
-    uint32_t n;                        // merges (0: nothing to replay)
-};
-// the smallest rank >= tmin of the pair (a, b), and the id that merge writes (rp_lookup)
-__device__ __forceinline__ bool rp32_lookup(const Rp32Table &t, uint32_t a, uint32_t b, uint32_t tmin, uint32_t *rank, uint32_t *merged) {
-    const unsigned long long key = YbW32::key(a, b);
-    uint32_t s = hash48(key) & t.mask;
-    bool hit = false;
-    for (uint32_t probe = 0; probe <= t.mask; ++probe) {
-        const unsigned long long k = t.idx_key[s];
-        if (k == key) {
-            hit = true;
-            break;
-        }
-        if (k == EMPTY32) return false;
-        s = (s + 1) & t.mask;
-    }
-    if (!hit) return false;
-    for (uint32_t i = t.idx_first[s]; i < t.n && t.ent[i].key == key; ++i)
-        if (t.ent[i].rank >= tmin) {
-            *rank = t.ent[i].rank;
-            *merged = t.ent[i].merged;
-            return true;
-        }
-    return false;
-}
-
+// (the id-pair table of a resumed load at 64-bit keys: Rp32Table and rp32_lookup of replay_logic.h)
 struct Words32Params {
     const uint8_t *bytes;
     const unsigned long long *off; // absolute

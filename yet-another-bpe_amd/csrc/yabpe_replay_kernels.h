@@ -1,6 +1,6 @@
 // yabpe_replay_kernels.h -- loading words in the state a trained model's merges leave them in (rules in replay_logic.h).
 //
-// Passes (host orchestration: load_words_impl in yabpe.hip, after the optional pooling of equal words):
+// Passes (host orchestration: load_replay, load_tiles and load_long_words in yabpe.hip, after the optional pooling of equal words):
 //   segment   k_replay_llen / exclusive_scan (scratch of the words of more than RP_SHORT bytes) -> k_replay_words: one wave
 //             per pooled word -- its u16 tokens after the replay (written where its bytes start) and their number
 //   place     exclusive_scan of the token counts: packed position of word w = its token offset + w (every earlier word
