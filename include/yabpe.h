@@ -748,6 +748,64 @@ typedef struct yabpe_mask_stats_t {
 } yabpe_mask_stats_t;
 int yabpe_mask_stats(yabpe_ctx *ctx, yabpe_mask_stats_t *out);
 
+/* Span-corruption batches (BBPETokenizer.corrupt_spans on the device, yet_another_bpe/tokenizer.py) -------------------
+ * The encoder-decoder denoising objective (T5 / UL2 / SpanBERT style): contiguous spans leave the input, one sentinel
+ * stands for each, and the target lists the sentinels with the ids they stand for.  ids, doc_off, n_docs and words as
+ * yabpe_mask takes them, host or device memory; yabpe_encode_words' results go straight in and are left alone.
+ * The rule, with rnd(seed, stream, i) of yet_another_bpe/synth.py: Kd = rnd(seed, 0x63, first_doc + d) for document d.  For
+ * token j of the document (0-based, counted before any cut) the unit is u = j, with YABPE_SPAN_WHOLE_WORD u = words[k] &
+ * 0x7FFFFFFF.  Per unit r = rnd(Kd, 0x6f, u): the unit opens a span iff (r >> 32) < open_threshold, and the span covers
+ * len(u) = 1 + #{k < max_len - 1 : (r & 0xFFFFFFFF) < len_threshold[k]} units from u on.  Unit v is noise iff some u in
+ * [max(0, v - max_len + 1), v] opens with u + len(u) > v; overlapping and adjacent spans merge.  A token is noise iff its unit
+ * is noise and its words entry has no YABPE_WORD_SPECIAL: specials are never removed, and they split runs.  No draw reads
+ * protection, the cut or the batch.  max_doc_ids (0: none): ids with j >= max_doc_ids appear in neither output.
+ * A run is a maximal stretch of consecutive kept noise ids of one document; the runs of a document are numbered k = 0, 1, ...
+ * With K = n_sentinels - (1 with YABPE_SPAN_FINAL_SENTINEL), the runs k >= K are not corrupted: their ids stay in the input and
+ * nothing of them goes to the target.  Per document, inputs: the kept ids in order, every run k < K replaced by
+ * sentinels[k]; targets: for every run k < K, sentinels[k] and then the run's ids; with YABPE_SPAN_FINAL_SENTINEL, then
+ * sentinels[min(n_runs, K)] if the document keeps at least one id.  An empty document gives two empty sequences.
+ * Results (device memory owned by the library, in buffers of their own: a later encode, mask or layout call leaves them
+ * valid; released by yabpe_span_free, the next yabpe_span_corrupt or yabpe_destroy): *out_dev_in, u32[*out_n_in], with
+ * *out_dev_in_off, u64[n_docs + 1], and the same for the targets -- what the layout calls take as ids and doc_off.
+ * YABPE_E_INVALID: open_threshold or a len_threshold above 2^32, len_threshold increasing, max_len outside 1 ..
+ * YABPE_SPAN_MAX_LEN, n_sentinels == 0 (== 1 with the final sentinel) or sentinels NULL, an unknown flag,
+ * YABPE_SPAN_WHOLE_WORD without words, a doc_off that does not ascend from 0 inside the ids.  YABPE_E_CAPACITY: more than
+ * 2^36 ids in one call.  Every error is found before a buffer is allocated. */
+#define YABPE_SPAN_MAX_LEN 32
+#define YABPE_SPAN_WHOLE_WORD 0x1u       /* the unit of the draws is the piece (words), not the token */
+#define YABPE_SPAN_FINAL_SENTINEL 0x2u   /* the targets of a document end with one more sentinel */
+typedef struct yabpe_span_t {
+    uint64_t seed, first_doc;
+    uint64_t open_threshold;                          /* To, <= 2^32 */
+    uint64_t len_threshold[YABPE_SPAN_MAX_LEN - 1];   /* C[0 .. max_len - 2], <= 2^32, non-increasing; the rest is not read */
+    uint32_t max_len;                                 /* Lmax, 1 .. YABPE_SPAN_MAX_LEN */
+    uint32_t n_sentinels;
+    const uint32_t *sentinels;                        /* n_sentinels ids, host memory */
+    uint64_t max_doc_ids;                             /* 0: no cut */
+    uint32_t flags;                                   /* YABPE_SPAN_* */
+} yabpe_span_t;
+int yabpe_span_corrupt(yabpe_ctx *ctx, const uint32_t *ids, uint64_t n_ids, const uint64_t *doc_off, uint32_t n_docs,
+                       const uint32_t *words, const yabpe_span_t *span, uint32_t **out_dev_in, uint64_t **out_dev_in_off,
+                       uint64_t *out_n_in, uint32_t **out_dev_tgt, uint64_t **out_dev_tgt_off, uint64_t *out_n_tgt);
+int yabpe_span_free(yabpe_ctx *ctx);
+/* What the last yabpe_span_corrupt saw and drew, and its device time. */
+typedef struct yabpe_span_stats_t {
+    uint64_t n_ids, n_docs;
+    uint64_t n_protected;      /* ids of special occurrences (never noise) */
+    uint64_t n_noise;          /* kept ids that are noise, those of runs past the cap included */
+    uint64_t n_runs;           /* runs, those past the cap included */
+    uint64_t n_runs_over;      /* runs past the sentinel cap (left in the inputs) */
+    uint64_t n_cut;            /* ids at or past max_doc_ids */
+    uint64_t n_in, n_tgt;      /* ids of the inputs / the targets, sentinels included */
+    double flags_ms;           /* the draws: a byte per id */
+    double index_ms;           /* run numbers, the sentinel cap, slots per id */
+    double place_ms;           /* the two position scans and the document offsets */
+    double write_ms;           /* the output pass */
+    double kernel_ms;          /* the four together */
+    double total_ms;           /* first to last event (counter reset, read-backs and allocation included) */
+} yabpe_span_stats_t;
+int yabpe_span_stats(yabpe_ctx *ctx, yabpe_span_stats_t *out);
+
 /* Multi-GPU (one process per GPU; words are sharded by the caller) -----------------
  * Every rank holds its shard of the words and a replica of the pair table.  After each apply pass the ranks
  * exchange their aggregated (pair, delta) records with ONE all-gather on the compute stream and every rank adds all

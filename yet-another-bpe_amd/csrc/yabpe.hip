@@ -32,6 +32,7 @@
 #include "yabpe_layout_kernels.h"
 #include "yabpe_fit_kernels.h"
 #include "yabpe_mask_kernels.h"
+#include "yabpe_span_kernels.h"
 #include "yabpe_replay_kernels.h"
 #include "yabpe_pool_kernels.h"
 #include "yabpe_norm_kernels.h"
@@ -225,6 +226,11 @@ struct yabpe_ctx {
     uint32_t *mask_ids = nullptr, *mask_labels = nullptr;
     yabpe_mask_stats_t mask_stats{};
     hipEvent_t mask_ev[4] = {};
+    // span-corruption batches (yabpe_span_corrupt): the results of the last call
+    uint32_t *span_in = nullptr, *span_tgt = nullptr;
+    unsigned long long *span_in_off = nullptr, *span_tgt_off = nullptr;
+    yabpe_span_stats_t span_stats{};
+    hipEvent_t span_ev[6] = {};
     // resumed load (yabpe_load_words_resumed)
     yabpe_resume_stats_t resume_stats{};
     // persistent word pool (yabpe_pool_add / yabpe_pool_get): arena, off / count / hash, slots (pool_logic.h)
@@ -1906,6 +1912,9 @@ void yabpe_destroy(yabpe_ctx *c) {
         if (e) (void)hipEventDestroy(e);
     yabpe_mask_free(c);
     for (auto &e : c->mask_ev)
+        if (e) (void)hipEventDestroy(e);
+    yabpe_span_free(c);
+    for (auto &e : c->span_ev)
         if (e) (void)hipEventDestroy(e);
     yabpe_pool_clear(c);
     for (auto &e : c->wpool_ev)
@@ -4733,6 +4742,176 @@ int yabpe_mask(yabpe_ctx *c, const uint32_t *ids, uint64_t n_ids, const uint64_t
 int yabpe_mask_stats(yabpe_ctx *c, yabpe_mask_stats_t *out) {
     if (!c || !out) return YABPE_E_INVALID;
     *out = c->mask_stats;
+    return YABPE_OK;
+}
+
+// ---------------------------------------------------------------------------------------------- span-corruption batches
+int yabpe_span_free(yabpe_ctx *c) {
+    if (!c) return YABPE_E_INVALID;
+    dfree(c->span_in);
+    dfree(c->span_tgt);
+    dfree(c->span_in_off);
+    dfree(c->span_tgt_off);
+    c->span_in = c->span_tgt = nullptr;
+    c->span_in_off = c->span_tgt_off = nullptr;
+    return YABPE_OK;
+}
+
+// BBPETokenizer.corrupt_spans on the device (yabpe_span_kernels.h; the rule: span_logic.h).  span_ev[0..5] bracket the call's
+// device work: [1..2] the flags pass, [2..3] run numbers and slots, [3..4] positions and offsets, [4..5] the write.  The outputs
+// are allocated after [4], once the totals of the scans are on the host, so [4..5] holds that read-back and the allocation too,
+// as [2..4] hold the synchronisations of exclusive_scan.  A call that the checks refuse has freed nothing.
+int yabpe_span_corrupt(yabpe_ctx *c, const uint32_t *ids, uint64_t n_ids, const uint64_t *doc_off, uint32_t n_docs, const uint32_t *words,
+                       const yabpe_span_t *span, uint32_t **out_dev_in, uint64_t **out_dev_in_off, uint64_t *out_n_in, uint32_t **out_dev_tgt,
+                       uint64_t **out_dev_tgt_off, uint64_t *out_n_tgt) {
+    if (!c || !out_dev_in || !out_dev_in_off || !out_n_in || !out_dev_tgt || !out_dev_tgt_off || !out_n_tgt) return YABPE_E_INVALID;
+    HIPCHK(c, hipSetDevice(c->device));
+    *out_dev_in = *out_dev_tgt = nullptr;
+    *out_dev_in_off = *out_dev_tgt_off = nullptr;
+    *out_n_in = *out_n_tgt = 0;
+    if (!span) return fail(c, YABPE_E_INVALID, "span is NULL");
+    static_assert(YABPE_SPAN_MAX_LEN == SPAN_MAX_LEN, "the header's and the rule's largest span length");
+    unsigned long long h_len[SPAN_MAX_LEN - 1] = {0};
+    for (uint32_t k = 0; k + 1 < SPAN_MAX_LEN; ++k) h_len[k] = span->len_threshold[k];
+    if (!span_rule_valid(span->open_threshold, h_len, span->max_len))
+        return fail(c, YABPE_E_INVALID, "open_threshold %llu, max_len %u: thresholds at most 2^32, len_threshold non-increasing, max_len in 1 .. %u",
+                    (unsigned long long)span->open_threshold, span->max_len, SPAN_MAX_LEN);
+    if (span->flags & ~(YABPE_SPAN_WHOLE_WORD | YABPE_SPAN_FINAL_SENTINEL)) return fail(c, YABPE_E_INVALID, "unknown span flags 0x%x", span->flags);
+    const bool whole_word = (span->flags & YABPE_SPAN_WHOLE_WORD) != 0, final_sentinel = (span->flags & YABPE_SPAN_FINAL_SENTINEL) != 0;
+    if (span->n_sentinels < (final_sentinel ? 2u : 1u) || !span->sentinels)
+        return fail(c, YABPE_E_INVALID, "%u sentinels: at least %u", span->sentinels ? span->n_sentinels : 0u, final_sentinel ? 2u : 1u);
+    if (whole_word && !words) return fail(c, YABPE_E_INVALID, "YABPE_SPAN_WHOLE_WORD needs the words array");
+    if (n_ids && !ids) return fail(c, YABPE_E_INVALID, "ids is NULL");
+    if (n_ids > LAY_MAX_SLOTS) return fail(c, YABPE_E_CAPACITY, "%llu ids: at most 2^36 in one call", (unsigned long long)n_ids);
+    if (!doc_off && n_docs > 1) return fail(c, YABPE_E_INVALID, "doc_off is NULL with %u documents", n_docs);
+    // the document starts on the host (validated: the kernels index the table with what they find in it) and on the device
+    const bool docs_dev = doc_off && is_device_ptr(doc_off);
+    if (!doc_off) n_docs = 1;
+    std::vector<uint64_t> h_docs(n_docs, 0);
+    if (doc_off && n_docs) {
+        if (docs_dev) HIPCHK(c, hipMemcpy(h_docs.data(), doc_off, (size_t)n_docs * 8, hipMemcpyDeviceToHost));
+        else memcpy(h_docs.data(), doc_off, (size_t)n_docs * 8);
+    }
+    TRY(check_starts(c, h_docs.data(), n_docs, n_ids, "ids"));
+    yabpe_span_free(c);
+    c->span_stats = yabpe_span_stats_t{};
+    c->span_stats.n_ids = n_ids;
+    c->span_stats.n_docs = n_docs;
+    for (auto &e : c->span_ev)
+        if (!e) HIPCHK(c, hipEventCreate(&e));
+    hipStream_t s = c->stream;
+    Scratch S(c->device, c->rank);
+    constexpr uint32_t N_COUNTERS = MASK_SHARDS * MASK_SHARD_STRIDE;
+    SpanParams P{};
+    const unsigned long long *d_len = nullptr;
+    P.n_ids = n_ids;
+    P.n_docs = n_docs;
+    TRY(to_device(c, S, ids, n_ids * 4, 4, &P.ids));
+    TRY(to_device(c, S, docs_dev ? (const unsigned long long *)doc_off : (const unsigned long long *)h_docs.data(), (uint64_t)n_docs * 8, 8, &P.doc_off));
+    if (words && n_ids) TRY(to_device(c, S, words, n_ids * 4, 4, &P.words));
+    TRY(to_device(c, S, (const unsigned long long *)h_len, sizeof(h_len), 8, &d_len));
+    TRY(to_device(c, S, span->sentinels, (uint64_t)span->n_sentinels * 4, 4, &P.sentinels));
+    P.seed = span->seed;
+    P.first_doc = span->first_doc;
+    P.rule = SpanRule{span->open_threshold, d_len, span->max_len};
+    P.max_doc_ids = span->max_doc_ids;
+    P.K = span->n_sentinels - (final_sentinel ? 1u : 0u);
+    P.whole_word = whole_word ? 1u : 0u;
+    P.final_sentinel = final_sentinel ? 1u : 0u;
+    HIPCHK(c, S.get(&P.flags, n_ids));
+    HIPCHK(c, S.get(&P.start, n_ids));
+    HIPCHK(c, S.get(&P.c_in, n_ids));
+    HIPCHK(c, S.get(&P.c_tgt, n_ids));
+    HIPCHK(c, S.get(&P.run, n_ids + 1));
+    HIPCHK(c, S.get(&P.in_pos, n_ids + 1));
+    HIPCHK(c, S.get(&P.tgt_pos, n_ids + 1));
+    HIPCHK(c, S.get(&P.counters, N_COUNTERS));
+    TRY(dmalloc(c, &c->span_in_off, (uint64_t)n_docs + 1));
+    TRY(dmalloc(c, &c->span_tgt_off, (uint64_t)n_docs + 1));
+    P.in_off = c->span_in_off;
+    P.tgt_off = c->span_tgt_off;
+    const dim3 grid(cdiv64(n_ids, SPAN_BLOCK)), block(SPAN_BLOCK);
+    // the call fails: nothing of it is left in the context (the stream is drained first: Scratch hands its buffers back)
+    auto hip_fail = [&](const char *what, hipError_t e) {
+        (void)hipStreamSynchronize(s);
+        yabpe_span_free(c);
+        return fail(c, YABPE_E_HIP, "%s failed: %s", what, hipGetErrorString(e));
+    };
+    hipError_t e = hipSuccess;
+    unsigned long long h_tot[3] = {0, 0, 0};  // ids in the inputs, in the targets; runs
+    HIPCHK(c, hipEventRecord(c->span_ev[0], s));
+    if ((e = hipMemsetAsync(P.counters, 0, N_COUNTERS * 8, s)) != hipSuccess) return hip_fail("the counter reset", e);
+    (void)hipEventRecord(c->span_ev[1], s);
+    if (n_ids) {
+        hipLaunchKernelGGL(k_span_flags, grid, block, 0, s, P);
+        if ((e = hipGetLastError()) != hipSuccess) return hip_fail("k_span_flags", e);
+    }
+    (void)hipEventRecord(c->span_ev[2], s);
+    if (n_ids) {
+        if (exclusive_scan<uint8_t>(s, P.start, n_ids, P.run, n_ids + 1) != 0) return hip_fail("the scan of the run starts", hipGetLastError());
+        hipLaunchKernelGGL(k_span_place, grid, block, 0, s, P);
+        if ((e = hipGetLastError()) != hipSuccess) return hip_fail("k_span_place", e);
+    }
+    (void)hipEventRecord(c->span_ev[3], s);
+    if (n_ids) {
+        if (exclusive_scan<uint8_t>(s, P.c_in, n_ids, P.in_pos, n_ids + 1) != 0) return hip_fail("the scan of the input slots", hipGetLastError());
+        if (exclusive_scan<uint8_t>(s, P.c_tgt, n_ids, P.tgt_pos, n_ids + 1) != 0) return hip_fail("the scan of the target slots", hipGetLastError());
+        hipLaunchKernelGGL(k_span_offsets, dim3(cdiv64((uint64_t)n_docs + 1, SPAN_BLOCK)), block, 0, s, P);
+        if ((e = hipGetLastError()) != hipSuccess) return hip_fail("k_span_offsets", e);
+        (void)hipMemcpyAsync(&h_tot[0], P.in_pos + n_ids, 8, hipMemcpyDeviceToHost, s);
+        (void)hipMemcpyAsync(&h_tot[1], P.tgt_pos + n_ids, 8, hipMemcpyDeviceToHost, s);
+        (void)hipMemcpyAsync(&h_tot[2], P.run + n_ids, 8, hipMemcpyDeviceToHost, s);
+    } else {
+        (void)hipMemsetAsync(c->span_in_off, 0, ((size_t)n_docs + 1) * 8, s);
+        (void)hipMemsetAsync(c->span_tgt_off, 0, ((size_t)n_docs + 1) * 8, s);
+    }
+    (void)hipEventRecord(c->span_ev[4], s);
+    if ((e = hipStreamSynchronize(s)) != hipSuccess) return hip_fail("the span passes", e);
+    if (h_tot[0] > n_ids || h_tot[1] > 2 * n_ids + n_docs)  // (what the rule can give at most: the write pass stores by these)
+        return hip_fail("the position scans", hipErrorUnknown);
+    if (dmalloc(c, &c->span_in, h_tot[0]) != 0 || dmalloc(c, &c->span_tgt, h_tot[1]) != 0) {
+        yabpe_span_free(c);
+        return YABPE_E_HIP;
+    }
+    P.out_in = c->span_in;
+    P.out_tgt = c->span_tgt;
+    if (n_ids) {
+        hipLaunchKernelGGL(k_span_write, grid, block, 0, s, P);
+        if ((e = hipGetLastError()) != hipSuccess) return hip_fail("k_span_write", e);
+    }
+    (void)hipEventRecord(c->span_ev[5], s);
+    unsigned long long h_all[N_COUNTERS] = {0}, h_cnt[SPAN_COUNTERS] = {0, 0, 0, 0};
+    (void)hipMemcpyAsync(h_all, P.counters, N_COUNTERS * 8, hipMemcpyDeviceToHost, s);
+    if ((e = hipStreamSynchronize(s)) != hipSuccess) return hip_fail("k_span_write", e);
+    for (uint32_t b = 0; b < MASK_SHARDS; ++b)
+        for (uint32_t k = 0; k < SPAN_COUNTERS; ++k) h_cnt[k] += h_all[b * MASK_SHARD_STRIDE + k];
+    float ms[5] = {0, 0, 0, 0, 0};
+    auto &st = c->span_stats;
+    st.total_ms = pass_times(c->span_ev, 5, ms);
+    st.flags_ms = ms[1];
+    st.index_ms = ms[2];
+    st.place_ms = ms[3];
+    st.write_ms = ms[4];
+    st.kernel_ms = (double)ms[1] + ms[2] + ms[3] + ms[4];
+    st.n_protected = h_cnt[SPAN_C_PROTECTED];
+    st.n_noise = h_cnt[SPAN_C_NOISE];
+    st.n_cut = h_cnt[SPAN_C_CUT];
+    st.n_runs_over = h_cnt[SPAN_C_OVER];
+    st.n_runs = h_tot[2];
+    st.n_in = h_tot[0];
+    st.n_tgt = h_tot[1];
+    *out_dev_in = c->span_in;
+    *out_dev_in_off = (uint64_t *)c->span_in_off;
+    *out_n_in = h_tot[0];
+    *out_dev_tgt = c->span_tgt;
+    *out_dev_tgt_off = (uint64_t *)c->span_tgt_off;
+    *out_n_tgt = h_tot[1];
+    return YABPE_OK;
+}
+
+int yabpe_span_stats(yabpe_ctx *c, yabpe_span_stats_t *out) {
+    if (!c || !out) return YABPE_E_INVALID;
+    *out = c->span_stats;
     return YABPE_OK;
 }
 

@@ -85,6 +85,18 @@ class MaskStats(ctypes.Structure):
         (n, c_double) for n in ("mask_ms", "total_ms")]
 
 
+class Span(ctypes.Structure):
+    """yabpe_span_t"""
+    _fields_ = [(n, c_uint64) for n in ("seed", "first_doc", "open_threshold")] + [("len_threshold", c_uint64 * 31), ("max_len", c_uint32),
+                                                                                   ("n_sentinels", c_uint32), ("sentinels", c_void_p),
+                                                                                   ("max_doc_ids", c_uint64), ("flags", c_uint32)]
+
+
+class SpanStats(ctypes.Structure):
+    _fields_ = [(n, c_uint64) for n in ("n_ids", "n_docs", "n_protected", "n_noise", "n_runs", "n_runs_over", "n_cut", "n_in", "n_tgt")] + [
+        (n, c_double) for n in ("flags_ms", "index_ms", "place_ms", "write_ms", "kernel_ms", "total_ms")]
+
+
 class Layout(ctypes.Structure):
     """yabpe_layout_t"""
     _fields_ = [(n, c_uint32) for n in ("row_len", "pad_id", "bos_id", "eos_id", "flags")]
@@ -155,6 +167,7 @@ SYMBOLS = [
     "yabpe_load_words_resumed", "yabpe_resume_stats",
     "yabpe_layout_pad", "yabpe_layout_pack", "yabpe_layout_windows", "yabpe_layout_pairs", "yabpe_layout_fit", "yabpe_layout_free", "yabpe_layout_stats",
     "yabpe_mask", "yabpe_mask_free", "yabpe_mask_stats",
+    "yabpe_span_corrupt", "yabpe_span_free", "yabpe_span_stats",
     "yabpe_pool_add", "yabpe_pool_get", "yabpe_pool_clear", "yabpe_pool_stats",
     "yabpe_normalize", "yabpe_normalize_free", "yabpe_normalize_stats",
     "yabpe_utf8_repair", "yabpe_utf8_repair_free", "yabpe_utf8_repair_stats",
@@ -234,6 +247,10 @@ def lib() -> ctypes.CDLL:
         L.yabpe_mask.argtypes = [c_void_p, c_void_p, c_uint64, c_void_p, c_uint32, c_void_p, POINTER(Mask), POINTER(c_void_p), POINTER(c_void_p)]
         L.yabpe_mask_free.argtypes = [c_void_p]
         L.yabpe_mask_stats.argtypes = [c_void_p, POINTER(MaskStats)]
+        L.yabpe_span_corrupt.argtypes = [c_void_p, c_void_p, c_uint64, c_void_p, c_uint32, c_void_p, POINTER(Span), POINTER(c_void_p), POINTER(c_void_p),
+                                         POINTER(c_uint64), POINTER(c_void_p), POINTER(c_void_p), POINTER(c_uint64)]
+        L.yabpe_span_free.argtypes = [c_void_p]
+        L.yabpe_span_stats.argtypes = [c_void_p, POINTER(SpanStats)]
         L.yabpe_pool_add.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_uint64]
         L.yabpe_pool_get.argtypes = [c_void_p, POINTER(c_void_p), POINTER(c_void_p), POINTER(c_void_p), POINTER(c_uint64), POINTER(c_uint64)]
         L.yabpe_pool_clear.argtypes = [c_void_p]
@@ -263,6 +280,8 @@ LAYOUT_NO_DOC = 0xFFFFFFFF  # `doc` of a packed slot past the end of the stream
 WORD_SPECIAL = 0x80000000  # yabpe_encode_words: bit 31 of a words entry (YABPE_WORD_SPECIAL)
 MASK_WHOLE_WORD = 0x1  # yabpe_mask_t.flags
 MASK_IGNORE = 0xFFFFFF9C  # yabpe_mask_t.ignore: -100 as i32, the label a loss skips
+SPAN_WHOLE_WORD, SPAN_FINAL_SENTINEL = 0x1, 0x2  # yabpe_span_t.flags
+SPAN_MAX_LEN = 32  # YABPE_SPAN_MAX_LEN
 PAIRS_MODES = {"longest_first": 0, "only_first": 1, "only_second": 2, "windows": 3}  # yabpe_pairs_t.mode (YABPE_PAIRS_*)
 
 
@@ -924,6 +943,61 @@ class Context:
     def mask_stats(self) -> dict:
         s = MaskStats()
         self._chk(lib().yabpe_mask_stats(self._h, byref(s)))
+        return _stats_dict(s)
+
+    # -- span-corruption batches (BBPETokenizer.corrupt_spans on the device)
+    def span_corrupt(self, ids, n_ids: int | None = None, doc_starts=None, n_docs: int | None = None, words=None, *, sentinels, seed: int = 0,
+                     first_doc: int = 0, open: int = 0, lens=(), max_len: int | None = None, max_doc_ids: int = 0, whole_word: bool = False,
+                     final_sentinel: bool = False, flags: int = 0):
+        """One span-corruption draw over ragged ids (yabpe_span_corrupt).  ids / doc_starts / words as mask takes them.  open,
+        lens: the thresholds To and C[0 .. max_len - 2] (BBPETokenizer.span_thresholds); max_len None: len(lens) + 1.
+        sentinels: the u32 table.  flags: further YABPE_SPAN_* bits as they are.
+        -> (dev_in_ptr u32[n_in], dev_in_off_ptr u64[n_docs + 1], n_in, dev_tgt_ptr u32[n_tgt], dev_tgt_off_ptr u64[n_docs + 1], n_tgt,
+        n_docs); the buffers live until the next span_corrupt, span_free() or close()."""
+        keep = docs = keep_words = None
+        if isinstance(ids, int):
+            ptr, n = c_void_p(ids), int(n_ids)
+        else:
+            keep = np.ascontiguousarray(ids, dtype=np.uint32)
+            ptr, n = c_void_p(keep.ctypes.data if keep.size else 0), int(keep.size)
+        if isinstance(doc_starts, int):
+            dptr, nd = c_void_p(doc_starts), int(n_docs)
+        else:
+            docs = _starts_arg(doc_starts)
+            dptr, nd = c_void_p(docs.ctypes.data), len(docs)
+        if words is None or isinstance(words, int):
+            wptr = c_void_p(words or 0)
+        else:
+            keep_words = np.ascontiguousarray(words, dtype=np.uint32)
+            if keep_words.size != n:
+                raise ValueError(f"words must hold one entry per id: {keep_words.size} for {n} ids")
+            if not keep_words.size:
+                keep_words = np.zeros(1, np.uint32)  # (no ids: never read, but not NULL -- the words are given)
+            wptr = c_void_p(keep_words.ctypes.data)
+        lens = [int(x) for x in lens]
+        if len(lens) > SPAN_MAX_LEN - 1:
+            raise ValueError(f"at most {SPAN_MAX_LEN - 1} length thresholds, not {len(lens)}")
+        sent = np.ascontiguousarray(sentinels, dtype=np.uint32).ravel()
+        sp = Span(int(seed), int(first_doc), int(open), (c_uint64 * 31)(*lens), len(lens) + 1 if max_len is None else int(max_len), int(sent.size),
+                  c_void_p(sent.ctypes.data if sent.size else 0), int(max_doc_ids),
+                  int(flags) | (SPAN_WHOLE_WORD if whole_word else 0) | (SPAN_FINAL_SENTINEL if final_sentinel else 0))
+        di, dio, dt, dto, ni, nt = c_void_p(), c_void_p(), c_void_p(), c_void_p(), c_uint64(), c_uint64()
+        self._chk(lib().yabpe_span_corrupt(self._h, ptr, n, dptr, nd, wptr, byref(sp), byref(di), byref(dio), byref(ni), byref(dt), byref(dto),
+                                           byref(nt)))
+        return di.value or 0, dio.value or 0, int(ni.value), dt.value or 0, dto.value or 0, int(nt.value), nd
+
+    def span_corrupt_to_host(self, ids, n_ids: int | None = None, doc_starts=None, n_docs: int | None = None, words=None, **kw):
+        """-> (inputs u32[n_in], in_off u64[n_docs + 1], targets u32[n_tgt], tgt_off u64[n_docs + 1]) copied to the host."""
+        di, dio, ni, dt, dto, nt, nd = self.span_corrupt(ids, n_ids, doc_starts, n_docs, words, **kw)
+        rag = lambda p, n: self.d2h(p, 4 * n, np.uint32) if n else np.zeros(0, np.uint32)  # noqa: E731
+        return rag(di, ni), self.d2h(dio, 8 * (nd + 1), np.uint64), rag(dt, nt), self.d2h(dto, 8 * (nd + 1), np.uint64)
+
+    def span_free(self) -> None:
+        self._chk(lib().yabpe_span_free(self._h))
+
+    def span_stats(self) -> dict:
+        s = SpanStats()
+        self._chk(lib().yabpe_span_stats(self._h, byref(s)))
         return _stats_dict(s)
 
     # -- the persistent word pool (corpora larger than device memory: words go in call by call, the merge loop loads the pool)

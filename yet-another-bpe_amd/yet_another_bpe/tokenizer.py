@@ -442,6 +442,168 @@ class BBPETokenizer:
         lab_rows, _ = self._padded_rows(labels, L, added, ign, None if bos is None else ign, None if eos is None else ign, truncation, padding_side)
         return rows, lab_rows, lengths
 
+    # ------------------------------------------------------------------ span-corruption batches (T5 / UL2 / SpanBERT denoising)
+    SPAN_MAX_LEN = 32  # YABPE_SPAN_MAX_LEN
+
+    @staticmethod
+    def span_thresholds(p: float = 0.15, mean_span_length: float = 3.0, max_span_length: int = 10) -> tuple[int, list[int]]:
+        """The integers the span rule runs on, from the user's numbers -> (To, C), len(C) = max_span_length - 1.  With T(x) =
+        min(2^32, int(x * 2^32)): C[k] = T((1 - 1/mean)^(k + 1)), the power by repeated multiplication: a drawn span is longer
+        than k + 1 units with probability C[k] / 2^32, a geometric length of mean mean_span_length that is clamped at
+        max_span_length.  A unit is noise iff an opener at most max_span_length - 1 units back reaches it, so with an opening
+        probability q its density is 1 - prod_{k < Lmax} (1 - q * S_k), S_0 = 1, S_k = C[k - 1] / 2^32; q is what 64 bisection
+        steps on [0, 1] leave as the upper end for density p, and To = T(q).  Doubles and + - * / only: every machine
+        gets the same integers."""
+        if not isinstance(p, numbers.Real) or not 0.0 <= float(p) <= 1.0:  # (NaN compares false)
+            raise ValueError(f"p must be a real number in [0, 1], not {p!r}")
+        if not isinstance(mean_span_length, numbers.Real) or not 1.0 <= float(mean_span_length) < float("inf"):
+            raise ValueError(f"mean_span_length must be a real number of at least 1, not {mean_span_length!r}")
+        try:
+            Lmax = operator.index(max_span_length)
+        except TypeError:
+            raise ValueError(f"max_span_length must be an integer in [1, {BBPETokenizer.SPAN_MAX_LEN}], not {max_span_length!r}") from None
+        if not 1 <= Lmax <= BBPETokenizer.SPAN_MAX_LEN:
+            raise ValueError(f"max_span_length must be an integer in [1, {BBPETokenizer.SPAN_MAX_LEN}], not {max_span_length!r}")
+        p, a = float(p), 1.0 - 1.0 / float(mean_span_length)
+        C, power = [], 1.0
+        for _ in range(Lmax - 1):
+            power = power * a
+            C.append(min(1 << 32, int(power * 4294967296.0)))
+        S = [1.0] + [c / 4294967296.0 for c in C]
+        lo, hi = 0.0, 1.0
+        for _ in range(64):
+            mid = (lo + hi) / 2.0
+            clear = 1.0
+            for s in S:
+                clear = clear * (1.0 - mid * s)
+            if 1.0 - clear < p:
+                lo = mid
+            else:
+                hi = mid
+        return min(1 << 32, int(hi * 4294967296.0)), C
+
+    def _sentinel_ids(self, sentinels) -> list[int]:
+        """ids, or special-token strings that have ids -> ids in [0, 2^32)"""
+        if sentinels is None or isinstance(sentinels, (str, bytes)):
+            raise ValueError("sentinels must be a sequence of ids or of special-token strings")
+        out = []
+        for s in sentinels:
+            if isinstance(s, str):
+                tid = self._vocab.get(s.encode("utf-8")) if s in self._special_set else None
+                if tid is None:
+                    raise ValueError(f"sentinel {s!r} is not a special token with an id")
+                s = tid
+            out.append(self._layout_ids(s, None, None)[0])
+        return out
+
+    def _span_args(self, sentinels, p, mean_span_length, max_span_length, seed, whole_word, final_sentinel, max_tokens, first_doc, have_words: bool):
+        """-> (sentinel ids, To, C, seed, first_doc, max_doc_ids), validated"""
+        To, C = self.span_thresholds(p, mean_span_length, max_span_length)
+        sent = self._sentinel_ids(sentinels)
+        if len(sent) < (2 if final_sentinel else 1):
+            raise ValueError(f"{len(sent)} sentinels: at least {2 if final_sentinel else 1} (one for a run" + (", one to end the targets)" if final_sentinel else ")"))
+        seed, first_doc = self._u64(seed, "seed"), self._u64(first_doc, "first_doc")
+        cut = 0 if max_tokens is None else self._row_length(max_tokens, "max_tokens", 1)
+        if cut >= 1 << 64:
+            raise ValueError(f"max_tokens must be below 2^64, not {max_tokens!r}")
+        if whole_word and not have_words:
+            raise ValueError("whole_word=True needs words_batch: the piece index of every id (encode_with_words)")
+        return sent, To, C, seed, first_doc, cut
+
+    @staticmethod
+    def _span_noise_units(kd: int, To: int, C: list[int]):
+        """-> noise(v) of the document with key kd, by the rule's definition: opens(u) and len(u) per unit, cached"""
+        Lmax = len(C) + 1
+
+        @lru_cache(maxsize=None)
+        def reach(u: int) -> int:  # one past the last unit u's span covers; u itself if u does not open
+            r = rnd_int(kd, 0x6f, u)
+            if (r >> 32) >= To:
+                return u
+            x = r & 0xFFFFFFFF
+            return u + 1 + sum(1 for k in range(Lmax - 1) if x < C[k])
+
+        def noise(v: int) -> bool:
+            return any(reach(u) > v for u in range(max(0, v - Lmax + 1), v + 1))
+
+        return noise
+
+    def corrupt_spans(self, ids_batch, words_batch=None, special_batch=None, *, sentinels, p: float = 0.15, mean_span_length: float = 3.0,
+                      max_span_length: int = 10, seed: int = 0, whole_word: bool = False, final_sentinel: bool = True,
+                      max_tokens: int | None = None, first_doc: int = 0) -> tuple[list[list[int]], list[list[int]]]:
+        """One span-corruption draw of encoder-decoder denoising (T5 / UL2 / SpanBERT) -> (inputs, targets), one ragged
+        sequence each per document: spans leave the input, one sentinel stands for each, and the target lists the sentinels
+        with the ids they stand for -- "A <s0> B <s1> C" and "<s0> x y <s1> z <s2>".  The result depends on (ids, words,
+        special, the arguments) alone.  (To, C) = span_thresholds(p, mean_span_length, max_span_length), Lmax =
+        max_span_length; with rnd of synth.py, document d has the key Kd = rnd(seed, 0x63, first_doc + d).  For token j of the
+        document (0-based, counted before the cut) the unit is u = j, with whole_word u = words[j].  Per unit r = rnd(Kd, 0x6f,
+        u): the unit opens a span iff (r >> 32) < To, of len(u) = 1 + #{k < Lmax - 1 : (r & 0xFFFFFFFF) < C[k]} units.  Unit v
+        is noise iff some u in [max(0, v - Lmax + 1), v] opens with u + len(u) > v.  A token is noise iff its unit is noise and
+        its `special` is false: specials are never removed, and they split runs.  No draw reads protection, the cut or the
+        batch.  max_tokens (None: no cut): tokens j >= max_tokens appear in neither output; a run the cut ends is shorter.
+        A run is a maximal stretch of consecutive kept noise tokens, numbered k = 0, 1, ... per document.  `sentinels`: ids,
+        or special-token strings that have ids; K = len(sentinels) - (1 if final_sentinel).  inputs: the kept tokens, every run k
+        < K replaced by sentinels[k]; targets: per run k < K, sentinels[k] and the run's ids; with final_sentinel then
+        sentinels[min(n_runs, K)], if the document keeps a token at all.  An empty document gives two empty sequences.
+        Two approximations, on purpose: overlapping and adjacent spans merge, so mean_span_length is the mean of the drawn
+        lengths before the max_span_length clamp, not of the merged runs, which are longer (p = 0.15, mean 3, Lmax 10: drawn 2.94,
+        runs 3.25); and runs k >= K are not corrupted -- their ids stay in the input and nothing goes to the target -- so with few
+        sentinels the density falls below p.  p is the density of noise units, hit to about 0.001."""
+        sent, To, C, seed, first_doc, cut = self._span_args(sentinels, p, mean_span_length, max_span_length, seed, whole_word, final_sentinel,
+                                                             max_tokens, first_doc, words_batch is not None)
+        K = len(sent) - (1 if final_sentinel else 0)
+        inputs, targets = [], []
+        for d, ids in enumerate(ids_batch):
+            noise = self._span_noise_units(rnd_int(seed, 0x63, first_doc + d), To, C)
+            words = words_batch[d] if whole_word else None
+            special = special_batch[d] if special_batch is not None else None
+            row, tgt, n_runs, in_run = [], [], 0, False
+            n_kept = min(len(ids), cut) if cut else len(ids)
+            for j in range(n_kept):
+                tid = int(ids[j])
+                if (special is None or not special[j]) and noise(int(words[j]) if whole_word else j):
+                    if not in_run:
+                        in_run, n_runs = True, n_runs + 1
+                        if n_runs <= K:
+                            row.append(sent[n_runs - 1])
+                            tgt.append(sent[n_runs - 1])
+                    (tgt if n_runs <= K else row).append(tid)
+                else:
+                    in_run = False
+                    row.append(tid)
+            if final_sentinel and n_kept:
+                tgt.append(sent[min(n_runs, K)])
+            inputs.append(row)
+            targets.append(tgt)
+        return inputs, targets
+
+    def encode_batch_span_corrupted(self, texts: Sequence[str], max_length: int | None = None, max_target_length: int | None = None, *,
+                                    sentinels, p: float = 0.15, mean_span_length: float = 3.0, max_span_length: int = 10, seed: int = 0,
+                                    whole_word: bool = False, final_sentinel: bool = True, max_tokens: int | None = None, first_doc: int = 0,
+                                    pad_id: int | None = None, bos_id: int | None = None, eos_id: int | None = None,
+                                    truncation: str = "right", padding_side: str = "right"):
+        """Encoder-decoder denoising rows in one call -> (rows, labels, lengths, label_lengths): encode_batch_with_words, then
+        corrupt_spans over the documents with their words and specials (max_tokens cuts the documents; the draws do not
+        depend on it or on the row lengths), then the inputs laid out as encode_batch_padded lays them out in rows of
+        max_length (None: the longest), and the targets the same way in rows of max_target_length with -100 in BOS, EOS and
+        pad slots."""
+        L, pad, bos, eos, added = self._padded_args(max_length, pad_id, bos_id, eos_id, truncation, padding_side)
+        LT = None if max_target_length is None else self._row_length(max_target_length, "max_target_length", added)
+        kw = {"sentinels": sentinels, "p": p, "mean_span_length": mean_span_length, "max_span_length": max_span_length, "seed": seed,
+              "whole_word": whole_word, "final_sentinel": final_sentinel, "max_tokens": max_tokens, "first_doc": first_doc}
+        self._span_args(have_words=True, **kw)  # (refused before any work)
+        docs = self.encode_batch_with_words(texts)
+        inputs, targets = self.corrupt_spans([d[0] for d in docs], [d[1] for d in docs], [d[2] for d in docs], **kw)
+        if L is None:
+            L = max((len(ids) + added for ids in inputs), default=0)
+        if LT is None:
+            LT = max((len(ids) + added for ids in targets), default=0)
+        ign = self.IGNORE_LABEL
+        rows, lengths = self._padded_rows(inputs, L, added, pad, bos, eos, truncation, padding_side)
+        lab_rows, lab_lengths = self._padded_rows(targets, LT, added, ign, None if bos is None else ign, None if eos is None else ign, truncation,
+                                                  padding_side)
+        return rows, lab_rows, lengths, lab_lengths
+
     # ------------------------------------------------------------------ fixed-shape batches
     def _layout_ids(self, pad_id, bos_id, eos_id) -> tuple[int, int | None, int | None, int]:
         """-> (pad id, bos id or None, eos id or None, n_added); every id given must be an integer in [0, 2^32)"""
@@ -943,6 +1105,73 @@ class BBPETokenizer:
         labels, _lengths = ctx.layout_pad_to_host(ml, ni, dd, n_docs, row_len=rows.shape[1], pad_id=ign, bos_id=None if bos is None else ign,
                                                   eos_id=None if eos is None else ign, **cut)
         return rows, labels.view(np.int32), lengths
+
+    @staticmethod
+    def _span_native_args(sent, To, C, seed, first_doc, cut, whole_word, final_sentinel) -> dict:
+        return {"sentinels": np.asarray(sent, dtype=np.uint32), "seed": seed, "first_doc": first_doc, "open": To, "lens": C, "max_doc_ids": cut,
+                "whole_word": whole_word, "final_sentinel": final_sentinel}
+
+    def corrupt_spans_array(self, ids, doc_off, words=None, special=None, *, sentinels, p: float = 0.15, mean_span_length: float = 3.0,
+                            max_span_length: int = 10, seed: int = 0, whole_word: bool = False, final_sentinel: bool = True,
+                            max_tokens: int | None = None, first_doc: int = 0) -> tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray]:
+        """corrupt_spans on the GPU (yabpe_span_corrupt), bit for bit: ids, doc_off, words and special as
+        encode_array_with_words returns them (words / special None: as corrupt_spans without that batch)
+        -> (in_ids np.uint32[n_in], in_off np.uint64[n_docs + 1], tgt_ids np.uint32[n_tgt], tgt_off np.uint64[n_docs + 1]):
+        document d's inputs are in_ids[in_off[d]:in_off[d + 1]], its targets tgt_ids[tgt_off[d]:tgt_off[d + 1]]."""
+        sent, To, C, seed, first_doc, cut = self._span_args(sentinels, p, mean_span_length, max_span_length, seed, whole_word, final_sentinel,
+                                                             max_tokens, first_doc, words is not None)
+        ids = np.ascontiguousarray(ids, dtype=np.uint32)
+        off = np.asarray(doc_off, dtype=np.int64)
+        if off.ndim != 1 or len(off) < 2 or off[0] != 0 or off[-1] != len(ids) or np.any(np.diff(off) < 0):
+            raise ValueError("doc_off must be n_docs + 1 ascending offsets from 0 to len(ids)")
+        packed = None
+        if words is not None or special is not None:
+            packed = np.zeros(len(ids), np.uint32) if words is None else np.array(words, dtype=np.uint32)
+            if len(packed) != len(ids) or (special is not None and len(special) != len(ids)):
+                raise ValueError("words and special must hold one entry per id")
+            if np.any(packed >> 31):
+                raise ValueError("a word index must be below 2^31")
+            if special is not None:
+                packed |= np.asarray(special, dtype=bool).astype(np.uint32) << 31
+        return self._device().span_corrupt_to_host(ids, None, off[:-1].astype(np.uint64), None, packed,
+                                                   **self._span_native_args(sent, To, C, seed, first_doc, cut, whole_word, final_sentinel))
+
+    def encode_array_span_corrupted(self, texts, max_length: int | None = None, max_target_length: int | None = None, *, sentinels,
+                                    p: float = 0.15, mean_span_length: float = 3.0, max_span_length: int = 10, seed: int = 0,
+                                    whole_word: bool = False, final_sentinel: bool = True, max_tokens: int | None = None, first_doc: int = 0,
+                                    pad_id: int | None = None, bos_id: int | None = None, eos_id: int | None = None,
+                                    truncation: str = "right", padding_side: str = "right"):
+        """encode_batch_span_corrupted(texts, ...), computed on the GPU: yabpe_encode_words, then yabpe_span_corrupt on its
+        device results, then yabpe_layout_pad over the inputs and, once those rows are copied out, over the targets with the
+        ignore value as pad, BOS and EOS id (the ragged arrays never visit the host).  `texts` as encode_array takes them.
+        -> (rows np.uint32[n_docs, L], labels np.int32[n_docs, LT], lengths np.uint32[n_docs], label_lengths np.uint32[n_docs])."""
+        L, pad, bos, eos, added = self._padded_args(max_length, pad_id, bos_id, eos_id, truncation, padding_side)
+        LT = None if max_target_length is None else self._row_length(max_target_length, "max_target_length", added)
+        sent, To, C, seed, first_doc, cut = self._span_args(sentinels, p, mean_span_length, max_span_length, seed, whole_word, final_sentinel,
+                                                             max_tokens, first_doc, True)
+        inp = self._device_input(texts)
+        n_docs = 0 if inp is None else len(inp[1])
+
+        def empty(width):
+            return np.zeros((n_docs, width or 0), np.uint32), np.zeros(n_docs, np.uint32)
+
+        if inp is None:
+            return empty(L)[0], empty(LT)[0].view(np.int32), empty(L)[1], empty(LT)[1]
+        from . import _native
+
+        ctx = self._device()
+        text, n_bytes, starts = self._device_text(ctx, inp)
+        di, dd, dw, ni = ctx.encode_words(text, n_bytes, doc_starts=starts)
+        si, sio, n_in, st, sto, n_tgt, _nd = ctx.span_corrupt(di, ni, dd, n_docs, dw, **self._span_native_args(sent, To, C, seed, first_doc, cut,
+                                                                                                            whole_word, final_sentinel))
+        cut_kw = {"trunc_left": truncation == "left", "pad_left": padding_side == "left"}
+        ign = _native.MASK_IGNORE
+        # (rows of no slots -- asked for, or only empty sequences and neither BOS nor EOS -- need no layout call)
+        rows, lengths = empty(L) if L == 0 else ctx.layout_pad_to_host(si, n_in, sio, n_docs, row_len=L or 0, pad_id=pad, bos_id=bos, eos_id=eos, **cut_kw)
+        labels, label_lengths = empty(LT) if LT == 0 else ctx.layout_pad_to_host(st, n_tgt, sto, n_docs, row_len=LT or 0, pad_id=ign,
+                                                                                 bos_id=None if bos is None else ign,
+                                                                                 eos_id=None if eos is None else ign, **cut_kw)
+        return rows, labels.view(np.int32), lengths, label_lengths
 
     def _device_encode_for_layout(self, ctx, inp, dropout=0.0, seed=0, offsets=None):
         """-> (ids pointer, document starts pointer, n_ids, spans): the device results the layout passes read -- yabpe_encode's,
