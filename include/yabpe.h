@@ -806,6 +806,77 @@ typedef struct yabpe_span_stats_t {
 } yabpe_span_stats_t;
 int yabpe_span_stats(yabpe_ctx *ctx, yabpe_span_stats_t *out);
 
+/* Fill-in-the-middle batches (BBPETokenizer.fim_tokens / fim_cuts on the device, yet_another_bpe/tokenizer.py) ---------
+ * The objective of decoder-only code models (Bavarian et al., 2022): a document is cut at two random places into prefix,
+ * middle and suffix and written as "pre P suf S mid M [eot]" (PSM) or "pre suf S mid P M [eot]" (SPM, the variant with
+ * prefix and middle adjacent).  The rule, with rnd(seed, stream, i) of yet_another_bpe/synth.py: Kd = rnd(seed, 0x66,
+ * first_doc + d) for document d; r = rnd(Kd, 0x61, 0): the document is transformed iff (r >> 32) < fim_threshold, and then SPM
+ * iff (r & 0xFFFFFFFF) < spm_threshold, else PSM; mode = 0 (left alone), 1 (PSM), 2 (SPM).  With n units in the document x =
+ * rnd(Kd, 0x62, 0) % (n + 1), y = rnd(Kd, 0x62, 1) % (n + 1), a = min(x, y), b = max(x, y): prefix = units [0, a), middle = [a,
+ * b), suffix = [b, n); a document left alone has a = b = n.  No draw reads the batch, the row length or another document.
+ * Units are ids (yabpe_fim without YABPE_FIM_PIECES) or code points of the text (yabpe_fim_cuts).
+ * The cut to max_len (0: none): with X = 3 + (1 with YABPE_FIM_EOT) and C = max_len - X, the excess max(0, p + m + s - C) of a
+ * transformed document leaves from the end of the suffix, then from the start of the prefix, then from the end of the middle;
+ * the sentinels always survive.  A document left alone keeps its first max_len ids.  Labels: the id of every slot; with
+ * YABPE_FIM_LOSS_MIDDLE `ignore` everywhere but on the middle's ids and the eot of a transformed document (every slot of a
+ * document left alone keeps its label).
+ *
+ * yabpe_fim_cuts makes the character-level cuts: text (host or device memory) with n_docs document starts as yabpe_encode
+ * takes them; per document n = its bytes that are no continuation bytes, the draws above, and the byte of its a-th and b-th
+ * code point.  *out_dev_piece_off: u64[3 * n_docs], the absolute byte starts of (document, middle, suffix) -- ascending, so
+ * yabpe_encode takes them (copied to the host) as the starts of 3 * n_docs documents; *out_dev_cuts: u64[3 * n_docs], (mode,
+ * a, b) in characters.  UTF-8 is not validated here: the encode behind it does.  Only seed, first_doc, the two thresholds and
+ * flags of *fim are read.
+ *
+ * yabpe_fim rearranges ragged ids.  ids / doc_off as yabpe_mask takes them, host or device memory.  Without
+ * YABPE_FIM_PIECES: n_docs documents, mode and cuts drawn on token indices, cuts must be NULL.  With YABPE_FIM_PIECES:
+ * n_docs is a multiple of 3, documents 3d, 3d + 1, 3d + 2 are prefix, middle and suffix of output document d (their lengths
+ * in ids are p, m, s), and cuts is what yabpe_fim_cuts returned (host or device memory; only the mode is read, a mode
+ * other than 1 and 2 is 0; first_doc + d then numbers nothing: no draw is made).  A document left alone is the three pieces
+ * back to back.  Results: *out_dev_ids and *out_dev_labels, u32[*out_n_out] each; *out_dev_off, u64[n_out_docs + 1] with
+ * n_out_docs = n_docs (n_docs / 3 with pieces) -- what the layout calls take as ids and doc_off; *out_dev_info, 4 u32 per
+ * output document: (mode, p, m, s) after the cut (of a document left alone at token level: (0, kept ids, 0, 0)).
+ *
+ * All results are device memory owned by the library, in buffers of their own: a later encode, mask, span or layout call
+ * leaves them valid.  Those of yabpe_fim_cuts live until the next yabpe_fim_cuts, those of yabpe_fim until the next
+ * yabpe_fim; yabpe_fim_free and yabpe_destroy release both.
+ * YABPE_E_INVALID: a threshold above 2^32, 0 < max_len <= X, an unknown flag, n_docs % 3 != 0 or cuts NULL with
+ * YABPE_FIM_PIECES, cuts given without it, a doc_off that does not ascend from 0 inside the ids / the text.
+ * YABPE_E_CAPACITY: a document of more than 2^32 - 1 ids, more than 2^36 output slots (judged by n_ids + X * n_out_docs, what
+ * the rule can give at most).  Every error is found before a buffer is allocated. */
+#define YABPE_FIM_EOT 0x1u           /* a transformed document ends with eot_id */
+#define YABPE_FIM_LOSS_MIDDLE 0x2u   /* only the middle and the eot of a transformed document carry labels */
+#define YABPE_FIM_PIECES 0x4u        /* the documents are the separately encoded pieces of yabpe_fim_cuts, three per document */
+typedef struct yabpe_fim_t {
+    uint64_t seed, first_doc;
+    uint64_t fim_threshold;          /* Tf, <= 2^32 */
+    uint64_t spm_threshold;          /* Ts, <= 2^32 */
+    uint32_t pre_id, suf_id, mid_id, eot_id;
+    uint32_t ignore;                 /* the label of a slot the loss skips */
+    uint64_t max_len;                /* 0: no cut; else above X */
+    uint32_t flags;                  /* YABPE_FIM_* */
+} yabpe_fim_t;
+int yabpe_fim_cuts(yabpe_ctx *ctx, const uint8_t *text, uint64_t n_bytes, const uint64_t *doc_off, uint32_t n_docs, const yabpe_fim_t *fim,
+                   uint64_t **out_dev_piece_off, uint64_t **out_dev_cuts);
+int yabpe_fim(yabpe_ctx *ctx, const uint32_t *ids, uint64_t n_ids, const uint64_t *doc_off, uint32_t n_docs, const uint64_t *cuts,
+              const yabpe_fim_t *fim, uint32_t **out_dev_ids, uint32_t **out_dev_labels, uint64_t **out_dev_off, uint32_t **out_dev_info,
+              uint64_t *out_n_out);
+int yabpe_fim_free(yabpe_ctx *ctx);
+/* What the last yabpe_fim saw and drew, and its device time; cuts_ms is that of the last yabpe_fim_cuts (which also sets
+ * n_docs and total_ms, and clears the rest). */
+typedef struct yabpe_fim_stats_t {
+    uint64_t n_docs;             /* documents that went out */
+    uint64_t n_psm, n_spm;       /* transformed documents of either order */
+    uint64_t n_truncated_docs;   /* documents that lost ids to max_len */
+    uint64_t n_ids_dropped;      /* the ids they lost */
+    uint64_t n_out;              /* output slots, sentinels included */
+    double cuts_ms;              /* yabpe_fim_cuts: lead-byte table, draws and selects */
+    double plan_ms;              /* the per-document plan and the scan of the lengths */
+    double write_ms;             /* the output pass (with the read-back of the total and the allocation in front of it) */
+    double total_ms;             /* first to last event of the last call */
+} yabpe_fim_stats_t;
+int yabpe_fim_stats(yabpe_ctx *ctx, yabpe_fim_stats_t *out);
+
 /* Multi-GPU (one process per GPU; words are sharded by the caller) -----------------
  * Every rank holds its shard of the words and a replica of the pair table.  After each apply pass the ranks
  * exchange their aggregated (pair, delta) records with ONE all-gather on the compute stream and every rank adds all

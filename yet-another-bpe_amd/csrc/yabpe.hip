@@ -33,6 +33,7 @@
 #include "yabpe_fit_kernels.h"
 #include "yabpe_mask_kernels.h"
 #include "yabpe_span_kernels.h"
+#include "yabpe_fim_kernels.h"
 #include "yabpe_replay_kernels.h"
 #include "yabpe_pool_kernels.h"
 #include "yabpe_norm_kernels.h"
@@ -231,6 +232,10 @@ struct yabpe_ctx {
     unsigned long long *span_in_off = nullptr, *span_tgt_off = nullptr;
     yabpe_span_stats_t span_stats{};
     hipEvent_t span_ev[6] = {};
+    // fill-in-the-middle batches: the results of the last yabpe_fim_cuts ([0..1]) and of the last yabpe_fim ([2..5])
+    void *fim_buf[6] = {};
+    yabpe_fim_stats_t fim_stats{};
+    hipEvent_t fim_ev[4] = {};
     // resumed load (yabpe_load_words_resumed)
     yabpe_resume_stats_t resume_stats{};
     // persistent word pool (yabpe_pool_add / yabpe_pool_get): arena, off / count / hash, slots (pool_logic.h)
@@ -1915,6 +1920,9 @@ void yabpe_destroy(yabpe_ctx *c) {
         if (e) (void)hipEventDestroy(e);
     yabpe_span_free(c);
     for (auto &e : c->span_ev)
+        if (e) (void)hipEventDestroy(e);
+    yabpe_fim_free(c);
+    for (auto &e : c->fim_ev)
         if (e) (void)hipEventDestroy(e);
     yabpe_pool_clear(c);
     for (auto &e : c->wpool_ev)
@@ -4912,6 +4920,234 @@ int yabpe_span_corrupt(yabpe_ctx *c, const uint32_t *ids, uint64_t n_ids, const 
 int yabpe_span_stats(yabpe_ctx *c, yabpe_span_stats_t *out) {
     if (!c || !out) return YABPE_E_INVALID;
     *out = c->span_stats;
+    return YABPE_OK;
+}
+
+// ---------------------------------------------------------------------------------------------- fill-in-the-middle batches
+namespace {
+enum FimBuf { FB_PIECE_OFF = 0, FB_CUTS = 1, FB_IDS = 2, FB_LABELS = 3, FB_OFF = 4, FB_INFO = 5 };
+
+void fim_free_bufs(yabpe_ctx *c, int first, int last) {
+    for (int k = first; k <= last; ++k) {
+        dfree(c->fim_buf[k]);
+        c->fim_buf[k] = nullptr;
+    }
+}
+
+// the checks both calls share: the rule's own, then the document starts -> *h_docs (n_docs entries; {0} without doc_off)
+int fim_check(yabpe_ctx *c, const yabpe_fim_t *fim, const uint64_t *doc_off, uint32_t *n_docs, uint64_t limit, const char *what,
+              std::vector<uint64_t> *h_docs) {
+    if (!fim) return fail(c, YABPE_E_INVALID, "fim is NULL");
+    static_assert(YABPE_FIM_EOT == FIM_EOT && YABPE_FIM_LOSS_MIDDLE == FIM_LOSS_MIDDLE && YABPE_FIM_PIECES == FIM_PIECES, "the header's and the rule's flags");
+    if (!fim_rule_valid(fim->fim_threshold, fim->spm_threshold, fim->max_len, fim->flags))
+        return fail(c, YABPE_E_INVALID, "fim_threshold %llu, spm_threshold %llu, max_len %llu, flags 0x%x: thresholds at most 2^32, max_len 0 or above %llu, flags within 0x%x",
+                    (unsigned long long)fim->fim_threshold, (unsigned long long)fim->spm_threshold, (unsigned long long)fim->max_len, fim->flags,
+                    fim_extra(fim->flags & FIM_FLAGS), FIM_FLAGS);
+    if (!doc_off && *n_docs > 1) return fail(c, YABPE_E_INVALID, "doc_off is NULL with %u documents", *n_docs);
+    if (!doc_off) *n_docs = 1;
+    h_docs->assign(*n_docs, 0);
+    if (doc_off && *n_docs) {
+        if (is_device_ptr(doc_off)) HIPCHK(c, hipMemcpy(h_docs->data(), doc_off, (size_t)*n_docs * 8, hipMemcpyDeviceToHost));
+        else memcpy(h_docs->data(), doc_off, (size_t)*n_docs * 8);
+    }
+    return check_starts(c, h_docs->data(), *n_docs, limit, what);
+}
+}  // namespace
+
+int yabpe_fim_free(yabpe_ctx *c) {
+    if (!c) return YABPE_E_INVALID;
+    fim_free_bufs(c, FB_PIECE_OFF, FB_INFO);
+    return YABPE_OK;
+}
+
+// BBPETokenizer.fim_cuts on the device (k_enc_lead_count, one scan, k_fim_cuts; the rule: fim_logic.h).  fim_ev[0..1] bracket
+// the device work.  A call that the checks refuse has freed nothing.
+int yabpe_fim_cuts(yabpe_ctx *c, const uint8_t *text, uint64_t n_bytes, const uint64_t *doc_off, uint32_t n_docs, const yabpe_fim_t *fim,
+                   uint64_t **out_dev_piece_off, uint64_t **out_dev_cuts) {
+    if (!c || !out_dev_piece_off || !out_dev_cuts) return YABPE_E_INVALID;
+    HIPCHK(c, hipSetDevice(c->device));
+    *out_dev_piece_off = *out_dev_cuts = nullptr;
+    if (n_bytes && !text) return fail(c, YABPE_E_INVALID, "text is NULL");
+    std::vector<uint64_t> h_docs;
+    TRY(fim_check(c, fim, doc_off, &n_docs, n_bytes, "text", &h_docs));
+    fim_free_bufs(c, FB_PIECE_OFF, FB_CUTS);
+    c->fim_stats = yabpe_fim_stats_t{};
+    c->fim_stats.n_docs = n_docs;
+    for (auto &e : c->fim_ev)
+        if (!e) HIPCHK(c, hipEventCreate(&e));
+    hipStream_t s = c->stream;
+    Scratch S(c->device, c->rank);
+    FimCutParams P{};
+    P.n_bytes = n_bytes;
+    P.n_docs = n_docs;
+    TRY(to_device(c, S, text, n_bytes, 16, &P.text));  // (enc_lead reads the text in aligned 16-byte chunks)
+    TRY(to_device(c, S, (const unsigned long long *)h_docs.data(), (uint64_t)n_docs * 8, 8, &P.doc_off));
+    const unsigned long long n_gran = (n_bytes + ENC_GRANULE - 1) / ENC_GRANULE;
+    uint8_t *lead_cnt = nullptr;
+    unsigned long long *table = nullptr, *piece_off = nullptr, *cuts = nullptr;
+    HIPCHK(c, S.get(&lead_cnt, n_gran));
+    HIPCHK(c, S.get(&table, n_gran + 1));
+    TRY(dmalloc(c, &piece_off, 3ull * n_docs));
+    c->fim_buf[FB_PIECE_OFF] = piece_off;
+    TRY(dmalloc(c, &cuts, 3ull * n_docs));
+    c->fim_buf[FB_CUTS] = cuts;
+    P.table = table;
+    P.seed = fim->seed;
+    P.first_doc = fim->first_doc;
+    P.fim = fim->fim_threshold;
+    P.spm = fim->spm_threshold;
+    P.piece_off = piece_off;
+    P.cuts = cuts;
+    auto hip_fail = [&](const char *what, hipError_t e) {
+        (void)hipStreamSynchronize(s);
+        fim_free_bufs(c, FB_PIECE_OFF, FB_CUTS);
+        return fail(c, YABPE_E_HIP, "%s failed: %s", what, hipGetErrorString(e));
+    };
+    hipError_t e = hipSuccess;
+    HIPCHK(c, hipEventRecord(c->fim_ev[0], s));
+    if (n_gran) {
+        hipLaunchKernelGGL(k_enc_lead_count, dim3((uint32_t)((n_gran * 4 + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, s, P.text, (unsigned long long)n_bytes, lead_cnt);
+        if ((e = hipGetLastError()) != hipSuccess) return hip_fail("k_enc_lead_count", e);
+        if (exclusive_scan<uint8_t>(s, lead_cnt, n_gran, table, n_gran + 1) != 0) return hip_fail("the scan of the lead-byte counts", hipGetLastError());
+    } else if ((e = hipMemsetAsync(table, 0, 8, s)) != hipSuccess) {
+        return hip_fail("the table reset", e);
+    }
+    hipLaunchKernelGGL(k_fim_cuts, dim3(cdiv64(n_docs, FIM_BLOCK)), dim3(FIM_BLOCK), 0, s, P);
+    if ((e = hipGetLastError()) != hipSuccess) return hip_fail("k_fim_cuts", e);
+    (void)hipEventRecord(c->fim_ev[1], s);
+    if ((e = hipStreamSynchronize(s)) != hipSuccess) return hip_fail("the cut passes", e);
+    float ms[1] = {0};
+    c->fim_stats.total_ms = pass_times(c->fim_ev, 1, ms);
+    c->fim_stats.cuts_ms = ms[0];
+    *out_dev_piece_off = (uint64_t *)piece_off;
+    *out_dev_cuts = (uint64_t *)cuts;
+    return YABPE_OK;
+}
+
+// BBPETokenizer.fim_tokens on the device (yabpe_fim_kernels.h; the rule: fim_logic.h).  fim_ev[0..3] bracket the call's device
+// work: [1..2] the plan and the scan of the lengths, [2..3] the write.  The outputs are allocated after [2], once the total is
+// on the host, so [2..3] holds that read-back and the allocation too.  A call that the checks refuse has freed nothing.
+int yabpe_fim(yabpe_ctx *c, const uint32_t *ids, uint64_t n_ids, const uint64_t *doc_off, uint32_t n_docs, const uint64_t *cuts,
+              const yabpe_fim_t *fim, uint32_t **out_dev_ids, uint32_t **out_dev_labels, uint64_t **out_dev_off, uint32_t **out_dev_info,
+              uint64_t *out_n_out) {
+    if (!c || !out_dev_ids || !out_dev_labels || !out_dev_off || !out_dev_info || !out_n_out) return YABPE_E_INVALID;
+    HIPCHK(c, hipSetDevice(c->device));
+    *out_dev_ids = *out_dev_labels = *out_dev_info = nullptr;
+    *out_dev_off = nullptr;
+    *out_n_out = 0;
+    if (n_ids && !ids) return fail(c, YABPE_E_INVALID, "ids is NULL");
+    const bool docs_dev = doc_off && is_device_ptr(doc_off);
+    std::vector<uint64_t> h_docs;
+    TRY(fim_check(c, fim, doc_off, &n_docs, n_ids, "ids", &h_docs));
+    const bool pieces = (fim->flags & YABPE_FIM_PIECES) != 0;
+    if (pieces && n_docs % 3 != 0) return fail(c, YABPE_E_INVALID, "%u documents with YABPE_FIM_PIECES: a multiple of 3 (prefix, middle, suffix)", n_docs);
+    if (pieces && !cuts) return fail(c, YABPE_E_INVALID, "YABPE_FIM_PIECES needs the cuts of yabpe_fim_cuts");
+    if (!pieces && cuts) return fail(c, YABPE_E_INVALID, "cuts are given without YABPE_FIM_PIECES");
+    const uint32_t stride = pieces ? 3u : 1u, n_out_docs = n_docs / stride;
+    for (uint32_t d = 0; d < n_out_docs; ++d) {
+        const uint64_t last = (uint64_t)(d + 1) * stride < n_docs ? h_docs[(size_t)(d + 1) * stride] : n_ids;
+        if (last - h_docs[(size_t)d * stride] > FIM_MAX_DOC)
+            return fail(c, YABPE_E_CAPACITY, "document %u has %llu ids: at most 2^32 - 1", d, (unsigned long long)(last - h_docs[(size_t)d * stride]));
+    }
+    if (n_ids > LAY_MAX_SLOTS || n_ids + fim_extra(fim->flags) * n_out_docs > LAY_MAX_SLOTS)
+        return fail(c, YABPE_E_CAPACITY, "%llu ids in %u documents: at most 2^36 output slots in one call", (unsigned long long)n_ids, n_out_docs);
+    fim_free_bufs(c, FB_IDS, FB_INFO);
+    const double cuts_ms = c->fim_stats.cuts_ms;
+    c->fim_stats = yabpe_fim_stats_t{};
+    c->fim_stats.cuts_ms = cuts_ms;
+    c->fim_stats.n_docs = n_out_docs;
+    for (auto &e : c->fim_ev)
+        if (!e) HIPCHK(c, hipEventCreate(&e));
+    hipStream_t s = c->stream;
+    Scratch S(c->device, c->rank);
+    constexpr uint32_t N_COUNTERS = MASK_SHARDS * MASK_SHARD_STRIDE;
+    FimParams P{};
+    P.n_ids = n_ids;
+    P.n_in = n_docs;
+    P.n_docs = n_out_docs;
+    TRY(to_device(c, S, ids, n_ids * 4, 4, &P.ids));
+    TRY(to_device(c, S, docs_dev ? (const unsigned long long *)doc_off : (const unsigned long long *)h_docs.data(), (uint64_t)n_docs * 8, 8, &P.doc_off));
+    if (pieces) TRY(to_device(c, S, (const unsigned long long *)cuts, (uint64_t)n_docs * 8, 8, &P.cuts));
+    P.seed = fim->seed;
+    P.first_doc = fim->first_doc;
+    P.rule = FimRule{fim->fim_threshold, fim->spm_threshold, fim->pre_id, fim->suf_id, fim->mid_id, fim->eot_id, fim->ignore, fim->max_len, fim->flags};
+    HIPCHK(c, S.get(&P.aux, n_out_docs));
+    HIPCHK(c, S.get(&P.len, n_out_docs));
+    HIPCHK(c, S.get(&P.counters, N_COUNTERS));
+    unsigned long long *out_off = nullptr;
+    uint4 *info = nullptr;
+    TRY(dmalloc(c, &out_off, (uint64_t)n_out_docs + 1));
+    c->fim_buf[FB_OFF] = out_off;
+    TRY(dmalloc(c, &info, (uint64_t)n_out_docs));
+    c->fim_buf[FB_INFO] = info;
+    P.out_off = out_off;
+    P.info = info;
+    // the call fails: nothing of it is left in the context (the stream is drained first: Scratch hands its buffers back)
+    auto hip_fail = [&](const char *what, hipError_t e) {
+        (void)hipStreamSynchronize(s);
+        fim_free_bufs(c, FB_IDS, FB_INFO);
+        return fail(c, YABPE_E_HIP, "%s failed: %s", what, hipGetErrorString(e));
+    };
+    hipError_t e = hipSuccess;
+    unsigned long long h_out = 0;
+    HIPCHK(c, hipEventRecord(c->fim_ev[0], s));
+    if ((e = hipMemsetAsync(P.counters, 0, N_COUNTERS * 8, s)) != hipSuccess) return hip_fail("the counter reset", e);
+    (void)hipEventRecord(c->fim_ev[1], s);
+    if (n_out_docs) {
+        hipLaunchKernelGGL(k_fim_plan, dim3(cdiv64(n_out_docs, FIM_BLOCK)), dim3(FIM_BLOCK), 0, s, P);
+        if ((e = hipGetLastError()) != hipSuccess) return hip_fail("k_fim_plan", e);
+        if (exclusive_scan<unsigned long long>(s, P.len, n_out_docs, out_off, (unsigned long long)n_out_docs + 1) != 0)
+            return hip_fail("the scan of the sequence lengths", hipGetLastError());
+        (void)hipMemcpyAsync(&h_out, out_off + n_out_docs, 8, hipMemcpyDeviceToHost, s);
+    } else {
+        (void)hipMemsetAsync(out_off, 0, 8, s);
+    }
+    (void)hipEventRecord(c->fim_ev[2], s);
+    if ((e = hipStreamSynchronize(s)) != hipSuccess) return hip_fail("the plan pass", e);
+    if (h_out > n_ids + fim_extra(fim->flags) * n_out_docs)  // (what the rule can give at most: the write pass stores by this)
+        return hip_fail("the scan of the sequence lengths", hipErrorUnknown);
+    uint32_t *o_ids = nullptr, *o_lab = nullptr;
+    if (dmalloc(c, &o_ids, h_out) != 0 || dmalloc(c, &o_lab, h_out) != 0) {
+        dfree(o_ids);
+        fim_free_bufs(c, FB_IDS, FB_INFO);
+        return YABPE_E_HIP;
+    }
+    c->fim_buf[FB_IDS] = o_ids;
+    c->fim_buf[FB_LABELS] = o_lab;
+    P.out_ids = o_ids;
+    P.out_labels = o_lab;
+    P.n_out = h_out;
+    if (h_out) {
+        hipLaunchKernelGGL(k_fim_write, dim3(cdiv64(h_out, FIM_BLOCK)), dim3(FIM_BLOCK), 0, s, P);
+        if ((e = hipGetLastError()) != hipSuccess) return hip_fail("k_fim_write", e);
+    }
+    (void)hipEventRecord(c->fim_ev[3], s);
+    unsigned long long h_all[N_COUNTERS] = {0}, h_cnt[FIM_COUNTERS] = {0, 0, 0, 0};
+    (void)hipMemcpyAsync(h_all, P.counters, N_COUNTERS * 8, hipMemcpyDeviceToHost, s);
+    if ((e = hipStreamSynchronize(s)) != hipSuccess) return hip_fail("k_fim_write", e);
+    for (uint32_t b = 0; b < MASK_SHARDS; ++b)
+        for (uint32_t k = 0; k < FIM_COUNTERS; ++k) h_cnt[k] += h_all[b * MASK_SHARD_STRIDE + k];
+    float ms[3] = {0, 0, 0};
+    auto &st = c->fim_stats;
+    st.total_ms = pass_times(c->fim_ev, 3, ms);
+    st.plan_ms = ms[1];
+    st.write_ms = ms[2];
+    st.n_psm = h_cnt[FIM_C_PSM];
+    st.n_spm = h_cnt[FIM_C_SPM];
+    st.n_truncated_docs = h_cnt[FIM_C_TRUNCATED];
+    st.n_ids_dropped = h_cnt[FIM_C_DROPPED];
+    st.n_out = h_out;
+    *out_dev_ids = o_ids;
+    *out_dev_labels = o_lab;
+    *out_dev_off = (uint64_t *)out_off;
+    *out_dev_info = (uint32_t *)info;
+    *out_n_out = h_out;
+    return YABPE_OK;
+}
+
+int yabpe_fim_stats(yabpe_ctx *c, yabpe_fim_stats_t *out) {
+    if (!c || !out) return YABPE_E_INVALID;
+    *out = c->fim_stats;
     return YABPE_OK;
 }
 

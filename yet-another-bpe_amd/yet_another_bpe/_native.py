@@ -97,6 +97,17 @@ class SpanStats(ctypes.Structure):
         (n, c_double) for n in ("flags_ms", "index_ms", "place_ms", "write_ms", "kernel_ms", "total_ms")]
 
 
+class Fim(ctypes.Structure):
+    """yabpe_fim_t"""
+    _fields_ = [(n, c_uint64) for n in ("seed", "first_doc", "fim_threshold", "spm_threshold")] + [
+        (n, c_uint32) for n in ("pre_id", "suf_id", "mid_id", "eot_id", "ignore")] + [("max_len", c_uint64), ("flags", c_uint32)]
+
+
+class FimStats(ctypes.Structure):
+    _fields_ = [(n, c_uint64) for n in ("n_docs", "n_psm", "n_spm", "n_truncated_docs", "n_ids_dropped", "n_out")] + [
+        (n, c_double) for n in ("cuts_ms", "plan_ms", "write_ms", "total_ms")]
+
+
 class Layout(ctypes.Structure):
     """yabpe_layout_t"""
     _fields_ = [(n, c_uint32) for n in ("row_len", "pad_id", "bos_id", "eos_id", "flags")]
@@ -168,6 +179,7 @@ SYMBOLS = [
     "yabpe_layout_pad", "yabpe_layout_pack", "yabpe_layout_windows", "yabpe_layout_pairs", "yabpe_layout_fit", "yabpe_layout_free", "yabpe_layout_stats",
     "yabpe_mask", "yabpe_mask_free", "yabpe_mask_stats",
     "yabpe_span_corrupt", "yabpe_span_free", "yabpe_span_stats",
+    "yabpe_fim_cuts", "yabpe_fim", "yabpe_fim_free", "yabpe_fim_stats",
     "yabpe_pool_add", "yabpe_pool_get", "yabpe_pool_clear", "yabpe_pool_stats",
     "yabpe_normalize", "yabpe_normalize_free", "yabpe_normalize_stats",
     "yabpe_utf8_repair", "yabpe_utf8_repair_free", "yabpe_utf8_repair_stats",
@@ -251,6 +263,11 @@ def lib() -> ctypes.CDLL:
                                          POINTER(c_uint64), POINTER(c_void_p), POINTER(c_void_p), POINTER(c_uint64)]
         L.yabpe_span_free.argtypes = [c_void_p]
         L.yabpe_span_stats.argtypes = [c_void_p, POINTER(SpanStats)]
+        L.yabpe_fim_cuts.argtypes = [c_void_p, c_void_p, c_uint64, c_void_p, c_uint32, POINTER(Fim), POINTER(c_void_p), POINTER(c_void_p)]
+        L.yabpe_fim.argtypes = [c_void_p, c_void_p, c_uint64, c_void_p, c_uint32, c_void_p, POINTER(Fim), POINTER(c_void_p), POINTER(c_void_p),
+                                POINTER(c_void_p), POINTER(c_void_p), POINTER(c_uint64)]
+        L.yabpe_fim_free.argtypes = [c_void_p]
+        L.yabpe_fim_stats.argtypes = [c_void_p, POINTER(FimStats)]
         L.yabpe_pool_add.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_uint64]
         L.yabpe_pool_get.argtypes = [c_void_p, POINTER(c_void_p), POINTER(c_void_p), POINTER(c_void_p), POINTER(c_uint64), POINTER(c_uint64)]
         L.yabpe_pool_clear.argtypes = [c_void_p]
@@ -282,6 +299,7 @@ MASK_WHOLE_WORD = 0x1  # yabpe_mask_t.flags
 MASK_IGNORE = 0xFFFFFF9C  # yabpe_mask_t.ignore: -100 as i32, the label a loss skips
 SPAN_WHOLE_WORD, SPAN_FINAL_SENTINEL = 0x1, 0x2  # yabpe_span_t.flags
 SPAN_MAX_LEN = 32  # YABPE_SPAN_MAX_LEN
+FIM_EOT, FIM_LOSS_MIDDLE, FIM_PIECES = 0x1, 0x2, 0x4  # yabpe_fim_t.flags
 PAIRS_MODES = {"longest_first": 0, "only_first": 1, "only_second": 2, "windows": 3}  # yabpe_pairs_t.mode (YABPE_PAIRS_*)
 
 
@@ -998,6 +1016,77 @@ class Context:
     def span_stats(self) -> dict:
         s = SpanStats()
         self._chk(lib().yabpe_span_stats(self._h, byref(s)))
+        return _stats_dict(s)
+
+    # -- fill-in-the-middle batches (BBPETokenizer.fim_tokens / fim_cuts on the device)
+    @staticmethod
+    def _fim_arg(seed=0, first_doc=0, fim=0, spm=0, pre_id=0, suf_id=0, mid_id=0, eot_id=None, ignore=MASK_IGNORE, max_len=0,
+                 loss_middle=False, pieces=False, flags=0) -> Fim:
+        return Fim(int(seed), int(first_doc), int(fim), int(spm), int(pre_id), int(suf_id), int(mid_id), int(eot_id or 0), int(ignore), int(max_len),
+                   int(flags) | (0 if eot_id is None else FIM_EOT) | (FIM_LOSS_MIDDLE if loss_middle else 0) | (FIM_PIECES if pieces else 0))
+
+    def fim_cuts(self, text, n_bytes: int | None = None, doc_starts=None, n_docs: int | None = None, **kw):
+        """The character-level cuts of every document (yabpe_fim_cuts).  text as encode takes it; doc_starts: a u64 table
+        (staged) or a device address with n_docs.  kw: seed, first_doc, fim, spm (the thresholds Tf, Ts), flags.
+        -> (dev_piece_off_ptr u64[3 * n_docs], dev_cuts_ptr u64[3 * n_docs], n_docs); the buffers live until the next
+        fim_cuts, fim_free() or close()."""
+        _keep, ptr, n = _text_arg(text, n_bytes)
+        if isinstance(doc_starts, int):
+            docs, dptr, nd = None, c_void_p(doc_starts), int(n_docs)
+        else:
+            docs = _starts_arg(doc_starts)
+            dptr, nd = c_void_p(docs.ctypes.data), len(docs)
+        f = self._fim_arg(**kw)
+        po, cu = c_void_p(), c_void_p()
+        self._chk(lib().yabpe_fim_cuts(self._h, ptr, n, dptr, nd, byref(f), byref(po), byref(cu)))
+        return po.value or 0, cu.value or 0, nd
+
+    def fim_cuts_to_host(self, text, n_bytes: int | None = None, doc_starts=None, n_docs: int | None = None, **kw):
+        """-> (piece_off u64[n_docs, 3], cuts u64[n_docs, 3]) copied to the host."""
+        po, cu, nd = self.fim_cuts(text, n_bytes, doc_starts, n_docs, **kw)
+        return self.d2h(po, 24 * nd, np.uint64).reshape(nd, 3), self.d2h(cu, 24 * nd, np.uint64).reshape(nd, 3)
+
+    def fim(self, ids, n_ids: int | None = None, doc_starts=None, n_docs: int | None = None, cuts=None, **kw):
+        """One fill-in-the-middle rearrangement of ragged ids (yabpe_fim).  ids / doc_starts as mask takes them (doc_starts 0
+        with n_docs: a NULL table); cuts: None, a u64 array (staged) or a device address -- what fim_cuts returns, with
+        pieces=True.  kw: seed, first_doc, fim, spm, pre_id, suf_id, mid_id, eot_id (None: no eot), ignore, max_len,
+        loss_middle, pieces, flags (further YABPE_FIM_* bits as they are).
+        -> (dev_ids_ptr u32[n_out], dev_labels_ptr u32[n_out], dev_off_ptr u64[n_out_docs + 1], dev_info_ptr u32[n_out_docs, 4],
+        n_out, n_out_docs); the buffers live until the next fim, fim_free() or close()."""
+        keep = docs = keep_cuts = None
+        if isinstance(ids, int):
+            ptr, n = c_void_p(ids), int(n_ids)
+        else:
+            keep = np.ascontiguousarray(ids, dtype=np.uint32)
+            ptr, n = c_void_p(keep.ctypes.data if keep.size else 0), int(keep.size)
+        if isinstance(doc_starts, int):
+            dptr, nd = c_void_p(doc_starts), int(n_docs)
+        else:
+            docs = _starts_arg(doc_starts)
+            dptr, nd = c_void_p(docs.ctypes.data), len(docs)
+        if cuts is None or isinstance(cuts, int):
+            cptr = c_void_p(cuts or 0)
+        else:
+            keep_cuts = np.ascontiguousarray(cuts, dtype=np.uint64).ravel()
+            cptr = c_void_p(keep_cuts.ctypes.data)
+        f = self._fim_arg(**kw)
+        di, dl, do, dn, no = c_void_p(), c_void_p(), c_void_p(), c_void_p(), c_uint64()
+        self._chk(lib().yabpe_fim(self._h, ptr, n, dptr, nd, cptr, byref(f), byref(di), byref(dl), byref(do), byref(dn), byref(no)))
+        return di.value or 0, dl.value or 0, do.value or 0, dn.value or 0, int(no.value), nd // 3 if f.flags & FIM_PIECES else nd
+
+    def fim_to_host(self, ids, n_ids: int | None = None, doc_starts=None, n_docs: int | None = None, cuts=None, **kw):
+        """-> (ids u32[n_out], labels i32[n_out], off u64[n_out_docs + 1], info u32[n_out_docs, 4]) copied to the host."""
+        di, dl, do, dn, no, nd = self.fim(ids, n_ids, doc_starts, n_docs, cuts, **kw)
+        rag = lambda p: self.d2h(p, 4 * no, np.uint32) if no else np.zeros(0, np.uint32)  # noqa: E731
+        info = self.d2h(dn, 16 * nd, np.uint32).reshape(nd, 4) if nd else np.zeros((0, 4), np.uint32)
+        return rag(di), rag(dl).view(np.int32), self.d2h(do, 8 * (nd + 1), np.uint64), info
+
+    def fim_free(self) -> None:
+        self._chk(lib().yabpe_fim_free(self._h))
+
+    def fim_stats(self) -> dict:
+        s = FimStats()
+        self._chk(lib().yabpe_fim_stats(self._h, byref(s)))
         return _stats_dict(s)
 
     # -- the persistent word pool (corpora larger than device memory: words go in call by call, the merge loop loads the pool)

@@ -158,7 +158,10 @@ class BBPETokenizer:
         return normalize_text(lowercase_text(text, self._lowercase), self._normalizer)
 
     def encode(self, text: str) -> list[int]:
-        text = self.normalize(text)
+        return self._encode_normalized(self.normalize(text))
+
+    def _encode_normalized(self, text: str) -> list[int]:
+        """the ids of a text that normalize() has already seen (or a piece cut out of one): specials, pattern, merges"""
         if not text:
             return []
         ids: list[int] = []
@@ -603,6 +606,153 @@ class BBPETokenizer:
         lab_rows, lab_lengths = self._padded_rows(targets, LT, added, ign, None if bos is None else ign, None if eos is None else ign, truncation,
                                                   padding_side)
         return rows, lab_rows, lengths, lab_lengths
+
+    # ------------------------------------------------------------------ fill-in-the-middle batches (decoder-only code models)
+    FIM_LOSSES = ("all", "middle")
+    FIM_LEVELS = ("char", "token")
+
+    def _fim_args(self, pre, suf, mid, eot, fim_rate, spm_rate, seed, first_doc, max_length, loss):
+        """-> (pre id, suf id, mid id, eot id or None, Tf, Ts, seed, first_doc, max_len (0: no cut), loss == "middle"), validated
+        as yabpe_fim validates them"""
+        Tf, Ts = self._dropout_threshold(fim_rate), self._dropout_threshold(spm_rate)
+        if loss not in self.FIM_LOSSES:
+            raise ValueError(f"loss must be 'all' or 'middle', not {loss!r}")
+        for name, v in (("pre", pre), ("suf", suf), ("mid", mid)):
+            if v is None:
+                raise ValueError(f"{name} must be an id or a special-token string")
+        pre, suf, mid = self._sentinel_ids([pre, suf, mid])
+        eot = None if eot is None else self._sentinel_ids([eot])[0]
+        seed, first_doc = self._u64(seed, "seed"), self._u64(first_doc, "first_doc")
+        X = 3 + (eot is not None)
+        max_len = 0
+        if max_length is not None:
+            max_len = self._row_length(max_length, "max_length", 0)
+            if max_len <= X:
+                raise ValueError(f"max_length must be above {X} (the sentinels always survive), not {max_len}: max_len 0 or above {X}")
+            if max_len >= 1 << 64:
+                raise ValueError(f"max_length must be below 2^64, not {max_length!r}")
+        return pre, suf, mid, eot, Tf, Ts, seed, first_doc, max_len, loss == "middle"
+
+    @staticmethod
+    def _fim_draw(seed: int, doc: int, n: int, Tf: int, Ts: int) -> tuple[int, int, int]:
+        """-> (mode, a, b) of document number `doc` (first_doc + d) with n units"""
+        kd = rnd_int(seed, 0x66, doc)
+        r = rnd_int(kd, 0x61, 0)
+        if (r >> 32) >= Tf:
+            return 0, n, n
+        x, y = rnd_int(kd, 0x62, 0) % (n + 1), rnd_int(kd, 0x62, 1) % (n + 1)
+        return (2 if (r & 0xFFFFFFFF) < Ts else 1), min(x, y), max(x, y)
+
+    def _fim_sequence(self, mode: int, P: list[int], M: list[int], S: list[int], pre, suf, mid, eot, max_len: int, loss_middle: bool):
+        """One document from its three pieces -> (sequence, labels, (mode, p, m, s) after the cut)"""
+        ign = self.IGNORE_LABEL
+        if mode == 0:
+            ids = P + M + S
+            if max_len:
+                ids = ids[:max_len]
+            p = min(len(P), len(ids))
+            m = min(len(M), len(ids) - p)
+            return ids, list(ids), (0, p, m, len(ids) - p - m)
+        X = 3 + (eot is not None)
+        if max_len:
+            e = max(0, len(P) + len(M) + len(S) - (max_len - X))
+            t = min(e, len(S))
+            S, e = S[:len(S) - t], e - t
+            t = min(e, len(P))
+            P, e = P[t:], e - t
+            M = M[:len(M) - e]
+        tail = [] if eot is None else [eot]
+        if mode == 1:
+            parts = [([pre], 0), (P, 0), ([suf], 0), (S, 0), ([mid], 0), (M, 1), (tail, 1)]
+        else:
+            parts = [([pre], 0), ([suf], 0), (S, 0), ([mid], 0), (P, 0), (M, 1), (tail, 1)]
+        seq, lab = [], []
+        for ids, in_loss in parts:
+            seq.extend(ids)
+            lab.extend(ids if in_loss or not loss_middle else [ign] * len(ids))
+        return seq, lab, (mode, len(P), len(M), len(S))
+
+    def fim_tokens(self, ids_batch, *, pre, suf, mid, eot=None, fim_rate: float = 0.5, spm_rate: float = 0.5, seed: int = 0, first_doc: int = 0,
+                   max_length: int | None = None, loss: str = "all") -> tuple[list[list[int]], list[list[int]], list[tuple[int, int, int, int]]]:
+        """One fill-in-the-middle draw (Bavarian et al., 2022) at token level -> (sequences, labels, info), one entry each per
+        document.  The result depends on (ids, the arguments) alone.  With rnd of synth.py and T(x) = min(2^32, int(x * 2^32)),
+        Tf = T(fim_rate), Ts = T(spm_rate): document d has the key Kd = rnd(seed, 0x66, first_doc + d); r = rnd(Kd, 0x61, 0); the
+        document is transformed iff (r >> 32) < Tf, and then SPM iff (r & 0xFFFFFFFF) < Ts, else PSM.  With n ids: x = rnd(Kd,
+        0x62, 0) % (n + 1), y = rnd(Kd, 0x62, 1) % (n + 1), a = min(x, y), b = max(x, y); P = ids[:a], M = ids[a:b], S = ids[b:].
+        PSM: pre P suf S mid M [eot]; SPM: pre suf S mid P M [eot] (prefix and middle adjacent); a document left alone: its ids.
+        pre, suf, mid, eot: ids, or special-token strings that have ids; eot None: nothing is appended.
+        max_length (None: no cut; else above X = 3 + (1 with eot)): the excess over max_length - X leaves from the end of S, then
+        from the start of P, then from the end of M; the sentinels always survive.  A document left alone keeps its first
+        max_length ids.  labels: the id of every slot; with loss "middle" -100 everywhere but on M and the eot of a transformed
+        document (a document left alone keeps all its labels).  info[d] = (mode, len(P), len(M), len(S)) after the cut, mode 0
+        (left alone: (0, kept ids, 0, 0)), 1 (PSM) or 2 (SPM)."""
+        pre, suf, mid, eot, Tf, Ts, seed, first_doc, max_len, loss_middle = self._fim_args(pre, suf, mid, eot, fim_rate, spm_rate, seed, first_doc,
+                                                                                           max_length, loss)
+        seqs, labels, info = [], [], []
+        for d, ids in enumerate(ids_batch):
+            ids = [int(t) for t in ids]
+            mode, a, b = self._fim_draw(seed, first_doc + d, len(ids), Tf, Ts)
+            seq, lab, inf = self._fim_sequence(mode, ids[:a], ids[a:b], ids[b:], pre, suf, mid, eot, max_len, loss_middle)
+            seqs.append(seq)
+            labels.append(lab)
+            info.append(inf)
+        return seqs, labels, info
+
+    def fim_cuts(self, texts: Sequence[str], *, fim_rate: float = 0.5, spm_rate: float = 0.5, seed: int = 0,
+                 first_doc: int = 0) -> list[tuple[int, int, int]]:
+        """The character-level cuts of fill-in-the-middle -> (mode, a, b) per document, in code points of t = normalize(text):
+        the draws of fim_tokens with n = len(t); prefix t[:a], middle t[a:b], suffix t[b:]."""
+        Tf, Ts = self._dropout_threshold(fim_rate), self._dropout_threshold(spm_rate)
+        seed, first_doc = self._u64(seed, "seed"), self._u64(first_doc, "first_doc")
+        return [self._fim_draw(seed, first_doc + d, len(self.normalize(t)), Tf, Ts) for d, t in enumerate(texts)]
+
+    def _fim_level(self, level) -> bool:
+        if level not in self.FIM_LEVELS:
+            raise ValueError(f"level must be 'char' or 'token', not {level!r}")
+        return level == "char"
+
+    def _fim_row_args(self, max_length, pad_id, bos_id, eos_id, truncation, padding_side, pre, suf, mid, eot, fim_rate, spm_rate, seed, first_doc, loss):
+        """-> (_padded_args' results, _fim_args' results): the sequences are cut to max_length minus BOS and EOS"""
+        L, pad, bos, eos, added = self._padded_args(max_length, pad_id, bos_id, eos_id, truncation, padding_side)
+        fim = self._fim_args(pre, suf, mid, eot, fim_rate, spm_rate, seed, first_doc, None if L is None else L - added, loss)
+        return (L, pad, bos, eos, added), fim
+
+    def encode_batch_fim(self, texts: Sequence[str], max_length: int | None = None, *, level: str = "char", pre, suf, mid, eot=None,
+                         fim_rate: float = 0.5, spm_rate: float = 0.5, seed: int = 0, first_doc: int = 0, loss: str = "all",
+                         pad_id: int | None = None, bos_id: int | None = None, eos_id: int | None = None, truncation: str = "right",
+                         padding_side: str = "right"):
+        """Fill-in-the-middle rows in one call -> (input_ids, labels, lengths, info).  level "token": fim_tokens over
+        encode_batch(texts).  level "char" (the paper's recommended form: a cut through a word shows the model sub-token
+        boundaries): t = normalize(text), (mode, a, b) = fim_cuts, and the three pieces t[:a], t[a:b], t[b:] are encoded each
+        on its own without normalising again; info then counts the pieces' ids.  A special token that a cut runs through is plain
+        text in both pieces; one that lies inside a piece is a special.  (A normaliser is not applied across a cut either: the
+        pieces are cut out of the normalised text.)  The sequences are cut by the rule of fim_tokens to max_length minus BOS and
+        EOS (None: no cut), so the sentinels survive and `truncation` has nothing left to cut; the rows are laid out as
+        encode_batch_padded lays them out (max_length None: the longest), labels with -100 in BOS, EOS and pad slots and
+        wherever the loss skips."""
+        (L, pad, bos, eos, added), (pre, suf, mid, eot, Tf, Ts, seed, first_doc, max_len, loss_middle) = self._fim_row_args(
+            max_length, pad_id, bos_id, eos_id, truncation, padding_side, pre, suf, mid, eot, fim_rate, spm_rate, seed, first_doc, loss)
+        chars = self._fim_level(level)
+        seqs, labels, info = [], [], []
+        for d, text in enumerate(texts):
+            if chars:
+                t = self.normalize(text)
+                mode, a, b = self._fim_draw(seed, first_doc + d, len(t), Tf, Ts)
+                P, M, S = (self._encode_normalized(x) for x in (t[:a], t[a:b], t[b:]))
+            else:
+                ids = self.encode(text)
+                mode, a, b = self._fim_draw(seed, first_doc + d, len(ids), Tf, Ts)
+                P, M, S = ids[:a], ids[a:b], ids[b:]
+            seq, lab, inf = self._fim_sequence(mode, P, M, S, pre, suf, mid, eot, max_len, loss_middle)
+            seqs.append(seq)
+            labels.append(lab)
+            info.append(inf)
+        if L is None:
+            L = max((len(ids) + added for ids in seqs), default=0)
+        ign = self.IGNORE_LABEL
+        rows, lengths = self._padded_rows(seqs, L, added, pad, bos, eos, truncation, padding_side)
+        lab_rows, _ = self._padded_rows(labels, L, added, ign, None if bos is None else ign, None if eos is None else ign, truncation, padding_side)
+        return rows, lab_rows, lengths, info
 
     # ------------------------------------------------------------------ fixed-shape batches
     def _layout_ids(self, pad_id, bos_id, eos_id) -> tuple[int, int | None, int | None, int]:
@@ -1172,6 +1322,85 @@ class BBPETokenizer:
                                                                                  bos_id=None if bos is None else ign,
                                                                                  eos_id=None if eos is None else ign, **cut_kw)
         return rows, labels.view(np.int32), lengths, label_lengths
+
+    @staticmethod
+    def _fim_native_args(pre, suf, mid, eot, Tf, Ts, seed, first_doc, max_len, loss_middle) -> dict:
+        from . import _native
+
+        return {"seed": seed, "first_doc": first_doc, "fim": Tf, "spm": Ts, "pre_id": pre, "suf_id": suf, "mid_id": mid, "eot_id": eot,
+                "ignore": _native.MASK_IGNORE, "max_len": max_len, "loss_middle": loss_middle}
+
+    def fim_array(self, ids, doc_off, *, pre, suf, mid, eot=None, fim_rate: float = 0.5, spm_rate: float = 0.5, seed: int = 0, first_doc: int = 0,
+                  max_length: int | None = None, loss: str = "all", cuts=None) -> tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray]:
+        """fim_tokens on the GPU (yabpe_fim), bit for bit: ids and doc_off as encode_array returns them
+        -> (seq_ids np.uint32[n_out], labels np.int32[n_out], off np.uint64[n_docs + 1], info np.uint32[n_docs, 4]): document
+        d's sequence is seq_ids[off[d]:off[d + 1]].  cuts (np.uint64[n, 3], what fim_cuts_array returns as cuts): the
+        documents are then the 3 n separately encoded pieces of n documents, three in a row each, and only the modes are read."""
+        args = self._fim_args(pre, suf, mid, eot, fim_rate, spm_rate, seed, first_doc, max_length, loss)
+        ids = np.ascontiguousarray(ids, dtype=np.uint32)
+        off = np.asarray(doc_off, dtype=np.int64)
+        if off.ndim != 1 or len(off) < 2 or off[0] != 0 or off[-1] != len(ids) or np.any(np.diff(off) < 0):
+            raise ValueError("doc_off must be n_docs + 1 ascending offsets from 0 to len(ids)")
+        if cuts is not None:
+            cuts = np.ascontiguousarray(cuts, dtype=np.uint64)
+            if cuts.size != len(off) - 1:
+                raise ValueError(f"cuts must hold (mode, a, b) per document: {cuts.size} values for {len(off) - 1} pieces")
+        return self._device().fim_to_host(ids, None, off[:-1].astype(np.uint64), None, cuts, pieces=cuts is not None, **self._fim_native_args(*args))
+
+    def fim_cuts_array(self, texts, *, fim_rate: float = 0.5, spm_rate: float = 0.5, seed: int = 0, first_doc: int = 0,
+                       errors: str = "strict") -> tuple[np.ndarray, np.ndarray]:
+        """fim_cuts on the GPU (yabpe_fim_cuts behind the text front): `texts` as encode_array takes them
+        -> (cuts np.uint64[n_docs, 3], piece_off np.uint64[n_docs, 3]): (mode, a, b) in code points of normalize(texts[d]), and
+        the byte starts of (document, middle, suffix) in the normalised text that normalize_array returns."""
+        Tf, Ts = self._dropout_threshold(fim_rate), self._dropout_threshold(spm_rate)
+        seed, first_doc = self._u64(seed, "seed"), self._u64(first_doc, "first_doc")
+        inp = self._device_input(texts)
+        if inp is None:
+            check_errors(errors)
+            return np.zeros((0, 3), np.uint64), np.zeros((0, 3), np.uint64)
+        ctx = self._device()
+        text, n_bytes, starts = self._device_text(ctx, inp, errors)
+        piece_off, cuts = ctx.fim_cuts_to_host(text, n_bytes, starts, seed=seed, first_doc=first_doc, fim=Tf, spm=Ts)
+        return cuts, piece_off
+
+    def encode_array_fim(self, texts, max_length: int | None = None, *, level: str = "char", pre, suf, mid, eot=None, fim_rate: float = 0.5,
+                         spm_rate: float = 0.5, seed: int = 0, first_doc: int = 0, loss: str = "all", pad_id: int | None = None,
+                         bos_id: int | None = None, eos_id: int | None = None, truncation: str = "right", padding_side: str = "right"):
+        """encode_batch_fim(texts, ...), computed on the GPU.  level "char": yabpe_fim_cuts on the device text, the 3 n piece
+        starts copied to the host (24 bytes a document: yabpe_encode takes host starts), one yabpe_encode over the 3 n pieces,
+        yabpe_fim with pieces; level "token": yabpe_encode, then yabpe_fim.  Then yabpe_layout_pad over the sequences and, once
+        those rows are copied out, over the labels with the ignore value as pad, BOS and EOS id (the ragged arrays never visit
+        the host).  `texts` as encode_array takes them.
+        -> (rows np.uint32[n_docs, L], labels np.int32[n_docs, L], lengths np.uint32[n_docs], info np.uint32[n_docs, 4])."""
+        (L, pad, bos, eos, _added), args = self._fim_row_args(max_length, pad_id, bos_id, eos_id, truncation, padding_side, pre, suf, mid, eot,
+                                                              fim_rate, spm_rate, seed, first_doc, loss)
+        chars = self._fim_level(level)
+        inp = self._device_input(texts)
+        if inp is None:
+            return np.zeros((0, L or 0), np.uint32), np.zeros((0, L or 0), np.int32), np.zeros(0, np.uint32), np.zeros((0, 4), np.uint32)
+        from . import _native
+
+        ctx = self._device()
+        n_docs = len(inp[1])
+        native = self._fim_native_args(*args)
+        text, n_bytes, starts = self._device_text(ctx, inp)
+        if chars:
+            dpo, dcuts, _nd = ctx.fim_cuts(text, n_bytes, starts, seed=native["seed"], first_doc=native["first_doc"], fim=native["fim"], spm=native["spm"])
+            piece_off = ctx.d2h(dpo, 24 * n_docs, np.uint64)
+            di, dd, ni = ctx.encode(text, n_bytes, doc_starts=piece_off)
+            fi, fl, fo, fn, n_out, _nd = ctx.fim(di, ni, dd, 3 * n_docs, dcuts, pieces=True, **native)
+        else:
+            di, dd, ni = ctx.encode(text, n_bytes, doc_starts=starts)
+            fi, fl, fo, fn, n_out, _nd = ctx.fim(di, ni, dd, n_docs, None, **native)
+        info = ctx.d2h(fn, 16 * n_docs, np.uint32).reshape(n_docs, 4)
+        cut = {"trunc_left": truncation == "left", "pad_left": padding_side == "left"}
+        ign = _native.MASK_IGNORE
+        rows, lengths = ctx.layout_pad_to_host(fi, n_out, fo, n_docs, row_len=L or 0, pad_id=pad, bos_id=bos, eos_id=eos, **cut)
+        if rows.shape[1] == 0:  # (only empty sequences and neither BOS nor EOS)
+            return rows, np.zeros(rows.shape, np.int32), lengths, info
+        labels, _lengths = ctx.layout_pad_to_host(fl, n_out, fo, n_docs, row_len=rows.shape[1], pad_id=ign, bos_id=None if bos is None else ign,
+                                                  eos_id=None if eos is None else ign, **cut)
+        return rows, labels.view(np.int32), lengths, info
 
     def _device_encode_for_layout(self, ctx, inp, dropout=0.0, seed=0, offsets=None):
         """-> (ids pointer, document starts pointer, n_ids, spans): the device results the layout passes read -- yabpe_encode's,
