@@ -877,6 +877,75 @@ typedef struct yabpe_fim_stats_t {
 } yabpe_fim_stats_t;
 int yabpe_fim_stats(yabpe_ctx *ctx, yabpe_fim_stats_t *out);
 
+/* Conversation batches (BBPETokenizer.chat_tokens on the device, yet_another_bpe/tokenizer.py) --------------------------
+ * Supervised fine-tuning on conversations: a conversation is a list of (role, content) turns, written through a chat
+ * template, with the loss on the assistant's turns only and the cut to max_len by whole turns.
+ * Pieces are encoded separately.  The template gives every role r a header H_r = head_ids[head_off[r] .. head_off[r + 1])
+ * and a footer F_r (foot_ids / foot_off alike), a conversation prefix X = prefix_ids[0 .. n_prefix) and, with
+ * YABPE_CHAT_GEN_PROMPT, a generation prompt G = H_gen_role appended after the last turn.  All are id sequences in host
+ * memory, encoded once by the caller.  The content c_t of every turn is a document of its own in ids / doc_off, so no merge
+ * crosses a piece boundary and label boundaries are exact; this is deliberately not "render the string, then tokenise it".
+ *   body_t = H_{r_t} + c_t + F_{r_t}          seq = X + body_0 + ... + body_{T-1} + [G]          (T = 0 gives X + [G])
+ * Labels: `ignore` everywhere, but in a turn whose role is in train_mask the content and footer ids carry their own id.
+ * YABPE_CHAT_LOSS_ALL: every id of every body does.  YABPE_CHAT_LOSS_LAST: only turn T - 1, and only if its role is in
+ * train_mask.  X and G never carry a label.
+ * The cut to max_len (0: none): X and G always survive, B = max_len - n_prefix - |G| ids are left for the bodies.  Without
+ * YABPE_CHAT_DROP_OLDEST the first B ids of the concatenated bodies stay (the cut may fall inside a header, a content or a
+ * footer), and q = k = 0.  With it: q = 1 iff YABPE_CHAT_PIN_FIRST, T > 0 and r_0 is in pin_mask, else 0; L(k) = |body_0 ..
+ * body_{q-1}| + |body_k .. body_{T-1}|; k = the smallest value of [q, max(q, T - 1)] with L(k) <= B, or max(q, T - 1) if there
+ * is none; turns [0, q) and [k, T) stay -- the last turn always -- and what is still longer than B is cut on the right to
+ * B.  No rule reads the batch or another conversation.
+ *
+ * ids / doc_off: the n_turns separately encoded contents as yabpe_mask takes them, host or device memory (yabpe_encode's
+ * results pass straight in; doc_off may be NULL with n_turns = 0).  conv_off: n_convs ascending starts into the turns, the
+ * first one 0; roles: one byte per turn; both host or device memory.  Results: *out_dev_ids and *out_dev_labels,
+ * u32[*out_n_out] each; *out_dev_off, u64[n_convs + 1] -- what the layout calls take as ids and doc_off; *out_dev_info, 4 u32
+ * per conversation: (q, k, ids kept, ids that carry a label) after the cut.  All are device memory owned by the library, in
+ * buffers of their own, valid until the next yabpe_chat, yabpe_chat_free or yabpe_destroy; a refused call leaves the
+ * previous results valid.
+ * YABPE_E_INVALID: n_roles outside 1 .. YABPE_CHAT_MAX_ROLES, a role >= n_roles, unknown flags or both LOSS flags, gen_role
+ * >= n_roles with YABPE_CHAT_GEN_PROMPT, 0 < max_len <= n_prefix + |G|, offsets that do not ascend from 0 (template tables,
+ * doc_off inside the ids, conv_off inside the turns), turns without a conversation.
+ * YABPE_E_CAPACITY: more than 2,048 template ids in all (X, every header, every footer: the write pass keeps them in LDS),
+ * more than 2^36 output slots, a conversation of more than 2^32 - 1 ids.  Every error is found before a result buffer is
+ * allocated. */
+#define YABPE_CHAT_MAX_ROLES 16
+#define YABPE_CHAT_MAX_TEMPLATE_IDS 2048
+#define YABPE_CHAT_LOSS_ALL 0x01u      /* every id of every body carries its label */
+#define YABPE_CHAT_LOSS_LAST 0x02u     /* only the last turn does (not together with LOSS_ALL) */
+#define YABPE_CHAT_DROP_OLDEST 0x04u   /* the cut drops whole turns, oldest first */
+#define YABPE_CHAT_PIN_FIRST 0x08u     /* a first turn whose role is in pin_mask is never dropped (read only with DROP_OLDEST) */
+#define YABPE_CHAT_GEN_PROMPT 0x10u    /* append the header of gen_role */
+typedef struct yabpe_chat_t {
+    uint32_t n_roles;                       /* 1 .. YABPE_CHAT_MAX_ROLES */
+    const uint32_t *head_ids, *head_off;    /* host memory; head_off: n_roles + 1 offsets */
+    const uint32_t *foot_ids, *foot_off;
+    const uint32_t *prefix_ids;
+    uint32_t n_prefix;
+    uint32_t train_mask, pin_mask;          /* bit r: role r */
+    uint32_t gen_role;
+    uint32_t ignore;                        /* the label of a slot the loss skips */
+    uint64_t max_len;                       /* 0: no cut */
+    uint32_t flags;                         /* YABPE_CHAT_* */
+} yabpe_chat_t;
+int yabpe_chat(yabpe_ctx *ctx, const uint32_t *ids, uint64_t n_ids, const uint64_t *doc_off, uint32_t n_turns, const uint64_t *conv_off,
+               uint32_t n_convs, const uint8_t *roles, const yabpe_chat_t *chat, uint32_t **out_dev_ids, uint32_t **out_dev_labels,
+               uint64_t **out_dev_off, uint32_t **out_dev_info, uint64_t *out_n_out);
+int yabpe_chat_free(yabpe_ctx *ctx);
+/* What the last yabpe_chat saw and cut, and its device time. */
+typedef struct yabpe_chat_stats_t {
+    uint64_t n_convs, n_turns;
+    uint64_t n_turns_dropped;     /* whole turns the cut dropped */
+    uint64_t n_ids_cut;           /* ids of the uncut sequences that did not go out */
+    uint64_t n_out;               /* output slots */
+    uint64_t n_labelled;          /* of them with a label */
+    uint64_t n_convs_unlabelled;  /* conversations without any label */
+    double plan_ms;               /* turn lengths, plan, kept lengths and the two scans */
+    double write_ms;              /* the output pass and the tally (with the read-back of the total and the allocation in front) */
+    double total_ms;              /* first to last event of the call */
+} yabpe_chat_stats_t;
+int yabpe_chat_stats(yabpe_ctx *ctx, yabpe_chat_stats_t *out);
+
 /* Multi-GPU (one process per GPU; words are sharded by the caller) -----------------
  * Every rank holds its shard of the words and a replica of the pair table.  After each apply pass the ranks
  * exchange their aggregated (pair, delta) records with ONE all-gather on the compute stream and every rank adds all

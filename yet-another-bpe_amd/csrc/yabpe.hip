@@ -34,6 +34,7 @@
 #include "yabpe_mask_kernels.h"
 #include "yabpe_span_kernels.h"
 #include "yabpe_fim_kernels.h"
+#include "yabpe_chat_kernels.h"
 #include "yabpe_replay_kernels.h"
 #include "yabpe_pool_kernels.h"
 #include "yabpe_norm_kernels.h"
@@ -236,6 +237,10 @@ struct yabpe_ctx {
     void *fim_buf[6] = {};
     yabpe_fim_stats_t fim_stats{};
     hipEvent_t fim_ev[4] = {};
+    // conversation batches: the results of the last yabpe_chat (ids, labels, offsets, info)
+    void *chat_buf[4] = {};
+    yabpe_chat_stats_t chat_stats{};
+    hipEvent_t chat_ev[3] = {};
     // resumed load (yabpe_load_words_resumed)
     yabpe_resume_stats_t resume_stats{};
     // persistent word pool (yabpe_pool_add / yabpe_pool_get): arena, off / count / hash, slots (pool_logic.h)
@@ -1923,6 +1928,9 @@ void yabpe_destroy(yabpe_ctx *c) {
         if (e) (void)hipEventDestroy(e);
     yabpe_fim_free(c);
     for (auto &e : c->fim_ev)
+        if (e) (void)hipEventDestroy(e);
+    yabpe_chat_free(c);
+    for (auto &e : c->chat_ev)
         if (e) (void)hipEventDestroy(e);
     yabpe_pool_clear(c);
     for (auto &e : c->wpool_ev)
@@ -5148,6 +5156,215 @@ int yabpe_fim(yabpe_ctx *c, const uint32_t *ids, uint64_t n_ids, const uint64_t 
 int yabpe_fim_stats(yabpe_ctx *c, yabpe_fim_stats_t *out) {
     if (!c || !out) return YABPE_E_INVALID;
     *out = c->fim_stats;
+    return YABPE_OK;
+}
+
+// ---------------------------------------------------------------------------------------------- conversation batches
+namespace {
+enum ChatBuf { CB_IDS = 0, CB_LABELS = 1, CB_OFF = 2, CB_INFO = 3 };
+
+// a table the caller may hold in host or in device memory -> *h (n entries)
+int chat_to_host(yabpe_ctx *c, const uint64_t *src, uint64_t n, std::vector<uint64_t> *h) {
+    h->assign(n, 0);
+    if (!n) return 0;
+    if (is_device_ptr(src)) HIPCHK(c, hipMemcpy(h->data(), src, n * 8, hipMemcpyDeviceToHost));
+    else memcpy(h->data(), src, n * 8);
+    return 0;
+}
+
+// The rule's own checks and the template -> *tpl, the table the kernels read (CHAT_TPL_HDR starts, then X, headers, footers);
+// *n_gen = |G|.
+int chat_check(yabpe_ctx *c, const yabpe_chat_t *chat, std::vector<uint32_t> *tpl, uint32_t *n_gen) {
+    if (!chat) return fail(c, YABPE_E_INVALID, "chat is NULL");
+    static_assert(YABPE_CHAT_LOSS_ALL == CHAT_LOSS_ALL && YABPE_CHAT_LOSS_LAST == CHAT_LOSS_LAST && YABPE_CHAT_DROP_OLDEST == CHAT_DROP_OLDEST &&
+                      YABPE_CHAT_PIN_FIRST == CHAT_PIN_FIRST && YABPE_CHAT_GEN_PROMPT == CHAT_GEN_PROMPT && YABPE_CHAT_MAX_ROLES == CHAT_MAX_ROLES &&
+                      YABPE_CHAT_MAX_TEMPLATE_IDS == CHAT_MAX_TPL,
+                  "the header's and the rule's constants");
+    const uint32_t nr = chat->n_roles;
+    if (!chat_rule_valid(nr, chat->flags, chat->gen_role, 0, 0, 0))
+        return fail(c, YABPE_E_INVALID, "n_roles %u, flags 0x%x, gen_role %u: 1 to %u roles, flags within 0x%x and not both LOSS flags, gen_role below n_roles",
+                    nr, chat->flags, chat->gen_role, CHAT_MAX_ROLES, CHAT_FLAGS);
+    if (!chat->head_off || !chat->foot_off) return fail(c, YABPE_E_INVALID, "head_off or foot_off is NULL");
+    for (const uint32_t *off : {chat->head_off, chat->foot_off}) {
+        if (off[0] != 0) return fail(c, YABPE_E_INVALID, "template offsets must start at 0");
+        for (uint32_t r = 0; r < nr; ++r)
+            if (off[r + 1] < off[r]) return fail(c, YABPE_E_INVALID, "template offsets must ascend");
+    }
+    const uint64_t nh = chat->head_off[nr], nf = chat->foot_off[nr], nx = chat->n_prefix;
+    if ((nh && !chat->head_ids) || (nf && !chat->foot_ids) || (nx && !chat->prefix_ids)) return fail(c, YABPE_E_INVALID, "template ids are NULL");
+    if (nh + nf + nx > CHAT_MAX_TPL)
+        return fail(c, YABPE_E_CAPACITY, "%llu template ids (prefix, headers, footers): at most %u", (unsigned long long)(nh + nf + nx), CHAT_MAX_TPL);
+    *n_gen = (chat->flags & CHAT_GEN_PROMPT) ? chat->head_off[chat->gen_role + 1] - chat->head_off[chat->gen_role] : 0;
+    if (!chat_rule_valid(nr, chat->flags, chat->gen_role, chat->max_len, nx, *n_gen))
+        return fail(c, YABPE_E_INVALID, "max_len %llu: 0 or above %llu (the prefix and the generation prompt always survive)",
+                    (unsigned long long)chat->max_len, (unsigned long long)(nx + *n_gen));
+    tpl->assign(CHAT_TPL_HDR + nx + nh + nf, 0);
+    for (uint32_t r = 0; r <= CHAT_MAX_ROLES; ++r) {  // (past n_roles: empty)
+        (*tpl)[r] = (uint32_t)(CHAT_TPL_HDR + nx + chat->head_off[r < nr ? r : nr]);
+        (*tpl)[CHAT_MAX_ROLES + 1 + r] = (uint32_t)(CHAT_TPL_HDR + nx + nh + chat->foot_off[r < nr ? r : nr]);
+    }
+    if (nx) memcpy(tpl->data() + CHAT_TPL_HDR, chat->prefix_ids, nx * 4);
+    if (nh) memcpy(tpl->data() + CHAT_TPL_HDR + nx, chat->head_ids, nh * 4);
+    if (nf) memcpy(tpl->data() + CHAT_TPL_HDR + nx + nh, chat->foot_ids, nf * 4);
+    return 0;
+}
+}  // namespace
+
+int yabpe_chat_free(yabpe_ctx *c) {
+    if (!c) return YABPE_E_INVALID;
+    for (auto &p : c->chat_buf) {
+        dfree(p);
+        p = nullptr;
+    }
+    return YABPE_OK;
+}
+
+// BBPETokenizer.chat_tokens on the device (yabpe_chat_kernels.h; the rule: chat_logic.h).  chat_ev[0..2] bracket the call's
+// device work: [0..1] turn lengths, plan, kept lengths and the two scans, [1..2] the write and the tally.  The outputs are
+// allocated after [1], once the status and the total are on the host, so [1..2] holds that read-back and the allocation
+// too.  Until then everything lives in the call's Scratch: a call that is refused -- by the checks here or by the status
+// the plan passes raise -- has freed nothing, and the previous results stay valid.
+int yabpe_chat(yabpe_ctx *c, const uint32_t *ids, uint64_t n_ids, const uint64_t *doc_off, uint32_t n_turns, const uint64_t *conv_off,
+               uint32_t n_convs, const uint8_t *roles, const yabpe_chat_t *chat, uint32_t **out_dev_ids, uint32_t **out_dev_labels,
+               uint64_t **out_dev_off, uint32_t **out_dev_info, uint64_t *out_n_out) {
+    if (!c || !out_dev_ids || !out_dev_labels || !out_dev_off || !out_dev_info || !out_n_out) return YABPE_E_INVALID;
+    HIPCHK(c, hipSetDevice(c->device));
+    *out_dev_ids = *out_dev_labels = *out_dev_info = nullptr;
+    *out_dev_off = nullptr;
+    *out_n_out = 0;
+    std::vector<uint32_t> tpl;
+    uint32_t n_gen = 0;
+    TRY(chat_check(c, chat, &tpl, &n_gen));
+    if (n_ids && !ids) return fail(c, YABPE_E_INVALID, "ids is NULL");
+    if (n_turns && (!doc_off || !roles)) return fail(c, YABPE_E_INVALID, "doc_off or roles is NULL with %u turns", n_turns);
+    if (n_convs && !conv_off) return fail(c, YABPE_E_INVALID, "conv_off is NULL with %u conversations", n_convs);
+    if (n_turns && !n_convs) return fail(c, YABPE_E_INVALID, "%u turns without a conversation", n_turns);
+    if (!n_turns && n_ids) return fail(c, YABPE_E_INVALID, "%llu ids without a turn", (unsigned long long)n_ids);
+    const bool docs_dev = doc_off && is_device_ptr(doc_off);
+    std::vector<uint64_t> h_docs, h_convs;
+    TRY(chat_to_host(c, doc_off, n_turns, &h_docs));
+    if (n_turns) TRY(check_starts(c, h_docs.data(), n_turns, n_ids, "ids"));
+    TRY(chat_to_host(c, conv_off, n_convs, &h_convs));
+    if (n_convs && h_convs[0] != 0) return fail(c, YABPE_E_INVALID, "conv_off must hold n_convs starts, the first one 0");
+    for (uint32_t k = 1; k < n_convs; ++k)
+        if (h_convs[k] < h_convs[k - 1] || h_convs[k] > n_turns) return fail(c, YABPE_E_INVALID, "conversation starts must ascend inside the turns");
+    h_convs.push_back(n_turns);  // (the kernels read n_convs + 1 offsets)
+    const uint64_t n_rec = (uint64_t)n_turns + n_convs, nx = chat->n_prefix;
+    if (n_ids > LAY_MAX_SLOTS)  // (what the template adds is judged below, by the scanned total)
+        return fail(c, YABPE_E_CAPACITY, "%llu ids in %u conversations: at most 2^36 output slots in one call", (unsigned long long)n_ids, n_convs);
+    for (auto &e : c->chat_ev)
+        if (!e) HIPCHK(c, hipEventCreate(&e));
+    hipStream_t s = c->stream;
+    Scratch S(c->device, c->rank);
+    ChatParams P{};
+    P.n_ids = n_ids;
+    P.n_turns = n_turns;
+    P.n_convs = n_convs;
+    P.n_rec = n_rec;
+    P.n_tpl = (uint32_t)tpl.size() - CHAT_TPL_HDR;
+    P.n_x = (uint32_t)nx;
+    P.n_g = n_gen;
+    P.n_roles = chat->n_roles;
+    P.gen_role = (chat->flags & CHAT_GEN_PROMPT) ? chat->gen_role : 0;
+    P.train_mask = chat->train_mask;
+    P.pin_mask = chat->pin_mask;
+    P.ignore = chat->ignore;
+    P.flags = chat->flags;
+    P.B = chat->max_len ? chat->max_len - nx - n_gen : ~0ull;
+    TRY(to_device(c, S, ids, n_ids * 4, 16, &P.ids));  // (the write pass loads 16 bytes where a content run allows)
+    TRY(to_device(c, S, docs_dev ? (const unsigned long long *)doc_off : (const unsigned long long *)h_docs.data(), (uint64_t)n_turns * 8, 8, &P.doc_off));
+    TRY(to_device(c, S, (const unsigned long long *)h_convs.data(), (uint64_t)h_convs.size() * 8, 8, &P.conv_off));
+    TRY(to_device(c, S, roles, n_turns, 1, &P.roles));
+    TRY(to_device(c, S, (const uint32_t *)tpl.data(), (uint64_t)tpl.size() * 4, 4, &P.tpl));
+    unsigned long long *out_off = nullptr;
+    HIPCHK(c, S.get(&P.len, n_rec));
+    HIPCHK(c, S.get(&P.Gs, (uint64_t)n_turns + 1));
+    HIPCHK(c, S.get(&P.O, n_rec + 1));
+    HIPCHK(c, S.get(&P.rec4, n_rec));
+    HIPCHK(c, S.get(&P.rec2, n_rec));
+    HIPCHK(c, S.get(&P.counters, CHAT_COUNTERS + 1));  // (the status word behind the counters)
+    HIPCHK(c, S.get(&P.info, n_convs));
+    HIPCHK(c, S.get(&out_off, (uint64_t)n_convs + 1));
+    P.status = (uint32_t *)(P.counters + CHAT_COUNTERS);
+    P.out_off = out_off;
+    auto hip_fail = [&](const char *what, hipError_t e) {  // (the stream is drained first: Scratch hands its buffers back)
+        (void)hipStreamSynchronize(s);
+        return fail(c, YABPE_E_HIP, "%s failed: %s", what, hipGetErrorString(e));
+    };
+    hipError_t e = hipSuccess;
+    unsigned long long h_out = 0;
+    uint32_t h_status = 0;
+    HIPCHK(c, hipEventRecord(c->chat_ev[0], s));
+    if ((e = hipMemsetAsync(P.counters, 0, (CHAT_COUNTERS + 1) * 8, s)) != hipSuccess) return hip_fail("the counter reset", e);
+    if (n_turns) {
+        hipLaunchKernelGGL(k_chat_turn_len, dim3(cdiv64(n_turns, CHAT_BLOCK)), dim3(CHAT_BLOCK), 0, s, P);
+        if ((e = hipGetLastError()) != hipSuccess) return hip_fail("k_chat_turn_len", e);
+    }
+    if (exclusive_scan<unsigned long long>(s, P.len, n_turns, P.Gs, (unsigned long long)n_turns + 1) != 0)
+        return hip_fail("the scan of the turn lengths", hipGetLastError());
+    if (n_convs) {
+        hipLaunchKernelGGL(k_chat_plan, dim3(cdiv64(n_convs, CHAT_BLOCK)), dim3(CHAT_BLOCK), 0, s, P);
+        if ((e = hipGetLastError()) != hipSuccess) return hip_fail("k_chat_plan", e);
+        hipLaunchKernelGGL(k_chat_kept, dim3(cdiv64(n_rec, CHAT_BLOCK)), dim3(CHAT_BLOCK), 0, s, P);
+        if ((e = hipGetLastError()) != hipSuccess) return hip_fail("k_chat_kept", e);
+    }
+    if (exclusive_scan<unsigned long long>(s, P.len, n_rec, P.O, n_rec + 1) != 0) return hip_fail("the scan of the kept lengths", hipGetLastError());
+    (void)hipMemcpyAsync(&h_out, P.O + n_rec, 8, hipMemcpyDeviceToHost, s);
+    (void)hipMemcpyAsync(&h_status, P.status, 4, hipMemcpyDeviceToHost, s);
+    (void)hipEventRecord(c->chat_ev[1], s);
+    if ((e = hipStreamSynchronize(s)) != hipSuccess) return hip_fail("the plan passes", e);
+    if (h_status & CHAT_BAD_ROLE) return fail(c, YABPE_E_INVALID, "a turn has a role that is not below n_roles = %u", chat->n_roles);
+    if (h_status & CHAT_TOO_LONG) return fail(c, YABPE_E_CAPACITY, "a conversation has more than 2^32 - 1 ids");
+    if (h_out > LAY_MAX_SLOTS) return fail(c, YABPE_E_CAPACITY, "%llu output slots: at most 2^36 in one call", h_out);
+    uint32_t *o_ids = nullptr, *o_lab = nullptr;
+    if (dmalloc(c, &o_ids, h_out) != 0 || dmalloc(c, &o_lab, h_out) != 0) {
+        dfree(o_ids);
+        return YABPE_E_HIP;
+    }
+    S.adopt(o_ids);  // (the call's own until it has succeeded)
+    S.adopt(o_lab);
+    P.out_ids = o_ids;
+    P.out_labels = o_lab;
+    P.n_out = h_out;
+    if (h_out) {
+        hipLaunchKernelGGL(k_chat_write, dim3(cdiv64(h_out, CHAT_TILE)), dim3(CHAT_BLOCK), 0, s, P);
+        if ((e = hipGetLastError()) != hipSuccess) return hip_fail("k_chat_write", e);
+    }
+    hipLaunchKernelGGL(k_chat_finish, dim3(cdiv64((uint64_t)n_convs + 1, CHAT_BLOCK)), dim3(CHAT_BLOCK), 0, s, P);
+    if ((e = hipGetLastError()) != hipSuccess) return hip_fail("k_chat_finish", e);
+    (void)hipEventRecord(c->chat_ev[2], s);
+    unsigned long long h_cnt[CHAT_COUNTERS] = {0, 0, 0, 0};
+    (void)hipMemcpyAsync(h_cnt, P.counters, CHAT_COUNTERS * 8, hipMemcpyDeviceToHost, s);
+    if ((e = hipStreamSynchronize(s)) != hipSuccess) return hip_fail("k_chat_write", e);
+    yabpe_chat_free(c);  // the previous results go, this call's take their place
+    c->chat_buf[CB_IDS] = S.take(o_ids);
+    c->chat_buf[CB_LABELS] = S.take(o_lab);
+    c->chat_buf[CB_OFF] = S.take(out_off);
+    c->chat_buf[CB_INFO] = S.take(P.info);
+    float ms[2] = {0, 0};
+    auto &st = c->chat_stats;
+    st = yabpe_chat_stats_t{};
+    st.total_ms = pass_times(c->chat_ev, 2, ms);
+    st.plan_ms = ms[0];
+    st.write_ms = ms[1];
+    st.n_convs = n_convs;
+    st.n_turns = n_turns;
+    st.n_turns_dropped = h_cnt[CHAT_C_DROPPED];
+    st.n_ids_cut = h_cnt[CHAT_C_CUT];
+    st.n_out = h_out;
+    st.n_labelled = h_cnt[CHAT_C_LABELLED];
+    st.n_convs_unlabelled = h_cnt[CHAT_C_UNLABELLED];
+    *out_dev_ids = o_ids;
+    *out_dev_labels = o_lab;
+    *out_dev_off = (uint64_t *)out_off;
+    *out_dev_info = (uint32_t *)P.info;
+    *out_n_out = h_out;
+    return YABPE_OK;
+}
+
+int yabpe_chat_stats(yabpe_ctx *c, yabpe_chat_stats_t *out) {
+    if (!c || !out) return YABPE_E_INVALID;
+    *out = c->chat_stats;
     return YABPE_OK;
 }
 

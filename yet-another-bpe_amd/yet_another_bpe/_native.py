@@ -108,6 +108,18 @@ class FimStats(ctypes.Structure):
         (n, c_double) for n in ("cuts_ms", "plan_ms", "write_ms", "total_ms")]
 
 
+class Chat(ctypes.Structure):
+    """yabpe_chat_t"""
+    _fields_ = [("n_roles", c_uint32), ("head_ids", c_void_p), ("head_off", c_void_p), ("foot_ids", c_void_p), ("foot_off", c_void_p),
+                ("prefix_ids", c_void_p)] + [(n, c_uint32) for n in ("n_prefix", "train_mask", "pin_mask", "gen_role", "ignore")] + [
+        ("max_len", c_uint64), ("flags", c_uint32)]
+
+
+class ChatStats(ctypes.Structure):
+    _fields_ = [(n, c_uint64) for n in ("n_convs", "n_turns", "n_turns_dropped", "n_ids_cut", "n_out", "n_labelled", "n_convs_unlabelled")] + [
+        (n, c_double) for n in ("plan_ms", "write_ms", "total_ms")]
+
+
 class Layout(ctypes.Structure):
     """yabpe_layout_t"""
     _fields_ = [(n, c_uint32) for n in ("row_len", "pad_id", "bos_id", "eos_id", "flags")]
@@ -180,6 +192,7 @@ SYMBOLS = [
     "yabpe_mask", "yabpe_mask_free", "yabpe_mask_stats",
     "yabpe_span_corrupt", "yabpe_span_free", "yabpe_span_stats",
     "yabpe_fim_cuts", "yabpe_fim", "yabpe_fim_free", "yabpe_fim_stats",
+    "yabpe_chat", "yabpe_chat_free", "yabpe_chat_stats",
     "yabpe_pool_add", "yabpe_pool_get", "yabpe_pool_clear", "yabpe_pool_stats",
     "yabpe_normalize", "yabpe_normalize_free", "yabpe_normalize_stats",
     "yabpe_utf8_repair", "yabpe_utf8_repair_free", "yabpe_utf8_repair_stats",
@@ -268,6 +281,10 @@ def lib() -> ctypes.CDLL:
                                 POINTER(c_void_p), POINTER(c_void_p), POINTER(c_uint64)]
         L.yabpe_fim_free.argtypes = [c_void_p]
         L.yabpe_fim_stats.argtypes = [c_void_p, POINTER(FimStats)]
+        L.yabpe_chat.argtypes = [c_void_p, c_void_p, c_uint64, c_void_p, c_uint32, c_void_p, c_uint32, c_void_p, POINTER(Chat), POINTER(c_void_p),
+                                 POINTER(c_void_p), POINTER(c_void_p), POINTER(c_void_p), POINTER(c_uint64)]
+        L.yabpe_chat_free.argtypes = [c_void_p]
+        L.yabpe_chat_stats.argtypes = [c_void_p, POINTER(ChatStats)]
         L.yabpe_pool_add.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_uint64]
         L.yabpe_pool_get.argtypes = [c_void_p, POINTER(c_void_p), POINTER(c_void_p), POINTER(c_void_p), POINTER(c_uint64), POINTER(c_uint64)]
         L.yabpe_pool_clear.argtypes = [c_void_p]
@@ -300,6 +317,9 @@ MASK_IGNORE = 0xFFFFFF9C  # yabpe_mask_t.ignore: -100 as i32, the label a loss s
 SPAN_WHOLE_WORD, SPAN_FINAL_SENTINEL = 0x1, 0x2  # yabpe_span_t.flags
 SPAN_MAX_LEN = 32  # YABPE_SPAN_MAX_LEN
 FIM_EOT, FIM_LOSS_MIDDLE, FIM_PIECES = 0x1, 0x2, 0x4  # yabpe_fim_t.flags
+CHAT_LOSS_ALL, CHAT_LOSS_LAST, CHAT_DROP_OLDEST, CHAT_PIN_FIRST, CHAT_GEN_PROMPT = 0x01, 0x02, 0x04, 0x08, 0x10  # yabpe_chat_t.flags
+CHAT_MAX_ROLES, CHAT_MAX_TEMPLATE_IDS = 16, 2048  # YABPE_CHAT_MAX_ROLES, YABPE_CHAT_MAX_TEMPLATE_IDS
+CHAT_TILE, CHAT_STAGE = 1024, 256  # chat_logic.h: output slots a workgroup of the write pass owns, turn records it stages at a time
 PAIRS_MODES = {"longest_first": 0, "only_first": 1, "only_second": 2, "windows": 3}  # yabpe_pairs_t.mode (YABPE_PAIRS_*)
 
 
@@ -1087,6 +1107,70 @@ class Context:
     def fim_stats(self) -> dict:
         s = FimStats()
         self._chk(lib().yabpe_fim_stats(self._h, byref(s)))
+        return _stats_dict(s)
+
+    # -- conversation batches (BBPETokenizer.chat_tokens on the device)
+    def chat(self, ids, n_ids: int | None = None, doc_starts=None, n_turns: int | None = None, conv_starts=None, n_convs: int | None = None,
+             roles=None, *, heads=(), feet=(), prefix=(), train_mask: int = 0, pin_mask: int = 0, gen_role: int | None = None,
+             ignore: int = MASK_IGNORE, max_len: int = 0, loss_all: bool = False, loss_last: bool = False, drop_oldest: bool = False,
+             pin_first: bool = False, flags: int = 0, n_roles: int | None = None):
+        """The sequences and labels of conversations from their separately encoded contents (yabpe_chat).  ids / doc_starts: the
+        n_turns contents as mask takes them (an empty doc_starts array: no turns); conv_starts: the first turn of every
+        conversation, a u64 array (staged; empty: no conversations) or a device address with n_convs; roles: one role index per
+        turn, a u8 array or a device address.  heads / feet: the header and footer ids of every role, prefix: the ids of X;
+        gen_role: None, or the role whose header is appended.  flags: further YABPE_CHAT_* bits as they are.
+        -> (dev_ids_ptr u32[n_out], dev_labels_ptr u32[n_out], dev_off_ptr u64[n_convs + 1], dev_info_ptr u32[n_convs, 4], n_out,
+        n_convs); the buffers live until the next chat, chat_free() or close()."""
+        if isinstance(ids, int):
+            keep, ptr, n = None, c_void_p(ids), int(n_ids)
+        else:
+            keep = np.ascontiguousarray(ids, dtype=np.uint32)
+            ptr, n = c_void_p(keep.ctypes.data if keep.size else 0), int(keep.size)
+        tables = []
+        for starts, count in ((doc_starts, n_turns), (conv_starts, n_convs)):
+            if isinstance(starts, int):
+                tables.append((None, c_void_p(starts), int(count)))
+            else:
+                t = np.ascontiguousarray(starts if starts is not None else [], dtype=np.uint64)
+                tables.append((t, c_void_p(t.ctypes.data if t.size else 0), len(t)))
+        (_docs, dptr, nt), (_convs, cptr, nc) = tables
+        if isinstance(roles, int):
+            keep_roles, rptr = None, c_void_p(roles)
+        else:
+            keep_roles = np.ascontiguousarray(roles if roles is not None else [], dtype=np.uint8)
+            if keep_roles.size != nt:
+                raise ValueError(f"roles must hold one entry per turn: {keep_roles.size} for {nt} turns")
+            rptr = c_void_p(keep_roles.ctypes.data if keep_roles.size else 0)
+        if len(heads) != len(feet):
+            raise ValueError(f"{len(heads)} headers and {len(feet)} footers: one of each per role")
+
+        def table(pieces):
+            flat = np.ascontiguousarray([t for p in pieces for t in p], dtype=np.uint32)
+            return flat, np.concatenate(([0], np.cumsum([len(p) for p in pieces], dtype=np.int64))).astype(np.uint32)
+
+        (h_ids, h_off), (f_ids, f_off), pre = table(heads), table(feet), np.ascontiguousarray(prefix, dtype=np.uint32)
+        arg = Chat(len(heads) if n_roles is None else int(n_roles), h_ids.ctypes.data, h_off.ctypes.data, f_ids.ctypes.data, f_off.ctypes.data,
+                   pre.ctypes.data, int(pre.size), int(train_mask), int(pin_mask), int(gen_role or 0), int(ignore), int(max_len),
+                   int(flags) | (CHAT_LOSS_ALL if loss_all else 0) | (CHAT_LOSS_LAST if loss_last else 0) | (CHAT_DROP_OLDEST if drop_oldest else 0)
+                   | (CHAT_PIN_FIRST if pin_first else 0) | (0 if gen_role is None else CHAT_GEN_PROMPT))
+        di, dl, do, dn, no = c_void_p(), c_void_p(), c_void_p(), c_void_p(), c_uint64()
+        self._chk(lib().yabpe_chat(self._h, ptr, n, dptr, nt, cptr, nc, rptr, byref(arg), byref(di), byref(dl), byref(do), byref(dn), byref(no)))
+        return di.value or 0, dl.value or 0, do.value or 0, dn.value or 0, int(no.value), nc
+
+    def chat_to_host(self, ids, n_ids: int | None = None, doc_starts=None, n_turns: int | None = None, conv_starts=None,
+                     n_convs: int | None = None, roles=None, **kw):
+        """-> (ids u32[n_out], labels i32[n_out], off u64[n_convs + 1], info u32[n_convs, 4]) copied to the host."""
+        di, dl, do, dn, no, nc = self.chat(ids, n_ids, doc_starts, n_turns, conv_starts, n_convs, roles, **kw)
+        rag = lambda p: self.d2h(p, 4 * no, np.uint32) if no else np.zeros(0, np.uint32)  # noqa: E731
+        info = self.d2h(dn, 16 * nc, np.uint32).reshape(nc, 4) if nc else np.zeros((0, 4), np.uint32)
+        return rag(di), rag(dl).view(np.int32), self.d2h(do, 8 * (nc + 1), np.uint64), info
+
+    def chat_free(self) -> None:
+        self._chk(lib().yabpe_chat_free(self._h))
+
+    def chat_stats(self) -> dict:
+        s = ChatStats()
+        self._chk(lib().yabpe_chat_stats(self._h, byref(s)))
         return _stats_dict(s)
 
     # -- the persistent word pool (corpora larger than device memory: words go in call by call, the merge loop loads the pool)

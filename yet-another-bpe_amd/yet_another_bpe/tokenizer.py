@@ -13,6 +13,8 @@ encode_array_dropout / encode_batch_device_dropout compute the same ids on the G
 forms take dropout= and seed=.  encode_with_words also says which piece of its document every id was made from, mask_tokens
 draws a seeded masked-language-model mask over such ids, encode_batch_masked lays both out as padded rows;
 encode_array_with_words / mask_array / encode_array_masked compute the same on the GPU (yabpe_encode_words, yabpe_mask).
+chat_tokens / encode_batch_chat write conversations through a ChatTemplate with labels on the assistant's turns;
+chat_array / encode_array_chat compute the same on the GPU (yabpe_chat).
 """
 from __future__ import annotations
 
@@ -22,6 +24,7 @@ import operator
 from collections.abc import Sequence
 from functools import lru_cache
 from pathlib import Path
+from typing import NamedTuple
 
 import numpy as np
 import regex
@@ -32,6 +35,17 @@ from .trainer import (CL100K_DIGIT_GROUP, NORMALIZERS, PRETOKENIZER_NAMES, BBPET
                       device_text_front, lowercase_text, normalize_text, read_lowercase, read_normalizer, read_pretokenizer, split_pattern)
 
 _WORD_CACHE = 8192
+
+
+class ChatTemplate(NamedTuple):
+    """A chat template as chat_tokens takes it: roles maps every role name to its (header, footer) strings, in the order that
+    numbers the roles; prefix opens every conversation; the generation prompt is the header of generation_role.  Llama-3:
+        ChatTemplate({r: (f"<|start_header_id|>{r}<|end_header_id|>\\n\\n", "<|eot_id|>") for r in ("system", "user", "assistant", "ipython")},
+                     prefix="<|begin_of_text|>")
+    The strings are encoded one by one with the tokenizer's encode, so a special token in them is a special if the model has it."""
+    roles: dict
+    prefix: str = ""
+    generation_role: str = "assistant"
 
 
 class BBPETokenizer:
@@ -754,6 +768,168 @@ class BBPETokenizer:
         lab_rows, _ = self._padded_rows(labels, L, added, ign, None if bos is None else ign, None if eos is None else ign, truncation, padding_side)
         return rows, lab_rows, lengths, info
 
+    # ------------------------------------------------------------------ conversation batches (supervised fine-tuning)
+    ChatTemplate = ChatTemplate  # (BBPETokenizer.ChatTemplate(roles, prefix, generation_role): a template of one's own)
+    CHATML = ChatTemplate({r: (f"<|im_start|>{r}\n", "<|im_end|>\n") for r in ("system", "user", "assistant", "tool")})
+    CHAT_LOSSES = ("roles", "all", "last")
+    CHAT_TRUNCATIONS = ("right", "drop_oldest")
+    CHAT_MAX_ROLES, CHAT_MAX_TEMPLATE_IDS = 16, 2048  # YABPE_CHAT_MAX_ROLES, YABPE_CHAT_MAX_TEMPLATE_IDS
+
+    def _chat_args(self, template, train_roles, loss, max_length, truncation, pin_first, pin_roles, add_generation_prompt) -> dict:
+        """The template encoded piece by piece and the rule's arguments, validated as yabpe_chat validates them -> a dict: names
+        (role -> index), heads, feet (ids per role), X, G, gen (role index or None), train_mask, pin_mask, max_len (0: no cut),
+        loss, drop_oldest, pin_first"""
+        try:
+            names = {str(r): i for i, r in enumerate(template.roles)}
+            heads, feet = ([self.encode(template.roles[r][k]) for r in template.roles] for k in (0, 1))
+            X = self.encode(template.prefix)
+        except (AttributeError, TypeError, IndexError, KeyError):
+            raise ValueError(f"template must be a ChatTemplate (roles: role -> (header, footer); prefix; generation_role), not {template!r}") from None
+        if not 1 <= len(names) <= self.CHAT_MAX_ROLES:
+            raise ValueError(f"a template has 1 to {self.CHAT_MAX_ROLES} roles, not {len(names)}")
+        n_tpl = len(X) + sum(len(p) for p in heads + feet)
+        if n_tpl > self.CHAT_MAX_TEMPLATE_IDS:
+            raise ValueError(f"the template's prefix, headers and footers are {n_tpl} ids: at most {self.CHAT_MAX_TEMPLATE_IDS}")
+        if loss not in self.CHAT_LOSSES:
+            raise ValueError(f"loss must be 'roles', 'all' or 'last', not {loss!r}")
+        if truncation not in self.CHAT_TRUNCATIONS:
+            raise ValueError(f"truncation must be 'right' or 'drop_oldest', not {truncation!r}")
+        masks = []
+        if pin_roles is None:
+            pin_roles = [r for r in ("system",) if r in names]
+        for what, roles in (("train_roles", train_roles), ("pin_roles", pin_roles)):
+            roles = [roles] if isinstance(roles, str) else list(roles)
+            for r in roles:
+                if r not in names:
+                    raise ValueError(f"{what}: the template has no role {r!r}")
+            masks.append(sum({1 << names[r] for r in roles}))
+        gen = None
+        if add_generation_prompt:
+            if template.generation_role not in names:
+                raise ValueError(f"generation_role: the template has no role {template.generation_role!r}")
+            gen = names[template.generation_role]
+        G = [] if gen is None else heads[gen]
+        max_len = 0
+        if max_length is not None:
+            max_len = self._row_length(max_length, "max_length", 0)
+            if max_len <= len(X) + len(G) or max_len >= 1 << 64:
+                raise ValueError(f"max_length must be above {len(X) + len(G)} (the prefix and the generation prompt always survive) and below 2^64, "
+                                 f"not {max_len}")
+        return {"names": names, "heads": heads, "feet": feet, "X": X, "G": G, "gen": gen, "train_mask": masks[0], "pin_mask": masks[1],
+                "max_len": max_len, "loss": loss, "drop_oldest": truncation == "drop_oldest", "pin_first": bool(pin_first)}
+
+    @staticmethod
+    def _chat_role(names: dict, role) -> int:
+        if role not in names:
+            raise ValueError(f"the template has no role {role!r}")
+        return names[role]
+
+    def _chat_sequence(self, turns, A: dict):
+        """One conversation from its turns [(role index, content ids)] -> (sequence, labels, (q, k, ids kept, ids with a label))"""
+        ign, T, loss = self.IGNORE_LABEL, len(turns), A["loss"]
+        bodies, labs = [], []
+        for j, (r, ids) in enumerate(turns):
+            H, F = A["heads"][r], A["feet"][r]
+            trains = loss == "all" or (bool(A["train_mask"] >> r & 1) and (loss != "last" or j == T - 1))
+            bodies.append(H + ids + F)
+            labs.append((H if loss == "all" else [ign] * len(H)) + (ids + F if trains else [ign] * (len(ids) + len(F))))
+        B = A["max_len"] - len(A["X"]) - len(A["G"]) if A["max_len"] else None
+        q = k = 0
+        if A["drop_oldest"]:
+            q = k = int(A["pin_first"] and T > 0 and bool(A["pin_mask"] >> turns[0][0] & 1))
+            if B is not None:
+                last = max(q, T - 1)
+                kept_len = lambda k: sum(len(b) for b in bodies[:q]) + sum(len(b) for b in bodies[k:])  # noqa: E731  (L(k))
+                k = next((k for k in range(q, last + 1) if kept_len(k) <= B), last)
+        keep = [j for j in range(T) if j < q or j >= k]
+        body = [t for j in keep for t in bodies[j]][:B]
+        lab = [t for j in keep for t in labs[j]][:B]
+        seq = A["X"] + body + A["G"]
+        labels = [ign] * len(A["X"]) + lab + [ign] * len(A["G"])
+        return seq, labels, (q, k, len(seq), len(lab) - lab.count(ign))
+
+    def chat_tokens(self, contents_ids, roles, conv_sizes, *, template: ChatTemplate = CHATML, train_roles=("assistant",), loss: str = "roles",
+                    max_length: int | None = None, truncation: str = "drop_oldest", pin_first: bool = True, pin_roles=None,
+                    add_generation_prompt: bool = False) -> tuple[list[list[int]], list[list[int]], list[tuple[int, int, int, int]]]:
+        """Conversations for supervised fine-tuning from contents that are already encoded -> (sequences, labels, info), one
+        entry each per conversation.  contents_ids[t] and roles[t] (a role name of the template) are turn t of the batch;
+        conversation c owns the next conv_sizes[c] turns.
+        Pieces are encoded separately: the template gives every role r a header H_r and a footer F_r, a prefix X and a generation
+        prompt G = the header of template.generation_role; each string is encoded on its own with encode (specials in them are
+        specials), and every content is a document of its own.  The sequence is the concatenation of these id sequences, so no
+        merge crosses a piece boundary and label boundaries are exact.  This is deliberately not "render the string, then
+        tokenise it": the ids can differ from those of the rendered string where a merge would span a boundary.
+          body_t = H_{r_t} + c_t + F_{r_t}       seq = X + body_0 + ... + body_{T-1} + [G with add_generation_prompt]
+        No turns give X + [G]; empty contents are valid.
+        labels: -100 everywhere, but in a turn whose role is in train_roles the content and footer ids carry their own id.  loss
+        "all": every id of every body does; "last": only turn T - 1, and only if its role is in train_roles.  X and G never do.
+        max_length (None: no cut): X and G always survive, B = max_length - len(X) - len(G) must be positive.  truncation "right":
+        the first B ids of the concatenated bodies stay, wherever the cut falls.  "drop_oldest" works on whole turns: q = 1 if
+        pin_first, T > 0 and r_0 is in pin_roles (None: "system" if the template has it), else 0; L(k) = the ids of bodies [0, q) and [k, T); k is the smallest value of
+        [q, max(q, T - 1)] with L(k) <= B, or max(q, T - 1) if there is none; turns [0, q) and [k, T) stay -- the last turn
+        always -- and what is still longer than B is cut on the right.  No rule reads the batch or another conversation.
+        info[c] = (q, k, ids kept, ids that carry a label) after the cut; with truncation "right" q = k = 0."""
+        A = self._chat_args(template, train_roles, loss, max_length, truncation, pin_first, pin_roles, add_generation_prompt)
+        sizes = [operator.index(n) for n in conv_sizes]
+        if len(contents_ids) != len(roles) or min(sizes, default=0) < 0 or sum(sizes) != len(roles):
+            raise ValueError(f"{len(contents_ids)} contents, {len(roles)} roles and conv_sizes that sum to {sum(sizes)}: all three must agree")
+        turns = [(self._chat_role(A["names"], r), [int(t) for t in ids]) for r, ids in zip(roles, contents_ids)]
+        out, at = ([], [], []), 0
+        for n in sizes:
+            for dst, v in zip(out, self._chat_sequence(turns[at:at + n], A)):
+                dst.append(v)
+            at += n
+        return out
+
+    @staticmethod
+    def _chat_turns(conversations) -> tuple[list[str], list[str], list[int]]:
+        """-> (role of every turn, content of every turn, turns per conversation); a turn is (role, content) or a mapping with
+        "role" and "content\""""
+        roles, contents, sizes = [], [], []
+        for conv in conversations:
+            sizes.append(len(conv))
+            for turn in conv:
+                role, content = (turn["role"], turn["content"]) if hasattr(turn, "keys") else turn
+                if not isinstance(content, str):
+                    raise ValueError(f"the content of a turn must be a str, not {content!r}")
+                roles.append(role)
+                contents.append(content)
+        return roles, contents, sizes
+
+    def _chat_row_args(self, max_length, pad_id, bos_id, eos_id, padding_side, *chat_args):
+        """-> (_padded_args' results, _chat_args' result): the sequences are cut to max_length minus BOS and EOS"""
+        L, pad, bos, eos, added = self._padded_args(max_length, pad_id, bos_id, eos_id, "right", padding_side)
+        template, train_roles, loss, truncation, pin_first, pin_roles, add_generation_prompt = chat_args
+        A = self._chat_args(template, train_roles, loss, None if L is None else L - added, truncation, pin_first, pin_roles, add_generation_prompt)
+        return (L, pad, bos, eos, added), A
+
+    def encode_batch_chat(self, conversations, max_length: int | None = None, *, template: ChatTemplate = CHATML, train_roles=("assistant",),
+                          loss: str = "roles", truncation: str = "drop_oldest", pin_first: bool = True, pin_roles=None,
+                          add_generation_prompt: bool = False, pad_id: int | None = None, bos_id: int | None = None, eos_id: int | None = None,
+                          padding_side: str = "right"):
+        """Conversation rows in one call -> (input_ids, labels, lengths, info).  A conversation is a sequence of (role, content)
+        tuples or of {"role", "content"} mappings; a role the template does not have is a ValueError that names it.  Every
+        content is encoded with encode as a document of its own, then chat_tokens' rule applies with the cut to max_length minus
+        BOS and EOS (None: no cut).  The rows are laid out as encode_batch_padded lays them out (max_length None: the longest),
+        labels with -100 in BOS, EOS and pad slots and wherever the loss skips."""
+        (L, pad, bos, eos, added), A = self._chat_row_args(max_length, pad_id, bos_id, eos_id, padding_side, template, train_roles, loss, truncation,
+                                                           pin_first, pin_roles, add_generation_prompt)
+        roles, contents, sizes = self._chat_turns(conversations)
+        turns = [(self._chat_role(A["names"], r), self.encode(t)) for r, t in zip(roles, contents)]
+        seqs, labels, info, at = [], [], [], 0
+        for n in sizes:
+            seq, lab, inf = self._chat_sequence(turns[at:at + n], A)
+            seqs.append(seq)
+            labels.append(lab)
+            info.append(inf)
+            at += n
+        if L is None:
+            L = max((len(ids) + added for ids in seqs), default=0)
+        ign = self.IGNORE_LABEL
+        rows, lengths = self._padded_rows(seqs, L, added, pad, bos, eos, "right", padding_side)
+        lab_rows, _ = self._padded_rows(labels, L, added, ign, None if bos is None else ign, None if eos is None else ign, "right", padding_side)
+        return rows, lab_rows, lengths, info
+
     # ------------------------------------------------------------------ fixed-shape batches
     def _layout_ids(self, pad_id, bos_id, eos_id) -> tuple[int, int | None, int | None, int]:
         """-> (pad id, bos id or None, eos id or None, n_added); every id given must be an integer in [0, 2^32)"""
@@ -1399,6 +1575,78 @@ class BBPETokenizer:
         if rows.shape[1] == 0:  # (only empty sequences and neither BOS nor EOS)
             return rows, np.zeros(rows.shape, np.int32), lengths, info
         labels, _lengths = ctx.layout_pad_to_host(fl, n_out, fo, n_docs, row_len=rows.shape[1], pad_id=ign, bos_id=None if bos is None else ign,
+                                                  eos_id=None if eos is None else ign, **cut)
+        return rows, labels.view(np.int32), lengths, info
+
+    @staticmethod
+    def _chat_native_args(A: dict) -> dict:
+        from . import _native
+
+        return {"heads": A["heads"], "feet": A["feet"], "prefix": A["X"], "train_mask": A["train_mask"], "pin_mask": A["pin_mask"], "gen_role": A["gen"],
+                "ignore": _native.MASK_IGNORE, "max_len": A["max_len"], "loss_all": A["loss"] == "all", "loss_last": A["loss"] == "last",
+                "drop_oldest": A["drop_oldest"], "pin_first": A["pin_first"]}
+
+    def _chat_role_array(self, names: dict, roles) -> np.ndarray:
+        """role names, or indices in the template's order, -> u8 indices"""
+        idx = np.asarray([self._chat_role(names, r) if isinstance(r, str) else operator.index(r) for r in roles], dtype=np.int64)
+        if idx.size and (idx.min() < 0 or idx.max() >= len(names)):
+            raise ValueError(f"role indices must lie in [0, {len(names)})")
+        return idx.astype(np.uint8)
+
+    def chat_array(self, ids, doc_off, conv_off, roles, *, template: ChatTemplate = CHATML, train_roles=("assistant",), loss: str = "roles",
+                   max_length: int | None = None, truncation: str = "drop_oldest", pin_first: bool = True, pin_roles=None,
+                   add_generation_prompt: bool = False) -> tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray]:
+        """chat_tokens on the GPU (yabpe_chat), bit for bit: ids and doc_off are the contents of all turns as encode_array returns
+        them, conv_off the n_convs + 1 ascending turn offsets of the conversations (from 0 to the number of turns), roles one
+        role name (or index in the template's order) per turn
+        -> (seq_ids np.uint32[n_out], labels np.int32[n_out], off np.uint64[n_convs + 1], info np.uint32[n_convs, 4]):
+        conversation c's sequence is seq_ids[off[c]:off[c + 1]]."""
+        A = self._chat_args(template, train_roles, loss, max_length, truncation, pin_first, pin_roles, add_generation_prompt)
+        ids = np.ascontiguousarray(ids, dtype=np.uint32)
+        off, coff = np.asarray(doc_off, dtype=np.int64), np.asarray(conv_off, dtype=np.int64)
+        if off.ndim != 1 or len(off) < 1 or off[0] != 0 or off[-1] != len(ids) or np.any(np.diff(off) < 0):
+            raise ValueError("doc_off must be n_turns + 1 ascending offsets from 0 to len(ids)")
+        if coff.ndim != 1 or len(coff) < 1 or coff[0] != 0 or coff[-1] != len(off) - 1 or np.any(np.diff(coff) < 0):
+            raise ValueError("conv_off must be n_convs + 1 ascending offsets from 0 to the number of turns")
+        if len(roles) != len(off) - 1:
+            raise ValueError(f"roles must hold one entry per turn: {len(roles)} for {len(off) - 1} turns")
+        return self._device().chat_to_host(ids, None, off[:-1].astype(np.uint64), None, coff[:-1].astype(np.uint64), None,
+                                           self._chat_role_array(A["names"], roles), **self._chat_native_args(A))
+
+    def encode_array_chat(self, conversations, max_length: int | None = None, *, template: ChatTemplate = CHATML, train_roles=("assistant",),
+                          loss: str = "roles", truncation: str = "drop_oldest", pin_first: bool = True, pin_roles=None,
+                          add_generation_prompt: bool = False, pad_id: int | None = None, bos_id: int | None = None, eos_id: int | None = None,
+                          padding_side: str = "right"):
+        """encode_batch_chat(conversations, ...), computed on the GPU: one yabpe_encode over the contents of all turns behind the
+        text front (lowercase, the normaliser and the patterns apply), yabpe_chat on its device results, then yabpe_layout_pad
+        over the sequences and, once those rows are copied out, over the labels with the ignore value as pad, BOS and EOS id (the
+        ragged arrays never visit the host).
+        -> (rows np.uint32[n_convs, L], labels np.int32[n_convs, L], lengths np.uint32[n_convs], info np.uint32[n_convs, 4])."""
+        (L, pad, bos, eos, _added), A = self._chat_row_args(max_length, pad_id, bos_id, eos_id, padding_side, template, train_roles, loss, truncation,
+                                                            pin_first, pin_roles, add_generation_prompt)
+        roles, contents, sizes = self._chat_turns(conversations)
+        role_idx = self._chat_role_array(A["names"], roles)
+        n_convs = len(sizes)
+        if n_convs == 0:
+            return np.zeros((0, L or 0), np.uint32), np.zeros((0, L or 0), np.int32), np.zeros(0, np.uint32), np.zeros((0, 4), np.uint32)
+        from . import _native
+
+        ctx = self._device()
+        conv_starts = np.concatenate(([0], np.cumsum(sizes)[:-1])).astype(np.uint64)
+        inp = self._device_input(contents)
+        if inp is None:  # (conversations without turns)
+            di, dd, ni = np.zeros(0, np.uint32), np.zeros(0, np.uint64), None
+        else:
+            text, n_bytes, starts = self._device_text(ctx, inp)
+            di, dd, ni = ctx.encode(text, n_bytes, doc_starts=starts)
+        fi, fl, fo, fn, n_out, _nc = ctx.chat(di, ni, dd, len(contents), conv_starts, None, role_idx, **self._chat_native_args(A))
+        info = ctx.d2h(fn, 16 * n_convs, np.uint32).reshape(n_convs, 4)
+        cut = {"pad_left": padding_side == "left"}
+        ign = _native.MASK_IGNORE
+        rows, lengths = ctx.layout_pad_to_host(fi, n_out, fo, n_convs, row_len=L or 0, pad_id=pad, bos_id=bos, eos_id=eos, **cut)
+        if rows.shape[1] == 0:  # (only empty sequences and neither BOS nor EOS)
+            return rows, np.zeros(rows.shape, np.int32), lengths, info
+        labels, _lengths = ctx.layout_pad_to_host(fl, n_out, fo, n_convs, row_len=rows.shape[1], pad_id=ign, bos_id=None if bos is None else ign,
                                                   eos_id=None if eos is None else ign, **cut)
         return rows, labels.view(np.int32), lengths, info
 
