@@ -689,9 +689,48 @@ typedef struct yabpe_fit_rows_t {
 } yabpe_fit_rows_t;
 int yabpe_layout_fit(yabpe_ctx *ctx, const uint32_t *ids, uint64_t n_ids, const uint64_t *doc_off, uint32_t n_docs,
                      const yabpe_layout_t *layout, yabpe_fit_rows_t *out);
+/* Labelled sequences packed whole (BBPETokenizer.fit_labelled on the device): what yabpe_mask, yabpe_span_corrupt, yabpe_fim and
+ * yabpe_chat return -- ragged ids, their labels as u32 words with the call's `ignore`, and the sequence starts -- packed several
+ * whole sequences a row, for supervised fine-tuning with position ids that restart and attention cut at the seams.
+ * ids and labels: n_ids u32 each; seq_off: n_seqs ascending starts, the first one 0 (sequence s ends where s + 1 starts, the last
+ * one at n_ids; NULL with n_seqs <= 1: one sequence); all three host or device memory, left alone.  No model is needed.
+ * With C = row_len: a sequence longer than C loses ids and labels from its right end, n_s = min(len, C); nothing is added (the
+ * sequences carry their own BOS, EOS and sentinels); a sequence with n_s == 0 is in no row.  Rows, shapes and dealing are
+ * exactly yabpe_layout_fit's on the lengths n_s.
+ * Per slot of sequence s at position p: ids[s][p], seq = s, pos = p and the label -- aligned (no flag): labels[s][p], but
+ * `ignore` at p == 0 with YABPE_FITL_MASK_FIRST (the first id of a sequence is not predicted from the last id of the one in
+ * front); YABPE_FITL_SHIFTED: labels[s][p + 1] if p + 1 < n_s, else `ignore` -- the target of the slot, never taken across a seam
+ * and never an id the row does not hold (MASK_FIRST has no effect then).  Pad slots: pad_id, ignore, 0xFFFFFFFF, 0.
+ * Per row r: used[r] = its filled slots, labelled[r] = its slots whose label is not `ignore`.  Per placed sequence, in row order
+ * and left to right within a row: placed[3 t .. 3 t + 2] = (seq, col, len); row_first[r] = the first record of row r,
+ * row_first[n_rows] = n_placed -- cu_seqlens of any set of rows is r * C + col, max_seqlen the largest len.
+ * Results are device memory owned by the library, in buffers of their own, released by yabpe_layout_free, the next layout call
+ * or yabpe_destroy.  A refused call leaves the previous layout results valid.  n_seqs = 0: no rows and NULL results; only empty
+ * sequences: no rows, row_first = {0}.
+ * YABPE_E_INVALID: row_len == 0 or > 2^24 - 1; flags outside YABPE_FITL_*; a bad seq_off.  YABPE_E_CAPACITY: more than 2^36
+ * output slots.  Every error is found before a result buffer is allocated.  yabpe_layout_stats: n_docs = n_seqs,
+ * n_truncated_docs, n_ids_dropped and n_pad_slots as for yabpe_layout_fit; lengths_ms = lengths + histogram + sort, write_ms =
+ * the place records and the output pass, total_ms includes the plan, which runs on the host. */
+#define YABPE_FITL_SHIFTED    0x01u
+#define YABPE_FITL_MASK_FIRST 0x02u
+typedef struct yabpe_fit_labels_t {
+    uint32_t row_len;  /* C */
+    uint32_t pad_id;
+    uint32_t ignore;   /* the label word of a slot the loss skips */
+    uint32_t flags;    /* YABPE_FITL_* */
+} yabpe_fit_labels_t;
+typedef struct yabpe_fit_label_rows_t {
+    uint32_t *ids, *labels, *seq, *pos;   /* n_rows * row_len each */
+    uint32_t *used, *labelled;            /* n_rows each */
+    uint32_t *placed;                     /* 3 * n_placed: (seq, col, len) */
+    uint32_t *row_first;                  /* n_rows + 1 */
+    uint64_t n_rows, n_placed;
+} yabpe_fit_label_rows_t;
+int yabpe_layout_fit_labels(yabpe_ctx *ctx, const uint32_t *ids, const uint32_t *labels, uint64_t n_ids, const uint64_t *seq_off,
+                            uint32_t n_seqs, const yabpe_fit_labels_t *opt, yabpe_fit_label_rows_t *out);
 int yabpe_layout_free(yabpe_ctx *ctx);
-/* What the last yabpe_layout_pad / yabpe_layout_pack / yabpe_layout_windows / yabpe_layout_pairs / yabpe_layout_fit saw, and the device time of
- * its phases (HIP events around each phase's launches). */
+/* What the last yabpe_layout_pad / yabpe_layout_pack / yabpe_layout_windows / yabpe_layout_pairs / yabpe_layout_fit /
+ * yabpe_layout_fit_labels saw, and the device time of its phases (HIP events around each phase's launches). */
 typedef struct yabpe_layout_stats_t {
     uint64_t n_ids, n_docs;
     uint64_t n_rows, row_len;

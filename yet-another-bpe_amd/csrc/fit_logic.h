@@ -167,3 +167,61 @@ inline void fit_plan(const uint32_t *hist, uint32_t C, FitPlan *out) {
     out->n_rows = row;
     out->steps = steps;
 }
+
+// ---- labelled sequences (BBPETokenizer.fit_labelled; yabpe_layout_fit_labels in yabpe.hip, yabpe_fitlab_kernels.h)
+// The sequences arrive with their labels and are cut on the right to C; rows, shapes and dealing are the plan above on the
+// lengths n_s = min(len, C).  A placed sequence is a RECORD; the records are numbered in row order, within a row left to
+// right, so record t of the plan is row `first[s] + i`, place j of shape s with t = base[s] + i * places(s) + j.
+//   Rule 7 (fitl_record_base / fitl_find_record): the first record of every shape; the shape, row and place of record t.
+//   Rule 8 (fitl_label): which entry of the labels, if any, the slot at position p of a sequence of n kept ids holds.
+constexpr uint32_t FITL_SHIFTED = 0x1u;     // YABPE_FITL_SHIFTED: the slot holds the label of the next position
+constexpr uint32_t FITL_MASK_FIRST = 0x2u;  // YABPE_FITL_MASK_FIRST: (aligned form) position 0 of every sequence is ignored
+constexpr uint32_t FITL_FLAGS = FITL_SHIFTED | FITL_MASK_FIRST;
+constexpr uint32_t FITL_SLOTS = 4;          // consecutive output slots a lane of the write pass owns (16-byte stores)
+constexpr uint32_t FITL_BLOCK = 256;        // threads of both kernels
+constexpr uint32_t FITL_TILE = FITL_BLOCK * FITL_SLOTS;  // output slots a workgroup of the write pass owns
+constexpr uint32_t FITL_STAGE = FITL_BLOCK; // resolved records the write pass holds in LDS at a time
+
+// Rule 8.  *src = the index inside the sequence's labels that the slot at position p < n holds; false: the slot holds `ignore`.
+// Shifted: the target of the slot is the next position, never taken across the end of the sequence (so never across a seam,
+// and never an id the cut dropped); aligned: the slot's own label, but not at position 0 with FITL_MASK_FIRST -- the first id
+// of a sequence is not predicted from the last id of the sequence in front of it.
+YB_HD bool fitl_label(uint32_t flags, uint32_t p, uint32_t n, uint32_t *src) {
+    if (flags & FITL_SHIFTED) {
+        *src = p + 1;
+        return p + 1 < n;
+    }
+    *src = p;
+    return !((flags & FITL_MASK_FIRST) && p == 0);
+}
+
+// Rule 7.  base[s] = the first record of shape s, base[n_shapes] = the placed sequences (they are fewer than 2^32: a record
+// is a sequence of the call).
+inline void fitl_record_base(const FitPlan &plan, std::vector<uint32_t> *base) {
+    base->assign(plan.place.size(), 0);
+    for (uint32_t s = 0; s + 1 < plan.place.size(); ++s)
+        (*base)[s + 1] = (uint32_t)((*base)[s] + (plan.first[s + 1] - plan.first[s]) * (plan.place[s + 1] - plan.place[s]));
+}
+
+// Record t < base[n_shapes] -> its shape; *i = its row inside the shape, *j = its place inside the row.  Every shape has a row
+// and every row a place, so base ascends strictly.
+YB_HD uint32_t fitl_find_record(const uint32_t *base, const uint32_t *place, uint32_t n_shapes, uint32_t t, uint32_t *i, uint32_t *j) {
+    uint32_t lo = 0, hi = n_shapes - 1;
+    while (lo < hi) {
+        const uint32_t mid = lo + (hi - lo + 1) / 2;
+        if (base[mid] <= t)
+            lo = mid;
+        else
+            hi = mid - 1;
+    }
+    const uint32_t per = place[lo + 1] - place[lo];
+    *i = (t - base[lo]) / per;
+    *j = (t - base[lo]) % per;
+    return lo;
+}
+
+// The resolved record of a placed sequence, private to the write pass (16 bytes: one load).
+struct alignas(16) FitlRec {
+    unsigned long long src;  // where the sequence starts in the ragged ids and labels
+    unsigned long long at;   // its first output slot, row * C + col: ascends strictly with the record
+};

@@ -31,6 +31,7 @@
 #include "yabpe_decode_kernels.h"
 #include "yabpe_layout_kernels.h"
 #include "yabpe_fit_kernels.h"
+#include "yabpe_fitlab_kernels.h"
 #include "yabpe_mask_kernels.h"
 #include "yabpe_span_kernels.h"
 #include "yabpe_fim_kernels.h"
@@ -110,7 +111,7 @@ struct EventPair {
 // The slots of yabpe_ctx::lay_buf, u32 arrays unless said otherwise.  yabpe_layout_pad: ROWS, ROW_DOC (the kept lengths);
 // yabpe_layout_pack: ROWS, ROW_DOC, ROW_START (ids, doc, pos: a slot each); yabpe_layout_windows: ROWS .. ROW_LEN, SPANS;
 // yabpe_layout_pairs: all seven (ROW_DOC = row_pair, ROW_LEN = first_len); yabpe_layout_fit: ROWS, ROW_DOC, ROW_START (ids, doc,
-// pos: a slot each) and ROW_LEN (used).
+// pos: a slot each) and ROW_LEN (used); yabpe_layout_fit_labels: those four (ROW_DOC = seq) and the last four.
 enum LayBuf {
     LB_ROWS,        // the ids of every output slot
     LB_ROW_DOC,     // per row: the document (pair) it comes from
@@ -119,6 +120,10 @@ enum LayBuf {
     LB_SPANS,       // with spans: a (start, end) u64 pair per output slot
     LB_SECOND_LEN,  // per row: the ids it keeps of the second side
     LB_TYPES,       // a byte per output slot
+    LB_LABELS,      // the label of every output slot
+    LB_LABELLED,    // per row: the slots whose label is not `ignore`
+    LB_PLACED,      // per placed sequence: (seq, col, len)
+    LB_ROW_FIRST,   // per row, and one more: its first placed sequence
     LB_COUNT
 };
 
@@ -4658,6 +4663,171 @@ int yabpe_layout_fit(yabpe_ctx *c, const uint32_t *ids, uint64_t n_ids, const ui
     out->pos = c->lay_buf[LB_ROW_START];
     out->used = c->lay_buf[LB_ROW_LEN];
     out->n_rows = n_rows;
+    return YABPE_OK;
+}
+
+// BBPETokenizer.fit_labelled on the device (yabpe_fitlab_kernels.h; the rules: fit_logic.h).  The lengths, the sort and the plan
+// are yabpe_layout_fit's; lay_ev[0..1] bracket lengths + histogram + sort, [2..3] the places and the write.  Until the kernels have
+// run everything lives in the call's Scratch, the results included: a call that is refused has freed nothing, and the previous
+// results stay valid.
+int yabpe_layout_fit_labels(yabpe_ctx *c, const uint32_t *ids, const uint32_t *labels, uint64_t n_ids, const uint64_t *seq_off, uint32_t n_seqs,
+                            const yabpe_fit_labels_t *opt, yabpe_fit_label_rows_t *out) {
+    if (!c || !out) return YABPE_E_INVALID;
+    HIPCHK(c, hipSetDevice(c->device));
+    *out = yabpe_fit_label_rows_t{};
+    if (!opt) return fail(c, YABPE_E_INVALID, "the options are NULL");
+    if (opt->flags & ~FITL_FLAGS) return fail(c, YABPE_E_INVALID, "unknown flags 0x%x (the call takes 0x%x)", opt->flags & ~FITL_FLAGS, FITL_FLAGS);
+    if (opt->row_len == 0) return fail(c, YABPE_E_INVALID, "row_len is 0: a row holds at least one slot");
+    if (opt->row_len > FIT_MAX_ROW) return fail(c, YABPE_E_INVALID, "row_len %u: at most 2^24 - 1 slots a row", opt->row_len);
+    if (n_ids && (!ids || !labels)) return fail(c, YABPE_E_INVALID, "ids or labels is NULL");
+    if (!seq_off && n_seqs > 1) return fail(c, YABPE_E_INVALID, "seq_off is NULL with %u sequences", n_seqs);
+    const uint32_t C = opt->row_len;
+    auto reset_stats = [&] {
+        c->lay_stats = yabpe_layout_stats_t{};
+        c->lay_stats.n_ids = n_ids;
+        c->lay_stats.n_docs = n_seqs;
+        c->lay_stats.row_len = C;
+    };
+    if (n_seqs == 0) {  // no sequences: no rows
+        yabpe_layout_free(c);
+        reset_stats();
+        return YABPE_OK;
+    }
+    const bool off_dev = seq_off && is_device_ptr(seq_off);
+    std::vector<uint64_t> h_off(n_seqs, 0);
+    if (seq_off) {
+        if (off_dev) HIPCHK(c, hipMemcpy(h_off.data(), seq_off, (size_t)n_seqs * 8, hipMemcpyDeviceToHost));
+        else memcpy(h_off.data(), seq_off, (size_t)n_seqs * 8);
+    }
+    TRY(check_starts(c, h_off.data(), n_seqs, n_ids, "ids"));
+    for (auto &e : c->lay_ev)
+        if (!e) HIPCHK(c, hipEventCreate(&e));
+    hipStream_t s = c->stream;
+    Scratch S(c->device, c->rank);
+    FitlParams P{};
+    P.n_seqs = n_seqs;
+    P.n_ids = n_ids;
+    P.C = C;
+    P.flags = opt->flags;
+    P.pad_id = opt->pad_id;
+    P.ignore = opt->ignore;
+    TRY(to_device(c, S, ids, n_ids * 4, 16, &P.ids));  // (the write pass loads 16 bytes where a source run allows)
+    TRY(to_device(c, S, labels, n_ids * 4, 16, &P.labels));
+    TRY(to_device(c, S, off_dev ? (const unsigned long long *)seq_off : (const unsigned long long *)h_off.data(), (uint64_t)n_seqs * 8, 8, &P.seq_off));
+    auto hip_fail = [&](const char *what, hipError_t e) {  // (the stream is drained first: Scratch hands its buffers back)
+        (void)hipStreamSynchronize(s);
+        return fail(c, YABPE_E_HIP, "%s failed: %s", what, hipGetErrorString(e));
+    };
+    hipError_t e = hipSuccess;
+    // ---- lengths: the key n_s of every sequence, their histogram, the call's counters; then the sequences stably by key
+    uint32_t *key = nullptr, *hist = nullptr;
+    unsigned long long *counters = nullptr, h_cnt[4] = {0, 0, 0, 0};
+    HIPCHK(c, S.get(&key, n_seqs));
+    HIPCHK(c, S.get(&hist, (uint64_t)C + 1));
+    HIPCHK(c, S.get(&counters, 4));
+    std::vector<uint32_t> h_hist((size_t)C + 1, 0);
+    HIPCHK(c, hipEventRecord(c->lay_ev[0], s));
+    if ((e = hipMemsetAsync(counters, 0, 32, s)) != hipSuccess) return hip_fail("the counter reset", e);
+    if ((e = hipMemsetAsync(hist, 0, ((size_t)C + 1) * 4, s)) != hipSuccess) return hip_fail("the histogram reset", e);
+    const FitLenParams LP{P.seq_off, n_seqs, n_ids, C, 0u, key, hist, counters};  // (no BOS, no EOS: n_s = min(len, C))
+    if (C < (uint32_t)FIT_HIST_LDS)
+        hipLaunchKernelGGL(k_fit_lengths<true>, dim3(cdiv64(n_seqs, BLOCK)), dim3(BLOCK), 0, s, LP);
+    else
+        hipLaunchKernelGGL(k_fit_lengths<false>, dim3(cdiv64(n_seqs, BLOCK)), dim3(BLOCK), 0, s, LP);
+    if ((e = hipGetLastError()) != hipSuccess) return hip_fail("k_fit_lengths", e);
+    (void)hipMemcpyAsync(h_hist.data(), hist, ((size_t)C + 1) * 4, hipMemcpyDeviceToHost, s);
+    (void)hipMemcpyAsync(h_cnt, counters, 32, hipMemcpyDeviceToHost, s);
+    if ((e = hipStreamSynchronize(s)) != hipSuccess) return hip_fail("the lengths pass", e);
+    const uint32_t max_key = (uint32_t)std::min<unsigned long long>(h_cnt[0], C);  // 0: every sequence is empty, no rows
+    if (max_key && fit_sort(c, S, s, key, n_seqs, fit_sort_passes(max_key), &P.sorted_seq) != 0) {
+        (void)hipStreamSynchronize(s);
+        return YABPE_E_HIP;
+    }
+    (void)hipEventRecord(c->lay_ev[1], s);
+    // ---- plan (host, beside the sort): histogram -> shapes, rows, places, first records
+    FitPlan plan;
+    std::vector<uint32_t> base;
+    if (max_key) fit_plan(h_hist.data(), C, &plan);
+    if (plan.n_rows > LAY_MAX_SLOTS / C) {
+        (void)hipStreamSynchronize(s);
+        return fail(c, YABPE_E_CAPACITY, "%llu rows of %u slots: at most 2^36 slots in one call", plan.n_rows, C);
+    }
+    P.n_rows = plan.n_rows;
+    P.n_slots = plan.n_rows * C;
+    if (P.n_rows) {
+        fitl_record_base(plan, &base);
+        P.n_shapes = plan.n_shapes();
+        P.n_placed = base.back();
+        unsigned long long *d_first = nullptr;
+        uint32_t *d_place = nullptr, *d_base = nullptr;
+        FitPlace *d_pl = nullptr;
+        HIPCHK(c, S.get(&d_first, plan.first.size()));
+        HIPCHK(c, S.get(&d_place, plan.place.size()));
+        HIPCHK(c, S.get(&d_base, base.size()));
+        HIPCHK(c, S.get(&d_pl, plan.pl.size()));
+        (void)hipMemcpyAsync(d_first, plan.first.data(), plan.first.size() * sizeof(unsigned long long), hipMemcpyHostToDevice, s);
+        (void)hipMemcpyAsync(d_place, plan.place.data(), plan.place.size() * sizeof(uint32_t), hipMemcpyHostToDevice, s);
+        (void)hipMemcpyAsync(d_base, base.data(), base.size() * sizeof(uint32_t), hipMemcpyHostToDevice, s);
+        if ((e = hipMemcpyAsync(d_pl, plan.pl.data(), plan.pl.size() * sizeof(FitPlace), hipMemcpyHostToDevice, s)) != hipSuccess)
+            return hip_fail("the copy of the plan", e);
+        P.first = d_first;
+        P.place = d_place;
+        P.base = d_base;
+        P.pl = d_pl;
+    }
+    // ---- places + write: every error has been found; the results are the call's own until the kernels have run
+    HIPCHK(c, S.get(&P.rec, P.n_placed));
+    HIPCHK(c, S.get(&P.rec2, P.n_placed));
+    uint32_t *res[LB_COUNT] = {};
+    const std::pair<int, uint64_t> want[] = {{LB_ROWS, P.n_slots},    {LB_LABELS, P.n_slots},  {LB_ROW_DOC, P.n_slots},
+                                             {LB_ROW_START, P.n_slots}, {LB_ROW_LEN, P.n_rows},  {LB_LABELLED, P.n_rows},
+                                             {LB_PLACED, 3ull * P.n_placed}, {LB_ROW_FIRST, P.n_rows + 1}};
+    for (auto &w : want) {
+        if (dmalloc(c, &res[w.first], w.second) != 0) {
+            (void)hipStreamSynchronize(s);
+            return YABPE_E_HIP;
+        }
+        S.adopt(res[w.first]);
+    }
+    P.out_ids = res[LB_ROWS];
+    P.out_labels = res[LB_LABELS];
+    P.out_seq = res[LB_ROW_DOC];
+    P.out_pos = res[LB_ROW_START];
+    P.used = res[LB_ROW_LEN];
+    P.labelled = res[LB_LABELLED];
+    P.placed = res[LB_PLACED];
+    P.row_first = res[LB_ROW_FIRST];
+    (void)hipEventRecord(c->lay_ev[2], s);
+    hipLaunchKernelGGL(k_fitl_places, dim3(cdiv64(std::max<uint64_t>(P.n_placed, 1), FITL_BLOCK)), dim3(FITL_BLOCK), 0, s, P);
+    if ((e = hipGetLastError()) != hipSuccess) return hip_fail("k_fitl_places", e);
+    if (P.n_slots) {
+        hipLaunchKernelGGL(k_fitl_write, dim3(cdiv64(P.n_slots, FITL_TILE)), dim3(FITL_BLOCK), 0, s, P);
+        if ((e = hipGetLastError()) != hipSuccess) return hip_fail("k_fitl_write", e);
+    }
+    (void)hipEventRecord(c->lay_ev[3], s);
+    if ((e = hipStreamSynchronize(s)) != hipSuccess) return hip_fail("the write pass", e);
+    yabpe_layout_free(c);  // the previous results go, this call's take their place
+    for (auto &w : want) c->lay_buf[w.first] = S.take(res[w.first]);
+    reset_stats();
+    float ms[3] = {0, 0, 0};
+    auto &st = c->lay_stats;
+    st.total_ms = pass_times(c->lay_ev, 3, ms);
+    st.lengths_ms = ms[0];
+    st.write_ms = ms[2];
+    st.n_rows = P.n_rows;
+    st.n_truncated_docs = h_cnt[1];
+    st.n_ids_dropped = h_cnt[2];
+    st.n_pad_slots = P.n_slots - h_cnt[3];
+    out->ids = res[LB_ROWS];
+    out->labels = res[LB_LABELS];
+    out->seq = res[LB_ROW_DOC];
+    out->pos = res[LB_ROW_START];
+    out->used = res[LB_ROW_LEN];
+    out->labelled = res[LB_LABELLED];
+    out->placed = res[LB_PLACED];
+    out->row_first = res[LB_ROW_FIRST];
+    out->n_rows = P.n_rows;
+    out->n_placed = P.n_placed;
     return YABPE_OK;
 }
 

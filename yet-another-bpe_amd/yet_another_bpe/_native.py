@@ -145,6 +145,17 @@ class FitRows(ctypes.Structure):
     _fields_ = [(n, c_void_p) for n in ("ids", "doc", "pos", "used")] + [("n_rows", c_uint64)]
 
 
+class FitLabels(ctypes.Structure):
+    """yabpe_fit_labels_t"""
+    _fields_ = [(n, c_uint32) for n in ("row_len", "pad_id", "ignore", "flags")]
+
+
+class FitLabelRows(ctypes.Structure):
+    """yabpe_fit_label_rows_t"""
+    _fields_ = [(n, c_void_p) for n in ("ids", "labels", "seq", "pos", "used", "labelled", "placed", "row_first")] + [
+        (n, c_uint64) for n in ("n_rows", "n_placed")]
+
+
 class ResumeStats(ctypes.Structure):
     _fields_ = [(n, c_uint64) for n in ("n_unique", "n_long", "tokens")] + [(n, c_double) for n in ("segment_ms", "build_ms")]
 
@@ -188,7 +199,7 @@ SYMBOLS = [
     "yabpe_encode_set_model", "yabpe_encode", "yabpe_encode_spans", "yabpe_encode_dropout", "yabpe_encode_words", "yabpe_encode_free", "yabpe_encode_stats", "yabpe_encode_checksum",
     "yabpe_decode_set_model", "yabpe_decode", "yabpe_decode_free", "yabpe_decode_stats",
     "yabpe_load_words_resumed", "yabpe_resume_stats",
-    "yabpe_layout_pad", "yabpe_layout_pack", "yabpe_layout_windows", "yabpe_layout_pairs", "yabpe_layout_fit", "yabpe_layout_free", "yabpe_layout_stats",
+    "yabpe_layout_pad", "yabpe_layout_pack", "yabpe_layout_windows", "yabpe_layout_pairs", "yabpe_layout_fit", "yabpe_layout_fit_labels", "yabpe_layout_free", "yabpe_layout_stats",
     "yabpe_mask", "yabpe_mask_free", "yabpe_mask_stats",
     "yabpe_span_corrupt", "yabpe_span_free", "yabpe_span_stats",
     "yabpe_fim_cuts", "yabpe_fim", "yabpe_fim_free", "yabpe_fim_stats",
@@ -267,6 +278,7 @@ def lib() -> ctypes.CDLL:
         L.yabpe_layout_windows.argtypes = [c_void_p, c_void_p, c_uint64, c_void_p, c_uint32, c_void_p, POINTER(Layout), c_uint32, POINTER(Windows)]
         L.yabpe_layout_pairs.argtypes = [c_void_p, c_void_p, c_uint64, c_void_p, c_uint32, c_void_p, POINTER(Layout), POINTER(Pairs), POINTER(PairRows)]
         L.yabpe_layout_fit.argtypes = [c_void_p, c_void_p, c_uint64, c_void_p, c_uint32, POINTER(Layout), POINTER(FitRows)]
+        L.yabpe_layout_fit_labels.argtypes = [c_void_p, c_void_p, c_void_p, c_uint64, c_void_p, c_uint32, POINTER(FitLabels), POINTER(FitLabelRows)]
         L.yabpe_layout_free.argtypes = [c_void_p]
         L.yabpe_layout_stats.argtypes = [c_void_p, POINTER(LayoutStats)]
         L.yabpe_mask.argtypes = [c_void_p, c_void_p, c_uint64, c_void_p, c_uint32, c_void_p, POINTER(Mask), POINTER(c_void_p), POINTER(c_void_p)]
@@ -320,6 +332,8 @@ FIM_EOT, FIM_LOSS_MIDDLE, FIM_PIECES = 0x1, 0x2, 0x4  # yabpe_fim_t.flags
 CHAT_LOSS_ALL, CHAT_LOSS_LAST, CHAT_DROP_OLDEST, CHAT_PIN_FIRST, CHAT_GEN_PROMPT = 0x01, 0x02, 0x04, 0x08, 0x10  # yabpe_chat_t.flags
 CHAT_MAX_ROLES, CHAT_MAX_TEMPLATE_IDS = 16, 2048  # YABPE_CHAT_MAX_ROLES, YABPE_CHAT_MAX_TEMPLATE_IDS
 CHAT_TILE, CHAT_STAGE = 1024, 256  # chat_logic.h: output slots a workgroup of the write pass owns, turn records it stages at a time
+FITL_SHIFTED, FITL_MASK_FIRST = 0x1, 0x2  # yabpe_fit_labels_t.flags
+FITL_TILE, FITL_STAGE = 1024, 256  # fit_logic.h: output slots a workgroup of the labelled write pass owns, records it stages at a time
 PAIRS_MODES = {"longest_first": 0, "only_first": 1, "only_second": 2, "windows": 3}  # yabpe_pairs_t.mode (YABPE_PAIRS_*)
 
 
@@ -335,6 +349,16 @@ def _text_arg(text, n_bytes):
 def _starts_arg(starts) -> np.ndarray:
     """Ascending chunk / part / document starts as the u64 table a driver takes (None or empty: one, at 0)"""
     return np.ascontiguousarray(starts if starts is not None and len(starts) else [0], dtype=np.uint64)
+
+
+def _u32_words(labels) -> np.ndarray:
+    """labels as the u32 words a driver takes: an i32 array (-100 is the ignore word) keeps its bits"""
+    a = np.ascontiguousarray(labels)
+    if a.dtype == np.int32:
+        return a.view(np.uint32)
+    if a.dtype == np.uint32:
+        return a
+    return (np.asarray(a, dtype=np.int64) & 0xFFFFFFFF).astype(np.uint32)
 
 
 def _stats_dict(s: ctypes.Structure) -> dict:
@@ -924,6 +948,47 @@ class Context:
         di, dd, dp, du, nr = self.layout_fit(ids, n_ids, doc_starts, n_docs, **kw)
         rl = int(kw.get("row_len", 0))
         return tuple(self._rows_to_host(p, nr, rl) for p in (di, dd, dp)) + (self._rows_to_host(du, nr),)
+
+    def layout_fit_labels(self, ids, labels, n_ids: int | None = None, seq_starts=None, n_seqs: int | None = None, row_len: int = 0,
+                          pad_id: int = 0, ignore: int = MASK_IGNORE, shifted: bool = False, mask_first: bool = False, flags: int = 0):
+        """Labelled sequences whole in rows of row_len (yabpe_layout_fit_labels).  ids / labels: u32 arrays of one length
+        (staged; labels may be i32) or device addresses (n_ids required); seq_starts: the ascending sequence starts, the first
+        one 0, as an array (empty: no sequences) or a device address with n_seqs -- what fim() and chat() return goes straight in.
+        -> a dict of device addresses ids, labels, seq, pos (u32[n_rows * row_len] each), used, labelled (u32[n_rows]), placed
+        (u32[n_placed, 3]), row_first (u32[n_rows + 1]) and the counts n_rows, n_placed; the buffers live until the next layout
+        call, layout_free() or close()."""
+        if isinstance(ids, int) != isinstance(labels, int):
+            raise ValueError("ids and labels must both be arrays or both be device addresses")
+        if isinstance(ids, int):
+            keep, iptr, lptr, n = None, c_void_p(ids), c_void_p(labels), int(n_ids)
+        else:
+            keep = (np.ascontiguousarray(ids, dtype=np.uint32), _u32_words(labels))
+            if keep[0].size != keep[1].size:
+                raise ValueError(f"{keep[0].size} ids and {keep[1].size} labels: one label per id")
+            n = int(keep[0].size)
+            iptr, lptr = (c_void_p(a.ctypes.data if n else 0) for a in keep)
+        if isinstance(seq_starts, int):
+            _starts, sptr, ns = None, c_void_p(seq_starts), int(n_seqs)
+        else:
+            _starts = np.ascontiguousarray(seq_starts if seq_starts is not None else [0], dtype=np.uint64)
+            sptr, ns = c_void_p(_starts.ctypes.data if _starts.size else 0), len(_starts)
+        opt = FitLabels(int(row_len), int(pad_id), int(ignore) & 0xFFFFFFFF,
+                        int(flags) | (FITL_SHIFTED if shifted else 0) | (FITL_MASK_FIRST if mask_first else 0))
+        w = FitLabelRows()
+        self._chk(lib().yabpe_layout_fit_labels(self._h, iptr, lptr, n, sptr, ns, byref(opt), byref(w)))
+        return {f: getattr(w, f) or 0 for f, _ in w._fields_}
+
+    def layout_fit_labels_to_host(self, ids, labels, n_ids: int | None = None, seq_starts=None, n_seqs: int | None = None, **kw):
+        """-> a dict: ids, seq, pos u32[n_rows, row_len], labels i32[n_rows, row_len], used, labelled u32[n_rows], placed
+        u32[n_placed, 3], row_first u32[n_rows + 1], copied to the host."""
+        w = self.layout_fit_labels(ids, labels, n_ids, seq_starts, n_seqs, **kw)
+        nr, rl = w["n_rows"], int(kw.get("row_len", 0))
+        out = {k: self._rows_to_host(w[k], nr, rl) for k in ("ids", "labels", "seq", "pos")}
+        out["labels"] = out["labels"].view(np.int32)
+        out.update({k: self._rows_to_host(w[k], nr) for k in ("used", "labelled")})
+        out["placed"] = self._rows_to_host(w["placed"], w["n_placed"], 3)
+        out["row_first"] = self._rows_to_host(w["row_first"], nr + 1) if w["row_first"] else np.zeros(1, np.uint32)
+        return out
 
     def layout_free(self) -> None:
         self._chk(lib().yabpe_layout_free(self._h))

@@ -14,10 +14,13 @@ forms take dropout= and seed=.  encode_with_words also says which piece of its d
 draws a seeded masked-language-model mask over such ids, encode_batch_masked lays both out as padded rows;
 encode_array_with_words / mask_array / encode_array_masked compute the same on the GPU (yabpe_encode_words, yabpe_mask).
 chat_tokens / encode_batch_chat write conversations through a ChatTemplate with labels on the assistant's turns;
-chat_array / encode_array_chat compute the same on the GPU (yabpe_chat).
+chat_array / encode_array_chat compute the same on the GPU (yabpe_chat).  fit_labelled / encode_batch_chat_fit pack such
+labelled sequences whole into rows, several a row, with the seam records a varlen attention kernel needs; fit_labelled_array /
+encode_array_chat_fit compute the same on the GPU (yabpe_layout_fit_labels).
 """
 from __future__ import annotations
 
+import itertools
 import json
 import numbers
 import operator
@@ -1015,29 +1018,13 @@ class BBPETokenizer:
         cut = lambda flat, filler: [(flat + [filler] * fill)[r * seq_len:(r + 1) * seq_len] for r in range(n_rows)]  # noqa: E731
         return cut(stream, pad), cut(doc, 0xFFFFFFFF), cut(pos, 0)
 
-    def encode_batch_fit(self, texts: Sequence[str], seq_len: int, *, pad_id: int | None = None, bos_id: int | None = None,
-                         eos_id: int | None = None, dropout: float = 0.0,
-                         seed: int = 0) -> tuple[list[list[int]], list[list[int]], list[list[int]], list[int]]:
-        """Whole documents in rows of C = seq_len slots, packed by best-fit decreasing: no seq(d) = [bos_id] + encode(texts[d]) +
-        [eos_id] is cut across two rows -> (ids, doc, pos, used).  A seq longer than C loses content ids from its end (BOS and
-        EOS survive, as in encode_batch_padded); n_d = its length after that; a document with n_d == 0 is in no row.
-        Plan, on H[k] = the documents with n_d == k: the state maps a shape -- the lengths of a row's sequences in placement
-        order, non-increasing, room = C - their sum -- to the rows that have it.  For k = C .. 1 with n = H[k] sequences left:
-        among the shapes with a row left and room >= k the one with the smallest room, of several the greatest tuple; t = room
-        // k; min(rows, n // t) of its rows take t sequences each, then, if rows of it and sequences remain, one more row takes
-        the rest; with no such shape n // t rows of t = C // k sequences open and one row of the n % t left.
-        Rows: the shapes in descending tuple order, the rows of a shape consecutive; a row holds its sequences end to end from
-        column 0.  For every k the documents with n_d == k, in ascending d, take the places of length k in row order, within a
-        row left to right.  doc and pos are encode_batch_packed's; pad slots hold pad_id, 0xFFFFFFFF and 0; used[r] = the filled
-        slots of row r.  dropout > 0: the content ids are encode_batch_dropout(texts, dropout, seed)."""
-        pad, bos, eos, added = self._layout_ids(pad_id, bos_id, eos_id)
-        C = self._row_length(seq_len, "seq_len", max(1, added))
-        seqs = []
-        for ids in self._encode_batch_for_layout(texts, dropout, seed):
-            seqs.append(([bos] if bos is not None else []) + ids[:max(0, C - added)] + ([eos] if eos is not None else []))
+    @staticmethod
+    def _fit_rows(lengths: Sequence[int], C: int) -> list[list[int]]:
+        """The plan encode_batch_fit and fit_labelled share: the lengths n_d (each at most C) -> the rows, each the indices of its
+        sequences from left to right (encode_batch_fit's docstring states the rule)."""
         by_len: dict[int, list[int]] = {}
-        for d, seq in enumerate(seqs):
-            by_len.setdefault(len(seq), []).append(d)
+        for d, n in enumerate(lengths):
+            by_len.setdefault(n, []).append(d)
         count: dict[tuple, int] = {}  # shape -> rows
 
         def move(src, dst, m):
@@ -1070,7 +1057,29 @@ class BBPETokenizer:
                     n = 0
         shapes = [s for s in sorted(count, reverse=True) for _ in range(count[s])]
         taken = {k: iter(docs) for k, docs in by_len.items()}  # the next document of every length
-        rows = [[next(taken[k]) for k in s] for s in shapes]
+        return [[next(taken[k]) for k in s] for s in shapes]
+
+    def encode_batch_fit(self, texts: Sequence[str], seq_len: int, *, pad_id: int | None = None, bos_id: int | None = None,
+                         eos_id: int | None = None, dropout: float = 0.0,
+                         seed: int = 0) -> tuple[list[list[int]], list[list[int]], list[list[int]], list[int]]:
+        """Whole documents in rows of C = seq_len slots, packed by best-fit decreasing: no seq(d) = [bos_id] + encode(texts[d]) +
+        [eos_id] is cut across two rows -> (ids, doc, pos, used).  A seq longer than C loses content ids from its end (BOS and
+        EOS survive, as in encode_batch_padded); n_d = its length after that; a document with n_d == 0 is in no row.
+        Plan, on H[k] = the documents with n_d == k: the state maps a shape -- the lengths of a row's sequences in placement
+        order, non-increasing, room = C - their sum -- to the rows that have it.  For k = C .. 1 with n = H[k] sequences left:
+        among the shapes with a row left and room >= k the one with the smallest room, of several the greatest tuple; t = room
+        // k; min(rows, n // t) of its rows take t sequences each, then, if rows of it and sequences remain, one more row takes
+        the rest; with no such shape n // t rows of t = C // k sequences open and one row of the n % t left.
+        Rows: the shapes in descending tuple order, the rows of a shape consecutive; a row holds its sequences end to end from
+        column 0.  For every k the documents with n_d == k, in ascending d, take the places of length k in row order, within a
+        row left to right.  doc and pos are encode_batch_packed's; pad slots hold pad_id, 0xFFFFFFFF and 0; used[r] = the filled
+        slots of row r.  dropout > 0: the content ids are encode_batch_dropout(texts, dropout, seed)."""
+        pad, bos, eos, added = self._layout_ids(pad_id, bos_id, eos_id)
+        C = self._row_length(seq_len, "seq_len", max(1, added))
+        seqs = []
+        for ids in self._encode_batch_for_layout(texts, dropout, seed):
+            seqs.append(([bos] if bos is not None else []) + ids[:max(0, C - added)] + ([eos] if eos is not None else []))
+        rows = self._fit_rows([len(seq) for seq in seqs], C)
         out_ids, out_doc, out_pos, used = [], [], [], []
         for row in rows:
             fill = C - sum(len(seqs[d]) for d in row)
@@ -1079,6 +1088,88 @@ class BBPETokenizer:
             out_pos.append([p for d in row for p in range(len(seqs[d]))] + [0] * fill)
             used.append(C - fill)
         return out_ids, out_doc, out_pos, used
+
+    FIT_MAX_ROW = (1 << 24) - 1  # the longest row of the whole-sequence packs (fit_logic.h)
+
+    def _fit_label_args(self, seq_len, pad_id, ignore, labels, mask_first) -> tuple[int, int, int, bool, bool]:
+        """-> (C, pad id, ignore, shifted, mask_first), validated as yabpe_layout_fit_labels validates them"""
+        pad, _bos, _eos, _added = self._layout_ids(pad_id, None, None)
+        C = self._row_length(seq_len, "seq_len", 1)
+        if C > self.FIT_MAX_ROW:
+            raise ValueError(f"seq_len must be at most {self.FIT_MAX_ROW}, not {C}")
+        if labels not in ("shifted", "aligned"):
+            raise ValueError(f"labels must be 'shifted' or 'aligned', not {labels!r}")
+        try:
+            ignore = operator.index(ignore)
+        except TypeError:
+            raise ValueError(f"ignore must be an integer, not {ignore!r}") from None
+        if not -(1 << 31) <= ignore < 1 << 31:
+            raise ValueError(f"ignore must fit 32 signed bits, not {ignore}")
+        return C, pad, ignore, labels == "shifted", bool(mask_first)
+
+    def fit_labelled(self, ids_batch, labels_batch, seq_len: int, *, pad_id: int | None = None, ignore: int = -100, labels: str = "shifted",
+                     mask_first: bool = True) -> dict:
+        """Labelled sequences (what mask_tokens, corrupt_spans, fim_tokens and chat_tokens return) packed whole into rows of C =
+        seq_len slots, several a row, for supervised fine-tuning with position ids that restart and attention cut at the seams.
+        A sequence longer than C loses ids and labels from its right end, n_s = min(len, C); nothing is added (the sequences
+        carry their own BOS, EOS and sentinels); a sequence with n_s == 0 is in no row.  Rows, shapes and dealing are exactly
+        encode_batch_fit's on the lengths n_s.
+        Per slot of sequence s at position p: ids[s][p], seq = s, pos = p, and the label -- labels "aligned": labels[s][p], but
+        `ignore` at p == 0 with mask_first (the first id of a sequence is not predicted from the last id of the one in front);
+        "shifted": labels[s][p + 1] if p + 1 < n_s, else `ignore` -- the target of the slot, never taken across a seam and never
+        an id the row does not hold; mask_first has no effect then.  Pad slots hold pad_id, ignore, 0xFFFFFFFF and 0.
+        -> a dict: ids, labels, seq, pos (rows of C), used[r] = the filled slots of row r, labelled[r] = its slots whose label is
+        not `ignore` (a loss averaged per token needs it), placed = the record (seq, col, len) of every placed sequence in row
+        order, left to right within a row, row_first[r] = the first record of row r, with len(placed) behind the last row:
+        cu_seqlens of any set of rows is r * C + col, max_seqlen the largest len."""
+        C, pad, ignore, shifted, mask_first = self._fit_label_args(seq_len, pad_id, ignore, labels, mask_first)
+        if len(ids_batch) != len(labels_batch) or any(len(a) != len(b) for a, b in zip(ids_batch, labels_batch)):
+            raise ValueError("labels_batch must hold one label per id of ids_batch")
+        seqs = [[int(t) for t in ids[:C]] for ids in ids_batch]
+        labs = []
+        for lab in labels_batch:
+            lab = [int(t) for t in lab[:C]]
+            if shifted:
+                lab = lab[1:] + [ignore] * bool(lab)
+            elif mask_first and lab:
+                lab[0] = ignore
+            labs.append(lab)
+        out = {k: [] for k in ("ids", "labels", "seq", "pos", "used", "labelled", "placed", "row_first")}
+        for row in self._fit_rows([len(seq) for seq in seqs], C):
+            fill = C - sum(len(seqs[s]) for s in row)
+            out["row_first"].append(len(out["placed"]))
+            out["placed"] += [(s, col, len(seqs[s])) for s, col in zip(row, itertools.accumulate([0] + [len(seqs[s]) for s in row]))]
+            out["ids"].append([t for s in row for t in seqs[s]] + [pad] * fill)
+            out["labels"].append([t for s in row for t in labs[s]] + [ignore] * fill)
+            out["seq"].append([s for s in row for _ in seqs[s]] + [0xFFFFFFFF] * fill)
+            out["pos"].append([p for s in row for p in range(len(seqs[s]))] + [0] * fill)
+            out["used"].append(C - fill)
+            out["labelled"].append(C - out["labels"][-1].count(ignore))
+        out["row_first"].append(len(out["placed"]))
+        return out
+
+    def encode_batch_chat_fit(self, conversations, seq_len: int, *, template: ChatTemplate = CHATML, train_roles=("assistant",),
+                              loss: str = "roles", truncation: str = "drop_oldest", pin_first: bool = True, pin_roles=None,
+                              add_generation_prompt: bool = False, pad_id: int | None = None, labels: str = "shifted",
+                              mask_first: bool = True) -> dict:
+        """Conversations packed whole for supervised fine-tuning in one call: encode_batch_chat's sequences and labels with
+        max_length = seq_len and neither BOS nor EOS -- so the chat cut shortens a long conversation (whole turns with
+        "drop_oldest"), not the pack's right cut -- then fit_labelled with ignore = -100.
+        -> fit_labelled's dict plus info, chat_tokens' (q, k, ids kept, ids that carry a label) per conversation."""
+        C, pad, ign, _shifted, _first = self._fit_label_args(seq_len, pad_id, self.IGNORE_LABEL, labels, mask_first)
+        A = self._chat_args(template, train_roles, loss, C, truncation, pin_first, pin_roles, add_generation_prompt)
+        roles, contents, sizes = self._chat_turns(conversations)
+        turns = [(self._chat_role(A["names"], r), self.encode(t)) for r, t in zip(roles, contents)]
+        seqs, labs, info, at = [], [], [], 0
+        for n in sizes:
+            seq, lab, inf = self._chat_sequence(turns[at:at + n], A)
+            seqs.append(seq)
+            labs.append(lab)
+            info.append(inf)
+            at += n
+        out = self.fit_labelled(seqs, labs, C, pad_id=pad, ignore=ign, labels=labels, mask_first=mask_first)
+        out["info"] = info
+        return out
 
     def _windows_args(self, max_length, stride, pad_id, bos_id, eos_id, padding_side, offsets, dropout, seed):
         pad, bos, eos, added = self._layout_ids(pad_id, bos_id, eos_id)
@@ -1727,6 +1818,57 @@ class BBPETokenizer:
         ctx = self._device()
         di, dd, ni, _spans = self._device_encode_for_layout(ctx, inp, dropout, seed)
         return ctx.layout_fit_to_host(di, ni, dd, len(inp[1]), row_len=seq_len, pad_id=pad, bos_id=bos, eos_id=eos)
+
+    def fit_labelled_array(self, ids, labels, off, seq_len: int, *, pad_id: int | None = None, ignore: int = -100, labels_form: str = "shifted",
+                           mask_first: bool = True) -> dict:
+        """fit_labelled on the GPU (yabpe_layout_fit_labels), array for array: ids and labels are the ragged sequences back to
+        back (labels as i32 or u32 words), off the n_seqs + 1 ascending offsets from 0 to len(ids) -- what mask_array,
+        corrupt_spans_array, fim_array and chat_array return.  labels_form: fit_labelled's `labels`.
+        -> a dict of arrays: ids, seq, pos np.uint32[n_rows, seq_len], labels np.int32[n_rows, seq_len], used, labelled
+        np.uint32[n_rows], placed np.uint32[n_placed, 3], row_first np.uint32[n_rows + 1]."""
+        C, pad, ignore, shifted, mask_first = self._fit_label_args(seq_len, pad_id, ignore, labels_form, mask_first)
+        ids = np.ascontiguousarray(ids, dtype=np.uint32)
+        off = np.asarray(off, dtype=np.int64)
+        if off.ndim != 1 or len(off) < 1 or off[0] != 0 or off[-1] != len(ids) or np.any(np.diff(off) < 0):
+            raise ValueError("off must be n_seqs + 1 ascending offsets from 0 to len(ids)")
+        if len(labels) != len(ids):
+            raise ValueError(f"{len(ids)} ids and {len(labels)} labels: one label per id")
+        return self._device().layout_fit_labels_to_host(ids, labels, None, off[:-1].astype(np.uint64), None, row_len=C, pad_id=pad, ignore=ignore,
+                                                        shifted=shifted, mask_first=mask_first)
+
+    def encode_array_chat_fit(self, conversations, seq_len: int, *, template: ChatTemplate = CHATML, train_roles=("assistant",),
+                              loss: str = "roles", truncation: str = "drop_oldest", pin_first: bool = True, pin_roles=None,
+                              add_generation_prompt: bool = False, pad_id: int | None = None, labels: str = "shifted",
+                              mask_first: bool = True) -> dict:
+        """encode_batch_chat_fit(conversations, ...), computed on the GPU: one yabpe_encode over the contents of all turns,
+        yabpe_chat on its device results with max_len = seq_len, then yabpe_layout_fit_labels on the sequences, labels and
+        offsets yabpe_chat left on the device (the ragged arrays never visit the host).
+        -> fit_labelled_array's dict plus info np.uint32[n_convs, 4]."""
+        from . import _native
+
+        C, pad, _ign, shifted, mask_first = self._fit_label_args(seq_len, pad_id, self.IGNORE_LABEL, labels, mask_first)
+        A = self._chat_args(template, train_roles, loss, C, truncation, pin_first, pin_roles, add_generation_prompt)
+        roles, contents, sizes = self._chat_turns(conversations)
+        role_idx = self._chat_role_array(A["names"], roles)
+        n_convs = len(sizes)
+        ctx = self._device()
+        pack = {"row_len": C, "pad_id": pad, "ignore": _native.MASK_IGNORE, "shifted": shifted, "mask_first": mask_first}
+        if n_convs == 0:
+            out = ctx.layout_fit_labels_to_host(np.zeros(0, np.uint32), np.zeros(0, np.uint32), None, [], None, **pack)
+            out["info"] = np.zeros((0, 4), np.uint32)
+            return out
+        conv_starts = np.concatenate(([0], np.cumsum(sizes)[:-1])).astype(np.uint64)
+        inp = self._device_input(contents)
+        if inp is None:  # (conversations without turns)
+            di, dd, ni = np.zeros(0, np.uint32), np.zeros(0, np.uint64), None
+        else:
+            text, n_bytes, starts = self._device_text(ctx, inp)
+            di, dd, ni = ctx.encode(text, n_bytes, doc_starts=starts)
+        fi, fl, fo, fn, n_out, _nc = ctx.chat(di, ni, dd, len(contents), conv_starts, None, role_idx, **self._chat_native_args(A))
+        info = ctx.d2h(fn, 16 * n_convs, np.uint32).reshape(n_convs, 4)
+        out = ctx.layout_fit_labels_to_host(fi, fl, n_out, fo, n_convs, **pack)
+        out["info"] = info
+        return out
 
     def encode_array_windows(self, texts, max_length: int, stride: int = 0, *, pad_id: int | None = None, bos_id: int | None = None,
                              eos_id: int | None = None, padding_side: str = "right", offsets: str | None = None,
