@@ -562,6 +562,50 @@ typedef struct yabpe_decode_stats_t {
 } yabpe_decode_stats_t;
 int yabpe_decode_stats(yabpe_ctx *ctx, yabpe_decode_stats_t *out);
 
+/* Decoding id rows (BBPETokenizer.decode_rows / decode_rows_with_offsets on the device) ----------------------------------
+ * ids is a matrix of n_rows rows of row_len ids, as a model hands it back.  Of row r the columns [lo, hi) count, lo =
+ * row_start[r] (NULL: 0), hi = row_end[r] (NULL: row_len); 0 <= lo <= hi <= row_len, anything else on any row:
+ * YABPE_E_INVALID (found on the device, reported before a result is allocated).  The first of them whose id is one of
+ * stop_ids ends the row in front of it (YABPE_DECODE_ROWS_INCLUDE_STOP: behind it); of the columns that remain, those whose id
+ * is one of skip_ids are dropped (the caller lists specials and the pad id there); the rest are the row's kept ids, and its text
+ * is what yabpe_decode makes of them as one document.  At most YABPE_DECODE_ROWS_MAX_STOP stop ids and
+ * YABPE_DECODE_ROWS_MAX_SKIP skip ids (more: YABPE_E_CAPACITY); duplicates are allowed.  opt == NULL: no flags, no ids.
+ * ids, row_start and row_end may be host or device memory.  Results (device memory owned by the library, released by
+ * yabpe_decode_free, the next yabpe_decode / yabpe_decode_rows or yabpe_destroy): *out_dev_text = *out_n_bytes bytes,
+ * *out_dev_text_off = n_rows + 1 offsets into them, *out_dev_kept = the kept ids of every row, and, when out_dev_spans is not
+ * NULL, *out_dev_spans = n_rows * row_len (start, end) pairs in characters (code points) of the row's text: with b = the bytes
+ * of the row's kept tokens in the columns in front of column c, len = those of its own token (0 when it is not kept or the vocab
+ * does not name it) and nchars(x) = the characters errors="replace" makes of the first x bytes of the row's kept tokens, the
+ * pair is (nchars(b), nchars(b + len)) -- (0, 0) in front of the window, (n, n) behind the stop.
+ * n_rows * row_len >= 2^36, or a row whose text has 2^32 - 1 characters or more: YABPE_E_CAPACITY.  No model: YABPE_E_INVALID. */
+#define YABPE_DECODE_ROWS_INCLUDE_STOP 0x1u
+#define YABPE_DECODE_ROWS_MAX_STOP 64u
+#define YABPE_DECODE_ROWS_MAX_SKIP 1024u
+typedef struct yabpe_decode_rows_t {
+    uint32_t flags;
+    uint32_t n_stop;
+    const uint32_t *stop_ids;
+    uint32_t n_skip;
+    const uint32_t *skip_ids;
+} yabpe_decode_rows_t;
+int yabpe_decode_rows(yabpe_ctx *ctx, const uint32_t *ids, uint32_t n_rows, uint32_t row_len, const uint32_t *row_start,
+                      const uint32_t *row_end, const yabpe_decode_rows_t *opt, uint8_t **out_dev_text, uint64_t **out_dev_text_off,
+                      uint64_t *out_n_bytes, uint32_t **out_dev_spans, uint32_t **out_dev_kept);
+/* What the last yabpe_decode_rows saw, and the device time of its phases; the decoder's own passes are in yabpe_decode_stats. */
+typedef struct yabpe_decode_rows_stats_t {
+    uint64_t n_rows, row_len;
+    uint64_t n_kept;           /* ids that went to the decoder */
+    uint64_t n_gathered;       /* bytes of their tokens */
+    uint64_t n_bytes;          /* bytes out */
+    double select_ms;          /* stop search, skip test, per-row counts + their two scans */
+    double compact_ms;         /* kept ids back to back */
+    double decode_ms;          /* yabpe_decode's passes on them (its total_ms, less the two phases below, which run inside it) */
+    double chars_ms;           /* 0 without offsets: character-start mask per text tile + scan */
+    double spans_ms;           /* 0 without offsets: the (start, end) of every column */
+    double total_ms;           /* first to last event, host gaps in between included */
+} yabpe_decode_rows_stats_t;
+int yabpe_decode_rows_stats(yabpe_ctx *ctx, yabpe_decode_rows_stats_t *out);
+
 /* Fixed-shape batches (BBPETokenizer.encode_batch_padded / encode_batch_packed on the device) -----------------------
  * ids and doc_off are taken as yabpe_decode takes them: document d = ids[doc_off[d], doc_off[d + 1]) (the last one ends at
  * n_ids; doc_off[0] = 0, ascending; doc_off == NULL with n_docs <= 1: one document), host or device memory; yabpe_encode's

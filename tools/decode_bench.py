@@ -6,7 +6,10 @@ text written once) over the device time against the 8 TB/s spec HBM peak and aga
 same bytes (half read, half written), timed in the same run (torch copy_ between two HBM buffers, HIP events).  A second line decodes the same ids with 1 %
 of them replaced by single bytes 0x80-0xFF (the repair path).  For comparison, the plain-Python BBPETokenizer.decode on one
 core over a sample of the ids.
-   python tools/decode_bench.py [--mib 1024] [--merges 32000] [--reps 3] [--py-ids 4000000] [--json out.json]"""
+   python tools/decode_bench.py [--mib 1024] [--merges 32000] [--reps 3] [--py-ids 4000000] [--json out.json]
+With --rows B,T: the row decoder (yabpe_decode_rows) on a [B, T] matrix of ids and, in the same run, yabpe_decode on exactly the
+ids it keeps (rows_mode below; profiles/decode_rows_bench.txt).
+   python tools/decode_bench.py --rows 4096,4096 [--reps 3] [--json out.json]"""
 import argparse, json, subprocess, sys, time
 from pathlib import Path
 REPO = Path(__file__).resolve().parent.parent
@@ -24,7 +27,63 @@ ap.add_argument("--merges", type=int, default=32000)
 ap.add_argument("--reps", type=int, default=3)
 ap.add_argument("--py-ids", type=int, default=4_000_000)
 ap.add_argument("--json", default="")
+ap.add_argument("--rows", default="", help="B,T: time yabpe_decode_rows on a [B, T] matrix of ids instead (see rows_mode)")
 a = ap.parse_args()
+
+
+def rows_mode(B: int, T: int, reps: int) -> dict:
+    """yabpe_decode_rows on a [B, T] matrix as a generate loop hands it back: a prompt of up to T/4 ids in front (the window
+    starts behind it), an EOS somewhere in the second half with arbitrary ids behind it, 1 % specials.  Vocab: the 256 bytes,
+    32,000 words of 2 to 8 lower-case letters, 64 two- and three-byte characters.  Device time per phase (HIP events inside
+    the call), best of reps after a warm-up, without and with offsets; and in the same run yabpe_decode on exactly the kept ids,
+    ragged, as the yardstick: the difference is the price of selection (and of offsets)."""
+    rng = np.random.default_rng(5)
+    words = {bytes(rng.integers(97, 123, rng.integers(2, 9)).astype(np.uint8)) for _ in range(40000)}
+    toks = [bytes([b]) for b in range(256)] + sorted(w for w in words if len(w) > 1)[:32000] + [chr(0xE9 + k).encode() for k in range(32)] + [
+        chr(0x4E2D + k).encode() for k in range(32)]
+    vocab = {t: i for i, t in enumerate(toks)}
+    eos, pad, sep = len(toks), len(toks) + 1, len(toks) + 2
+    rows = rng.integers(0, len(toks), (B, T), dtype=np.uint32)
+    rows[rng.random((B, T)) < 0.01] = sep
+    starts = rng.integers(0, T // 4 + 1, B).astype(np.uint32)
+    stop = rng.integers(T // 2, T, B)
+    rows[np.arange(B), stop] = eos
+    col = np.arange(T)[None, :]
+    keep = (col >= starts[:, None]) & (col < stop[:, None]) & (rows != sep) & (rows != pad)
+    kept_ids = rows[keep]
+    kept_off = np.concatenate(([0], np.cumsum(keep.sum(1)))).astype(np.uint64)
+    out = {"B": B, "T": T, "ids": B * T, "kept_ids": int(kept_ids.size)}
+    with _native.Context() as ctx:
+        ctx.decode_set_model(vocab)
+        for name, offsets in (("rows", False), ("rows_with_offsets", True)):
+            runs = []
+            for _ in range(reps + 1):
+                res = ctx.decode_rows(rows, starts=starts, stop_ids=[eos], skip_ids=[pad, sep], offsets=offsets)
+                runs.append({**ctx.decode_rows_stats(), **{"decode_" + k: v for k, v in ctx.decode_stats().items() if k.endswith("_ms")}})
+            kept = ctx.d2h(res[3], 4 * B, np.uint32)
+            assert np.array_equal(kept, keep.sum(1)) and runs[-1]["n_kept"] == kept_ids.size
+            best = min(runs[1:], key=lambda r: r["total_ms"])
+            out[name] = {k: round(v, 4) if isinstance(v, float) else v for k, v in best.items()}
+        runs = []
+        for _ in range(reps + 1):
+            _dt, _do, nb = ctx.decode(kept_ids, doc_starts=kept_off[:-1])
+            runs.append(ctx.decode_stats())
+        assert nb == out["rows"]["n_bytes"]
+        best = min(runs[1:], key=lambda r: r["total_ms"])
+        out["decode_kept_ids"] = {k: round(v, 4) if isinstance(v, float) else v for k, v in best.items()}
+    for name in ("rows", "rows_with_offsets"):
+        out[name]["over_decode_ms"] = round(out[name]["total_ms"] - out["decode_kept_ids"]["total_ms"], 4)
+        out[name]["GB_per_s_ids_in"] = round(4 * B * T / out[name]["total_ms"] / 1e6, 2)
+    return out
+
+
+if a.rows:
+    res = rows_mode(*(int(x) for x in a.rows.split(",")), a.reps)
+    print(json.dumps(res))
+    if a.json:
+        Path(a.json).parent.mkdir(parents=True, exist_ok=True)
+        Path(a.json).write_text(json.dumps(res, indent=1))
+    sys.exit(0)
 
 
 def copy_ms(nbytes: int, reps: int) -> float:

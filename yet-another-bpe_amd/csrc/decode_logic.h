@@ -82,6 +82,18 @@ YB_HD uint32_t dec_out_len(const DecView &v, uint64_t p, uint64_t ds, uint64_t d
     return 3u;
 }
 
+// Character starts (decode_rows_with_offsets).  With data = the bytes of a document and nchars(b) = len(data[:b].decode("utf-8",
+// "replace")), nchars(b) = the number of bytes in [0, b) that start a character of the replace-mode decoding of ALL of data:
+// an ASCII byte, the lead of a well-formed sequence, or the first byte of a maximal ill-formed subpart -- in the charges above,
+// every byte that is no continuation byte, and a continuation byte charged 3.  The decoder is greedy from left to right, so the
+// characters that end at or before b are the same in data[:b] and in data, and a sequence that b cuts off (well-formed in data
+// or not) is a prefix of a maximal subpart whose first byte lies in front of b: data[:b] ends with exactly one U+FFFD for it,
+// the one its first byte already counts.  So a count over any range of the text needs only the role of each byte, which
+// dec_out_len gives from 3 bytes either way.
+YB_HD bool dec_char_start(const DecView &v, uint64_t p, uint64_t ds, uint64_t de) {
+    return !dec_cont(v.T(p)) || dec_out_len(v, p, ds, de) == 3u;
+}
+
 // Writes the bytes dec_out_len charged to p (len = its result) at out.
 YB_HD void dec_emit(uint8_t b, uint32_t len, uint8_t *out) {
     if (len == 1) {

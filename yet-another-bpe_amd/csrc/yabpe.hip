@@ -29,6 +29,7 @@
 #include "yabpe_encode_kernels.h"
 #include "yabpe_dropout_kernels.h"
 #include "yabpe_decode_kernels.h"
+#include "yabpe_decrows_kernels.h"
 #include "yabpe_layout_kernels.h"
 #include "yabpe_fit_kernels.h"
 #include "yabpe_fitlab_kernels.h"
@@ -225,6 +226,10 @@ struct yabpe_ctx {
     unsigned long long *dec_doc = nullptr;
     yabpe_decode_stats_t dec_stats{};
     hipEvent_t dec_ev[7] = {};
+    // id rows (yabpe_decode_rows): its results beside dec_text / dec_doc
+    uint32_t *drow_spans = nullptr, *drow_kept = nullptr;
+    yabpe_decode_rows_stats_t drow_stats{};
+    hipEvent_t drow_ev[8] = {};
     // fixed-shape batches (yabpe_layout_pad / yabpe_layout_pack / yabpe_layout_windows / yabpe_layout_pairs)
     uint32_t *lay_buf[LB_COUNT] = {};         // results of the last layout call, by LayBuf (which says what each call keeps where)
     yabpe_layout_stats_t lay_stats{};
@@ -1921,6 +1926,8 @@ void yabpe_destroy(yabpe_ctx *c) {
     yabpe_decode_free(c);
     dfree(c->dec_ent); dfree(c->dec_pool);
     for (auto &e : c->dec_ev)
+        if (e) (void)hipEventDestroy(e);
+    for (auto &e : c->drow_ev)
         if (e) (void)hipEventDestroy(e);
     yabpe_layout_free(c);
     for (auto &e : c->lay_ev)
@@ -4251,10 +4258,26 @@ int yabpe_decode_free(yabpe_ctx *c) {
     if (!c) return YABPE_E_INVALID;
     dfree(c->dec_text);
     dfree(c->dec_doc);
+    dfree(c->drow_spans);
+    dfree(c->drow_kept);
     c->dec_text = nullptr;
     c->dec_doc = nullptr;
+    c->drow_spans = nullptr;
+    c->drow_kept = nullptr;
     return YABPE_OK;
 }
+
+extern "C++" {
+namespace {
+// The decoder's passes over n_ids > 0 ids on the device (16-B aligned) and the n_docs starts of their documents, for
+// yabpe_decode and yabpe_decode_rows (defined below yabpe_decode).  The caller has freed the last results, reset dec_stats,
+// created dec_ev and allocated c->dec_doc.  after_check(gathered text, its bytes) is called once the text is gathered and
+// checked and before anything is read back or repaired: what it launches runs in the shadow of that read-back.
+template <class Hook>
+int decode_passes(yabpe_ctx *c, Scratch &S, const uint32_t *d_ids, uint64_t n_ids, const unsigned long long *d_docs, uint32_t n_docs,
+                  uint8_t **out_dev_text, uint64_t **out_dev_text_off, uint64_t *out_n_bytes, Hook after_check);
+}  // namespace
+}  // extern "C++"
 
 int yabpe_decode(yabpe_ctx *c, const uint32_t *ids, uint64_t n_ids, const uint64_t *doc_off, uint32_t n_docs, uint8_t **out_dev_text,
                  uint64_t **out_dev_text_off, uint64_t *out_n_bytes) {
@@ -4297,6 +4320,18 @@ int yabpe_decode(yabpe_ctx *c, const uint32_t *ids, uint64_t n_ids, const uint64
         *out_dev_text_off = (uint64_t *)c->dec_doc;
         return YABPE_OK;
     }
+    return decode_passes(c, S, d_ids, n_ids, d_docs, n_docs, out_dev_text, out_dev_text_off, out_n_bytes,
+                         [](const uint8_t *, unsigned long long) { return 0; });
+}
+
+extern "C++" {
+namespace {
+template <class Hook>
+int decode_passes(yabpe_ctx *c, Scratch &S, const uint32_t *d_ids, uint64_t n_ids, const unsigned long long *d_docs, uint32_t n_docs,
+                  uint8_t **out_dev_text, uint64_t **out_dev_text_off, uint64_t *out_n_bytes, Hook after_check) {
+    hipStream_t s = c->stream;
+    const unsigned long long nb = (n_ids + DEC_IPB - 1) / DEC_IPB;
+    if (nb > (1ull << 23)) return fail(c, YABPE_E_CAPACITY, "%llu ids in one call: at most 2^34", (unsigned long long)n_ids);
     const DecTable tab{c->dec_ent, c->dec_n, c->dec_pool};
     // ---- lengths: per-block byte counts -> block output bases
     unsigned long long *bsum = nullptr, *bbase = nullptr, *counters = nullptr;
@@ -4328,6 +4363,7 @@ int yabpe_decode(yabpe_ctx *c, const uint32_t *ids, uint64_t n_ids, const uint64
     if (nt) hipLaunchKernelGGL(k_dec_check, dim3((uint32_t)nt), dim3(BLOCK), 0, s, DecCheckParams{gtext, G, c->dec_doc, n_docs, osum, counters});
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipEventRecord(c->dec_ev[4], s));
+    TRY(after_check(gtext, G));
     unsigned long long h_cnt[2] = {0, 0};
     HIPCHK(c, hipMemcpyAsync(h_cnt, counters, 16, hipMemcpyDeviceToHost, s));
     const hipError_t ce = hipStreamSynchronize(s);
@@ -4390,10 +4426,182 @@ int yabpe_decode(yabpe_ctx *c, const uint32_t *ids, uint64_t n_ids, const uint64
     *out_n_bytes = n_out;
     return YABPE_OK;
 }
+}  // namespace
+}  // extern "C++"
 
 int yabpe_decode_stats(yabpe_ctx *c, yabpe_decode_stats_t *out) {
     if (!c || !out) return YABPE_E_INVALID;
     *out = c->dec_stats;
+    return YABPE_OK;
+}
+
+// ---------------------------------------------------------------------------------------------- decoding id rows
+int yabpe_decode_rows(yabpe_ctx *c, const uint32_t *ids, uint32_t n_rows, uint32_t row_len, const uint32_t *row_start, const uint32_t *row_end,
+                      const yabpe_decode_rows_t *opt, uint8_t **out_dev_text, uint64_t **out_dev_text_off, uint64_t *out_n_bytes,
+                      uint32_t **out_dev_spans, uint32_t **out_dev_kept) {
+    if (!c || !out_dev_text || !out_dev_text_off || !out_n_bytes || !out_dev_kept) return YABPE_E_INVALID;
+    HIPCHK(c, hipSetDevice(c->device));
+    *out_dev_text = nullptr; *out_dev_text_off = nullptr; *out_n_bytes = 0; *out_dev_kept = nullptr;
+    if (out_dev_spans) *out_dev_spans = nullptr;
+    static_assert(YABPE_DECODE_ROWS_INCLUDE_STOP == DROW_INCLUDE_STOP && YABPE_DECODE_ROWS_MAX_STOP == DROW_MAX_STOP &&
+                  YABPE_DECODE_ROWS_MAX_SKIP == DROW_MAX_SKIP, "the header's and the kernels' flags and caps");
+    if (!c->have_dec_model) return fail(c, YABPE_E_INVALID, "no model: call yabpe_decode_set_model first");
+    const unsigned long long n = (unsigned long long)n_rows * row_len;
+    if (n >= (1ull << 36)) return fail(c, YABPE_E_CAPACITY, "%u rows of %u ids: fewer than 2^36 ids in one call", n_rows, row_len);
+    if (n && !ids) return fail(c, YABPE_E_INVALID, "ids is NULL");
+    const uint32_t flags = opt ? opt->flags : 0u, n_stop = opt ? opt->n_stop : 0u, n_skip = opt ? opt->n_skip : 0u;
+    if (flags & ~DROW_INCLUDE_STOP) return fail(c, YABPE_E_INVALID, "flags 0x%x: within 0x%x", flags, DROW_INCLUDE_STOP);
+    if (n_stop > DROW_MAX_STOP || n_skip > DROW_MAX_SKIP)
+        return fail(c, YABPE_E_CAPACITY, "%u stop ids and %u skip ids: at most %u and %u", n_stop, n_skip, DROW_MAX_STOP, DROW_MAX_SKIP);
+    if ((n_stop && !opt->stop_ids) || (n_skip && !opt->skip_ids)) return fail(c, YABPE_E_INVALID, "stop_ids / skip_ids is NULL");
+    // the two lists, each sorted and unique, back to back, and their filters
+    std::vector<uint32_t> h_set;
+    DrowSets sets{};
+    for (int which = 0; which < 2; ++which) {
+        const uint32_t cnt = which ? n_skip : n_stop, *list = !cnt ? nullptr : which ? opt->skip_ids : opt->stop_ids;
+        std::vector<uint32_t> v(list, list + cnt);
+        std::sort(v.begin(), v.end());
+        v.erase(std::unique(v.begin(), v.end()), v.end());
+        unsigned long long f = 0;
+        for (uint32_t id : v) f |= 1ull << (id & 63u);
+        (which ? sets.n_skip : sets.n_stop) = (uint32_t)v.size();
+        (which ? sets.f_skip : sets.f_stop) = f;
+        h_set.insert(h_set.end(), v.begin(), v.end());
+    }
+    yabpe_decode_free(c);
+    c->dec_stats = yabpe_decode_stats_t{};
+    c->drow_stats = yabpe_decode_rows_stats_t{};
+    c->drow_stats.n_rows = n_rows;
+    c->drow_stats.row_len = row_len;
+    for (auto &e : c->dec_ev)
+        if (!e) HIPCHK(c, hipEventCreate(&e));
+    for (auto &e : c->drow_ev)
+        if (!e) HIPCHK(c, hipEventCreate(&e));
+    hipStream_t s = c->stream;
+    Scratch S(c->device, c->rank);
+    // inputs on the device (16-B aligned ids: the kernels load them 4 at a time)
+    const uint32_t *d_ids = nullptr, *d_lo = nullptr, *d_hi = nullptr;
+    TRY(to_device(c, S, ids, n * 4, 16, &d_ids));
+    if (row_start) TRY(to_device(c, S, row_start, (uint64_t)n_rows * 4, 4, &d_lo));
+    if (row_end) TRY(to_device(c, S, row_end, (uint64_t)n_rows * 4, 4, &d_hi));
+    uint32_t *d_set = nullptr, *status = nullptr, *kept = nullptr;
+    uint2 *win = nullptr;
+    unsigned long long *rbytes = nullptr, *koff = nullptr, *rbase = nullptr;
+    HIPCHK(c, S.get(&d_set, h_set.size()));
+    if (!h_set.empty()) HIPCHK(c, hipMemcpy(d_set, h_set.data(), h_set.size() * 4, hipMemcpyHostToDevice));
+    sets.ids = d_set;
+    HIPCHK(c, S.get(&status, 1));
+    HIPCHK(c, S.get(&kept, n_rows));
+    HIPCHK(c, S.get(&win, n_rows));
+    HIPCHK(c, S.get(&rbytes, n_rows));
+    HIPCHK(c, S.get(&koff, (uint64_t)n_rows + 1));
+    HIPCHK(c, S.get(&rbase, (uint64_t)n_rows + 1));
+    const DecTable tab{c->dec_ent, c->dec_n, c->dec_pool};
+    const uint32_t row_blocks = (n_rows + WPB - 1) / WPB;
+    // ---- select: stop, skip, per-row counts -> where every row's kept ids and bytes go; the one read-back for sizes
+    unsigned long long N = 0, G = 0;
+    uint32_t h_status = 0, h_status_end = 0;
+    HIPCHK(c, hipEventRecord(c->drow_ev[0], s));
+    TRY(fill_u32(c, status, 1, 0u));
+    if (n_rows) {
+        hipLaunchKernelGGL(k_drow_select, dim3(row_blocks), dim3(BLOCK), 0, s,
+                           DrowSelectParams{d_ids, n_rows, row_len, d_lo, d_hi, sets, flags, tab, win, kept, rbytes, status});
+        HIPCHK(c, hipGetLastError());
+        if (exclusive_scan<uint32_t>(s, kept, n_rows, koff, (uint64_t)n_rows + 1) != 0 ||
+            exclusive_scan<unsigned long long>(s, rbytes, n_rows, rbase, (uint64_t)n_rows + 1) != 0)
+            return fail(c, YABPE_E_HIP, "scan of the row counts failed");
+        HIPCHK(c, hipEventRecord(c->drow_ev[1], s));
+        HIPCHK(c, hipMemcpyAsync(&N, koff + n_rows, 8, hipMemcpyDeviceToHost, s));
+        HIPCHK(c, hipMemcpyAsync(&G, rbase + n_rows, 8, hipMemcpyDeviceToHost, s));
+        HIPCHK(c, hipMemcpyAsync(&h_status, status, 4, hipMemcpyDeviceToHost, s));
+        const hipError_t se = hipStreamSynchronize(s);
+        if (se != hipSuccess) return fail(c, YABPE_E_HIP, "row selection failed: %s", hipGetErrorString(se));
+    }
+    if (h_status & DROW_E_WINDOW)
+        return fail(c, YABPE_E_INVALID, "a row's window is not 0 <= row_start <= row_end <= row_len (%u)", row_len);
+    const bool want_spans = out_dev_spans != nullptr;
+    auto &st = c->drow_stats;
+    st.n_kept = N;
+    st.n_gathered = G;
+    c->dec_stats.n_ids = N;
+    c->dec_stats.n_docs = n_rows;
+    c->drow_kept = S.take(kept);
+    TRY(dmalloc(c, &c->dec_doc, (uint64_t)n_rows + 1));
+    bool with_chars = false;
+    if (N == 0) {  // every row is empty
+        TRY(fill_u32(c, (uint32_t *)c->dec_doc, 2 * ((uint64_t)n_rows + 1), 0u));
+        TRY(dmalloc(c, &c->dec_text, 1));
+        if (want_spans) {
+            TRY(dmalloc(c, &c->drow_spans, 2 * n));
+            TRY(fill_u32(c, c->drow_spans, 2 * n, 0u));
+        }
+    } else {
+        // ---- compact: the kept ids back to back, then the decoder's passes on them; offsets in the shadow of its read-back
+        uint32_t *kids = nullptr;
+        HIPCHK(c, S.get(&kids, N));
+        HIPCHK(c, hipEventRecord(c->drow_ev[2], s));
+        hipLaunchKernelGGL(k_drow_compact, dim3(row_blocks), dim3(BLOCK), 0, s, DrowCompactParams{d_ids, n_rows, row_len, sets, win, koff, kids});
+        HIPCHK(c, hipGetLastError());
+        HIPCHK(c, hipEventRecord(c->drow_ev[3], s));
+        auto offsets = [&](const uint8_t *gtext, unsigned long long n_text) -> int {
+            if (!want_spans && !(h_status & DROW_BIG_ROW)) return 0;  // (fewer bytes than DROW_MAX_CHARS: fewer characters, too)
+            const unsigned long long nt = (n_text + DEC_TILE - 1) / DEC_TILE;
+            DrowChars ch{};
+            uint32_t *tcount = nullptr;
+            HIPCHK(c, S.get(&ch.mask, nt * DROW_WORDS));
+            HIPCHK(c, S.get(&ch.wpre, nt * DROW_WORDS));
+            HIPCHK(c, S.get(&ch.tpre, nt + 1));
+            HIPCHK(c, S.get(&tcount, nt));
+            if (want_spans) TRY(dmalloc(c, &c->drow_spans, 2 * n));
+            HIPCHK(c, hipEventRecord(c->drow_ev[4], s));
+            if (nt) hipLaunchKernelGGL(k_drow_chars, dim3((uint32_t)nt), dim3(BLOCK), 0, s, DrowCharsParams{gtext, n_text, rbase, n_rows, ch, tcount});
+            HIPCHK(c, hipGetLastError());
+            if (exclusive_scan<uint32_t>(s, tcount, nt, ch.tpre, nt + 1) != 0) return fail(c, YABPE_E_HIP, "scan of the tile character counts failed");
+            HIPCHK(c, hipEventRecord(c->drow_ev[5], s));
+            hipLaunchKernelGGL(k_drow_spans, dim3(row_blocks), dim3(BLOCK), 0, s,
+                               DrowSpansParams{d_ids, n_rows, row_len, sets, tab, win, rbase, ch, (uint2 *)c->drow_spans, status});
+            HIPCHK(c, hipGetLastError());
+            HIPCHK(c, hipEventRecord(c->drow_ev[6], s));
+            HIPCHK(c, hipMemcpyAsync(&h_status_end, status, 4, hipMemcpyDeviceToHost, s));
+            with_chars = true;
+            return 0;
+        };
+        uint8_t *text = nullptr;
+        uint64_t *text_off = nullptr, n_bytes = 0;
+        TRY(decode_passes(c, S, kids, N, koff, n_rows, &text, &text_off, &n_bytes, offsets));
+        if (h_status_end & DROW_E_CHARS) {
+            yabpe_decode_free(c);
+            return fail(c, YABPE_E_CAPACITY, "a row's text has 2^32 - 1 characters or more");
+        }
+        st.n_bytes = n_bytes;
+    }
+    HIPCHK(c, hipEventRecord(c->drow_ev[7], s));
+    HIPCHK(c, hipStreamSynchronize(s));
+    float ms[5] = {0, 0, 0, 0, 0};
+    if (n_rows) (void)hipEventElapsedTime(&ms[0], c->drow_ev[0], c->drow_ev[1]);
+    if (N) (void)hipEventElapsedTime(&ms[1], c->drow_ev[2], c->drow_ev[3]);
+    if (with_chars) {
+        (void)hipEventElapsedTime(&ms[2], c->drow_ev[4], c->drow_ev[5]);
+        (void)hipEventElapsedTime(&ms[3], c->drow_ev[5], c->drow_ev[6]);
+    }
+    (void)hipEventElapsedTime(&ms[4], c->drow_ev[0], c->drow_ev[7]);
+    st.select_ms = ms[0];
+    st.compact_ms = ms[1];
+    st.decode_ms = c->dec_stats.total_ms - ms[2] - ms[3];  // (the offsets ran between the decoder's check and its read-back)
+    st.chars_ms = ms[2];
+    st.spans_ms = ms[3];
+    st.total_ms = ms[4];
+    *out_dev_text = c->dec_text;
+    *out_dev_text_off = (uint64_t *)c->dec_doc;
+    *out_n_bytes = st.n_bytes;
+    *out_dev_kept = c->drow_kept;
+    if (out_dev_spans) *out_dev_spans = c->drow_spans;
+    return YABPE_OK;
+}
+
+int yabpe_decode_rows_stats(yabpe_ctx *c, yabpe_decode_rows_stats_t *out) {
+    if (!c || !out) return YABPE_E_INVALID;
+    *out = c->drow_stats;
     return YABPE_OK;
 }
 

@@ -69,6 +69,16 @@ class DecodeStats(ctypes.Structure):
         (n, c_double) for n in ("lengths_ms", "gather_ms", "check_ms", "repair_ms", "total_ms")]
 
 
+class DecodeRows(ctypes.Structure):
+    """yabpe_decode_rows_t"""
+    _fields_ = [("flags", c_uint32), ("n_stop", c_uint32), ("stop_ids", c_void_p), ("n_skip", c_uint32), ("skip_ids", c_void_p)]
+
+
+class DecodeRowsStats(ctypes.Structure):
+    _fields_ = [(n, c_uint64) for n in ("n_rows", "row_len", "n_kept", "n_gathered", "n_bytes")] + [
+        (n, c_double) for n in ("select_ms", "compact_ms", "decode_ms", "chars_ms", "spans_ms", "total_ms")]
+
+
 class LayoutStats(ctypes.Structure):
     _fields_ = [(n, c_uint64) for n in ("n_ids", "n_docs", "n_rows", "row_len", "n_truncated_docs", "n_ids_dropped", "n_pad_slots")] + [
         (n, c_double) for n in ("lengths_ms", "write_ms", "total_ms")]
@@ -197,7 +207,7 @@ SYMBOLS = [
     "yabpe_memcpy_d2h", "yabpe_memcpy_h2d", "yabpe_pretokenize", "yabpe_pretokenize_free",
     "yabpe_comm_unique_id", "yabpe_comm_init", "yabpe_comm_init_custom", "yabpe_comm_enable_p2p",
     "yabpe_encode_set_model", "yabpe_encode", "yabpe_encode_spans", "yabpe_encode_dropout", "yabpe_encode_words", "yabpe_encode_free", "yabpe_encode_stats", "yabpe_encode_checksum",
-    "yabpe_decode_set_model", "yabpe_decode", "yabpe_decode_free", "yabpe_decode_stats",
+    "yabpe_decode_set_model", "yabpe_decode", "yabpe_decode_free", "yabpe_decode_stats", "yabpe_decode_rows", "yabpe_decode_rows_stats",
     "yabpe_load_words_resumed", "yabpe_resume_stats",
     "yabpe_layout_pad", "yabpe_layout_pack", "yabpe_layout_windows", "yabpe_layout_pairs", "yabpe_layout_fit", "yabpe_layout_fit_labels", "yabpe_layout_free", "yabpe_layout_stats",
     "yabpe_mask", "yabpe_mask_free", "yabpe_mask_stats",
@@ -271,6 +281,9 @@ def lib() -> ctypes.CDLL:
         L.yabpe_decode.argtypes = [c_void_p, c_void_p, c_uint64, c_void_p, c_uint32, POINTER(c_void_p), POINTER(c_void_p), POINTER(c_uint64)]
         L.yabpe_decode_free.argtypes = [c_void_p]
         L.yabpe_decode_stats.argtypes = [c_void_p, POINTER(DecodeStats)]
+        L.yabpe_decode_rows.argtypes = [c_void_p, c_void_p, c_uint32, c_uint32, c_void_p, c_void_p, POINTER(DecodeRows), POINTER(c_void_p),
+                                        POINTER(c_void_p), POINTER(c_uint64), POINTER(c_void_p), POINTER(c_void_p)]
+        L.yabpe_decode_rows_stats.argtypes = [c_void_p, POINTER(DecodeRowsStats)]
         L.yabpe_layout_pad.argtypes = [c_void_p, c_void_p, c_uint64, c_void_p, c_uint32, POINTER(Layout), POINTER(c_void_p), POINTER(c_void_p),
                                        POINTER(c_uint32)]
         L.yabpe_layout_pack.argtypes = [c_void_p, c_void_p, c_uint64, c_void_p, c_uint32, POINTER(Layout), POINTER(c_void_p), POINTER(c_void_p),
@@ -329,6 +342,8 @@ MASK_IGNORE = 0xFFFFFF9C  # yabpe_mask_t.ignore: -100 as i32, the label a loss s
 SPAN_WHOLE_WORD, SPAN_FINAL_SENTINEL = 0x1, 0x2  # yabpe_span_t.flags
 SPAN_MAX_LEN = 32  # YABPE_SPAN_MAX_LEN
 FIM_EOT, FIM_LOSS_MIDDLE, FIM_PIECES = 0x1, 0x2, 0x4  # yabpe_fim_t.flags
+DECODE_ROWS_INCLUDE_STOP = 0x1  # yabpe_decode_rows_t.flags
+DECODE_ROWS_MAX_STOP, DECODE_ROWS_MAX_SKIP = 64, 1024  # YABPE_DECODE_ROWS_MAX_STOP / _SKIP
 CHAT_LOSS_ALL, CHAT_LOSS_LAST, CHAT_DROP_OLDEST, CHAT_PIN_FIRST, CHAT_GEN_PROMPT = 0x01, 0x02, 0x04, 0x08, 0x10  # yabpe_chat_t.flags
 CHAT_MAX_ROLES, CHAT_MAX_TEMPLATE_IDS = 16, 2048  # YABPE_CHAT_MAX_ROLES, YABPE_CHAT_MAX_TEMPLATE_IDS
 CHAT_TILE, CHAT_STAGE = 1024, 256  # chat_logic.h: output slots a workgroup of the write pass owns, turn records it stages at a time
@@ -802,6 +817,57 @@ class Context:
     def decode_stats(self) -> dict:
         s = DecodeStats()
         self._chk(lib().yabpe_decode_stats(self._h, byref(s)))
+        return _stats_dict(s)
+
+    # -- decoding id rows (BBPETokenizer.decode_rows / decode_rows_with_offsets on the device)
+    def decode_rows(self, rows, n_rows: int | None = None, row_len: int | None = None, starts=None, ends=None, *, stop_ids=(),
+                    skip_ids=(), include_stop: bool = False, offsets: bool = False):
+        """rows: a 2-D u32 array (staged) or a device address (n_rows and row_len required); starts / ends: a u32 per row, as an
+        array or a device address, None: 0 / row_len; stop_ids / skip_ids: at most DECODE_ROWS_MAX_STOP / _SKIP ids.
+        -> (dev_text_ptr u8, dev_text_off_ptr u64[n_rows + 1], n_bytes, dev_kept_ptr u32[n_rows], dev_spans_ptr u32[n_rows,
+        row_len, 2] or None without offsets); the buffers live until the next decode call, decode_free() or close()."""
+        keep = []
+        if isinstance(rows, int):
+            ptr, nr, rl = c_void_p(rows), int(n_rows), int(row_len)
+        else:
+            a = np.ascontiguousarray(rows, dtype=np.uint32)
+            if a.ndim != 2:
+                raise ValueError("rows must be a 2-D array")
+            keep.append(a)
+            ptr, (nr, rl) = c_void_p(a.ctypes.data if a.size else 0), a.shape
+
+        def per_row(v):
+            if v is None or isinstance(v, int):
+                return c_void_p(v)
+            keep.append(np.ascontiguousarray(v, dtype=np.uint32))
+            if keep[-1].shape != (nr,):
+                raise ValueError("starts and ends hold one entry per row")
+            return c_void_p(keep[-1].ctypes.data if nr else 0)
+
+        lo, hi = per_row(starts), per_row(ends)
+        stop, skip = (np.unique(np.asarray(list(v), dtype=np.uint32)) for v in (stop_ids, skip_ids))
+        opt = DecodeRows(DECODE_ROWS_INCLUDE_STOP if include_stop else 0, len(stop), stop.ctypes.data, len(skip), skip.ctypes.data)
+        dt, do, nb, dk, ds = c_void_p(), c_void_p(), c_uint64(0), c_void_p(), c_void_p()
+        self._chk(lib().yabpe_decode_rows(self._h, ptr, nr, rl, lo, hi, byref(opt), byref(dt), byref(do), byref(nb),
+                                          byref(ds) if offsets else None, byref(dk)))
+        return dt.value or 0, do.value, nb.value, dk.value, ds.value if offsets else None
+
+    def decode_rows_to_host(self, rows, n_rows: int | None = None, row_len: int | None = None, starts=None, ends=None, **kw):
+        """-> (text u8[n_bytes], text_off u64[n_rows + 1], n_kept u32[n_rows]) copied to the host, and spans u32[n_rows, row_len, 2]
+        with offsets=True."""
+        if not isinstance(rows, int):
+            n_rows, row_len = np.shape(rows)
+        dt, do, nb, dk, ds = self.decode_rows(rows, n_rows, row_len, starts, ends, **kw)
+        out = (self.d2h(dt, nb) if nb else np.zeros(0, np.uint8), self.d2h(do, 8 * (n_rows + 1), np.uint64),
+               self.d2h(dk, 4 * n_rows, np.uint32) if n_rows else np.zeros(0, np.uint32))
+        if ds is None:
+            return out
+        n = n_rows * row_len
+        return out + ((self.d2h(ds, 8 * n, np.uint32) if n else np.zeros(0, np.uint32)).reshape(n_rows, row_len, 2),)
+
+    def decode_rows_stats(self) -> dict:
+        s = DecodeRowsStats()
+        self._chk(lib().yabpe_decode_rows_stats(self._h, byref(s)))
         return _stats_dict(s)
 
     # -- fixed-shape batches (BBPETokenizer.encode_batch_padded / encode_batch_packed / encode_batch_windows on the device)

@@ -1923,6 +1923,63 @@ class BBPETokenizer:
     def decode_batch(self, ids_batch: Sequence[Sequence[int]]) -> list[str]:
         return [self.decode(ids) for ids in ids_batch]
 
+    # ------------------------------------------------------------------ decode id rows: what a model hands back
+    def _rows_args(self, rows, starts, ends, stop_ids, skip_special_tokens, skip_ids, pad_id):
+        """-> (rows as a list of equal-length lists, T, starts, ends, the stop set, the skip set), validated"""
+        rows = rows.tolist() if isinstance(rows, np.ndarray) else [list(r) for r in rows]
+        T = len(rows[0]) if rows else 0
+        if any(not isinstance(r, list) or len(r) != T for r in rows):
+            raise ValueError("rows must hold rows of equal length")
+        lo = [0] * len(rows) if starts is None else [int(x) for x in starts]
+        hi = [T] * len(rows) if ends is None else [int(x) for x in ends]
+        if len(lo) != len(rows) or len(hi) != len(rows):
+            raise ValueError("starts and ends hold one entry per row")
+        if any(not 0 <= a <= b <= T for a, b in zip(lo, hi)):
+            raise ValueError("every row needs 0 <= start <= end <= the row length")
+        skip = {int(i) for i in skip_ids}
+        if pad_id is not None:
+            skip.add(int(pad_id))
+        if skip_special_tokens:
+            skip.update(self._vocab[s.encode("utf-8")] for s in self._special_tokens if s.encode("utf-8") in self._vocab)
+        return rows, T, lo, hi, {int(i) for i in stop_ids}, skip
+
+    def decode_rows_with_offsets(self, rows, *, starts=None, ends=None, stop_ids=(), include_stop: bool = False,
+                                 skip_special_tokens: bool = True, skip_ids=(), pad_id: int | None = None):
+        """Decodes a [B, T] matrix of ids (a 2-D array or equal-length lists; B = 0 and T = 0 are allowed), row by row.  Of row r
+        the columns [starts[r], ends[r]) count (None: 0 / T; anything but 0 <= start <= end <= T: ValueError).  The first of them
+        whose id is in stop_ids ends the row: the considered columns stop in front of it (include_stop: behind it).  Then a
+        considered column is dropped when its id is in skip_ids, is pad_id or (skip_special_tokens) is the id of one of the
+        tokenizer's specials -- after the stop rule, so an EOS that is a special still cuts.  The rest are the row's kept ids
+        and its text is decode(kept ids).
+        -> (texts, offsets, n_kept): offsets[r][c] = (nchars(b), nchars(b + len)) for EVERY column c, in characters of texts[r],
+        with data = the bytes of the row's kept tokens, b = those in the columns before c, len = those of column c's own token (0
+        when it is not kept or the vocab does not name it) and nchars(x) = len(data[:x].decode("utf-8", "replace")).  Spans
+        never decrease along a row; columns before the window are (0, 0), those behind the stop (n, n) with n = len(texts[r]);
+        a token that ends inside a character owns it, one that only continues it has an empty span."""
+        rows, T, lo, hi, stop, skip = self._rows_args(rows, starts, ends, stop_ids, skip_special_tokens, skip_ids, pad_id)
+        inv = self._vocab_inv
+        texts, offsets, n_kept = [], [], []
+        for row, a, b in zip(rows, lo, hi):
+            cut = next((c for c in range(a, b) if row[c] in stop), None)
+            end = b if cut is None else cut + 1 if include_stop else cut
+            kept = [c for c in range(a, end) if row[c] not in skip]
+            own = {c: inv.get(row[c], b"") for c in kept}
+            data = b"".join(own[c] for c in kept)
+            pos, at, spans = 0, 0, []  # at = nchars(pos)
+            for c in range(T):
+                pos += len(own.get(c, b""))
+                nxt = len(data[:pos].decode("utf-8", "replace")) if c in own and own[c] else at
+                spans.append((at, nxt))
+                at = nxt
+            texts.append(self.decode([row[c] for c in kept]))
+            offsets.append(spans)
+            n_kept.append(len(kept))
+        return texts, offsets, n_kept
+
+    def decode_rows(self, rows, **kw) -> list[str]:
+        """The texts of decode_rows_with_offsets(rows, ...): decode with skip_special_tokens and "only the completion"."""
+        return self.decode_rows_with_offsets(rows, **kw)[0]
+
     # ------------------------------------------------------------------ decode on the GPU (yabpe_decode; same text as decode)
     def decode_array(self, ids, doc_off=None) -> tuple[np.ndarray, np.ndarray]:
         """Decodes on the GPU: document d = ids[doc_off[d]:doc_off[d + 1]] (encode_array's layout: n_docs + 1 offsets, the
@@ -1950,6 +2007,44 @@ class BBPETokenizer:
         text, toff = self.decode_array(flat, off)
         data, toff = text.tobytes(), toff.tolist()
         return [data[toff[d]:toff[d + 1]].decode("utf-8") for d in range(len(ids_batch))]
+
+    def decode_rows_array(self, rows, *, starts=None, ends=None, stop_ids=(), include_stop: bool = False, skip_special_tokens: bool = True,
+                          skip_ids=(), pad_id: int | None = None, offsets: bool = False):
+        """decode_rows / decode_rows_with_offsets on the GPU (yabpe_decode_rows): the same arguments; encode_array_padded's rows and
+        lengths go straight in (ends=lengths for right padding, starts=T - lengths for left).
+        -> (text np.uint8[n], text_off np.uint64[B + 1], n_kept np.uint32[B]): text[text_off[r]:text_off[r + 1]] is row r's text
+        as UTF-8; with offsets=True also spans np.uint32[B, T, 2], the (start, end) of every column in characters of its row's
+        text."""
+        if isinstance(rows, np.ndarray):
+            arr = rows
+        else:
+            try:
+                arr = np.asarray([list(r) for r in rows], dtype=np.int64)
+            except OverflowError:
+                arr = np.asarray([list(r) for r in rows], dtype=object)
+        if arr.ndim == 1 and arr.size == 0:
+            arr = arr.reshape(0, 0)
+        if arr.ndim != 2:
+            raise ValueError("rows must hold rows of equal length")
+        B, T = arr.shape
+        for name, v in (("starts", starts), ("ends", ends)):
+            if v is not None and (len(v) != B or any(not 0 <= int(x) <= T for x in v)):
+                raise ValueError(f"{name} holds one entry in [0, T] per row")
+        if starts is not None and any(int(a) > int(b) for a, b in zip(starts, [T] * B if ends is None else ends)):
+            raise ValueError("every row needs 0 <= start <= end <= the row length")
+        _rows, _T, _lo, _hi, stop, skip = self._rows_args([], None, None, stop_ids, skip_special_tokens, skip_ids, pad_id)
+        stop, skip = ({i for i in s if 0 <= i < 1 << 32} for s in (stop, skip))
+        if arr.dtype != np.uint32:  # ids no vocab can hold become one that no vocab names and neither list holds
+            bad = ~_u32_mask(arr.ravel()).astype(bool).reshape(B, T)
+            arr = np.where(bad, next(i for i in range((1 << 32) - 1, 0, -1) if i not in stop and i not in skip), arr).astype(np.uint32)
+        return self._device("decode").decode_rows_to_host(arr, starts=starts, ends=ends, stop_ids=sorted(stop), skip_ids=sorted(skip),
+                                                          include_stop=include_stop, offsets=offsets)
+
+    def decode_rows_device(self, rows, **kw) -> list[str]:
+        """decode_rows(rows, ...), computed on the GPU in one call."""
+        text, toff, _kept = self.decode_rows_array(rows, **kw)
+        data, toff = text.tobytes(), toff.tolist()
+        return [data[toff[r]:toff[r + 1]].decode("utf-8") for r in range(len(toff) - 1)]
 
     # ------------------------------------------------------------------ introspection
     @property
