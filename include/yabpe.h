@@ -1029,6 +1029,47 @@ typedef struct yabpe_chat_stats_t {
 } yabpe_chat_stats_t;
 int yabpe_chat_stats(yabpe_ctx *ctx, yabpe_chat_stats_t *out);
 
+/* Near-duplicate detection (BBPETokenizer.minhash_tokens on the device, yet_another_bpe/tokenizer.py) -----------------
+ * MinHash signatures over n-gram shingles of ragged ids, and optionally the LSH band keys.  ids / doc_off / n_docs as yabpe_mask
+ * takes them, host or device memory; yabpe_encode's results go straight in and are left alone.  With mix and rnd(seed, stream,
+ * i) of yet_another_bpe/synth.py, G = 0x9E3779B97F4A7C15, u64 with wraparound:
+ *   shingles   a document of L ids has L - ngram + 1 of them, one per window of ngram consecutive ids (L >= ngram), one of all
+ *              its ids (0 < L < ngram), none (L = 0);
+ *   hash       of a shingle of m ids: s = rnd(0, 0x68, m); for every id in order s = mix(s + G * (id + 1)); h = s >> 32;
+ *   functions  a_k = rnd(seed, 0x70, k) | 1, b_k = rnd(seed, 0x71, k), p_k(h) = (a_k * h + b_k) >> 32 for k < num_perm;
+ *   signature  sig[d][k] = the minimum of p_k(h) over the shingles of d, 0xFFFFFFFF for a document without shingles;
+ *   band key   bands > 0, r = num_perm / bands: key[d][t] = s after s = rnd(0, 0x6b, t) and s = mix(s + G * (v + 1)) for
+ *              v = sig[d][t * r], ..., sig[d][t * r + r - 1].  Two documents are LSH candidates iff key[.][t] agrees for a t.
+ * Results (device memory owned by the library, in buffers of their own: a later encode, mask or layout call leaves them valid;
+ * released by yabpe_minhash_free, the next yabpe_minhash or yabpe_destroy): *out_dev_sig u32[n_docs][num_perm],
+ * *out_dev_shingles u64[n_docs] (every document's shingle count), *out_dev_keys u64[n_docs][bands] (NULL with bands == 0).
+ * YABPE_E_INVALID: num_perm outside [1, 1024], ngram outside [1, 32], bands that is neither 0 nor a divisor of num_perm, flags
+ * other than 0, a doc_off that does not ascend from 0 inside the ids.  YABPE_E_CAPACITY: more than 2^36 ids or n_docs * num_perm
+ * above 2^36 slots, 2^31 pieces or more (a piece: up to 1,024 shingle positions of one document).  Every error is found
+ * before a buffer is allocated. */
+typedef struct yabpe_minhash_t {
+    uint64_t seed;
+    uint32_t num_perm;   /* K: hash functions, 1 .. 1024 */
+    uint32_t ngram;      /* n: ids per shingle, 1 .. 32 */
+    uint32_t bands;      /* 0: no keys; else a divisor of num_perm */
+    uint32_t flags;      /* 0 */
+} yabpe_minhash_t;
+int yabpe_minhash(yabpe_ctx *ctx, const uint32_t *ids, uint64_t n_ids, const uint64_t *doc_off, uint32_t n_docs,
+                  const yabpe_minhash_t *rule, uint32_t **out_dev_sig, uint64_t **out_dev_shingles, uint64_t **out_dev_keys);
+int yabpe_minhash_free(yabpe_ctx *ctx);
+/* What the last yabpe_minhash saw, and its device time. */
+typedef struct yabpe_minhash_stats_t {
+    uint64_t n_ids, n_docs;
+    uint64_t n_pieces;            /* workgroups of the signature kernel */
+    uint64_t n_shingles;          /* over all documents */
+    uint64_t n_multi_piece_docs;  /* documents of more than one piece (their rows are combined with atomicMin) */
+    double plan_ms;               /* shingle and piece counts, their scan, the preset rows */
+    double sig_ms;                /* the signature kernel */
+    double keys_ms;               /* the band keys (0 without bands) */
+    double total_ms;              /* first to last event of the call */
+} yabpe_minhash_stats_t;
+int yabpe_minhash_stats(yabpe_ctx *ctx, yabpe_minhash_stats_t *out);
+
 /* Multi-GPU (one process per GPU; words are sharded by the caller) -----------------
  * Every rank holds its shard of the words and a replica of the pair table.  After each apply pass the ranks
  * exchange their aggregated (pair, delta) records with ONE all-gather on the compute stream and every rank adds all

@@ -34,6 +34,7 @@
 #include "yabpe_fit_kernels.h"
 #include "yabpe_fitlab_kernels.h"
 #include "yabpe_mask_kernels.h"
+#include "yabpe_minhash_kernels.h"
 #include "yabpe_span_kernels.h"
 #include "yabpe_fim_kernels.h"
 #include "yabpe_chat_kernels.h"
@@ -251,6 +252,10 @@ struct yabpe_ctx {
     void *chat_buf[4] = {};
     yabpe_chat_stats_t chat_stats{};
     hipEvent_t chat_ev[3] = {};
+    // near-duplicate detection: the results of the last yabpe_minhash (signatures, shingle counts, band keys)
+    void *mh_buf[3] = {};
+    yabpe_minhash_stats_t mh_stats{};
+    hipEvent_t mh_ev[4] = {};
     // resumed load (yabpe_load_words_resumed)
     yabpe_resume_stats_t resume_stats{};
     // persistent word pool (yabpe_pool_add / yabpe_pool_get): arena, off / count / hash, slots (pool_logic.h)
@@ -1943,6 +1948,9 @@ void yabpe_destroy(yabpe_ctx *c) {
         if (e) (void)hipEventDestroy(e);
     yabpe_chat_free(c);
     for (auto &e : c->chat_ev)
+        if (e) (void)hipEventDestroy(e);
+    yabpe_minhash_free(c);
+    for (auto &e : c->mh_ev)
         if (e) (void)hipEventDestroy(e);
     yabpe_pool_clear(c);
     for (auto &e : c->wpool_ev)
@@ -5743,6 +5751,113 @@ int yabpe_chat(yabpe_ctx *c, const uint32_t *ids, uint64_t n_ids, const uint64_t
 int yabpe_chat_stats(yabpe_ctx *c, yabpe_chat_stats_t *out) {
     if (!c || !out) return YABPE_E_INVALID;
     *out = c->chat_stats;
+    return YABPE_OK;
+}
+
+// ---------------------------------------------------------------------------------------------- near-duplicate detection
+int yabpe_minhash_free(yabpe_ctx *c) {
+    if (!c) return YABPE_E_INVALID;
+    for (auto &p : c->mh_buf) {
+        dfree(p);
+        p = nullptr;
+    }
+    return YABPE_OK;
+}
+
+// BBPETokenizer.minhash_tokens on the device (yabpe_minhash_kernels.h; the rule: minhash_logic.h).  mh_ev[0..3] bracket the
+// plan (counts, scan, preset rows), the signature kernel and the band keys.  A call that the checks refuse has freed nothing.
+int yabpe_minhash(yabpe_ctx *c, const uint32_t *ids, uint64_t n_ids, const uint64_t *doc_off, uint32_t n_docs, const yabpe_minhash_t *rule,
+                  uint32_t **out_dev_sig, uint64_t **out_dev_shingles, uint64_t **out_dev_keys) {
+    if (!c || !out_dev_sig || !out_dev_shingles || !out_dev_keys) return YABPE_E_INVALID;
+    HIPCHK(c, hipSetDevice(c->device));
+    *out_dev_sig = nullptr; *out_dev_shingles = nullptr; *out_dev_keys = nullptr;
+    if (!rule) return fail(c, YABPE_E_INVALID, "rule is NULL");
+    const MinhashRule R{rule->seed, rule->num_perm, rule->ngram, rule->bands};
+    if (!mh_rule_valid(R))
+        return fail(c, YABPE_E_INVALID, "num_perm %u, ngram %u, bands %u: num_perm in [1, %u], ngram in [1, %u], bands 0 or a divisor of num_perm",
+                    R.num_perm, R.ngram, R.bands, MH_MAX_PERM, MH_MAX_NGRAM);
+    if (rule->flags) return fail(c, YABPE_E_INVALID, "unknown minhash flags 0x%x", rule->flags);
+    if (n_ids && !ids) return fail(c, YABPE_E_INVALID, "ids is NULL");
+    if (n_ids > MH_MAX_SLOTS) return fail(c, YABPE_E_CAPACITY, "%llu ids: at most 2^36 in one call", (unsigned long long)n_ids);
+    if (!doc_off && n_docs > 1) return fail(c, YABPE_E_INVALID, "doc_off is NULL with %u documents", n_docs);
+    const bool docs_dev = doc_off && is_device_ptr(doc_off);
+    if (!doc_off) n_docs = 1;
+    std::vector<uint64_t> h_docs(n_docs, 0);
+    if (doc_off && n_docs) {
+        if (docs_dev) HIPCHK(c, hipMemcpy(h_docs.data(), doc_off, (size_t)n_docs * 8, hipMemcpyDeviceToHost));
+        else memcpy(h_docs.data(), doc_off, (size_t)n_docs * 8);
+    }
+    TRY(check_starts(c, h_docs.data(), n_docs, n_ids, "ids"));
+    const unsigned long long n_slots = (unsigned long long)n_docs * R.num_perm;
+    if (n_slots > MH_MAX_SLOTS) return fail(c, YABPE_E_CAPACITY, "%u documents of %u slots: at most 2^36 slots in one call", n_docs, R.num_perm);
+    // what the plan kernels will find, counted here from the validated starts: the grid of k_minhash and the statistics
+    unsigned long long n_pieces = 0, n_shingles = 0, n_multi = 0;
+    for (uint32_t d = 0; d < n_docs; ++d) {
+        const unsigned long long S = mh_shingles((d + 1 < n_docs ? h_docs[d + 1] : n_ids) - h_docs[d], R.ngram);
+        n_shingles += S;
+        n_pieces += mh_pieces(S);
+        n_multi += S > MH_TILE;
+    }
+    if (n_pieces > 0x7FFFFFFFull) return fail(c, YABPE_E_CAPACITY, "%llu pieces of up to %u shingles: fewer than 2^31 in one call", n_pieces, MH_TILE);
+    yabpe_minhash_free(c);
+    auto &st = c->mh_stats;
+    st = yabpe_minhash_stats_t{};
+    st.n_ids = n_ids;
+    st.n_docs = n_docs;
+    st.n_pieces = n_pieces;
+    st.n_shingles = n_shingles;
+    st.n_multi_piece_docs = n_multi;
+    for (auto &e : c->mh_ev)
+        if (!e) HIPCHK(c, hipEventCreate(&e));
+    hipStream_t s = c->stream;
+    Scratch S(c->device, c->rank);
+    MinhashParams P{};
+    unsigned long long *piece_off = nullptr;
+    TRY(to_device(c, S, ids, n_ids * 4, 4, &P.ids));
+    TRY(to_device(c, S, docs_dev ? (const unsigned long long *)doc_off : (const unsigned long long *)h_docs.data(), (uint64_t)n_docs * 8, 8, &P.doc_off));
+    HIPCHK(c, S.get(&P.pieces, n_docs));
+    HIPCHK(c, S.get(&piece_off, (uint64_t)n_docs + 1));
+    TRY(dmalloc(c, (uint32_t **)&c->mh_buf[0], n_slots));
+    TRY(dmalloc(c, (unsigned long long **)&c->mh_buf[1], n_docs));
+    if (R.bands) TRY(dmalloc(c, (unsigned long long **)&c->mh_buf[2], (unsigned long long)n_docs * R.bands));
+    P.n_ids = n_ids;
+    P.n_docs = n_docs;
+    P.rule = R;
+    P.piece_off = piece_off;
+    P.sig = (uint32_t *)c->mh_buf[0];
+    P.n_shingles = (unsigned long long *)c->mh_buf[1];
+    P.keys = (unsigned long long *)c->mh_buf[2];
+    auto hip_fail = [&](const char *what, hipError_t e) {
+        yabpe_minhash_free(c);
+        return fail(c, YABPE_E_HIP, "minhash: %s failed: %s", what, hipGetErrorString(e));
+    };
+    HIPCHK(c, hipEventRecord(c->mh_ev[0], s));
+    hipLaunchKernelGGL(k_minhash_plan, dim3(cdiv64(n_docs, MH_BLOCK)), dim3(MH_BLOCK), 0, s, P);
+    if (exclusive_scan<uint32_t>(s, P.pieces, n_docs, piece_off, (unsigned long long)n_docs + 1) != 0)
+        return hip_fail("the scan of the piece counts", hipGetLastError());
+    hipLaunchKernelGGL(k_minhash_fill, dim3(cdiv64(n_slots, MH_BLOCK)), dim3(MH_BLOCK), 0, s, P);
+    (void)hipEventRecord(c->mh_ev[1], s);
+    if (n_pieces) hipLaunchKernelGGL(k_minhash, dim3((uint32_t)n_pieces), dim3(MH_BLOCK), 0, s, P);
+    (void)hipEventRecord(c->mh_ev[2], s);
+    if (R.bands) hipLaunchKernelGGL(k_minhash_keys, dim3(cdiv64((unsigned long long)n_docs * R.bands, MH_BLOCK)), dim3(MH_BLOCK), 0, s, P);
+    const hipError_t le = hipGetLastError();
+    (void)hipEventRecord(c->mh_ev[3], s);
+    const hipError_t se = hipStreamSynchronize(s);
+    if (le != hipSuccess || se != hipSuccess) return hip_fail("a kernel", le != hipSuccess ? le : se);
+    float ms[3] = {0, 0, 0};
+    st.total_ms = pass_times(c->mh_ev, 3, ms);
+    st.plan_ms = ms[0];
+    st.sig_ms = ms[1];
+    st.keys_ms = R.bands ? ms[2] : 0.0;
+    *out_dev_sig = P.sig;
+    *out_dev_shingles = (uint64_t *)P.n_shingles;
+    *out_dev_keys = (uint64_t *)P.keys;
+    return YABPE_OK;
+}
+
+int yabpe_minhash_stats(yabpe_ctx *c, yabpe_minhash_stats_t *out) {
+    if (!c || !out) return YABPE_E_INVALID;
+    *out = c->mh_stats;
     return YABPE_OK;
 }
 

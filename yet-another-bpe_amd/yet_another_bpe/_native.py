@@ -130,6 +130,16 @@ class ChatStats(ctypes.Structure):
         (n, c_double) for n in ("plan_ms", "write_ms", "total_ms")]
 
 
+class Minhash(ctypes.Structure):
+    """yabpe_minhash_t"""
+    _fields_ = [("seed", c_uint64)] + [(n, c_uint32) for n in ("num_perm", "ngram", "bands", "flags")]
+
+
+class MinhashStats(ctypes.Structure):
+    _fields_ = [(n, c_uint64) for n in ("n_ids", "n_docs", "n_pieces", "n_shingles", "n_multi_piece_docs")] + [
+        (n, c_double) for n in ("plan_ms", "sig_ms", "keys_ms", "total_ms")]
+
+
 class Layout(ctypes.Structure):
     """yabpe_layout_t"""
     _fields_ = [(n, c_uint32) for n in ("row_len", "pad_id", "bos_id", "eos_id", "flags")]
@@ -214,6 +224,7 @@ SYMBOLS = [
     "yabpe_span_corrupt", "yabpe_span_free", "yabpe_span_stats",
     "yabpe_fim_cuts", "yabpe_fim", "yabpe_fim_free", "yabpe_fim_stats",
     "yabpe_chat", "yabpe_chat_free", "yabpe_chat_stats",
+    "yabpe_minhash", "yabpe_minhash_free", "yabpe_minhash_stats",
     "yabpe_pool_add", "yabpe_pool_get", "yabpe_pool_clear", "yabpe_pool_stats",
     "yabpe_normalize", "yabpe_normalize_free", "yabpe_normalize_stats",
     "yabpe_utf8_repair", "yabpe_utf8_repair_free", "yabpe_utf8_repair_stats",
@@ -310,6 +321,10 @@ def lib() -> ctypes.CDLL:
                                  POINTER(c_void_p), POINTER(c_void_p), POINTER(c_void_p), POINTER(c_uint64)]
         L.yabpe_chat_free.argtypes = [c_void_p]
         L.yabpe_chat_stats.argtypes = [c_void_p, POINTER(ChatStats)]
+        L.yabpe_minhash.argtypes = [c_void_p, c_void_p, c_uint64, c_void_p, c_uint32, POINTER(Minhash), POINTER(c_void_p), POINTER(c_void_p),
+                                    POINTER(c_void_p)]
+        L.yabpe_minhash_free.argtypes = [c_void_p]
+        L.yabpe_minhash_stats.argtypes = [c_void_p, POINTER(MinhashStats)]
         L.yabpe_pool_add.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_uint64]
         L.yabpe_pool_get.argtypes = [c_void_p, POINTER(c_void_p), POINTER(c_void_p), POINTER(c_void_p), POINTER(c_uint64), POINTER(c_uint64)]
         L.yabpe_pool_clear.argtypes = [c_void_p]
@@ -348,6 +363,7 @@ CHAT_LOSS_ALL, CHAT_LOSS_LAST, CHAT_DROP_OLDEST, CHAT_PIN_FIRST, CHAT_GEN_PROMPT
 CHAT_MAX_ROLES, CHAT_MAX_TEMPLATE_IDS = 16, 2048  # YABPE_CHAT_MAX_ROLES, YABPE_CHAT_MAX_TEMPLATE_IDS
 CHAT_TILE, CHAT_STAGE = 1024, 256  # chat_logic.h: output slots a workgroup of the write pass owns, turn records it stages at a time
 FITL_SHIFTED, FITL_MASK_FIRST = 0x1, 0x2  # yabpe_fit_labels_t.flags
+MINHASH_MAX_PERM, MINHASH_MAX_NGRAM, MINHASH_TILE = 1024, 32, 1024  # minhash_logic.h: MH_MAX_PERM, MH_MAX_NGRAM, MH_TILE
 FITL_TILE, FITL_STAGE = 1024, 256  # fit_logic.h: output slots a workgroup of the labelled write pass owns, records it stages at a time
 PAIRS_MODES = {"longest_first": 0, "only_first": 1, "only_second": 2, "windows": 3}  # yabpe_pairs_t.mode (YABPE_PAIRS_*)
 
@@ -1302,6 +1318,43 @@ class Context:
     def chat_stats(self) -> dict:
         s = ChatStats()
         self._chk(lib().yabpe_chat_stats(self._h, byref(s)))
+        return _stats_dict(s)
+
+    # -- near-duplicate detection (BBPETokenizer.minhash_tokens on the device)
+    def minhash(self, ids, n_ids: int | None = None, doc_starts=None, n_docs: int | None = None, *, num_perm: int = 128, ngram: int = 5,
+                bands: int = 0, seed: int = 0):
+        """MinHash signatures and band keys of ragged ids (yabpe_minhash).  ids / doc_starts as mask takes them; bands 0: no keys.
+        -> (dev_sig_ptr u32[n_docs, num_perm], dev_shingles_ptr u64[n_docs], dev_keys_ptr u64[n_docs, bands] or 0, n_docs); the
+        buffers live until the next minhash, minhash_free() or close()."""
+        keep = docs = None
+        if isinstance(ids, int):
+            ptr, n = c_void_p(ids), int(n_ids)
+        else:
+            keep = np.ascontiguousarray(ids, dtype=np.uint32)
+            ptr, n = c_void_p(keep.ctypes.data if keep.size else 0), int(keep.size)
+        if isinstance(doc_starts, int):
+            dptr, nd = c_void_p(doc_starts), int(n_docs)
+        else:
+            docs = _starts_arg(doc_starts)
+            dptr, nd = c_void_p(docs.ctypes.data), len(docs)
+        rule = Minhash(int(seed), int(num_perm), int(ngram), int(bands), 0)
+        ds, dn, dk = c_void_p(), c_void_p(), c_void_p()
+        self._chk(lib().yabpe_minhash(self._h, ptr, n, dptr, nd, byref(rule), byref(ds), byref(dn), byref(dk)))
+        return ds.value or 0, dn.value or 0, dk.value or 0, nd
+
+    def minhash_to_host(self, ids, n_ids: int | None = None, doc_starts=None, n_docs: int | None = None, *, num_perm: int = 128, bands: int = 0,
+                        **kw):
+        """-> (sig u32[n_docs, num_perm], n_shingles u64[n_docs], keys u64[n_docs, bands] or None) copied to the host."""
+        ds, dn, dk, nd = self.minhash(ids, n_ids, doc_starts, n_docs, num_perm=num_perm, bands=bands, **kw)
+        keys = self.d2h(dk, 8 * nd * bands, np.uint64).reshape(nd, bands) if bands else None
+        return self.d2h(ds, 4 * nd * num_perm, np.uint32).reshape(nd, num_perm), self.d2h(dn, 8 * nd, np.uint64), keys
+
+    def minhash_free(self) -> None:
+        self._chk(lib().yabpe_minhash_free(self._h))
+
+    def minhash_stats(self) -> dict:
+        s = MinhashStats()
+        self._chk(lib().yabpe_minhash_stats(self._h, byref(s)))
         return _stats_dict(s)
 
     # -- the persistent word pool (corpora larger than device memory: words go in call by call, the merge loop loads the pool)

@@ -16,7 +16,9 @@ encode_array_with_words / mask_array / encode_array_masked compute the same on t
 chat_tokens / encode_batch_chat write conversations through a ChatTemplate with labels on the assistant's turns;
 chat_array / encode_array_chat compute the same on the GPU (yabpe_chat).  fit_labelled / encode_batch_chat_fit pack such
 labelled sequences whole into rows, several a row, with the seam records a varlen attention kernel needs; fit_labelled_array /
-encode_array_chat_fit compute the same on the GPU (yabpe_layout_fit_labels).
+encode_array_chat_fit compute the same on the GPU (yabpe_layout_fit_labels).  minhash_tokens / encode_batch_minhash give every
+document a MinHash signature over its id n-grams and LSH band keys, for near-duplicate detection; minhash_array /
+encode_array_minhash compute the same on the GPU (yabpe_minhash).
 """
 from __future__ import annotations
 
@@ -32,7 +34,7 @@ from typing import NamedTuple
 import numpy as np
 import regex
 
-from .synth import rnd_int
+from .synth import rnd, rnd_int
 from .trainer import (CL100K_DIGIT_GROUP, NORMALIZERS, PRETOKENIZER_NAMES, BBPETrainerConfig, check_digit_group, check_errors,
                       check_lowercase, check_lowercase_specials, check_normalized_specials, check_normalizer, check_pretokenizer, device_options,
                       device_text_front, lowercase_text, normalize_text, read_lowercase, read_normalizer, read_pretokenizer, split_pattern)
@@ -1353,6 +1355,94 @@ class BBPETokenizer:
         out = (rows, types, row_pair, row_start, first_len, second_len)
         return out if offsets is None else out + (spans,)
 
+    # ------------------------------------------------------------------ near-duplicate detection (MinHash over id shingles, LSH bands)
+    MINHASH_MAX_PERM, MINHASH_MAX_NGRAM = 1024, 32  # MH_MAX_PERM, MH_MAX_NGRAM of csrc/minhash_logic.h
+    _MH_SHINGLE, _MH_A, _MH_B, _MH_BAND = 0x68, 0x70, 0x71, 0x6B  # the streams of rnd the rule draws from
+
+    @classmethod
+    def _minhash_args(cls, num_perm, ngram, bands, seed) -> tuple[int, int, int, int]:
+        """-> (num_perm, ngram, bands or 0, seed), validated as yabpe_minhash validates them"""
+        try:
+            num_perm, ngram, bands = operator.index(num_perm), operator.index(ngram), 0 if bands is None else operator.index(bands)
+        except TypeError:
+            raise ValueError(f"num_perm, ngram and bands must be integers, not {num_perm!r}, {ngram!r}, {bands!r}") from None
+        if not 1 <= num_perm <= cls.MINHASH_MAX_PERM or not 1 <= ngram <= cls.MINHASH_MAX_NGRAM or bands < 0 or (bands and num_perm % bands):
+            raise ValueError(f"num_perm {num_perm}, ngram {ngram}, bands {bands}: num_perm in [1, {cls.MINHASH_MAX_PERM}], ngram in "
+                             f"[1, {cls.MINHASH_MAX_NGRAM}], bands None or a divisor of num_perm")
+        return num_perm, ngram, bands, cls._u64(seed, "seed")
+
+    @classmethod
+    def minhash_params(cls, num_perm: int = 128, seed: int = 0) -> tuple[list[int], list[int]]:
+        """The multiply-shift hash functions of (num_perm, seed) -> (a, b): a_k = rnd(seed, 0x70, k) | 1, b_k = rnd(seed, 0x71, k),
+        and p_k(h) = ((a_k * h + b_k) mod 2^64) >> 32 for a 32-bit shingle hash h."""
+        num_perm, _n, _b, seed = cls._minhash_args(num_perm, 1, None, seed)
+        return [rnd_int(seed, cls._MH_A, k) | 1 for k in range(num_perm)], [rnd_int(seed, cls._MH_B, k) for k in range(num_perm)]
+
+    @classmethod
+    def _shingle_hashes(cls, ids, ngram: int) -> np.ndarray:
+        """The 32-bit hashes of a document's shingles, in order (as u64 values): with m = min(ngram, len(ids)) ids a shingle,
+        s = rnd(0, 0x68, m), then s = mix(s + G * (id + 1)) = rnd(s, 0, id) for its ids in order, h = s >> 32."""
+        ids = np.asarray(ids, dtype=np.uint64)
+        m = min(ngram, len(ids))
+        if m == 0:
+            return np.zeros(0, np.uint64)
+        count = len(ids) - m + 1
+        s = np.full(count, rnd_int(0, cls._MH_SHINGLE, m), np.uint64)
+        for j in range(m):
+            s = rnd(s, 0, ids[j:j + count])
+        return s >> np.uint64(32)
+
+    def minhash_tokens(self, ids_batch, *, num_perm: int = 128, ngram: int = 5, bands: int | None = None, seed: int = 0):
+        """MinHash signatures of id sequences for near-duplicate detection -> (signatures, n_shingles, keys): per document
+        num_perm u32 values, its number of shingles, and with bands its `bands` u64 LSH keys (keys None without).  u64 with
+        wraparound throughout, mix and rnd of synth.py, G = 0x9E3779B97F4A7C15:
+          shingles   a document of L ids has L - ngram + 1, one per window of ngram consecutive ids; one of all its ids when
+                     0 < L < ngram; none when L = 0.
+          hash       of a shingle of m ids: s = rnd(0, 0x68, m), then s = mix(s + G * (id + 1)) for its ids in order; h = s >> 32.
+                     It depends on the ids alone.
+          signature  with (a, b) = minhash_params(num_perm, seed): sig[k] = min over the shingles of ((a_k * h + b_k) mod 2^64)
+                     >> 32; 0xFFFFFFFF in every slot of a document without shingles.  Order and multiplicity of the shingles
+                     do not matter; the share of equal slots of two signatures estimates the Jaccard index of the shingle sets.
+          band keys  bands must divide num_perm, r = num_perm / bands: key[t] = s after s = rnd(0, 0x6b, t) and s =
+                     mix(s + G * (v + 1)) for v = sig[t * r], ..., sig[t * r + r - 1].  Two documents are LSH candidates iff
+                     they have the same key[t] for some band t.
+        num_perm outside [1, 1024], ngram outside [1, 32], bands that does not divide num_perm: ValueError."""
+        num_perm, ngram, bands, seed = self._minhash_args(num_perm, ngram, bands, seed)
+        a, b = (np.asarray(x, dtype=np.uint64) for x in self.minhash_params(num_perm, seed))
+        sigs, counts, keys = [], [], []
+        for ids in ids_batch:
+            h = self._shingle_hashes(ids, ngram)
+            sig = np.full(num_perm, 0xFFFFFFFF, np.uint64)
+            with np.errstate(over="ignore"):
+                for lo in range(0, len(h), 4096):  # (a block of shingles at a time: [block, num_perm] values)
+                    sig = np.minimum(sig, ((a[None, :] * h[lo:lo + 4096, None] + b[None, :]) >> np.uint64(32)).min(axis=0))
+            sig = sig.tolist()
+            sigs.append(sig)
+            counts.append(len(h))
+            if bands:
+                r, row = num_perm // bands, []
+                for t in range(bands):
+                    s = rnd_int(0, self._MH_BAND, t)
+                    for v in sig[t * r:(t + 1) * r]:
+                        s = rnd_int(s, 0, v)
+                    row.append(s)
+                keys.append(row)
+        return sigs, counts, keys if bands else None
+
+    def encode_batch_minhash(self, texts: Sequence[str], **kw):
+        """encode_batch(texts), then minhash_tokens over the ids with the same keyword arguments."""
+        self._minhash_args(kw.get("num_perm", 128), kw.get("ngram", 5), kw.get("bands"), kw.get("seed", 0))  # (refused before any work)
+        return self.minhash_tokens(self.encode_batch(texts), **kw)
+
+    @staticmethod
+    def minhash_jaccard(sig_a, sig_b) -> float:
+        """The share of slots in which two signatures of the same (num_perm, ngram, seed) agree: the MinHash estimate of the
+        Jaccard index of the two shingle sets (standard error sqrt(J (1 - J) / num_perm))."""
+        sig_a, sig_b = np.asarray(sig_a), np.asarray(sig_b)
+        if sig_a.shape != sig_b.shape or sig_a.ndim != 1 or not len(sig_a):
+            raise ValueError("two signatures of the same, non-zero length are needed")
+        return float(np.count_nonzero(sig_a == sig_b)) / len(sig_a)
+
     # ------------------------------------------------------------------ encode on the GPU (yabpe_encode; same ids as encode)
     def _device(self, model: str = "encode"):
         if self._device_ctx is None:
@@ -1740,6 +1830,29 @@ class BBPETokenizer:
         labels, _lengths = ctx.layout_pad_to_host(fl, n_out, fo, n_convs, row_len=rows.shape[1], pad_id=ign, bos_id=None if bos is None else ign,
                                                   eos_id=None if eos is None else ign, **cut)
         return rows, labels.view(np.int32), lengths, info
+
+    def minhash_array(self, ids, doc_off, *, num_perm: int = 128, ngram: int = 5, bands: int | None = None, seed: int = 0):
+        """minhash_tokens on the GPU (yabpe_minhash), value for value: ids and doc_off as encode_array returns them
+        -> (signatures np.uint32[n_docs, num_perm], n_shingles np.uint64[n_docs], keys np.uint64[n_docs, bands] or None)."""
+        num_perm, ngram, bands, seed = self._minhash_args(num_perm, ngram, bands, seed)
+        ids = np.ascontiguousarray(ids, dtype=np.uint32)
+        off = np.asarray(doc_off, dtype=np.int64)
+        if off.ndim != 1 or len(off) < 2 or off[0] != 0 or off[-1] != len(ids) or np.any(np.diff(off) < 0):
+            raise ValueError("doc_off must be n_docs + 1 ascending offsets from 0 to len(ids)")
+        return self._device().minhash_to_host(ids, None, off[:-1].astype(np.uint64), None, num_perm=num_perm, ngram=ngram, bands=bands, seed=seed)
+
+    def encode_array_minhash(self, texts, *, num_perm: int = 128, ngram: int = 5, bands: int | None = None, seed: int = 0, errors: str = "strict"):
+        """encode_batch_minhash(texts, ...), computed on the GPU: yabpe_encode, then yabpe_minhash on its device results (the ids
+        never visit the host).  `texts` and errors as encode_array takes them; the results as minhash_array's."""
+        num_perm, ngram, bands, seed = self._minhash_args(num_perm, ngram, bands, seed)
+        inp = self._device_input(texts)
+        if inp is None:
+            check_errors(errors)
+            return np.zeros((0, num_perm), np.uint32), np.zeros(0, np.uint64), np.zeros((0, bands), np.uint64) if bands else None
+        ctx = self._device()
+        text, n_bytes, starts = self._device_text(ctx, inp, errors)
+        di, dd, ni = ctx.encode(text, n_bytes, doc_starts=starts)
+        return ctx.minhash_to_host(di, ni, dd, len(inp[1]), num_perm=num_perm, ngram=ngram, bands=bands, seed=seed)
 
     def _device_encode_for_layout(self, ctx, inp, dropout=0.0, seed=0, offsets=None):
         """-> (ids pointer, document starts pointer, n_ids, spans): the device results the layout passes read -- yabpe_encode's,
