@@ -1070,6 +1070,52 @@ typedef struct yabpe_minhash_stats_t {
 } yabpe_minhash_stats_t;
 int yabpe_minhash_stats(yabpe_ctx *ctx, yabpe_minhash_stats_t *out);
 
+/* Near-duplicate clusters (BBPETokenizer.minhash_clusters on the device, yet_another_bpe/tokenizer.py) -----------------
+ * From sig u32[n_docs][num_perm], keys u64[n_docs][bands] and optionally shingles u64[n_docs], host or device memory (the
+ * device results of yabpe_minhash go straight in and are left valid and untouched; keys are taken as given, never recomputed):
+ *   takes part  document d iff shingles is NULL or shingles[d] > 0 (documents without shingles all carry the row 0xFFFFFFFF...
+ *               and would form one cluster); one that does not is its own cluster;
+ *   bucket      (t, v): the participating documents with keys[d][t] == v, all 64 bits, the same band t; its anchor is its
+ *               smallest document index;
+ *   candidate   (d, anchor) for every d of a bucket other than its anchor; a pair that several bands give is one candidate;
+ *   accepted    iff sig[d][k] == sig[anchor][k] for at least min_agree values of k (min_agree 0: everything; sig is never read
+ *               and may be NULL).  For a Jaccard threshold: min_agree = ceil(threshold * num_perm);
+ *   cluster[d]  the smallest document index of d's connected component under the accepted edges; cluster[d] == d: keep d.
+ * With min_agree > 0 a document is compared with its buckets' anchors only, not with the other members of those buckets: two
+ * members that both fail against the anchor stay apart unless another band joins them.
+ * Result (device memory owned by the library, in a buffer of its own: a later encode, minhash or layout call leaves it valid;
+ * released by yabpe_minhash_cluster_free, the next yabpe_minhash_cluster or yabpe_destroy): *out_dev_cluster u32[n_docs], NULL
+ * with n_docs == 0.  The hash table has the smallest power of two >= 2 * n_docs * bands of slots, 2^10 at least; the option
+ * "cluster_slots_log2" forces 2^value slots (tests and measurements; 0: auto).
+ * YABPE_E_INVALID: bands == 0 or above 1024, num_perm outside [1, 1024], min_agree > num_perm, sig == NULL with min_agree > 0,
+ * keys == NULL with n_docs > 0, flags other than 0, a forced table of fewer than n_docs * bands + 1 slots.  YABPE_E_CAPACITY:
+ * n_docs * bands > 2^30.  Every error is found before a buffer is allocated. */
+typedef struct yabpe_cluster_t {
+    uint32_t num_perm;   /* K: values of a signature row, 1 .. 1024 */
+    uint32_t bands;      /* B: keys of a row, 1 .. 1024 */
+    uint32_t min_agree;  /* 0 .. num_perm */
+    uint32_t flags;      /* 0 */
+} yabpe_cluster_t;
+int yabpe_minhash_cluster(yabpe_ctx *ctx, const uint32_t *sig, const uint64_t *keys, const uint64_t *shingles, uint32_t n_docs,
+                          const yabpe_cluster_t *rule, uint32_t **out_dev_cluster);
+int yabpe_minhash_cluster_free(yabpe_ctx *ctx);
+/* What the last yabpe_minhash_cluster saw, and its device time.  The integers are functions of the input alone. */
+typedef struct yabpe_cluster_stats_t {
+    uint64_t n_docs;
+    uint64_t n_participating;     /* documents that take part */
+    uint64_t n_entries;           /* n_participating * bands: what the table holds */
+    uint64_t n_candidates;        /* distinct (d, anchor) pairs */
+    uint64_t n_accepted;          /* of them, with min_agree values or more in common */
+    uint64_t n_clusters;          /* components, singletons included */
+    uint64_t n_slots;             /* of the table */
+    double preset_ms;             /* slots, anchors, parents and counters preset */
+    double insert_ms;             /* the table and the anchors */
+    double link_ms;               /* candidates, verification, union-find */
+    double flatten_ms;            /* labels and the cluster count */
+    double total_ms;              /* first to last event of the call */
+} yabpe_cluster_stats_t;
+int yabpe_minhash_cluster_stats(yabpe_ctx *ctx, yabpe_cluster_stats_t *out);
+
 /* Multi-GPU (one process per GPU; words are sharded by the caller) -----------------
  * Every rank holds its shard of the words and a replica of the pair table.  After each apply pass the ranks
  * exchange their aggregated (pair, delta) records with ONE all-gather on the compute stream and every rank adds all

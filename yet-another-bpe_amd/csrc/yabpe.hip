@@ -35,6 +35,7 @@
 #include "yabpe_fitlab_kernels.h"
 #include "yabpe_mask_kernels.h"
 #include "yabpe_minhash_kernels.h"
+#include "yabpe_cluster_kernels.h"
 #include "yabpe_span_kernels.h"
 #include "yabpe_fim_kernels.h"
 #include "yabpe_chat_kernels.h"
@@ -256,6 +257,10 @@ struct yabpe_ctx {
     void *mh_buf[3] = {};
     yabpe_minhash_stats_t mh_stats{};
     hipEvent_t mh_ev[4] = {};
+    // near-duplicate clusters: the result of the last yabpe_minhash_cluster (cluster u32[n_docs])
+    uint32_t *cl_buf = nullptr;
+    yabpe_cluster_stats_t cl_stats{};
+    hipEvent_t cl_ev[5] = {};
     // resumed load (yabpe_load_words_resumed)
     yabpe_resume_stats_t resume_stats{};
     // persistent word pool (yabpe_pool_add / yabpe_pool_get): arena, off / count / hash, slots (pool_logic.h)
@@ -1951,6 +1956,9 @@ void yabpe_destroy(yabpe_ctx *c) {
         if (e) (void)hipEventDestroy(e);
     yabpe_minhash_free(c);
     for (auto &e : c->mh_ev)
+        if (e) (void)hipEventDestroy(e);
+    yabpe_minhash_cluster_free(c);
+    for (auto &e : c->cl_ev)
         if (e) (void)hipEventDestroy(e);
     yabpe_pool_clear(c);
     for (auto &e : c->wpool_ev)
@@ -5858,6 +5866,100 @@ int yabpe_minhash(yabpe_ctx *c, const uint32_t *ids, uint64_t n_ids, const uint6
 int yabpe_minhash_stats(yabpe_ctx *c, yabpe_minhash_stats_t *out) {
     if (!c || !out) return YABPE_E_INVALID;
     *out = c->mh_stats;
+    return YABPE_OK;
+}
+
+// ---------------------------------------------------------------------------------------------- near-duplicate clusters
+int yabpe_minhash_cluster_free(yabpe_ctx *c) {
+    if (!c) return YABPE_E_INVALID;
+    dfree(c->cl_buf);
+    c->cl_buf = nullptr;
+    return YABPE_OK;
+}
+
+// BBPETokenizer.minhash_clusters on the device (yabpe_cluster_kernels.h; the rule: cluster_logic.h).  cl_ev[0..4] bracket the
+// preset, the insert, the link and the flatten launch.  The table is sized by n_docs * bands, the entries of a call in which
+// every document takes part: known before a kernel runs.  A call that the checks refuse has freed nothing.
+int yabpe_minhash_cluster(yabpe_ctx *c, const uint32_t *sig, const uint64_t *keys, const uint64_t *shingles, uint32_t n_docs,
+                          const yabpe_cluster_t *rule, uint32_t **out_dev_cluster) {
+    if (!c || !out_dev_cluster) return YABPE_E_INVALID;
+    HIPCHK(c, hipSetDevice(c->device));
+    *out_dev_cluster = nullptr;
+    if (!rule) return fail(c, YABPE_E_INVALID, "rule is NULL");
+    const ClusterRule R{rule->num_perm, rule->bands, rule->min_agree};
+    if (!cl_rule_valid(R))
+        return fail(c, YABPE_E_INVALID, "num_perm %u, bands %u, min_agree %u: num_perm in [1, %u], bands in [1, %u], min_agree <= num_perm",
+                    R.num_perm, R.bands, R.min_agree, MH_MAX_PERM, CL_MAX_BANDS);
+    if (rule->flags) return fail(c, YABPE_E_INVALID, "unknown cluster flags 0x%x", rule->flags);
+    if (R.min_agree && !sig) return fail(c, YABPE_E_INVALID, "sig is NULL with min_agree %u", R.min_agree);
+    if (n_docs && !keys) return fail(c, YABPE_E_INVALID, "keys is NULL with %u documents", n_docs);
+    const unsigned long long n_all = (unsigned long long)n_docs * R.bands;
+    if (n_all > CL_MAX_ENTRIES) return fail(c, YABPE_E_CAPACITY, "%u documents of %u bands: at most 2^30 entries in one call", n_docs, R.bands);
+    const int64_t forced = optv(c, "cluster_slots_log2", 0);
+    if (forced < 0 || forced > CL_MAX_SLOTS_LOG2 || (forced && (1ull << forced) < n_all + 1))
+        return fail(c, YABPE_E_INVALID, "option cluster_slots_log2 is %lld: 0, or at most %u with 2^it >= entries + 1 = %llu", (long long)forced,
+                    CL_MAX_SLOTS_LOG2, n_all + 1);
+    const uint32_t slots_log2 = forced ? (uint32_t)forced : cl_slots_log2(n_all);
+    const unsigned long long n_slots = 1ull << slots_log2;
+    yabpe_minhash_cluster_free(c);
+    auto &st = c->cl_stats;
+    st = yabpe_cluster_stats_t{};
+    st.n_docs = n_docs;
+    if (!n_docs) return YABPE_OK;
+    st.n_slots = n_slots;
+    for (auto &e : c->cl_ev)
+        if (!e) HIPCHK(c, hipEventCreate(&e));
+    hipStream_t s = c->stream;
+    Scratch S(c->device, c->rank);
+    ClusterParams P{};
+    if (R.min_agree) TRY(to_device(c, S, sig, (uint64_t)n_docs * R.num_perm * 4, 4, &P.sig));
+    TRY(to_device(c, S, (const unsigned long long *)keys, n_all * 8, 8, &P.keys));
+    if (shingles) TRY(to_device(c, S, (const unsigned long long *)shingles, (uint64_t)n_docs * 8, 8, &P.shingles));
+    HIPCHK(c, S.get(&P.table, n_slots));
+    HIPCHK(c, S.get(&P.anchor, n_slots));
+    HIPCHK(c, S.get(&P.slot_of, n_all));
+    HIPCHK(c, S.get(&P.parent, n_docs));
+    HIPCHK(c, S.get(&P.counters, CL_COUNTERS));
+    TRY(dmalloc(c, &c->cl_buf, n_docs));
+    P.n_docs = n_docs;
+    P.rule = R;
+    P.slots_log2 = slots_log2;
+    P.cluster = c->cl_buf;
+    HIPCHK(c, hipEventRecord(c->cl_ev[0], s));
+    hipLaunchKernelGGL(k_cluster_preset, dim3(cdiv64(std::max<unsigned long long>(n_slots, n_docs), BLOCK)), dim3(BLOCK), 0, s, P);
+    (void)hipEventRecord(c->cl_ev[1], s);
+    hipLaunchKernelGGL(k_cluster_insert, dim3(cdiv64(n_all, BLOCK)), dim3(BLOCK), 0, s, P);
+    (void)hipEventRecord(c->cl_ev[2], s);
+    hipLaunchKernelGGL(k_cluster_link, dim3(cdiv64(n_docs, CL_WAVES)), dim3(BLOCK), 0, s, P);
+    (void)hipEventRecord(c->cl_ev[3], s);
+    hipLaunchKernelGGL(k_cluster_flatten, dim3(cdiv64(n_docs, BLOCK)), dim3(BLOCK), 0, s, P);
+    const hipError_t le = hipGetLastError();
+    (void)hipEventRecord(c->cl_ev[4], s);
+    uint32_t h_cnt[CL_COUNTERS] = {};
+    const hipError_t ce = hipMemcpyAsync(h_cnt, P.counters, sizeof h_cnt, hipMemcpyDeviceToHost, s);
+    const hipError_t se = hipStreamSynchronize(s);
+    if (le != hipSuccess || ce != hipSuccess || se != hipSuccess) {
+        yabpe_minhash_cluster_free(c);
+        return fail(c, YABPE_E_HIP, "minhash_cluster: a kernel failed: %s", hipGetErrorString(le != hipSuccess ? le : ce != hipSuccess ? ce : se));
+    }
+    float ms[4] = {0, 0, 0, 0};
+    st.total_ms = pass_times(c->cl_ev, 4, ms);
+    st.preset_ms = ms[0];
+    st.insert_ms = ms[1];
+    st.link_ms = ms[2];
+    st.flatten_ms = ms[3];
+    st.n_participating = h_cnt[CL_C_PARTICIPATING];
+    st.n_entries = (uint64_t)h_cnt[CL_C_PARTICIPATING] * R.bands;
+    st.n_candidates = h_cnt[CL_C_CANDIDATES];
+    st.n_accepted = h_cnt[CL_C_ACCEPTED];
+    st.n_clusters = h_cnt[CL_C_CLUSTERS];
+    *out_dev_cluster = c->cl_buf;
+    return YABPE_OK;
+}
+
+int yabpe_minhash_cluster_stats(yabpe_ctx *c, yabpe_cluster_stats_t *out) {
+    if (!c || !out) return YABPE_E_INVALID;
+    *out = c->cl_stats;
     return YABPE_OK;
 }
 

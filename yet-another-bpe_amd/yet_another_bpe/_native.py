@@ -38,6 +38,7 @@ class SegmentTooLong(ValueError):
         self.position = position
 
 
+E_INVALID = -1
 E_CAPACITY = -4
 E_UTF8 = -7
 NORM_NFC = 1  # yabpe_normalize: form
@@ -140,6 +141,16 @@ class MinhashStats(ctypes.Structure):
         (n, c_double) for n in ("plan_ms", "sig_ms", "keys_ms", "total_ms")]
 
 
+class Cluster(ctypes.Structure):
+    """yabpe_cluster_t"""
+    _fields_ = [(n, c_uint32) for n in ("num_perm", "bands", "min_agree", "flags")]
+
+
+class ClusterStats(ctypes.Structure):
+    _fields_ = [(n, c_uint64) for n in ("n_docs", "n_participating", "n_entries", "n_candidates", "n_accepted", "n_clusters", "n_slots")] + [
+        (n, c_double) for n in ("preset_ms", "insert_ms", "link_ms", "flatten_ms", "total_ms")]
+
+
 class Layout(ctypes.Structure):
     """yabpe_layout_t"""
     _fields_ = [(n, c_uint32) for n in ("row_len", "pad_id", "bos_id", "eos_id", "flags")]
@@ -225,6 +236,7 @@ SYMBOLS = [
     "yabpe_fim_cuts", "yabpe_fim", "yabpe_fim_free", "yabpe_fim_stats",
     "yabpe_chat", "yabpe_chat_free", "yabpe_chat_stats",
     "yabpe_minhash", "yabpe_minhash_free", "yabpe_minhash_stats",
+    "yabpe_minhash_cluster", "yabpe_minhash_cluster_free", "yabpe_minhash_cluster_stats",
     "yabpe_pool_add", "yabpe_pool_get", "yabpe_pool_clear", "yabpe_pool_stats",
     "yabpe_normalize", "yabpe_normalize_free", "yabpe_normalize_stats",
     "yabpe_utf8_repair", "yabpe_utf8_repair_free", "yabpe_utf8_repair_stats",
@@ -325,6 +337,9 @@ def lib() -> ctypes.CDLL:
                                     POINTER(c_void_p)]
         L.yabpe_minhash_free.argtypes = [c_void_p]
         L.yabpe_minhash_stats.argtypes = [c_void_p, POINTER(MinhashStats)]
+        L.yabpe_minhash_cluster.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_uint32, POINTER(Cluster), POINTER(c_void_p)]
+        L.yabpe_minhash_cluster_free.argtypes = [c_void_p]
+        L.yabpe_minhash_cluster_stats.argtypes = [c_void_p, POINTER(ClusterStats)]
         L.yabpe_pool_add.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_uint64]
         L.yabpe_pool_get.argtypes = [c_void_p, POINTER(c_void_p), POINTER(c_void_p), POINTER(c_void_p), POINTER(c_uint64), POINTER(c_uint64)]
         L.yabpe_pool_clear.argtypes = [c_void_p]
@@ -1355,6 +1370,38 @@ class Context:
     def minhash_stats(self) -> dict:
         s = MinhashStats()
         self._chk(lib().yabpe_minhash_stats(self._h, byref(s)))
+        return _stats_dict(s)
+
+    # -- near-duplicate clusters (BBPETokenizer.minhash_clusters on the device)
+    def minhash_cluster(self, sig, keys, n_shingles, n_docs: int, *, num_perm: int, bands: int, min_agree: int = 0) -> int:
+        """Clusters from signatures u32[n_docs, num_perm], keys u64[n_docs, bands] and optionally shingle counts u64[n_docs]
+        (yabpe_minhash_cluster): each a device pointer (minhash()'s results go straight in), a host array or None.
+        -> dev_cluster_ptr u32[n_docs] (0 with n_docs == 0); it lives until the next minhash_cluster, minhash_cluster_free() or close()."""
+        keep = []
+
+        def arg(a, dtype):
+            if a is None or isinstance(a, int):
+                return c_void_p(a or None)
+            keep.append(np.ascontiguousarray(a, dtype=dtype))
+            return c_void_p(keep[-1].ctypes.data)  # (an empty array still is an array: not NULL)
+
+        rule = Cluster(int(num_perm), int(bands), int(min_agree), 0)
+        out = c_void_p()
+        self._chk(lib().yabpe_minhash_cluster(self._h, arg(sig, np.uint32), arg(keys, np.uint64), arg(n_shingles, np.uint64), int(n_docs), byref(rule),
+                                              byref(out)))
+        return out.value or 0
+
+    def minhash_cluster_to_host(self, sig, keys, n_shingles, n_docs: int, **kw) -> np.ndarray:
+        """-> cluster u32[n_docs] copied to the host."""
+        dc = self.minhash_cluster(sig, keys, n_shingles, n_docs, **kw)
+        return self.d2h(dc, 4 * int(n_docs), np.uint32) if n_docs else np.zeros(0, np.uint32)
+
+    def minhash_cluster_free(self) -> None:
+        self._chk(lib().yabpe_minhash_cluster_free(self._h))
+
+    def minhash_cluster_stats(self) -> dict:
+        s = ClusterStats()
+        self._chk(lib().yabpe_minhash_cluster_stats(self._h, byref(s)))
         return _stats_dict(s)
 
     # -- the persistent word pool (corpora larger than device memory: words go in call by call, the merge loop loads the pool)

@@ -18,7 +18,9 @@ chat_array / encode_array_chat compute the same on the GPU (yabpe_chat).  fit_la
 labelled sequences whole into rows, several a row, with the seam records a varlen attention kernel needs; fit_labelled_array /
 encode_array_chat_fit compute the same on the GPU (yabpe_layout_fit_labels).  minhash_tokens / encode_batch_minhash give every
 document a MinHash signature over its id n-grams and LSH band keys, for near-duplicate detection; minhash_array /
-encode_array_minhash compute the same on the GPU (yabpe_minhash).
+encode_array_minhash compute the same on the GPU (yabpe_minhash).  minhash_clusters / encode_batch_clusters turn signatures
+and band keys into the cluster of every document (LSH buckets, verification against the bucket's smallest document, union-find);
+minhash_clusters_array / encode_array_clusters compute the same on the GPU (yabpe_minhash_cluster).
 """
 from __future__ import annotations
 
@@ -1443,6 +1445,104 @@ class BBPETokenizer:
             raise ValueError("two signatures of the same, non-zero length are needed")
         return float(np.count_nonzero(sig_a == sig_b)) / len(sig_a)
 
+    # ------------------------------------------------------------------ near-duplicate clusters (LSH buckets, verification, union-find)
+    CLUSTER_MAX_BANDS, CLUSTER_MAX_ENTRIES = 1024, 1 << 30  # CL_MAX_BANDS, CL_MAX_ENTRIES of csrc/cluster_logic.h
+
+    @classmethod
+    def _cluster_args(cls, signatures, keys, n_shingles, min_agree):
+        """-> (sig u32[n, K] or None, keys u64[n, B], n_shingles u64[n] or None, min_agree), validated as yabpe_minhash_cluster
+        validates them (a missing signatures counts as num_perm = 1)"""
+        try:
+            min_agree = operator.index(min_agree)
+        except TypeError:
+            raise ValueError(f"min_agree must be an integer, not {min_agree!r}") from None
+        keys = np.ascontiguousarray(keys, dtype=np.uint64)
+        if keys.ndim != 2 or not 1 <= keys.shape[1] <= cls.CLUSTER_MAX_BANDS:
+            raise ValueError(f"keys must be [n_docs, bands] with bands in [1, {cls.CLUSTER_MAX_BANDS}], not of shape {keys.shape}")
+        n = len(keys)
+        if keys.size > cls.CLUSTER_MAX_ENTRIES:
+            raise ValueError(f"{n} documents of {keys.shape[1]} bands: at most 2^30 entries in one call")
+        if signatures is not None:
+            signatures = np.ascontiguousarray(signatures, dtype=np.uint32)
+            if signatures.ndim != 2 or len(signatures) != n or not 1 <= signatures.shape[1] <= cls.MINHASH_MAX_PERM:
+                raise ValueError(f"signatures must be [{n}, num_perm] with num_perm in [1, {cls.MINHASH_MAX_PERM}], not of shape {signatures.shape}")
+        if not 0 <= min_agree <= (1 if signatures is None else signatures.shape[1]) or (min_agree and signatures is None):
+            raise ValueError(f"min_agree {min_agree}: in [0, num_perm], and 0 without signatures")
+        if n_shingles is not None:
+            n_shingles = np.ascontiguousarray(n_shingles, dtype=np.uint64)
+            if n_shingles.shape != (n,):
+                raise ValueError(f"n_shingles must hold one count per document ({n}), not {n_shingles.shape}")
+        return signatures, keys, n_shingles, min_agree
+
+    def minhash_clusters(self, signatures, keys, n_shingles=None, *, min_agree: int = 0):
+        """Near-duplicate clusters from what minhash_tokens returns -> (cluster, stats): cluster[d] is the smallest document
+        index of d's cluster, so cluster[d] == d marks the document to keep.  signatures [n, num_perm] u32, keys [n, bands]
+        u64 (taken as given, never recomputed), n_shingles [n] or None.  Integers throughout:
+          takes part  document d iff n_shingles is None or n_shingles[d] > 0 (documents without shingles all carry the row
+                      0xFFFFFFFF... and would form one cluster); one that does not is its own cluster.
+          bucket      (t, v): the participating documents with keys[d][t] == v -- all 64 bits, the same band t.  Its anchor
+                      is its smallest document index.
+          candidate   (d, anchor) for every d of a bucket other than the anchor; a pair from several bands is one candidate.
+          accepted    iff signatures[d] and signatures[anchor] agree in at least min_agree slots.  min_agree = 0 accepts
+                      everything and never reads the signatures (they may be None).  For a Jaccard threshold pass
+                      min_agree = ceil(threshold * num_perm).
+          cluster     the connected components under the accepted edges.
+        With min_agree > 0 a document is compared with its buckets' anchors only, not with the other members of those buckets:
+        two members that both fail against the anchor stay apart unless another band joins them.
+        stats: n_docs, n_participating, n_entries (participating documents x bands), n_candidates, n_accepted, n_clusters
+        (singletons included).  bands or num_perm outside [1, 1024], min_agree outside [0, num_perm], min_agree > 0 without
+        signatures, shapes that do not fit, more than 2^30 entries: ValueError."""
+        sig, keys, cnt, m = self._cluster_args(signatures, keys, n_shingles, min_agree)
+        n, rows = len(keys), keys.tolist()
+        part = [d for d in range(n) if cnt is None or cnt[d] > 0]
+        anchor: dict = {}
+        for d in part:  # (ascending: the first document of a bucket is its smallest)
+            for t, v in enumerate(rows[d]):
+                anchor.setdefault((t, v), d)
+        parent = list(range(n))
+
+        def find(x):
+            while parent[x] != x:
+                parent[x] = parent[parent[x]]
+                x = parent[x]
+            return x
+
+        n_cand = n_acc = 0
+        for d in part:
+            for a in sorted({anchor[(t, v)] for t, v in enumerate(rows[d])} - {d}):
+                n_cand += 1
+                if m == 0 or int(np.count_nonzero(sig[d] == sig[a])) >= m:
+                    n_acc += 1
+                    ra, rb = find(d), find(a)
+                    parent[max(ra, rb)] = min(ra, rb)  # (the smaller root stays the root: it is its tree's minimum)
+        cluster = [find(d) for d in range(n)]
+        stats = {"n_docs": n, "n_participating": len(part), "n_entries": len(part) * keys.shape[1], "n_candidates": n_cand, "n_accepted": n_acc,
+                 "n_clusters": sum(c == d for d, c in enumerate(cluster))}
+        return cluster, stats
+
+    def encode_batch_clusters(self, texts: Sequence[str], *, num_perm: int = 128, ngram: int = 5, bands: int | None = None, seed: int = 0,
+                              min_agree: int = 0):
+        """encode_batch_minhash(texts, ...), then minhash_clusters over its results -> (cluster, n_shingles).  bands is required."""
+        self._clusters_kw(num_perm, ngram, bands, seed, min_agree)  # (refused before any work)
+        sig, cnt, keys = self.encode_batch_minhash(texts, num_perm=num_perm, ngram=ngram, bands=bands, seed=seed)
+        if not sig:
+            return [], []
+        return self.minhash_clusters(sig, keys, cnt, min_agree=min_agree)[0], cnt
+
+    @classmethod
+    def _clusters_kw(cls, num_perm, ngram, bands, seed, min_agree):
+        """the arguments of encode_batch_clusters / encode_array_clusters -> (num_perm, ngram, bands, seed, min_agree)"""
+        num_perm, ngram, bands, seed = cls._minhash_args(num_perm, ngram, bands, seed)
+        if not bands:
+            raise ValueError("bands is required: clusters come from the band keys")
+        try:
+            min_agree = operator.index(min_agree)
+        except TypeError:
+            raise ValueError(f"min_agree must be an integer, not {min_agree!r}") from None
+        if not 0 <= min_agree <= num_perm:
+            raise ValueError(f"min_agree {min_agree}: in [0, num_perm = {num_perm}]")
+        return num_perm, ngram, bands, seed, min_agree
+
     # ------------------------------------------------------------------ encode on the GPU (yabpe_encode; same ids as encode)
     def _device(self, model: str = "encode"):
         if self._device_ctx is None:
@@ -1853,6 +1953,31 @@ class BBPETokenizer:
         text, n_bytes, starts = self._device_text(ctx, inp, errors)
         di, dd, ni = ctx.encode(text, n_bytes, doc_starts=starts)
         return ctx.minhash_to_host(di, ni, dd, len(inp[1]), num_perm=num_perm, ngram=ngram, bands=bands, seed=seed)
+
+    def minhash_clusters_array(self, signatures, keys, n_shingles=None, *, min_agree: int = 0):
+        """minhash_clusters on the GPU (yabpe_minhash_cluster), value for value, from host arrays (device pointers go through
+        Context.minhash_cluster) -> (cluster np.uint32[n_docs], stats: minhash_clusters' and n_slots and the device times)."""
+        sig, keys, cnt, m = self._cluster_args(signatures, keys, n_shingles, min_agree)
+        ctx = self._device()
+        cluster = ctx.minhash_cluster_to_host(sig, keys, cnt, len(keys), num_perm=1 if sig is None else sig.shape[1], bands=keys.shape[1], min_agree=m)
+        return cluster, ctx.minhash_cluster_stats()
+
+    def encode_array_clusters(self, texts, *, num_perm: int = 128, ngram: int = 5, bands: int | None = None, seed: int = 0, min_agree: int = 0,
+                              errors: str = "strict"):
+        """encode_batch_clusters(texts, ...), computed on the GPU: yabpe_encode, yabpe_minhash on its device results, then
+        yabpe_minhash_cluster on those (nothing visits the host in between) -> (cluster np.uint32[n_docs], n_shingles
+        np.uint64[n_docs]).  `texts` and errors as encode_array takes them; bands is required."""
+        num_perm, ngram, bands, seed, min_agree = self._clusters_kw(num_perm, ngram, bands, seed, min_agree)
+        inp = self._device_input(texts)
+        if inp is None:
+            check_errors(errors)
+            return np.zeros(0, np.uint32), np.zeros(0, np.uint64)
+        ctx = self._device()
+        text, n_bytes, starts = self._device_text(ctx, inp, errors)
+        di, dd, ni = ctx.encode(text, n_bytes, doc_starts=starts)
+        ds, dn, dk, nd = ctx.minhash(di, ni, dd, len(inp[1]), num_perm=num_perm, ngram=ngram, bands=bands, seed=seed)
+        cluster = ctx.minhash_cluster_to_host(ds, dk, dn, nd, num_perm=num_perm, bands=bands, min_agree=min_agree)
+        return cluster, ctx.d2h(dn, 8 * nd, np.uint64)
 
     def _device_encode_for_layout(self, ctx, inp, dropout=0.0, seed=0, offsets=None):
         """-> (ids pointer, document starts pointer, n_ids, spans): the device results the layout passes read -- yabpe_encode's,
