@@ -210,6 +210,31 @@ __device__ __forceinline__ SigProbe sig_probe(const unsigned long long *sig, uin
 // the wait-count pass has to see it.)  gfx9 encoding: vmcnt 0, expcnt 7, lgkmcnt 15.
 __device__ __forceinline__ void vm_drain() { __builtin_amdgcn_s_waitcnt(0x0F70); }
 
+// A value of the kernel's argument segment, loaded WHERE IT IS USED (off: its byte offset in the segment).  A by-value
+// argument is otherwise loaded at the kernel's entry and kept until its last use; in a kernel that is out of scalar
+// registers (k_scan_skip) it then sits in the lanes of a spill VGPR, and whatever a loop touches of it, even on a path
+// that is never taken, is moved in and out of the lanes inside that loop (tools/spill_report.py).  The pointer is made
+// opaque here, so the loads cannot be hoisted above this point: cold groups (the riders', the selection's, the pair table
+// of a rare path) cost a scalar load where they are needed and nothing anywhere else.
+// (A typed pointer into the constant address space: aligned dwords at a uniform address, i.e. scalar loads.)
+template <class T>
+__device__ __forceinline__ T kernarg_read(uint32_t off) {
+    typedef const __attribute__((address_space(4))) unsigned char *BytePtr;
+    typedef const __attribute__((address_space(4))) T *Ptr;
+    Ptr p = (Ptr)((BytePtr)__builtin_amdgcn_kernarg_segment_ptr() + off);
+    asm volatile("" : "+s"(p));
+    T v;
+    __builtin_memcpy(&v, p, sizeof(T));
+    return v;
+}
+// The pair table as the delta helpers take it (agg_add, agg_add_wave): the table itself, or the place of one in the
+// argument segment -- read only by the path that leaves the LDS aggregator and goes straight to HBM (pt_get).
+template <uint32_t OFF>
+struct KernargTable {};
+__device__ __forceinline__ const PairTable &pt_get(const PairTable &t) { return t; }
+template <uint32_t OFF>
+__device__ __forceinline__ PairTable pt_get(KernargTable<OFF>) { return kernarg_read<PairTable>(OFF); }
+
 // Within one wave LDS operations complete in order; this keeps the compiler from moving a lane's LDS reads
 // above other lanes' LDS writes.
 __device__ __forceinline__ void wave_sync() {
@@ -348,8 +373,8 @@ __device__ __forceinline__ void agg_init(Agg<V> g, int nt = BLOCK) { // nt: thre
     }
 }
 
-template <class V>
-__device__ __forceinline__ void agg_add(Agg<V> g, const PairTable &t, DevState *st, uint32_t key, long long d) {
+template <class V, class Tab>
+__device__ __forceinline__ void agg_add(Agg<V> g, const Tab &t, DevState *st, uint32_t key, long long d) { // Tab: PairTable or KernargTable
     uint32_t s = hash32(key) & g.mask;
 #pragma unroll 1
     for (int probe = 0; probe < 8; ++probe) {
@@ -364,7 +389,7 @@ __device__ __forceinline__ void agg_add(Agg<V> g, const PairTable &t, DevState *
         }
         s = (s + 1) & g.mask;
     }
-    gt_add(t, st, key, d); // aggregator full around this hash: go straight to HBM
+    gt_add(pt_get(t), st, key, d); // aggregator full around this hash: go straight to HBM
     vm_drain();            // (rare path; see vm_drain)
 }
 
@@ -395,7 +420,8 @@ struct KeyMemo {
 
 // Flat layout: lanes of one wave usually carry the same few keys (Zipf) -- peel the hottest keys off with
 // ballots so that one lane adds the wave's total instead of 64 lanes serialising on one LDS address.
-__device__ __forceinline__ void agg_add_wave(Agg<int> g, const PairTable &t, DevState *st, bool valid, uint32_t key,
+template <class Tab>
+__device__ __forceinline__ void agg_add_wave(Agg<int> g, const Tab &t, DevState *st, bool valid, uint32_t key,
                                              int sign, int lane, KeyMemo &memo, int role) {
     unsigned long long pend = __ballot(valid);
 #pragma unroll 1
@@ -421,7 +447,7 @@ __device__ __forceinline__ void agg_add_wave(Agg<int> g, const PairTable &t, Dev
                 if (slot < (uint32_t)AGG_N) {
                     atomicAdd(&g.vals[slot], sum);
                 } else {
-                    gt_add(t, st, k, (long long)sum); // aggregator full around this hash: straight to HBM
+                    gt_add(pt_get(t), st, k, (long long)sum); // aggregator full around this hash: straight to HBM
                     vm_drain();
                 }
             }
@@ -861,8 +887,9 @@ __device__ unsigned long long g_slow_prof[8]; // [0] tiles, [1..5] cycles per ph
 #define YB_STAMP(i) do { } while (0)
 #endif
 
-// What a workgroup needs to run the slow path
-template <class AggV>
+// What a workgroup needs to run the slow path.  TAB_OFF != 0 (k_scan_skip): where the pair table stands in the kernel's
+// argument segment -- P.out is then not used by the rewrite, and nothing of the table lives through the caller's loop.
+template <class AggV, uint32_t TAB_OFF = 0>
 struct SlowCtx {
     ApplyParams P;
     Agg<AggV> agg;
@@ -871,6 +898,9 @@ struct SlowCtx {
     int lane;
     KeyMemo memo; // wave-uniform
     int *hist;    // != NULL: the direct-indexed delta store (Hist) is in use instead of agg
+    __device__ __forceinline__ auto table() const { // where the deltas go when the aggregator cannot take them
+        if constexpr (TAB_OFF != 0) return KernargTable<TAB_OFF>{}; else return P.out;
+    }
 };
 
 // slot q of the tile (wave-uniform q), read out of the registers that hold the tile: lane (q>>3)&63 owns it
@@ -909,8 +939,8 @@ __device__ unsigned long long g_ss_prof[8];
 // DEFER (batched sparse launch: several merges may rewrite the same tile one after the other): nothing is stored -- the
 // rewritten tile replaces `r`, `len` becomes its new length and `first_changed` the first slot that differs from HBM; the
 // caller writes the tile back once, after the last merge of the batch has seen it.
-template <class AggV, bool HIST = false, bool WEIGHTED = false, bool DEFER = false>
-__device__ __forceinline__ void single_site_tile(SlowCtx<AggV> &C, uint32_t tile, uint32_t &len, TileRegs &r,
+template <class AggV, bool HIST = false, bool WEIGHTED = false, bool DEFER = false, uint32_t TAB_OFF = 0>
+__device__ __forceinline__ void single_site_tile(SlowCtx<AggV, TAB_OFF> &C, uint32_t tile, uint32_t &len, TileRegs &r,
                                                  int lane_s, uint32_t mm_s, unsigned long long &wave_sites,
                                                  unsigned long long &wave_freed, uint32_t &first_changed) {
     const ApplyParams &P = C.P;
@@ -1027,7 +1057,7 @@ __device__ __forceinline__ void single_site_tile(SlowCtx<AggV> &C, uint32_t tile
         if constexpr (HIST) { // lane = role: (L,a) -1, (L,c) +1, (b,R) -1, (c,R) +1
             if (on) atomicAdd(&C.hist[lane * HIST_V + (int)(lane < 2 ? L : R)], (lane & 1) ? 1 : -1);
         } else {
-            if (on) agg_add(C.agg, P.out, st, lane < 2 ? kl : kr, (lane & 1) ? w : -w);
+            if (on) agg_add(C.agg, C.table(), st, lane < 2 ? kl : kr, (lane & 1) ? w : -w);
         }
     }
     YB_SS_STAMP(2);
@@ -1039,8 +1069,8 @@ __device__ __forceinline__ void single_site_tile(SlowCtx<AggV> &C, uint32_t tile
 // write-back.  Work is proportional to the number of sites.  Returns false when nothing changed.
 // HAVE_MASKS: the caller has the candidate masks of the two segments already (match_mask8): pmA, pmB.
 // DEFER: see single_site_tile -- the compacted tile is read back from the LDS image into `r` instead of being stored.
-template <bool WEIGHTED, class AggV, bool HIST = false, bool HAVE_MASKS = false, bool DEFER = false>
-__device__ __forceinline__ bool slow_tile(SlowCtx<AggV> &C, WaveLds &W, uint32_t tile, uint32_t &len_io, TileRegs &r,
+template <bool WEIGHTED, class AggV, bool HIST = false, bool HAVE_MASKS = false, bool DEFER = false, uint32_t TAB_OFF = 0>
+__device__ __forceinline__ bool slow_tile(SlowCtx<AggV, TAB_OFF> &C, WaveLds &W, uint32_t tile, uint32_t &len_io, TileRegs &r,
                                           uint32_t na, uint32_t nb, unsigned long long &wave_sites,
                                           unsigned long long &wave_freed, uint32_t &first_changed, uint32_t pmA = 0u, uint32_t pmB = 0u) {
     const uint32_t len = len_io;
@@ -1142,12 +1172,12 @@ __device__ __forceinline__ bool slow_tile(SlowCtx<AggV> &C, WaveLds &W, uint32_t
                 const uint32_t widx = wbase + W.spref[p >> 5] + __popc(sw & ((1u << (p & 31)) - 1u));
                 const long long w = (long long)P.wfreq[widx];
                 if (d.left) {
-                    if (d.lo != self) agg_add(C.agg, P.out, st, d.lo, -w);
-                    agg_add(C.agg, P.out, st, d.ln, +w);
+                    if (d.lo != self) agg_add(C.agg, C.table(), st, d.lo, -w);
+                    agg_add(C.agg, C.table(), st, d.ln, +w);
                 }
                 if (d.right) {
-                    if (d.ro != self) agg_add(C.agg, P.out, st, d.ro, -w);
-                    agg_add(C.agg, P.out, st, d.rn, +w);
+                    if (d.ro != self) agg_add(C.agg, C.table(), st, d.ro, -w);
+                    agg_add(C.agg, C.table(), st, d.rn, +w);
                 }
             }
         } else if constexpr (HIST) { // (every delta has one fixed half: the other one is the index -- see Hist)
@@ -1157,10 +1187,10 @@ __device__ __forceinline__ bool slow_tile(SlowCtx<AggV> &C, WaveLds &W, uint32_t
             if (d.right && d.ro != self) atomicAdd(&C.hist[2 * HIST_V + (int)(d.ro & 0xffffu)], -1);
             if (d.right) atomicAdd(&C.hist[3 * HIST_V + (int)(d.rn & 0xffffu)], 1);
         } else {
-            agg_add_wave(C.agg, P.out, st, d.left && d.lo != self, d.lo, -1, lane, C.memo, 0);
-            agg_add_wave(C.agg, P.out, st, d.left, d.ln, +1, lane, C.memo, 1);
-            agg_add_wave(C.agg, P.out, st, d.right && d.ro != self, d.ro, -1, lane, C.memo, 2);
-            agg_add_wave(C.agg, P.out, st, d.right, d.rn, +1, lane, C.memo, 3);
+            agg_add_wave(C.agg, C.table(), st, d.left && d.lo != self, d.lo, -1, lane, C.memo, 0);
+            agg_add_wave(C.agg, C.table(), st, d.left, d.ln, +1, lane, C.memo, 1);
+            agg_add_wave(C.agg, C.table(), st, d.right && d.ro != self, d.ro, -1, lane, C.memo, 2);
+            agg_add_wave(C.agg, C.table(), st, d.right, d.rn, +1, lane, C.memo, 3);
         }
     }
     wave_sync();
@@ -3144,7 +3174,13 @@ __device__ __forceinline__ bool scan_skip_block(DevState *st, const ScanSkipPara
     // (the second round's counter: the 8-wave form only.  The 16-wave form is chosen where the stream fits ONE round of its
     // workgroups; forced on a longer stream it deals the second round by workgroup index -- it has no register to spare)
     constexpr bool DYN = NW == 8;
-    __shared__ uint32_t s_n, s_claim;             // entries on the hit list; the next one no wave has taken yet
+    // Q in the argument segment (it follows the DevState pointer).  What the candidate loop does not touch is read from
+    // there by the role that needs it, behind the role branch (kernarg_read): the riders' parameters, the selection's, and
+    // the pair table -- the flush's after the loop, the rewrite's only on the path that leaves the LDS aggregator.
+    constexpr uint32_t Q_OFF = 8;
+    static_assert(alignof(ScanSkipParams) == 8, "Q follows the 8-byte first argument without padding");
+    constexpr uint32_t TAB_OFF = Q_OFF + offsetof(ScanSkipParams, A) + offsetof(ApplyParams, out);
+    __shared__ uint32_t s_n, s_claim;            // entries on the hit list; the next one no wave has taken yet
     __shared__ uint32_t s_piece;                  // second round: the piece thread 0 took for the workgroup
     __shared__ uint2 s_list[NT * KTM];            // (tile, live length | merges noted << 16)
     __shared__ uint32_t s_keys[AGG_N];
@@ -3189,17 +3225,17 @@ __device__ __forceinline__ bool scan_skip_block(DevState *st, const ScanSkipPara
     if (blockIdx.x >= Q.scan_blocks) {
         if (NW > WPB && threadIdx.x >= BLOCK) return false; // (lexrank maintenance and the long words are written for BLOCK threads: the other waves end here)
         if (blockIdx.x >= Q.long_first)
-            apply_long_block(Q.LW, blockIdx.x - Q.long_first);
+            apply_long_block(kernarg_read<LongParams>(Q_OFF + offsetof(ScanSkipParams, LW)), blockIdx.x - Q.long_first);
         else
-            rank_update_block(Q.R, blockIdx.x - Q.scan_blocks);
+            rank_update_block(kernarg_read<RankParams>(Q_OFF + offsetof(ScanSkipParams, R)), blockIdx.x - Q.scan_blocks);
         YB_SCAN_STAMP(7);
         YB_LAUNCH_END(prof_it);
         return true;
     }
     const uint32_t n_blocks = Q.scan_blocks;
     const uint32_t nbatch = __builtin_amdgcn_readfirstlane(nb_);
-    SlowCtx<AggV> C{P, Agg<AggV>{s_keys, s_vals, P.agg_mask}, st, 0u, 0u, 0u, 0u, 0u, lane,
-                    KeyMemo{{EMPTY, EMPTY, EMPTY, EMPTY}, {0u, 0u, 0u, 0u}}};
+    SlowCtx<AggV, TAB_OFF> C{P, Agg<AggV>{s_keys, s_vals, P.agg_mask}, st, 0u, 0u, 0u, 0u, 0u, lane,
+                             KeyMemo{{EMPTY, EMPTY, EMPTY, EMPTY}, {0u, 0u, 0u, 0u}}};
     WaveLds &W = s_w[wib];
     __syncthreads();
     YB_SCAN_STAMP(6); // (profile build: LDS tables initialised)
@@ -3394,7 +3430,8 @@ __device__ __forceinline__ bool scan_skip_block(DevState *st, const ScanSkipPara
 #ifdef YB_PROFILE_LAUNCH
     const unsigned long long prof_tc = wall_clock64(); // (every wave of the workgroup has left the candidate loop)
 #endif
-    apply_epilogue<AggV, NT>(P, C.agg, st, s_cnt, wave_sites, wave_freed, lane);
+    // (the table and the counters' place: read here, once per workgroup, not carried through the loop)
+    apply_epilogue<AggV, NT>(kernarg_read<ApplyParams>(Q_OFF + offsetof(ScanSkipParams, A)), C.agg, st, s_cnt, wave_sites, wave_freed, lane);
     YB_SCAN_STAMP(7);
 #ifdef YB_PROFILE_LAUNCH
     YB_LAUNCH_WG_END(prof_it, n_read, prof_tc);
@@ -3409,7 +3446,8 @@ template <bool WEIGHTED, int NW>
 __global__ __launch_bounds__(NW * 64, 16 / NW) void k_scan_skip(DevState *st, ScanSkipParams Q) { // (NW = 8 or 16; <= 128 VGPRs, 16 waves per CU)
     __shared__ WinEnt s_selwin[WIN];
     if (!scan_skip_block<WEIGHTED, NW>(st, Q)) return;
-    fused_select_tail(Q.F, s_selwin);
+    // (the selection's parameters: read by the workgroup that gets here, in one trip with the ticket's address)
+    fused_select_tail(kernarg_read<FuseParams>(8 + offsetof(ScanSkipParams, F)), s_selwin);
 }
 
 // ================================================================ table growth: re-insert live entries (count != 0)
