@@ -1116,6 +1116,52 @@ typedef struct yabpe_cluster_stats_t {
 } yabpe_cluster_stats_t;
 int yabpe_minhash_cluster_stats(yabpe_ctx *ctx, yabpe_cluster_stats_t *out);
 
+/* Exact-substring duplicates (BBPETokenizer.duplicate_spans on the device, yet_another_bpe/tokenizer.py) -----------------
+ * Every run of min_len = n ids that occurs again inside the call's ids, marked and optionally removed (the first occurrence
+ * stays).  ids / doc_off / n_docs as yabpe_minhash takes them, host or device memory; yabpe_encode's device results go straight
+ * in and are left untouched.  Integers only:
+ *   window     n consecutive ids inside one document: global position p starts one iff p + n <= the end of p's document;
+ *   first[p]   the smallest global position whose window holds the same n ids as p's, in any document;
+ *   repeat     window p iff first[p] + n <= p: an equal window ends at or before p begins (a run of one id of length L >= 2 n
+ *              keeps n ids and loses L - n; a shorter one loses nothing);
+ *   dup[i]     1 iff i lies inside a repeat window of its document; n_dup[d] counts them; a span is a maximal run of them;
+ *   compact    with YABPE_DUP_COMPACT: the ids with dup == 0 in order and their n_docs + 1 document offsets (a document may
+ *              become empty).
+ * Results (device memory owned by the library, in buffers of their own: a later encode, minhash or layout call leaves them
+ * valid; released by yabpe_dup_spans_free, the next yabpe_dup_spans or yabpe_destroy): *out_dev_dup u8[n_ids], *out_dev_n_dup
+ * u64[n_docs]; with YABPE_DUP_COMPACT *out_dev_ids u32[*out_n_kept] and *out_dev_off u64[n_docs + 1], NULL without (these
+ * three pointers may be NULL when the flag is not set).  *out_n_kept = n_ids - the duplicated ids, with or without the flag.
+ * The hash table has the smallest power of two >= 2 * windows of slots, 2^10 at least; the option "dup_slots_log2" forces
+ * 2^value slots (tests and measurements; 0: auto).
+ * YABPE_E_INVALID: min_len outside [1, 1024], unknown flags, a doc_off that does not ascend from 0 inside the ids, a forced
+ * table of fewer than windows + 1 slots.  YABPE_E_CAPACITY: more than 2^30 ids.  Every error is found before a buffer is
+ * allocated. */
+#define YABPE_DUP_COMPACT 1u
+typedef struct yabpe_dup_t {
+    uint32_t min_len;    /* n: 1 .. 1024 */
+    uint32_t flags;      /* 0 or YABPE_DUP_COMPACT */
+} yabpe_dup_t;
+int yabpe_dup_spans(yabpe_ctx *ctx, const uint32_t *ids, uint64_t n_ids, const uint64_t *doc_off, uint32_t n_docs,
+                    const yabpe_dup_t *rule, uint8_t **out_dev_dup, uint64_t **out_dev_n_dup, uint32_t **out_dev_ids,
+                    uint64_t *out_n_kept, uint64_t **out_dev_off);
+int yabpe_dup_spans_free(yabpe_ctx *ctx);
+/* What the last yabpe_dup_spans saw, and its device time.  The integers are functions of the input alone. */
+typedef struct yabpe_dup_stats_t {
+    uint64_t n_ids, n_docs;
+    uint64_t n_windows;           /* over all documents: what the table holds */
+    uint64_t n_repeats;           /* windows with an equal window that ends at or before their start */
+    uint64_t n_dup_ids;           /* ids inside a repeat window */
+    uint64_t n_spans;             /* maximal runs of them */
+    uint64_t n_kept;              /* n_ids - n_dup_ids */
+    uint64_t n_slots;             /* of the table */
+    double plan_ms;               /* counts, scans, the table preset */
+    double insert_ms;             /* window hashes and the table */
+    double mark_ms;               /* repeat flags, the mask, the counts */
+    double compact_ms;            /* the scan and the scatter (0 without YABPE_DUP_COMPACT) */
+    double total_ms;              /* first to last event of the call */
+} yabpe_dup_stats_t;
+int yabpe_dup_spans_stats(yabpe_ctx *ctx, yabpe_dup_stats_t *out);
+
 /* Multi-GPU (one process per GPU; words are sharded by the caller) -----------------
  * Every rank holds its shard of the words and a replica of the pair table.  After each apply pass the ranks
  * exchange their aggregated (pair, delta) records with ONE all-gather on the compute stream and every rank adds all

@@ -36,6 +36,7 @@
 #include "yabpe_mask_kernels.h"
 #include "yabpe_minhash_kernels.h"
 #include "yabpe_cluster_kernels.h"
+#include "yabpe_dup_kernels.h"
 #include "yabpe_span_kernels.h"
 #include "yabpe_fim_kernels.h"
 #include "yabpe_chat_kernels.h"
@@ -261,6 +262,10 @@ struct yabpe_ctx {
     uint32_t *cl_buf = nullptr;
     yabpe_cluster_stats_t cl_stats{};
     hipEvent_t cl_ev[5] = {};
+    // exact-substring duplicates: the results of the last yabpe_dup_spans (dup u8[n_ids], n_dup u64[n_docs], kept ids, their offsets)
+    void *dup_buf[4] = {};
+    yabpe_dup_stats_t dup_stats{};
+    hipEvent_t dup_ev[5] = {};
     // resumed load (yabpe_load_words_resumed)
     yabpe_resume_stats_t resume_stats{};
     // persistent word pool (yabpe_pool_add / yabpe_pool_get): arena, off / count / hash, slots (pool_logic.h)
@@ -1959,6 +1964,9 @@ void yabpe_destroy(yabpe_ctx *c) {
         if (e) (void)hipEventDestroy(e);
     yabpe_minhash_cluster_free(c);
     for (auto &e : c->cl_ev)
+        if (e) (void)hipEventDestroy(e);
+    yabpe_dup_spans_free(c);
+    for (auto &e : c->dup_ev)
         if (e) (void)hipEventDestroy(e);
     yabpe_pool_clear(c);
     for (auto &e : c->wpool_ev)
@@ -5960,6 +5968,152 @@ int yabpe_minhash_cluster(yabpe_ctx *c, const uint32_t *sig, const uint64_t *key
 int yabpe_minhash_cluster_stats(yabpe_ctx *c, yabpe_cluster_stats_t *out) {
     if (!c || !out) return YABPE_E_INVALID;
     *out = c->cl_stats;
+    return YABPE_OK;
+}
+
+// ---------------------------------------------------------------------------------------------- exact-substring duplicates
+int yabpe_dup_spans_free(yabpe_ctx *c) {
+    if (!c) return YABPE_E_INVALID;
+    for (auto &p : c->dup_buf) {
+        dfree(p);
+        p = nullptr;
+    }
+    return YABPE_OK;
+}
+
+// BBPETokenizer.duplicate_spans on the device (yabpe_dup_kernels.h; the rule: dup_logic.h).  dup_ev[0..4] bracket the plan
+// (counts, two scans, the table preset), the insert, the mark and the compaction.  The window count, and with it the table
+// size and both grids, come from the validated starts on the host: known before a kernel runs.  The kept ids get a buffer of
+// n_ids, their count being known only at the end.  A call that the checks refuse has freed nothing.
+int yabpe_dup_spans(yabpe_ctx *c, const uint32_t *ids, uint64_t n_ids, const uint64_t *doc_off, uint32_t n_docs, const yabpe_dup_t *rule,
+                    uint8_t **out_dev_dup, uint64_t **out_dev_n_dup, uint32_t **out_dev_ids, uint64_t *out_n_kept, uint64_t **out_dev_off) {
+    if (!c || !out_dev_dup || !out_dev_n_dup) return YABPE_E_INVALID;
+    HIPCHK(c, hipSetDevice(c->device));
+    *out_dev_dup = nullptr; *out_dev_n_dup = nullptr;
+    if (out_dev_ids) *out_dev_ids = nullptr;
+    if (out_dev_off) *out_dev_off = nullptr;
+    if (out_n_kept) *out_n_kept = 0;
+    if (!rule) return fail(c, YABPE_E_INVALID, "rule is NULL");
+    if (!dup_rule_valid(rule->min_len, rule->flags))
+        return fail(c, YABPE_E_INVALID, "min_len %u, flags 0x%x: min_len in [1, %u], flags 0 or YABPE_DUP_COMPACT", rule->min_len, rule->flags, DUP_MAX_LEN);
+    const bool compact = rule->flags & DUP_F_COMPACT;
+    if (compact && (!out_dev_ids || !out_dev_off || !out_n_kept)) return fail(c, YABPE_E_INVALID, "YABPE_DUP_COMPACT needs out_dev_ids, out_n_kept and out_dev_off");
+    if (n_ids > DUP_MAX_IDS) return fail(c, YABPE_E_CAPACITY, "%llu ids: at most 2^30 in one call", (unsigned long long)n_ids);
+    if (n_ids && !ids) return fail(c, YABPE_E_INVALID, "ids is NULL");
+    if (!doc_off && n_docs > 1) return fail(c, YABPE_E_INVALID, "doc_off is NULL with %u documents", n_docs);
+    const bool docs_dev = doc_off && is_device_ptr(doc_off);
+    if (!doc_off) n_docs = n_docs || n_ids ? 1 : 0;
+    std::vector<uint64_t> h_docs(n_docs, 0);
+    if (doc_off && n_docs) {
+        if (docs_dev) HIPCHK(c, hipMemcpy(h_docs.data(), doc_off, (size_t)n_docs * 8, hipMemcpyDeviceToHost));
+        else memcpy(h_docs.data(), doc_off, (size_t)n_docs * 8);
+    }
+    if (n_docs || n_ids) TRY(check_starts(c, h_docs.data(), n_docs, n_ids, "ids"));
+    const uint32_t n = rule->min_len;
+    unsigned long long n_windows = 0, n_pieces = 0, n_tiles = 0;
+    for (uint32_t d = 0; d < n_docs; ++d) {
+        const unsigned long long L = (d + 1 < n_docs ? h_docs[d + 1] : n_ids) - h_docs[d], W = dup_windows(L, n);
+        n_windows += W;
+        n_pieces += dup_tiles(W);
+        n_tiles += dup_tiles(L);
+    }
+    const int64_t forced = optv(c, "dup_slots_log2", 0);
+    if (forced < 0 || forced > DUP_MAX_SLOTS_LOG2 || (forced && (1ull << forced) < n_windows + 1))
+        return fail(c, YABPE_E_INVALID, "option dup_slots_log2 is %lld: 0, or at most %u with 2^it >= windows + 1 = %llu", (long long)forced,
+                    DUP_MAX_SLOTS_LOG2, n_windows + 1);
+    const uint32_t slots_log2 = forced ? (uint32_t)forced : dup_slots_log2(n_windows);
+    const unsigned long long n_slots = 1ull << slots_log2;
+    yabpe_dup_spans_free(c);
+    auto &st = c->dup_stats;
+    st = yabpe_dup_stats_t{};
+    st.n_ids = n_ids;
+    st.n_docs = n_docs;
+    st.n_windows = n_windows;
+    st.n_kept = n_ids;
+    if (!n_docs) return YABPE_OK;
+    st.n_slots = n_slots;
+    for (auto &e : c->dup_ev)
+        if (!e) HIPCHK(c, hipEventCreate(&e));
+    hipStream_t s = c->stream;
+    Scratch S(c->device, c->rank);
+    DupParams P{};
+    unsigned long long *piece_off = nullptr, *tile_off = nullptr, *dup_off = nullptr;
+    TRY(to_device(c, S, ids, n_ids * 4, 4, &P.ids));
+    TRY(to_device(c, S, docs_dev ? (const unsigned long long *)doc_off : (const unsigned long long *)h_docs.data(), (uint64_t)n_docs * 8, 8, &P.doc_off));
+    HIPCHK(c, S.get(&P.pieces, n_docs));
+    HIPCHK(c, S.get(&P.tiles, n_docs));
+    HIPCHK(c, S.get(&piece_off, (uint64_t)n_docs + 1));
+    HIPCHK(c, S.get(&tile_off, (uint64_t)n_docs + 1));
+    HIPCHK(c, S.get(&P.table, n_slots));
+    HIPCHK(c, S.get(&P.slot_of, n_ids));
+    HIPCHK(c, S.get(&P.counters, DUP_COUNTERS));
+    if (compact) HIPCHK(c, S.get(&dup_off, n_ids + 1));
+    TRY(dmalloc(c, (uint8_t **)&c->dup_buf[0], n_ids));
+    TRY(dmalloc(c, (unsigned long long **)&c->dup_buf[1], n_docs));
+    if (compact) {
+        TRY(dmalloc(c, (uint32_t **)&c->dup_buf[2], n_ids));
+        TRY(dmalloc(c, (unsigned long long **)&c->dup_buf[3], (uint64_t)n_docs + 1));
+    }
+    P.n_ids = (uint32_t)n_ids;
+    P.n_docs = n_docs;
+    P.n = n;
+    P.pow_n = dup_pow(DUP_B, n);
+    P.slots_log2 = slots_log2;
+    P.piece_off = piece_off;
+    P.tile_off = tile_off;
+    P.dup_off = dup_off;
+    P.dup = (uint8_t *)c->dup_buf[0];
+    P.n_dup = (unsigned long long *)c->dup_buf[1];
+    P.out_ids = (uint32_t *)c->dup_buf[2];
+    P.out_off = (unsigned long long *)c->dup_buf[3];
+    auto hip_fail = [&](const char *what, hipError_t e) {
+        yabpe_dup_spans_free(c);
+        return fail(c, YABPE_E_HIP, "dup_spans: %s failed: %s", what, hipGetErrorString(e));
+    };
+    HIPCHK(c, hipEventRecord(c->dup_ev[0], s));
+    hipLaunchKernelGGL(k_dup_plan, dim3(cdiv64(n_docs, BLOCK)), dim3(BLOCK), 0, s, P);
+    if (exclusive_scan<uint32_t>(s, P.pieces, n_docs, piece_off, (unsigned long long)n_docs + 1) != 0 ||
+        exclusive_scan<uint32_t>(s, P.tiles, n_docs, tile_off, (unsigned long long)n_docs + 1) != 0)
+        return hip_fail("the scan of the piece counts", hipGetLastError());
+    if (fill_u32(c, P.table, n_slots, DUP_EMPTY) != 0) return hip_fail("the table preset", hipGetLastError());
+    (void)hipEventRecord(c->dup_ev[1], s);
+    if (n_pieces) hipLaunchKernelGGL(k_dup_insert, dim3((uint32_t)n_pieces), dim3(BLOCK), 0, s, P);
+    (void)hipEventRecord(c->dup_ev[2], s);
+    if (n_tiles) hipLaunchKernelGGL(k_dup_mark, dim3((uint32_t)n_tiles), dim3(BLOCK), 0, s, P);
+    (void)hipEventRecord(c->dup_ev[3], s);
+    if (compact) {
+        if (exclusive_scan<uint8_t>(s, P.dup, n_ids, dup_off, n_ids + 1) != 0) return hip_fail("the scan of the mask", hipGetLastError());
+        hipLaunchKernelGGL(k_dup_compact, dim3(cdiv64(std::max<uint64_t>(n_ids, (uint64_t)n_docs + 1), BLOCK)), dim3(BLOCK), 0, s, P);
+    }
+    const hipError_t le = hipGetLastError();
+    (void)hipEventRecord(c->dup_ev[4], s);
+    unsigned long long h_cnt[DUP_COUNTERS] = {};
+    const hipError_t ce = hipMemcpyAsync(h_cnt, P.counters, sizeof h_cnt, hipMemcpyDeviceToHost, s);
+    const hipError_t se = hipStreamSynchronize(s);
+    if (le != hipSuccess || ce != hipSuccess || se != hipSuccess) return hip_fail("a kernel", le != hipSuccess ? le : ce != hipSuccess ? ce : se);
+    float ms[4] = {0, 0, 0, 0};
+    st.total_ms = pass_times(c->dup_ev, 4, ms);
+    st.plan_ms = ms[0];
+    st.insert_ms = ms[1];
+    st.mark_ms = ms[2];
+    st.compact_ms = compact ? ms[3] : 0.0;
+    st.n_repeats = h_cnt[DUP_C_REPEATS];
+    st.n_dup_ids = h_cnt[DUP_C_DUP_IDS];
+    st.n_spans = h_cnt[DUP_C_SPANS];
+    st.n_kept = n_ids - st.n_dup_ids;
+    *out_dev_dup = P.dup;
+    *out_dev_n_dup = (uint64_t *)P.n_dup;
+    if (out_n_kept) *out_n_kept = st.n_kept;
+    if (compact) {
+        *out_dev_ids = P.out_ids;
+        *out_dev_off = (uint64_t *)P.out_off;
+    }
+    return YABPE_OK;
+}
+
+int yabpe_dup_spans_stats(yabpe_ctx *c, yabpe_dup_stats_t *out) {
+    if (!c || !out) return YABPE_E_INVALID;
+    *out = c->dup_stats;
     return YABPE_OK;
 }
 

@@ -151,6 +151,19 @@ class ClusterStats(ctypes.Structure):
         (n, c_double) for n in ("preset_ms", "insert_ms", "link_ms", "flatten_ms", "total_ms")]
 
 
+class Dup(ctypes.Structure):
+    """yabpe_dup_t"""
+    _fields_ = [(n, c_uint32) for n in ("min_len", "flags")]
+
+
+class DupStats(ctypes.Structure):
+    _fields_ = [(n, c_uint64) for n in ("n_ids", "n_docs", "n_windows", "n_repeats", "n_dup_ids", "n_spans", "n_kept", "n_slots")] + [
+        (n, c_double) for n in ("plan_ms", "insert_ms", "mark_ms", "compact_ms", "total_ms")]
+
+
+DUP_COMPACT = 1  # yabpe_dup_spans: flags
+
+
 class Layout(ctypes.Structure):
     """yabpe_layout_t"""
     _fields_ = [(n, c_uint32) for n in ("row_len", "pad_id", "bos_id", "eos_id", "flags")]
@@ -237,6 +250,7 @@ SYMBOLS = [
     "yabpe_chat", "yabpe_chat_free", "yabpe_chat_stats",
     "yabpe_minhash", "yabpe_minhash_free", "yabpe_minhash_stats",
     "yabpe_minhash_cluster", "yabpe_minhash_cluster_free", "yabpe_minhash_cluster_stats",
+    "yabpe_dup_spans", "yabpe_dup_spans_free", "yabpe_dup_spans_stats",
     "yabpe_pool_add", "yabpe_pool_get", "yabpe_pool_clear", "yabpe_pool_stats",
     "yabpe_normalize", "yabpe_normalize_free", "yabpe_normalize_stats",
     "yabpe_utf8_repair", "yabpe_utf8_repair_free", "yabpe_utf8_repair_stats",
@@ -340,6 +354,10 @@ def lib() -> ctypes.CDLL:
         L.yabpe_minhash_cluster.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_uint32, POINTER(Cluster), POINTER(c_void_p)]
         L.yabpe_minhash_cluster_free.argtypes = [c_void_p]
         L.yabpe_minhash_cluster_stats.argtypes = [c_void_p, POINTER(ClusterStats)]
+        L.yabpe_dup_spans.argtypes = [c_void_p, c_void_p, c_uint64, c_void_p, c_uint32, POINTER(Dup), POINTER(c_void_p), POINTER(c_void_p),
+                                      POINTER(c_void_p), POINTER(c_uint64), POINTER(c_void_p)]
+        L.yabpe_dup_spans_free.argtypes = [c_void_p]
+        L.yabpe_dup_spans_stats.argtypes = [c_void_p, POINTER(DupStats)]
         L.yabpe_pool_add.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_uint64]
         L.yabpe_pool_get.argtypes = [c_void_p, POINTER(c_void_p), POINTER(c_void_p), POINTER(c_void_p), POINTER(c_uint64), POINTER(c_uint64)]
         L.yabpe_pool_clear.argtypes = [c_void_p]
@@ -1402,6 +1420,47 @@ class Context:
     def minhash_cluster_stats(self) -> dict:
         s = ClusterStats()
         self._chk(lib().yabpe_minhash_cluster_stats(self._h, byref(s)))
+        return _stats_dict(s)
+
+    # -- exact-substring duplicates (BBPETokenizer.duplicate_spans on the device)
+    def dup_spans(self, ids, n_ids: int | None = None, doc_starts=None, n_docs: int | None = None, *, min_len: int = 50, compact: bool = False,
+                  flags: int = 0):
+        """Repeated runs of min_len ids (yabpe_dup_spans).  ids / doc_starts as minhash takes them (device pointers with n_ids /
+        n_docs, or host arrays; encode()'s results go straight in).  -> (dev_dup_ptr u8[n_ids], dev_n_dup_ptr u64[n_docs],
+        dev_kept_ids_ptr u32[n_kept] or 0, n_kept, dev_kept_off_ptr u64[n_docs + 1] or 0, n_ids, n_docs); the buffers live until
+        the next dup_spans, dup_spans_free() or close().  flags: further bits of yabpe_dup_t.flags, passed as they are."""
+        keep = docs = None
+        if isinstance(ids, int):
+            ptr, n = c_void_p(ids), int(n_ids)
+        else:
+            keep = np.ascontiguousarray(ids, dtype=np.uint32)
+            ptr, n = c_void_p(keep.ctypes.data if keep.size else 0), int(keep.size)
+        if isinstance(doc_starts, int):
+            dptr, nd = c_void_p(doc_starts), int(n_docs)
+        else:
+            docs = np.ascontiguousarray([] if doc_starts is None else doc_starts, dtype=np.uint64)  # (no starts: no documents)
+            dptr, nd = c_void_p(docs.ctypes.data), len(docs)
+        rule = Dup(int(min_len), (DUP_COMPACT if compact else 0) | int(flags))
+        dd, dn, di, do, nk = c_void_p(), c_void_p(), c_void_p(), c_void_p(), c_uint64(0)
+        self._chk(lib().yabpe_dup_spans(self._h, ptr, n, dptr, nd, byref(rule), byref(dd), byref(dn), byref(di), byref(nk), byref(do)))
+        return dd.value or 0, dn.value or 0, di.value or 0, nk.value, do.value or 0, n, nd
+
+    def dup_spans_to_host(self, ids, n_ids: int | None = None, doc_starts=None, n_docs: int | None = None, *, min_len: int = 50, compact: bool = False):
+        """-> (dup u8[n_ids], n_dup u64[n_docs], kept ids u32[n_kept] or None, kept doc_off u64[n_docs + 1] or None) copied to the host."""
+        dd, dn, di, nk, do, n, nd = self.dup_spans(ids, n_ids, doc_starts, n_docs, min_len=min_len, compact=compact)
+        dup = self.d2h(dd, n, np.uint8) if n else np.zeros(0, np.uint8)
+        n_dup = self.d2h(dn, 8 * nd, np.uint64) if nd else np.zeros(0, np.uint64)
+        if not compact:
+            return dup, n_dup, None, None
+        kept = self.d2h(di, 4 * nk, np.uint32) if nk else np.zeros(0, np.uint32)
+        return dup, n_dup, kept, self.d2h(do, 8 * (nd + 1), np.uint64) if nd else np.zeros(1, np.uint64)
+
+    def dup_spans_free(self) -> None:
+        self._chk(lib().yabpe_dup_spans_free(self._h))
+
+    def dup_spans_stats(self) -> dict:
+        s = DupStats()
+        self._chk(lib().yabpe_dup_spans_stats(self._h, byref(s)))
         return _stats_dict(s)
 
     # -- the persistent word pool (corpora larger than device memory: words go in call by call, the merge loop loads the pool)

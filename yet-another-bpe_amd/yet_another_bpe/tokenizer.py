@@ -20,7 +20,9 @@ encode_array_chat_fit compute the same on the GPU (yabpe_layout_fit_labels).  mi
 document a MinHash signature over its id n-grams and LSH band keys, for near-duplicate detection; minhash_array /
 encode_array_minhash compute the same on the GPU (yabpe_minhash).  minhash_clusters / encode_batch_clusters turn signatures
 and band keys into the cluster of every document (LSH buckets, verification against the bucket's smallest document, union-find);
-minhash_clusters_array / encode_array_clusters compute the same on the GPU (yabpe_minhash_cluster).
+minhash_clusters_array / encode_array_clusters compute the same on the GPU (yabpe_minhash_cluster).  duplicate_spans /
+remove_duplicate_spans / encode_batch_dedup mark and remove every run of min_len ids that occurs again (exact-substring
+deduplication); duplicate_spans_array / encode_array_dedup compute the same on the GPU (yabpe_dup_spans).
 """
 from __future__ import annotations
 
@@ -1543,6 +1545,63 @@ class BBPETokenizer:
             raise ValueError(f"min_agree {min_agree}: in [0, num_perm = {num_perm}]")
         return num_perm, ngram, bands, seed, min_agree
 
+    # ------------------------------------------------------------------ exact-substring duplicates (repeated runs of ids)
+    DUP_MAX_LEN, DUP_MAX_IDS = 1024, 1 << 30  # DUP_MAX_LEN, DUP_MAX_IDS of csrc/dup_logic.h
+
+    @classmethod
+    def _dup_len(cls, min_len) -> int:
+        """-> min_len, validated as yabpe_dup_spans validates it"""
+        try:
+            min_len = operator.index(min_len)
+        except TypeError:
+            raise ValueError(f"min_len must be an integer, not {min_len!r}") from None
+        if not 1 <= min_len <= cls.DUP_MAX_LEN:
+            raise ValueError(f"min_len {min_len}: in [1, {cls.DUP_MAX_LEN}]")
+        return min_len
+
+    def duplicate_spans(self, ids_batch, *, min_len: int = 50):
+        """Exact-substring duplicates -> (masks, n_dup, stats): masks[d][j] is 1 iff id j of document d lies inside a run of
+        min_len ids that already occurred, n_dup[d] their number.  With n = min_len and global positions (the documents back to
+        back), integers throughout:
+          window    n consecutive ids inside one document; windows never cross a document seam, a document of fewer than n
+                    ids has none.
+          first[p]  the smallest global position whose window holds the same n ids as p's, in any document.
+          repeat    window p iff first[p] + n <= p: an equal window ENDS at or before p begins.  (If the smallest equal window
+                    overlaps p, every later one before p does too.)  A run of one id of length L >= 2 n so keeps n ids and loses L - n.
+          mask      id i is duplicated iff it lies inside a repeat window of its document; a span is a maximal run of them.
+        The first occurrence of everything stays.  stats: n_ids, n_docs, n_windows, n_repeats, n_dup_ids, n_spans, n_kept.
+        min_len outside [1, 1024], more than 2^30 ids: ValueError."""
+        n = self._dup_len(min_len)
+        docs = [[int(t) for t in ids] for ids in ids_batch]
+        if sum(len(ids) for ids in docs) > self.DUP_MAX_IDS:
+            raise ValueError("at most 2^30 ids in one call")
+        first: dict = {}
+        masks, base, n_windows, n_repeats, n_spans = [], 0, 0, 0, 0
+        for ids in docs:  # (ascending global positions: setdefault leaves the smallest)
+            mask = [0] * len(ids)
+            for p in range(len(ids) - n + 1):
+                n_windows += 1
+                if first.setdefault(tuple(ids[p:p + n]), base + p) + n <= base + p:
+                    n_repeats += 1
+                    mask[p:p + n] = [1] * n
+            n_spans += sum(1 for j, m in enumerate(mask) if m and not (j and mask[j - 1]))
+            masks.append(mask)
+            base += len(ids)
+        n_dup = [sum(m) for m in masks]
+        stats = {"n_ids": base, "n_docs": len(docs), "n_windows": n_windows, "n_repeats": n_repeats, "n_dup_ids": sum(n_dup), "n_spans": n_spans,
+                 "n_kept": base - sum(n_dup)}
+        return masks, n_dup, stats
+
+    def remove_duplicate_spans(self, ids_batch, *, min_len: int = 50):
+        """-> (the documents without the ids duplicate_spans marks, n_dup); a document may become empty."""
+        masks, n_dup, _stats = self.duplicate_spans(ids_batch, min_len=min_len)
+        return [[int(t) for t, m in zip(ids, mask) if not m] for ids, mask in zip(ids_batch, masks)], n_dup
+
+    def encode_batch_dedup(self, texts: Sequence[str], min_len: int = 50):
+        """encode_batch(texts), then remove_duplicate_spans over the ids -> (ids per document, n_dup)."""
+        min_len = self._dup_len(min_len)  # (refused before any work)
+        return self.remove_duplicate_spans(self.encode_batch(texts), min_len=min_len)
+
     # ------------------------------------------------------------------ encode on the GPU (yabpe_encode; same ids as encode)
     def _device(self, model: str = "encode"):
         if self._device_ctx is None:
@@ -1978,6 +2037,38 @@ class BBPETokenizer:
         ds, dn, dk, nd = ctx.minhash(di, ni, dd, len(inp[1]), num_perm=num_perm, ngram=ngram, bands=bands, seed=seed)
         cluster = ctx.minhash_cluster_to_host(ds, dk, dn, nd, num_perm=num_perm, bands=bands, min_agree=min_agree)
         return cluster, ctx.d2h(dn, 8 * nd, np.uint64)
+
+    def duplicate_spans_array(self, ids, doc_off, *, min_len: int = 50, compact: bool = False):
+        """duplicate_spans on the GPU (yabpe_dup_spans), value for value: ids and doc_off as encode_array returns them
+        -> (dup np.uint8[n], n_dup np.uint64[n_docs], stats: duplicate_spans' and n_slots and the device times); with compact
+        -> (dup, n_dup, stats, kept ids np.uint32[n_kept], kept doc_off np.uint64[n_docs + 1]), what remove_duplicate_spans leaves."""
+        min_len = self._dup_len(min_len)
+        ids = np.ascontiguousarray(ids, dtype=np.uint32)
+        off = np.asarray(doc_off, dtype=np.int64)
+        if off.ndim != 1 or len(off) < 1 or off[0] != 0 or off[-1] != len(ids) or np.any(np.diff(off) < 0):
+            raise ValueError("doc_off must be n_docs + 1 ascending offsets from 0 to len(ids)")
+        if len(ids) > self.DUP_MAX_IDS:
+            raise ValueError("at most 2^30 ids in one call")
+        ctx = self._device()
+        dup, n_dup, kept, kept_off = ctx.dup_spans_to_host(ids, None, off[:-1].astype(np.uint64), None, min_len=min_len, compact=compact)
+        return (dup, n_dup, ctx.dup_spans_stats()) + ((kept, kept_off) if compact else ())
+
+    def encode_array_dedup(self, texts, min_len: int = 50, *, errors: str = "strict"):
+        """encode_batch_dedup(texts, min_len), computed on the GPU: yabpe_encode, then yabpe_dup_spans with YABPE_DUP_COMPACT on
+        its device results (the ids never visit the host) -> (ids np.uint32[n_kept], doc_off np.uint64[n_docs + 1], n_dup
+        np.uint64[n_docs]): ids and doc_off as encode_array returns them, so decode_array takes them.  `texts` and errors as
+        encode_array takes them."""
+        min_len = self._dup_len(min_len)
+        inp = self._device_input(texts)
+        if inp is None:
+            check_errors(errors)
+            return np.zeros(0, np.uint32), np.zeros(1, np.uint64), np.zeros(0, np.uint64)
+        ctx = self._device()
+        text, n_bytes, starts = self._device_text(ctx, inp, errors)
+        di, dd, ni = ctx.encode(text, n_bytes, doc_starts=starts)
+        _dm, dn, dk, nk, do, _n, nd = ctx.dup_spans(di, ni, dd, len(inp[1]), min_len=min_len, compact=True)
+        kept = ctx.d2h(dk, 4 * nk, np.uint32) if nk else np.zeros(0, np.uint32)
+        return kept, ctx.d2h(do, 8 * (nd + 1), np.uint64), ctx.d2h(dn, 8 * nd, np.uint64)
 
     def _device_encode_for_layout(self, ctx, inp, dropout=0.0, seed=0, offsets=None):
         """-> (ids pointer, document starts pointer, n_ids, spans): the device results the layout passes read -- yabpe_encode's,
