@@ -221,8 +221,11 @@ template <class T>
 __device__ __forceinline__ T kernarg_read(uint32_t off) {
     typedef const __attribute__((address_space(4))) unsigned char *BytePtr;
     typedef const __attribute__((address_space(4))) T *Ptr;
-    Ptr p = (Ptr)((BytePtr)__builtin_amdgcn_kernarg_segment_ptr() + off);
-    asm volatile("" : "+s"(p));
+    // (the SEGMENT's pointer is what is made opaque, not the sum: `off` then folds into the load's immediate.  An opaque sum
+    // is a loop-invariant 64-bit address per use, which the compiler computes at the entry and parks in a spill VGPR too)
+    BytePtr base = (BytePtr)__builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(base));
+    Ptr p = (Ptr)(base + off);
     T v;
     __builtin_memcpy(&v, p, sizeof(T));
     return v;
@@ -232,8 +235,31 @@ __device__ __forceinline__ T kernarg_read(uint32_t off) {
 template <uint32_t OFF>
 struct KernargTable {};
 __device__ __forceinline__ const PairTable &pt_get(const PairTable &t) { return t; }
+// (member by member, a scalar load each: read as ONE object the table arrives in 8-dword register tuples, and a tuple that
+// does not fit is parked and brought back WHOLE wherever one member of it is used -- tools/spill_report.py: 8 saves and 50
+// restores on this rare path, and the tuple's registers were missing on the common one: 109 + 21 spill moves per tile and
+// merge in k_scan_skip<false,8>, 34 + 3 with the members read one by one)
 template <uint32_t OFF>
-__device__ __forceinline__ PairTable pt_get(KernargTable<OFF>) { return kernarg_read<PairTable>(OFF); }
+__device__ __forceinline__ PairTable pt_get(KernargTable<OFF>) {
+    PairTable t;
+#define YB_PT_MEMBER(NAME) t.NAME = kernarg_read<decltype(t.NAME)>(OFF + (uint32_t)offsetof(PairTable, NAME))
+    YB_PT_MEMBER(keys);
+    YB_PT_MEMBER(cnt);
+    YB_PT_MEMBER(cap);
+    YB_PT_MEMBER(max_probe);
+    YB_PT_MEMBER(entries);
+    YB_PT_MEMBER(cand_cs);
+    YB_PT_MEMBER(cand_list);
+    YB_PT_MEMBER(cand_bits);
+    YB_PT_MEMBER(cand_T);
+    YB_PT_MEMBER(sink_rec);
+    YB_PT_MEMBER(sink_hdr);
+    YB_PT_MEMBER(sink_cap);
+#undef YB_PT_MEMBER
+    // (sink_cap is the last of the 12 members, with nothing but tail padding behind it: a new member has to be added above)
+    static_assert(offsetof(PairTable, sink_cap) == 80 && sizeof(PairTable) == 88, "pt_get(KernargTable) reads PairTable member by member");
+    return t;
+}
 
 // Within one wave LDS operations complete in order; this keeps the compiler from moving a lane's LDS reads
 // above other lanes' LDS writes.
@@ -887,11 +913,15 @@ __device__ unsigned long long g_slow_prof[8]; // [0] tiles, [1..5] cycles per ph
 #define YB_STAMP(i) do { } while (0)
 #endif
 
-// What a workgroup needs to run the slow path.  TAB_OFF != 0 (k_scan_skip): where the pair table stands in the kernel's
-// argument segment -- P.out is then not used by the rewrite, and nothing of the table lives through the caller's loop.
-template <class AggV, uint32_t TAB_OFF = 0>
+// What a workgroup needs to run the slow path.  A_OFF != 0 (k_scan_skip): where the ApplyParams stand in the kernel's
+// argument segment (never at 0: another argument comes first).  The context then holds NO copy of the parameters: the tile path
+// reads each of the stream's buffers from the argument segment where it uses it (kernarg_read: one scalar load whose
+// latency the lane reads and the prefetch in front of the use cover), and neither a pointer nor the table lives through
+// the caller's candidate loop -- where it sat in the lanes of a spill VGPR and came back several times per tile.
+struct NoParams {};
+template <class AggV, uint32_t A_OFF = 0>
 struct SlowCtx {
-    ApplyParams P;
+    typename std::conditional<A_OFF != 0, NoParams, ApplyParams>::type P;
     Agg<AggV> agg;
     DevState *st;
     uint32_t a, b, c, mk, self;
@@ -899,8 +929,20 @@ struct SlowCtx {
     KeyMemo memo; // wave-uniform
     int *hist;    // != NULL: the direct-indexed delta store (Hist) is in use instead of agg
     __device__ __forceinline__ auto table() const { // where the deltas go when the aggregator cannot take them
-        if constexpr (TAB_OFF != 0) return KernargTable<TAB_OFF>{}; else return P.out;
+        if constexpr (A_OFF != 0) return KernargTable<A_OFF + (uint32_t)offsetof(ApplyParams, out)>{}; else return P.out;
     }
+#define YB_CTX_PARAM(T, NAME)                                                                                           \
+    __device__ __forceinline__ T NAME() const {                                                                         \
+        if constexpr (A_OFF != 0) return kernarg_read<T>(A_OFF + (uint32_t)offsetof(ApplyParams, NAME));                            \
+        else return P.NAME;                                                                                             \
+    }
+    YB_CTX_PARAM(uint16_t *, tiles)
+    YB_CTX_PARAM(uint32_t *, tile_len)
+    YB_CTX_PARAM(const uint32_t *, tile_wbase)
+    YB_CTX_PARAM(const uint32_t *, wfreq)
+    YB_CTX_PARAM(unsigned long long *, sig)
+    YB_CTX_PARAM(uint32_t, sig_stride)
+#undef YB_CTX_PARAM
 };
 
 // slot q of the tile (wave-uniform q), read out of the registers that hold the tile: lane (q>>3)&63 owns it
@@ -939,11 +981,10 @@ __device__ unsigned long long g_ss_prof[8];
 // DEFER (batched sparse launch: several merges may rewrite the same tile one after the other): nothing is stored -- the
 // rewritten tile replaces `r`, `len` becomes its new length and `first_changed` the first slot that differs from HBM; the
 // caller writes the tile back once, after the last merge of the batch has seen it.
-template <class AggV, bool HIST = false, bool WEIGHTED = false, bool DEFER = false, uint32_t TAB_OFF = 0>
-__device__ __forceinline__ void single_site_tile(SlowCtx<AggV, TAB_OFF> &C, uint32_t tile, uint32_t &len, TileRegs &r,
+template <class AggV, bool HIST = false, bool WEIGHTED = false, bool DEFER = false, uint32_t A_OFF = 0>
+__device__ __forceinline__ void single_site_tile(SlowCtx<AggV, A_OFF> &C, uint32_t tile, uint32_t &len, TileRegs &r,
                                                  int lane_s, uint32_t mm_s, unsigned long long &wave_sites,
                                                  unsigned long long &wave_freed, uint32_t &first_changed) {
-    const ApplyParams &P = C.P;
     DevState *st = C.st;
     const uint32_t a = C.a, b = C.b, c = C.c;
     const int lane = C.lane;
@@ -953,6 +994,9 @@ __device__ __forceinline__ void single_site_tile(SlowCtx<AggV, TAB_OFF> &C, uint
 #endif
     const int j = __ffs((int)mm_s) - 1;
     const int p = j < 8 ? lane_s * 8 + j : 512 + lane_s * 8 + (j - 8); // the site (wave-uniform)
+    // (the signatures' place: where it comes from the argument segment, the lane reads below cover the scalar load)
+    unsigned long long *const sig = C.sig();
+    const uint32_t sig_stride = C.sig_stride();
     const uint32_t L = tile_elem_uniform(r, p - 1), R = tile_elem_uniform(r, p + 2);
     const bool left = L < YB_PAD, right = R < YB_PAD;
     const bool dead = !WEIGHTED && !left && R == YB_SEP; // flat layout: the word was exactly (a b): it leaves the stream (yb_site_word_dies)
@@ -966,8 +1010,8 @@ __device__ __forceinline__ void single_site_tile(SlowCtx<AggV, TAB_OFF> &C, uint
         uint32_t cnt = lane < lane_s ? __popc(mine) : lane == lane_s ? __popc(mine & below) : 0u;
         if (inB) cnt += __popc(sepA);
         cnt = wave_inclusive_sum(cnt);
-        const uint32_t widx = P.tile_wbase[tile] + (uint32_t)__builtin_amdgcn_readlane(cnt, 63);
-        w = (long long)P.wfreq[widx];
+        const uint32_t widx = C.tile_wbase()[tile] + (uint32_t)__builtin_amdgcn_readlane(cnt, 63);
+        w = (long long)C.wfreq()[widx];
     }
 
     YB_SS_STAMP(1);
@@ -975,15 +1019,16 @@ __device__ __forceinline__ void single_site_tile(SlowCtx<AggV, TAB_OFF> &C, uint
     // soon as the neighbours are known: these are the wave's only memory operations here (DEFER form), and the candidate loop
     // cannot take the next tile's prefetched registers before they are acknowledged (the in-order vmcnt leaves the compiler no
     // other choice): the compaction and the LDS deltas below run meanwhile.  (Non-DEFER form: the stores below go out next.)
-    if (P.sig && !dead && lane < 2) {
-        if (lane ? right : left) sig_set_pair(P.sig, P.sig_stride, tile, lane ? yb_pairkey(c, R) : yb_pairkey(L, c));
+    if (sig && !dead && lane < 2) {
+        if (lane ? right : left) sig_set_pair(sig, sig_stride, tile, lane ? yb_pairkey(c, R) : yb_pairkey(L, c));
     }
     // ---- compaction in registers
     const int D0 = dead ? p : p + 1; // first slot that leaves
     const int s = dead ? 3 : 1;      // how many leave (contiguous)
     const uint32_t new_len = len - (uint32_t)s;
     const uint32_t pad_end = (new_len + 7u) & ~7u;
-    uint4 *wb = reinterpret_cast<uint4 *>(P.tiles + (size_t)tile * CAP);
+    uint4 *wb = nullptr; // (non-DEFER form only)
+    if constexpr (!DEFER) wb = reinterpret_cast<uint4 *>(C.tiles() + (size_t)tile * CAP);
     (void)wb;
     (void)pad_end;
     uint4 ra = r.va, rb = r.vb; // DEFER: the rewritten tile
@@ -1044,7 +1089,7 @@ __device__ __forceinline__ void single_site_tile(SlowCtx<AggV, TAB_OFF> &C, uint
         len = new_len;
         first_changed = min(first_changed, (uint32_t)p);
     } else {
-        if (lane == 0) P.tile_len[tile] = new_len;
+        if (lane == 0) C.tile_len()[tile] = new_len;
     }
     YB_SS_STAMP(4);
     YB_SS_STAMP(3);
@@ -1069,12 +1114,11 @@ __device__ __forceinline__ void single_site_tile(SlowCtx<AggV, TAB_OFF> &C, uint
 // write-back.  Work is proportional to the number of sites.  Returns false when nothing changed.
 // HAVE_MASKS: the caller has the candidate masks of the two segments already (match_mask8): pmA, pmB.
 // DEFER: see single_site_tile -- the compacted tile is read back from the LDS image into `r` instead of being stored.
-template <bool WEIGHTED, class AggV, bool HIST = false, bool HAVE_MASKS = false, bool DEFER = false, uint32_t TAB_OFF = 0>
-__device__ __forceinline__ bool slow_tile(SlowCtx<AggV, TAB_OFF> &C, WaveLds &W, uint32_t tile, uint32_t &len_io, TileRegs &r,
+template <bool WEIGHTED, class AggV, bool HIST = false, bool HAVE_MASKS = false, bool DEFER = false, uint32_t A_OFF = 0>
+__device__ __forceinline__ bool slow_tile(SlowCtx<AggV, A_OFF> &C, WaveLds &W, uint32_t tile, uint32_t &len_io, TileRegs &r,
                                           uint32_t na, uint32_t nb, unsigned long long &wave_sites,
                                           unsigned long long &wave_freed, uint32_t &first_changed, uint32_t pmA = 0u, uint32_t pmB = 0u) {
     const uint32_t len = len_io;
-    const ApplyParams &P = C.P;
     DevState *st = C.st;
     const uint32_t a = C.a, b = C.b, c = C.c, mk = C.mk, self = C.self;
     const int lane = C.lane;
@@ -1128,7 +1172,7 @@ __device__ __forceinline__ bool slow_tile(SlowCtx<AggV, TAB_OFF> &C, WaveLds &W,
     if (WEIGHTED) {
         reinterpret_cast<uint8_t *>(W.smask)[lane] = (uint8_t)eq_mask8(r.va, YB_SEP);
         reinterpret_cast<uint8_t *>(W.smask)[64 + lane] = (uint8_t)eq_mask8(r.vb, YB_SEP);
-        wbase = P.tile_wbase[tile];
+        wbase = C.tile_wbase()[tile];
     }
     wave_sync();
     if (WEIGHTED) {
@@ -1154,11 +1198,13 @@ __device__ __forceinline__ bool slow_tile(SlowCtx<AggV, TAB_OFF> &C, WaveLds &W,
         YbDeltas d;
         d.left = d.right = false;
         d.lo = d.ln = d.ro = d.rn = 0;
+        unsigned long long *const sig = C.sig(); // (per turn where it comes from the argument segment: the LDS reads of the deltas cover it)
+        const uint32_t sig_stride = C.sig_stride();
         if (site) {
             yb_site_deltas(p, a, b, c, T, M, d);
-            if (P.sig) { // the pairs this site creates are now present in the tile
-                if (d.left) sig_set_pair(P.sig, P.sig_stride, tile, d.ln);
-                if (d.right) sig_set_pair(P.sig, P.sig_stride, tile, d.rn);
+            if (sig) { // the pairs this site creates are now present in the tile
+                if (d.left) sig_set_pair(sig, sig_stride, tile, d.ln);
+                if (d.right) sig_set_pair(sig, sig_stride, tile, d.rn);
             }
             atomicOr(&W.dmask[(p + 1) >> 5], 1u << ((p + 1) & 31));
             if (!WEIGHTED && yb_site_word_dies(p, T)) {
@@ -1170,7 +1216,7 @@ __device__ __forceinline__ bool slow_tile(SlowCtx<AggV, TAB_OFF> &C, WaveLds &W,
             if (site) {
                 const uint32_t sw = W.smask[p >> 5];
                 const uint32_t widx = wbase + W.spref[p >> 5] + __popc(sw & ((1u << (p & 31)) - 1u));
-                const long long w = (long long)P.wfreq[widx];
+                const long long w = (long long)C.wfreq()[widx];
                 if (d.left) {
                     if (d.lo != self) agg_add(C.agg, C.table(), st, d.lo, -w);
                     agg_add(C.agg, C.table(), st, d.ln, +w);
@@ -1253,10 +1299,10 @@ __device__ __forceinline__ bool slow_tile(SlowCtx<AggV, TAB_OFF> &C, WaveLds &W,
         first_changed = min(first_changed, first_drop);
         wave_sync(); // (the image is read: the next rewrite of this wave may stage over it)
     } else {
-        uint4 *wb = reinterpret_cast<uint4 *>(P.tiles + (size_t)tile * CAP);
+        uint4 *wb = reinterpret_cast<uint4 *>(C.tiles() + (size_t)tile * CAP);
         if ((uint32_t)pA < new_len && (uint32_t)pA + 8 > first_drop) wb[lane] = *reinterpret_cast<const uint4 *>(outb + pA);
         if ((uint32_t)pB < new_len && (uint32_t)pB + 8 > first_drop) wb[64 + lane] = *reinterpret_cast<const uint4 *>(outb + pB);
-        if (lane == 0) P.tile_len[tile] = new_len;
+        if (lane == 0) C.tile_len()[tile] = new_len;
     }
     wave_freed += dropped;
     YB_STAMP(4);
@@ -3179,7 +3225,7 @@ __device__ __forceinline__ bool scan_skip_block(DevState *st, const ScanSkipPara
     // the pair table -- the flush's after the loop, the rewrite's only on the path that leaves the LDS aggregator.
     constexpr uint32_t Q_OFF = 8;
     static_assert(alignof(ScanSkipParams) == 8, "Q follows the 8-byte first argument without padding");
-    constexpr uint32_t TAB_OFF = Q_OFF + offsetof(ScanSkipParams, A) + offsetof(ApplyParams, out);
+    constexpr uint32_t A_OFF = Q_OFF + offsetof(ScanSkipParams, A);
     __shared__ uint32_t s_n, s_claim;            // entries on the hit list; the next one no wave has taken yet
     __shared__ uint32_t s_piece;                  // second round: the piece thread 0 took for the workgroup
     __shared__ uint2 s_list[NT * KTM];            // (tile, live length | merges noted << 16)
@@ -3234,7 +3280,8 @@ __device__ __forceinline__ bool scan_skip_block(DevState *st, const ScanSkipPara
     }
     const uint32_t n_blocks = Q.scan_blocks;
     const uint32_t nbatch = __builtin_amdgcn_readfirstlane(nb_);
-    SlowCtx<AggV, TAB_OFF> C{P, Agg<AggV>{s_keys, s_vals, P.agg_mask}, st, 0u, 0u, 0u, 0u, 0u, lane,
+    // (the context holds none of the stream's pointers: C.tiles(), C.tile_len(), C.sig() ... read the argument segment at the use)
+    SlowCtx<AggV, A_OFF> C{NoParams{}, Agg<AggV>{s_keys, s_vals, P.agg_mask}, st, 0u, 0u, 0u, 0u, 0u, lane,
                              KeyMemo{{EMPTY, EMPTY, EMPTY, EMPTY}, {0u, 0u, 0u, 0u}}};
     WaveLds &W = s_w[wib];
     __syncthreads();
@@ -3245,16 +3292,24 @@ __device__ __forceinline__ bool scan_skip_block(DevState *st, const ScanSkipPara
     const uint32_t chunk = Q.chunk;
     // first round: chunk blockIdx.x.  Then the tiles from `rest0` on, if there are any: in pieces, first come first served
     uint32_t t0 = blockIdx.x * chunk; // (the only thing about the workgroup's place in the stream that lives through the candidate loop)
-    while (t0 < P.n_tiles) {
+    constexpr uint32_t NT_OFF = A_OFF + offsetof(ApplyParams, n_tiles);
+    // What the sweep reads of the stream.  The FIRST chunk's come with the arguments that are loaded at the kernel's entry (no
+    // trip of their own in front of every launch's sweep: measured on the pooled layout, whose launches are short); a later
+    // chunk's are read again from the argument segment at the end of the chunk before it -- dead through the candidate loop.
+    uint32_t n_tiles = P.n_tiles;
+    const uint32_t *sw_len = P.tile_len;
+    const unsigned long long *sw_sig = P.sig;
+    uint32_t sw_stride = P.sig_stride;
+    while (t0 < n_tiles) {
         // all of this thread's lengths are requested first, then the signature words merge by merge
         uint32_t len[KTM], km[KTM];
-        const uint32_t t_end = min(P.n_tiles, t0 + ((DYN && Q.piece_ctr && t0 >= n_blocks * chunk) ? Q.piece : chunk));
+        const uint32_t t_end = min(n_tiles, t0 + ((DYN && Q.piece_ctr && t0 >= n_blocks * chunk) ? Q.piece : chunk));
 #pragma unroll
         for (uint32_t j = 0; j < (uint32_t)KTM; ++j) {
             const uint32_t t = t0 + j * NT + threadIdx.x;
             len[j] = 0;
             km[j] = 0;
-            if (j < kt && t < t_end) len[j] = P.tile_len[t]; // (t_end: the end of this workgroup's run of tiles, or of the stream)
+            if (j < kt && t < t_end) len[j] = sw_len[t]; // (t_end: the end of this workgroup's run of tiles, or of the stream)
         }
         // (KG merges' words in flight at a time -- 16 loads per thread: ONE trip to memory for a batch of up to KG instead of one per
         // two merges; the registers are free here, the rewrite is what sets the kernel's count)
@@ -3264,7 +3319,7 @@ __device__ __forceinline__ bool scan_skip_block(DevState *st, const ScanSkipPara
 #pragma unroll
             for (uint32_t kk = 0; kk < KG; ++kk) {
                 const bool on = k0 + kk < nbatch; // uniform
-                const unsigned long long *rowp = P.sig + (size_t)s_bm.row[(k0 + kk) & (uint32_t)(KMAX - 1)] * P.sig_stride;
+                const unsigned long long *rowp = sw_sig + (size_t)s_bm.row[(k0 + kk) & (uint32_t)(KMAX - 1)] * sw_stride;
 #pragma unroll
                 for (uint32_t j = 0; j < (uint32_t)KTM; ++j) {
                     const uint32_t t = t0 + j * NT + threadIdx.x;
@@ -3305,14 +3360,14 @@ __device__ __forceinline__ bool scan_skip_block(DevState *st, const ScanSkipPara
         // waited for in full -- ~900 cycles per tile; issued a tile earlier they are long acknowledged)
         TileRegs pend = TileRegs{make_uint4(0u, 0u, 0u, 0u), make_uint4(0u, 0u, 0u, 0u)};
         uint32_t pend_tile = 0, pend_len = 0, pend_fc = CAP;
-        auto write_back = [&](const TileRegs &t, uint32_t tile_, uint32_t len_, uint32_t fc_) {
+        auto write_back = [&](uint16_t *tiles_, const TileRegs &t, uint32_t tile_, uint32_t len_, uint32_t fc_) {
             // the 16-B groups from the first changed slot to the end of what is live
             const uint32_t pad_end = (len_ + 7u) & ~7u;
-            uint4 *wb = reinterpret_cast<uint4 *>(P.tiles + (size_t)tile_ * CAP);
+            uint4 *wb = reinterpret_cast<uint4 *>(tiles_ + (size_t)tile_ * CAP);
             const uint32_t gA = (uint32_t)lane * 8u, gB = 512u + (uint32_t)lane * 8u;
             if (gA + 8u > fc_ && gA < pad_end) wb[lane] = t.va;
             if (gB + 8u > fc_ && gB < pad_end) wb[64 + lane] = t.vb;
-            if (lane == 0) P.tile_len[tile_] = len_;
+            if (lane == 0) C.tile_len()[tile_] = len_;
         };
         // the next entry nobody has taken (tiles differ a lot in what they cost -- a tile that passed the signature test without
         // holding the pair is dropped after the match: dealt out by turns, the waves of a workgroup finish far apart).  Claimed at
@@ -3325,21 +3380,22 @@ __device__ __forceinline__ bool scan_skip_block(DevState *st, const ScanSkipPara
         uint32_t j = wib;                // the entry whose tile is in q0
         uint32_t jn = j < n ? claim() : n; // the one after it
         uint2 it0 = j < n ? list_at(j) : make_uint2(0u, 0u);
-        TileRegs q0 = load_tile(P.tiles, it0.x, it0.y & 0xffffu, lane);
+        TileRegs q0 = load_tile(C.tiles(), it0.x, it0.y & 0xffffu, lane);
         while (j < n) {
+            uint16_t *const tiles = C.tiles(); // (once per tile, while the prefetched tile is on its way: the write-back's and the next prefetch's)
             const uint32_t tile = it0.x;
             uint32_t tlen = it0.y & 0xffffu, kmask = it0.y >> 16;
             TileRegs r = q0;
             asm volatile("" : "+v"(r.va.x), "+v"(r.vb.x)); // (the prefetched registers are taken HERE: in front of the stores below)
             if (pend_fc < (uint32_t)CAP) {
-                write_back(pend, pend_tile, pend_len, pend_fc);
+                write_back(tiles, pend, pend_tile, pend_len, pend_fc);
                 pend_fc = CAP;
             }
             asm volatile("" ::: "memory"); // (the stores stay here: their registers are free for the next prefetch)
             j = jn;
             if (j < n) { // (one candidate ahead: a second one in flight cost the flat form its fourth wave per SIMD)
                 it0 = list_at(j);
-                q0 = load_tile(P.tiles, it0.x, it0.y & 0xffffu, lane);
+                q0 = load_tile(tiles, it0.x, it0.y & 0xffffu, lane);
             }
             const uint32_t len_in = tlen;
             uint32_t first_changed = CAP; // wave-uniform: the first slot of the tile that differs from what HBM holds
@@ -3389,7 +3445,7 @@ __device__ __forceinline__ bool scan_skip_block(DevState *st, const ScanSkipPara
             (void)len_in;
             if (j < n) jn = claim();
         }
-        if (pend_fc < (uint32_t)CAP) write_back(pend, pend_tile, pend_len, pend_fc);
+        if (pend_fc < (uint32_t)CAP) write_back(C.tiles(), pend, pend_tile, pend_len, pend_fc);
         __syncthreads();
         YB_SCAN_STAMP(2);
 #ifdef YB_PROFILE_SCAN
@@ -3424,6 +3480,10 @@ __device__ __forceinline__ bool scan_skip_block(DevState *st, const ScanSkipPara
             if (t0 + rest0 < t0) break; // (u32 wrap)
             t0 += rest0;
         }
+        n_tiles = kernarg_read<uint32_t>(NT_OFF);
+        sw_len = C.tile_len();
+        sw_sig = C.sig();
+        sw_stride = C.sig_stride();
     }
     if (threadIdx.x == 0 && Q.blk_read) Q.blk_read[blockIdx.x] += n_read;
     YB_SCAN_STAMP(4);
@@ -3431,7 +3491,7 @@ __device__ __forceinline__ bool scan_skip_block(DevState *st, const ScanSkipPara
     const unsigned long long prof_tc = wall_clock64(); // (every wave of the workgroup has left the candidate loop)
 #endif
     // (the table and the counters' place: read here, once per workgroup, not carried through the loop)
-    apply_epilogue<AggV, NT>(kernarg_read<ApplyParams>(Q_OFF + offsetof(ScanSkipParams, A)), C.agg, st, s_cnt, wave_sites, wave_freed, lane);
+    apply_epilogue<AggV, NT>(kernarg_read<ApplyParams>(A_OFF), C.agg, st, s_cnt, wave_sites, wave_freed, lane);
     YB_SCAN_STAMP(7);
 #ifdef YB_PROFILE_LAUNCH
     YB_LAUNCH_WG_END(prof_it, n_read, prof_tc);
