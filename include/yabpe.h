@@ -1162,6 +1162,48 @@ typedef struct yabpe_dup_stats_t {
 } yabpe_dup_stats_t;
 int yabpe_dup_spans_stats(yabpe_ctx *ctx, yabpe_dup_stats_t *out);
 
+/* Repetition signals (BBPETokenizer.repetition_stats on the device, yet_another_bpe/tokenizer.py) -----------------
+ * Per document and per requested n-gram length, three integers -- the signals of the Gopher repetition filters (Rae et al.
+ * 2021, table A1) over token ids.  ids / doc_off / n_docs as yabpe_minhash takes them, host or device memory; yabpe_encode's
+ * device results go straight in and are left untouched.  For a document d of L ids and a length n (csrc/rep_logic.h):
+ *   window     n consecutive ids of d: L - n + 1 of them, none when L < n; windows never cross a document seam, and equal
+ *              windows of two different documents never meet;
+ *   count(w)   the windows of d that hold the same n ids as w (overlapping ones count);
+ *   top        the largest count in d: 0 without windows, 1 when nothing repeats;
+ *   distinct   the number of classes of equal windows in d (n = 1: the unique ids);
+ *   covered    the ids of d inside at least one window with count >= 2, every id once.
+ * Results (device memory owned by the library, in buffers of their own: a later encode, minhash, dup or layout call leaves
+ * them valid; released by yabpe_repetition_free, the next yabpe_repetition or yabpe_destroy): *out_dev_top,
+ * *out_dev_distinct, *out_dev_covered, each u32[n_docs][n_ngrams]; NULL with n_docs == 0.
+ * A document of at most 2,048 ids is counted in LDS, every length from one read of its ids; a longer one per length in a hash
+ * table in HBM over the windows of the long documents: the smallest power of two >= 2 * their windows at the smallest length,
+ * 2^10 at least.  Options (tests and measurements): "rep_slots_log2" forces 2^value slots (0: auto); "rep_doc_max" lowers the
+ * short/long boundary to 1 .. 2,048 ids (0: 2,048) -- with 1 every document of two ids or more takes the long form.
+ * YABPE_E_INVALID: n_ngrams outside [1, 16], a length outside [1, 64], lengths that do not strictly ascend, flags != 0, a
+ * doc_off that does not ascend from 0 inside the ids, rep_doc_max outside [0, 2,048], a forced table of fewer than
+ * windows + 1 slots.  YABPE_E_CAPACITY: more than 2^30 ids.  Every error is found before a buffer is allocated. */
+typedef struct yabpe_repetition_t {
+    uint32_t n_ngrams;      /* 1 .. 16 */
+    uint32_t ngram[16];     /* strictly ascending, each 1 .. 64 */
+    uint32_t flags;         /* 0 */
+} yabpe_repetition_t;
+/* What the last yabpe_repetition saw, and its device time.  The integers are functions of the input alone. */
+typedef struct yabpe_repetition_stats_t {
+    uint64_t n_ids, n_docs, n_ngrams;
+    uint64_t n_short_docs;        /* documents of at most the boundary's ids, empty ones included */
+    uint64_t n_long_docs;
+    uint64_t n_long_windows;      /* windows of the long documents, summed over the lengths */
+    uint64_t n_slots;             /* of the global table (0 without long documents) */
+    double plan_ms;               /* counts, scans */
+    double short_ms;              /* the LDS form, all lengths */
+    double long_ms;               /* per length: table preset, insert, mark */
+    double total_ms;              /* first to last event of the call */
+} yabpe_repetition_stats_t;
+int yabpe_repetition(yabpe_ctx *ctx, const uint32_t *ids, uint64_t n_ids, const uint64_t *doc_off, uint32_t n_docs,
+                     const yabpe_repetition_t *rule, uint32_t **out_dev_top, uint32_t **out_dev_distinct, uint32_t **out_dev_covered);
+int yabpe_repetition_free(yabpe_ctx *ctx);
+int yabpe_repetition_stats(yabpe_ctx *ctx, yabpe_repetition_stats_t *out);
+
 /* Multi-GPU (one process per GPU; words are sharded by the caller) -----------------
  * Every rank holds its shard of the words and a replica of the pair table.  After each apply pass the ranks
  * exchange their aggregated (pair, delta) records with ONE all-gather on the compute stream and every rank adds all

@@ -37,6 +37,7 @@
 #include "yabpe_minhash_kernels.h"
 #include "yabpe_cluster_kernels.h"
 #include "yabpe_dup_kernels.h"
+#include "yabpe_rep_kernels.h"
 #include "yabpe_span_kernels.h"
 #include "yabpe_fim_kernels.h"
 #include "yabpe_chat_kernels.h"
@@ -266,6 +267,10 @@ struct yabpe_ctx {
     void *dup_buf[4] = {};
     yabpe_dup_stats_t dup_stats{};
     hipEvent_t dup_ev[5] = {};
+    // repetition signals: the results of the last yabpe_repetition (top, distinct, covered, each u32[n_docs][n_ngrams])
+    uint32_t *rep_buf[3] = {};
+    yabpe_repetition_stats_t rep_stats{};
+    hipEvent_t rep_ev[4] = {};
     // resumed load (yabpe_load_words_resumed)
     yabpe_resume_stats_t resume_stats{};
     // persistent word pool (yabpe_pool_add / yabpe_pool_get): arena, off / count / hash, slots (pool_logic.h)
@@ -1967,6 +1972,9 @@ void yabpe_destroy(yabpe_ctx *c) {
         if (e) (void)hipEventDestroy(e);
     yabpe_dup_spans_free(c);
     for (auto &e : c->dup_ev)
+        if (e) (void)hipEventDestroy(e);
+    yabpe_repetition_free(c);
+    for (auto &e : c->rep_ev)
         if (e) (void)hipEventDestroy(e);
     yabpe_pool_clear(c);
     for (auto &e : c->wpool_ev)
@@ -6114,6 +6122,149 @@ int yabpe_dup_spans(yabpe_ctx *c, const uint32_t *ids, uint64_t n_ids, const uin
 int yabpe_dup_spans_stats(yabpe_ctx *c, yabpe_dup_stats_t *out) {
     if (!c || !out) return YABPE_E_INVALID;
     *out = c->dup_stats;
+    return YABPE_OK;
+}
+
+// ---------------------------------------------------------------------------------------------- repetition signals
+int yabpe_repetition_free(yabpe_ctx *c) {
+    if (!c) return YABPE_E_INVALID;
+    for (auto &p : c->rep_buf) {
+        dfree(p);
+        p = nullptr;
+    }
+    return YABPE_OK;
+}
+
+// BBPETokenizer.repetition_stats on the device (yabpe_rep_kernels.h; the rule: rep_logic.h).  rep_ev[0..3] bracket the plan
+// (counts, three scans), the short form (one launch for every length) and the long form (per length: the table preset, the
+// insert, the mark).  Which document takes which form, the window counts, the table size and every grid come from the
+// validated starts on the host: known before a kernel runs.  A call that the checks refuse has freed nothing.
+int yabpe_repetition(yabpe_ctx *c, const uint32_t *ids, uint64_t n_ids, const uint64_t *doc_off, uint32_t n_docs, const yabpe_repetition_t *rule,
+                     uint32_t **out_dev_top, uint32_t **out_dev_distinct, uint32_t **out_dev_covered) {
+    if (!c || !out_dev_top || !out_dev_distinct || !out_dev_covered) return YABPE_E_INVALID;
+    HIPCHK(c, hipSetDevice(c->device));
+    *out_dev_top = nullptr; *out_dev_distinct = nullptr; *out_dev_covered = nullptr;
+    if (!rule) return fail(c, YABPE_E_INVALID, "rule is NULL");
+    if (!rep_rule_valid(rule->n_ngrams, rule->ngram, rule->flags))
+        return fail(c, YABPE_E_INVALID, "n_ngrams %u, flags 0x%x: 1 .. %u lengths, each in [1, %u], strictly ascending; flags 0", rule->n_ngrams, rule->flags,
+                    REP_MAX_NGRAMS, REP_MAX_LEN);
+    if (n_ids > DUP_MAX_IDS) return fail(c, YABPE_E_CAPACITY, "%llu ids: at most 2^30 in one call", (unsigned long long)n_ids);
+    if (n_ids && !ids) return fail(c, YABPE_E_INVALID, "ids is NULL");
+    if (!doc_off && n_docs > 1) return fail(c, YABPE_E_INVALID, "doc_off is NULL with %u documents", n_docs);
+    const int64_t doc_max = optv(c, "rep_doc_max", 0);
+    if (!rep_doc_max_valid(doc_max)) return fail(c, YABPE_E_INVALID, "option rep_doc_max is %lld: 0, or 1 .. %u", (long long)doc_max, REP_DOC);
+    const bool docs_dev = doc_off && is_device_ptr(doc_off);
+    if (!doc_off) n_docs = n_docs || n_ids ? 1 : 0;
+    std::vector<uint64_t> h_docs(n_docs, 0);
+    if (doc_off && n_docs) {
+        if (docs_dev) HIPCHK(c, hipMemcpy(h_docs.data(), doc_off, (size_t)n_docs * 8, hipMemcpyDeviceToHost));
+        else memcpy(h_docs.data(), doc_off, (size_t)n_docs * 8);
+    }
+    if (n_docs || n_ids) TRY(check_starts(c, h_docs.data(), n_docs, n_ids, "ids"));
+    const uint32_t K = rule->n_ngrams, boundary = rep_boundary(doc_max);
+    unsigned long long n_short = 0, n_short_wg = 0, n_long = 0, n_pieces = 0, n_tiles = 0, long_windows[REP_MAX_NGRAMS] = {}, n_long_windows = 0;
+    for (uint32_t d = 0; d < n_docs; ++d) {
+        const unsigned long long L = (d + 1 < n_docs ? h_docs[d + 1] : n_ids) - h_docs[d];
+        if (!rep_is_long(L, boundary)) {
+            ++n_short;
+            n_short_wg += L ? 1 : 0;
+            continue;
+        }
+        ++n_long;
+        n_pieces += dup_tiles(dup_windows(L, rule->ngram[0]));
+        n_tiles += dup_tiles(L);
+        for (uint32_t k = 0; k < K; ++k) long_windows[k] += dup_windows(L, rule->ngram[k]);
+    }
+    for (uint32_t k = 0; k < K; ++k) n_long_windows += long_windows[k];
+    const int64_t forced = optv(c, "rep_slots_log2", 0);  // (the smallest length has the most windows: ascending lengths)
+    if (forced < 0 || forced > DUP_MAX_SLOTS_LOG2 || (forced && n_long && (1ull << forced) < long_windows[0] + 1))
+        return fail(c, YABPE_E_INVALID, "option rep_slots_log2 is %lld: 0, or at most %u with 2^it >= windows + 1 = %llu", (long long)forced,
+                    DUP_MAX_SLOTS_LOG2, long_windows[0] + 1);
+    const uint32_t slots_log2 = forced ? (uint32_t)forced : dup_slots_log2(long_windows[0]);
+    const unsigned long long n_slots = n_long ? 1ull << slots_log2 : 0ull;
+    yabpe_repetition_free(c);
+    auto &st = c->rep_stats;
+    st = yabpe_repetition_stats_t{};
+    st.n_ids = n_ids;
+    st.n_docs = n_docs;
+    st.n_ngrams = K;
+    st.n_short_docs = n_short;
+    st.n_long_docs = n_long;
+    st.n_long_windows = n_long_windows;
+    st.n_slots = n_slots;
+    if (!n_docs) return YABPE_OK;
+    for (auto &e : c->rep_ev)
+        if (!e) HIPCHK(c, hipEventCreate(&e));
+    hipStream_t s = c->stream;
+    Scratch S(c->device, c->rank);
+    RepParams P{};
+    unsigned long long *short_off = nullptr, *piece_off = nullptr, *tile_off = nullptr;
+    TRY(to_device(c, S, ids, n_ids * 4, 4, &P.ids));
+    TRY(to_device(c, S, docs_dev ? (const unsigned long long *)doc_off : (const unsigned long long *)h_docs.data(), (uint64_t)n_docs * 8, 8, &P.doc_off));
+    HIPCHK(c, S.get(&P.shorts, n_docs));
+    HIPCHK(c, S.get(&P.pieces, n_docs));
+    HIPCHK(c, S.get(&P.tiles, n_docs));
+    HIPCHK(c, S.get(&short_off, (uint64_t)n_docs + 1));
+    HIPCHK(c, S.get(&piece_off, (uint64_t)n_docs + 1));
+    HIPCHK(c, S.get(&tile_off, (uint64_t)n_docs + 1));
+    if (n_long) {
+        HIPCHK(c, S.get(&P.table, n_slots));
+        HIPCHK(c, S.get(&P.count, n_slots));
+        HIPCHK(c, S.get(&P.slot_of, n_ids));
+    }
+    for (auto &p : c->rep_buf) TRY(dmalloc(c, &p, (uint64_t)n_docs * K));
+    P.n_ids = (uint32_t)n_ids;
+    P.n_docs = n_docs;
+    P.n_ngrams = K;
+    P.boundary = boundary;
+    for (uint32_t k = 0; k < K; ++k) {
+        P.ngram[k] = rule->ngram[k];
+        P.pow_n[k] = dup_pow(DUP_B, rule->ngram[k]);
+    }
+    P.slots_log2 = slots_log2;
+    P.short_off = short_off;
+    P.piece_off = piece_off;
+    P.tile_off = tile_off;
+    P.top = c->rep_buf[0];
+    P.distinct = c->rep_buf[1];
+    P.covered = c->rep_buf[2];
+    auto hip_fail = [&](const char *what, hipError_t e) {
+        yabpe_repetition_free(c);
+        return fail(c, YABPE_E_HIP, "repetition: %s failed: %s", what, hipGetErrorString(e));
+    };
+    HIPCHK(c, hipEventRecord(c->rep_ev[0], s));
+    hipLaunchKernelGGL(k_rep_plan, dim3(cdiv64(n_docs, BLOCK)), dim3(BLOCK), 0, s, P);
+    if (exclusive_scan<uint32_t>(s, P.shorts, n_docs, short_off, (unsigned long long)n_docs + 1) != 0 ||
+        exclusive_scan<uint32_t>(s, P.pieces, n_docs, piece_off, (unsigned long long)n_docs + 1) != 0 ||
+        exclusive_scan<uint32_t>(s, P.tiles, n_docs, tile_off, (unsigned long long)n_docs + 1) != 0)
+        return hip_fail("the scan of the counts", hipGetLastError());
+    (void)hipEventRecord(c->rep_ev[1], s);
+    if (n_short_wg) hipLaunchKernelGGL(k_rep_short, dim3((uint32_t)n_short_wg), dim3(BLOCK), 0, s, P);
+    (void)hipEventRecord(c->rep_ev[2], s);
+    for (uint32_t k = 0; k < K && long_windows[k]; ++k) {  // (ascending lengths: no windows from the first length without any)
+        P.k = k;
+        if (fill_u32(c, P.table, n_slots, REP_EMPTY) != 0 || fill_u32(c, P.count, n_slots, 0) != 0) return hip_fail("the table preset", hipGetLastError());
+        hipLaunchKernelGGL(k_rep_insert, dim3((uint32_t)n_pieces), dim3(BLOCK), 0, s, P);
+        hipLaunchKernelGGL(k_rep_mark, dim3((uint32_t)n_tiles), dim3(BLOCK), 0, s, P);
+    }
+    const hipError_t le = hipGetLastError();
+    (void)hipEventRecord(c->rep_ev[3], s);
+    const hipError_t se = hipStreamSynchronize(s);
+    if (le != hipSuccess || se != hipSuccess) return hip_fail("a kernel", le != hipSuccess ? le : se);
+    float ms[3] = {0, 0, 0};
+    st.total_ms = pass_times(c->rep_ev, 3, ms);
+    st.plan_ms = ms[0];
+    st.short_ms = ms[1];
+    st.long_ms = ms[2];
+    *out_dev_top = P.top;
+    *out_dev_distinct = P.distinct;
+    *out_dev_covered = P.covered;
+    return YABPE_OK;
+}
+
+int yabpe_repetition_stats(yabpe_ctx *c, yabpe_repetition_stats_t *out) {
+    if (!c || !out) return YABPE_E_INVALID;
+    *out = c->rep_stats;
     return YABPE_OK;
 }
 

@@ -164,6 +164,20 @@ class DupStats(ctypes.Structure):
 DUP_COMPACT = 1  # yabpe_dup_spans: flags
 
 
+class Repetition(ctypes.Structure):
+    """yabpe_repetition_t"""
+    _fields_ = [("n_ngrams", c_uint32), ("ngram", c_uint32 * 16), ("flags", c_uint32)]
+
+
+class RepetitionStats(ctypes.Structure):
+    _fields_ = [(n, c_uint64) for n in ("n_ids", "n_docs", "n_ngrams", "n_short_docs", "n_long_docs", "n_long_windows", "n_slots")] + [
+        (n, c_double) for n in ("plan_ms", "short_ms", "long_ms", "total_ms")]
+
+
+REP_DOC = 2048  # csrc/rep_logic.h: a document of more ids takes the long form of yabpe_repetition
+DUP_TILE = 1024  # csrc/dup_logic.h: window positions of one piece of the long form
+
+
 class Layout(ctypes.Structure):
     """yabpe_layout_t"""
     _fields_ = [(n, c_uint32) for n in ("row_len", "pad_id", "bos_id", "eos_id", "flags")]
@@ -251,6 +265,7 @@ SYMBOLS = [
     "yabpe_minhash", "yabpe_minhash_free", "yabpe_minhash_stats",
     "yabpe_minhash_cluster", "yabpe_minhash_cluster_free", "yabpe_minhash_cluster_stats",
     "yabpe_dup_spans", "yabpe_dup_spans_free", "yabpe_dup_spans_stats",
+    "yabpe_repetition", "yabpe_repetition_free", "yabpe_repetition_stats",
     "yabpe_pool_add", "yabpe_pool_get", "yabpe_pool_clear", "yabpe_pool_stats",
     "yabpe_normalize", "yabpe_normalize_free", "yabpe_normalize_stats",
     "yabpe_utf8_repair", "yabpe_utf8_repair_free", "yabpe_utf8_repair_stats",
@@ -358,6 +373,10 @@ def lib() -> ctypes.CDLL:
                                       POINTER(c_void_p), POINTER(c_uint64), POINTER(c_void_p)]
         L.yabpe_dup_spans_free.argtypes = [c_void_p]
         L.yabpe_dup_spans_stats.argtypes = [c_void_p, POINTER(DupStats)]
+        L.yabpe_repetition.argtypes = [c_void_p, c_void_p, c_uint64, c_void_p, c_uint32, POINTER(Repetition), POINTER(c_void_p), POINTER(c_void_p),
+                                       POINTER(c_void_p)]
+        L.yabpe_repetition_free.argtypes = [c_void_p]
+        L.yabpe_repetition_stats.argtypes = [c_void_p, POINTER(RepetitionStats)]
         L.yabpe_pool_add.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_uint64]
         L.yabpe_pool_get.argtypes = [c_void_p, POINTER(c_void_p), POINTER(c_void_p), POINTER(c_void_p), POINTER(c_uint64), POINTER(c_uint64)]
         L.yabpe_pool_clear.argtypes = [c_void_p]
@@ -1461,6 +1480,45 @@ class Context:
     def dup_spans_stats(self) -> dict:
         s = DupStats()
         self._chk(lib().yabpe_dup_spans_stats(self._h, byref(s)))
+        return _stats_dict(s)
+
+    # -- repetition signals (BBPETokenizer.repetition_stats on the device)
+    def repetition(self, ids, n_ids: int | None = None, doc_starts=None, n_docs: int | None = None, *, ngrams=(2, 3, 4, 5, 6, 7, 8, 9, 10),
+                   flags: int = 0):
+        """Per document and n-gram length the largest class of equal windows, the number of classes and the ids inside repeated
+        windows (yabpe_repetition).  ids / doc_starts as dup_spans takes them (device pointers with n_ids / n_docs, or host
+        arrays; encode()'s results go straight in).  -> (dev_top_ptr, dev_distinct_ptr, dev_covered_ptr, each u32[n_docs,
+        len(ngrams)] or 0 without documents, n_docs); the buffers live until the next repetition, repetition_free() or close().
+        ngrams and flags are passed as they are: the library checks them."""
+        keep = docs = None
+        if isinstance(ids, int):
+            ptr, n = c_void_p(ids), int(n_ids)
+        else:
+            keep = np.ascontiguousarray(ids, dtype=np.uint32)
+            ptr, n = c_void_p(keep.ctypes.data if keep.size else 0), int(keep.size)
+        if isinstance(doc_starts, int):
+            dptr, nd = c_void_p(doc_starts), int(n_docs)
+        else:
+            docs = np.ascontiguousarray([] if doc_starts is None else doc_starts, dtype=np.uint64)  # (no starts: no documents)
+            dptr, nd = c_void_p(docs.ctypes.data), len(docs)
+        ngrams = [int(g) for g in ngrams]
+        rule = Repetition(len(ngrams), (c_uint32 * 16)(*[g & 0xFFFFFFFF for g in ngrams[:16]]), int(flags))
+        dt, dc, dv = c_void_p(), c_void_p(), c_void_p()
+        self._chk(lib().yabpe_repetition(self._h, ptr, n, dptr, nd, byref(rule), byref(dt), byref(dc), byref(dv)))
+        return dt.value or 0, dc.value or 0, dv.value or 0, nd
+
+    def repetition_to_host(self, ids, n_ids: int | None = None, doc_starts=None, n_docs: int | None = None, *, ngrams=(2, 3, 4, 5, 6, 7, 8, 9, 10)):
+        """-> (top, distinct, covered), each u32[n_docs, len(ngrams)], copied to the host."""
+        ptrs = self.repetition(ids, n_ids, doc_starts, n_docs, ngrams=ngrams)
+        nd, k = ptrs[3], len(ngrams)
+        return tuple(self.d2h(p, 4 * nd * k, np.uint32).reshape(nd, k) if nd else np.zeros((0, k), np.uint32) for p in ptrs[:3])
+
+    def repetition_free(self) -> None:
+        self._chk(lib().yabpe_repetition_free(self._h))
+
+    def repetition_stats(self) -> dict:
+        s = RepetitionStats()
+        self._chk(lib().yabpe_repetition_stats(self._h, byref(s)))
         return _stats_dict(s)
 
     # -- the persistent word pool (corpora larger than device memory: words go in call by call, the merge loop loads the pool)

@@ -22,10 +22,14 @@ encode_array_minhash compute the same on the GPU (yabpe_minhash).  minhash_clust
 and band keys into the cluster of every document (LSH buckets, verification against the bucket's smallest document, union-find);
 minhash_clusters_array / encode_array_clusters compute the same on the GPU (yabpe_minhash_cluster).  duplicate_spans /
 remove_duplicate_spans / encode_batch_dedup mark and remove every run of min_len ids that occurs again (exact-substring
-deduplication); duplicate_spans_array / encode_array_dedup compute the same on the GPU (yabpe_dup_spans).
+deduplication); duplicate_spans_array / encode_array_dedup compute the same on the GPU (yabpe_dup_spans).  repetition_stats /
+encode_batch_repetition give every document the signals of the Gopher repetition filters over its ids (the largest class of
+equal n-grams, the number of classes, the ids inside repeated n-grams); repetition_array / encode_array_repetition compute the
+same on the GPU (yabpe_repetition), and repetition_keep turns them into a keep mask on the host.
 """
 from __future__ import annotations
 
+import collections
 import itertools
 import json
 import numbers
@@ -1602,6 +1606,82 @@ class BBPETokenizer:
         min_len = self._dup_len(min_len)  # (refused before any work)
         return self.remove_duplicate_spans(self.encode_batch(texts), min_len=min_len)
 
+    # ------------------------------------------------------------------ repetition signals (per-document n-gram repeat statistics)
+    REP_NGRAMS = (2, 3, 4, 5, 6, 7, 8, 9, 10)
+    REP_MAX_NGRAMS, REP_MAX_LEN = 16, 64  # REP_MAX_NGRAMS, REP_MAX_LEN of csrc/rep_logic.h
+
+    @classmethod
+    def _rep_ngrams(cls, ngrams) -> tuple:
+        """-> the lengths, validated as yabpe_repetition validates them"""
+        try:
+            ngrams = tuple(operator.index(g) for g in ngrams)
+        except TypeError:
+            raise ValueError(f"ngrams must be integers, not {ngrams!r}") from None
+        if not 1 <= len(ngrams) <= cls.REP_MAX_NGRAMS or any(not 1 <= g <= cls.REP_MAX_LEN for g in ngrams) or \
+                any(b <= a for a, b in zip(ngrams, ngrams[1:])):
+            raise ValueError(f"ngrams {ngrams}: 1 to {cls.REP_MAX_NGRAMS} lengths in [1, {cls.REP_MAX_LEN}], strictly ascending")
+        return ngrams
+
+    def repetition_stats(self, ids_batch, *, ngrams=REP_NGRAMS):
+        """The signals of the Gopher repetition filters (Rae et al. 2021, table A1) over token ids -> (top, distinct, covered):
+        nested lists [document][length].  For a document of L ids and a length n, integers throughout:
+          window    n consecutive ids of the document: L - n + 1 of them, none when L < n.  Windows never cross a document
+                    seam, and equal windows of two different documents never meet.
+          count(w)  the windows of the document that hold the same n ids as w; overlapping ones count (a run of one id of
+                    length L has one class of L - n + 1 windows).
+          top       the largest count: 0 without windows, 1 when nothing repeats.
+          distinct  the number of classes of equal windows (n = 1: the unique ids).
+          covered   the ids inside at least one window with count >= 2, every id once (the paper's "not counting overlapping
+                    n-grams twice").
+        ngrams: 1 to 16 lengths in [1, 64], strictly ascending; else, or with more than 2^30 ids: ValueError."""
+        ngrams = self._rep_ngrams(ngrams)
+        docs = [[int(t) for t in ids] for ids in ids_batch]
+        if sum(len(ids) for ids in docs) > self.DUP_MAX_IDS:
+            raise ValueError("at most 2^30 ids in one call")
+        top, distinct, covered = [], [], []
+        for ids in docs:
+            row = []
+            for n in ngrams:
+                windows = [tuple(ids[p:p + n]) for p in range(len(ids) - n + 1)]
+                count = collections.Counter(windows)
+                inside = [0] * len(ids)
+                for p, w in enumerate(windows):
+                    if count[w] >= 2:
+                        inside[p:p + n] = [1] * n
+                row.append((max(count.values(), default=0), len(count), sum(inside)))
+            top.append([r[0] for r in row])
+            distinct.append([r[1] for r in row])
+            covered.append([r[2] for r in row])
+        return top, distinct, covered
+
+    def encode_batch_repetition(self, texts: Sequence[str], ngrams=REP_NGRAMS):
+        """encode_batch(texts), then repetition_stats over the ids -> (ids per document, top, distinct, covered)."""
+        ngrams = self._rep_ngrams(ngrams)  # (refused before any work)
+        ids_batch = self.encode_batch(texts)
+        return (ids_batch,) + self.repetition_stats(ids_batch, ngrams=ngrams)
+
+    @staticmethod
+    def repetition_keep(lengths, top, covered, ngrams, *, top_max={2: .20, 3: .18, 4: .16},
+                        dup_max={5: .15, 6: .14, 7: .13, 8: .12, 9: .11, 10: .10}) -> np.ndarray:
+        """The repetition filters over what repetition_stats / repetition_array return -> keep bool[n_docs].  lengths: the
+        documents' id counts; top and covered: [n_docs][len(ngrams)].  With L the length of a document, it fails when
+          for a length n in top_max   top >= 2 and top * n / L > top_max[n]   (the share taken by the most frequent n-gram), or
+          for a length n in dup_max   covered / L > dup_max[n]                (the share inside repeated n-grams).
+        Empty documents are kept; lengths absent from ngrams are skipped.  The defaults are the paper's bounds, which were set
+        for words and characters, while these signals run over token ids: a starting point, not a calibrated filter."""
+        ngrams = [int(g) for g in ngrams]
+        L = np.asarray(lengths, dtype=np.float64).reshape(-1)
+        top = np.asarray(top, dtype=np.float64).reshape(len(L), len(ngrams))
+        covered = np.asarray(covered, dtype=np.float64).reshape(len(L), len(ngrams))
+        safe = np.maximum(L, 1.0)  # (an empty document has top = covered = 0: it fails nothing)
+        keep = np.ones(len(L), dtype=bool)
+        for k, n in enumerate(ngrams):
+            if n in top_max:
+                keep &= ~((top[:, k] >= 2) & (top[:, k] * n / safe > top_max[n]))
+            if n in dup_max:
+                keep &= ~(covered[:, k] / safe > dup_max[n])
+        return keep
+
     # ------------------------------------------------------------------ encode on the GPU (yabpe_encode; same ids as encode)
     def _device(self, model: str = "encode"):
         if self._device_ctx is None:
@@ -2069,6 +2149,37 @@ class BBPETokenizer:
         _dm, dn, dk, nk, do, _n, nd = ctx.dup_spans(di, ni, dd, len(inp[1]), min_len=min_len, compact=True)
         kept = ctx.d2h(dk, 4 * nk, np.uint32) if nk else np.zeros(0, np.uint32)
         return kept, ctx.d2h(do, 8 * (nd + 1), np.uint64), ctx.d2h(dn, 8 * nd, np.uint64)
+
+    def repetition_array(self, ids, doc_off, *, ngrams=REP_NGRAMS):
+        """repetition_stats on the GPU (yabpe_repetition), value for value: ids and doc_off as encode_array returns them
+        -> (top, distinct, covered, stats): each result np.uint32[n_docs, len(ngrams)]; stats: n_ids, n_docs, n_ngrams,
+        n_short_docs / n_long_docs (which form took how many documents), n_long_windows, n_slots and the device times."""
+        ngrams = self._rep_ngrams(ngrams)
+        ids = np.ascontiguousarray(ids, dtype=np.uint32)
+        off = np.asarray(doc_off, dtype=np.int64)
+        if off.ndim != 1 or len(off) < 1 or off[0] != 0 or off[-1] != len(ids) or np.any(np.diff(off) < 0):
+            raise ValueError("doc_off must be n_docs + 1 ascending offsets from 0 to len(ids)")
+        if len(ids) > self.DUP_MAX_IDS:
+            raise ValueError("at most 2^30 ids in one call")
+        ctx = self._device()
+        return ctx.repetition_to_host(ids, None, off[:-1].astype(np.uint64), None, ngrams=ngrams) + (ctx.repetition_stats(),)
+
+    def encode_array_repetition(self, texts, ngrams=REP_NGRAMS, *, errors: str = "strict"):
+        """encode_batch_repetition(texts, ngrams), computed on the GPU: yabpe_encode, then yabpe_repetition on its device results
+        (which it leaves as they are) -> (ids np.uint32[n], doc_off np.uint64[n_docs + 1], top, distinct, covered): ids and
+        doc_off as encode_array returns them, the signals as repetition_array's.  `texts` and errors as encode_array takes them."""
+        ngrams = self._rep_ngrams(ngrams)
+        inp = self._device_input(texts)
+        if inp is None:
+            check_errors(errors)
+            return (np.zeros(0, np.uint32), np.zeros(1, np.uint64)) + tuple(np.zeros((0, len(ngrams)), np.uint32) for _ in range(3))
+        ctx = self._device()
+        text, n_bytes, starts = self._device_text(ctx, inp, errors)
+        di, dd, ni = ctx.encode(text, n_bytes, doc_starts=starts)
+        nd = len(inp[1])
+        signals = ctx.repetition_to_host(di, ni, dd, nd, ngrams=ngrams)
+        ids = ctx.d2h(di, 4 * ni, np.uint32) if ni else np.zeros(0, np.uint32)
+        return (ids, ctx.d2h(dd, 8 * (nd + 1), np.uint64)) + signals
 
     def _device_encode_for_layout(self, ctx, inp, dropout=0.0, seed=0, offsets=None):
         """-> (ids pointer, document starts pointer, n_ids, spans): the device results the layout passes read -- yabpe_encode's,
